@@ -53,7 +53,13 @@ def parse():
                     help="skip config.parity_full_length (50 batch-1 forwards against the committed oracle fixture): with it a "
                          "rocprofv3 --stats run of this script averages headline and batch-1 launches together")
     ap.add_argument("--cpu-seconds", type=float, default=45.0, help="budget for the CPU baseline sample")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the final latents of the last timed run as DIR/latents.npy (float32; over 64 MB a fixed "
+                         "seeded subset of whole images), to compare two builds output for output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def cpu_model_string():
@@ -375,7 +381,8 @@ def spawn_ranks(args) -> int:
 
 
 def timed_runs(model, args_like, dev, rank, world, sdist):
-    """W warm-up + K timed sampling runs of one workload; returns (images/s, ms per run, loop seconds, final latents).
+    """W warm-up + K timed sampling runs of one workload; returns (images/s, ms per run, loop seconds, initial latents,
+    guidance, final latents of the last timed run gathered over ranks).
     The timed region is bracketed by a barrier + device synchronisation on both sides, MAX over ranks."""
     from sonicdiffusionbayeslab_amd.deepcache import DeepCacheSDHelper
     from sonicdiffusionbayeslab_amd.registry import schedulers_registry
@@ -402,9 +409,11 @@ def timed_runs(model, args_like, dev, rank, world, sdist):
     neg = ne.repeat(hi - lo, 1, 1).to(dev)
 
     def one_run():
+        # the scheduler's own draws (LCM step noise) from a generator seeded afresh per run: every run, warm-up or timed,
+        # computes the same thing whatever ran before it
         out, secs, _ = model(prompt_embeds=pe, negative_prompt_embeds=neg, latents=lat,
                              num_inference_steps=a.ddim_steps, guidance_scale=guidance,
-                             output_type="latent", collect_x0=False)
+                             generator=torch.Generator().manual_seed(31), output_type="latent", collect_x0=False)
         return sdist.gather_latents(out.images, world, gb), secs
 
     for _ in range(a.warmup):
@@ -429,7 +438,22 @@ def timed_runs(model, args_like, dev, rank, world, sdist):
     assert torch.isfinite(final).all(), "non-finite latents"
     if helper is not None:
         helper.disable()
-    return gb * a.steps / elapsed, 1e3 * elapsed / a.steps, loop_secs, lat, guidance
+    return gb * a.steps / elapsed, 1e3 * elapsed / a.steps, loop_secs, lat, guidance, final
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, final):
+    """--dump-outputs: what the timed call returns (output_type="latent": the final latents, [global batch, 4, S, S]) as
+    out_dir/latents.npy in float32.  Past DUMP_MAX_BYTES a fixed seeded subset of whole images is kept, in batch order."""
+    import numpy as np
+    x = final.detach().float().cpu()
+    keep = DUMP_MAX_BYTES // (x[0].numel() * 4)
+    if x.shape[0] > keep:
+        x = x[torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "latents.npy"), x.numpy())
 
 
 def other_configs(model, args, dev, sdist, sd):
@@ -443,7 +467,7 @@ def other_configs(model, args, dev, sdist, sd):
             ("configs[3] per-GPU share: DeepCache N=3 branch 0, DDIM 50 steps, CFG 7.5, batch 16", "ddim", 50, 16, 3),
             ("configs[4] per-GPU share: LCM 4 steps, no CFG, batch 32", "lcm", 4, 32, 0)):
         a = types.SimpleNamespace(scheduler=sched, ddim_steps=steps, batch=batch, cache_interval=interval, steps=2, warmup=1)
-        ips, ms, loop_secs, _, _ = timed_runs(model, a, dev, 0, 1, sdist)
+        ips, ms, loop_secs, _, _, _ = timed_runs(model, a, dev, 0, 1, sdist)
         out.append({"workload": label, "value": ips, "unit": "images/s", "ms_per_step": ms, "steps": 2, "warmup": 1,
                     "dtype": "bf16", "loop_only_s_per_image": loop_secs / (2 * batch)})
     # configs[4] as BASELINE names it: fp8 MFMA weights (a second weight replica, e4m3 conv / FF / QKV contractions)
@@ -451,7 +475,7 @@ def other_configs(model, args, dev, sdist, sd):
     m8 = StableDiffusionModel(unet_config=model.unet_config, state_dict=dict(sd), source="synthetic(seed=1234)",
                               weight_dtype="fp8").to(dev)
     a = types.SimpleNamespace(scheduler="lcm", ddim_steps=4, batch=32, cache_interval=0, steps=2, warmup=1)
-    ips, ms, loop_secs, lat8, _ = timed_runs(m8, a, dev, 0, 1, sdist)
+    ips, ms, loop_secs, lat8, _, _ = timed_runs(m8, a, dev, 0, 1, sdist)
     prof = m8.unet.forward_profiled(lat8, 32, 501.0)
     prof = m8.unet.forward_profiled(lat8, 32, 501.0)
     c8, g8 = prof["conv3x3_fp8"], prof["gemm_fp8"]
@@ -520,7 +544,9 @@ def main():
     B = args.batch
     gb = B * world
     # synthetic inputs, resident in HBM before the timed region; global draw sliced per rank
-    value, ms_per_step, loop_secs, lat, guidance = timed_runs(model, args, dev, rank, world, sdist)
+    value, ms_per_step, loop_secs, lat, guidance, final = timed_runs(model, args, dev, rank, world, sdist)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, final)
     elapsed = ms_per_step * args.steps / 1e3
     is_headline = (args.scheduler == "ddim" and args.ddim_steps == 50 and B == 8 and not args.cache_interval
                    and args.sample_size == 64 and args.dtype == "bf16")
