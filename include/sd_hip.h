@@ -26,7 +26,7 @@ typedef struct sd_unet sd_unet;
 
 /* diffusers UNet2DConditionModel config subset used by SD-1.5 */
 typedef struct sd_unet_config {
-    int sample_size;             /* latent H = W (64 for 512x512) */
+    int sample_size;             /* default latent H = W (64 for 512x512); the _hw entry points take other sizes */
     int in_channels;             /* 4 */
     int out_channels;            /* 4 */
     int num_levels;              /* 4 */
@@ -100,11 +100,21 @@ int sd_unet_set_fp8_scale(sd_unet* u, const char* name, float scale);
  * passed to set_context and to every forward of one sampling run. */
 long long sd_unet_workspace_bytes(sd_unet* u, int unet_batch, int cache_branch_id);
 
+/* Latent height / width per call (additions to ABI 3).  Each entry point without the suffix is its _hw form at
+ * (sample_size, sample_size).  A UNet handle takes sides that are multiples of 2^(num_levels - 1) (8 for SD-1.5) up to
+ * 256; a VAE handle (sd_vae_decode_hw; size its workspace with sd_unet_workspace_bytes_hw, cache_branch_id = -1) takes
+ * sides that are multiples of 8 in [8, 128].  A handle keeps one plan per (batch, branch, variant, latent_h, latent_w):
+ * sizes may alternate on one handle, and a workspace sized for one size serves another only if it is large enough.
+ * set_context prepares the forwards of ONE latent size: call it again (same workspace) after changing the size. */
+long long sd_unet_workspace_bytes_hw(sd_unet* u, int unet_batch, int cache_branch_id, int latent_h, int latent_w);
+
 /* Prompt conditioning: device fp32 [unet_batch, context_len, cross_attention_dim]
  * (`prompt_embeds` after the CFG concat, src/models.py:154-155).  Projects K/V of all
  * cross-attention layers once -- they are step-invariant. */
 int sd_unet_set_context(sd_unet* u, void* stream, const float* encoder_hidden_states, int unet_batch,
                         int cache_branch_id, void* workspace, long long workspace_bytes);
+int sd_unet_set_context_hw(sd_unet* u, void* stream, const float* encoder_hidden_states, int unet_batch,
+                           int cache_branch_id, int latent_h, int latent_w, void* workspace, long long workspace_bytes);
 
 enum { SD_CACHE_OFF = 0, SD_CACHE_FULL_AND_STORE = 1, SD_CACHE_SKIP = 2 };
 
@@ -119,6 +129,10 @@ enum { SD_CACHE_OFF = 0, SD_CACHE_FULL_AND_STORE = 1, SD_CACHE_SKIP = 2 };
 int sd_unet_forward(sd_unet* u, void* stream, const float* latents, int latent_batch, int unet_batch,
                     float timestep, float* eps_out, void* workspace, long long workspace_bytes, int cache_mode,
                     int cache_branch_id);
+/* The same at latent [latent_batch, 4, latent_h, latent_w] (eps_out [unet_batch, 4, latent_h, latent_w]). */
+int sd_unet_forward_hw(sd_unet* u, void* stream, const float* latents, int latent_batch, int unet_batch, int latent_h,
+                       int latent_w, float timestep, float* eps_out, void* workspace, long long workspace_bytes,
+                       int cache_mode, int cache_branch_id);
 
 /* ---- AutoencoderKL decoder: replaces `self.vae.decode(latents / scaling_factor)`
  * (src/models.py:287-302).  `sd_vae` IS the `sd_unet` handle type: parameters are enumerated / loaded /
@@ -130,6 +144,10 @@ typedef struct sd_unet sd_vae;
 int sd_vae_create(const sd_unet_config* cfg, sd_vae** out);
 int sd_vae_decode(sd_vae* v, void* stream, const float* latents, int batch, float latent_scale, float* images_out,
                   void* workspace, long long workspace_bytes);
+/* latents [batch, 4, latent_h, latent_w] -> images [batch, 3, 8 latent_h, 8 latent_w].  Beyond 4096 latent pixels the
+ * mid-block attention runs its query rows in chunks of 2048 with a long-row softmax (scores stay <= 64 MiB). */
+int sd_vae_decode_hw(sd_vae* v, void* stream, const float* latents, int batch, int latent_h, int latent_w, float latent_scale,
+                     float* images_out, void* workspace, long long workspace_bytes);
 
 /* ---- CLIP text encoder: replaces `self.text_encoder(text_input_ids)[0]` inside
  * `encode_prompt` (src/models.py:139-155; transformers CLIPTextModel, quick_gelu, causal mask).  `sd_clip` IS the
@@ -211,6 +229,13 @@ int sd_op_gemm_batched_softmax_ln(void* stream, const void* X, long long ldx, co
  * [Cout][Cin/64][3*3][64] (K runs over 64-channel slice, tap, channel) */
 int sd_op_conv3x3(void* stream, const void* X, const void* W, const float* bias, const float* bias2, const void* R,
                   void* Y, int B, int Hin, int Win, int Cin, int Cout, int stride, int upsample);
+/* Which kernel a 3x3 conv of this shape runs on: 0 = implicit GEMM, 1 = halo kernel (9 taps), 2 = halo kernel's 4-tap
+ * mode.  M = output rows (B Hout Wout; for upsample = 2, the sub-pixel form, 4 B Hin Win); upsample 1 = fused nearest-2x;
+ * dtype 0 = bf16, 1 = fp8 e4m3 (Cin padded to 128).  No device work. */
+int sd_op_conv3x3_kernel(int M, int N, int Cin, int Hin, int Win, int stride, int upsample, int dtype);
+/* In-place softmax(scale * row) of bf16 S [rows, cols], cols a multiple of 8: the VAE mid-block attention's softmax
+ * (one wave per row up to 4096 columns; beyond, a workgroup per row with an online max / sum over the row). */
+int sd_op_softmax_rows(void* stream, void* S, long long rows, int cols, float scale);
 /* Upsample2D (nearest 2x, then 3x3 conv; diffusers resnet.py, the UNet's three upsamplers) as four 2x2 convs on the
  * LOW-RES input -- one per output sub-pixel phase -- with the 3x3 taps that read the same low-res pixel summed: 4/9 of
  * the multiply-adds, the same linear map.  W4 = bf16 [4 phases (py, px)][Cout][Cin/64][4 taps (dy, dx)][64];

@@ -72,11 +72,15 @@ _SIGS = {
     "sd_unet_workspace_bytes": (_ll, [_vp, _i, _i]),
     "sd_unet_set_context": (_i, [_vp, _vp, _vp, _i, _i, _vp, _ll]),
     "sd_unet_forward": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _ll, _i, _i]),
+    "sd_unet_workspace_bytes_hw": (_ll, [_vp, _i, _i, _i, _i]),
+    "sd_unet_set_context_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _ll]),
+    "sd_unet_forward_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _ll, _i, _i]),
     "sd_unet_forward_profiled": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _ll, _i, _i, C.POINTER(C.c_double),
                                       C.POINTER(_ll), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "sd_unet_forward_op_times": (_ll, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _ll, _i, _i, C.c_char_p, _ll]),
     "sd_vae_create": (_i, [C.POINTER(SdUnetConfig), C.POINTER(_vp)]),
     "sd_vae_decode": (_i, [_vp, _vp, _vp, _i, _f, _vp, _vp, _ll]),
+    "sd_vae_decode_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _ll]),
     "sd_clip_create": (_i, [C.POINTER(SdClipConfig), C.POINTER(_vp)]),
     "sd_clip_encode": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _ll]),
     "sd_unet_debug_tensor": (_i, [_vp, _vp, C.c_char_p, _vp, _ll, _vp, _i, _i]),
@@ -91,6 +95,8 @@ _SIGS = {
     "sd_op_groupnorm": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i]),
     "sd_op_conv3x3_groupnorm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _i]),
     "sd_op_conv3x3_splitk": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "sd_op_conv3x3_kernel": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "sd_op_softmax_rows": (_i, [_vp, _vp, _ll, _i, _f]),
     "sd_op_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f]),
     "sd_op_attention": (_i, [_vp, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _i, _i, _i, _i, _i, _f]),
     "sd_op_gemm_qkv_headmajor": (_i, [_vp, _vp, _ll, _vp, _vp, _vp, _i, _i, _i, _i]),

@@ -28,6 +28,8 @@
 
 #include <stdlib.h>
 
+#include <algorithm>
+
 namespace {
 
 constexpr int BM = 256, BN = 160;
@@ -70,10 +72,19 @@ __device__ __forceinline__ int swz_of(int row, int dt) { return dt ? (((row >> 1
 // (2 y + py, 2 x + px).  The halo of a slice is still 7 pieces per wave, now spread 2-2-2-1 over the four taps (56 KiB of halo
 // + 4 x 20 KiB of W per slice against the implicit-GEMM kernel's 4 x (32 + 20) KiB).  Same K order (slice, tap, channel) and
 // the same 16x16x32 accumulation chains as the implicit-GEMM form: bit-identical results.
-template <int DT, int DIAG = 0, int NWV = 8, int SUB = 0>
+//
+// GEN = 1 (geometry mode): output widths that are not a power of two dividing 256, or images whose H * W is not a power of
+// two (the 512x768 / 768x512 / 768x768 UNet levels).  A tile is ONE piece of RW = p.rows_per_batch whole output rows of ONE
+// image (the host picks the largest RW with RW * Wout <= 256 whose halo fits, even with the fused upsample); tiles_m =
+// B * ceil(Hout / RW).  Tile rows beyond RW * Wout and beyond the image's last row are masked: their halo slots read zeros
+// and they store nothing.  The sample / row / column come from divisions done once per item / per thread, not shifts.
+// Same K order and accumulation chains as the power-of-two mode; no GroupNorm block statistics (tiles are not 64-row
+// aligned).  GEN = 0 is the power-of-two kernel unchanged.
+template <int DT, int DIAG = 0, int NWV = 8, int SUB = 0, int GEN = 0>
 __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(const GemmArgs p) {
     static_assert(NWV == 8 || (NWV == 4 && DT == 0), "4-wave layout: bf16 only");
     static_assert(!SUB || (DT == 0 && DIAG == 0 && NWV == 8), "sub-pixel upsampler: bf16, 8 waves");
+    static_assert(!GEN || (SUB == 0 && DIAG == 0 && NWV == 8), "geometry mode: 9 taps, 8 waves");
     constexpr int NTAP = SUB ? 4 : 9;             // taps = K tiles per channel slice
     constexpr int NT = NWV * 64;
     constexpr int WMW = NWV == 8 ? 4 : 2;         // waves along the pixels
@@ -106,10 +117,11 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
     // low-resolution input: (RW / 2 + 2) x (Win + 2) slots, and a tap reads slot ((y + dy - 1) >> 1, ...).
     const int up = SUB ? 0 : p.up;
     const int Ho = SUB ? p.Hin : p.Hout, Wo = SUB ? p.Win : p.Wout, HWo = Ho * Wo;
-    const int RW = min(Ho, BM / Wo);
+    const int RW = GEN ? p.rows_per_batch : min(Ho, BM / Wo);
     const int PW = p.Win + 2, PP = ((RW >> up) + 2) * PW;
     const int PIX = RW * Wo;                     // output pixels per piece
-    const int HP = (BM / PIX) * PP;              // halo slots in use (<= HSLOTS, checked on the host)
+    const int HP = GEN ? PP : (BM / PIX) * PP;   // halo slots in use (<= HSLOTS, checked on the host)
+    const int tpi = GEN ? (Ho + RW - 1) / RW : 1;   // GEN: tiles per image
 
     const char* Xb = (const char*)p.X;
     const char* Wg = (const char*)p.W;
@@ -125,6 +137,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
     const int lgW = __builtin_ctz(Wo), lgHW = __builtin_ctz(HWo);
     const int RWin = RW >> up;                   // input rows under one piece
     int hrel[HPIECES];
+    int hyv[GEN ? HPIECES : 1];                  // GEN: halo row of piece j (row validity is checked per item)
     // The 50 halo pieces do not divide over 8 waves x 7: waves >= 2 re-issue their piece 5 as piece 6 (same source,
     // same LDS destination -- harmless), so that every wave issues the same number of DMAs and the counted
     // vmcnt waits of the K loop are compile-time constants.
@@ -139,6 +152,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
         hrel[j] = ok ? ((((hy - 1) * p.Win + (hx - 1)) * p.Cin * ESZ + ((cpos ^ swz_of(slot, DT)) << 4)) | i |
                         (hy == 0 ? 4 : 0) | (hy == RWin + 1 ? 8 : 0))
                      : HREL_ZERO;
+        if (GEN) hyv[j] = hy;
     }
 
     // W stage pieces: wave w issues pieces w, w + 8 and w + 16; waves 4-7 have no third piece and re-issue w + 8
@@ -146,6 +160,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
 
     // ---- per-item state: tile origin, K range, source offsets -------------------------------------------
     int split = 0, m0 = 0, n0 = 0, s_begin = 0, s_end = 0, phase = 0;
+    int mend = 0;                                // GEN: end of this item's valid output rows
     unsigned hoff[HPIECES];                      // byte offsets into X; NOSRC = zero page
     unsigned woffs[WPW];                         // byte offsets into W
     auto setup = [&](int w) {
@@ -182,6 +197,19 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
         }
         m0 = tile_m * BM;
         n0 = tile_n * BN;
+        if (GEN) {
+            const int b = tile_m / tpi, y0 = (tile_m - b * tpi) * RW;    // sample, first output row
+            m0 = b * HWo + y0 * Wo;
+            mend = m0 + min(RW, Ho - y0) * Wo;
+            const int ybase = y0 >> up;                                  // first input row under the tile
+            const unsigned base = (unsigned)(((long)b * p.Hin + ybase) * p.Win * p.Cin * ESZ);
+#pragma unroll
+            for (int j = 0; j < HPIECES; ++j) {
+                const int iy = ybase - 1 + hyv[j];
+                const bool ok = hrel[j] != HREL_ZERO && iy >= 0 && iy < p.Hin;
+                hoff[j] = ok ? base + (unsigned)(hrel[j] & ~15) : NOSRC;
+            }
+        } else {
 #pragma unroll
         for (int j = 0; j < HPIECES; ++j) {
             const int mp = m0 + (hrel[j] & 3) * PIX;                   // first output pixel of the piece
@@ -191,6 +219,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
                             !((hrel[j] & 8) && ybase + RWin == p.Hin);
             const unsigned base = (unsigned)(((long)b * p.Hin + ybase) * p.Win * p.Cin * ESZ);
             hoff[j] = ok ? base + (unsigned)(hrel[j] & ~15) : NOSRC;
+        }
         }
 #pragma unroll
         for (int i = 0; i < WPW; ++i) {
@@ -245,10 +274,17 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
     int hbase[TM], hrc[TM];                       // this lane's pixels: piece base slot (+1,+1), row << 16 | column
 #pragma unroll
     for (int f = 0; f < TM; ++f) {
+        if (GEN) {               // one piece; tile rows past it re-read its last pixel (masked at the store)
+            const int pt = min(wm * WTM + f * 16 + lrow, PIX - 1);
+            const int row = pt / Wo;
+            hrc[f] = row << 16 | (pt - row * Wo);
+            hbase[f] = PW + 1;
+        } else {
         const int pt = wm * WTM + f * 16 + lrow;
         const int i = pt / PIX, rem = pt - i * PIX;
         hrc[f] = (rem >> lgW) << 16 | (rem & (Wo - 1));
         hbase[f] = i * PP + PW + 1;
+        }
     }
     const int wfrag = (wn * WTN + lrow) * 128;
     // bf16: k-step 0 reads chunk lq ^ (row & 7), k-step 1 = ^ 64; fp8: chunks 2 lq and 2 lq + 1 (= ^ 16), each ^ f(row)
@@ -475,6 +511,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
         // no ordinary load is outstanding once the next item's LDS-DMA is in flight ----------------------
         // (accumulator layout as gemm_kernel: a lane owns 4 consecutive channels of one pixel per 16x16 tile)
         const int em0 = m0, en0 = n0, esplit = split, ephase = phase;
+        const int elim = GEN ? mend : Mrows;      // rows >= elim are not stored (GEN: tail rows of the tile)
         // row of C that holds tile row m (SUB: low-res pixel (b, y, x) of phase (py, px) -> output pixel (2 y + py, 2 x + px))
         auto crow = [&](int m) -> long {
             if (!SUB) return m;
@@ -498,7 +535,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
                     const int n = min(en0 + wn * WTN + a * 16 + lq * 4, p.N - 4);
 #pragma unroll
                     for (int b = 0; b < TM; ++b) {
-                        const int m = min(em0 + wm * WTM + b * 16 + lrow, Mrows - 1);
+                        const int m = min(em0 + wm * WTM + b * 16 + lrow, elim - 1);
                         rr[a][b] = *(const u32x2*)(p.R + crow(m) * p.ldr + n);
                     }
                 }
@@ -538,7 +575,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
             for (int j = 0; j < HPIECES; ++j) issue_h(j, s_begin, hb);
             issue_w(s_begin * NTAP, Wb + wst * WBYTES);
             issue_w(s_begin * NTAP + 1, Wb + (wst == 2 ? 0 : wst + 1) * WBYTES);
-            stores_pending = p.splitk == 1 && wide_ok && (em0 + BM <= Mrows) && (en0 + BN <= p.N);
+            stores_pending = p.splitk == 1 && wide_ok && (em0 + BM <= elim) && (en0 + BN <= p.N);
         }
 
         // ---- epilogue, phase B: stores only ----------------------------------------------------------------
@@ -551,13 +588,13 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
 #pragma unroll
                 for (int b = 0; b < TM; ++b) {
                     const int m = em0 + wm * WTM + b * 16 + lrow;
-                    if (m >= p.M) continue;
+                    if (m >= (GEN ? elim : p.M)) continue;
                     *(f32x4*)(slab + (long)m * p.N + n) = acc[a][b];
                 }
             }
         } else {
             // GroupNorm statistics of this tile for the consuming GroupNorm (64-row blocks = this wave's rows)
-            if (p.stats) {
+            if (!GEN && p.stats) {
                 // (SUB: the blocks of a sample are contiguous in the row order (sample, phase, low-res pixel) the consumer
                 // expects of a sub-pixel conv: block = (b * 4 + phase) * HW / 64 + block within the phase)
                 const int r0 = em0 + wm * WTM;
@@ -576,7 +613,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
                     const int m = em0 + wm * WTM + b * 16 + lrow;
                     const f32x4 v = acc[a][b];
                     u32x2 o = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
-                    if (m < Mrows) *(u32x2*)(p.C + crow(m) * p.ldc + n) = o;
+                    if (m < elim) *(u32x2*)(p.C + crow(m) * p.ldc + n) = o;
                 }
             };
 #pragma unroll
@@ -591,7 +628,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
                         const auto s1 = __builtin_amdgcn_permlane16_swap(pack2bf(vx[2], vx[3]), pack2bf(vy[2], vy[3]), false, false);
                         const u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
                         const int col = nb + (lq & 1) * 16 + (lq >> 1) * 8;
-                        if (m < Mrows) *(u32x4*)(p.C + crow(m) * p.ldc + col) = o;
+                        if (m < elim) *(u32x4*)(p.C + crow(m) * p.ldc + col) = o;
                     }
                 } else {
                     store_narrow(a);
@@ -611,10 +648,46 @@ bool halo_enabled() {
 }  // namespace
 
 // The halo kernel takes stride-1 convs (optionally with the fused nearest-2x upsample) whose 256-pixel tiles
-// are whole output rows and whose halo fits the 448 slots: every stride-1 conv of the SD-1.5 UNet.  Strided
+// are whole output rows and whose halo fits the 400 slots: every stride-1 conv of the SD-1.5 UNet at 512x512 (power-of-two
+// geometry; other sizes: the geometry mode, sd_conv_halo_mode).  Strided
 // convs and wide images (the VAE decoder) stay on the implicit-GEMM kernel.  At width 8 a 16-pixel fragment
 // spans two rows and its LDS read is 2-way bank conflicted on a few lanes; it still beats re-staging X.
+static bool pow2_applicable(const GemmArgs& a);
+static int launch_halo_gen(GemmArgs a, hipStream_t stream);
+
 bool sd_conv_halo_applicable(const GemmArgs& a) {
+    return sd_conv_halo_mode(a) != 0;
+}
+
+// Rows per tile of the geometry mode (conv_halo_kernel GEN = 1) for a stride-1 conv with output width W: the largest RW with
+// RW * W <= 256, RW <= H, RW even with the fused upsample, whose halo ((RW >> up) + 2) x (Win + 2) fits the slots; 0 = none.
+static int gen_rows(const GemmArgs& a) {
+    const int H = a.Hin << a.up, W = a.Win << a.up;
+    if (W < 8 || W > BM) return 0;
+    int rw = std::min(H, BM / W);
+    if (a.up) rw &= ~1;
+    while (rw > 0 && ((rw >> a.up) + 2) * (a.Win + 2) > HSLOTS) rw -= a.up ? 2 : 1;
+    return rw;
+}
+
+// 1: the power-of-two kernel, 2: the geometry mode (GEN), 0: neither (implicit GEMM).  The geometry mode takes a conv the
+// power-of-two kernel cannot when its tiles are at least 3/4 full (RW * Wout >= 192 of 256 rows; measured at the 512x768 /
+// 768x512 / 768x768 UNet levels) and no GroupNorm block statistics are asked of it.
+int sd_conv_halo_mode(const GemmArgs& a) {
+    if (!halo_enabled() || a.stride != 1) return 0;
+    const long ldw0 = a.ldw ? a.ldw : a.K;
+    if ((long)a.M * a.Cin * 2 >= (1l << 32) || (long)a.N * ldw0 * 2 >= (1l << 32)) return 0;
+    if (a.dt == 1 && a.Cin % 128) return 0;
+    if (pow2_applicable(a)) return 1;
+    const char* env = getenv("SD_CONV_HALO_GEN");       // per call: tools/bench_resolution.py times both kernels in one process
+    if ((env && atoi(env) == 0) || a.subpix || a.stats) return 0;
+    const int H = a.Hin << a.up, W = a.Win << a.up;
+    if (a.M % (H * W)) return 0;
+    const int rw = gen_rows(a);
+    return rw > 0 && rw * W >= 192 ? 2 : 0;
+}
+
+static bool pow2_applicable(const GemmArgs& a) {
     if (!halo_enabled() || a.stride != 1) return false;
     const int H = a.Hin << a.up, W = a.Win << a.up;          // output = upsampled input size
     if (W < 8 || W > BM || BM % W) return false;
@@ -696,6 +769,7 @@ int sd_launch_conv3x3_halo(const GemmArgs& a0, hipStream_t stream) {
     }
     const int slices = a.Cin / (a.dt ? 128 : 64);
     SD_REQUIRE(a.splitk <= slices, "conv3x3 halo: splitk %d exceeds the %d channel slices", a.splitk, slices);
+    if (!pow2_applicable(a0)) return launch_halo_gen(a, stream);
     static bool attr_set = false;
     if (!attr_set) {
         SD_CHECK_HIP(hipFuncSetAttribute((const void*)conv_halo_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
@@ -735,6 +809,27 @@ int sd_launch_conv3x3_halo(const GemmArgs& a0, hipStream_t stream) {
     if (a.dt) hipLaunchKernelGGL(conv_halo_kernel<1>, dim3(grid), dim3(512), SMEM, stream, a);
     else hipLaunchKernelGGL(conv_halo_kernel<0>, dim3(grid), dim3(512), SMEM, stream, a);
 #endif
+    if (a.splitk > 1 && !a.defer_reduce) sd_launch_splitk_reduce(a, stream);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+static int launch_halo_gen(GemmArgs a, hipStream_t stream) {
+    const int Ho = a.Hin << a.up, Wo = a.Win << a.up, rw = gen_rows(a);
+    SD_REQUIRE(rw > 0 && a.Hout == Ho && a.Wout == Wo && a.M % (Ho * Wo) == 0 && !a.stats && a.tune == 0,
+               "conv3x3 halo (geometry mode): shape %dx%d -> %dx%d not taken", a.Hin, a.Win, Ho, Wo);
+    a.rows_per_batch = rw;                       // (conv_halo_kernel GEN: output rows per tile)
+    a.tiles_m = (a.M / (Ho * Wo)) * ((Ho + rw - 1) / rw);
+    static bool attr_set = false;
+    if (!attr_set) {
+        SD_CHECK_HIP(hipFuncSetAttribute((const void*)conv_halo_kernel<0, 0, 8, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
+        SD_CHECK_HIP(hipFuncSetAttribute((const void*)conv_halo_kernel<1, 0, 8, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
+        attr_set = true;
+    }
+    int grid = a.tiles_m * a.tiles_n * a.splitk;
+    if (grid > 256) grid = 256;
+    if (a.dt) hipLaunchKernelGGL((conv_halo_kernel<1, 0, 8, 0, 1>), dim3(grid), dim3(512), SMEM, stream, a);
+    else hipLaunchKernelGGL((conv_halo_kernel<0, 0, 8, 0, 1>), dim3(grid), dim3(512), SMEM, stream, a);
     if (a.splitk > 1 && !a.defer_reduce) sd_launch_splitk_reduce(a, stream);
     SD_CHECK_HIP(hipGetLastError());
     return 0;

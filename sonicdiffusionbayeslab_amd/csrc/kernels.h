@@ -80,6 +80,7 @@ int sd_launch_gemm_lean(const GemmArgs& a, int epi, int rows, hipStream_t stream
 void sd_launch_splitk_reduce(const GemmArgs& a, hipStream_t stream);   // slab -> C (+bias +bias2 +R)
 // conv_halo.hip: LDS-resident-halo kernel for stride-1 convs on whole-row tiles
 bool sd_conv_halo_applicable(const GemmArgs& a);
+int sd_conv_halo_mode(const GemmArgs& a);   // 1: power-of-two geometry, 2: geometry mode (GEN), 0: implicit GEMM
 int sd_conv3x3_splitk(int M, int N, int Cin, int Hin, int Win, int stride, int up, int dt = 0);
 bool sd_conv_halo_subpix_applicable(const GemmArgs& a);      // the sub-pixel upsampler on the halo kernel's 4-tap mode
 int sd_launch_conv3x3_halo(const GemmArgs& a, hipStream_t stream);
@@ -118,6 +119,7 @@ int sd_launch_groupnorm(const GroupNormArgs& a, hipStream_t stream);
 
 // in-place row softmax of bf16 scores: p = softmax(scale * s) over `cols` (multiple of 8)
 int sd_launch_softmax_rows(bf16_t* s, long rows, int cols, float scale, hipStream_t stream);
+int sd_launch_softmax_rows_long(bf16_t* s, long rows, int cols, float scale, hipStream_t stream);   // any cols % 8 == 0
 // VAE post_quant_conv: y[b,co,p] = sum_ci W[co,ci] * (x[b,ci,p] * in_scale) + bias[co]  (fp32 NCHW, 4 -> 4)
 int sd_launch_pqconv(const float* x, const float* W, const float* bias, float* y, int B, int HW, float in_scale,
                      hipStream_t stream);

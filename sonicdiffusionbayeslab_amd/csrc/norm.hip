@@ -616,7 +616,61 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(bf16_t* __restrict__ 
     }
 }
 
+// Rows longer than softmax_rows_kernel's 4096 columns (the VAE mid-block attention beyond a 64x64 latent): one 256-thread
+// workgroup per row, two passes over the row in global memory -- an online (max, sum) over 8-column chunks, then the
+// normalised write.  Outside the sampling loop: correctness and bounded registers, not speed.
+__global__ __launch_bounds__(256) void softmax_rows_long_kernel(bf16_t* __restrict__ s, int cols, float scale) {
+    __shared__ float red_m[4], red_s[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    bf16_t* r = s + (long)blockIdx.x * cols;
+    const int nchunks = cols >> 3;
+    const float c = scale * 1.4426950408889634f;           // exp(scale x) = exp2(c x)
+    float mx = -1e30f, sum = 0.f;                           // running max of x and sum of exp2(c (x - mx))
+    for (int ch = tid; ch < nchunks; ch += 256) {
+        const u32x4 v = *(const u32x4*)(r + (long)ch * 8);
+        float f[8] = {bflo(v[0]), bfhi(v[0]), bflo(v[1]), bfhi(v[1]), bflo(v[2]), bfhi(v[2]), bflo(v[3]), bfhi(v[3])};
+        float m = mx;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) m = fmaxf(m, f[j]);
+        sum *= __builtin_amdgcn_exp2f((mx - m) * c);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sum += __builtin_amdgcn_exp2f((f[j] - m) * c);
+        mx = m;
+    }
+    // combine (max, sum) pairs: first across the wave, then across the four waves
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(mx, o), os = __shfl_xor(sum, o);
+        const float m = fmaxf(mx, om);
+        sum = sum * __builtin_amdgcn_exp2f((mx - m) * c) + os * __builtin_amdgcn_exp2f((om - m) * c);
+        mx = m;
+    }
+    if (lane == 0) { red_m[wave] = mx; red_s[wave] = sum; }
+    __syncthreads();
+    float m = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
+    float tot = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) tot += red_s[w] * __builtin_amdgcn_exp2f((red_m[w] - m) * c);
+    const float inv = 1.0f / tot;
+    for (int ch = tid; ch < nchunks; ch += 256) {
+        const u32x4 v = *(const u32x4*)(r + (long)ch * 8);
+        float f[8] = {bflo(v[0]), bfhi(v[0]), bflo(v[1]), bfhi(v[1]), bflo(v[2]), bfhi(v[2]), bflo(v[3]), bfhi(v[3])};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = __builtin_amdgcn_exp2f((f[j] - m) * c) * inv;
+        const u32x4 o = {pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7])};
+        *(u32x4*)(r + (long)ch * 8) = o;
+    }
+}
+
 }  // namespace
+
+int sd_launch_softmax_rows_long(bf16_t* s, long rows, int cols, float scale, hipStream_t stream) {
+    SD_REQUIRE(s && rows > 0 && rows <= 0x7fffffffL, "softmax_rows_long: %ld rows", rows);
+    SD_REQUIRE(cols % 8 == 0 && cols > 0, "softmax_rows_long: cols=%d must be a positive multiple of 8", cols);
+    hipLaunchKernelGGL(softmax_rows_long_kernel, dim3((unsigned)rows), dim3(256), 0, stream, s, cols, scale);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
 
 int sd_launch_softmax_rows(bf16_t* s, long rows, int cols, float scale, hipStream_t stream) {
     SD_REQUIRE(s && rows > 0, "softmax_rows: empty");

@@ -35,6 +35,8 @@ void sd_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* sd_last_error(void) { return g_err; }
+// (the latent-size entry points -- the _hw forms, sd_op_conv3x3_kernel, sd_op_softmax_rows -- are additions under version 3:
+// resolve them by name)
 extern "C" int sd_abi_version(void) { return 3; }   // 2: sd_unet_config.weight_dtype, fp8 entry points; 3: round-2 fusion entry points
 
 static void* g_zero_page = nullptr;
@@ -179,6 +181,7 @@ struct Tn {
 struct Plan {
     int UB = 0, branch = -1;
     int rep = 1;                          // 2: the prompt-independent prefix runs once per latent (CFG pair), see Builder::build
+    int lh = 0, lw = 0;                   // latent height / width the plan is built for
     std::vector<Tn> tensors;
     std::vector<Op> ops;
     std::vector<char> skipped;            // per op: skipped on a DeepCache skip step
@@ -222,8 +225,9 @@ struct sd_unet {
         act_names.push_back(name); act_scale.push_back(dflt); act_amax.push_back(0.f);
         return (int)act_names.size() - 1;
     }
-    std::map<std::tuple<int, int, int>, Plan> plans;     // (UNet batch, DeepCache branch, prefix replication)
+    std::map<std::tuple<int, int, int, int, int>, Plan> plans;   // (UNet batch, DeepCache branch, prefix replication, latent H, W)
     int last_rep = 1;                                    // variant of the last forward (sd_unet_debug_tensor)
+    int last_h = 0, last_w = 0;                          // latent size of the last forward (sd_unet_debug_tensor)
     std::unordered_map<std::string, long> tproj_off;  // resnet prefix -> float index into tproj vector
     long tproj_total = 0;
 };
@@ -1044,31 +1048,36 @@ struct Builder {
         return o.out;
     }
     // fq: x is an e4m3 tensor of pad128(cin) channels written with activation scale xs
-    int conv3(int x, int hin, int cin, int cout, int stride, int up, const std::string& w, const std::string& b,
+    int conv3(int x, int hin, int win, int cin, int cout, int stride, int up, const std::string& w, const std::string& b,
               long b2idx, int b2t, int r, bool fq = false) {
-        Op o; o.kind = OP_CONV3; o.x1 = x; o.B = UB; o.Hin = hin; o.Win = hin; o.Cin = cin; o.N = cout;
+        Op o; o.kind = OP_CONV3; o.x1 = x; o.B = UB; o.Hin = hin; o.Win = win; o.Cin = cin; o.N = cout;
         o.stride = stride; o.up = up;
-        const int hv = hin << up;
-        o.Hout = o.Wout = (hv + 2 - 3) / stride + 1;
+        o.Hout = ((hin << up) + 2 - 3) / stride + 1;
+        o.Wout = ((win << up) + 2 - 3) / stride + 1;
         o.M = UB * o.Hout * o.Wout; o.K = 9 * cin; o.Kalg = o.K;
         o.b = W(b); o.b2t = b2t; o.b2idx = b2idx; o.r = r;
         if (fq) { o.dt = 1; o.Cin = pad128(cin); o.K = 9 * o.Cin; o.w = W(w + ".fp8"); o.wsc = W(w + ".scale"); o.xs = xscale(x); }
         else o.w = W(w);
         // upsampler: nearest-2x + 3x3 as four 2x2 convs on the low-res input, 4/9 of the multiply-adds (SD_CONV_SUBPIXEL=0: off)
         static const bool subpix_off = getenv("SD_CONV_SUBPIXEL") && atoi(getenv("SD_CONV_SUBPIXEL")) == 0;
-        if (up && !fq && !subpix_off && u->kind == 0 && stride == 1 && r < 0 && b2t < 0 && (hin * hin) % 64 == 0 &&
+        if (up && !fq && !subpix_off && u->kind == 0 && stride == 1 && r < 0 && b2t < 0 && (hin * win) % 64 == 0 &&
             u->woff.count(w + ".sub")) {
             o.subpix = 1; o.K = 4 * cin; o.Kalg = 4 * cin;        // (Kalg: the EXECUTED multiply-adds, 4/9 of the 3x3 form)
             o.w = W(w + ".sub"); o.splitk = 1;
             o.out = tensor((size_t)o.M * cout * 2);
-            if ((hin * hin) % 128 == 0) want_stats(o, o.M, cout);     // (8x8 inputs run on 64-row tiles: no block statistics)
+            if ((hin * win) % 128 == 0) want_stats(o, o.M, cout);     // (8x8 inputs run on 64-row tiles: no block statistics)
             push(o);
             return o.out;
         }
-        o.splitk = sd_conv3x3_splitk(o.M, o.N, o.Cin, hin, hin, stride, up, o.dt);
+        o.splitk = sd_conv3x3_splitk(o.M, o.N, o.Cin, hin, win, stride, up, o.dt);
         if (o.splitk > 1) o.aux = tensor((size_t)o.splitk * o.M * o.N * 4);
         o.out = tensor((size_t)o.M * cout * 2);
-        want_stats(o, o.M, cout);         // every 3x3 conv of the UNet feeds a GroupNorm (directly or as a skip)
+        // every 3x3 conv of the UNet feeds a GroupNorm (directly or as a skip); the halo kernel's geometry mode delivers no
+        // block statistics (its tiles are not 64-row aligned): that GroupNorm runs its own statistics pass
+        GemmArgs g;
+        g.M = o.M; g.N = o.N; g.Cin = o.Cin; g.K = o.K; g.ldw = o.K; g.Hin = hin; g.Win = win; g.Hout = o.Hout; g.Wout = o.Wout;
+        g.stride = stride; g.up = up; g.dt = o.dt;
+        if (sd_conv_halo_mode(g) != 2) want_stats(o, o.M, cout);
         push(o);
         return o.out;
     }
@@ -1107,20 +1116,20 @@ struct Builder {
         return o.out;
     }
     // ResnetBlock2D (A.3); input may be a virtual channel concat [x1 | x2]
-    int resnet(const std::string& p, int x1, int c1, int x2, int c2, int cout, int res, int tproj_t) {
-        const int hw = res * res, cin = c1 + c2, M = UB * hw;
+    int resnet(const std::string& p, int x1, int c1, int x2, int c2, int cout, int rh, int rw, int tproj_t) {
+        const int hw = rh * rw, cin = c1 + c2, M = UB * hw;
         const bool fq = u->fp8;          // GroupNorm+SiLU writes e4m3, both 3x3 convs contract in fp8
         int t1 = gn(x1, c1, x2, c2, hw, p + "norm1.weight", p + "norm1.bias", u->cfg.norm_eps, 1, fq);
-        int t2 = conv3(t1, res, cin, cout, 1, 0, p + "conv1.weight", p + "conv1.bias", u->tproj_off.at(p), tproj_t, -1, fq);
+        int t2 = conv3(t1, rh, rw, cin, cout, 1, 0, p + "conv1.weight", p + "conv1.bias", u->tproj_off.at(p), tproj_t, -1, fq);
         int t3 = gn(t2, cout, -1, 0, hw, p + "norm2.weight", p + "norm2.bias", u->cfg.norm_eps, 1, fq);
         int sc = x1;
         if (cin != cout) sc = gemm(x1, c1, x2, c2, M, cout, p + "conv_shortcut.weight", p + "conv_shortcut.bias", -1, 0);
-        return conv3(t3, res, cout, cout, 1, 0, p + "conv2.weight", p + "conv2.bias", 0, -1, sc, fq);
+        return conv3(t3, rh, rw, cout, cout, 1, 0, p + "conv2.weight", p + "conv2.bias", 0, -1, sc, fq);
     }
     // Transformer2DModel with one BasicTransformerBlock (A.4)
     int n_transformers = 0;
-    int transformer(const std::string& p, int x, int C, int res) {
-        const int hw = res * res, L = u->cfg.context_len;
+    int transformer(const std::string& p, int x, int C, int rh, int rw) {
+        const int hw = rh * rw, L = u->cfg.context_len;
         int M = UB * hw;
         const std::string t = p + "transformer_blocks.0.";
         const bool fq = u->fp8;
@@ -1247,22 +1256,25 @@ struct Builder {
     }
 
     // ---- AutoencoderKL decoder: latents/scale -> post_quant_conv -> decoder -> image ----
-    int vae_resnet(const std::string& p, int x, int cin, int cout, int res) {
-        const int hw = res * res, M = UB * hw;
+    int vae_resnet(const std::string& p, int x, int cin, int cout, int rh, int rw) {
+        const int hw = rh * rw, M = UB * hw;
         int t1 = gn(x, cin, -1, 0, hw, p + "norm1.weight", p + "norm1.bias", 1e-6f, 1);
-        int t2 = conv3(t1, res, cin, cout, 1, 0, p + "conv1.weight", p + "conv1.bias", 0, -1, -1);
+        int t2 = conv3(t1, rh, rw, cin, cout, 1, 0, p + "conv1.weight", p + "conv1.bias", 0, -1, -1);
         int t3 = gn(t2, cout, -1, 0, hw, p + "norm2.weight", p + "norm2.bias", 1e-6f, 1);
         int sc = x;
         if (cin != cout) sc = gemm(x, cin, -1, 0, M, cout, p + "conv_shortcut.weight", p + "conv_shortcut.bias", -1, 0);
-        return conv3(t3, res, cout, cout, 1, 0, p + "conv2.weight", p + "conv2.bias", 0, -1, sc);
+        return conv3(t3, rh, rw, cout, cout, 1, 0, p + "conv2.weight", p + "conv2.bias", 0, -1, sc);
     }
     // single-head attention with head dim C (512): too wide for the flash kernel's register tile, so it
-    // is three GEMMs per image (S = Q K^T, row softmax, O = P V with V^T produced directly by a GEMM)
-    int vae_attention(const std::string& p, int x, int C, int res) {
-        const int hw = res * res, M = UB * hw;
+    // is three GEMMs per image (S = Q K^T, row softmax, O = P V with V^T produced directly by a GEMM).
+    // Up to 4096 tokens S holds all query rows of an image; beyond that the query rows go in chunks of
+    // 2048 (S <= 2048 x 16384 bf16 = 64 MiB at a 128x128 latent) and the softmax is the long-row kernel.
+    int vae_attention(const std::string& p, int x, int C, int rh, int rw) {
+        const int hw = rh * rw, M = UB * hw;
+        const int qc = hw <= 4096 ? hw : 2048;      // query rows per S chunk
         int g = gn(x, C, -1, 0, hw, p + "group_norm.weight", p + "group_norm.bias", 1e-6f, 0);
         int qk = gemm(g, C, -1, 0, M, 2 * C, p + "qk.weight", p + "qk.bias", -1, 0);
-        const int vT = tensor((size_t)UB * C * hw * 2), S = tensor((size_t)hw * hw * 2), O = tensor((size_t)M * C * 2);
+        const int vT = tensor((size_t)UB * C * hw * 2), S = tensor((size_t)qc * hw * 2), O = tensor((size_t)M * C * 2);
         for (int img = 0; img < UB; ++img) {
             {   // V^T[C, hw] = Wv[C, C] . g_img[hw, C]^T   (bias of V is added to O: rows of P sum to 1)
                 Op o; o.kind = OP_GEMM; o.wx = W(p + "to_v.weight"); o.ldx_o = C; o.K1 = C; o.K = C; o.M = C; o.N = hw;
@@ -1270,18 +1282,21 @@ struct Builder {
                 o.out = vT; o.coff = (long)img * C * hw; o.ldc_o = hw;
                 push(o);
             }
-            {   // S[hw, hw] = Q_img . K_img^T
-                Op o; o.kind = OP_GEMM; o.x1 = qk; o.xoff = (long)img * hw * 2 * C; o.ldx_o = 2 * C; o.K1 = C; o.K = C;
-                o.M = hw; o.N = hw; o.wt = qk; o.woff_el = (long)img * hw * 2 * C + C; o.ldw_o = 2 * C;
-                o.out = S; o.ldc_o = hw;
-                push(o);
-            }
-            { Op o; o.kind = OP_SOFTMAX; o.x1 = S; o.out = S; o.M = hw; o.N = hw; o.scale = 1.0f / sqrtf((float)C); push(o); }
-            {   // O_img[hw, C] = P . V + b_v
-                Op o; o.kind = OP_GEMM; o.x1 = S; o.ldx_o = hw; o.K1 = hw; o.K = hw; o.M = hw; o.N = C;
-                o.wt = vT; o.woff_el = (long)img * C * hw; o.ldw_o = hw; o.b = W(p + "to_v.bias");
-                o.out = O; o.coff = (long)img * hw * C; o.ldc_o = C;
-                push(o);
+            for (int q0 = 0; q0 < hw; q0 += qc) {
+                const int rows = std::min(qc, hw - q0);
+                {   // S[rows, hw] = Q_img[q0 : q0 + rows] . K_img^T
+                    Op o; o.kind = OP_GEMM; o.x1 = qk; o.xoff = ((long)img * hw + q0) * 2 * C; o.ldx_o = 2 * C; o.K1 = C; o.K = C;
+                    o.M = rows; o.N = hw; o.wt = qk; o.woff_el = (long)img * hw * 2 * C + C; o.ldw_o = 2 * C;
+                    o.out = S; o.ldc_o = hw;
+                    push(o);
+                }
+                { Op o; o.kind = OP_SOFTMAX; o.x1 = S; o.out = S; o.M = rows; o.N = hw; o.scale = 1.0f / sqrtf((float)C); push(o); }
+                {   // O_img[q0 : q0 + rows, C] = P . V + b_v
+                    Op o; o.kind = OP_GEMM; o.x1 = S; o.ldx_o = hw; o.K1 = hw; o.K = hw; o.M = rows; o.N = C;
+                    o.wt = vT; o.woff_el = (long)img * C * hw; o.ldw_o = hw; o.b = W(p + "to_v.bias");
+                    o.out = O; o.coff = ((long)img * hw + q0) * C; o.ldc_o = C;
+                    push(o);
+                }
             }
         }
         return gemm(O, C, -1, 0, M, C, p + "to_out.0.weight", p + "to_out.0.bias", x, 0);
@@ -1289,35 +1304,35 @@ struct Builder {
     void build_vae() {
         const sd_unet_config& c = u->cfg;
         const int nl = c.num_levels, top = c.block_out_channels[nl - 1];
-        int res = c.sample_size;
-        int t_pq = tensor((size_t)UB * c.in_channels * res * res * 4);
-        { Op o; o.kind = OP_PQCONV; o.x1 = T_LATENTS; o.out = t_pq; o.B = UB; o.HW = res * res;
+        int rh = pl.lh, rw = pl.lw;
+        int t_pq = tensor((size_t)UB * c.in_channels * rh * rw * 4);
+        { Op o; o.kind = OP_PQCONV; o.x1 = T_LATENTS; o.out = t_pq; o.B = UB; o.HW = rh * rw;
           o.w = W("post_quant_conv.weight"); o.b = W("post_quant_conv.bias"); push(o); }
         int h;
-        { Op o; o.kind = OP_CONV_IN; o.x1 = t_pq; o.B = UB; o.Hin = res; o.Win = res; o.Cin = c.in_channels; o.N = top;
-          o.w = W("decoder.conv_in.weight"); o.b = W("decoder.conv_in.bias"); o.out = tensor((size_t)UB * res * res * top * 2);
+        { Op o; o.kind = OP_CONV_IN; o.x1 = t_pq; o.B = UB; o.Hin = rh; o.Win = rw; o.Cin = c.in_channels; o.N = top;
+          o.w = W("decoder.conv_in.weight"); o.b = W("decoder.conv_in.bias"); o.out = tensor((size_t)UB * rh * rw * top * 2);
           push(o); h = o.out; }
         pl.taps["conv_in"] = h;
-        h = vae_resnet("decoder.mid_block.resnets.0.", h, top, top, res);
-        h = vae_attention("decoder.mid_block.attentions.0.", h, top, res);
-        h = vae_resnet("decoder.mid_block.resnets.1.", h, top, top, res);
+        h = vae_resnet("decoder.mid_block.resnets.0.", h, top, top, rh, rw);
+        h = vae_attention("decoder.mid_block.attentions.0.", h, top, rh, rw);
+        h = vae_resnet("decoder.mid_block.resnets.1.", h, top, top, rh, rw);
         pl.taps["mid"] = h;
         int ch = top;
         for (int i = 0; i < nl; ++i) {
             const int co = c.block_out_channels[nl - 1 - i];
             const std::string bp = "decoder.up_blocks." + std::to_string(i) + ".";
             for (int j = 0; j < c.layers_per_block + 1; ++j) {
-                h = vae_resnet(bp + "resnets." + std::to_string(j) + ".", h, ch, co, res);
+                h = vae_resnet(bp + "resnets." + std::to_string(j) + ".", h, ch, co, rh, rw);
                 ch = co;
             }
             if (i < nl - 1) {
-                h = conv3(h, res, co, co, 1, 1, bp + "upsamplers.0.conv.weight", bp + "upsamplers.0.conv.bias", 0, -1, -1);
-                res *= 2;
+                h = conv3(h, rh, rw, co, co, 1, 1, bp + "upsamplers.0.conv.weight", bp + "upsamplers.0.conv.bias", 0, -1, -1);
+                rh *= 2; rw *= 2;
             }
             pl.taps["up" + std::to_string(i)] = h;
         }
-        int g = gn(h, ch, -1, 0, res * res, "decoder.conv_norm_out.weight", "decoder.conv_norm_out.bias", 1e-6f, 1);
-        { Op o; o.kind = OP_CONV_OUT; o.x1 = g; o.out = T_EPS; o.B = UB; o.Hin = res; o.Win = res; o.Cin = ch; o.N = c.out_channels;
+        int g = gn(h, ch, -1, 0, rh * rw, "decoder.conv_norm_out.weight", "decoder.conv_norm_out.bias", 1e-6f, 1);
+        { Op o; o.kind = OP_CONV_OUT; o.x1 = g; o.out = T_EPS; o.B = UB; o.Hin = rh; o.Win = rw; o.Cin = ch; o.N = c.out_channels;
           o.w = W("decoder.conv_out.weight"); o.b = W("decoder.conv_out.bias"); push(o); }
     }
 
@@ -1365,12 +1380,12 @@ struct Builder {
         { Op o; o.kind = OP_GEMV; o.x1 = t_h1; o.out = t_emb; o.N = temb; o.K = temb; o.silu_in = 1; o.w = W("time_embedding.linear_2.weight"); o.b = W("time_embedding.linear_2.bias"); push(o); }
         { Op o; o.kind = OP_GEMV; o.x1 = t_emb; o.out = t_proj; o.N = (int)u->tproj_total; o.K = temb; o.silu_in = 1; o.w = W("tproj.weight"); o.b = W("tproj.bias"); push(o); }
         // ---- conv_in ----
-        int res = c.sample_size;
+        int rh = pl.lh, rw = pl.lw;
         int h;
         if (pl.rep > 1) { prefix_rep = pl.rep; UB /= pl.rep; }       // (restored by the first transformer block)
-        { Op o; o.kind = OP_CONV_IN; o.x1 = T_LATENTS; o.B = UB; o.Hin = res; o.Win = res; o.Cin = c.in_channels; o.N = c0;
-          o.w = W("conv_in.weight"); o.b = W("conv_in.bias"); o.out = tensor((size_t)UB * res * res * c0 * 2); push(o); h = o.out; }
-        const int h_skip = prefix_rep > 1 ? replicate(h, (size_t)UB * res * res * c0 * 2, prefix_rep) : h;
+        { Op o; o.kind = OP_CONV_IN; o.x1 = T_LATENTS; o.B = UB; o.Hin = rh; o.Win = rw; o.Cin = c.in_channels; o.N = c0;
+          o.w = W("conv_in.weight"); o.b = W("conv_in.bias"); o.out = tensor((size_t)UB * rh * rw * c0 * 2); push(o); h = o.out; }
+        const int h_skip = prefix_rep > 1 ? replicate(h, (size_t)UB * rh * rw * c0 * 2, prefix_rep) : h;
         pl.taps["conv_in"] = h_skip;
         int ch = c0;
         std::vector<int> skips{h_skip}, skip_ch{c0};
@@ -1381,18 +1396,18 @@ struct Builder {
             wrapstack.push_back(Wrap{0, i, 0});
             for (int j = 0; j < c.layers_per_block; ++j) {
                 wrapstack.push_back(Wrap{0, i, j});
-                h = resnet(bp + "resnets." + std::to_string(j) + ".", h, ch, -1, 0, co, res, t_proj);
+                h = resnet(bp + "resnets." + std::to_string(j) + ".", h, ch, -1, 0, co, rh, rw, t_proj);
                 ch = co;
-                if (c.attn_levels[i]) h = transformer(bp + "attentions." + std::to_string(j) + ".", h, co, res);
+                if (c.attn_levels[i]) h = transformer(bp + "attentions." + std::to_string(j) + ".", h, co, rh, rw);
                 wrapstack.pop_back();
                 skips.push_back(h); skip_ch.push_back(co);
             }
             if (i < nl - 1) {
                 wrapstack.push_back(Wrap{0, i, c.layers_per_block});
                 const std::string d = bp + "downsamplers.0.conv.";
-                h = conv3(h, res, co, co, 2, 0, d + "weight", d + "bias", 0, -1, -1);
+                h = conv3(h, rh, rw, co, co, 2, 0, d + "weight", d + "bias", 0, -1, -1);
                 wrapstack.pop_back();
-                res /= 2;
+                rh /= 2; rw /= 2;
                 skips.push_back(h); skip_ch.push_back(co);
             }
             wrapstack.pop_back();
@@ -1400,9 +1415,9 @@ struct Builder {
         }
         // ---- mid ----
         wrapstack.push_back(Wrap{1, 0, 0});
-        h = resnet("mid_block.resnets.0.", h, ch, -1, 0, ch, res, t_proj);
-        h = transformer("mid_block.attentions.0.", h, ch, res);
-        h = resnet("mid_block.resnets.1.", h, ch, -1, 0, ch, res, t_proj);
+        h = resnet("mid_block.resnets.0.", h, ch, -1, 0, ch, rh, rw, t_proj);
+        h = transformer("mid_block.attentions.0.", h, ch, rh, rw);
+        h = resnet("mid_block.resnets.1.", h, ch, -1, 0, ch, rh, rw, t_proj);
         wrapstack.pop_back();
         pl.taps["mid"] = h;
         // ---- up ----
@@ -1416,24 +1431,24 @@ struct Builder {
                 skips.pop_back(); skip_ch.pop_back();
                 const int rl = nres - 1 - j;
                 wrapstack.push_back(Wrap{2, rb, rl});
-                h = resnet(bp + "resnets." + std::to_string(j) + ".", h, ch, s, sc, co, res, t_proj);
+                h = resnet(bp + "resnets." + std::to_string(j) + ".", h, ch, s, sc, co, rh, rw, t_proj);
                 ch = co;
-                if (c.attn_levels[lev]) h = transformer(bp + "attentions." + std::to_string(j) + ".", h, co, res);
+                if (c.attn_levels[lev]) h = transformer(bp + "attentions." + std::to_string(j) + ".", h, co, rh, rw);
                 wrapstack.pop_back();
             }
             if (i < nl - 1) {
                 wrapstack.push_back(Wrap{2, rb, 0});
                 const std::string up = bp + "upsamplers.0.conv.";
-                h = conv3(h, res, co, co, 1, 1, up + "weight", up + "bias", 0, -1, -1);
+                h = conv3(h, rh, rw, co, co, 1, 1, up + "weight", up + "bias", 0, -1, -1);
                 wrapstack.pop_back();
-                res *= 2;
+                rh *= 2; rw *= 2;
             }
             wrapstack.pop_back();
             pl.taps["up" + std::to_string(i)] = h;
         }
         // ---- out ----
-        int g = gn(h, ch, -1, 0, res * res, "conv_norm_out.weight", "conv_norm_out.bias", c.norm_eps, 1);
-        { Op o; o.kind = OP_CONV_OUT; o.x1 = g; o.out = T_EPS; o.B = UB; o.Hin = res; o.Win = res; o.Cin = ch; o.N = c.out_channels;
+        int g = gn(h, ch, -1, 0, rh * rw, "conv_norm_out.weight", "conv_norm_out.bias", c.norm_eps, 1);
+        { Op o; o.kind = OP_CONV_OUT; o.x1 = g; o.out = T_EPS; o.B = UB; o.Hin = rh; o.Win = rw; o.Cin = ch; o.N = c.out_channels;
           o.w = W("conv_out.weight"); o.b = W("conv_out.bias"); push(o); }
     }
 };
@@ -1567,21 +1582,44 @@ static int plan_rep(const sd_unet* u, int latent_batch, int unet_batch) {
     return (!off && u->kind == 0 && u->cfg.attn_levels[0] && latent_batch > 0 && unet_batch == 2 * latent_batch) ? 2 : 1;
 }
 
-int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep = 1) {
+// Latent sizes a handle takes per call (the _hw entry points).  UNet: both sides divisible by 2^(num_levels - 1), so that
+// every downsampler halves them exactly; VAE decoder: sides that are multiples of 8 (the mid-block attention's token count
+// HW = h * w then stays a multiple of 64) up to 128.  The handle's sample_size is the default and always accepted.
+static int check_latent_size(const sd_unet* u, int lh, int lw, const char* who) {
+    if (u->kind == 1) {
+        SD_REQUIRE(lh >= 8 && lw >= 8 && lh <= 128 && lw <= 128 && lh % 8 == 0 && lw % 8 == 0,
+                   "%s: latent %dx%d (the VAE decoder takes sides that are multiples of 8 in [8, 128])", who, lh, lw);
+    } else if (u->kind == 0) {
+        const int d = 1 << (u->cfg.num_levels - 1);
+        SD_REQUIRE(lh >= d && lw >= d && lh <= 256 && lw <= 256 && lh % d == 0 && lw % d == 0,
+                   "%s: latent %dx%d (both sides must be multiples of %d, at most 256)", who, lh, lw, d);
+    }
+    return 0;
+}
+
+// lh / lw < 0: the handle's sample_size (square)
+int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep = 1, int lh = -1, int lw = -1) {
     SD_REQUIRE(u && u->finalized, "unet: parameters not finalized");
     SD_REQUIRE(UB > 0 && UB <= 4096, "unet: bad batch %d", UB);
     SD_REQUIRE(branch < 3 * u->cfg.num_levels, "unet: cache_branch_id %d out of range", branch);
     if (branch < 0) branch = -1;
-    auto key = std::make_tuple(UB, branch, rep);
+    if (lh < 0) lh = u->cfg.sample_size;
+    if (lw < 0) lw = u->cfg.sample_size;
+    auto key = std::make_tuple(UB, branch, rep, lh, lw);
     auto it = u->plans.find(key);
     if (it == u->plans.end()) {
+        if (lh != u->cfg.sample_size || lw != u->cfg.sample_size)
+            if (check_latent_size(u, lh, lw, "unet")) return -1;
         Plan pl;
         pl.UB = UB;
         pl.branch = branch;
         pl.rep = rep;
+        pl.lh = lh;
+        pl.lw = lw;
         Builder b{u, pl, UB, {}};
         b.build();
-        SD_REQUIRE(b.error.empty(), "unet: cannot build the plan for batch %d (cache branch %d): %s", UB, branch, b.error.c_str());
+        SD_REQUIRE(b.error.empty(), "unet: cannot build the plan for batch %d (cache branch %d, latent %dx%d): %s", UB, branch, lh, lw,
+                   b.error.c_str());
         fuse_deferred_reduce(u, pl);
         assign_memory(u, pl);
         it = u->plans.emplace(key, std::move(pl)).first;
@@ -1608,6 +1646,7 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
             return sd_launch_pqconv(latents, (const float*)(wb + o.w), (const float*)(wb + o.b), (float*)T(o.out), o.B,
                                     o.HW, timestep /* carries the latent scale for the VAE */, stream);
         case OP_SOFTMAX:
+            if (o.N > 4096) return sd_launch_softmax_rows_long((bf16_t*)T(o.x1), o.M, o.N, o.scale, stream);
             return sd_launch_softmax_rows((bf16_t*)T(o.x1), o.M, o.N, o.scale, stream);
         case OP_GN: {
             GroupNormArgs a;
@@ -1755,8 +1794,8 @@ extern "C" int sd_vae_create(const sd_unet_config* cfg, sd_unet** out) {
         SD_REQUIRE(c % 64 == 0 && c % cfg->norm_num_groups == 0 && (cpg >= 8 || cpg == 4),
                    "sd_vae_create: block_out_channels[%d]=%d must be a multiple of 64 with 4 or >= 8 channels per group", i, c);
     }
-    SD_REQUIRE(cfg->sample_size >= 8 && cfg->sample_size <= 64 && (cfg->sample_size * cfg->sample_size) % 64 == 0,
-               "sd_vae_create: latent size %d (the mid-block attention handles 64 <= HW <= 4096 tokens)", cfg->sample_size);
+    SD_REQUIRE(cfg->sample_size >= 8 && cfg->sample_size <= 128 && (cfg->sample_size * cfg->sample_size) % 64 == 0,
+               "sd_vae_create: latent size %d (8 .. 128, HW a multiple of 64)", cfg->sample_size);
     sd_unet* u = new sd_unet();
     u->kind = 1;
     u->cfg = *cfg;
@@ -1769,9 +1808,17 @@ extern "C" int sd_vae_create(const sd_unet_config* cfg, sd_unet** out) {
 extern "C" int sd_vae_decode(sd_unet* u, void* stream, const float* latents, int batch, float latent_scale,
                              float* images_out, void* workspace, long long workspace_bytes) {
     SD_REQUIRE(u && u->kind == 1, "vae_decode: not a VAE handle");
+    return sd_vae_decode_hw(u, stream, latents, batch, u->cfg.sample_size, u->cfg.sample_size, latent_scale, images_out,
+                            workspace, workspace_bytes);
+}
+
+extern "C" int sd_vae_decode_hw(sd_unet* u, void* stream, const float* latents, int batch, int latent_h, int latent_w,
+                                float latent_scale, float* images_out, void* workspace, long long workspace_bytes) {
+    SD_REQUIRE(u && u->kind == 1, "vae_decode: not a VAE handle");
     SD_REQUIRE(latents && images_out && workspace && batch > 0, "vae_decode: null argument");
+    if (check_latent_size(u, latent_h, latent_w, "vae_decode")) return -1;
     Plan* pl;
-    int rc = get_plan(u, batch, -1, &pl);
+    int rc = get_plan(u, batch, -1, &pl, 1, latent_h, latent_w);
     if (rc) return rc;
     SD_REQUIRE((long long)pl->total_bytes <= workspace_bytes, "vae_decode: workspace too small (%lld < %zu)", workspace_bytes,
                pl->total_bytes);
@@ -1893,11 +1940,18 @@ extern "C" long long sd_unet_debug_packed(const sd_unet* u, const char* key, voi
 }
 
 extern "C" long long sd_unet_workspace_bytes(sd_unet* u, int unet_batch, int cache_branch_id) {
+    SD_REQUIRE(u, "workspace_bytes: null handle");
+    return sd_unet_workspace_bytes_hw(u, unet_batch, cache_branch_id, u->cfg.sample_size, u->cfg.sample_size);
+}
+
+extern "C" long long sd_unet_workspace_bytes_hw(sd_unet* u, int unet_batch, int cache_branch_id, int latent_h, int latent_w) {
+    SD_REQUIRE(u, "workspace_bytes: null handle");
+    if (check_latent_size(u, latent_h, latent_w, "workspace_bytes")) return -1;
     Plan* pl;
-    if (get_plan(u, unet_batch, cache_branch_id, &pl)) return -1;
+    if (get_plan(u, unet_batch, cache_branch_id, &pl, 1, latent_h, latent_w)) return -1;
     size_t bytes = pl->total_bytes;
     if (unet_batch % 2 == 0 && plan_rep(u, unet_batch / 2, unet_batch) == 2) {      // the CFG-pair variant of the plan
-        if (get_plan(u, unet_batch, cache_branch_id, &pl, 2)) return -1;
+        if (get_plan(u, unet_batch, cache_branch_id, &pl, 2, latent_h, latent_w)) return -1;
         bytes = std::max(bytes, pl->total_bytes);
     }
     return (long long)bytes;
@@ -1905,9 +1959,20 @@ extern "C" long long sd_unet_workspace_bytes(sd_unet* u, int unet_batch, int cac
 
 extern "C" int sd_unet_set_context(sd_unet* u, void* stream, const float* ehs, int unet_batch, int cache_branch_id,
                                    void* workspace, long long workspace_bytes) {
+    SD_REQUIRE(u, "set_context: null handle");
+    return sd_unet_set_context_hw(u, stream, ehs, unet_batch, cache_branch_id, u->cfg.sample_size, u->cfg.sample_size,
+                                  workspace, workspace_bytes);
+}
+
+// The context tensors of a (batch, branch) sit at the same offsets in every plan variant of ONE latent size: a size change
+// needs its own set_context.
+extern "C" int sd_unet_set_context_hw(sd_unet* u, void* stream, const float* ehs, int unet_batch, int cache_branch_id,
+                                      int latent_h, int latent_w, void* workspace, long long workspace_bytes) {
+    SD_REQUIRE(u && u->kind == 0, "set_context: not a UNet handle");
     SD_REQUIRE(ehs && workspace, "set_context: null argument");
+    if (check_latent_size(u, latent_h, latent_w, "set_context")) return -1;
     Plan* plp;
-    int rc = get_plan(u, unet_batch, cache_branch_id, &plp);
+    int rc = get_plan(u, unet_batch, cache_branch_id, &plp, 1, latent_h, latent_w);
     if (rc) return rc;
     Plan& pl = *plp;
     SD_REQUIRE((long long)pl.total_bytes <= workspace_bytes, "set_context: workspace too small (%lld < %zu)",
@@ -1977,7 +2042,16 @@ extern "C" int sd_unet_forward(sd_unet* u, void* stream, const float* latents, i
                                float timestep, float* eps_out, void* workspace, long long workspace_bytes,
                                int cache_mode, int cache_branch_id) {
     SD_REQUIRE(u && u->kind == 0, "forward: not a UNet handle");
+    return sd_unet_forward_hw(u, stream, latents, latent_batch, unet_batch, u->cfg.sample_size, u->cfg.sample_size, timestep,
+                              eps_out, workspace, workspace_bytes, cache_mode, cache_branch_id);
+}
+
+extern "C" int sd_unet_forward_hw(sd_unet* u, void* stream, const float* latents, int latent_batch, int unet_batch,
+                                  int latent_h, int latent_w, float timestep, float* eps_out, void* workspace,
+                                  long long workspace_bytes, int cache_mode, int cache_branch_id) {
+    SD_REQUIRE(u && u->kind == 0, "forward: not a UNet handle");
     SD_REQUIRE(latents && eps_out && workspace, "forward: null argument");
+    if (check_latent_size(u, latent_h, latent_w, "forward")) return -1;
     SD_REQUIRE(latent_batch > 0 && unet_batch % latent_batch == 0, "forward: unet batch %d not a multiple of latent batch %d",
                unet_batch, latent_batch);
     SD_REQUIRE(cache_mode >= 0 && cache_mode <= 2, "forward: cache_mode %d", cache_mode);
@@ -1985,7 +2059,8 @@ extern "C" int sd_unet_forward(sd_unet* u, void* stream, const float* latents, i
     Plan* pl;
     const int rep = plan_rep(u, latent_batch, unet_batch);
     u->last_rep = rep;
-    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep);
+    u->last_h = latent_h; u->last_w = latent_w;
+    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, latent_h, latent_w);
     if (rc) return rc;
     SD_REQUIRE((long long)pl->total_bytes <= workspace_bytes, "forward: workspace too small (%lld < %zu)", workspace_bytes,
                pl->total_bytes);
@@ -2142,6 +2217,7 @@ static int profiled_run(sd_unet* u, void* stream, const float* latents, int late
     Plan* pl;
     const int rep = plan_rep(u, latent_batch, unet_batch);
     u->last_rep = rep;
+    u->last_h = u->last_w = u->cfg.sample_size;
     int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep);
     if (rc) return rc;
     *plan = pl;
@@ -2238,7 +2314,7 @@ extern "C" int sd_unet_debug_tensor(sd_unet* u, void* stream, const char* name, 
                                     void* workspace, int unet_batch, int cache_branch_id) {
     SD_REQUIRE(u && u->debug_taps, "debug_tensor: create the handle with SD_DEBUG_TAPS=1 in the environment");
     Plan* pl;
-    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, u->last_rep);
+    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, u->last_rep, u->last_h > 0 ? u->last_h : -1, u->last_w > 0 ? u->last_w : -1);
     if (rc) return rc;
     auto it = pl->taps.find(name);
     SD_REQUIRE(it != pl->taps.end(), "debug_tensor: unknown tap '%s'", name);
@@ -2323,6 +2399,29 @@ extern "C" int sd_op_conv3x3(void* stream, const void* X, const void* W, const f
         SD_REQUIRE(a.slab, "sd_op_conv3x3: cannot allocate split-K scratch");
     }
     return sd_launch_conv3x3(a, (hipStream_t)stream);
+}
+
+// Which kernel sd_launch_conv3x3 runs a 3x3 conv of this shape on (the plan and the op entry points use the same predicates).
+extern "C" int sd_op_conv3x3_kernel(int M, int N, int Cin, int Hin, int Win, int stride, int upsample, int dtype) {
+    SD_REQUIRE(M > 0 && N > 0 && Cin > 0 && Hin > 0 && Win > 0 && (stride == 1 || stride == 2) && upsample >= 0 && upsample <= 2 &&
+                   (dtype == 0 || dtype == 1), "conv3x3_kernel: bad arguments");
+    GemmArgs a;
+    a.M = M; a.N = N; a.Cin = Cin; a.Hin = Hin; a.Win = Win; a.stride = stride; a.dt = dtype;
+    if (upsample == 2) {            // the sub-pixel form: four 2x2 convs on the low-res input, M = 4 B Hin Win
+        a.subpix = 1; a.up = 0; a.K = 4 * Cin; a.ldw = a.K; a.Hout = 2 * Hin; a.Wout = 2 * Win;
+        a.w_batch_stride = (long)N * a.K; a.splitk = 1;
+        return sd_conv_halo_subpix_applicable(a) ? 2 : 0;
+    }
+    a.up = upsample; a.K = 9 * Cin; a.ldw = a.K;
+    a.Hout = ((Hin << a.up) + 2 - 3) / stride + 1; a.Wout = ((Win << a.up) + 2 - 3) / stride + 1;
+    return sd_conv_halo_mode(a) != 0 ? 1 : 0;       // (either geometry of the halo kernel)
+}
+
+// In-place row softmax of bf16 S [rows, cols] with scale, as the VAE mid-block attention runs it (<= 4096 columns: one wave
+// per row; beyond: the long-row kernel)
+extern "C" int sd_op_softmax_rows(void* stream, void* S, long long rows, int cols, float scale) {
+    if (cols > 4096) return sd_launch_softmax_rows_long((bf16_t*)S, rows, cols, scale, (hipStream_t)stream);
+    return sd_launch_softmax_rows((bf16_t*)S, rows, cols, scale, (hipStream_t)stream);
 }
 
 // Timing ablations of the halo conv kernel (csrc/conv_halo.hip, template parameter DIAG; WRONG results by design, Y is

@@ -111,6 +111,7 @@ class StableDiffusionModel:
         self._deepcache = None          # set by DeepCacheSDHelper.enable()
         self._lora = []
         self._fp8_calibrated = False    # fp8 handles: per-tensor activation scales, calibrated once on a FIXED seeded batch
+        self._size = None               # (height, width) in pixels of the current call, set by _begin
         self.fp8_scales = {}            # {tensor name: scale} in use (reported by the harness next to the results)
 
     # -- loading ---------------------------------------------------------------------------
@@ -230,6 +231,9 @@ class StableDiffusionModel:
         shape = (batch_size, num_channels, height // self.vae_scale_factor, width // self.vae_scale_factor)
         if latents is None:
             latents = sdist.randn(shape, generator)      # (the global batch's draw, sliced, under a sharded harness call)
+        elif tuple(latents.shape[-2:]) != shape[-2:]:
+            raise ValueError(f"latents {tuple(latents.shape)} do not match height x width = {height}x{width} "
+                             f"(latent {shape[2]}x{shape[3]})")
         latents = latents.to(device, torch.float32)
         return (latents * self.scheduler.init_noise_sigma).contiguous()
 
@@ -240,6 +244,22 @@ class StableDiffusionModel:
         return result, x0_preds
 
     # -- pieces shared by the four pipelines ------------------------------------------------------
+    SIZE_RULE = "height and width must each be a multiple of 64 in [256, 1024]"
+
+    def check_size(self, height: Optional[int], width: Optional[int]):
+        """(height, width) in pixels for a pipeline call.  ``None`` is ``sample_size * 8`` (the default size, always
+        accepted); any other value must follow ``SIZE_RULE``.  Raises ``ValueError`` naming the rule."""
+        default = self.unet_config.sample_size * self.vae_scale_factor
+        out = []
+        for name, v in (("height", height), ("width", width)):
+            if v is None or (isinstance(v, int) and not isinstance(v, bool) and v == default):
+                out.append(default)
+                continue
+            if not isinstance(v, int) or isinstance(v, bool) or v % 64 or not 256 <= v <= 1024:
+                raise ValueError(f"{name}={v!r}: {self.SIZE_RULE}")
+            out.append(v)
+        return out[0], out[1]
+
     def _begin(self, prompt, height, width, guidance_scale, negative_prompt, num_images_per_prompt, prompt_embeds,
                negative_prompt_embeds, guidance_rescale=0.0, timesteps=None, sigmas=None):
         """Steps 0-3 of the reference's ``call`` (``src/models.py:110-160``): argument checks, batch size,
@@ -248,15 +268,12 @@ class StableDiffusionModel:
             raise NotImplementedError("guidance_rescale is never used by the reference (src/models.py:53)")
         if num_images_per_prompt != 1 or timesteps is not None or sigmas is not None:
             raise NotImplementedError("custom timesteps / num_images_per_prompt are outside the reference's use")
+        height, width = self.check_size(height, width)          # before any GPU work
+        self._size = (height, width)
         self._ensure_unet()
         if not self._fp8_calibrated:
             self.calibrate_fp8()        # fp8 handles only; shared by the four pipelines (all enter through _begin)
         device = self.unet.device
-        cfgu = self.unet_config
-        height = height or cfgu.sample_size * self.vae_scale_factor
-        width = width or cfgu.sample_size * self.vae_scale_factor
-        if height != cfgu.sample_size * 8 or width != cfgu.sample_size * 8:
-            raise ValueError("resolution is fixed by the UNet sample_size")
         self._guidance_scale = guidance_scale
         if prompt is not None and isinstance(prompt, str):
             batch_size = 1
@@ -270,9 +287,23 @@ class StableDiffusionModel:
         ctx = torch.cat([negative_prompt_embeds, prompt_embeds]) if do_cfg else prompt_embeds   # :154-155
         return device, batch_size, do_cfg, ctx
 
+    @property
+    def latent_size(self):
+        """(h, w) of the latent of the current call (``_begin`` fixed the pixel size)."""
+        return self._size[0] // self.vae_scale_factor, self._size[1] // self.vae_scale_factor
+
+    def _start_loop(self, batch_size, device, generator, latents, ctx, cache_branch_id):
+        """Initial latents at the call's size, DeepCache branch and prompt context of the UNet."""
+        c = self.unet_config
+        latents = self.prepare_latents(batch_size, c.in_channels, self._size[0], self._size[1], device, generator, latents)
+        self.unet.set_deepcache(cache_branch_id)
+        self.unet.set_context(ctx, *self.latent_size)
+        return latents
+
     def _eps_buffer(self, unet_batch, device):
         c = self.unet_config
-        return torch.empty((unet_batch, c.out_channels, c.sample_size, c.sample_size), dtype=torch.float32, device=device)
+        h, w = self.latent_size
+        return torch.empty((unet_batch, c.out_channels, h, w), dtype=torch.float32, device=device)
 
     def _finish(self, latents, x0_preds, output_type, return_dict, execution_time):
         """``src/models.py:287-335``: decode (outside the timed loop), post-process, 3-tuple."""
@@ -349,12 +380,8 @@ class StableDiffusionModel:
 
         self.scheduler.set_timesteps(num_inference_steps, device=device)                        # :167-169
         ts_host = list(self.scheduler._timesteps_list)
-        latents = self.prepare_latents(batch_size, cfgu.in_channels, cfgu.sample_size * 8, cfgu.sample_size * 8,
-                                       device, generator, latents)
-
         dc = self._deepcache
-        self.unet.set_deepcache(dc.cache_branch_id if dc is not None else -1)
-        self.unet.set_context(ctx)
+        latents = self._start_loop(batch_size, device, generator, latents, ctx, dc.cache_branch_id if dc is not None else -1)
         eps = self._eps_buffer(unet_batch, device)
         self._num_timesteps = len(ts_host)
         x0_preds = []
@@ -467,10 +494,7 @@ class StableDiffusionModelTwoSchedulers(_VariantBase):
         first, second = self.switch_timestamp(self.scheduler_first._timesteps_list,
                                               self.scheduler_second._timesteps_list, num_step_switch, type_switch)
         self.scheduler = self.scheduler_first                     # prepare_latents reads init_noise_sigma
-        latents = self.prepare_latents(batch_size, c.in_channels, c.sample_size * 8, c.sample_size * 8, device,
-                                       generator, latents)
-        self.unet.set_deepcache(-1)
-        self.unet.set_context(ctx)
+        latents = self._start_loop(batch_size, device, generator, latents, ctx, -1)
         eps = self._eps_buffer(unet_batch, device)
         self._num_timesteps = len(first) + len(second)                                              # :545
         x0_preds = []
@@ -527,10 +551,7 @@ class StableDiffusionModelInterlivingSchedulers(_VariantBase):
         self.scheduler_inter.set_timesteps(num_inference_steps // order, device=device)             # :888-894
         keep, t_inter = self.interleave_plan(self.scheduler_main._timesteps_list, order, interliving_steps)
         self.scheduler = self.scheduler_main
-        latents = self.prepare_latents(batch_size, c.in_channels, c.sample_size * 8, c.sample_size * 8, device,
-                                       generator, latents)
-        self.unet.set_deepcache(-1)
-        self.unet.set_context(ctx)
+        latents = self._start_loop(batch_size, device, generator, latents, ctx, -1)
         eps = self._eps_buffer(unet_batch, device)
         self._num_timesteps = len(self.scheduler_main._timesteps_list) - len(interliving_steps)     # :946
         x0_preds = []
@@ -570,10 +591,7 @@ class StableDiffusionModelSkipTimesteps(_VariantBase):
         unet_batch = ctx.shape[0]
         self.scheduler.set_timesteps(num_inference_steps, device=device)
         ts_host = list(self.scheduler._timesteps_list)
-        latents = self.prepare_latents(batch_size, c.in_channels, c.sample_size * 8, c.sample_size * 8, device,
-                                       generator, latents)
-        self.unet.set_deepcache(-1)
-        self.unet.set_context(ctx)
+        latents = self._start_loop(batch_size, device, generator, latents, ctx, -1)
         eps = self._eps_buffer(unet_batch, device)
         self._num_timesteps = len(ts_host)                                                          # :1322
         x0_preds = []

@@ -87,12 +87,18 @@ class HipUNet2DConditionModel:
             pass
 
     # -- workspace / context ---------------------------------------------------------------
-    def _workspace(self, unet_batch: int) -> torch.Tensor:
-        key = (unet_batch, self.cache_branch_id)
+    def latent_size(self, height: Optional[int] = None, width: Optional[int] = None):
+        """(h, w) of the latent: ``sample_size`` where not given."""
+        s = self.config.sample_size
+        return (s if height is None else int(height)), (s if width is None else int(width))
+
+    def _workspace(self, unet_batch: int, h: Optional[int] = None, w: Optional[int] = None) -> torch.Tensor:
+        h, w = self.latent_size(h, w)
+        key = (unet_batch, self.cache_branch_id, h, w)
         if self._ws is None or self._ws_key != key:
-            n = self._lib.sd_unet_workspace_bytes(self._handle, unet_batch, self.cache_branch_id)
+            n = self._lib.sd_unet_workspace_bytes_hw(self._handle, unet_batch, self.cache_branch_id, h, w)
             if n < 0:
-                _lib.check(-1, "sd_unet_workspace_bytes")
+                _lib.check(-1, "sd_unet_workspace_bytes_hw")
             self._ws = None
             self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
             self._ws_key = key
@@ -108,45 +114,50 @@ class HipUNet2DConditionModel:
             self.cache_branch_id = cache_branch_id
             self._ws_key = None
 
-    def set_context(self, encoder_hidden_states: torch.Tensor) -> None:
-        """Project K/V of the prompt for all cross-attention layers (once per sampling run)."""
+    def set_context(self, encoder_hidden_states: torch.Tensor, height: Optional[int] = None,
+                    width: Optional[int] = None) -> None:
+        """Project K/V of the prompt for all cross-attention layers (once per sampling run), for forwards at latent
+        ``height`` x ``width`` (default ``sample_size``; a forward at another size needs a new ``set_context``)."""
+        h, w = self.latent_size(height, width)
         ehs = encoder_hidden_states.to(self.device, torch.float32).contiguous()
         ub = ehs.shape[0]
         if ehs.shape[1] != self.config.context_len or ehs.shape[2] != self.config.cross_attention_dim:
             raise ValueError(f"encoder_hidden_states must be [N,{self.config.context_len},"
                              f"{self.config.cross_attention_dim}], got {tuple(ehs.shape)}")
-        ws = self._workspace(ub)
-        _lib.check(self._lib.sd_unet_set_context(self._handle, _lib.current_stream(), ehs.data_ptr(), ub,
-                                                 self.cache_branch_id, self._ws_ptr(ws), ws.numel() - 256),
-                   "sd_unet_set_context")
+        ws = self._workspace(ub, h, w)
+        _lib.check(self._lib.sd_unet_set_context_hw(self._handle, _lib.current_stream(), ehs.data_ptr(), ub,
+                                                    self.cache_branch_id, h, w, self._ws_ptr(ws), ws.numel() - 256),
+                   "sd_unet_set_context_hw")
         self._ctx_keepalive = ehs
-        self._ctx_key = (encoder_hidden_states.data_ptr(), encoder_hidden_states._version, ub)
+        self._ctx_key = (encoder_hidden_states.data_ptr(), encoder_hidden_states._version, ub, h, w)
 
     # -- forward ---------------------------------------------------------------------------
     def forward_latents(self, latents: torch.Tensor, unet_batch: int, timestep: float,
                         out: Optional[torch.Tensor] = None, cache_mode: int = CACHE_OFF) -> torch.Tensor:
         """eps [unet_batch,4,H,W] fp32 for fp32 NCHW ``latents`` [B,4,H,W]; ``unet_batch`` is B or
-        a multiple of it (CFG: 2B, the duplication is fused).  ``set_context`` must have run."""
-        if self._ctx_key is None or self._ctx_key[2] != unet_batch:
-            raise _lib.SdHipError("set_context(encoder_hidden_states) must be called for this batch first")
+        a multiple of it (CFG: 2B, the duplication is fused).  H and W are taken from ``latents``: each a
+        multiple of 2^(levels - 1).  ``set_context`` must have run for this batch and size."""
+        if latents.dim() != 4 or latents.shape[1] != self.config.in_channels:
+            raise ValueError(f"latents must be [B,{self.config.in_channels},H,W], got {tuple(latents.shape)}")
+        b, c, h, w = latents.shape
+        if self._ctx_key is None or self._ctx_key[2:] != (unet_batch, h, w):
+            raise _lib.SdHipError(f"set_context(encoder_hidden_states, {h}, {w}) must be called for this batch and size first")
         if latents.dtype != torch.float32 or not latents.is_contiguous() or latents.device != self.device:
             latents = latents.to(self.device, torch.float32).contiguous()
-        b, c, h, w = latents.shape
-        if c != self.config.in_channels or h != self.config.sample_size or w != self.config.sample_size:
-            raise ValueError(f"latents must be [B,{self.config.in_channels},{self.config.sample_size},"
-                             f"{self.config.sample_size}], got {tuple(latents.shape)}")
         if out is None:
             out = torch.empty((unet_batch, self.config.out_channels, h, w), dtype=torch.float32, device=self.device)
-        ws = self._workspace(unet_batch)
-        _lib.check(self._lib.sd_unet_forward(self._handle, _lib.current_stream(), latents.data_ptr(), b, unet_batch,
-                                             float(timestep), out.data_ptr(), self._ws_ptr(ws), ws.numel() - 256,
-                                             cache_mode, self.cache_branch_id), "sd_unet_forward")
+        ws = self._workspace(unet_batch, h, w)
+        _lib.check(self._lib.sd_unet_forward_hw(self._handle, _lib.current_stream(), latents.data_ptr(), b, unet_batch, h, w,
+                                                float(timestep), out.data_ptr(), self._ws_ptr(ws), ws.numel() - 256,
+                                                cache_mode, self.cache_branch_id), "sd_unet_forward_hw")
         return out
 
     # -- fp8 activation-scale calibration (include/sd_hip.h::sd_unet_calibrate_fp8) ---------------------------------
     def calibrate_fp8(self, latents: torch.Tensor, unet_batch: int, timesteps, margin: float = 2.0) -> Dict[str, float]:
         """Per-tensor e4m3 activation scales from the amax observed on ``latents`` at each of ``timesteps`` (the context of
-        ``set_context`` is used; ``unet_batch`` as for ``forward_latents``).  Returns ``fp8_scales()``."""
+        ``set_context`` is used; ``unet_batch`` as for ``forward_latents``).  Returns ``fp8_scales()``.
+        Calibration runs at the square ``sample_size`` latent; the per-tensor scales it sets are reused by the plans of
+        every latent size (the same tensors, named after their modules)."""
         if self.weight_dtype != "fp8_e4m3":
             raise _lib.SdHipError("calibrate_fp8: the handle was not created with weight_dtype='fp8'")
         if self.cache_branch_id != -1:
@@ -154,9 +165,12 @@ class HipUNet2DConditionModel:
             # branch's plan would be read at another plan's offsets
             raise _lib.SdHipError("calibrate_fp8: call set_deepcache(-1) and set_context(...) first (the calibration pass runs "
                                   "the plan without DeepCache)")
-        if self._ctx_key is None or self._ctx_key[2] != unet_batch:
-            raise _lib.SdHipError("set_context(encoder_hidden_states) must be called for this batch first")
+        s = self.config.sample_size
+        if self._ctx_key is None or self._ctx_key[2:] != (unet_batch, s, s):
+            raise _lib.SdHipError("set_context(encoder_hidden_states) must be called for this batch first (at sample_size)")
         latents = latents.to(self.device, torch.float32).contiguous()
+        if tuple(latents.shape[2:]) != (s, s):
+            raise ValueError(f"calibrate_fp8: latents must be {s}x{s} (sample_size), got {tuple(latents.shape)}")
         ws = self._workspace(unet_batch)
         for t in timesteps:
             _lib.check(self._lib.sd_unet_calibrate_fp8(self._handle, _lib.current_stream(), latents.data_ptr(), latents.shape[0],
@@ -187,8 +201,11 @@ class HipUNet2DConditionModel:
 
     def forward_profiled(self, latents: torch.Tensor, unet_batch: int, timestep: float, cache_mode: int = CACHE_OFF):
         """One forward with a hipEvent pair around every launch (measurement only, synchronises).
-        Returns {kind: dict(ms, launches, flops, bytes)}."""
+        Returns {kind: dict(ms, launches, flops, bytes)}.  Square ``sample_size`` latents only."""
         latents = latents.to(self.device, torch.float32).contiguous()
+        s = self.config.sample_size
+        if tuple(latents.shape[2:]) != (s, s):
+            raise ValueError(f"forward_profiled: {s}x{s} latents only, got {tuple(latents.shape)}")
         out = torch.empty((unet_batch, self.config.out_channels, latents.shape[2], latents.shape[3]),
                           dtype=torch.float32, device=self.device)
         ws = self._workspace(unet_batch)
@@ -207,16 +224,19 @@ class HipUNet2DConditionModel:
         """diffusers-style call of the reference loop (``src/models.py:227-235``)."""
         if timestep_cond is not None or added_cond_kwargs is not None:
             raise NotImplementedError("timestep_cond / added_cond_kwargs are not part of the SD-1.5 hot path")
-        key = (encoder_hidden_states.data_ptr(), encoder_hidden_states._version, sample.shape[0])
+        h, w = sample.shape[2], sample.shape[3]
+        key = (encoder_hidden_states.data_ptr(), encoder_hidden_states._version, sample.shape[0], h, w)
         if self._ctx_key != key:
-            self.set_context(encoder_hidden_states)
+            self.set_context(encoder_hidden_states, h, w)
         t = float(timestep.item()) if torch.is_tensor(timestep) else float(timestep)
         eps = self.forward_latents(sample, sample.shape[0], t)
         return (eps.to(sample.dtype),)
 
-    def debug_tensor(self, name: str, unet_batch: int, numel: int) -> torch.Tensor:
+    def debug_tensor(self, name: str, unet_batch: int, numel: int, height: Optional[int] = None,
+                     width: Optional[int] = None) -> torch.Tensor:
+        """Tap ``name`` of the last forward; ``height`` / ``width``: its latent size (default ``sample_size``)."""
         out = torch.empty(numel, dtype=torch.float32)
-        ws = self._workspace(unet_batch)
+        ws = self._workspace(unet_batch, height, width)
         _lib.check(self._lib.sd_unet_debug_tensor(self._handle, _lib.current_stream(), name.encode(), out.data_ptr(),
                                                   numel, self._ws_ptr(ws), unet_batch, self.cache_branch_id),
                    "sd_unet_debug_tensor")

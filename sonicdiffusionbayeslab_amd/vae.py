@@ -128,7 +128,7 @@ class HipVaeDecoder:
                        f"load_param({name})")
         _lib.check(self._lib.sd_unet_finalize(self._handle), "finalize")
         self._ws: Optional[torch.Tensor] = None
-        self._ws_batch = None
+        self._ws_key = None
 
     def __del__(self):
         try:
@@ -138,32 +138,34 @@ class HipVaeDecoder:
         except Exception:
             pass
 
-    def _workspace(self, batch: int) -> torch.Tensor:
-        if self._ws is None or self._ws_batch != batch:
-            n = self._lib.sd_unet_workspace_bytes(self._handle, batch, -1)
+    def _workspace(self, batch: int, h: int, w: int) -> torch.Tensor:
+        if self._ws is None or self._ws_key != (batch, h, w):
+            n = self._lib.sd_unet_workspace_bytes_hw(self._handle, batch, -1, h, w)
             if n < 0:
-                _lib.check(-1, "sd_unet_workspace_bytes")
+                _lib.check(-1, "sd_unet_workspace_bytes_hw")
             self._ws = None
             self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
-            self._ws_batch = batch
+            self._ws_key = (batch, h, w)
         return self._ws
 
     def decode(self, latents: torch.Tensor, latent_scale: float = 1.0, chunk: int = 8) -> torch.Tensor:
         """``latents * latent_scale`` -> decoded images (pass ``1 / scaling_factor`` to fuse the division
-        of src/models.py:288).  Large batches are decoded ``chunk`` images at a time."""
+        of src/models.py:288).  Large batches are decoded ``chunk`` images at a time.  Latent sides: multiples of 8
+        in [8, 128] (``sample_size`` is only the default); the images are ``[B, 3, 8h, 8w]``."""
         lat = latents.to(self.device, torch.float32).contiguous()
+        if lat.dim() != 4 or lat.shape[1] != self.config.in_channels:
+            raise ValueError(f"latents must be [B,{self.config.in_channels},h,w], got {tuple(lat.shape)}")
         b, c, h, w = lat.shape
-        if c != self.config.in_channels or h != self.config.sample_size or w != self.config.sample_size:
-            raise ValueError(f"latents must be [B,{self.config.in_channels},{self.config.sample_size},"
-                             f"{self.config.sample_size}], got {tuple(lat.shape)}")
+        if not (8 <= h <= 128 and 8 <= w <= 128 and h % 8 == 0 and w % 8 == 0):
+            raise ValueError(f"latents {h}x{w}: the VAE decoder takes sides that are multiples of 8 in [8, 128]")
         out = torch.empty((b, self.config.out_channels, 8 * h, 8 * w), dtype=torch.float32, device=self.device)
         for s in range(0, b, chunk):
             n = min(chunk, b - s)
-            ws = self._workspace(n)
+            ws = self._workspace(n, h, w)
             wsp = (ws.data_ptr() + 255) // 256 * 256
-            _lib.check(self._lib.sd_vae_decode(self._handle, _lib.current_stream(), lat[s:s + n].data_ptr(), n,
-                                               float(latent_scale), out[s:s + n].data_ptr(), wsp, ws.numel() - 256),
-                       "sd_vae_decode")
+            _lib.check(self._lib.sd_vae_decode_hw(self._handle, _lib.current_stream(), lat[s:s + n].data_ptr(), n, h, w,
+                                                  float(latent_scale), out[s:s + n].data_ptr(), wsp, ws.numel() - 256),
+                       "sd_vae_decode_hw")
         return out
 
     __call__ = decode
