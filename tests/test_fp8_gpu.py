@@ -32,6 +32,12 @@ pytestmark = pytest.mark.gpu
 
 from sonicdiffusionbayeslab_amd import _lib
 from tests.util import cosine, oracle_cfg, rel_l2, synth_inputs
+from tests.bounds import (ATOL_TINY, U32, NHWC, assert_e4m3_codes, assert_elementwise, attention_elementwise, check_guards,
+                          conv3x3_nhwc_ref, conv_gn_elementwise, device_operand, forget_guards, fp8_conv_ref,
+                          fp8_gemm_ref_bound, geglu_ref_bound, gemm_bound, grouped_softmax_elementwise, guarded,
+                          guarded_input, linear_bound, ln_fold_elementwise, ln_fold_ref_bound, norm_ref_bound, sample_rows,
+                          softmax_rows_ref_bound, softmax_rows_elementwise, subpixel_ref, ulp_bf16,
+                          xattn_elementwise)
 
 TOL = 6e-3
 PROD_TOL = 2e-2
@@ -47,10 +53,11 @@ def stream():
 
 
 def P(t):
+    """The device pointer of a kernel operand or output: guarded buffers as they are, anything else copied into a
+    NaN-poisoned guarded buffer (tests/bounds.py), kept alive until the test ends."""
     if t is None:
         return None
-    if t.device.type != "cuda":
-        t = t.cuda()
+    t = device_operand(t)
     _KEEP.append(t)
     return t.data_ptr()
 
@@ -60,6 +67,7 @@ def _drop_keep():
     yield
     torch.cuda.synchronize()
     _KEEP.clear()
+    check_guards()              # every guard of every operand and output of the test (tests/bounds.py)
 
 
 def pad128(c):
@@ -104,11 +112,13 @@ def test_gemm_fp8(sdlib, M, N, K, bias, res):
     if bias: ref = ref + b
     if res: ref = ref + r
     Kp = pad128(K)
-    out = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((M, N), torch.bfloat16)
     _lib.check(sdlib.sd_op_gemm_fp8(stream(), P(padk(xc, Kp)), Kp, P(padk(wc, Kp)), P(wsc), xs, P(b),
                                     P(r.bfloat16()) if res else None, N, P(out), N, M, N, Kp, 0, 0, 1.0))
     torch.cuda.synchronize()
     assert rel_l2(out, ref) < TOL
+    r64, m64, k_eff = fp8_gemm_ref_bound(xq, xs, wq, wsc, b, r)
+    assert_elementwise(out, r64, linear_bound(r64, m64, k_eff), f"gemm fp8 {M}x{N}x{K}", ("row", "col"))
 
 
 @pytest.mark.parametrize("M,C,out_fp8", [(200, 320, 0), (200, 320, 1), (512, 640, 1), (96, 1280, 0)])
@@ -130,8 +140,10 @@ def test_gemm_geglu_fp8(sdlib, M, C, out_fp8):
     idx = torch.tensor(idx)
     Kp = pad128(C)
     wp, sp, bp = padk(wc[idx].contiguous(), Kp), wsc[idx].contiguous(), b[idx].contiguous()
+    p64, m64, k_eff = fp8_gemm_ref_bound(xq, xs, wq, wsc, b)
+    acc = U32 * k_eff * m64
     if out_fp8:
-        out = torch.full((M, H), 0x7f, device="cuda", dtype=torch.uint8)
+        out = guarded((M, H), torch.uint8, fill=0x7f)
         _lib.check(sdlib.sd_op_gemm_fp8(stream(), P(padk(xc, Kp)), Kp, P(wp), P(sp), xs, P(bp), None, 0, P(out), H, M,
                                         8 * C, Kp, 1, 1, os_))
         torch.cuda.synchronize()
@@ -139,12 +151,17 @@ def test_gemm_geglu_fp8(sdlib, M, C, out_fp8):
         assert torch.isfinite(got).all()
         assert rel_l2(got, q8(ref * os_)[1] / os_) < PROD_TOL
         assert rel_l2(got, ref) < 4e-2                  # e4m3 itself: 2^-4 relative steps
+        # in code units: the fp64 value times the output scale (one more fp32 rounding) decides the code
+        g64, gb = geglu_ref_bound(p64[:, :H], acc[:, :H], p64[:, H:], acc[:, H:], out_ulp=False)
+        assert_e4m3_codes(out, g64 * os_, gb * os_ + U32 * (g64 * os_).abs(), f"geglu fp8 e4m3 out {M}x{H}x{C}", ("row", "col"))
     else:
-        out = torch.full((M, H), float("nan"), device="cuda", dtype=torch.bfloat16)
+        out = guarded((M, H), torch.bfloat16)
         _lib.check(sdlib.sd_op_gemm_fp8(stream(), P(padk(xc, Kp)), Kp, P(wp), P(sp), xs, P(bp), None, 0, P(out), H, M,
                                         8 * C, Kp, 1, 0, 1.0))
         torch.cuda.synchronize()
         assert rel_l2(out, ref) < TOL
+        assert_elementwise(out, *geglu_ref_bound(p64[:, :H], acc[:, :H], p64[:, H:], acc[:, H:]), f"geglu fp8 {M}x{H}x{C}",
+                           ("row", "col"))
 
 
 @pytest.mark.parametrize("B,H,Cin,Cout,stride,up,extras", [
@@ -182,11 +199,13 @@ def test_conv3x3_fp8(sdlib, B, H, Cin, Cout, stride, up, extras):
     wpad[:, :Cin] = wc
     wd = wpad.permute(0, 2, 3, 1).reshape(Cout, 9, Cp // 128, 128).permute(0, 2, 1, 3).contiguous()
     rd = r.permute(0, 2, 3, 1).contiguous().bfloat16() if extras else None
-    out = torch.full((B, Ho, Ho, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((B, Ho, Ho, Cout), torch.bfloat16)
     _lib.check(sdlib.sd_op_conv3x3_fp8(stream(), P(xd), P(wd), P(wsc), xs, P(b), P(b2) if extras else None, P(rd),
                                        P(out), B, H, H, Cp, Cout, stride, up))
     torch.cuda.synchronize()
     assert rel_l2(out.permute(0, 3, 1, 2), ref) < TOL
+    r64, m64, k_eff = fp8_conv_ref(xq / xs, wq, wsc, b, b2, r, stride, up)
+    assert_elementwise(out, r64, linear_bound(r64, m64, k_eff + 9 * (Cp - Cin)), f"conv3x3 fp8 B={B} H={H} {Cin}->{Cout} s{stride} up{up}", NHWC)
 
 
 @pytest.mark.parametrize("B,HW,C1,C2,silu", [(2, 256, 320, 0, 1), (2, 64, 640, 320, 1), (1, 1024, 1280, 0, 0),
@@ -202,13 +221,16 @@ def test_groupnorm_fp8_out(sdlib, B, HW, C1, C2, silu):
     ref = ref.permute(0, 2, 1)
     x1 = x[..., :C1].contiguous().bfloat16()
     x2 = x[..., C1:].contiguous().bfloat16() if C2 else None
-    out = torch.full((B, HW, Cp), 0x7f, device="cuda", dtype=torch.uint8)
+    out = guarded((B, HW, Cp), torch.uint8, fill=0x7f)
     _lib.check(sdlib.sd_op_groupnorm_fp8(stream(), P(x1), C1, P(x2), C2, P(gm), P(bt), P(out), B, HW, 32, 1e-5, silu, Cp, s))
     torch.cuda.synchronize()
     o = out.cpu()
     assert (o[..., C:] == 0).all(), "K-tail padding must be zero"
     got = o[..., :C].contiguous().view(torch.float8_e4m3fn).float() / s
     assert rel_l2(got, q8(ref * s)[1] / s) < PROD_TOL
+    n64, nb = norm_ref_bound(x, gm, bt, HW * C // 32, 1e-5, silu, groups=32, out_ulp=False)
+    assert_e4m3_codes(o[..., :C].contiguous(), n64 * s, nb * s + U32 * (n64 * s).abs(), f"groupnorm fp8 e4m3 B={B} HW={HW} C={C1}+{C2}",
+                      ("b", "pixel", "c"))
 
 
 @pytest.mark.parametrize("rows,C", [(300, 320), (129, 640), (64, 1280), (50, 768)])
@@ -218,21 +240,24 @@ def test_layernorm_fp8_out_and_quantize(sdlib, rows, C):
     x = (torch.randn(rows, C, generator=g) * 1.5 + 0.2).bfloat16().float()
     gm, bt = torch.randn(C, generator=g) * 0.3 + 1, torch.randn(C, generator=g) * 0.2
     ref = F.layer_norm(x, (C,), gm, bt, 1e-5)
-    out = torch.full((rows, Cp), 0x7f, device="cuda", dtype=torch.uint8)
+    out = guarded((rows, Cp), torch.uint8, fill=0x7f)
     _lib.check(sdlib.sd_op_layernorm_fp8(stream(), P(x.bfloat16()), P(gm), P(bt), P(out), rows, C, Cp, 1e-5, s))
     torch.cuda.synchronize()
     o = out.cpu()
     assert (o[:, C:] == 0).all()
     assert rel_l2(o[:, :C].contiguous().view(torch.float8_e4m3fn).float() / s, q8(ref * s)[1] / s) < PROD_TOL
+    n64, nb = norm_ref_bound(x, gm, bt, C, 1e-5, False, out_ulp=False)
+    assert_e4m3_codes(o[:, :C].contiguous(), n64 * s, nb * s + U32 * (n64 * s).abs(), f"layernorm fp8 e4m3 {rows}x{C}", ("row", "c"))
     # plain conversion: bit-exact against torch's e4m3 rounding (same format, same nearest-even rule, saturation)
     big = x * 100.0                                   # exercises the +-448 saturation
-    out2 = torch.full((rows, Cp), 0x7f, device="cuda", dtype=torch.uint8)
+    out2 = guarded((rows, Cp), torch.uint8, fill=0x7f)
     _lib.check(sdlib.sd_op_quantize_fp8(stream(), P(big.bfloat16()), P(out2), rows, C, Cp, 1.0))
     torch.cuda.synchronize()
     want = q8(big.bfloat16().float())[0]
     got = out2.cpu()[:, :C]
     same = (got == want) | ((got & 0x7f) == 0) & ((want & 0x7f) == 0)      # +0 / -0
     assert same.all() and (out2.cpu()[:, C:] == 0).all()
+    assert assert_e4m3_codes(got.contiguous(), big.bfloat16().double(), 0.0, f"quantize fp8 {rows}x{C}", ("row", "c")) == 0
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -12,8 +12,14 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from sonicdiffusionbayeslab_amd import _lib
+from tests.bounds import (ATOL_TINY, U32, assert_elementwise, attention_ref_bound, check_guards, conv3x3_nhwc_ref,
+                          forget_guards, gemm_bound, gemm_ref, geglu_ref_bound, guarded, guarded_input, linear_bound,
+                          ln_fold_ref_bound, norm_ref_bound, softmax_rows_ref_bound, subpixel_ref, ulp_bf16,
+                          attention_elementwise, conv_gn_elementwise, grouped_softmax_elementwise, ln_fold_elementwise,
+                          sample_rows, xattn_elementwise, xattn_norm2_elementwise)
 
 TOL = 6e-3
+NHWC = ("b", "y", "x", "c")
 
 
 def dev(t, dtype=None):
@@ -46,11 +52,31 @@ def P(t, dtype=None):
     return t.data_ptr()
 
 
+def G(t, dtype=None, **kw):
+    """A kernel operand in its own allocation between NaN-poisoned guards (tests/bounds.py)."""
+    return guarded_input(t, dtype, **kw)
+
+
+def OUT(shape, dtype=torch.bfloat16, **kw):
+    """A NaN-prefilled kernel output between sentinel guards (tests/bounds.py)."""
+    return guarded(shape, dtype, **kw)
+
+
+def nchw(w, Cout, Cin):
+    """[Cout][Cin/64][9][64] packed conv weight -> [Cout, Cin, 3, 3]."""
+    return w.float().cpu().view(Cout, Cin // 64, 3, 3, 64).permute(0, 1, 4, 2, 3).reshape(Cout, Cin, 3, 3)
+
+
+
+
+
+
 @pytest.fixture(autouse=True)
 def _drop_keep():
     yield
     torch.cuda.synchronize()
     _KEEP.clear()
+    forget_guards()
 
 
 @pytest.mark.parametrize("M,N,K,K1,bias,bias2,res", [
@@ -71,17 +97,19 @@ def test_gemm(sdlib, M, N, K, K1, bias, bias2, res):
     if bias: ref = ref + b
     if bias2: ref = ref + b2
     if res: ref = ref + r
-    x1 = dev(x[:, :K1].contiguous(), torch.bfloat16)
-    x2 = dev(x[:, K1:].contiguous(), torch.bfloat16) if K1 < K else None
-    wd = dev(w, torch.bfloat16)
-    bd = dev(b) if bias else None
-    b2d = dev(b2) if bias2 else None
-    rd = dev(r, torch.bfloat16) if res else None
-    out = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
+    x1 = G(x[:, :K1].contiguous(), torch.bfloat16)
+    x2 = G(x[:, K1:].contiguous(), torch.bfloat16) if K1 < K else None
+    wd = G(w, torch.bfloat16)
+    bd = G(b) if bias else None
+    b2d = G(b2) if bias2 else None
+    rd = G(r, torch.bfloat16) if res else None
+    out = OUT((M, N))
     _lib.check(sdlib.sd_op_gemm(stream(), P(x1), K1, P(x2), K - K1, K1, P(wd), P(bd),
                                 P(b2d), P(rd), N, P(out), N, M, N, K, 0))
     torch.cuda.synchronize()
+    check_guards()
     assert rel_l2(out, ref) < TOL
+    assert_elementwise(out, *gemm_bound(x, w, b, b2, r), f"gemm {M}x{N}x{K} K1={K1}", ("row", "col"))
 
 
 def test_gemm_geglu(sdlib):
@@ -99,13 +127,18 @@ def test_gemm_geglu(sdlib):
         grp, within = divmod(r, 32)
         idx.append(grp * 16 + within if within < 16 else H + grp * 16 + within - 16)
     idx = torch.tensor(idx)
-    wp, bp = dev(w[idx].contiguous(), torch.bfloat16), dev(b[idx].contiguous())
-    xd = dev(x, torch.bfloat16)
-    out = torch.full((M, H), float("nan"), device="cuda", dtype=torch.bfloat16)
+    wp, bp = G(w[idx].contiguous(), torch.bfloat16), G(b[idx].contiguous())
+    xd = G(x, torch.bfloat16)
+    out = OUT((M, H))
     _lib.check(sdlib.sd_op_gemm(stream(), P(xd), C, None, 0, C, P(wp), P(bp), None, None, 0,
                                 P(out), H, M, 8 * C, C, 1))
     torch.cuda.synchronize()
+    check_guards()
     assert rel_l2(out, ref) < TOL
+    p64, m64 = gemm_ref(x, w, b)
+    acc = U32 * (C + 1) * m64
+    assert_elementwise(out, *geglu_ref_bound(p64[:, :H], acc[:, :H], p64[:, H:], acc[:, H:]), f"geglu gemm {M}x{H}x{C}",
+                       ("row", "col"))
 
 
 @pytest.mark.parametrize("B,H,Cin,Cout,stride,up,extras", [
@@ -136,15 +169,18 @@ def test_conv3x3(sdlib, B, H, Cin, Cout, stride, up, extras):
         b2 = torch.randn(Cout, generator=g)
         r = r16(torch.randn(B, Cout, Ho, Ho, generator=g))
         ref = ref + b2[None, :, None, None] + r
-    xd = dev(x.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
-    wd = dev(w.permute(0, 2, 3, 1).reshape(Cout, 9, Cin // 64, 64).permute(0, 2, 1, 3).contiguous(), torch.bfloat16)
-    rd = dev(r.permute(0, 2, 3, 1).contiguous(), torch.bfloat16) if extras else None
-    out = torch.full((B, Ho, Ho, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
-    _lib.check(sdlib.sd_op_conv3x3(stream(), P(xd), P(wd), P(b),
-                                   P(b2) if extras else None, P(rd), P(out), B, H, H, Cin,
+    xd = G(x.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
+    wd = G(w.permute(0, 2, 3, 1).reshape(Cout, 9, Cin // 64, 64).permute(0, 2, 1, 3).contiguous(), torch.bfloat16)
+    rd = G(r.permute(0, 2, 3, 1).contiguous(), torch.bfloat16) if extras else None
+    out = OUT((B, Ho, Ho, Cout))
+    _lib.check(sdlib.sd_op_conv3x3(stream(), P(xd), P(wd), P(G(b)),
+                                   P(G(b2)) if extras else None, P(rd), P(out), B, H, H, Cin,
                                    Cout, stride, up))
     torch.cuda.synchronize()
+    check_guards()
     assert rel_l2(out.permute(0, 3, 1, 2), ref) < TOL
+    r64, m64 = conv3x3_nhwc_ref(x, w, b, b2, r, stride, up)
+    assert_elementwise(out, r64, linear_bound(r64, m64, 9 * Cin + 3), f"conv3x3 B={B} H={H} {Cin}->{Cout} s{stride} up{up}", NHWC)
 
 
 @pytest.mark.parametrize("B,H,Cin,Cout", [(2, 64, 128, 320), (3, 16, 320, 192), (5, 8, 256, 192), (1, 32, 640, 640)])
@@ -155,14 +191,17 @@ def test_conv3x3_halo_four_wave_layout_is_bit_identical(sdlib, B, H, Cin, Cout):
     ablation mode: it carries none of those kernels."""
     abl = _lib.load_ablate()
     g = torch.Generator().manual_seed(B + H + Cin)
-    xd = dev(r16(torch.randn(B, H, H, Cin, generator=g)), torch.bfloat16)
-    wd = dev(r16(torch.randn(Cout, Cin // 64, 9, 64, generator=g) / math.sqrt(9 * Cin)), torch.bfloat16)
+    xd = G(r16(torch.randn(B, H, H, Cin, generator=g)), torch.bfloat16)
+    wd = G(r16(torch.randn(Cout, Cin // 64, 9, 64, generator=g) / math.sqrt(9 * Cin)), torch.bfloat16)
     outs = []
     for lib, mode in ((sdlib, 0), (abl, 0), (abl, 256)):
-        out = torch.full((B, H, H, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
+        out = OUT((B, H, H, Cout))
         _lib.check(lib.sd_op_conv3x3_ablate(stream(), P(xd), P(wd), P(out), B, H, H, Cin, Cout, mode), lib=lib)
         torch.cuda.synchronize()
         outs.append(out)
+    check_guards()
+    r64, m64 = conv3x3_nhwc_ref(xd.float().cpu().permute(0, 3, 1, 2), nchw(wd, Cout, Cin))
+    assert_elementwise(outs[0], r64, linear_bound(r64, m64, 9 * Cin), f"conv3x3 halo B={B} H={H} {Cin}->{Cout}", NHWC)
     assert torch.isfinite(outs[0].float()).all()
     assert torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16))
     assert torch.equal(outs[0].view(torch.int16), outs[2].view(torch.int16))
@@ -200,20 +239,25 @@ def test_conv3x3_upsample_as_four_subpixel_convs(sdlib, B, H, Cin, Cout):
     b = torch.randn(Cout, generator=g)
     ref = F.conv2d(F.interpolate(x, scale_factor=2.0, mode="nearest"), w, b, padding=1)
     w4p = _subpixel_weights(w)
-    xd = dev(x.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
+    xd = G(x.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
+    w4d, bd = G(w4p, torch.bfloat16), G(b)
 
     def run():
-        out = torch.full((B, 2 * H, 2 * H, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
-        _lib.check(sdlib.sd_op_conv3x3_upsample_subpixel(stream(), P(xd), P(w4p, torch.bfloat16), P(b), P(out), B, H, H, Cin, Cout))
+        out = OUT((B, 2 * H, 2 * H, Cout))
+        _lib.check(sdlib.sd_op_conv3x3_upsample_subpixel(stream(), P(xd), P(w4d), P(bd), P(out), B, H, H, Cin, Cout))
         torch.cuda.synchronize()
         return out
     out = run()
     assert rel_l2(out.permute(0, 3, 1, 2), ref) < TOL
+    # elementwise: from the bf16-rounded summed phase weights the kernel reads (their rounding is the formulation's)
+    r64, m64 = subpixel_ref(x, w4p.to(torch.bfloat16), b)
+    assert_elementwise(out, r64, linear_bound(r64, m64, 4 * Cin + 1), f"conv3x3 subpixel B={B} H={H} {Cin}->{Cout}", NHWC)
     os.environ["SD_SUBPIX_HALO"] = "0"
     try:
         other = run()
     finally:
         del os.environ["SD_SUBPIX_HALO"]
+    check_guards()
     assert torch.equal(out.view(torch.int16), other.view(torch.int16))
 
 
@@ -231,18 +275,29 @@ def test_conv3x3_upsample_subpixel_groupnorm_producer_statistics(sdlib, B, H, Ci
     gamma, beta = torch.randn(Cout, generator=g), torch.randn(Cout, generator=g)
     conv = r16(F.conv2d(F.interpolate(x, scale_factor=2.0, mode="nearest"), w, b, padding=1))
     ref = F.silu(F.group_norm(conv, 32, gamma, beta, 1e-5))
-    xd = dev(x.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
-    y = torch.full((B, 2 * H, 2 * H, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
-    yn = torch.full_like(y, float("nan"))
-    _lib.check(sdlib.sd_op_conv3x3_upsample_subpixel_groupnorm(stream(), P(xd), P(_subpixel_weights(w), torch.bfloat16), P(b), P(y),
-                                                               B, H, H, Cin, Cout, P(gamma), P(beta), P(yn), 32, 1e-5, 1))
+    xd = G(x.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
+    w4p = _subpixel_weights(w)
+    gd, btd = G(gamma), G(beta)
+    y = OUT((B, 2 * H, 2 * H, Cout))
+    yn = OUT((B, 2 * H, 2 * H, Cout))
+    _lib.check(sdlib.sd_op_conv3x3_upsample_subpixel_groupnorm(stream(), P(xd), P(G(w4p, torch.bfloat16)), P(G(b)), P(y),
+                                                               B, H, H, Cin, Cout, P(gd), P(btd), P(yn), 32, 1e-5, 1))
     torch.cuda.synchronize()
     assert rel_l2(y.permute(0, 3, 1, 2), conv) < TOL
     assert rel_l2(yn.permute(0, 3, 1, 2), ref) < TOL
-    own = torch.full_like(y, float("nan"))
-    _lib.check(sdlib.sd_op_groupnorm(stream(), P(y), Cout, None, 0, P(gamma), P(beta), P(own), B, 4 * H * H, 32, 1e-5, 1))
+    own = OUT((B, 2 * H, 2 * H, Cout))
+    _lib.check(sdlib.sd_op_groupnorm(stream(), P(y), Cout, None, 0, P(gd), P(btd), P(own), B, 4 * H * H, 32, 1e-5, 1))
     torch.cuda.synchronize()
+    check_guards()
     assert rel_l2(yn, own) < 2e-3
+    r64, m64 = subpixel_ref(x, w4p.to(torch.bfloat16), b)
+    assert_elementwise(y, r64, linear_bound(r64, m64, 4 * Cin + 1), f"conv3x3 subpixel+gn conv B={B} H={H} {Cin}->{Cout}", NHWC)
+    # the normalisation, chained from the kernel's own stored conv output
+    yk = y.float().cpu().view(B, 4 * H * H, Cout)
+    n64, nb = norm_ref_bound(yk, gamma, beta, 4 * H * H * Cout // 32, 1e-5, True, groups=32)
+    for t, name in ((yn, "producer statistics"), (own, "own statistics")):
+        assert_elementwise(t.view(B, 4 * H * H, Cout), n64, nb, f"groupnorm after subpixel conv ({name}) B={B} H={H} C={Cout}",
+                           ("b", "pixel", "c"))
 
 
 @pytest.mark.parametrize("B,HW,C1,C2,silu,eps", [
@@ -261,13 +316,16 @@ def test_groupnorm(sdlib, B, HW, C1, C2, silu, eps):
     ref = F.group_norm(x.permute(0, 2, 1), 32, gamma, beta, eps)
     if silu: ref = F.silu(ref)
     ref = ref.permute(0, 2, 1)
-    x1 = dev(x[..., :C1].contiguous(), torch.bfloat16)
-    x2 = dev(x[..., C1:].contiguous(), torch.bfloat16) if C2 else None
-    out = torch.full((B, HW, C), float("nan"), device="cuda", dtype=torch.bfloat16)
-    _lib.check(sdlib.sd_op_groupnorm(stream(), P(x1), C1, P(x2), C2, P(gamma),
-                                     P(beta), P(out), B, HW, 32, eps, silu))
+    x1 = G(x[..., :C1].contiguous(), torch.bfloat16)
+    x2 = G(x[..., C1:].contiguous(), torch.bfloat16) if C2 else None
+    out = OUT((B, HW, C))
+    _lib.check(sdlib.sd_op_groupnorm(stream(), P(x1), C1, P(x2), C2, P(G(gamma)),
+                                     P(G(beta)), P(out), B, HW, 32, eps, silu))
     torch.cuda.synchronize()
+    check_guards()
     assert rel_l2(out, ref) < TOL
+    assert_elementwise(out, *norm_ref_bound(x, gamma, beta, HW * C // 32, eps, silu, groups=32),
+                       f"groupnorm B={B} HW={HW} C={C1}+{C2}", ("b", "pixel", "c"))
 
 
 @pytest.mark.parametrize("B,H,Cin,Cout", [
@@ -286,21 +344,26 @@ def test_conv3x3_groupnorm_producer_statistics(sdlib, B, H, Cin, Cout):
     gamma, beta = torch.randn(Cout, generator=g), torch.randn(Cout, generator=g)
     conv = r16(F.conv2d(x, w, b, padding=1) + b2[None, :, None, None] + r)
     ref = F.silu(F.group_norm(conv, 32, gamma, beta, 1e-5))
-    xd = dev(x.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
-    wd = dev(w.permute(0, 2, 3, 1).reshape(Cout, 9, Cin // 64, 64).permute(0, 2, 1, 3).contiguous(), torch.bfloat16)
-    rd = dev(r.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
-    y = torch.full((B, H, H, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
-    yn = torch.full_like(y, float("nan"))
-    _lib.check(sdlib.sd_op_conv3x3_groupnorm(stream(), P(xd), P(wd), P(b), P(b2), P(rd), P(y), B, H, H, Cin, Cout,
-                                             P(gamma), P(beta), P(yn), 32, 1e-5, 1))
+    xd = G(x.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
+    wd = G(w.permute(0, 2, 3, 1).reshape(Cout, 9, Cin // 64, 64).permute(0, 2, 1, 3).contiguous(), torch.bfloat16)
+    rd = G(r.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
+    gd, btd = G(gamma), G(beta)
+    y = OUT((B, H, H, Cout))
+    yn = OUT((B, H, H, Cout))
+    _lib.check(sdlib.sd_op_conv3x3_groupnorm(stream(), P(xd), P(wd), P(G(b)), P(G(b2)), P(rd), P(y), B, H, H, Cin, Cout,
+                                             P(gd), P(btd), P(yn), 32, 1e-5, 1))
     torch.cuda.synchronize()
     assert rel_l2(y.permute(0, 3, 1, 2), conv) < TOL
     assert rel_l2(yn.permute(0, 3, 1, 2), ref) < TOL
     # and the same GroupNorm computing its own statistics from the stored tensor agrees to rounding
-    own = torch.full_like(y, float("nan"))
-    _lib.check(sdlib.sd_op_groupnorm(stream(), P(y), Cout, None, 0, P(gamma), P(beta), P(own), B, H * H, 32, 1e-5, 1))
+    own = OUT((B, H, H, Cout))
+    _lib.check(sdlib.sd_op_groupnorm(stream(), P(y), Cout, None, 0, P(gd), P(btd), P(own), B, H * H, 32, 1e-5, 1))
     torch.cuda.synchronize()
+    check_guards()
     assert rel_l2(yn, own) < 2e-3
+    conv_gn_elementwise(x, w, b, b2, r, gamma, beta, y, (yn, own), f"conv3x3+gn B={B} H={H} {Cin}->{Cout}")
+
+
 
 
 @pytest.mark.parametrize("B,H,Cin,Cout,res", [
@@ -323,15 +386,16 @@ def test_conv3x3_groupnorm_small_images_finish_the_deferred_splitk_reduce(sdlib,
     gamma, beta = torch.randn(Cout, generator=g), torch.randn(Cout, generator=g)
     conv = r16(F.conv2d(x, w, b, padding=1) + b2[None, :, None, None] + (r if res else 0.0))
     ref = F.silu(F.group_norm(conv, 32, gamma, beta, 1e-5))
-    xd = dev(x.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
-    wd = dev(w.permute(0, 2, 3, 1).reshape(Cout, 9, Cin // 64, 64).permute(0, 2, 1, 3).contiguous(), torch.bfloat16)
-    rd = dev(r.permute(0, 2, 3, 1).contiguous(), torch.bfloat16) if res else None
+    xd = G(x.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
+    wd = G(w.permute(0, 2, 3, 1).reshape(Cout, 9, Cin // 64, 64).permute(0, 2, 1, 3).contiguous(), torch.bfloat16)
+    rd = G(r.permute(0, 2, 3, 1).contiguous(), torch.bfloat16) if res else None
+    bd, b2d, gd, btd = G(b), G(b2), G(gamma), G(beta)
 
     def run():
-        y = torch.full((B, H, H, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
-        yn = torch.full_like(y, float("nan"))
-        _lib.check(sdlib.sd_op_conv3x3_groupnorm(stream(), P(xd), P(wd), P(b), P(b2), P(rd) if res else None, P(y), B, H, H, Cin,
-                                                 Cout, P(gamma), P(beta), P(yn), 32, 1e-5, 1))
+        y = OUT((B, H, H, Cout))
+        yn = OUT((B, H, H, Cout))
+        _lib.check(sdlib.sd_op_conv3x3_groupnorm(stream(), P(xd), P(wd), P(bd), P(b2d), P(rd) if res else None, P(y), B, H, H, Cin,
+                                                 Cout, P(gd), P(btd), P(yn), 32, 1e-5, 1))
         torch.cuda.synchronize()
         return y, yn
     assert sdlib.sd_op_conv3x3_splitk(B * H * H, Cout, Cin, H, H, 1, 0) > 1       # the case exists to exercise the slabs
@@ -343,8 +407,10 @@ def test_conv3x3_groupnorm_small_images_finish_the_deferred_splitk_reduce(sdlib,
         y2, yn2 = run()
     finally:
         del os.environ["SD_GN_SLAB"]
+    check_guards()
     assert torch.equal(y.view(torch.int16), y2.view(torch.int16))
     assert torch.equal(yn.view(torch.int16), yn2.view(torch.int16))
+    conv_gn_elementwise(x, w, b, b2, r, gamma, beta, y, (yn,), f"conv3x3+gn split-K B={B} H={H} {Cin}->{Cout}")
 
 
 def fold_layernorm(w, gamma, beta, bias):
@@ -386,25 +452,35 @@ def test_layernorm_folded_into_gemm(sdlib, M, C, N2, epi, mean):
     wg, c1, c2 = fold_layernorm(w2p, gamma, beta, b2p)
     parts = sdlib.sd_op_ln_partials(0, M, C)
     assert parts == 2 * ((C + 159) // 160)
-    hd = torch.full((M, C), float("nan"), device="cuda", dtype=torch.bfloat16)
-    rs = torch.full((parts, M, 2), float("nan"), device="cuda")
-    _lib.check(sdlib.sd_op_gemm_rowstats(stream(), P(x, torch.bfloat16), C, P(w1, torch.bfloat16), P(b1), P(r, torch.bfloat16), C,
-                                         P(hd), C, M, C, C, P(rs)))
+    hd = OUT((M, C))
+    rs = OUT((parts, M, 2), torch.float32)
+    _lib.check(sdlib.sd_op_gemm_rowstats(stream(), P(G(x, torch.bfloat16)), C, P(G(w1, torch.bfloat16)), P(G(b1)),
+                                         P(G(r, torch.bfloat16)), C, P(hd), C, M, C, C, P(rs)))
     torch.cuda.synchronize()
     assert rel_l2(hd, h) < TOL
+    assert_elementwise(hd, *gemm_bound(x, w1, b1, None, r16(r)), f"gemm rowstats {M}x{C}", ("row", "col"))
     tot, h64 = rs.sum(0).cpu().double(), hd.double().cpu()
     assert torch.allclose(tot[:, 0], h64.sum(1), rtol=1e-4, atol=1e-2)
     assert torch.allclose(tot[:, 1], (h64 * h64).sum(1), rtol=1e-4, atol=1e-2)
+    # partials: fp32 sums of the stored bf16 values (C / parts terms each, then the partials' own sum here)
+    sl = h64.view(M, parts, C // parts).permute(1, 0, 2)
+    for j, (want, mag) in enumerate(((sl.sum(-1), sl.abs().sum(-1)), ((sl * sl).sum(-1), (sl * sl).sum(-1)))):
+        assert_elementwise(rs[..., j], want, U32 * (C // parts + 1) * mag + ATOL_TINY, f"gemm rowstats partial[{j}] {M}x{C}",
+                           ("part", "row"))
     No = N2 // 2 if epi else N2
-    out = torch.full((M, No), float("nan"), device="cuda", dtype=torch.bfloat16)
-    _lib.check(sdlib.sd_op_gemm_ln(stream(), P(hd), C, P(wg, torch.bfloat16), P(c1), P(c2), P(rs), parts, 1e-5,
+    out = OUT((M, No))
+    _lib.check(sdlib.sd_op_gemm_ln(stream(), P(hd), C, P(G(wg, torch.bfloat16)), P(G(c1)), P(G(c2)), P(rs), parts, 1e-5,
                                    P(out), No, M, N2, C, epi))
     torch.cuda.synchronize()
+    check_guards()
+    ln_fold_elementwise(out, hd, wg, c1, c2, rs, epi, f"gemm_ln {M}x{N2}x{C} epi{epi}", idx=idx if epi else None)
     # reference from the device's own h (the fold is judged, not the producer's rounding)
     hh = hd.float().cpu()
     z = F.layer_norm(hh, (C,), gamma, beta, 1e-5) @ r16(w2).t() + b2
     ref = z[:, :N2 // 2] * F.gelu(z[:, N2 // 2:]) if epi else z
     assert rel_l2(out, ref) < TOL
+
+
 
 
 def _gemm_plan(sdlib, lean, x, x2, w, b, b2, r, M, N, K, K1, want_rs=False, want_st=False, ln=None, hm_tokens=0):
@@ -414,10 +490,10 @@ def _gemm_plan(sdlib, lean, x, x2, w, b, b2, r, M, N, K, K1, want_rs=False, want
     os.environ["SD_GEMM_LEAN"] = "1" if lean else "0"
     try:
         ncols = N // 3 if hm_tokens else N
-        out = torch.full((M, ncols), float("nan"), device="cuda", dtype=torch.bfloat16)
-        rs = torch.full((2 * (N // 160), M, 2), float("nan"), device="cuda") if want_rs else None
-        st = torch.full((M // 64, N, 2), float("nan"), device="cuda") if want_st else None
-        kv = torch.full((2, M // hm_tokens, ncols // 40, hm_tokens, 40), float("nan"), device="cuda", dtype=torch.bfloat16) if hm_tokens else None
+        out = OUT((M, ncols))
+        rs = OUT((2 * (N // 160), M, 2), torch.float32) if want_rs else None
+        st = OUT((M // 64, N, 2), torch.float32) if want_st else None
+        kv = OUT((2, M // hm_tokens, ncols // 40, hm_tokens, 40)) if hm_tokens else None
         ln_rs, ln_parts, ln_c1 = ln if ln else (None, 0, None)
         _lib.check(sdlib.sd_op_gemm_plan(stream(), P(x), K1, P(x2), K - K1, K1, P(w), P(b), P(b2), P(r), N, P(out), ncols, M, N, K,
                                          P(rs), P(st), P(ln_rs), ln_parts, P(ln_c1), 1e-5, P(kv), hm_tokens))
@@ -445,11 +521,13 @@ def test_gemm_lean_kernel_is_bit_identical_to_the_general_kernel(sdlib, M, N, K,
     b = torch.randn(N, generator=g) if bias else None
     b2 = torch.randn(N, generator=g) if bias2 else None
     r = r16(torch.randn(M, N, generator=g)) if res else None
-    x1 = dev(x[:, :K1].contiguous(), torch.bfloat16)
-    x2 = dev(x[:, K1:].contiguous(), torch.bfloat16) if K1 < K else None
-    args = (x1, x2, dev(w, torch.bfloat16), dev(b) if bias else None, dev(b2) if bias2 else None,
-            dev(r, torch.bfloat16) if res else None, M, N, K, K1, rowstats, stats)
+    x1 = G(x[:, :K1].contiguous(), torch.bfloat16)
+    x2 = G(x[:, K1:].contiguous(), torch.bfloat16) if K1 < K else None
+    args = (x1, x2, G(w, torch.bfloat16), G(b) if bias else None, G(b2) if bias2 else None,
+            G(r, torch.bfloat16) if res else None, M, N, K, K1, rowstats, stats)
     lean, general = _gemm_plan(sdlib, True, *args), _gemm_plan(sdlib, False, *args)
+    check_guards()
+    assert_elementwise(lean[0], *gemm_bound(x, w, b, b2, r), f"gemm lean {M}x{N}x{K} K1={K1}", ("row", "col"))
     ref = x @ w.t()
     for t in (b, b2, r):
         if t is not None:
@@ -476,11 +554,12 @@ def test_gemm_lean_layernorm_fold_and_headmajor_kv(sdlib, B, tokens, C, mean):
     parts = 2 * (C // 160)
     hh = h.view(M, parts, C // parts)
     rs = torch.stack([hh.sum(2), (hh * hh).sum(2)], dim=2).permute(1, 0, 2).contiguous()      # [parts][M][2]
-    ln = (dev(rs), parts, dev(c1))
-    args = (dev(h, torch.bfloat16), None, dev(wg, torch.bfloat16), dev(c2), None, None, M, N, C, C)
+    ln = (G(rs), parts, G(c1))
+    args = (G(h, torch.bfloat16), None, G(wg, torch.bfloat16), G(c2), None, None, M, N, C, C)
     plain = _gemm_plan(sdlib, True, *args, ln=ln)[0]
     ref = F.layer_norm(h, (C,), gamma, beta, 1e-5) @ r16(w).t()
     assert rel_l2(plain, ref) < TOL
+    ln_fold_elementwise(plain, h, wg, c1, c2, rs, 0, f"gemm lean ln-fold {M}x{N}x{C}")
     assert torch.equal(plain, _gemm_plan(sdlib, False, *args, ln=ln)[0])
     if C // 40 == 8:                                 # head dim 40, >= 8192 rows (128-row tiles): the 64x64 level's layout
         for lean in (True, False):
@@ -489,6 +568,7 @@ def test_gemm_lean_layernorm_fold_and_headmajor_kv(sdlib, B, tokens, C, mean):
             for which in (0, 1):
                 want = plain[:, (1 + which) * C:(2 + which) * C].reshape(B, tokens, C // 40, 40).permute(0, 2, 1, 3)
                 assert torch.equal(kv[which], want)
+    check_guards()
 
 
 @pytest.mark.parametrize("M,C,fold", [(512, 320, True), (256, 640, True), (256, 1280, True), (512, 320, False), (300, 640, False),
@@ -511,16 +591,16 @@ def test_gemm_lean_geglu_kernel_is_bit_identical_to_the_general_kernel(sdlib, M,
         wg, c1, c2 = fold_layernorm(w[idx], gamma, beta, b[idx])
         parts = 2 * (C // 160) if fold is True else int(fold)
         hh = h.view(M, parts, C // parts)
-        rs = dev(torch.stack([hh.sum(2), (hh * hh).sum(2)], dim=2).permute(1, 0, 2).contiguous())
-        hd, wd, c1d, c2d = dev(h, torch.bfloat16), dev(wg, torch.bfloat16), dev(c1), dev(c2)
+        rs = G(torch.stack([hh.sum(2), (hh * hh).sum(2)], dim=2).permute(1, 0, 2).contiguous())
+        hd, wd, c1d, c2d = G(h, torch.bfloat16), G(wg, torch.bfloat16), G(c1), G(c2)
     else:
         z = h @ r16(w).t() + b
-        hd, wd, bd = dev(h, torch.bfloat16), dev(w[idx].contiguous(), torch.bfloat16), dev(b[idx].contiguous())
+        hd, wd, bd = G(h, torch.bfloat16), G(w[idx].contiguous(), torch.bfloat16), G(b[idx].contiguous())
     ref = z[:, :H] * F.gelu(z[:, H:])
     for lean in ("1", "0"):
         os.environ["SD_GEMM_LEAN"] = lean
         try:
-            out = torch.full((M, H), float("nan"), device="cuda", dtype=torch.bfloat16)
+            out = OUT((M, H))
             if fold:
                 _lib.check(sdlib.sd_op_gemm_ln(stream(), P(hd), C, P(wd), P(c1d), P(c2d), P(rs), parts, 1e-5, P(out), H, M, N, C, 1))
             else:
@@ -531,6 +611,14 @@ def test_gemm_lean_geglu_kernel_is_bit_identical_to_the_general_kernel(sdlib, M,
         outs.append(out)
     assert torch.isfinite(outs[0].float()).all() and rel_l2(outs[0], ref) < TOL
     assert torch.equal(outs[0], outs[1])
+    check_guards()
+    if fold:
+        ln_fold_elementwise(outs[0], h, wg, c1, c2, rs, 1, f"geglu lean ln-fold {M}x{N}x{C} parts={parts}", idx=idx)
+    else:
+        p64, m64 = gemm_ref(h, r16(w), b)
+        acc = U32 * (C + 1) * m64
+        assert_elementwise(outs[0], *geglu_ref_bound(p64[:, :H], acc[:, :H], p64[:, H:], acc[:, H:]), f"geglu lean {M}x{N}x{C}",
+                           ("row", "col"))
 
 
 @pytest.mark.parametrize("M,C,epi", [(16384, 640, 1), (65536, 320, 0), (16384, 640, 0), (4096, 1280, 1)])
@@ -549,13 +637,22 @@ def test_layernorm_fold_gemms_are_run_to_run_deterministic_at_bench_shapes(sdlib
     parts = 2 * (C // 160)
     xf = x.float().view(M, parts, C // parts)
     rs = torch.stack([xf.sum(2), (xf * xf).sum(2)], dim=2).permute(1, 0, 2).contiguous()
-    outs = [torch.full((M, H), float("nan"), device="cuda", dtype=torch.bfloat16) for _ in range(6)]
+    x, w, c1, c2, rs = G(x), G(w), G(c1), G(c2), G(rs)
+    outs = [OUT((M, H)) for _ in range(6)]
     for out in outs:
         _lib.check(sdlib.sd_op_gemm_ln(stream(), P(x), C, P(w), P(c1), P(c2), P(rs), parts, 1e-5, P(out), H, M, N, C, epi))
     torch.cuda.synchronize()
+    check_guards()
     assert torch.isfinite(outs[0].float()).all()
     for out in outs[1:]:
         assert torch.equal(out, outs[0])
+    # per element on the first and last 256 rows (the fp64 reference of all rows would dominate the suite's time);
+    # epi 1 packs [16 value | 16 gate] in the weight's row order, which the reference here follows
+    rows = torch.cat([torch.arange(256), torch.arange(M - 256, M)])
+    idx = None
+    if epi:
+        idx = torch.tensor([(q // 32) * 16 + q % 32 if q % 32 < 16 else H + (q // 32) * 16 + q % 32 - 16 for q in range(N)])
+    ln_fold_elementwise(outs[0], x, w, c1, c2, rs, epi, f"gemm_ln bench {M}x{N}x{C} epi{epi}", rows=rows, idx=idx)
 
 
 @pytest.mark.parametrize("rows,C", [(300, 320), (77, 640), (1024, 1280)])
@@ -564,11 +661,13 @@ def test_layernorm(sdlib, rows, C):
     x = r16(torch.randn(rows, C, generator=g) * 3 + 1)
     gamma, beta = torch.randn(C, generator=g), torch.randn(C, generator=g)
     ref = F.layer_norm(x, (C,), gamma, beta, 1e-5)
-    out = torch.full((rows, C), float("nan"), device="cuda", dtype=torch.bfloat16)
-    _lib.check(sdlib.sd_op_layernorm(stream(), P(x, torch.bfloat16), P(gamma),
-                                     P(beta), P(out), rows, C, 1e-5))
+    out = OUT((rows, C))
+    _lib.check(sdlib.sd_op_layernorm(stream(), P(G(x, torch.bfloat16)), P(G(gamma)),
+                                     P(G(beta)), P(out), rows, C, 1e-5))
     torch.cuda.synchronize()
+    check_guards()
     assert rel_l2(out, ref) < TOL
+    assert_elementwise(out, *norm_ref_bound(x, gamma, beta, C, 1e-5, False), f"layernorm {rows}x{C}", ("row", "c"))
 
 
 @pytest.mark.parametrize("B,heads,Nq,Nk,D,spike", [
@@ -597,14 +696,18 @@ def test_attention(sdlib, B, heads, Nq, Nk, D, spike):
     vh = v.view(B, Nk, heads, D).transpose(1, 2)
     ref = F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(B, Nq, C)
     # pack K|V side by side like the fused projections do
-    kv = dev(torch.cat([k, v], dim=-1).contiguous(), torch.bfloat16)
-    qd = dev(q, torch.bfloat16)
-    out = torch.full((B, Nq, C), float("nan"), device="cuda", dtype=torch.bfloat16)
+    kv = G(torch.cat([k, v], dim=-1).contiguous(), torch.bfloat16)
+    qd = G(q, torch.bfloat16)
+    out = OUT((B, Nq, C))
     kvp = P(kv)
     _lib.check(sdlib.sd_op_attention(stream(), P(qd), C, kvp, 2 * C, kvp + 2 * C, 2 * C, P(out), C, B,
                                      heads, Nq, Nk, D, 1.0 / math.sqrt(D)))
     torch.cuda.synchronize()
+    check_guards()
     assert rel_l2(out, ref) < 1e-2   # P is rounded to bf16 before PV
+    attention_elementwise(out, q, k, v, heads, D, f"attention B={B} {Nq}x{Nk} d{D}")
+
+
 
 
 @pytest.mark.parametrize("Nk,spikes", [(512, ((70, 6.0), (300, 14.0), (509, 40.0))), (1024, ((5, 30.0), (640, 3.0))),
@@ -623,14 +726,16 @@ def test_attention_pipelined_kernel_moves_its_stale_reference(sdlib, Nk, spikes)
         k[:, pos] = r16(k[:, pos] * f)
     qh, kh, vh = (t.view(B, -1, heads, D).transpose(1, 2) for t in (q, k, v))
     ref = F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(B, Nq, C)
-    kv = dev(torch.cat([k, v], dim=-1).contiguous(), torch.bfloat16)
-    out = torch.full((B, Nq, C), float("nan"), device="cuda", dtype=torch.bfloat16)
+    kv = G(torch.cat([k, v], dim=-1).contiguous(), torch.bfloat16)
+    out = OUT((B, Nq, C))
     kvp = P(kv)
-    _lib.check(sdlib.sd_op_attention(stream(), P(dev(q, torch.bfloat16)), C, kvp, 2 * C, kvp + 2 * C, 2 * C, P(out), C, B,
+    _lib.check(sdlib.sd_op_attention(stream(), P(G(q, torch.bfloat16)), C, kvp, 2 * C, kvp + 2 * C, 2 * C, P(out), C, B,
                                      heads, Nq, Nk, D, 1.0 / math.sqrt(D)))
     torch.cuda.synchronize()
+    check_guards()
     assert torch.isfinite(out.float()).all()
     assert rel_l2(out, ref) < 1e-2
+    attention_elementwise(out, q, k, v, heads, D, f"attention stale-reference Nk={Nk}")
 
 
 def _dominant_key_case(g, B, heads, D, Nq, Nk, spikes):
@@ -673,14 +778,16 @@ def test_attention_running_maximum_survives_dominant_keys_in_either_lane_half(sd
     for pos, _ in spikes:                                          # the construction really produces the jumps it claims
         assert (s[..., pos] - s[..., :pos].amax(-1)).min() > 150.0
     ref = F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(B, Nq, C)
-    kv = dev(torch.cat([k, v], dim=-1).contiguous(), torch.bfloat16)
-    out = torch.full((B, Nq, C), float("nan"), device="cuda", dtype=torch.bfloat16)
+    kv = G(torch.cat([k, v], dim=-1).contiguous(), torch.bfloat16)
+    out = OUT((B, Nq, C))
     kvp = P(kv)
-    _lib.check(sdlib.sd_op_attention(stream(), P(dev(q, torch.bfloat16)), C, kvp, 2 * C, kvp + 2 * C, 2 * C, P(out), C, B,
+    _lib.check(sdlib.sd_op_attention(stream(), P(G(q, torch.bfloat16)), C, kvp, 2 * C, kvp + 2 * C, 2 * C, P(out), C, B,
                                      heads, Nq, Nk, D, scale))
     torch.cuda.synchronize()
+    check_guards()
     assert torch.isfinite(out.float()).all()
     assert rel_l2(out, ref) < 1e-2
+    attention_elementwise(out, q, k, v, heads, D, f"attention dominant keys d{D} Nk={Nk}")
 
 
 def test_clip_attention_with_a_dominant_bos_key(sdlib):
@@ -690,10 +797,12 @@ def test_clip_attention_with_a_dominant_bos_key(sdlib):
     B, L, heads, D = 2, 77, 12, 64
     H = heads * D
     q, k, v = _dominant_key_case(g, B, heads, D, L, L, ((0, 40.0),))
-    qkv = dev(torch.cat([q, k, v], dim=-1).contiguous(), torch.bfloat16)
-    out = torch.full((B * L, H), float("nan"), device="cuda", dtype=torch.bfloat16)
+    qkv = G(torch.cat([q, k, v], dim=-1).contiguous(), torch.bfloat16)
+    out = OUT((B * L, H))
     _lib.check(sdlib.sd_op_clip_attention(stream(), P(qkv), P(out), B, L, H, heads))
     torch.cuda.synchronize()
+    check_guards()
+    attention_elementwise(out, q, k, v, heads, D, "attention clip causal", causal=True)
     qh, kh, vh = (t.view(B, L, heads, D).transpose(1, 2) for t in (q, k, v))
     ref = F.scaled_dot_product_attention(qh, kh, vh, is_causal=True).transpose(1, 2).reshape(B * L, H)
     assert torch.isfinite(out.float()).all()
@@ -709,27 +818,36 @@ def test_qkv_projection_and_attention_head_major(sdlib):
     x = r16(torch.randn(M, C, generator=g))
     w = r16(torch.randn(3 * C, C, generator=g) / math.sqrt(C))
     qkv = r16(x @ w.t())
-    q = torch.full((M, C), float("nan"), device="cuda", dtype=torch.bfloat16)
-    kv = torch.full((2, B, H, N, D), float("nan"), device="cuda", dtype=torch.bfloat16)
-    _lib.check(sdlib.sd_op_gemm_qkv_headmajor(stream(), P(x, torch.bfloat16), C, P(w, torch.bfloat16), P(q), P(kv), M, C, N, C))
+    q = OUT((M, C))
+    kv = OUT((2, B, H, N, D))
+    _lib.check(sdlib.sd_op_gemm_qkv_headmajor(stream(), P(G(x, torch.bfloat16)), C, P(G(w, torch.bfloat16)), P(q), P(kv), M, C, N, C))
     torch.cuda.synchronize()
     assert rel_l2(q, qkv[:, :C]) < TOL
     for which in (0, 1):
         want = qkv[:, (1 + which) * C:(2 + which) * C].view(B, N, H, D).permute(0, 2, 1, 3)
         assert rel_l2(kv[which], want) < TOL
-    out = torch.full((B, N, C), float("nan"), device="cuda", dtype=torch.bfloat16)
-    _lib.check(sdlib.sd_op_attention_headmajor(stream(), P(q), C, P(kv[0]), P(kv[1]), P(out), C, B, H, N, N, D, 1.0 / math.sqrt(D)))
+    r64, b64 = gemm_bound(x, w)
+    assert_elementwise(q, r64[:, :C], b64[:, :C], "gemm qkv head-major q", ("row", "col"))
+    for which in (0, 1):
+        sl = slice((1 + which) * C, (2 + which) * C)
+        assert_elementwise(kv[which], r64[:, sl].reshape(B, N, H, D).permute(0, 2, 1, 3), b64[:, sl].reshape(B, N, H, D).permute(0, 2, 1, 3),
+                           f"gemm qkv head-major {'kv'[which]}", ("b", "head", "token", "d"))
+    out = OUT((B, N, C))
+    # K and V each in their own poisoned allocation (an over-read of K must not land in V)
+    _lib.check(sdlib.sd_op_attention_headmajor(stream(), P(q), C, P(G(kv[0])), P(G(kv[1])), P(out), C, B, H, N, N, D, 1.0 / math.sqrt(D)))
     torch.cuda.synchronize()
     qh = q.float().cpu().view(B, N, H, D).transpose(1, 2)
     ref = F.scaled_dot_product_attention(qh, kv[0].float().cpu(), kv[1].float().cpu()).transpose(1, 2).reshape(B, N, C)
     assert rel_l2(out, ref) < 1e-2   # P is rounded to bf16 before PV
     # and the token-major call on the same data gives the same result bit for bit (only the DMA source addresses differ)
-    ktm = kv[0].permute(0, 2, 1, 3).reshape(B, N, C).contiguous()
-    vtm = kv[1].permute(0, 2, 1, 3).reshape(B, N, C).contiguous()
-    out2 = torch.full_like(out, float("nan"))
+    ktm = G(kv[0].permute(0, 2, 1, 3).reshape(B, N, C).contiguous())
+    vtm = G(kv[1].permute(0, 2, 1, 3).reshape(B, N, C).contiguous())
+    out2 = OUT((B, N, C))
     _lib.check(sdlib.sd_op_attention(stream(), P(q), C, P(ktm), C, P(vtm), C, P(out2), C, B, H, N, N, D, 1.0 / math.sqrt(D)))
     torch.cuda.synchronize()
+    check_guards()
     assert torch.equal(out, out2)
+    attention_elementwise(out, q.view(B, N, C), ktm, vtm, H, D, "attention head-major 2x4096 d40")
 
 
 def test_conv_in_out(sdlib):
@@ -739,22 +857,28 @@ def test_conv_in_out(sdlib):
     w = torch.randn(C, 4, 3, 3, generator=g) / 6
     b = torch.randn(C, generator=g)
     ref = F.conv2d(torch.cat([x, x]), w, b, padding=1)
-    wt = dev(w.reshape(C, 36).t().contiguous())
-    out = torch.full((B, H, H, C), float("nan"), device="cuda", dtype=torch.bfloat16)
-    _lib.check(sdlib.sd_op_conv_in(stream(), P(x), Bs, P(wt), P(b), P(out), B, H, H, 4, C))
+    wt = G(w.reshape(C, 36).t().contiguous())
+    out = OUT((B, H, H, C))
+    _lib.check(sdlib.sd_op_conv_in(stream(), P(G(x)), Bs, P(wt), P(G(b)), P(out), B, H, H, 4, C))
     torch.cuda.synchronize()
+    check_guards()
     assert rel_l2(out.permute(0, 3, 1, 2), ref) < TOL
+    r64, m64 = conv3x3_nhwc_ref(torch.cat([x, x]), w, b)          # fp32 inputs and weights: fp32 products (one more rounding)
+    assert_elementwise(out, r64, linear_bound(r64, m64, 2 * 36 + 1), "conv_in", NHWC)
     # conv_out
     y = r16(torch.randn(B, C, H, H, generator=g))
     w2 = r16(torch.randn(4, C, 3, 3, generator=g) / math.sqrt(9 * C))
     b2 = torch.randn(4, generator=g)
     ref2 = F.conv2d(y, w2, b2, padding=1)
-    yd = dev(y.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
-    wp = dev(w2.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
-    out2 = torch.full((B, 4, H, H), float("nan"), device="cuda")
-    _lib.check(sdlib.sd_op_conv_out(stream(), P(yd), P(wp), P(b2), P(out2), B, H, H, C, 4))
+    yd = G(y.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
+    wp = G(w2.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
+    out2 = OUT((B, 4, H, H), torch.float32)
+    _lib.check(sdlib.sd_op_conv_out(stream(), P(yd), P(wp), P(G(b2)), P(out2), B, H, H, C, 4))
     torch.cuda.synchronize()
+    check_guards()
     assert rel_l2(out2, ref2) < 1e-5
+    r64, m64 = conv3x3_nhwc_ref(y, w2, b2)
+    assert_elementwise(out2.permute(0, 2, 3, 1), r64, linear_bound(r64, m64, 9 * C + 1, torch.float32), "conv_out", NHWC)
 
 
 @pytest.mark.parametrize("B,H,W,C,Cout", [
@@ -768,12 +892,16 @@ def test_conv_out_matrix_core_kernel(sdlib, B, H, W, C, Cout):
     w2 = r16(torch.randn(Cout, C, 3, 3, generator=g) / math.sqrt(9 * C))
     b2 = torch.randn(Cout, generator=g)
     ref = F.conv2d(y, w2, b2, padding=1)
-    yd = dev(y.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
-    wp = dev(w2.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
-    out = torch.full((B, Cout, H, W), float("nan"), device="cuda")
-    _lib.check(sdlib.sd_op_conv_out(stream(), P(yd), P(wp), P(b2), P(out), B, H, W, C, Cout))
+    yd = G(y.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
+    wp = G(w2.permute(0, 2, 3, 1).contiguous(), torch.bfloat16)
+    out = OUT((B, Cout, H, W), torch.float32)
+    _lib.check(sdlib.sd_op_conv_out(stream(), P(yd), P(wp), P(G(b2)), P(out), B, H, W, C, Cout))
     torch.cuda.synchronize()
+    check_guards()
     assert rel_l2(out, ref) < 1e-5
+    r64, m64 = conv3x3_nhwc_ref(y, w2, b2)
+    assert_elementwise(out.permute(0, 2, 3, 1), r64, linear_bound(r64, m64, 9 * C + 1, torch.float32),
+                       f"conv_out matrix-core B={B} {H}x{W} {C}->{Cout}", NHWC)
 
 
 def test_time_embedding(sdlib):
@@ -785,13 +913,25 @@ def test_time_embedding(sdlib):
         f = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32) / half)
         emb = torch.cat([torch.cos(t * f), torch.sin(t * f)])
         ref = F.linear(F.silu(F.linear(emb, w1, b1)), w2, b2)
-        scratch = torch.zeros(320 + 1280, device="cuda")
-        out = torch.zeros(1280, device="cuda")
-        _lib.check(sdlib.sd_op_time_embedding(stream(), t, P(w1, torch.bfloat16), P(b1),
-                                              P(w2, torch.bfloat16), P(b2), P(scratch),
+        scratch = OUT((320 + 1280,), torch.float32)
+        out = OUT((1280,), torch.float32)
+        _lib.check(sdlib.sd_op_time_embedding(stream(), t, P(G(w1, torch.bfloat16)), P(G(b1)),
+                                              P(G(w2, torch.bfloat16)), P(G(b2)), P(scratch),
                                               P(out), 320, 1280))
         torch.cuda.synchronize()
+        check_guards()
         assert rel_l2(out, ref) < 1e-4
+        # each stage from the kernel's own stored intermediate: sinusoid (fp32 expf of the frequency exponent, t f rounded,
+        # cosf / sinf: <= 16 u |t f| of phase + 2^-21), GEMV + bias, SiLU (a few ulp) + GEMV + bias
+        fd = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float64) / half)
+        e64 = torch.cat([torch.cos(t * fd), torch.sin(t * fd)])
+        assert_elementwise(scratch[:320], e64, 16 * U32 * t * torch.cat([fd, fd]) + 2.0 ** -21, f"time embedding sinusoid t={t}")
+        emb_k, h_k = scratch[:320].double().cpu(), scratch[320:].double().cpu()
+        r1, m1 = gemm_ref(emb_k[None], w1, b1)
+        assert_elementwise(scratch[320:], r1[0], linear_bound(r1[0], m1[0], 321, torch.float32), f"time embedding linear_1 t={t}")
+        sh = F.silu(h_k)
+        r2, m2 = gemm_ref(sh[None], w2, b2)
+        assert_elementwise(out, r2[0], linear_bound(r2[0], m2[0], 1281 + 8, torch.float32), f"time embedding linear_2 t={t}")
 
 
 def test_sched_step_kernel(sdlib):
@@ -817,6 +957,8 @@ def test_sched_step_kernel(sdlib):
         assert torch.allclose(got.cpu(), ref, rtol=1e-5, atol=1e-5)
 
 
+
+
 @pytest.mark.parametrize("B,rows,N,K,epi", [(3, 256, 640, 320, 2), (2, 128, 320, 640, 0), (4, 1024, 640, 640, 2)])
 def test_gemm_batched_weights_and_grouped_softmax(sdlib, B, rows, N, K, epi):
     """Per-sample W (+ residual / bias) and the softmax-over-77-of-80 epilogue: the two GEMMs of the folded
@@ -836,13 +978,24 @@ def test_gemm_batched_weights_and_grouped_softmax(sdlib, B, rows, N, K, epi):
         bias = torch.randn(N, generator=g)
         res = r16(torch.randn(B * rows, N, generator=g))
         ref = ref.reshape(B * rows, N) + bias + res
-    out = torch.full((B * rows, N), float("nan"), device="cuda", dtype=torch.bfloat16)
-    _lib.check(sdlib.sd_op_gemm_batched(stream(), P(x, torch.bfloat16), K, P(w, torch.bfloat16), N * K, rows,
-                                        P(bias) if bias is not None else None,
-                                        P(res, torch.bfloat16) if res is not None else None, N, P(out), N,
+    out = OUT((B * rows, N))
+    _lib.check(sdlib.sd_op_gemm_batched(stream(), P(G(x, torch.bfloat16)), K, P(G(w, torch.bfloat16)), N * K, rows,
+                                        P(G(bias)) if bias is not None else None,
+                                        P(G(res, torch.bfloat16)) if res is not None else None, N, P(out), N,
                                         B * rows, N, K, epi, 77 if epi else 0))
     torch.cuda.synchronize()
+    check_guards()
     assert rel_l2(out, ref) < TOL
+    s64 = torch.einsum("brk,bnk->brn", xb.double(), w.double())
+    m64 = torch.einsum("brk,bnk->brn", xb.double().abs(), w.double().abs())
+    if epi == 2:
+        grouped_softmax_elementwise(out, s64.reshape(B * rows, N), U32 * K * m64.reshape(B * rows, N), 77,
+                                     f"gemm batched softmax B={B} rows={rows} K={K}")
+    else:
+        r64 = s64.reshape(B * rows, N) + bias.double() + res.double()
+        m64 = m64.reshape(B * rows, N) + bias.double().abs() + res.double().abs()
+        assert_elementwise(out, r64, linear_bound(r64, m64, K + 2), f"gemm batched B={B} rows={rows} {N}x{K}", ("row", "col"))
+
     if epi == 2:
         o = out.float().view(B * rows, N // 80, 80)
         assert (o[..., 77:] == 0).all() and (o.sum(-1) - 1).abs().max() < 2e-2
@@ -872,15 +1025,23 @@ def test_gemm_per_sample_softmax_with_layernorm_folded(sdlib, B, rows, C, offset
     ref = torch.zeros_like(S)
     ref[..., :L] = torch.softmax(S[..., :L], dim=-1)
     ref = ref.view(M, N).float()
-    out = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
-    _lib.check(sdlib.sd_op_gemm_batched_softmax_ln(stream(), P(x, torch.bfloat16), C, P(wln, torch.bfloat16), N * C, rows, P(out), N,
-                                                   M, N, C, L, P(rs), parts, P(c1), P(c2), 1e-5))
+    out = OUT((M, N))
+    _lib.check(sdlib.sd_op_gemm_batched_softmax_ln(stream(), P(G(x, torch.bfloat16)), C, P(G(wln, torch.bfloat16)), N * C, rows,
+                                                   P(out), N, M, N, C, L, P(G(rs)), parts, P(G(c1)), P(G(c2)), 1e-5))
     torch.cuda.synchronize()
+    check_guards()
+    tot = rs.double().sum(0)
+    zs, dzs = zip(*(ln_fold_ref_bound(x[b * rows:(b + 1) * rows], wln[b], c1[b], c2[b], tot[b * rows:(b + 1) * rows, 0],
+                                      tot[b * rows:(b + 1) * rows, 1], 1e-5) for b in range(B)))
+    grouped_softmax_elementwise(out, torch.cat(zs), torch.cat(dzs), L, f"gemm batched softmax+ln B={B} rows={rows} C={C}")
     e = rel_l2(out, ref)
     print(f"softmax GEMM + norm2 B={B} rows={rows} C={C} offset={offset}: {e:.3e}")
     assert e < 1e-2                               # (bf16 rounding of the centred operand and of the probabilities)
     o = out.float().view(M, N // 80, 80)
     assert (o[..., L:] == 0).all() and (o.sum(-1) - 1).abs().max() < 2e-2
+
+
+
 
 
 @pytest.mark.parametrize("B,hw,C,spike", [(2, 256, 320, False), (1, 1024, 640, True), (3, 128, 1280, False), (2, 4096, 320, False),
@@ -938,9 +1099,9 @@ def test_xattn_fused(sdlib, B, hw, C, spike):
     # tiled operand layouts (one contiguous KiB per 16-row x 64-byte DMA piece): A^T [C/32][640][32], Bw [C/32][20][32][32]
     At_t = At.view(B, H * 80, C // 32, 32).permute(0, 2, 1, 3).contiguous()
     Bw_t = Bw.view(B, C // 32, 32, 20, 32).permute(0, 1, 3, 2, 4).contiguous()
-    out = torch.full((M, C), float("nan"), device="cuda", dtype=torch.bfloat16)
-    _lib.check(sdlib.sd_op_xattn_fused(stream(), P(x, torch.bfloat16), P(r, torch.bfloat16), P(out), P(At_t, torch.bfloat16),
-                                       P(Bw_t, torch.bfloat16), P(bo), M, C, hw, L))
+    xd_, rd_, Ad_, Bd_, bod = G(x, torch.bfloat16), G(r, torch.bfloat16), G(At_t, torch.bfloat16), G(Bw_t, torch.bfloat16), G(bo)
+    out = OUT((M, C))
+    _lib.check(sdlib.sd_op_xattn_fused(stream(), P(xd_), P(rd_), P(out), P(Ad_), P(Bd_), P(bod), M, C, hw, L))
     torch.cuda.synchronize()
     e1, e2 = rel_l2(out, ref_fold), rel_l2(out, ref_attn)
     print(f"xattn fused B={B} hw={hw} C={C}: vs folded fp32 {e1:.3e}, vs SDPA + linears {e2:.3e}")
@@ -948,12 +1109,16 @@ def test_xattn_fused(sdlib, B, hw, C, spike):
     assert e1 < 8e-3 and e2 < 2e-2
     # the same launch also delivers the LayerNorm partials of its stored rows (norm3 folded into the GEGLU projection)
     parts = sdlib.sd_op_ln_partials(1, M, C)
-    rs = torch.full((parts, M, 2), float("nan"), device="cuda")
-    out2 = torch.full_like(out, float("nan"))
-    _lib.check(sdlib.sd_op_xattn_fused_rowstats(stream(), P(x, torch.bfloat16), P(r, torch.bfloat16), P(out2), P(At_t, torch.bfloat16),
-                                                P(Bw_t, torch.bfloat16), P(bo), M, C, hw, L, P(rs)))
+    rs = OUT((parts, M, 2), torch.float32)
+    out2 = OUT((M, C))
+    _lib.check(sdlib.sd_op_xattn_fused_rowstats(stream(), P(xd_), P(rd_), P(out2), P(Ad_), P(Bd_), P(bod), M, C, hw, L, P(rs)))
     torch.cuda.synchronize()
+    check_guards()
     assert torch.equal(out2, out)
+    sel = sample_rows(B, hw)
+    x64, A64 = x.double().view(B, hw, C)[sel], At.double()[sel]
+    xattn_elementwise(out.view(B, hw, C)[sel], torch.einsum("bmc,bkc->bmk", x64, A64), torch.einsum("bmc,bkc->bmk", x64.abs(), A64.abs()),
+                       U32 * (C + 2), Bn[sel], r.view(B, hw, C)[sel], bo, L, f"xattn fused B={B} hw={hw} C={C}")
     tot = rs.sum(0).cpu()
     o64 = out.double().cpu()
     assert torch.allclose(tot[:, 0].double(), o64.sum(1), rtol=1e-4, atol=1e-2)
@@ -1020,15 +1185,78 @@ def test_xattn_fused_with_norm2_folded(sdlib, B, hw, C, offset, dup):
     Bw[:, :, perm] = Bn.transpose(1, 2)
     At_t = At_ln.view(B, H * 80, C // 32, 32).permute(0, 2, 1, 3).contiguous()
     Bw_t = Bw.view(B, C // 32, 32, 20, 32).permute(0, 1, 3, 2, 4).contiguous()
-    out = torch.full((M, C), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = OUT((M, C))
     oparts = sdlib.sd_op_ln_partials(1, M, C)
-    ors = torch.full((oparts, M, 2), float("nan"), device="cuda")
-    _lib.check(sdlib.sd_op_xattn_fused_ln(stream(), P(x, torch.bfloat16), P(r, torch.bfloat16), P(out), P(At_t, torch.bfloat16),
-                                          P(Bw_t, torch.bfloat16), P(bo), M, C, hw, L, P(rs), parts, Mu, P(c2), 1e-5, P(ors)))
+    ors = OUT((oparts, M, 2), torch.float32)
+    _lib.check(sdlib.sd_op_xattn_fused_ln(stream(), P(G(x, torch.bfloat16)), P(G(r, torch.bfloat16)), P(out), P(G(At_t, torch.bfloat16)),
+                                          P(G(Bw_t, torch.bfloat16)), P(G(bo)), M, C, hw, L, P(G(rs)), parts, Mu, P(G(c2)), 1e-5, P(ors)))
     torch.cuda.synchronize()
+    check_guards()
+    xattn_norm2_elementwise(out, x, At_ln, c2, rs, Bn, r, bo, L, B, hw, C, Mu, f"xattn fused+norm2 B={B} hw={hw} C={C}")
     e1, e2 = rel_l2(out, ref_fold), rel_l2(out, ref_attn)
     print(f"xattn fused + norm2 B={B} hw={hw} C={C} offset={offset}: vs folded fp64 {e1:.3e}, vs LayerNorm + SDPA + linears {e2:.3e}")
     assert torch.isfinite(out.float()).all()
     assert e1 < 8e-3 and e2 < 2e-2
     tot = ors.sum(0).cpu()
     assert torch.allclose(tot[:, 0].double(), out.double().cpu().sum(1), rtol=1e-4, atol=1e-2)
+
+
+@pytest.mark.parametrize("form,hw,M,pad", [
+    ("v_t", 4096, 512, 64),        # V^T[C, hw] = Wv . g_img^T: M = C = 512, N = hw, ldc = hw (+ a gap here)
+    ("s", 4096, 1000, 32),         # S = Q K^T from the packed q|k rows: ldx = 2C, a ragged query chunk
+    ("s", 16384, 200, 32),         # ... 128 x 128 latent: N = hw = 16384
+    ("pv", 4096, 1000, 64),        # O[q0 : q0 + rows] = P V + b_v: ldx = hw (+ gap), written at a row offset (coff)
+    ("pv", 16384, 200, 64),
+])
+def test_gemm_strided_and_offset_operands_of_the_chunked_vae_attention(sdlib, form, hw, M, pad):
+    """The chunked VAE mid-block attention (csrc/unet.hip, vae_attention) runs its three GEMMs on row-strided operands and
+    writes at an offset into a bigger tensor.  Here every stride is wider than its rows (ldx > K1, ldx2 > K - K1, ldr > N,
+    ldc > N): the gap columns are sentinel-filled and must stay so, rows of the output tensor before and after the written
+    block must stay NaN, operands are read only inside their rows (NaN-poisoned gaps), and every element meets its bound."""
+    C = 512
+    g = torch.Generator().manual_seed(hw + M + pad)
+    if form == "v_t":
+        N, K, K1 = hw, C, C
+        x = r16(torch.randn(M, K, generator=g) / math.sqrt(C))
+        w = r16(torch.randn(N, K, generator=g))
+        b = None
+        ldx, ldx2 = K + pad, 0
+    elif form == "s":
+        N, K, K1 = hw, C, C // 2                          # the K range split over X / X2, both rows of the q|k buffer
+        x = r16(torch.randn(M, K, generator=g))
+        w = r16(torch.randn(N, K, generator=g) / math.sqrt(C))
+        b = None
+        ldx, ldx2 = 2 * C, 2 * C
+    else:
+        N, K, K1 = C, hw, hw
+        x = r16(torch.softmax(torch.randn(M, K, generator=g) * 3, -1))
+        w = r16(torch.randn(N, K, generator=g))
+        b = torch.randn(N, generator=g)
+        ldx, ldx2 = K + pad, 0
+    res = r16(torch.randn(M, N, generator=g)) if form == "s" else None
+    ldr, ldc = N + pad, N + pad
+    # X (and X2) as column blocks of a row-strided buffer; poison in the gaps
+    xbuf = G(torch.cat([x[:, :K1], torch.zeros(M, ldx - K1)], 1) if ldx > K1 else x[:, :K1], torch.bfloat16, ld=None)
+    x1 = xbuf[:, :K1]
+    x2 = None
+    if K1 < K:
+        x2buf = G(torch.cat([x[:, K1:], torch.zeros(M, ldx2 - (K - K1))], 1), torch.bfloat16)
+        x2 = x2buf[:, :K - K1]
+        for t, lo in ((xbuf, K1), (x2buf, K - K1)):
+            t[:, lo:] = float("nan")
+    elif ldx > K1:
+        xbuf[:, K1:] = float("nan")
+    rd = G(res, torch.bfloat16, ld=ldr) if res is not None else None
+    row0, total = 37, M + 37 + 11                          # the output block sits at a row offset inside a bigger tensor
+    outbuf = OUT((total, N), ld=ldc)
+    out = outbuf[row0:row0 + M]
+    _lib.check(sdlib.sd_op_gemm(stream(), P(x1), ldx, P(x2) if x2 is not None else None, ldx2, K1, P(G(w, torch.bfloat16)),
+                                P(G(b)) if b is not None else None, None, P(rd) if rd is not None else None, ldr, P(out), ldc,
+                                M, N, K, 0))
+    torch.cuda.synchronize()
+    check_guards()
+    around = torch.cat([outbuf[:row0], outbuf[row0 + M:]]).view(torch.int16)
+    assert (around == torch.tensor(0x7FC0, dtype=torch.int16)).all(), "rows outside the written block were stored"
+    ref, bound = gemm_bound(x, w, b, None, res)
+    assert rel_l2(out, ref) < TOL
+    assert_elementwise(out, ref, bound, f"gemm strided {form} hw={hw} M={M}", ("row", "col"))

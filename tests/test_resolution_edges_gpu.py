@@ -18,6 +18,12 @@ pytestmark = pytest.mark.gpu
 
 from sonicdiffusionbayeslab_amd import _lib
 from tests.util import cosine, oracle_cfg, rel_l2
+from tests.bounds import (ATOL_TINY, U32, NHWC, assert_e4m3_codes, assert_elementwise, attention_elementwise, check_guards,
+                          conv3x3_nhwc_ref, conv_gn_elementwise, device_operand, forget_guards, fp8_conv_ref,
+                          fp8_gemm_ref_bound, geglu_ref_bound, gemm_bound, grouped_softmax_elementwise, guarded,
+                          guarded_input, linear_bound, ln_fold_elementwise, ln_fold_ref_bound, norm_ref_bound, sample_rows,
+                          softmax_rows_ref_bound, softmax_rows_elementwise, subpixel_ref, ulp_bf16,
+                          xattn_elementwise, xattn_norm2_elementwise)
 
 OP_TOL = 6e-3                     # test_ops_gpu.py / test_fp8_gpu.py: one kernel, bf16 output rounding
 ATTN_TOL = 1e-2                   # test_ops_gpu.py::test_attention: P rounded to bf16 before PV
@@ -35,8 +41,7 @@ def P(t, dtype=None):
     """Upload (if needed) and return the device pointer, keeping the tensor alive until the test ends."""
     if t is None:
         return None
-    if t.device.type != "cuda" or (dtype is not None and t.dtype != dtype):
-        t = t.to("cuda", dtype=dtype) if dtype else t.to("cuda")
+    t = device_operand(t, dtype)                  # guarded buffers as they are, anything else into a guarded copy
     _KEEP.append(t)
     return t.data_ptr()
 
@@ -46,6 +51,7 @@ def _drop_keep():
     yield
     torch.cuda.synchronize()
     _KEEP.clear()
+    check_guards()              # every guard of every operand and output of the test (tests/bounds.py)
 
 
 def r16(t):
@@ -114,7 +120,7 @@ def test_attention_at_odd_level_token_counts(sdlib, B, Nq, Nk, D, spikes):
             assert (s[..., pos] - s[..., :pos].amax(-1)).min() > 150.0
     ref = F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(B, Nq, C)
     kv = torch.cat([k, v], dim=-1).contiguous().to("cuda", torch.bfloat16)
-    out = torch.full((B, Nq, C), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((B, Nq, C), torch.bfloat16)
     kvp = P(kv)
     _lib.check(sdlib.sd_op_attention(stream(), P(q, torch.bfloat16), C, kvp, 2 * C, kvp + 2 * C, 2 * C, P(out), C, B,
                                      heads, Nq, Nk, D, 1.0 / math.sqrt(D)))
@@ -122,6 +128,7 @@ def test_attention_at_odd_level_token_counts(sdlib, B, Nq, Nk, D, spikes):
     err = rel_l2(out, ref)
     print(f"attention B={B} Nq={Nq} Nk={Nk} d={D} spikes={len(spikes)}: rel-L2 {err:.3e}")
     assert torch.isfinite(out.float()).all() and err < ATTN_TOL
+    attention_elementwise(out, q, k, v, heads, D, f"attention odd tokens B={B} {Nq}x{Nk} d{D} spikes={len(spikes)}")
 
 
 @pytest.mark.parametrize("B,N,Nk,D", [(2, 25, 25, 160), (2, 140, 140, 160), (2, 140, 77, 160), (2, 560, 560, 80), (2, 1008, 1008, 80),
@@ -138,7 +145,7 @@ def test_attention_moderate_key_spike_in_the_ragged_last_tile(sdlib, B, N, Nk, D
     qh, kh, vh = (t.view(B, -1, heads, D).transpose(1, 2) for t in (q, k, v))
     ref = F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(B, N, C)
     kv = torch.cat([k, v], dim=-1).contiguous().to("cuda", torch.bfloat16)
-    out = torch.full((B, N, C), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((B, N, C), torch.bfloat16)
     kvp = P(kv)
     _lib.check(sdlib.sd_op_attention(stream(), P(q, torch.bfloat16), C, kvp, 2 * C, kvp + 2 * C, 2 * C, P(out), C, B,
                                      heads, N, Nk, D, 1.0 / math.sqrt(D)))
@@ -146,6 +153,7 @@ def test_attention_moderate_key_spike_in_the_ragged_last_tile(sdlib, B, N, Nk, D
     err = rel_l2(out, ref)
     print(f"attention, key {Nk - 3} x6, B={B} Nq={N} Nk={Nk} d={D}: rel-L2 {err:.3e}")
     assert torch.isfinite(out.float()).all() and err < ATTN_TOL
+    attention_elementwise(out, q, k, v, heads, D, f"attention ragged-tile spike B={B} {N}x{Nk} d{D}")
 
 
 # ------------------------------------------------------------------------------------------ head-major q|k|v
@@ -160,27 +168,36 @@ def test_qkv_projection_and_attention_head_major_at_non_power_of_two_tokens(sdli
     x = r16(torch.randn(M, C, generator=g))
     w = r16(torch.randn(3 * C, C, generator=g) / math.sqrt(C))
     qkv = r16(x @ w.t())
-    q = torch.full((M, C), float("nan"), device="cuda", dtype=torch.bfloat16)
-    kv = torch.full((2, B, H, N, D), float("nan"), device="cuda", dtype=torch.bfloat16)
+    q = guarded((M, C), torch.bfloat16)
+    kv = guarded((2, B, H, N, D), torch.bfloat16)
     _lib.check(sdlib.sd_op_gemm_qkv_headmajor(stream(), P(x, torch.bfloat16), C, P(w, torch.bfloat16), P(q), P(kv), M, C, N, C))
     torch.cuda.synchronize()
     eq = rel_l2(q, qkv[:, :C])
     ekv = [rel_l2(kv[which], qkv[:, (1 + which) * C:(2 + which) * C].view(B, N, H, D).permute(0, 2, 1, 3)) for which in (0, 1)]
-    out = torch.full((B, N, C), float("nan"), device="cuda", dtype=torch.bfloat16)
-    _lib.check(sdlib.sd_op_attention_headmajor(stream(), P(q), C, P(kv[0]), P(kv[1]), P(out), C, B, H, N, N, D, 1.0 / math.sqrt(D)))
+    out = guarded((B, N, C), torch.bfloat16)
+    # K and V each in their own poisoned allocation (an over-read of K must not land in V)
+    _lib.check(sdlib.sd_op_attention_headmajor(stream(), P(q), C, P(guarded_input(kv[0])), P(guarded_input(kv[1])), P(out), C, B, H,
+                                               N, N, D, 1.0 / math.sqrt(D)))
     torch.cuda.synchronize()
     qh = q.float().cpu().view(B, N, H, D).transpose(1, 2)
     ref = F.scaled_dot_product_attention(qh, kv[0].float().cpu(), kv[1].float().cpu()).transpose(1, 2).reshape(B, N, C)
     ea = rel_l2(out, ref)
     print(f"head-major q|k|v B={B} tokens={N}: q {eq:.3e} k {ekv[0]:.3e} v {ekv[1]:.3e}, attention {ea:.3e}")
     assert eq < OP_TOL and max(ekv) < OP_TOL and ea < ATTN_TOL
+    r64, b64 = gemm_bound(x, w)
+    assert_elementwise(q, r64[:, :C], b64[:, :C], f"gemm qkv head-major q B={B} N={N}", ("row", "col"))
+    for which in (0, 1):
+        sl = slice((1 + which) * C, (2 + which) * C)
+        hm = lambda t: t[:, sl].reshape(B, N, H, D).permute(0, 2, 1, 3)
+        assert_elementwise(kv[which], hm(r64), hm(b64), f"gemm qkv head-major {'kv'[which]} B={B} N={N}", ("b", "head", "token", "d"))
     # the token-major call on the same data gives the same result bit for bit
     ktm = kv[0].permute(0, 2, 1, 3).reshape(B, N, C).contiguous()
     vtm = kv[1].permute(0, 2, 1, 3).reshape(B, N, C).contiguous()
-    out2 = torch.full_like(out, float("nan"))
+    out2 = guarded(out.shape, out.dtype)
     _lib.check(sdlib.sd_op_attention(stream(), P(q), C, P(ktm), C, P(vtm), C, P(out2), C, B, H, N, N, D, 1.0 / math.sqrt(D)))
     torch.cuda.synchronize()
     assert torch.equal(out, out2)
+    attention_elementwise(out, q.view(B, N, C), ktm, vtm, H, D, f"attention head-major B={B} N={N}")
 
 
 def fold_layernorm(w, gamma, beta, bias):
@@ -193,8 +210,8 @@ def fold_layernorm(w, gamma, beta, bias):
 
 def _gemm_plan(sdlib, x, w, bias, M, N, K, ln, hm_tokens=0):
     ncols = N // 3 if hm_tokens else N
-    out = torch.full((M, ncols), float("nan"), device="cuda", dtype=torch.bfloat16)
-    kv = (torch.full((2, M // hm_tokens, ncols // 40, hm_tokens, 40), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((M, ncols), torch.bfloat16)
+    kv = (guarded((2, M // hm_tokens, ncols // 40, hm_tokens, 40), torch.bfloat16)
           if hm_tokens else None)
     ln_rs, ln_parts, ln_c1 = ln
     _lib.check(sdlib.sd_op_gemm_plan(stream(), P(x), K, None, 0, K, P(w), P(bias), None, None, N, P(out), ncols, M, N, K,
@@ -227,6 +244,7 @@ def test_gemm_plan_layernorm_fold_with_head_major_kv_at_non_power_of_two_tokens(
     q, kv = _gemm_plan(sdlib, xd, wd, c2d, M, N, C, ln, hm_tokens=tokens)
     print(f"LayerNorm-fold q|k|v, head-major K / V, B={B} tokens={tokens}: rel-L2 {err:.3e}")
     assert err < OP_TOL
+    ln_fold_elementwise(plain, h, wg, c1, c2, rs, 0, f"gemm plan ln-fold B={B} tokens={tokens}")
     assert torch.equal(q, plain[:, :C])
     for which in (0, 1):
         want = plain[:, (1 + which) * C:(2 + which) * C].reshape(B, tokens, C // 40, 40).permute(0, 2, 1, 3)
@@ -289,7 +307,7 @@ def test_xattn_fused_at_non_power_of_two_rows_per_sample(sdlib, B, hw, C):
     ref_fold = (r.view(B, hw, C) + torch.einsum("bmk,bkc->bmc", Pm, o["Bn"]) + o["bo"]).view(M, C)
     ref_attn = _sdpa_xattn(o, x.view(B, hw, C), r, B, hw, C)
     At_t, Bw_t = _tile_xattn(At, o["Bn"], B, C)
-    out = torch.full((M, C), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((M, C), torch.bfloat16)
     _lib.check(sdlib.sd_op_xattn_fused(stream(), P(x, torch.bfloat16), P(r, torch.bfloat16), P(out), P(At_t, torch.bfloat16),
                                        P(Bw_t, torch.bfloat16), P(o["bo"]), M, C, hw, o["L"]))
     torch.cuda.synchronize()
@@ -297,6 +315,10 @@ def test_xattn_fused_at_non_power_of_two_rows_per_sample(sdlib, B, hw, C):
     print(f"xattn fused B={B} hw={hw} C={C}: vs folded fp32 {e1:.3e}, vs SDPA + linears {e2:.3e}")
     assert torch.isfinite(out.float()).all()
     assert e1 < 8e-3 and e2 < 2e-2               # test_ops_gpu.py::test_xattn_fused's gates
+    sel = sample_rows(B, hw)
+    x64, A64 = x.double().view(B, hw, C)[sel], At.double()[sel]
+    xattn_elementwise(out.view(B, hw, C)[sel], torch.einsum("bmc,bkc->bmk", x64, A64), torch.einsum("bmc,bkc->bmk", x64.abs(), A64.abs()),
+                      U32 * (C + 2), o["Bn"][sel], r.view(B, hw, C)[sel], o["bo"], o["L"], f"xattn fused B={B} hw={hw} C={C}")
 
 
 @pytest.mark.parametrize("B,hw,C", XATTN_FUSED)
@@ -323,9 +345,9 @@ def test_xattn_fused_with_norm2_folded_at_non_power_of_two_rows_per_sample(sdlib
     xn = (((x.double() - mean) * rstd) * gamma.double() + beta.double()).float().view(B, hw, C)
     ref_attn = _sdpa_xattn(o, xn, r, B, hw, C)
     At_t, Bw_t = _tile_xattn(At_ln, o["Bn"], B, C)
-    out = torch.full((M, C), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((M, C), torch.bfloat16)
     oparts = sdlib.sd_op_ln_partials(1, M, C)
-    ors = torch.full((oparts, M, 2), float("nan"), device="cuda")
+    ors = guarded((oparts, M, 2), torch.float32)
     _lib.check(sdlib.sd_op_xattn_fused_ln(stream(), P(x, torch.bfloat16), P(r, torch.bfloat16), P(out), P(At_t, torch.bfloat16),
                                           P(Bw_t, torch.bfloat16), P(o["bo"]), M, C, hw, o["L"], P(rs), parts, M, P(c2), 1e-5, P(ors)))
     torch.cuda.synchronize()
@@ -333,6 +355,8 @@ def test_xattn_fused_with_norm2_folded_at_non_power_of_two_rows_per_sample(sdlib
     print(f"xattn fused + norm2 B={B} hw={hw} C={C}: vs folded fp64 {e1:.3e}, vs LayerNorm + SDPA + linears {e2:.3e}")
     assert torch.isfinite(out.float()).all()
     assert e1 < 8e-3 and e2 < 2e-2
+    xattn_norm2_elementwise(out, x, At_ln, c2, rs, o["Bn"], r, o["bo"], o["L"], B, hw, C, M,
+                            f"xattn fused+norm2 B={B} hw={hw} C={C}")
     tot = ors.sum(0).cpu()
     assert torch.allclose(tot[:, 0].double(), out.double().cpu().sum(1), rtol=1e-4, atol=1e-2)
 
@@ -357,19 +381,26 @@ def test_fold_gemms_at_non_power_of_two_rows_per_sample(sdlib, B, rows, C):
     Pref = torch.zeros_like(S)
     Pref[..., :77] = torch.softmax(S[..., :77], dim=-1)
     Pref = Pref.view(M, NP)
-    pd = torch.full((M, NP), float("nan"), device="cuda", dtype=torch.bfloat16)
+    pd = guarded((M, NP), torch.bfloat16)
     _lib.check(sdlib.sd_op_gemm_batched(stream(), P(x, torch.bfloat16), C, P(At, torch.bfloat16), NP * C, rows, None, None, NP,
                                         P(pd), NP, M, NP, C, 2, 77))
     torch.cuda.synchronize()
     e1 = rel_l2(pd, Pref)
+    s64 = torch.einsum("brk,bnk->brn", x.double().view(B, rows, C), At.double()).reshape(M, NP)
+    m64 = torch.einsum("brk,bnk->brn", x.double().abs().view(B, rows, C), At.double().abs()).reshape(M, NP)
+    grouped_softmax_elementwise(pd, s64, U32 * C * m64, 77, f"fold gemm softmax B={B} rows={rows} C={C}")
     po = pd.float().cpu().view(M, 8, 80)
     assert (po[..., 77:] == 0).all() and (po.sum(-1) - 1).abs().max() < 2e-2
     Bt = o["Bn"].transpose(1, 2).contiguous()                                # [B, C, 640]: per-sample W of the second GEMM
-    out = torch.full((M, C), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((M, C), torch.bfloat16)
     _lib.check(sdlib.sd_op_gemm_batched(stream(), P(pd), NP, P(Bt, torch.bfloat16), C * NP, rows, P(o["bo"]), P(r, torch.bfloat16), C,
                                         P(out), C, M, C, NP, 0, 0))
     torch.cuda.synchronize()
     ref2 = (r.view(B, rows, C) + torch.einsum("brk,bck->brc", po.view(B, rows, NP), Bt) + o["bo"]).view(M, C)
+    pb, Bb = po.double().view(B, rows, NP), r16(Bt).double()               # from the kernel's own stored P
+    r64 = (torch.einsum("brk,bck->brc", pb, Bb) + r.double().view(B, rows, C) + o["bo"].double()).view(M, C)
+    m64 = (torch.einsum("brk,bck->brc", pb.abs(), Bb.abs()) + r.double().abs().view(B, rows, C) + o["bo"].double().abs()).view(M, C)
+    assert_elementwise(out, r64, linear_bound(r64, m64, NP + 2), f"fold gemm P B + R B={B} rows={rows} C={C}", ("row", "col"))
     e2 = rel_l2(out, ref2)
     e3 = rel_l2(out, _sdpa_xattn(o, x.view(B, rows, C), r, B, rows, C))
     print(f"fold GEMMs B={B} rows={rows} C={C}: P {e1:.3e}, P B + R {e2:.3e}, vs SDPA + linears {e3:.3e}")
@@ -399,13 +430,17 @@ def test_fold_softmax_gemm_with_norm2_at_non_power_of_two_rows_per_sample(sdlib,
     ref = torch.zeros_like(S)
     ref[..., :L] = torch.softmax(S[..., :L], dim=-1)
     ref = ref.view(M, N).float()
-    out = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((M, N), torch.bfloat16)
     _lib.check(sdlib.sd_op_gemm_batched_softmax_ln(stream(), P(x, torch.bfloat16), C, P(wln, torch.bfloat16), N * C, rows, P(out), N,
                                                    M, N, C, L, P(rs), parts, P(c1), P(c2), 1e-5))
     torch.cuda.synchronize()
     e = rel_l2(out, ref)
     print(f"softmax GEMM + norm2 B={B} rows={rows} C={C}: rel-L2 {e:.3e}")
     assert e < 1e-2
+    tot = rs.double().sum(0)
+    zs, dzs = zip(*(ln_fold_ref_bound(x[b * rows:(b + 1) * rows], wln[b], c1[b], c2[b], tot[b * rows:(b + 1) * rows, 0],
+                                      tot[b * rows:(b + 1) * rows, 1], 1e-5) for b in range(B)))
+    grouped_softmax_elementwise(out, torch.cat(zs), torch.cat(dzs), L, f"fold softmax+ln B={B} rows={rows} C={C}")
     o = out.float().view(M, N // 80, 80)
     assert (o[..., L:] == 0).all() and (o.sum(-1) - 1).abs().max() < 2e-2
 
@@ -423,7 +458,7 @@ def test_to_q_gemm_with_norm2_folded_at_ragged_row_counts(sdlib, M, C):
     parts = 2 * ((C + 159) // 160)
     hh = h.double().view(M, parts, C // parts)
     rs = torch.stack([hh.sum(2), (hh * hh).sum(2)], dim=2).permute(1, 0, 2).float().contiguous()
-    out = torch.full((M, C), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((M, C), torch.bfloat16)
     _lib.check(sdlib.sd_op_gemm_ln(stream(), P(h, torch.bfloat16), C, P(wg, torch.bfloat16), P(c1), P(c2), P(rs), parts, 1e-5,
                                    P(out), C, M, C, C, 0))
     torch.cuda.synchronize()
@@ -431,6 +466,7 @@ def test_to_q_gemm_with_norm2_folded_at_ragged_row_counts(sdlib, M, C):
     err = rel_l2(out, ref)
     print(f"to_q + norm2 fold M={M} C={C}: rel-L2 {err:.3e}")
     assert torch.isfinite(out.float()).all() and err < OP_TOL
+    ln_fold_elementwise(out, h, wg, c1, c2, rs, 0, f"to_q ln-fold M={M} C={C}")
 
 
 # ------------------------------------------------------------------------------------------ GroupNorm
@@ -443,11 +479,13 @@ def _gn_case(sdlib, B, HW, C1, C2, silu, eps, seed):
     if silu:
         ref = F.silu(ref)
     ref = ref.permute(0, 2, 1)
-    out = torch.full((B, HW, C), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((B, HW, C), torch.bfloat16)
     _lib.check(sdlib.sd_op_groupnorm(stream(), P(x[..., :C1].contiguous(), torch.bfloat16), C1,
                                      P(x[..., C1:].contiguous(), torch.bfloat16) if C2 else None, C2, P(gamma), P(beta), P(out),
                                      B, HW, 32, eps, silu))
     torch.cuda.synchronize()
+    assert_elementwise(out, *norm_ref_bound(x, gamma, beta, HW * C // 32, eps, silu, groups=32),
+                       f"groupnorm odd pixels B={B} HW={HW} C={C1}+{C2}", ("b", "pixel", "c"))
     return rel_l2(out, ref)
 
 
@@ -492,8 +530,8 @@ def test_conv3x3_groupnorm_deferred_splitk_reduce_at_odd_sizes(sdlib, B, H, W, C
     rd = r.permute(0, 2, 3, 1).contiguous().to("cuda", torch.bfloat16) if res else None
 
     def run():
-        y = torch.full((B, H, W, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
-        yn = torch.full_like(y, float("nan"))
+        y = guarded((B, H, W, Cout), torch.bfloat16)
+        yn = guarded(y.shape, y.dtype)
         _lib.check(sdlib.sd_op_conv3x3_groupnorm(stream(), P(xd), P(wd), P(b), P(b2), P(rd), P(y), B, H, W, Cin, Cout,
                                                  P(gamma), P(beta), P(yn), 32, 1e-5, 1))
         torch.cuda.synchronize()
@@ -507,6 +545,7 @@ def test_conv3x3_groupnorm_deferred_splitk_reduce_at_odd_sizes(sdlib, B, H, W, C
     assert e1 < OP_TOL and e2 < OP_TOL
     assert torch.equal(y.view(torch.int16), y2.view(torch.int16))
     assert torch.equal(yn.view(torch.int16), yn2.view(torch.int16))
+    conv_gn_elementwise(x, w, b, b2, r, gamma, beta, y, (yn,), f"conv3x3+gn split-K odd {B}x{H}x{W} {Cin}->{Cout}")
 
 
 # ------------------------------------------------------------------------------------------ 3x3 conv
@@ -548,7 +587,7 @@ def test_conv3x3_at_odd_level_sizes_bf16(sdlib, B, H, W, Cin, Cout, up, kernel):
     Ho, Wo = ref.shape[-2:]
     r = r16(torch.randn(B, Cout, Ho, Wo, generator=g))
     ref = ref + r
-    out = torch.full((B, Ho, Wo, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((B, Ho, Wo, Cout), torch.bfloat16)
     _lib.check(sdlib.sd_op_conv3x3(stream(), P(x.permute(0, 2, 3, 1).contiguous(), torch.bfloat16), P(_pack_w(w), torch.bfloat16),
                                    P(b), P(b2), P(r.permute(0, 2, 3, 1).contiguous(), torch.bfloat16), P(out), B, H, W, Cin, Cout, 1, up))
     torch.cuda.synchronize()
@@ -557,6 +596,8 @@ def test_conv3x3_at_odd_level_sizes_bf16(sdlib, B, H, W, Cin, Cout, up, kernel):
     splitk = sdlib.sd_op_conv3x3_splitk(B * Ho * Wo, Cout, Cin, H, W, 1, up)
     print(f"conv3x3 {B}x{H}x{W} up={up} {Cin}->{Cout}: kernel {kern} split-K {splitk} rel-L2 {err:.3e}")
     assert kern == kernel and err < OP_TOL
+    r64, m64 = conv3x3_nhwc_ref(x, w, b, b2, r, 1, up)
+    assert_elementwise(out, r64, linear_bound(r64, m64, 9 * Cin + 3), f"conv3x3 odd {B}x{H}x{W} up{up} {Cin}->{Cout} k{kern} s{splitk}", NHWC)
 
 
 @pytest.mark.parametrize("B,H,W,C", [(2, 10, 14, 1280), (2, 14, 18, 1280), (2, 20, 28, 640), (32, 10, 14, 1280)])
@@ -568,7 +609,7 @@ def test_conv3x3_stride2_from_odd_sizes(sdlib, B, H, W, C):
     b = torch.randn(C, generator=g)
     ref = _conv_ref(x, w, b, 0, stride=2)
     Ho, Wo = ref.shape[-2:]
-    out = torch.full((B, Ho, Wo, C), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((B, Ho, Wo, C), torch.bfloat16)
     _lib.check(sdlib.sd_op_conv3x3(stream(), P(x.permute(0, 2, 3, 1).contiguous(), torch.bfloat16), P(_pack_w(w), torch.bfloat16),
                                    P(b), None, None, P(out), B, H, W, C, C, 2, 0))
     torch.cuda.synchronize()
@@ -576,6 +617,8 @@ def test_conv3x3_stride2_from_odd_sizes(sdlib, B, H, W, C):
     kern = sdlib.sd_op_conv3x3_kernel(B * Ho * Wo, C, C, H, W, 2, 0, 0)
     print(f"conv3x3 stride 2 {B}x{H}x{W} -> {Ho}x{Wo} C={C}: kernel {kern} rel-L2 {err:.3e}")
     assert kern == 0 and err < OP_TOL
+    r64, m64 = conv3x3_nhwc_ref(x, w, b, None, None, 2)
+    assert_elementwise(out, r64, linear_bound(r64, m64, 9 * C + 1), f"conv3x3 stride2 odd {B}x{H}x{W} C={C}", NHWC)
 
 
 # fp8 (Cin a multiple of 128; the UNet's level-0 convs pad 320 to 384 and are covered at 64x96 by test_resolution_gpu.py)
@@ -597,13 +640,15 @@ def test_conv3x3_at_odd_level_sizes_fp8(sdlib, B, H, W, Cin, Cout, up, kernel):
     Ho, Wo = ref.shape[-2:]
     xd = xq.view(torch.uint8).permute(0, 2, 3, 1).contiguous()
     wd = wc.permute(0, 2, 3, 1).reshape(Cout, 9, Cin // 128, 128).permute(0, 2, 1, 3).contiguous()
-    out = torch.full((B, Ho, Wo, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((B, Ho, Wo, Cout), torch.bfloat16)
     _lib.check(sdlib.sd_op_conv3x3_fp8(stream(), P(xd), P(wd), P(wsc), xs, P(b), None, None, P(out), B, H, W, Cin, Cout, 1, up))
     torch.cuda.synchronize()
     err = rel_l2(out.permute(0, 3, 1, 2), ref)
     kern = sdlib.sd_op_conv3x3_kernel(B * Ho * Wo, Cout, Cin, H, W, 1, up, 1)
     print(f"conv3x3 fp8 {B}x{H}x{W} up={up} Cin={Cin}: kernel {kern} rel-L2 {err:.3e}")
     assert kern == kernel and err < OP_TOL
+    r64, m64, k_eff = fp8_conv_ref(xq.float() / xs, wq, wsc, b, up=up)
+    assert_elementwise(out, r64, linear_bound(r64, m64, k_eff), f"conv3x3 fp8 odd {B}x{H}x{W} up{up} {Cin}->{Cout} k{kern}", NHWC)
 
 
 # ------------------------------------------------------------------------------------------ softmax rows
@@ -617,13 +662,14 @@ def test_softmax_rows_at_vae_mid_block_widths(sdlib, rows, cols):
     s[::2, cols - 9] = 420.0
     scale = 1 / math.sqrt(512)
     ref = torch.softmax(s * scale, dim=-1)
-    d = s.to(torch.bfloat16).cuda()
+    d = guarded_input(s, torch.bfloat16)         # in place: the scores' own poisoned guards
     _lib.check(sdlib.sd_op_softmax_rows(stream(), d.data_ptr(), rows, cols, scale))
     torch.cuda.synchronize()
     err = rel_l2(d, ref)
     print(f"softmax {rows}x{cols}: rel-L2 {err:.3e}")
     assert torch.isfinite(d.float()).all() and err < OP_TOL
     assert torch.allclose(d.float().sum(-1).cpu(), torch.ones(rows), atol=2e-2)
+    softmax_rows_elementwise(d, s, scale, f"softmax mid-block rows {rows}x{cols}")
 
 
 # ------------------------------------------------------------------------------------------ large operands
@@ -648,7 +694,7 @@ def test_conv3x3_large_operands(sdlib, B, H, W, Cin, Cout, kernel):
     w = (torch.randn((Cout, Cin, 3, 3), generator=g, device="cuda") / math.sqrt(9 * Cin)).to(torch.bfloat16).float()
     b = torch.randn(Cout, generator=g, device="cuda")
     wd = _pack_w(w).to(torch.bfloat16)
-    out = torch.full((B, H, W, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = torch.full((B, H, W, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)     # no guards: device memory
     try:
         _lib.check(sdlib.sd_op_conv3x3(stream(), x.data_ptr(), wd.data_ptr(), b.data_ptr(), None, None,
                                        out.data_ptr(), B, H, W, Cin, Cout, 1, 0))
@@ -661,6 +707,11 @@ def test_conv3x3_large_operands(sdlib, B, H, W, Cin, Cout, kernel):
         finite = bool(torch.isfinite(out).all())
         print(f"conv3x3 {B}x{H}x{W} {Cin}->{Cout} ({nbytes / 2**30:.1f} GiB input): kernel {kernel}, last rows rel-L2 {err:.3e}")
         assert finite and err < OP_TOL
+        cp = F.pad(crop.double(), (1, 1, 0, 1))
+        r64 = (F.conv2d(cp, w.cpu().double()) + b.cpu().double()[None, :, None, None]).permute(0, 2, 3, 1)
+        m64 = (F.conv2d(cp.abs(), w.cpu().double().abs()) + b.cpu().double().abs()[None, :, None, None]).permute(0, 2, 3, 1)
+        assert_elementwise(got.permute(0, 2, 3, 1), r64, linear_bound(r64, m64, 9 * Cin + 1),
+                           f"conv3x3 large operands {B}x{H}x{W} {Cin}->{Cout} last rows", NHWC)
     finally:
         del x, wd, out
         torch.cuda.empty_cache()

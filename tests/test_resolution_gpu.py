@@ -13,6 +13,12 @@ pytestmark = pytest.mark.gpu
 
 from sonicdiffusionbayeslab_amd import _lib
 from tests.util import cosine, oracle_cfg, rel_l2
+from tests.bounds import (ATOL_TINY, U32, NHWC, assert_e4m3_codes, assert_elementwise, attention_elementwise, check_guards,
+                          conv3x3_nhwc_ref, conv_gn_elementwise, device_operand, forget_guards, fp8_conv_ref,
+                          fp8_gemm_ref_bound, geglu_ref_bound, gemm_bound, grouped_softmax_elementwise, guarded,
+                          guarded_input, linear_bound, ln_fold_elementwise, ln_fold_ref_bound, norm_ref_bound, sample_rows,
+                          softmax_rows_ref_bound, softmax_rows_elementwise, subpixel_ref, ulp_bf16,
+                          xattn_elementwise)
 
 OP_TOL = 6e-3                     # test_ops_gpu.py / test_fp8_gpu.py: one kernel, bf16 output rounding
 UNET_TOL = 2e-2                   # one UNet forward
@@ -26,10 +32,11 @@ def stream():
 
 
 def P(t):
+    """The device pointer of a kernel operand or output: guarded buffers as they are, anything else copied into a
+    NaN-poisoned guarded buffer (tests/bounds.py), kept alive until the test ends."""
     if t is None:
         return None
-    if t.device.type != "cuda":
-        t = t.cuda()
+    t = device_operand(t)
     _KEEP.append(t)
     return t.data_ptr()
 
@@ -39,6 +46,7 @@ def _drop_keep():
     yield
     torch.cuda.synchronize()
     _KEEP.clear()
+    check_guards()              # every guard of every operand and output of the test (tests/bounds.py)
 
 
 def r16(t):
@@ -86,13 +94,15 @@ def test_conv3x3_non_square_bf16(sdlib, B, H, W, Cin, Cout, up, kernel):
     xd = x.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
     wd = w.permute(0, 2, 3, 1).reshape(Cout, 9, Cin // 64, 64).permute(0, 2, 1, 3).contiguous().to(torch.bfloat16)
     rd = r.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
-    out = torch.full((B, Ho, Wo, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((B, Ho, Wo, Cout), torch.bfloat16)
     _lib.check(sdlib.sd_op_conv3x3(stream(), P(xd), P(wd), P(b), P(b2), P(rd), P(out), B, H, W, Cin, Cout, 1, up))
     torch.cuda.synchronize()
     err = rel_l2(out.permute(0, 3, 1, 2), ref)
     kern = sdlib.sd_op_conv3x3_kernel(B * Ho * Wo, Cout, Cin, H, W, 1, up, 0)
     print(f"conv3x3 {B}x{H}x{W} up={up} Cin={Cin} Cout={Cout}: kernel {kern} rel-L2 {err:.3e}")
     assert kern == kernel and err < OP_TOL
+    r64, m64 = conv3x3_nhwc_ref(x, w, b, b2, r, 1, up)
+    assert_elementwise(out, r64, linear_bound(r64, m64, 9 * Cin + 3), f"conv3x3 non-square {B}x{H}x{W} up{up} {Cin}->{Cout} k{kern}", NHWC)
 
 
 @pytest.mark.parametrize("B,H,W,Cin,Cout,up", [(2, 32, 48, 640, 640, 0), (1, 16, 24, 1280, 320, 1), (3, 20, 20, 128, 192, 0)])
@@ -109,7 +119,7 @@ def test_conv3x3_geometry_mode_with_split_k_and_tails(sdlib, monkeypatch, B, H, 
     wd = w.permute(0, 2, 3, 1).reshape(Cout, 9, Cin // 64, 64).permute(0, 2, 1, 3).contiguous().to(torch.bfloat16)
 
     def run():
-        out = torch.full((B, Ho, Wo, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
+        out = guarded((B, Ho, Wo, Cout), torch.bfloat16)
         _lib.check(sdlib.sd_op_conv3x3(stream(), P(xd), P(wd), P(b), None, None, P(out), B, H, W, Cin, Cout, 1, up))
         torch.cuda.synchronize()
         return out.permute(0, 3, 1, 2).float().cpu()
@@ -121,6 +131,10 @@ def test_conv3x3_geometry_mode_with_split_k_and_tails(sdlib, monkeypatch, B, H, 
     err, diff = rel_l2(got, ref), rel_l2(got, other)
     print(f"geometry mode {B}x{H}x{W} up={up}: rel-L2 {err:.3e}, vs implicit GEMM {diff:.3e}")
     assert err < OP_TOL and diff < 2e-3
+    r64, m64 = conv3x3_nhwc_ref(x, w, b, None, None, 1, up)
+    bound = linear_bound(r64, m64, 9 * Cin + 1)
+    assert_elementwise(got.permute(0, 2, 3, 1), r64, bound, f"conv3x3 geometry-mode {B}x{H}x{W} up{up} {Cin}->{Cout}", NHWC)
+    assert_elementwise(other.permute(0, 2, 3, 1), r64, bound, f"conv3x3 implicit-gemm {B}x{H}x{W} up{up} {Cin}->{Cout}", NHWC)
 
 
 def _subpixel_weights(w):
@@ -147,13 +161,15 @@ def test_conv3x3_upsample_subpixel_non_square(sdlib, B, H, W, Cin, Cout):
     ref = _conv_ref(x, w, b, 1)
     xd = x.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
     w4 = _subpixel_weights(w).to(torch.bfloat16)
-    out = torch.full((B, 2 * H, 2 * W, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((B, 2 * H, 2 * W, Cout), torch.bfloat16)
     _lib.check(sdlib.sd_op_conv3x3_upsample_subpixel(stream(), P(xd), P(w4), P(b), P(out), B, H, W, Cin, Cout))
     torch.cuda.synchronize()
     err = rel_l2(out.permute(0, 3, 1, 2), ref)
     kern = sdlib.sd_op_conv3x3_kernel(4 * B * H * W, Cout, Cin, H, W, 1, 2, 0)
     print(f"sub-pixel upsampler {B}x{H}x{W} -> {2 * H}x{2 * W}: kernel {kern} rel-L2 {err:.3e}")
     assert kern == 0 and err < OP_TOL            # (the 4-tap mode keeps power-of-two geometry: DESIGN 4b)
+    r64, m64 = subpixel_ref(x, w4, b)            # from the bf16-rounded summed phase weights the kernel reads
+    assert_elementwise(out, r64, linear_bound(r64, m64, 4 * Cin + 1), f"conv3x3 subpixel non-square {B}x{H}x{W} {Cin}->{Cout}", NHWC)
 
 
 @pytest.mark.parametrize("B,H,W,Cin,Cout,kernel", [(1, 64, 96, 384, 320, 1), (1, 32, 48, 640, 640, 1),
@@ -171,7 +187,7 @@ def test_conv3x3_non_square_fp8(sdlib, B, H, W, Cin, Cout, kernel):
     ref = F.conv2d(xq.float() / xs, wq * wsc[:, None, None, None], b, padding=1)
     xd = xc.permute(0, 2, 3, 1).contiguous()
     wd = wc.permute(0, 2, 3, 1).reshape(Cout, 9, Cin // 128, 128).permute(0, 2, 1, 3).contiguous()
-    out = torch.full((B, H, W, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = guarded((B, H, W, Cout), torch.bfloat16)
     _lib.check(sdlib.sd_op_conv3x3_fp8(stream(), P(xd), P(wd), P(wsc), xs, P(b), None, None, P(out), B, H, W, Cin, Cout,
                                        1, 0))
     torch.cuda.synchronize()
@@ -179,6 +195,8 @@ def test_conv3x3_non_square_fp8(sdlib, B, H, W, Cin, Cout, kernel):
     kern = sdlib.sd_op_conv3x3_kernel(B * H * W, Cout, Cin, H, W, 1, 0, 1)
     print(f"conv3x3 fp8 {B}x{H}x{W} Cin={Cin}: kernel {kern} rel-L2 {err:.3e}")
     assert kern == kernel and err < OP_TOL
+    r64, m64, k_eff = fp8_conv_ref(xq.float() / xs, wq, wsc, b)
+    assert_elementwise(out, r64, linear_bound(r64, m64, k_eff), f"conv3x3 fp8 non-square {B}x{H}x{W} {Cin}->{Cout} k{kern}", NHWC)
 
 
 def test_conv3x3_kernel_report_matches_the_square_unet_shapes(sdlib):
@@ -199,13 +217,14 @@ def test_softmax_rows_long(sdlib, rows, cols):
     s = r16(torch.randn(rows, cols, generator=g) * 20)
     scale = 1 / math.sqrt(512)
     ref = torch.softmax(s * scale, dim=-1)
-    d = s.to(torch.bfloat16).cuda()
+    d = guarded_input(s, torch.bfloat16)         # in place: the scores' own poisoned guards
     _lib.check(sdlib.sd_op_softmax_rows(stream(), d.data_ptr(), rows, cols, scale))
     torch.cuda.synchronize()
     err = rel_l2(d, ref)
     print(f"softmax {rows}x{cols}: rel-L2 {err:.3e}")
     assert torch.isfinite(d.float()).all() and err < OP_TOL
     assert torch.allclose(d.float().sum(-1).cpu(), torch.ones(rows), atol=2e-2)
+    softmax_rows_elementwise(d, s, scale, f"softmax long rows {rows}x{cols}")
 
 
 # ------------------------------------------------------------------------------------------ VAE decoder
