@@ -206,6 +206,21 @@ int sd_sched_step(void* stream, const float* eps, int cfg, float guidance, const
                   const float* m2, const float* m3, const float* noise, float* prev, float* y2, float* m_out,
                   const float coef[10], long long n);
 
+/* ---- rescaled classifier-free guidance (guidance_rescale; diffusers' rescale_noise_cfg) ----
+ * eps holds [u: batch samples | c: batch samples] of n_per_sample fp32 elements each.  Per sample b, with
+ * g = u + guidance*(c - u) formed as sd_sched_step forms it:
+ *   k_out[b] = rescale * std(c_b) / std(g_b) + (1 - rescale)      (torch.std: unbiased, no epsilon)
+ * Deterministic: k_out[b] depends on sample b's elements and n_per_sample only -- one workgroup per sample, a fixed
+ * thread/element assignment, double partials summed in a fixed order (mean, then the centred sum of squares).
+ * n_per_sample: a positive multiple of 4; batch <= 65535. */
+int sd_cfg_rescale_factors(void* stream, const float* eps, int batch, long long n_per_sample, float guidance,
+                           float rescale, float* k_out);
+/* sd_sched_step with the (CFG-combined) prediction of sample b = i / n_per_sample scaled by k[b] before every use:
+ * e := k[b]*e in prev, y2 and m_out.  Same operands and coefficients as sd_sched_step. */
+int sd_sched_step_rescaled(void* stream, const float* eps, int cfg, float guidance, const float* x, const float* m1,
+                           const float* m2, const float* m3, const float* noise, float* prev, float* y2, float* m_out,
+                           const float coef[10], long long n, const float* k, long long n_per_sample);
+
 /* ---- operator-level entry points (each is one hot kernel; used by the parity tests) ----------- */
 /* C[M,N] = [X|X2][M,K] . W[N,K]^T + bias + bias2 + R ; epi=1: GEGLU on interleaved W (N -> N/2) */
 int sd_op_gemm(void* stream, const void* X, long long ldx, const void* X2, long long ldx2, int K1, const void* W,

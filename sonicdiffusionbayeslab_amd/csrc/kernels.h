@@ -216,3 +216,10 @@ struct StepCoef {
 int sd_launch_sched_step(const float* eps, int cfg, float guidance, const float* x, const float* m1,
                          const float* m2, const float* m3, const float* noise, float* prev, float* y2, float* m_out,
                          StepCoef c, long n, hipStream_t stream);
+// guidance_rescale: k_out[b] = r * std(c_b) / std(g_b) + (1 - r), g = u + s (c - u); eps = [u: batch | c: batch] samples
+int sd_launch_cfg_rescale_factors(const float* eps, int batch, long n_per_sample, float guidance, float rescale, float* k_out,
+                                  hipStream_t stream);
+// sd_launch_sched_step with e := k[i / n_per_sample] * e (after the CFG combine, before every use)
+int sd_launch_sched_step_rescaled(const float* eps, int cfg, float guidance, const float* x, const float* m1,
+                                  const float* m2, const float* m3, const float* noise, float* prev, float* y2,
+                                  float* m_out, StepCoef c, const float* k, long n_per_sample, long n, hipStream_t stream);

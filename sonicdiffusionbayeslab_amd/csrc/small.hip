@@ -223,6 +223,98 @@ __global__ void sched_step_kernel(const float* __restrict__ eps, int cfg, float 
     ((f32x4*)prev)[i] = p;
 }
 
+// ---- rescaled CFG (guidance_rescale): per-sample factor k_b, then the step with e := k_b * e ---------------------------
+// g = u + s (c - u) is formed exactly as the step below forms it (same expression, same unit), so the std the factor sees
+// is the std of the values the step scales.  One block per sample, fixed thread -> element assignment, double partials,
+// wave butterflies and an in-order sum of the wave partials: k_b depends on sample b's data and n_per_sample only (not on
+// the batch, the sample's position or the grid) -- dist.py's sharding invariant.  Two passes (mean, then centred sum).
+constexpr int RESCALE_THREADS = 512;
+
+__device__ __forceinline__ f32x4 cfg_combine(f32x4 e, f32x4 et, float guidance) { return e + guidance * (et - e); }
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// in-order block sum of two doubles; every thread gets the totals
+__device__ __forceinline__ void block_sum2_f64(double& a, double& b, double (*red)[RESCALE_THREADS / 64]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    a = wave_sum_f64(a);
+    b = wave_sum_f64(b);
+    if (lane == 0) {
+        red[0][wave] = a;
+        red[1][wave] = b;
+    }
+    __syncthreads();
+    a = 0.0;
+    b = 0.0;
+#pragma unroll
+    for (int w = 0; w < RESCALE_THREADS / 64; ++w) {
+        a += red[0][w];
+        b += red[1][w];
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(RESCALE_THREADS) void cfg_rescale_factors_kernel(const float* __restrict__ eps, int batch,
+                                                                              long n4s, float guidance, float rescale,
+                                                                              float* __restrict__ k_out) {
+    __shared__ double red[2][RESCALE_THREADS / 64];
+    const int b = blockIdx.x;
+    const f32x4* u = (const f32x4*)eps + (long)b * n4s;
+    const f32x4* c = (const f32x4*)eps + ((long)batch + b) * n4s;
+    double sc = 0.0, sg = 0.0;
+    for (long i = threadIdx.x; i < n4s; i += RESCALE_THREADS) {
+        const f32x4 et = c[i], g = cfg_combine(u[i], et, guidance);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            sc += (double)et[j];
+            sg += (double)g[j];
+        }
+    }
+    block_sum2_f64(sc, sg, red);
+    const double n = 4.0 * (double)n4s;
+    const double mc = sc / n, mg = sg / n;
+    double qc = 0.0, qg = 0.0;
+    for (long i = threadIdx.x; i < n4s; i += RESCALE_THREADS) {
+        const f32x4 et = c[i], g = cfg_combine(u[i], et, guidance);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double dc = (double)et[j] - mc, dg = (double)g[j] - mg;
+            qc += dc * dc;
+            qg += dg * dg;
+        }
+    }
+    block_sum2_f64(qc, qg, red);
+    // std(c) / std(g): the (n - 1) of torch.std cancels in the ratio
+    if (threadIdx.x == 0) k_out[b] = (float)((double)rescale * sqrt(qc / qg) + (1.0 - (double)rescale));
+}
+
+// sched_step_kernel with the CFG-combined prediction scaled by its sample's factor: e := k[b] * e before every use
+__global__ void sched_step_rescaled_kernel(const float* __restrict__ eps, int cfg, float guidance,
+                                           const float* __restrict__ x, const float* __restrict__ m1,
+                                           const float* __restrict__ m2, const float* __restrict__ m3,
+                                           const float* __restrict__ noise, float* __restrict__ prev,
+                                           float* __restrict__ y2, float* __restrict__ m_out, StepCoef c,
+                                           const float* __restrict__ k, long n4s, long n4) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    f32x4 e = ((const f32x4*)eps)[i];
+    if (cfg) e = cfg_combine(e, ((const f32x4*)eps)[i + n4], guidance);
+    e = k[i / n4s] * e;
+    const f32x4 xv = ((const f32x4*)x)[i];
+    f32x4 p = c.px * xv + c.pe * e;
+    if (m1) p += c.p1 * ((const f32x4*)m1)[i];
+    if (m2) p += c.p2 * ((const f32x4*)m2)[i];
+    if (m3) p += c.p3 * ((const f32x4*)m3)[i];
+    if (noise) p += c.pn * ((const f32x4*)noise)[i];
+    if (y2) ((f32x4*)y2)[i] = c.yx * xv + c.ye * e;
+    if (m_out) ((f32x4*)m_out)[i] = c.mx * xv + c.me * e;
+    ((f32x4*)prev)[i] = p;
+}
+
 __global__ void f32_to_bf16_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, long n4) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
@@ -420,6 +512,32 @@ int sd_launch_sched_step(const float* eps, int cfg, float guidance, const float*
     const long n4 = n / 4;
     hipLaunchKernelGGL(sched_step_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, eps, cfg, guidance,
                        x, m1, m2, m3, noise, prev, y2, m_out, c, n4);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sd_launch_cfg_rescale_factors(const float* eps, int batch, long n_per_sample, float guidance, float rescale, float* k_out,
+                                  hipStream_t stream) {
+    SD_REQUIRE(eps && k_out, "cfg_rescale_factors: null operand");
+    SD_REQUIRE(batch > 0 && batch <= 65535, "cfg_rescale_factors: batch=%d", batch);
+    SD_REQUIRE(n_per_sample >= 4 && n_per_sample % 4 == 0,
+               "cfg_rescale_factors: n_per_sample=%ld must be a positive multiple of 4", n_per_sample);
+    hipLaunchKernelGGL(cfg_rescale_factors_kernel, dim3(batch), dim3(RESCALE_THREADS), 0, stream, eps, batch,
+                       n_per_sample / 4, guidance, rescale, k_out);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sd_launch_sched_step_rescaled(const float* eps, int cfg, float guidance, const float* x, const float* m1,
+                                  const float* m2, const float* m3, const float* noise, float* prev, float* y2,
+                                  float* m_out, StepCoef c, const float* k, long n_per_sample, long n, hipStream_t stream) {
+    SD_REQUIRE(eps && x && prev && k, "sched_step_rescaled: null operand");
+    SD_REQUIRE(n > 0 && n % 4 == 0, "sched_step_rescaled: n=%ld must be a positive multiple of 4", n);
+    SD_REQUIRE(n_per_sample > 0 && n_per_sample % 4 == 0 && n % n_per_sample == 0,
+               "sched_step_rescaled: n_per_sample=%ld must be a positive multiple of 4 dividing n=%ld", n_per_sample, n);
+    const long n4 = n / 4;
+    hipLaunchKernelGGL(sched_step_rescaled_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, eps, cfg,
+                       guidance, x, m1, m2, m3, noise, prev, y2, m_out, c, k, n_per_sample / 4, n4);
     SD_CHECK_HIP(hipGetLastError());
     return 0;
 }

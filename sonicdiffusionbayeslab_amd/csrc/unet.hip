@@ -2338,6 +2338,21 @@ extern "C" int sd_sched_step(void* stream, const float* eps, int cfg, float guid
     return sd_launch_sched_step(eps, cfg, guidance, x, m1, m2, m3, noise, prev, y2, m_out, c, (long)n, (hipStream_t)stream);
 }
 
+extern "C" int sd_cfg_rescale_factors(void* stream, const float* eps, int batch, long long n_per_sample, float guidance,
+                                      float rescale, float* k_out) {
+    return sd_launch_cfg_rescale_factors(eps, batch, (long)n_per_sample, guidance, rescale, k_out, (hipStream_t)stream);
+}
+
+extern "C" int sd_sched_step_rescaled(void* stream, const float* eps, int cfg, float guidance, const float* x,
+                                      const float* m1, const float* m2, const float* m3, const float* noise, float* prev,
+                                      float* y2, float* m_out, const float coef[10], long long n, const float* k,
+                                      long long n_per_sample) {
+    SD_REQUIRE(coef, "sched_step_rescaled: null coefficients");
+    StepCoef c{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7], coef[8], coef[9]};
+    return sd_launch_sched_step_rescaled(eps, cfg, guidance, x, m1, m2, m3, noise, prev, y2, m_out, c, k, (long)n_per_sample,
+                                         (long)n, (hipStream_t)stream);
+}
+
 // ---- operator-level entry points -------------------------------------------------------------
 extern "C" int sd_op_gemm(void* stream, const void* X, long long ldx, const void* X2, long long ldx2, int K1,
                           const void* W, const float* bias, const float* bias2, const void* R, long long ldr, void* C,

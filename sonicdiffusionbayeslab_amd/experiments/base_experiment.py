@@ -147,6 +147,10 @@ class BaseMethod(ABC):
         ``extra(point)`` -> additional logged values."""
         batch_size = self.config.inference.get("batch_size", 1)
         self.metric_dict = defaultdict(list)
+        # optional experiment_params.guidance_rescale (rescaled CFG, src/models.py:244-250); absent: the call is unchanged
+        rescale = self.config.get("experiment_params", {}).get("guidance_rescale", None)
+        if rescale is not None:
+            call_kwargs = (lambda kw: lambda p: {**kw(p), "guidance_rescale": float(rescale)})(call_kwargs)
         for point in points:
             self.model.to(self.device)
             if hasattr(self.model, "calibrate_fp8") and not getattr(self.model, "_fp8_calibrated", True):

@@ -1,10 +1,12 @@
 """``methods_registry["deep_cache"]`` (``src/experiments/deep_cache.py:10-58``).
 
-The reference does not swap the scheduler here (``:17-18``) and so runs the checkpoint's PNDM:
-that is the default (``pndm_scheduler``); a ``scheduler.scheduler_name`` key in the YAML selects
-another plugin (BASELINE config 4 quotes DeepCache on DDIM 50 steps, see configs/deep_cache_config.yaml)."""
+The reference does not swap the scheduler here (``:17-18``) and so runs the checkpoint's own scheduler
+(PNDM for SD-1.5, else the class the checkpoint's scheduler config names): that is the default; a
+``scheduler.scheduler_name`` key in the YAML selects another plugin (BASELINE config 4 quotes DeepCache on DDIM 50
+steps, see configs/deep_cache_config.yaml)."""
 from ..deepcache import DeepCacheSDHelper
 from ..registry import methods_registry, schedulers_registry
+from ..schedulers import checkpoint_scheduler_name
 from .base_experiment import BaseMethod
 
 
@@ -16,8 +18,9 @@ class DeepCacheMethod(BaseMethod):
         self.cache_branch_id = ep.get("cache_branch_id", 0)
 
     def setup_scheduler(self):
-        name = self.config.get("scheduler", {}).get("scheduler_name", "pndm_scheduler")
-        self.model.scheduler = schedulers_registry[name].from_config(self.model.scheduler.config)
+        config = self.model.scheduler.config
+        name = self.config.get("scheduler", {}).get("scheduler_name", None) or checkpoint_scheduler_name(config)
+        self.model.scheduler = schedulers_registry[name].from_config(config)
 
     def run_experiment(self):
         # one helper per interval, enabled across the whole sweep of step counts (:23-58)

@@ -35,7 +35,7 @@ from .registry import models_registry
 from .schedulers import PNDMConfigStub
 from .unet import CACHE_FULL_AND_STORE, CACHE_OFF, CACHE_SKIP, HipUNet2DConditionModel
 from .vae import HipVaeDecoder, VaeConfig, load_vae_state_dict, make_synthetic_vae_state_dict
-from .weights import UNetConfig, load_unet_config, load_unet_state_dict, make_synthetic_state_dict
+from .weights import UNetConfig, load_scheduler_config, load_unet_config, load_unet_state_dict, make_synthetic_state_dict
 
 
 @dataclass
@@ -128,6 +128,7 @@ class StableDiffusionModel:
             has_clip = all(os.path.exists(os.path.join(path, *p)) for p in (("tokenizer", "vocab.json"),
                                                                             ("tokenizer", "merges.txt"),
                                                                             ("text_encoder", "model.safetensors")))
+            kwargs.setdefault("scheduler", PNDMConfigStub(load_scheduler_config(path)))   # the checkpoint's own scheduler config
             return cls(unet_config=load_unet_config(path), state_dict=load_unet_state_dict(path), source=f"local:{path}",
                        clip_dir=path if has_clip else None, **kwargs)
         seed = int(os.environ.get("SD_AMD_WEIGHTS_SEED", "1234"))
@@ -263,9 +264,8 @@ class StableDiffusionModel:
     def _begin(self, prompt, height, width, guidance_scale, negative_prompt, num_images_per_prompt, prompt_embeds,
                negative_prompt_embeds, guidance_rescale=0.0, timesteps=None, sigmas=None):
         """Steps 0-3 of the reference's ``call`` (``src/models.py:110-160``): argument checks, batch size,
-        prompt encoding, CFG concat; uploads the prompt K/V projections.  Returns (device, batch, do_cfg, ctx)."""
-        if guidance_rescale != 0.0:
-            raise NotImplementedError("guidance_rescale is never used by the reference (src/models.py:53)")
+        prompt encoding, CFG concat; uploads the prompt K/V projections.  Returns (device, batch, do_cfg, ctx).
+        ``guidance_rescale`` is not validated (as upstream): the step rescales when CFG runs and it is > 0."""
         if num_images_per_prompt != 1 or timesteps is not None or sigmas is not None:
             raise NotImplementedError("custom timesteps / num_images_per_prompt are outside the reference's use")
         height, width = self.check_size(height, width)          # before any GPU work
@@ -399,6 +399,8 @@ class StableDiffusionModel:
             kw = {}
             if is_lcm and step_noise is not None and i < len(ts_host) - 1:
                 kw["noise"] = step_noise[i]
+            if do_cfg and guidance_rescale > 0.0:                                                 # :244-250
+                kw["guidance_rescale"] = guidance_rescale
             step = self.scheduler.step_fused(eps, guidance_scale, latents, t, cfg=do_cfg,          # :238-261
                                              eta=eta, generator=generator, **kw)
             if len(step) == 1:                                                                      # :257-261
@@ -431,22 +433,29 @@ def _push_history(sched, noise_pred, latents):
 
 
 class _VariantBase(StableDiffusionModel):
-    """Shared step of the variant loops: UNet forward, then CFG combine + ``scheduler.step`` in the one fused
-    launch, returning the new latents and the CFG-combined noise prediction the hand-off needs."""
+    """Shared step of the variant loops: UNet forward, then CFG combine (+ rescale) + ``scheduler.step`` in the fused
+    launches, returning the new latents; ``_combined`` gives the (rescaled) CFG-combined noise prediction the hand-off
+    needs."""
 
-    def _step_with(self, sched, eps, latents, t, unet_batch, do_cfg, guidance_scale, eta, generator, x0_preds):
+    def _step_with(self, sched, eps, latents, t, unet_batch, do_cfg, guidance_scale, eta, generator, x0_preds,
+                   guidance_rescale=0.0):
         self.unet.forward_latents(latents, unet_batch, float(t), out=eps, cache_mode=CACHE_OFF)
-        step = sched.step_fused(eps, guidance_scale, latents, t, cfg=do_cfg, eta=eta, generator=generator)
+        kw = {"guidance_rescale": guidance_rescale} if do_cfg and guidance_rescale > 0.0 else {}   # :583-590
+        step = sched.step_fused(eps, guidance_scale, latents, t, cfg=do_cfg, eta=eta, generator=generator, **kw)
         if len(step) == 2:
             x0_preds.append(step[1][0:1])
         return step[0]
 
     @staticmethod
-    def _combined(eps, do_cfg, guidance_scale):
+    def _combined(eps, do_cfg, guidance_scale, sched=None):
+        """The noise prediction the step saw: CFG combine, scaled by the rescale factors ``sched``'s last step computed
+        (``rescale_factors``; None when it did not rescale)."""
         if not do_cfg:
             return eps
         u, c = eps.chunk(2)
-        return u + guidance_scale * (c - u)                                                         # :238-242
+        g = u + guidance_scale * (c - u)                                                            # :238-242
+        k = getattr(sched, "rescale_factors", None)
+        return g if k is None else g * k.view(-1, *([1] * (g.dim() - 1)))
 
 
 @models_registry.add_to_registry("stable_diffusion_model_two_schedulers")
@@ -505,9 +514,9 @@ class StableDiffusionModelTwoSchedulers(_VariantBase):
             in_first = i < len(first)
             sched = self.scheduler_first if in_first else self.scheduler_second
             latents = self._step_with(sched, eps, latents, t, unet_batch, do_cfg, guidance_scale, eta, generator,
-                                      x0_preds)
+                                      x0_preds, guidance_rescale)
             if in_first and hand_off:                                                               # :603-611
-                _push_history(self.scheduler_second, self._combined(eps, do_cfg, guidance_scale), latents)
+                _push_history(self.scheduler_second, self._combined(eps, do_cfg, guidance_scale, sched), latents)
         torch.cuda.synchronize(device)
         return self._finish(latents, x0_preds, output_type, return_dict, time.time() - start_time)
 
@@ -560,13 +569,15 @@ class StableDiffusionModelInterlivingSchedulers(_VariantBase):
         for t in keep:
             if t in t_inter:                                                                        # :1008-1034
                 latents = self._step_with(self.scheduler_inter, eps, latents, t, unet_batch, do_cfg, guidance_scale,
-                                          eta, generator, x0_preds)
-                _push_history(self.scheduler_main, self._combined(eps, do_cfg, guidance_scale), latents)
+                                          eta, generator, x0_preds, guidance_rescale)
+                _push_history(self.scheduler_main, self._combined(eps, do_cfg, guidance_scale, self.scheduler_inter),
+                              latents)
             else:                                                                                   # :1035-1054
                 latents = self._step_with(self.scheduler_main, eps, latents, t, unet_batch, do_cfg, guidance_scale,
-                                          eta, generator, x0_preds)
+                                          eta, generator, x0_preds, guidance_rescale)
                 if _is_dpm(self.scheduler_inter):
-                    _push_history(self.scheduler_inter, self._combined(eps, do_cfg, guidance_scale), latents)
+                    _push_history(self.scheduler_inter, self._combined(eps, do_cfg, guidance_scale, self.scheduler_main),
+                                  latents)
         torch.cuda.synchronize(device)
         return self._finish(latents, x0_preds, output_type, return_dict, time.time() - start_time)
 
@@ -601,7 +612,7 @@ class StableDiffusionModelSkipTimesteps(_VariantBase):
             if i in skip:                                                                           # :1327-1330
                 continue
             latents = self._step_with(self.scheduler, eps, latents, t, unet_batch, do_cfg, guidance_scale, eta,
-                                      generator, x0_preds)
+                                      generator, x0_preds, guidance_rescale)
         torch.cuda.synchronize(device)
         return self._finish(latents, x0_preds, output_type, return_dict, time.time() - start_time)
 

@@ -52,6 +52,22 @@ class SchedulerConfig(dict):
             raise AttributeError(k) from None
 
 
+def rescale_zero_terminal_snr(betas: torch.Tensor) -> torch.Tensor:
+    """diffusers' ``rescale_zero_terminal_snr`` (Lin et al. 2023, Algorithm 1), in the same fp32 torch operations and
+    order, so the tables are bit-identical to upstream's: shift sqrt(alpha_bar) to end at 0, rescale it to keep its
+    first value, and return the betas of that schedule."""
+    alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
+    alphas_bar_sqrt = alphas_cumprod.sqrt()
+    alphas_bar_sqrt_0 = alphas_bar_sqrt[0].clone()
+    alphas_bar_sqrt_T = alphas_bar_sqrt[-1].clone()
+    alphas_bar_sqrt -= alphas_bar_sqrt_T
+    alphas_bar_sqrt *= alphas_bar_sqrt_0 / (alphas_bar_sqrt_0 - alphas_bar_sqrt_T)
+    alphas_bar = alphas_bar_sqrt ** 2
+    alphas = alphas_bar[1:] / alphas_bar[:-1]
+    alphas = torch.cat([alphas_bar[0:1], alphas])
+    return 1 - alphas
+
+
 def _alphas_cumprod_fp32(cfg) -> np.ndarray:
     if cfg.get("trained_betas") is not None:
         betas = torch.tensor(cfg["trained_betas"], dtype=torch.float32)
@@ -62,7 +78,37 @@ def _alphas_cumprod_fp32(cfg) -> np.ndarray:
         betas = torch.linspace(cfg["beta_start"], cfg["beta_end"], cfg["num_train_timesteps"], dtype=torch.float32)
     else:
         raise NotImplementedError(f"beta_schedule {cfg['beta_schedule']}")
+    if cfg.get("rescale_betas_zero_snr", False):
+        betas = rescale_zero_terminal_snr(betas)
     return torch.cumprod(1.0 - betas, dim=0).numpy()
+
+
+PREDICTION_TYPES = ("epsilon", "v_prediction", "sample")
+
+
+def prediction_coefs(prediction_type: str, alpha: float, sigma: float):
+    """(dx, de, ex, ee): x0 = dx*x + de*m and eps = ex*x + ee*m for a model output m at a step with x = alpha*x0 +
+    sigma*eps (diffusers 0.32.1's conversions; alpha = sqrt(alpha_bar), sigma = sqrt(1 - alpha_bar) for DDIM / LCM / PNDM,
+    DPM-Solver's alpha_t, sigma_t from its sigmas).  Every case is linear in (x, m), so each is a coefficient table of the
+    one fused step."""
+    if prediction_type == "epsilon":
+        return 1.0 / alpha, -sigma / alpha, 0.0, 1.0
+    if prediction_type == "v_prediction":
+        return alpha, -sigma, sigma, alpha
+    if prediction_type == "sample":
+        return 0.0, 1.0, 1.0 / sigma, -alpha / sigma
+    raise NotImplementedError(f"prediction_type {prediction_type!r}: {PREDICTION_TYPES} are built")
+
+
+def cfg_rescale_factors(eps: torch.Tensor, batch: int, guidance: float, rescale: float) -> torch.Tensor:
+    """``sd_cfg_rescale_factors``: k[b] = rescale * std(c_b) / std(g_b) + (1 - rescale), g = u + guidance*(c - u), for
+    eps = [u | c] (2*batch samples, fp32, contiguous).  diffusers' rescale_noise_cfg is g := k[b] * g."""
+    lib = _lib.load()
+    n = eps.numel() // (2 * batch)
+    k = torch.empty(batch, dtype=torch.float32, device=eps.device)
+    _lib.check(lib.sd_cfg_rescale_factors(_lib.current_stream(), eps.data_ptr(), int(batch), int(n), float(guidance),
+                                          float(rescale), k.data_ptr()), "sd_cfg_rescale_factors")
+    return k
 
 
 class _FusedStepScheduler:
@@ -111,8 +157,10 @@ class _FusedStepScheduler:
 
     # --- the single fused launch ------------------------------------------------------------
     @staticmethod
-    def _launch(eps, cfg, guidance, x, m1, m2, noise, coef, want_y2=True, want_m=False, m3=None):
-        """coef = (px, pe, p1, p2, pn, yx, ye, mx, me[, p3]) -- see include/sd_hip.h::sd_sched_step."""
+    def _launch(eps, cfg, guidance, x, m1, m2, noise, coef, want_y2=True, want_m=False, m3=None, k=None):
+        """coef = (px, pe, p1, p2, pn, yx, ye, mx, me[, p3]) -- see include/sd_hip.h::sd_sched_step.  ``k`` (per-sample
+        rescaled-CFG factors, ``cfg_rescale_factors``): the step scales the combined prediction by them
+        (sd_sched_step_rescaled); None launches sd_sched_step."""
         lib = _lib.load()
         n = x.numel()
         prev = torch.empty_like(x)
@@ -120,16 +168,49 @@ class _FusedStepScheduler:
         mo = torch.empty_like(x) if want_m else None
         c10 = [float(v) for v in coef] + [0.0] * (10 - len(coef))
         carr = (C.c_float * 10)(*c10)
-        _lib.check(lib.sd_sched_step(_lib.current_stream(), eps.data_ptr(), int(cfg), float(guidance), x.data_ptr(),
-                                     _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(m3), _lib.ptr(noise), prev.data_ptr(),
-                                     _lib.ptr(y2), _lib.ptr(mo), carr, n), "sd_sched_step")
+        if k is None:
+            _lib.check(lib.sd_sched_step(_lib.current_stream(), eps.data_ptr(), int(cfg), float(guidance), x.data_ptr(),
+                                         _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(m3), _lib.ptr(noise), prev.data_ptr(),
+                                         _lib.ptr(y2), _lib.ptr(mo), carr, n), "sd_sched_step")
+        else:
+            _lib.check(lib.sd_sched_step_rescaled(_lib.current_stream(), eps.data_ptr(), int(cfg), float(guidance),
+                                                  x.data_ptr(), _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(m3), _lib.ptr(noise),
+                                                  prev.data_ptr(), _lib.ptr(y2), _lib.ptr(mo), carr, n, k.data_ptr(),
+                                                  n // x.shape[0]), "sd_sched_step_rescaled")
         return prev, y2, mo
+
+    def _rescale(self, eps, cfg, guidance, guidance_rescale, x):
+        """The rescaled-CFG factors of this step (``src/models.py:244-250``: only with CFG and guidance_rescale > 0),
+        kept in ``rescale_factors`` for the variant pipelines' history hand-off; None otherwise."""
+        self.rescale_factors = None
+        if cfg and guidance_rescale > 0.0:
+            self.rescale_factors = cfg_rescale_factors(eps, x.shape[0], guidance, guidance_rescale)
+        return self.rescale_factors
+
+    def _check_prediction_type(self):
+        if self.config.prediction_type not in PREDICTION_TYPES:
+            raise NotImplementedError(f"prediction_type {self.config.prediction_type!r} is not built for "
+                                      f"{type(self).__name__} (built: {PREDICTION_TYPES})")
+
+    def _refuse_epsilon_at_zero_snr(self, ts):
+        """Deliberate deviation from upstream: epsilon prediction at a step whose alpha_bar is 0 (a zero-terminal-SNR
+        schedule reaching its last training timestep) divides by zero there, and upstream returns NaN latents.  This
+        refuses the combination before any GPU work."""
+        if self.config.prediction_type != "epsilon":
+            return
+        for t in ts:
+            if float(self.alphas_cumprod[int(t)]) == 0.0:
+                raise ValueError(f"prediction_type='epsilon' with rescale_betas_zero_snr=True and timestep_spacing="
+                                 f"{self.config.get('timestep_spacing')!r}: alpha_bar is 0 at timestep {int(t)}, where an "
+                                 "epsilon prediction determines no x0; use prediction_type='v_prediction' (or 'sample')")
 
     @staticmethod
     def _prep(t: torch.Tensor) -> torch.Tensor:
         if not t.is_cuda:
             raise _lib.SdHipError("scheduler.step runs as a HIP kernel: tensors must live on the GPU")
         return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+    rescale_factors: Optional[torch.Tensor] = None
 
     def step(self, model_output, timestep, sample, eta: float = 0.0, generator=None, variance_noise=None,
              return_dict: bool = False, **kwargs):
@@ -146,13 +227,15 @@ class DDIMSchedulerMy(_FusedStepScheduler):
     ``src/models.py:43,185``).  A.6.1."""
     _own_defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                          trained_betas=None, clip_sample=True, set_alpha_to_one=True, steps_offset=0,
-                         prediction_type="epsilon", thresholding=False, timestep_spacing="leading")
+                         prediction_type="epsilon", thresholding=False, timestep_spacing="leading",
+                         rescale_betas_zero_snr=False)
     _accepted = tuple(_own_defaults)
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
-        if self.config.prediction_type != "epsilon" or self.config.clip_sample or self.config.thresholding:
-            raise NotImplementedError("only epsilon prediction without clipping is on the SD-1.5 hot path")
+        if self.config.clip_sample or self.config.thresholding:
+            raise NotImplementedError("clip_sample / thresholding are not on the hot path")
+        self._check_prediction_type()
         self.final_alpha_cumprod = 1.0 if self.config.set_alpha_to_one else float(self.alphas_cumprod[0])
 
     def set_timesteps(self, num_inference_steps: int, device=None):
@@ -169,27 +252,30 @@ class DDIMSchedulerMy(_FusedStepScheduler):
             ts = np.round(np.arange(T, 0, -T / num_inference_steps)).astype(np.int64) - 1
         else:
             raise ValueError(sp)
+        self._refuse_epsilon_at_zero_snr(ts)
         self._set(ts, device)
 
     def coefficients(self, timestep: int):
-        """(c_x, c_e, d_x, d_e): prev = c_x*x + c_e*eps, x0 = d_x*x + d_e*eps (A.7 KATs)."""
+        """(c_x, c_e, d_x, d_e): prev = c_x*x + c_e*m, x0 = d_x*x + d_e*m for the model output m (A.7 KATs)."""
         t = int(timestep)
         prev_t = t - self.config.num_train_timesteps // self.num_inference_steps
         a = float(self.alphas_cumprod[t])
         ap = float(self.alphas_cumprod[prev_t]) if prev_t >= 0 else self.final_alpha_cumprod
-        dx, de = 1.0 / math.sqrt(a), -math.sqrt(1.0 - a) / math.sqrt(a)
-        cx = math.sqrt(ap) * dx
-        ce = math.sqrt(ap) * de + math.sqrt(1.0 - ap)
+        dx, de, ex, ee = prediction_coefs(self.config.prediction_type, math.sqrt(a), math.sqrt(1.0 - a))
+        cx = math.sqrt(ap) * dx + math.sqrt(1.0 - ap) * ex
+        ce = math.sqrt(ap) * de + math.sqrt(1.0 - ap) * ee
         return cx, ce, dx, de
 
-    def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None):
+    def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
+                   guidance_rescale: float = 0.0):
         if eta != 0.0:
             raise NotImplementedError("DDIM eta != 0 is never used by the reference (src/models.py:43)")
         if self.num_inference_steps is None:
             raise ValueError("run set_timesteps first")
         cx, ce, dx, de = self.coefficients(timestep)
-        prev, x0, _ = self._launch(self._prep(model_output), cfg, guidance_scale, self._prep(sample), None, None, None,
-                                   (cx, ce, 0, 0, 0, dx, de, 0, 0))
+        e, x = self._prep(model_output), self._prep(sample)
+        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x)
+        prev, x0, _ = self._launch(e, cfg, guidance_scale, x, None, None, None, (cx, ce, 0, 0, 0, dx, de, 0, 0), k=k)
         return prev, x0
 
 
@@ -208,7 +294,8 @@ class DPMSolverScheduler(_FusedStepScheduler):
     _own_defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                          trained_betas=None, solver_order=2, prediction_type="epsilon", thresholding=False,
                          algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True,
-                         euler_at_final=False, final_sigmas_type="zero", timestep_spacing="linspace", steps_offset=0)
+                         euler_at_final=False, final_sigmas_type="zero", timestep_spacing="linspace", steps_offset=0,
+                         rescale_betas_zero_snr=False)
     _accepted = tuple(_own_defaults)
 
     def __init__(self, **kwargs):
@@ -219,8 +306,12 @@ class DPMSolverScheduler(_FusedStepScheduler):
         if c.algorithm_type not in ("dpmsolver++", "sde-dpmsolver++") and c.final_sigmas_type == "zero":
             raise ValueError(f"`final_sigmas_type` {c.final_sigmas_type} is not supported for `algorithm_type` "
                              f"{c.algorithm_type}. Please choose `sigma_min` instead.")
-        if c.solver_type != "midpoint" or c.prediction_type != "epsilon" or c.thresholding:
-            raise NotImplementedError("only midpoint / epsilon / no thresholding is on the hot path")
+        if c.solver_type != "midpoint" or c.thresholding:
+            raise NotImplementedError("only midpoint / no thresholding is on the hot path")
+        self._check_prediction_type()
+        if c.rescale_betas_zero_snr:
+            # as upstream: close to 0 without being 0, so that the first sigma is finite
+            self.alphas_cumprod[-1] = 2 ** -24
         if c.solver_order not in (1, 2, 3):
             raise ValueError("solver_order must be 1, 2 or 3")
         self.model_outputs: List[Optional[torch.Tensor]] = [None] * c.solver_order
@@ -256,6 +347,7 @@ class DPMSolverScheduler(_FusedStepScheduler):
         else:
             raise ValueError(c.final_sigmas_type)
         self.sigmas = np.concatenate([sig, [sig_last]]).astype(np.float32)
+        self._refuse_epsilon_at_zero_snr(ts)
         self._set(ts, device)
         self.model_outputs = [None] * c.solver_order
         self.lower_order_nums = 0
@@ -269,10 +361,11 @@ class DPMSolverScheduler(_FusedStepScheduler):
 
     def _convert_coefs(self, i: int):
         a0, s0, _ = self._alpha_sigma_lambda(float(self.sigmas[i]))
-        yx, ye = 1.0 / a0, -s0 / a0                       # x0 = (x - sigma_t eps) / alpha_t
+        dx, de, ex, ee = prediction_coefs(self.config.prediction_type, a0, s0)
         if self.config.algorithm_type in ("dpmsolver++", "sde-dpmsolver++"):        # src/schedulers.py:35
-            return yx, ye, yx, ye                         # history entry m := x0
-        return yx, ye, 0.0, 1.0                           # history entry m := eps  (:64)
+            return dx, de, dx, de                         # history entry m := x0
+        # history entry m := eps (:64); x0 = (x - sigma_t eps) / alpha_t from that eps (:94)
+        return (1.0 - s0 * ex) / a0, -s0 * ee / a0, ex, ee
 
     def convert_model_output(self, model_output, *args, sample=None, **kwargs):
         """``src/schedulers.py:14-96``: returns (converted_output, x0_pred) at the current step."""
@@ -345,7 +438,7 @@ class DPMSolverScheduler(_FusedStepScheduler):
         return ratio + c0 * mx, c0 * me, c1, c2, pn
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   variance_noise: Optional[torch.Tensor] = None):
+                   variance_noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0):
         c = self.config
         if self.num_inference_steps is None:
             raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
@@ -372,8 +465,10 @@ class DPMSolverScheduler(_FusedStepScheduler):
             if variance_noise is None:
                 variance_noise = sdist.randn(x.shape, generator)
             z = self._prep(variance_noise.to(x.device))
-        prev, x0, m0 = self._launch(self._prep(model_output), cfg, guidance_scale, x, m1, m2, z,
-                                    (px, pe, p1, p2, pn, yx, ye, mx, me), want_y2=True, want_m=True)
+        e = self._prep(model_output)
+        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x)
+        prev, x0, m0 = self._launch(e, cfg, guidance_scale, x, m1, m2, z, (px, pe, p1, p2, pn, yx, ye, mx, me),
+                                    want_y2=True, want_m=True, k=k)
         for k in range(c.solver_order - 1):
             self.model_outputs[k] = self.model_outputs[k + 1]
         self.model_outputs[-1] = m0
@@ -390,13 +485,14 @@ class LCMScheduler(_FusedStepScheduler):
     _own_defaults = dict(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                          trained_betas=None, original_inference_steps=50, clip_sample=False, set_alpha_to_one=True,
                          steps_offset=0, prediction_type="epsilon", thresholding=False, timestep_spacing="leading",
-                         timestep_scaling=10.0)
+                         timestep_scaling=10.0, rescale_betas_zero_snr=False)
     _accepted = tuple(_own_defaults)
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
-        if self.config.prediction_type != "epsilon" or self.config.clip_sample or self.config.thresholding:
-            raise NotImplementedError("only epsilon prediction without clipping is on the hot path")
+        if self.config.clip_sample or self.config.thresholding:
+            raise NotImplementedError("clip_sample / thresholding are not on the hot path")
+        self._check_prediction_type()
         self.final_alpha_cumprod = 1.0 if self.config.set_alpha_to_one else float(self.alphas_cumprod[0])
 
     def set_timesteps(self, num_inference_steps: int, device=None, original_inference_steps=None):
@@ -407,10 +503,11 @@ class LCMScheduler(_FusedStepScheduler):
         k = c.num_train_timesteps // original
         origin = (np.asarray(list(range(1, int(original) + 1))) * k - 1)[::-1].copy()
         idx = np.floor(np.linspace(0, len(origin), num=num_inference_steps, endpoint=False)).astype(np.int64)
+        self._refuse_epsilon_at_zero_snr(origin[idx])
         self._set(origin[idx], device)
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   noise: Optional[torch.Tensor] = None):
+                   noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0):
         if self.num_inference_steps is None:
             raise ValueError("run set_timesteps first")
         if self._step_index is None:
@@ -423,7 +520,7 @@ class LCMScheduler(_FusedStepScheduler):
         st = t * self.config.timestep_scaling
         c_skip = 0.25 / (st * st + 0.25)
         c_out = st / math.sqrt(st * st + 0.25)
-        dx, de = 1.0 / math.sqrt(a), -math.sqrt(1.0 - a) / math.sqrt(a)
+        dx, de, _, _ = prediction_coefs(self.config.prediction_type, math.sqrt(a), math.sqrt(1.0 - a))
         yx, ye = c_out * dx + c_skip, c_out * de            # "denoised"
         x = self._prep(sample)
         last = i == self.num_inference_steps - 1
@@ -434,7 +531,9 @@ class LCMScheduler(_FusedStepScheduler):
                 noise = sdist.randn(x.shape, generator)
             z = self._prep(noise.to(x.device))
             coef = (math.sqrt(ap) * yx, math.sqrt(ap) * ye, 0, 0, math.sqrt(1.0 - ap), yx, ye, 0, 0)
-        prev, den, _ = self._launch(self._prep(model_output), cfg, guidance_scale, x, None, None, z, coef)
+        e = self._prep(model_output)
+        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x)
+        prev, den, _ = self._launch(e, cfg, guidance_scale, x, None, None, z, coef, k=k)
         self._step_index += 1
         return prev, den
 
@@ -454,9 +553,11 @@ class PNDMScheduler(_FusedStepScheduler):
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
-        if not self.config.skip_prk_steps or self.config.prediction_type != "epsilon" or \
-                self.config.timestep_spacing != "leading":
-            raise NotImplementedError("only the SD-1.5 PLMS configuration (skip_prk_steps, epsilon, leading) is built")
+        if not self.config.skip_prk_steps or self.config.timestep_spacing != "leading":
+            raise NotImplementedError("only the SD-1.5 PLMS configuration (skip_prk_steps, leading) is built")
+        if self.config.prediction_type not in ("epsilon", "v_prediction"):       # as upstream's _get_prev_sample
+            raise ValueError(f"prediction_type given as {self.config.prediction_type} must be one of `epsilon` or "
+                             "`v_prediction`")
         self.final_alpha_cumprod = 1.0 if self.config.set_alpha_to_one else float(self.alphas_cumprod[0])
         self.ets: List[torch.Tensor] = []
         self.counter = 0
@@ -472,13 +573,19 @@ class PNDMScheduler(_FusedStepScheduler):
         self.ets, self.counter, self.cur_sample = [], 0, None
 
     def _prev_coefs(self, t: int, prev_t: int):
+        """(sample coefficient, model-output coefficient) of ``_get_prev_sample``.  v-prediction: upstream converts the
+        PLMS-combined output m to eps = sqrt(a_t)*m + sqrt(1 - a_t)*sample there, which is folded into the two."""
         a_t = float(self.alphas_cumprod[t])
         a_p = float(self.alphas_cumprod[prev_t]) if prev_t >= 0 else self.final_alpha_cumprod
         sample_coeff = math.sqrt(a_p / a_t)
         denom = a_t * math.sqrt(1 - a_p) + math.sqrt(a_t * (1 - a_t) * a_p)
-        return sample_coeff, -(a_p - a_t) / denom
+        k = -(a_p - a_t) / denom
+        if self.config.prediction_type == "v_prediction":
+            return sample_coeff + k * math.sqrt(1.0 - a_t), k * math.sqrt(a_t)
+        return sample_coeff, k
 
-    def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None):
+    def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
+                   guidance_rescale: float = 0.0):
         if self.num_inference_steps is None:
             raise ValueError("run set_timesteps first")
         t = int(timestep)
@@ -486,6 +593,7 @@ class PNDMScheduler(_FusedStepScheduler):
         prev_t = t - ratio
         x = self._prep(sample)
         e = self._prep(model_output)
+        kr = self._rescale(e, cfg, guidance_scale, guidance_rescale, x)
         hist = self.ets
         if self.counter != 1:
             n_hist = min(len(hist), 3)
@@ -495,7 +603,7 @@ class PNDMScheduler(_FusedStepScheduler):
             ws = [w[i + 1] if i < n_hist else 0.0 for i in range(3)]
             prev, _, e_out = self._launch(e, cfg, guidance_scale, x, ms[0], ms[1], None,
                                           (sc, k * w[0], k * ws[0], k * ws[1], 0, 0, 0, 0.0, 1.0, k * ws[2]),
-                                          want_y2=False, want_m=True, m3=ms[2])
+                                          want_y2=False, want_m=True, m3=ms[2], k=kr)
             self.ets = (hist + [e_out])[-4:]
             if self.counter == 0:
                 self.cur_sample = x
@@ -503,7 +611,7 @@ class PNDMScheduler(_FusedStepScheduler):
             # second call (same timestep again): average with the first prediction, restart from cur_sample
             sc, k = self._prev_coefs(t + ratio, t)
             prev, _, _ = self._launch(e, cfg, guidance_scale, self.cur_sample, hist[-1], None, None,
-                                      (sc, 0.5 * k, 0.5 * k, 0, 0, 0, 0, 0, 0, 0), want_y2=False, want_m=False)
+                                      (sc, 0.5 * k, 0.5 * k, 0, 0, 0, 0, 0, 0, 0), want_y2=False, want_m=False, k=kr)
             self.cur_sample = None
         self.counter += 1
         return (prev,)
@@ -514,15 +622,31 @@ class PNDMScheduler(_FusedStepScheduler):
         return (prev.to(out_dtype),)
 
 
+# the checkpoint's scheduler class (``_class_name`` of scheduler/scheduler_config.json) -> its registry key
+CHECKPOINT_SCHEDULERS = {"PNDMScheduler": "pndm_scheduler", "DDIMScheduler": "ddim_scheduler",
+                         "DPMSolverMultistepScheduler": "dpm_solver_scheduler", "LCMScheduler": "lcm_scheduler"}
+
+
+def checkpoint_scheduler_name(config) -> str:
+    """Registry key of the scheduler class a checkpoint's config names (PNDM when it names none, as SD-1.5 ships);
+    raises NotImplementedError for a class that is not built."""
+    cls = config.get("_class_name", "PNDMScheduler")
+    if cls not in CHECKPOINT_SCHEDULERS:
+        raise NotImplementedError(f"the checkpoint's scheduler class {cls!r} is not built "
+                                  f"(built: {sorted(CHECKPOINT_SCHEDULERS)})")
+    return CHECKPOINT_SCHEDULERS[cls]
+
+
 class PNDMConfigStub:
     """The checkpoint's scheduler config holder: ``from_config(model.scheduler.config)``
-    (``src/experiments/base_experiment.py:69-72``) reads the SD-1.5 PNDM config from it.  Call
-    ``PNDMScheduler.from_config(stub.config)`` to actually step with PNDM."""
+    (``src/experiments/base_experiment.py:69-72``) reads the checkpoint's scheduler config from it -- SD-1.5's PNDM
+    config unless a local checkpoint ships its own (``weights.load_scheduler_config``).  Call
+    ``schedulers_registry[checkpoint_scheduler_name(stub.config)].from_config(stub.config)`` to actually step with it."""
     order = 1
     init_noise_sigma = 1.0
 
-    def __init__(self):
-        self.config = SchedulerConfig(SD15_SCHEDULER_CONFIG)
+    def __init__(self, config=None):
+        self.config = SchedulerConfig(SD15_SCHEDULER_CONFIG if config is None else config)
 
     def set_timesteps(self, *a, **k):
         raise NotImplementedError("this is only the checkpoint's scheduler CONFIG; build a scheduler with "

@@ -139,6 +139,21 @@ def make_synthetic_state_dict(cfg: UNetConfig, seed: int = 1234) -> Dict[str, to
     return dict(sd)
 
 
+def load_scheduler_config(model_dir: str) -> dict:
+    """The checkpoint's scheduler config: ``scheduler/scheduler_config.json`` of a local diffusers directory over the
+    SD-1.5 defaults (``schedulers.SD15_SCHEDULER_CONFIG``).  Keys starting with ``_`` are dropped except ``_class_name``
+    (the checkpoint's scheduler class, ``schedulers.checkpoint_scheduler_name``).  No file: the SD-1.5 config."""
+    import json
+    from .schedulers import SD15_SCHEDULER_CONFIG
+    cfg = dict(SD15_SCHEDULER_CONFIG)
+    path = os.path.join(model_dir, "scheduler", "scheduler_config.json")
+    if os.path.isfile(path):
+        with open(path) as f:
+            raw = json.load(f)
+        cfg.update({k: v for k, v in raw.items() if not k.startswith("_") or k == "_class_name"})
+    return cfg
+
+
 def load_unet_config(model_dir: str) -> "UNetConfig | None":
     """``<dir>/unet/config.json`` of a LOCAL diffusers checkpoint -> ``UNetConfig`` (None if the file is absent: the
     SD-1.5 defaults then apply).  Only the keys this build implements are read; a checkpoint that needs anything else
