@@ -51,6 +51,11 @@ typedef struct sd_unet_config {
     int weight_dtype;
     float fp8_act_scale_norm;    /* GroupNorm(+SiLU) / LayerNorm outputs */
     float fp8_act_scale_ff;      /* GEGLU outputs (input of ff.net.2) */
+    /* LCM-distilled UNets (diffusers time_cond_proj_dim; 0 = none, SD-1.5): the time embedding carries
+     * time_embedding.cond_proj.weight [block_out_channels[0], time_cond_proj_dim] and adds cond_proj(cond) to the timestep
+     * sinusoid before linear_1 (sd_unet_set_timestep_cond).  A multiple of 8.  VAE and CLIP handles ignore it.
+     * (Appended under ABI 3: zero-initialise the struct.) */
+    int time_cond_proj_dim;
 } sd_unet_config;
 enum { SD_DTYPE_BF16 = 0, SD_DTYPE_FP8_E4M3 = 1 };
 
@@ -115,6 +120,15 @@ int sd_unet_set_context(sd_unet* u, void* stream, const float* encoder_hidden_st
                         int cache_branch_id, void* workspace, long long workspace_bytes);
 int sd_unet_set_context_hw(sd_unet* u, void* stream, const float* encoder_hidden_states, int unet_batch,
                            int cache_branch_id, int latent_h, int latent_w, void* workspace, long long workspace_bytes);
+
+/* Timestep condition of an LCM-distilled UNet (time_cond_proj_dim > 0; src/models.py:195-202,231 of the reference pass
+ * timestep_cond = get_guidance_scale_embedding(guidance_scale - 1)).  `cond`: device fp32 [time_cond_proj_dim], 16-byte
+ * aligned.  One GEMV on `stream` stores row = cond_proj.weight . cond ([block_out_channels[0]] fp32, fp32 accumulation) in
+ * the handle; every later forward of the handle (any batch, size or DeepCache branch) adds the row to its timestep sinusoid
+ * -- the same launches as without it.  One condition per forward, as there is one timestep per forward.  cond = NULL clears
+ * it: forwards are then those of a UNet without cond_proj (what diffusers does for timestep_cond=None).  Issue it on the
+ * stream of the forwards that should see it (or order the streams). */
+int sd_unet_set_timestep_cond(sd_unet* u, void* stream, const float* cond);
 
 enum { SD_CACHE_OFF = 0, SD_CACHE_FULL_AND_STORE = 1, SD_CACHE_SKIP = 2 };
 
@@ -296,6 +310,10 @@ int sd_op_conv_out(void* stream, const void* x, const void* Wp, const float* bia
                    int Cin, int Cout);
 int sd_op_time_embedding(void* stream, float t, const void* W1, const float* b1, const void* W2, const float* b2,
                          float* scratch, float* temb, int dim_in, int dim);
+/* the two kernels of a conditioned time embedding: row = Wc . cond (Wc bf16 [dim][cond_dim], cond fp32 [cond_dim], 16-byte
+ * aligned, cond_dim a multiple of 8), then emb = [cos(t f_k) | sin(t f_k)] + row (fp32 [dim], dim even) */
+int sd_op_timestep_cond(void* stream, float t, const float* cond, const void* Wc, float* row, float* emb, int cond_dim,
+                        int dim);
 
 /* Fused prompt cross-attention of one transformer block (src/models.py:227-235 -> diffusers Attention over the 77 prompt
  * keys): Y = R + sum_h softmax_L(X A_h) B_h + b_o in ONE launch, probabilities kept in registers.  8 heads x 80 key

@@ -29,6 +29,7 @@ class SdUnetConfig(C.Structure):
         ("attn_levels", C.c_int * 8), ("cross_attention_dim", C.c_int), ("num_heads", C.c_int),
         ("norm_num_groups", C.c_int), ("norm_eps", C.c_float), ("context_len", C.c_int),
         ("weight_dtype", C.c_int), ("fp8_act_scale_norm", C.c_float), ("fp8_act_scale_ff", C.c_float),
+        ("time_cond_proj_dim", C.c_int),
     ]
 
 
@@ -71,6 +72,7 @@ _SIGS = {
     "sd_unet_set_fp8_scale": (_i, [_vp, C.c_char_p, _f]),
     "sd_unet_workspace_bytes": (_ll, [_vp, _i, _i]),
     "sd_unet_set_context": (_i, [_vp, _vp, _vp, _i, _i, _vp, _ll]),
+    "sd_unet_set_timestep_cond": (_i, [_vp, _vp, _vp]),
     "sd_unet_forward": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _ll, _i, _i]),
     "sd_unet_workspace_bytes_hw": (_ll, [_vp, _i, _i, _i, _i]),
     "sd_unet_set_context_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _ll]),
@@ -107,6 +109,7 @@ _SIGS = {
     "sd_op_conv_in": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "sd_op_conv_out": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "sd_op_time_embedding": (_i, [_vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i]),
+    "sd_op_timestep_cond": (_i, [_vp, _f, _vp, _vp, _vp, _vp, _i, _i]),
     "sd_op_ln_partials": (_i, [_i, _i, _i]),
     "sd_op_gemm_rowstats": (_i, [_vp, _vp, _ll, _vp, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _vp]),
     "sd_op_gemm_plan": (_i, [_vp, _vp, _ll, _vp, _ll, _i, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _f,

@@ -157,6 +157,8 @@ int sd_launch_attention(const AttnArgs& a, hipStream_t stream);
 int sd_launch_gemv(const float* x, const bf16_t* W, const float* b, float* y, int N, int K, int silu_in,
                    hipStream_t stream);
 int sd_launch_timestep_sinusoid(float t, float* out, int dim, hipStream_t stream);
+// out[i] = sinusoid(t)[i] + row[i]  (time embedding of a UNet with cond_proj, the row = cond_proj . condition)
+int sd_launch_timestep_sinusoid_row(float t, const float* row, float* out, int dim, hipStream_t stream);
 int sd_launch_f32_to_bf16(const float* src, bf16_t* dst, long n, hipStream_t stream);
 // dst[b][c][r'] = src[b][r][c]; perm16: r' = r with bits 2 and 3 swapped (the k order in which a 32x32 MFMA
 // accumulator tile is consumed as the next product's operand, see xattn.hip)

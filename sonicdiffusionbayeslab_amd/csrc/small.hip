@@ -7,14 +7,26 @@
 namespace {
 
 // ---- timestep sinusoid: flip_sin_to_cos=True, freq_shift=0 -> [cos(t f_k) | sin(t f_k)] ----
-__global__ void sinusoid_kernel(float t, float* __restrict__ out, int dim) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ float sinusoid_at(float t, int i, int dim) {
     const int half = dim / 2;
-    if (i >= dim) return;
     const int k = i < half ? i : i - half;
     const float f = expf(-9.210340371976184f * (float)k / (float)half);  // ln(10000)
     const float e = t * f;
-    out[i] = i < half ? cosf(e) : sinf(e);
+    return i < half ? cosf(e) : sinf(e);
+}
+
+__global__ void sinusoid_kernel(float t, float* __restrict__ out, int dim) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= dim) return;
+    out[i] = sinusoid_at(t, i, dim);
+}
+
+// the same plus a row (LCM-distilled UNets: TimestepEmbedding adds cond_proj(condition) to the sinusoid before linear_1;
+// the row is that projection, computed once per condition by gemv_kernel)
+__global__ void sinusoid_row_kernel(float t, const float* __restrict__ row, float* __restrict__ out, int dim) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= dim) return;
+    out[i] = sinusoid_at(t, i, dim) + row[i];
 }
 
 // ---- GEMV: one wave per output row --------------------------------------------------------
@@ -359,6 +371,13 @@ int sd_launch_f32_to_bf16(const float* src, bf16_t* dst, long n, hipStream_t str
 int sd_launch_timestep_sinusoid(float t, float* out, int dim, hipStream_t stream) {
     SD_REQUIRE(out && dim > 0 && dim % 2 == 0, "sinusoid: bad dim %d", dim);
     hipLaunchKernelGGL(sinusoid_kernel, dim3((dim + 255) / 256), dim3(256), 0, stream, t, out, dim);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sd_launch_timestep_sinusoid_row(float t, const float* row, float* out, int dim, hipStream_t stream) {
+    SD_REQUIRE(row && out && dim > 0 && dim % 2 == 0, "sinusoid_row: bad operands (dim %d)", dim);
+    hipLaunchKernelGGL(sinusoid_row_kernel, dim3((dim + 255) / 256), dim3(256), 0, stream, t, row, out, dim);
     SD_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -36,7 +36,8 @@ void sd_set_error(const char* fmt, ...) {
 }
 extern "C" const char* sd_last_error(void) { return g_err; }
 // (the latent-size entry points -- the _hw forms, sd_op_conv3x3_kernel, sd_op_softmax_rows -- are additions under version 3:
-// resolve them by name)
+// resolve them by name; so are sd_unet_set_timestep_cond, sd_op_timestep_cond and sd_unet_config.time_cond_proj_dim, appended
+// last: a caller zero-initialises the struct)
 extern "C" int sd_abi_version(void) { return 3; }   // 2: sd_unet_config.weight_dtype, fp8 entry points; 3: round-2 fusion entry points
 
 static void* g_zero_page = nullptr;
@@ -230,6 +231,11 @@ struct sd_unet {
     int last_h = 0, last_w = 0;                          // latent size of the last forward (sd_unet_debug_tensor)
     std::unordered_map<std::string, long> tproj_off;  // resnet prefix -> float index into tproj vector
     long tproj_total = 0;
+    // LCM-distilled UNets (cfg.time_cond_proj_dim > 0): cond_proj . condition, [c0] fp32, written by sd_unet_set_timestep_cond.
+    // Owned by the handle (not the workspace) so that it outlives plans, sizes and DeepCache branches; while cond_set, every
+    // forward's OP_SINUSOID adds it to the sinusoid.
+    float* dcond = nullptr;
+    bool cond_set = false;
 };
 
 namespace {
@@ -297,6 +303,7 @@ void enumerate_params(sd_unet* u) {
     const int c0 = c.block_out_channels[0], temb = 4 * c0, nl = c.num_levels;
     e.add("time_embedding.linear_1.weight", {temb, c0});
     e.add("time_embedding.linear_1.bias", {temb});
+    if (c.time_cond_proj_dim > 0) e.add("time_embedding.cond_proj.weight", {c0, c.time_cond_proj_dim});
     e.add("time_embedding.linear_2.weight", {temb, temb});
     e.add("time_embedding.linear_2.bias", {temb});
     e.add("conv_in.weight", {c0, c.in_channels, 3, 3});
@@ -890,6 +897,7 @@ int pack_all(sd_unet* u) {
     const int c0 = c.block_out_channels[0], temb = 4 * c0, nl = c.num_levels;
     pk.bf16_same("time_embedding.linear_1.weight"); pk.f32("time_embedding.linear_1.bias");
     pk.bf16_same("time_embedding.linear_2.weight"); pk.f32("time_embedding.linear_2.bias");
+    if (c.time_cond_proj_dim > 0) pk.bf16_same("time_embedding.cond_proj.weight");     // (gemv_kernel operand, like linear_1)
     {   // conv_in: [O][I][3][3] -> Wt[k = ic*9+tap][O] fp32
         const auto& d = pk.P("conv_in.weight");
         const int O = c0, I = c.in_channels;
@@ -1634,6 +1642,7 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
     const char* wb = u->dweights;
     switch (o.kind) {
         case OP_SINUSOID:
+            if (u->cond_set) return sd_launch_timestep_sinusoid_row(timestep, u->dcond, (float*)T(o.out), o.N, stream);
             return sd_launch_timestep_sinusoid(timestep, (float*)T(o.out), o.N, stream);
         case OP_GEMV:
             return sd_launch_gemv((const float*)T(o.x1), (const bf16_t*)(wb + o.w), (const float*)(wb + o.b),
@@ -1773,6 +1782,9 @@ extern "C" int sd_unet_create(const sd_unet_config* cfg, sd_unet** out) {
     SD_REQUIRE(cfg->weight_dtype == SD_DTYPE_BF16 || cfg->weight_dtype == SD_DTYPE_FP8_E4M3,
                "sd_unet_create: weight_dtype %d (0 = bf16, 1 = fp8 e4m3)", cfg->weight_dtype);
     SD_REQUIRE(cfg->fp8_act_scale_norm >= 0.f && cfg->fp8_act_scale_ff >= 0.f, "sd_unet_create: negative fp8 activation scale");
+    SD_REQUIRE(cfg->time_cond_proj_dim >= 0 && cfg->time_cond_proj_dim % 8 == 0,
+               "sd_unet_create: time_cond_proj_dim %d must be 0 (none) or a positive multiple of 8 (the GEMV reads 8 at a time)",
+               cfg->time_cond_proj_dim);
     sd_unet* u = new sd_unet();   // no device work here: parameter enumeration also runs on a CPU-only box
     u->cfg = *cfg;
     u->fp8 = cfg->weight_dtype == SD_DTYPE_FP8_E4M3;
@@ -1799,6 +1811,7 @@ extern "C" int sd_vae_create(const sd_unet_config* cfg, sd_unet** out) {
     sd_unet* u = new sd_unet();
     u->kind = 1;
     u->cfg = *cfg;
+    u->cfg.time_cond_proj_dim = 0;      // (a UNet field)
     u->debug_taps = getenv("SD_DEBUG_TAPS") != nullptr;
     enumerate_params_vae(u);
     *out = u;
@@ -1870,6 +1883,7 @@ extern "C" int sd_clip_encode(sd_unet* u, void* stream, const int* input_ids, in
 extern "C" void sd_unet_destroy(sd_unet* u) {
     if (!u) return;
     if (u->dweights) (void)hipFree(u->dweights);
+    if (u->dcond) (void)hipFree(u->dcond);
     delete u;
 }
 
@@ -1923,6 +1937,8 @@ extern "C" int sd_unet_finalize(sd_unet* u) {
     if (ensure_zero_page()) return -2;
     SD_CHECK_HIP(hipMalloc((void**)&u->dweights, u->hblob.size()));
     SD_CHECK_HIP(hipMemcpy(u->dweights, u->hblob.data(), u->hblob.size(), hipMemcpyHostToDevice));
+    if (u->kind == 0 && u->cfg.time_cond_proj_dim > 0)
+        SD_CHECK_HIP(hipMalloc((void**)&u->dcond, (size_t)u->cfg.block_out_channels[0] * sizeof(float)));
     u->hblob.release();
     for (auto& p : u->params) std::vector<float>().swap(p.data);
     u->finalized = true;
@@ -2035,6 +2051,23 @@ extern "C" int sd_unet_set_context_hw(sd_unet* u, void* stream, const float* ehs
             if (f.perm && (rc = sd_launch_retile32(tmp, bw_dst, unet_batch, C, NP, 32, (hipStream_t)stream))) return rc;
         }
     }
+    return 0;
+}
+
+extern "C" int sd_unet_set_timestep_cond(sd_unet* u, void* stream, const float* cond) {
+    SD_REQUIRE(u && u->kind == 0, "set_timestep_cond: not a UNet handle");
+    if (!cond) {
+        u->cond_set = false;
+        return 0;
+    }
+    const int d = u->cfg.time_cond_proj_dim, c0 = u->cfg.block_out_channels[0];
+    SD_REQUIRE(d > 0, "set_timestep_cond: the UNet has no time_embedding.cond_proj (time_cond_proj_dim = 0)");
+    SD_REQUIRE(u->finalized && u->dcond, "set_timestep_cond: parameters not finalized");
+    SD_REQUIRE(((uintptr_t)cond & 15) == 0, "set_timestep_cond: cond must be 16-byte aligned");
+    const int rc = sd_launch_gemv(cond, (const bf16_t*)(u->dweights + u->woff.at("time_embedding.cond_proj.weight")), nullptr,
+                                  u->dcond, c0, d, 0, (hipStream_t)stream);
+    if (rc) return rc;
+    u->cond_set = true;
     return 0;
 }
 
@@ -2620,6 +2653,15 @@ extern "C" int sd_op_time_embedding(void* stream, float t, const void* W1, const
     if ((rc = sd_launch_timestep_sinusoid(t, scratch, dim_in, (hipStream_t)stream))) return rc;
     if ((rc = sd_launch_gemv(scratch, (const bf16_t*)W1, b1, scratch + dim_in, dim, dim_in, 0, (hipStream_t)stream))) return rc;
     return sd_launch_gemv(scratch + dim_in, (const bf16_t*)W2, b2, temb, dim, dim, 1, (hipStream_t)stream);
+}
+
+extern "C" int sd_op_timestep_cond(void* stream, float t, const float* cond, const void* Wc, float* row, float* emb,
+                                   int cond_dim, int dim) {
+    SD_REQUIRE(cond && Wc && row && emb, "timestep_cond: null operand");
+    SD_REQUIRE(((uintptr_t)cond & 15) == 0 && cond_dim > 0, "timestep_cond: cond must be 16-byte aligned, cond_dim > 0");
+    int rc;
+    if ((rc = sd_launch_gemv(cond, (const bf16_t*)Wc, nullptr, row, dim, cond_dim, 0, (hipStream_t)stream))) return rc;
+    return sd_launch_timestep_sinusoid_row(t, row, emb, dim, (hipStream_t)stream);
 }
 
 // ---- fp8-e4m3 operand path, operator level (parity tests of SD_DTYPE_FP8_E4M3) ---------------------------------

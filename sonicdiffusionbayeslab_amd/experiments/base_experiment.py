@@ -64,6 +64,8 @@ class BaseMethod(ABC):
         extra = {}
         if self.config.model.get("weight_dtype", None) is not None:      # key of this build: "bf16" | "fp8"
             extra["weight_dtype"] = self.config.model.weight_dtype
+        if self.config.model.get("time_cond_proj_dim", None) is not None:   # key of this build: shapes a hub name's stand-in
+            extra["time_cond_proj_dim"] = int(self.config.model.time_cond_proj_dim)
         self.model = models_registry[model_name].from_pretrained(
             self.config.model.pretrained_model,
             timestamps=self.config.model.get("timestamps", None),

@@ -23,6 +23,7 @@ exist offline) -- ``weights_source`` / the reports say which.
 from __future__ import annotations
 
 import hashlib
+import math
 import os
 import time
 from dataclasses import dataclass
@@ -66,6 +67,21 @@ class SyntheticTextEncoder:
 
 class _VaeConfig:
     scaling_factor = 0.18215
+
+
+def get_guidance_scale_embedding(w, embedding_dim: int = 512, dtype=torch.float32) -> torch.Tensor:
+    """Guidance-scale embedding of LCM-distilled UNets (diffusers ``LatentConsistencyModelPipeline``; the reference feeds
+    ``w = guidance_scale - 1``, ``src/models.py:195-202``): ``w`` (scalar or [n]) -> [n, embedding_dim] =
+    ``[sin(1000 w f_k) | cos(1000 w f_k)]``, ``f_k = exp(-k ln(10000) / (half - 1))``, one zero column appended for an odd
+    dimension.  Not the timestep sinusoid (that one is ``[cos | sin]`` with denominator ``half``)."""
+    w = torch.as_tensor(w, dtype=torch.float32).reshape(-1) * 1000.0
+    half = embedding_dim // 2
+    freq = torch.exp(torch.arange(half, dtype=dtype) * -(math.log(10000.0) / (half - 1)))
+    emb = w.to(dtype)[:, None] * freq[None, :]
+    emb = torch.cat([torch.sin(emb), torch.cos(emb)], dim=1)
+    if embedding_dim % 2 == 1:
+        emb = torch.nn.functional.pad(emb, (0, 1))
+    return emb
 
 
 def postprocess_images(image01: torch.Tensor, output_type: str):
@@ -124,14 +140,23 @@ class StableDiffusionModel:
         resolved offline, in which case SD-1.5-shaped synthetic weights seeded
         by ``SD_AMD_WEIGHTS_SEED`` (default 1234) are used and ``weights_source`` says so."""
         path = os.environ.get("SD_AMD_MODEL_DIR") or str(pretrained_model_name_or_path)
+        # time_cond_proj_dim (YAML model.time_cond_proj_dim): shapes the synthetic stand-in of a hub name; a local checkpoint's
+        # unet/config.json decides, and a different value is an error
+        tcond = kwargs.pop("time_cond_proj_dim", None)
         if os.path.isdir(path):
             has_clip = all(os.path.exists(os.path.join(path, *p)) for p in (("tokenizer", "vocab.json"),
                                                                             ("tokenizer", "merges.txt"),
                                                                             ("text_encoder", "model.safetensors")))
             kwargs.setdefault("scheduler", PNDMConfigStub(load_scheduler_config(path)))   # the checkpoint's own scheduler config
-            return cls(unet_config=load_unet_config(path), state_dict=load_unet_state_dict(path), source=f"local:{path}",
+            ucfg = load_unet_config(path)
+            have = ucfg.time_cond_proj_dim if ucfg is not None else None
+            if tcond is not None and tcond != have:
+                raise ValueError(f"time_cond_proj_dim={tcond} conflicts with the checkpoint {path!r} (its UNet has {have})")
+            return cls(unet_config=ucfg, state_dict=load_unet_state_dict(path), source=f"local:{path}",
                        clip_dir=path if has_clip else None, **kwargs)
         seed = int(os.environ.get("SD_AMD_WEIGHTS_SEED", "1234"))
+        if tcond is not None:
+            kwargs.setdefault("unet_config", UNetConfig(time_cond_proj_dim=int(tcond)))
         return cls(weights_seed=seed, source=f"synthetic(seed={seed}) for {pretrained_model_name_or_path}", **kwargs)
 
     def _ensure_unet(self):
@@ -244,6 +269,14 @@ class StableDiffusionModel:
             return result, execution_time, x0_preds
         return result, x0_preds
 
+    def guidance_condition(self, guidance_scale: float) -> Optional[torch.Tensor]:
+        """``timestep_cond`` of the reference (``src/models.py:195-202``): the guidance embedding of ``guidance_scale - 1``
+        ([1, time_cond_proj_dim] fp32) when the UNet has ``time_cond_proj_dim``, else None."""
+        d = self.unet_config.time_cond_proj_dim
+        if d is None:
+            return None
+        return get_guidance_scale_embedding(float(guidance_scale) - 1.0, d)
+
     # -- pieces shared by the four pipelines ------------------------------------------------------
     SIZE_RULE = "height and width must each be a multiple of 64 in [256, 1024]"
 
@@ -275,6 +308,7 @@ class StableDiffusionModel:
             self.calibrate_fp8()        # fp8 handles only; shared by the four pipelines (all enter through _begin)
         device = self.unet.device
         self._guidance_scale = guidance_scale
+        self.unet.set_timestep_cond(self.guidance_condition(guidance_scale))      # (None clears it)
         if prompt is not None and isinstance(prompt, str):
             batch_size = 1
         elif prompt is not None:
@@ -326,13 +360,15 @@ class StableDiffusionModel:
     FP8_CALIBRATION_SEED = 20240229
     FP8_CALIBRATION_PROMPTS = ("", "a photograph of an astronaut riding a horse")
     FP8_CALIBRATION_TIMESTEPS = (999.0, 499.0, 1.0)
+    FP8_CALIBRATION_GUIDANCE = 8.0      # UNets with time_cond_proj_dim: the guidance scale the calibration forwards embed
 
     def calibrate_fp8(self, scales=None, margin: float = 2.0):
         """fp8 handles (``weight_dtype="fp8"``): fix the per-tensor e4m3 activation scales, ONCE and deterministically.
         ``scales`` given (e.g. saved from an earlier run: ``model.fp8_scales``): they are loaded through
         ``sd_unet_set_fp8_scale``.  Otherwise they come from the amax observed on a fixed calibration batch -- two latents
         drawn from a generator seeded with ``FP8_CALIBRATION_SEED``, the text encoder's embeddings of two fixed prompts, no
-        CFG, at three fixed timesteps (``sd_unet_calibrate_fp8``, margin 2) -- so every rank of a sharded run, whatever its
+        CFG, the guidance embedding of ``FP8_CALIBRATION_GUIDANCE`` for a UNet with ``time_cond_proj_dim``, at three fixed
+        timesteps (``sd_unet_calibrate_fp8``, margin 2) -- so every rank of a sharded run, whatever its
         shard, and every world size end up with the SAME scales (dist.py's invariant: an image does not depend on the
         world size; round 3 calibrated on the first call's own inputs, which differ per rank).  Runs outside any timed
         region; ``SD_AMD_FP8_CALIBRATE=0`` keeps the static defaults (clipping at |x| > 56 / 224)."""
@@ -354,8 +390,10 @@ class StableDiffusionModel:
             branch = self.unet.cache_branch_id
             self.unet.set_deepcache(-1)             # the calibration pass runs the plan without DeepCache
             self.unet.set_context(ctx)
+            self.unet.set_timestep_cond(self.guidance_condition(self.FP8_CALIBRATION_GUIDANCE))
             self.unet.calibrate_fp8(lat, 2, list(self.FP8_CALIBRATION_TIMESTEPS), margin=margin)
-            self.unet.set_deepcache(branch)         # (the caller sets its own context next)
+            self.unet.set_timestep_cond(None)
+            self.unet.set_deepcache(branch)         # (the caller sets its own context and condition next)
             how = "calibrated on the fixed seeded batch"
         self.fp8_scales = dict(self.unet.fp8_scales())
         self._fp8_calibrated = True

@@ -34,6 +34,7 @@ def _c_config(cfg: UNetConfig, weight_dtype: str = "bf16", fp8_act_scales=(0.0, 
     c.layers_per_block = cfg.layers_per_block
     c.cross_attention_dim, c.num_heads = cfg.cross_attention_dim, cfg.num_heads
     c.norm_num_groups, c.norm_eps, c.context_len = cfg.norm_num_groups, cfg.norm_eps, cfg.context_len
+    c.time_cond_proj_dim = cfg.time_cond_proj_dim or 0
     return c
 
 
@@ -76,6 +77,7 @@ class HipUNet2DConditionModel:
         self._ws_key = None
         self._ctx_key = None
         self._ctx_keepalive = None
+        self._cond = None                   # the condition set on the handle (device fp32 [time_cond_proj_dim]) or None
         self.cache_branch_id = -1
 
     def __del__(self):
@@ -130,6 +132,27 @@ class HipUNet2DConditionModel:
                    "sd_unet_set_context_hw")
         self._ctx_keepalive = ehs
         self._ctx_key = (encoder_hidden_states.data_ptr(), encoder_hidden_states._version, ub, h, w)
+
+    def set_timestep_cond(self, cond: Optional[torch.Tensor]) -> None:
+        """Condition of an LCM-distilled UNet (``time_cond_proj_dim`` set): ``cond`` [d] or [1, d], e.g.
+        ``get_guidance_scale_embedding(guidance_scale - 1, d)``.  Every later forward adds ``cond_proj(cond)`` to its timestep
+        sinusoid (one GEMV now, none per forward).  ``None`` clears it: forwards then skip the projection, as diffusers does
+        for ``timestep_cond=None``."""
+        if cond is None:
+            _lib.check(self._lib.sd_unet_set_timestep_cond(self._handle, _lib.current_stream(), None), "sd_unet_set_timestep_cond")
+            self._cond = None
+            return
+        d = self.config.time_cond_proj_dim
+        if d is None:
+            raise ValueError("timestep_cond given, but this UNet has no time_embedding.cond_proj (time_cond_proj_dim is None)")
+        row = cond.detach().to(self.device, torch.float32).reshape(-1).contiguous()
+        if row.numel() != d:
+            raise ValueError(f"timestep_cond must be [{d}] or [1, {d}], got {tuple(cond.shape)}")
+        if row.data_ptr() % 16:
+            row = row.clone()
+        _lib.check(self._lib.sd_unet_set_timestep_cond(self._handle, _lib.current_stream(), row.data_ptr()),
+                   "sd_unet_set_timestep_cond")
+        self._cond = row                    # (also keeps the operand alive until the GEMV has run)
 
     # -- forward ---------------------------------------------------------------------------
     def forward_latents(self, latents: torch.Tensor, unet_batch: int, timestep: float,
@@ -221,9 +244,11 @@ class HipUNet2DConditionModel:
     def __call__(self, sample: torch.Tensor, timestep, encoder_hidden_states: torch.Tensor = None,
                  timestep_cond=None, cross_attention_kwargs=None, added_cond_kwargs=None, return_dict: bool = False,
                  **kwargs):
-        """diffusers-style call of the reference loop (``src/models.py:227-235``)."""
-        if timestep_cond is not None or added_cond_kwargs is not None:
-            raise NotImplementedError("timestep_cond / added_cond_kwargs are not part of the SD-1.5 hot path")
+        """diffusers-style call of the reference loop (``src/models.py:227-235``).  ``timestep_cond`` ([B, d] or [d]) is
+        the guidance embedding of an LCM-distilled UNet: one row for the whole batch (ONE_ROW_RULE); None runs without it."""
+        if added_cond_kwargs is not None:
+            raise NotImplementedError("added_cond_kwargs is not part of the SD-1.5 hot path")
+        self._apply_timestep_cond(timestep_cond)
         h, w = sample.shape[2], sample.shape[3]
         key = (encoder_hidden_states.data_ptr(), encoder_hidden_states._version, sample.shape[0], h, w)
         if self._ctx_key != key:
@@ -231,6 +256,25 @@ class HipUNet2DConditionModel:
         t = float(timestep.item()) if torch.is_tensor(timestep) else float(timestep)
         eps = self.forward_latents(sample, sample.shape[0], t)
         return (eps.to(sample.dtype),)
+
+    ONE_ROW_RULE = "timestep_cond must be one row for the whole batch (one guidance scale per call)"
+
+    def _apply_timestep_cond(self, timestep_cond) -> None:
+        if timestep_cond is None:
+            if self._cond is not None:
+                self.set_timestep_cond(None)
+            return
+        if self.config.time_cond_proj_dim is None:
+            raise ValueError("timestep_cond given, but this UNet has no time_embedding.cond_proj (time_cond_proj_dim is None)")
+        tc = torch.as_tensor(timestep_cond).detach().to(self.device, torch.float32)
+        if tc.dim() == 2:
+            if tc.shape[0] > 1 and not bool((tc == tc[:1]).all()):
+                raise ValueError(f"{self.ONE_ROW_RULE}; got {tc.shape[0]} different rows")
+            tc = tc[0]
+        elif tc.dim() != 1:
+            raise ValueError(f"timestep_cond must be [B, d] or [d], got {tuple(tc.shape)}")
+        if self._cond is None or self._cond.shape != tc.shape or not torch.equal(self._cond, tc):
+            self.set_timestep_cond(tc)
 
     def debug_tensor(self, name: str, unet_batch: int, numel: int, height: Optional[int] = None,
                      width: Optional[int] = None) -> torch.Tensor:

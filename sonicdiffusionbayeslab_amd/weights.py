@@ -10,8 +10,8 @@ from __future__ import annotations
 
 import math
 import os
-from dataclasses import dataclass
-from typing import Dict, List, Tuple
+from dataclasses import InitVar, dataclass
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -30,7 +30,22 @@ class UNetConfig:
     norm_num_groups: int = 32
     norm_eps: float = 1e-5
     context_len: int = 77
-    time_cond_proj_dim = None  # read by the reference loop at src/models.py:196
+    # LCM-distilled UNets (diffusers ``time_cond_proj_dim``, read by the reference loop at src/models.py:195-202): the time
+    # embedding adds ``cond_proj(guidance embedding)`` to the timestep sinusoid.  None = no cond_proj (SD-1.5).  Declared as
+    # an InitVar and kept as an instance attribute: ``dataclasses.asdict`` of a config then still builds the oracle's
+    # ``UNetConfig`` (which has no such field), and ``dataclasses.replace`` carries the value over.
+    time_cond_proj_dim: InitVar[Optional[int]] = None
+
+    def __post_init__(self, time_cond_proj_dim):
+        if time_cond_proj_dim is not None and (isinstance(time_cond_proj_dim, bool) or int(time_cond_proj_dim) <= 0
+                                               or int(time_cond_proj_dim) != time_cond_proj_dim):
+            raise ValueError(f"time_cond_proj_dim={time_cond_proj_dim!r}: a positive integer or None")
+        self.time_cond_proj_dim = None if time_cond_proj_dim is None else int(time_cond_proj_dim)
+
+    def __eq__(self, other):            # (the generated one compares fields only)
+        if other.__class__ is not self.__class__:
+            return NotImplemented
+        return _shared_fields(self) == _shared_fields(other) and self.time_cond_proj_dim == other.time_cond_proj_dim
 
 
 def param_shapes(cfg: UNetConfig) -> List[Tuple[str, Tuple[int, ...]]]:
@@ -66,6 +81,8 @@ def param_shapes(cfg: UNetConfig) -> List[Tuple[str, Tuple[int, ...]]]:
         add(p + "proj_out.weight", (c, c, 1, 1)); add(p + "proj_out.bias", (c,))
 
     add("time_embedding.linear_1.weight", (temb, c0)); add("time_embedding.linear_1.bias", (temb,))
+    if cfg.time_cond_proj_dim is not None:
+        add("time_embedding.cond_proj.weight", (c0, cfg.time_cond_proj_dim))
     add("time_embedding.linear_2.weight", (temb, temb)); add("time_embedding.linear_2.bias", (temb,))
     add("conv_in.weight", (c0, cfg.in_channels, 3, 3)); add("conv_in.bias", (c0,))
     ch = c0
@@ -115,14 +132,17 @@ def make_synthetic_state_dict(cfg: UNetConfig, seed: int = 1234) -> Dict[str, to
     The values do not depend on ``sample_size`` (no parameter shape does); generating 0.86 G Gaussians takes ~10 s, so the
     result is cached per (architecture, seed) for the life of the process and every call returns a NEW dict over the same
     read-only tensors (callers replace entries -- LoRA fusion, tests -- and never write into a tensor).
+
+    ``time_cond_proj_dim`` set: ``time_embedding.cond_proj.weight`` is drawn from a generator of its own (seed
+    ``COND_PROJ_SEED_OFFSET + seed``), so every other parameter is bit-identical to the plain config's.
     """
     key = (cfg.in_channels, cfg.out_channels, tuple(cfg.block_out_channels), cfg.layers_per_block, tuple(cfg.attn_levels),
            cfg.cross_attention_dim, int(seed))
     if key in _SYNTHETIC_CACHE:
-        return dict(_SYNTHETIC_CACHE[key])
+        return _with_cond_proj(dict(_SYNTHETIC_CACHE[key]), cfg, seed)
     g = torch.Generator().manual_seed(seed)
     sd: Dict[str, torch.Tensor] = {}
-    for name, shape in param_shapes(cfg):
+    for name, shape in param_shapes(UNetConfig(**_shared_fields(cfg))):     # (without cond_proj)
         leaf = name.rsplit(".", 2)[-2]
         is_norm = leaf.startswith("norm") or leaf == "conv_norm_out"
         if name.endswith(".bias"):
@@ -136,7 +156,25 @@ def make_synthetic_state_dict(cfg: UNetConfig, seed: int = 1234) -> Dict[str, to
     if len(_SYNTHETIC_CACHE) >= 2:            # (3.4 GB per SD-1.5-sized entry)
         _SYNTHETIC_CACHE.pop(next(iter(_SYNTHETIC_CACHE)))
     _SYNTHETIC_CACHE[key] = sd
-    return dict(sd)
+    return _with_cond_proj(dict(sd), cfg, seed)
+
+
+COND_PROJ_SEED_OFFSET = 7919
+
+
+def _shared_fields(cfg: UNetConfig) -> dict:
+    """The config's dataclass fields (everything but ``time_cond_proj_dim``)."""
+    import dataclasses
+    return {f.name: getattr(cfg, f.name) for f in dataclasses.fields(cfg)}
+
+
+def _with_cond_proj(sd: Dict[str, torch.Tensor], cfg: UNetConfig, seed: int) -> Dict[str, torch.Tensor]:
+    d = cfg.time_cond_proj_dim
+    if d is not None:
+        g = torch.Generator().manual_seed(COND_PROJ_SEED_OFFSET + int(seed))
+        shape = (cfg.block_out_channels[0], d)
+        sd["time_embedding.cond_proj.weight"] = (torch.randn(shape, generator=g) / math.sqrt(d)).to(torch.bfloat16).float()
+    return sd
 
 
 def load_scheduler_config(model_dir: str) -> dict:
@@ -180,8 +218,11 @@ def load_unet_config(model_dir: str) -> "UNetConfig | None":
         if len(set(heads)) != 1:
             raise NotImplementedError("per-level head counts are not built")
         heads = heads[0]
+    tcond = c.get("time_cond_proj_dim", None)
+    if tcond is not None and (isinstance(tcond, bool) or not isinstance(tcond, int) or tcond <= 0):
+        raise NotImplementedError(f"unet config time_cond_proj_dim={tcond!r}: a positive integer (LCM-distilled) or null")
     for key, want in (("use_linear_projection", False), ("act_fn", "silu"), ("flip_sin_to_cos", True), ("freq_shift", 0),
-                      ("time_cond_proj_dim", None), ("class_embed_type", None), ("addition_embed_type", None),
+                      ("class_embed_type", None), ("addition_embed_type", None),
                       ("dual_cross_attention", False), ("only_cross_attention", False), ("upcast_attention", False)):
         if c.get(key, want) != want:
             raise NotImplementedError(f"unet config {key}={c[key]!r}: this build implements {want!r} (SD-1.5)")
@@ -190,7 +231,8 @@ def load_unet_config(model_dir: str) -> "UNetConfig | None":
                       block_out_channels=tuple(int(v) for v in c.get("block_out_channels", (320, 640, 1280, 1280))),
                       layers_per_block=int(c.get("layers_per_block", 2)), attn_levels=attn,
                       cross_attention_dim=int(c.get("cross_attention_dim", 768)), num_heads=int(heads),
-                      norm_num_groups=int(c.get("norm_num_groups", 32)), norm_eps=float(c.get("norm_eps", 1e-5)))
+                      norm_num_groups=int(c.get("norm_num_groups", 32)), norm_eps=float(c.get("norm_eps", 1e-5)),
+                      time_cond_proj_dim=tcond)
 
 
 def load_unet_state_dict(model_dir: str) -> Dict[str, torch.Tensor]:
