@@ -25,6 +25,6 @@ attn)    # 64x64 self-attention alone: round-2 kernel vs the round-3 one (SD_ATT
   bash $R/tools/r3_attn_pmc.sh 0 7 ;;
 stats)
   rm -rf $O/stats
-  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-e2e --no-other-configs > $O/stats_bench.log 2>&1 || fail $O/stats_bench.log
+  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-e2e --no-other-configs > $O/stats_bench.log 2>&1 || fail $O/stats_bench.log
   tail -1 $O/stats_bench.log | cut -c1-300; find $O/stats -name "*kernel_stats.csv" | head -2 ;;
 esac; done

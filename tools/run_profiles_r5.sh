@@ -6,7 +6,7 @@ fail() { grep -v "^    @" $1 | tail -5; exit 1; }
 for step in "$@"; do case $step in
 stats)   # HEADLINE workload only: no other_configs, no end-to-end, no CPU baseline, no batch-1 full-length parity loop
   rm -rf $O/r5_stats
-  ARGS="--steps 1 --warmup 1 --no-cpu-baseline --no-e2e --no-other-configs --no-parity-full-length"
+  ARGS="--full --steps 1 --warmup 1 --no-cpu-baseline --no-e2e --no-other-configs --no-parity-full-length"
   timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r5_stats -- python $R/bench.py $ARGS > $O/r5_stats_bench.log 2>&1 || fail $O/r5_stats_bench.log
   F=$(find $O/r5_stats -name "*kernel_stats.csv"); N=$(echo "$F" | wc -l)
   [ "$N" = "1" ] || { echo "expected ONE kernel_stats.csv (one profiled process), found $N: $F"; exit 1; }
