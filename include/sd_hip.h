@@ -185,6 +185,46 @@ int sd_clip_create(const sd_clip_config* cfg, sd_clip** out);
 int sd_clip_encode(sd_clip* c, void* stream, const int* input_ids, int batch, float* hidden_out, void* workspace,
                    long long workspace_bytes);
 
+/* ---- CLIP score: the reference's quality metric (quality_metrics.clip_score; torchmetrics CLIPScore over
+ * transformers CLIPModel.get_image_features / get_text_features).
+ * Text side: a kind-2 handle created with a projection also takes `text_projection.weight` [projection_dim, hidden_size];
+ * sd_clip_text_embeds runs the text tower on int32 ids [batch, max_positions], takes the row at the EOS position (the first
+ * position holding eos_token_id; eos_token_id < 0: the argmax of the ids, transformers' rule for configs whose
+ * eos_token_id is 2), applies final_layer_norm and the projection -> fp32 [batch, projection_dim].
+ * Vision side: `sd_clip_vision` is again the sd_unet handle type (kind 3), parameters under transformers'
+ * CLIPVisionModelWithProjection names (vision_model.embeddings.{class_embedding, patch_embedding.weight,
+ * position_embedding.weight}, vision_model.pre_layrnorm.*, vision_model.encoder.layers.N.*, vision_model.post_layernorm.*,
+ * visual_projection.weight), enumerated / loaded / finalised through the sd_unet_* calls.  encode: device uint8 images
+ * [batch, 3, height, width] (any size) -> CLIPImageProcessor (shortest edge -> image_size with Pillow's bicubic, bit-exact;
+ * centre crop; OpenAI CLIP mean / std) -> ViT (non-causal attention, head dim 64, <= 320 tokens) -> post_layernorm of the
+ * class token -> visual_projection: fp32 image_embeds [batch, projection_dim].  One plan per (batch, height, width).
+ * sd_clip_score: raw[b] = 100 cos(image_embeds[b], text_embeds[b]) and score[b] = max(raw[b], 0) (either may be NULL). */
+typedef struct sd_clip_vision_config {
+    int hidden_size;         /* 768 (ViT-B/16) */
+    int num_layers;          /* 12 */
+    int num_heads;           /* 12 (head dim 64) */
+    int intermediate_size;   /* 3072 */
+    int image_size;          /* 224: resize shortest edge and centre crop */
+    int patch_size;          /* 16 */
+    int projection_dim;      /* 512 */
+    float layer_norm_eps;    /* 1e-5 */
+} sd_clip_vision_config;
+typedef struct sd_unet sd_clip_vision;
+int sd_clip_create_projected(const sd_clip_config* cfg, int projection_dim, int eos_token_id, sd_clip** out);
+long long sd_clip_text_embeds_workspace_bytes(sd_clip* c, int batch);
+int sd_clip_text_embeds(sd_clip* c, void* stream, const int* input_ids, int batch, float* text_embeds, void* workspace,
+                        long long workspace_bytes);
+int sd_clip_vision_create(const sd_clip_vision_config* cfg, sd_clip_vision** out);
+long long sd_clip_vision_workspace_bytes(sd_clip_vision* v, int batch, int height, int width);
+int sd_clip_vision_encode(sd_clip_vision* v, void* stream, const unsigned char* images, int batch, int height, int width,
+                          float* image_embeds, void* workspace, long long workspace_bytes);
+int sd_clip_score(void* stream, const float* image_embeds, const float* text_embeds, int batch, int dim, float* raw,
+                  float* score);
+/* Host only: Pillow's bicubic tap table (precompute_coeffs + normalize_coeffs_8bpc, 22 fractional bits) for a resize of
+ * in_size -> out_size, output positions [first, first + count).  Returns the tap stride ksize; with non-NULL arrays also
+ * writes xmin[count], xcnt[count] and coeffs[count][ksize]. */
+int sd_clip_resize_taps(int in_size, int out_size, int first, int count, int* xmin, int* xcnt, int* coeffs);
+
 /* Measurement hook for bench.py: the same forward with a hipEvent pair around every launch.  Per
  * op kind (0 sinusoid, 1 gemv, 2 conv_in, 3 groupnorm, 4 conv3x3, 5 gemm, 6 layernorm,
  * 7 attention, 8 conv_out; 16 conv3x3 with fp8 operands, 17 gemm with fp8 operands, 18 fused prompt cross-attention)
@@ -304,6 +344,12 @@ int sd_op_attention_headmajor(void* stream, const void* Q, long long ldq, const 
 /* causal self-attention of the CLIP text tower (transformers CLIPAttention, reached from src/models.py:139-155) on the fused
  * projection output qkv [B * L][3 H] (q | k | v, bf16) -> out [B * L][H]; L <= 128, head dim 64 (16 in the reduced tests) */
 int sd_op_clip_attention(void* stream, const void* qkv, void* out, int B, int L, int H, int heads);
+/* non-causal ViT self-attention on the fused projection output qkv [B * L][3 H] -> out [B * L][H]; head dim 64, L <= 320 */
+int sd_op_vit_attention(void* stream, const void* qkv, void* out, int B, int L, int H, int heads);
+/* the CLIP preprocessing of sd_clip_vision_encode on its own: uint8 [B][3][H][W] -> uint8 crop [B][3][S][S] and bf16 patch
+ * rows [B (S/P)^2][Kp], Kp = 3 P^2 rounded up to a multiple of 64 (zero columns past 3 P^2).  Synchronises the stream. */
+int sd_op_clip_preprocess(void* stream, const unsigned char* images, int B, int H, int W, int S, int P, unsigned char* crop,
+                          void* patches);
 int sd_op_conv_in(void* stream, const float* x, int Bsrc, const float* Wt, const float* bias, void* y, int B, int H,
                   int W, int Cin, int Cout);
 int sd_op_conv_out(void* stream, const void* x, const void* Wp, const float* bias, float* y, int B, int H, int W,

@@ -44,6 +44,13 @@ class SdClipConfig(C.Structure):
     ]
 
 
+class SdClipVisionConfig(C.Structure):
+    _fields_ = [
+        ("hidden_size", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int), ("intermediate_size", C.c_int),
+        ("image_size", C.c_int), ("patch_size", C.c_int), ("projection_dim", C.c_int), ("layer_norm_eps", C.c_float),
+    ]
+
+
 class SdHipError(RuntimeError):
     pass
 
@@ -85,6 +92,16 @@ _SIGS = {
     "sd_vae_decode_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _ll]),
     "sd_clip_create": (_i, [C.POINTER(SdClipConfig), C.POINTER(_vp)]),
     "sd_clip_encode": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _ll]),
+    "sd_clip_create_projected": (_i, [C.POINTER(SdClipConfig), _i, _i, C.POINTER(_vp)]),
+    "sd_clip_text_embeds_workspace_bytes": (_ll, [_vp, _i]),
+    "sd_clip_text_embeds": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _ll]),
+    "sd_clip_vision_create": (_i, [C.POINTER(SdClipVisionConfig), C.POINTER(_vp)]),
+    "sd_clip_vision_workspace_bytes": (_ll, [_vp, _i, _i, _i]),
+    "sd_clip_vision_encode": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _ll]),
+    "sd_clip_score": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "sd_clip_resize_taps": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
+    "sd_op_vit_attention": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
+    "sd_op_clip_preprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "sd_unet_debug_tensor": (_i, [_vp, _vp, C.c_char_p, _vp, _ll, _vp, _i, _i]),
     "sd_sched_step": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _ll]),
     "sd_cfg_rescale_factors": (_i, [_vp, _vp, _i, _ll, _f, _f, _vp]),

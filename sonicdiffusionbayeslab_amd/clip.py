@@ -102,17 +102,37 @@ def load_clip_state_dict(model_dir: str) -> Dict[str, torch.Tensor]:
 class HipClipTextModel:
     """``text_encoder(input_ids)[0]`` replacement: int token ids ``[B,77]`` -> fp32 ``[B,77,768]`` on the GPU."""
 
-    def __init__(self, config: ClipTextConfig, state_dict: Dict[str, torch.Tensor], device: str = "cuda:0"):
+    def __init__(self, config: ClipTextConfig, state_dict: Dict[str, torch.Tensor], device: str = "cuda:0",
+                 text_projection: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None):
+        """``text_projection`` ([projection_dim, hidden], CLIPModel's ``text_projection.weight``) enables ``embeds``: the
+        pooled, projected text features.  Pooling row: the first ``eos_token_id``; ``None``: the argmax of the ids."""
         if not torch.cuda.is_available():
             raise _lib.SdHipError("HipClipTextModel needs an MI355X (no CPU fallback exists)")
         self.config = config
         self.device = torch.device(device)
         self._lib = _lib.load()
         self._handle = C.c_void_p()
-        torch.cuda.set_device(self.device)
+        self._ws: Optional[torch.Tensor] = None
+        self._ws_batch = None
+        self._ews: Optional[torch.Tensor] = None
+        self._ews_batch = None
+        # the weights go to self.device; the process's current device is left as it is (a device guard per call)
+        with torch.cuda.device(self.device):
+            self._build(config, state_dict, text_projection, eos_token_id)
+
+    def _build(self, config, state_dict, text_projection, eos_token_id):
         c = _lib.SdClipConfig(config.vocab_size, config.hidden_size, config.num_hidden_layers, config.num_attention_heads,
                               config.intermediate_size, config.max_position_embeddings, config.layer_norm_eps)
-        _lib.check(self._lib.sd_clip_create(C.byref(c), C.byref(self._handle)), "sd_clip_create")
+        self.projection_dim = 0 if text_projection is None else int(text_projection.shape[0])
+        if text_projection is None:
+            _lib.check(self._lib.sd_clip_create(C.byref(c), C.byref(self._handle)), "sd_clip_create")
+        else:
+            eos = -1 if eos_token_id is None else int(eos_token_id)
+            _lib.check(self._lib.sd_clip_create_projected(C.byref(c), self.projection_dim, eos, C.byref(self._handle)),
+                       "sd_clip_create_projected")
+            t = text_projection.detach().to("cpu", torch.float32).contiguous()
+            _lib.check(self._lib.sd_unet_load_param(self._handle, b"text_projection.weight", t.data_ptr(), t.numel()),
+                       "load_param(text_projection.weight)")
         sd = normalise_clip_state_dict(state_dict)
         for name, shape in clip_param_shapes(config):
             if name not in sd:
@@ -123,8 +143,6 @@ class HipClipTextModel:
             _lib.check(self._lib.sd_unet_load_param(self._handle, name.encode(), t.data_ptr(), t.numel()),
                        f"load_param({name})")
         _lib.check(self._lib.sd_unet_finalize(self._handle), "finalize")
-        self._ws: Optional[torch.Tensor] = None
-        self._ws_batch = None
 
     def __del__(self):
         try:
@@ -145,6 +163,10 @@ class HipClipTextModel:
         return self._ws
 
     def encode(self, input_ids: torch.Tensor) -> torch.Tensor:
+        with torch.cuda.device(self.device):
+            return self._encode(input_ids)
+
+    def _encode(self, input_ids: torch.Tensor) -> torch.Tensor:
         L, H = self.config.max_position_embeddings, self.config.hidden_size
         ids = input_ids.to(self.device, torch.int32).contiguous()
         if ids.dim() != 2 or ids.shape[1] != L:
@@ -160,6 +182,35 @@ class HipClipTextModel:
         return out
 
     __call__ = encode
+
+    def embeds(self, input_ids: torch.Tensor) -> torch.Tensor:
+        """``CLIPModel.get_text_features(input_ids)``: fp32 ``[B, projection_dim]`` (the EOS row of the final LayerNorm
+        output, times ``text_projection``).  Needs a handle built with ``text_projection``."""
+        with torch.cuda.device(self.device):
+            return self._embeds(input_ids)
+
+    def _embeds(self, input_ids: torch.Tensor) -> torch.Tensor:
+        if not self.projection_dim:
+            raise ValueError("this HipClipTextModel was built without text_projection")
+        L = self.config.max_position_embeddings
+        ids = input_ids.to(self.device, torch.int32).contiguous()
+        if ids.dim() != 2 or ids.shape[1] != L:
+            raise ValueError(f"input_ids must be [B,{L}], got {tuple(ids.shape)}")
+        if int(ids.min()) < 0 or int(ids.max()) >= self.config.vocab_size:
+            raise ValueError("token id outside the vocabulary")
+        b = ids.shape[0]
+        if self._ews is None or self._ews_batch != b:
+            n = self._lib.sd_clip_text_embeds_workspace_bytes(self._handle, b)
+            if n < 0:
+                _lib.check(-1, "sd_clip_text_embeds_workspace_bytes")
+            self._ews = None
+            self._ews = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+            self._ews_batch = b
+        out = torch.empty((b, self.projection_dim), dtype=torch.float32, device=self.device)
+        wsp = (self._ews.data_ptr() + 255) // 256 * 256
+        _lib.check(self._lib.sd_clip_text_embeds(self._handle, _lib.current_stream(), ids.data_ptr(), b, out.data_ptr(), wsp,
+                                                 self._ews.numel() - 256), "sd_clip_text_embeds")
+        return out
 
 
 # --------------------------------------------------------------------------------------------------

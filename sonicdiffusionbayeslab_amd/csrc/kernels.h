@@ -3,6 +3,8 @@
 // can take the whole GPU host down), enqueues on the caller's stream only, never synchronises,
 // and returns 0 / negative with the message available through sd_last_error().
 #pragma once
+#include <vector>
+
 #include "common.h"
 
 struct GemmArgs {
@@ -199,6 +201,25 @@ int sd_launch_clip_embed(const int* ids, const bf16_t* tok, const bf16_t* pos, b
 int sd_launch_clip_attention(const bf16_t* qkv, bf16_t* out, int B, int L, int H, int heads, hipStream_t stream);
 int sd_launch_quick_gelu(bf16_t* x, long n, hipStream_t stream);
 int sd_launch_bf16_to_f32(const bf16_t* src, float* dst, long n, hipStream_t stream);
+
+// vit.hip: CLIP vision tower pieces and the CLIP score
+// geometry of one input size: crop S x S, the R intermediate rows from input row y0, and the offsets (in ints) of the tap
+// tables in one int array: x min / count / coefficients of the S crop columns, then the same for the S crop rows (y min
+// relative to y0)
+struct ClipPrepGeom {
+    int H = 0, W = 0, S = 0, y0 = 0, R = 0, ksx = 0, ksy = 0;
+    int o_xmin = 0, o_xcnt = 0, o_xk = 0, o_ymin = 0, o_ycnt = 0, o_yk = 0;
+};
+void sd_clip_resize_geometry(int H, int W, int S, int* rh, int* rw, int* top, int* left);
+int sd_clip_prep_tables(int H, int W, int S, std::vector<int>& tab, ClipPrepGeom& g);
+// uint8 images [B][3][H][W] -> bf16 patch rows [B * (S/P)^2][Kp] (tmp: uint8 [B][3][R][S]; crop: optional uint8 [B][3][S][S])
+int sd_launch_clip_preprocess(const unsigned char* img, int B, const ClipPrepGeom& g, const int* dtab, unsigned char* tmp,
+                              bf16_t* patches, int P, int Kp, unsigned char* crop, hipStream_t stream);
+int sd_launch_vit_embed(const bf16_t* prow, const float* cls, const bf16_t* pos, bf16_t* out, int B, int Np, int H,
+                        hipStream_t stream);
+int sd_launch_vit_attention(const bf16_t* qkv, bf16_t* out, int B, int L, int H, int heads, hipStream_t stream);
+int sd_launch_pool_rows(const bf16_t* src, const int* ids, int B, int L, int H, int eos_id, bf16_t* dst, hipStream_t stream);
+int sd_launch_clip_score(const float* img, const float* txt, int B, int P, float* raw, float* score, hipStream_t stream);
 
 // conv_in: NCHW fp32 latents [Bsrc,4,H,W] (batch index taken modulo Bsrc: CFG duplication is
 // fused) -> NHWC bf16 [B,H,W,Cout]

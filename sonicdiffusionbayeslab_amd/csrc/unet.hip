@@ -91,7 +91,10 @@ struct Wrap {  // one DeepCache-wrapped module enclosing an op
 };
 
 enum OpKind { OP_SINUSOID, OP_GEMV, OP_CONV_IN, OP_GN, OP_CONV3, OP_GEMM, OP_LN, OP_ATTN, OP_CONV_OUT, OP_SOFTMAX, OP_PQCONV,
-              OP_CLIP_EMBED, OP_CLIP_ATTN, OP_QGELU, OP_TO_F32, OP_XATTN, OP_REPLICATE };
+              OP_CLIP_EMBED, OP_CLIP_ATTN, OP_QGELU, OP_TO_F32, OP_XATTN, OP_REPLICATE,
+              OP_VIT_PREP, OP_VIT_EMBED, OP_VIT_ATTN, OP_POOL };
+
+constexpr int REP_TEXT_POOLED = 2;       // Plan::rep of a CLIP text handle's sd_clip_text_embeds plan
 
 struct Op {
     int kind = 0;
@@ -105,6 +108,7 @@ struct Op {
     int heads = 0, D = 0, Nq = 0, Nk = 0;
     long ldq = 0, ldk = 0, ldv = 0, ldo = 0, qoff = 0, koff = 0, voff = 0;
     int silu_in = 0, splitk = 1;
+    int pool_by_ids = 0;          // OP_POOL: the row is the EOS position of the call's token ids (0: row 0, the class token)
     // split-K producer + single-launch GroupNorm as ONE reduce (fuse_deferred_reduce): the producer (CONV3 / GEMM) sets `defer`
     // and launches no splitk_reduce_kernel; the GroupNorm reads the producer's slabs (slab_t, slab_k of them) with its bias /
     // time-embedding row / residual and writes the producer's output tensor on the way (GroupNormArgs::slab)
@@ -181,7 +185,10 @@ struct Tn {
 
 struct Plan {
     int UB = 0, branch = -1;
-    int rep = 1;                          // 2: the prompt-independent prefix runs once per latent (CFG pair), see Builder::build
+    // UNet (kind 0): 2 = the prompt-independent prefix runs once per latent (CFG pair), see Builder::build.  CLIP text
+    // (kind 2): REP_TEXT_POOLED = the pooled + projected output variant of sd_clip_text_embeds, see build_clip.  The field is
+    // part of the plan key, so the variants of one batch size are distinct plans.
+    int rep = 1;
     int lh = 0, lw = 0;                   // latent height / width the plan is built for
     std::vector<Tn> tensors;
     std::vector<Op> ops;
@@ -196,14 +203,23 @@ struct Plan {
     int ctx_fold_scratch = -1;            // masked K / V expansions [2][UB][heads*80][Cmax]
     std::map<std::string, int> taps;
     size_t total_bytes = 0;
+    // CLIP vision plans (kind 3): preprocessing geometry of the plan's input size and its tap tables (host copy while the plan
+    // is built; the device copy belongs to the handle, one per input size)
+    ClipPrepGeom geom;
+    std::vector<int> prep_tab;
+    const int* dtab = nullptr;
 };
 
 }  // namespace
 
 struct sd_unet {
-    int kind = 0;   // 0 = UNet2DConditionModel, 1 = AutoencoderKL decoder, 2 = CLIP text encoder (same handle type)
+    int kind = 0;   // 0 = UNet2DConditionModel, 1 = AutoencoderKL decoder, 2 = CLIP text encoder, 3 = CLIP vision tower
     sd_unet_config cfg;
     sd_clip_config clip;
+    sd_clip_vision_config vis;
+    int text_proj = 0;                 // kind 2 with text_projection.weight [text_proj, hidden] (sd_clip_create_projected)
+    int eos_id = -1;                   // pooled text row: first position of this id; < 0: argmax of the ids
+    std::map<std::pair<int, int>, int*> prep_tabs;     // kind 3: device tap tables per input (H, W)
     std::vector<ParamSpec> params;
     std::unordered_map<std::string, int> pindex;
     std::unordered_map<std::string, size_t> woff;  // packed item -> byte offset into dweights
@@ -372,6 +388,34 @@ void enumerate_params_clip(sd_unet* u) {
     }
     e.add("text_model.final_layer_norm.weight", {H});
     e.add("text_model.final_layer_norm.bias", {H});
+    if (u->text_proj) e.add("text_projection.weight", {u->text_proj, H});
+}
+
+// transformers CLIPVisionModelWithProjection names (`vision_model.` prefix; `pre_layrnorm` is transformers' spelling)
+std::string vit_layer(int i) { return "vision_model.encoder.layers." + std::to_string(i) + "."; }
+int vit_kp(const sd_clip_vision_config& c) { return (3 * c.patch_size * c.patch_size + 63) / 64 * 64; }
+
+void enumerate_params_vit(sd_unet* u) {
+    const sd_clip_vision_config& c = u->vis;
+    Enum e{u};
+    const int H = c.hidden_size, I = c.intermediate_size, G = c.image_size / c.patch_size;
+    e.add("vision_model.embeddings.class_embedding", {H});
+    e.add("vision_model.embeddings.patch_embedding.weight", {H, 3, c.patch_size, c.patch_size});
+    e.add("vision_model.embeddings.position_embedding.weight", {G * G + 1, H});
+    e.add("vision_model.pre_layrnorm.weight", {H}); e.add("vision_model.pre_layrnorm.bias", {H});
+    for (int i = 0; i < c.num_layers; ++i) {
+        const std::string p = vit_layer(i);
+        for (const char* n : {"k_proj", "v_proj", "q_proj", "out_proj"}) {
+            e.add(p + "self_attn." + n + ".weight", {H, H});
+            e.add(p + "self_attn." + n + ".bias", {H});
+        }
+        e.add(p + "layer_norm1.weight", {H}); e.add(p + "layer_norm1.bias", {H});
+        e.add(p + "mlp.fc1.weight", {I, H}); e.add(p + "mlp.fc1.bias", {I});
+        e.add(p + "mlp.fc2.weight", {H, I}); e.add(p + "mlp.fc2.bias", {H});
+        e.add(p + "layer_norm2.weight", {H}); e.add(p + "layer_norm2.bias", {H});
+    }
+    e.add("vision_model.post_layernorm.weight", {H}); e.add("vision_model.post_layernorm.bias", {H});
+    e.add("visual_projection.weight", {c.projection_dim, H});
 }
 
 void enumerate_params_vae(sd_unet* u) {
@@ -865,33 +909,58 @@ int pack_vae(sd_unet* u) {
     return 0;
 }
 
+// the encoder layers of both CLIP towers: fused q | k | v rows and biases, bf16 GEMM weights, fp32 vectors
+void pack_clip_layer(Packer& pk, const std::string& p, int H) {
+    const std::string a = p + "self_attn.";
+    pk.concat_rows(a + "qkv.weight", {a + "q_proj.weight", a + "k_proj.weight", a + "v_proj.weight"});
+    {
+        size_t off = pk.alloc(a + "qkv.bias", (size_t)3 * H * 4);
+        float* o = (float*)(pk.u->hblob.data() + off);
+        for (const char* n : {"q_proj.bias", "k_proj.bias", "v_proj.bias"})
+            for (float v : pk.P(a + n)) *o++ = v;
+    }
+    pk.bf16_same(a + "out_proj.weight"); pk.f32(a + "out_proj.bias");
+    pk.f32(p + "layer_norm1.weight"); pk.f32(p + "layer_norm1.bias");
+    pk.bf16_same(p + "mlp.fc1.weight"); pk.f32(p + "mlp.fc1.bias");
+    pk.bf16_same(p + "mlp.fc2.weight"); pk.f32(p + "mlp.fc2.bias");
+    pk.f32(p + "layer_norm2.weight"); pk.f32(p + "layer_norm2.bias");
+}
+
 int pack_clip(sd_unet* u) {
     const sd_clip_config& c = u->clip;
     Packer pk{u};
     pk.bf16_same("text_model.embeddings.token_embedding.weight");
     pk.bf16_same("text_model.embeddings.position_embedding.weight");
-    for (int i = 0; i < c.num_layers; ++i) {
-        const std::string p = clip_layer(i), a = p + "self_attn.";
-        pk.concat_rows(a + "qkv.weight", {a + "q_proj.weight", a + "k_proj.weight", a + "v_proj.weight"});
-        {
-            size_t off = pk.alloc(a + "qkv.bias", (size_t)3 * c.hidden_size * 4);
-            float* o = (float*)(u->hblob.data() + off);
-            for (const char* n : {"q_proj.bias", "k_proj.bias", "v_proj.bias"})
-                for (float v : pk.P(a + n)) *o++ = v;
-        }
-        pk.bf16_same(a + "out_proj.weight"); pk.f32(a + "out_proj.bias");
-        pk.f32(p + "layer_norm1.weight"); pk.f32(p + "layer_norm1.bias");
-        pk.bf16_same(p + "mlp.fc1.weight"); pk.f32(p + "mlp.fc1.bias");
-        pk.bf16_same(p + "mlp.fc2.weight"); pk.f32(p + "mlp.fc2.bias");
-        pk.f32(p + "layer_norm2.weight"); pk.f32(p + "layer_norm2.bias");
-    }
+    for (int i = 0; i < c.num_layers; ++i) pack_clip_layer(pk, clip_layer(i), c.hidden_size);
     pk.f32("text_model.final_layer_norm.weight"); pk.f32("text_model.final_layer_norm.bias");
+    if (u->text_proj) pk.bf16_same("text_projection.weight");
+    return 0;
+}
+
+int pack_vit(sd_unet* u) {
+    const sd_clip_vision_config& c = u->vis;
+    Packer pk{u};
+    const int H = c.hidden_size, K = 3 * c.patch_size * c.patch_size, Kp = vit_kp(c);
+    pk.f32("vision_model.embeddings.class_embedding");
+    {   // [H][3][P][P] -> bf16 rows [H][Kp], columns (c, kh, kw) as the patch rows of the preprocessing, zero past K
+        const auto& d = pk.P("vision_model.embeddings.patch_embedding.weight");
+        size_t off = pk.alloc("vision_model.embeddings.patch_embedding.weight", (size_t)H * Kp * 2);
+        unsigned short* o = (unsigned short*)(u->hblob.data() + off);
+        for (int n = 0; n < H; ++n)
+            for (int k = 0; k < Kp; ++k) o[(size_t)n * Kp + k] = k < K ? f32_to_bf16_host(d[(size_t)n * K + k]) : 0;
+    }
+    pk.bf16_same("vision_model.embeddings.position_embedding.weight");
+    pk.f32("vision_model.pre_layrnorm.weight"); pk.f32("vision_model.pre_layrnorm.bias");
+    for (int i = 0; i < c.num_layers; ++i) pack_clip_layer(pk, vit_layer(i), H);
+    pk.f32("vision_model.post_layernorm.weight"); pk.f32("vision_model.post_layernorm.bias");
+    pk.bf16_same("visual_projection.weight");
     return 0;
 }
 
 int pack_all(sd_unet* u) {
     if (u->kind == 1) return pack_vae(u);
     if (u->kind == 2) return pack_clip(u);
+    if (u->kind == 3) return pack_vit(u);
     const sd_unet_config& c = u->cfg;
     Packer pk{u};
     const int c0 = c.block_out_channels[0], temb = 4 * c0, nl = c.num_levels;
@@ -1367,13 +1436,60 @@ struct Builder {
             t = gemm(f, I, -1, 0, M, H, p + "mlp.fc2.weight", p + "mlp.fc2.bias", t, 0);
             pl.taps["layer" + std::to_string(i)] = t;
         }
+        if (pl.rep == REP_TEXT_POOLED) {      // pooled + projected variant (sd_clip_text_embeds): the EOS row, final LayerNorm, text_projection
+            int pr;
+            { Op o; o.kind = OP_POOL; o.x1 = t; o.pool_by_ids = 1; o.B = UB; o.Nq = L; o.N = H; o.out = tensor((size_t)UB * H * 2); push(o); pr = o.out; }
+            int f = ln(pr, UB, H, "text_model.final_layer_norm.weight", "text_model.final_layer_norm.bias");
+            int e = gemm(f, H, -1, 0, UB, u->text_proj, "text_projection.weight", "", -1, 0);
+            { Op o; o.kind = OP_TO_F32; o.x1 = e; o.out = T_EPS; o.M = UB; o.N = u->text_proj; push(o); }
+            return;
+        }
         int f = ln(t, M, H, "text_model.final_layer_norm.weight", "text_model.final_layer_norm.bias");
         { Op o; o.kind = OP_TO_F32; o.x1 = f; o.out = T_EPS; o.M = M; o.N = H; push(o); }
+    }
+
+    // CLIPVisionModelWithProjection (transformers modeling_clip.py): CLIPImageProcessor on the uint8 input (OP_VIT_PREP), patch
+    // embedding as a GEMM over the patch rows (no bias), class token + position embedding, pre_layrnorm, the pre-LN encoder
+    // layers with NON-causal attention, post_layernorm of the class-token row, visual_projection (no bias) -> image_embeds
+    void build_vit() {
+        const sd_clip_vision_config& c = u->vis;
+        const int S = c.image_size, P = c.patch_size, G = S / P, Np = G * G, L = Np + 1;
+        const int H = c.hidden_size, I = c.intermediate_size, Kp = vit_kp(c), M = UB * L;
+        if (sd_clip_prep_tables(pl.lh, pl.lw, S, pl.prep_tab, pl.geom)) { error = sd_last_error(); return; }
+        int patches;
+        { Op o; o.kind = OP_VIT_PREP; o.x1 = T_LATENTS; o.B = UB; o.K = Kp; o.Cin = P;
+          o.aux = tensor((size_t)UB * 3 * pl.geom.R * S); o.out = tensor((size_t)UB * Np * Kp * 2); push(o); patches = o.out; }
+        int pe = gemm(patches, Kp, -1, 0, UB * Np, H, "vision_model.embeddings.patch_embedding.weight", "", -1, 0);
+        int t;
+        { Op o; o.kind = OP_VIT_EMBED; o.x1 = pe; o.B = UB; o.Nq = Np; o.N = H;
+          o.b = W("vision_model.embeddings.class_embedding"); o.g = W("vision_model.embeddings.position_embedding.weight");
+          o.out = tensor((size_t)M * H * 2); push(o); t = o.out; }
+        t = ln(t, M, H, "vision_model.pre_layrnorm.weight", "vision_model.pre_layrnorm.bias");
+        for (int i = 0; i < c.num_layers; ++i) {
+            const std::string p = vit_layer(i), a = p + "self_attn.";
+            int n1 = ln(t, M, H, p + "layer_norm1.weight", p + "layer_norm1.bias");
+            int qkv = gemm(n1, H, -1, 0, M, 3 * H, a + "qkv.weight", a + "qkv.bias", -1, 0);
+            int at;
+            { Op o; o.kind = OP_VIT_ATTN; o.x1 = qkv; o.B = UB; o.Nq = L; o.N = H; o.heads = c.num_heads;
+              o.out = tensor((size_t)M * H * 2); push(o); at = o.out; }
+            t = gemm(at, H, -1, 0, M, H, a + "out_proj.weight", a + "out_proj.bias", t, 0);
+            int n2 = ln(t, M, H, p + "layer_norm2.weight", p + "layer_norm2.bias");
+            int f = gemm(n2, H, -1, 0, M, I, p + "mlp.fc1.weight", p + "mlp.fc1.bias", -1, 0);
+            { Op o; o.kind = OP_QGELU; o.x1 = f; o.out = f; o.M = M; o.N = I; push(o); }
+            t = gemm(f, I, -1, 0, M, H, p + "mlp.fc2.weight", p + "mlp.fc2.bias", t, 0);
+            pl.taps["layer" + std::to_string(i)] = t;
+        }
+        int pr;
+        { Op o; o.kind = OP_POOL; o.x1 = t; o.B = UB; o.Nq = L; o.N = H; o.out = tensor((size_t)UB * H * 2); push(o); pr = o.out; }
+        int f = ln(pr, UB, H, "vision_model.post_layernorm.weight", "vision_model.post_layernorm.bias");
+        int e = gemm(f, H, -1, 0, UB, c.projection_dim, "visual_projection.weight", "", -1, 0);
+        { Op o; o.kind = OP_TO_F32; o.x1 = e; o.out = T_EPS; o.M = UB; o.N = c.projection_dim; push(o); }
     }
 
     void build() {
         if (u->kind == 1) { build_vae(); return; }
         if (u->kind == 2) { build_clip(); return; }
+        if (u->kind == 3) { build_vit(); return; }
         const sd_unet_config& c = u->cfg;
         const int nl = c.num_levels, c0 = c.block_out_channels[0], temb = 4 * c0;
         const int L = c.context_len;
@@ -1630,6 +1746,15 @@ int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep = 1, int lh = -
                    b.error.c_str());
         fuse_deferred_reduce(u, pl);
         assign_memory(u, pl);
+        if (u->kind == 3) {     // tap tables of this input size: uploaded once, owned by the handle
+            int*& d = u->prep_tabs[std::make_pair(lh, lw)];
+            if (!d) {
+                SD_CHECK_HIP(hipMalloc((void**)&d, pl.prep_tab.size() * sizeof(int)));
+                SD_CHECK_HIP(hipMemcpy(d, pl.prep_tab.data(), pl.prep_tab.size() * sizeof(int), hipMemcpyHostToDevice));
+            }
+            pl.dtab = d;
+            std::vector<int>().swap(pl.prep_tab);
+        }
         it = u->plans.emplace(key, std::move(pl)).first;
     }
     *out = &it->second;
@@ -1745,6 +1870,17 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
             return sd_launch_clip_attention((const bf16_t*)T(o.x1), (bf16_t*)T(o.out), o.B, o.Nq, o.N, o.heads, stream);
         case OP_QGELU:
             return sd_launch_quick_gelu((bf16_t*)T(o.x1), (long)o.M * o.N, stream);
+        case OP_VIT_PREP:
+            return sd_launch_clip_preprocess((const unsigned char*)latents, o.B, pl.geom, pl.dtab, (unsigned char*)T(o.aux),
+                                             (bf16_t*)T(o.out), o.Cin, o.K, nullptr, stream);
+        case OP_VIT_EMBED:
+            return sd_launch_vit_embed((const bf16_t*)T(o.x1), (const float*)(wb + o.b), (const bf16_t*)(wb + o.g),
+                                       (bf16_t*)T(o.out), o.B, o.Nq, o.N, stream);
+        case OP_VIT_ATTN:
+            return sd_launch_vit_attention((const bf16_t*)T(o.x1), (bf16_t*)T(o.out), o.B, o.Nq, o.N, o.heads, stream);
+        case OP_POOL:
+            return sd_launch_pool_rows((const bf16_t*)T(o.x1), o.pool_by_ids ? (const int*)latents : nullptr, o.B, o.Nq, o.N, u->eos_id,
+                                       (bf16_t*)T(o.out), stream);
         case OP_TO_F32:
             return sd_launch_bf16_to_f32((const bf16_t*)T(o.x1), eps_out, (long)o.M * o.N, stream);
         case OP_CONV_OUT:
@@ -1880,10 +2016,113 @@ extern "C" int sd_clip_encode(sd_unet* u, void* stream, const int* input_ids, in
     return 0;
 }
 
+// ---- CLIP score (quality_metrics.clip_score): text_projection on the pooled text row, the vision tower, the score ----
+extern "C" int sd_clip_create_projected(const sd_clip_config* cfg, int projection_dim, int eos_token_id, sd_unet** out) {
+    SD_REQUIRE(cfg && out, "sd_clip_create_projected: null argument");
+    SD_REQUIRE(projection_dim > 0 && projection_dim % 4 == 0 && cfg->hidden_size % 64 == 0,
+               "sd_clip_create_projected: projection_dim %d must be a positive multiple of 4", projection_dim);
+    sd_clip_config c = *cfg;
+    sd_unet* u = nullptr;
+    int rc = sd_clip_create(&c, &u);
+    if (rc) return rc;
+    u->params.clear(); u->pindex.clear();
+    u->text_proj = projection_dim;
+    u->eos_id = eos_token_id;
+    enumerate_params_clip(u);
+    *out = u;
+    return 0;
+}
+
+extern "C" long long sd_clip_text_embeds_workspace_bytes(sd_unet* u, int batch) {
+    SD_REQUIRE(u && u->kind == 2 && u->text_proj > 0, "clip_text_embeds: not a projected CLIP text handle");
+    Plan* pl;
+    if (get_plan(u, batch, -1, &pl, REP_TEXT_POOLED)) return -1;
+    return (long long)pl->total_bytes;
+}
+
+extern "C" int sd_clip_text_embeds(sd_unet* u, void* stream, const int* input_ids, int batch, float* text_embeds,
+                                   void* workspace, long long workspace_bytes) {
+    SD_REQUIRE(u && u->kind == 2 && u->text_proj > 0, "clip_text_embeds: not a projected CLIP text handle");
+    SD_REQUIRE(input_ids && text_embeds && workspace && batch > 0, "clip_text_embeds: null argument");
+    Plan* pl;
+    int rc = get_plan(u, batch, -1, &pl, REP_TEXT_POOLED);
+    if (rc) return rc;
+    SD_REQUIRE((long long)pl->total_bytes <= workspace_bytes, "clip_text_embeds: workspace too small (%lld < %zu)",
+               workspace_bytes, pl->total_bytes);
+    SD_REQUIRE(((uintptr_t)workspace & 255) == 0, "clip_text_embeds: workspace must be 256-byte aligned");
+    for (size_t i = 0; i < pl->ops.size(); ++i)
+        if ((rc = run_op(u, *pl, pl->ops[i], (char*)workspace, (const float*)input_ids, batch, text_embeds, 0.f, (hipStream_t)stream)))
+            return rc;
+    return 0;
+}
+
+static int check_image_size(int H, int W, const char* who) {
+    SD_REQUIRE(H >= 1 && W >= 1 && H <= 8192 && W <= 8192, "%s: image %dx%d (sides 1..8192 are accepted)", who, H, W);
+    return 0;
+}
+
+extern "C" int sd_clip_vision_create(const sd_clip_vision_config* cfg, sd_unet** out) {
+    SD_REQUIRE(cfg && out, "sd_clip_vision_create: null argument");
+    const sd_clip_vision_config& c = *cfg;
+    SD_REQUIRE(c.hidden_size % 64 == 0 && c.hidden_size > 0 && c.intermediate_size % 64 == 0 && c.intermediate_size > 0,
+               "sd_clip_vision_create: hidden %d / intermediate %d must be positive multiples of 64", c.hidden_size,
+               c.intermediate_size);
+    SD_REQUIRE(c.hidden_size <= 1536, "sd_clip_vision_create: hidden size %d (LayerNorm kernel handles <= 1536)", c.hidden_size);
+    SD_REQUIRE(c.num_heads > 0 && c.hidden_size % c.num_heads == 0 && c.hidden_size / c.num_heads == 64,
+               "sd_clip_vision_create: head dim %d (64 is built)", c.num_heads > 0 ? c.hidden_size / c.num_heads : 0);
+    SD_REQUIRE(c.patch_size >= 1 && c.image_size >= c.patch_size && c.image_size % c.patch_size == 0,
+               "sd_clip_vision_create: image_size %d / patch_size %d", c.image_size, c.patch_size);
+    const int G = c.image_size / c.patch_size;
+    SD_REQUIRE(G * G + 1 <= 320, "sd_clip_vision_create: %d tokens (at most 320 are built)", G * G + 1);
+    SD_REQUIRE(c.projection_dim > 0 && c.projection_dim % 4 == 0, "sd_clip_vision_create: projection_dim %d", c.projection_dim);
+    SD_REQUIRE(c.num_layers >= 1, "sd_clip_vision_create: num_layers %d", c.num_layers);
+    SD_REQUIRE(fabsf(c.layer_norm_eps - 1e-5f) < 1e-9f, "sd_clip_vision_create: layer_norm_eps %g (1e-5 is built)", c.layer_norm_eps);
+    sd_unet* u = new sd_unet();
+    u->kind = 3;
+    memset(&u->cfg, 0, sizeof(u->cfg));
+    u->cfg.num_levels = 1;
+    u->vis = c;
+    enumerate_params_vit(u);
+    *out = u;
+    return 0;
+}
+
+extern "C" long long sd_clip_vision_workspace_bytes(sd_unet* u, int batch, int height, int width) {
+    SD_REQUIRE(u && u->kind == 3, "clip_vision: not a CLIP vision handle");
+    if (check_image_size(height, width, "clip_vision")) return -1;
+    Plan* pl;
+    if (get_plan(u, batch, -1, &pl, 1, height, width)) return -1;
+    return (long long)pl->total_bytes;
+}
+
+extern "C" int sd_clip_vision_encode(sd_unet* u, void* stream, const unsigned char* images, int batch, int height, int width,
+                                     float* image_embeds, void* workspace, long long workspace_bytes) {
+    SD_REQUIRE(u && u->kind == 3, "clip_vision: not a CLIP vision handle");
+    SD_REQUIRE(images && image_embeds && workspace && batch > 0, "clip_vision: null argument");
+    if (check_image_size(height, width, "clip_vision")) return -1;
+    Plan* pl;
+    int rc = get_plan(u, batch, -1, &pl, 1, height, width);
+    if (rc) return rc;
+    SD_REQUIRE((long long)pl->total_bytes <= workspace_bytes, "clip_vision: workspace too small (%lld < %zu)", workspace_bytes,
+               pl->total_bytes);
+    SD_REQUIRE(((uintptr_t)workspace & 255) == 0, "clip_vision: workspace must be 256-byte aligned");
+    for (size_t i = 0; i < pl->ops.size(); ++i)
+        if ((rc = run_op(u, *pl, pl->ops[i], (char*)workspace, (const float*)images, batch, image_embeds, 0.f, (hipStream_t)stream)))
+            return rc;
+    return 0;
+}
+
+extern "C" int sd_clip_score(void* stream, const float* image_embeds, const float* text_embeds, int batch, int dim,
+                             float* raw, float* score) {
+    return sd_launch_clip_score(image_embeds, text_embeds, batch, dim, raw, score, (hipStream_t)stream);
+}
+
 extern "C" void sd_unet_destroy(sd_unet* u) {
     if (!u) return;
     if (u->dweights) (void)hipFree(u->dweights);
     if (u->dcond) (void)hipFree(u->dcond);
+    for (auto& kv : u->prep_tabs)
+        if (kv.second) (void)hipFree(kv.second);
     delete u;
 }
 
@@ -2612,6 +2851,44 @@ extern "C" int sd_op_attention(void* stream, const void* Q, long long ldq, const
 // the CLIP text tower's causal self-attention on the fused projection output qkv [B * L][3 H] (q | k | v) -> out [B * L][H]
 extern "C" int sd_op_clip_attention(void* stream, const void* qkv, void* out, int B, int L, int H, int heads) {
     return sd_launch_clip_attention((const bf16_t*)qkv, (bf16_t*)out, B, L, H, heads, (hipStream_t)stream);
+}
+
+extern "C" int sd_op_vit_attention(void* stream, const void* qkv, void* out, int B, int L, int H, int heads) {
+    return sd_launch_vit_attention((const bf16_t*)qkv, (bf16_t*)out, B, L, H, heads, (hipStream_t)stream);
+}
+
+// CLIPImageProcessor on device: uint8 images [B][3][H][W] -> the uint8 crop [B][3][S][S] and bf16 patch rows
+// [B * (S/P)^2][Kp] (Kp = 3 P^2 rounded up to 64).  Synchronises the stream (the tap tables and the intermediate are
+// allocated for the call).
+extern "C" int sd_op_clip_preprocess(void* stream, const unsigned char* images, int B, int H, int W, int S, int P,
+                                     unsigned char* crop, void* patches) {
+    SD_REQUIRE(images && crop && patches && B > 0, "clip_preprocess: null argument");
+    if (check_image_size(H, W, "clip_preprocess")) return -1;
+    SD_REQUIRE(S >= 1 && P >= 1 && S % P == 0, "clip_preprocess: crop %d patch %d", S, P);
+    std::vector<int> tab;
+    ClipPrepGeom g;
+    if (sd_clip_prep_tables(H, W, S, tab, g)) return -1;
+    const int Kp = (3 * P * P + 63) / 64 * 64;
+    int* dtab = nullptr;
+    unsigned char* tmp = nullptr;
+    SD_CHECK_HIP(hipMalloc((void**)&dtab, tab.size() * sizeof(int)));
+    if (hipMalloc((void**)&tmp, (size_t)B * 3 * g.R * S) != hipSuccess) {
+        (void)hipFree(dtab);
+        SD_REQUIRE(false, "clip_preprocess: cannot allocate the intermediate");
+    }
+    int rc = 0;
+    if (hipMemcpy(dtab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+        sd_set_error("clip_preprocess: tap table upload failed");
+        rc = -2;
+    }
+    if (!rc) rc = sd_launch_clip_preprocess(images, B, g, dtab, tmp, (bf16_t*)patches, P, Kp, crop, (hipStream_t)stream);
+    if (!rc && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {
+        sd_set_error("clip_preprocess: stream synchronisation failed");
+        rc = -2;
+    }
+    (void)hipFree(tmp);
+    (void)hipFree(dtab);
+    return rc;
 }
 
 // q|k|v projection the way the plan runs it at the 64x64 level: Q token-major [M][C], K and V head-major

@@ -92,8 +92,13 @@ class BaseMethod(ABC):
         self.clip_score_gen_metric = None
         qm = self.config.get("quality_metrics", None)
         path = qm.get("clip_score", {}).get("model_name_or_path", None) if qm else None
+        # optional quality_metrics.clip_score.backend ("transformers" | "hip"); absent: the metric's default
+        backend = qm.get("clip_score", {}).get("backend", None) if qm else None
         if path and os.path.isdir(str(path)):
-            self.clip_score_gen_metric = metrics_registry["clip_score"](model_name_or_path=str(path))
+            kw = {"backend": str(backend)} if backend else {}
+            if backend == "hip" and str(self.device).startswith("cuda"):
+                kw["device"] = self.device          # this rank's GPU (the towers are built at the first score)
+            self.clip_score_gen_metric = metrics_registry["clip_score"](model_name_or_path=str(path), **kw)
         self.clip_score_source = str(path) if self.clip_score_gen_metric is not None else (
             f"not computable offline ({path!r} is not a local directory)" if path else "not configured")
 

@@ -35,11 +35,25 @@ class TimeMetric:
 class ClipScoreMetric:
     """100 * cos(E_img, E_txt), clamped at 0, averaged (torchmetrics 1.6.1 CLIPScore, A.8)."""
 
-    def __init__(self, model_name_or_path: str = "openai/clip-vit-base-patch16"):
+    def __init__(self, model_name_or_path: str = "openai/clip-vit-base-patch16", backend: str = "transformers",
+                 device=None):
+        """backend ``"transformers"``: CLIPModel + CLIPProcessor in fp32 on the host; ``"hip"``: both towers on libsdhip
+        (``clip_score.HipClipScorer``, uint8 images in) on ``device`` (``None``: the current device when the towers are
+        built).  The hip backend checks the checkpoint's config here and builds the towers at the first ``update``, so
+        that a process that never scores (a rank other than 0) puts no CLIP weights on a GPU."""
+        if backend not in ("transformers", "hip"):
+            raise ValueError(f"clip_score backend {backend!r}: 'transformers' or 'hip'")
         if not os.path.isdir(str(model_name_or_path)):
             raise FileNotFoundError(
                 f"CLIP checkpoint {model_name_or_path!r} is a network fetch and unavailable offline; "
                 "pass a local directory to compute CLIP score")
+        self.backend = backend
+        if backend == "hip":
+            from .clip_score import read_clip_configs
+            read_clip_configs(str(model_name_or_path))          # unsupported configs fail here, before any GPU work
+            self.path, self.device, self.scorer = str(model_name_or_path), device, None
+            self.reset()
+            return
         from transformers import CLIPModel, CLIPProcessor
         self.model = CLIPModel.from_pretrained(model_name_or_path).eval()
         self.processor = CLIPProcessor.from_pretrained(model_name_or_path)
@@ -47,6 +61,14 @@ class ClipScoreMetric:
 
     @torch.no_grad()
     def update(self, images, text):
+        if self.backend == "hip":
+            if self.scorer is None:
+                from .clip_score import HipClipScorer
+                self.scorer = HipClipScorer.from_pretrained(self.path, device=self.device)
+            _, score = self.scorer.score_pairs(images, list(text))
+            self.score += score.sum().item()
+            self.n += len(text)
+            return
         inp = self.processor(text=list(text), images=[i for i in images], return_tensors="pt", padding=True, truncation=True)
         # (transformers 4.48 returns the projected embedding itself, 5.x an output object whose pooler_output is it)
         emb = lambda o: o if torch.is_tensor(o) else o.pooler_output
