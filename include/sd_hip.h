@@ -163,6 +163,23 @@ int sd_vae_decode(sd_vae* v, void* stream, const float* latents, int batch, floa
 int sd_vae_decode_hw(sd_vae* v, void* stream, const float* latents, int batch, int latent_h, int latent_w, float latent_scale,
                      float* images_out, void* workspace, long long workspace_bytes);
 
+/* ---- AutoencoderKL encoder: `vae.encode(image)` of diffusers 0.32.1 (AutoencoderKL.encode, as
+ * StableDiffusionImg2ImgPipeline.prepare_latents calls it; upstream-recall).  Additions under ABI 3: resolve them by name.
+ * The handle is again an `sd_unet`: parameters (diffusers names encoder.* and quant_conv.*) are enumerated / loaded /
+ * finalised and the workspace is sized through the sd_unet_* functions (sd_unet_workspace_bytes_hw with cache_branch_id = -1
+ * and the LATENT size).  cfg as for sd_vae_create: sample_size = latent size, in_channels = 4 (latent), out_channels = 3
+ * (image), four levels.
+ * encode: fp32 NCHW images [batch,3,8h,8w] in [0,1] -> 2 x - 1 -> encoder -> quant_conv -> fp32 NCHW moments [batch,8,h,w] =
+ * [mean | logvar]; latent sides are multiples of 8 in [8, 128].  conv_in runs in fp32 on the fp32 image, conv_out
+ * contracts bf16 operands into fp32 and quant_conv is applied to those sums in fp32 by the same kernel. */
+int sd_vae_encoder_create(const sd_unet_config* cfg, sd_vae** out);
+int sd_vae_encode_hw(sd_vae* v, void* stream, const float* images, int batch, int latent_h, int latent_w, float* moments_out,
+                     void* workspace, long long workspace_bytes);
+/* DiagonalGaussianDistribution of the moments [batch,8,hw]: latents_out [batch,4,hw] =
+ * scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise), or scale * mean when noise is NULL (mode()).  One launch. */
+int sd_vae_posterior_sample(void* stream, const float* moments, const float* noise_or_null, float scale, float* latents_out,
+                            int batch, long long hw);
+
 /* ---- CLIP text encoder: replaces `self.text_encoder(text_input_ids)[0]` inside
  * `encode_prompt` (src/models.py:139-155; transformers CLIPTextModel, quick_gelu, causal mask).  `sd_clip` IS the
  * `sd_unet` handle type: parameters (transformers names, `text_model.` prefix: embeddings.token_embedding.weight,
@@ -301,6 +318,10 @@ int sd_op_conv3x3(void* stream, const void* X, const void* W, const float* bias,
 /* Which kernel a 3x3 conv of this shape runs on: 0 = implicit GEMM, 1 = halo kernel (9 taps), 2 = halo kernel's 4-tap
  * mode.  M = output rows (B Hout Wout; for upsample = 2, the sub-pixel form, 4 B Hin Win); upsample 1 = fused nearest-2x;
  * dtype 0 = bf16, 1 = fp8 e4m3 (Cin padded to 128).  No device work. */
+/* The 3x3 stride-2 conv padded on the right and the bottom only: F.conv2d(F.pad(x, (0, 1, 0, 1)), w, b, stride = 2), the
+ * AutoencoderKL encoder's downsampler.  W as for sd_op_conv3x3; Hin and Win even; Y = [B, Hin / 2, Win / 2, Cout]. */
+int sd_op_conv3x3_down_asym(void* stream, const void* X, const void* W, const float* bias, void* Y, int B, int Hin, int Win,
+                            int Cin, int Cout);
 int sd_op_conv3x3_kernel(int M, int N, int Cin, int Hin, int Win, int stride, int upsample, int dtype);
 /* In-place softmax(scale * row) of bf16 S [rows, cols], cols a multiple of 8: the VAE mid-block attention's softmax
  * (one wave per row up to 4096 columns; beyond, a workgroup per row with an online max / sum over the row). */

@@ -90,6 +90,9 @@ _SIGS = {
     "sd_vae_create": (_i, [C.POINTER(SdUnetConfig), C.POINTER(_vp)]),
     "sd_vae_decode": (_i, [_vp, _vp, _vp, _i, _f, _vp, _vp, _ll]),
     "sd_vae_decode_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _ll]),
+    "sd_vae_encoder_create": (_i, [C.POINTER(SdUnetConfig), C.POINTER(_vp)]),
+    "sd_vae_encode_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _ll]),
+    "sd_vae_posterior_sample": (_i, [_vp, _vp, _vp, _f, _vp, _i, _ll]),
     "sd_clip_create": (_i, [C.POINTER(SdClipConfig), C.POINTER(_vp)]),
     "sd_clip_encode": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _ll]),
     "sd_clip_create_projected": (_i, [C.POINTER(SdClipConfig), _i, _i, C.POINTER(_vp)]),
@@ -110,6 +113,7 @@ _SIGS = {
     "sd_op_gemm_batched": (_i, [_vp, _vp, _ll, _vp, _ll, _i, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _i, _i]),
     "sd_op_gemm_batched_softmax_ln": (_i, [_vp, _vp, _ll, _vp, _ll, _i, _vp, _ll, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f]),
     "sd_op_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
+    "sd_op_conv3x3_down_asym": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "sd_op_conv3x3_ablate": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "sd_op_conv3x3_upsample_subpixel": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "sd_op_conv3x3_upsample_subpixel_groupnorm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _i]),

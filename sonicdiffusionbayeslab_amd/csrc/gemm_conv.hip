@@ -155,7 +155,8 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, 2) void gemm_kernel(const Ge
             const int hw = p.Hout * p.Wout;
             const int b = m / hw, rem = m - b * hw;
             const int oy = rem / p.Wout, ox = rem - oy * p.Wout;
-            const int y0 = oy * p.stride - 1, x0 = ox * p.stride - 1;
+            const int po = p.asym ? 0 : 1;       // window origin: (oy * stride - 1) with symmetric padding, (oy * stride) without
+            const int y0 = oy * p.stride - po, x0 = ox * p.stride - po;
             xoy[i] = y0; xox[i] = x0; xb[i] = m < p.M ? b * p.Hin * p.Win : -1;
             xptr[i] = (const char*)p.X + ((long)b * p.Hin * p.Win + (long)y0 * p.Win + x0) * p.Cin * ESZ + gch * 16;
             int mask = 0;
@@ -884,6 +885,9 @@ int sd_launch_conv3x3(const GemmArgs& a, hipStream_t stream) {
     SD_REQUIRE(!(a.up && a.stride != 1), "conv3x3: upsample needs stride 1");
     SD_REQUIRE(a.zero_page != nullptr, "conv3x3: zero page missing");
     const int hv = a.Hin << a.up, wv = a.Win << a.up;
+    // asymmetric stride 2 (pad right 1 / bottom 1 only): even sides, so that the last window ends exactly one past the edge
+    SD_REQUIRE(!a.asym || (a.stride == 2 && a.dt == 0 && a.Hin % 2 == 0 && a.Win % 2 == 0 && !a.stats),
+               "conv3x3: the asymmetric form is bf16, stride 2, even input sides (%dx%d stride %d)", a.Hin, a.Win, a.stride);
     SD_REQUIRE(a.Hout == (hv + 2 - 3) / a.stride + 1 && a.Wout == (wv + 2 - 3) / a.stride + 1,
                "conv3x3: output size %dx%d inconsistent with input %dx%d stride %d up %d", a.Hout, a.Wout,
                a.Hin, a.Win, a.stride, a.up);

@@ -24,6 +24,10 @@ struct GemmArgs {
     int M = 0, N = 0, K = 0;
     // conv geometry
     int Hin = 0, Win = 0, Cin = 0, Hout = 0, Wout = 0, stride = 1, up = 0;
+    // CONV, stride 2 only: the 3x3 window of output (oy, ox) starts AT input (2 oy, 2 ox) instead of (2 oy - 1, 2 ox - 1): the
+    // AutoencoderKL encoder's downsampler, F.pad(x, (0, 1, 0, 1)) followed by an unpadded stride-2 conv.  The row below the
+    // bottom edge and the column right of the right edge read as zero; Hin and Win are even and Hout = Hin / 2 exactly.
+    int asym = 0;
     int splitk = 1;                   // > 1: K is split over blocks, fp32 partials go through `slab`
     float* slab = nullptr;            // [splitk, M, N] fp32 scratch (required when splitk > 1)
     // split-K only: leave the partial sums in `slab` and launch no splitk_reduce_kernel -- the consuming single-launch
@@ -225,6 +229,18 @@ int sd_launch_clip_score(const float* img, const float* txt, int B, int P, float
 // fused) -> NHWC bf16 [B,H,W,Cout]
 int sd_launch_conv_in(const float* x, int Bsrc, const float* Wt /*[Cin*9][Cout] fp32*/, const float* bias,
                       bf16_t* y, int B, int H, int W, int Cin, int Cout, hipStream_t stream);
+// AutoencoderKL encoder entry: fp32 NCHW images [B,3,H,W] in [0,1] -> conv_in(2 x - 1) as NHWC bf16 [B,H,W,Cout]
+// (the preprocessing is applied in the load; the zero padding is of the PREPROCESSED image)
+int sd_launch_conv_in_image(const float* img, const float* Wt /*[27][Cout] fp32*/, const float* bias, bf16_t* y, int B, int H,
+                            int W, int Cout, hipStream_t stream);
+// AutoencoderKL encoder exit: conv_out (3x3, Cin -> 8, bf16 operands, fp32 sums) and quant_conv (1x1, 8 -> 8, fp32) in one
+// launch: NHWC bf16 [B,H,W,Cin] -> moments NCHW fp32 [B,8,H,W]
+int sd_launch_vae_enc_out(const bf16_t* x, const bf16_t* Wp /*[8][9][Cin]*/, const float* bias, const float* Wq /*[8][8]*/,
+                          const float* bq, float* y, int B, int H, int W, int Cin, hipStream_t stream);
+// DiagonalGaussianDistribution: z = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise), or scale * mean when noise is
+// null (mode()).  moments [B][2 C][hw] fp32 = [mean | logvar], noise / z [B][C][hw] fp32.
+int sd_launch_vae_posterior(const float* moments, const float* noise, float scale, float* z, int B, int C, long hw,
+                            hipStream_t stream);
 // conv_out: NHWC bf16 [B,H,W,Cin] -> NCHW fp32 [B,Cout,H,W]  (Cout <= 4)
 int sd_launch_conv_out(const bf16_t* x, const bf16_t* Wp /*[Cout][9][Cin]*/, const float* bias, float* y, int B,
                        int H, int W, int Cin, int Cout, hipStream_t stream);

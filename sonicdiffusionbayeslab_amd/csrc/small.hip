@@ -54,7 +54,9 @@ __global__ __launch_bounds__(256) void gemv_kernel(const float* __restrict__ x, 
 }
 
 // ---- conv_in: 3x3, Cin = 4, one block per output row, thread = 2 output channels ------------
-template <int CIN>
+// IMG (the AutoencoderKL encoder's entry, Cin = 3): x holds images in [0, 1] and the conv sees 2 x - 1, applied in the load
+// to the pixels INSIDE the image -- the padding ring is zero in the preprocessed domain
+template <int CIN, bool IMG = false>
 __global__ void conv_in_kernel(const float* __restrict__ x, int Bsrc, const float* __restrict__ Wt,
                                const float* __restrict__ bias, bf16_t* __restrict__ y, int H, int W, int Cout) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -68,7 +70,10 @@ __global__ void conv_in_kernel(const float* __restrict__ x, int Bsrc, const floa
         const int dy = rem / PW, px = rem - dy * PW;
         const int iy = yrow + dy - 1, ix = px - 1;
         float v = 0.f;
-        if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = x[(((long)bs * CIN + ci) * H + iy) * W + ix];
+        if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
+            v = x[(((long)bs * CIN + ci) * H + iy) * W + ix];
+            if (IMG) v = 2.f * v - 1.f;
+        }
         patch[i] = v;
     }
     __syncthreads();
@@ -335,6 +340,66 @@ __global__ void f32_to_bf16_kernel(const float* __restrict__ src, bf16_t* __rest
     ((u32x2*)dst)[i] = o;
 }
 
+// ---- AutoencoderKL encoder exit: conv_out 3x3 Cin -> 8 and quant_conv 1x1 8 -> 8, one wave per latent pixel ------------
+// The 3x3 contracts bf16 operands into fp32 (lane = 8-channel chunk, as conv_out_kernel).  The butterfly reduction leaves all
+// 8 sums in every lane, so lane co < 8 applies row co of quant_conv to them in fp32 and stores moment channel co.
+__global__ __launch_bounds__(256) void vae_enc_out_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ Wp,
+                                                          const float* __restrict__ bias, const float* __restrict__ Wq,
+                                                          const float* __restrict__ bq, float* __restrict__ y, int B, int H,
+                                                          int W, int Cin) {
+    const int lane = threadIdx.x & 63;
+    const long pix = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long npix = (long)B * H * W;
+    if (pix >= npix) return;
+    const int b = (int)(pix / (H * W));
+    const int rem = (int)(pix - (long)b * H * W);
+    const int oy = rem / W, ox = rem - oy * W;
+    const int nchunks = Cin / 8;
+    float acc[8];
+#pragma unroll
+    for (int co = 0; co < 8; ++co) acc[co] = 0.f;
+    for (int ch = lane; ch < nchunks; ch += 64) {
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int iy = oy + tap / 3 - 1, ix = ox + tap % 3 - 1;
+            if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
+            const u32x4 v = *(const u32x4*)(x + (((long)b * H + iy) * W + ix) * Cin + ch * 8);
+            const float f[8] = {bflo(v[0]), bfhi(v[0]), bflo(v[1]), bfhi(v[1]),
+                                bflo(v[2]), bfhi(v[2]), bflo(v[3]), bfhi(v[3])};
+#pragma unroll
+            for (int co = 0; co < 8; ++co) {
+                const u32x4 w = *(const u32x4*)(Wp + ((long)co * 9 + tap) * Cin + ch * 8);
+                acc[co] += f[0] * bflo(w[0]) + f[1] * bfhi(w[0]) + f[2] * bflo(w[1]) + f[3] * bfhi(w[1]) +
+                           f[4] * bflo(w[2]) + f[5] * bfhi(w[2]) + f[6] * bflo(w[3]) + f[7] * bfhi(w[3]);
+            }
+        }
+    }
+#pragma unroll
+    for (int co = 0; co < 8; ++co) acc[co] = wave_sum(acc[co]) + bias[co];
+    if (lane < 8) {
+        float q = bq[lane];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) q += Wq[lane * 8 + c] * acc[c];
+        y[(((long)b * 8 + lane) * H + oy) * W + ox] = q;
+    }
+}
+
+// ---- DiagonalGaussianDistribution.sample() / .mode() times the scaling factor: one elementwise fp32 launch ----------
+__global__ void vae_posterior_kernel(const float* __restrict__ moments, const float* __restrict__ noise, float scale,
+                                     float* __restrict__ z, int C, long hw, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long chw = (long)C * hw;
+    const long b = i / chw, r = i - b * chw;
+    const float mean = moments[b * 2 * chw + r];
+    float v = mean;
+    if (noise) {
+        const float lv = fminf(fmaxf(moments[b * 2 * chw + chw + r], -30.f), 20.f);
+        v = mean + expf(0.5f * lv) * noise[i];
+    }
+    z[i] = scale * v;
+}
+
 __global__ void pqconv_kernel(const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ bias,
                               float* __restrict__ y, int B, int HW, float in_scale) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -356,6 +421,27 @@ int sd_launch_pqconv(const float* x, const float* W, const float* bias, float* y
     SD_REQUIRE(x && W && bias && y && B > 0 && HW > 0, "pqconv: bad operand");
     const long n = (long)B * HW;
     hipLaunchKernelGGL(pqconv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, W, bias, y, B, HW, in_scale);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sd_launch_vae_enc_out(const bf16_t* x, const bf16_t* Wp, const float* bias, const float* Wq, const float* bq, float* y,
+                          int B, int H, int W, int Cin, hipStream_t stream) {
+    SD_REQUIRE(x && Wp && bias && Wq && bq && y, "vae_enc_out: null operand");
+    SD_REQUIRE(Cin % 8 == 0 && Cin > 0 && B > 0 && H > 0 && W > 0, "vae_enc_out: B=%d H=%d W=%d Cin=%d", B, H, W, Cin);
+    const long npix = (long)B * H * W;
+    hipLaunchKernelGGL(vae_enc_out_kernel, dim3((unsigned)((npix + 3) / 4)), dim3(256), 0, stream, x, Wp, bias, Wq, bq, y, B, H,
+                       W, Cin);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sd_launch_vae_posterior(const float* moments, const float* noise, float scale, float* z, int B, int C, long hw,
+                            hipStream_t stream) {
+    SD_REQUIRE(moments && z && B > 0 && C > 0 && hw > 0, "vae_posterior: bad operand");
+    const long n = (long)B * C * hw;
+    hipLaunchKernelGGL(vae_posterior_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, moments, noise, scale, z, C,
+                       hw, n);
     SD_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -495,6 +581,19 @@ int sd_launch_conv_in(const float* x, int Bsrc, const float* Wt, const float* bi
     const int threads = (Cout / 2 + 63) / 64 * 64;
     const size_t smem = (size_t)Cin * 3 * (W + 2) * sizeof(float);
     hipLaunchKernelGGL((conv_in_kernel<4>), dim3(H, B), dim3(threads), smem, stream, x, Bsrc, Wt, bias, y, H, W, Cout);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sd_launch_conv_in_image(const float* img, const float* Wt, const float* bias, bf16_t* y, int B, int H, int W, int Cout,
+                            hipStream_t stream) {
+    SD_REQUIRE(img && Wt && bias && y, "conv_in_image: null operand");
+    SD_REQUIRE(Cout % 2 == 0 && Cout / 2 <= 1024, "conv_in_image: Cout=%d", Cout);
+    SD_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && W <= 4096, "conv_in_image: B=%d H=%d W=%d", B, H, W);
+    const int threads = (Cout / 2 + 63) / 64 * 64;
+    const size_t smem = (size_t)3 * 3 * (W + 2) * sizeof(float);       // (36.9 KiB at the widest image, 1024)
+    SD_REQUIRE(smem <= 64 * 1024, "conv_in_image: W=%d needs %zu bytes of LDS (64 KiB per workgroup)", W, smem);
+    hipLaunchKernelGGL((conv_in_kernel<3, true>), dim3(H, B), dim3(threads), smem, stream, img, B, Wt, bias, y, H, W, Cout);
     SD_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -92,7 +92,7 @@ struct Wrap {  // one DeepCache-wrapped module enclosing an op
 
 enum OpKind { OP_SINUSOID, OP_GEMV, OP_CONV_IN, OP_GN, OP_CONV3, OP_GEMM, OP_LN, OP_ATTN, OP_CONV_OUT, OP_SOFTMAX, OP_PQCONV,
               OP_CLIP_EMBED, OP_CLIP_ATTN, OP_QGELU, OP_TO_F32, OP_XATTN, OP_REPLICATE,
-              OP_VIT_PREP, OP_VIT_EMBED, OP_VIT_ATTN, OP_POOL };
+              OP_VIT_PREP, OP_VIT_EMBED, OP_VIT_ATTN, OP_POOL, OP_CONV_IN_IMG, OP_ENC_OUT };
 
 constexpr int REP_TEXT_POOLED = 2;       // Plan::rep of a CLIP text handle's sd_clip_text_embeds plan
 
@@ -134,6 +134,7 @@ struct Op {
     // LayerNorm fold: rs = row partials this op writes ([np][M][2] fp32); lnrs / lnnp / c1 = partials and column sums
     // this GEMM normalises with (its x1 is the un-normalised tensor, its weights carry gamma, its bias W beta + b)
     int subpix = 0;                   // CONV3 with up: four 2x2 convs on the low-res input (GemmArgs::subpix)
+    int asym = 0;                     // CONV3 stride 2 padded right / bottom only (GemmArgs::asym: the VAE encoder's downsamplers)
     int hm = 0;                       // GEMM: q|k|v with head-major K / V (HW = tokens per sample); ATTN: K / V are head-major
     int qps = 0;                      // ATTN: Q arrives multiplied by scale * log2 e (folded into W_q at pack time)
     int rs = -1, lnrs = -1, lnnp = 0;
@@ -213,7 +214,8 @@ struct Plan {
 }  // namespace
 
 struct sd_unet {
-    int kind = 0;   // 0 = UNet2DConditionModel, 1 = AutoencoderKL decoder, 2 = CLIP text encoder, 3 = CLIP vision tower
+    // 0 = UNet2DConditionModel, 1 = AutoencoderKL decoder, 2 = CLIP text encoder, 3 = CLIP vision tower, 4 = AutoencoderKL encoder
+    int kind = 0;
     sd_unet_config cfg;
     sd_clip_config clip;
     sd_clip_vision_config vis;
@@ -457,6 +459,49 @@ void enumerate_params_vae(sd_unet* u) {
     e.add("decoder.conv_norm_out.weight", {ch}); e.add("decoder.conv_norm_out.bias", {ch});
     e.add("decoder.conv_out.weight", {c.out_channels, ch, 3, 3});
     e.add("decoder.conv_out.bias", {c.out_channels});
+}
+
+// AutoencoderKL encoder (diffusers 0.32.1 names): encoder.* + quant_conv.  cfg.out_channels = image channels (3),
+// cfg.in_channels = latent channels (4): the moments carry 2 * in_channels = 8.
+void enumerate_params_vae_encoder(sd_unet* u) {
+    const sd_unet_config& c = u->cfg;
+    Enum e{u};
+    const int nl = c.num_levels, top = c.block_out_channels[nl - 1], c0 = c.block_out_channels[0], zc = 2 * c.in_channels;
+    auto resnet = [&](const std::string& p, int cin, int cout) {
+        e.add(p + "norm1.weight", {cin}); e.add(p + "norm1.bias", {cin});
+        e.add(p + "conv1.weight", {cout, cin, 3, 3}); e.add(p + "conv1.bias", {cout});
+        e.add(p + "norm2.weight", {cout}); e.add(p + "norm2.bias", {cout});
+        e.add(p + "conv2.weight", {cout, cout, 3, 3}); e.add(p + "conv2.bias", {cout});
+        if (cin != cout) { e.add(p + "conv_shortcut.weight", {cout, cin, 1, 1}); e.add(p + "conv_shortcut.bias", {cout}); }
+    };
+    e.add("encoder.conv_in.weight", {c0, c.out_channels, 3, 3});
+    e.add("encoder.conv_in.bias", {c0});
+    int ch = c0;
+    for (int i = 0; i < nl; ++i) {
+        const int co = c.block_out_channels[i];
+        const std::string bp = "encoder.down_blocks." + std::to_string(i) + ".";
+        for (int j = 0; j < c.layers_per_block; ++j) {
+            resnet(bp + "resnets." + std::to_string(j) + ".", ch, co);
+            ch = co;
+        }
+        if (i < nl - 1) {
+            e.add(bp + "downsamplers.0.conv.weight", {co, co, 3, 3});
+            e.add(bp + "downsamplers.0.conv.bias", {co});
+        }
+    }
+    resnet("encoder.mid_block.resnets.0.", top, top);
+    const std::string a = "encoder.mid_block.attentions.0.";
+    e.add(a + "group_norm.weight", {top}); e.add(a + "group_norm.bias", {top});
+    for (const char* n : {"to_q", "to_k", "to_v", "to_out.0"}) {
+        e.add(a + n + ".weight", {top, top});
+        e.add(a + n + ".bias", {top});
+    }
+    resnet("encoder.mid_block.resnets.1.", top, top);
+    e.add("encoder.conv_norm_out.weight", {top}); e.add("encoder.conv_norm_out.bias", {top});
+    e.add("encoder.conv_out.weight", {zc, top, 3, 3});
+    e.add("encoder.conv_out.bias", {zc});
+    e.add("quant_conv.weight", {zc, zc, 1, 1});
+    e.add("quant_conv.bias", {zc});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -909,6 +954,48 @@ int pack_vae(sd_unet* u) {
     return 0;
 }
 
+int pack_vae_encoder(sd_unet* u) {
+    const sd_unet_config& c = u->cfg;
+    Packer pk{u};
+    const int nl = c.num_levels, top = c.block_out_channels[nl - 1], c0 = c.block_out_channels[0];
+    {   // conv_in: [O][3][3][3] -> Wt[k = ic*9+tap][O] fp32 (the entry conv runs in fp32 on the fp32 image)
+        const auto& d = pk.P("encoder.conv_in.weight");
+        const int O = c0, I = c.out_channels;
+        size_t off = pk.alloc("encoder.conv_in.weight", d.size() * 4);
+        float* o = (float*)(u->hblob.data() + off);
+        for (int oc = 0; oc < O; ++oc)
+            for (int k = 0; k < I * 9; ++k) o[(size_t)k * O + oc] = d[(size_t)oc * I * 9 + k];
+        pk.f32("encoder.conv_in.bias");
+    }
+    int ch = c0;
+    for (int i = 0; i < nl; ++i) {
+        const int co = c.block_out_channels[i];
+        const std::string bp = "encoder.down_blocks." + std::to_string(i) + ".";
+        for (int j = 0; j < c.layers_per_block; ++j) {
+            pk.resnet(bp + "resnets." + std::to_string(j) + ".", ch, co);
+            ch = co;
+        }
+        if (i < nl - 1) { pk.conv3(bp + "downsamplers.0.conv.weight", co, co); pk.f32(bp + "downsamplers.0.conv.bias"); }
+    }
+    pk.resnet("encoder.mid_block.resnets.0.", top, top);
+    const std::string a = "encoder.mid_block.attentions.0.";
+    pk.f32(a + "group_norm.weight"); pk.f32(a + "group_norm.bias");
+    pk.concat_rows(a + "qk.weight", {a + "to_q.weight", a + "to_k.weight"});
+    {
+        size_t off = pk.alloc(a + "qk.bias", (size_t)2 * top * 4);
+        float* o = (float*)(u->hblob.data() + off);
+        for (const char* n : {"to_q.bias", "to_k.bias"})
+            for (float v : pk.P(a + n)) *o++ = v;
+    }
+    pk.bf16_same(a + "to_v.weight"); pk.f32(a + "to_v.bias");
+    pk.bf16_same(a + "to_out.0.weight"); pk.f32(a + "to_out.0.bias");
+    pk.resnet("encoder.mid_block.resnets.1.", top, top);
+    pk.f32("encoder.conv_norm_out.weight"); pk.f32("encoder.conv_norm_out.bias");
+    pk.conv3_ohwi("encoder.conv_out.weight", 2 * c.in_channels, top); pk.f32("encoder.conv_out.bias");
+    pk.f32("quant_conv.weight"); pk.f32("quant_conv.bias");       // applied in fp32 by the exit kernel
+    return 0;
+}
+
 // the encoder layers of both CLIP towers: fused q | k | v rows and biases, bf16 GEMM weights, fp32 vectors
 void pack_clip_layer(Packer& pk, const std::string& p, int H) {
     const std::string a = p + "self_attn.";
@@ -961,6 +1048,7 @@ int pack_all(sd_unet* u) {
     if (u->kind == 1) return pack_vae(u);
     if (u->kind == 2) return pack_clip(u);
     if (u->kind == 3) return pack_vit(u);
+    if (u->kind == 4) return pack_vae_encoder(u);
     const sd_unet_config& c = u->cfg;
     Packer pk{u};
     const int c0 = c.block_out_channels[0], temb = 4 * c0, nl = c.num_levels;
@@ -1413,6 +1501,43 @@ struct Builder {
           o.w = W("decoder.conv_out.weight"); o.b = W("decoder.conv_out.bias"); push(o); }
     }
 
+    // ---- AutoencoderKL encoder (diffusers 0.32.1 AutoencoderKL.encode, upstream-recall): image -> moments [mean | logvar] ----
+    // The plan's (lh, lw) is the LATENT size; the image is 2^(levels - 1) times that.  Entry and exit are kernels of their
+    // own (small.hip); everything between runs on the decoder's ops, with the downsamplers on the conv's asymmetric mode.
+    void build_vae_encoder() {
+        const sd_unet_config& c = u->cfg;
+        const int nl = c.num_levels, top = c.block_out_channels[nl - 1], c0 = c.block_out_channels[0];
+        int rh = pl.lh << (nl - 1), rw = pl.lw << (nl - 1);
+        int h;
+        { Op o; o.kind = OP_CONV_IN_IMG; o.x1 = T_LATENTS; o.B = UB; o.Hin = rh; o.Win = rw; o.Cin = c.out_channels; o.N = c0;
+          o.w = W("encoder.conv_in.weight"); o.b = W("encoder.conv_in.bias"); o.out = tensor((size_t)UB * rh * rw * c0 * 2);
+          push(o); h = o.out; }
+        pl.taps["conv_in"] = h;
+        int ch = c0;
+        for (int i = 0; i < nl; ++i) {
+            const int co = c.block_out_channels[i];
+            const std::string bp = "encoder.down_blocks." + std::to_string(i) + ".";
+            for (int j = 0; j < c.layers_per_block; ++j) {
+                h = vae_resnet(bp + "resnets." + std::to_string(j) + ".", h, ch, co, rh, rw);
+                ch = co;
+            }
+            if (i < nl - 1) {
+                h = conv3(h, rh, rw, co, co, 2, 0, bp + "downsamplers.0.conv.weight", bp + "downsamplers.0.conv.bias", 0, -1, -1);
+                pl.ops.back().asym = 1;
+                rh /= 2; rw /= 2;
+            }
+            pl.taps["down" + std::to_string(i)] = h;
+        }
+        h = vae_resnet("encoder.mid_block.resnets.0.", h, top, top, rh, rw);
+        h = vae_attention("encoder.mid_block.attentions.0.", h, top, rh, rw);
+        h = vae_resnet("encoder.mid_block.resnets.1.", h, top, top, rh, rw);
+        pl.taps["mid"] = h;
+        int g = gn(h, top, -1, 0, rh * rw, "encoder.conv_norm_out.weight", "encoder.conv_norm_out.bias", 1e-6f, 1);
+        { Op o; o.kind = OP_ENC_OUT; o.x1 = g; o.out = T_EPS; o.B = UB; o.Hin = rh; o.Win = rw; o.Cin = top; o.N = 2 * c.in_channels;
+          o.w = W("encoder.conv_out.weight"); o.b = W("encoder.conv_out.bias");
+          o.g = W("quant_conv.weight"); o.be = W("quant_conv.bias"); push(o); }
+    }
+
     // CLIPTextTransformer (transformers 4.48.0 modeling_clip.py): token + position embedding,
     // pre-LN layers with causal self-attention and a quick_gelu MLP, final LayerNorm -> last_hidden_state
     void build_clip() {
@@ -1490,6 +1615,7 @@ struct Builder {
         if (u->kind == 1) { build_vae(); return; }
         if (u->kind == 2) { build_clip(); return; }
         if (u->kind == 3) { build_vit(); return; }
+        if (u->kind == 4) { build_vae_encoder(); return; }
         const sd_unet_config& c = u->cfg;
         const int nl = c.num_levels, c0 = c.block_out_channels[0], temb = 4 * c0;
         const int L = c.context_len;
@@ -1710,9 +1836,10 @@ static int plan_rep(const sd_unet* u, int latent_batch, int unet_batch) {
 // every downsampler halves them exactly; VAE decoder: sides that are multiples of 8 (the mid-block attention's token count
 // HW = h * w then stays a multiple of 64) up to 128.  The handle's sample_size is the default and always accepted.
 static int check_latent_size(const sd_unet* u, int lh, int lw, const char* who) {
-    if (u->kind == 1) {
+    if (u->kind == 1 || u->kind == 4) {
         SD_REQUIRE(lh >= 8 && lw >= 8 && lh <= 128 && lw <= 128 && lh % 8 == 0 && lw % 8 == 0,
-                   "%s: latent %dx%d (the VAE decoder takes sides that are multiples of 8 in [8, 128])", who, lh, lw);
+                   "%s: latent %dx%d (the VAE %s takes sides that are multiples of 8 in [8, 128])", who, lh, lw,
+                   u->kind == 1 ? "decoder" : "encoder");
     } else if (u->kind == 0) {
         const int d = 1 << (u->cfg.num_levels - 1);
         SD_REQUIRE(lh >= d && lw >= d && lh <= 256 && lw <= 256 && lh % d == 0 && lw % d == 0,
@@ -1808,6 +1935,7 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
             a.zero_page = g_zero_page; a.splitk = o.splitk; a.slab = (float*)T(o.aux); a.defer_reduce = o.defer;
             if (o.dt) { a.dt = 1; a.wscale = (const float*)(wb + o.wsc); a.xscale_inv = 1.0f / o.xs; }
             a.stats = (float*)T(o.stats);
+            a.asym = o.asym;
             if (o.subpix) { a.subpix = 1; a.up = 0; a.w_batch_stride = (long)o.N * 4 * o.Cin; }
             return sd_launch_conv3x3(a, stream);
         }
@@ -1883,6 +2011,13 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
                                        (bf16_t*)T(o.out), stream);
         case OP_TO_F32:
             return sd_launch_bf16_to_f32((const bf16_t*)T(o.x1), eps_out, (long)o.M * o.N, stream);
+        case OP_CONV_IN_IMG:
+            return sd_launch_conv_in_image(latents, (const float*)(wb + o.w), (const float*)(wb + o.b), (bf16_t*)T(o.out), o.B,
+                                           o.Hin, o.Win, o.N, stream);
+        case OP_ENC_OUT:
+            return sd_launch_vae_enc_out((const bf16_t*)T(o.x1), (const bf16_t*)(wb + o.w), (const float*)(wb + o.b),
+                                         (const float*)(wb + o.g), (const float*)(wb + o.be), eps_out, o.B, o.Hin, o.Win, o.Cin,
+                                         stream);
         case OP_CONV_OUT:
             return sd_launch_conv_out((const bf16_t*)T(o.x1), (const bf16_t*)(wb + o.w), (const float*)(wb + o.b), eps_out,
                                       o.B, o.Hin, o.Win, o.Cin, o.N, stream);
@@ -1976,6 +2111,54 @@ extern "C" int sd_vae_decode_hw(sd_unet* u, void* stream, const float* latents, 
         if ((rc = run_op(u, *pl, pl->ops[i], (char*)workspace, latents, batch, images_out, latent_scale, (hipStream_t)stream)))
             return rc;
     return 0;
+}
+
+// ---- AutoencoderKL encoder: `vae.encode(image)` of diffusers' StableDiffusionImg2ImgPipeline.prepare_latents (upstream-recall) ----
+extern "C" int sd_vae_encoder_create(const sd_unet_config* cfg, sd_unet** out) {
+    SD_REQUIRE(cfg && out, "sd_vae_encoder_create: null argument");
+    SD_REQUIRE(cfg->num_levels >= 1 && cfg->num_levels <= 8, "sd_vae_encoder_create: num_levels %d", cfg->num_levels);
+    SD_REQUIRE(cfg->in_channels == 4 && cfg->out_channels == 3,
+               "sd_vae_encoder_create: %d latent / %d image channels (4 / 3 are built: 8 moment channels, RGB entry conv)",
+               cfg->in_channels, cfg->out_channels);
+    SD_REQUIRE(cfg->num_levels == 4, "sd_vae_encoder_create: %d levels (4 are built: the image is 8 x the latent, and a latent side that is a "
+               "multiple of 8 keeps every level's sides even)", cfg->num_levels);
+    for (int i = 0; i < cfg->num_levels; ++i) {
+        const int c = cfg->block_out_channels[i], cpg = cfg->norm_num_groups ? c / cfg->norm_num_groups : 0;
+        SD_REQUIRE(c % 64 == 0 && c % cfg->norm_num_groups == 0 && (cpg >= 8 || cpg == 4),
+                   "sd_vae_encoder_create: block_out_channels[%d]=%d must be a multiple of 64 with 4 or >= 8 channels per group", i, c);
+    }
+    SD_REQUIRE(cfg->sample_size >= 8 && cfg->sample_size <= 128 && cfg->sample_size % 8 == 0,
+               "sd_vae_encoder_create: latent size %d (a multiple of 8 in [8, 128])", cfg->sample_size);
+    sd_unet* u = new sd_unet();
+    u->kind = 4;
+    u->cfg = *cfg;
+    u->cfg.time_cond_proj_dim = 0;      // (a UNet field)
+    u->debug_taps = getenv("SD_DEBUG_TAPS") != nullptr;
+    enumerate_params_vae_encoder(u);
+    *out = u;
+    return 0;
+}
+
+extern "C" int sd_vae_encode_hw(sd_unet* u, void* stream, const float* images, int batch, int latent_h, int latent_w,
+                                float* moments_out, void* workspace, long long workspace_bytes) {
+    SD_REQUIRE(u && u->kind == 4, "vae_encode: not a VAE encoder handle");
+    SD_REQUIRE(images && moments_out && workspace && batch > 0, "vae_encode: null argument");
+    if (check_latent_size(u, latent_h, latent_w, "vae_encode")) return -1;
+    Plan* pl;
+    int rc = get_plan(u, batch, -1, &pl, 1, latent_h, latent_w);
+    if (rc) return rc;
+    SD_REQUIRE((long long)pl->total_bytes <= workspace_bytes, "vae_encode: workspace too small (%lld < %zu)", workspace_bytes,
+               pl->total_bytes);
+    SD_REQUIRE(((uintptr_t)workspace & 255) == 0, "vae_encode: workspace must be 256-byte aligned");
+    for (size_t i = 0; i < pl->ops.size(); ++i)
+        if ((rc = run_op(u, *pl, pl->ops[i], (char*)workspace, images, batch, moments_out, 0.f, (hipStream_t)stream))) return rc;
+    return 0;
+}
+
+extern "C" int sd_vae_posterior_sample(void* stream, const float* moments, const float* noise_or_null, float scale,
+                                       float* latents_out, int batch, long long hw) {
+    SD_REQUIRE(moments && latents_out && batch > 0 && hw > 0, "vae_posterior_sample: null argument");
+    return sd_launch_vae_posterior(moments, noise_or_null, scale, latents_out, batch, 4, (long)hw, (hipStream_t)stream);
 }
 
 // ---- CLIP text encoder: `self.text_encoder(text_input_ids)[0]` inside encode_prompt (src/models.py:139-155) ----
@@ -2684,6 +2867,26 @@ extern "C" int sd_op_conv3x3(void* stream, const void* X, const void* W, const f
     if (a.splitk > 1) {
         a.slab = (float*)op_scratch((size_t)a.splitk * a.M * a.N * 4);
         SD_REQUIRE(a.slab, "sd_op_conv3x3: cannot allocate split-K scratch");
+    }
+    return sd_launch_conv3x3(a, (hipStream_t)stream);
+}
+
+// 3x3 stride-2 conv padded on the right and bottom only (GemmArgs::asym; the AutoencoderKL encoder's downsampler): W packed as
+// for sd_op_conv3x3, Hin and Win even, Y = [B, Hin / 2, Win / 2, Cout]
+extern "C" int sd_op_conv3x3_down_asym(void* stream, const void* X, const void* W, const float* bias, void* Y, int B, int Hin,
+                                       int Win, int Cin, int Cout) {
+    if (ensure_zero_page()) return -2;
+    SD_REQUIRE(X && W && Y && B > 0 && Hin > 0 && Win > 0 && Hin % 2 == 0 && Win % 2 == 0,
+               "conv3x3_down_asym: even input sides (%dx%d)", Hin, Win);
+    GemmArgs a;
+    a.X = (const bf16_t*)X; a.W = (const bf16_t*)W; a.bias = bias; a.C = (bf16_t*)Y; a.ldc = Cout;
+    a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.stride = 2; a.up = 0; a.asym = 1;
+    a.Hout = Hin / 2; a.Wout = Win / 2;
+    a.M = B * a.Hout * a.Wout; a.N = Cout; a.K = 9 * Cin; a.K1 = a.K; a.zero_page = g_zero_page;
+    a.splitk = sd_conv3x3_splitk(a.M, a.N, Cin, Hin, Win, 2, 0);
+    if (a.splitk > 1) {
+        a.slab = (float*)op_scratch((size_t)a.splitk * a.M * a.N * 4);
+        SD_REQUIRE(a.slab, "sd_op_conv3x3_down_asym: cannot allocate split-K scratch");
     }
     return sd_launch_conv3x3(a, (hipStream_t)stream);
 }

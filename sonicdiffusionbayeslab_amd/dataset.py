@@ -7,6 +7,34 @@ from __future__ import annotations
 import json
 import os
 
+import torch
+
+
+def image_transform(img, size: int) -> torch.Tensor:
+    """The reference's image transform (``src/experiments/base_experiment.py:79-85``: ``Resize(size)``,
+    ``CenterCrop(size)``, ``ToTensor()``) restated on Pillow alone: the SHORTER side is resized to ``size`` with bilinear
+    interpolation and the other to ``int(size * long / short)``, the centre ``size x size`` window is cut
+    (offset ``int(round((side - size) / 2))``), and the uint8 RGB values are divided by 255 -> fp32 ``[3, size, size]``."""
+    import numpy as np
+    from PIL import Image
+    img = img.convert("RGB")
+    w, h = img.size
+    if w <= h:
+        nw, nh = size, int(size * h / w)
+    else:
+        nh, nw = size, int(size * w / h)
+    if (nw, nh) != (w, h):
+        img = img.resize((nw, nh), Image.BILINEAR)
+    left, top = int(round((nw - size) / 2.0)), int(round((nh - size) / 2.0))
+    img = img.crop((left, top, left + size, top + size))
+    return torch.from_numpy(np.asarray(img, dtype=np.float32) / 255.0).permute(2, 0, 1).contiguous()
+
+
+def load_image(path: str, size: int) -> torch.Tensor:
+    from PIL import Image
+    with Image.open(path) as im:
+        return image_transform(im, size)
+
 
 class PromptDataset:
     def __init__(self, image_dir: str, prompts_file: str):

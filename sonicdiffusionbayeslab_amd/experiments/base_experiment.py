@@ -23,7 +23,7 @@ from collections import defaultdict
 import torch
 
 from .. import dist as sdist
-from ..dataset import PromptDataset
+from ..dataset import PromptDataset, load_image
 from ..registry import metrics_registry, models_registry, schedulers_registry
 
 
@@ -82,6 +82,20 @@ class BaseMethod(ABC):
 
     def setup_dataset(self):
         self.test_dataset = PromptDataset(self.config.dataset.img_dataset, self.config.dataset.prompts)
+        # optional experiment_params.strength (key of this build): image-to-image -- every prompt's own file from
+        # dataset.img_dataset is the start image of its sample.  Absent: nothing is opened, as before.
+        strength = self.config.get("experiment_params", {}).get("strength", None)
+        self.img2img_strength = None if strength is None else float(strength)
+        if self.img2img_strength is not None and not os.path.isdir(str(self.config.dataset.img_dataset)):
+            raise FileNotFoundError(f"experiment_params.strength is set (image-to-image) but the image directory "
+                                    f"dataset.img_dataset = {str(self.config.dataset.img_dataset)!r} does not exist")
+
+    def load_images(self, files):
+        """The start images of one prompt batch, ``[B, 3, S, S]`` in [0, 1] (``dataset.image_size``; the reference's
+        transform, ``dataset.image_transform``)."""
+        size = int(self.config.dataset.get("image_size", 512))
+        root = str(self.config.dataset.img_dataset)
+        return torch.stack([load_image(os.path.join(root, f), size) for f in files])
 
     def setup_metrics(self):
         """``src/experiments/base_experiment.py:93-113``.  ``time_metric`` always; ``clip_score`` (``:96-98``) when
@@ -123,6 +137,10 @@ class BaseMethod(ABC):
             sharded = sdist.active()
             lo, hi = sdist.shard_range(len(prompts), self.rank, self.world) if sharded else (0, len(prompts))
             local_prompts = prompts[lo:hi]
+            if getattr(self, "img2img_strength", None) is not None and len(local_prompts) > 0:
+                # image-to-image: this rank's slice of the batch's start images rides with its slice of the prompts
+                call_kwargs = {**call_kwargs, "image": self.load_images(list(batch["image_file"])[lo:hi]),
+                               "strength": self.img2img_strength}
             if len(local_prompts) > 0:
                 # every Gaussian of the call (initial latents, per-step noise of the stochastic samplers) is drawn for the
                 # GLOBAL batch from the shared generator and sliced: dist.randn inside dist.shard_draws

@@ -35,7 +35,7 @@ from . import dist as sdist
 from .registry import models_registry
 from .schedulers import PNDMConfigStub
 from .unet import CACHE_FULL_AND_STORE, CACHE_OFF, CACHE_SKIP, HipUNet2DConditionModel
-from .vae import HipVaeDecoder, VaeConfig, load_vae_state_dict, make_synthetic_vae_state_dict
+from .vae import HipVaeDecoder, HipVaeEncoder, VaeConfig, load_vae_state_dict, make_synthetic_vae_state_dict
 from .weights import UNetConfig, load_scheduler_config, load_unet_config, load_unet_state_dict, make_synthetic_state_dict
 
 
@@ -120,6 +120,7 @@ class StableDiffusionModel:
         # a local checkpoint with tokenizer/ + text_encoder/: the CLIP text tower on libsdhip replaces the stand-in
         self._clip_dir = clip_dir if text_encoder is None else None
         self.vae_decoder = vae_decoder
+        self.vae_encoder = None         # HipVaeEncoder, built by the first image-to-image call
         self.vae_config = _VaeConfig()
         self.device = torch.device("cpu")
         self._num_timesteps = 0
@@ -190,6 +191,20 @@ class StableDiffusionModel:
             sd = sd or make_synthetic_vae_state_dict(cfg)
             self.vae_decoder = HipVaeDecoder(cfg, sd, device=str(self.unet.device))
         return self.vae_decoder
+
+    def _ensure_vae_encoder(self):
+        """AutoencoderKL encoder on libsdhip (image-to-image); weights from where the decoder's come from."""
+        if self.vae_encoder is None:
+            self._ensure_unet()
+            cfg = VaeConfig(sample_size=self.unet_config.sample_size)
+            path = os.environ.get("SD_AMD_MODEL_DIR", "")
+            try:
+                sd = load_vae_state_dict(path) if path and os.path.isdir(path) else None
+            except FileNotFoundError:
+                sd = None
+            sd = sd or make_synthetic_vae_state_dict(cfg)
+            self.vae_encoder = HipVaeEncoder(cfg, sd, device=str(self.unet.device))
+        return self.vae_encoder
 
     def to(self, device):
         """``model.to(device)`` (``base_experiment.py:64``; ``ddim.py:31,33``).  The UNet weights
@@ -401,6 +416,124 @@ class StableDiffusionModel:
             self.weights_source += f" (per-tensor e4m3 activation scales {how})"
         return self.fp8_scales
 
+    # -- image-to-image (diffusers StableDiffusionImg2ImgPipeline, upstream-recall) -----------------------------------
+    @staticmethod
+    def img2img_steps(num_inference_steps: int, strength: float):
+        """``get_timesteps`` of diffusers' StableDiffusionImg2ImgPipeline: ``init = min(int(N * strength), N)``,
+        ``t_start = max(N - init, 0)``; returns ``(t_start, steps that run = N - t_start)``.  ``strength`` outside [0, 1]
+        and a combination that leaves no step to run raise ``ValueError``."""
+        if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 <= float(strength) <= 1.0:
+            raise ValueError(f"strength={strength!r}: the value of strength should be in [0.0, 1.0]")
+        n = int(num_inference_steps)
+        init = min(int(n * float(strength)), n)
+        t_start = max(n - init, 0)
+        if n - t_start < 1:
+            raise ValueError(f"strength={strength} with num_inference_steps={n} leaves {n - t_start} steps to run; "
+                             "image-to-image needs at least one (int(num_inference_steps * strength) >= 1)")
+        return t_start, n - t_start
+
+    @staticmethod
+    def _image_tensor(image) -> torch.Tensor:
+        """``image`` of a pipeline call -> fp32 [B, 3, H, W] in [0, 1] on the host: a float tensor as it is, a list of PIL
+        images of one size through ``/ 255`` (VaeImageProcessor.pil_to_numpy)."""
+        if isinstance(image, torch.Tensor):
+            if image.dim() != 4 or image.shape[1] != 3 or not image.is_floating_point():
+                raise ValueError(f"image must be a float tensor [B,3,H,W] in [0,1], got {tuple(image.shape)} {image.dtype}")
+            return image
+        if isinstance(image, (list, tuple)) and len(image) > 0 and all(hasattr(im, "convert") for im in image):
+            import numpy as np
+            sizes = {im.size for im in image}
+            if len(sizes) != 1:
+                raise ValueError(f"image: the PIL images of one call must have one size, got {sorted(sizes)}")
+            arr = np.stack([np.asarray(im.convert("RGB"), dtype=np.float32) / 255.0 for im in image])
+            return torch.from_numpy(arr).permute(0, 3, 1, 2).contiguous()
+        raise ValueError("image must be a float tensor [B,3,H,W] in [0,1] or a list of PIL images of one size")
+
+    def _img2img_args(self, image, strength, sample_mode, prompt, prompt_embeds, height, width, latents,
+                      num_inference_steps):
+        """Every argument check of an image-to-image call, before any GPU work.  Returns (image tensor on the host, height,
+        width, t_start)."""
+        from .schedulers import PNDMScheduler
+        if latents is not None:
+            raise ValueError("image and latents are exclusive: the start latents of an image-to-image call are the noised "
+                             "encoding of the image")
+        if isinstance(self.scheduler, PNDMScheduler) or not hasattr(self.scheduler, "add_noise"):
+            raise NotImplementedError(f"image= with {type(self.scheduler).__name__} is not built: PNDMScheduler duplicates its "
+                                      "second timestep, and a schedule sliced at t_start changes what its PLMS warm-up means "
+                                      "(DDIM, DPM-Solver and LCM are built)")
+        if sample_mode not in ("sample", "argmax"):
+            raise ValueError(f"sample_mode={sample_mode!r}: 'sample' or 'argmax'")
+        t_start, _ = self.img2img_steps(num_inference_steps, strength)
+        img = self._image_tensor(image)
+        ih, iw = int(img.shape[2]), int(img.shape[3])
+        self.check_size(ih, iw)                  # the image's sides obey SIZE_RULE like height / width
+        for name, v, iv in (("height", height, ih), ("width", width, iw)):
+            if v is not None and v != iv:
+                raise ValueError(f"{name}={v} disagrees with the image ({ih}x{iw}): the image defines the size of the call")
+        n_prompt = 1 if isinstance(prompt, str) else len(prompt) if prompt is not None else int(prompt_embeds.shape[0])
+        if img.shape[0] != n_prompt:
+            raise ValueError(f"image batch {img.shape[0]} does not match the prompt batch {n_prompt}")
+        return img, ih, iw, t_start
+
+    def _img2img_start(self, img, sample_mode, generator, device, first_timestep):
+        """Steps of StableDiffusionImg2ImgPipeline.prepare_latents, in upstream's order: encode, draw the posterior noise,
+        draw the forward noise, ``add_noise`` at the first timestep that runs.  Both draws go through ``dist.randn`` (the
+        global batch's draws under a sharded harness call).  Returns (noised start latents, clean scaled latents)."""
+        enc = self._ensure_vae_encoder()
+        moments = enc.encode(img.to(device))
+        shape = (moments.shape[0], moments.shape[1] // 2, moments.shape[2], moments.shape[3])
+        post = sdist.randn(shape, generator) if sample_mode == "sample" else None
+        init = enc.sample(moments, post, mode=sample_mode, scale=self.vae_config.scaling_factor)
+        noise = sdist.randn(shape, generator)
+        return self.scheduler.add_noise(init, noise, first_timestep), init
+
+    @torch.no_grad()
+    def _call_img2img(self, prompt, image, strength, sample_mode, height, width, num_inference_steps, timesteps, sigmas,
+                      guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents, prompt_embeds,
+                      negative_prompt_embeds, output_type, return_dict, guidance_rescale, step_noise, collect_x0):
+        """The loop of ``call`` started part-way down the schedule from a noised encoding of ``image`` (SDEdit).  The
+        schedule is the full ``num_inference_steps`` one; the last ``N - t_start`` of its timesteps run.  A multistep
+        scheduler starts with a fresh history at that index (``_index_of`` resolves it from the timestep) while its
+        lower-order rules at the end still count against the full schedule.  DeepCache's plan indexes the list that runs,
+        so the first executed step is a full one."""
+        img, ih, iw, t_start = self._img2img_args(image, strength, sample_mode, prompt, prompt_embeds, height, width, latents,
+                                                  num_inference_steps)
+        device, batch_size, do_cfg, ctx = self._begin(prompt, ih, iw, guidance_scale, negative_prompt,
+                                                      num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
+                                                      guidance_rescale, timesteps, sigmas)
+        unet_batch = ctx.shape[0]
+        self.scheduler.set_timesteps(num_inference_steps, device=device)
+        ts_host = list(self.scheduler._timesteps_list)[t_start * self.scheduler.order:]
+        dc = self._deepcache
+        # encoding and noising sit outside the timed region, as text encoding does
+        start, _ = self._img2img_start(img, sample_mode, generator, device, ts_host[0])
+        self.img2img_start_latents = start
+        latents = self._start_loop(batch_size, device, None, start, ctx, dc.cache_branch_id if dc is not None else -1)
+        eps = self._eps_buffer(unet_batch, device)
+        self._num_timesteps = len(ts_host)
+        x0_preds = []
+        is_lcm = hasattr(self.scheduler, "config") and "timestep_scaling" in self.scheduler.config
+
+        torch.cuda.synchronize(device)
+        start_time = time.time()
+        for i, t in enumerate(ts_host):
+            mode = CACHE_OFF
+            if dc is not None:
+                mode = CACHE_FULL_AND_STORE if ts_host.index(t) % dc.cache_interval == 0 else CACHE_SKIP
+            self.unet.forward_latents(latents, unet_batch, float(t), out=eps, cache_mode=mode)
+            kw = {}
+            if is_lcm and step_noise is not None and i < len(ts_host) - 1:
+                kw["noise"] = step_noise[i]             # indexed by EXECUTED step
+            if do_cfg and guidance_rescale > 0.0:
+                kw["guidance_rescale"] = guidance_rescale
+            step = self.scheduler.step_fused(eps, guidance_scale, latents, t, cfg=do_cfg, eta=eta, generator=generator, **kw)
+            latents, x0 = step[0], step[1]
+            if collect_x0:
+                x0_preds.append(x0[0:1])
+        torch.cuda.synchronize(device)
+        execution_time = time.time() - start_time
+        return self._finish(latents, x0_preds, output_type, return_dict, execution_time)
+
     # -- the sampling loop (src/models.py:32-335) ----------------------------------------------
     @torch.no_grad()
     def call(self, prompt: Union[str, List[str]] = None, height: Optional[int] = None, width: Optional[int] = None,
@@ -409,7 +542,16 @@ class StableDiffusionModel:
              latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None,
              negative_prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil",
              return_dict: bool = True, guidance_rescale: float = 0.0, step_noise: Optional[torch.Tensor] = None,
-             collect_x0: bool = True, **kwargs):
+             collect_x0: bool = True, image=None, strength: float = 0.8, sample_mode: str = "sample", **kwargs):
+        """``image`` ([B,3,H,W] floats in [0,1], or a list of PIL images of one size): image-to-image with the semantics
+        of diffusers' StableDiffusionImg2ImgPipeline -- the image defines the size, ``strength`` in [0, 1] how far up the
+        schedule its encoding is noised (``img2img_steps``), ``sample_mode`` whether the posterior is sampled or its mode
+        taken.  ``image is None``: text-to-image, the path below."""
+        if image is not None:
+            return self._call_img2img(prompt, image, strength, sample_mode, height, width, num_inference_steps, timesteps,
+                                      sigmas, guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents,
+                                      prompt_embeds, negative_prompt_embeds, output_type, return_dict, guidance_rescale,
+                                      step_noise, collect_x0)
         device, batch_size, do_cfg, ctx = self._begin(prompt, height, width, guidance_scale, negative_prompt,
                                                       num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
                                                       guidance_rescale, timesteps, sigmas)
@@ -484,6 +626,11 @@ class _VariantBase(StableDiffusionModel):
             x0_preds.append(step[1][0:1])
         return step[0]
 
+    def _refuse_image(self, kwargs):
+        if kwargs.get("image") is not None:
+            raise NotImplementedError(f"image= (image-to-image) is not built for {type(self).__name__}; "
+                                      "StableDiffusionModel runs it")
+
     @staticmethod
     def _combined(eps, do_cfg, guidance_scale, sched=None):
         """The noise prediction the step saw: CFG combine, scaled by the rescale factors ``sched``'s last step computed
@@ -529,6 +676,7 @@ class StableDiffusionModelTwoSchedulers(_VariantBase):
              num_images_per_prompt: int = 1, eta: float = 0.0, generator=None, latents=None, prompt_embeds=None,
              negative_prompt_embeds=None, output_type: str = "pil", return_dict: bool = True,
              guidance_rescale: float = 0.0, **kwargs):
+        self._refuse_image(kwargs)
         if self.scheduler_first is None or self.scheduler_second is None:
             raise ValueError("scheduler_first / scheduler_second must be set (two_schedulers.py:44-62)")
         device, batch_size, do_cfg, ctx = self._begin(prompt, height, width, guidance_scale, negative_prompt,
@@ -585,6 +733,7 @@ class StableDiffusionModelInterlivingSchedulers(_VariantBase):
              num_images_per_prompt: int = 1, eta: float = 0.0, generator=None, latents=None, prompt_embeds=None,
              negative_prompt_embeds=None, output_type: str = "pil", return_dict: bool = True,
              guidance_rescale: float = 0.0, **kwargs):
+        self._refuse_image(kwargs)
         if self.scheduler_main is None or self.scheduler_inter is None:
             raise ValueError("scheduler_main / scheduler_inter must be set (interliving_exp.py:41-62)")
         interliving_steps = list(interliving_steps or [])
@@ -632,6 +781,7 @@ class StableDiffusionModelSkipTimesteps(_VariantBase):
              num_images_per_prompt: int = 1, eta: float = 0.0, generator=None, latents=None, prompt_embeds=None,
              negative_prompt_embeds=None, output_type: str = "pil", return_dict: bool = True,
              guidance_rescale: float = 0.0, **kwargs):
+        self._refuse_image(kwargs)
         skip = set(int(i) for i in (skip_timesteps or []))
         device, batch_size, do_cfg, ctx = self._begin(prompt, height, width, guidance_scale, negative_prompt,
                                                       num_images_per_prompt, prompt_embeds, negative_prompt_embeds,

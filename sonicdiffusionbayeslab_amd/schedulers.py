@@ -212,6 +212,26 @@ class _FusedStepScheduler:
 
     rescale_factors: Optional[torch.Tensor] = None
 
+    # --- forward process (image-to-image start; diffusers' ``add_noise``, upstream-recall) -----------------------------
+    def _add_noise_coefs(self, timestep):
+        """(sqrt(alpha_bar_t), sqrt(1 - alpha_bar_t)) from the fp32 table, as DDIM / LCM upstream."""
+        a = float(self.alphas_cumprod[int(timestep)])
+        return math.sqrt(a), math.sqrt(1.0 - a)
+
+    def add_noise(self, original_samples, noise, timestep):
+        """``sqrt(alpha_bar_t) * x0 + sqrt(1 - alpha_bar_t) * noise`` at one scalar ``timestep`` of the schedule, as ONE
+        ``sd_sched_step`` launch (coef[0] on the sample, coef[4] on the noise operand; the prediction operand has
+        coefficient 0).  Does not touch the multistep state."""
+        if self.num_inference_steps is None:
+            raise ValueError("run set_timesteps first")
+        alpha, sigma = self._add_noise_coefs(timestep)
+        x = self._prep(original_samples)
+        z = self._prep(noise.to(x.device))
+        if z.shape != x.shape:
+            raise ValueError(f"add_noise: noise {tuple(z.shape)} does not match the samples {tuple(x.shape)}")
+        noisy, _, _ = self._launch(x, False, 0.0, x, None, None, z, (alpha, 0, 0, 0, sigma, 0, 0, 0, 0), want_y2=False)
+        return noisy
+
     def step(self, model_output, timestep, sample, eta: float = 0.0, generator=None, variance_noise=None,
              return_dict: bool = False, **kwargs):
         """Drop-in ``scheduler.step`` (CFG already combined by the caller, src/models.py:253)."""
@@ -358,6 +378,13 @@ class DPMSolverScheduler(_FusedStepScheduler):
         sh = sigma * alpha
         lam = math.log(alpha) - math.log(sh) if sh > 0 else math.inf
         return alpha, sh, lam
+
+    def _add_noise_coefs(self, timestep):
+        """alpha_t, sigma_t of the scheduler's OWN sigma table at the index the loop begins at (upstream's
+        DPMSolverMultistepScheduler.add_noise with begin_index set; the table is interpolated, so this is not
+        sqrt(alpha_bar) of the fp32 table bit for bit)."""
+        alpha, sigma, _ = self._alpha_sigma_lambda(float(self.sigmas[self._index_of(timestep)]))
+        return alpha, sigma
 
     def _convert_coefs(self, i: int):
         a0, s0, _ = self._alpha_sigma_lambda(float(self.sigmas[i]))
@@ -615,6 +642,10 @@ class PNDMScheduler(_FusedStepScheduler):
             self.cur_sample = None
         self.counter += 1
         return (prev,)
+
+    def add_noise(self, original_samples, noise, timestep):
+        raise NotImplementedError("PNDMScheduler: starting part-way down the schedule (image-to-image) is not built -- its "
+                                  "second timestep is duplicated, and slicing the list changes what the PLMS warm-up means")
 
     def step(self, model_output, timestep, sample, return_dict: bool = False, **kwargs):
         out_dtype = model_output.dtype

@@ -1,10 +1,15 @@
-"""``AutoencoderKL`` decoder on libsdhip -- SURVEY.md §8f "next" row 1.
+"""``AutoencoderKL`` decoder and encoder on libsdhip -- SURVEY.md §8f "next" row 1.
 
 Replaces ``self.vae.decode(latents / self.vae.config.scaling_factor)`` of the reference pipeline
 (``src/models.py:287-302``): 2.5 TFLOP per 512x512 image, outside the reference's timed loop but what
 turns latents into the ``[B,3,512,512]`` tensor the harness consumes (``output_type="pt"``).  Same
 kernels as the UNet (implicit-GEMM conv with fused upsample, GroupNorm+SiLU, GEMM) plus a row softmax
 for the single 512-wide attention head of the mid block.  No CPU fallback.
+
+``HipVaeEncoder`` is ``AutoencoderKL.encode`` of diffusers 0.32.1 (upstream-recall, like the decoder): what
+``StableDiffusionImg2ImgPipeline.prepare_latents`` runs on the input picture.  Entry conv (fp32 image in, ``2x - 1`` in the
+load), the stride-2 downsamplers padded right / bottom only, and the exit (conv_out + quant_conv + the posterior sample) are
+kernels of their own; the resnets and the mid attention run on the decoder's ops.
 """
 from __future__ import annotations
 
@@ -66,11 +71,46 @@ def vae_param_shapes(cfg: VaeConfig) -> List[Tuple[str, Tuple[int, ...]]]:
     return out
 
 
-def make_synthetic_vae_state_dict(cfg: VaeConfig, seed: int = 4321) -> Dict[str, torch.Tensor]:
-    """Seeded SD-1.5-shaped decoder weights on the bf16 grid (no VAE weights exist offline)."""
-    g = torch.Generator().manual_seed(seed)
+def vae_encoder_param_shapes(cfg: VaeConfig) -> List[Tuple[str, Tuple[int, ...]]]:
+    """``encoder.*`` and ``quant_conv.*`` of diffusers' AutoencoderKL state dict, in module order."""
+    out: List[Tuple[str, Tuple[int, ...]]] = []
+    add = lambda n, s: out.append((n, tuple(s)))
+    nl = len(cfg.block_out_channels)
+    top, c0, zc = cfg.block_out_channels[-1], cfg.block_out_channels[0], 2 * cfg.in_channels
+
+    def resnet(p, cin, cout):
+        add(p + "norm1.weight", (cin,)); add(p + "norm1.bias", (cin,))
+        add(p + "conv1.weight", (cout, cin, 3, 3)); add(p + "conv1.bias", (cout,))
+        add(p + "norm2.weight", (cout,)); add(p + "norm2.bias", (cout,))
+        add(p + "conv2.weight", (cout, cout, 3, 3)); add(p + "conv2.bias", (cout,))
+        if cin != cout:
+            add(p + "conv_shortcut.weight", (cout, cin, 1, 1)); add(p + "conv_shortcut.bias", (cout,))
+
+    add("encoder.conv_in.weight", (c0, cfg.out_channels, 3, 3)); add("encoder.conv_in.bias", (c0,))
+    ch = c0
+    for i in range(nl):
+        co = cfg.block_out_channels[i]
+        for j in range(cfg.layers_per_block):
+            resnet(f"encoder.down_blocks.{i}.resnets.{j}.", ch, co)
+            ch = co
+        if i < nl - 1:
+            add(f"encoder.down_blocks.{i}.downsamplers.0.conv.weight", (co, co, 3, 3))
+            add(f"encoder.down_blocks.{i}.downsamplers.0.conv.bias", (co,))
+    resnet("encoder.mid_block.resnets.0.", top, top)
+    a = "encoder.mid_block.attentions.0."
+    add(a + "group_norm.weight", (top,)); add(a + "group_norm.bias", (top,))
+    for n in ("to_q", "to_k", "to_v", "to_out.0"):
+        add(a + n + ".weight", (top, top)); add(a + n + ".bias", (top,))
+    resnet("encoder.mid_block.resnets.1.", top, top)
+    add("encoder.conv_norm_out.weight", (top,)); add("encoder.conv_norm_out.bias", (top,))
+    add("encoder.conv_out.weight", (zc, top, 3, 3)); add("encoder.conv_out.bias", (zc,))
+    add("quant_conv.weight", (zc, zc, 1, 1)); add("quant_conv.bias", (zc,))
+    return out
+
+
+def _draw_synthetic(shapes, g) -> Dict[str, torch.Tensor]:
     sd = {}
-    for name, shape in vae_param_shapes(cfg):
+    for name, shape in shapes:
         leaf = name.rsplit(".", 2)[-2]
         is_norm = "norm" in leaf
         if name.endswith(".bias"):
@@ -80,6 +120,25 @@ def make_synthetic_vae_state_dict(cfg: VaeConfig, seed: int = 4321) -> Dict[str,
         else:
             t = torch.randn(shape, generator=g) / math.sqrt(math.prod(shape[1:]))
         sd[name] = t.to(torch.bfloat16).float()
+    return sd
+
+
+# The synthetic encoder's posterior: with the initialisation above the logvar half of the moments comes out around
+# +0.2 +- 0.6 while the mean half has std ~0.47, i.e. an encoded image would be mostly posterior noise.  A trained VAE's
+# posterior is narrow (SD-1.5: logvar around -17 .. -8), so the stand-in fixes the logvar biases of quant_conv at this
+# constant: std = exp(0.5 * (-8 + 0.2)) ~ 0.02 next to a mean of std ~0.47.
+SYNTHETIC_LOGVAR_BIAS = -8.0
+_ENCODER_SEED_OFFSET = 7919          # the encoder tensors come from a generator of their own: seed + this
+
+
+def make_synthetic_vae_state_dict(cfg: VaeConfig, seed: int = 4321) -> Dict[str, torch.Tensor]:
+    """Seeded SD-1.5-shaped VAE weights on the bf16 grid (no VAE weights exist offline).  The decoder tensors are drawn
+    first, from ``Generator(seed)`` alone; the encoder tensors from ``Generator(seed + 7919)``, so adding them moved no
+    decoder value.  ``quant_conv.bias[latent channels:]`` (the logvar half) is ``SYNTHETIC_LOGVAR_BIAS``."""
+    sd = _draw_synthetic(vae_param_shapes(cfg), torch.Generator().manual_seed(seed))
+    enc = _draw_synthetic(vae_encoder_param_shapes(cfg), torch.Generator().manual_seed(seed + _ENCODER_SEED_OFFSET))
+    enc["quant_conv.bias"][cfg.in_channels:] = SYNTHETIC_LOGVAR_BIAS
+    sd.update(enc)
     return sd
 
 
@@ -169,3 +228,84 @@ class HipVaeDecoder:
         return out
 
     __call__ = decode
+
+
+def _load_params(lib, handle, shapes, state_dict, what: str):
+    for name, shape in shapes:
+        if name not in state_dict:
+            raise KeyError(f"state_dict lacks VAE parameter {name!r}")
+        t = state_dict[name].detach().to("cpu", torch.float32).contiguous()
+        if t.dim() == 4 and len(shape) == 2:       # legacy attention weights stored as 1x1 convs
+            t = t.reshape(shape)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+        _lib.check(lib.sd_unet_load_param(handle, name.encode(), t.data_ptr(), t.numel()), f"load_param({name})")
+    _lib.check(lib.sd_unet_finalize(handle), f"finalize({what})")
+
+
+class HipVaeEncoder:
+    """``vae.encode`` replacement: ``encode(images) -> moments [B, 8, H/8, W/8]`` (``[mean | logvar]``, fp32, on the GPU) and
+    ``sample(moments)`` = ``DiagonalGaussianDistribution.sample() / .mode()`` times the scaling factor."""
+
+    def __init__(self, config: VaeConfig, state_dict: Dict[str, torch.Tensor], device: str = "cuda:0"):
+        if not torch.cuda.is_available():
+            raise _lib.SdHipError("HipVaeEncoder needs an MI355X (no CPU fallback exists)")
+        self.config = config
+        self.device = torch.device(device)
+        self._lib = _lib.load()
+        self._handle = C.c_void_p()
+        torch.cuda.set_device(self.device)
+        _lib.check(self._lib.sd_vae_encoder_create(C.byref(_c_config(config)), C.byref(self._handle)), "sd_vae_encoder_create")
+        _load_params(self._lib, self._handle, vae_encoder_param_shapes(config), state_dict, "vae encoder")
+        self._ws: Optional[torch.Tensor] = None
+        self._ws_key = None
+
+    __del__ = HipVaeDecoder.__del__
+    _workspace = HipVaeDecoder._workspace
+
+    def encode(self, images: torch.Tensor, chunk: int = 8) -> torch.Tensor:
+        """``images`` [B, 3, H, W] in [0, 1] (the ``2x - 1`` of diffusers' VaeImageProcessor happens in the entry kernel) ->
+        moments [B, 8, H/8, W/8].  H and W: multiples of 64 in [64, 1024] (latent sides that are multiples of 8 in [8, 128]).
+        Large batches are encoded ``chunk`` images at a time."""
+        img = images.to(self.device, torch.float32).contiguous()
+        if img.dim() != 4 or img.shape[1] != self.config.out_channels:
+            raise ValueError(f"images must be [B,{self.config.out_channels},H,W], got {tuple(img.shape)}")
+        b, _, hh, ww = img.shape
+        if hh % 64 or ww % 64 or not (64 <= hh <= 1024 and 64 <= ww <= 1024):
+            raise ValueError(f"images {hh}x{ww}: the VAE encoder takes sides that are multiples of 64 in [64, 1024]")
+        h, w = hh // 8, ww // 8
+        out = torch.empty((b, 2 * self.config.in_channels, h, w), dtype=torch.float32, device=self.device)
+        for s in range(0, b, chunk):
+            n = min(chunk, b - s)
+            ws = self._workspace(n, h, w)
+            wsp = (ws.data_ptr() + 255) // 256 * 256
+            _lib.check(self._lib.sd_vae_encode_hw(self._handle, _lib.current_stream(), img[s:s + n].data_ptr(), n, h, w,
+                                                  out[s:s + n].data_ptr(), wsp, ws.numel() - 256), "sd_vae_encode_hw")
+        return out
+
+    def sample(self, moments: torch.Tensor, noise: Optional[torch.Tensor] = None, mode: str = "sample",
+               scale: Optional[float] = None, generator=None) -> torch.Tensor:
+        """``scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise)`` for ``mode="sample"`` (``noise`` drawn from
+        ``generator`` on the host when not given), ``scale * mean`` for ``mode="argmax"``; ``scale`` defaults to the
+        config's ``scaling_factor``.  One elementwise launch."""
+        if mode not in ("sample", "argmax"):
+            raise ValueError(f"mode={mode!r}: 'sample' or 'argmax'")
+        m = moments.to(self.device, torch.float32).contiguous()
+        zc = self.config.in_channels
+        if m.dim() != 4 or m.shape[1] != 2 * zc:
+            raise ValueError(f"moments must be [B,{2 * zc},h,w], got {tuple(m.shape)}")
+        b, _, h, w = m.shape
+        z = None
+        if mode == "sample":
+            if noise is None:
+                noise = torch.randn((b, zc, h, w), generator=generator, dtype=torch.float32)
+            if tuple(noise.shape) != (b, zc, h, w):
+                raise ValueError(f"noise must be {(b, zc, h, w)}, got {tuple(noise.shape)}")
+            z = noise.to(self.device, torch.float32).contiguous()
+        out = torch.empty((b, zc, h, w), dtype=torch.float32, device=self.device)
+        sc = self.config.scaling_factor if scale is None else float(scale)
+        _lib.check(self._lib.sd_vae_posterior_sample(_lib.current_stream(), m.data_ptr(), _lib.ptr(z), float(sc),
+                                                     out.data_ptr(), b, h * w), "sd_vae_posterior_sample")
+        return out
+
+    __call__ = encode
