@@ -242,6 +242,45 @@ int sd_clip_score(void* stream, const float* image_embeds, const float* text_emb
  * writes xmin[count], xcnt[count] and coeffs[count][ksize]. */
 int sd_clip_resize_taps(int in_size, int out_size, int first, int count, int* xmin, int* xcnt, int* coeffs);
 
+/* ---- FID (reference src/metrics/metrics.py:98-112: torchmetrics FrechetInceptionDistance over torch-fidelity's
+ * FeatureExtractorInceptionV3, "pt_inception-2015-12-05") ----
+ * The handle owns the 94 conv blocks of the FID Inception-v3 with BatchNorm (eps 1e-3, running statistics) folded into
+ * weight and bias by the caller: sd_inception_conv_info enumerates them in forward order (name = the module's state-dict
+ * prefix, e.g. "Mixed_6c.branch7x7dbl_3"; shape = [Cout, Cin, kh, kw]), sd_inception_load_conv takes the folded fp32 OIHW
+ * weight and the folded bias from the HOST, sd_inception_finalize uploads them (bf16 OHWI weights, fp32 biases).
+ * sd_inception_features: uint8 images [batch, 3, height, width] (any size) -> TensorFlow-1 legacy bilinear resize to 299 x 299
+ * (src = dst * in / out, no half-pixel offset; lerp along x, then y) -> (x - 128) / 128 -> the network as deep as `tap` needs
+ * -> fp32 features [batch, tap], the global spatial mean of: 64 = first max pool, 192 = second max pool, 768 = Mixed_6e,
+ * 2048 = Mixed_7c.  Activations are bf16 NHWC; every conv runs on one implicit-GEMM MFMA kernel whose epilogue writes the
+ * branch's channel slice of the block output.  The workspace (256-byte aligned) depends on (batch, tap) only.
+ * sd_fid_accumulate: sum[dim] += sum_b f_b, cov_sum[dim][dim] += sum_b f_b f_b^T, count += batch, all fp64 / int64 on the
+ * device, in one launch -- the state torchmetrics keeps (features.double()). */
+typedef struct sd_inception sd_inception;
+int sd_inception_create(sd_inception** out);
+void sd_inception_destroy(sd_inception* h);
+int sd_inception_num_convs(const sd_inception* h);
+int sd_inception_conv_info(const sd_inception* h, int index, char* name, int name_cap, long long shape[4]);
+int sd_inception_load_conv(sd_inception* h, const char* name, const float* weight_oihw, long long weight_numel,
+                           const float* bias, int cout);
+int sd_inception_finalize(sd_inception* h);
+long long sd_inception_workspace_bytes(sd_inception* h, int batch, int tap);
+int sd_inception_features(sd_inception* h, void* stream, const unsigned char* images, int batch, int height, int width,
+                          int tap, float* features, void* workspace, long long workspace_bytes);
+int sd_fid_accumulate(void* stream, const float* features, int batch, int dim, double* sum, double* cov_sum,
+                      long long* count);
+/* operator level: Y[.., coff : coff + Cout] of rows of ldy channels = relu?(conv(X NHWC bf16, W bf16 [Cout][kh][kw][Cin],
+ * stride, padding (pad_h, pad_w)) + bias); any Cin / Cout (no padding of tensors asked of the caller) */
+int sd_op_inception_conv(void* stream, const void* X, const void* W, const float* bias, void* Y, int B, int Hin, int Win,
+                         int Cin, int Cout, int kh, int kw, int stride, int pad_h, int pad_w, int ldy, int coff, int relu);
+/* 3x3 pools on NHWC bf16 into a channel slice: max with (stride, pad) = (2, 0) or (1, 1), padding never wins; average with
+ * stride 1, pad 1 dividing by the number of in-bounds taps (count_include_pad=False) */
+int sd_op_maxpool3x3(void* stream, const void* X, void* Y, int B, int H, int W, int C, int stride, int pad, int ldy, int coff);
+int sd_op_avgpool3x3(void* stream, const void* X, void* Y, int B, int H, int W, int C, int ldy, int coff);
+/* out fp32 [B][C] = mean over the HW pixels of X bf16 [B][HW][C] */
+int sd_op_global_mean(void* stream, const void* X, float* out, int B, int HW, int C);
+/* the preprocessing of sd_inception_features alone: uint8 [B][3][H][W] -> [B][299][299][3], bf16 or (out_fp32) fp32 */
+int sd_op_inception_resize(void* stream, const unsigned char* images, int B, int H, int W, void* out, int out_fp32);
+
 /* Measurement hook for bench.py: the same forward with a hipEvent pair around every launch.  Per
  * op kind (0 sinusoid, 1 gemv, 2 conv_in, 3 groupnorm, 4 conv3x3, 5 gemm, 6 layernorm,
  * 7 attention, 8 conv_out; 16 conv3x3 with fp8 operands, 17 gemm with fp8 operands, 18 fused prompt cross-attention)

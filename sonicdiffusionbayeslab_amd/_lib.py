@@ -105,6 +105,20 @@ _SIGS = {
     "sd_clip_resize_taps": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
     "sd_op_vit_attention": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
     "sd_op_clip_preprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sd_inception_create": (_i, [C.POINTER(_vp)]),
+    "sd_inception_destroy": (None, [_vp]),
+    "sd_inception_num_convs": (_i, [_vp]),
+    "sd_inception_conv_info": (_i, [_vp, _i, C.c_char_p, _i, C.POINTER(_ll)]),
+    "sd_inception_load_conv": (_i, [_vp, C.c_char_p, _vp, _ll, _vp, _i]),
+    "sd_inception_finalize": (_i, [_vp]),
+    "sd_inception_workspace_bytes": (_ll, [_vp, _i, _i]),
+    "sd_inception_features": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _ll]),
+    "sd_fid_accumulate": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "sd_op_inception_conv": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "sd_op_maxpool3x3": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "sd_op_avgpool3x3": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+    "sd_op_global_mean": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "sd_op_inception_resize": (_i, [_vp, _vp, _i, _i, _i, _vp, _i]),
     "sd_unet_debug_tensor": (_i, [_vp, _vp, C.c_char_p, _vp, _ll, _vp, _i, _i]),
     "sd_sched_step": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _ll]),
     "sd_cfg_rescale_factors": (_i, [_vp, _vp, _i, _ll, _f, _f, _vp]),

@@ -262,3 +262,12 @@ int sd_launch_cfg_rescale_factors(const float* eps, int batch, long n_per_sample
 int sd_launch_sched_step_rescaled(const float* eps, int cfg, float guidance, const float* x, const float* m1,
                                   const float* m2, const float* m3, const float* noise, float* prev, float* y2,
                                   float* m_out, StepCoef c, const float* k, long n_per_sample, long n, hipStream_t stream);
+
+// inception.hip: FID Inception-v3 pieces (general implicit-GEMM conv, 3x3 pools, global mean, TF1 bilinear preprocessing)
+int sd_launch_inception_conv(const bf16_t* x, const bf16_t* w, const float* bias, bf16_t* y, int B, int Hin, int Win, int Cin,
+                             int Cout, int kh, int kw, int stride, int ph, int pw, int ldy, int coff, int relu,
+                             hipStream_t stream);
+int sd_launch_inception_pool(const bf16_t* x, bf16_t* y, int B, int H, int W, int C, int stride, int pad, int avg, int ldy,
+                             int coff, hipStream_t stream);
+int sd_launch_inception_mean(const bf16_t* x, float* out, int B, int HW, int C, hipStream_t stream);
+int sd_launch_inception_resize(const unsigned char* img, void* out, int B, int H, int W, int S, int out_fp32, hipStream_t stream);

@@ -100,7 +100,9 @@ class BaseMethod(ABC):
     def setup_metrics(self):
         """``src/experiments/base_experiment.py:93-113``.  ``time_metric`` always; ``clip_score`` (``:96-98``) when
         ``quality_metrics.clip_score.model_name_or_path`` is a LOCAL checkpoint directory -- a hub name is a network
-        fetch and the metric is then reported as not computable.  FID / ImageReward are not built."""
+        fetch and the metric is then reported as not computable.  ``fid`` (``:105-109``) when the key of this
+        build ``quality_metrics.fid.weights`` names a LOCAL Inception checkpoint file (beside the reference's ``feature`` /
+        ``input_img_size`` / ``normalize``).  ImageReward is not built."""
         self.metric_dict = defaultdict(list)
         self.time_metric = metrics_registry["time_metric"]()
         self.clip_score_gen_metric = None
@@ -115,6 +117,16 @@ class BaseMethod(ABC):
             self.clip_score_gen_metric = metrics_registry["clip_score"](model_name_or_path=str(path), **kw)
         self.clip_score_source = str(path) if self.clip_score_gen_metric is not None else (
             f"not computable offline ({path!r} is not a local directory)" if path else "not configured")
+        self.fid_metric = None
+        fq = qm.get("fid", None) if qm else None
+        fw = fq.get("weights", None) if fq else None
+        if fw and os.path.isfile(str(fw)):
+            kw = {"device": self.device} if str(self.device).startswith("cuda") else {}
+            self.fid_metric = metrics_registry["fid"](feature=int(fq.get("feature", 2048)),
+                                                      input_img_size=fq.get("input_img_size", None),
+                                                      normalize=bool(fq.get("normalize", False)), weights=str(fw), **kw)
+        self.fid_source = str(fw) if self.fid_metric is not None else (
+            f"not computable offline ({fw!r} is not a local file)" if fw else "not configured")
 
     def setup_loggers(self):
         self.logger = None
@@ -129,11 +141,13 @@ class BaseMethod(ABC):
         out_type = self.config.inference.get("output_type", "pt")        # the reference hard-codes "pt" (:145)
         images, x0_preds = [], []
         self.last_prompts = []                                           # prompt of every returned image, in order
+        self.last_image_files = []                                       # and its file under dataset.img_dataset
         for idx, batch in enumerate(test_dataloader):
             if limit is not None and idx >= limit:
                 break
             prompts = list(batch["prompt"])
             self.last_prompts.extend(prompts)
+            self.last_image_files.extend(batch.get("image_file", []))
             sharded = sdist.active()
             lo, hi = sdist.shard_range(len(prompts), self.rank, self.world) if sharded else (0, len(prompts))
             local_prompts = prompts[lo:hi]
@@ -185,7 +199,7 @@ class BaseMethod(ABC):
             self.model.to("cpu")
             self.validate(f"{self.config.experiment_name}, {label(point)}",
                           additional_values=extra(point) if extra else None, n_images=len(images),
-                          images=images, prompts=self.last_prompts)
+                          images=images, prompts=self.last_prompts, image_files=getattr(self, "last_image_files", None))
 
     def clip_score(self, images, prompts, batch_size: int = 32):
         """``validate`` of the reference for the parity metric (``:198-201``): generated images -> uint8 by
@@ -200,15 +214,37 @@ class BaseMethod(ABC):
             m.update(gen, prompts[s:s + batch_size])
         return float(m.compute())
 
-    def validate(self, name_images, additional_values=None, n_images=0, images=None, prompts=None):
+    def fid(self, images, image_files, batch_size: int = 32):
+        """``validate`` of the reference for FID (``:198-206``): per batch the generated images
+        (``(img * 255).to(uint8)``, ``real=False``) and the dataset's images of the same files (``load_images``,
+        ``real=True``).  None when no local Inception checkpoint was configured, the run produced latents, or a file of the
+        batch is not under ``dataset.img_dataset``."""
+        m = self.fid_metric
+        if m is None or not images or images[0].dim() != 3 or images[0].shape[0] != 3:
+            return None
+        root = str(self.config.dataset.img_dataset)
+        if not image_files or len(image_files) != len(images) or not all(os.path.isfile(os.path.join(root, f)) for f in image_files):
+            self.fid_source = f"not computable: the batch's image files are not under dataset.img_dataset = {root!r}"
+            return None
+        m.reset()
+        for s in range(0, len(images), batch_size):
+            m.update((torch.stack(images[s:s + batch_size]) * 255).to(torch.uint8), real=False)
+            m.update((self.load_images(image_files[s:s + batch_size]) * 255).to(torch.uint8), real=True)
+        return float(m.compute())
+
+    def validate(self, name_images, additional_values=None, n_images=0, images=None, prompts=None, image_files=None):
         """The hot-path metric, seconds / image over the loop (``time_metric``), and -- with a local CLIP checkpoint and
-        decoded images -- the reference's parity metric ``clip_score``."""
+        decoded images -- the reference's parity metric ``clip_score``; with a local Inception checkpoint and the batch's
+        dataset images, ``fid``."""
         if additional_values:
             for k, v in additional_values.items():
                 self.metric_dict[k].append(v)
         cs = self.clip_score(images, prompts) if (images is not None and self.rank == 0) else None
         if cs is not None:
             self.metric_dict["clip_score"].append(cs)
+        fid = self.fid(images, image_files) if (images is not None and self.rank == 0) else None
+        if fid is not None:
+            self.metric_dict["fid"].append(fid)
         t = float(self.time_metric.compute())
         self.metric_dict["nfe"].append(self.model.num_timesteps)
         self.metric_dict["time_metric"].append(t)
@@ -219,7 +255,8 @@ class BaseMethod(ABC):
                           "images": n_images, "time_metric_s_per_image": t,
                           "images_per_s": (1.0 / t if t > 0 else None), "weights": self.model.weights_source,
                           "clip_score": cs, "clip_score_model": self.clip_score_source, "n_gpus": self.world,
-                          "fp8_activation_scales": self._fp8_scale_report()}), flush=True)
+                          "fp8_activation_scales": self._fp8_scale_report(),
+                          "fid": fid, "fid_weights": self.fid_source}), flush=True)
 
     def _fp8_scale_report(self):
         """The e4m3 activation scales the run used (fp8 handles; None otherwise): count, range and a digest, so that two

@@ -4,7 +4,8 @@
 needs CLIP ViT-B/16 weights that only exist as a network fetch, so it is registered but raises
 unless a LOCAL checkpoint directory is given.  ``BaseMethod.setup_metrics`` builds it when
 ``quality_metrics.clip_score.model_name_or_path`` is such a directory and ``validate`` then reports it
-(``src/experiments/base_experiment.py:96-98,198-201``)."""
+(``src/experiments/base_experiment.py:96-98,198-201``).  ``fid`` (``:98-112``) runs the FID Inception-v3 on libsdhip from a
+LOCAL checkpoint file (``quality_metrics.fid.weights``); there is no host network behind it."""
 from __future__ import annotations
 
 import os
@@ -84,3 +85,94 @@ class ClipScoreMetric:
 
     def reset(self):
         self.score, self.n = 0.0, 0
+
+
+@metrics_registry.add_to_registry("fid")
+class FID:
+    """torchmetrics' ``FrechetInceptionDistance`` surface (the reference's ``FID``, ``src/metrics/metrics.py:98-112``) on
+    libsdhip: Inception features on the GPU (``fid.HipInceptionFeatures``), the fp64 sum / outer-product sum / count per
+    side on the GPU (``sd_fid_accumulate``), the Frechet distance on the host in fp64."""
+
+    def __init__(self, feature: int = 2048, input_img_size=None, normalize: bool = False, reset_real_features: bool = True,
+                 weights=None, device=None):
+        """``weights``: a LOCAL ``.pth`` / ``.safetensors`` state dict of the FID Inception-v3 (pt_inception-2015-12-05).
+        ``input_img_size`` is accepted and ignored (upstream sizes a dummy input with it).  The network is built at the first
+        ``update``, so a process that never scores puts no weights on a GPU."""
+        from .fid import check_feature
+        self.feature = check_feature(feature)
+        if not isinstance(normalize, bool):
+            raise ValueError("Argument `normalize` expected to be a bool")
+        if not isinstance(reset_real_features, bool):
+            raise ValueError("Argument `reset_real_features` expected to be a bool")
+        if weights is None or not os.path.isfile(str(weights)):
+            raise FileNotFoundError(
+                f"FID Inception weights {weights!r} are a network fetch and unavailable offline; "
+                "pass a local checkpoint file to compute FID")
+        self.weights, self.device = str(weights), device
+        self.normalize, self.reset_real_features = normalize, reset_real_features
+        self.feature_fn = None              # images uint8 [B,3,H,W] -> features [B, feature]; built at the first update
+        self._state = {}
+        self.reset(_all=True)
+
+    def _side(self, real: bool, like: torch.Tensor):
+        key = "real" if real else "fake"
+        if self._state.get(key) is None:
+            d = self.feature
+            self._state[key] = (torch.zeros(d, dtype=torch.float64, device=like.device),
+                                torch.zeros(d, d, dtype=torch.float64, device=like.device),
+                                torch.zeros(1, dtype=torch.int64, device=like.device))
+        return self._state[key]
+
+    @torch.no_grad()
+    def update(self, imgs: torch.Tensor, real: bool) -> None:
+        if imgs.dim() == 3:
+            imgs = imgs.unsqueeze(0)
+        if self.normalize:
+            if not imgs.is_floating_point():
+                raise ValueError("normalize=True expects float images in [0, 1]")
+            imgs = (imgs * 255).byte()
+        if imgs.dtype != torch.uint8:
+            raise ValueError(f"FID expects uint8 images (or float in [0, 1] with normalize=True), got {imgs.dtype}")
+        if self.feature_fn is None:
+            from .fid import HipInceptionFeatures
+            net = HipInceptionFeatures.from_file(self.weights, device=self.device)
+            self.feature_fn = lambda x: net.features(x, self.feature)
+        f = self.feature_fn(imgs)
+        total, cov, n = self._side(real, f)
+        if f.is_cuda:
+            from .fid import fid_accumulate
+            fid_accumulate(f, total, cov, n)
+        else:                               # features handed in on the host (a test's stand-in feature function)
+            fd = f.double()
+            total += fd.sum(0)
+            cov += fd.t() @ fd
+            n += fd.shape[0]
+
+    def compute(self) -> torch.Tensor:
+        from .fid import frechet_distance
+        stats = []
+        for key in ("real", "fake"):
+            st = self._state.get(key)
+            n = int(st[2].item()) if st is not None else 0
+            if n < 2:
+                raise RuntimeError("More than one sample is required for both the real and fake distributed to compute FID")
+            total, cov = st[0].cpu(), st[1].cpu()
+            mean = total / n
+            stats.append((mean, (cov - n * torch.outer(mean, mean)) / (n - 1)))
+        (mu_r, s_r), (mu_f, s_f) = stats
+        return frechet_distance(mu_r, s_r, mu_f, s_f)
+
+    def reset(self, _all: bool = False) -> None:
+        """Forget the generated statistics, and the real ones unless ``reset_real_features=False``."""
+        self._state["fake"] = None
+        if _all or self.reset_real_features:
+            self._state["real"] = None
+
+    def calc_metric(self, imgs, reals) -> float:
+        """``src/metrics/metrics.py:100-112``: PIL images (or uint8 ``[3,H,W]`` tensors) with a real / generated flag each."""
+        import numpy as np
+        for img, real in zip(imgs, reals):
+            if not torch.is_tensor(img):
+                img = torch.from_numpy(np.asarray(img.convert("RGB"), dtype=np.uint8).copy()).permute(2, 0, 1).contiguous()
+            self.update(imgs=img, real=real)
+        return self.compute().item()
