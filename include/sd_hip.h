@@ -357,6 +357,19 @@ int sd_op_conv3x3(void* stream, const void* X, const void* W, const float* bias,
 /* Which kernel a 3x3 conv of this shape runs on: 0 = implicit GEMM, 1 = halo kernel (9 taps), 2 = halo kernel's 4-tap
  * mode.  M = output rows (B Hout Wout; for upsample = 2, the sub-pixel form, 4 B Hin Win); upsample 1 = fused nearest-2x;
  * dtype 0 = bf16, 1 = fp8 e4m3 (Cin padded to 128).  No device work. */
+/* A ResNet block's conv2 with its 1x1 conv_shortcut folded into the same launch (the halo kernel's shortcut phase):
+ *   Y = conv3x3(X, W) + [Xs1 | Xs2] Wsc^T + bias,   stride 1, pad 1, bf16.
+ * X = [B, H, W, Cin] and W as for sd_op_conv3x3; Xs1 = [B, H, W, Cs1], Xs2 = [B, H, W, Cs2] (NULL with Cs2 = 0): the
+ * shortcut's input as a virtual channel concat, Cs1 and Cs2 multiples of 64; Wsc = bf16 [Cout][Cs1 + Cs2]; bias = fp32
+ * [Cout], the SUM of the two convs' biases.  The 1x1 product is accumulated in fp32 on the conv's accumulators (no bf16
+ * rounding of the shortcut on its own).  Returns an error where the conv does not run on the halo kernel's 9-tap mode. */
+int sd_op_conv3x3_shortcut(void* stream, const void* X, const void* W, const float* bias, const void* Xs1, int Cs1,
+                           const void* Xs2, int Cs2, const void* Wsc, void* Y, int B, int H, int Wd, int Cin, int Cout);
+/* The same launch feeding GroupNorm(+SiLU) from its epilogue's block statistics, as sd_op_conv3x3_groupnorm does for the
+ * plain conv (H * W a multiple of 64, images the single-launch GroupNorm does not take): Y = conv output, Yn = normalised. */
+int sd_op_conv3x3_shortcut_groupnorm(void* stream, const void* X, const void* W, const float* bias, const void* Xs1, int Cs1,
+                                     const void* Xs2, int Cs2, const void* Wsc, void* Y, int B, int H, int Wd, int Cin,
+                                     int Cout, const float* gamma, const float* beta, void* Yn, int groups, float eps, int silu);
 /* The 3x3 stride-2 conv padded on the right and the bottom only: F.conv2d(F.pad(x, (0, 1, 0, 1)), w, b, stride = 2), the
  * AutoencoderKL encoder's downsampler.  W as for sd_op_conv3x3; Hin and Win even; Y = [B, Hin / 2, Win / 2, Cout]. */
 int sd_op_conv3x3_down_asym(void* stream, const void* X, const void* W, const float* bias, void* Y, int B, int Hin, int Win,

@@ -80,9 +80,21 @@ __device__ __forceinline__ int swz_of(int row, int dt) { return dt ? (((row >> 1
 // and they store nothing.  The sample / row / column come from divisions done once per item / per thread, not shifts.
 // Same K order and accumulation chains as the power-of-two mode; no GroupNorm block statistics (tiles are not 64-row
 // aligned).  GEN = 0 is the power-of-two kernel unchanged.
-template <int DT, int DIAG = 0, int NWV = 8, int SUB = 0, int GEN = 0>
+//
+// SC = 1 (round 6): the ResNet 1x1 shortcut folded into conv2 (GemmArgs::Xs1 ...).  Between an item's tap loop and its epilogue
+// the item's accumulators take  acc += Xs[256 rows x Csc] . Wsc[160 x Csc]^T  in a plain two-stage GEMM K loop over
+// 64-channel tiles of the shortcut source, the two-segment virtual concat [Xs1 | Xs2] of the GEMM path.  An X stage is the
+// item's BM consecutive output rows x 128 B (32 one-KiB pieces of 8 rows, four per wave, chunk swizzle on the source as in
+// gemm_lean.hip) in the first 32 KiB of a halo buffer -- both are free by then --, a W stage is 160 rows x 128 B of
+// Wsc[Cout][Csc] in the W ring.  Rows beyond M (GEN: beyond the item's last valid row) and channels beyond Cout are out of
+// the buffer ranges and read zeros.  Split j of splitk takes shortcut tiles [j nsc / splitk, (j + 1) nsc / splitk).  The
+// epilogue adds ONE bias vector (conv2.bias + conv_shortcut.bias, summed by the packer) and loads no residual.
+// The stages alternate so that the LAST tile is read from the halo buffer / W stage the next item's prologue does not
+// refill: as without the phase, that prologue needs no barrier of its own.
+template <int DT, int DIAG = 0, int NWV = 8, int SUB = 0, int GEN = 0, int SC = 0>
 __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(const GemmArgs p) {
     static_assert(NWV == 8 || (NWV == 4 && DT == 0), "4-wave layout: bf16 only");
+    static_assert(!SC || (DT == 0 && DIAG == 0 && NWV == 8 && SUB == 0), "shortcut phase: bf16, 8 waves, 9 taps");
     static_assert(!SUB || (DT == 0 && DIAG == 0 && NWV == 8), "sub-pixel upsampler: bf16, 8 waves");
     static_assert(!GEN || (SUB == 0 && DIAG == 0 && NWV == 8), "geometry mode: 9 taps, 8 waves");
     constexpr int NTAP = SUB ? 4 : 9;             // taps = K tiles per channel slice
@@ -289,6 +301,13 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
     const int wfrag = (wn * WTN + lrow) * 128;
     // bf16: k-step 0 reads chunk lq ^ (row & 7), k-step 1 = ^ 64; fp8: chunks 2 lq and 2 lq + 1 (= ^ 16), each ^ f(row)
     const int wswz0 = DT ? ((2 * lq) ^ swz_of(lane, 1)) << 4 : (lq ^ (lane & 7)) << 4;
+
+    // shortcut phase: LDS-DMA piece = 8 rows x 128 B, lane l fills chunk position l & 7 of row l >> 3 with source chunk
+    // (l & 7) ^ (l >> 3); the rest of a piece's address (tile origin, piece, K tile) is a scalar offset
+    const int sc_gch = ((lane & 7) ^ (lane >> 3)) << 4;
+    const int scp1 = SC ? p.Csc1 * 2 : 0, scp2 = SC ? p.Csc2 * 2 : 0, scpw = SC ? (int)p.ldwsc * 2 : 0;      // row pitches in bytes
+    const int vXs1 = (lane >> 3) * scp1 + sc_gch, vXs2 = (lane >> 3) * scp2 + sc_gch, vWs = (lane >> 3) * scpw + sc_gch;
+    const int scfrag = (wm * WTM + lrow) * 128 + ((lq ^ (lane & 7)) << 4);      // this lane's row of pixel tile 0 (+ 2048 f), k-step 0
 
     auto frag_addr = [&](int f, int tp) -> int {     // this lane's pixel of tile f at tap tp: halo slot -> byte offset
         const int hp = hbase[f] + (((hrc[f] >> 16) + (tp / 3 - 1)) >> up) * PW + (((hrc[f] & 0xffff) + (tp % 3 - 1)) >> up);
@@ -507,6 +526,65 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
         }
         if (CARRY) mfmas(xf1, wf1);               // the last tap's second k-step
 
+        if (SC) {
+            const int nsc = (p.Csc1 + p.Csc2) >> 6, nsc1 = p.Csc1 >> 6;
+            const int t_begin = (int)((long)nsc * split / p.splitk), t_end = (int)((long)nsc * (split + 1) / p.splitk);
+            if (t_begin < t_end) {
+                const unsigned rows = (unsigned)(GEN ? min(mend, p.M) : p.M);       // rows >= this read zeros
+                auto stage_sc = [&](int t, char* xb, char* wb) {
+                    const bool seg1 = t < nsc1;
+                    const int pitch = seg1 ? scp1 : scp2;
+                    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(seg1 ? p.Xs1 : p.Xs2), 0,
+                                                                                        (int)(rows * (unsigned)pitch), 0x00020000);
+                    const int vx = seg1 ? vXs1 : vXs2;
+                    const int so = (m0 + wave * 8) * pitch + (seg1 ? t : t - nsc1) * 128;
+#pragma unroll
+                    for (int i = 0; i < BM / 64; ++i)
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, LDS_PTR(xb + (wave + 8 * i) * 1024), 16, vx, so + i * 64 * pitch, 0, 0);
+                    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.Wsc, 0, (int)((unsigned)p.N * (unsigned)scpw), 0x00020000);
+#pragma unroll
+                    for (int i = 0; i < WPW; ++i) {
+                        const int pc = wpiece(i);
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, LDS_PTR(wb + pc * 1024), 16, vWs, (n0 + pc * 8) * scpw + t * 128, 0, 0);
+                    }
+                };
+                // counted from the END: the last tile sits in the halo buffer and the W stage the next item's prologue leaves alone
+                char* const xlast = hsel ? Hb0 : Hb1;
+                char* const xprev = hsel ? Hb1 : Hb0;
+                char* const wlast = Wb + (wst == 0 ? 2 : wst - 1) * WBYTES;
+                char* const wprev = Wb + wst * WBYTES;
+                // every wave is done with the last tap's W stage and halo, and the empty refills of the last taps have retired
+                wait_vmcnt<0>();
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                {
+                    const bool e0 = ((t_end - 1 - t_begin) & 1) == 0;
+                    stage_sc(t_begin, e0 ? xlast : xprev, e0 ? wlast : wprev);
+                }
+                for (int t = t_begin; t < t_end; ++t) {
+                    const bool e = ((t_end - 1 - t) & 1) == 0;
+                    const char* xcur = e ? xlast : xprev;
+                    const char* wcur = e ? wlast : wprev;
+                    wait_vmcnt<0>();
+                    __builtin_amdgcn_s_barrier();       // tile t has landed; every wave is done reading tile t - 1
+                    asm volatile("" ::: "memory");
+#pragma unroll
+                    for (int f = 0; f < TM; ++f) xf0[f] = *(const bf16x8*)(xcur + scfrag + f * 2048);
+#pragma unroll
+                    for (int a = 0; a < TN; ++a) wf0[a] = *(const bf16x8*)(wcur + wfrag + a * 2048 + wswz0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (t + 1 < t_end) stage_sc(t + 1, e ? xprev : xlast, e ? wprev : wlast);
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int f = 0; f < TM; ++f) xf1[f] = *(const bf16x8*)(xcur + ((scfrag + f * 2048) ^ 64));
+#pragma unroll
+                    for (int a = 0; a < TN; ++a) wf1[a] = *(const bf16x8*)(wcur + wfrag + a * 2048 + (wswz0 ^ 64));
+                    mfmas(xf0, wf0);
+                    mfmas(xf1, wf1);
+                }
+            }
+        }
+
         // ---- epilogue, phase A: every LOAD the epilogue needs, folded into the accumulators now so that
         // no ordinary load is outstanding once the next item's LDS-DMA is in flight ----------------------
         // (accumulator layout as gemm_kernel: a lane owns 4 consecutive channels of one pixel per 16x16 tile)
@@ -528,7 +606,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
             }
         }
         if (p.splitk == 1) {
-            if (p.R) {
+            if (SC == 0 && p.R) {
                 u32x2 rr[TN][TM];
 #pragma unroll
                 for (int a = 0; a < TN; ++a) {
@@ -552,7 +630,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : 1) void conv_halo_kernel(c
                 for (int a = 0; a < TN; ++a) {
                     const int n = min(en0 + wn * WTN + a * 16 + lq * 4, p.N - 4);
                     f32x4 bv = *(const f32x4*)(p.bias + n);
-                    if (p.bias2) bv += *(const f32x4*)(p.bias2 + n);
+                    if (SC == 0 && p.bias2) bv += *(const f32x4*)(p.bias2 + n);
 #pragma unroll
                     for (int b = 0; b < TM; ++b) acc[a][b] += bv;
                 }
@@ -702,6 +780,19 @@ static bool pow2_applicable(const GemmArgs& a) {
     return true;
 }
 
+// The 1x1 shortcut folded into the conv (conv_halo_kernel SC = 1): the halo kernel's 9-tap mode in bf16 -- either geometry --
+// without a residual or a second bias vector, shortcut segments of whole 64-channel K tiles, 32-bit byte offsets into the
+// shortcut operands (a tile's rows may run up to BM past M before the range check drops them).
+bool sd_conv_halo_shortcut_applicable(const GemmArgs& a) {
+    if (a.dt != 0 || a.subpix || a.up || a.stride != 1 || a.R != nullptr || a.bias2 != nullptr || a.tune != 0) return false;
+    if (!sd_conv_halo_applicable(a)) return false;
+    if (a.Csc1 < 64 || a.Csc1 % 64 || a.Csc2 < 0 || a.Csc2 % 64) return false;
+    const long ldw = a.ldwsc ? a.ldwsc : a.Csc1 + a.Csc2;
+    if (ldw < a.Csc1 + a.Csc2 || (ldw & 7)) return false;
+    const long big = 1l << 32;
+    return ((long)a.M + BM) * std::max(a.Csc1, a.Csc2) * 2 < big && ((long)a.N + BN) * ldw * 2 < big;
+}
+
 // The sub-pixel upsampler (GemmArgs::subpix: four 2x2 convs on the low-res input) on the halo kernel's 4-tap mode: the tile
 // grid is the LOW-RES image; only where (pixel tiles x 4 phases x channel tiles) fills the 256 CUs -- the 8x8 -> 16x16
 // upsampler (128 items at UNet batch 16) stays on the implicit-GEMM kernel's 64-row tiles.  SD_SUBPIX_HALO=0: never.
@@ -769,11 +860,18 @@ int sd_launch_conv3x3_halo(const GemmArgs& a0, hipStream_t stream) {
     }
     const int slices = a.Cin / (a.dt ? 128 : 64);
     SD_REQUIRE(a.splitk <= slices, "conv3x3 halo: splitk %d exceeds the %d channel slices", a.splitk, slices);
+    if (a.Wsc) {
+        SD_REQUIRE(a.Xs1 && (a.Xs2 || a.Csc2 == 0) && sd_conv_halo_shortcut_applicable(a0),
+                   "conv3x3 halo: the 1x1 shortcut (%d + %d channels) cannot ride on this conv", a.Csc1, a.Csc2);
+        if (a.ldwsc == 0) a.ldwsc = a.Csc1 + a.Csc2;
+        if (a.Csc2 == 0) a.Xs2 = a.Xs1;
+    }
     if (!pow2_applicable(a0)) return launch_halo_gen(a, stream);
     static bool attr_set = false;
     if (!attr_set) {
         SD_CHECK_HIP(hipFuncSetAttribute((const void*)conv_halo_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
         SD_CHECK_HIP(hipFuncSetAttribute((const void*)conv_halo_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
+        SD_CHECK_HIP(hipFuncSetAttribute((const void*)conv_halo_kernel<0, 0, 8, 0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
 #ifdef SD_ABLATE
         SD_CHECK_HIP(hipFuncSetAttribute((const void*)conv_halo_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
         SD_CHECK_HIP(hipFuncSetAttribute((const void*)conv_halo_kernel<0, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
@@ -786,6 +884,13 @@ int sd_launch_conv3x3_halo(const GemmArgs& a0, hipStream_t stream) {
     }
     int grid = a.tiles_m * a.tiles_n * a.splitk;
     if (grid > 256) grid = 256;                  // persistent: one 8-wave workgroup per CU
+    if (a.Wsc) {
+        a.tune = 0;
+        hipLaunchKernelGGL((conv_halo_kernel<0, 0, 8, 0, 0, 1>), dim3(grid), dim3(512), SMEM, stream, a);
+        if (a.splitk > 1 && !a.defer_reduce) sd_launch_splitk_reduce(a, stream);
+        SD_CHECK_HIP(hipGetLastError());
+        return 0;
+    }
 #ifdef SD_ABLATE
     // The SD_ABLATE build only (libsdhip_ablate.so): the DIAG instantiations (timing ablations, WRONG results by design) are
     // reached through sd_op_conv3x3_ablate (GemmArgs::tune) alone -- never from the environment; tune bit 8 (+ 256) or
@@ -824,11 +929,13 @@ static int launch_halo_gen(GemmArgs a, hipStream_t stream) {
     if (!attr_set) {
         SD_CHECK_HIP(hipFuncSetAttribute((const void*)conv_halo_kernel<0, 0, 8, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
         SD_CHECK_HIP(hipFuncSetAttribute((const void*)conv_halo_kernel<1, 0, 8, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
+        SD_CHECK_HIP(hipFuncSetAttribute((const void*)conv_halo_kernel<0, 0, 8, 0, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
         attr_set = true;
     }
     int grid = a.tiles_m * a.tiles_n * a.splitk;
     if (grid > 256) grid = 256;
-    if (a.dt) hipLaunchKernelGGL((conv_halo_kernel<1, 0, 8, 0, 1>), dim3(grid), dim3(512), SMEM, stream, a);
+    if (a.Wsc) hipLaunchKernelGGL((conv_halo_kernel<0, 0, 8, 0, 1, 1>), dim3(grid), dim3(512), SMEM, stream, a);
+    else if (a.dt) hipLaunchKernelGGL((conv_halo_kernel<1, 0, 8, 0, 1>), dim3(grid), dim3(512), SMEM, stream, a);
     else hipLaunchKernelGGL((conv_halo_kernel<0, 0, 8, 0, 1>), dim3(grid), dim3(512), SMEM, stream, a);
     if (a.splitk > 1 && !a.defer_reduce) sd_launch_splitk_reduce(a, stream);
     SD_CHECK_HIP(hipGetLastError());

@@ -892,6 +892,9 @@ int sd_launch_conv3x3(const GemmArgs& a, hipStream_t stream) {
                "conv3x3: output size %dx%d inconsistent with input %dx%d stride %d up %d", a.Hout, a.Wout,
                a.Hin, a.Win, a.stride, a.up);
     SD_REQUIRE(a.M % (a.Hout * a.Wout) == 0, "conv3x3: M not a multiple of Hout*Wout");
+    // a folded 1x1 shortcut exists on the halo kernel only: never dropped silently
+    SD_REQUIRE(!a.Wsc || sd_conv_halo_shortcut_applicable(a), "conv3x3: the 1x1 shortcut (%d + %d channels) cannot ride on this conv",
+               a.Csc1, a.Csc2);
     if (sd_conv_halo_applicable(a)) return sd_launch_conv3x3_halo(a, stream);
     if (a.dt == 1) return launch<128, 160, 2, 2, 2, AMODE_CONV, EPI_STD, 1>(a, stream);
     if (big_tile_ok(a.M, a.N, 160)) return launch<256, 160, 4, 2, 3, AMODE_CONV, EPI_STD>(a, stream);

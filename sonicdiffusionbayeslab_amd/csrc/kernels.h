@@ -72,6 +72,15 @@ struct GemmArgs {
     float xscale_inv = 1.0f;          // 1 / activation scale (X_fp8 = sat(X * xscale))
     int out_fp8 = 0;                  // GEGLU epilogue only: store e4m3 bytes (ldc in bytes) ...
     float oscale = 1.0f;              // ... of out * oscale
+    // CONV on the halo kernel's 9-tap mode, bf16: the ResNet 1x1 shortcut folded into conv2 (conv_halo_kernel SC = 1):
+    //   C = conv3x3(X, W) + [Xs1 | Xs2] . Wsc^T + bias,  Xs1 = [M, Csc1] and Xs2 = [M, Csc2] dense rows (Xs2 optional), Wsc =
+    //   [N, ldwsc] rows with the Csc1 + Csc2 shortcut channels K-contiguous; Csc1 and Csc2 multiples of 64; bias = the SUM of
+    //   the two biases; no bias2, no residual (sd_conv_halo_shortcut_applicable)
+    const bf16_t* Xs1 = nullptr;
+    const bf16_t* Xs2 = nullptr;
+    const bf16_t* Wsc = nullptr;
+    long ldwsc = 0;
+    int Csc1 = 0, Csc2 = 0;
 };
 
 int sd_gemm_tile_rows(int M, int N, int K = 0);   // 64 or 128: M tile of the plain (std epilogue) GEMM (K = 0: not known)
@@ -90,6 +99,8 @@ int sd_conv_halo_mode(const GemmArgs& a);   // 1: power-of-two geometry, 2: geom
 int sd_conv3x3_splitk(int M, int N, int Cin, int Hin, int Win, int stride, int up, int dt = 0);
 bool sd_conv_halo_subpix_applicable(const GemmArgs& a);      // the sub-pixel upsampler on the halo kernel's 4-tap mode
 int sd_launch_conv3x3_halo(const GemmArgs& a, hipStream_t stream);
+// the 1x1 shortcut fields of `a` (Xs1 ... Csc2) can ride on the launch sd_launch_conv3x3 makes for the conv of `a`
+bool sd_conv_halo_shortcut_applicable(const GemmArgs& a);
 
 // GroupNorm over NHWC (optionally a two-tensor channel concat) -> bf16 [B, HW, C1+C2]
 struct GroupNormArgs {

@@ -141,6 +141,10 @@ struct Op {
     size_t c1 = NOFF;
     size_t wsc = NOFF;
     float xs = 1.f, os = 1.f;
+    // CONV3 with the resnet's 1x1 shortcut folded in (GemmArgs::Xs1 ...): shortcut sources [scx1 | scx2] of scc1 + scc2
+    // channels, scw = the packed conv_shortcut weight; `b` is then the summed bias vector and Kalg counts the shortcut channels
+    int scx1 = -1, scx2 = -1, scc1 = 0, scc2 = 0;
+    size_t scw = NOFF;
     int nwrap = 0;
     Wrap wraps[3];
 };
@@ -808,7 +812,15 @@ struct Packer {
         f32(p + "conv2.bias");
         if (u->fp8) { conv3_fp8(p + "conv1.weight", cout, cin); conv3_fp8(p + "conv2.weight", cout, cout); }
         else { conv3(p + "conv1.weight", cout, cin); conv3(p + "conv2.weight", cout, cout); }
-        if (cin != cout) { bf16_same(p + "conv_shortcut.weight"); f32(p + "conv_shortcut.bias"); }
+        if (cin != cout) {
+            bf16_same(p + "conv_shortcut.weight"); f32(p + "conv_shortcut.bias");
+            // conv2 with the shortcut folded in (Builder::resnet) adds ONE vector: the two biases summed in fp32
+            const auto& b2 = P(p + "conv2.bias");
+            const auto& bs = P(p + "conv_shortcut.bias");
+            const size_t off = alloc(p + "conv2.bias+shortcut", b2.size() * 4);
+            float* o = (float*)(u->hblob.data() + off);
+            for (size_t i = 0; i < b2.size(); ++i) o[i] = b2[i] + bs[i];
+        }
     }
     void transformer(const std::string& p, int c) {
         f32(p + "norm.weight"); f32(p + "norm.bias");
@@ -1280,6 +1292,9 @@ struct Builder {
         push(o);
         return o.out;
     }
+    // SD_SHORTCUT_FUSE=0: the conv_shortcut of a resnet stays a GEMM of its own (read when a plan is built: two handles of one
+    // process can differ)
+    bool shortcut_fuse = !(getenv("SD_SHORTCUT_FUSE") && atoi(getenv("SD_SHORTCUT_FUSE")) == 0);
     // ResnetBlock2D (A.3); input may be a virtual channel concat [x1 | x2]
     int resnet(const std::string& p, int x1, int c1, int x2, int c2, int cout, int rh, int rw, int tproj_t) {
         const int hw = rh * rw, cin = c1 + c2, M = UB * hw;
@@ -1288,7 +1303,21 @@ struct Builder {
         int t2 = conv3(t1, rh, rw, cin, cout, 1, 0, p + "conv1.weight", p + "conv1.bias", u->tproj_off.at(p), tproj_t, -1, fq);
         int t3 = gn(t2, cout, -1, 0, hw, p + "norm2.weight", p + "norm2.bias", u->cfg.norm_eps, 1, fq);
         int sc = x1;
-        if (cin != cout) sc = gemm(x1, c1, x2, c2, M, cout, p + "conv_shortcut.weight", p + "conv_shortcut.bias", -1, 0);
+        if (cin != cout) {
+            // The 1x1 shortcut rides on conv2's halo-kernel launch where it can (UNet, bf16): conv2 owns the same output tile in
+            // fp32 accumulators, so the GEMM's launch, its rounded output and conv2's residual read all go (conv_halo.hip SC).
+            GemmArgs g;
+            g.M = M; g.N = cout; g.Cin = cout; g.K = 9 * cout; g.ldw = g.K; g.Hin = g.Hout = rh; g.Win = g.Wout = rw;
+            g.Csc1 = c1; g.Csc2 = x2 >= 0 ? c2 : 0;
+            if (shortcut_fuse && !fq && u->kind == 0 && u->woff.count(p + "conv2.bias+shortcut") && sd_conv_halo_shortcut_applicable(g)) {
+                const int out = conv3(t3, rh, rw, cout, cout, 1, 0, p + "conv2.weight", p + "conv2.bias+shortcut", 0, -1, -1, fq);
+                Op& o = pl.ops.back();
+                o.scx1 = x1; o.scc1 = c1; o.scx2 = x2; o.scc2 = g.Csc2; o.scw = W(p + "conv_shortcut.weight");
+                o.Kalg += cin;          // the launch's algorithmic work includes the shortcut's K
+                return out;
+            }
+            sc = gemm(x1, c1, x2, c2, M, cout, p + "conv_shortcut.weight", p + "conv_shortcut.bias", -1, 0);
+        }
         return conv3(t3, rh, rw, cout, cout, 1, 0, p + "conv2.weight", p + "conv2.bias", 0, -1, sc, fq);
     }
     // Transformer2DModel with one BasicTransformerBlock (A.4)
@@ -1710,9 +1739,9 @@ bool wrap_skipped(const Wrap& w, int branch) {
     return w.type == 0 ? w.layer_i >= cache_layer_id : w.layer_i > cache_layer_id;
 }
 
-void op_tensors(const Op& o, int ins[12], int& nin) {
+void op_tensors(const Op& o, int ins[16], int& nin) {
     nin = 0;
-    for (int t : {o.x1, o.x2, o.r, o.b2t, o.wt, o.s1, o.s2, o.lnrs, o.slab_t, o.slab_r, o.slab_b2t})
+    for (int t : {o.x1, o.x2, o.r, o.b2t, o.wt, o.s1, o.s2, o.lnrs, o.slab_t, o.slab_r, o.slab_b2t, o.scx1, o.scx2})
         if (t >= 0) ins[nin++] = t;
 }
 
@@ -1745,7 +1774,7 @@ void fuse_deferred_reduce(sd_unet* u, Plan& pl) {
         if ((long)G.B * G.HW != P.M || G.C1 != P.N || skipped(P) != skipped(G)) continue;
         bool first_reader = true;
         for (int i = p + 1; i < g && first_reader; ++i) {
-            int ins[12], nin;
+            int ins[16], nin;
             op_tensors(pl.ops[i], ins, nin);
             for (int k = 0; k < nin; ++k)
                 if (ins[k] == P.out) first_reader = false;
@@ -1773,7 +1802,7 @@ void assign_memory(sd_unet* u, Plan& pl) {
         }
         for (int i = 0; i < nops; ++i) {
             if (pl.skipped[i]) continue;
-            int ins[12], nin;
+            int ins[16], nin;
             op_tensors(pl.ops[i], ins, nin);
             for (int k = 0; k < nin; ++k) {
                 const int p = producer[ins[k]];
@@ -1786,7 +1815,7 @@ void assign_memory(sd_unet* u, Plan& pl) {
     // lifetimes over the full plan
     for (int i = 0; i < nops; ++i) {
         const Op& o = pl.ops[i];
-        int ins[12], nin;
+        int ins[16], nin;
         op_tensors(o, ins, nin);
         for (int k = 0; k < nin; ++k) pl.tensors[ins[k]].last = std::max(pl.tensors[ins[k]].last, i);
         for (int t : {o.out, o.aux, o.stats, o.rs})
@@ -1937,6 +1966,10 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
             a.stats = (float*)T(o.stats);
             a.asym = o.asym;
             if (o.subpix) { a.subpix = 1; a.up = 0; a.w_batch_stride = (long)o.N * 4 * o.Cin; }
+            if (o.scw != NOFF) {
+                a.Xs1 = (const bf16_t*)T(o.scx1); a.Csc1 = o.scc1; a.Xs2 = (const bf16_t*)T(o.scx2); a.Csc2 = o.scc2;
+                a.Wsc = (const bf16_t*)(wb + o.scw); a.ldwsc = o.scc1 + o.scc2;
+            }
             return sd_launch_conv3x3(a, stream);
         }
         case OP_GEMM: {
@@ -2869,6 +2902,64 @@ extern "C" int sd_op_conv3x3(void* stream, const void* X, const void* W, const f
         SD_REQUIRE(a.slab, "sd_op_conv3x3: cannot allocate split-K scratch");
     }
     return sd_launch_conv3x3(a, (hipStream_t)stream);
+}
+
+// A resnet's conv2 with its 1x1 shortcut folded in, as the plan runs the pair (conv_halo.hip SC):
+//   Y = conv3x3(X, W) + [Xs1 | Xs2] . Wsc^T + bias,  X = [B, H, W, Cin], Xs1 / Xs2 = [B, H, W, Cs1 / Cs2] (Xs2 null when Cs2 =
+//   0), Wsc = [Cout, Cs1 + Cs2], bias = the sum of the two biases.  Cin is independent of Cout (small sizes reach split-K).
+// Returns the library's error code where sd_conv_halo_shortcut_applicable says no.
+static int conv3x3_shortcut_args(GemmArgs& a, const void* X, const void* W, const float* bias, const void* Xs1, int Cs1,
+                                 const void* Xs2, int Cs2, const void* Wsc, void* Y, int B, int H, int Wd, int Cin, int Cout) {
+    SD_REQUIRE(X && W && Xs1 && Wsc && Y && B > 0 && H > 0 && Wd > 0 && Cin > 0 && Cout > 0 && Cs1 > 0 && Cs2 >= 0 && (Xs2 || Cs2 == 0),
+               "conv3x3_shortcut: bad arguments");
+    a.X = (const bf16_t*)X; a.W = (const bf16_t*)W; a.bias = bias; a.C = (bf16_t*)Y; a.ldc = Cout;
+    a.Hin = a.Hout = H; a.Win = a.Wout = Wd; a.Cin = Cin; a.stride = 1; a.up = 0;
+    a.M = B * H * Wd; a.N = Cout; a.K = 9 * Cin; a.K1 = a.K; a.zero_page = g_zero_page;
+    a.Xs1 = (const bf16_t*)Xs1; a.Csc1 = Cs1; a.Xs2 = (const bf16_t*)Xs2; a.Csc2 = Cs2; a.Wsc = (const bf16_t*)Wsc; a.ldwsc = Cs1 + Cs2;
+    SD_REQUIRE(Cin % 64 == 0 && sd_conv_halo_shortcut_applicable(a),
+               "conv3x3_shortcut: %dx%d, %d -> %d channels with a %d + %d channel shortcut is not a shape the halo kernel folds", H, Wd,
+               Cin, Cout, Cs1, Cs2);
+    return 0;
+}
+
+extern "C" int sd_op_conv3x3_shortcut(void* stream, const void* X, const void* W, const float* bias, const void* Xs1, int Cs1,
+                                      const void* Xs2, int Cs2, const void* Wsc, void* Y, int B, int H, int Wd, int Cin, int Cout) {
+    if (ensure_zero_page()) return -2;
+    GemmArgs a;
+    if (int rc = conv3x3_shortcut_args(a, X, W, bias, Xs1, Cs1, Xs2, Cs2, Wsc, Y, B, H, Wd, Cin, Cout)) return rc;
+    a.splitk = sd_conv3x3_splitk(a.M, a.N, Cin, H, Wd, 1, 0);
+    if (a.splitk > 1) {
+        a.slab = (float*)op_scratch((size_t)a.splitk * a.M * a.N * 4);
+        SD_REQUIRE(a.slab, "sd_op_conv3x3_shortcut: cannot allocate split-K scratch");
+    }
+    return sd_launch_conv3x3(a, (hipStream_t)stream);
+}
+
+// The same launch feeding a GroupNorm(+SiLU) from its epilogue's block statistics (large images: H * W a multiple of 64 and
+// not the single-launch GroupNorm's): Y = the conv output, Yn = the normalised output.
+extern "C" int sd_op_conv3x3_shortcut_groupnorm(void* stream, const void* X, const void* W, const float* bias, const void* Xs1,
+                                                int Cs1, const void* Xs2, int Cs2, const void* Wsc, void* Y, int B, int H, int Wd,
+                                                int Cin, int Cout, const float* gamma, const float* beta, void* Yn, int groups,
+                                                float eps, int silu) {
+    if (ensure_zero_page()) return -2;
+    const int HW = H * Wd;
+    SD_REQUIRE(HW % 64 == 0 && !sd_groupnorm_uses_small(B, HW, Cout, 0, groups),
+               "sd_op_conv3x3_shortcut_groupnorm: %dx%d pixels per sample: producer statistics come in 64-pixel blocks", H, Wd);
+    GemmArgs a;
+    if (int rc = conv3x3_shortcut_args(a, X, W, bias, Xs1, Cs1, Xs2, Cs2, Wsc, Y, B, H, Wd, Cin, Cout)) return rc;
+    const size_t stats_bytes = (size_t)B * (HW / 64) * Cout * 2 * 4;
+    char* scratch = (char*)op_scratch(stats_bytes + sd_groupnorm_scratch_bytes(B, HW, groups));
+    SD_REQUIRE(scratch, "sd_op_conv3x3_shortcut_groupnorm: cannot allocate scratch");
+    a.splitk = 1;
+    a.stats = (float*)scratch;
+    SD_REQUIRE(sd_conv_halo_mode(a) == 1, "sd_op_conv3x3_shortcut_groupnorm: the geometry mode delivers no block statistics");
+    if (int rc = sd_launch_conv3x3(a, (hipStream_t)stream)) return rc;
+    GroupNormArgs g;
+    g.x1 = (const bf16_t*)Y; g.C1 = Cout; g.gamma = gamma; g.beta = beta; g.y = (bf16_t*)Yn; g.B = B; g.HW = HW;
+    g.groups = groups; g.eps = eps; g.silu = silu; g.nsplit = sd_groupnorm_nsplit(B, HW);
+    g.partial = (float*)(scratch + stats_bytes);
+    g.stats1 = (const float*)scratch;
+    return sd_launch_groupnorm(g, (hipStream_t)stream);
 }
 
 // 3x3 stride-2 conv padded on the right and bottom only (GemmArgs::asym; the AutoencoderKL encoder's downsampler): W packed as
