@@ -130,6 +130,19 @@ int sd_unet_set_context_hw(sd_unet* u, void* stream, const float* encoder_hidden
  * stream of the forwards that should see it (or order the streams). */
 int sd_unet_set_timestep_cond(sd_unet* u, void* stream, const float* cond);
 
+/* Condition of an inpainting UNet (in_channels = 9: conv_in reads [latents 4 | mask 1 | masked-image latents 4], diffusers'
+ * StableDiffusionInpaintPipeline).  `mask` [batch,1,latent_h,latent_w] (fp32 0 / 1; 1 = repaint) and `masked_latents`
+ * [batch,4,latent_h,latent_w] (the scaled encoding of the image with the repainted region blanked), both device fp32 and
+ * 16-byte aligned, are packed into the handle ONCE per call (one launch on `stream`), the way sd_unet_set_context_hw stores the
+ * prompt.  Every later forward at that latent size reads channels 0..3 from its latents and channels 4..8 from the stored
+ * condition, each with the batch index taken modulo its source batch (CFG duplication stays fused; unet_batch must be a
+ * multiple of `batch`): no concatenated tensor is built per forward, and the launch count of a forward is unchanged.  A forward
+ * on a 9-channel handle with no condition set, or at another size or batch, fails and says so.  A 4-channel handle refuses the
+ * call.  The operands may be freed once the stream has run the launch.  mask = masked_latents = NULL clears the condition
+ * (nothing is launched; batch and size are ignored): forwards fail again until one is set. */
+int sd_unet_set_inpaint_cond_hw(sd_unet* u, void* stream, const float* mask, const float* masked_latents, int batch,
+                                int latent_h, int latent_w);
+
 enum { SD_CACHE_OFF = 0, SD_CACHE_FULL_AND_STORE = 1, SD_CACHE_SKIP = 2 };
 
 /* eps = UNet(latent_model_input, t, encoder_hidden_states)  (src/models.py:217-235).
@@ -331,6 +344,28 @@ int sd_sched_step_rescaled(void* stream, const float* eps, int cfg, float guidan
                            const float* m2, const float* m3, const float* noise, float* prev, float* y2, float* m_out,
                            const float coef[10], long long n, const float* k, long long n_per_sample);
 
+/* ---- inpainting (diffusers' StableDiffusionInpaintPipeline) ----
+ * sd_sched_step_inpaint: sd_sched_step (k = NULL) or sd_sched_step_rescaled (k given) with the latent blend of a 4-channel
+ * UNet's inpainting loop in the SAME launch:
+ *   prev = mask ? step : a*init + s*blend_noise
+ * mask [n / n_per_sample][hw] fp32 (>= 0.5: repaint, take the step), broadcast over the n_per_sample / hw channels of its
+ * sample; init / blend_noise: n fp32 elements like x (the clean image latents and the call's forward noise); (a, s) =
+ * (sqrt(alpha_bar), sqrt(1 - alpha_bar)) of the NEXT timestep, (1, 0) after the last step.  s == 0 skips the noise term
+ * (blend_noise may then be NULL), so a = 1 returns init bit for bit.  The step side is the expression of the unmasked kernels
+ * in their order: where the mask is set, prev is bit-identical to theirs; y2 and m_out do not see the mask.  hw and
+ * n_per_sample / hw: hw a positive multiple of 4 dividing n_per_sample. */
+int sd_sched_step_inpaint(void* stream, const float* eps, int cfg, float guidance, const float* x, const float* m1,
+                          const float* m2, const float* m3, const float* noise, float* prev, float* y2, float* m_out,
+                          const float coef[10], long long n, const float* k, long long n_per_sample, const float* init,
+                          const float* blend_noise, const float* mask, float a, float s, long long hw);
+/* One launch: image [batch,3,height,width] fp32 in [0,1] and mask [batch,1,height,width] fp32 ->
+ *   masked_image [batch,3,height,width] = mask >= 0.5 ? 0.5 : image   (the encoder's input domain: 2 * 0.5 - 1 is exactly 0,
+ *                                                                      upstream's (2 image - 1) * (mask < 0.5))
+ *   latent_mask  [batch,1,height/8,width/8] = mask(8i, 8j) >= 0.5 as fp32 0 / 1   (binarise, then nearest resize)
+ * height and width: positive multiples of 8. */
+int sd_inpaint_prepare(void* stream, const float* image, const float* mask, float* masked_image, float* latent_mask,
+                       int batch, int height, int width);
+
 /* ---- operator-level entry points (each is one hot kernel; used by the parity tests) ----------- */
 /* C[M,N] = [X|X2][M,K] . W[N,K]^T + bias + bias2 + R ; epi=1: GEGLU on interleaved W (N -> N/2) */
 int sd_op_gemm(void* stream, const void* X, long long ldx, const void* X2, long long ldx2, int K1, const void* W,
@@ -425,6 +460,10 @@ int sd_op_clip_preprocess(void* stream, const unsigned char* images, int B, int 
                           void* patches);
 int sd_op_conv_in(void* stream, const float* x, int Bsrc, const float* Wt, const float* bias, void* y, int B, int H,
                   int W, int Cin, int Cout);
+/* conv_in of an inpainting UNet: x [Bsrc,4,H,W] and cond [Bcond,5,H,W] fp32 (batch indices modulo their source batch), Wt
+ * [81][Cout] fp32 (k = ic*9 + tap over the 9 concatenated channels) -> y NHWC bf16 [B,H,W,Cout]; one launch, Cout <= 1024 */
+int sd_op_conv_in_cond(void* stream, const float* x, int Bsrc, const float* cond, int Bcond, const float* Wt,
+                       const float* bias, void* y, int B, int H, int W, int Cout);
 int sd_op_conv_out(void* stream, const void* x, const void* Wp, const float* bias, float* y, int B, int H, int W,
                    int Cin, int Cout);
 int sd_op_time_embedding(void* stream, float t, const void* W1, const float* b1, const void* W2, const float* b2,

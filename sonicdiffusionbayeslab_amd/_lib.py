@@ -123,6 +123,11 @@ _SIGS = {
     "sd_sched_step": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _ll]),
     "sd_cfg_rescale_factors": (_i, [_vp, _vp, _i, _ll, _f, _f, _vp]),
     "sd_sched_step_rescaled": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _ll, _vp, _ll]),
+    "sd_sched_step_inpaint": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _ll, _vp, _ll,
+                                   _vp, _vp, _vp, _f, _f, _ll]),
+    "sd_inpaint_prepare": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
+    "sd_unet_set_inpaint_cond_hw": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
+    "sd_op_conv_in_cond": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i]),
     "sd_op_gemm": (_i, [_vp, _vp, _ll, _vp, _ll, _i, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _i]),
     "sd_op_gemm_batched": (_i, [_vp, _vp, _ll, _vp, _ll, _i, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _i, _i]),
     "sd_op_gemm_batched_softmax_ln": (_i, [_vp, _vp, _ll, _vp, _ll, _i, _vp, _ll, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f]),

@@ -240,6 +240,15 @@ int sd_launch_clip_score(const float* img, const float* txt, int B, int P, float
 // fused) -> NHWC bf16 [B,H,W,Cout]
 int sd_launch_conv_in(const float* x, int Bsrc, const float* Wt /*[Cin*9][Cout] fp32*/, const float* bias,
                       bf16_t* y, int B, int H, int W, int Cin, int Cout, hipStream_t stream);
+// conv_in of an inpainting UNet (Cin = 9): channels 0..3 from x [Bsrc,4,H,W], channels 4..8 from cond [Bcond,5,H,W] (both
+// batch indices taken modulo their source batch) -> NHWC bf16 [B,H,W,Cout]; Wt [81][Cout] fp32
+int sd_launch_conv_in_cond(const float* x, int Bsrc, const float* cond, int Bcond, const float* Wt, const float* bias,
+                           bf16_t* y, int B, int H, int W, int Cout, hipStream_t stream);
+// cond [B,5,hw] = [mask [B,1,hw] | masked [B,4,hw]] (fp32; hw a multiple of 4)
+int sd_launch_inpaint_cond_pack(const float* mask, const float* masked, float* cond, int B, long hw, hipStream_t stream);
+// inpainting, pixel space: masked [B,3,H,W] = mask >= 0.5 ? 0.5 : img, lmask [B,1,H/8,W/8] = (mask(8i, 8j) >= 0.5) as 0 / 1
+int sd_launch_inpaint_prepare(const float* img, const float* mask, float* masked, float* lmask, int B, int H, int W,
+                              hipStream_t stream);
 // AutoencoderKL encoder entry: fp32 NCHW images [B,3,H,W] in [0,1] -> conv_in(2 x - 1) as NHWC bf16 [B,H,W,Cout]
 // (the preprocessing is applied in the load; the zero padding is of the PREPROCESSED image)
 int sd_launch_conv_in_image(const float* img, const float* Wt /*[27][Cout] fp32*/, const float* bias, bf16_t* y, int B, int H,
@@ -273,6 +282,12 @@ int sd_launch_cfg_rescale_factors(const float* eps, int batch, long n_per_sample
 int sd_launch_sched_step_rescaled(const float* eps, int cfg, float guidance, const float* x, const float* m1,
                                   const float* m2, const float* m3, const float* noise, float* prev, float* y2,
                                   float* m_out, StepCoef c, const float* k, long n_per_sample, long n, hipStream_t stream);
+// sd_launch_sched_step (k null) / sd_launch_sched_step_rescaled with prev := mask ? prev : a * init + s * blend_noise;
+// mask [n / n_per_sample][hw] fp32 0 / 1, broadcast over the n_per_sample / hw channels of its sample
+int sd_launch_sched_step_inpaint(const float* eps, int cfg, float guidance, const float* x, const float* m1,
+                                 const float* m2, const float* m3, const float* noise, float* prev, float* y2,
+                                 float* m_out, StepCoef c, const float* k, long n_per_sample, long n, const float* init,
+                                 const float* blend_noise, const float* mask, float a, float s, long hw, hipStream_t stream);
 
 // inception.hip: FID Inception-v3 pieces (general implicit-GEMM conv, 3x3 pools, global mean, TF1 bilinear preprocessing)
 int sd_launch_inception_conv(const bf16_t* x, const bf16_t* w, const float* bias, bf16_t* y, int B, int Hin, int Win, int Cin,

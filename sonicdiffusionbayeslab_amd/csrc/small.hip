@@ -103,6 +103,91 @@ __global__ void conv_in_kernel(const float* __restrict__ x, int Bsrc, const floa
     }
 }
 
+// ---- conv_in of an inpainting UNet: 3x3, Cin = 9 = [4 latent | 1 mask | 4 masked-image latent] channels ------------------
+// Channels 0..3 come from the latents (batch index modulo Bsrc, as above), channels 4..8 from the condition the handle stores
+// once per call ([Bcond][5][H][W] fp32, batch index modulo Bcond): the concatenated input exists only as this block's LDS
+// patch.  One block per output row, thread = ONE output channel: 81 weights per channel live in registers (two channels per
+// thread, as the 4-channel form has, would be 162).  The sum runs in the 4-channel kernel's order (bias, then ci, dy, dx), so
+// with zero weights on channels 4..8 it is that kernel's sum followed by 45 additions of zero.
+constexpr int INPAINT_CIN = 9, INPAINT_COND = 5;
+
+// (launched with Cout threads rounded up to whole waves, at most 1024: the bound keeps it within 128 VGPRs)
+__global__ __launch_bounds__(1024) void conv_in_cond_kernel(const float* __restrict__ x, int Bsrc,
+                                                            const float* __restrict__ cond, int Bcond,
+                                                            const float* __restrict__ Wt, const float* __restrict__ bias,
+                                                            bf16_t* __restrict__ y, int H, int W, int Cout) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* patch = (float*)smem;  // [9][3][W+2]
+    constexpr int CL = INPAINT_CIN - INPAINT_COND;
+    const int yrow = blockIdx.x, b = blockIdx.y;
+    const int bs = b % Bsrc, bc = b % Bcond;
+    const int tid = threadIdx.x;
+    const int PW = W + 2;
+    for (int i = tid; i < INPAINT_CIN * 3 * PW; i += blockDim.x) {
+        const int ci = i / (3 * PW), rem = i - ci * 3 * PW;
+        const int dy = rem / PW, px = rem - dy * PW;
+        const int iy = yrow + dy - 1, ix = px - 1;
+        float v = 0.f;
+        if (iy >= 0 && iy < H && ix >= 0 && ix < W)
+            v = ci < CL ? x[(((long)bs * CL + ci) * H + iy) * W + ix]
+                        : cond[(((long)bc * INPAINT_COND + (ci - CL)) * H + iy) * W + ix];
+        patch[i] = v;
+    }
+    __syncthreads();
+    const int co = tid;
+    if (co >= Cout) return;
+    float w0[INPAINT_CIN * 9];
+#pragma unroll
+    for (int k = 0; k < INPAINT_CIN * 9; ++k) w0[k] = Wt[k * Cout + co];
+    const float b0 = bias[co];
+    bf16_t* yr = y + (((long)b * H + yrow) * W) * Cout + co;
+    for (int ox = 0; ox < W; ++ox) {
+        float a0 = b0;
+#pragma unroll
+        for (int ci = 0; ci < INPAINT_CIN; ++ci)
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+                for (int dx = 0; dx < 3; ++dx) a0 += patch[(ci * 3 + dy) * PW + ox + dx] * w0[ci * 9 + dy * 3 + dx];
+        yr[(long)ox * Cout] = f2bf(a0);
+    }
+}
+
+// the five constant channels of a call, packed once: cond[b] = [mask[b] | masked_latents[b]] ([B][5][hw] fp32)
+__global__ void inpaint_cond_pack_kernel(const float* __restrict__ mask, const float* __restrict__ masked,
+                                         float* __restrict__ cond, long hw4, long n4) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    const long per = INPAINT_COND * hw4;
+    const long b = i / per, j = i - b * per;
+    ((f32x4*)cond)[i] = j < hw4 ? ((const f32x4*)mask)[b * hw4 + j]
+                                : ((const f32x4*)masked)[b * (per - hw4) + (j - hw4)];
+}
+
+// ---- inpainting, pixel space: masked image and latent mask in one launch ----------------------------------------------
+// thread = 4 pixels of one row.  masked = m >= 0.5 ? 0.5 : img  (the encoder's [0, 1] domain: 2 * 0.5 - 1 is exactly 0);
+// latent mask (i, j) = (m(8 i, 8 j) >= 0.5) as fp32 0 / 1 (nearest resize to H/8 x W/8), written by the thread that holds
+// that pixel.
+__global__ void inpaint_prepare_kernel(const float* __restrict__ img, const float* __restrict__ mask,
+                                       float* __restrict__ masked, float* __restrict__ lmask, int H, int W, long n4) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    const int W4 = W / 4;
+    const long hw4 = (long)H * W4;
+    const long b = i / hw4, p = i - b * hw4;
+    const int yy = (int)(p / W4), x4 = (int)(p - (long)yy * W4);
+    const f32x4 m = ((const f32x4*)mask)[i];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        f32x4 v = ((const f32x4*)img)[(b * 3 + c) * hw4 + p];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = m[j] >= 0.5f ? 0.5f : v[j];
+        ((f32x4*)masked)[(b * 3 + c) * hw4 + p] = v;
+    }
+    if ((yy & 7) == 0 && (x4 & 1) == 0)
+        lmask[(b * (H / 8) + yy / 8) * (W / 8) + x4 / 2] = m[0] >= 0.5f ? 1.f : 0.f;
+}
+
 // ---- conv_out: 3x3, Cout <= 4, one wave per output pixel ------------------------------------
 __global__ __launch_bounds__(256) void conv_out_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ Wp,
                                                        const float* __restrict__ bias, float* __restrict__ y, int B,
@@ -329,6 +414,46 @@ __global__ void sched_step_rescaled_kernel(const float* __restrict__ eps, int cf
     if (noise) p += c.pn * ((const f32x4*)noise)[i];
     if (y2) ((f32x4*)y2)[i] = c.yx * xv + c.ye * e;
     if (m_out) ((f32x4*)m_out)[i] = c.mx * xv + c.me * e;
+    ((f32x4*)prev)[i] = p;
+}
+
+// ---- inpainting with a 4-channel UNet: the step and the latent blend in one launch --------------------------------------
+// prev = mask ? step : a * init + s * blend_noise, mask [B][1][hw] broadcast over the channels.  The step side is
+// sched_step_kernel's (RESCALED: sched_step_rescaled_kernel's) expression, statement for statement; y2 and m_out do not see
+// the mask.  s == 0 (after the last step: a = 1) skips the noise term, so the kept side is then a * init alone.
+template <bool RESCALED>
+__global__ void sched_step_inpaint_kernel(const float* __restrict__ eps, int cfg, float guidance,
+                                          const float* __restrict__ x, const float* __restrict__ m1,
+                                          const float* __restrict__ m2, const float* __restrict__ m3,
+                                          const float* __restrict__ noise, float* __restrict__ prev,
+                                          float* __restrict__ y2, float* __restrict__ m_out, StepCoef c,
+                                          const float* __restrict__ k, long n4s, long n4, const float* __restrict__ init,
+                                          const float* __restrict__ blend_noise, const float* __restrict__ mask, float a,
+                                          float s, long hw4) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    f32x4 e = ((const f32x4*)eps)[i];
+    if (RESCALED) {
+        if (cfg) e = cfg_combine(e, ((const f32x4*)eps)[i + n4], guidance);
+        e = k[i / n4s] * e;
+    } else if (cfg) {
+        const f32x4 et = ((const f32x4*)eps)[i + n4];
+        e = e + guidance * (et - e);
+    }
+    const f32x4 xv = ((const f32x4*)x)[i];
+    f32x4 p = c.px * xv + c.pe * e;
+    if (m1) p += c.p1 * ((const f32x4*)m1)[i];
+    if (m2) p += c.p2 * ((const f32x4*)m2)[i];
+    if (m3) p += c.p3 * ((const f32x4*)m3)[i];
+    if (noise) p += c.pn * ((const f32x4*)noise)[i];
+    if (y2) ((f32x4*)y2)[i] = c.yx * xv + c.ye * e;
+    if (m_out) ((f32x4*)m_out)[i] = c.mx * xv + c.me * e;
+    const long b = i / n4s;
+    const f32x4 mk = ((const f32x4*)mask)[b * hw4 + (i - b * n4s) % hw4];
+    f32x4 keep = a * ((const f32x4*)init)[i];
+    if (s != 0.f) keep += s * ((const f32x4*)blend_noise)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p[j] = mk[j] >= 0.5f ? p[j] : keep[j];
     ((f32x4*)prev)[i] = p;
 }
 
@@ -585,6 +710,44 @@ int sd_launch_conv_in(const float* x, int Bsrc, const float* Wt, const float* bi
     return 0;
 }
 
+int sd_launch_conv_in_cond(const float* x, int Bsrc, const float* cond, int Bcond, const float* Wt, const float* bias,
+                           bf16_t* y, int B, int H, int W, int Cout, hipStream_t stream) {
+    SD_REQUIRE(x && cond && Wt && bias && y, "conv_in_cond: null operand");
+    SD_REQUIRE(Cout > 0 && Cout <= 1024, "conv_in_cond: Cout=%d", Cout);
+    SD_REQUIRE(Bsrc > 0 && Bcond > 0 && B > 0 && B <= 65535 && B % Bsrc == 0 && B % Bcond == 0,
+               "conv_in_cond: batch %d not a multiple of the latent batch %d and the condition batch %d", B, Bsrc, Bcond);
+    SD_REQUIRE(H > 0 && W > 0, "conv_in_cond: H=%d W=%d", H, W);
+    const int threads = (Cout + 63) / 64 * 64;
+    const size_t smem = (size_t)INPAINT_CIN * 3 * (W + 2) * sizeof(float);
+    SD_REQUIRE(smem <= 64 * 1024, "conv_in_cond: W=%d needs %zu bytes of LDS (64 KiB per workgroup)", W, smem);
+    hipLaunchKernelGGL(conv_in_cond_kernel, dim3(H, B), dim3(threads), smem, stream, x, Bsrc, cond, Bcond, Wt, bias, y, H, W,
+                       Cout);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sd_launch_inpaint_cond_pack(const float* mask, const float* masked, float* cond, int B, long hw, hipStream_t stream) {
+    SD_REQUIRE(mask && masked && cond, "inpaint_cond_pack: null operand");
+    SD_REQUIRE(B > 0 && hw > 0 && hw % 4 == 0, "inpaint_cond_pack: B=%d hw=%ld (a positive multiple of 4)", B, hw);
+    const long n4 = (long)B * INPAINT_COND * (hw / 4);
+    hipLaunchKernelGGL(inpaint_cond_pack_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, mask, masked, cond,
+                       hw / 4, n4);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sd_launch_inpaint_prepare(const float* img, const float* mask, float* masked, float* lmask, int B, int H, int W,
+                              hipStream_t stream) {
+    SD_REQUIRE(img && mask && masked && lmask, "inpaint_prepare: null operand");
+    SD_REQUIRE(B > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0,
+               "inpaint_prepare: B=%d H=%d W=%d (H and W must be positive multiples of 8)", B, H, W);
+    const long n4 = (long)B * H * (W / 4);
+    hipLaunchKernelGGL(inpaint_prepare_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, img, mask, masked,
+                       lmask, H, W, n4);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 int sd_launch_conv_in_image(const float* img, const float* Wt, const float* bias, bf16_t* y, int B, int H, int W, int Cout,
                             hipStream_t stream) {
     SD_REQUIRE(img && Wt && bias && y, "conv_in_image: null operand");
@@ -656,6 +819,28 @@ int sd_launch_sched_step_rescaled(const float* eps, int cfg, float guidance, con
     const long n4 = n / 4;
     hipLaunchKernelGGL(sched_step_rescaled_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, eps, cfg,
                        guidance, x, m1, m2, m3, noise, prev, y2, m_out, c, k, n_per_sample / 4, n4);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sd_launch_sched_step_inpaint(const float* eps, int cfg, float guidance, const float* x, const float* m1,
+                                 const float* m2, const float* m3, const float* noise, float* prev, float* y2,
+                                 float* m_out, StepCoef c, const float* k, long n_per_sample, long n, const float* init,
+                                 const float* blend_noise, const float* mask, float a, float s, long hw, hipStream_t stream) {
+    SD_REQUIRE(eps && x && prev && init && mask, "sched_step_inpaint: null operand");
+    SD_REQUIRE(blend_noise || s == 0.f, "sched_step_inpaint: s=%g needs blend_noise", (double)s);
+    SD_REQUIRE(n > 0 && n % 4 == 0, "sched_step_inpaint: n=%ld must be a positive multiple of 4", n);
+    SD_REQUIRE(hw > 0 && hw % 4 == 0, "sched_step_inpaint: hw=%ld must be a positive multiple of 4", hw);
+    SD_REQUIRE(n_per_sample > 0 && n_per_sample % hw == 0 && n % n_per_sample == 0,
+               "sched_step_inpaint: n_per_sample=%ld must be a multiple of hw=%ld dividing n=%ld", n_per_sample, hw, n);
+    const long n4 = n / 4;
+    const dim3 grid((unsigned)((n4 + 255) / 256));
+    if (k)
+        hipLaunchKernelGGL(sched_step_inpaint_kernel<true>, grid, dim3(256), 0, stream, eps, cfg, guidance, x, m1, m2, m3, noise,
+                           prev, y2, m_out, c, k, n_per_sample / 4, n4, init, blend_noise, mask, a, s, hw / 4);
+    else
+        hipLaunchKernelGGL(sched_step_inpaint_kernel<false>, grid, dim3(256), 0, stream, eps, cfg, guidance, x, m1, m2, m3, noise,
+                           prev, y2, m_out, c, k, n_per_sample / 4, n4, init, blend_noise, mask, a, s, hw / 4);
     SD_CHECK_HIP(hipGetLastError());
     return 0;
 }

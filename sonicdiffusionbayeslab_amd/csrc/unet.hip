@@ -258,6 +258,12 @@ struct sd_unet {
     // forward's OP_SINUSOID adds it to the sinusoid.
     float* dcond = nullptr;
     bool cond_set = false;
+    // inpainting UNets (cfg.in_channels == 9): the five constant input channels of a call, [inpaint_b][5][h][w] fp32 =
+    // [mask | masked-image latents], written by sd_unet_set_inpaint_cond_hw.  Owned by the handle like dcond; OP_CONV_IN reads
+    // channels 4..8 from it (batch index modulo inpaint_b), so no concatenated input is built per forward.
+    float* dinpaint = nullptr;
+    size_t inpaint_cap = 0;
+    int inpaint_b = 0, inpaint_h = 0, inpaint_w = 0;
 };
 
 namespace {
@@ -1929,6 +1935,15 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
             return sd_launch_gemv((const float*)T(o.x1), (const bf16_t*)(wb + o.w), (const float*)(wb + o.b),
                                   (float*)T(o.out), o.N, o.K, o.silu_in, stream);
         case OP_CONV_IN:
+            if (u->kind == 0 && o.Cin == 9) {
+                SD_REQUIRE(u->inpaint_b > 0, "forward: this UNet has in_channels = 9 and no inpainting condition is set "
+                                             "(sd_unet_set_inpaint_cond_hw: mask and masked-image latents)");
+                SD_REQUIRE(u->inpaint_h == o.Hin && u->inpaint_w == o.Win && o.B % u->inpaint_b == 0,
+                           "forward: the inpainting condition was set for batch %d at %dx%d, the forward runs batch %d at %dx%d",
+                           u->inpaint_b, u->inpaint_h, u->inpaint_w, o.B, o.Hin, o.Win);
+                return sd_launch_conv_in_cond(latents, latent_batch, u->dinpaint, u->inpaint_b, (const float*)(wb + o.w),
+                                              (const float*)(wb + o.b), (bf16_t*)T(o.out), o.B, o.Hin, o.Win, o.N, stream);
+            }
             return sd_launch_conv_in(o.x1 >= 0 ? (const float*)T(o.x1) : latents, o.x1 >= 0 ? o.B : latent_batch,
                                      (const float*)(wb + o.w), (const float*)(wb + o.b), (bf16_t*)T(o.out), o.B, o.Hin,
                                      o.Win, o.Cin, o.N, stream);
@@ -2067,7 +2082,10 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
 extern "C" int sd_unet_create(const sd_unet_config* cfg, sd_unet** out) {
     SD_REQUIRE(cfg && out, "sd_unet_create: null argument");
     SD_REQUIRE(cfg->num_levels >= 1 && cfg->num_levels <= 8, "sd_unet_create: num_levels %d", cfg->num_levels);
-    SD_REQUIRE(cfg->in_channels == 4 && cfg->out_channels >= 1 && cfg->out_channels <= 4, "sd_unet_create: in/out channels");
+    SD_REQUIRE(cfg->in_channels == 4 || cfg->in_channels == 9,
+               "sd_unet_create: in_channels %d (4, or 9 for an inpainting UNet: latents | mask | masked-image latents)",
+               cfg->in_channels);
+    SD_REQUIRE(cfg->out_channels >= 1 && cfg->out_channels <= 4, "sd_unet_create: out_channels %d", cfg->out_channels);
     for (int i = 0; i < cfg->num_levels; ++i) {
         const int c = cfg->block_out_channels[i];
         SD_REQUIRE(c % 64 == 0 && c % cfg->norm_num_groups == 0 && c / cfg->norm_num_groups >= 8,
@@ -2337,6 +2355,7 @@ extern "C" void sd_unet_destroy(sd_unet* u) {
     if (!u) return;
     if (u->dweights) (void)hipFree(u->dweights);
     if (u->dcond) (void)hipFree(u->dcond);
+    if (u->dinpaint) (void)hipFree(u->dinpaint);
     for (auto& kv : u->prep_tabs)
         if (kv.second) (void)hipFree(kv.second);
     delete u;
@@ -2523,6 +2542,33 @@ extern "C" int sd_unet_set_timestep_cond(sd_unet* u, void* stream, const float* 
                                   u->dcond, c0, d, 0, (hipStream_t)stream);
     if (rc) return rc;
     u->cond_set = true;
+    return 0;
+}
+
+extern "C" int sd_unet_set_inpaint_cond_hw(sd_unet* u, void* stream, const float* mask, const float* masked_latents, int batch,
+                                           int latent_h, int latent_w) {
+    SD_REQUIRE(u && u->kind == 0, "set_inpaint_cond: not a UNet handle");
+    SD_REQUIRE(u->cfg.in_channels == 9, "set_inpaint_cond: the UNet has in_channels = %d (an inpainting UNet has 9)",
+               u->cfg.in_channels);
+    if (!mask && !masked_latents) {     // clear: the next forward needs a condition of its own
+        u->inpaint_b = 0;
+        return 0;
+    }
+    SD_REQUIRE(mask && masked_latents && batch > 0, "set_inpaint_cond: null argument");
+    SD_REQUIRE((((uintptr_t)mask | (uintptr_t)masked_latents) & 15) == 0, "set_inpaint_cond: operands must be 16-byte aligned");
+    if (check_latent_size(u, latent_h, latent_w, "set_inpaint_cond")) return -1;
+    const size_t bytes = (size_t)batch * 5 * latent_h * latent_w * sizeof(float);
+    if (bytes > u->inpaint_cap) {
+        if (u->dinpaint) (void)hipFree(u->dinpaint);     // (synchronises: no earlier forward still reads it)
+        u->dinpaint = nullptr; u->inpaint_cap = 0; u->inpaint_b = 0;
+        SD_CHECK_HIP(hipMalloc((void**)&u->dinpaint, bytes));
+        u->inpaint_cap = bytes;
+    }
+    u->inpaint_b = 0;
+    const int rc = sd_launch_inpaint_cond_pack(mask, masked_latents, u->dinpaint, batch, (long)latent_h * latent_w,
+                                               (hipStream_t)stream);
+    if (rc) return rc;
+    u->inpaint_b = batch; u->inpaint_h = latent_h; u->inpaint_w = latent_w;
     return 0;
 }
 
@@ -2839,6 +2885,22 @@ extern "C" int sd_sched_step_rescaled(void* stream, const float* eps, int cfg, f
     StepCoef c{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7], coef[8], coef[9]};
     return sd_launch_sched_step_rescaled(eps, cfg, guidance, x, m1, m2, m3, noise, prev, y2, m_out, c, k, (long)n_per_sample,
                                          (long)n, (hipStream_t)stream);
+}
+
+extern "C" int sd_sched_step_inpaint(void* stream, const float* eps, int cfg, float guidance, const float* x, const float* m1,
+                                     const float* m2, const float* m3, const float* noise, float* prev, float* y2,
+                                     float* m_out, const float coef[10], long long n, const float* k, long long n_per_sample,
+                                     const float* init, const float* blend_noise, const float* mask, float a, float s,
+                                     long long hw) {
+    SD_REQUIRE(coef, "sched_step_inpaint: null coefficients");
+    StepCoef c{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7], coef[8], coef[9]};
+    return sd_launch_sched_step_inpaint(eps, cfg, guidance, x, m1, m2, m3, noise, prev, y2, m_out, c, k, (long)n_per_sample,
+                                        (long)n, init, blend_noise, mask, a, s, (long)hw, (hipStream_t)stream);
+}
+
+extern "C" int sd_inpaint_prepare(void* stream, const float* image, const float* mask, float* masked_image, float* latent_mask,
+                                  int batch, int height, int width) {
+    return sd_launch_inpaint_prepare(image, mask, masked_image, latent_mask, batch, height, width, (hipStream_t)stream);
 }
 
 // ---- operator-level entry points -------------------------------------------------------------
@@ -3206,6 +3268,11 @@ extern "C" int sd_op_attention_headmajor(void* stream, const void* Q, long long 
     if (ensure_zero_page()) return -2;
     a.consts = g_zero_page;
     return sd_launch_attention(a, (hipStream_t)stream);
+}
+
+extern "C" int sd_op_conv_in_cond(void* stream, const float* x, int Bsrc, const float* cond, int Bcond, const float* Wt,
+                                  const float* bias, void* y, int B, int H, int W, int Cout) {
+    return sd_launch_conv_in_cond(x, Bsrc, cond, Bcond, Wt, bias, (bf16_t*)y, B, H, W, Cout, (hipStream_t)stream);
 }
 
 extern "C" int sd_op_conv_in(void* stream, const float* x, int Bsrc, const float* Wt, const float* bias, void* y, int B,

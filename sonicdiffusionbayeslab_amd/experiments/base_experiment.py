@@ -90,6 +90,41 @@ class BaseMethod(ABC):
             raise FileNotFoundError(f"experiment_params.strength is set (image-to-image) but the image directory "
                                     f"dataset.img_dataset = {str(self.config.dataset.img_dataset)!r} does not exist")
 
+        # optional experiment_params.inpaint_box = [top, left, bottom, right] (key of this build), pixels of dataset.image_size,
+        # each a multiple of 8: inpainting -- every prompt's own file is the image and the box the region to repaint;
+        # strength is experiment_params.strength, or 1.0.  Absent: nothing changes.
+        self.inpaint_box = self.parse_inpaint_box(self.config.get("experiment_params", {}).get("inpaint_box", None),
+                                                  int(self.config.dataset.get("image_size", 512)))
+        if self.inpaint_box is not None:
+            if not os.path.isdir(str(self.config.dataset.img_dataset)):
+                raise FileNotFoundError(f"experiment_params.inpaint_box is set (inpainting) but the image directory "
+                                        f"dataset.img_dataset = {str(self.config.dataset.img_dataset)!r} does not exist")
+            if self.img2img_strength is None:
+                self.img2img_strength = 1.0
+
+    @staticmethod
+    def parse_inpaint_box(box, image_size: int):
+        """``experiment_params.inpaint_box`` -> (top, left, bottom, right) or None.  Four integers, multiples of 8, with
+        0 <= top < bottom <= image_size and 0 <= left < right <= image_size; anything else raises ``ValueError``."""
+        if box is None:
+            return None
+        box = list(box) if isinstance(box, (list, tuple)) else box
+        if not isinstance(box, list) or len(box) != 4 or any(isinstance(v, bool) or not isinstance(v, int) for v in box):
+            raise ValueError(f"experiment_params.inpaint_box={box!r}: four integers [top, left, bottom, right]")
+        t, l, b, r = box
+        if any(v % 8 for v in box) or not (0 <= t < b <= image_size and 0 <= l < r <= image_size):
+            raise ValueError(f"experiment_params.inpaint_box={box!r}: multiples of 8 with 0 <= top < bottom <= {image_size} and "
+                             f"0 <= left < right <= {image_size} (dataset.image_size)")
+        return t, l, b, r
+
+    def inpaint_mask(self, n: int) -> torch.Tensor:
+        """The box as a mask [n, 1, S, S]: 1 inside (repaint), 0 outside (keep)."""
+        size = int(self.config.dataset.get("image_size", 512))
+        t, l, b, r = self.inpaint_box
+        m = torch.zeros(n, 1, size, size)
+        m[:, :, t:b, l:r] = 1.0
+        return m
+
     def load_images(self, files):
         """The start images of one prompt batch, ``[B, 3, S, S]`` in [0, 1] (``dataset.image_size``; the reference's
         transform, ``dataset.image_transform``)."""
@@ -155,6 +190,8 @@ class BaseMethod(ABC):
                 # image-to-image: this rank's slice of the batch's start images rides with its slice of the prompts
                 call_kwargs = {**call_kwargs, "image": self.load_images(list(batch["image_file"])[lo:hi]),
                                "strength": self.img2img_strength}
+                if getattr(self, "inpaint_box", None) is not None:
+                    call_kwargs["mask_image"] = self.inpaint_mask(hi - lo)
             if len(local_prompts) > 0:
                 # every Gaussian of the call (initial latents, per-step noise of the stochastic samplers) is drawn for the
                 # GLOBAL batch from the shared generator and sliced: dist.randn inside dist.shard_draws
@@ -176,7 +213,7 @@ class BaseMethod(ABC):
     def _empty_result(self, out_type: str) -> torch.Tensor:
         ucfg = self.model.unet_config
         if out_type == "latent":
-            return torch.empty((0, ucfg.in_channels, ucfg.sample_size, ucfg.sample_size), device=self.device)
+            return torch.empty((0, ucfg.out_channels, ucfg.sample_size, ucfg.sample_size), device=self.device)
         return torch.empty((0, 3, ucfg.sample_size * 8, ucfg.sample_size * 8), device=self.device)
 
     def sweep(self, points, call_kwargs, label, extra=None, guidance_scale: float = 7.5):

@@ -34,7 +34,7 @@ import torch
 from . import dist as sdist
 from .registry import models_registry
 from .schedulers import PNDMConfigStub
-from .unet import CACHE_FULL_AND_STORE, CACHE_OFF, CACHE_SKIP, HipUNet2DConditionModel
+from .unet import CACHE_FULL_AND_STORE, CACHE_OFF, CACHE_SKIP, LATENT_CHANNELS, HipUNet2DConditionModel
 from .vae import HipVaeDecoder, HipVaeEncoder, VaeConfig, load_vae_state_dict, make_synthetic_vae_state_dict
 from .weights import UNetConfig, load_scheduler_config, load_unet_config, load_unet_state_dict, make_synthetic_state_dict
 
@@ -67,6 +67,16 @@ class SyntheticTextEncoder:
 
 class _VaeConfig:
     scaling_factor = 0.18215
+
+
+class _Unset:
+    """Default of ``strength``: 0.8 for image-to-image, 1.0 with ``mask_image`` (upstream's defaults); an explicit value wins."""
+
+    def __repr__(self):
+        return "<0.8, or 1.0 with mask_image>"
+
+
+STRENGTH_UNSET = _Unset()
 
 
 def get_guidance_scale_embedding(w, embedding_dim: int = 512, dtype=torch.float32) -> torch.Tensor:
@@ -344,7 +354,7 @@ class StableDiffusionModel:
     def _start_loop(self, batch_size, device, generator, latents, ctx, cache_branch_id):
         """Initial latents at the call's size, DeepCache branch and prompt context of the UNet."""
         c = self.unet_config
-        latents = self.prepare_latents(batch_size, c.in_channels, self._size[0], self._size[1], device, generator, latents)
+        latents = self.prepare_latents(batch_size, LATENT_CHANNELS, self._size[0], self._size[1], device, generator, latents)
         self.unet.set_deepcache(cache_branch_id)
         self.unet.set_context(ctx, *self.latent_size)
         return latents
@@ -400,13 +410,20 @@ class StableDiffusionModel:
         else:
             cfgu = self.unet_config
             g = torch.Generator().manual_seed(self.FP8_CALIBRATION_SEED)
-            lat = torch.randn((2, cfgu.in_channels, cfgu.sample_size, cfgu.sample_size), generator=g)
+            lat = torch.randn((2, LATENT_CHANNELS, cfgu.sample_size, cfgu.sample_size), generator=g)
             ctx = self.text_encoder(list(self.FP8_CALIBRATION_PROMPTS)).to(self.unet.device, torch.float32)
             branch = self.unet.cache_branch_id
             self.unet.set_deepcache(-1)             # the calibration pass runs the plan without DeepCache
             self.unet.set_context(ctx)
             self.unet.set_timestep_cond(self.guidance_condition(self.FP8_CALIBRATION_GUIDANCE))
+            if cfgu.in_channels == 9:
+                # an inpainting UNet: a FIXED condition beside the fixed latents -- repaint everything (mask of ones) over a
+                # blank masked image (zero latents) -- so the scales stay independent of rank and call
+                s_ = cfgu.sample_size
+                self.unet.set_inpaint_cond(torch.ones(2, 1, s_, s_), torch.zeros(2, LATENT_CHANNELS, s_, s_))
             self.unet.calibrate_fp8(lat, 2, list(self.FP8_CALIBRATION_TIMESTEPS), margin=margin)
+            if cfgu.in_channels == 9:
+                self.unet.clear_inpaint_cond()      # (the caller sets its own inpainting condition)
             self.unet.set_timestep_cond(None)
             self.unet.set_deepcache(branch)         # (the caller sets its own context and condition next)
             how = "calibrated on the fixed seeded batch"
@@ -534,6 +551,134 @@ class StableDiffusionModel:
         execution_time = time.time() - start_time
         return self._finish(latents, x0_preds, output_type, return_dict, execution_time)
 
+    # -- inpainting (diffusers StableDiffusionInpaintPipeline, upstream-recall; DESIGN.md "Inpainting") ------------------
+    @staticmethod
+    def _mask_tensor(mask_image) -> torch.Tensor:
+        """``mask_image`` of a pipeline call -> fp32 [B, 1, H, W] in [0, 1] on the host: a float tensor [B,1,H,W] or
+        [B,H,W] as it is, a list of PIL images of one size through ``convert("L")`` and ``/ 255``."""
+        if isinstance(mask_image, torch.Tensor):
+            m = mask_image
+            if m.dim() == 3:
+                m = m[:, None]
+            if m.dim() != 4 or m.shape[1] != 1 or not m.is_floating_point():
+                raise ValueError(f"mask_image must be a float tensor [B,1,H,W] or [B,H,W] in [0,1], got "
+                                 f"{tuple(mask_image.shape)} {mask_image.dtype}")
+            return m.to(torch.float32)
+        if isinstance(mask_image, (list, tuple)) and len(mask_image) > 0 and all(hasattr(im, "convert") for im in mask_image):
+            import numpy as np
+            sizes = {im.size for im in mask_image}
+            if len(sizes) != 1:
+                raise ValueError(f"mask_image: the PIL masks of one call must have one size, got {sorted(sizes)}")
+            arr = np.stack([np.asarray(im.convert("L"), dtype=np.float32) / 255.0 for im in mask_image])
+            return torch.from_numpy(arr)[:, None].contiguous()
+        raise ValueError("mask_image must be a float tensor [B,1,H,W] or [B,H,W] in [0,1] or a list of PIL images of one size")
+
+    def _inpaint_args(self, image, mask_image, strength, sample_mode, prompt, prompt_embeds, height, width, latents,
+                      num_inference_steps):
+        """Every argument check of an inpainting call, before any GPU work: those of image-to-image, then the mask's.
+        Returns (image, mask [B,1,H,W], height, width, t_start), tensors on the host."""
+        img, ih, iw, t_start = self._img2img_args(image, strength, sample_mode, prompt, prompt_embeds, height, width, None,
+                                                  num_inference_steps)
+        mask = self._mask_tensor(mask_image)
+        if tuple(mask.shape[2:]) != (ih, iw):
+            raise ValueError(f"mask_image size {int(mask.shape[2])}x{int(mask.shape[3])} does not match the image size {ih}x{iw}")
+        if mask.shape[0] != img.shape[0]:
+            raise ValueError(f"mask_image batch {mask.shape[0]} does not match the image batch {img.shape[0]}")
+        if latents is not None:
+            if float(strength) != 1.0:
+                raise ValueError(f"latents= with mask_image is the forward noise of the call and is accepted only at strength == "
+                                 f"1.0 (got strength={strength}): below it the loop would start from pure noise part-way down "
+                                 "the schedule")
+            want = (img.shape[0], LATENT_CHANNELS, ih // self.vae_scale_factor, iw // self.vae_scale_factor)
+            if tuple(latents.shape) != want:
+                raise ValueError(f"latents {tuple(latents.shape)} do not match the image: expected {want}")
+        return img, mask, ih, iw, t_start
+
+    def inpaint_prepare(self, image: torch.Tensor, mask: torch.Tensor):
+        """``sd_inpaint_prepare`` (one launch): (masked image [B,3,H,W] in the encoder's [0, 1] domain -- 0.5 where the
+        mask is >= 0.5 --, latent mask [B,1,H/8,W/8] fp32 0 / 1 = the binarised mask's pixel (8i, 8j))."""
+        from . import _lib
+        lib = _lib.load()
+        self._ensure_unet()
+        img = image.to(self.unet.device, torch.float32).contiguous()
+        m = mask.to(self.unet.device, torch.float32).contiguous()
+        b, _, h, w = img.shape
+        if h % 8 or w % 8 or tuple(m.shape) != (b, 1, h, w):
+            raise ValueError(f"inpaint_prepare: image {tuple(img.shape)} (sides multiples of 8) and mask {tuple(m.shape)}")
+        masked = torch.empty_like(img)
+        lmask = torch.empty((b, 1, h // 8, w // 8), dtype=torch.float32, device=img.device)
+        _lib.check(lib.sd_inpaint_prepare(_lib.current_stream(), img.data_ptr(), m.data_ptr(), masked.data_ptr(),
+                                          lmask.data_ptr(), b, h, w), "sd_inpaint_prepare")
+        return masked, lmask
+
+    @torch.no_grad()
+    def _call_inpaint(self, prompt, image, mask_image, strength, sample_mode, height, width, num_inference_steps, timesteps,
+                      sigmas, guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents, prompt_embeds,
+                      negative_prompt_embeds, output_type, return_dict, guidance_rescale, step_noise, collect_x0):
+        """The loop of ``_call_img2img`` with a mask (1 = repaint, 0 = keep).  A 4-channel UNet: after every step the kept
+        region is replaced by the image's latents noised to the NEXT timestep (the image's latents themselves after the last
+        step) -- inside the step's launch (``step_fused(inpaint=...)``).  A 9-channel UNet reads the latent mask and the
+        masked image's latents as input channels 4..8 (``set_inpaint_cond``, once per call) and the loop does not blend.
+        Draws, in order: posterior noise of the image latents, forward noise (or ``latents``), and for a 9-channel UNet the
+        posterior noise of the masked-image latents."""
+        img, mask, ih, iw, t_start = self._inpaint_args(image, mask_image, strength, sample_mode, prompt, prompt_embeds, height,
+                                                        width, latents, num_inference_steps)
+        device, batch_size, do_cfg, ctx = self._begin(prompt, ih, iw, guidance_scale, negative_prompt,
+                                                      num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
+                                                      guidance_rescale, timesteps, sigmas)
+        nine = self.unet_config.in_channels == 9
+        unet_batch = ctx.shape[0]
+        self.scheduler.set_timesteps(num_inference_steps, device=device)
+        ts_host = list(self.scheduler._timesteps_list)[t_start * self.scheduler.order:]
+        dc = self._deepcache
+        # mask processing, encoding and noising sit outside the timed region, as text encoding does
+        enc = self._ensure_vae_encoder()
+        scale = self.vae_config.scaling_factor
+        img = img.to(device)
+        masked_img, lmask = self.inpaint_prepare(img, mask)
+        shape = (batch_size, LATENT_CHANNELS, ih // self.vae_scale_factor, iw // self.vae_scale_factor)
+        init = None
+        if not (nine and latents is not None):          # (9 channels from given noise at strength 1: nothing reads them)
+            moments = enc.encode(img)
+            post = sdist.randn(shape, generator) if sample_mode == "sample" else None
+            init = enc.sample(moments, post, mode=sample_mode, scale=scale)
+        noise = (latents if latents is not None else sdist.randn(shape, generator)).to(device, torch.float32).contiguous()
+        if nine:
+            post = sdist.randn(shape, generator) if sample_mode == "sample" else None
+            masked_latents = enc.sample(enc.encode(masked_img), post, mode=sample_mode, scale=scale)
+            self.unet.set_inpaint_cond(lmask, masked_latents)
+        # upstream: pure noise (times init_noise_sigma, in _start_loop) at strength 1, the noised image latents below it
+        start = noise if float(strength) == 1.0 else self.scheduler.add_noise(init, noise, ts_host[0])
+        self.inpaint_image_latents, self.inpaint_latent_mask = init, lmask
+        latents = self._start_loop(batch_size, device, None, start, ctx, dc.cache_branch_id if dc is not None else -1)
+        self.img2img_start_latents = latents
+        eps = self._eps_buffer(unet_batch, device)
+        self._num_timesteps = len(ts_host)
+        x0_preds = []
+        is_lcm = hasattr(self.scheduler, "config") and "timestep_scaling" in self.scheduler.config
+
+        torch.cuda.synchronize(device)
+        start_time = time.time()
+        for i, t in enumerate(ts_host):
+            mode = CACHE_OFF
+            if dc is not None:
+                mode = CACHE_FULL_AND_STORE if ts_host.index(t) % dc.cache_interval == 0 else CACHE_SKIP
+            self.unet.forward_latents(latents, unet_batch, float(t), out=eps, cache_mode=mode)
+            kw = {}
+            if is_lcm and step_noise is not None and i < len(ts_host) - 1:
+                kw["noise"] = step_noise[i]             # indexed by EXECUTED step
+            if do_cfg and guidance_rescale > 0.0:
+                kw["guidance_rescale"] = guidance_rescale
+            if not nine:
+                kw["inpaint"] = (init, noise, lmask, ts_host[i + 1] if i + 1 < len(ts_host) else None)
+            step = self.scheduler.step_fused(eps, guidance_scale, latents, t, cfg=do_cfg, eta=eta, generator=generator, **kw)
+            latents, x0 = step[0], step[1]
+            if collect_x0:
+                x0_preds.append(x0[0:1])
+        torch.cuda.synchronize(device)
+        execution_time = time.time() - start_time
+        return self._finish(latents, x0_preds, output_type, return_dict, execution_time)
+
     # -- the sampling loop (src/models.py:32-335) ----------------------------------------------
     @torch.no_grad()
     def call(self, prompt: Union[str, List[str]] = None, height: Optional[int] = None, width: Optional[int] = None,
@@ -542,11 +687,31 @@ class StableDiffusionModel:
              latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None,
              negative_prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil",
              return_dict: bool = True, guidance_rescale: float = 0.0, step_noise: Optional[torch.Tensor] = None,
-             collect_x0: bool = True, image=None, strength: float = 0.8, sample_mode: str = "sample", **kwargs):
+             collect_x0: bool = True, image=None, strength=STRENGTH_UNSET, sample_mode: str = "sample", mask_image=None,
+             padding_mask_crop=None, **kwargs):
         """``image`` ([B,3,H,W] floats in [0,1], or a list of PIL images of one size): image-to-image with the semantics
         of diffusers' StableDiffusionImg2ImgPipeline -- the image defines the size, ``strength`` in [0, 1] how far up the
         schedule its encoding is noised (``img2img_steps``), ``sample_mode`` whether the posterior is sampled or its mode
-        taken.  ``image is None``: text-to-image, the path below."""
+        taken.  ``mask_image`` ([B,1,H,W] or [B,H,W] floats in [0,1], or PIL images; 1 = repaint, 0 = keep) beside ``image``:
+        inpainting with the semantics of StableDiffusionInpaintPipeline (``_call_inpaint``); ``strength`` then defaults to 1.0
+        instead of 0.8, and ``latents`` is the forward noise (strength 1.0 only).  A UNet with 9 input channels runs only with
+        ``mask_image``.  ``image is None``: text-to-image, the path below."""
+        if padding_mask_crop is not None:
+            raise NotImplementedError("padding_mask_crop is not built (the crop-and-paste of StableDiffusionInpaintPipeline; "
+                                      "without it upstream composites nothing in pixel space, and neither does this)")
+        if mask_image is not None:
+            if image is None:
+                raise ValueError("mask_image without image: inpainting needs the image the mask refers to")
+            return self._call_inpaint(prompt, image, mask_image, 1.0 if strength is STRENGTH_UNSET else strength, sample_mode,
+                                      height, width, num_inference_steps, timesteps, sigmas, guidance_scale, negative_prompt,
+                                      num_images_per_prompt, eta, generator, latents, prompt_embeds, negative_prompt_embeds,
+                                      output_type, return_dict, guidance_rescale, step_noise, collect_x0)
+        if self.unet_config.in_channels == 9:
+            raise ValueError("this UNet has 9 input channels (an inpainting checkpoint: latents | mask | masked-image latents): "
+                             "it runs only with image= and mask_image=, not as " +
+                             ("plain image-to-image" if image is not None else "text-to-image"))
+        if strength is STRENGTH_UNSET:
+            strength = 0.8
         if image is not None:
             return self._call_img2img(prompt, image, strength, sample_mode, height, width, num_inference_steps, timesteps,
                                       sigmas, guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents,
@@ -627,6 +792,9 @@ class _VariantBase(StableDiffusionModel):
         return step[0]
 
     def _refuse_image(self, kwargs):
+        if kwargs.get("mask_image") is not None:
+            raise NotImplementedError(f"mask_image= (inpainting) is not built for {type(self).__name__}; "
+                                      "StableDiffusionModel runs it")
         if kwargs.get("image") is not None:
             raise NotImplementedError(f"image= (image-to-image) is not built for {type(self).__name__}; "
                                       "StableDiffusionModel runs it")

@@ -157,10 +157,11 @@ class _FusedStepScheduler:
 
     # --- the single fused launch ------------------------------------------------------------
     @staticmethod
-    def _launch(eps, cfg, guidance, x, m1, m2, noise, coef, want_y2=True, want_m=False, m3=None, k=None):
+    def _launch(eps, cfg, guidance, x, m1, m2, noise, coef, want_y2=True, want_m=False, m3=None, k=None, blend=None):
         """coef = (px, pe, p1, p2, pn, yx, ye, mx, me[, p3]) -- see include/sd_hip.h::sd_sched_step.  ``k`` (per-sample
         rescaled-CFG factors, ``cfg_rescale_factors``): the step scales the combined prediction by them
-        (sd_sched_step_rescaled); None launches sd_sched_step."""
+        (sd_sched_step_rescaled); None launches sd_sched_step.  ``blend`` = (init, blend_noise, mask, a, s), the latent
+        blend of inpainting (``_blend``): the same step as sd_sched_step_inpaint, with or without ``k`` -- still one launch."""
         lib = _lib.load()
         n = x.numel()
         prev = torch.empty_like(x)
@@ -168,7 +169,14 @@ class _FusedStepScheduler:
         mo = torch.empty_like(x) if want_m else None
         c10 = [float(v) for v in coef] + [0.0] * (10 - len(coef))
         carr = (C.c_float * 10)(*c10)
-        if k is None:
+        if blend is not None:
+            init, bnoise, mask, a, s = blend
+            _lib.check(lib.sd_sched_step_inpaint(_lib.current_stream(), eps.data_ptr(), int(cfg), float(guidance), x.data_ptr(),
+                                                 _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(m3), _lib.ptr(noise), prev.data_ptr(),
+                                                 _lib.ptr(y2), _lib.ptr(mo), carr, n, _lib.ptr(k), n // x.shape[0],
+                                                 init.data_ptr(), bnoise.data_ptr(), mask.data_ptr(), float(a), float(s),
+                                                 mask.numel() // mask.shape[0]), "sd_sched_step_inpaint")
+        elif k is None:
             _lib.check(lib.sd_sched_step(_lib.current_stream(), eps.data_ptr(), int(cfg), float(guidance), x.data_ptr(),
                                          _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(m3), _lib.ptr(noise), prev.data_ptr(),
                                          _lib.ptr(y2), _lib.ptr(mo), carr, n), "sd_sched_step")
@@ -211,6 +219,26 @@ class _FusedStepScheduler:
         return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
 
     rescale_factors: Optional[torch.Tensor] = None
+
+    def _blend_kw(self, inpaint, x):
+        """``blend=`` of ``_launch`` for an inpainting step; nothing otherwise (the launch is then called as before)."""
+        return {} if inpaint is None else {"blend": self._blend(inpaint, x)}
+
+    def _blend(self, inpaint, x):
+        """``inpaint`` of ``step_fused`` -> the blend operands of the launch.  ``inpaint = (init, noise, mask,
+        next_timestep_or_None)``: after the step, latents := mask ? prev : add_noise(init, noise, next_timestep), and ``init``
+        itself after the last step (None).  ``init`` / ``noise``: fp32 like the sample; ``mask``: [B, 1, h, w] fp32 0 / 1.
+        (a, s) are ``_add_noise_coefs`` of the next timestep, (1, 0) after the last step."""
+        if inpaint is None:
+            return None
+        init, noise, mask, t_next = inpaint
+        init, noise, mask = self._prep(init), self._prep(noise), self._prep(mask)
+        if init.shape != x.shape or noise.shape != x.shape:
+            raise ValueError(f"inpaint: init {tuple(init.shape)} / noise {tuple(noise.shape)} do not match the sample {tuple(x.shape)}")
+        if mask.dim() != 4 or mask.shape[0] != x.shape[0] or mask.shape[1] != 1 or mask.shape[2:] != x.shape[2:]:
+            raise ValueError(f"inpaint: mask {tuple(mask.shape)} must be [{x.shape[0]}, 1, {x.shape[2]}, {x.shape[3]}]")
+        a, s = (1.0, 0.0) if t_next is None else self._add_noise_coefs(t_next)
+        return init, noise, mask, a, s
 
     # --- forward process (image-to-image start; diffusers' ``add_noise``, upstream-recall) -----------------------------
     def _add_noise_coefs(self, timestep):
@@ -287,7 +315,7 @@ class DDIMSchedulerMy(_FusedStepScheduler):
         return cx, ce, dx, de
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   guidance_rescale: float = 0.0):
+                   guidance_rescale: float = 0.0, inpaint=None):
         if eta != 0.0:
             raise NotImplementedError("DDIM eta != 0 is never used by the reference (src/models.py:43)")
         if self.num_inference_steps is None:
@@ -295,7 +323,8 @@ class DDIMSchedulerMy(_FusedStepScheduler):
         cx, ce, dx, de = self.coefficients(timestep)
         e, x = self._prep(model_output), self._prep(sample)
         k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x)
-        prev, x0, _ = self._launch(e, cfg, guidance_scale, x, None, None, None, (cx, ce, 0, 0, 0, dx, de, 0, 0), k=k)
+        prev, x0, _ = self._launch(e, cfg, guidance_scale, x, None, None, None, (cx, ce, 0, 0, 0, dx, de, 0, 0), k=k,
+                                   **self._blend_kw(inpaint, x))
         return prev, x0
 
 
@@ -465,7 +494,7 @@ class DPMSolverScheduler(_FusedStepScheduler):
         return ratio + c0 * mx, c0 * me, c1, c2, pn
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   variance_noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0):
+                   variance_noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0, inpaint=None):
         c = self.config
         if self.num_inference_steps is None:
             raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
@@ -494,8 +523,9 @@ class DPMSolverScheduler(_FusedStepScheduler):
             z = self._prep(variance_noise.to(x.device))
         e = self._prep(model_output)
         k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x)
+        # (inpainting: the history entry m0 and x0 are taken before the blend, as upstream steps first and blends after)
         prev, x0, m0 = self._launch(e, cfg, guidance_scale, x, m1, m2, z, (px, pe, p1, p2, pn, yx, ye, mx, me),
-                                    want_y2=True, want_m=True, k=k)
+                                    want_y2=True, want_m=True, k=k, **self._blend_kw(inpaint, x))
         for k in range(c.solver_order - 1):
             self.model_outputs[k] = self.model_outputs[k + 1]
         self.model_outputs[-1] = m0
@@ -534,7 +564,7 @@ class LCMScheduler(_FusedStepScheduler):
         self._set(origin[idx], device)
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0):
+                   noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0, inpaint=None):
         if self.num_inference_steps is None:
             raise ValueError("run set_timesteps first")
         if self._step_index is None:
@@ -560,7 +590,7 @@ class LCMScheduler(_FusedStepScheduler):
             coef = (math.sqrt(ap) * yx, math.sqrt(ap) * ye, 0, 0, math.sqrt(1.0 - ap), yx, ye, 0, 0)
         e = self._prep(model_output)
         k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x)
-        prev, den, _ = self._launch(e, cfg, guidance_scale, x, None, None, z, coef, k=k)
+        prev, den, _ = self._launch(e, cfg, guidance_scale, x, None, None, z, coef, k=k, **self._blend_kw(inpaint, x))
         self._step_index += 1
         return prev, den
 
@@ -612,7 +642,10 @@ class PNDMScheduler(_FusedStepScheduler):
         return sample_coeff, k
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   guidance_rescale: float = 0.0):
+                   guidance_rescale: float = 0.0, inpaint=None):
+        if inpaint is not None:
+            raise NotImplementedError("PNDMScheduler: the latent blend of inpainting is not built (its second timestep is "
+                                      "duplicated; DDIM, DPM-Solver and LCM are built)")
         if self.num_inference_steps is None:
             raise ValueError("run set_timesteps first")
         t = int(timestep)

@@ -18,6 +18,7 @@ from . import _lib
 from .weights import UNetConfig, param_shapes
 
 CACHE_OFF, CACHE_FULL_AND_STORE, CACHE_SKIP = 0, 1, 2
+LATENT_CHANNELS = 4         # channels of the latents crossing the ABI (an inpainting UNet's other 5 are set per call)
 
 
 def _c_config(cfg: UNetConfig, weight_dtype: str = "bf16", fp8_act_scales=(0.0, 0.0)) -> _lib.SdUnetConfig:
@@ -78,6 +79,7 @@ class HipUNet2DConditionModel:
         self._ctx_key = None
         self._ctx_keepalive = None
         self._cond = None                   # the condition set on the handle (device fp32 [time_cond_proj_dim]) or None
+        self._inpaint_key = None            # (batch, h, w) of the inpainting condition on the handle (in_channels == 9)
         self.cache_branch_id = -1
 
     def __del__(self):
@@ -154,15 +156,42 @@ class HipUNet2DConditionModel:
                    "sd_unet_set_timestep_cond")
         self._cond = row                    # (also keeps the operand alive until the GEMV has run)
 
+    def set_inpaint_cond(self, mask: torch.Tensor, masked_latents: torch.Tensor) -> None:
+        """Condition of an inpainting UNet (``in_channels == 9``): ``mask`` [B,1,h,w] (0 / 1, 1 = repaint) and
+        ``masked_latents`` [B,4,h,w] (scaled encoding of the masked image), stored on the handle once per call (one launch);
+        every later forward at this size reads them as input channels 4..8, duplicated under CFG like the latents."""
+        if self.config.in_channels != 9:
+            raise ValueError(f"set_inpaint_cond: this UNet has in_channels = {self.config.in_channels} (an inpainting UNet has 9)")
+        m = mask.detach().to(self.device, torch.float32).contiguous()
+        z = masked_latents.detach().to(self.device, torch.float32).contiguous()
+        if m.dim() != 4 or z.dim() != 4 or m.shape[1] != 1 or z.shape[1] != LATENT_CHANNELS or m.shape[0] != z.shape[0] \
+                or m.shape[2:] != z.shape[2:]:
+            raise ValueError(f"set_inpaint_cond: mask [B,1,h,w] and masked_latents [B,{LATENT_CHANNELS},h,w], got "
+                             f"{tuple(m.shape)} and {tuple(z.shape)}")
+        b, _, h, w = z.shape
+        _lib.check(self._lib.sd_unet_set_inpaint_cond_hw(self._handle, _lib.current_stream(), m.data_ptr(), z.data_ptr(), b, h, w),
+                   "sd_unet_set_inpaint_cond_hw")
+        self._inpaint_key = (b, h, w)
+
+    def clear_inpaint_cond(self) -> None:
+        """Drop the inpainting condition of the handle: the next forward needs a ``set_inpaint_cond`` of its own."""
+        _lib.check(self._lib.sd_unet_set_inpaint_cond_hw(self._handle, _lib.current_stream(), None, None, 0, 0, 0),
+                   "sd_unet_set_inpaint_cond_hw")
+        self._inpaint_key = None
+
     # -- forward ---------------------------------------------------------------------------
     def forward_latents(self, latents: torch.Tensor, unet_batch: int, timestep: float,
                         out: Optional[torch.Tensor] = None, cache_mode: int = CACHE_OFF) -> torch.Tensor:
         """eps [unet_batch,4,H,W] fp32 for fp32 NCHW ``latents`` [B,4,H,W]; ``unet_batch`` is B or
         a multiple of it (CFG: 2B, the duplication is fused).  H and W are taken from ``latents``: each a
         multiple of 2^(levels - 1).  ``set_context`` must have run for this batch and size."""
-        if latents.dim() != 4 or latents.shape[1] != self.config.in_channels:
-            raise ValueError(f"latents must be [B,{self.config.in_channels},H,W], got {tuple(latents.shape)}")
+        if latents.dim() != 4 or latents.shape[1] != LATENT_CHANNELS:
+            raise ValueError(f"latents must be [B,{LATENT_CHANNELS},H,W], got {tuple(latents.shape)}")
         b, c, h, w = latents.shape
+        if self.config.in_channels == 9 and (self._inpaint_key is None or self._inpaint_key[1:] != (h, w)
+                                             or unet_batch % self._inpaint_key[0]):
+            raise _lib.SdHipError(f"this UNet has in_channels = 9: set_inpaint_cond(mask, masked_latents) must be called for "
+                                  f"this batch and size ({h}x{w}) first")
         if self._ctx_key is None or self._ctx_key[2:] != (unet_batch, h, w):
             raise _lib.SdHipError(f"set_context(encoder_hidden_states, {h}, {w}) must be called for this batch and size first")
         if latents.dtype != torch.float32 or not latents.is_contiguous() or latents.device != self.device:
@@ -192,8 +221,8 @@ class HipUNet2DConditionModel:
         if self._ctx_key is None or self._ctx_key[2:] != (unet_batch, s, s):
             raise _lib.SdHipError("set_context(encoder_hidden_states) must be called for this batch first (at sample_size)")
         latents = latents.to(self.device, torch.float32).contiguous()
-        if tuple(latents.shape[2:]) != (s, s):
-            raise ValueError(f"calibrate_fp8: latents must be {s}x{s} (sample_size), got {tuple(latents.shape)}")
+        if tuple(latents.shape[1:]) != (LATENT_CHANNELS, s, s):
+            raise ValueError(f"calibrate_fp8: latents must be [B,{LATENT_CHANNELS},{s},{s}] (sample_size), got {tuple(latents.shape)}")
         ws = self._workspace(unet_batch)
         for t in timesteps:
             _lib.check(self._lib.sd_unet_calibrate_fp8(self._handle, _lib.current_stream(), latents.data_ptr(), latents.shape[0],

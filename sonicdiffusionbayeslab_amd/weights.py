@@ -201,10 +201,18 @@ def load_unet_config(model_dir: str) -> "UNetConfig | None":
     for cand in (os.path.join(model_dir, "unet", "config.json"), os.path.join(model_dir, "config.json")):
         if os.path.isfile(cand):
             with open(cand) as f:
-                c = json.load(f)
-            break
-    else:
-        return None
+                return read_unet_config(json.load(f))
+    return None
+
+
+def read_unet_config(c: dict) -> UNetConfig:
+    """The dict of a diffusers ``unet/config.json`` -> ``UNetConfig`` (``load_unet_config`` on an open file).
+    ``in_channels``: 4, or 9 for an inpainting checkpoint ([latents | mask | masked-image latents]); any other value is
+    refused by name."""
+    cin = c.get("in_channels", 4)
+    if isinstance(cin, bool) or cin not in (4, 9):
+        raise NotImplementedError(f"unet config in_channels={cin!r}: 4 (text-to-image) and 9 (inpainting: latents | mask | "
+                                  "masked-image latents) are built")
     down = list(c.get("down_block_types", ["CrossAttnDownBlock2D"] * 3 + ["DownBlock2D"]))
     up = list(c.get("up_block_types", ["UpBlock2D"] + ["CrossAttnUpBlock2D"] * 3))
     known = {"CrossAttnDownBlock2D": True, "DownBlock2D": False}
