@@ -542,6 +542,9 @@ int sd_op_groupnorm_fp8(void* stream, const void* x1, int C1, const void* x2, in
 int sd_op_layernorm_fp8(void* stream, const void* x, const float* gamma, const float* beta, void* y, int rows, int C,
                         int Cpad, float eps, float oscale);
 int sd_op_quantize_fp8(void* stream, const void* x_bf16, void* y_fp8, long long rows, int C, int Cpad, float scale);
+/* the measurement of sd_unet_calibrate_fp8: *out_code (a device word, zeroed here) = the largest magnitude code
+ * (byte & 0x7f) among `nbytes` e4m3 bytes; codes 16-byte aligned, nbytes a multiple of 16 */
+int sd_op_amax_e4m3(void* stream, const void* codes, long long nbytes, unsigned* out_code);
 
 #ifdef __cplusplus
 }

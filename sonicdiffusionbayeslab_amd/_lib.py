@@ -167,6 +167,7 @@ _SIGS = {
     "sd_op_groupnorm_fp8": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _f]),
     "sd_op_layernorm_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f]),
     "sd_op_quantize_fp8": (_i, [_vp, _vp, _vp, _ll, _i, _i, _f]),
+    "sd_op_amax_e4m3": (_i, [_vp, _vp, _ll, _vp]),
 }
 
 

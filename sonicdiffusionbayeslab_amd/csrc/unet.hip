@@ -3364,6 +3364,13 @@ extern "C" int sd_op_quantize_fp8(void* stream, const void* x_bf16, void* y_fp8,
     return sd_launch_quantize_fp8((const bf16_t*)x_bf16, y_fp8, (long)rows, C, Cpad, scale, (hipStream_t)stream);
 }
 
+// the measurement behind sd_unet_calibrate_fp8, on its own: *out_code = the largest (byte & 0x7f) of the tensor
+extern "C" int sd_op_amax_e4m3(void* stream, const void* codes, long long nbytes, unsigned* out_code) {
+    SD_REQUIRE(out_code, "sd_op_amax_e4m3: null output");
+    SD_CHECK_HIP(hipMemsetAsync(out_code, 0, sizeof(unsigned), (hipStream_t)stream));
+    return sd_launch_amax_e4m3(codes, (long)nbytes, out_code, (hipStream_t)stream);
+}
+
 // ---- fused prompt cross-attention, operator level: Y = R + sum_h softmax_L(X A_h) B_h + b_o (xattn.hip) ----
 // ---- LayerNorm folded into the consuming GEMM (the plan's norm1 -> q|k|v and norm3 -> GEGLU pairs) ----
 // number of per-row partials a producer writes: kind 0 = GEMM with N output columns, kind 1 = fused cross-attention (M, C)

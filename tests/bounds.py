@@ -120,6 +120,175 @@ def assert_e4m3_codes(got_codes, scaled_ref, acc_bound, what, names=None):
     return ndiff
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the flip budget: how many outputs are not the correctly rounded fp64 value
+# ---------------------------------------------------------------------------------------------------------------------
+# The two gates above allow every element its a-priori WORST case; for the normalisations that is the output ulp (bf16) or a
+# band round every rounding midpoint that carries n_stat u (e4m3), wide enough to pass an eps 100x too large or a count off
+# by one.  A kernel whose only errors are a few fp32 roundings differs from RN(fp64) on ~1e-5 .. 1e-4 of its outputs, one with
+# such a mistake on 1e-3 .. 1e-1: the COUNT separates them.  The budget is never taken from the kernel: it is four times the
+# count of plain fp32 restatements of the kernel's own formulas on the CPU (gn_restatements / ln_restatements), plus 8.
+
+FLIP_FACTOR, FLIP_FLOOR, FLIP_REF_MAX = 4, 8, 1e-3
+
+
+def _round_to(ref, mant_bits, min_exp=None):
+    """fp64 -> the nearest value (ties to even) of a binary format with ``mant_bits`` explicit mantissa bits, in ONE rounding
+    (torch converts fp64 through fp32, which rounds twice)."""
+    ref = ref.double()
+    u = _ulp(ref, mant_bits, min_exp)
+    safe = torch.where(u > 0, u, torch.ones_like(u))
+    return torch.where(u > 0, torch.round(ref / safe) * safe, torch.zeros_like(ref))
+
+
+def _ordinal(codes, mag_mask):
+    """Sign-magnitude codes -> integers in value order (+0 and -0 both 0): adjacent codes differ by one."""
+    c = codes.to(torch.int32)
+    mag = c & mag_mask
+    return torch.where((c & (mag_mask + 1)) != 0, -mag, mag)
+
+
+def flip_ordinals(t, kind):
+    """The value-ordered code of every element of ``t`` rounded to ``kind``: "bf16" (t = a bf16 tensor, or fp32 / fp64 values
+    still to be rounded) or "e4m3" (t = uint8 codes, or fp32 / fp64 values already times the output scale)."""
+    t = t.detach().cpu()
+    if kind == "bf16":
+        if t.dtype == torch.float64:
+            t = _round_to(t, 7).float()                                   # exact: the value is a bf16 number
+        return _ordinal(t.to(torch.bfloat16).contiguous().view(torch.int16), 0x7fff)
+    assert kind == "e4m3", kind
+    if t.dtype == torch.float64:
+        t = _round_to(t.clamp(-448.0, 448.0), 3, min_exp=-6).float()
+    if t.dtype != torch.uint8:
+        t = t.float().clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8)
+    assert not ((t & 0x7f) == 0x7f).any(), "NaN code (0x7f)"
+    return _ordinal(t, 0x7f)
+
+
+def count_flips(t, ref64, kind):
+    return int((flip_ordinals(t, kind) != flip_ordinals(ref64.double(), kind)).sum())
+
+
+def assert_e4m3_interval(got_codes, scaled_ref, bound, what):
+    """e4m3 outputs where the a-priori bound exceeds one code spacing (a GEGLU product near zero at a large output scale:
+    the documented polynomial error times the scale spans several subnormal codes), so assert_e4m3_codes' "one code at a
+    midpoint" cannot describe it: the code must be the rounding of SOME value within ``bound`` of scaled_ref, i.e. lie
+    between RN(ref - bound) and RN(ref + bound).  Where bound is below half a code spacing this is assert_e4m3_codes' rule."""
+    ref = scaled_ref.double().cpu()
+    b = torch.as_tensor(bound, dtype=torch.float64).cpu().expand_as(ref)
+    lo, hi, have = flip_ordinals(ref - b, "e4m3"), flip_ordinals(ref + b, "e4m3"), flip_ordinals(got_codes, "e4m3")
+    bad = (have < lo) | (have > hi)
+    wide = int(((hi - lo) > 1).sum())
+    print(f"[bounds] {what}: {int(bad.sum())} of {ref.numel()} codes outside [RN(ref - bound), RN(ref + bound)]; the interval spans "
+          f"more than two codes on {wide} elements")
+    assert not bad.any(), f"{what}: {int(bad.sum())} e4m3 codes are not the rounding of any value within the bound of the fp64 value"
+    return wide
+
+
+def near_midpoint_count(scaled_ref, half_width):
+    """How many elements of the (scaled, fp64) e4m3 reference lie within ``half_width`` of a rounding midpoint: the allowance
+    of a DOCUMENTED approximation (e.g. GELU_POLY |a gate| os), computed from the reference alone."""
+    ref = scaled_ref.double().cpu().clamp(-448.0, 448.0).abs()
+    u = ulp_e4m3(ref)
+    lo = (ref / u).floor() * u
+    return int(((ref - (lo + 0.5 * u)).abs() <= torch.as_tensor(half_width, dtype=torch.float64).expand_as(ref)).sum())
+
+
+def assert_flip_budget(got, ref64, restatements, kind, what, extra=0, acc_bound=None):
+    """``got`` (bf16 tensor / e4m3 codes) against RN(ref64) -- for e4m3 ref64 is already times the output scale -- by COUNT:
+    every element that is not the correctly rounded fp64 value must be an adjacent code, and there may be at most
+    4 F_ref + 8 (+ ``extra``) of them, F_ref = the largest such count among the CPU fp32 ``restatements`` (fp32 values
+    before the output rounding).  The factor 4: the kernels add v_exp_f32, v_rcp_f32 and rsqrtf at ~1 ulp each and another
+    summation tree to the restatement's few fp32 roundings, and flips are proportional to the relative error; the 8 is the
+    Poisson floor of counts of 0 .. 10.  F_ref <= 1e-3 numel is asserted, so the budget cannot hide a failure of the
+    reference.  ``acc_bound`` (the operation's a-priori bound WITHOUT the output ulp, in ref64's units): where it reaches one
+    ulp of the output format -- a bf16 output that cancels to nearly zero, whose grid is finer than fp32 noise -- a flip need
+    not be to the adjacent code (it still counts, and the per-element gate still bounds it).  Prints and returns
+    (flips, F_ref)."""
+    want = flip_ordinals(ref64.double(), kind)
+    have = flip_ordinals(got, kind)
+    assert have.shape == want.shape, f"{what}: shape {tuple(have.shape)} vs reference {tuple(want.shape)}"
+    numel = want.numel()
+    d = (have - want).abs()
+    flips = int((d != 0).sum())
+    f_ref = max(int((flip_ordinals(r, kind) != want).sum()) for r in restatements)
+    budget = FLIP_FACTOR * f_ref + FLIP_FLOOR + int(extra)
+    print(f"[bounds] {what}: flips {flips} of {numel} (fp32 restatements F_ref {f_ref}, budget {budget}"
+          + (f", of which {int(extra)} for a documented approximation" if extra else "") + ")")
+    assert f_ref <= FLIP_REF_MAX * numel, f"{what}: the fp32 restatement itself flips {f_ref} of {numel} codes (> 1e-3)"
+    far = d > 1
+    if acc_bound is not None:
+        r = ref64.double().cpu()
+        u = ulp_bf16(r) if kind == "bf16" else ulp_e4m3(r.clamp(-448.0, 448.0))
+        far = far & (u > torch.as_tensor(acc_bound, dtype=torch.float64).cpu().expand_as(r))
+    far = int(far.sum())
+    assert far == 0, f"{what}: {far} of {numel} outputs are more than one {kind} code from the rounded fp64 value"
+    assert flips <= budget, (f"{what}: {flips} of {numel} outputs are not the rounded fp64 value; the fp32 restatements give "
+                             f"at most {f_ref}: budget {FLIP_FACTOR} x {f_ref} + {FLIP_FLOOR}"
+                             + (f" + {int(extra)}" if extra else "") + f" = {budget}")
+    return flips, f_ref
+
+
+def _silu32(y):
+    return y / (1.0 + torch.exp(-y))                                       # fp32, as silu_f (csrc/common.h) states it
+
+
+def _serial_sum(t, dim):
+    """fp32 sum along ``dim`` in index order, one addition after the other."""
+    acc = torch.zeros_like(t.select(dim, 0))
+    for i in range(t.shape[dim]):
+        acc = acc + t.select(dim, i)
+    return acc
+
+
+def gn_restatements(x, gamma, beta, groups, eps, silu, scale=None, cnt_add=0):
+    """GroupNorm(+SiLU) of x [B, HW, C] (the kernel's bf16 input as fp32) in plain fp32, in the kernels' own formulas
+    (csrc/norm.hip): one-pass variance max(E[x^2] - mean^2, 0), rstd = rsqrt(var + eps); both affine forms --
+    x sc + (beta - mean sc), sc = rstd gamma (gn_apply_kernel) and (x - mean) rstd gamma + beta (gn_unit_store) -- and
+    two summation orders: torch's pairwise sum over the group, and per-pixel sums added serially over the pixels.
+    ``scale``: the e4m3 output scale (multiplied last, as the kernels do).  ``cnt_add`` states a wrong count (tests of the
+    budget itself).  Returns the four fp32 tensors."""
+    x = x.float()
+    B, HW, C = x.shape
+    cpg = C // groups
+    xg = x.view(B, HW, groups, cpg)
+    g, bt = gamma.float().view(1, 1, groups, cpg), beta.float().view(1, 1, groups, cpg)
+    cnt = torch.tensor(float(HW * cpg + cnt_add), dtype=torch.float32)
+    eps = torch.tensor(eps, dtype=torch.float32)
+    flat = xg.permute(0, 2, 1, 3).reshape(B, groups, HW * cpg)
+    sums = [(flat.sum(-1), (flat * flat).sum(-1)),
+            (_serial_sum(xg.sum(3), 1), _serial_sum((xg * xg).sum(3), 1))]
+    out = []
+    for s, q in sums:
+        mean = (s / cnt).view(B, 1, groups, 1)
+        var = ((q / cnt).view(B, 1, groups, 1) - mean * mean).clamp(min=0.0)
+        rstd = torch.rsqrt(var + eps)
+        sc = rstd * g
+        for y in (xg * sc + (bt - mean * sc), (xg - mean) * rstd * g + bt):
+            if silu:
+                y = _silu32(y)
+            if scale is not None:
+                y = y * scale
+            out.append(y.reshape(B, HW, C))
+    return out
+
+
+def ln_restatements(x, gamma, beta, eps, scale=None):
+    """LayerNorm of x [rows, C] in plain fp32 as layernorm_kernel / layernorm_grouped_kernel state it (csrc/norm.hip):
+    two passes -- mean, then sum((x - mean)^2) -- rstd = rsqrt(q / C + eps), (x - mean) rstd gamma + beta; torch's pairwise
+    row sums and serial ones."""
+    x = x.float()
+    C = x.shape[-1]
+    eps = torch.tensor(eps, dtype=torch.float32)
+    out = []
+    for total in (lambda t: t.sum(-1, keepdim=True), lambda t: _serial_sum(t, 1).unsqueeze(-1)):
+        mean = total(x) / C
+        d = x - mean
+        rstd = torch.rsqrt(total(d * d) / C + eps)
+        y = d * rstd * gamma.float() + beta.float()
+        out.append(y * scale if scale is not None else y)
+    return out
+
+# ---------------------------------------------------------------------------------------------------------------------
 # bounds per operation
 # ---------------------------------------------------------------------------------------------------------------------
 
@@ -487,9 +656,10 @@ def heads_view(t, B, N, heads, D):
     return t.to(torch.bfloat16).float().cpu().view(B, N, heads, D).permute(0, 2, 1, 3)
 
 
-def conv_gn_elementwise(x, w, b, b2, r, gamma, beta, y, normed, what):
+def conv_gn_elementwise(x, w, b, b2, r, gamma, beta, y, normed, what, flip=()):
     """The conv output against its fp64 reference; each normalised output chained from the kernel's own stored conv output
-    (statistics of the bf16-rounded values, as the epilogue sums them)."""
+    (statistics of the bf16-rounded values, as the epilogue sums them).  ``flip``: the indices of ``normed`` that come from
+    the GroupNorm kernels' own statistics and also get the flip budget."""
     B, Cout, H, W = x.shape[0], w.shape[0], x.shape[-2], x.shape[-1]
     r64, m64 = conv3x3_nhwc_ref(x, w, b, b2, r)
     assert_elementwise(y, r64, linear_bound(r64, m64, 9 * x.shape[1] + 3), what + " conv", NHWC)
@@ -497,6 +667,9 @@ def conv_gn_elementwise(x, w, b, b2, r, gamma, beta, y, normed, what):
     n64, nb = norm_ref_bound(yk, gamma, beta, H * W * Cout // 32, 1e-5, True, groups=32)
     for i, t in enumerate(normed):
         assert_elementwise(t.view(B, H * W, Cout), n64, nb, what + f" groupnorm[{i}]", ("b", "pixel", "c"))
+        if i in flip:
+            assert_flip_budget(t.view(B, H * W, Cout), n64, gn_restatements(yk, gamma, beta, 32, 1e-5, True), "bf16",
+                               what + f" groupnorm[{i}]", acc_bound=nb - ulp_bf16(n64))
 
 
 def ln_fold_elementwise(out, h, wg, c1, c2, rs, epi, what, rows=None, idx=None):

@@ -4,16 +4,29 @@ Exact fp64 results rounded to the output format stand in for a correct kernel: t
 kinds the kernels risk (a halo corner, a wrapped halo column, a dropped bias, a split-K slab counted twice, a ragged key
 tile, a tail row from the neighbouring image) are injected into the same results: each must pass the rel-L2 gate the GPU
 tests have always used -- the gap is real -- and fail the elementwise gate.  The guard bands must catch single stray
-stores and accept an untouched buffer."""
+stores and accept an untouched buffer.
+
+The flip budget (assert_flip_budget) is checked the same way for GroupNorm: every fp32 restatement passes against the
+others, an eps 10x / 100x too large and a count off by one fail it at a small-kernel shape and at (1, 1024, 1280), for bf16
+and for e4m3 outputs -- and eps x 100 (bf16) / eps = 1e-3 (e4m3) still pass the per-element gates, which is the gap the
+budget closes.  Measured here (flips of numel, restatement form 0 as "the kernel"):
+    bf16 (1, 256, 1280) 327680:   F_ref 33;  eps x 10 1372, eps x 100 10895, cnt + 1 5516
+    bf16 (1, 1024, 1280) 1310720: F_ref 208; eps x 10 5188, eps x 100 42016, cnt + 1 6415
+    e4m3 (1, 256, 1280) x 8:      F_ref 1;   eps x 10 47,   eps = 1e-3 629,   cnt + 1 528
+    e4m3 (1, 1024, 1280) x 8:     F_ref 21;  eps x 10 230,  eps = 1e-3 2595,  cnt + 1 558
+(F_ref: 48 .. 54 with torch's pairwise sums, 206 .. 208 with serial sums over the pixels at 1024 x 40 values per group.)
+At 64 pixels x 20 channels per group the statistics term of the e4m3 gate is small enough to refuse eps = 1e-3 on 4 of 161
+differing codes; from 10240 values per group on it passes it whole."""
 import math
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.bounds import (assert_e4m3_codes, assert_elementwise, attention_ref_bound, check_guards, conv3x3_nhwc_ref,
-                          elementwise_ratio, forget_guards, gemm_bound, guarded, guarded_input, linear_bound,
-                          norm_ref_bound, ulp_e4m3)
+from tests.bounds import (U32, assert_e4m3_codes, assert_e4m3_interval, assert_elementwise, assert_flip_budget, attention_ref_bound, check_guards,
+                          conv3x3_nhwc_ref, count_flips, elementwise_ratio, flip_ordinals, forget_guards, gemm_bound,
+                          gn_restatements, guarded, guarded_input, linear_bound, ln_restatements, near_midpoint_count,
+                          norm_ref_bound, ulp_bf16, ulp_e4m3)
 from tests.util import rel_l2
 
 OLD_TOL, OLD_TOL_ATTN = 6e-3, 1e-2
@@ -195,6 +208,101 @@ def test_exact_e4m3_codes_and_a_code_off():
     alt[j] = pair[1] if int(pair[0]) == int(codes[j]) else pair[0]
     assert int(alt[j]) != int(codes[j])
     assert assert_e4m3_codes(alt, v, (frac[j] - 0.5).abs() * u[j] * 1.01, "e4m3 one code at a midpoint") == 1
+
+
+# ---- the flip budget ---------------------------------------------------------------------------------------------------
+
+FLIP_SHAPES = [(1, 256, 1280), (1, 1024, 1280)]          # gn_small_kernel's largest group (10240 values); the split path
+
+
+@pytest.fixture(scope="module", params=FLIP_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def gn_flip_case(request):
+    B, HW, C = request.param
+    g = torch.Generator().manual_seed(HW + C)
+    x = (torch.randn(B, HW, C, generator=g) * 2 + 0.5).bfloat16().float()
+    out = {}
+    for kind, silu, scale in (("bf16", True, None), ("e4m3", True, 8.0)):
+        if kind == "bf16":
+            gamma, beta = torch.randn(C, generator=g), torch.randn(C, generator=g)
+        else:
+            gamma, beta = torch.randn(C, generator=g) * 0.3 + 1, torch.randn(C, generator=g) * 0.2
+        ref, bound = norm_ref_bound(x, gamma, beta, HW * C // 32, 1e-5, silu, groups=32, out_ulp=kind == "bf16")
+        if scale:
+            ref, bound = ref * scale, bound * scale + U32 * (ref * scale).abs()
+        out[kind] = (gamma, beta, silu, scale, ref, bound, gn_restatements(x, gamma, beta, 32, 1e-5, silu, scale))
+    return x, out
+
+
+def old_gate_passes(got32, ref, bound, kind, what):
+    if kind == "bf16":
+        assert_elementwise(got32.to(torch.bfloat16), ref, bound, what)
+    else:
+        assert_e4m3_codes(got32.clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8), ref, bound, what)
+
+
+@pytest.mark.parametrize("kind", ["bf16", "e4m3"])
+def test_flip_budget_passes_every_fp32_restatement(gn_flip_case, kind):
+    x, cases = gn_flip_case
+    _, _, _, _, ref, bound, rest = cases[kind]
+    acc = bound - ulp_bf16(ref) if kind == "bf16" else None      # bf16 outputs that cancel to ~0: see assert_flip_budget
+    assert len(rest) == 4                                        # two summation orders x two affine forms
+    for i, r in enumerate(rest):
+        others = rest[:i] + rest[i + 1:]
+        got = r.to(torch.bfloat16) if kind == "bf16" else r.clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
+        flips, f_ref = assert_flip_budget(got, ref, others, kind, f"restatement {i} {kind} {tuple(x.shape)}", acc_bound=acc)
+        assert f_ref <= 2.5e-4 * ref.numel()                     # the issue's measurement: 2.3e-4 (bf16), 2e-5 (e4m3) at most
+        old_gate_passes(r, ref, bound, kind, f"restatement {i} {kind}, per element")
+
+
+@pytest.mark.parametrize("kind", ["bf16", "e4m3"])
+@pytest.mark.parametrize("mutant", ["eps x 10", "eps x 100", "cnt + 1"])
+def test_flip_budget_fails_a_wrong_eps_and_a_wrong_count(gn_flip_case, kind, mutant):
+    x, cases = gn_flip_case
+    gamma, beta, silu, scale, ref, bound, rest = cases[kind]
+    eps, cnt_add = {"eps x 10": (1e-4, 0), "eps x 100": (1e-3, 0), "cnt + 1": (1e-5, 1)}[mutant]
+    for form, bad in enumerate(gn_restatements(x, gamma, beta, 32, eps, silu, scale, cnt_add=cnt_add)):
+        f_ref = max(count_flips(r, ref, kind) for r in rest)
+        flips = count_flips(bad, ref, kind)
+        print(f"mutant {mutant} form {form} {kind} {tuple(x.shape)}: flips {flips}, F_ref {f_ref}, numel {ref.numel()}")
+        assert flips > 4 * f_ref + 8
+        got = bad.to(torch.bfloat16) if kind == "bf16" else bad.clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
+        with pytest.raises(AssertionError):
+            assert_flip_budget(got, ref, rest, kind, f"mutant {mutant} {kind}", acc_bound=bound - ulp_bf16(ref) if kind == "bf16" else None)
+        if mutant == "eps x 100":                               # = 1e-3: the gap -- today's per-element gates accept it
+            old_gate_passes(bad, ref, bound, kind, f"mutant {mutant} {kind}, per element")
+
+
+def test_flip_budget_layernorm_restatements_and_helpers():
+    g = torch.Generator().manual_seed(11)
+    rows, C = 129, 640
+    x = (torch.randn(rows, C, generator=g) * 1.5 + 0.2).bfloat16().float()
+    gamma, beta = torch.randn(C, generator=g) * 0.3 + 1, torch.randn(C, generator=g) * 0.2
+    for kind, scale in (("bf16", None), ("e4m3", 8.0)):
+        ref, _ = norm_ref_bound(x, gamma, beta, C, 1e-5, False, out_ulp=False)
+        ref = ref * scale if scale else ref
+        a, b = ln_restatements(x, gamma, beta, 1e-5, scale)
+        got = a.to(torch.bfloat16) if kind == "bf16" else a.clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
+        assert_flip_budget(got, ref, [b], kind, f"layernorm restatement {kind} {rows}x{C}")
+    # the rounding the count is taken against is ONE rounding of the fp64 value; +0 and -0 are the same code
+    v = torch.tensor([1.0 + 2.0 ** -8 + 2.0 ** -30, 1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8, -0.0, 0.0], dtype=torch.float64)
+    assert flip_ordinals(v, "bf16").tolist() == [0x3f81, 0x3f80, 0x3f82, 0, 0]
+    e = torch.tensor([17.0, 19.0, 500.0, -500.0, 2.0 ** -10, 3 * 2.0 ** -10, -0.0], dtype=torch.float64)
+    assert flip_ordinals(e, "e4m3").tolist() == [0x58, 0x5a, 0x7e, -0x7e, 0, 2, 0]
+    assert flip_ordinals(torch.tensor([0x80, 0x00, 0x7e, 0xfe], dtype=torch.uint8), "e4m3").tolist() == [0, 0, 0x7e, -0x7e]
+    with pytest.raises(AssertionError):
+        flip_ordinals(torch.tensor([0x7f], dtype=torch.uint8), "e4m3")
+    # two codes away is refused whatever the budget
+    far = torch.tensor([1.0, 2.0], dtype=torch.float64)
+    with pytest.raises(AssertionError, match="more than one"):
+        assert_flip_budget(torch.tensor([1.0, 2.03125]).bfloat16(), far, [far.float()], "bf16", "two codes off")
+    # the interval form of the e4m3 gate: any code between RN(ref - bound) and RN(ref + bound), nothing outside
+    r = torch.tensor([-0.00065, 17.3, 100.0], dtype=torch.float64)
+    inside = torch.tensor([-0.013671875, 18.0, 104.0]).to(torch.float8_e4m3fn).view(torch.uint8)
+    assert assert_e4m3_interval(inside, r, torch.tensor([0.014, 0.5, 1.0], dtype=torch.float64), "interval") == 1
+    outside = torch.tensor([-0.017578125, 18.0, 104.0]).to(torch.float8_e4m3fn).view(torch.uint8)
+    with pytest.raises(AssertionError):
+        assert_e4m3_interval(outside, r, torch.tensor([0.014, 0.5, 1.0], dtype=torch.float64), "interval, one code beyond")
+    assert near_midpoint_count(torch.tensor([17.0, 17.1, 18.1, 19.1], dtype=torch.float64), 0.15) == 3   # midpoints 17, 19
 
 
 # ---- guards -----------------------------------------------------------------------------------------------------------

@@ -20,7 +20,22 @@ points, so two correct implementations of the same scheme agree only to about th
   * HIP vs the emulation <= 1.5e-1 (sanity bound of the same order as the scheme's error);
   * free-running 4-step LCM latents vs the emulation <= 1.2e-1, cosine >= 0.99.
 Bit-level agreement of the quantisation itself is pinned elsewhere: operator tests above (kernels), 
-tests/test_host_cpu.py::test_finalize_packs_weights_on_the_host (weight codes and scales, bit for bit)."""
+tests/test_host_cpu.py::test_finalize_packs_weights_on_the_host (weight codes and scales, bit for bit).
+
+The forward-level HIP-vs-emulation gates come from the reference's own sensitivity (tests/fp8_sensitivity.py, pinned by
+tests/test_fp8_sensitivity_cpu.py): min(FWD_TOL, 1.5 D8).  Because such a gate says almost nothing about one kernel, the e4m3
+producers are pinned at operator level by COUNT (tests/bounds.py::assert_flip_budget: outputs that are not the correctly
+rounded fp64 value, budget 4 F_ref + 8 from fp32 restatements on the CPU), at the default and at calibrated scales, the
+amax reduction exactly, and the calibration tensor by tensor against a sequential reference.  Measured flips / F_ref / numel:
+  GroupNorm, default scale 8:  0 / 1 / 163840, 0 / 0 / 122880, 3 / 8 / 1310720, 0 / 0 / 92160, 1 / 1 / 40960
+  GroupNorm (2, 256, 320):     gains x 30 at 0.25: 2 / 2;  x 30 at 8 (3.8 % saturate): 2 / 2;  x 1 at 64: 0 / 1   (of 163840)
+  GroupNorm (3, 16, 1280+640): 0 / 0 in all three (of 92160; 4.1 % saturate at x 30, scale 8)
+  GroupNorm (2, 64, 640+320):  0 / 1, 0 / 2 (3.9 % saturate), 0 / 0   (of 122880)
+  LayerNorm: 0 flips and F_ref 0 in all ten cases (7.6 % / 7.8 % saturate at x 30, scale 8); quantize: exactly 0
+  GEGLU -> e4m3 (flips / F_ref / numel + the documented-polynomial allowance): os 2: 264 / 0 / 256000 + 1269,
+  1243 / 3 / 1310720 + 6407; os 0.25: 95 / 0 / 256000 + 412; os 64 (0.5 % saturate; interval gate, 6673 elements span > 2 codes): 1178 / 4 / 256000 + 4018
+No kernel needed an addition to its restatement; the GEGLU epilogue's polynomial Phi (csrc/common.h, |gelu err| <= 1.3e-5 |x|)
+is the one documented approximation: the elements it can flip are counted from the reference alone and added to the budget."""
 import dataclasses
 import math
 
@@ -31,11 +46,13 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from sonicdiffusionbayeslab_amd import _lib
+from tests.fp8_sensitivity import D8, MARGIN, T_SENS, CalibratingEmulation, checkpoint, damax, hot_keys, product_scale
 from tests.util import cosine, oracle_cfg, rel_l2, synth_inputs
-from tests.bounds import (ATOL_TINY, U32, NHWC, assert_e4m3_codes, assert_elementwise, attention_elementwise, check_guards,
-                          conv3x3_nhwc_ref, conv_gn_elementwise, device_operand, forget_guards, fp8_conv_ref,
-                          fp8_gemm_ref_bound, geglu_ref_bound, gemm_bound, grouped_softmax_elementwise, guarded,
-                          guarded_input, linear_bound, ln_fold_elementwise, ln_fold_ref_bound, norm_ref_bound, sample_rows,
+from tests.bounds import (ATOL_TINY, GELU_POLY, U32, NHWC, assert_e4m3_codes, assert_e4m3_interval, assert_elementwise, assert_flip_budget,
+                          attention_elementwise, check_guards, conv3x3_nhwc_ref, conv_gn_elementwise, count_flips,
+                          device_operand, forget_guards, fp8_conv_ref, fp8_gemm_ref_bound, geglu_ref_bound, gemm_bound,
+                          gn_restatements, grouped_softmax_elementwise, guarded, guarded_input, linear_bound,
+                          ln_fold_elementwise, ln_fold_ref_bound, ln_restatements, near_midpoint_count, norm_ref_bound, sample_rows,
                           softmax_rows_ref_bound, softmax_rows_elementwise, subpixel_ref, ulp_bf16,
                           xattn_elementwise)
 
@@ -121,10 +138,39 @@ def test_gemm_fp8(sdlib, M, N, K, bias, res):
     assert_elementwise(out, r64, linear_bound(r64, m64, k_eff), f"gemm fp8 {M}x{N}x{K}", ("row", "col"))
 
 
+def geglu_restatements(xq, xs, wq, wsc, b, os_):
+    """value * GELU(gate) * os in plain fp32 from the e4m3 operands, as the fp8 GEMM's epilogue states it
+    (csrc/gemm_conv.hip): the raw sums times wscale[n] * (1 / xscale), plus the bias; value * (gate * Phi(gate)) with the
+    exact erf; times the output scale.  Two summation orders: one fp32 matmul over K, and 64-wide K slices added serially."""
+    xq, wq = xq.float(), wq.float()
+    K = xq.shape[1]
+    whole = xq @ wq.t()
+    sliced = torch.zeros_like(whole)
+    for k in range(0, K, 64):
+        sliced = sliced + xq[:, k:k + 64] @ wq[:, k:k + 64].t()
+    out = []
+    for acc in (whole, sliced):
+        z = acc * (wsc.float() * torch.tensor(1.0 / xs, dtype=torch.float32)) + b.float()
+        a, gate = z.chunk(2, dim=-1)
+        out.append(a * (gate * (0.5 * (1.0 + torch.erf(gate * 0.70710678118654752)))) * os_)
+    return out
+
+
 @pytest.mark.parametrize("M,C,out_fp8", [(200, 320, 0), (200, 320, 1), (512, 640, 1), (96, 1280, 0)])
 def test_gemm_geglu_fp8(sdlib, M, C, out_fp8):
+    _geglu_fp8_case(sdlib, M, C, out_fp8, 2.0)
+
+
+@pytest.mark.parametrize("os_", [0.25, 64.0])
+def test_gemm_geglu_fp8_out_at_calibrated_scales(sdlib, os_):
+    """The e4m3 GEGLU output at scales a calibration gives (the default is 2): 0.25 reaches the subnormal codes, 64 saturates
+    0.5 % of the values (+-0x7e, never the NaN code)."""
+    _geglu_fp8_case(sdlib, 200, 320, 1, os_)
+
+
+def _geglu_fp8_case(sdlib, M, C, out_fp8, os_):
     g = torch.Generator().manual_seed(3 + C)
-    xs, os_ = 8.0, 2.0
+    xs = 8.0
     xc, xq = q8(torch.randn(M, C, generator=g) * xs)
     w = torch.randn(8 * C, C, generator=g) / math.sqrt(C)
     b = torch.randn(8 * C, generator=g)
@@ -150,10 +196,23 @@ def test_gemm_geglu_fp8(sdlib, M, C, out_fp8):
         got = out.cpu().view(torch.float8_e4m3fn).float() / os_
         assert torch.isfinite(got).all()
         assert rel_l2(got, q8(ref * os_)[1] / os_) < PROD_TOL
-        assert rel_l2(got, ref) < 4e-2                  # e4m3 itself: 2^-4 relative steps
+        if os_ == 2.0:
+            assert rel_l2(got, ref) < 4e-2              # e4m3 itself: 2^-4 relative steps (0.25: subnormals; 64: saturation)
         # in code units: the fp64 value times the output scale (one more fp32 rounding) decides the code
         g64, gb = geglu_ref_bound(p64[:, :H], acc[:, :H], p64[:, H:], acc[:, H:], out_ulp=False)
-        assert_e4m3_codes(out, g64 * os_, gb * os_ + U32 * (g64 * os_).abs(), f"geglu fp8 e4m3 out {M}x{H}x{C}", ("row", "col"))
+        what, gbs = f"geglu fp8 e4m3 out {M}x{H}x{C} os {os_:g}", gb * os_ + U32 * (g64 * os_).abs()
+        if os_ <= 2.0:
+            assert_e4m3_codes(out, g64 * os_, gbs, what, ("row", "col"))
+        else:
+            # at os 64 the documented polynomial error GELU_POLY |value gate| os reaches several SUBNORMAL codes where the
+            # product is nearly zero (a negative gate): no longer "one code at a midpoint", but still inside the bound
+            assert_e4m3_interval(out, g64 * os_, gbs, what)
+            assert not ((out.cpu() & 0x7f) == 0x7f).any() and ((out.cpu() & 0x7f) == 0x7e).any()       # saturates at +-448
+        # by count: the epilogue's polynomial Phi is a documented approximation (csrc/common.h: |gelu err| <= 1.3e-5 |x|), so
+        # the elements whose fp64 value lies within GELU_POLY |value gate| os of a midpoint are added to the budget
+        poly = near_midpoint_count(g64 * os_, GELU_POLY * (p64[:, :H] * p64[:, H:]).abs() * os_)
+        assert_flip_budget(out.cpu(), g64 * os_, geglu_restatements(xq, xs, wq, wsc, b, os_), "e4m3", what, extra=poly,
+                           acc_bound=gbs if os_ > 2.0 else None)
     else:
         out = guarded((M, H), torch.bfloat16)
         _lib.check(sdlib.sd_op_gemm_fp8(stream(), P(padk(xc, Kp)), Kp, P(wp), P(sp), xs, P(bp), None, 0, P(out), H, M,
@@ -211,10 +270,27 @@ def test_conv3x3_fp8(sdlib, B, H, Cin, Cout, stride, up, extras):
 @pytest.mark.parametrize("B,HW,C1,C2,silu", [(2, 256, 320, 0, 1), (2, 64, 640, 320, 1), (1, 1024, 1280, 0, 0),
                                                (3, 16, 1280, 640, 1), (2, 64, 320, 0, 1)])
 def test_groupnorm_fp8_out(sdlib, B, HW, C1, C2, silu):
+    _groupnorm_fp8_case(sdlib, B, HW, C1, C2, silu, 1.0, 8.0)
+
+
+# the scales a calibration gives: gains x 30 at 0.25; gains x 30 at 8 (about 4 % of the values saturate: +-0x7e, never 0x7f);
+# gains near 1 at 64
+CALIBRATED = [(30.0, 0.25), (30.0, 8.0), (1.0, 64.0)]
+
+
+@pytest.mark.parametrize("gain,s", CALIBRATED)
+@pytest.mark.parametrize("B,HW,C1,C2,silu", [(2, 256, 320, 0, 1),         # split path
+                                               (3, 16, 1280, 640, 1),       # gn_small_kernel, a group straddles the concat
+                                               (2, 64, 640, 320, 1)])       # concat on the split path
+def test_groupnorm_fp8_out_at_calibrated_scales(sdlib, B, HW, C1, C2, silu, gain, s):
+    _groupnorm_fp8_case(sdlib, B, HW, C1, C2, silu, gain, s)
+
+
+def _groupnorm_fp8_case(sdlib, B, HW, C1, C2, silu, gain, s):
     g = torch.Generator().manual_seed(HW + C1)
-    C, Cp, s = C1 + C2, pad128(C1 + C2), 8.0
+    C, Cp = C1 + C2, pad128(C1 + C2)
     x = (torch.randn(B, HW, C, generator=g) * 2 + 0.5).bfloat16().float()
-    gm, bt = torch.randn(C, generator=g) * 0.3 + 1, torch.randn(C, generator=g) * 0.2
+    gm, bt = (torch.randn(C, generator=g) * 0.3 + 1) * gain, torch.randn(C, generator=g) * 0.2
     ref = F.group_norm(x.permute(0, 2, 1), 32, gm, bt, 1e-5)
     if silu:
         ref = F.silu(ref)
@@ -229,16 +305,32 @@ def test_groupnorm_fp8_out(sdlib, B, HW, C1, C2, silu):
     got = o[..., :C].contiguous().view(torch.float8_e4m3fn).float() / s
     assert rel_l2(got, q8(ref * s)[1] / s) < PROD_TOL
     n64, nb = norm_ref_bound(x, gm, bt, HW * C // 32, 1e-5, silu, groups=32, out_ulp=False)
-    assert_e4m3_codes(o[..., :C].contiguous(), n64 * s, nb * s + U32 * (n64 * s).abs(), f"groupnorm fp8 e4m3 B={B} HW={HW} C={C1}+{C2}",
-                      ("b", "pixel", "c"))
+    what = f"groupnorm fp8 e4m3 B={B} HW={HW} C={C1}+{C2} gain {gain:g} scale {s:g}"
+    assert_e4m3_codes(o[..., :C].contiguous(), n64 * s, nb * s + U32 * (n64 * s).abs(), what, ("b", "pixel", "c"))
+    assert_flip_budget(o[..., :C].contiguous(), n64 * s, gn_restatements(x, gm, bt, 32, 1e-5, silu, scale=s), "e4m3", what)
+    assert not ((o & 0x7f) == 0x7f).any()                # saturation stops at +-448 = 0x7e
+    sat = float(((n64 * s).abs() >= 448.0).double().mean())
+    print(f"{what}: {sat:.2%} of the values saturate")
+    if gain == 30.0 and s == 8.0:
+        assert sat > 0.01 and ((o[..., :C] & 0x7f) == 0x7e).any()
 
 
 @pytest.mark.parametrize("rows,C", [(300, 320), (129, 640), (64, 1280), (50, 768)])
 def test_layernorm_fp8_out_and_quantize(sdlib, rows, C):
+    _layernorm_fp8_case(sdlib, rows, C, 1.0, 8.0)
+
+
+@pytest.mark.parametrize("gain,s", CALIBRATED)
+@pytest.mark.parametrize("rows,C", [(129, 640), (50, 768)])       # layernorm_grouped_kernel; one wave per row
+def test_layernorm_fp8_out_at_calibrated_scales(sdlib, rows, C, gain, s):
+    _layernorm_fp8_case(sdlib, rows, C, gain, s)
+
+
+def _layernorm_fp8_case(sdlib, rows, C, gain, s):
     g = torch.Generator().manual_seed(rows + C)
-    Cp, s = pad128(C), 8.0
+    Cp = pad128(C)
     x = (torch.randn(rows, C, generator=g) * 1.5 + 0.2).bfloat16().float()
-    gm, bt = torch.randn(C, generator=g) * 0.3 + 1, torch.randn(C, generator=g) * 0.2
+    gm, bt = (torch.randn(C, generator=g) * 0.3 + 1) * gain, torch.randn(C, generator=g) * 0.2
     ref = F.layer_norm(x, (C,), gm, bt, 1e-5)
     out = guarded((rows, Cp), torch.uint8, fill=0x7f)
     _lib.check(sdlib.sd_op_layernorm_fp8(stream(), P(x.bfloat16()), P(gm), P(bt), P(out), rows, C, Cp, 1e-5, s))
@@ -247,7 +339,14 @@ def test_layernorm_fp8_out_and_quantize(sdlib, rows, C):
     assert (o[:, C:] == 0).all()
     assert rel_l2(o[:, :C].contiguous().view(torch.float8_e4m3fn).float() / s, q8(ref * s)[1] / s) < PROD_TOL
     n64, nb = norm_ref_bound(x, gm, bt, C, 1e-5, False, out_ulp=False)
-    assert_e4m3_codes(o[:, :C].contiguous(), n64 * s, nb * s + U32 * (n64 * s).abs(), f"layernorm fp8 e4m3 {rows}x{C}", ("row", "c"))
+    what = f"layernorm fp8 e4m3 {rows}x{C} gain {gain:g} scale {s:g}"
+    assert_e4m3_codes(o[:, :C].contiguous(), n64 * s, nb * s + U32 * (n64 * s).abs(), what, ("row", "c"))
+    assert_flip_budget(o[:, :C].contiguous(), n64 * s, ln_restatements(x, gm, bt, 1e-5, scale=s), "e4m3", what)
+    assert not ((o & 0x7f) == 0x7f).any()
+    sat = float(((n64 * s).abs() >= 448.0).double().mean())
+    print(f"{what}: {sat:.2%} of the values saturate")
+    if gain == 30.0 and s == 8.0:
+        assert sat > 0.01 and ((o[:, :C] & 0x7f) == 0x7e).any()
     # plain conversion: bit-exact against torch's e4m3 rounding (same format, same nearest-even rule, saturation)
     big = x * 100.0                                   # exercises the +-448 saturation
     out2 = guarded((rows, Cp), torch.uint8, fill=0x7f)
@@ -258,6 +357,50 @@ def test_layernorm_fp8_out_and_quantize(sdlib, rows, C):
     same = (got == want) | ((got & 0x7f) == 0) & ((want & 0x7f) == 0)      # +0 / -0
     assert same.all() and (out2.cpu()[:, C:] == 0).all()
     assert assert_e4m3_codes(got.contiguous(), big.bfloat16().double(), 0.0, f"quantize fp8 {rows}x{C}", ("row", "c")) == 0
+    assert count_flips(got.contiguous(), big.bfloat16().double(), "e4m3") == 0        # a conversion: exactly no flips
+
+
+def _amax_cases():
+    """(name, bytes): amax_e4m3_kernel reads 16-byte granules, 256 per block and at most 2048 blocks per pass."""
+    import numpy as np
+    rng = np.random.default_rng(7)
+    low = lambda n: rng.integers(0, 0x30, n, dtype=np.uint8) | (rng.integers(0, 2, n, dtype=np.uint8) << 7)   # |code| < 0x30, either sign
+    cases = [("16 bytes", low(16))]
+    big = 2048 * 256 + 1                                  # granules: one more than the grid covers in one pass
+    t = low(16 * big); t[-5] = 0x61
+    cases.append(("grid-stride tail granule", t))
+    t = low(16 * big); t[0] = 0x62
+    cases.append(("maximum in the first byte", t))
+    t = low(16 * big); t[-1] = 0x63
+    cases.append(("maximum in the last byte", t))
+    for k in range(16):
+        t = low(16 * 1000); t[16 * 777 + k] = 0x40 + k
+        cases.append((f"maximum in byte {k} of a granule", t))
+    t = low(16 * 1000); t[4321] = 0x80 | 0x6a
+    cases.append(("maximum carried by a negative value", t))
+    cases.append(("all zero", np.zeros(16 * 1000, dtype=np.uint8)))
+    cases.append(("all negative zero", np.full(16 * 300, 0x80, dtype=np.uint8)))
+    t = low(16 * 1000); t[9999] = 0x7f
+    cases.append(("a NaN code 0x7f", t))
+    t = low(16 * 1000); t[15] = 0xff
+    cases.append(("a negative NaN code 0xff", t))
+    return cases
+
+
+def test_amax_e4m3_is_the_largest_magnitude_code(sdlib):
+    """amax_e4m3_kernel (csrc/norm.hip) through sd_op_amax_e4m3, exactly against max(byte & 0x7f): the measurement behind
+    sd_unet_calibrate_fp8, which until here was only ever compared with itself."""
+    import numpy as np
+    word = torch.full((1,), 0x5a5a5a5a, dtype=torch.int32, device="cuda")       # the operator zeroes it
+    for name, codes in _amax_cases():
+        want = int((codes & 0x7f).max())
+        x = guarded_input(torch.from_numpy(codes).view(-1, 16), torch.uint8, label=name)     # rows = granules, 0x7f-poisoned guards
+        _lib.check(sdlib.sd_op_amax_e4m3(stream(), x.data_ptr(), codes.size, word.data_ptr()))
+        torch.cuda.synchronize()
+        got = int(word.item())
+        print(f"amax e4m3, {name} ({codes.size} bytes): 0x{got:02x}")
+        assert got == want, (name, hex(got), hex(want))
+    assert sdlib.sd_op_amax_e4m3(stream(), x.data_ptr(), 24, word.data_ptr()) != 0          # not whole granules: refused
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -291,7 +434,10 @@ def test_unet_forward_fp8_matches_emulating_oracle(small_fp8, t):
     print(f"fp8 forward t={t}: vs emulating oracle {e_q:.3e} (cos {cosine(eps, ref_q):.5f}); vs unquantised oracle "
           f"{e_f:.3e}; oracle fp8-vs-fp32 {rel_l2(ref_q, ref):.3e}")
     assert torch.isfinite(eps).all()
-    assert e_q < FWD_TOL and cosine(eps, ref) > 0.99
+    # two correct implementations of the scheme agree to about D8, the emulating oracle's own movement under a 2^-8
+    # perturbation of its quantised tensors (tests/fp8_sensitivity.py: 7.58e-2 -> gate 1.14e-1; HIP measures 1.089e-1 at
+    # t = 981 and 9.21e-2 at t = 21)
+    assert e_q < min(FWD_TOL, 1.5 * D8["ordinary"]) and cosine(eps, ref) > 0.99
     assert e_f < FWD_EXCESS * rel_l2(ref_q, ref) + 1e-2
 
 
@@ -336,11 +482,9 @@ def test_fp8_calibration_positions_the_range(small_fp8):
     from oracle.unet import unet_forward
     from sonicdiffusionbayeslab_amd.unet import HipUNet2DConditionModel
     cfg, sd0, _ = small_fp8
-    sd = dict(sd0)
-    hot = [k for k in sd if k.endswith(("resnets.0.norm2.weight", "transformer_blocks.0.norm3.weight")) and "down_blocks.1" in k]
+    hot = hot_keys(sd0)
     assert len(hot) >= 2
-    for k in hot:
-        sd[k] = (sd[k] * 30.0).to(torch.bfloat16).float()
+    sd = checkpoint(sd0, "hot")                         # those gains times 30
     net = HipUNet2DConditionModel(cfg, sd, weight_dtype="fp8")
     lat, pe, ne = synth_inputs(cfg, 1)
     ctx = torch.cat([ne, pe])
@@ -355,8 +499,8 @@ def test_fp8_calibration_positions_the_range(small_fp8):
     full = net.fp8_scales(with_amax=True)
     assert set(scales) == set(defaults) and len(scales) >= 60
     for name, (s, amax) in full.items():
-        assert amax > 0 and s * amax <= 448.0 / 2.0 * 1.0001 and s * amax > 448.0 / 8.0, (name, s, amax)   # margin 2, power-of-two floor
-        assert s == 2.0 ** round(math.log2(s))
+        assert amax > 0 and s == product_scale(amax, 2.0), (name, s, amax)     # margin 2, power-of-two floor: exactly the rule
+        assert s == 2.0 ** round(math.log2(s)) and 448.0 / 8.0 < s * amax <= 448.0 / 2.0 * 1.0001
     hot_names = [k[: -len(".weight")] for k in hot]
     assert all(full[n][1] > 56.0 and full[n][0] < 8.0 for n in hot_names), [full[n] for n in hot_names]
     net.set_context(ctx.cuda())
@@ -367,11 +511,14 @@ def test_fp8_calibration_positions_the_range(small_fp8):
     print(f"fp8 calibration: vs unquantised oracle {e_before:.3e} with the default scales (hot layers saturate) -> {e_after:.3e} "
           f"calibrated; emulated calibrated scheme {scheme:.3e}; HIP vs emulation {rel_l2(after, ref_q):.3e}")
     assert e_after < 0.5 * e_before
-    # HIP vs the emulating oracle under 30x gains: both quantise the same way, but a last-bit difference in a GroupNorm variance
-    # flips e4m3 ties in the hot layers and the comparison moves by percent: 1.462e-1 / 1.482e-1 / 1.513e-1 on three builds of
-    # round 5 that differ only in how hipcc contracts the variance sum (packed / scalar fp32, helper inlining) -- the scheme's own
-    # distance from the unquantised oracle is 1.63e-1.  Gate at that distance, not at the ordinary forward's FWD_TOL.
-    assert e_after < FWD_EXCESS * scheme + 1e-2 and rel_l2(after, ref_q) < max(FWD_TOL, scheme)
+    # HIP vs the emulating oracle under 30x gains, from the reference's own sensitivity (tests/fp8_sensitivity.py, t = 499,
+    # rel-L2 of the emulating oracle's output when every tensor it quantises is first multiplied by 1 + d):
+    #     checkpoint        scheme (vs unquantised)   |d| <= 2^-23     |d| <= 2^-8
+    #     ordinary          0.0950                    0.0540, 0.0545   0.0758, 0.0771
+    #     30x gains         0.1603                    0.0766, 0.0975   0.1422, 0.1442
+    # one fp32 ulp already moves the output by half the scheme's own error, so any two implementations differ by about D8:
+    # gate at the scheme's distance (this checkpoint's 1.5 D8 = 0.213 lies above it), not at the ordinary forward's FWD_TOL.
+    assert e_after < FWD_EXCESS * scheme + 1e-2 and rel_l2(after, ref_q) < min(max(FWD_TOL, scheme), 1.5 * D8["hot"])
     # a saved calibration restores bit-identical behaviour on a fresh handle
     net2 = HipUNet2DConditionModel(cfg, sd, weight_dtype="fp8")
     net2.set_context(ctx.cuda())
@@ -379,3 +526,58 @@ def test_fp8_calibration_positions_the_range(small_fp8):
     net2.set_fp8_scales(scales)
     net2.set_context(ctx.cuda())
     assert torch.equal(net2.forward_latents(lat.cuda(), 2, t), after)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# calibration against the oracle
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module", params=["ordinary", "hot"])
+def calibration_oracle(request, small_fp8):
+    """The sequential reference of sd_unet_calibrate_fp8 (tests/fp8_sensitivity.py::CalibratingEmulation) at t = 499, margin 2,
+    and its own sensitivity D: twice the largest relative amax change of any tensor when the same reference runs with every
+    quantised tensor perturbed by 2^-8 (seeds 0 .. 2)."""
+    from oracle.fp8 import Fp8Emulation
+    from oracle.unet import unet_forward
+    cfg, sd0, _ = small_fp8
+    sd = checkpoint(sd0, request.param)
+    lat, pe, ne = synth_inputs(cfg, 1)
+    ctx = torch.cat([ne, pe])
+    plain = Fp8Emulation(sd)
+
+    def run(**kw):
+        fq = CalibratingEmulation(sd, MARGIN, share=plain, **kw)
+        with torch.no_grad():
+            unet_forward(sd, oracle_cfg(cfg), torch.cat([lat, lat]), T_SENS, ctx, fq=fq)
+        return fq
+    seq = run()
+    D = 2.0 * max(damax(seq.amax, run(amp=2.0 ** -8, seed=seed).amax) for seed in range(3))
+    return request.param, cfg, sd, lat, ctx, seq, D
+
+
+def test_fp8_calibration_amax_and_scales_match_the_sequential_oracle(calibration_oracle):
+    """``sd_unet_calibrate_fp8`` against the reference, tensor by tensor: the same tensor names; every scale exactly the
+    product's rule (largest power of two <= 448 / (margin amax)) applied to the product's own amax; every amax within
+    2^-4 + D of the reference's -- 2^-4 is the e4m3 half-step of the probe read-back (the amax is read from e4m3 codes),
+    D the reference's own sensitivity (calibration_oracle).
+    Measured (108 tensors each; D is a maximum over tensors and seeds and moves with the host's fp32 summation order:
+    0.168 .. 0.212 and 0.239 .. 0.313 on two hosts): ordinary checkpoint D = 0.1676, worst |amax_hip / amax_ref - 1| = 0.1456
+    (up_blocks.1.attentions.2.transformer_blocks.0.norm3) against the bound 0.2301, 106 of 108 scales equal the reference's;
+    30x-gain checkpoint D = 0.2389, worst 0.1157 (up_blocks.1.attentions.2.transformer_blocks.0.ff.net.0) against 0.3014,
+    107 of 108 scales equal."""
+    from sonicdiffusionbayeslab_amd.unet import HipUNet2DConditionModel
+    which, cfg, sd, lat, ctx, seq, D = calibration_oracle
+    net = HipUNet2DConditionModel(cfg, sd, weight_dtype="fp8")
+    net.set_context(ctx.cuda())
+    net.calibrate_fp8(lat.cuda(), 2, [T_SENS], margin=MARGIN)
+    full = net.fp8_scales(with_amax=True)
+    assert set(full) == set(seq.amax), sorted(set(full) ^ set(seq.amax))                    # (a)
+    worst, at = 0.0, None
+    for name, (s, amax) in full.items():
+        assert amax > 0 and s == product_scale(amax, MARGIN), (name, s, amax)               # (b)
+        r = abs(amax / seq.amax[name] - 1.0)
+        if r > worst:
+            worst, at = r, name
+    agree = sum(full[n][0] == seq.scales[n] for n in full)
+    print(f"fp8 calibration vs the sequential oracle, {which} checkpoint: {len(full)} tensors, D {D:.4f}, worst |amax_hip / amax_ref - 1| "
+          f"{worst:.4f} at {at} (bound {2.0 ** -4 + D:.4f}); {agree} scales equal the reference's")
+    assert worst <= 2.0 ** -4 + D, (at, full[at], seq.amax[at])                             # (c)

@@ -79,6 +79,15 @@ def test_abi_library_exports_every_declared_symbol():
     assert lib.sd_abi_version() == 3
 
 
+def test_amax_operator_symbol_is_exported_and_the_abi_version_stays():
+    """sd_op_amax_e4m3 (the measurement of sd_unet_calibrate_fp8 as an operator, tests/test_fp8_gpu.py) is additive."""
+    lib = _lib.load()
+    n = "sd_op_amax_e4m3"
+    assert hasattr(lib, n), n
+    assert n in _lib._SIGS and n in _lib.declared_symbols(), n
+    assert lib.sd_abi_version() == 3
+
+
 def test_param_enumeration_matches_library():
     from sonicdiffusionbayeslab_amd.unet import _c_config
     lib = _lib.load()

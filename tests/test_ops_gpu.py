@@ -12,9 +12,9 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from sonicdiffusionbayeslab_amd import _lib
-from tests.bounds import (ATOL_TINY, U32, assert_elementwise, attention_ref_bound, check_guards, conv3x3_nhwc_ref,
-                          forget_guards, gemm_bound, gemm_ref, geglu_ref_bound, guarded, guarded_input, linear_bound,
-                          ln_fold_ref_bound, norm_ref_bound, softmax_rows_ref_bound, subpixel_ref, ulp_bf16,
+from tests.bounds import (ATOL_TINY, U32, assert_elementwise, assert_flip_budget, attention_ref_bound, check_guards,
+                          conv3x3_nhwc_ref, forget_guards, gemm_bound, gemm_ref, geglu_ref_bound, gn_restatements, guarded,
+                          guarded_input, linear_bound, ln_fold_ref_bound, ln_restatements, norm_ref_bound, softmax_rows_ref_bound, subpixel_ref, ulp_bf16,
                           attention_elementwise, conv_gn_elementwise, grouped_softmax_elementwise, ln_fold_elementwise,
                           sample_rows, xattn_elementwise, xattn_norm2_elementwise)
 
@@ -267,7 +267,8 @@ def test_conv3x3_upsample_as_four_subpixel_convs(sdlib, B, H, Cin, Cout):
                                                                    # (8x8 inputs carry no producer statistics: 64-pixel phases)
 def test_conv3x3_upsample_subpixel_groupnorm_producer_statistics(sdlib, B, H, Cin, Cout):
     """Upsample2D -> the next resnet's GroupNorm with the statistics from the conv epilogue: 64-row blocks in the row order
-    (sample, phase, low-res pixel), whichever kernel ran the conv."""
+    (sample, phase, low-res pixel), whichever kernel ran the conv.  The "own statistics" leg also gets the flip budget;
+    measured flips / F_ref / numel: 363 / 1325 / 10485760, 340 / 2326 / 10485760, 33 / 102 / 655360."""
     g = torch.Generator().manual_seed(H + Cin + Cout + 1)
     x = r16(torch.randn(B, Cin, H, H, generator=g))
     w = r16(torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(9 * Cin))
@@ -298,6 +299,8 @@ def test_conv3x3_upsample_subpixel_groupnorm_producer_statistics(sdlib, B, H, Ci
     for t, name in ((yn, "producer statistics"), (own, "own statistics")):
         assert_elementwise(t.view(B, 4 * H * H, Cout), n64, nb, f"groupnorm after subpixel conv ({name}) B={B} H={H} C={Cout}",
                            ("b", "pixel", "c"))
+    assert_flip_budget(own.view(B, 4 * H * H, Cout), n64, gn_restatements(yk, gamma, beta, 32, 1e-5, True), "bf16",
+                       f"groupnorm after subpixel conv (own statistics) B={B} H={H} C={Cout}", acc_bound=nb - ulp_bf16(n64))
 
 
 @pytest.mark.parametrize("B,HW,C1,C2,silu,eps", [
@@ -307,8 +310,20 @@ def test_conv3x3_upsample_subpixel_groupnorm_producer_statistics(sdlib, B, H, Ci
     (3, 16, 1280, 640, 1, 1e-5),    # single-launch small-image kernel, a group straddles the concat boundary
     (2, 64, 1280, 1280, 1, 1e-5),   # small-image kernel at the 8x8 level (80 channels per group)
     (5, 64, 1280, 0, 0, 1e-6),      # ... 40 channels per group, no SiLU
+    # the VAE's channel counts (128 / 256 / 512 = 4 / 8 / 16 channels per group, eps 1e-6)
+    (1, 4096, 128, 0, 1, 1e-6),     # split path, 4 channels per group: every 8-channel chunk straddles two groups
+    (2, 1000, 128, 0, 0, 1e-6),     # ... with a ragged pixel split
+    (2, 64, 128, 0, 1, 1e-6),       # gn_small_kernel with one 4-channel unit per pixel
+    (1, 1024, 256, 0, 1, 1e-6),     # 8 channels per group
+    (2, 256, 512, 0, 1, 1e-6),      # gn_small_kernel, 16 channels per group: the VAE mid block at a 16x16 latent
+    (1, 4096, 512, 0, 0, 1e-6),     # split path, 16 channels per group: the attention's GroupNorm
 ])
 def test_groupnorm(sdlib, B, HW, C1, C2, silu, eps):
+    """Against torch, per element (norm_ref_bound), and by count (assert_flip_budget: outputs that are not the correctly
+    rounded fp64 value, against four fp32 restatements of the kernels' formulas on the CPU, budget 4 F_ref + 8).
+    Measured, flips / F_ref / numel in the order of the cases: 2 / 9 / 163840, 1 / 3 / 122880, 97 / 392 / 2621440,
+    2 / 3 / 92160, 17 / 21 / 327680, 15 / 31 / 409600; the VAE's widths: 12 / 125 / 524288, 10 / 51 / 256000, 0 / 0 / 16384,
+    11 / 30 / 262144, 9 / 12 / 262144, 74 / 493 / 2097152.  No kernel needed an addition to its restatement."""
     g = torch.Generator().manual_seed(HW + C1)
     C = C1 + C2
     x = r16(torch.randn(B, HW, C, generator=g) * 2 + 0.5)
@@ -324,8 +339,10 @@ def test_groupnorm(sdlib, B, HW, C1, C2, silu, eps):
     torch.cuda.synchronize()
     check_guards()
     assert rel_l2(out, ref) < TOL
-    assert_elementwise(out, *norm_ref_bound(x, gamma, beta, HW * C // 32, eps, silu, groups=32),
-                       f"groupnorm B={B} HW={HW} C={C1}+{C2}", ("b", "pixel", "c"))
+    n64, nb = norm_ref_bound(x, gamma, beta, HW * C // 32, eps, silu, groups=32)
+    assert_elementwise(out, n64, nb, f"groupnorm B={B} HW={HW} C={C1}+{C2}", ("b", "pixel", "c"))
+    assert_flip_budget(out, n64, gn_restatements(x, gamma, beta, 32, eps, silu), "bf16", f"groupnorm B={B} HW={HW} C={C1}+{C2}",
+                       acc_bound=nb - ulp_bf16(n64))
 
 
 @pytest.mark.parametrize("B,H,Cin,Cout", [
@@ -335,7 +352,9 @@ def test_groupnorm(sdlib, B, HW, C1, C2, silu, eps):
     (1, 32, 64, 256),      # 8 channels per group, Cout tail in the second channel tile
 ])
 def test_conv3x3_groupnorm_producer_statistics(sdlib, B, H, Cin, Cout):
-    """The plan's conv -> GroupNorm pair: statistics come from the conv epilogue (sums of the bf16-rounded outputs)."""
+    """The plan's conv -> GroupNorm pair: statistics come from the conv epilogue (sums of the bf16-rounded outputs).
+    The "own statistics" leg also gets the flip budget; measured flips / F_ref / numel: 128 / 733 / 2621440, 63 / 251 / 1966080,
+    43 / 97 / 1310720, 0 / 22 / 262144."""
     g = torch.Generator().manual_seed(H + Cin + Cout)
     x = r16(torch.randn(B, Cin, H, H, generator=g))
     w = r16(torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(9 * Cin))
@@ -361,7 +380,7 @@ def test_conv3x3_groupnorm_producer_statistics(sdlib, B, H, Cin, Cout):
     torch.cuda.synchronize()
     check_guards()
     assert rel_l2(yn, own) < 2e-3
-    conv_gn_elementwise(x, w, b, b2, r, gamma, beta, y, (yn, own), f"conv3x3+gn B={B} H={H} {Cin}->{Cout}")
+    conv_gn_elementwise(x, w, b, b2, r, gamma, beta, y, (yn, own), f"conv3x3+gn B={B} H={H} {Cin}->{Cout}", flip=(1,))
 
 
 
@@ -657,6 +676,8 @@ def test_layernorm_fold_gemms_are_run_to_run_deterministic_at_bench_shapes(sdlib
 
 @pytest.mark.parametrize("rows,C", [(300, 320), (77, 640), (1024, 1280)])
 def test_layernorm(sdlib, rows, C):
+    """Per element and by count (assert_flip_budget against the two-pass fp32 restatements of the kernels' formula); measured
+    flips / F_ref / numel: 3 / 4 / 96000, 1 / 5 / 49280, 47 / 153 / 1310720."""
     g = torch.Generator().manual_seed(rows)
     x = r16(torch.randn(rows, C, generator=g) * 3 + 1)
     gamma, beta = torch.randn(C, generator=g), torch.randn(C, generator=g)
@@ -667,7 +688,9 @@ def test_layernorm(sdlib, rows, C):
     torch.cuda.synchronize()
     check_guards()
     assert rel_l2(out, ref) < TOL
-    assert_elementwise(out, *norm_ref_bound(x, gamma, beta, C, 1e-5, False), f"layernorm {rows}x{C}", ("row", "c"))
+    n64, nb = norm_ref_bound(x, gamma, beta, C, 1e-5, False)
+    assert_elementwise(out, n64, nb, f"layernorm {rows}x{C}", ("row", "c"))
+    assert_flip_budget(out, n64, ln_restatements(x, gamma, beta, 1e-5), "bf16", f"layernorm {rows}x{C}", acc_bound=nb - ulp_bf16(n64))
 
 
 @pytest.mark.parametrize("B,heads,Nq,Nk,D,spike", [
