@@ -6,7 +6,7 @@ TEST INFRASTRUCTURE (see oracle/__init__.py) -- parity unpinned; the reference i
 (``configs/consistency_model_config.yaml:1-34``, ``src/experiments/consistency_model.py:9-52`` run fp16): what is
 emulated here is this build's own quantisation scheme, so that its error is separated from kernel error.
 
-Scheme (identical in csrc/unet.hip):
+Scheme (identical in csrc/pack.hip for the weights, csrc/plan.hip for the activation tensors):
   * weights of the resnet 3x3 convs, proj_in, attn1 to_q/to_k/to_v, ff.net.0.proj and ff.net.2: OCP e4m3fn, one
     fp32 scale per OUTPUT channel (row): scale = amax / 448, w_q = rne(w / scale), saturating;
   * the activations entering those contractions -- GroupNorm(+SiLU) and LayerNorm outputs (scale ``s_norm``) and the

@@ -23,8 +23,8 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libsdhip.so")
 ABLATE_LIB_PATH = os.path.join(LIB_DIR, "libsdhip_ablate.so")
 ABLATE_SOURCES = ("gemm_conv.hip", "conv_halo.hip")     # the translation units with SD_ABLATE code
-SOURCES = ["gemm_conv.hip", "gemm_lean.hip", "conv_halo.hip", "norm.hip", "attention.hip", "xattn.hip", "small.hip", "clip.hip", "vit.hip", "inception.hip", "unet.hip"]
-HEADERS = ["common.h", "kernels.h", os.path.join("..", "..", "include", "sd_hip.h")]
+SOURCES = ["gemm_conv.hip", "gemm_lean.hip", "conv_halo.hip", "norm.hip", "attention.hip", "xattn.hip", "small.hip", "clip.hip", "vit.hip", "inception.hip", "unet.hip", "pack.hip", "plan.hip", "ops.hip"]
+HEADERS = ["common.h", "kernels.h", "model.h",os.path.join("..", "..", "include", "sd_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # No packed fp32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) in these units: hipcc broadcasts a scalar
 # into a packed operand with op_sel, and the form that feeds a LO lane from the HI dword of a register pair loses that operand

@@ -207,7 +207,7 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// host-side error plumbing (defined in unet.hip)
+// host-side error plumbing (defined in unet.hip; the host units pack.hip, plan.hip and ops.hip use it too)
 extern "C" const char* sd_last_error(void);
 void sd_set_error(const char* fmt, ...);
 #define SD_CHECK_HIP(expr)                                                              \

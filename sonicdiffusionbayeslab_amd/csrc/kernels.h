@@ -1,4 +1,4 @@
-// Internal launcher interface shared by the kernel translation units and unet.hip.
+// Internal launcher interface shared by the kernel translation units and the host units (unet.hip, plan.hip, ops.hip).
 // Every launcher validates its operand shapes on the host BEFORE launching (a faulting kernel
 // can take the whole GPU host down), enqueues on the caller's stream only, never synchronises,
 // and returns 0 / negative with the message available through sd_last_error().

@@ -1,0 +1,249 @@
+// libsdhip host side, internal: the data model shared by the host units -- pack.hip (parameter enumeration, weight packer),
+// plan.hip (plan builder, workspace assignment), unet.hip (run_op, the handle ABI) and ops.hip (operator entry points) -- and
+// the few functions that cross between them.
+#pragma once
+#include "../../include/sd_hip.h"
+#include "common.h"
+#include "kernels.h"
+
+#include <string.h>
+#include <sys/mman.h>
+
+#include <algorithm>
+#include <map>
+#include <new>
+#include <string>
+#include <tuple>
+#include <unordered_map>
+#include <vector>
+
+namespace sdhip {
+
+constexpr size_t NOFF = (size_t)-1;
+constexpr int T_LATENTS = -2, T_EPS = -3;
+
+struct ParamSpec {
+    std::string name;
+    std::vector<long long> shape;
+    std::vector<float> data;
+    bool loaded = false;
+    long long numel() const {
+        long long n = 1;
+        for (auto s : shape) n *= s;
+        return n;
+    }
+};
+
+struct Wrap {  // one DeepCache-wrapped module enclosing an op
+    int type;  // 0 down, 1 mid, 2 up
+    int block_i, layer_i;
+};
+
+enum OpKind { OP_SINUSOID, OP_GEMV, OP_CONV_IN, OP_GN, OP_CONV3, OP_GEMM, OP_LN, OP_ATTN, OP_CONV_OUT, OP_SOFTMAX, OP_PQCONV,
+              OP_CLIP_EMBED, OP_CLIP_ATTN, OP_QGELU, OP_TO_F32, OP_XATTN, OP_REPLICATE,
+              OP_VIT_PREP, OP_VIT_EMBED, OP_VIT_ATTN, OP_POOL, OP_CONV_IN_IMG, OP_ENC_OUT };
+
+constexpr int REP_TEXT_POOLED = 2;       // Plan::rep of a CLIP text handle's sd_clip_text_embeds plan
+
+struct Op {
+    int kind = 0;
+    int x1 = -1, x2 = -1, r = -1, out = -1, aux = -1, b2t = -1;
+    size_t w = NOFF, b = NOFF, g = NOFF, be = NOFF;
+    long b2idx = 0;
+    int M = 0, N = 0, K = 0, K1 = 0, epi = 0;
+    int B = 0, Hin = 0, Win = 0, Cin = 0, Hout = 0, Wout = 0, stride = 1, up = 0;
+    int C1 = 0, C2 = 0, HW = 0, silu = 0, nsplit = 0;
+    float eps = 0.f;
+    int heads = 0, D = 0, Nq = 0, Nk = 0;
+    long ldq = 0, ldk = 0, ldv = 0, ldo = 0, qoff = 0, koff = 0, voff = 0;
+    int silu_in = 0, splitk = 1;
+    int pool_by_ids = 0;          // OP_POOL: the row is the EOS position of the call's token ids (0: row 0, the class token)
+    // split-K producer + single-launch GroupNorm as ONE reduce (fuse_deferred_reduce): the producer (CONV3 / GEMM) sets `defer`
+    // and launches no splitk_reduce_kernel; the GroupNorm reads the producer's slabs (slab_t, slab_k of them) with its bias /
+    // time-embedding row / residual and writes the producer's output tensor on the way (GroupNormArgs::slab)
+    int defer = 0, slab_t = -1, slab_k = 0, slab_r = -1, slab_b2t = -1;
+    size_t slab_b = NOFF;
+    long slab_b2idx = 0;
+    // generalised GEMM operands (VAE attention): W operand taken from an activation tensor, X taken
+    // from the weight blob, element offsets into tensors and explicit row strides
+    int wt = -1;
+    size_t wx = NOFF;
+    long xoff = 0, woff_el = 0, coff = 0, ldx_o = 0, ldw_o = 0, ldc_o = 0;
+    float scale = 0.f;
+    long wbs = 0;                 // per-sample W: batch stride (elements), rows per sample, softmax width
+    int rpb = 0, sm_valid = 0;
+    // fp8-e4m3 operands (SD_DTYPE_FP8_E4M3): this op's X and W are e4m3 (K / Cin padded to 128), wsc = offset of
+    // the per-output-channel weight scales, xs = activation scale of its input; out_fp8: the op WRITES e4m3
+    // (rows of Cpad bytes) with scale os.  Kalg: unpadded contraction length (algorithmic FLOPs).
+    int dt = 0, out_fp8 = 0, Cpad = 0, Kalg = 0;
+    int sname = -1;                   // fp8 producer: index into sd_unet::act_names of the tensor it writes (its scale = os)
+    // GroupNorm statistics from the producer's epilogue: `stats` = tensor this op writes ([M/64][N][2] fp32),
+    // s1 / s2 = the statistics tensors of a GroupNorm's sources (it then skips its statistics pass)
+    int stats = -1, s1 = -1, s2 = -1;
+    // LayerNorm fold: rs = row partials this op writes ([np][M][2] fp32); lnrs / lnnp / c1 = partials and column sums
+    // this GEMM normalises with (its x1 is the un-normalised tensor, its weights carry gamma, its bias W beta + b)
+    int subpix = 0;                   // CONV3 with up: four 2x2 convs on the low-res input (GemmArgs::subpix)
+    int asym = 0;                     // CONV3 stride 2 padded right / bottom only (GemmArgs::asym: the VAE encoder's downsamplers)
+    int hm = 0;                       // GEMM: q|k|v with head-major K / V (HW = tokens per sample); ATTN: K / V are head-major
+    int qps = 0;                      // ATTN: Q arrives multiplied by scale * log2 e (folded into W_q at pack time)
+    int rs = -1, lnrs = -1, lnnp = 0;
+    size_t c1 = NOFF;
+    size_t wsc = NOFF;
+    float xs = 1.f, os = 1.f;
+    // CONV3 with the resnet's 1x1 shortcut folded in (GemmArgs::Xs1 ...): shortcut sources [scx1 | scx2] of scc1 + scc2
+    // channels, scw = the packed conv_shortcut weight; `b` is then the summed bias vector and Kalg counts the shortcut channels
+    int scx1 = -1, scx2 = -1, scc1 = 0, scc2 = 0;
+    size_t scw = NOFF;
+    int nwrap = 0;
+    Wrap wraps[3];
+};
+
+// Host staging buffer of the packed weights: ONE anonymous mapping reserved up front and populated by the kernel in bulk
+// (MAP_POPULATE, transparent huge pages where available).  A std::vector paid ~20 us per 4 KiB first-touch fault here:
+// 11-19 s of a 22 s finalize for the 2.3 GB UNet blob.
+struct HostBlob {
+    unsigned char* p = nullptr;
+    size_t n = 0, cap = 0;
+    unsigned char* data() { return p; }
+    const unsigned char* data() const { return p; }
+    size_t size() const { return n; }
+    bool empty() const { return n == 0; }
+    bool reserve(size_t bytes) {
+        if (bytes <= cap) return true;
+        void* q = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_POPULATE, -1, 0);
+        if (q == MAP_FAILED) return false;
+        (void)madvise(q, bytes, MADV_HUGEPAGE);
+        if (p) { memcpy(q, p, n); munmap(p, cap); }
+        p = (unsigned char*)q; cap = bytes;
+        return true;
+    }
+    void resize(size_t bytes) {             // (new bytes are zero: fresh anonymous pages)
+        // a failed mapping surfaces as an error of sd_unet_finalize (which catches this), never as an abort of the host process
+        if (bytes > cap && !reserve(std::max(bytes, cap * 2))) throw std::bad_alloc();
+        n = bytes;
+    }
+    void release() { if (p) munmap(p, cap); p = nullptr; n = cap = 0; }
+    ~HostBlob() { release(); }
+    HostBlob() = default;
+    HostBlob(const HostBlob&) = delete;
+    HostBlob& operator=(const HostBlob&) = delete;
+};
+
+struct Tn {
+    size_t bytes = 0;
+    int def = -1, last = -1;
+    bool persistent = false;
+    bool ctx = false;            // written by sd_unet_set_context: same offset in every plan variant of a (batch, branch)
+    size_t off = NOFF;
+};
+
+struct Plan {
+    int UB = 0, branch = -1;
+    // UNet (kind 0): 2 = the prompt-independent prefix runs once per latent (CFG pair), see Builder::build.  CLIP text
+    // (kind 2): REP_TEXT_POOLED = the pooled + projected output variant of sd_clip_text_embeds, see build_clip.  The field is
+    // part of the plan key, so the variants of one batch size are distinct plans.
+    int rep = 1;
+    int lh = 0, lw = 0;                   // latent height / width the plan is built for
+    std::vector<Tn> tensors;
+    std::vector<Op> ops;
+    std::vector<char> skipped;            // per op: skipped on a DeepCache skip step
+    std::vector<int> ctx_kv;              // tensor id of the [UB*L, 2C] K|V cache per cross-attn layer
+    std::vector<size_t> ctx_w;            // packed [2C, 768] weight offset per layer
+    std::vector<int> ctx_c;               // C per layer
+    int ctx_bf16 = -1;                    // bf16 copy of encoder_hidden_states
+    // folded prompt cross-attention (per layer): A^T [UB][heads*80][C] and B [UB][C][heads*80], see transformer()
+    struct Fold { int kv, at, bw, C; size_t wqT, wo; bool perm; int c2 = -1; size_t lnu = NOFF; int c1 = -1; size_t ones = NOFF; };   // perm: Bw in the fused kernel's k order; c2 >= 0: norm2 folded (wqT = the .ln weights, c2 = tensor of the beta terms)
+    std::vector<Fold> ctx_fold;
+    int ctx_fold_scratch = -1;            // masked K / V expansions [2][UB][heads*80][Cmax]
+    std::map<std::string, int> taps;
+    size_t total_bytes = 0;
+    // CLIP vision plans (kind 3): preprocessing geometry of the plan's input size and its tap tables (host copy while the plan
+    // is built; the device copy belongs to the handle, one per input size)
+    ClipPrepGeom geom;
+    std::vector<int> prep_tab;
+    const int* dtab = nullptr;
+};
+
+}  // namespace sdhip
+
+struct sd_unet {
+    // 0 = UNet2DConditionModel, 1 = AutoencoderKL decoder, 2 = CLIP text encoder, 3 = CLIP vision tower, 4 = AutoencoderKL encoder
+    int kind = 0;
+    sd_unet_config cfg;
+    sd_clip_config clip;
+    sd_clip_vision_config vis;
+    int text_proj = 0;                 // kind 2 with text_projection.weight [text_proj, hidden] (sd_clip_create_projected)
+    int eos_id = -1;                   // pooled text row: first position of this id; < 0: argmax of the ids
+    std::map<std::pair<int, int>, int*> prep_tabs;     // kind 3: device tap tables per input (H, W)
+    std::vector<sdhip::ParamSpec> params;
+    std::unordered_map<std::string, int> pindex;
+    std::unordered_map<std::string, size_t> woff;  // packed item -> byte offset into dweights
+    sdhip::HostBlob hblob;                                // host staging of the packed blob
+    char* dweights = nullptr;
+    bool finalized = false;
+    bool debug_taps = false;
+    bool fp8 = false;                  // cfg.weight_dtype == SD_DTYPE_FP8_E4M3
+    float s_norm = 8.f, s_ff = 2.f;    // fp8 activation scales (GroupNorm / LayerNorm outputs, GEGLU outputs): the DEFAULTS
+    // per-tensor activation scales (sd_unet_calibrate_fp8 / sd_unet_set_fp8_scale): every e4m3 activation tensor is named
+    // after the module that writes it ("<resnet>.norm1", "<attn>.norm", "<block>.norm1|3", "<block>.ff.net.0"); a tensor
+    // without an entry uses the default of its kind.  act_amax: largest |value| calibration has seen (0 = never calibrated).
+    std::vector<std::string> act_names;
+    std::unordered_map<std::string, int> act_index;
+    std::vector<float> act_scale, act_amax;
+    int act_id(const std::string& name, float dflt) {
+        auto it = act_index.find(name);
+        if (it != act_index.end()) return it->second;
+        act_index[name] = (int)act_names.size();
+        act_names.push_back(name); act_scale.push_back(dflt); act_amax.push_back(0.f);
+        return (int)act_names.size() - 1;
+    }
+    std::map<std::tuple<int, int, int, int, int>, sdhip::Plan> plans;   // (UNet batch, DeepCache branch, prefix replication, latent H, W)
+    int last_rep = 1;                                    // variant of the last forward (sd_unet_debug_tensor)
+    int last_h = 0, last_w = 0;                          // latent size of the last forward (sd_unet_debug_tensor)
+    std::unordered_map<std::string, long> tproj_off;  // resnet prefix -> float index into tproj vector
+    long tproj_total = 0;
+    // LCM-distilled UNets (cfg.time_cond_proj_dim > 0): cond_proj . condition, [c0] fp32, written by sd_unet_set_timestep_cond.
+    // Owned by the handle (not the workspace) so that it outlives plans, sizes and DeepCache branches; while cond_set, every
+    // forward's OP_SINUSOID adds it to the sinusoid.
+    float* dcond = nullptr;
+    bool cond_set = false;
+    // inpainting UNets (cfg.in_channels == 9): the five constant input channels of a call, [inpaint_b][5][h][w] fp32 =
+    // [mask | masked-image latents], written by sd_unet_set_inpaint_cond_hw.  Owned by the handle like dcond; OP_CONV_IN reads
+    // channels 4..8 from it (batch index modulo inpaint_b), so no concatenated input is built per forward.
+    float* dinpaint = nullptr;
+    size_t inpaint_cap = 0;
+    int inpaint_b = 0, inpaint_h = 0, inpaint_w = 0;
+};
+
+namespace sdhip {
+
+// pack.hip
+void enumerate_params(sd_unet* u);
+void enumerate_params_vae(sd_unet* u);
+void enumerate_params_vae_encoder(sd_unet* u);
+void enumerate_params_clip(sd_unet* u);
+void enumerate_params_vit(sd_unet* u);
+int pack_all(sd_unet* u);
+double pack_alloc_seconds();      // staging-blob growth inside the last pack_all (SD_PACK_TIMING)
+// transformers CLIPTextModel state_dict names (4.48.0 layout, `text_model.` prefix)
+inline std::string clip_layer(int i) { return "text_model.encoder.layers." + std::to_string(i) + "."; }
+// transformers CLIPVisionModelWithProjection names (`vision_model.` prefix; `pre_layrnorm` is transformers' spelling)
+inline std::string vit_layer(int i) { return "vision_model.encoder.layers." + std::to_string(i) + "."; }
+inline int vit_kp(const sd_clip_vision_config& c) { return (3 * c.patch_size * c.patch_size + 63) / 64 * 64; }
+
+// plan.hip
+int plan_rep(const sd_unet* u, int latent_batch, int unet_batch);
+int check_latent_size(const sd_unet* u, int lh, int lw, const char* who);
+int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep = 1, int lh = -1, int lw = -1);     // lh / lw < 0: the handle's sample_size (square)
+
+// unet.hip
+int ensure_zero_page();
+const void* zero_page();          // (null until ensure_zero_page has run)
+int check_image_size(int H, int W, const char* who);
+int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* latents, int latent_batch, float* eps_out,
+           float timestep, hipStream_t stream);
+
+// ops.hip
+void* op_scratch(size_t bytes);
+
+}  // namespace sdhip

@@ -439,6 +439,52 @@ def test_finalize_packs_weights_on_the_host(dtype):
     lib.sd_unet_destroy(h)
 
 
+def _host_pack_case(kind):
+    """(create(handle) -> rc, parameter shapes, state dict) of the smallest config the GPU tests of `kind` use."""
+    from sonicdiffusionbayeslab_amd import clip, clip_score, vae
+    from tests.clip_score_util import tiny_configs, tiny_state_dict
+    lib = _lib.load()
+    if kind.startswith("vae"):
+        cfg = vae.VaeConfig(sample_size=16)
+        create, shapes = ((lib.sd_vae_create, vae.vae_param_shapes) if kind == "vae_decoder" else
+                          (lib.sd_vae_encoder_create, vae.vae_encoder_param_shapes))
+        c = vae._c_config(cfg)
+        return (lambda h: create(C.byref(c), C.byref(h))), shapes(cfg), vae.make_synthetic_vae_state_dict(cfg)
+    tcfg, vcfg = tiny_configs()
+    if kind == "clip_text":
+        c = _lib.SdClipConfig(tcfg.vocab_size, tcfg.hidden_size, tcfg.num_hidden_layers, tcfg.num_attention_heads,
+                              tcfg.intermediate_size, tcfg.max_position_embeddings, tcfg.layer_norm_eps)
+        return (lambda h: lib.sd_clip_create(C.byref(c), C.byref(h))), clip.clip_param_shapes(tcfg), tiny_state_dict()
+    c = _lib.SdClipVisionConfig(vcfg.hidden_size, vcfg.num_hidden_layers, vcfg.num_attention_heads, vcfg.intermediate_size,
+                                vcfg.image_size, vcfg.patch_size, vcfg.projection_dim, vcfg.layer_norm_eps)
+    return (lambda h: lib.sd_clip_vision_create(C.byref(c), C.byref(h))), clip_score.clip_vision_param_shapes(vcfg), tiny_state_dict()
+
+
+@pytest.mark.parametrize("kind,plain", [("vae_decoder", "decoder.conv_norm_out.weight"), ("vae_encoder", "encoder.conv_norm_out.weight"),
+                                        ("clip_text", "text_model.final_layer_norm.weight"),
+                                        ("clip_vision", "vision_model.post_layernorm.weight")])
+def test_finalize_packs_the_other_handle_kinds_on_the_host(kind, plain):
+    """The packers of the VAE decoder / encoder and of the two CLIP towers run here as the UNet's does above: finalize packs
+    on the host and stops at the upload, and an fp32 vector the packer stores as the parameter itself (Packer::f32, under
+    the parameter's own name) reads back bit-equal from the staging blob."""
+    if torch.cuda.is_available():
+        pytest.skip("host-side packer check runs on the CPU-only box (the blob is released after a successful upload)")
+    lib = _lib.load()
+    create, shapes, sd = _host_pack_case(kind)
+    h = C.c_void_p()
+    _lib.check(create(h))
+    for name, shape in shapes:
+        t = sd[name].float().contiguous()
+        assert tuple(t.shape) == tuple(shape), name
+        _lib.check(lib.sd_unet_load_param(h, name.encode(), t.data_ptr(), t.numel()))
+    assert lib.sd_unet_finalize(h) == -2 and b"hipMalloc" in lib.sd_last_error()      # packed, then no device to upload to
+    want = sd[plain].float().contiguous()
+    got = torch.empty_like(want)
+    assert lib.sd_unet_debug_packed(h, plain.encode(), got.data_ptr(), want.numel() * 4) >= 0, lib.sd_last_error()
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+    lib.sd_unet_destroy(h)
+
+
 def test_geglu_polynomial_gelu_error_bound():
     """The GEGLU epilogue's transcendental-free GELU (csrc/common.h::geglu_pair): its constants, evaluated in float32 the
     way the kernel does, stay within 1.3e-5 |x| of the exact-erf GELU (diffusers GEGLU -> F.gelu, approximate='none')."""

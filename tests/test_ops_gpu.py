@@ -433,7 +433,7 @@ def test_conv3x3_groupnorm_small_images_finish_the_deferred_splitk_reduce(sdlib,
 
 
 def fold_layernorm(w, gamma, beta, bias):
-    """Host-side packing of a LayerNorm-folded GEMM weight (mirror of the packer's ln_fold in unet.hip)."""
+    """Host-side packing of a LayerNorm-folded GEMM weight (mirror of the packer's ln_fold in pack.hip)."""
     wg = r16(w * gamma[None, :])
     c1 = wg.double().sum(1).float()
     c2 = (w.double() @ beta.double()).float() + (bias if bias is not None else 0.0)
@@ -1232,7 +1232,7 @@ def test_xattn_fused_with_norm2_folded(sdlib, B, hw, C, offset, dup):
     ("pv", 16384, 200, 64),
 ])
 def test_gemm_strided_and_offset_operands_of_the_chunked_vae_attention(sdlib, form, hw, M, pad):
-    """The chunked VAE mid-block attention (csrc/unet.hip, vae_attention) runs its three GEMMs on row-strided operands and
+    """The chunked VAE mid-block attention (csrc/plan.hip, vae_attention) runs its three GEMMs on row-strided operands and
     writes at an offset into a bigger tensor.  Here every stride is wider than its rows (ldx > K1, ldx2 > K - K1, ldr > N,
     ldc > N): the gap columns are sentinel-filled and must stay so, rows of the output tensor before and after the written
     block must stay NaN, operands are read only inside their rows (NaN-poisoned gaps), and every element meets its bound."""

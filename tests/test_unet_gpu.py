@@ -100,7 +100,7 @@ def _fused_groupnorms(net, lat, ub):
 
 def test_deferred_splitk_reduce_in_the_single_launch_groupnorm_is_bit_identical(small_unet):
     """At the 8x8 / 16x16 levels the plan hands the fp32 partial slabs of a split-K conv / GEMM to the single-launch GroupNorm
-    that reads its output first (csrc/unet.hip fuse_deferred_reduce: resnet conv1 -> norm2, conv2 / proj_out / downsampler ->
+    that reads its output first (csrc/plan.hip fuse_deferred_reduce: resnet conv1 -> norm2, conv2 / proj_out / downsampler ->
     the next block's norm1, incl. the up path's channel concat): same sums in the same order, one launch instead of two.  A second
     handle built with SD_GN_SLAB=0 (conv + splitk_reduce, then the GroupNorm) must give the same bits."""
     from sonicdiffusionbayeslab_amd.unet import HipUNet2DConditionModel
