@@ -56,6 +56,15 @@ typedef struct sd_unet_config {
      * sinusoid before linear_1 (sd_unet_set_timestep_cond).  A multiple of 8.  VAE and CLIP handles ignore it.
      * (Appended under ABI 3: zero-initialise the struct.) */
     int time_cond_proj_dim;
+    /* IP-Adapter image prompts (diffusers IPAdapterAttnProcessor2_0 + ImageProjection, the plain ip-adapter_sd15 family; both
+     * 0 = none).  ip_adapter_tokens: image tokens per sample (4 is built); ip_adapter_embed_dim: width E of image_embeds (1024
+     * for the published adapter; a multiple of 64).  With them set the handle additionally takes
+     *   encoder_hid_proj.image_projection_layers.0.image_embeds.{weight [tokens * cross_attention_dim, E], bias},
+     *   encoder_hid_proj.image_projection_layers.0.norm.{weight, bias} [cross_attention_dim], and per attn2 layer
+     *   <block>.attn2.processor.to_k_ip.0.weight / to_v_ip.0.weight [C, cross_attention_dim]
+     * and sd_unet_set_ip_adapter_hw conditions its forwards.  num_heads must be 1, 2, 4 or 8.  (Appended under ABI 3.) */
+    int ip_adapter_tokens;
+    int ip_adapter_embed_dim;
 } sd_unet_config;
 enum { SD_DTYPE_BF16 = 0, SD_DTYPE_FP8_E4M3 = 1 };
 
@@ -143,6 +152,23 @@ int sd_unet_set_timestep_cond(sd_unet* u, void* stream, const float* cond);
 int sd_unet_set_inpaint_cond_hw(sd_unet* u, void* stream, const float* mask, const float* masked_latents, int batch,
                                 int latent_h, int latent_w);
 
+/* Image prompt of a handle with an IP-Adapter (ip_adapter_tokens > 0): decoupled cross-attention, per attn2 layer
+ *   attn = softmax_77(q k^T / sqrt d) v + scale * softmax_T(q K_ip^T / sqrt d) V_ip,   h = h + to_out(attn).
+ * Call it AFTER sd_unet_set_context_hw with the same batch, branch, size and workspace.  `image_embeds`: device fp32
+ * [unet_batch, ip_adapter_embed_dim], 16-byte aligned, the CFG halves already concatenated (negative first; diffusers uses
+ * zeros there).  It runs the token projection + LayerNorm, to_k_ip | to_v_ip of every layer and folds, per sample and head,
+ *   A = (K_ip / sqrt d) W_q   and   B = scale * V_ip W_o^T
+ * into context tensors of the workspace; `scale` lives in B, so changing it means calling again.  From then on every forward
+ * of the handle runs the "IP on" plan variant: one extra launch per transformer block (profile kind 22) writes
+ * R' = h + sum_heads softmax_T(LN(h) A^T) B, which the block's prompt cross-attention takes as its residual.  While any
+ * (batch, branch, size) of the handle has an image prompt set, a forward for which it has NOT been set fails and says so.
+ * image_embeds = NULL clears the prompt of that (batch, branch, size) (nothing is launched; workspace may be NULL): once none
+ * is left the handle runs the plans of a handle without an adapter, bit for bit.  sd_unet_workspace_bytes_hw of such a handle
+ * covers both variants.  sd_unet_calibrate_fp8 always runs without the image prompt and CLEARS every image prompt of the
+ * handle (its plan uses the workspace where the folded operands lie): call this again after calibrating. */
+int sd_unet_set_ip_adapter_hw(sd_unet* u, void* stream, const float* image_embeds, int unet_batch, int cache_branch_id,
+                              int latent_h, int latent_w, float scale, void* workspace, long long workspace_bytes);
+
 enum { SD_CACHE_OFF = 0, SD_CACHE_FULL_AND_STORE = 1, SD_CACHE_SKIP = 2 };
 
 /* eps = UNet(latent_model_input, t, encoder_hidden_states)  (src/models.py:217-235).
@@ -226,7 +252,7 @@ int sd_clip_encode(sd_clip* c, void* stream, const int* input_ids, int batch, fl
  * position_embedding.weight}, vision_model.pre_layrnorm.*, vision_model.encoder.layers.N.*, vision_model.post_layernorm.*,
  * visual_projection.weight), enumerated / loaded / finalised through the sd_unet_* calls.  encode: device uint8 images
  * [batch, 3, height, width] (any size) -> CLIPImageProcessor (shortest edge -> image_size with Pillow's bicubic, bit-exact;
- * centre crop; OpenAI CLIP mean / std) -> ViT (non-causal attention, head dim 64, <= 320 tokens) -> post_layernorm of the
+ * centre crop; OpenAI CLIP mean / std) -> ViT (non-causal attention, head dim 64 or 80, <= 320 tokens) -> post_layernorm of the
  * class token -> visual_projection: fp32 image_embeds [batch, projection_dim].  One plan per (batch, height, width).
  * sd_clip_score: raw[b] = 100 cos(image_embeds[b], text_embeds[b]) and score[b] = max(raw[b], 0) (either may be NULL). */
 typedef struct sd_clip_vision_config {
@@ -238,7 +264,11 @@ typedef struct sd_clip_vision_config {
     int patch_size;          /* 16 */
     int projection_dim;      /* 512 */
     float layer_norm_eps;    /* 1e-5 */
+    /* MLP activation: SD_ACT_QUICK_GELU (x sigmoid(1.702 x): OpenAI CLIP) or SD_ACT_GELU (exact, erf: the OpenCLIP ViT-H/14 that
+     * IP-Adapters use as image encoder, hidden 1280 / 16 heads = head dim 80).  (Appended: zero-initialise the struct.) */
+    int hidden_act;
 } sd_clip_vision_config;
+enum { SD_ACT_QUICK_GELU = 0, SD_ACT_GELU = 1 };
 typedef struct sd_unet sd_clip_vision;
 int sd_clip_create_projected(const sd_clip_config* cfg, int projection_dim, int eos_token_id, sd_clip** out);
 long long sd_clip_text_embeds_workspace_bytes(sd_clip* c, int batch);
@@ -296,8 +326,8 @@ int sd_op_inception_resize(void* stream, const unsigned char* images, int B, int
 
 /* Measurement hook for bench.py: the same forward with a hipEvent pair around every launch.  Per
  * op kind (0 sinusoid, 1 gemv, 2 conv_in, 3 groupnorm, 4 conv3x3, 5 gemm, 6 layernorm,
- * 7 attention, 8 conv_out; 16 conv3x3 with fp8 operands, 17 gemm with fp8 operands, 18 fused prompt cross-attention)
- * it returns summed
+ * 7 attention, 8 conv_out; 16 conv3x3 with fp8 operands, 17 gemm with fp8 operands, 18 fused prompt cross-attention,
+ * 22 IP-Adapter image branch) it returns summed
  * milliseconds, launch count, algorithmic FLOPs and algorithmic HBM bytes in arrays of SD_PROFILE_KINDS = 32
  * entries.  Synchronises the stream; never used inside a timed region. */
 #define SD_PROFILE_KINDS 32
@@ -500,6 +530,16 @@ int sd_op_gemm_plan(void* stream, const void* X, long long ldx, const void* X2, 
                     void* KV, int hm_tokens);
 int sd_op_xattn_fused_rowstats(void* stream, const void* X, const void* R, void* Y, const void* At, const void* Bw,
                                const float* bias, int M, int C, int rows_per_sample, int L, float* rowstats);
+/* The IP-Adapter image branch as one launch (what sd_unet_set_ip_adapter_hw's plan variant runs in front of every prompt
+ * cross-attention):  Rout[m] = R[m] + sum_h softmax_T( LN(R[m]) . A_h[s]^T ) . B_h[s],  s = m / rows_per_sample.
+ * R, Rout: bf16 [M][C], Rout != R.  A: bf16 [samples][32][C], row head * (32 / heads) + t = the folded key t of that head
+ * (softmax scale included), every other row zero.  Bt: bf16 [samples][C][32], the folded values in the same slots (adapter
+ * scale included).  gamma / beta: fp32 [C], the LayerNorm the kernel applies from each row's own statistics; the normalised
+ * row is rounded to bf16 before the first product, the probabilities before the second; sums, softmax and the residual add
+ * are fp32 with one bf16 rounding on store.  C % 32 == 0 (at most 2048), heads in {1, 2, 4, 8}, T = 4, any
+ * rows_per_sample >= 1 (a tile of 32 rows never spans two samples), M a multiple of rows_per_sample; 16-byte aligned. */
+int sd_op_ip_xattn(void* stream, const void* R, void* Rout, const void* A, const void* Bt, const float* gamma, const float* beta,
+                   float eps, long long M, int C, int rows_per_sample, int heads, int T);
 int sd_op_xattn_fused(void* stream, const void* X, const void* R, void* Y, const void* At, const void* Bw,
                       const float* bias, int M, int C, int rows_per_sample, int L);
 /* The same with the block's norm2 folded in (how the plan runs it at the 64x64 / 32x32 levels): X holds the UN-normalised rows

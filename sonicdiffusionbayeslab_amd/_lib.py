@@ -30,6 +30,7 @@ class SdUnetConfig(C.Structure):
         ("norm_num_groups", C.c_int), ("norm_eps", C.c_float), ("context_len", C.c_int),
         ("weight_dtype", C.c_int), ("fp8_act_scale_norm", C.c_float), ("fp8_act_scale_ff", C.c_float),
         ("time_cond_proj_dim", C.c_int),
+        ("ip_adapter_tokens", C.c_int), ("ip_adapter_embed_dim", C.c_int),
     ]
 
 
@@ -48,6 +49,7 @@ class SdClipVisionConfig(C.Structure):
     _fields_ = [
         ("hidden_size", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int), ("intermediate_size", C.c_int),
         ("image_size", C.c_int), ("patch_size", C.c_int), ("projection_dim", C.c_int), ("layer_norm_eps", C.c_float),
+        ("hidden_act", C.c_int),            # 0 = quick_gelu, 1 = gelu (exact); appended: the eight-value form leaves it 0
     ]
 
 
@@ -127,6 +129,8 @@ _SIGS = {
                                    _vp, _vp, _vp, _f, _f, _ll]),
     "sd_inpaint_prepare": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
     "sd_unet_set_inpaint_cond_hw": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
+    "sd_unet_set_ip_adapter_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _ll]),
+    "sd_op_ip_xattn": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _ll, _i, _i, _i, _i]),
     "sd_op_conv_in_cond": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i]),
     "sd_op_gemm": (_i, [_vp, _vp, _ll, _vp, _ll, _i, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _i]),
     "sd_op_gemm_batched": (_i, [_vp, _vp, _ll, _vp, _ll, _i, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _i, _i]),

@@ -38,6 +38,10 @@ class ClipVisionConfig:
     patch_size: int = 16
     projection_dim: int = 512
     layer_norm_eps: float = 1e-5
+    hidden_act: str = "quick_gelu"      # or "gelu" (exact): the OpenCLIP ViT-H/14 image encoder of the IP-Adapters
+
+
+HIDDEN_ACTS = {"quick_gelu": 0, "gelu": 1}      # include/sd_hip.h: SD_ACT_*
 
 
 def clip_vision_param_shapes(cfg: ClipVisionConfig) -> List[Tuple[str, Tuple[int, ...]]]:
@@ -81,17 +85,23 @@ def make_synthetic_clip_vision_state_dict(cfg: ClipVisionConfig, seed: int = 555
     return sd
 
 
-def check_vision_config(cfg: ClipVisionConfig, hidden_act: str = "quick_gelu") -> None:
-    """The shapes libsdhip builds; ValueError naming the field otherwise (raised before any GPU work)."""
-    if hidden_act != "quick_gelu":
-        raise ValueError(f"vision_config.hidden_act={hidden_act!r}: only 'quick_gelu' is built")
+def check_vision_config(cfg: ClipVisionConfig, hidden_act: Optional[str] = None, extended: bool = False) -> None:
+    """The shapes libsdhip builds; ValueError naming the field otherwise (raised before any GPU work).  ``hidden_act``: the
+    checkpoint's activation (default: the config's own).  ``extended``: also the tower of the IP-Adapters' image encoder --
+    exact ``gelu`` and head dim 80 (ViT-H/14); without it the CLIP-score checkpoints' rule stands (``quick_gelu``, head dim
+    64: the text tower beside it builds nothing else)."""
+    hidden_act = cfg.hidden_act if hidden_act is None else hidden_act
+    if hidden_act != "quick_gelu" and not (extended and hidden_act == "gelu"):
+        raise ValueError(f"vision_config.hidden_act={hidden_act!r}: only 'quick_gelu' is built" +
+                         (" (and 'gelu')" if extended else ""))
     H = cfg.hidden_size
     if H % 64 or H <= 0 or H > 1536:
         raise ValueError(f"vision_config.hidden_size={H}: a multiple of 64 up to 1536 is built")
     if cfg.intermediate_size % 64 or cfg.intermediate_size <= 0:
         raise ValueError(f"vision_config.intermediate_size={cfg.intermediate_size}: a multiple of 64 is built")
-    if cfg.num_attention_heads <= 0 or H % cfg.num_attention_heads or H // cfg.num_attention_heads != 64:
-        raise ValueError(f"vision_config.num_attention_heads={cfg.num_attention_heads}: head dim 64 is built")
+    if cfg.num_attention_heads <= 0 or H % cfg.num_attention_heads or H // cfg.num_attention_heads not in ((64, 80) if extended else (64,)):
+        raise ValueError(f"vision_config.num_attention_heads={cfg.num_attention_heads}: head dim 64 is built" +
+                         (" (and 80)" if extended else ""))
     if cfg.patch_size <= 0 or cfg.image_size % cfg.patch_size:
         raise ValueError(f"vision_config.patch_size={cfg.patch_size} must divide image_size={cfg.image_size}")
     if (cfg.image_size // cfg.patch_size) ** 2 + 1 > MAX_TOKENS:
@@ -126,7 +136,7 @@ class HipClipVisionModel:
     def __init__(self, config: ClipVisionConfig, state_dict: Dict[str, torch.Tensor], device=None):
         """``device``: where the weights live and the tower runs (``None``: the current device); the process's current
         device is left as it is."""
-        check_vision_config(config)
+        check_vision_config(config, extended=True)
         if not torch.cuda.is_available():
             raise _lib.SdHipError("HipClipVisionModel needs an MI355X (no CPU fallback exists)")
         self.config = config
@@ -141,7 +151,7 @@ class HipClipVisionModel:
     def _build(self, config: ClipVisionConfig, state_dict: Dict[str, torch.Tensor]) -> None:
         c = _lib.SdClipVisionConfig(config.hidden_size, config.num_hidden_layers, config.num_attention_heads,
                                     config.intermediate_size, config.image_size, config.patch_size, config.projection_dim,
-                                    config.layer_norm_eps)
+                                    config.layer_norm_eps, HIDDEN_ACTS[config.hidden_act])
         _lib.check(self._lib.sd_clip_vision_create(C.byref(c), C.byref(self._handle)), "sd_clip_vision_create")
         for name, shape in clip_vision_param_shapes(config):
             if name not in state_dict:

@@ -84,6 +84,14 @@ __global__ void quick_gelu_kernel(bf16_t* __restrict__ x, long n2) {
     *(unsigned*)(x + 2 * i) = pack2bf(a / (1.0f + __expf(-1.702f * a)), b / (1.0f + __expf(-1.702f * b)));
 }
 
+// exact GELU in place: x Phi(x) (transformers' "gelu"; the erf form of common.h, 1.3e-5 |x| from the exact value)
+__global__ void gelu_erf_kernel(bf16_t* __restrict__ x, long n2) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n2) return;
+    const unsigned v = *(const unsigned*)(x + 2 * i);
+    *(unsigned*)(x + 2 * i) = pack2bf(gelu_erf_f(bflo(v)), gelu_erf_f(bfhi(v)));
+}
+
 __global__ void bf16_to_f32_kernel(const bf16_t* __restrict__ src, float* __restrict__ dst, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = bf2f(src[i]);
@@ -125,6 +133,14 @@ int sd_launch_quick_gelu(bf16_t* x, long n, hipStream_t stream) {
     SD_REQUIRE(x && n > 0 && n % 2 == 0, "quick_gelu: n=%ld", n);
     const long n2 = n / 2;
     hipLaunchKernelGGL(quick_gelu_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, stream, x, n2);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sd_launch_gelu_erf(bf16_t* x, long n, hipStream_t stream) {
+    SD_REQUIRE(x && n > 0 && n % 2 == 0, "gelu: n=%ld", n);
+    const long n2 = n / 2;
+    hipLaunchKernelGGL(gelu_erf_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, stream, x, n2);
     SD_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -208,13 +208,22 @@ struct XattnArgs {
 bool sd_xattn_fused_applicable(int rows_per_sample, int C, int heads, int L);
 int sd_xattn_slices(int M, int C);     // channel slices of the launch (LayerNorm partials per row = 2 * slices)
 int sd_launch_xattn_fused(const XattnArgs& a, hipStream_t stream);
+// slots: key slots per head of the expansion (80 for the prompt; the IP-Adapter's image tokens use their own count)
 int sd_launch_xattn_expand(const bf16_t* kv, bf16_t* out, int B, int L, int C, int NH, int col_off, float scale,
-                           hipStream_t stream);
+                           hipStream_t stream, int slots = 80);
+// ip_xattn.hip: the IP-Adapter image branch  Y = R + sum_h softmax_T(LN(R) A_h^T) B_h  (one launch per transformer block)
+//   R, Y [M][C] (Y != R); A [samples][32][C]: row (head * (32 / heads) + token) = (K_ip,h[token] / sqrt(d)) . W_q,h, the other
+//   rows zero; Bt [samples][C][32]: the same slots as columns = scale * V_ip,h[token] . W_o,h^T; gamma / beta [C]: norm2, applied
+//   in the kernel from the row's own statistics.  C % 32 == 0, T = 4, heads in {1, 2, 4, 8}; any rows_per_sample >= 1.
+bool sd_ip_xattn_applicable(int C, int heads, int T);
+int sd_launch_ip_xattn(const bf16_t* R, bf16_t* Y, const bf16_t* A, const bf16_t* Bt, const float* gamma, const float* beta,
+                       float eps, long M, int C, int rows_per_sample, int heads, int T, hipStream_t stream);
 // clip.hip: CLIP text encoder pieces
 int sd_launch_clip_embed(const int* ids, const bf16_t* tok, const bf16_t* pos, bf16_t* out, int rows, int L, int H,
                          int vocab, hipStream_t stream);
 int sd_launch_clip_attention(const bf16_t* qkv, bf16_t* out, int B, int L, int H, int heads, hipStream_t stream);
 int sd_launch_quick_gelu(bf16_t* x, long n, hipStream_t stream);
+int sd_launch_gelu_erf(bf16_t* x, long n, hipStream_t stream);      // exact (erf) GELU in place: common.h::gelu_erf_f
 int sd_launch_bf16_to_f32(const bf16_t* src, float* dst, long n, hipStream_t stream);
 
 // vit.hip: CLIP vision tower pieces and the CLIP score

@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <map>
 #include <new>
+#include <set>
 #include <string>
 #include <tuple>
 #include <unordered_map>
@@ -41,7 +42,7 @@ struct Wrap {  // one DeepCache-wrapped module enclosing an op
 
 enum OpKind { OP_SINUSOID, OP_GEMV, OP_CONV_IN, OP_GN, OP_CONV3, OP_GEMM, OP_LN, OP_ATTN, OP_CONV_OUT, OP_SOFTMAX, OP_PQCONV,
               OP_CLIP_EMBED, OP_CLIP_ATTN, OP_QGELU, OP_TO_F32, OP_XATTN, OP_REPLICATE,
-              OP_VIT_PREP, OP_VIT_EMBED, OP_VIT_ATTN, OP_POOL, OP_CONV_IN_IMG, OP_ENC_OUT };
+              OP_VIT_PREP, OP_VIT_EMBED, OP_VIT_ATTN, OP_POOL, OP_CONV_IN_IMG, OP_ENC_OUT, OP_IP_XATTN };
 
 constexpr int REP_TEXT_POOLED = 2;       // Plan::rep of a CLIP text handle's sd_clip_text_embeds plan
 
@@ -134,6 +135,7 @@ struct Tn {
     int def = -1, last = -1;
     bool persistent = false;
     bool ctx = false;            // written by sd_unet_set_context: same offset in every plan variant of a (batch, branch)
+    bool ctx_ip = false;         // ctx tensor of the IP-Adapter variant (sd_unet_set_ip_adapter_hw): laid out BEHIND the others
     size_t off = NOFF;
 };
 
@@ -144,6 +146,15 @@ struct Plan {
     // part of the plan key, so the variants of one batch size are distinct plans.
     int rep = 1;
     int lh = 0, lw = 0;                   // latent height / width the plan is built for
+    // IP-Adapter variant (part of the plan key): one OP_IP_XATTN in front of every block's prompt cross-attention, whose
+    // residual operand becomes that op's output.  ip_fold: per block the folded operands A [UB][32][C] and Bt [UB][C][32]
+    // (ip_xattn.hip) with the packed weights they are folded from; ip_e / ip_proj / ip_tok / ip_kv: what
+    // sd_unet_set_ip_adapter_hw computes on the way (bf16: embeds [UB][E], projection [UB][T * CD], tokens [UB * T][CD], and one
+    // block's K_ip | V_ip [UB * T][2 C]).
+    int ip = 0;
+    struct IpFold { int at, bt, C; size_t wqT, wo, wkv; };
+    std::vector<IpFold> ip_fold;
+    int ip_e = -1, ip_proj = -1, ip_tok = -1, ip_kv = -1;
     std::vector<Tn> tensors;
     std::vector<Op> ops;
     std::vector<char> skipped;            // per op: skipped on a DeepCache skip step
@@ -197,8 +208,8 @@ struct sd_unet {
         act_names.push_back(name); act_scale.push_back(dflt); act_amax.push_back(0.f);
         return (int)act_names.size() - 1;
     }
-    std::map<std::tuple<int, int, int, int, int>, sdhip::Plan> plans;   // (UNet batch, DeepCache branch, prefix replication, latent H, W)
-    int last_rep = 1;                                    // variant of the last forward (sd_unet_debug_tensor)
+    std::map<std::tuple<int, int, int, int, int, int>, sdhip::Plan> plans;   // (UNet batch, DeepCache branch, prefix replication, latent H, W, IP-Adapter variant)
+    int last_rep = 1, last_ip = 0;                       // variant of the last forward (sd_unet_debug_tensor)
     int last_h = 0, last_w = 0;                          // latent size of the last forward (sd_unet_debug_tensor)
     std::unordered_map<std::string, long> tproj_off;  // resnet prefix -> float index into tproj vector
     long tproj_total = 0;
@@ -213,6 +224,10 @@ struct sd_unet {
     float* dinpaint = nullptr;
     size_t inpaint_cap = 0;
     int inpaint_b = 0, inpaint_h = 0, inpaint_w = 0;
+    // IP-Adapter (cfg.ip_adapter_tokens > 0): the (UNet batch, DeepCache branch, latent H, W) whose workspace holds folded image
+    // operands (sd_unet_set_ip_adapter_hw).  While the set is not empty every forward runs the "IP on" plan variant and must find
+    // its own key here; empty = the plans of a handle without an adapter.
+    std::set<std::tuple<int, int, int, int>> ip_keys;
 };
 
 namespace sdhip {
@@ -234,7 +249,8 @@ inline int vit_kp(const sd_clip_vision_config& c) { return (3 * c.patch_size * c
 // plan.hip
 int plan_rep(const sd_unet* u, int latent_batch, int unet_batch);
 int check_latent_size(const sd_unet* u, int lh, int lw, const char* who);
-int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep = 1, int lh = -1, int lw = -1);     // lh / lw < 0: the handle's sample_size (square)
+int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep = 1, int lh = -1, int lw = -1, int ip = 0);     // lh / lw < 0: the handle's sample_size (square)
+bool ip_active(const sd_unet* u, int UB, int branch, int lh, int lw);     // is this forward's IP-Adapter key set?
 
 // unet.hip
 int ensure_zero_page();

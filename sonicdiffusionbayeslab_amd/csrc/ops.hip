@@ -541,6 +541,14 @@ extern "C" int sd_op_xattn_fused_rowstats(void* stream, const void* X, const voi
     return sd_launch_xattn_fused(a, (hipStream_t)stream);
 }
 
+// the IP-Adapter image branch on its own (ip_xattn.hip; the launch the "IP on" plan puts in front of a block's prompt
+// cross-attention): Rout = R + sum_h softmax_T(LayerNorm(R; gamma, beta, eps) A_h^T) B_h
+extern "C" int sd_op_ip_xattn(void* stream, const void* R, void* Rout, const void* A, const void* Bt, const float* gamma,
+                              const float* beta, float eps, long long M, int C, int rows_per_sample, int heads, int T) {
+    return sd_launch_ip_xattn((const bf16_t*)R, (bf16_t*)Rout, (const bf16_t*)A, (const bf16_t*)Bt, gamma, beta, eps, (long)M, C,
+                              rows_per_sample, heads, T, (hipStream_t)stream);
+}
+
 extern "C" int sd_op_xattn_fused(void* stream, const void* X, const void* R, void* Y, const void* At, const void* Bw,
                                  const float* bias, int M, int C, int rows_per_sample, int L) {
     SD_REQUIRE(sd_xattn_fused_applicable(rows_per_sample, C, 8, L) || getenv("SD_XATTN_FUSED"),

@@ -60,6 +60,10 @@ struct Enum {
         add(t + "attn2.to_v.weight", {c, ctx});
         add(t + "attn2.to_out.0.weight", {c, c});
         add(t + "attn2.to_out.0.bias", {c});
+        if (u->cfg.ip_adapter_tokens > 0) {      // IPAdapterAttnProcessor2_0 of one adapter (diffusers' names)
+            add(t + "attn2.processor.to_k_ip.0.weight", {c, ctx});
+            add(t + "attn2.processor.to_v_ip.0.weight", {c, ctx});
+        }
         add(t + "ff.net.0.proj.weight", {8 * c, c});
         add(t + "ff.net.0.proj.bias", {8 * c});
         add(t + "ff.net.2.weight", {c, 4 * c});
@@ -137,6 +141,13 @@ void enumerate_params(sd_unet* u) {
     e.add("conv_norm_out.bias", {c0});
     e.add("conv_out.weight", {c.out_channels, c0, 3, 3});
     e.add("conv_out.bias", {c.out_channels});
+    if (c.ip_adapter_tokens > 0) {      // ImageProjection of the IP-Adapter (diffusers: unet.encoder_hid_proj)
+        const std::string p = "encoder_hid_proj.image_projection_layers.0.";
+        e.add(p + "image_embeds.weight", {c.ip_adapter_tokens * c.cross_attention_dim, c.ip_adapter_embed_dim});
+        e.add(p + "image_embeds.bias", {c.ip_adapter_tokens * c.cross_attention_dim});
+        e.add(p + "norm.weight", {c.cross_attention_dim});
+        e.add(p + "norm.bias", {c.cross_attention_dim});
+    }
 }
 
 void enumerate_params_clip(sd_unet* u) {
@@ -611,6 +622,8 @@ struct Packer {
             ln_fold(t + "attn2.to_q.weight", P(t + "attn2.to_q.weight").data(), c, c, P(t + "norm2.weight"), P(t + "norm2.bias"), nullptr);
         concat_rows(t + "attn2.kv.weight", {t + "attn2.to_k.weight", t + "attn2.to_v.weight"});
         bf16_same(t + "attn2.to_out.0.weight"); f32(t + "attn2.to_out.0.bias");
+        if (u->cfg.ip_adapter_tokens > 0)      // to_k_ip | to_v_ip as one projection of the image tokens, like attn2.kv
+            concat_rows(t + "attn2.kv_ip.weight", {t + "attn2.processor.to_k_ip.0.weight", t + "attn2.processor.to_v_ip.0.weight"});
         geglu(t, c);
         f32(t + "ff.net.2.bias");
         bf16_same(p + "proj_out.weight"); f32(p + "proj_out.bias");
@@ -794,6 +807,11 @@ int pack_all(sd_unet* u) {
     }
     pk.f32("conv_norm_out.weight"); pk.f32("conv_norm_out.bias");
     pk.conv3_ohwi("conv_out.weight", c.out_channels, c0); pk.f32("conv_out.bias");
+    if (c.ip_adapter_tokens > 0) {
+        const std::string p = "encoder_hid_proj.image_projection_layers.0.";
+        pk.bf16_same(p + "image_embeds.weight"); pk.f32(p + "image_embeds.bias");
+        pk.f32(p + "norm.weight"); pk.f32(p + "norm.bias");
+    }
     return 0;
 }
 

@@ -81,6 +81,11 @@ struct Builder {
         pl.tensors[id].ctx = true;
         return id;
     }
+    int ctx_ip_tensor(size_t bytes) {    // ... by sd_unet_set_ip_adapter_hw (laid out behind the others: see assign_memory)
+        const int id = ctx_tensor(bytes);
+        pl.tensors[id].ctx_ip = true;
+        return id;
+    }
     int tensor(size_t bytes, bool persistent = false) {
         Tn t;
         t.bytes = (bytes + 255) / 256 * 256;
@@ -293,13 +298,24 @@ struct Builder {
         pl.ctx_kv.push_back(kv);
         pl.ctx_w.push_back(W(t + "attn2.kv.weight"));
         pl.ctx_c.push_back(C);
+        // IP-Adapter variant: the image branch runs first and writes R' = h1 + sum_h softmax_T(LN(h1) A_ip,h^T) B_ip,h (ip_xattn.hip:
+        // its own LayerNorm from the row itself, whatever form and fold the text attention below uses); R' then is the RESIDUAL
+        // operand of that form, whose other operands stay as they are:  h2 = h1 + scale to_out(image) + to_out(text) + b_o
+        int res = h1;
+        if (pl.ip) {
+            const int at = ctx_ip_tensor((size_t)UB * 32 * C * 2), bt = ctx_ip_tensor((size_t)UB * C * 32 * 2);
+            pl.ip_fold.push_back(Plan::IpFold{at, bt, C, W(t + "attn2.to_q.weight.T"), W(t + "attn2.to_out.0.weight"), W(t + "attn2.kv_ip.weight")});
+            Op o; o.kind = OP_IP_XATTN; o.x1 = h1; o.wt = at; o.x2 = bt; o.M = M; o.N = C; o.rpb = hw; o.heads = NH;
+            o.g = W(t + "norm2.weight"); o.be = W(t + "norm2.bias"); o.eps = 1e-5f;
+            o.out = tensor((size_t)M * C * 2); push(o); res = o.out;
+        }
         int h2;
         if (xmode == 0) {
             int at = ctx_tensor((size_t)UB * NP * C * 2), bw = ctx_tensor((size_t)UB * C * NP * 2);
             Plan::Fold fd{kv, at, bw, C, W(t + (np2 > 0 ? "attn2.to_q.weight.T.ln" : "attn2.to_q.weight.T")), W(t + "attn2.to_out.0.weight"), true};
             if (np2 > 0) { fd.c2 = ctx_tensor((size_t)UB * NP * 4); fd.lnu = W(t + "attn2.to_q.lnu"); }
             pl.ctx_fold.push_back(fd);
-            Op o; o.kind = OP_XATTN; o.x1 = n2; o.r = h1; o.wt = at; o.x2 = bw; o.M = M; o.N = C; o.K = NP; o.rpb = hw;
+            Op o; o.kind = OP_XATTN; o.x1 = n2; o.r = res; o.wt = at; o.x2 = bw; o.M = M; o.N = C; o.K = NP; o.rpb = hw;
             o.sm_valid = L; o.b = W(t + "attn2.to_out.0.bias"); o.heads = NH;
             if (np2 > 0) { o.lnrs = rs2; o.lnnp = np2; o.s1 = fd.c2; o.ldx_o = rs2_rows; }   // (s1: the c2 tensor; ldx_o: rows of the partials)
             o.out = tensor((size_t)M * C * 2); push(o); h2 = o.out;
@@ -317,13 +333,13 @@ struct Builder {
               if (np2 > 0) { o.lnrs = rs2; o.lnnp = np2; o.s1 = fd.c1; o.s2 = fd.c2; }          // (s1 / s2: the per-sample c1 / c2 tensors)
               o.out = tensor((size_t)M * NP * 2); push(o); pr = o.out; }
             { Op o; o.kind = OP_GEMM; o.x1 = pr; o.K1 = NP; o.K = NP; o.M = M; o.N = C; o.epi = 0;
-              o.wt = bw; o.wbs = (long)C * NP; o.rpb = hw; o.b = W(t + "attn2.to_out.0.bias"); o.r = h1;
+              o.wt = bw; o.wbs = (long)C * NP; o.rpb = hw; o.b = W(t + "attn2.to_out.0.bias"); o.r = res;
               o.out = tensor((size_t)M * C * 2); push(o); h2 = o.out; }
         } else {
             int q2 = np2 > 0 ? gemm_ln(h1, rs2, np2, M, C, C, t + "attn2.to_q.weight", 0)
                              : gemm(n2, C, -1, 0, M, C, t + "attn2.to_q.weight", "", -1, 0);
             int a2 = attn(q2, 0, C, kv, 0, C, 2 * C, hw, L, C);
-            h2 = gemm(a2, C, -1, 0, M, C, t + "attn2.to_out.0.weight", t + "attn2.to_out.0.bias", h1, 0);
+            h2 = gemm(a2, C, -1, 0, M, C, t + "attn2.to_out.0.weight", t + "attn2.to_out.0.bias", res, 0);
         }
         int ff;
         if (!fq && (np = want_rowstats(pl.ops.back(), M, C, rs)) > 0) {       // norm3 folded into the GEGLU projection
@@ -466,18 +482,26 @@ struct Builder {
     }
 
     // one pre-LN encoder layer of either CLIP tower (p = the layer's prefix, t = the residual stream [M][H]); `attn_kind` =
-    // OP_CLIP_ATTN (causal) or OP_VIT_ATTN, over L tokens per sample
-    int clip_encoder_layer(const std::string& p, int t, int M, int L, int H, int I, int heads, int attn_kind) {
+    // OP_CLIP_ATTN (causal) or OP_VIT_ATTN, over L tokens per sample; gelu: the exact (erf) GELU instead of quick_gelu.  A
+    // vision tower with head dim 80 (ViT-H/14) runs its non-causal attention on the general attention kernels, reading q | k | v
+    // in place from the strided projection output
+    int clip_encoder_layer(const std::string& p, int t, int M, int L, int H, int I, int heads, int attn_kind, bool gelu = false) {
         const std::string a = p + "self_attn.";
         int n1 = ln(t, M, H, p + "layer_norm1.weight", p + "layer_norm1.bias");
         int qkv = gemm(n1, H, -1, 0, M, 3 * H, a + "qkv.weight", a + "qkv.bias", -1, 0);
         int at;
-        { Op o; o.kind = attn_kind; o.x1 = qkv; o.B = UB; o.Nq = L; o.N = H; o.heads = heads;
-          o.out = tensor((size_t)M * H * 2); push(o); at = o.out; }
+        if (attn_kind == OP_VIT_ATTN && H / heads == 80) {
+            Op o; o.kind = OP_ATTN; o.x1 = qkv; o.x2 = qkv; o.qoff = 0; o.koff = H; o.voff = 2 * H; o.ldq = o.ldk = o.ldv = 3 * H;
+            o.ldo = H; o.B = UB; o.heads = heads; o.D = 80; o.Nq = L; o.Nk = L;
+            o.out = tensor((size_t)M * H * 2); push(o); at = o.out;
+        } else {
+            Op o; o.kind = attn_kind; o.x1 = qkv; o.B = UB; o.Nq = L; o.N = H; o.heads = heads;
+            o.out = tensor((size_t)M * H * 2); push(o); at = o.out;
+        }
         t = gemm(at, H, -1, 0, M, H, a + "out_proj.weight", a + "out_proj.bias", t, 0);
         int n2 = ln(t, M, H, p + "layer_norm2.weight", p + "layer_norm2.bias");
         int f = gemm(n2, H, -1, 0, M, I, p + "mlp.fc1.weight", p + "mlp.fc1.bias", -1, 0);
-        { Op o; o.kind = OP_QGELU; o.x1 = f; o.out = f; o.M = M; o.N = I; push(o); }
+        { Op o; o.kind = OP_QGELU; o.x1 = f; o.out = f; o.M = M; o.N = I; o.epi = gelu ? 1 : 0; push(o); }      // (epi 1: exact GELU)
         return gemm(f, I, -1, 0, M, H, p + "mlp.fc2.weight", p + "mlp.fc2.bias", t, 0);
     }
 
@@ -524,7 +548,7 @@ struct Builder {
           o.out = tensor((size_t)M * H * 2); push(o); t = o.out; }
         t = ln(t, M, H, "vision_model.pre_layrnorm.weight", "vision_model.pre_layrnorm.bias");
         for (int i = 0; i < c.num_layers; ++i) {
-            t = clip_encoder_layer(vit_layer(i), t, M, L, H, I, c.num_heads, OP_VIT_ATTN);
+            t = clip_encoder_layer(vit_layer(i), t, M, L, H, I, c.num_heads, OP_VIT_ATTN, c.hidden_act == SD_ACT_GELU);
             pl.taps["layer" + std::to_string(i)] = t;
         }
         int pr;
@@ -545,6 +569,15 @@ struct Builder {
         pl.ctx_bf16 = ctx_tensor((size_t)UB * L * c.cross_attention_dim * 2);
         // masked K / V expansions used by sd_unet_set_context for the folded cross-attention (sized for the widest level)
         pl.ctx_fold_scratch = ctx_tensor((size_t)3 * UB * c.num_heads * 80 * c.block_out_channels[nl - 1] * 2);
+        if (pl.ip) {      // what sd_unet_set_ip_adapter_hw computes on the way to the folded operands (its expansions reuse the scratch above)
+            const int T = c.ip_adapter_tokens, CD = c.cross_attention_dim;
+            int cmax = 0;
+            for (int i = 0; i < nl; ++i) cmax = std::max(cmax, c.block_out_channels[i]);
+            pl.ip_e = ctx_ip_tensor((size_t)UB * c.ip_adapter_embed_dim * 2);
+            pl.ip_proj = ctx_ip_tensor((size_t)UB * T * CD * 2);
+            pl.ip_tok = ctx_ip_tensor((size_t)UB * T * CD * 2);
+            pl.ip_kv = ctx_ip_tensor((size_t)UB * T * 2 * cmax * 2);
+        }
         // ---- time embedding (M = 1: the reference passes one scalar t per call) ----
         int t_sin = tensor((size_t)c0 * 4), t_h1 = tensor((size_t)temb * 4), t_emb = tensor((size_t)temb * 4);
         int t_proj = tensor((size_t)u->tproj_total * 4);
@@ -721,7 +754,9 @@ void assign_memory(sd_unet* u, Plan& pl) {
     // persistent region
     size_t off = 0;
     for (auto& t : pl.tensors)               // what sd_unet_set_context writes: first, so every variant agrees on it
-        if (t.ctx) { t.off = off; off += t.bytes; }
+        if (t.ctx && !t.ctx_ip) { t.off = off; off += t.bytes; }
+    for (auto& t : pl.tensors)               // ... then what sd_unet_set_ip_adapter_hw writes: the prompt's tensors sit where the
+        if (t.ctx_ip) { t.off = off; off += t.bytes; }      // plans without an image prompt have them
     for (auto& t : pl.tensors)
         if (t.persistent && !t.ctx) { t.off = off; off += t.bytes; }
     const size_t arena0 = off;
@@ -773,14 +808,18 @@ int check_latent_size(const sd_unet* u, int lh, int lw, const char* who) {
     return 0;
 }
 
-int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw) {
+bool ip_active(const sd_unet* u, int UB, int branch, int lh, int lw) {
+    return u->ip_keys.count(std::make_tuple(UB, branch < 0 ? -1 : branch, lh, lw)) != 0;
+}
+
+int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw, int ip) {
     SD_REQUIRE(u && u->finalized, "unet: parameters not finalized");
     SD_REQUIRE(UB > 0 && UB <= 4096, "unet: bad batch %d", UB);
     SD_REQUIRE(branch < 3 * u->cfg.num_levels, "unet: cache_branch_id %d out of range", branch);
     if (branch < 0) branch = -1;
     if (lh < 0) lh = u->cfg.sample_size;
     if (lw < 0) lw = u->cfg.sample_size;
-    auto key = std::make_tuple(UB, branch, rep, lh, lw);
+    auto key = std::make_tuple(UB, branch, rep, lh, lw, ip);
     auto it = u->plans.find(key);
     if (it == u->plans.end()) {
         if (lh != u->cfg.sample_size || lw != u->cfg.sample_size)
@@ -791,6 +830,7 @@ int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw
         pl.rep = rep;
         pl.lh = lh;
         pl.lw = lw;
+        pl.ip = ip;
         Builder b{u, pl, UB, {}};
         b.build();
         SD_REQUIRE(b.error.empty(), "unet: cannot build the plan for batch %d (cache branch %d, latent %dx%d): %s", UB, branch, lh, lw,

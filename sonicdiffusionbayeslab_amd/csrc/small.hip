@@ -602,11 +602,12 @@ int sd_launch_gemv(const float* x, const bf16_t* W, const float* b, float* y, in
     return 0;
 }
 
-// out[b][h*80 + j][c] = (j < L and c in head h) ? scale * kv[b*L + j][col_off + c] : 0   (kv rows are [K | V], 2C wide)
+// out[b][h*S + j][c] = (j < L and c in head h) ? scale * kv[b*L + j][col_off + c] : 0   (kv rows are [K | V], 2C wide; S key
+// slots per head: 80 for the prompt)
 __global__ void xattn_expand_kernel(const bf16_t* __restrict__ kv, bf16_t* __restrict__ out, int L, int C, int NH,
-                                    int col_off, float scale) {
-    const int row = blockIdx.x;                       // b * NH * 80 + h * 80 + j
-    const int j = row % 80, h = (row / 80) % NH, b = row / (80 * NH);
+                                    int col_off, float scale, int S) {
+    const int row = blockIdx.x;                       // b * NH * S + h * S + j
+    const int j = row % S, h = (row / S) % NH, b = row / (S * NH);
     const int d = C / NH;
     const bf16_t* src = kv + ((long)b * L + (j < L ? j : 0)) * 2 * C + col_off;
     bf16_t* dst = out + (long)row * C;
@@ -689,10 +690,10 @@ int sd_launch_retile32(const bf16_t* src, bf16_t* dst, int B, int R, int K, int 
 }
 
 int sd_launch_xattn_expand(const bf16_t* kv, bf16_t* out, int B, int L, int C, int NH, int col_off, float scale,
-                           hipStream_t stream) {
-    SD_REQUIRE(kv && out && B > 0 && L > 0 && L <= 80 && NH > 0 && C % NH == 0 && (C / NH) % 2 == 0,
-               "xattn_expand: B=%d L=%d C=%d heads=%d", B, L, C, NH);
-    hipLaunchKernelGGL(xattn_expand_kernel, dim3(B * NH * 80), dim3(128), 0, stream, kv, out, L, C, NH, col_off, scale);
+                           hipStream_t stream, int slots) {
+    SD_REQUIRE(kv && out && B > 0 && L > 0 && slots > 0 && L <= slots && NH > 0 && C % NH == 0 && (C / NH) % 2 == 0,
+               "xattn_expand: B=%d L=%d C=%d heads=%d slots=%d", B, L, C, NH, slots);
+    hipLaunchKernelGGL(xattn_expand_kernel, dim3(B * NH * slots), dim3(128), 0, stream, kv, out, L, C, NH, col_off, scale, slots);
     SD_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -160,6 +160,10 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
             }
             return sd_launch_xattn_fused(a, stream);
         }
+        case OP_IP_XATTN:
+            return sd_launch_ip_xattn((const bf16_t*)T(o.x1), (bf16_t*)T(o.out), (const bf16_t*)T(o.wt), (const bf16_t*)T(o.x2),
+                                      (const float*)(wb + o.g), (const float*)(wb + o.be), o.eps, o.M, o.N, o.rpb, o.heads,
+                                      u->cfg.ip_adapter_tokens, stream);
         case OP_REPLICATE:
             return sd_launch_replicate(T(o.x1), T(o.out), (long)o.M * 16, o.N, stream);
         case OP_CLIP_EMBED:
@@ -168,6 +172,7 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
         case OP_CLIP_ATTN:
             return sd_launch_clip_attention((const bf16_t*)T(o.x1), (bf16_t*)T(o.out), o.B, o.Nq, o.N, o.heads, stream);
         case OP_QGELU:
+            if (o.epi) return sd_launch_gelu_erf((bf16_t*)T(o.x1), (long)o.M * o.N, stream);
             return sd_launch_quick_gelu((bf16_t*)T(o.x1), (long)o.M * o.N, stream);
         case OP_VIT_PREP:
             return sd_launch_clip_preprocess((const unsigned char*)latents, o.B, pl.geom, pl.dtab, (unsigned char*)T(o.aux),
@@ -210,7 +215,7 @@ static sd_unet* new_handle(int kind, const sd_unet_config* cfg) {
     u->kind = kind;
     if (cfg) {
         u->cfg = *cfg;
-        if (kind != 0) u->cfg.time_cond_proj_dim = 0;      // (a UNet field)
+        if (kind != 0) u->cfg.time_cond_proj_dim = u->cfg.ip_adapter_tokens = u->cfg.ip_adapter_embed_dim = 0;      // (UNet fields)
         u->debug_taps = getenv("SD_DEBUG_TAPS") != nullptr;
     } else {
         memset(&u->cfg, 0, sizeof(u->cfg));
@@ -274,6 +279,17 @@ extern "C" int sd_unet_create(const sd_unet_config* cfg, sd_unet** out) {
     SD_REQUIRE(cfg->time_cond_proj_dim >= 0 && cfg->time_cond_proj_dim % 8 == 0,
                "sd_unet_create: time_cond_proj_dim %d must be 0 (none) or a positive multiple of 8 (the GEMV reads 8 at a time)",
                cfg->time_cond_proj_dim);
+    if (cfg->ip_adapter_tokens != 0 || cfg->ip_adapter_embed_dim != 0) {
+        SD_REQUIRE(cfg->ip_adapter_tokens == 4, "sd_unet_create: ip_adapter_tokens %d (4 image tokens are built: the plain ip-adapter_sd15 "
+                   "family; the \"plus\" / \"full-face\" adapters with 16 or 257 tokens are not)", cfg->ip_adapter_tokens);
+        SD_REQUIRE(cfg->ip_adapter_embed_dim > 0 && cfg->ip_adapter_embed_dim % 64 == 0,
+                   "sd_unet_create: ip_adapter_embed_dim %d must be a positive multiple of 64", cfg->ip_adapter_embed_dim);
+        SD_REQUIRE(cfg->cross_attention_dim <= 1536, "sd_unet_create: an IP-Adapter needs cross_attention_dim <= 1536 (the token LayerNorm)");
+        for (int i = 0; i < cfg->num_levels; ++i)
+            SD_REQUIRE(sd_ip_xattn_applicable(cfg->block_out_channels[i], cfg->num_heads, cfg->ip_adapter_tokens),
+                       "sd_unet_create: an IP-Adapter needs 1, 2, 4 or 8 heads and channels that are a multiple of 32 up to 2048 "
+                       "(level %d: %d channels, %d heads)", i, cfg->block_out_channels[i], cfg->num_heads);
+    }
     sd_unet* u = new_handle(0, cfg);
     u->fp8 = cfg->weight_dtype == SD_DTYPE_FP8_E4M3;
     if (cfg->fp8_act_scale_norm > 0.f) u->s_norm = cfg->fp8_act_scale_norm;
@@ -425,8 +441,11 @@ extern "C" int sd_clip_vision_create(const sd_clip_vision_config* cfg, sd_unet**
                "sd_clip_vision_create: hidden %d / intermediate %d must be positive multiples of 64", c.hidden_size,
                c.intermediate_size);
     SD_REQUIRE(c.hidden_size <= 1536, "sd_clip_vision_create: hidden size %d (LayerNorm kernel handles <= 1536)", c.hidden_size);
-    SD_REQUIRE(c.num_heads > 0 && c.hidden_size % c.num_heads == 0 && c.hidden_size / c.num_heads == 64,
-               "sd_clip_vision_create: head dim %d (64 is built)", c.num_heads > 0 ? c.hidden_size / c.num_heads : 0);
+    SD_REQUIRE(c.num_heads > 0 && c.hidden_size % c.num_heads == 0 &&
+                   (c.hidden_size / c.num_heads == 64 || c.hidden_size / c.num_heads == 80),
+               "sd_clip_vision_create: head dim %d (64 and 80 are built)", c.num_heads > 0 ? c.hidden_size / c.num_heads : 0);
+    SD_REQUIRE(c.hidden_act == SD_ACT_QUICK_GELU || c.hidden_act == SD_ACT_GELU,
+               "sd_clip_vision_create: hidden_act %d (0 = quick_gelu, 1 = gelu)", c.hidden_act);
     SD_REQUIRE(c.patch_size >= 1 && c.image_size >= c.patch_size && c.image_size % c.patch_size == 0,
                "sd_clip_vision_create: image_size %d / patch_size %d", c.image_size, c.patch_size);
     const int G = c.image_size / c.patch_size;
@@ -553,10 +572,12 @@ extern "C" long long sd_unet_workspace_bytes_hw(sd_unet* u, int unet_batch, int 
     Plan* pl;
     if (get_plan(u, unet_batch, cache_branch_id, &pl, 1, latent_h, latent_w)) return -1;
     size_t bytes = pl->total_bytes;
-    if (unet_batch % 2 == 0 && plan_rep(u, unet_batch / 2, unet_batch) == 2) {      // the CFG-pair variant of the plan
-        if (get_plan(u, unet_batch, cache_branch_id, &pl, 2, latent_h, latent_w)) return -1;
-        bytes = std::max(bytes, pl->total_bytes);
-    }
+    const bool pair = unet_batch % 2 == 0 && plan_rep(u, unet_batch / 2, unet_batch) == 2;      // the CFG-pair variant of the plan
+    for (int ip = 0; ip <= (u->kind == 0 && u->cfg.ip_adapter_tokens > 0 ? 1 : 0); ++ip)         // ... and the IP-Adapter variants
+        for (int rep = 1; rep <= (pair ? 2 : 1); ++rep) {
+            if (get_plan(u, unet_batch, cache_branch_id, &pl, rep, latent_h, latent_w, ip)) return -1;
+            bytes = std::max(bytes, pl->total_bytes);
+        }
     return (long long)bytes;
 }
 
@@ -675,6 +696,75 @@ extern "C" int sd_unet_set_inpaint_cond_hw(sd_unet* u, void* stream, const float
     return 0;
 }
 
+// ---- IP-Adapter image prompt (diffusers IPAdapterAttnProcessor2_0 + ImageProjection, upstream-recall) ----
+// a forward of a handle that has an image prompt set somewhere must find one for ITS (batch, branch, size)
+static int check_ip_set(const sd_unet* u, const char* who, int unet_batch, int cache_branch_id, int latent_h, int latent_w) {
+    SD_REQUIRE(ip_active(u, unet_batch, cache_branch_id, latent_h, latent_w),
+               "%s: the handle runs with an IP-Adapter image prompt, but none is set for batch %d, cache branch %d at %dx%d "
+               "(sd_unet_set_ip_adapter_hw after sd_unet_set_context_hw, same workspace; image_embeds = NULL clears the others)",
+               who, unet_batch, cache_branch_id < 0 ? -1 : cache_branch_id, latent_h, latent_w);
+    return 0;
+}
+
+extern "C" int sd_unet_set_ip_adapter_hw(sd_unet* u, void* stream, const float* image_embeds, int unet_batch, int cache_branch_id,
+                                         int latent_h, int latent_w, float scale, void* workspace, long long workspace_bytes) {
+    SD_REQUIRE(u && u->kind == 0, "set_ip_adapter: not a UNet handle");
+    const sd_unet_config& c = u->cfg;
+    SD_REQUIRE(c.ip_adapter_tokens > 0, "set_ip_adapter: the UNet was created without an IP-Adapter (ip_adapter_tokens = 0)");
+    const auto key = std::make_tuple(unet_batch, cache_branch_id < 0 ? -1 : cache_branch_id, latent_h, latent_w);
+    if (!image_embeds) {        // clear: nothing is launched
+        u->ip_keys.erase(key);
+        return 0;
+    }
+    SD_REQUIRE(workspace, "set_ip_adapter: null workspace");
+    SD_REQUIRE(((uintptr_t)image_embeds & 15) == 0, "set_ip_adapter: image_embeds must be 16-byte aligned");
+    SD_REQUIRE(scale == scale && fabsf(scale) <= 1e4f, "set_ip_adapter: scale %g", scale);
+    if (check_latent_size(u, latent_h, latent_w, "set_ip_adapter")) return -1;
+    Plan* plp;
+    int rc = get_plan(u, unet_batch, cache_branch_id, &plp, 1, latent_h, latent_w, 1);
+    if (rc) return rc;
+    const Plan& pl = *plp;
+    if (check_workspace(pl, "set_ip_adapter", workspace, workspace_bytes)) return -1;
+    u->ip_keys.erase(key);      // (set again only once every launch below is enqueued)
+    char* ws = (char*)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    auto TP = [&](int id) { return (bf16_t*)(ws + pl.tensors[id].off); };
+    auto WF = [&](const char* k) { return (const float*)(u->dweights + u->woff.at(k)); };
+    auto gemm = [&](const bf16_t* X, int rows, int K, size_t w, int N, const float* bias, bf16_t* out) {      // out [rows][N] = X [rows][K] . W[N][K]^T + bias
+        GemmArgs a;
+        a.X = X; a.ldx = K; a.K1 = K; a.K = K; a.M = rows; a.N = N;
+        a.W = (const bf16_t*)(u->dweights + w); a.bias = bias;
+        a.C = out; a.ldc = N;
+        a.zero_page = g_zero_page;
+        return sd_launch_gemm(a, 0, st);
+    };
+    const int T = c.ip_adapter_tokens, E = c.ip_adapter_embed_dim, CD = c.cross_attention_dim, NH = c.num_heads, UB = unet_batch;
+    const std::string ipj = "encoder_hid_proj.image_projection_layers.0.";
+    // ImageProjection: tokens = LayerNorm(Linear(image_embeds).reshape(UB, T, CD))
+    if ((rc = sd_launch_f32_to_bf16(image_embeds, TP(pl.ip_e), (long)UB * E, st))) return rc;
+    if ((rc = gemm(TP(pl.ip_e), UB, E, u->woff.at(ipj + "image_embeds.weight"), T * CD, WF((ipj + "image_embeds.bias").c_str()), TP(pl.ip_proj))))
+        return rc;
+    if ((rc = sd_launch_layernorm(TP(pl.ip_proj), WF((ipj + "norm.weight").c_str()), WF((ipj + "norm.bias").c_str()), TP(pl.ip_tok), UB * T,
+                                  CD, 1e-5f, st))) return rc;
+    // per block: K_ip | V_ip, their per-head expansions over 32 key slots (32 / heads per head, T of them used), and the folds
+    //   A [UB][32][C] = (K_ip / sqrt d)_expanded . W_q      Bt [UB][C][32] = ((scale V_ip)_expanded . W_o^T)^T
+    const int SPH = 32 / NH;
+    for (const Plan::IpFold& f : pl.ip_fold) {
+        const int C = f.C, d = C / NH;
+        bf16_t* kexp = TP(pl.ctx_fold_scratch);
+        bf16_t* vexp = kexp + (size_t)UB * 32 * C;
+        bf16_t* tmp = vexp + (size_t)UB * 32 * C;
+        if ((rc = gemm(TP(pl.ip_tok), UB * T, CD, f.wkv, 2 * C, nullptr, TP(pl.ip_kv)))) return rc;
+        if ((rc = sd_launch_xattn_expand(TP(pl.ip_kv), kexp, UB, T, C, NH, 0, 1.0f / sqrtf((float)d), st, SPH))) return rc;
+        if ((rc = sd_launch_xattn_expand(TP(pl.ip_kv), vexp, UB, T, C, NH, C, scale, st, SPH))) return rc;
+        if ((rc = gemm(kexp, UB * 32, C, f.wqT, C, nullptr, TP(f.at)))) return rc;
+        if ((rc = gemm(vexp, UB * 32, C, f.wo, C, nullptr, tmp))) return rc;
+        if ((rc = sd_launch_transpose_bf16(tmp, TP(f.bt), UB, 32, C, st))) return rc;
+    }
+    u->ip_keys.insert(key);
+    return 0;
+}
+
 extern "C" int sd_unet_forward(sd_unet* u, void* stream, const float* latents, int latent_batch, int unet_batch,
                                float timestep, float* eps_out, void* workspace, long long workspace_bytes,
                                int cache_mode, int cache_branch_id) {
@@ -695,9 +785,11 @@ extern "C" int sd_unet_forward_hw(sd_unet* u, void* stream, const float* latents
     SD_REQUIRE(cache_mode == SD_CACHE_OFF || cache_branch_id >= 0, "forward: DeepCache modes need cache_branch_id >= 0");
     Plan* pl;
     const int rep = plan_rep(u, latent_batch, unet_batch);
-    u->last_rep = rep;
+    const int ip = u->ip_keys.empty() ? 0 : 1;
+    if (ip && check_ip_set(u, "forward", unet_batch, cache_branch_id, latent_h, latent_w)) return -1;
+    u->last_rep = rep; u->last_ip = ip;
     u->last_h = latent_h; u->last_w = latent_w;
-    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, latent_h, latent_w);
+    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, latent_h, latent_w, ip);
     if (rc) return rc;
     return run_plan(u, *pl, "forward", workspace, workspace_bytes, latents, latent_batch, eps_out, timestep, stream, cache_mode);
 }
@@ -728,6 +820,9 @@ extern "C" int sd_unet_calibrate_fp8(sd_unet* u, void* stream, const float* late
     int rc = get_plan(u, unet_batch, -1, &plp, rep);
     if (rc) return rc;
     if (check_workspace(*plp, "calibrate_fp8", workspace, workspace_bytes)) return -1;
+    // calibration runs the plan WITHOUT an image prompt, whose activations lie where the "IP on" plan keeps the folded
+    // image operands: every image prompt of the handle is gone after it, so a later forward asks for it by name
+    u->ip_keys.clear();
     hipStream_t st = (hipStream_t)stream;
     unsigned* dmax = (unsigned*)op_scratch(256);
     SD_REQUIRE(dmax, "calibrate_fp8: cannot allocate scratch");
@@ -828,6 +923,10 @@ static void op_work(const Op& o, double* flops, double* bytes) {
         case OP_REPLICATE:
             *bytes = 16.0 * o.M * (1.0 + o.N);
             break;
+        case OP_IP_XATTN:   // scores and P B over the 32 image-key slots; R in, R' out
+            *flops = 4.0 * o.M * 32.0 * o.N;
+            *bytes = 2.0 * 2.0 * o.M * o.N;
+            break;
         default:
             break;
     }
@@ -843,9 +942,11 @@ static int profiled_run(sd_unet* u, void* stream, const float* latents, int late
     SD_REQUIRE(latent_batch > 0 && unet_batch % latent_batch == 0, "forward_profiled: bad batch");
     Plan* pl;
     const int rep = plan_rep(u, latent_batch, unet_batch);
-    u->last_rep = rep;
+    const int ip = u->ip_keys.empty() ? 0 : 1;
+    if (ip && check_ip_set(u, "forward_profiled", unet_batch, cache_branch_id, u->cfg.sample_size, u->cfg.sample_size)) return -1;
+    u->last_rep = rep; u->last_ip = ip;
     u->last_h = u->last_w = u->cfg.sample_size;
-    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep);
+    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, -1, -1, ip);
     if (rc) return rc;
     *plan = pl;
     SD_REQUIRE((long long)pl->total_bytes <= workspace_bytes, "forward_profiled: workspace too small");
@@ -904,7 +1005,7 @@ extern "C" int sd_unet_forward_profiled(sd_unet* u, void* stream, const float* l
             a.w_batch_stride = (long)o.N * 4 * o.Cin;
             halo4 = sd_conv_halo_subpix_applicable(a);
         }
-        const int kd = o.kind == OP_XATTN ? 18 : o.kind == OP_REPLICATE ? 19 : halo4 ? 21 :
+        const int kd = o.kind == OP_XATTN ? 18 : o.kind == OP_REPLICATE ? 19 : o.kind == OP_IP_XATTN ? 22 : halo4 ? 21 :
                        (o.kind == OP_CONV3 && !o.dt && (o.subpix || o.stride != 1)) ? 20 :
                        (o.dt ? (o.kind == OP_CONV3 ? 16 : 17) : o.kind);
         kind_ms[kd] += ms; kind_launches[kd] += 1; kind_flops[kd] += fl; kind_bytes[kd] += by;
@@ -941,7 +1042,7 @@ extern "C" int sd_unet_debug_tensor(sd_unet* u, void* stream, const char* name, 
                                     void* workspace, int unet_batch, int cache_branch_id) {
     SD_REQUIRE(u && u->debug_taps, "debug_tensor: create the handle with SD_DEBUG_TAPS=1 in the environment");
     Plan* pl;
-    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, u->last_rep, u->last_h > 0 ? u->last_h : -1, u->last_w > 0 ? u->last_w : -1);
+    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, u->last_rep, u->last_h > 0 ? u->last_h : -1, u->last_w > 0 ? u->last_w : -1, u->last_ip);
     if (rc) return rc;
     auto it = pl->taps.find(name);
     SD_REQUIRE(it != pl->taps.end(), "debug_tensor: unknown tap '%s'", name);

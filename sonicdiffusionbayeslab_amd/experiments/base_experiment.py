@@ -186,6 +186,9 @@ class BaseMethod(ABC):
             sharded = sdist.active()
             lo, hi = sdist.shard_range(len(prompts), self.rank, self.world) if sharded else (0, len(prompts))
             local_prompts = prompts[lo:hi]
+            if sharded and (call_kwargs.get("ip_adapter_image") is not None or call_kwargs.get("ip_adapter_image_embeds") is not None):
+                # an IP-Adapter image prompt given per prompt is sliced with the prompts, as image= is below
+                call_kwargs = self.model.shard_ip_adapter_args(call_kwargs, lo, hi, len(prompts))
             if getattr(self, "img2img_strength", None) is not None and len(local_prompts) > 0:
                 # image-to-image: this rank's slice of the batch's start images rides with its slice of the prompts
                 call_kwargs = {**call_kwargs, "image": self.load_images(list(batch["image_file"])[lo:hi]),

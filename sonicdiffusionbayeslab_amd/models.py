@@ -140,6 +140,15 @@ class StableDiffusionModel:
         self._fp8_calibrated = False    # fp8 handles: per-tensor activation scales, calibrated once on a FIXED seeded batch
         self._size = None               # (height, width) in pixels of the current call, set by _begin
         self.fp8_scales = {}            # {tensor name: scale} in use (reported by the harness next to the results)
+        # IP-Adapter (load_ip_adapter): its UNet-named weights until the handle is built, the scale of the image branch, the
+        # local image_encoder directory (ip_adapter_image) and its tower, and the embeds of the call in progress
+        self._ip_sd = None
+        self._ip_loaded = False
+        self._ip_source = None          # what load_ip_adapter appended to weights_source (unload_ip_adapter takes it off)
+        self._ip_scale = 1.0
+        self._ip_encoder_dir = None
+        self._ip_encoder = None
+        self._ip_pending = None
 
     # -- loading ---------------------------------------------------------------------------
     @classmethod
@@ -173,6 +182,8 @@ class StableDiffusionModel:
     def _ensure_unet(self):
         if self.unet is None:
             sd = self._state_dict or make_synthetic_state_dict(self.unet_config, self._weights_seed)
+            if self._ip_sd is not None:
+                sd = {**sd, **self._ip_sd}
             for item in self._lora:
                 if item[0] == "file":
                     from .weights import fuse_lora_state_dict
@@ -186,6 +197,7 @@ class StableDiffusionModel:
             if self.unet.weight_dtype != "bf16":
                 self.weights_source += f" [{self.unet.weight_dtype} weights + activations in the conv / FF / QKV contractions]"
             self._state_dict = None
+            self._ip_sd = None
 
     def _ensure_vae(self):
         """AutoencoderKL decoder on libsdhip; local weights if the model directory has
@@ -250,6 +262,235 @@ class StableDiffusionModel:
         if getattr(self, "_pending_lora", None) is not None:
             self._lora.append(self._pending_lora)
             self._pending_lora = None
+
+    # -- IP-Adapter image prompts (diffusers IPAdapterMixin, upstream-recall; DESIGN.md "IP-Adapter") ----------------------
+    IP_ADAPTER_EMBED_DIM = 1024         # image_embeds width of the published ip-adapter_sd15 (CLIP ViT-H/14 projection)
+
+    def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder=None, weight_name=None,
+                        image_encoder_folder="image_encoder"):
+        """``pipe.load_ip_adapter(...)`` for ONE plain adapter (``ip-adapter_sd15``: ImageProjection, 4 image tokens).  Like
+        ``load_lora_weights`` it must run before the model moves to the GPU.  A local file, or a local directory with
+        ``[subfolder/]weight_name`` (``.safetensors`` or ``.bin``, upstream layout), is read for real and its
+        ``image_encoder_folder`` -- relative to the subfolder as upstream resolves it, or to the directory -- serves
+        ``ip_adapter_image``; a hub NAME is a network fetch, for which seeded synthetic adapter weights of the
+        published shape stand in (``weights_source`` says so; only ``ip_adapter_image_embeds`` works then)."""
+        import dataclasses
+        from .weights import load_ip_adapter_state_dict, make_synthetic_ip_adapter_state_dict
+        if self.unet is not None:
+            raise RuntimeError("load_ip_adapter must be called before the model is moved to the GPU")
+        src = pretrained_model_name_or_path_or_dict
+        if isinstance(src, (list, tuple)) or isinstance(weight_name, (list, tuple)) or isinstance(subfolder, (list, tuple)):
+            raise NotImplementedError("load_ip_adapter: several IP-Adapters at once are not built (one adapter, one image per sample)")
+        if self._ip_loaded:
+            raise NotImplementedError("load_ip_adapter: an adapter is already loaded (several at once are not built; unload_ip_adapter first)")
+        if isinstance(src, dict):
+            raise NotImplementedError("load_ip_adapter: pass a local file or directory (a state dict goes through "
+                                      "weights.map_ip_adapter_state_dict)")
+        path = str(src)
+        base = self.unet_config
+        if os.path.isdir(path):
+            root = os.path.join(path, subfolder) if subfolder else path
+            if weight_name is None:
+                raise ValueError("load_ip_adapter: weight_name is needed with a directory (e.g. 'ip-adapter_sd15.safetensors')")
+            file = os.path.join(root, weight_name)
+        else:
+            root, file = os.path.dirname(path), path
+        if os.path.isfile(file):
+            sd, e = load_ip_adapter_state_dict(file, base)
+            self._ip_source = f" + IP-Adapter(local:{file})"
+            if image_encoder_folder is not None:
+                for cand in (os.path.join(root, image_encoder_folder), os.path.join(os.path.dirname(root), image_encoder_folder),
+                             os.path.join(path, image_encoder_folder) if os.path.isdir(path) else None):
+                    if cand and os.path.isfile(os.path.join(cand, "config.json")):
+                        self._ip_encoder_dir = cand
+                        break
+        elif os.path.isdir(path) or not self._looks_like_hub_name(path):
+            raise FileNotFoundError(f"load_ip_adapter: no adapter file at {file!r}")
+        else:
+            seed = int.from_bytes(hashlib.sha256(f"{path}/{subfolder}/{weight_name}".encode()).digest()[:4], "little")
+            e = self.IP_ADAPTER_EMBED_DIM
+            sd = make_synthetic_ip_adapter_state_dict(dataclasses.replace(base, ip_adapter_embed_dim=e), seed)
+            self._ip_source = f" + SYNTHETIC stand-in for the hub IP-Adapter {path} (seed={seed})"
+        self.weights_source += self._ip_source
+        self.unet_config = dataclasses.replace(base, ip_adapter_embed_dim=e)
+        self._ip_sd, self._ip_loaded = sd, True
+
+    @staticmethod
+    def _looks_like_hub_name(path: str) -> bool:
+        """``name`` or ``org/name`` of hub characters, nothing that only a file system path has: not absolute, no ``.`` / ``..``
+        / ``~`` component, no weight-file extension, no second separator.  Anything else that does not exist is a mistyped
+        local path and raises, so that random stand-in weights never replace a checkpoint the caller meant to load."""
+        import re
+        if os.path.isabs(path) or path.lower().endswith((".safetensors", ".bin", ".pt", ".pth", ".ckpt")):
+            return False
+        parts = path.split("/")
+        return 1 <= len(parts) <= 2 and all(re.fullmatch(r"[A-Za-z0-9][A-Za-z0-9._\-]*", q) and q != ".." for q in parts)
+
+    def set_ip_adapter_scale(self, scale):
+        """One float for every block (diffusers' per-block dicts are not built); applies from the next call on."""
+        if isinstance(scale, (dict, list, tuple)):
+            raise NotImplementedError("set_ip_adapter_scale: one float (per-block scale dicts and per-adapter lists are not built)")
+        if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(float(scale)):
+            raise ValueError(f"set_ip_adapter_scale: scale={scale!r} must be a finite number")
+        self._ip_scale = float(scale)
+
+    def unload_ip_adapter(self):
+        """Calls run without an image prompt again (``ip_adapter_image*`` arguments are refused).  Before the model has
+        moved to the GPU the adapter's weights are dropped as well; afterwards they stay in the handle, unused."""
+        import dataclasses
+        self._ip_loaded = False
+        self._ip_encoder_dir, self._ip_encoder, self._ip_pending = None, None, None
+        src = self._ip_source
+        if src and self.weights_source.endswith(src):
+            self.weights_source = self.weights_source[:-len(src)]
+        elif src:
+            self.weights_source = self.weights_source.replace(src, "", 1)
+        self._ip_source = None
+        if self.unet is None:
+            self._ip_sd = None
+            self.unet_config = dataclasses.replace(self.unet_config, ip_adapter_embed_dim=None, ip_adapter_tokens=None)
+        else:
+            self.unet.clear_ip_adapter()
+
+    IP_ARGS_RULE = "ip_adapter_image and ip_adapter_image_embeds are exclusive: pass one of them"
+
+    def _ip_adapter_args(self, ip_adapter_image, ip_adapter_image_embeds, batch_size: int, do_cfg: bool):
+        """Every check of the two image-prompt arguments, on the host, before any GPU work.  Returns None (no image prompt),
+        ("embeds", positive [B, E], negative [B, E] or None) or ("image", uint8 [B,3,H,W])."""
+        if ip_adapter_image is None and ip_adapter_image_embeds is None:
+            return None
+        if ip_adapter_image is not None and ip_adapter_image_embeds is not None:
+            raise ValueError(self.IP_ARGS_RULE)
+        if not self._ip_loaded or self.unet_config.ip_adapter_embed_dim is None:
+            raise ValueError("ip_adapter_image / ip_adapter_image_embeds need a loaded IP-Adapter (load_ip_adapter before the model "
+                             "moves to the GPU)")
+        e = self.unet_config.ip_adapter_embed_dim
+        if ip_adapter_image_embeds is not None:
+            emb = ip_adapter_image_embeds
+            if isinstance(emb, (list, tuple)):
+                if len(emb) != 1:
+                    raise NotImplementedError(f"ip_adapter_image_embeds: a list of {len(emb)} (several IP-Adapters at once are not built)")
+                emb = emb[0]
+            if not torch.is_tensor(emb) or not emb.is_floating_point():
+                raise ValueError("ip_adapter_image_embeds must be a float tensor or a one-element list of one")
+            if emb.dim() == 3:
+                if emb.shape[1] != 1:
+                    raise NotImplementedError(f"ip_adapter_image_embeds {tuple(emb.shape)}: several images per sample are not built")
+                emb = emb[:, 0]
+            if emb.dim() != 2 or emb.shape[1] != e:
+                raise ValueError(f"ip_adapter_image_embeds must be [B, {e}] or [B, 1, {e}] (E = {e} of the loaded adapter), got "
+                                 f"{tuple(ip_adapter_image_embeds[0].shape if isinstance(ip_adapter_image_embeds, (list, tuple)) else ip_adapter_image_embeds.shape)}")
+            emb = emb.detach().to("cpu", torch.float32)
+            n, neg = int(emb.shape[0]), None
+            if do_cfg and n == 2 * batch_size and batch_size >= 1 and n != 1:
+                neg, emb = emb[:batch_size], emb[batch_size:]         # negative first, like the prompt
+            elif n == 1:
+                emb = emb.expand(batch_size, e)
+            elif n != batch_size:
+                raise ValueError(f"ip_adapter_image_embeds batch {n} does not match the prompt batch {batch_size} "
+                                 f"(B, 1, or 2 B = negative | positive under CFG)")
+            return ("embeds", emb, neg)
+        img = ip_adapter_image
+        if isinstance(img, (list, tuple)) and len(img) > 0 and isinstance(img[0], (list, tuple)):
+            raise NotImplementedError("ip_adapter_image: nested lists (several IP-Adapters or several images per sample) are not built")
+        if hasattr(img, "convert"):
+            img = [img]
+        if isinstance(img, (list, tuple)) and len(img) > 0 and all(hasattr(im, "convert") for im in img):
+            import numpy as np
+            sizes = {im.size for im in img}
+            if len(sizes) != 1:
+                raise ValueError(f"ip_adapter_image: the PIL images of one call must have one size, got {sorted(sizes)}")
+            img = torch.from_numpy(np.stack([np.asarray(im.convert("RGB"), dtype=np.uint8) for im in img])).permute(0, 3, 1, 2)
+        if not torch.is_tensor(img) or img.dim() != 4 or img.shape[1] != 3:
+            raise ValueError("ip_adapter_image must be a list of PIL images of one size or a uint8 / float [B,3,H,W] tensor")
+        if img.is_floating_point():
+            img = (img.clamp(0, 1) * 255.0).round().to(torch.uint8)       # (what VaeImageProcessor's 'pil' output holds)
+        elif img.dtype != torch.uint8:
+            raise ValueError(f"ip_adapter_image: dtype {img.dtype} (uint8, or floats in [0, 1])")
+        if img.shape[0] == 1 and batch_size > 1:
+            img = img.expand(batch_size, -1, -1, -1)
+        if img.shape[0] != batch_size:
+            raise ValueError(f"ip_adapter_image batch {img.shape[0]} does not match the prompt batch {batch_size}")
+        self._ip_image_encoder_config()          # (refuses a missing or unbuilt encoder by name, still on the host)
+        return ("image", img.contiguous())
+
+    def _ip_image_encoder_config(self):
+        """(ClipVisionConfig, hidden_act) of the adapter's ``image_encoder`` directory, checked against what the HIP vision
+        tower builds and against the adapter's embed dim."""
+        import json
+        from .clip_score import ClipVisionConfig, check_vision_config
+        d = self._ip_encoder_dir
+        if d is None:
+            raise ValueError("ip_adapter_image needs the adapter's image encoder: no local image_encoder directory was found by "
+                             "load_ip_adapter (pass ip_adapter_image_embeds instead)")
+        with open(os.path.join(d, "config.json"), encoding="utf-8") as f:
+            j = json.load(f)
+        j = {**j.get("vision_config", {}), **{k: v for k, v in j.items() if k != "vision_config"}}
+        cfg = ClipVisionConfig(hidden_size=int(j["hidden_size"]), num_hidden_layers=int(j["num_hidden_layers"]),
+                               num_attention_heads=int(j["num_attention_heads"]), intermediate_size=int(j["intermediate_size"]),
+                               image_size=int(j.get("image_size", 224)), patch_size=int(j.get("patch_size", 14)),
+                               projection_dim=int(j.get("projection_dim", 512)), layer_norm_eps=float(j.get("layer_norm_eps", 1e-5)),
+                               hidden_act=str(j.get("hidden_act", "quick_gelu")))
+        try:
+            check_vision_config(cfg, extended=True)        # (also ViT-H/14: head dim 80, exact gelu)
+        except ValueError as err:
+            raise NotImplementedError(f"ip_adapter_image: the image encoder at {d!r} is not built by the HIP vision tower ({err}); "
+                                      "pass ip_adapter_image_embeds") from None
+        if cfg.projection_dim != self.unet_config.ip_adapter_embed_dim:
+            raise ValueError(f"ip_adapter_image: the image encoder projects to {cfg.projection_dim}, the adapter takes "
+                             f"E = {self.unet_config.ip_adapter_embed_dim}")
+        return cfg
+
+    def encode_ip_adapter_image(self, images: torch.Tensor) -> torch.Tensor:
+        """uint8 [B,3,H,W] -> ``image_embeds`` [B, E] through the adapter's CLIP vision tower on libsdhip."""
+        if self._ip_encoder is None:
+            from safetensors.torch import load_file
+            from .clip_score import HipClipVisionModel
+            cfg = self._ip_image_encoder_config()
+            sd = {k: v.float() for k, v in load_file(os.path.join(self._ip_encoder_dir, "model.safetensors")).items()}
+            self._ip_encoder = HipClipVisionModel(cfg, sd, device=str(self.unet.device))
+        return self._ip_encoder.encode(images)
+
+    @staticmethod
+    def shard_ip_adapter_args(kwargs: dict, lo: int, hi: int, n: int) -> dict:
+        """A sharded harness call: the rows [lo, hi) of ``ip_adapter_image`` / ``ip_adapter_image_embeds`` ride with this
+        rank's prompts (``dist.shard_range``), as ``image=`` does.  A batch of 1 is broadcast and stays; embeds with 2 n rows
+        (negative | positive) are sliced per half."""
+        out = dict(kwargs)
+
+        def cut(v):
+            if isinstance(v, (list, tuple)) and len(v) == 1 and torch.is_tensor(v[0]):
+                return [cut(v[0])]
+            if torch.is_tensor(v):
+                if v.shape[0] == 2 * n and n > 1:
+                    return torch.cat([v[lo:hi], v[n + lo:n + hi]])
+                return v[lo:hi] if v.shape[0] == n and n > 1 else v
+            if isinstance(v, (list, tuple)) and len(v) == n and n > 1:
+                return list(v[lo:hi])
+            return v
+        for k in ("ip_adapter_image", "ip_adapter_image_embeds"):
+            if out.get(k) is not None:
+                out[k] = cut(out[k])
+        return out
+
+    def _apply_ip_adapter(self, do_cfg: bool):
+        """After ``set_context`` of a call: fold this call's image prompt into the UNet, or clear the last call's."""
+        ip, self._ip_pending = self._ip_pending, None
+        if ip is None:
+            if self.unet.config.ip_adapter_embed_dim is not None:
+                self.unet.clear_ip_adapter()
+            return
+        dev = self.unet.device
+        if ip[0] == "image":
+            pos, neg = self.encode_ip_adapter_image(ip[1].to(dev)), None
+        else:
+            pos, neg = ip[1].to(dev), None if ip[2] is None else ip[2].to(dev)
+        if do_cfg:
+            emb = torch.cat([torch.zeros_like(pos) if neg is None else neg, pos])      # negative first; diffusers: zeros_like
+        else:
+            emb = pos
+        self.ip_adapter_image_embeds = emb
+        self.unet.set_ip_adapter(emb.contiguous(), self._ip_scale, *self.latent_size)
 
     # -- properties the harness reads --------------------------------------------------------
     @property
@@ -320,13 +561,17 @@ class StableDiffusionModel:
         return out[0], out[1]
 
     def _begin(self, prompt, height, width, guidance_scale, negative_prompt, num_images_per_prompt, prompt_embeds,
-               negative_prompt_embeds, guidance_rescale=0.0, timesteps=None, sigmas=None):
+               negative_prompt_embeds, guidance_rescale=0.0, timesteps=None, sigmas=None, ip_adapter_image=None,
+               ip_adapter_image_embeds=None):
         """Steps 0-3 of the reference's ``call`` (``src/models.py:110-160``): argument checks, batch size,
         prompt encoding, CFG concat; uploads the prompt K/V projections.  Returns (device, batch, do_cfg, ctx).
         ``guidance_rescale`` is not validated (as upstream): the step rescales when CFG runs and it is > 0."""
         if num_images_per_prompt != 1 or timesteps is not None or sigmas is not None:
             raise NotImplementedError("custom timesteps / num_images_per_prompt are outside the reference's use")
         height, width = self.check_size(height, width)          # before any GPU work
+        n_prompt = 1 if isinstance(prompt, str) else len(prompt) if prompt is not None else int(prompt_embeds.shape[0])
+        self._ip_pending = self._ip_adapter_args(ip_adapter_image, ip_adapter_image_embeds, n_prompt,
+                                                 guidance_scale > 1 and self.unet_config.time_cond_proj_dim is None)
         self._size = (height, width)
         self._ensure_unet()
         if not self._fp8_calibrated:
@@ -357,6 +602,7 @@ class StableDiffusionModel:
         latents = self.prepare_latents(batch_size, LATENT_CHANNELS, self._size[0], self._size[1], device, generator, latents)
         self.unet.set_deepcache(cache_branch_id)
         self.unet.set_context(ctx, *self.latent_size)
+        self._apply_ip_adapter(ctx.shape[0] == 2 * batch_size and self.do_classifier_free_guidance)
         return latents
 
     def _eps_buffer(self, unet_batch, device):
@@ -414,6 +660,8 @@ class StableDiffusionModel:
             ctx = self.text_encoder(list(self.FP8_CALIBRATION_PROMPTS)).to(self.unet.device, torch.float32)
             branch = self.unet.cache_branch_id
             self.unet.set_deepcache(-1)             # the calibration pass runs the plan without DeepCache
+            if cfgu.ip_adapter_embed_dim is not None:
+                self.unet.clear_ip_adapter()        # ... and without an image prompt: the scales do not depend on the call's image
             self.unet.set_context(ctx)
             self.unet.set_timestep_cond(self.guidance_condition(self.FP8_CALIBRATION_GUIDANCE))
             if cfgu.in_channels == 9:
@@ -507,7 +755,8 @@ class StableDiffusionModel:
     @torch.no_grad()
     def _call_img2img(self, prompt, image, strength, sample_mode, height, width, num_inference_steps, timesteps, sigmas,
                       guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents, prompt_embeds,
-                      negative_prompt_embeds, output_type, return_dict, guidance_rescale, step_noise, collect_x0):
+                      negative_prompt_embeds, output_type, return_dict, guidance_rescale, step_noise, collect_x0,
+                      ip_args=(None, None)):
         """The loop of ``call`` started part-way down the schedule from a noised encoding of ``image`` (SDEdit).  The
         schedule is the full ``num_inference_steps`` one; the last ``N - t_start`` of its timesteps run.  A multistep
         scheduler starts with a fresh history at that index (``_index_of`` resolves it from the timestep) while its
@@ -517,7 +766,7 @@ class StableDiffusionModel:
                                                   num_inference_steps)
         device, batch_size, do_cfg, ctx = self._begin(prompt, ih, iw, guidance_scale, negative_prompt,
                                                       num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
-                                                      guidance_rescale, timesteps, sigmas)
+                                                      guidance_rescale, timesteps, sigmas, *ip_args)
         unet_batch = ctx.shape[0]
         self.scheduler.set_timesteps(num_inference_steps, device=device)
         ts_host = list(self.scheduler._timesteps_list)[t_start * self.scheduler.order:]
@@ -614,7 +863,8 @@ class StableDiffusionModel:
     @torch.no_grad()
     def _call_inpaint(self, prompt, image, mask_image, strength, sample_mode, height, width, num_inference_steps, timesteps,
                       sigmas, guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents, prompt_embeds,
-                      negative_prompt_embeds, output_type, return_dict, guidance_rescale, step_noise, collect_x0):
+                      negative_prompt_embeds, output_type, return_dict, guidance_rescale, step_noise, collect_x0,
+                      ip_args=(None, None)):
         """The loop of ``_call_img2img`` with a mask (1 = repaint, 0 = keep).  A 4-channel UNet: after every step the kept
         region is replaced by the image's latents noised to the NEXT timestep (the image's latents themselves after the last
         step) -- inside the step's launch (``step_fused(inpaint=...)``).  A 9-channel UNet reads the latent mask and the
@@ -625,7 +875,7 @@ class StableDiffusionModel:
                                                         width, latents, num_inference_steps)
         device, batch_size, do_cfg, ctx = self._begin(prompt, ih, iw, guidance_scale, negative_prompt,
                                                       num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
-                                                      guidance_rescale, timesteps, sigmas)
+                                                      guidance_rescale, timesteps, sigmas, *ip_args)
         nine = self.unet_config.in_channels == 9
         unet_batch = ctx.shape[0]
         self.scheduler.set_timesteps(num_inference_steps, device=device)
@@ -688,8 +938,12 @@ class StableDiffusionModel:
              negative_prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil",
              return_dict: bool = True, guidance_rescale: float = 0.0, step_noise: Optional[torch.Tensor] = None,
              collect_x0: bool = True, image=None, strength=STRENGTH_UNSET, sample_mode: str = "sample", mask_image=None,
-             padding_mask_crop=None, **kwargs):
-        """``image`` ([B,3,H,W] floats in [0,1], or a list of PIL images of one size): image-to-image with the semantics
+             padding_mask_crop=None, ip_adapter_image=None, ip_adapter_image_embeds=None, **kwargs):
+        """``ip_adapter_image`` (PIL images or uint8 / float [B,3,H,W]) or ``ip_adapter_image_embeds`` ([B, E], [B, 1, E] or
+        [2 B, ...] negative first under CFG; a tensor or a one-element list): the image prompt of a loaded IP-Adapter
+        (``load_ip_adapter``), for every kind of call below.
+
+        ``image`` ([B,3,H,W] floats in [0,1], or a list of PIL images of one size): image-to-image with the semantics
         of diffusers' StableDiffusionImg2ImgPipeline -- the image defines the size, ``strength`` in [0, 1] how far up the
         schedule its encoding is noised (``img2img_steps``), ``sample_mode`` whether the posterior is sampled or its mode
         taken.  ``mask_image`` ([B,1,H,W] or [B,H,W] floats in [0,1], or PIL images; 1 = repaint, 0 = keep) beside ``image``:
@@ -705,7 +959,8 @@ class StableDiffusionModel:
             return self._call_inpaint(prompt, image, mask_image, 1.0 if strength is STRENGTH_UNSET else strength, sample_mode,
                                       height, width, num_inference_steps, timesteps, sigmas, guidance_scale, negative_prompt,
                                       num_images_per_prompt, eta, generator, latents, prompt_embeds, negative_prompt_embeds,
-                                      output_type, return_dict, guidance_rescale, step_noise, collect_x0)
+                                      output_type, return_dict, guidance_rescale, step_noise, collect_x0,
+                                      (ip_adapter_image, ip_adapter_image_embeds))
         if self.unet_config.in_channels == 9:
             raise ValueError("this UNet has 9 input channels (an inpainting checkpoint: latents | mask | masked-image latents): "
                              "it runs only with image= and mask_image=, not as " +
@@ -716,10 +971,10 @@ class StableDiffusionModel:
             return self._call_img2img(prompt, image, strength, sample_mode, height, width, num_inference_steps, timesteps,
                                       sigmas, guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents,
                                       prompt_embeds, negative_prompt_embeds, output_type, return_dict, guidance_rescale,
-                                      step_noise, collect_x0)
+                                      step_noise, collect_x0, (ip_adapter_image, ip_adapter_image_embeds))
         device, batch_size, do_cfg, ctx = self._begin(prompt, height, width, guidance_scale, negative_prompt,
                                                       num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
-                                                      guidance_rescale, timesteps, sigmas)
+                                                      guidance_rescale, timesteps, sigmas, ip_adapter_image, ip_adapter_image_embeds)
         cfgu = self.unet_config
         unet_batch = ctx.shape[0]
 
@@ -843,13 +1098,13 @@ class StableDiffusionModelTwoSchedulers(_VariantBase):
              timesteps=None, sigmas=None, guidance_scale: float = 7.5, negative_prompt=None,
              num_images_per_prompt: int = 1, eta: float = 0.0, generator=None, latents=None, prompt_embeds=None,
              negative_prompt_embeds=None, output_type: str = "pil", return_dict: bool = True,
-             guidance_rescale: float = 0.0, **kwargs):
+             guidance_rescale: float = 0.0, ip_adapter_image=None, ip_adapter_image_embeds=None, **kwargs):
         self._refuse_image(kwargs)
         if self.scheduler_first is None or self.scheduler_second is None:
             raise ValueError("scheduler_first / scheduler_second must be set (two_schedulers.py:44-62)")
         device, batch_size, do_cfg, ctx = self._begin(prompt, height, width, guidance_scale, negative_prompt,
                                                       num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
-                                                      guidance_rescale, timesteps, sigmas)
+                                                      guidance_rescale, timesteps, sigmas, ip_adapter_image, ip_adapter_image_embeds)
         c = self.unet_config
         unet_batch = ctx.shape[0]
         self.scheduler_first.set_timesteps(num_inference_steps_first, device=device)               # :484-487
@@ -900,14 +1155,14 @@ class StableDiffusionModelInterlivingSchedulers(_VariantBase):
              timesteps=None, sigmas=None, guidance_scale: float = 7.5, negative_prompt=None,
              num_images_per_prompt: int = 1, eta: float = 0.0, generator=None, latents=None, prompt_embeds=None,
              negative_prompt_embeds=None, output_type: str = "pil", return_dict: bool = True,
-             guidance_rescale: float = 0.0, **kwargs):
+             guidance_rescale: float = 0.0, ip_adapter_image=None, ip_adapter_image_embeds=None, **kwargs):
         self._refuse_image(kwargs)
         if self.scheduler_main is None or self.scheduler_inter is None:
             raise ValueError("scheduler_main / scheduler_inter must be set (interliving_exp.py:41-62)")
         interliving_steps = list(interliving_steps or [])
         device, batch_size, do_cfg, ctx = self._begin(prompt, height, width, guidance_scale, negative_prompt,
                                                       num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
-                                                      guidance_rescale, timesteps, sigmas)
+                                                      guidance_rescale, timesteps, sigmas, ip_adapter_image, ip_adapter_image_embeds)
         c = self.unet_config
         unet_batch = ctx.shape[0]
         order = self.scheduler_main.config.solver_order
@@ -948,12 +1203,12 @@ class StableDiffusionModelSkipTimesteps(_VariantBase):
              timesteps=None, sigmas=None, guidance_scale: float = 7.5, negative_prompt=None,
              num_images_per_prompt: int = 1, eta: float = 0.0, generator=None, latents=None, prompt_embeds=None,
              negative_prompt_embeds=None, output_type: str = "pil", return_dict: bool = True,
-             guidance_rescale: float = 0.0, **kwargs):
+             guidance_rescale: float = 0.0, ip_adapter_image=None, ip_adapter_image_embeds=None, **kwargs):
         self._refuse_image(kwargs)
         skip = set(int(i) for i in (skip_timesteps or []))
         device, batch_size, do_cfg, ctx = self._begin(prompt, height, width, guidance_scale, negative_prompt,
                                                       num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
-                                                      guidance_rescale, timesteps, sigmas)
+                                                      guidance_rescale, timesteps, sigmas, ip_adapter_image, ip_adapter_image_embeds)
         c = self.unet_config
         unet_batch = ctx.shape[0]
         self.scheduler.set_timesteps(num_inference_steps, device=device)

@@ -36,6 +36,7 @@ def _c_config(cfg: UNetConfig, weight_dtype: str = "bf16", fp8_act_scales=(0.0, 
     c.cross_attention_dim, c.num_heads = cfg.cross_attention_dim, cfg.num_heads
     c.norm_num_groups, c.norm_eps, c.context_len = cfg.norm_num_groups, cfg.norm_eps, cfg.context_len
     c.time_cond_proj_dim = cfg.time_cond_proj_dim or 0
+    c.ip_adapter_tokens, c.ip_adapter_embed_dim = cfg.ip_adapter_tokens or 0, cfg.ip_adapter_embed_dim or 0
     return c
 
 
@@ -80,6 +81,13 @@ class HipUNet2DConditionModel:
         self._ctx_keepalive = None
         self._cond = None                   # the condition set on the handle (device fp32 [time_cond_proj_dim]) or None
         self._inpaint_key = None            # (batch, h, w) of the inpainting condition on the handle (in_channels == 9)
+        # IP-Adapter image prompt (config.ip_adapter_embed_dim set): _ip_on = forwards run with one; _ip_keys = the (batch,
+        # branch, h, w) whose workspace holds folded image operands; _ip_call = what __call__ last set (embeds identity, scale)
+        self._ip_on = False
+        self._ip_keys = set()
+        self._ip_call = None
+        self._ip_keepalive = None
+        self.ip_adapter_scale = 1.0         # scale __call__(added_cond_kwargs=...) applies (diffusers: set_ip_adapter_scale)
         self.cache_branch_id = -1
 
     def __del__(self):
@@ -103,6 +111,7 @@ class HipUNet2DConditionModel:
             n = self._lib.sd_unet_workspace_bytes_hw(self._handle, unet_batch, self.cache_branch_id, h, w)
             if n < 0:
                 _lib.check(-1, "sd_unet_workspace_bytes_hw")
+            self._drop_ip_keys()            # (the folded image operands lived in the old workspace, like the context)
             self._ws = None
             self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
             self._ws_key = key
@@ -179,6 +188,51 @@ class HipUNet2DConditionModel:
                    "sd_unet_set_inpaint_cond_hw")
         self._inpaint_key = None
 
+    # -- IP-Adapter image prompt ---------------------------------------------------------------
+    def _drop_ip_keys(self) -> None:
+        for ub, branch, h, w in self._ip_keys:
+            _lib.check(self._lib.sd_unet_set_ip_adapter_hw(self._handle, _lib.current_stream(), None, ub, branch, h, w, 0.0, None, 0),
+                       "sd_unet_set_ip_adapter_hw")
+        self._ip_keys = set()
+        self._ip_call = None
+
+    def set_ip_adapter(self, image_embeds: torch.Tensor, scale: float = 1.0, height: Optional[int] = None,
+                       width: Optional[int] = None) -> None:
+        """Image prompt of a UNet built with an IP-Adapter: ``image_embeds`` [N, E] fp32 (N = the UNet batch, CFG halves
+        already concatenated, negative first) for forwards at latent ``height`` x ``width``.  Call it after ``set_context``
+        for the same batch and size: it projects the image tokens, ``to_k_ip`` / ``to_v_ip`` of every attn2 layer and folds
+        them with ``scale`` into per-sample operands in the workspace (once per sampling run; a new scale means a new call).
+        Every later forward adds ``scale * softmax(q K_ip^T / sqrt d) V_ip`` to its prompt cross-attention until
+        ``clear_ip_adapter``."""
+        e = self.config.ip_adapter_embed_dim
+        if e is None:
+            raise ValueError("set_ip_adapter: this UNet was built without an IP-Adapter (ip_adapter_embed_dim is None)")
+        if isinstance(scale, dict) or not isinstance(scale, (int, float)) or isinstance(scale, bool):
+            raise NotImplementedError("set_ip_adapter: scale must be one float (per-block scale dicts are not built)")
+        if not torch.is_tensor(image_embeds) or image_embeds.dim() != 2 or image_embeds.shape[1] != e:
+            raise ValueError(f"image_embeds must be [N, {e}], got "
+                             f"{tuple(image_embeds.shape) if torch.is_tensor(image_embeds) else type(image_embeds).__name__}")
+        h, w = self.latent_size(height, width)
+        ub = int(image_embeds.shape[0])
+        if self._ctx_key is None or self._ctx_key[2:] != (ub, h, w):
+            raise _lib.SdHipError(f"set_context(encoder_hidden_states, {h}, {w}) must be called for this batch ({ub}) and size first")
+        emb = image_embeds.detach().to(self.device, torch.float32).contiguous()
+        if emb.data_ptr() % 16:
+            emb = emb.clone()
+        ws = self._workspace(ub, h, w)
+        _lib.check(self._lib.sd_unet_set_ip_adapter_hw(self._handle, _lib.current_stream(), emb.data_ptr(), ub, self.cache_branch_id,
+                                                       h, w, float(scale), self._ws_ptr(ws), ws.numel() - 256),
+                   "sd_unet_set_ip_adapter_hw")
+        self._ip_keepalive = emb
+        self._ip_keys.add((ub, self.cache_branch_id, h, w))
+        self._ip_on = True
+
+    def clear_ip_adapter(self) -> None:
+        """Drop every image prompt of the handle: forwards are again those of a UNet without an adapter, bit for bit."""
+        self._drop_ip_keys()
+        self._ip_on = False
+        self._ip_keepalive = None
+
     # -- forward ---------------------------------------------------------------------------
     def forward_latents(self, latents: torch.Tensor, unet_batch: int, timestep: float,
                         out: Optional[torch.Tensor] = None, cache_mode: int = CACHE_OFF) -> torch.Tensor:
@@ -194,6 +248,9 @@ class HipUNet2DConditionModel:
                                   f"this batch and size ({h}x{w}) first")
         if self._ctx_key is None or self._ctx_key[2:] != (unet_batch, h, w):
             raise _lib.SdHipError(f"set_context(encoder_hidden_states, {h}, {w}) must be called for this batch and size first")
+        if self._ip_on and (unet_batch, self.cache_branch_id, h, w) not in self._ip_keys:
+            raise _lib.SdHipError(f"this UNet runs with an IP-Adapter image prompt: set_ip_adapter(image_embeds, scale, {h}, {w}) must "
+                                  f"be called for this batch ({unet_batch}) and size after set_context (or clear_ip_adapter())")
         if latents.dtype != torch.float32 or not latents.is_contiguous() or latents.device != self.device:
             latents = latents.to(self.device, torch.float32).contiguous()
         if out is None:
@@ -249,7 +306,7 @@ class HipUNet2DConditionModel:
 
     KIND_NAMES = {0: "sinusoid", 1: "gemv", 2: "conv_in", 3: "groupnorm", 4: "conv3x3", 5: "gemm", 6: "layernorm",
                   7: "attention", 8: "conv_out", 16: "conv3x3_fp8", 17: "gemm_fp8", 18: "xattn_fused",
-                  19: "replicate", 20: "conv3x3_gemm", 21: "conv3x3_halo_subpix"}
+                  19: "replicate", 20: "conv3x3_gemm", 21: "conv3x3_halo_subpix", 22: "ip_xattn"}
 
     def forward_profiled(self, latents: torch.Tensor, unet_batch: int, timestep: float, cache_mode: int = CACHE_OFF):
         """One forward with a hipEvent pair around every launch (measurement only, synchronises).
@@ -275,16 +332,47 @@ class HipUNet2DConditionModel:
                  **kwargs):
         """diffusers-style call of the reference loop (``src/models.py:227-235``).  ``timestep_cond`` ([B, d] or [d]) is
         the guidance embedding of an LCM-distilled UNet: one row for the whole batch (ONE_ROW_RULE); None runs without it."""
+        emb = None
         if added_cond_kwargs is not None:
-            raise NotImplementedError("added_cond_kwargs is not part of the SD-1.5 hot path")
+            if self.config.ip_adapter_embed_dim is None:
+                raise NotImplementedError("added_cond_kwargs is not part of the SD-1.5 hot path (this UNet has no IP-Adapter)")
+            if set(added_cond_kwargs) != {"image_embeds"}:
+                raise NotImplementedError(f"added_cond_kwargs {sorted(added_cond_kwargs)}: only {{'image_embeds': ...}} of one "
+                                          "IP-Adapter is built")
+            emb = self._call_image_embeds(added_cond_kwargs["image_embeds"], sample.shape[0])
         self._apply_timestep_cond(timestep_cond)
         h, w = sample.shape[2], sample.shape[3]
         key = (encoder_hidden_states.data_ptr(), encoder_hidden_states._version, sample.shape[0], h, w)
         if self._ctx_key != key:
             self.set_context(encoder_hidden_states, h, w)
+        if emb is None:
+            if self._ip_on:
+                self.clear_ip_adapter()
+        else:
+            ip_call = (emb.data_ptr(), emb._version, float(self.ip_adapter_scale), sample.shape[0], self.cache_branch_id, h, w)
+            if self._ip_call != ip_call or ip_call[3:] not in self._ip_keys:
+                self.set_ip_adapter(emb, self.ip_adapter_scale, h, w)
+                self._ip_call = ip_call
         t = float(timestep.item()) if torch.is_tensor(timestep) else float(timestep)
         eps = self.forward_latents(sample, sample.shape[0], t)
         return (eps.to(sample.dtype),)
+
+    def _call_image_embeds(self, image_embeds, batch: int) -> torch.Tensor:
+        """``added_cond_kwargs["image_embeds"]`` of diffusers: a tensor or a one-element list, [N, E] or [N, 1, E]."""
+        if isinstance(image_embeds, (list, tuple)):
+            if len(image_embeds) != 1:
+                raise NotImplementedError(f"image_embeds: a list of {len(image_embeds)} (several IP-Adapters at once are not built)")
+            image_embeds = image_embeds[0]
+        e = self.config.ip_adapter_embed_dim
+        if not torch.is_tensor(image_embeds):
+            raise ValueError("image_embeds must be a tensor or a one-element list of tensors")
+        if image_embeds.dim() == 3:
+            if image_embeds.shape[1] != 1:
+                raise NotImplementedError(f"image_embeds {tuple(image_embeds.shape)}: several images per sample are not built")
+            image_embeds = image_embeds[:, 0]
+        if image_embeds.dim() != 2 or image_embeds.shape[1] != e or image_embeds.shape[0] != batch:
+            raise ValueError(f"image_embeds must be [{batch}, {e}] or [{batch}, 1, {e}], got {tuple(image_embeds.shape)}")
+        return image_embeds
 
     ONE_ROW_RULE = "timestep_cond must be one row for the whole batch (one guidance scale per call)"
 

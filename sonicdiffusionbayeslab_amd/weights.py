@@ -35,17 +35,40 @@ class UNetConfig:
     # an InitVar and kept as an instance attribute: ``dataclasses.asdict`` of a config then still builds the oracle's
     # ``UNetConfig`` (which has no such field), and ``dataclasses.replace`` carries the value over.
     time_cond_proj_dim: InitVar[Optional[int]] = None
+    # IP-Adapter image prompts (diffusers ``ImageProjection`` + ``IPAdapterAttnProcessor2_0``, the plain ip-adapter_sd15
+    # family): width E of ``image_embeds`` (1024 for the published adapter), None = no adapter.  The UNet then carries the
+    # token projection and ``to_k_ip`` / ``to_v_ip`` of every attn2 layer (``param_shapes``).  ``ip_adapter_tokens`` is the
+    # number of image tokens per sample: IP_ADAPTER_TOKENS with an adapter, else None.  InitVars like the field above.
+    ip_adapter_embed_dim: InitVar[Optional[int]] = None
+    ip_adapter_tokens: InitVar[Optional[int]] = None
 
-    def __post_init__(self, time_cond_proj_dim):
+    def __post_init__(self, time_cond_proj_dim, ip_adapter_embed_dim, ip_adapter_tokens):
         if time_cond_proj_dim is not None and (isinstance(time_cond_proj_dim, bool) or int(time_cond_proj_dim) <= 0
                                                or int(time_cond_proj_dim) != time_cond_proj_dim):
             raise ValueError(f"time_cond_proj_dim={time_cond_proj_dim!r}: a positive integer or None")
         self.time_cond_proj_dim = None if time_cond_proj_dim is None else int(time_cond_proj_dim)
+        e, t = ip_adapter_embed_dim, ip_adapter_tokens
+        if e is None:
+            if t is not None:
+                raise ValueError(f"ip_adapter_tokens={t!r} without ip_adapter_embed_dim")
+            self.ip_adapter_embed_dim = self.ip_adapter_tokens = None
+            return
+        if isinstance(e, bool) or int(e) != e or int(e) <= 0 or int(e) % 64:
+            raise ValueError(f"ip_adapter_embed_dim={e!r}: a positive multiple of 64 or None")
+        if t is not None and (isinstance(t, bool) or t != IP_ADAPTER_TOKENS):
+            raise NotImplementedError(f"ip_adapter_tokens={t!r}: {IP_ADAPTER_TOKENS} image tokens are built (the plain "
+                                      "ip-adapter_sd15 family; the 'plus' / 'full-face' adapters have 16 or 257)")
+        self.ip_adapter_embed_dim, self.ip_adapter_tokens = int(e), IP_ADAPTER_TOKENS
 
     def __eq__(self, other):            # (the generated one compares fields only)
         if other.__class__ is not self.__class__:
             return NotImplemented
-        return _shared_fields(self) == _shared_fields(other) and self.time_cond_proj_dim == other.time_cond_proj_dim
+        return (_shared_fields(self) == _shared_fields(other) and self.time_cond_proj_dim == other.time_cond_proj_dim
+                and self.ip_adapter_embed_dim == other.ip_adapter_embed_dim)
+
+
+IP_ADAPTER_TOKENS = 4
+IP_PROJ = "encoder_hid_proj.image_projection_layers.0."       # diffusers: unet.encoder_hid_proj of one loaded adapter
 
 
 def param_shapes(cfg: UNetConfig) -> List[Tuple[str, Tuple[int, ...]]]:
@@ -76,6 +99,8 @@ def param_shapes(cfg: UNetConfig) -> List[Tuple[str, Tuple[int, ...]]]:
         add(t + "attn1.to_out.0.weight", (c, c)); add(t + "attn1.to_out.0.bias", (c,))
         add(t + "attn2.to_q.weight", (c, c)); add(t + "attn2.to_k.weight", (c, ctx)); add(t + "attn2.to_v.weight", (c, ctx))
         add(t + "attn2.to_out.0.weight", (c, c)); add(t + "attn2.to_out.0.bias", (c,))
+        if cfg.ip_adapter_embed_dim is not None:
+            add(t + "attn2.processor.to_k_ip.0.weight", (c, ctx)); add(t + "attn2.processor.to_v_ip.0.weight", (c, ctx))
         add(t + "ff.net.0.proj.weight", (8 * c, c)); add(t + "ff.net.0.proj.bias", (8 * c,))
         add(t + "ff.net.2.weight", (c, 4 * c)); add(t + "ff.net.2.bias", (c,))
         add(p + "proj_out.weight", (c, c, 1, 1)); add(p + "proj_out.bias", (c,))
@@ -115,7 +140,138 @@ def param_shapes(cfg: UNetConfig) -> List[Tuple[str, Tuple[int, ...]]]:
             add(f"up_blocks.{i}.upsamplers.0.conv.bias", (co,))
     add("conv_norm_out.weight", (c0,)); add("conv_norm_out.bias", (c0,))
     add("conv_out.weight", (cfg.out_channels, c0, 3, 3)); add("conv_out.bias", (cfg.out_channels,))
+    if cfg.ip_adapter_embed_dim is not None:
+        td = cfg.ip_adapter_tokens * cfg.cross_attention_dim
+        add(IP_PROJ + "image_embeds.weight", (td, cfg.ip_adapter_embed_dim)); add(IP_PROJ + "image_embeds.bias", (td,))
+        add(IP_PROJ + "norm.weight", (cfg.cross_attention_dim,)); add(IP_PROJ + "norm.bias", (cfg.cross_attention_dim,))
     return out
+
+
+def attn2_prefixes(cfg: UNetConfig) -> List[str]:
+    """The ``...transformer_blocks.0.attn2.`` prefixes in the order of diffusers' ``unet.attn_processors``: all of
+    ``down_blocks``, then all of ``up_blocks``, then ``mid_block`` (module registration order, NOT forward order).  An
+    IP-Adapter checkpoint numbers the processors in that order, attn1 and attn2 alternating: the i-th prefix here is
+    its key ``2 i + 1`` (1, 3, ..., 31 for SD-1.5)."""
+    nl = len(cfg.block_out_channels)
+    out = []
+    for i in range(nl):
+        if cfg.attn_levels[i]:
+            out += [f"down_blocks.{i}.attentions.{j}.transformer_blocks.0.attn2." for j in range(cfg.layers_per_block)]
+    for i in range(nl):
+        if cfg.attn_levels[nl - 1 - i]:
+            out += [f"up_blocks.{i}.attentions.{j}.transformer_blocks.0.attn2." for j in range(cfg.layers_per_block + 1)]
+    out.append("mid_block.attentions.0.transformer_blocks.0.attn2.")
+    return out
+
+
+def ip_adapter_param_shapes(cfg: UNetConfig) -> List[Tuple[str, Tuple[int, ...]]]:
+    """(name, shape) of the parameters an IP-Adapter adds to the UNet (``cfg.ip_adapter_embed_dim`` set)."""
+    plain = {n for n, _ in param_shapes(without_ip_adapter(cfg))}
+    return [(n, s) for n, s in param_shapes(cfg) if n not in plain]
+
+
+def without_ip_adapter(cfg: UNetConfig) -> UNetConfig:
+    import dataclasses
+    return dataclasses.replace(cfg, ip_adapter_embed_dim=None, ip_adapter_tokens=None)
+
+
+IP_ADAPTER_SEED_OFFSET = 104729
+
+
+def make_synthetic_ip_adapter_state_dict(cfg: UNetConfig, seed: int = 1234, gain: float = 1.0) -> Dict[str, torch.Tensor]:
+    """Seeded IP-Adapter-shaped weights under the UNet's names (``ip_adapter_param_shapes``), fp32 on the bf16 grid, from a
+    generator of their own: linear weights ~ N(0, gain^2 / fan_in), the projection bias ~ N(0, 0.05^2), the token LayerNorm
+    1 + N(0, 0.1^2) / N(0, 0.1^2).  Stands in for a hub adapter (no weights exist offline) and serves the tests."""
+    if cfg.ip_adapter_embed_dim is None:
+        raise ValueError("make_synthetic_ip_adapter_state_dict: the config has no ip_adapter_embed_dim")
+    g = torch.Generator().manual_seed(IP_ADAPTER_SEED_OFFSET + int(seed))
+    sd = {}
+    for name, shape in ip_adapter_param_shapes(cfg):
+        if name.endswith("norm.weight"):
+            t = 1.0 + 0.1 * torch.randn(shape, generator=g)
+        elif name.endswith("norm.bias"):
+            t = 0.1 * torch.randn(shape, generator=g)
+        elif name.endswith(".bias"):
+            t = 0.05 * torch.randn(shape, generator=g)
+        else:
+            t = torch.randn(shape, generator=g) * (gain / math.sqrt(shape[1]))
+        sd[name] = t.to(torch.bfloat16).float()
+    return sd
+
+
+def to_upstream_ip_adapter(sd: Dict[str, torch.Tensor], cfg: UNetConfig) -> Dict[str, Dict[str, torch.Tensor]]:
+    """The inverse of ``map_ip_adapter_state_dict``: UNet names -> the checkpoint's two groups (what ``ip-adapter_sd15.bin``
+    holds).  Tests and tools write synthetic checkpoints with it."""
+    out = {"image_proj": {"proj.weight": sd[IP_PROJ + "image_embeds.weight"], "proj.bias": sd[IP_PROJ + "image_embeds.bias"],
+                          "norm.weight": sd[IP_PROJ + "norm.weight"], "norm.bias": sd[IP_PROJ + "norm.bias"]},
+           "ip_adapter": {}}
+    for i, p in enumerate(attn2_prefixes(cfg)):
+        out["ip_adapter"][f"{2 * i + 1}.to_k_ip.weight"] = sd[p + "processor.to_k_ip.0.weight"]
+        out["ip_adapter"][f"{2 * i + 1}.to_v_ip.weight"] = sd[p + "processor.to_v_ip.0.weight"]
+    return out
+
+
+def map_ip_adapter_state_dict(groups: Dict[str, Dict[str, torch.Tensor]], cfg: UNetConfig):
+    """An IP-Adapter checkpoint's groups ``image_proj`` / ``ip_adapter`` (upstream layout) -> (UNet-named fp32 state dict,
+    embed dim E).  ``ip_adapter`` keys are ``"{k}.to_k_ip.weight"`` / ``"{k}.to_v_ip.weight"`` with k = 1, 3, ...: k counts
+    ``unet.attn_processors`` -- attn1 / attn2 alternating over all of down_blocks, then all of up_blocks, then mid_block
+    (``attn2_prefixes``), which is NOT the forward order.  Missing keys raise ``KeyError``, wrong shapes ``ValueError``, and
+    the projections this build does not run (Resampler / MLP: the 'plus' and 'full-face' adapters) ``NotImplementedError``,
+    each naming the key."""
+    for grp in ("image_proj", "ip_adapter"):
+        if grp not in groups:
+            raise KeyError(f"IP-Adapter checkpoint lacks the group {grp!r}")
+    proj, ipa = groups["image_proj"], groups["ip_adapter"]
+    if any(k.startswith(("latents", "proj_in", "layers.", "proj.0", "proj.3", "perceiver_resampler")) for k in proj):
+        raise NotImplementedError("IP-Adapter image_proj is a Resampler / MLP projection (the 'plus' / 'full-face' adapters, 16 or "
+                                  "257 image tokens): only the plain ImageProjection (proj + norm, 4 tokens) is built")
+    for k in ("proj.weight", "proj.bias", "norm.weight", "norm.bias"):
+        if k not in proj:
+            raise KeyError(f"IP-Adapter checkpoint lacks image_proj.{k}")
+    cd = cfg.cross_attention_dim
+    w = proj["proj.weight"]
+    if w.dim() != 2 or w.shape[0] % cd:
+        raise ValueError(f"image_proj.proj.weight: expected [T * {cd}, E], got {tuple(w.shape)}")
+    tokens, e = w.shape[0] // cd, int(w.shape[1])
+    if tokens != IP_ADAPTER_TOKENS:
+        raise NotImplementedError(f"image_proj.proj.weight {tuple(w.shape)}: {tokens} image tokens; {IP_ADAPTER_TOKENS} are built")
+    want = {"proj.bias": (tokens * cd,), "norm.weight": (cd,), "norm.bias": (cd,)}
+    for k, shp in want.items():
+        if tuple(proj[k].shape) != shp:
+            raise ValueError(f"image_proj.{k}: expected shape {shp}, got {tuple(proj[k].shape)}")
+    f32 = lambda t: t.detach().to("cpu", torch.float32).contiguous()
+    sd = {IP_PROJ + "image_embeds.weight": f32(w), IP_PROJ + "image_embeds.bias": f32(proj["proj.bias"]),
+          IP_PROJ + "norm.weight": f32(proj["norm.weight"]), IP_PROJ + "norm.bias": f32(proj["norm.bias"])}
+    chan = {n[: -len("to_q.weight")]: s[0] for n, s in param_shapes(without_ip_adapter(cfg)) if n.endswith("attn2.to_q.weight")}
+    for i, p in enumerate(attn2_prefixes(cfg)):
+        for which in ("to_k_ip", "to_v_ip"):
+            k = f"{2 * i + 1}.{which}.weight"
+            if k not in ipa:
+                raise KeyError(f"IP-Adapter checkpoint lacks ip_adapter.{k} (the attn2 of {p[:-1]})")
+            if tuple(ipa[k].shape) != (chan[p], cd):
+                raise ValueError(f"ip_adapter.{k}: expected shape {(chan[p], cd)} (the attn2 of {p[:-1]}), got {tuple(ipa[k].shape)}")
+            sd[p + f"processor.{which}.0.weight"] = f32(ipa[k])
+    return sd, e
+
+
+def load_ip_adapter_state_dict(path: str, cfg: UNetConfig):
+    """A LOCAL IP-Adapter file in the upstream layout -> ``map_ip_adapter_state_dict``'s result: a ``.safetensors`` with the
+    ``image_proj.`` / ``ip_adapter.`` key prefixes, or a ``.bin`` (``torch.save`` of the nested dict).  Never fetches."""
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"no IP-Adapter file at {path!r}")
+    if path.endswith(".safetensors"):
+        from safetensors.torch import load_file
+        groups: Dict[str, Dict[str, torch.Tensor]] = {"image_proj": {}, "ip_adapter": {}}
+        for k, v in load_file(path).items():
+            grp, _, rest = k.partition(".")
+            if grp in groups:
+                groups[grp][rest] = v
+        groups = {g: d for g, d in groups.items() if d}
+    else:
+        groups = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(groups, dict):
+            raise ValueError(f"{path!r}: an IP-Adapter .bin holds a dict with the groups 'image_proj' and 'ip_adapter'")
+    return map_ip_adapter_state_dict(groups, cfg)
 
 
 _SYNTHETIC_CACHE: Dict[tuple, Dict[str, torch.Tensor]] = {}
