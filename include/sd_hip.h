@@ -401,6 +401,13 @@ int sd_inpaint_prepare(void* stream, const float* image, const float* mask, floa
 int sd_op_gemm(void* stream, const void* X, long long ldx, const void* X2, long long ldx2, int K1, const void* W,
                const float* bias, const float* bias2, const void* R, long long ldr, void* C, long long ldc, int M,
                int N, int K, int epi);
+/* Which variant of the general GEMM kernel the plain (epi = 0) entry points run a problem on; no device work (additions
+ * under ABI 3: resolve them by name).  sd_op_gemm_tile_rows: the rows of the bf16 output tile, 64 or 128 (tiles are 160
+ * columns wide).  sd_op_gemm_splitk: the split-K factor (1 = none) sd_op_gemm picks (dtype 0, bf16) or sd_op_gemm_fp8 picks
+ * (dtype 1, K in e4m3 elements; always on the 128-row tile).  Split s of S covers the 64-element (fp8: 128-element) K tiles
+ * [KT s / S, KT (s + 1) / S) of the KT the problem has. */
+int sd_op_gemm_tile_rows(int M, int N, int K);
+int sd_op_gemm_splitk(int M, int N, int K, int dtype);
 /* Same GEMM with a PER-SAMPLE weight matrix: rows [b*rows_per_batch, (b+1)*rows_per_batch) use W + b*w_batch_stride
  * (elements; rows_per_batch a multiple of 128).  epi=2: row softmax over the first sm_valid of every 80 output
  * columns, the rest written as 0.  The two halves of the folded prompt cross-attention

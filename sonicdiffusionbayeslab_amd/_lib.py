@@ -133,6 +133,8 @@ _SIGS = {
     "sd_op_ip_xattn": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _ll, _i, _i, _i, _i]),
     "sd_op_conv_in_cond": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i]),
     "sd_op_gemm": (_i, [_vp, _vp, _ll, _vp, _ll, _i, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _i]),
+    "sd_op_gemm_tile_rows": (_i, [_i, _i, _i]),
+    "sd_op_gemm_splitk": (_i, [_i, _i, _i, _i]),
     "sd_op_gemm_batched": (_i, [_vp, _vp, _ll, _vp, _ll, _i, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _i, _i]),
     "sd_op_gemm_batched_softmax_ln": (_i, [_vp, _vp, _ll, _vp, _ll, _i, _vp, _ll, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f]),
     "sd_op_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),

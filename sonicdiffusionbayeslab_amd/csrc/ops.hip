@@ -74,6 +74,22 @@ static XattnArgs xattn_args(const void* X, const void* R, void* Y, const void* A
     return a;
 }
 
+// Split factor of the plain-epilogue GEMM entry points: dtype 0 = sd_op_gemm (bf16), 1 = sd_op_gemm_fp8 (K in e4m3 elements:
+// the heuristic counts 128-byte K tiles, and the fp8 kernel has the 128-row tile only)
+static int op_gemm_splitk(int M, int N, int K, int dtype) {
+    return dtype ? sd_gemm_splitk(M, N, K / 2, 128) : sd_gemm_splitk(M, N, K);
+}
+
+// Which variant sd_op_gemm / sd_op_gemm_fp8 run a plain-epilogue problem on (the tests assert the one they mean to hit)
+extern "C" int sd_op_gemm_tile_rows(int M, int N, int K) {
+    SD_REQUIRE(M > 0 && N > 0 && K >= 0, "gemm_tile_rows: bad arguments");
+    return sd_gemm_tile_rows(M, N, K);
+}
+extern "C" int sd_op_gemm_splitk(int M, int N, int K, int dtype) {
+    SD_REQUIRE(M > 0 && N > 0 && K > 0 && (dtype == 0 || dtype == 1), "gemm_splitk: bad arguments");
+    return op_gemm_splitk(M, N, K, dtype);
+}
+
 extern "C" int sd_op_gemm(void* stream, const void* X, long long ldx, const void* X2, long long ldx2, int K1,
                           const void* W, const float* bias, const float* bias2, const void* R, long long ldr, void* C,
                           long long ldc, int M, int N, int K, int epi) {
@@ -82,7 +98,7 @@ extern "C" int sd_op_gemm(void* stream, const void* X, long long ldx, const void
     a.X = (const bf16_t*)X; a.ldx = ldx; a.X2 = (const bf16_t*)X2; a.ldx2 = ldx2; a.K1 = K1;
     a.W = (const bf16_t*)W; a.bias = bias; a.bias2 = bias2; a.R = (const bf16_t*)R; a.ldr = ldr;
     a.C = (bf16_t*)C; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.zero_page = zero_page();
-    a.splitk = epi ? 1 : sd_gemm_splitk(M, N, K);
+    a.splitk = epi ? 1 : op_gemm_splitk(M, N, K, 0);
     if (splitk_slab(a, "sd_op_gemm")) return -1;
     return sd_launch_gemm(a, epi, (hipStream_t)stream);
 }
@@ -438,7 +454,7 @@ extern "C" int sd_op_gemm_fp8(void* stream, const void* X, long long ldx, const 
     a.X = (const bf16_t*)X; a.ldx = ldx; a.K1 = K; a.W = (const bf16_t*)W; a.bias = bias; a.R = (const bf16_t*)R; a.ldr = ldr;
     a.C = (bf16_t*)C; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.zero_page = zero_page();
     a.dt = 1; a.wscale = wscale; a.xscale_inv = 1.0f / xscale; a.out_fp8 = out_fp8; a.oscale = oscale;
-    a.splitk = epi ? 1 : sd_gemm_splitk(M, N, K / 2, 128);
+    a.splitk = epi ? 1 : op_gemm_splitk(M, N, K, 1);
     if (splitk_slab(a, "sd_op_gemm_fp8")) return -1;
     return sd_launch_gemm(a, epi, (hipStream_t)stream);
 }

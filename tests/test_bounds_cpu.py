@@ -2,7 +2,9 @@
 
 Exact fp64 results rounded to the output format stand in for a correct kernel: they must pass with margin.  Faults of the
 kinds the kernels risk (a halo corner, a wrapped halo column, a dropped bias, a split-K slab counted twice, a ragged key
-tile, a tail row from the neighbouring image) are injected into the same results: each must pass the rel-L2 gate the GPU
+tile, a tail row from the neighbouring image; on a split-K GEMM of 170 row tiles: a tile that counts a split twice, an item that
+starts one K tile late, tail rows with the residual of another row, a second K segment read from the wrong offset) are injected
+into the same results: each must pass the rel-L2 gate the GPU
 tests have always used -- the gap is real -- and fail the elementwise gate.  The guard bands must catch single stray
 stores and accept an untouched buffer.
 
@@ -154,6 +156,97 @@ def test_gemm_tails_and_fault_last_row_misses_k_tail():
     bad = ref2.clone()
     bad[-1] -= x[-1, -32:] @ w[:, -32:].t()
     fault_report("last row misses the last 32 of K", r16(bad), ref2, bound2, OLD_TOL, old_gate_passes=False)
+
+
+# ---- split-K GEMM over many row tiles ---------------------------------------------------------------------------------
+# Faults of gemm_kernel's work loop (csrc/gemm_conv.hip: decode(), the next item's prefetch, the K1 boundary inside a split)
+# and of splitk_reduce_kernel, on tests/gemm_cases.py::FAULT_CASE: 10817 x 160 x 2560 with K1 = 1280, bias and residual; 64-row
+# tiles, 170 M tiles of one N tile, the last tile holding ONE row; three splits over K tiles 0..12 | 13..25 | 26..39, K1 at
+# tile 20 (tests/test_gemm_dispatch_cpu.py pins that variant).  The old gate is the 1e-2 rel-L2 of the whole-model tests, the
+# only ones that ran these paths.
+#
+# Why this shape: a norm over the whole output sees a fault by its share of the energy.  With unit-variance product, bias
+# and residual, a FULL 64 x 160 tile that counts one of S splits twice carries (10240 / (M N)) / (3 S) of it, and the
+# heuristic gives S <= 512 x 10240 / (M N): rel-L2 >= sqrt(1 / (3 x 512)) = 2.6e-2 at every shape, above the old gate.  The
+# faults that slip under it are those of a ragged last tile, of one K tile of one item, or of the few tail rows -- where such
+# kernels go wrong -- and the shape is as large as a split-K problem gets so that a whole row of residuals from the wrong row
+# (energy 2 N of 3 M N) stays below 1e-2 as well.  The full-tile forms are reported too: both gates refuse them.
+
+GEMM_OLD_TOL = 1e-2
+
+
+@pytest.fixture(scope="module")
+def splitk_case():
+    from tests.gemm_cases import FAULT_CASE as c, derive
+    d = derive(c, c.rows, c.split)
+    assert (d["m_tiles"], d["n_tiles"], d["M"] % c.rows, d["ranges"], d["k1_tile"]) == (170, 1, 1, [(0, 13), (13, 26), (26, 40)], 20)
+    g = torch.Generator().manual_seed(12)
+    x = r16(torch.randn(c.M, c.K, generator=g))
+    w = r16(torch.randn(c.N, c.K, generator=g) / math.sqrt(c.K))
+    b = torch.randn(c.N, generator=g).float().double()
+    r = r16(torch.randn(c.M, c.N, generator=g))
+    ref, bound = gemm_bound(x, w, b, None, r)
+    return c, d, x, w, r, ref, bound
+
+
+def partial(x, w, rows, kt0, kt1, xk0=None):
+    """Rows ``rows`` of the partial product over K tiles [kt0, kt1); xk0: the K tile X is read from instead of kt0."""
+    xk0 = kt0 if xk0 is None else xk0
+    return x[rows, xk0 * 64:(xk0 + kt1 - kt0) * 64] @ w[:, kt0 * 64:kt1 * 64].t()
+
+
+def test_exact_splitk_gemm_passes_with_margin(splitk_case):
+    c, _, _, _, _, ref, bound = splitk_case
+    assert assert_elementwise(r16(ref), ref, bound, f"exact gemm {c.M}x{c.N}x{c.K}", ("row", "col")) <= 0.5 + 1e-9
+
+
+def test_fault_one_tile_adds_one_split_s_partial_twice(splitk_case):
+    """(a) The last 64 x 160 tile (its one valid row) adds split 1's slab twice; the same on a full tile fails both gates."""
+    c, d, x, w, _, ref, bound = splitk_case
+    tail = slice(c.M - 1, c.M)
+    bad = ref.clone()
+    bad[tail] += partial(x, w, tail, *d["ranges"][1])
+    fault_report("last tile adds split 1 twice", r16(bad), ref, bound, GEMM_OLD_TOL)
+    full = slice(64, 128)
+    bad = ref.clone()
+    bad[full] += partial(x, w, full, *d["ranges"][1])
+    fault_report("a full tile adds split 1 twice", r16(bad), ref, bound, GEMM_OLD_TOL, old_gate_passes=False)
+
+
+def test_fault_second_m_tile_s_last_split_starts_one_k_tile_late(splitk_case):
+    """(b) The item (M tile 1, last split) decodes kt_begin + 1: the 64-wide K tile 26 is missing from rows 64..127."""
+    c, d, x, w, _, ref, bound = splitk_case
+    kt = d["ranges"][-1][0]
+    rows = slice(64, 128)
+    bad = ref.clone()
+    bad[rows] -= partial(x, w, rows, kt, kt + 1)
+    fault_report("M tile 1, last split, starts one K tile late", r16(bad), ref, bound, GEMM_OLD_TOL)
+
+
+def test_fault_tail_rows_take_the_residual_of_the_tile_above(splitk_case):
+    """(c) The reduce adds R[m - rows] to the rows of the M tail (a clamped or tile-relative row index)."""
+    c, _, _, _, r, ref, bound = splitk_case
+    first = c.M - c.M % c.rows
+    bad = ref.clone()
+    bad[first:] += r[first - c.rows:c.M - c.rows] - r[first:]
+    fault_report("tail rows with the residual of row m - 64", r16(bad), ref, bound, GEMM_OLD_TOL)
+
+
+def test_fault_second_segment_read_from_the_wrong_offset(splitk_case):
+    """(d) The K1 boundary inside a split, on the last tile's items.  Split 1 straddles it: its X2 tiles 20..25 are X2's first
+    six, and a kernel that indexes X2 by the tile's position in the SPLIT reads tiles 7..12 of X2 instead.  Split 2 lies wholly
+    in the second segment: reading 'from X2's start' instead of from its offset gives it X2 tiles 0..13 for 6..19."""
+    c, d, x, w, _, ref, bound = splitk_case
+    tail = slice(c.M - 1, c.M)
+    (b1, e1), (b2, e2) = d["ranges"][1], d["ranges"][2]
+    k1 = d["k1_tile"]
+    assert b1 < k1 < e1 and b2 > k1
+    bad = ref.clone()
+    bad[tail] += partial(x, w, tail, k1, e1, xk0=k1 + (k1 - b1)) - partial(x, w, tail, k1, e1)
+    fault_report("the straddling split indexes X2 by the position in the split", r16(bad), ref, bound, GEMM_OLD_TOL)
+    bad = ref.clone()
+    bad[tail] += partial(x, w, tail, b2, e2, xk0=k1) - partial(x, w, tail, b2, e2)
+    fault_report("the split behind it reads X2 from its start", r16(bad), ref, bound, GEMM_OLD_TOL)
 
 
 # ---- attention --------------------------------------------------------------------------------------------------------

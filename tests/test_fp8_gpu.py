@@ -38,6 +38,7 @@ No kernel needed an addition to its restatement; the GEGLU epilogue's polynomial
 is the one documented approximation: the elements it can flip are counted from the reference alone and added to the budget."""
 import dataclasses
 import math
+import os
 
 import pytest
 import torch
@@ -47,6 +48,7 @@ pytestmark = pytest.mark.gpu
 
 from sonicdiffusionbayeslab_amd import _lib
 from tests.fp8_sensitivity import D8, MARGIN, T_SENS, CalibratingEmulation, checkpoint, damax, hot_keys, product_scale
+from tests.gemm_cases import FP8_CASES, case_id, derive, holds
 from tests.util import cosine, oracle_cfg, rel_l2, synth_inputs
 from tests.bounds import (ATOL_TINY, GELU_POLY, U32, NHWC, assert_e4m3_codes, assert_e4m3_interval, assert_elementwise, assert_flip_budget,
                           attention_elementwise, check_guards, conv3x3_nhwc_ref, conv_gn_elementwise, count_flips,
@@ -117,8 +119,18 @@ def padk(codes, Kp):
     (130, 640, 1280, False, True),
     (64, 1280, 5120, True, True),       # ff.net.2 at the 8x8 level: split-K
     (1000, 960, 320, False, False),     # fused QKV shape
+    # split-K over several 128-row tiles and the persistent loop (tests/gemm_cases.py: M tail 44 on 3 M tiles; N tail;
+    # 768 items with the dequantisation in splitk_reduce_kernel)
+    *[(c.M, c.N, c.K, c.bias, c.res) for c in FP8_CASES],
 ])
 def test_gemm_fp8(sdlib, M, N, K, bias, res):
+    case = {(c.M, c.N, c.K): c for c in FP8_CASES}.get((M, N, K))
+    if case is not None and not any(v in os.environ for v in ("SD_SPLITK", "SD_GEMM_SMALL", "SD_GEMM_BIG", "SD_GEMM_LEAN")):
+        split = sdlib.sd_op_gemm_splitk(M, N, K, 1)                 # the variant the case exists for (product defaults)
+        d = derive(case, 128, split)
+        print(f"[variant] gemm fp8 {case_id(case)}: rows 128 / split {split} / items {d['items']} (grid {d['grid']}), K tiles {d['kts']}")
+        assert (split, d["items"]) == (case.split, case.items), (split, d["items"])
+        assert all(holds(p, d) for p in case.props), [p for p in case.props if not holds(p, d)]
     g = torch.Generator().manual_seed(M + N + K)
     xs = 8.0
     xc, xq = q8(torch.randn(M, K, generator=g) * xs)            # activations as their producer would write them
@@ -133,6 +145,7 @@ def test_gemm_fp8(sdlib, M, N, K, bias, res):
     _lib.check(sdlib.sd_op_gemm_fp8(stream(), P(padk(xc, Kp)), Kp, P(padk(wc, Kp)), P(wsc), xs, P(b),
                                     P(r.bfloat16()) if res else None, N, P(out), N, M, N, Kp, 0, 0, 1.0))
     torch.cuda.synchronize()
+    check_guards()
     assert rel_l2(out, ref) < TOL
     r64, m64, k_eff = fp8_gemm_ref_bound(xq, xs, wq, wsc, b, r)
     assert_elementwise(out, r64, linear_bound(r64, m64, k_eff), f"gemm fp8 {M}x{N}x{K}", ("row", "col"))
