@@ -169,6 +169,46 @@ int sd_unet_set_inpaint_cond_hw(sd_unet* u, void* stream, const float* mask, con
 int sd_unet_set_ip_adapter_hw(sd_unet* u, void* stream, const float* image_embeds, int unet_batch, int cache_branch_id,
                               int latent_h, int latent_w, float scale, void* workspace, long long workspace_bytes);
 
+/* ---- ControlNet (diffusers ControlNetModel, guess_mode = False).  Additions under ABI 3: resolve by name. ----
+ * The handle is again an `sd_unet` (its own kind): cfg as for the UNet it is paired with (in_channels = 4, bf16 only: fp8 is
+ * refused by name; no IP-Adapter fields); cond_embed_channels: diffusers' conditioning_embedding_out_channels, the four
+ * widths of ControlNetConditioningEmbedding's conv chain (16, 32, 96, 256 for the published SD-1.5 ControlNets; multiples
+ * of 8).  Parameters under diffusers' names -- time_embedding.*,
+ * conv_in.*, down_blocks.*, mid_block.* as in the UNet, controlnet_cond_embedding.{conv_in, blocks.0..5, conv_out}.{weight,
+ * bias}, controlnet_down_blocks.N.{weight [C, C, 1, 1], bias}, controlnet_mid_block.{weight, bias} -- are enumerated / loaded /
+ * finalised through the sd_unet_* calls; sd_unet_workspace_bytes_hw sizes its workspace (cache_branch_id = -1),
+ * sd_unet_set_context_hw stores its prompt and sd_unet_set_timestep_cond its LCM condition.
+ *
+ * Residual buffer (caller-owned, 256-byte aligned, sd_controlnet_residual_bytes_hw bytes; the same function serves a UNet
+ * handle of the same widths): bf16, channel-last, one segment [unet_batch][h_i * w_i][C_i] per residual in diffusers' order --
+ * conv_in's output, then per level its layers_per_block block outputs followed by its downsampler's output (none at the last
+ * level), then the mid block: 12 + 1 segments for SD-1.5, with (C, side divisor) = (c0, 1) x 3, (c0, 2), (c1, 2) x 2,
+ * (c1, 4), (c2, 4) x 2, (c2, 8), (c3, 8) x 2 and the mid (c3, 8).  Segment i starts where segment i - 1 ends, rounded up to
+ * 256 bytes.  The residuals are stored UNSCALED: conditioning_scale is applied where they are consumed. */
+int sd_controlnet_create(const sd_unet_config* cfg, const int cond_embed_channels[4], sd_unet** out);
+long long sd_controlnet_residual_bytes_hw(const sd_unet* u, int unet_batch, int latent_h, int latent_w);
+/* The step-invariant conditioning embedding, once per call: cond_image = device fp32 [batch, 3, 8 latent_h, 8 latent_w] in
+ * [0, 1] (rgb, not normalised), 16-byte aligned.  Eight convs (3x3, pad 1; SiLU after all but the last; stride 2 on blocks
+ * 1, 3, 5) on the general implicit-GEMM conv kernel leave [batch][latent_h * latent_w][block_out_channels[0]] bf16 on the
+ * handle; every later forward at that latent size adds it inside conv_in, reading sample b's row from b % batch (unet_batch
+ * must be a multiple of batch).  Scratch is owned by the handle.  cond_image = NULL clears it. */
+int sd_controlnet_set_cond_hw(sd_unet* u, void* stream, const float* cond_image, int batch, int latent_h, int latent_w);
+/* residuals = ControlNet(latents, t, prompt, cond): the UNet's time embedding, conv_in (+ the stored embedding, in the same
+ * launch), down path and mid block, then one 1x1 GEMM per residual into `residuals` (layout above).  latents / latent_batch /
+ * unet_batch as for sd_unet_forward_hw (a CFG pair runs its prompt-independent prefix once). */
+int sd_controlnet_forward_hw(sd_unet* u, void* stream, const float* latents, int latent_batch, int unet_batch, int latent_h,
+                             int latent_w, float timestep, void* residuals, void* workspace, long long workspace_bytes);
+/* UNet side: while residuals are set, every forward of the handle runs the "control" plan variant -- today's ops, then after
+ * the mid block ONE launch (profile kind 23) that does x <- bf16(float(x) + scale * float(r)) in place on the twelve skip
+ * tensors and the mid output (every reader of the unmodified tensors has run by then), and up-block GroupNorms that compute
+ * their own statistics where the plain plan took them from the producer of a tensor this variant modifies.  `residuals`: a
+ * buffer in the layout above for (unet_batch, latent_h, latent_w), borrowed until cleared or replaced; a forward at another
+ * batch or size, or with a DeepCache mode, fails and says so.  residuals = NULL clears: the handle runs the plain plans again,
+ * bit for bit.  fp8 handles refuse.  A handle builds and sizes the control variants only from its first call of this function on:
+ * sd_unet_workspace_bytes_hw covers them from then on, so query it again after the first call (the context tensors keep their
+ * offsets, so a larger workspace may be filled by copying the old one); a forward whose workspace is too small fails and says so. */
+int sd_unet_set_control_residuals_hw(sd_unet* u, const void* residuals, float scale, int unet_batch, int latent_h, int latent_w);
+
 enum { SD_CACHE_OFF = 0, SD_CACHE_FULL_AND_STORE = 1, SD_CACHE_SKIP = 2 };
 
 /* eps = UNet(latent_model_input, t, encoder_hidden_states)  (src/models.py:217-235).
@@ -312,7 +352,8 @@ int sd_inception_features(sd_inception* h, void* stream, const unsigned char* im
 int sd_fid_accumulate(void* stream, const float* features, int batch, int dim, double* sum, double* cov_sum,
                       long long* count);
 /* operator level: Y[.., coff : coff + Cout] of rows of ldy channels = relu?(conv(X NHWC bf16, W bf16 [Cout][kh][kw][Cin],
- * stride, padding (pad_h, pad_w)) + bias); any Cin / Cout (no padding of tensors asked of the caller) */
+ * stride, padding (pad_h, pad_w)) + bias); any Cin / Cout (no padding of tensors asked of the caller).  relu = 2: SiLU
+ * instead (the ControlNet's conditioning embedding runs on this kernel) */
 int sd_op_inception_conv(void* stream, const void* X, const void* W, const float* bias, void* Y, int B, int Hin, int Win,
                          int Cin, int Cout, int kh, int kw, int stride, int pad_h, int pad_w, int ldy, int coff, int relu);
 /* 3x3 pools on NHWC bf16 into a channel slice: max with (stride, pad) = (2, 0) or (1, 1), padding never wins; average with
@@ -327,7 +368,7 @@ int sd_op_inception_resize(void* stream, const unsigned char* images, int B, int
 /* Measurement hook for bench.py: the same forward with a hipEvent pair around every launch.  Per
  * op kind (0 sinusoid, 1 gemv, 2 conv_in, 3 groupnorm, 4 conv3x3, 5 gemm, 6 layernorm,
  * 7 attention, 8 conv_out; 16 conv3x3 with fp8 operands, 17 gemm with fp8 operands, 18 fused prompt cross-attention,
- * 22 IP-Adapter image branch) it returns summed
+ * 22 IP-Adapter image branch, 23 ControlNet residual add) it returns summed
  * milliseconds, launch count, algorithmic FLOPs and algorithmic HBM bytes in arrays of SD_PROFILE_KINDS = 32
  * entries.  Synchronises the stream; never used inside a timed region. */
 #define SD_PROFILE_KINDS 32
@@ -501,6 +542,14 @@ int sd_op_conv_in(void* stream, const float* x, int Bsrc, const float* Wt, const
  * [81][Cout] fp32 (k = ic*9 + tap over the 9 concatenated channels) -> y NHWC bf16 [B,H,W,Cout]; one launch, Cout <= 1024 */
 int sd_op_conv_in_cond(void* stream, const float* x, int Bsrc, const float* cond, int Bcond, const float* Wt,
                        const float* bias, void* y, int B, int H, int W, int Cout);
+/* conv_in of a ControlNet: y = bf16(conv_in(x) + float(addend)), x [Bsrc,4,H,W] fp32, addend NHWC bf16 [Badd,H,W,Cout] (batch
+ * indices modulo their source batch), fp32 accumulation, ONE rounding, 16-byte stores; Cout a multiple of 8, <= 2048 */
+int sd_op_conv_in_add(void* stream, const float* x, int Bsrc, const void* addend, int Badd, const float* Wt, const float* bias,
+                      void* y, int B, int H, int W, int Cout);
+/* x[dst_off[i] + j] <- bf16(float(x[dst_off[i] + j]) + scale * float(r[src_off[i] + j])), j < count[i], for nseg <= 16 segments
+ * in ONE launch (bf16 element offsets, multiples of 8; any count; x and r 16-byte aligned; host arrays) */
+int sd_op_residual_add(void* stream, void* x, const long long* dst_off, const void* r, const long long* src_off,
+                       const long long* count, int nseg, float scale);
 int sd_op_conv_out(void* stream, const void* x, const void* Wp, const float* bias, float* y, int B, int H, int W,
                    int Cin, int Cout);
 int sd_op_time_embedding(void* stream, float t, const void* W1, const float* b1, const void* W2, const float* b2,

@@ -131,6 +131,13 @@ _SIGS = {
     "sd_unet_set_inpaint_cond_hw": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
     "sd_unet_set_ip_adapter_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _ll]),
     "sd_op_ip_xattn": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _ll, _i, _i, _i, _i]),
+    "sd_controlnet_create": (_i, [C.POINTER(SdUnetConfig), C.POINTER(_i), C.POINTER(_vp)]),
+    "sd_controlnet_residual_bytes_hw": (_ll, [_vp, _i, _i, _i]),
+    "sd_controlnet_set_cond_hw": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "sd_controlnet_forward_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _ll]),
+    "sd_unet_set_control_residuals_hw": (_i, [_vp, _vp, _f, _i, _i, _i]),
+    "sd_op_conv_in_add": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "sd_op_residual_add": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f]),
     "sd_op_conv_in_cond": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i]),
     "sd_op_gemm": (_i, [_vp, _vp, _ll, _vp, _ll, _i, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _i]),
     "sd_op_gemm_tile_rows": (_i, [_i, _i, _i]),

@@ -22,7 +22,7 @@
 namespace {
 
 // ---- implicit-GEMM conv ------------------------------------------------------------------------------------------------
-// C[m][n] = relu(sum_k A[m][k] W[n][k] + bias[n]);  m = (b, oy, ox), k = (ky, kx, ci), A gathered from the NHWC input (zero
+// C[m][n] = act(sum_k A[m][k] W[n][k] + bias[n]), act = none / relu / (relu = 2) SiLU;  m = (b, oy, ox), k = (ky, kx, ci), A gathered from the NHWC input (zero
 // outside the image and past K).  Workgroup: 64 rows x 64 columns, 4 waves of 32 x 32 (2 x 2 MFMA tiles), K in steps of 32.
 // Each thread stages one 8-element k-chunk of one A row and of one W row per step: global -> registers (issued before the
 // step's MFMAs) -> the other half of a double-buffered LDS image; one barrier per step.  LDS rows are padded to 40 elements
@@ -142,7 +142,8 @@ __global__ __launch_bounds__(256) void inception_conv_kernel(ConvArgs a) {
                 const long row = (long)blockIdx.x * BM + wm + i * 16 + 4 * g + r;
                 if (row >= a.M) continue;
                 float v = acc[i][j][r] + bv;
-                if (a.relu) v = fmaxf(v, 0.f);
+                if (a.relu == 1) v = fmaxf(v, 0.f);
+                else if (a.relu == 2) v = silu_f(v);
                 a.y[row * a.ldy + a.coff + col] = f2bf(v);
             }
     }

@@ -253,6 +253,15 @@ int sd_launch_conv_in(const float* x, int Bsrc, const float* Wt /*[Cin*9][Cout] 
 // batch indices taken modulo their source batch) -> NHWC bf16 [B,H,W,Cout]; Wt [81][Cout] fp32
 int sd_launch_conv_in_cond(const float* x, int Bsrc, const float* cond, int Bcond, const float* Wt, const float* bias,
                            bf16_t* y, int B, int H, int W, int Cout, hipStream_t stream);
+constexpr int SD_MAX_RES_SEGMENTS = 16;      // segments of one residual-add launch (a ControlNet has 12 + 1)
+// conv_in of a ControlNet: conv_in(x) + addend in one launch (addend NHWC bf16 [Badd,H,W,Cout], batch index modulo Badd; fp32
+// sum, one bf16 rounding, 16-byte stores; Cout a multiple of 8)
+int sd_launch_conv_in_add(const float* x, int Bsrc, const bf16_t* addend, int Badd, const float* Wt, const float* bias,
+                          bf16_t* y, int B, int H, int W, int Cout, hipStream_t stream);
+// x[k][j] <- bf16(float(x[k][j]) + scale * float(r[k][j])), j < n[k], for nseg <= 16 segments in ONE launch (host arrays of
+// device pointers; 16-byte aligned; any n)
+int sd_launch_residual_add(bf16_t* const* x, const bf16_t* const* r, const long* n, int nseg, float scale, hipStream_t stream);
+int sd_launch_nchw_to_nhwc_bf16(const float* src, bf16_t* dst, int B, int C, long hw, hipStream_t stream);
 // cond [B,5,hw] = [mask [B,1,hw] | masked [B,4,hw]] (fp32; hw a multiple of 4)
 int sd_launch_inpaint_cond_pack(const float* mask, const float* masked, float* cond, int B, long hw, hipStream_t stream);
 // inpainting, pixel space: masked [B,3,H,W] = mask >= 0.5 ? 0.5 : img, lmask [B,1,H/8,W/8] = (mask(8i, 8j) >= 0.5) as 0 / 1
@@ -300,7 +309,7 @@ int sd_launch_sched_step_inpaint(const float* eps, int cfg, float guidance, cons
 
 // inception.hip: FID Inception-v3 pieces (general implicit-GEMM conv, 3x3 pools, global mean, TF1 bilinear preprocessing)
 int sd_launch_inception_conv(const bf16_t* x, const bf16_t* w, const float* bias, bf16_t* y, int B, int Hin, int Win, int Cin,
-                             int Cout, int kh, int kw, int stride, int ph, int pw, int ldy, int coff, int relu,
+                             int Cout, int kh, int kw, int stride, int ph, int pw, int ldy, int coff, int relu /* 2: SiLU */,
                              hipStream_t stream);
 int sd_launch_inception_pool(const bf16_t* x, bf16_t* y, int B, int H, int W, int C, int stride, int pad, int avg, int ldy,
                              int coff, hipStream_t stream);

@@ -21,7 +21,8 @@
 namespace sdhip {
 
 constexpr size_t NOFF = (size_t)-1;
-constexpr int T_LATENTS = -2, T_EPS = -3;
+constexpr int T_LATENTS = -2, T_EPS = -3;       // T_EPS: the call's output buffer (a ControlNet's residual GEMMs write it at Op::coff)
+constexpr int MAX_CONTROL_RES = SD_MAX_RES_SEGMENTS;      // residual segments of a ControlNet (12 + 1 for SD-1.5): one add launch
 
 struct ParamSpec {
     std::string name;
@@ -42,7 +43,7 @@ struct Wrap {  // one DeepCache-wrapped module enclosing an op
 
 enum OpKind { OP_SINUSOID, OP_GEMV, OP_CONV_IN, OP_GN, OP_CONV3, OP_GEMM, OP_LN, OP_ATTN, OP_CONV_OUT, OP_SOFTMAX, OP_PQCONV,
               OP_CLIP_EMBED, OP_CLIP_ATTN, OP_QGELU, OP_TO_F32, OP_XATTN, OP_REPLICATE,
-              OP_VIT_PREP, OP_VIT_EMBED, OP_VIT_ATTN, OP_POOL, OP_CONV_IN_IMG, OP_ENC_OUT, OP_IP_XATTN };
+              OP_VIT_PREP, OP_VIT_EMBED, OP_VIT_ATTN, OP_POOL, OP_CONV_IN_IMG, OP_ENC_OUT, OP_IP_XATTN, OP_RES_ADD };
 
 constexpr int REP_TEXT_POOLED = 2;       // Plan::rep of a CLIP text handle's sd_clip_text_embeds plan
 
@@ -95,6 +96,9 @@ struct Op {
     // channels, scw = the packed conv_shortcut weight; `b` is then the summed bias vector and Kalg counts the shortcut channels
     int scx1 = -1, scx2 = -1, scc1 = 0, scc2 = 0;
     size_t scw = NOFF;
+    // OP_RES_ADD (the "control" plan variant): the tensors the ControlNet residuals are added to, in segment order
+    int nres = 0;
+    int res_t[MAX_CONTROL_RES];
     int nwrap = 0;
     Wrap wraps[3];
 };
@@ -155,6 +159,11 @@ struct Plan {
     struct IpFold { int at, bt, C; size_t wqT, wo, wkv; };
     std::vector<IpFold> ip_fold;
     int ip_e = -1, ip_proj = -1, ip_tok = -1, ip_kv = -1;
+    // "control" variant (part of the plan key): one OP_RES_ADD after the mid block adds the ControlNet residuals in place to the
+    // twelve skip tensors and the mid output; up-block GroupNorms of those tensors compute their own statistics
+    int cn = 0;
+    std::vector<size_t> cn_off;           // UNet / ControlNet plans: the residual segments' byte offsets and bf16 element
+    std::vector<long> cn_count;           // counts for this batch and size (control_segments)
     std::vector<Tn> tensors;
     std::vector<Op> ops;
     std::vector<char> skipped;            // per op: skipped on a DeepCache skip step
@@ -178,7 +187,8 @@ struct Plan {
 }  // namespace sdhip
 
 struct sd_unet {
-    // 0 = UNet2DConditionModel, 1 = AutoencoderKL decoder, 2 = CLIP text encoder, 3 = CLIP vision tower, 4 = AutoencoderKL encoder
+    // 0 = UNet2DConditionModel, 1 = AutoencoderKL decoder, 2 = CLIP text encoder, 3 = CLIP vision tower, 4 = AutoencoderKL encoder,
+    // 5 = ControlNetModel (the UNet's time embedding, conv_in, down path and mid block + the zero convs)
     int kind = 0;
     sd_unet_config cfg;
     sd_clip_config clip;
@@ -208,8 +218,8 @@ struct sd_unet {
         act_names.push_back(name); act_scale.push_back(dflt); act_amax.push_back(0.f);
         return (int)act_names.size() - 1;
     }
-    std::map<std::tuple<int, int, int, int, int, int>, sdhip::Plan> plans;   // (UNet batch, DeepCache branch, prefix replication, latent H, W, IP-Adapter variant)
-    int last_rep = 1, last_ip = 0;                       // variant of the last forward (sd_unet_debug_tensor)
+    std::map<std::tuple<int, int, int, int, int, int, int>, sdhip::Plan> plans;   // (UNet batch, DeepCache branch, prefix replication, latent H, W, IP-Adapter variant, control variant)
+    int last_rep = 1, last_ip = 0, last_cn = 0;                       // variant of the last forward (sd_unet_debug_tensor)
     int last_h = 0, last_w = 0;                          // latent size of the last forward (sd_unet_debug_tensor)
     std::unordered_map<std::string, long> tproj_off;  // resnet prefix -> float index into tproj vector
     long tproj_total = 0;
@@ -228,6 +238,22 @@ struct sd_unet {
     // operands (sd_unet_set_ip_adapter_hw).  While the set is not empty every forward runs the "IP on" plan variant and must find
     // its own key here; empty = the plans of a handle without an adapter.
     std::set<std::tuple<int, int, int, int>> ip_keys;
+    // ControlNet residuals of a UNet (sd_unet_set_control_residuals_hw): the caller's buffer, borrowed, with the scale and the
+    // (UNet batch, latent H, W) it is laid out for.  Null = the plain plans.
+    const char* ctrl_res = nullptr;
+    float ctrl_scale = 0.f;
+    int ctrl_ub = 0, ctrl_h = 0, ctrl_w = 0;
+    // set by the first sd_unet_set_control_residuals_hw: from then on sd_unet_workspace_bytes_hw covers the control plan variants
+    // (a handle that never sees a ControlNet builds and sizes only today's plans)
+    bool ctrl_enabled = false;
+    // ControlNet handle (kind 5): the conditioning embedding [cn_b][cn_h * cn_w][c0] bf16 of the call and the scratch its conv
+    // chain runs in (sd_controlnet_set_cond_hw), owned by the handle like dinpaint; conv_in adds it (batch index modulo cn_b)
+    bf16_t* cn_embed = nullptr;
+    char* cn_scratch = nullptr;
+    size_t cn_embed_cap = 0, cn_scratch_cap = 0;
+    int cn_b = 0, cn_h = 0, cn_w = 0;
+    int cond_embed[4] = {0, 0, 0, 0};       // conditioning_embedding_out_channels
+    bool unet_like() const { return kind == 0 || kind == 5; }      // runs the UNet's encoder ops (plan.hip Builder::build)
 };
 
 namespace sdhip {
@@ -238,6 +264,7 @@ void enumerate_params_vae(sd_unet* u);
 void enumerate_params_vae_encoder(sd_unet* u);
 void enumerate_params_clip(sd_unet* u);
 void enumerate_params_vit(sd_unet* u);
+int cond_embed_convs(const sd_unet* u, std::string names[8], int cin[8], int cout[8], int stride[8]);     // ControlNetConditioningEmbedding's chain
 int pack_all(sd_unet* u);
 double pack_alloc_seconds();      // staging-blob growth inside the last pack_all (SD_PACK_TIMING)
 // transformers CLIPTextModel state_dict names (4.48.0 layout, `text_model.` prefix)
@@ -249,8 +276,11 @@ inline int vit_kp(const sd_clip_vision_config& c) { return (3 * c.patch_size * c
 // plan.hip
 int plan_rep(const sd_unet* u, int latent_batch, int unet_batch);
 int check_latent_size(const sd_unet* u, int lh, int lw, const char* who);
-int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep = 1, int lh = -1, int lw = -1, int ip = 0);     // lh / lw < 0: the handle's sample_size (square)
+int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep = 1, int lh = -1, int lw = -1, int ip = 0, int cn = 0);     // lh / lw < 0: the handle's sample_size (square)
 bool ip_active(const sd_unet* u, int UB, int branch, int lh, int lw);     // is this forward's IP-Adapter key set?
+// the ControlNet residual segments of a (UNet batch, latent size), in order: byte offset into the residual buffer and bf16
+// element count of each (include/sd_hip.h: the layout); returns the buffer's bytes
+size_t control_segments(const sd_unet_config& c, int UB, int lh, int lw, std::vector<size_t>* off, std::vector<long>* count);
 
 // unet.hip
 int ensure_zero_page();

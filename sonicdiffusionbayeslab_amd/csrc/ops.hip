@@ -416,6 +416,25 @@ extern "C" int sd_op_conv_in_cond(void* stream, const float* x, int Bsrc, const 
     return sd_launch_conv_in_cond(x, Bsrc, cond, Bcond, Wt, bias, (bf16_t*)y, B, H, W, Cout, (hipStream_t)stream);
 }
 
+extern "C" int sd_op_conv_in_add(void* stream, const float* x, int Bsrc, const void* addend, int Badd, const float* Wt,
+                                 const float* bias, void* y, int B, int H, int W, int Cout) {
+    return sd_launch_conv_in_add(x, Bsrc, (const bf16_t*)addend, Badd, Wt, bias, (bf16_t*)y, B, H, W, Cout, (hipStream_t)stream);
+}
+
+extern "C" int sd_op_residual_add(void* stream, void* x, const long long* dst_off, const void* r, const long long* src_off,
+                                  const long long* count, int nseg, float scale) {
+    SD_REQUIRE(x && r && dst_off && src_off && count, "sd_op_residual_add: null argument");
+    SD_REQUIRE(nseg >= 1 && nseg <= MAX_CONTROL_RES, "sd_op_residual_add: %d segments (1 .. %d)", nseg, MAX_CONTROL_RES);
+    bf16_t* xs[MAX_CONTROL_RES];
+    const bf16_t* rs[MAX_CONTROL_RES];
+    long n[MAX_CONTROL_RES];
+    for (int k = 0; k < nseg; ++k) {
+        SD_REQUIRE(dst_off[k] >= 0 && src_off[k] >= 0 && count[k] > 0, "sd_op_residual_add: segment %d", k);
+        xs[k] = (bf16_t*)x + dst_off[k]; rs[k] = (const bf16_t*)r + src_off[k]; n[k] = (long)count[k];
+    }
+    return sd_launch_residual_add(xs, rs, n, nseg, scale, (hipStream_t)stream);
+}
+
 extern "C" int sd_op_conv_in(void* stream, const float* x, int Bsrc, const float* Wt, const float* bias, void* y, int B,
                              int H, int W, int Cin, int Cout) {
     return sd_launch_conv_in(x, Bsrc, Wt, bias, (bf16_t*)y, B, H, W, Cin, Cout, (hipStream_t)stream);

@@ -1,4 +1,4 @@
-// libsdhip host side: parameter enumeration (the state_dict names of the five handle kinds) and the weight packer.  Pure host
+// libsdhip host side: parameter enumeration (the state_dict names of the six handle kinds) and the weight packer.  Pure host
 // code: it runs on a box without a GPU too.
 #include "model.h"
 
@@ -91,9 +91,25 @@ struct Enum {
 };
 }  // namespace
 
+// ControlNetConditioningEmbedding (diffusers controlnet.py): conv_in 3 -> e0, blocks.2i e_i -> e_i, blocks.2i+1 e_i -> e_(i+1)
+// with stride 2, conv_out e3 -> block_out_channels[0]; all 3x3, pad 1
+int cond_embed_convs(const sd_unet* u, std::string names[8], int cin[8], int cout[8], int stride[8]) {
+    const std::string p = "controlnet_cond_embedding.";
+    const sd_unet_config& c = u->cfg;
+    const int* e = u->cond_embed;
+    names[0] = p + "conv_in."; cin[0] = 3; cout[0] = e[0]; stride[0] = 1;
+    for (int i = 0; i < 3; ++i) {
+        names[1 + 2 * i] = p + "blocks." + std::to_string(2 * i) + "."; cin[1 + 2 * i] = e[i]; cout[1 + 2 * i] = e[i]; stride[1 + 2 * i] = 1;
+        names[2 + 2 * i] = p + "blocks." + std::to_string(2 * i + 1) + "."; cin[2 + 2 * i] = e[i]; cout[2 + 2 * i] = e[i + 1]; stride[2 + 2 * i] = 2;
+    }
+    names[7] = p + "conv_out."; cin[7] = e[3]; cout[7] = c.block_out_channels[0]; stride[7] = 1;
+    return 8;
+}
+
 void enumerate_params(sd_unet* u) {
     const sd_unet_config& c = u->cfg;
     Enum e{u};
+    const bool cnet = u->kind == 5;       // a ControlNet: the UNet's encoder half under the same names, then its own convs
     const int c0 = c.block_out_channels[0], temb = 4 * c0, nl = c.num_levels;
     e.add("time_embedding.linear_1.weight", {temb, c0});
     e.add("time_embedding.linear_1.bias", {temb});
@@ -122,6 +138,22 @@ void enumerate_params(sd_unet* u) {
     e.resnet("mid_block.resnets.0.", ch, ch, temb);
     e.transformer("mid_block.attentions.0.", ch, c.cross_attention_dim);
     e.resnet("mid_block.resnets.1.", ch, ch, temb);
+    if (cnet) {
+        std::string names[8];
+        int cin[8], cout[8], stride[8];
+        cond_embed_convs(u, names, cin, cout, stride);
+        for (int i = 0; i < 8; ++i) {
+            e.add(names[i] + "weight", {cout[i], cin[i], 3, 3});
+            e.add(names[i] + "bias", {cout[i]});
+        }
+        for (size_t i = 0; i < skip_ch.size(); ++i) {
+            e.add("controlnet_down_blocks." + std::to_string(i) + ".weight", {skip_ch[i], skip_ch[i], 1, 1});
+            e.add("controlnet_down_blocks." + std::to_string(i) + ".bias", {skip_ch[i]});
+        }
+        e.add("controlnet_mid_block.weight", {ch, ch, 1, 1});
+        e.add("controlnet_mid_block.bias", {ch});
+        return;
+    }
     for (int i = 0; i < nl; ++i) {
         const int lev = nl - 1 - i, co = c.block_out_channels[lev];
         const std::string bp = "up_blocks." + std::to_string(i) + ".";
@@ -633,7 +665,7 @@ struct Packer {
 
 // walks the architecture once; F gets (kind, prefix, cin, cout/c) callbacks in forward order
 template <class FR, class FT>
-void walk_blocks(const sd_unet_config& c, FR&& on_resnet, FT&& on_transformer) {
+void walk_blocks(const sd_unet_config& c, FR&& on_resnet, FT&& on_transformer, bool up = true) {
     const int nl = c.num_levels;
     int ch = c.block_out_channels[0];
     std::vector<int> skip_ch{ch};
@@ -651,6 +683,7 @@ void walk_blocks(const sd_unet_config& c, FR&& on_resnet, FT&& on_transformer) {
     on_resnet("mid_block.resnets.0.", ch, ch);
     on_transformer("mid_block.attentions.0.", ch);
     on_resnet("mid_block.resnets.1.", ch, ch);
+    if (!up) return;       // (a ControlNet ends here)
     for (int i = 0; i < nl; ++i) {
         const int lev = nl - 1 - i, co = c.block_out_channels[lev];
         const std::string bp = "up_blocks." + std::to_string(i) + ".";
@@ -787,7 +820,7 @@ int pack_all(sd_unet* u) {
             u->tproj_off[p] = toff;
             toff += cout;
         },
-        [&](const std::string& p, int cc) { pk.transformer(p, cc); });
+        [&](const std::string& p, int cc) { pk.transformer(p, cc); }, u->kind != 5);
     u->tproj_total = toff;
     pk.concat_rows("tproj.weight", tw);
     {
@@ -800,10 +833,22 @@ int pack_all(sd_unet* u) {
         const int co = c.block_out_channels[i];
         const std::string d = "down_blocks." + std::to_string(i) + ".downsamplers.0.conv.";
         pk.conv3(d + "weight", co, co); pk.f32(d + "bias");
+        if (u->kind == 5) continue;
         const int lev = nl - 1 - i, cu = c.block_out_channels[lev];
         const std::string up = "up_blocks." + std::to_string(i) + ".upsamplers.0.conv.";
         pk.conv3(up + "weight", cu, cu); pk.f32(up + "bias");
         pk.conv3_subpixel(up + "weight", cu, cu);
+    }
+    if (u->kind == 5) {     // the conditioning embedding's convs as the general conv kernel reads them ([O][tap][I]), the zero convs as GEMM rows
+        std::string names[8];
+        int cin[8], cout[8], stride[8];
+        cond_embed_convs(u, names, cin, cout, stride);
+        for (int i = 0; i < 8; ++i) { pk.conv3_ohwi(names[i] + "weight", cout[i], cin[i]); pk.f32(names[i] + "bias"); }
+        for (int i = 0; u->pindex.count("controlnet_down_blocks." + std::to_string(i) + ".weight"); ++i) {
+            pk.bf16_same("controlnet_down_blocks." + std::to_string(i) + ".weight"); pk.f32("controlnet_down_blocks." + std::to_string(i) + ".bias");
+        }
+        pk.bf16_same("controlnet_mid_block.weight"); pk.f32("controlnet_mid_block.bias");
+        return 0;
     }
     pk.f32("conv_norm_out.weight"); pk.f32("conv_norm_out.bias");
     pk.conv3_ohwi("conv_out.weight", c.out_channels, c0); pk.f32("conv_out.bias");

@@ -36,7 +36,7 @@ struct Builder {
     // SD_GN_PRODUCER_STATS=0: every GroupNorm runs its own statistics pass (round-1 behaviour)
     bool producer_stats = !(getenv("SD_GN_PRODUCER_STATS") && atoi(getenv("SD_GN_PRODUCER_STATS")) == 0);
     void want_stats(Op& o, int M, int N) {      // called for producers whose output feeds a GroupNorm
-        if (!producer_stats || u->kind != 0 || o.splitk > 1 || M % 64 != 0 || o.epi != 0 || o.rpb != 0) return;
+        if (!producer_stats || !u->unet_like() || o.splitk > 1 || M % 64 != 0 || o.epi != 0 || o.rpb != 0) return;
         o.stats = tensor((size_t)(M / 64) * N * 2 * 4);
         stats_of[o.out] = o.stats;
     }
@@ -212,7 +212,7 @@ struct Builder {
             GemmArgs g;
             g.M = M; g.N = cout; g.Cin = cout; g.K = 9 * cout; g.ldw = g.K; g.Hin = g.Hout = rh; g.Win = g.Wout = rw;
             g.Csc1 = c1; g.Csc2 = x2 >= 0 ? c2 : 0;
-            if (shortcut_fuse && !fq && u->kind == 0 && u->woff.count(p + "conv2.bias+shortcut") && sd_conv_halo_shortcut_applicable(g)) {
+            if (shortcut_fuse && !fq && u->unet_like() && u->woff.count(p + "conv2.bias+shortcut") && sd_conv_halo_shortcut_applicable(g)) {
                 const int out = conv3(t3, rh, rw, cout, cout, 1, 0, p + "conv2.weight", p + "conv2.bias+shortcut", 0, -1, -1, fq);
                 Op& o = pl.ops.back();
                 o.scx1 = x1; o.scc1 = c1; o.scx2 = x2; o.scc2 = g.Csc2; o.scw = W(p + "conv_shortcut.weight");
@@ -594,7 +594,7 @@ struct Builder {
         const int h_skip = prefix_rep > 1 ? replicate(h, (size_t)UB * rh * rw * c0 * 2, prefix_rep) : h;
         pl.taps["conv_in"] = h_skip;
         int ch = c0;
-        std::vector<int> skips{h_skip}, skip_ch{c0};
+        std::vector<int> skips{h_skip}, skip_ch{c0}, skip_hw{rh * rw};
         // ---- down ----
         for (int i = 0; i < nl; ++i) {
             const int co = c.block_out_channels[i];
@@ -606,7 +606,7 @@ struct Builder {
                 ch = co;
                 if (c.attn_levels[i]) h = transformer(bp + "attentions." + std::to_string(j) + ".", h, co, rh, rw);
                 wrapstack.pop_back();
-                skips.push_back(h); skip_ch.push_back(co);
+                skips.push_back(h); skip_ch.push_back(co); skip_hw.push_back(rh * rw);
             }
             if (i < nl - 1) {
                 wrapstack.push_back(Wrap{0, i, c.layers_per_block});
@@ -614,7 +614,7 @@ struct Builder {
                 h = conv3(h, rh, rw, co, co, 2, 0, d + "weight", d + "bias", 0, -1, -1);
                 wrapstack.pop_back();
                 rh /= 2; rw /= 2;
-                skips.push_back(h); skip_ch.push_back(co);
+                skips.push_back(h); skip_ch.push_back(co); skip_hw.push_back(rh * rw);
             }
             wrapstack.pop_back();
             pl.taps["down" + std::to_string(i)] = h;
@@ -626,6 +626,42 @@ struct Builder {
         h = resnet("mid_block.resnets.1.", h, ch, -1, 0, ch, rh, rw, t_proj);
         wrapstack.pop_back();
         pl.taps["mid"] = h;
+        skips.push_back(h); skip_ch.push_back(ch); skip_hw.push_back(rh * rw);       // (the mid output: the thirteenth residual)
+        if ((int)skips.size() > MAX_CONTROL_RES && (u->kind == 5 || pl.cn)) { error = "more than 16 ControlNet residuals"; return; }
+        control_segments(c, UB, pl.lh, pl.lw, &pl.cn_off, &pl.cn_count);
+        if (u->kind == 5) {
+            // ---- ControlNet: the zero convs, one 1x1 GEMM per residual straight into the caller's buffer (T_EPS at the segment's
+            // offset, unscaled: conditioning_scale is applied where the residuals are consumed) ----
+            for (size_t i = 0; i < skips.size(); ++i) {
+                const bool mid = i + 1 == skips.size();
+                const std::string w = mid ? "controlnet_mid_block." : "controlnet_down_blocks." + std::to_string(i) + ".";
+                const int C = skip_ch[i], M = UB * skip_hw[i];
+                if ((long)M * C != pl.cn_count[i]) { error = "ControlNet residual layout"; return; }
+                Op o; o.kind = OP_GEMM; o.x1 = skips[i]; o.K1 = o.K = o.Kalg = C; o.M = M; o.N = C;
+                o.w = W(w + "weight"); o.b = W(w + "bias");
+                o.splitk = sd_gemm_splitk(M, C, C, 0);
+                if (o.splitk > 1) o.aux = tensor((size_t)o.splitk * M * C * 4);
+                o.out = T_EPS; o.coff = (long)(pl.cn_off[i] / 2);
+                push(o);
+            }
+            return;
+        }
+        if (pl.cn) {
+            // ---- "control" variant: x <- x + scale * r on the twelve skips (conv_in's is the replicated tensor under rep == 2)
+            // and the mid output, in place, ONE launch.  Every reader of the unmodified tensors -- the down path and the mid
+            // block, including a GroupNorm that finishes a producer's deferred split-K reduce -- has run (op_tensors lists the
+            // tensors as this op's inputs, so fuse_deferred_reduce never defers a reduce across it).  The producers' epilogue
+            // statistics of these tensors are stale from here on: the up-block GroupNorms run their own statistics pass.
+            Op o; o.kind = OP_RES_ADD; o.nres = (int)skips.size(); o.B = UB;
+            for (size_t i = 0; i < skips.size(); ++i) {
+                if ((long)UB * skip_hw[i] * skip_ch[i] != pl.cn_count[i]) { error = "ControlNet residual layout"; return; }
+                o.res_t[i] = skips[i];
+                o.M += (int)pl.cn_count[i];
+                stats_of.erase(skips[i]);
+            }
+            push(o);
+        }
+        skips.pop_back(); skip_ch.pop_back(); skip_hw.pop_back();
         // ---- up ----
         const int nres = c.layers_per_block + 1;
         for (int i = 0; i < nl; ++i) {
@@ -666,10 +702,11 @@ bool wrap_skipped(const Wrap& w, int branch) {
     return w.type == 0 ? w.layer_i >= cache_layer_id : w.layer_i > cache_layer_id;
 }
 
-void op_tensors(const Op& o, int ins[16], int& nin) {
+void op_tensors(const Op& o, int ins[32], int& nin) {
     nin = 0;
     for (int t : {o.x1, o.x2, o.r, o.b2t, o.wt, o.s1, o.s2, o.lnrs, o.slab_t, o.slab_r, o.slab_b2t, o.scx1, o.scx2})
         if (t >= 0) ins[nin++] = t;
+    for (int k = 0; k < o.nres; ++k) ins[nin++] = o.res_t[k];      // (OP_RES_ADD reads and rewrites them in place)
 }
 
 // A split-K conv / GEMM whose output is first read by a single-launch GroupNorm (the 8x8 and 16x16 levels: every resnet conv,
@@ -701,7 +738,7 @@ void fuse_deferred_reduce(sd_unet* u, Plan& pl) {
         if ((long)G.B * G.HW != P.M || G.C1 != P.N || skipped(P) != skipped(G)) continue;
         bool first_reader = true;
         for (int i = p + 1; i < g && first_reader; ++i) {
-            int ins[16], nin;
+            int ins[32], nin;
             op_tensors(pl.ops[i], ins, nin);
             for (int k = 0; k < nin; ++k)
                 if (ins[k] == P.out) first_reader = false;
@@ -729,7 +766,7 @@ void assign_memory(sd_unet* u, Plan& pl) {
         }
         for (int i = 0; i < nops; ++i) {
             if (pl.skipped[i]) continue;
-            int ins[16], nin;
+            int ins[32], nin;
             op_tensors(pl.ops[i], ins, nin);
             for (int k = 0; k < nin; ++k) {
                 const int p = producer[ins[k]];
@@ -742,7 +779,7 @@ void assign_memory(sd_unet* u, Plan& pl) {
     // lifetimes over the full plan
     for (int i = 0; i < nops; ++i) {
         const Op& o = pl.ops[i];
-        int ins[16], nin;
+        int ins[32], nin;
         op_tensors(o, ins, nin);
         for (int k = 0; k < nin; ++k) pl.tensors[ins[k]].last = std::max(pl.tensors[ins[k]].last, i);
         for (int t : {o.out, o.aux, o.stats, o.rs})
@@ -789,7 +826,7 @@ void assign_memory(sd_unet* u, Plan& pl) {
 // CFG de-duplication applies to a forward whose UNet batch is exactly two copies of the latent batch (SD_CFG_DEDUP=0: off)
 int plan_rep(const sd_unet* u, int latent_batch, int unet_batch) {
     static const bool off = getenv("SD_CFG_DEDUP") && atoi(getenv("SD_CFG_DEDUP")) == 0;
-    return (!off && u->kind == 0 && u->cfg.attn_levels[0] && latent_batch > 0 && unet_batch == 2 * latent_batch) ? 2 : 1;
+    return (!off && u->unet_like() && u->cfg.attn_levels[0] && latent_batch > 0 && unet_batch == 2 * latent_batch) ? 2 : 1;
 }
 
 // Latent sizes a handle takes per call (the _hw entry points).  UNet: both sides divisible by 2^(num_levels - 1), so that
@@ -800,7 +837,7 @@ int check_latent_size(const sd_unet* u, int lh, int lw, const char* who) {
         SD_REQUIRE(lh >= 8 && lw >= 8 && lh <= 128 && lw <= 128 && lh % 8 == 0 && lw % 8 == 0,
                    "%s: latent %dx%d (the VAE %s takes sides that are multiples of 8 in [8, 128])", who, lh, lw,
                    u->kind == 1 ? "decoder" : "encoder");
-    } else if (u->kind == 0) {
+    } else if (u->unet_like()) {
         const int d = 1 << (u->cfg.num_levels - 1);
         SD_REQUIRE(lh >= d && lw >= d && lh <= 256 && lw <= 256 && lh % d == 0 && lw % d == 0,
                    "%s: latent %dx%d (both sides must be multiples of %d, at most 256)", who, lh, lw, d);
@@ -808,18 +845,36 @@ int check_latent_size(const sd_unet* u, int lh, int lw, const char* who) {
     return 0;
 }
 
+size_t control_segments(const sd_unet_config& c, int UB, int lh, int lw, std::vector<size_t>* off, std::vector<long>* count) {
+    off->clear(); count->clear();
+    size_t bytes = 0;
+    auto seg = [&](int C, int h, int w) {
+        const long n = (long)UB * h * w * C;
+        off->push_back(bytes); count->push_back(n);
+        bytes = (bytes + (size_t)n * 2 + 255) / 256 * 256;
+    };
+    int h = lh, w = lw;
+    seg(c.block_out_channels[0], h, w);
+    for (int i = 0; i < c.num_levels; ++i) {
+        for (int j = 0; j < c.layers_per_block; ++j) seg(c.block_out_channels[i], h, w);
+        if (i < c.num_levels - 1) { h /= 2; w /= 2; seg(c.block_out_channels[i], h, w); }
+    }
+    seg(c.block_out_channels[c.num_levels - 1], h, w);
+    return bytes;
+}
+
 bool ip_active(const sd_unet* u, int UB, int branch, int lh, int lw) {
     return u->ip_keys.count(std::make_tuple(UB, branch < 0 ? -1 : branch, lh, lw)) != 0;
 }
 
-int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw, int ip) {
+int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw, int ip, int cn) {
     SD_REQUIRE(u && u->finalized, "unet: parameters not finalized");
     SD_REQUIRE(UB > 0 && UB <= 4096, "unet: bad batch %d", UB);
     SD_REQUIRE(branch < 3 * u->cfg.num_levels, "unet: cache_branch_id %d out of range", branch);
     if (branch < 0) branch = -1;
     if (lh < 0) lh = u->cfg.sample_size;
     if (lw < 0) lw = u->cfg.sample_size;
-    auto key = std::make_tuple(UB, branch, rep, lh, lw, ip);
+    auto key = std::make_tuple(UB, branch, rep, lh, lw, ip, cn);
     auto it = u->plans.find(key);
     if (it == u->plans.end()) {
         if (lh != u->cfg.sample_size || lw != u->cfg.sample_size)
@@ -831,6 +886,7 @@ int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw
         pl.lh = lh;
         pl.lw = lw;
         pl.ip = ip;
+        pl.cn = cn;
         Builder b{u, pl, UB, {}};
         b.build();
         SD_REQUIRE(b.error.empty(), "unet: cannot build the plan for batch %d (cache branch %d, latent %dx%d): %s", UB, branch, lh, lw,

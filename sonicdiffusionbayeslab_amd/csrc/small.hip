@@ -153,6 +153,106 @@ __global__ __launch_bounds__(1024) void conv_in_cond_kernel(const float* __restr
     }
 }
 
+// ---- conv_in of a ControlNet: the 4-channel conv above plus an addend (the conditioning embedding the handle stores once
+// per call, NHWC bf16 [Badd][H][W][Cout], batch index modulo Badd) in the SAME launch: the conv sum in the order of
+// conv_in_kernel, the addend added in fp32, ONE bf16 rounding.  Thread = 2 output channels as above; the four lanes of a
+// quad hold 8 consecutive channels, exchange their packed pairs and the quad's first lane stores 16 bytes.
+// (launched with Cout / 2 threads rounded up to whole waves, at most 1024: the bound keeps it within 128 VGPRs)
+__global__ __launch_bounds__(1024) void conv_in_add_kernel(const float* __restrict__ x, int Bsrc, const bf16_t* __restrict__ addend, int Badd,
+                                   const float* __restrict__ Wt, const float* __restrict__ bias, bf16_t* __restrict__ y,
+                                   int H, int W, int Cout) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* patch = (float*)smem;  // [4][3][W+2]
+    constexpr int CIN = 4;
+    const int yrow = blockIdx.x, b = blockIdx.y;
+    const int bs = b % Bsrc, ba = b % Badd;
+    const int tid = threadIdx.x;
+    const int PW = W + 2;
+    for (int i = tid; i < CIN * 3 * PW; i += blockDim.x) {
+        const int ci = i / (3 * PW), rem = i - ci * 3 * PW;
+        const int dy = rem / PW, px = rem - dy * PW;
+        const int iy = yrow + dy - 1, ix = px - 1;
+        float v = 0.f;
+        if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = x[(((long)bs * CIN + ci) * H + iy) * W + ix];
+        patch[i] = v;
+    }
+    __syncthreads();
+    const int co = tid * 2;
+    if (co >= Cout) return;          // (Cout % 8 == 0: a quad is inside or outside as a whole)
+    float w0[CIN * 9], w1[CIN * 9];
+#pragma unroll
+    for (int k = 0; k < CIN * 9; ++k) {
+        w0[k] = Wt[k * Cout + co];
+        w1[k] = Wt[k * Cout + co + 1];
+    }
+    const float b0 = bias[co], b1 = bias[co + 1];
+    const bf16_t* ar = addend + (((long)ba * H + yrow) * W) * Cout + co;
+    bf16_t* yr = y + (((long)b * H + yrow) * W) * Cout + co;
+    const int lane = tid & 63, q0 = lane & ~3;
+    for (int ox = 0; ox < W; ++ox) {
+        float a0 = b0, a1 = b1;
+#pragma unroll
+        for (int ci = 0; ci < CIN; ++ci)
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+                for (int dx = 0; dx < 3; ++dx) {
+                    const float v = patch[(ci * 3 + dy) * PW + ox + dx];
+                    a0 += v * w0[ci * 9 + dy * 3 + dx];
+                    a1 += v * w1[ci * 9 + dy * 3 + dx];
+                }
+        const unsigned ad = *(const unsigned*)(ar + (long)ox * Cout);
+        const int p = (int)pack2bf(a0 + bflo(ad), a1 + bfhi(ad));
+        u32x4 v;
+        v[0] = (unsigned)__shfl(p, q0); v[1] = (unsigned)__shfl(p, q0 + 1);
+        v[2] = (unsigned)__shfl(p, q0 + 2); v[3] = (unsigned)__shfl(p, q0 + 3);
+        if ((lane & 3) == 0) *(u32x4*)(yr + (long)ox * Cout) = v;
+    }
+}
+
+// ---- ControlNet residuals into the UNet's skip path: x <- bf16(float(x) + scale * float(r)) in place over up to 16 segments
+// in ONE launch.  The table rides in the kernel arguments; a block owns RES_ADD_BLOCK consecutive elements of one segment
+// (first_block[k] = the first block of segment k), a thread one 16-byte vector of x and of r; the last vector of a segment
+// whose length is no multiple of 8 goes element by element.
+constexpr int RES_ADD_MAX = SD_MAX_RES_SEGMENTS, RES_ADD_BLOCK = 256 * 8;
+struct ResAddArgs {
+    bf16_t* x[RES_ADD_MAX];
+    const bf16_t* r[RES_ADD_MAX];
+    long n[RES_ADD_MAX];
+    int first_block[RES_ADD_MAX];
+    int nseg;
+    float scale;
+};
+__global__ __launch_bounds__(256) void residual_add_kernel(ResAddArgs a) {
+    const int blk = (int)blockIdx.x;
+    bf16_t* x = a.x[0];
+    const bf16_t* r = a.r[0];
+    long n = a.n[0];
+    int first = 0;
+#pragma unroll
+    for (int k = 1; k < RES_ADD_MAX; ++k)
+        if (k < a.nseg && blk >= a.first_block[k]) { x = a.x[k]; r = a.r[k]; n = a.n[k]; first = a.first_block[k]; }
+    const long i0 = ((long)(blk - first) * 256 + threadIdx.x) * 8;
+    if (i0 >= n) return;
+    if (i0 + 8 <= n) {
+        u32x4 xv = *(const u32x4*)(x + i0);
+        const u32x4 rv = *(const u32x4*)(r + i0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xv[j] = pack2bf(bflo(xv[j]) + a.scale * bflo(rv[j]), bfhi(xv[j]) + a.scale * bfhi(rv[j]));
+        *(u32x4*)(x + i0) = xv;
+    } else {
+        for (long i = i0; i < n; ++i) x[i] = f2bf(bf2f(x[i]) + a.scale * bf2f(r[i]));
+    }
+}
+
+// fp32 NCHW [B][C][hw] -> bf16 NHWC [B][hw][C] (the ControlNet's control image, once per call; C = 3)
+__global__ void nchw_to_nhwc_bf16_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, int C, long hw, long total) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long b = i / hw, p = i - b * hw;
+    for (int c = 0; c < C; ++c) dst[i * C + c] = f2bf(src[(b * C + c) * hw + p]);
+}
+
 // the five constant channels of a call, packed once: cond[b] = [mask[b] | masked_latents[b]] ([B][5][hw] fp32)
 __global__ void inpaint_cond_pack_kernel(const float* __restrict__ mask, const float* __restrict__ masked,
                                          float* __restrict__ cond, long hw4, long n4) {
@@ -723,6 +823,51 @@ int sd_launch_conv_in_cond(const float* x, int Bsrc, const float* cond, int Bcon
     SD_REQUIRE(smem <= 64 * 1024, "conv_in_cond: W=%d needs %zu bytes of LDS (64 KiB per workgroup)", W, smem);
     hipLaunchKernelGGL(conv_in_cond_kernel, dim3(H, B), dim3(threads), smem, stream, x, Bsrc, cond, Bcond, Wt, bias, y, H, W,
                        Cout);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sd_launch_conv_in_add(const float* x, int Bsrc, const bf16_t* addend, int Badd, const float* Wt, const float* bias,
+                          bf16_t* y, int B, int H, int W, int Cout, hipStream_t stream) {
+    SD_REQUIRE(x && addend && Wt && bias && y, "conv_in_add: null operand");
+    SD_REQUIRE(Cout > 0 && Cout % 8 == 0 && Cout <= 2048, "conv_in_add: Cout=%d (a multiple of 8, at most 2048)", Cout);
+    SD_REQUIRE(Bsrc > 0 && Badd > 0 && B > 0 && B <= 65535 && B % Bsrc == 0 && B % Badd == 0,
+               "conv_in_add: batch %d not a multiple of the latent batch %d and the addend batch %d", B, Bsrc, Badd);
+    SD_REQUIRE(H > 0 && W > 0, "conv_in_add: H=%d W=%d", H, W);
+    SD_REQUIRE((((uintptr_t)addend | (uintptr_t)y) & 15) == 0, "conv_in_add: addend and y must be 16-byte aligned");
+    const int threads = (Cout / 2 + 63) / 64 * 64;
+    const size_t smem = (size_t)4 * 3 * (W + 2) * sizeof(float);
+    SD_REQUIRE(smem <= 64 * 1024, "conv_in_add: W=%d needs %zu bytes of LDS (64 KiB per workgroup)", W, smem);
+    hipLaunchKernelGGL(conv_in_add_kernel, dim3(H, B), dim3(threads), smem, stream, x, Bsrc, addend, Badd, Wt, bias, y, H, W, Cout);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sd_launch_residual_add(bf16_t* const* x, const bf16_t* const* r, const long* n, int nseg, float scale, hipStream_t stream) {
+    SD_REQUIRE(x && r && n && nseg >= 1 && nseg <= RES_ADD_MAX, "residual_add: %d segments (1 .. %d)", nseg, RES_ADD_MAX);
+    SD_REQUIRE(scale == scale && fabsf(scale) <= 1e4f, "residual_add: scale %g", scale);
+    ResAddArgs a;
+    long blocks = 0;
+    for (int k = 0; k < RES_ADD_MAX; ++k) {
+        const int s = k < nseg ? k : 0;
+        SD_REQUIRE(x[s] && r[s] && n[s] > 0, "residual_add: segment %d is empty or null", s);
+        SD_REQUIRE((((uintptr_t)x[s] | (uintptr_t)r[s]) & 15) == 0, "residual_add: segment %d is not 16-byte aligned", s);
+        a.x[k] = x[s]; a.r[k] = r[s]; a.n[k] = n[s];
+        a.first_block[k] = (int)blocks;
+        if (k < nseg) blocks += (n[s] + RES_ADD_BLOCK - 1) / RES_ADD_BLOCK;
+        SD_REQUIRE(blocks < (1L << 31), "residual_add: too many elements");
+    }
+    a.nseg = nseg; a.scale = scale;
+    hipLaunchKernelGGL(residual_add_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int sd_launch_nchw_to_nhwc_bf16(const float* src, bf16_t* dst, int B, int C, long hw, hipStream_t stream) {
+    SD_REQUIRE(src && dst && B > 0 && C > 0 && hw > 0, "nchw_to_nhwc_bf16: B=%d C=%d hw=%ld", B, C, hw);
+    const long total = (long)B * hw;
+    SD_REQUIRE((total + 255) / 256 < (1L << 31), "nchw_to_nhwc_bf16: too many pixels");
+    hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src, dst, C, hw, total);
     SD_CHECK_HIP(hipGetLastError());
     return 0;
 }

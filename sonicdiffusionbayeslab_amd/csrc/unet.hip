@@ -48,7 +48,7 @@ const void* zero_page() { return g_zero_page; }
 
 int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* latents, int latent_batch, float* eps_out,
            float timestep, hipStream_t stream) {
-    auto T = [&](int id) -> char* { return id >= 0 ? ws + pl.tensors[id].off : nullptr; };
+    auto T = [&](int id) -> char* { return id >= 0 ? ws + pl.tensors[id].off : id == T_EPS ? (char*)eps_out : nullptr; };
     const char* wb = u->dweights;
     switch (o.kind) {
         case OP_SINUSOID:
@@ -66,6 +66,14 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
                            u->inpaint_b, u->inpaint_h, u->inpaint_w, o.B, o.Hin, o.Win);
                 return sd_launch_conv_in_cond(latents, latent_batch, u->dinpaint, u->inpaint_b, (const float*)(wb + o.w),
                                               (const float*)(wb + o.b), (bf16_t*)T(o.out), o.B, o.Hin, o.Win, o.N, stream);
+            }
+            if (u->kind == 5) {
+                SD_REQUIRE(u->cn_b > 0, "controlnet_forward: no conditioning image is set (sd_controlnet_set_cond_hw)");
+                SD_REQUIRE(u->cn_h == o.Hin && u->cn_w == o.Win && o.B % u->cn_b == 0,
+                           "controlnet_forward: the conditioning image was set for batch %d at %dx%d, the forward runs batch %d at %dx%d",
+                           u->cn_b, u->cn_h, u->cn_w, o.B, o.Hin, o.Win);
+                return sd_launch_conv_in_add(latents, latent_batch, u->cn_embed, u->cn_b, (const float*)(wb + o.w),
+                                             (const float*)(wb + o.b), (bf16_t*)T(o.out), o.B, o.Hin, o.Win, o.N, stream);
             }
             return sd_launch_conv_in(o.x1 >= 0 ? (const float*)T(o.x1) : latents, o.x1 >= 0 ? o.B : latent_batch,
                                      (const float*)(wb + o.w), (const float*)(wb + o.b), (bf16_t*)T(o.out), o.B, o.Hin,
@@ -164,6 +172,17 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
             return sd_launch_ip_xattn((const bf16_t*)T(o.x1), (bf16_t*)T(o.out), (const bf16_t*)T(o.wt), (const bf16_t*)T(o.x2),
                                       (const float*)(wb + o.g), (const float*)(wb + o.be), o.eps, o.M, o.N, o.rpb, o.heads,
                                       u->cfg.ip_adapter_tokens, stream);
+        case OP_RES_ADD: {
+            SD_REQUIRE(u->ctrl_res && o.nres == (int)pl.cn_off.size() && o.nres <= MAX_CONTROL_RES, "forward: no ControlNet residuals are set");
+            bf16_t* x[MAX_CONTROL_RES];
+            const bf16_t* r[MAX_CONTROL_RES];
+            long n[MAX_CONTROL_RES];
+            for (int k = 0; k < o.nres; ++k) {
+                x[k] = (bf16_t*)T(o.res_t[k]); r[k] = (const bf16_t*)(u->ctrl_res + pl.cn_off[k]); n[k] = pl.cn_count[k];
+                SD_REQUIRE((size_t)n[k] * 2 <= pl.tensors[o.res_t[k]].bytes, "forward: ControlNet residual %d exceeds its tensor", k);
+            }
+            return sd_launch_residual_add(x, r, n, o.nres, u->ctrl_scale, stream);
+        }
         case OP_REPLICATE:
             return sd_launch_replicate(T(o.x1), T(o.out), (long)o.M * 16, o.N, stream);
         case OP_CLIP_EMBED:
@@ -215,7 +234,8 @@ static sd_unet* new_handle(int kind, const sd_unet_config* cfg) {
     u->kind = kind;
     if (cfg) {
         u->cfg = *cfg;
-        if (kind != 0) u->cfg.time_cond_proj_dim = u->cfg.ip_adapter_tokens = u->cfg.ip_adapter_embed_dim = 0;      // (UNet fields)
+        if (kind != 0) u->cfg.ip_adapter_tokens = u->cfg.ip_adapter_embed_dim = 0;      // (UNet fields)
+        if (kind != 0 && kind != 5) u->cfg.time_cond_proj_dim = 0;
         u->debug_taps = getenv("SD_DEBUG_TAPS") != nullptr;
     } else {
         memset(&u->cfg, 0, sizeof(u->cfg));
@@ -251,45 +271,51 @@ static int run_plan(sd_unet* u, const Plan& pl, const char* who, void* workspace
     return 0;
 }
 
-extern "C" int sd_unet_create(const sd_unet_config* cfg, sd_unet** out) {
-    SD_REQUIRE(cfg && out, "sd_unet_create: null argument");
-    SD_REQUIRE(cfg->num_levels >= 1 && cfg->num_levels <= 8, "sd_unet_create: num_levels %d", cfg->num_levels);
+// what a UNet and the ControlNet paired with it share (`who` names the entry point in the messages)
+static int check_unet_config(const sd_unet_config* cfg, const char* who) {
+    SD_REQUIRE(cfg->num_levels >= 1 && cfg->num_levels <= 8, "%s: num_levels %d", who, cfg->num_levels);
     SD_REQUIRE(cfg->in_channels == 4 || cfg->in_channels == 9,
-               "sd_unet_create: in_channels %d (4, or 9 for an inpainting UNet: latents | mask | masked-image latents)",
+               "%s: in_channels %d (4, or 9 for an inpainting UNet: latents | mask | masked-image latents)", who,
                cfg->in_channels);
-    SD_REQUIRE(cfg->out_channels >= 1 && cfg->out_channels <= 4, "sd_unet_create: out_channels %d", cfg->out_channels);
+    SD_REQUIRE(cfg->out_channels >= 1 && cfg->out_channels <= 4, "%s: out_channels %d", who, cfg->out_channels);
     for (int i = 0; i < cfg->num_levels; ++i) {
         const int c = cfg->block_out_channels[i];
         SD_REQUIRE(c % 64 == 0 && c % cfg->norm_num_groups == 0 && c / cfg->norm_num_groups >= 8,
-                   "sd_unet_create: block_out_channels[%d]=%d must be a multiple of 64 with >= 8 channels per group", i, c);
+                   "%s: block_out_channels[%d]=%d must be a multiple of 64 with >= 8 channels per group", who, i, c);
         if (cfg->attn_levels[i]) {
             const int d = c / cfg->num_heads;
             SD_REQUIRE(c % cfg->num_heads == 0 && (d == 40 || d == 80 || d == 160),
-                       "sd_unet_create: head dim %d at level %d not built (40/80/160)", d, i);
+                       "%s: head dim %d at level %d not built (40/80/160)", who, d, i);
         }
     }
     const int dmid = cfg->block_out_channels[cfg->num_levels - 1] / cfg->num_heads;
-    SD_REQUIRE(dmid == 40 || dmid == 80 || dmid == 160, "sd_unet_create: mid-block head dim %d not built", dmid);
-    SD_REQUIRE(cfg->cross_attention_dim % 64 == 0, "sd_unet_create: cross_attention_dim must be a multiple of 64");
-    SD_REQUIRE(cfg->sample_size % (1 << (cfg->num_levels - 1)) == 0, "sd_unet_create: sample_size not divisible");
-    SD_REQUIRE(cfg->context_len >= 1, "sd_unet_create: context_len");
+    SD_REQUIRE(dmid == 40 || dmid == 80 || dmid == 160, "%s: mid-block head dim %d not built", who, dmid);
+    SD_REQUIRE(cfg->cross_attention_dim % 64 == 0, "%s: cross_attention_dim must be a multiple of 64", who);
+    SD_REQUIRE(cfg->sample_size % (1 << (cfg->num_levels - 1)) == 0, "%s: sample_size not divisible", who);
+    SD_REQUIRE(cfg->context_len >= 1, "%s: context_len", who);
     SD_REQUIRE(cfg->weight_dtype == SD_DTYPE_BF16 || cfg->weight_dtype == SD_DTYPE_FP8_E4M3,
-               "sd_unet_create: weight_dtype %d (0 = bf16, 1 = fp8 e4m3)", cfg->weight_dtype);
-    SD_REQUIRE(cfg->fp8_act_scale_norm >= 0.f && cfg->fp8_act_scale_ff >= 0.f, "sd_unet_create: negative fp8 activation scale");
+               "%s: weight_dtype %d (0 = bf16, 1 = fp8 e4m3)", who, cfg->weight_dtype);
+    SD_REQUIRE(cfg->fp8_act_scale_norm >= 0.f && cfg->fp8_act_scale_ff >= 0.f, "%s: negative fp8 activation scale", who);
     SD_REQUIRE(cfg->time_cond_proj_dim >= 0 && cfg->time_cond_proj_dim % 8 == 0,
-               "sd_unet_create: time_cond_proj_dim %d must be 0 (none) or a positive multiple of 8 (the GEMV reads 8 at a time)",
+               "%s: time_cond_proj_dim %d must be 0 (none) or a positive multiple of 8 (the GEMV reads 8 at a time)", who,
                cfg->time_cond_proj_dim);
     if (cfg->ip_adapter_tokens != 0 || cfg->ip_adapter_embed_dim != 0) {
-        SD_REQUIRE(cfg->ip_adapter_tokens == 4, "sd_unet_create: ip_adapter_tokens %d (4 image tokens are built: the plain ip-adapter_sd15 "
-                   "family; the \"plus\" / \"full-face\" adapters with 16 or 257 tokens are not)", cfg->ip_adapter_tokens);
+        SD_REQUIRE(cfg->ip_adapter_tokens == 4, "%s: ip_adapter_tokens %d (4 image tokens are built: the plain ip-adapter_sd15 "
+                   "family; the \"plus\" / \"full-face\" adapters with 16 or 257 tokens are not)", who, cfg->ip_adapter_tokens);
         SD_REQUIRE(cfg->ip_adapter_embed_dim > 0 && cfg->ip_adapter_embed_dim % 64 == 0,
-                   "sd_unet_create: ip_adapter_embed_dim %d must be a positive multiple of 64", cfg->ip_adapter_embed_dim);
-        SD_REQUIRE(cfg->cross_attention_dim <= 1536, "sd_unet_create: an IP-Adapter needs cross_attention_dim <= 1536 (the token LayerNorm)");
+                   "%s: ip_adapter_embed_dim %d must be a positive multiple of 64", who, cfg->ip_adapter_embed_dim);
+        SD_REQUIRE(cfg->cross_attention_dim <= 1536, "%s: an IP-Adapter needs cross_attention_dim <= 1536 (the token LayerNorm)", who);
         for (int i = 0; i < cfg->num_levels; ++i)
             SD_REQUIRE(sd_ip_xattn_applicable(cfg->block_out_channels[i], cfg->num_heads, cfg->ip_adapter_tokens),
-                       "sd_unet_create: an IP-Adapter needs 1, 2, 4 or 8 heads and channels that are a multiple of 32 up to 2048 "
-                       "(level %d: %d channels, %d heads)", i, cfg->block_out_channels[i], cfg->num_heads);
+                       "%s: an IP-Adapter needs 1, 2, 4 or 8 heads and channels that are a multiple of 32 up to 2048 "
+                       "(level %d: %d channels, %d heads)", who, i, cfg->block_out_channels[i], cfg->num_heads);
     }
+    return 0;
+}
+
+extern "C" int sd_unet_create(const sd_unet_config* cfg, sd_unet** out) {
+    SD_REQUIRE(cfg && out, "sd_unet_create: null argument");
+    if (check_unet_config(cfg, "sd_unet_create")) return -1;
     sd_unet* u = new_handle(0, cfg);
     u->fp8 = cfg->weight_dtype == SD_DTYPE_FP8_E4M3;
     if (cfg->fp8_act_scale_norm > 0.f) u->s_norm = cfg->fp8_act_scale_norm;
@@ -489,6 +515,8 @@ extern "C" void sd_unet_destroy(sd_unet* u) {
     if (u->dweights) (void)hipFree(u->dweights);
     if (u->dcond) (void)hipFree(u->dcond);
     if (u->dinpaint) (void)hipFree(u->dinpaint);
+    if (u->cn_embed) (void)hipFree(u->cn_embed);
+    if (u->cn_scratch) (void)hipFree(u->cn_scratch);
     for (auto& kv : u->prep_tabs)
         if (kv.second) (void)hipFree(kv.second);
     delete u;
@@ -543,7 +571,7 @@ extern "C" int sd_unet_finalize(sd_unet* u) {
     if (ensure_zero_page()) return -2;
     SD_CHECK_HIP(hipMalloc((void**)&u->dweights, u->hblob.size()));
     SD_CHECK_HIP(hipMemcpy(u->dweights, u->hblob.data(), u->hblob.size(), hipMemcpyHostToDevice));
-    if (u->kind == 0 && u->cfg.time_cond_proj_dim > 0)
+    if (u->unet_like() && u->cfg.time_cond_proj_dim > 0)
         SD_CHECK_HIP(hipMalloc((void**)&u->dcond, (size_t)u->cfg.block_out_channels[0] * sizeof(float)));
     u->hblob.release();
     for (auto& p : u->params) std::vector<float>().swap(p.data);
@@ -574,10 +602,11 @@ extern "C" long long sd_unet_workspace_bytes_hw(sd_unet* u, int unet_batch, int 
     size_t bytes = pl->total_bytes;
     const bool pair = unet_batch % 2 == 0 && plan_rep(u, unet_batch / 2, unet_batch) == 2;      // the CFG-pair variant of the plan
     for (int ip = 0; ip <= (u->kind == 0 && u->cfg.ip_adapter_tokens > 0 ? 1 : 0); ++ip)         // ... and the IP-Adapter variants
-        for (int rep = 1; rep <= (pair ? 2 : 1); ++rep) {
-            if (get_plan(u, unet_batch, cache_branch_id, &pl, rep, latent_h, latent_w, ip)) return -1;
-            bytes = std::max(bytes, pl->total_bytes);
-        }
+        for (int rep = 1; rep <= (pair ? 2 : 1); ++rep)
+            for (int cn = 0; cn <= (u->kind == 0 && u->ctrl_enabled && cache_branch_id < 0 ? 1 : 0); ++cn) {      // ... and, once a ControlNet's residuals were set, the control variants
+                if (get_plan(u, unet_batch, cache_branch_id, &pl, rep, latent_h, latent_w, ip, cn)) return -1;
+                bytes = std::max(bytes, pl->total_bytes);
+            }
     return (long long)bytes;
 }
 
@@ -592,7 +621,7 @@ extern "C" int sd_unet_set_context(sd_unet* u, void* stream, const float* ehs, i
 // needs its own set_context.
 extern "C" int sd_unet_set_context_hw(sd_unet* u, void* stream, const float* ehs, int unet_batch, int cache_branch_id,
                                       int latent_h, int latent_w, void* workspace, long long workspace_bytes) {
-    SD_REQUIRE(u && u->kind == 0, "set_context: not a UNet handle");
+    SD_REQUIRE(u && u->unet_like(), "set_context: not a UNet or ControlNet handle");
     SD_REQUIRE(ehs && workspace, "set_context: null argument");
     if (check_latent_size(u, latent_h, latent_w, "set_context")) return -1;
     Plan* plp;
@@ -653,7 +682,7 @@ extern "C" int sd_unet_set_context_hw(sd_unet* u, void* stream, const float* ehs
 }
 
 extern "C" int sd_unet_set_timestep_cond(sd_unet* u, void* stream, const float* cond) {
-    SD_REQUIRE(u && u->kind == 0, "set_timestep_cond: not a UNet handle");
+    SD_REQUIRE(u && u->unet_like(), "set_timestep_cond: not a UNet or ControlNet handle");
     if (!cond) {
         u->cond_set = false;
         return 0;
@@ -765,6 +794,143 @@ extern "C" int sd_unet_set_ip_adapter_hw(sd_unet* u, void* stream, const float* 
     return 0;
 }
 
+// ---- ControlNet (diffusers ControlNetModel, upstream-recall) ----
+extern "C" int sd_controlnet_create(const sd_unet_config* cfg, const int cond_embed_channels[4], sd_unet** out) {
+    SD_REQUIRE(cfg && cond_embed_channels && out, "sd_controlnet_create: null argument");
+    SD_REQUIRE(cfg->weight_dtype != SD_DTYPE_FP8_E4M3, "sd_controlnet_create: weight_dtype=\"fp8\" is not built for a ControlNet (bf16 is "
+               "the only path)");
+    if (check_unet_config(cfg, "sd_controlnet_create")) return -1;
+    SD_REQUIRE(cfg->in_channels == 4, "sd_controlnet_create: in_channels %d (4 is built)", cfg->in_channels);
+    SD_REQUIRE(cfg->ip_adapter_tokens == 0 && cfg->ip_adapter_embed_dim == 0, "sd_controlnet_create: a ControlNet takes no IP-Adapter");
+    SD_REQUIRE(cfg->block_out_channels[0] % 8 == 0, "sd_controlnet_create: block_out_channels[0]");
+    int nres = 1;
+    for (int i = 0; i < cfg->num_levels; ++i) nres += cfg->layers_per_block + (i < cfg->num_levels - 1 ? 1 : 0);
+    SD_REQUIRE(nres + 1 <= MAX_CONTROL_RES, "sd_controlnet_create: %d residuals (at most %d are built)", nres + 1, MAX_CONTROL_RES);
+    for (int i = 0; i < 4; ++i)
+        SD_REQUIRE(cond_embed_channels[i] > 0 && cond_embed_channels[i] % 8 == 0 && cond_embed_channels[i] <= 1024,
+                   "sd_controlnet_create: cond_embed_channels[%d]=%d (conditioning_embedding_out_channels: four positive multiples "
+                   "of 8)", i, cond_embed_channels[i]);
+    sd_unet* u = new_handle(5, cfg);
+    for (int i = 0; i < 4; ++i) u->cond_embed[i] = cond_embed_channels[i];
+    enumerate_params(u);
+    *out = u;
+    return 0;
+}
+
+extern "C" long long sd_controlnet_residual_bytes_hw(const sd_unet* u, int unet_batch, int latent_h, int latent_w) {
+    SD_REQUIRE(u && u->unet_like(), "controlnet_residual_bytes: not a UNet or ControlNet handle");
+    SD_REQUIRE(unet_batch > 0 && unet_batch <= 4096, "controlnet_residual_bytes: bad batch %d", unet_batch);
+    if (check_latent_size(u, latent_h, latent_w, "controlnet_residual_bytes")) return -1;
+    std::vector<size_t> off;
+    std::vector<long> count;
+    return (long long)control_segments(u->cfg, unet_batch, latent_h, latent_w, &off, &count);
+}
+
+extern "C" int sd_controlnet_set_cond_hw(sd_unet* u, void* stream, const float* cond_image, int batch, int latent_h, int latent_w) {
+    SD_REQUIRE(u && u->kind == 5, "controlnet_set_cond: not a ControlNet handle");
+    if (!cond_image) {
+        u->cn_b = 0;
+        return 0;
+    }
+    SD_REQUIRE(u->finalized, "controlnet_set_cond: parameters not finalized");
+    SD_REQUIRE(batch > 0 && batch <= 4096, "controlnet_set_cond: bad batch %d", batch);
+    SD_REQUIRE(((uintptr_t)cond_image & 15) == 0, "controlnet_set_cond: cond_image must be 16-byte aligned");
+    if (check_latent_size(u, latent_h, latent_w, "controlnet_set_cond")) return -1;
+    std::string names[8];
+    int cin[8], cout[8], stride[8];
+    cond_embed_convs(u, names, cin, cout, stride);
+    // scratch: the bf16 NHWC image, then two buffers the chain alternates between, each as large as its largest tensor
+    const int H = 8 * latent_h, W = 8 * latent_w, c0 = u->cfg.block_out_channels[0];
+    auto up256 = [](size_t b) { return (b + 255) / 256 * 256; };
+    size_t big = 0;
+    {
+        int h = H, w = W;
+        for (int i = 0; i < 7; ++i) {
+            h = (h + 2 - 3) / stride[i] + 1; w = (w + 2 - 3) / stride[i] + 1;
+            big = std::max(big, (size_t)batch * h * w * cout[i] * 2);
+        }
+        SD_REQUIRE(h == latent_h && w == latent_w, "controlnet_set_cond: the embedding of a %dx%d image is %dx%d, not the latent %dx%d", H,
+                   W, h, w, latent_h, latent_w);
+    }
+    const size_t img_bytes = up256((size_t)batch * H * W * 3 * 2), buf_bytes = up256(big);
+    const size_t need = img_bytes + 2 * buf_bytes, out_bytes = (size_t)batch * latent_h * latent_w * c0 * 2;
+    u->cn_b = 0;
+    if (need > u->cn_scratch_cap) {
+        if (u->cn_scratch) (void)hipFree(u->cn_scratch);     // (synchronises: no earlier launch still uses it)
+        u->cn_scratch = nullptr; u->cn_scratch_cap = 0;
+        SD_CHECK_HIP(hipMalloc((void**)&u->cn_scratch, need));
+        u->cn_scratch_cap = need;
+    }
+    if (out_bytes > u->cn_embed_cap) {
+        if (u->cn_embed) (void)hipFree(u->cn_embed);
+        u->cn_embed = nullptr; u->cn_embed_cap = 0;
+        SD_CHECK_HIP(hipMalloc((void**)&u->cn_embed, out_bytes));
+        u->cn_embed_cap = out_bytes;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    bf16_t* img = (bf16_t*)u->cn_scratch;
+    bf16_t* buf[2] = {(bf16_t*)(u->cn_scratch + img_bytes), (bf16_t*)(u->cn_scratch + img_bytes + buf_bytes)};
+    int rc = sd_launch_nchw_to_nhwc_bf16(cond_image, img, batch, 3, (long)H * W, st);
+    if (rc) return rc;
+    const bf16_t* x = img;
+    int h = H, w = W;
+    for (int i = 0; i < 8; ++i) {
+        bf16_t* y = i == 7 ? u->cn_embed : buf[i & 1];
+        rc = sd_launch_inception_conv(x, (const bf16_t*)(u->dweights + u->woff.at(names[i] + "weight")),
+                                      (const float*)(u->dweights + u->woff.at(names[i] + "bias")), y, batch, h, w, cin[i], cout[i], 3, 3,
+                                      stride[i], 1, 1, cout[i], 0, i == 7 ? 0 : 2 /* SiLU */, st);
+        if (rc) return rc;
+        h = (h + 2 - 3) / stride[i] + 1; w = (w + 2 - 3) / stride[i] + 1;
+        x = y;
+    }
+    u->cn_b = batch; u->cn_h = latent_h; u->cn_w = latent_w;
+    return 0;
+}
+
+extern "C" int sd_controlnet_forward_hw(sd_unet* u, void* stream, const float* latents, int latent_batch, int unet_batch, int latent_h,
+                                        int latent_w, float timestep, void* residuals, void* workspace, long long workspace_bytes) {
+    SD_REQUIRE(u && u->kind == 5, "controlnet_forward: not a ControlNet handle");
+    SD_REQUIRE(latents && residuals && workspace, "controlnet_forward: null argument");
+    SD_REQUIRE(((uintptr_t)residuals & 255) == 0, "controlnet_forward: the residual buffer must be 256-byte aligned");
+    if (check_latent_size(u, latent_h, latent_w, "controlnet_forward")) return -1;
+    SD_REQUIRE(latent_batch > 0 && unet_batch % latent_batch == 0, "controlnet_forward: unet batch %d not a multiple of latent batch %d",
+               unet_batch, latent_batch);
+    Plan* pl;
+    const int rep = plan_rep(u, latent_batch, unet_batch);
+    u->last_rep = rep; u->last_ip = 0; u->last_cn = 0;
+    u->last_h = latent_h; u->last_w = latent_w;
+    int rc = get_plan(u, unet_batch, -1, &pl, rep, latent_h, latent_w);
+    if (rc) return rc;
+    return run_plan(u, *pl, "controlnet_forward", workspace, workspace_bytes, latents, latent_batch, (float*)residuals, timestep, stream);
+}
+
+extern "C" int sd_unet_set_control_residuals_hw(sd_unet* u, const void* residuals, float scale, int unet_batch, int latent_h, int latent_w) {
+    SD_REQUIRE(u && u->kind == 0, "set_control_residuals: not a UNet handle");
+    if (!residuals) {
+        u->ctrl_res = nullptr;
+        return 0;
+    }
+    SD_REQUIRE(!u->fp8, "set_control_residuals: ControlNet residuals on an fp8 UNet handle are not built");
+    SD_REQUIRE(((uintptr_t)residuals & 255) == 0, "set_control_residuals: the residual buffer must be 256-byte aligned");
+    SD_REQUIRE(scale == scale && fabsf(scale) <= 1e4f, "set_control_residuals: scale %g", scale);
+    SD_REQUIRE(unet_batch > 0 && unet_batch <= 4096, "set_control_residuals: bad batch %d", unet_batch);
+    if (check_latent_size(u, latent_h, latent_w, "set_control_residuals")) return -1;
+    u->ctrl_enabled = true;
+    u->ctrl_res = (const char*)residuals; u->ctrl_scale = scale;
+    u->ctrl_ub = unet_batch; u->ctrl_h = latent_h; u->ctrl_w = latent_w;
+    return 0;
+}
+
+// a forward of a handle with ControlNet residuals set must be the one they were laid out for
+static int check_control_set(const sd_unet* u, const char* who, int unet_batch, int latent_h, int latent_w, int cache_mode, int branch) {
+    SD_REQUIRE(u->ctrl_ub == unet_batch && u->ctrl_h == latent_h && u->ctrl_w == latent_w,
+               "%s: the ControlNet residuals were set for batch %d at %dx%d, the forward runs batch %d at %dx%d "
+               "(sd_unet_set_control_residuals_hw; residuals = NULL clears them)", who, u->ctrl_ub, u->ctrl_h, u->ctrl_w, unet_batch,
+               latent_h, latent_w);
+    SD_REQUIRE(cache_mode == SD_CACHE_OFF && branch < 0, "%s: ControlNet residuals with DeepCache are not built", who);
+    return 0;
+}
+
 extern "C" int sd_unet_forward(sd_unet* u, void* stream, const float* latents, int latent_batch, int unet_batch,
                                float timestep, float* eps_out, void* workspace, long long workspace_bytes,
                                int cache_mode, int cache_branch_id) {
@@ -787,9 +953,11 @@ extern "C" int sd_unet_forward_hw(sd_unet* u, void* stream, const float* latents
     const int rep = plan_rep(u, latent_batch, unet_batch);
     const int ip = u->ip_keys.empty() ? 0 : 1;
     if (ip && check_ip_set(u, "forward", unet_batch, cache_branch_id, latent_h, latent_w)) return -1;
-    u->last_rep = rep; u->last_ip = ip;
+    const int cn = u->ctrl_res ? 1 : 0;
+    if (cn && check_control_set(u, "forward", unet_batch, latent_h, latent_w, cache_mode, cache_branch_id)) return -1;
+    u->last_rep = rep; u->last_ip = ip; u->last_cn = cn;
     u->last_h = latent_h; u->last_w = latent_w;
-    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, latent_h, latent_w, ip);
+    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, latent_h, latent_w, ip, cn);
     if (rc) return rc;
     return run_plan(u, *pl, "forward", workspace, workspace_bytes, latents, latent_batch, eps_out, timestep, stream, cache_mode);
 }
@@ -923,6 +1091,9 @@ static void op_work(const Op& o, double* flops, double* bytes) {
         case OP_REPLICATE:
             *bytes = 16.0 * o.M * (1.0 + o.N);
             break;
+        case OP_RES_ADD:    // x and r in, x out
+            *bytes = 3.0 * 2.0 * (double)o.M;      // (M: the elements of all segments)
+            break;
         case OP_IP_XATTN:   // scores and P B over the 32 image-key slots; R in, R' out
             *flops = 4.0 * o.M * 32.0 * o.N;
             *bytes = 2.0 * 2.0 * o.M * o.N;
@@ -944,9 +1115,11 @@ static int profiled_run(sd_unet* u, void* stream, const float* latents, int late
     const int rep = plan_rep(u, latent_batch, unet_batch);
     const int ip = u->ip_keys.empty() ? 0 : 1;
     if (ip && check_ip_set(u, "forward_profiled", unet_batch, cache_branch_id, u->cfg.sample_size, u->cfg.sample_size)) return -1;
-    u->last_rep = rep; u->last_ip = ip;
+    const int cn = u->ctrl_res ? 1 : 0;
+    if (cn && check_control_set(u, "forward_profiled", unet_batch, u->cfg.sample_size, u->cfg.sample_size, cache_mode, cache_branch_id)) return -1;
+    u->last_rep = rep; u->last_ip = ip; u->last_cn = cn;
     u->last_h = u->last_w = u->cfg.sample_size;
-    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, -1, -1, ip);
+    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, -1, -1, ip, cn);
     if (rc) return rc;
     *plan = pl;
     SD_REQUIRE((long long)pl->total_bytes <= workspace_bytes, "forward_profiled: workspace too small");
@@ -1005,7 +1178,7 @@ extern "C" int sd_unet_forward_profiled(sd_unet* u, void* stream, const float* l
             a.w_batch_stride = (long)o.N * 4 * o.Cin;
             halo4 = sd_conv_halo_subpix_applicable(a);
         }
-        const int kd = o.kind == OP_XATTN ? 18 : o.kind == OP_REPLICATE ? 19 : o.kind == OP_IP_XATTN ? 22 : halo4 ? 21 :
+        const int kd = o.kind == OP_XATTN ? 18 : o.kind == OP_REPLICATE ? 19 : o.kind == OP_IP_XATTN ? 22 : o.kind == OP_RES_ADD ? 23 : halo4 ? 21 :
                        (o.kind == OP_CONV3 && !o.dt && (o.subpix || o.stride != 1)) ? 20 :
                        (o.dt ? (o.kind == OP_CONV3 ? 16 : 17) : o.kind);
         kind_ms[kd] += ms; kind_launches[kd] += 1; kind_flops[kd] += fl; kind_bytes[kd] += by;
@@ -1041,8 +1214,21 @@ extern "C" long long sd_unet_forward_op_times(sd_unet* u, void* stream, const fl
 extern "C" int sd_unet_debug_tensor(sd_unet* u, void* stream, const char* name, float* host_out, long long numel,
                                     void* workspace, int unet_batch, int cache_branch_id) {
     SD_REQUIRE(u && u->debug_taps, "debug_tensor: create the handle with SD_DEBUG_TAPS=1 in the environment");
+    if (u->kind == 5 && name && !strcmp(name, "cond_embedding")) {      // the stored conditioning embedding [cn_b][h w][c0]
+        SD_REQUIRE(u->cn_b > 0, "debug_tensor: no conditioning image is set");
+        const size_t have = (size_t)u->cn_b * u->cn_h * u->cn_w * u->cfg.block_out_channels[0];
+        SD_REQUIRE(numel >= 0 && (size_t)numel <= have, "debug_tensor: 'cond_embedding' holds %zu elements", have);
+        std::vector<unsigned short> tmp(numel);
+        SD_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+        SD_CHECK_HIP(hipMemcpy(tmp.data(), u->cn_embed, (size_t)numel * 2, hipMemcpyDeviceToHost));
+        for (long long i = 0; i < numel; ++i) {
+            unsigned v = (unsigned)tmp[i] << 16;
+            memcpy(&host_out[i], &v, 4);
+        }
+        return 0;
+    }
     Plan* pl;
-    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, u->last_rep, u->last_h > 0 ? u->last_h : -1, u->last_w > 0 ? u->last_w : -1, u->last_ip);
+    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, u->last_rep, u->last_h > 0 ? u->last_h : -1, u->last_w > 0 ? u->last_w : -1, u->last_ip, u->last_cn);
     if (rc) return rc;
     auto it = pl->taps.find(name);
     SD_REQUIRE(it != pl->taps.end(), "debug_tensor: unknown tap '%s'", name);

@@ -74,6 +74,8 @@ class BaseMethod(ABC):
             torch_dtype=torch.float16,
             **extra,
         )
+        if self.config.model.get("controlnet", None) is not None:      # key of this build: a local ControlNet directory or a hub name
+            self.model.load_controlnet(str(self.config.model.controlnet))
         self.model.to(self.device)
 
     def setup_scheduler(self, **kwargs):
@@ -101,6 +103,21 @@ class BaseMethod(ABC):
                                         f"dataset.img_dataset = {str(self.config.dataset.img_dataset)!r} does not exist")
             if self.img2img_strength is None:
                 self.img2img_strength = 1.0
+
+        # optional experiment_params.control_from_dataset: true (key of this build): every prompt's own file is the control
+        # image of its sample (model.controlnet), at experiment_params.controlnet_conditioning_scale (default 1.0)
+        ep = self.config.get("experiment_params", {})
+        self.control_from_dataset = bool(ep.get("control_from_dataset", False))
+        self.controlnet_conditioning_scale = float(ep.get("controlnet_conditioning_scale", 1.0))
+        if self.control_from_dataset:
+            if self.config.model.get("controlnet", None) is None:
+                raise ValueError("experiment_params.control_from_dataset is set but model.controlnet names no ControlNet")
+            if self.inpaint_box is not None:
+                raise NotImplementedError("experiment_params.control_from_dataset with inpaint_box (a ControlNet with inpainting) "
+                                          "is not built")
+            if not os.path.isdir(str(self.config.dataset.img_dataset)):
+                raise FileNotFoundError(f"experiment_params.control_from_dataset is set but the image directory "
+                                        f"dataset.img_dataset = {str(self.config.dataset.img_dataset)!r} does not exist")
 
     @staticmethod
     def parse_inpaint_box(box, image_size: int):
@@ -189,6 +206,12 @@ class BaseMethod(ABC):
             if sharded and (call_kwargs.get("ip_adapter_image") is not None or call_kwargs.get("ip_adapter_image_embeds") is not None):
                 # an IP-Adapter image prompt given per prompt is sliced with the prompts, as image= is below
                 call_kwargs = self.model.shard_ip_adapter_args(call_kwargs, lo, hi, len(prompts))
+            if sharded and call_kwargs.get("control_image") is not None:
+                call_kwargs = self.model.shard_control_args(call_kwargs, lo, hi, len(prompts))
+            if getattr(self, "control_from_dataset", False) and len(local_prompts) > 0:
+                # ControlNet: this rank's slice of the batch's files as control images, like the start images below
+                call_kwargs = {**call_kwargs, "control_image": self.load_images(list(batch["image_file"])[lo:hi]),
+                               "controlnet_conditioning_scale": self.controlnet_conditioning_scale}
             if getattr(self, "img2img_strength", None) is not None and len(local_prompts) > 0:
                 # image-to-image: this rank's slice of the batch's start images rides with its slice of the prompts
                 call_kwargs = {**call_kwargs, "image": self.load_images(list(batch["image_file"])[lo:hi]),

@@ -149,6 +149,15 @@ class StableDiffusionModel:
         self._ip_encoder_dir = None
         self._ip_encoder = None
         self._ip_pending = None
+        # ControlNet (load_controlnet): its config and weights (or the seed of a hub name's stand-in) until the handle is
+        # built, the handle, the checked arguments of the call in progress and what its loop runs with
+        self._cn_cfg = None
+        self._cn_sd = None
+        self._cn_seed = None
+        self._cn_source = None
+        self.controlnet = None
+        self._cn_run = None
+        self.control_image = None       # the control image of the last conditioned call, at the call's size
 
     # -- loading ---------------------------------------------------------------------------
     @classmethod
@@ -492,6 +501,159 @@ class StableDiffusionModel:
         self.ip_adapter_image_embeds = emb
         self.unet.set_ip_adapter(emb.contiguous(), self._ip_scale, *self.latent_size)
 
+    # -- ControlNet (diffusers StableDiffusionControlNetPipeline, upstream-recall) ---------------------------
+    def load_controlnet(self, pretrained_model_name_or_path):
+        """ONE ControlNet beside the UNet, before or after the model moves to the GPU.  A local directory in the upstream
+        layout (``config.json`` and ``diffusion_pytorch_model.safetensors`` / ``.bin``) is read for real and must pair with the
+        UNet (``weights.read_controlnet_config``); a hub NAME is a network fetch, for which a seeded ControlNet of
+        the UNet's shape with NON-zero zero convs stands in (``weights_source`` says so)."""
+        from .weights import controlnet_config_for, load_controlnet
+        src = pretrained_model_name_or_path
+        if isinstance(src, (list, tuple)):
+            raise NotImplementedError("load_controlnet: a list of ControlNets (Multi-ControlNet) is not built")
+        if self._cn_cfg is not None:
+            raise NotImplementedError("load_controlnet: a ControlNet is already loaded (several at once are not built; "
+                                      "unload_controlnet first)")
+        path = str(src)
+        if os.path.isdir(path):
+            self._cn_cfg, self._cn_sd = load_controlnet(path, self.unet_config)
+            self._cn_source = f" + ControlNet(local:{path})"
+        elif not self._looks_like_hub_name(path):
+            raise FileNotFoundError(f"load_controlnet: no ControlNet directory at {path!r}")
+        else:
+            self._cn_seed = int.from_bytes(hashlib.sha256(path.encode()).digest()[:4], "little")
+            self._cn_cfg = controlnet_config_for(self.unet_config)
+            self._cn_source = f" + SYNTHETIC stand-in for the hub ControlNet {path} (seed={self._cn_seed})"
+        self.weights_source += self._cn_source
+
+    def unload_controlnet(self):
+        """Calls run without a ControlNet again (``control_image`` is refused); the handle and its memory are dropped."""
+        src = self._cn_source
+        if src:
+            self.weights_source = self.weights_source.replace(src, "", 1)
+        self._cn_cfg = self._cn_sd = self._cn_seed = self._cn_source = None
+        self.controlnet = None
+        self._cn_run = None
+        if self.unet is not None:
+            self.unet.clear_control_residuals()
+
+    def _ensure_controlnet(self):
+        if self.controlnet is None:
+            from .controlnet import HipControlNetModel
+            from .weights import make_synthetic_controlnet_state_dict
+            sd = self._cn_sd if self._cn_sd is not None else make_synthetic_controlnet_state_dict(self._cn_cfg, self._cn_seed)
+            self.controlnet = HipControlNetModel(self._cn_cfg, sd, device=str(self.unet.device))
+            self._cn_sd = None
+        return self.controlnet
+
+    CONTROL_WINDOW_RULE = "0 <= control_guidance_start < control_guidance_end <= 1"
+
+    def _control_args(self, control_image, controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
+                      guess_mode, mask_image, n_prompt: int):
+        """Every check of the ControlNet arguments of a call, on the host, before any GPU work.  Returns None (no control
+        image) or dict(image [Bc,3,H,W] fp32 in [0,1] on the host, pil, scale, start, end)."""
+        if guess_mode:
+            raise NotImplementedError("guess_mode is not built")
+        if control_image is None:
+            return None
+        if self._cn_cfg is None:
+            raise ValueError("control_image needs a loaded ControlNet (load_controlnet)")
+        for name, v in (("controlnet_conditioning_scale", controlnet_conditioning_scale),
+                        ("control_guidance_start", control_guidance_start), ("control_guidance_end", control_guidance_end)):
+            if isinstance(v, (list, tuple)):
+                raise NotImplementedError(f"{name}: a list (Multi-ControlNet) is not built; one number")
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(float(v)):
+                raise ValueError(f"{name}={v!r} must be a finite number")
+        if not 0.0 <= float(control_guidance_start) < float(control_guidance_end) <= 1.0:
+            raise ValueError(f"control_guidance_start={control_guidance_start}, control_guidance_end={control_guidance_end}: "
+                             f"{self.CONTROL_WINDOW_RULE}")
+        if mask_image is not None:
+            raise NotImplementedError("control_image with mask_image (a ControlNet with inpainting) is not built")
+        if self._deepcache is not None:
+            raise NotImplementedError("control_image with DeepCache is not built (disable the DeepCache helper)")
+        if _lib_dtype_is_fp8(self.weight_dtype):
+            raise NotImplementedError("control_image with an fp8 UNet handle is not built (weight_dtype='bf16')")
+        img, pil = control_image, False
+        if hasattr(img, "convert"):
+            img = [img]
+        if isinstance(img, (list, tuple)):
+            if len(img) == 0 or not all(hasattr(im, "convert") for im in img):
+                raise NotImplementedError("control_image: a list of tensors or of lists (Multi-ControlNet) is not built; one "
+                                          "[B,3,H,W] tensor or a list of PIL images of one size")
+            img, pil = self._image_tensor(list(img)), True
+        if not torch.is_tensor(img) or img.dim() != 4 or img.shape[1] != 3 or not img.is_floating_point():
+            raise ValueError("control_image must be a float tensor [B,3,H,W] in [0,1] or a list of PIL images of one size")
+        if n_prompt is not None and img.shape[0] not in (1, n_prompt):
+            raise ValueError(f"control_image batch {img.shape[0]} does not match the prompt batch {n_prompt}")
+        return dict(image=img.detach().to("cpu", torch.float32), pil=pil, scale=float(controlnet_conditioning_scale),
+                    start=float(control_guidance_start), end=float(control_guidance_end))
+
+    @staticmethod
+    def resize_control_image(img: torch.Tensor, height: int, width: int, pil: bool = False) -> torch.Tensor:
+        """The control image at the call's size, as VaeImageProcessor.preprocess(image, height, width) resizes it upstream
+        (``do_normalize=False``): PIL images with Lanczos, tensors with ``F.interpolate``'s default (nearest).  Already at
+        that size: as it is."""
+        if tuple(img.shape[2:]) == (height, width):
+            return img
+        if pil:
+            import numpy as np
+            from PIL import Image
+            out = []
+            for im in img:
+                a = (im.permute(1, 2, 0).clamp(0, 1) * 255.0).round().to(torch.uint8).numpy()
+                r = Image.fromarray(a).resize((width, height), resample=Image.LANCZOS)
+                out.append(torch.from_numpy(np.asarray(r, dtype=np.float32) / 255.0).permute(2, 0, 1))
+            return torch.stack(out)
+        return torch.nn.functional.interpolate(img, size=(height, width))
+
+    @staticmethod
+    def shard_control_args(kwargs: dict, lo: int, hi: int, n: int) -> dict:
+        """A sharded harness call: the rows [lo, hi) of ``control_image`` ride with this rank's prompts, as
+        ``shard_ip_adapter_args`` slices the image prompt.  A batch of 1 is broadcast and stays."""
+        out = dict(kwargs)
+        v = out.get("control_image")
+        if torch.is_tensor(v) and v.shape[0] == n and n > 1:
+            out["control_image"] = v[lo:hi]
+        elif isinstance(v, (list, tuple)) and len(v) == n and n > 1:
+            out["control_image"] = list(v[lo:hi])
+        return out
+
+    def _apply_controlnet(self, ctx, cn):
+        """After ``set_context`` of a call: the ControlNet's prompt and conditioning embedding (once per call) from the checked
+        arguments ``cn`` (``_control_args``), or the plain plans if the call has no control image."""
+        self._cn_run = None
+        self.unet.clear_control_residuals()
+        if cn is None or cn["scale"] == 0.0:
+            return                           # (scale 0: neither the ControlNet nor the variant runs; the plain call, bit for bit)
+        net = self._ensure_controlnet()
+        h, w = self.latent_size
+        img = self.resize_control_image(cn["image"], self._size[0], self._size[1], cn["pil"])
+        self.control_image = img
+        net.set_context(ctx, h, w)
+        net.set_cond(img)                    # [1 or B, 3, H, W]: read modulo its batch, so both CFG halves see it
+        self._cn_run = dict(scale=cn["scale"], start=cn["start"], end=cn["end"], keep=None)
+
+    def _control_step(self, i: int, n_steps: int, latents, unet_batch: int, t) -> None:
+        """Before the UNet forward of step ``i`` of ``n_steps``: run the ControlNet and hand its residuals to the UNet at
+        ``controlnet_conditioning_scale * keep_i``; a step whose scale is 0 runs the plain plan."""
+        run = self._cn_run
+        if run is None:
+            return
+        if run["keep"] is None or len(run["keep"]) != n_steps:
+            from .weights import control_keep
+            run["keep"] = control_keep(n_steps, run["start"], run["end"])
+        s = run["scale"] * run["keep"][i]
+        if s == 0.0:
+            self.unet.clear_control_residuals()
+            return
+        buf = self.controlnet.forward_residuals(latents, unet_batch, float(t))
+        self.unet.set_control_residuals(buf, s, unet_batch, *self.latent_size)
+
+    def _control_end(self) -> None:
+        if self._cn_run is not None:
+            self.unet.clear_control_residuals()
+            self._cn_run = None
+
     # -- properties the harness reads --------------------------------------------------------
     @property
     def num_timesteps(self):
@@ -596,13 +758,14 @@ class StableDiffusionModel:
         """(h, w) of the latent of the current call (``_begin`` fixed the pixel size)."""
         return self._size[0] // self.vae_scale_factor, self._size[1] // self.vae_scale_factor
 
-    def _start_loop(self, batch_size, device, generator, latents, ctx, cache_branch_id):
+    def _start_loop(self, batch_size, device, generator, latents, ctx, cache_branch_id, control=None):
         """Initial latents at the call's size, DeepCache branch and prompt context of the UNet."""
         c = self.unet_config
         latents = self.prepare_latents(batch_size, LATENT_CHANNELS, self._size[0], self._size[1], device, generator, latents)
         self.unet.set_deepcache(cache_branch_id)
         self.unet.set_context(ctx, *self.latent_size)
         self._apply_ip_adapter(ctx.shape[0] == 2 * batch_size and self.do_classifier_free_guidance)
+        self._apply_controlnet(ctx, control)
         return latents
 
     def _eps_buffer(self, unet_batch, device):
@@ -756,7 +919,7 @@ class StableDiffusionModel:
     def _call_img2img(self, prompt, image, strength, sample_mode, height, width, num_inference_steps, timesteps, sigmas,
                       guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents, prompt_embeds,
                       negative_prompt_embeds, output_type, return_dict, guidance_rescale, step_noise, collect_x0,
-                      ip_args=(None, None)):
+                      ip_args=(None, None), control=None):
         """The loop of ``call`` started part-way down the schedule from a noised encoding of ``image`` (SDEdit).  The
         schedule is the full ``num_inference_steps`` one; the last ``N - t_start`` of its timesteps run.  A multistep
         scheduler starts with a fresh history at that index (``_index_of`` resolves it from the timestep) while its
@@ -774,7 +937,7 @@ class StableDiffusionModel:
         # encoding and noising sit outside the timed region, as text encoding does
         start, _ = self._img2img_start(img, sample_mode, generator, device, ts_host[0])
         self.img2img_start_latents = start
-        latents = self._start_loop(batch_size, device, None, start, ctx, dc.cache_branch_id if dc is not None else -1)
+        latents = self._start_loop(batch_size, device, None, start, ctx, dc.cache_branch_id if dc is not None else -1, control)
         eps = self._eps_buffer(unet_batch, device)
         self._num_timesteps = len(ts_host)
         x0_preds = []
@@ -786,6 +949,7 @@ class StableDiffusionModel:
             mode = CACHE_OFF
             if dc is not None:
                 mode = CACHE_FULL_AND_STORE if ts_host.index(t) % dc.cache_interval == 0 else CACHE_SKIP
+            self._control_step(i, len(ts_host), latents, unet_batch, t)
             self.unet.forward_latents(latents, unet_batch, float(t), out=eps, cache_mode=mode)
             kw = {}
             if is_lcm and step_noise is not None and i < len(ts_host) - 1:
@@ -796,6 +960,7 @@ class StableDiffusionModel:
             latents, x0 = step[0], step[1]
             if collect_x0:
                 x0_preds.append(x0[0:1])
+        self._control_end()
         torch.cuda.synchronize(device)
         execution_time = time.time() - start_time
         return self._finish(latents, x0_preds, output_type, return_dict, execution_time)
@@ -938,8 +1103,16 @@ class StableDiffusionModel:
              negative_prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil",
              return_dict: bool = True, guidance_rescale: float = 0.0, step_noise: Optional[torch.Tensor] = None,
              collect_x0: bool = True, image=None, strength=STRENGTH_UNSET, sample_mode: str = "sample", mask_image=None,
-             padding_mask_crop=None, ip_adapter_image=None, ip_adapter_image_embeds=None, **kwargs):
-        """``ip_adapter_image`` (PIL images or uint8 / float [B,3,H,W]) or ``ip_adapter_image_embeds`` ([B, E], [B, 1, E] or
+             padding_mask_crop=None, ip_adapter_image=None, ip_adapter_image_embeds=None, control_image=None,
+             controlnet_conditioning_scale=1.0, control_guidance_start=0.0, control_guidance_end=1.0, guess_mode=False,
+             **kwargs):
+        """``control_image`` ([B,3,H,W] floats in [0,1], rgb, or a list of PIL images of one size; resized to the call's size
+        as upstream resizes it, replicated over the batch, seen by both CFG halves): the structure condition of a loaded
+        ControlNet (``load_controlnet``) for text-to-image and image-to-image.  Step i of N runs the ControlNet at
+        ``controlnet_conditioning_scale * keep_i``, ``keep_i = 1 - float(i / N < control_guidance_start or (i + 1) / N >
+        control_guidance_end)``; a step whose scale is 0 runs the plain UNet plan, bit for bit.
+
+        ``ip_adapter_image`` (PIL images or uint8 / float [B,3,H,W]) or ``ip_adapter_image_embeds`` ([B, E], [B, 1, E] or
         [2 B, ...] negative first under CFG; a tensor or a one-element list): the image prompt of a loaded IP-Adapter
         (``load_ip_adapter``), for every kind of call below.
 
@@ -953,6 +1126,10 @@ class StableDiffusionModel:
         if padding_mask_crop is not None:
             raise NotImplementedError("padding_mask_crop is not built (the crop-and-paste of StableDiffusionInpaintPipeline; "
                                       "without it upstream composites nothing in pixel space, and neither does this)")
+        n_prompt = 1 if isinstance(prompt, str) else len(prompt) if prompt is not None else \
+            int(prompt_embeds.shape[0]) if prompt_embeds is not None else None      # (None: _begin refuses the call by name)
+        control = self._control_args(control_image, controlnet_conditioning_scale, control_guidance_start,
+                                     control_guidance_end, guess_mode, mask_image, n_prompt)
         if mask_image is not None:
             if image is None:
                 raise ValueError("mask_image without image: inpainting needs the image the mask refers to")
@@ -971,7 +1148,7 @@ class StableDiffusionModel:
             return self._call_img2img(prompt, image, strength, sample_mode, height, width, num_inference_steps, timesteps,
                                       sigmas, guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents,
                                       prompt_embeds, negative_prompt_embeds, output_type, return_dict, guidance_rescale,
-                                      step_noise, collect_x0, (ip_adapter_image, ip_adapter_image_embeds))
+                                      step_noise, collect_x0, (ip_adapter_image, ip_adapter_image_embeds), control)
         device, batch_size, do_cfg, ctx = self._begin(prompt, height, width, guidance_scale, negative_prompt,
                                                       num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
                                                       guidance_rescale, timesteps, sigmas, ip_adapter_image, ip_adapter_image_embeds)
@@ -981,7 +1158,8 @@ class StableDiffusionModel:
         self.scheduler.set_timesteps(num_inference_steps, device=device)                        # :167-169
         ts_host = list(self.scheduler._timesteps_list)
         dc = self._deepcache
-        latents = self._start_loop(batch_size, device, generator, latents, ctx, dc.cache_branch_id if dc is not None else -1)
+        latents = self._start_loop(batch_size, device, generator, latents, ctx, dc.cache_branch_id if dc is not None else -1,
+                                   control)
         eps = self._eps_buffer(unet_batch, device)
         self._num_timesteps = len(ts_host)
         x0_preds = []
@@ -995,6 +1173,7 @@ class StableDiffusionModel:
                 # DeepCache: index of t in scheduler.timesteps, first step always full (A.5)
                 cur = ts_host.index(t)      # first match, as DeepCache's list.index (duplicate PNDM timestep quirk)
                 mode = CACHE_FULL_AND_STORE if (cur - 0) % dc.cache_interval == 0 else CACHE_SKIP
+            self._control_step(i, len(ts_host), latents, unet_batch, t)
             self.unet.forward_latents(latents, unet_batch, float(t), out=eps, cache_mode=mode)     # :217-235
             kw = {}
             if is_lcm and step_noise is not None and i < len(ts_host) - 1:
@@ -1009,6 +1188,7 @@ class StableDiffusionModel:
                 latents, x0 = step[0], step[1]
                 if collect_x0:
                     x0_preds.append(x0[0:1])
+        self._control_end()
         torch.cuda.synchronize(device)
         execution_time = time.time() - start_time                                                 # :284-285
         return self._finish(latents, x0_preds, output_type, return_dict, execution_time)
@@ -1017,6 +1197,11 @@ class StableDiffusionModel:
 # --------------------------------------------------------------------------------------------------
 # Variant pipelines: host-only control flow over the same kernels.
 # --------------------------------------------------------------------------------------------------
+def _lib_dtype_is_fp8(weight_dtype) -> bool:
+    from ._lib import DTYPE_FP8_E4M3, DTYPES
+    return DTYPES.get(weight_dtype) == DTYPE_FP8_E4M3
+
+
 def _is_dpm(s) -> bool:
     return hasattr(s, "model_outputs") and hasattr(s, "convert_model_output")
 
@@ -1047,6 +1232,9 @@ class _VariantBase(StableDiffusionModel):
         return step[0]
 
     def _refuse_image(self, kwargs):
+        if kwargs.get("control_image") is not None or kwargs.get("guess_mode"):
+            raise NotImplementedError(f"control_image= (ControlNet) is not built for {type(self).__name__}; "
+                                      "StableDiffusionModel runs it")
         if kwargs.get("mask_image") is not None:
             raise NotImplementedError(f"mask_image= (inpainting) is not built for {type(self).__name__}; "
                                       "StableDiffusionModel runs it")

@@ -88,6 +88,8 @@ class HipUNet2DConditionModel:
         self._ip_call = None
         self._ip_keepalive = None
         self.ip_adapter_scale = 1.0         # scale __call__(added_cond_kwargs=...) applies (diffusers: set_ip_adapter_scale)
+        # ControlNet residuals on the handle: (buffer kept alive, scale, unet batch, h, w) or None (the plain plans)
+        self._control = None
         self.cache_branch_id = -1
 
     def __del__(self):
@@ -233,6 +235,53 @@ class HipUNet2DConditionModel:
         self._ip_on = False
         self._ip_keepalive = None
 
+    # -- ControlNet residuals ---------------------------------------------------------------------
+    def set_control_residuals(self, residuals: torch.Tensor, scale: float, unet_batch: int, height: Optional[int] = None,
+                              width: Optional[int] = None) -> None:
+        """``residuals``: the buffer ``HipControlNetModel.forward_residuals`` fills (bf16, channel-last, thirteen segments;
+        ``controlnet.residual_layout``) for forwards of ``unet_batch`` at latent ``height`` x ``width``.  Every later forward
+        adds ``scale`` times the residuals to its twelve skip tensors and its mid block's output, in one launch after the mid
+        block, until ``clear_control_residuals``.  The buffer is borrowed: the ControlNet may refill it before every step."""
+        from .controlnet import residual_layout
+        if self.weight_dtype != "bf16":
+            raise NotImplementedError("ControlNet residuals on an fp8 UNet handle are not built")
+        if self.cache_branch_id != -1:
+            raise NotImplementedError("ControlNet residuals with DeepCache are not built")
+        h, w = self.latent_size(height, width)
+        need = residual_layout(self.config, unet_batch, h, w)[1]
+        if not torch.is_tensor(residuals) or residuals.dtype != torch.uint8 or residuals.device != self.device or \
+                residuals.numel() < need or residuals.data_ptr() % 256:
+            raise ValueError(f"residuals must be a 256-byte aligned uint8 device tensor of at least {need} bytes "
+                             "(controlnet.new_residual_buffer)")
+        _lib.check(self._lib.sd_unet_set_control_residuals_hw(self._handle, residuals.data_ptr(), float(scale), unet_batch, h, w),
+                   "sd_unet_set_control_residuals_hw")
+        self._control = (residuals, float(scale), unet_batch, h, w)
+        self._grow_workspace_for_control()
+
+    def _grow_workspace_for_control(self) -> None:
+        """The handle sizes the control plan variants only once residuals were set on it: if the live workspace is smaller
+        than they need, move it into a larger one.  The context tensors (prompt, image prompt) lie at the same offsets in
+        every variant, at the front of the workspace, so the copy keeps them."""
+        if self._ws is None:
+            return
+        ub, branch, h, w = self._ws_key
+        n = self._lib.sd_unet_workspace_bytes_hw(self._handle, ub, branch, h, w)
+        if n < 0:
+            _lib.check(-1, "sd_unet_workspace_bytes_hw")
+        have = self._ws.numel() - 256
+        if n > have:
+            old, off = self._ws, self._ws_ptr(self._ws) - self._ws.data_ptr()
+            new = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+            noff = (-new.data_ptr()) % 256
+            new[noff:noff + have].copy_(old[off:off + have])
+            self._ws = new
+
+    def clear_control_residuals(self) -> None:
+        """Forwards are again those of a UNet that never saw a ControlNet, bit for bit."""
+        if self._control is not None:
+            _lib.check(self._lib.sd_unet_set_control_residuals_hw(self._handle, None, 0.0, 0, 0, 0), "sd_unet_set_control_residuals_hw")
+            self._control = None
+
     # -- forward ---------------------------------------------------------------------------
     def forward_latents(self, latents: torch.Tensor, unet_batch: int, timestep: float,
                         out: Optional[torch.Tensor] = None, cache_mode: int = CACHE_OFF) -> torch.Tensor:
@@ -251,6 +300,9 @@ class HipUNet2DConditionModel:
         if self._ip_on and (unet_batch, self.cache_branch_id, h, w) not in self._ip_keys:
             raise _lib.SdHipError(f"this UNet runs with an IP-Adapter image prompt: set_ip_adapter(image_embeds, scale, {h}, {w}) must "
                                   f"be called for this batch ({unet_batch}) and size after set_context (or clear_ip_adapter())")
+        if self._control is not None and self._control[2:] != (unet_batch, h, w):
+            raise _lib.SdHipError(f"the ControlNet residuals were set for batch {self._control[2]} at {self._control[3]}x{self._control[4]}: "
+                                  f"set_control_residuals for this batch ({unet_batch}) and size ({h}x{w}), or clear_control_residuals()")
         if latents.dtype != torch.float32 or not latents.is_contiguous() or latents.device != self.device:
             latents = latents.to(self.device, torch.float32).contiguous()
         if out is None:
@@ -306,7 +358,7 @@ class HipUNet2DConditionModel:
 
     KIND_NAMES = {0: "sinusoid", 1: "gemv", 2: "conv_in", 3: "groupnorm", 4: "conv3x3", 5: "gemm", 6: "layernorm",
                   7: "attention", 8: "conv_out", 16: "conv3x3_fp8", 17: "gemm_fp8", 18: "xattn_fused",
-                  19: "replicate", 20: "conv3x3_gemm", 21: "conv3x3_halo_subpix", 22: "ip_xattn"}
+                  19: "replicate", 20: "conv3x3_gemm", 21: "conv3x3_halo_subpix", 22: "ip_xattn", 23: "residual_add"}
 
     def forward_profiled(self, latents: torch.Tensor, unet_batch: int, timestep: float, cache_mode: int = CACHE_OFF):
         """One forward with a hipEvent pair around every launch (measurement only, synchronises).
@@ -329,9 +381,17 @@ class HipUNet2DConditionModel:
 
     def __call__(self, sample: torch.Tensor, timestep, encoder_hidden_states: torch.Tensor = None,
                  timestep_cond=None, cross_attention_kwargs=None, added_cond_kwargs=None, return_dict: bool = False,
-                 **kwargs):
+                 down_block_additional_residuals=None, mid_block_additional_residual=None, **kwargs):
         """diffusers-style call of the reference loop (``src/models.py:227-235``).  ``timestep_cond`` ([B, d] or [d]) is
-        the guidance embedding of an LCM-distilled UNet: one row for the whole batch (ONE_ROW_RULE); None runs without it."""
+        the guidance embedding of an LCM-distilled UNet: one row for the whole batch (ONE_ROW_RULE); None runs without it.
+        ``down_block_additional_residuals`` (twelve NCHW float tensors, already scaled) and
+        ``mid_block_additional_residual``: a ControlNet's outputs as diffusers passes them; they are converted to the
+        residual buffer (one bf16 rounding), added at scale 1 for this call and cleared after it.  Without them the call
+        leaves the handle as it is: residuals set through ``set_control_residuals`` stay in force until
+        ``clear_control_residuals``."""
+        if (down_block_additional_residuals is None) != (mid_block_additional_residual is None):
+            raise NotImplementedError("down_block_additional_residuals and mid_block_additional_residual go together (a ControlNet's "
+                                      "outputs; a T2I-Adapter's down residuals alone are not built)")
         emb = None
         if added_cond_kwargs is not None:
             if self.config.ip_adapter_embed_dim is None:
@@ -354,7 +414,16 @@ class HipUNet2DConditionModel:
                 self.set_ip_adapter(emb, self.ip_adapter_scale, h, w)
                 self._ip_call = ip_call
         t = float(timestep.item()) if torch.is_tensor(timestep) else float(timestep)
-        eps = self.forward_latents(sample, sample.shape[0], t)
+        if down_block_additional_residuals is not None:
+            from .controlnet import pack_residuals
+            buf = pack_residuals(down_block_additional_residuals, mid_block_additional_residual, self.config, self.device)
+            self.set_control_residuals(buf, 1.0, sample.shape[0], h, w)
+            try:
+                eps = self.forward_latents(sample, sample.shape[0], t)
+            finally:
+                self.clear_control_residuals()
+        else:
+            eps = self.forward_latents(sample, sample.shape[0], t)      # (residuals set with set_control_residuals stay in force)
         return (eps.to(sample.dtype),)
 
     def _call_image_embeds(self, image_embeds, batch: int) -> torch.Tensor:

@@ -274,6 +274,166 @@ def load_ip_adapter_state_dict(path: str, cfg: UNetConfig):
     return map_ip_adapter_state_dict(groups, cfg)
 
 
+# ---- ControlNet (diffusers ControlNetModel) ----------------------------------------------------------------
+CONTROLNET_EMBED_CHANNELS = (16, 32, 96, 256)        # conditioning_embedding_out_channels of the published SD-1.5 ControlNets
+CONTROLNET_SHARED_FIELDS = ("block_out_channels", "layers_per_block", "attn_levels", "cross_attention_dim", "num_heads",
+                            "norm_num_groups", "norm_eps", "context_len")
+CONTROLNET_SEED_OFFSET = 15485863
+CONTROLNET_SYNTHETIC_GAIN = 0.5                      # make_synthetic_controlnet_state_dict: see tests/test_controlnet_cpu.py
+
+
+@dataclass
+class ControlNetConfig:
+    """``unet``: the fields a ControlNet shares with the UNet it is paired with (4 input channels, no IP-Adapter; its
+    ``sample_size`` is only the default latent size); ``conditioning_embedding_out_channels``: the widths of the
+    conditioning embedding's conv chain."""
+    unet: UNetConfig
+    conditioning_embedding_out_channels: Tuple[int, ...] = CONTROLNET_EMBED_CHANNELS
+
+    def __post_init__(self):
+        e = tuple(int(v) for v in self.conditioning_embedding_out_channels)
+        if len(e) != 4 or any(v <= 0 or v % 8 for v in e):
+            raise NotImplementedError(f"conditioning_embedding_out_channels={e}: four positive multiples of 8 are built "
+                                      f"(the published ControlNets have {CONTROLNET_EMBED_CHANNELS})")
+        self.conditioning_embedding_out_channels = e
+        if self.unet.in_channels != 4 or self.unet.ip_adapter_embed_dim is not None:
+            raise NotImplementedError("a ControlNet has 4 input channels and no IP-Adapter")
+
+
+def controlnet_config_for(unet_cfg: UNetConfig, embed_channels=CONTROLNET_EMBED_CHANNELS) -> ControlNetConfig:
+    """The ControlNet config that pairs with ``unet_cfg`` (an inpainting UNet's ControlNet still reads 4 channels; the
+    ControlNet has no ``cond_proj``: upstream's pipeline passes it no ``timestep_cond``)."""
+    import dataclasses
+    base = dataclasses.replace(without_ip_adapter(unet_cfg), in_channels=4, out_channels=4, time_cond_proj_dim=None)
+    return ControlNetConfig(unet=base, conditioning_embedding_out_channels=tuple(embed_channels))
+
+
+def check_controlnet_pairs(cn: ControlNetConfig, unet_cfg: UNetConfig) -> None:
+    """The fields a ControlNet shares with its UNet must agree: the residuals are added to the UNet's skip tensors."""
+    for f in CONTROLNET_SHARED_FIELDS:
+        a, b = getattr(cn.unet, f), getattr(unet_cfg, f)
+        if (tuple(a) if isinstance(a, (list, tuple)) else a) != (tuple(b) if isinstance(b, (list, tuple)) else b):
+            raise ValueError(f"controlnet config {f}={a!r} does not match the UNet it is paired with ({f}={b!r})")
+
+
+def read_controlnet_config(c: dict, unet_config: Optional[UNetConfig] = None) -> ControlNetConfig:
+    """The dict of a diffusers ControlNet ``config.json`` -> ``ControlNetConfig``.  Read: ``conditioning_embedding_out_channels``,
+    ``controlnet_conditioning_channel_order`` ("rgb" only), ``global_pool_conditions`` (false only), ``conditioning_channels``
+    (3 only) and the fields shared with the UNet through ``read_unet_config`` (a ControlNet has no up blocks: they are taken
+    as the mirror of its down blocks).  With ``unet_config`` the shared fields must agree with it; anything else is refused
+    by name."""
+    order = c.get("controlnet_conditioning_channel_order", "rgb")
+    if order != "rgb":
+        raise NotImplementedError(f"controlnet config controlnet_conditioning_channel_order={order!r}: 'rgb' is built")
+    if c.get("global_pool_conditions", False) is not False:
+        raise NotImplementedError(f"controlnet config global_pool_conditions={c['global_pool_conditions']!r}: false is built")
+    if c.get("conditioning_channels", 3) != 3:
+        raise NotImplementedError(f"controlnet config conditioning_channels={c['conditioning_channels']!r}: 3 (an rgb image) is built")
+    if c.get("in_channels", 4) != 4:
+        raise NotImplementedError(f"controlnet config in_channels={c['in_channels']!r}: 4 is built")
+    down = list(c.get("down_block_types", ["CrossAttnDownBlock2D"] * 3 + ["DownBlock2D"]))
+    mirror = ["CrossAttnUpBlock2D" if d == "CrossAttnDownBlock2D" else "UpBlock2D" for d in reversed(down)]
+    shared = {k: v for k, v in c.items() if k not in ("time_cond_proj_dim", "up_block_types")}
+    shared["up_block_types"] = mirror
+    ucfg = read_unet_config(shared)
+    cn = ControlNetConfig(unet=ucfg, conditioning_embedding_out_channels=tuple(
+        c.get("conditioning_embedding_out_channels", CONTROLNET_EMBED_CHANNELS)))
+    if unet_config is not None:
+        check_controlnet_pairs(cn, unet_config)
+    return cn
+
+
+def controlnet_cond_embedding_convs(cn: ControlNetConfig) -> List[Tuple[str, int, int, int]]:
+    """(prefix, cin, cout, stride) of ControlNetConditioningEmbedding's eight 3x3 convs; SiLU follows all but the last."""
+    e, p = cn.conditioning_embedding_out_channels, "controlnet_cond_embedding."
+    out = [(p + "conv_in.", 3, e[0], 1)]
+    for i in range(3):
+        out += [(p + f"blocks.{2 * i}.", e[i], e[i], 1), (p + f"blocks.{2 * i + 1}.", e[i], e[i + 1], 2)]
+    return out + [(p + "conv_out.", e[3], cn.unet.block_out_channels[0], 1)]
+
+
+def controlnet_residual_shapes(cn, height: int, width: int) -> List[Tuple[int, int, int]]:
+    """(channels, h, w) of the thirteen residuals at a latent ``height`` x ``width`` (``cn``: a ControlNetConfig or the UNet's
+    config), in diffusers' order: conv_in, per level its blocks then its downsampler, the mid block last."""
+    u = cn.unet if isinstance(cn, ControlNetConfig) else cn
+    nl, h, w = len(u.block_out_channels), int(height), int(width)
+    out = [(u.block_out_channels[0], h, w)]
+    for i in range(nl):
+        out += [(u.block_out_channels[i], h, w)] * u.layers_per_block
+        if i < nl - 1:
+            h, w = h // 2, w // 2
+            out.append((u.block_out_channels[i], h, w))
+    return out + [(u.block_out_channels[-1], h, w)]
+
+
+def controlnet_param_shapes(cn: ControlNetConfig) -> List[Tuple[str, Tuple[int, ...]]]:
+    """(name, shape) of every ControlNet parameter: the UNet's time embedding, conv_in, down blocks and mid block under the
+    UNet's names, then the conditioning embedding and the zero convs."""
+    out = [(n, s) for n, s in param_shapes(cn.unet)
+           if not n.startswith(("up_blocks.", "conv_norm_out.", "conv_out."))]
+    for p, cin, cout, _ in controlnet_cond_embedding_convs(cn):
+        out += [(p + "weight", (cout, cin, 3, 3)), (p + "bias", (cout,))]
+    res = controlnet_residual_shapes(cn, 8, 8)
+    for i, (c, _, _) in enumerate(res[:-1]):
+        out += [(f"controlnet_down_blocks.{i}.weight", (c, c, 1, 1)), (f"controlnet_down_blocks.{i}.bias", (c,))]
+    c = res[-1][0]
+    return out + [("controlnet_mid_block.weight", (c, c, 1, 1)), ("controlnet_mid_block.bias", (c,))]
+
+
+def make_synthetic_controlnet_state_dict(cn: ControlNetConfig, seed: int = 1234,
+                                         gain: float = CONTROLNET_SYNTHETIC_GAIN) -> Dict[str, torch.Tensor]:
+    """Seeded ControlNet-shaped weights on the bf16 grid from a generator of their own.  The encoder half is drawn like the
+    UNet's (``make_synthetic_state_dict``'s rules).  Upstream initialises the zero convs and the embedding's ``conv_out`` to
+    ZERO: a fresh ControlNet is a no-op.  Here the zero convs are N(0, gain^2 / fan_in) with biases N(0, 0.05^2), so that the
+    residuals move the UNet's output (tests/test_controlnet_cpu.py fixes ``gain``), and the embedding's convs are
+    N(0, 2 / fan_in), its ``conv_out`` N(0, 9 / fan_in) (the strided SiLU chain shrinks a [0, 1] image): the embedding then is a third
+    of conv_in's output in size, so a wrong control image shows in every residual."""
+    g = torch.Generator().manual_seed(CONTROLNET_SEED_OFFSET + int(seed))
+    sd: Dict[str, torch.Tensor] = {}
+    for name, shape in controlnet_param_shapes(cn):
+        leaf = name.rsplit(".", 2)[-2]
+        is_norm = leaf.startswith("norm")
+        zero_conv = name.startswith(("controlnet_down_blocks.", "controlnet_mid_block."))
+        if name.endswith(".bias"):
+            t = torch.randn(shape, generator=g) * (0.1 if is_norm else 0.05)
+        elif is_norm:
+            t = 1.0 + 0.1 * torch.randn(shape, generator=g)
+        else:
+            fan_in = math.prod(shape[1:])
+            k = gain if zero_conv else 3.0 if name.startswith("controlnet_cond_embedding.conv_out.") else \
+                math.sqrt(2.0) if name.startswith("controlnet_cond_embedding.") else 1.0
+            t = torch.randn(shape, generator=g) * (k / math.sqrt(fan_in))
+        sd[name] = t.to(torch.bfloat16).float()
+    return sd
+
+
+def load_controlnet(path: str, unet_config: Optional[UNetConfig] = None):
+    """A LOCAL ControlNet directory in the upstream layout (``config.json`` and ``diffusion_pytorch_model.safetensors`` or
+    ``.bin``) -> (ControlNetConfig, fp32 state dict).  Never fetches."""
+    import json
+    cfile = os.path.join(path, "config.json")
+    if not os.path.isfile(cfile):
+        raise FileNotFoundError(f"no ControlNet config at {cfile!r}")
+    with open(cfile, encoding="utf-8") as f:
+        cn = read_controlnet_config(json.load(f), unet_config)
+    st, bn = os.path.join(path, "diffusion_pytorch_model.safetensors"), os.path.join(path, "diffusion_pytorch_model.bin")
+    if os.path.isfile(st):
+        from safetensors.torch import load_file
+        sd = load_file(st)
+    elif os.path.isfile(bn):
+        sd = torch.load(bn, map_location="cpu", weights_only=True)
+    else:
+        raise FileNotFoundError(f"no ControlNet weights under {path!r} (diffusion_pytorch_model.safetensors / .bin)")
+    return cn, {k: v.float() for k, v in sd.items()}
+
+
+def control_keep(num_steps: int, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0) -> List[float]:
+    """``controlnet_keep`` of StableDiffusionControlNetPipeline: step i of N keeps the ControlNet unless
+    ``i / N < start or (i + 1) / N > end``."""
+    n = int(num_steps)
+    return [1.0 - float(i / n < control_guidance_start or (i + 1) / n > control_guidance_end) for i in range(n)]
+
+
 _SYNTHETIC_CACHE: Dict[tuple, Dict[str, torch.Tensor]] = {}
 
 
