@@ -34,7 +34,7 @@ typedef struct sd_unet_config {
     int layers_per_block;        /* 2 */
     int attn_levels[8];          /* 1,1,1,0 : level carries Transformer2DModel blocks */
     int cross_attention_dim;     /* 768 */
-    int num_heads;               /* 8 (diffusers attention_head_dim=8 is used as head COUNT) */
+    int num_heads;               /* 8 (diffusers attention_head_dim=8 is used as head COUNT); see num_heads_per_level */
     int norm_num_groups;         /* 32 */
     float norm_eps;              /* 1e-5 */
     int context_len;             /* 77 */
@@ -62,9 +62,16 @@ typedef struct sd_unet_config {
      *   encoder_hid_proj.image_projection_layers.0.image_embeds.{weight [tokens * cross_attention_dim, E], bias},
      *   encoder_hid_proj.image_projection_layers.0.norm.{weight, bias} [cross_attention_dim], and per attn2 layer
      *   <block>.attn2.processor.to_k_ip.0.weight / to_v_ip.0.weight [C, cross_attention_dim]
-     * and sd_unet_set_ip_adapter_hw conditions its forwards.  num_heads must be 1, 2, 4 or 8.  (Appended under ABI 3.) */
+     * and sd_unet_set_ip_adapter_hw conditions its forwards.  Every level's head count must be 1, 2, 4 or 8.  (Appended under
+     * ABI 3.) */
     int ip_adapter_tokens;
     int ip_adapter_embed_dim;
+    /* Head COUNT of the transformer blocks per resolution level (Stable Diffusion 2.x: 5, 10, 20, 20 = head dim 64 at every
+     * level; diffusers' attention_head_dim list).  All zeros = num_heads at every level (SD-1.5).  Otherwise every one of the
+     * num_levels entries is positive; the mid block uses the last level's count and the up blocks mirror the down blocks.
+     * Channels / heads of an attention level must be 40, 64, 80 or 160.  An IP-Adapter needs 1, 2, 4 or 8 heads at every
+     * level.  (Appended under ABI 3: zero-initialise the struct.) */
+    int num_heads_per_level[8];
 } sd_unet_config;
 enum { SD_DTYPE_BF16 = 0, SD_DTYPE_FP8_E4M3 = 1 };
 
@@ -275,6 +282,9 @@ typedef struct sd_clip_config {
     int intermediate_size;   /* 3072 */
     int max_positions;       /* 77 */
     float layer_norm_eps;    /* 1e-5 */
+    /* MLP activation: SD_ACT_QUICK_GELU (0: OpenAI CLIP ViT-L/14, SD-1.5) or SD_ACT_GELU (exact, erf: the OpenCLIP ViT-H text
+     * tower of Stable Diffusion 2.x, hidden 1024 / 16 heads / 23 layers).  (Appended: zero-initialise the struct.) */
+    int hidden_act;
 } sd_clip_config;
 typedef struct sd_unet sd_clip;
 int sd_clip_create(const sd_clip_config* cfg, sd_clip** out);
@@ -519,6 +529,7 @@ int sd_op_conv3x3_groupnorm(void* stream, const void* X, const void* W, const fl
 int sd_op_conv3x3_splitk(int M, int Cout, int Cin, int Hin, int Win, int stride, int upsample);
 int sd_op_layernorm(void* stream, const void* x, const float* gamma, const float* beta, void* y, int rows, int C,
                     float eps);
+/* flash-style attention on token-major [B, N, heads * D] views; D = 40, 64, 80 or 160 (64: Stable Diffusion 2.x), any Nq / Nk */
 int sd_op_attention(void* stream, const void* Q, long long ldq, const void* K, long long ldk, const void* V,
                     long long ldv, void* O, long long ldo, int B, int heads, int Nq, int Nk, int D, float scale);
 /* the same with HEAD-MAJOR K / V, [B][heads][Nk][D] contiguous (how the plan's fused q|k|v projection stores K and V at

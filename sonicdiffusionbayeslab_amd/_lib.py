@@ -23,6 +23,8 @@ _ablate: Optional[C.CDLL] = None
 
 
 class SdUnetConfig(C.Structure):
+    """The fields of ``sd_unet_config`` up to the IP-Adapter's: only the PREFIX of what the library reads.  Never passed to an
+    entry point (their argument type is ``SdUnetConfigFull``, so ctypes refuses this one); kept as the base of the full struct."""
     _fields_ = [
         ("sample_size", C.c_int), ("in_channels", C.c_int), ("out_channels", C.c_int),
         ("num_levels", C.c_int), ("block_out_channels", C.c_int * 8), ("layers_per_block", C.c_int),
@@ -34,6 +36,15 @@ class SdUnetConfig(C.Structure):
     ]
 
 
+class SdUnetConfigFull(SdUnetConfig):
+    """``sd_unet_config`` as the library reads it today: the fields above, then what was appended after the IP-Adapter
+    (a ctypes subclass lays its fields out behind its base's).  Every entry point takes THIS type: the shorter base would be
+    read past its end."""
+    _fields_ = [
+        ("num_heads_per_level", C.c_int * 8),       # head count per level; all zeros = num_heads at every level
+    ]
+
+
 DTYPE_BF16, DTYPE_FP8_E4M3 = 0, 1
 DTYPES = {"bf16": DTYPE_BF16, "fp8": DTYPE_FP8_E4M3, "fp8_e4m3": DTYPE_FP8_E4M3}
 
@@ -42,6 +53,7 @@ class SdClipConfig(C.Structure):
     _fields_ = [
         ("vocab_size", C.c_int), ("hidden_size", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int),
         ("intermediate_size", C.c_int), ("max_positions", C.c_int), ("layer_norm_eps", C.c_float),
+        ("hidden_act", C.c_int),            # 0 = quick_gelu, 1 = gelu (exact); appended: the seven-value form leaves it 0
     ]
 
 
@@ -68,7 +80,7 @@ _vp, _i, _ll, _f = C.c_void_p, C.c_int, C.c_longlong, C.c_float
 _SIGS = {
     "sd_last_error": (C.c_char_p, []),
     "sd_abi_version": (_i, []),
-    "sd_unet_create": (_i, [C.POINTER(SdUnetConfig), C.POINTER(_vp)]),
+    "sd_unet_create": (_i, [C.POINTER(SdUnetConfigFull), C.POINTER(_vp)]),
     "sd_unet_destroy": (None, [_vp]),
     "sd_unet_num_params": (_i, [_vp]),
     "sd_unet_param_info": (_i, [_vp, _i, C.c_char_p, _i, C.POINTER(_ll), C.POINTER(_i)]),
@@ -89,10 +101,10 @@ _SIGS = {
     "sd_unet_forward_profiled": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _ll, _i, _i, C.POINTER(C.c_double),
                                       C.POINTER(_ll), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "sd_unet_forward_op_times": (_ll, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _ll, _i, _i, C.c_char_p, _ll]),
-    "sd_vae_create": (_i, [C.POINTER(SdUnetConfig), C.POINTER(_vp)]),
+    "sd_vae_create": (_i, [C.POINTER(SdUnetConfigFull), C.POINTER(_vp)]),
     "sd_vae_decode": (_i, [_vp, _vp, _vp, _i, _f, _vp, _vp, _ll]),
     "sd_vae_decode_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _ll]),
-    "sd_vae_encoder_create": (_i, [C.POINTER(SdUnetConfig), C.POINTER(_vp)]),
+    "sd_vae_encoder_create": (_i, [C.POINTER(SdUnetConfigFull), C.POINTER(_vp)]),
     "sd_vae_encode_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _ll]),
     "sd_vae_posterior_sample": (_i, [_vp, _vp, _vp, _f, _vp, _i, _ll]),
     "sd_clip_create": (_i, [C.POINTER(SdClipConfig), C.POINTER(_vp)]),
@@ -131,7 +143,7 @@ _SIGS = {
     "sd_unet_set_inpaint_cond_hw": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
     "sd_unet_set_ip_adapter_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _ll]),
     "sd_op_ip_xattn": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _ll, _i, _i, _i, _i]),
-    "sd_controlnet_create": (_i, [C.POINTER(SdUnetConfig), C.POINTER(_i), C.POINTER(_vp)]),
+    "sd_controlnet_create": (_i, [C.POINTER(SdUnetConfigFull), C.POINTER(_i), C.POINTER(_vp)]),
     "sd_controlnet_residual_bytes_hw": (_ll, [_vp, _i, _i, _i]),
     "sd_controlnet_set_cond_hw": (_i, [_vp, _vp, _vp, _i, _i, _i]),
     "sd_controlnet_forward_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _ll]),

@@ -1,8 +1,9 @@
 """CLIP text encoder + tokenizer -- SURVEY.md §8f "next" row 2.
 
 Replaces ``encode_prompt`` of the reference pipeline (``src/models.py:139-155``): tokenise the prompts
-(CLIP byte-level BPE, 77 tokens, padded with ``<|endoftext|>``), run ``CLIPTextModel`` (ViT-L/14 text tower:
-12 pre-LN layers, 12 heads of 64, quick_gelu MLP, causal mask, final LayerNorm) and hand its
+(CLIP byte-level BPE, 77 tokens, padded with the checkpoint's pad token: ``<|endoftext|>`` for SD-1.5, ``!`` for Stable
+Diffusion 2.x), run ``CLIPTextModel`` (ViT-L/14 text tower: 12 pre-LN layers, 12 heads of 64, quick_gelu MLP, causal mask,
+final LayerNorm; SD 2.x: the OpenCLIP ViT-H tower, 23 layers, 16 heads of 64, exact gelu) and hand its
 ``last_hidden_state`` ``[B,77,768]`` to the UNet as ``prompt_embeds``.
 
 * ``HipClipTextModel``   -- the transformer on libsdhip (``sd_clip_create`` / ``sd_clip_encode``); no CPU fallback.
@@ -42,6 +43,16 @@ class ClipTextConfig:
     bos_token_id: int = 49406
     eos_token_id: int = 49407
     pad_token_id: int = 49407          # SD-1.5's tokenizer pads with <|endoftext|>
+    # MLP activation: "quick_gelu" (OpenAI CLIP ViT-L/14: SD-1.5) or "gelu" (exact; the OpenCLIP ViT-H text tower of Stable
+    # Diffusion 2.x: hidden 1024, 16 heads, 23 layers).  Anything else is refused by name.
+    hidden_act: str = "quick_gelu"
+
+    def __post_init__(self):
+        if self.hidden_act not in CLIP_HIDDEN_ACTS:
+            raise NotImplementedError(f"text_encoder config hidden_act={self.hidden_act!r}: 'quick_gelu' and 'gelu' are built")
+
+
+CLIP_HIDDEN_ACTS = {"quick_gelu": 0, "gelu": 1}      # include/sd_hip.h: SD_ACT_QUICK_GELU / SD_ACT_GELU
 
 
 def clip_param_shapes(cfg: ClipTextConfig) -> List[Tuple[str, Tuple[int, ...]]]:
@@ -122,7 +133,8 @@ class HipClipTextModel:
 
     def _build(self, config, state_dict, text_projection, eos_token_id):
         c = _lib.SdClipConfig(config.vocab_size, config.hidden_size, config.num_hidden_layers, config.num_attention_heads,
-                              config.intermediate_size, config.max_position_embeddings, config.layer_norm_eps)
+                              config.intermediate_size, config.max_position_embeddings, config.layer_norm_eps,
+                              CLIP_HIDDEN_ACTS[config.hidden_act])
         self.projection_dim = 0 if text_projection is None else int(text_projection.shape[0])
         if text_projection is None:
             _lib.check(self._lib.sd_clip_create(C.byref(c), C.byref(self._handle)), "sd_clip_create")
@@ -249,6 +261,29 @@ def _basic_clean(text: str) -> str:
     return " ".join("".join(out).split())
 
 
+def read_special_tokens(tokenizer_dir: str) -> Dict[str, str]:
+    """``bos_token`` / ``eos_token`` / ``pad_token`` of a checkpoint's tokenizer: ``special_tokens_map.json`` over
+    ``tokenizer_config.json``, each value a string or a dict with ``content``.  Stable Diffusion 2.x pads with ``!`` (id 0),
+    SD-1.5 with ``<|endoftext|>``; a file that names none leaves the SD-1.5 defaults."""
+    out: Dict[str, str] = {}
+    for fname in ("tokenizer_config.json", "special_tokens_map.json"):
+        path = os.path.join(tokenizer_dir, fname)
+        if not os.path.isfile(path):
+            continue
+        with open(path, encoding="utf-8") as f:
+            j = json.load(f)
+        for name in ("bos_token", "eos_token", "pad_token"):
+            v = j.get(name)
+            if isinstance(v, dict):
+                v = v.get("content")
+            if v is None:
+                continue
+            if not isinstance(v, str):
+                raise ValueError(f"{path}: {name}={j[name]!r} is neither a string nor a dict with 'content'")
+            out[name] = v
+    return out
+
+
 class ClipBpeTokenizer:
     PAT = r"<\|startoftext\|>|<\|endoftext\|>|'s|'t|'re|'ve|'m|'ll|'d|[\p{L}]+|[\p{N}]|[^\s\p{L}\p{N}]+"
 
@@ -261,9 +296,14 @@ class ClipBpeTokenizer:
         self.pat = regex.compile(self.PAT, regex.IGNORECASE)
         self.model_max_length = model_max_length
         self.bos_token_id, self.eos_token_id = self.encoder[bos_token], self.encoder[eos_token]
+        if pad_token not in self.encoder:
+            raise KeyError(f"tokenizer pad_token {pad_token!r} is not in the vocabulary")
         self.pad_token_id = self.encoder[pad_token]
         self.unk_token_id = self.encoder.get(eos_token)      # CLIP's unk token is <|endoftext|>
         self.cache = {bos_token: bos_token, eos_token: eos_token}
+        # a pad token of its own (Stable Diffusion 2.x: "!") is a special token like the two above: where it occurs in a
+        # prompt, transformers emits the token itself ("wow!!" ends in two pad ids, not in the BPE of "!!")
+        self.special_split = pad_token if pad_token not in (bos_token, eos_token) else None
 
     @classmethod
     def from_pretrained(cls, tokenizer_dir: str, **kw) -> "ClipBpeTokenizer":
@@ -274,6 +314,8 @@ class ClipBpeTokenizer:
         if lines and lines[0].startswith("#version"):
             lines = lines[1:]
         merges = [tuple(l.split()) for l in lines if l and len(l.split()) == 2]
+        for name, tok in read_special_tokens(tokenizer_dir).items():
+            kw.setdefault(name, tok)
         return cls(vocab, merges, **kw)
 
     @classmethod
@@ -324,11 +366,15 @@ class ClipBpeTokenizer:
 
     def tokenize(self, text: str) -> List[str]:
         import regex
-        text = _basic_clean(text).lower()
+        text = _basic_clean(text)
         toks: List[str] = []
-        for tok in regex.findall(self.pat, text):
-            tok = "".join(self.byte_encoder[b] for b in tok.encode("utf-8"))
-            toks.extend(self.bpe(tok).split(" "))
+        parts = text.split(self.special_split) if self.special_split else [text]
+        for i, part in enumerate(parts):
+            if i:
+                toks.append(self.special_split)
+            for tok in regex.findall(self.pat, part.lower()):
+                tok = "".join(self.byte_encoder[b] for b in tok.encode("utf-8"))
+                toks.extend(self.bpe(tok).split(" "))
         return toks
 
     def encode(self, text: str) -> List[int]:
@@ -359,7 +405,8 @@ class ClipPromptEncoder:
                 j = json.load(f)
             cfg = ClipTextConfig(**{k: j[k] for k in ("vocab_size", "hidden_size", "num_hidden_layers",
                                                        "num_attention_heads", "intermediate_size",
-                                                       "max_position_embeddings", "layer_norm_eps") if k in j})
+                                                       "max_position_embeddings", "layer_norm_eps", "hidden_act") if k in j},
+                                 pad_token_id=tok.pad_token_id)
         return cls(tok, HipClipTextModel(cfg, load_clip_state_dict(model_dir), device=device))
 
     def __call__(self, prompts: List[str]) -> torch.Tensor:

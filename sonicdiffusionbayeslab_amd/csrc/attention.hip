@@ -1,5 +1,5 @@
 // Flash-style attention (self and cross) for gfx950, head dims 40 / 80 / 160 (SD-1.5: 8 heads
-// at C = 320 / 640 / 1280), arbitrary key count (4096 ... 64 for self-attention, 77 for the
+// at C = 320 / 640 / 1280) and 64 (SD 2.x: 5 / 10 / 20 heads; its pipelined kernel: attn_pipe64_kernel below), arbitrary key count (4096 ... 64 for self-attention, 77 for the
 // prompt cross-attention), bf16 in / fp32 accumulate / bf16 out.
 //
 // Layout: Q, K, V, O are token-major [B, N, heads*D] views (row strides ldq/ldk/ldv/ldo), so
@@ -1255,6 +1255,317 @@ int launch_attn_pipe80(const AttnArgs& a, hipStream_t stream) {
     return 0;
 }
 
+// =====================================================================================================
+// The same software pipeline for D = 64 (Stable Diffusion 2.x: 5 / 10 / 20 heads of 64).  attn_pipe80_kernel's scheme -- XCD-aware
+// 1-D grid, 4 waves x 32 queries, separate LDS-DMA rings of three K and three V tiles, stale softmax reference moved at 2^8,
+// hand-counted transposed V reads -- with KQ = 4 k-steps (K rows of 144 B: 8 data chunks + a zero chunk, an odd number of
+// 16-byte slots).  64 = 2 x 32 leaves no padding column in the two O^T tiles, so the denominator is a choice (template ONES).
+// =====================================================================================================
+template <bool ONES>
+struct Pipe64Cfg {
+    // ONES: the V rows carry a ones chunk at column 64 and a third 32-row O^T tile accumulates sum(P) on the matrix core (rows
+    // of 192 B, as at d = 80); otherwise two O^T tiles and the denominator is summed on the VALU (rows of 144 B)
+    static constexpr int D = 64, KQ = 4, DVT = ONES ? 3 : 2, CD = 8, CHK = 9, CHV = ONES ? 12 : 9, RSK = 144, RSV = CHV * 16;
+    static constexpr int KBYTES = 64 * RSK, NI = CHK + CHV, NW = 4;
+    static constexpr int NIW = (NI + NW - 1) / NW;     // DMA pieces per wave and iteration (the pieces past NI land in the padding KiB)
+    static constexpr int VBYTES = 64 * RSV, NSLOT = 3; // separate rings of three K and three V tiles, as Pipe80Cfg
+    static constexpr int VOFF = NSLOT * KBYTES, PADOFF = VOFF + NSLOT * VBYTES;
+    static constexpr int SMEM = PADOFF + 1024 + 256;   // ... + the tr over-read of the last V row of the last slot
+    static constexpr int RPS = 2 * DVT;                // transposed reads per register set
+    static_assert(KBYTES == CHK * 1024 && VBYTES == CHV * 1024 && SMEM <= 80 * 1024, "whole DMA pieces; two workgroups per CU");
+};
+
+template <bool ONES>
+__global__ __launch_bounds__(Pipe64Cfg<ONES>::NW * 64, 2) void attn_pipe64_kernel(const AttnArgs a) {
+    using Cfg = Pipe64Cfg<ONES>;
+    constexpr int D = Cfg::D, KQ = Cfg::KQ, DVT = Cfg::DVT, CD = Cfg::CD, CHK = Cfg::CHK, CHV = Cfg::CHV;
+    constexpr int RSK = Cfg::RSK, RSV = Cfg::RSV, KBYTES = Cfg::KBYTES, VBYTES = Cfg::VBYTES, NI = Cfg::NI, NIW = Cfg::NIW;
+    constexpr int NW = Cfg::NW, VOFF = Cfg::VOFF, PADOFF = Cfg::PADOFF, RPS = Cfg::RPS;
+
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    int qblk, head, b;
+    xcd_work_item((a.Nq + NW * 32 - 1) / (NW * 32), a.heads, a.xcd_order, qblk, head, b);
+    const int q = qblk * (NW * 32) + wave * 32 + r;
+    const bool qvalid = q < a.Nq;
+    const float c = a.q_prescaled ? 1.0f : a.scale * 1.4426950408889634f;
+    const char* zero = (const char*)a.consts;
+    const char* ones = zero + 256;
+
+    bf16x8 qf[KQ];
+    {
+        const bf16_t* qp = a.Q + ((long)b * a.Nq + (qvalid ? q : 0)) * a.ldq + head * D;
+#pragma unroll
+        for (int kk = 0; kk < KQ; ++kk) {
+            if (qvalid) qf[kk] = *(const bf16x8*)(qp + kk * 16 + h * 8);
+            else qf[kk] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int kk = 0; kk < KQ; ++kk) asm volatile("" : "+v"(qf[kk]));   // retire the loads before the DMA ring starts
+    }
+
+    // branch-free LDS-DMA descriptors (as attn_pipe40_kernel): per piece a source pointer for tile 0 and a byte step per tile
+    const char* d_ptr[NIW];
+    long d_step[NIW];
+#pragma unroll
+    for (int j = 0; j < NIW; ++j) {
+        const int inst = wave + NW * j;
+        d_ptr[j] = zero; d_step[j] = 0;
+        if (inst < CHK) {
+            const int ch = inst * 64 + lane, key = ch / CHK, part = ch - key * CHK;
+            if (part < CD) {
+                d_ptr[j] = (const char*)(a.K + (long)b * a.Nk * a.ldk + head * D + (long)key * a.ldk + part * 8);
+                d_step[j] = 64 * a.ldk * 2;
+            }
+        } else if (inst < NI) {
+            const int ch = (inst - CHK) * 64 + lane, key = ch / CHV, part = ch - key * CHV;
+            if (part < CD) {
+                d_ptr[j] = (const char*)(a.V + (long)b * a.Nk * a.ldv + head * D + (long)key * a.ldv + part * 8);
+                d_step[j] = 64 * a.ldv * 2;
+            } else if (ONES && part == CD) {
+                d_ptr[j] = ones;
+            }
+        }
+    }
+    const int ntiles = a.Nk / 64;                 // >= 3, all full (checked by the launcher)
+    // one batch = the K pieces of tile tk into K slot ks and the V pieces of tile tv into V slot vs (+ the padding piece);
+    // tiles past the end fetch the zero page (their slots are dead)
+    auto issue = [&](int tk, int ks, int tv, int vs) {
+#pragma unroll
+        for (int j = 0; j < NIW; ++j) {
+            const int inst = wave + NW * j;                   // wave-uniform
+            const bool isk = inst < CHK;
+            const int t = isk ? tk : tv;
+            const char* src = t < ntiles ? d_ptr[j] + d_step[j] * t : zero;
+            char* dst = isk ? smem + ks * KBYTES + inst * 1024 : inst < NI ? smem + VOFF + vs * VBYTES + (inst - CHK) * 1024 : smem + PADOFF;
+            glds16(src, dst);
+        }
+    };
+
+    f32x16 o[DVT];
+#pragma unroll
+    for (int t = 0; t < DVT; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[t][i] = 0.f;
+
+    const int kfrag_off = pi_swap23(r) * RSK + h * 16;
+    const int g16 = (lane >> 4) & 1, q4 = (lane & 15) >> 2, p4 = lane & 3;
+    const int vtr_off = VOFF + (8 * h + q4) * RSV + (16 * g16 + 4 * p4) * 2;
+    const unsigned lds_v = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem + (unsigned)vtr_off;
+
+    auto qk = [&](const char* tile, f32x16& s0, f32x16& s1) {
+        const char* kp = tile + kfrag_off;
+        s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(kp), qf[0], f32x16{}, 0, 0, 0);
+        s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(kp + 32 * RSK), qf[0], f32x16{}, 0, 0, 0);
+#pragma unroll
+        for (int kk = 1; kk < KQ; ++kk) {
+            s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(kp + kk * 32), qf[kk], s0, 0, 0, 0);
+            s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(kp + 32 * RSK + kk * 32), qf[kk], s1, 0, 0, 0);
+        }
+    };
+    float l_run = 0.f;                            // !ONES: this lane's share of the softmax denominator (its 32 keys of every tile)
+    auto exp_group = [&](const f32x16& c0, const f32x16& c1, int s2, float mc) -> bf16x8 {
+        float p[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) p[j] = __builtin_amdgcn_exp2f(__builtin_fmaf(s2 < 2 ? c0[8 * s2 + j] : c1[8 * (s2 - 2) + j], c, -mc));
+        if (!ONES) l_run += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+        u32x4 w = {pack2bf(p[0], p[1]), pack2bf(p[2], p[3]), pack2bf(p[4], p[5]), pack2bf(p[6], p[7])};
+        return __builtin_bit_cast(bf16x8, w);
+    };
+
+    // invariant at the start of iteration t: K(0 .. t+2) and V(0 .. t+1) have been requested, in batches of NIW pieces per wave
+    issue(0, 0, 0, 0);
+    issue(1, 1, 0, 0);                            // (no V tile of its own yet: V(0) again, identical bytes into the same slot)
+    issue(2, 2, 1, 1);
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NIW) : "memory");   // K(0), V(0) landed
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    f32x16 sa0, sa1, sb0, sb1;                    // S(t) / S(t+1), roles swap every iteration
+    qk(smem, sa0, sa1);
+    float m_run;                                  // the softmax reference M (a score), exact for tile 0, stale afterwards
+    {
+        float tm = fmaxf(sa0[0], sa1[0]);
+#pragma unroll
+        for (int i = 1; i < 16; ++i) tm = fmaxf(fmaxf(tm, sa0[i]), sa1[i]);
+        m_run = half_pair_max(tm);
+    }
+    constexpr float STALE = 8.f;                  // log2 of the largest probability before M is moved
+
+    // V^T fragments of P group G (keys 16 G .. 16 G + 15 of the tile) for the two or three 32-row O^T tiles: RPS transposed reads into
+    // register set S; READY(S, N): they have landed when at most N LDS operations issued after them are outstanding
+#define SD_VREAD64(S, G)                                                                                    \
+    SD_TR_READ(S##0l, vaddr, (G) * 16 * RSV); SD_TR_READ(S##0h, vaddr, (G) * 16 * RSV + 4 * RSV);           \
+    SD_TR_READ(S##1l, vaddr, (G) * 16 * RSV + 64); SD_TR_READ(S##1h, vaddr, (G) * 16 * RSV + 64 + 4 * RSV); \
+    if constexpr (ONES) { SD_TR_READ(S##2l, vaddr, (G) * 16 * RSV + 128); SD_TR_READ(S##2h, vaddr, (G) * 16 * RSV + 128 + 4 * RSV); }
+#define SD_VREADY64(S, N)                                                                                   \
+    if constexpr (ONES) {                                                                                   \
+        asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(S##0l), "+v"(S##0h), "+v"(S##1l), "+v"(S##1h), "+v"(S##2l), "+v"(S##2h) : "n"(N)); \
+        v2 = bf16x8{S##2l[0], S##2l[1], S##2l[2], S##2l[3], S##2h[0], S##2h[1], S##2h[2], S##2h[3]};        \
+    } else {                                                                                                \
+        asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(S##0l), "+v"(S##0h), "+v"(S##1l), "+v"(S##1h) : "n"(N)); \
+    }                                                                                                       \
+    v0 = bf16x8{S##0l[0], S##0l[1], S##0l[2], S##0l[3], S##0h[0], S##0h[1], S##0h[2], S##0h[3]};            \
+    v1 = bf16x8{S##1l[0], S##1l[1], S##1l[2], S##1l[3], S##1h[0], S##1h[1], S##1h[2], S##1h[3]};
+#define SD_PV64(G)                                                                                          \
+    o[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v0, pf[G], o[0], 0, 0, 0);                               \
+    o[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v1, pf[G], o[1], 0, 0, 0);                               \
+    if constexpr (ONES) o[2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v2, pf[G], o[2], 0, 0, 0);
+
+    // One steady-state iteration (t <= ntiles - 2): consumes S(t) in (c0, c1), produces S(t+1) in (n0, n1).
+    auto steady = [&](int t, int slot, f32x16& c0, f32x16& c1, f32x16& n0, f32x16& n1) {
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NIW) : "memory");     // K(t+1), V(t) landed; K(t+2), V(t+1) may be in flight
+        __builtin_amdgcn_s_barrier();                         // ... for every wave, and every wave is past QK(t) and PV(t-1)
+        asm volatile("" ::: "memory");
+        const int nslot = slot == 2 ? 0 : slot + 1, fslot = slot == 0 ? 2 : slot - 1;
+        issue(t + 3, slot, t + 2, fslot);                     // K(t+3) into the slot of K(t), V(t+2) into the slot of V(t-1)
+        const char* kp = smem + nslot * KBYTES + kfrag_off;
+        const float mc = m_run * c;
+        bf16x8 kf[2 * KQ];
+#pragma unroll
+        for (int kk = 0; kk < KQ; ++kk) {
+            kf[kk] = *(const bf16x8*)(kp + kk * 32);
+            kf[KQ + kk] = *(const bf16x8*)(kp + 32 * RSK + kk * 32);
+        }
+        bf16x8 pf[4], v0, v1, v2;
+        const unsigned vaddr = lds_v + (unsigned)(slot * VBYTES);
+        bf16x4 x0l, x0h, x1l, x1h, x2l, x2h, y0l, y0h, y1l, y1h, y2l, y2h;
+        __builtin_amdgcn_sched_barrier(0);
+        // phase A: two QK^T MFMAs of tile t+1 + exp2 / pack of 8 scores of tile t, four times (the first V read before the last)
+        n0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[0], qf[0], f32x16{}, 0, 0, 0);
+        n1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[KQ], qf[0], f32x16{}, 0, 0, 0);
+        pf[0] = exp_group(c0, c1, 0, mc);
+        __builtin_amdgcn_sched_barrier(0);
+        n0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[1], qf[1], n0, 0, 0, 0);
+        n1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[KQ + 1], qf[1], n1, 0, 0, 0);
+        pf[1] = exp_group(c0, c1, 1, mc);
+        __builtin_amdgcn_sched_barrier(0);
+        n0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[2], qf[2], n0, 0, 0, 0);
+        n1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[KQ + 2], qf[2], n1, 0, 0, 0);
+        pf[2] = exp_group(c0, c1, 2, mc);
+        __builtin_amdgcn_sched_barrier(0);
+        SD_VREAD64(x, 0)
+        __builtin_amdgcn_sched_barrier(0);
+        n0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[3], qf[3], n0, 0, 0, 0);
+        n1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[KQ + 3], qf[3], n1, 0, 0, 0);
+        pf[3] = exp_group(c0, c1, 3, mc);
+        __builtin_amdgcn_sched_barrier(0);
+        // phase B: DVT PV MFMAs per P group + a quarter of the running max over S(t+1)
+        SD_VREAD64(y, 1) SD_VREADY64(x, RPS)
+        SD_PV64(0)
+        float tm0 = fmaxf(n0[0], n1[0]);
+#pragma unroll
+        for (int i = 1; i < 4; ++i) tm0 = fmaxf(fmaxf(tm0, n0[i]), n1[i]);
+        __builtin_amdgcn_sched_barrier(0);
+        SD_VREAD64(x, 2) SD_VREADY64(y, RPS)
+        SD_PV64(1)
+#pragma unroll
+        for (int i = 4; i < 8; ++i) tm0 = fmaxf(fmaxf(tm0, n0[i]), n1[i]);
+        __builtin_amdgcn_sched_barrier(0);
+        SD_VREAD64(y, 3) SD_VREADY64(x, RPS)
+        SD_PV64(2)
+#pragma unroll
+        for (int i = 8; i < 12; ++i) tm0 = fmaxf(fmaxf(tm0, n0[i]), n1[i]);
+        __builtin_amdgcn_sched_barrier(0);
+        SD_VREADY64(y, 0)
+        SD_PV64(3)
+#pragma unroll
+        for (int i = 12; i < 16; ++i) tm0 = fmaxf(fmaxf(tm0, n0[i]), n1[i]);
+        const float tmx = half_pair_max(tm0);
+        __builtin_amdgcn_sched_barrier(0);
+        // rare: some query's tile maximum is more than 2^STALE above its reference -> every lane moves M up to its maximum so
+        // far; O (and the row sum in it) is rescaled once, S(t+1) is exponentiated against the new reference next iteration
+        if (!__all((tmx - m_run) * c <= STALE)) {
+            const float m_new = fmaxf(m_run, tmx);
+            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
+            if (!ONES) l_run *= alpha;
+#pragma unroll
+            for (int tt = 0; tt < DVT; ++tt)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) o[tt][i] *= alpha;
+            m_run = m_new;
+        }
+    };
+    auto final_tile = [&](int slot, f32x16& c0, f32x16& c1) {
+        // (what is still in flight fetched the zero page into dead slots)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const float mc = m_run * c;
+        bf16x8 pf[4], v0, v1, v2;
+#pragma unroll
+        for (int s2 = 0; s2 < 4; ++s2) pf[s2] = exp_group(c0, c1, s2, mc);
+        const unsigned vaddr = lds_v + (unsigned)(slot * VBYTES);
+        bf16x4 x0l, x0h, x1l, x1h, x2l, x2h;
+        __builtin_amdgcn_sched_barrier(0);
+        SD_VREAD64(x, 0) SD_VREADY64(x, 0) SD_PV64(0)
+        __builtin_amdgcn_sched_barrier(0);
+        SD_VREAD64(x, 1) SD_VREADY64(x, 0) SD_PV64(1)
+        __builtin_amdgcn_sched_barrier(0);
+        SD_VREAD64(x, 2) SD_VREADY64(x, 0) SD_PV64(2)
+        __builtin_amdgcn_sched_barrier(0);
+        SD_VREAD64(x, 3) SD_VREADY64(x, 0) SD_PV64(3)
+        __builtin_amdgcn_sched_barrier(0);
+    };
+#undef SD_VREAD64
+#undef SD_VREADY64
+#undef SD_PV64
+    int t = 0, slot = 0;
+    for (; t + 2 < ntiles; t += 2) {
+        steady(t, slot, sa0, sa1, sb0, sb1);
+        slot = slot == 2 ? 0 : slot + 1;
+        steady(t + 1, slot, sb0, sb1, sa0, sa1);
+        slot = slot == 2 ? 0 : slot + 1;
+    }
+    if (t + 2 == ntiles) {                        // even tile count: one more steady step, then the last tile
+        steady(t, slot, sa0, sa1, sb0, sb1);
+        slot = slot == 2 ? 0 : slot + 1;
+        final_tile(slot, sb0, sb1);
+    } else {
+        final_tile(slot, sa0, sa1);
+    }
+
+    // ONES: row 64 of O^T holds sum(P) (ones chunk): tile 2, row 0 -> register 0 of the h = 0 half; else the two lanes' sums
+    float l_tot;
+    if constexpr (ONES) l_tot = __shfl(o[DVT - 1][0], r);
+    else l_tot = l_run + __shfl_xor(l_run, 32);
+    const float inv = 1.0f / l_tot;
+    if (qvalid) {
+        bf16_t* op = a.O + ((long)b * a.Nq + q) * a.ldo + head * D;
+#pragma unroll
+        for (int tt = 0; tt < DVT; ++tt) {
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                const int dv = 32 * tt + 8 * g4 + 4 * h;
+                if (dv < D) {
+                    u32x2 w = {pack2bf(o[tt][4 * g4 + 0] * inv, o[tt][4 * g4 + 1] * inv),
+                               pack2bf(o[tt][4 * g4 + 2] * inv, o[tt][4 * g4 + 3] * inv)};
+                    *(u32x2*)(op + dv) = w;
+                }
+            }
+        }
+    }
+}
+
+template <bool ONES>
+int launch_attn_pipe64(const AttnArgs& a, hipStream_t stream) {
+    using Cfg = Pipe64Cfg<ONES>;
+    static bool attr_set = false;
+    if (!attr_set) {
+        SD_CHECK_HIP(hipFuncSetAttribute((const void*)attn_pipe64_kernel<ONES>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM));
+        attr_set = true;
+    }
+    constexpr int QB = Cfg::NW * 32;
+    SD_REQUIRE(a.Nk % 64 == 0 && a.Nk >= 192 && a.consts != nullptr, "attention: the pipelined d = 64 kernel takes key counts that are "
+               "multiples of 64 from 192 on (Nk=%d)", a.Nk);
+    SD_REQUIRE((long)((a.Nq + QB - 1) / QB) * a.heads * a.B < (1l << 31), "attention: grid too large");
+    dim3 grid(((a.Nq + QB - 1) / QB) * a.heads * a.B);          // 1-D: XCD-aware work order inside the kernel
+    hipLaunchKernelGGL(attn_pipe64_kernel<ONES>, grid, dim3(Cfg::NW * 64), Cfg::SMEM, stream, a);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 template <int D>
 int launch_attn_dma(const AttnArgs& a, hipStream_t stream) {
     // SD_ATTN_LDS_PAD (KiB): occupancy experiment knob -- extra dynamic LDS limits workgroups per CU
@@ -1288,6 +1599,8 @@ int launch_attn(const AttnArgs& a, hipStream_t stream) {
     SD_CHECK_HIP(hipGetLastError());
     return 0;
 }
+
+constexpr int PIPE64_DEFAULT = 2;      // 0: attn_kernel<64>, 1: attn_pipe64_kernel<ONES>, 2: attn_pipe64_kernel<VALU sum>
 
 }  // namespace
 
@@ -1330,7 +1643,19 @@ int sd_launch_attention(const AttnArgs& a0, hipStream_t stream) {
             if (dma && !no_pipe80 && !a.kv_head_major && a.Nk % 64 == 0 && a.Nk >= 192) return launch_attn_pipe80(a, stream);
             return (dma && dma80) ? launch_attn_dma<80>(a, stream) : launch_attn<80>(a, stream);
         }
+        // Stable Diffusion 2.x (5 / 10 / 20 heads of 64).  Key counts that are multiples of 64 from the ring's three tiles on: the
+        // pipelined kernel (PIPE64_DEFAULT: what the A/B of profiles/sd2_notes.md decided); everything else -- the 77 prompt keys,
+        // ragged and small levels -- the register-staged kernel (VALU denominator, as at 160).  SD_ATTN_PIPE64 = 0 | ones | valu
+        // (read per call: A/B inside one process) forces the general kernel or one of the two denominators.
+        case 64: {
+            static const bool no_pipe64 = getenv("SD_ATTN_NO_PIPE") != nullptr;
+            const char* e = getenv("SD_ATTN_PIPE64");
+            const int pick = e ? (e[0] == '0' ? 0 : e[0] == 'o' ? 1 : e[0] == 'v' ? 2 : PIPE64_DEFAULT) : PIPE64_DEFAULT;
+            if (dma && !no_pipe64 && pick && a.Nk % 64 == 0 && a.Nk >= 192)
+                return pick == 1 ? launch_attn_pipe64<true>(a, stream) : launch_attn_pipe64<false>(a, stream);
+            return launch_attn<64>(a, stream);
+        }
         case 160: return launch_attn<160>(a, stream);
-        default: sd_set_error("attention: head dim %d not supported (40, 80, 160)", a.D); return -1;
+        default: sd_set_error("attention: head dim %d not supported (40, 64, 80, 160)", a.D); return -1;
     }
 }

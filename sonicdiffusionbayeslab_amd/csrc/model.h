@@ -6,6 +6,7 @@
 #include "common.h"
 #include "kernels.h"
 
+#include <stdlib.h>
 #include <string.h>
 #include <sys/mman.h>
 
@@ -156,7 +157,7 @@ struct Plan {
     // sd_unet_set_ip_adapter_hw computes on the way (bf16: embeds [UB][E], projection [UB][T * CD], tokens [UB * T][CD], and one
     // block's K_ip | V_ip [UB * T][2 C]).
     int ip = 0;
-    struct IpFold { int at, bt, C; size_t wqT, wo, wkv; };
+    struct IpFold { int at, bt, C; size_t wqT, wo, wkv; int heads; };
     std::vector<IpFold> ip_fold;
     int ip_e = -1, ip_proj = -1, ip_tok = -1, ip_kv = -1;
     // "control" variant (part of the plan key): one OP_RES_ADD after the mid block adds the ControlNet residuals in place to the
@@ -172,9 +173,9 @@ struct Plan {
     std::vector<int> ctx_c;               // C per layer
     int ctx_bf16 = -1;                    // bf16 copy of encoder_hidden_states
     // folded prompt cross-attention (per layer): A^T [UB][heads*80][C] and B [UB][C][heads*80], see transformer()
-    struct Fold { int kv, at, bw, C; size_t wqT, wo; bool perm; int c2 = -1; size_t lnu = NOFF; int c1 = -1; size_t ones = NOFF; };   // perm: Bw in the fused kernel's k order; c2 >= 0: norm2 folded (wqT = the .ln weights, c2 = tensor of the beta terms)
+    struct Fold { int kv, at, bw, C, heads; size_t wqT, wo; bool perm; int c2 = -1; size_t lnu = NOFF; int c1 = -1; size_t ones = NOFF; };   // perm: Bw in the fused kernel's k order; c2 >= 0: norm2 folded (wqT = the .ln weights, c2 = tensor of the beta terms)
     std::vector<Fold> ctx_fold;
-    int ctx_fold_scratch = -1;            // masked K / V expansions [2][UB][heads*80][Cmax]
+    int ctx_fold_scratch = -1;            // masked K / V expansions [3][UB][max over levels of heads*80*C]
     std::map<std::string, int> taps;
     size_t total_bytes = 0;
     // CLIP vision plans (kind 3): preprocessing geometry of the plan's input size and its tap tables (host copy while the plan
@@ -257,6 +258,18 @@ struct sd_unet {
 };
 
 namespace sdhip {
+
+// Head count of the transformer blocks at a resolution level (sd_unet_config::num_heads_per_level; all zeros = num_heads at
+// every level), and of a block by its prefix: down_blocks.i sits on level i, up_blocks.i on level num_levels - 1 - i, the mid
+// block on the last level.
+inline int level_heads(const sd_unet_config& c, int level) {
+    return c.num_heads_per_level[level] > 0 ? c.num_heads_per_level[level] : c.num_heads;
+}
+inline int block_heads(const sd_unet_config& c, const std::string& p) {
+    if (p.compare(0, 12, "down_blocks.") == 0) return level_heads(c, atoi(p.c_str() + 12));
+    if (p.compare(0, 10, "up_blocks.") == 0) return level_heads(c, c.num_levels - 1 - atoi(p.c_str() + 10));
+    return level_heads(c, c.num_levels - 1);
+}
 
 // pack.hip
 void enumerate_params(sd_unet* u);

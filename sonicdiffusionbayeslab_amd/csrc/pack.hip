@@ -599,7 +599,7 @@ struct Packer {
         for (int i = 1; i <= 3; ++i) { f32(t + "norm" + std::to_string(i) + ".weight"); f32(t + "norm" + std::to_string(i) + ".bias"); }
         // The self-attention's softmax scale and the exp -> exp2 factor live in W_q (fp32, before the one rounding every weight
         // gets): S = (c W_q x) . k comes out of the attention kernels' QK^T product in exp2 units (AttnArgs::q_prescaled)
-        const float qs = 1.4426950408889634f / sqrtf((float)(c / u->cfg.num_heads));
+        const float qs = 1.4426950408889634f / sqrtf((float)(c / block_heads(u->cfg, p)));
         if (u->fp8) {
             fp8_same(p + "proj_in.weight", c, c);
             fp8_concat_rows(t + "attn1.qkv.weight", {t + "attn1.to_q.weight", t + "attn1.to_k.weight", t + "attn1.to_v.weight"}, c, qs);

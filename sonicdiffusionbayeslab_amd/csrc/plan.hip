@@ -187,9 +187,9 @@ struct Builder {
         push(o);
         return o.out;
     }
-    int attn(int q, long qoff, long ldq, int kv, long koff, long voff, long ldkv, int nq, int nk, int C) {
+    int attn(int q, long qoff, long ldq, int kv, long koff, long voff, long ldkv, int nq, int nk, int C, int heads) {
         Op o; o.kind = OP_ATTN; o.x1 = q; o.x2 = kv; o.qoff = qoff; o.koff = koff; o.voff = voff;
-        o.ldq = ldq; o.ldk = o.ldv = ldkv; o.ldo = C; o.B = UB; o.heads = u->cfg.num_heads; o.D = C / u->cfg.num_heads;
+        o.ldq = ldq; o.ldk = o.ldv = ldkv; o.ldo = C; o.B = UB; o.heads = heads; o.D = C / heads;
         o.Nq = nq; o.Nk = nk;
         o.out = tensor((size_t)UB * nq * C * 2);
         push(o);
@@ -227,6 +227,7 @@ struct Builder {
     int n_transformers = 0;
     int transformer(const std::string& p, int x, int C, int rh, int rw) {
         const int hw = rh * rw, L = u->cfg.context_len;
+        const int NH = block_heads(u->cfg, p), NP = NH * 80;      // heads of the level the block sits on
         int M = UB * hw;
         const std::string t = p + "transformer_blocks.0.";
         const bool fq = u->fp8;
@@ -243,16 +244,16 @@ struct Builder {
         // token-major Q block, so that the self-attention's LDS-DMA pieces are contiguous (SD_ATTN_HEADMAJOR=0: off)
         static const bool hm_off = (getenv("SD_ATTN_HEADMAJOR") && atoi(getenv("SD_ATTN_HEADMAJOR")) == 0) ||
                                    getenv("SD_ATTN_NO_PIPE") || getenv("SD_ATTN_NO_DMA") || getenv("SD_GEMM_BIG");
-        const bool hm = !hm_off && C / u->cfg.num_heads == 40 && C % 160 == 0 && hw % 128 == 0 && hw >= 256 &&
+        const bool hm = !hm_off && C / NH == 40 && C % 160 == 0 && hw % 128 == 0 && hw >= 256 &&
                         sd_gemm_tile_rows(M, 3 * C) == 128 && pl.ops.back().splitk == 1;
         int a1;
         if (hm) {
             pl.ops.back().hm = 1;
             pl.ops.back().HW = hw;
-            a1 = attn(qkv, 0, C, qkv, (long)M * C, 2l * M * C, C, hw, hw, C);
+            a1 = attn(qkv, 0, C, qkv, (long)M * C, 2l * M * C, C, hw, hw, C, NH);
             pl.ops.back().hm = 1;
         } else {
-            a1 = attn(qkv, 0, 3 * C, qkv, C, 2 * C, 3 * C, hw, hw, C);
+            a1 = attn(qkv, 0, 3 * C, qkv, C, 2 * C, 3 * C, hw, hw, C, NH);
         }
         pl.ops.back().qps = 1;          // W_q of attn1 carries the scale (Packer::transformer)
         int h1 = gemm(a1, C, -1, 0, M, C, t + "attn1.to_out.0.weight", t + "attn1.to_out.0.bias", h0, 0);
@@ -269,7 +270,7 @@ struct Builder {
         // are computed once per sampling run (sd_unet_set_context; 80 key slots per head, 3 of them padding).
         //  * SD_XATTN_FUSED (levels with >= n tokens, default 1024 = 64x64 and 32x32; 0 = never): ONE launch,
         //    Y = h1 + sum_h softmax_77(X A_h) B_h + b_o with the probabilities kept in registers (xattn.hip);
-        //  * SD_XATTN_FOLD (levels with <= n tokens, default 1024): two GEMMs with per-sample weights,
+        //  * SD_XATTN_FOLD (levels with <= n tokens, default 1024; heads * 80 a multiple of 64: 8 or 20 heads, not 5 or 10): two GEMMs with per-sample weights,
         //    P = softmax_77(X A) in the GEMM epilogue and h2 = h1 + P B + b_o;
         //  * otherwise to_q GEMM, the 77-key flash-attention kernel and the to_out GEMM.
         // norm2 (round 5): folded into the first kernel of whichever form runs -- rstd from the row partials attn1.to_out's
@@ -278,9 +279,8 @@ struct Builder {
         static const int fused_min_hw = getenv("SD_XATTN_FUSED") ? atoi(getenv("SD_XATTN_FUSED")) : 1024;
         static const int fold_max_hw = getenv("SD_XATTN_FOLD") ? atoi(getenv("SD_XATTN_FOLD")) : 1024;
         static const bool xln_off = getenv("SD_XATTN_LN") && atoi(getenv("SD_XATTN_LN")) == 0;
-        const int NH = u->cfg.num_heads, NP = NH * 80;
         const int xmode = (fused_min_hw > 0 && hw >= fused_min_hw && sd_xattn_fused_applicable(hw, C, NH, L)) ? 0
-                          : (hw <= fold_max_hw && hw % 128 == 0 && L <= 80) ? 1 : 2;
+                          : (hw <= fold_max_hw && hw % 128 == 0 && L <= 80 && NP % 64 == 0) ? 1 : 2;      // (NP is the second GEMM's K: heads % 4 == 0)
         int rs2 = -1, np2 = 0;
         const long rs2_rows = (long)pl.ops[to_out_op].M;     // (< M when the CFG pair was replicated after attn1.to_out ran)
         // (the set_context plan and the forward plan must agree on every operand it writes: the CFG-pair variant replicates the
@@ -304,7 +304,7 @@ struct Builder {
         int res = h1;
         if (pl.ip) {
             const int at = ctx_ip_tensor((size_t)UB * 32 * C * 2), bt = ctx_ip_tensor((size_t)UB * C * 32 * 2);
-            pl.ip_fold.push_back(Plan::IpFold{at, bt, C, W(t + "attn2.to_q.weight.T"), W(t + "attn2.to_out.0.weight"), W(t + "attn2.kv_ip.weight")});
+            pl.ip_fold.push_back(Plan::IpFold{at, bt, C, W(t + "attn2.to_q.weight.T"), W(t + "attn2.to_out.0.weight"), W(t + "attn2.kv_ip.weight"), NH});
             Op o; o.kind = OP_IP_XATTN; o.x1 = h1; o.wt = at; o.x2 = bt; o.M = M; o.N = C; o.rpb = hw; o.heads = NH;
             o.g = W(t + "norm2.weight"); o.be = W(t + "norm2.bias"); o.eps = 1e-5f;
             o.out = tensor((size_t)M * C * 2); push(o); res = o.out;
@@ -312,7 +312,7 @@ struct Builder {
         int h2;
         if (xmode == 0) {
             int at = ctx_tensor((size_t)UB * NP * C * 2), bw = ctx_tensor((size_t)UB * C * NP * 2);
-            Plan::Fold fd{kv, at, bw, C, W(t + (np2 > 0 ? "attn2.to_q.weight.T.ln" : "attn2.to_q.weight.T")), W(t + "attn2.to_out.0.weight"), true};
+            Plan::Fold fd{kv, at, bw, C, NH, W(t + (np2 > 0 ? "attn2.to_q.weight.T.ln" : "attn2.to_q.weight.T")), W(t + "attn2.to_out.0.weight"), true};
             if (np2 > 0) { fd.c2 = ctx_tensor((size_t)UB * NP * 4); fd.lnu = W(t + "attn2.to_q.lnu"); }
             pl.ctx_fold.push_back(fd);
             Op o; o.kind = OP_XATTN; o.x1 = n2; o.r = res; o.wt = at; o.x2 = bw; o.M = M; o.N = C; o.K = NP; o.rpb = hw;
@@ -321,7 +321,7 @@ struct Builder {
             o.out = tensor((size_t)M * C * 2); push(o); h2 = o.out;
         } else if (xmode == 1) {
             int at = ctx_tensor((size_t)UB * NP * C * 2), bw = ctx_tensor((size_t)UB * C * NP * 2);
-            Plan::Fold fd{kv, at, bw, C, W(t + (np2 > 0 ? "attn2.to_q.weight.T.ln" : "attn2.to_q.weight.T")), W(t + "attn2.to_out.0.weight"), false};
+            Plan::Fold fd{kv, at, bw, C, NH, W(t + (np2 > 0 ? "attn2.to_q.weight.T.ln" : "attn2.to_q.weight.T")), W(t + "attn2.to_out.0.weight"), false};
             if (np2 > 0) {      // c1 = row sums of the ROUNDED centred operand (what is left of the mean term), c2 = the beta term
                 fd.c2 = ctx_tensor((size_t)UB * NP * 4); fd.lnu = W(t + "attn2.to_q.lnu");
                 fd.c1 = ctx_tensor((size_t)UB * NP * 4); fd.ones = W(t + "attn2.to_q.ones");
@@ -338,7 +338,7 @@ struct Builder {
         } else {
             int q2 = np2 > 0 ? gemm_ln(h1, rs2, np2, M, C, C, t + "attn2.to_q.weight", 0)
                              : gemm(n2, C, -1, 0, M, C, t + "attn2.to_q.weight", "", -1, 0);
-            int a2 = attn(q2, 0, C, kv, 0, C, 2 * C, hw, L, C);
+            int a2 = attn(q2, 0, C, kv, 0, C, 2 * C, hw, L, C, NH);
             h2 = gemm(a2, C, -1, 0, M, C, t + "attn2.to_out.0.weight", t + "attn2.to_out.0.bias", res, 0);
         }
         int ff;
@@ -506,7 +506,8 @@ struct Builder {
     }
 
     // CLIPTextTransformer (transformers 4.48.0 modeling_clip.py): token + position embedding,
-    // pre-LN layers with causal self-attention and a quick_gelu MLP, final LayerNorm -> last_hidden_state
+    // pre-LN layers with causal self-attention and a quick_gelu (or, sd_clip_config::hidden_act, exact gelu) MLP, final
+    // LayerNorm -> last_hidden_state
     void build_clip() {
         const sd_clip_config& c = u->clip;
         const int L = c.max_positions, H = c.hidden_size, I = c.intermediate_size, M = UB * L;
@@ -515,7 +516,7 @@ struct Builder {
           o.w = W("text_model.embeddings.token_embedding.weight"); o.g = W("text_model.embeddings.position_embedding.weight");
           o.out = tensor((size_t)M * H * 2); push(o); t = o.out; }
         for (int i = 0; i < c.num_layers; ++i) {
-            t = clip_encoder_layer(clip_layer(i), t, M, L, H, I, c.num_heads, OP_CLIP_ATTN);
+            t = clip_encoder_layer(clip_layer(i), t, M, L, H, I, c.num_heads, OP_CLIP_ATTN, c.hidden_act == SD_ACT_GELU);
             pl.taps["layer" + std::to_string(i)] = t;
         }
         if (pl.rep == REP_TEXT_POOLED) {      // pooled + projected variant (sd_clip_text_embeds): the EOS row, final LayerNorm, text_projection
@@ -567,8 +568,12 @@ struct Builder {
         const int nl = c.num_levels, c0 = c.block_out_channels[0], temb = 4 * c0;
         const int L = c.context_len;
         pl.ctx_bf16 = ctx_tensor((size_t)UB * L * c.cross_attention_dim * 2);
-        // masked K / V expansions used by sd_unet_set_context for the folded cross-attention (sized for the widest level)
-        pl.ctx_fold_scratch = ctx_tensor((size_t)3 * UB * c.num_heads * 80 * c.block_out_channels[nl - 1] * 2);
+        // masked K / V expansions used by sd_unet_set_context for the folded cross-attention: sized for the level with the most
+        // (head, key slot) rows x channels (the mid block sits on the last level)
+        size_t fold_max = 0;
+        for (int i = 0; i < nl; ++i)
+            if (c.attn_levels[i] || i == nl - 1) fold_max = std::max(fold_max, (size_t)level_heads(c, i) * 80 * c.block_out_channels[i]);
+        pl.ctx_fold_scratch = ctx_tensor((size_t)3 * UB * fold_max * 2);
         if (pl.ip) {      // what sd_unet_set_ip_adapter_hw computes on the way to the folded operands (its expansions reuse the scratch above)
             const int T = c.ip_adapter_tokens, CD = c.cross_attention_dim;
             int cmax = 0;

@@ -278,18 +278,30 @@ static int check_unet_config(const sd_unet_config* cfg, const char* who) {
                "%s: in_channels %d (4, or 9 for an inpainting UNet: latents | mask | masked-image latents)", who,
                cfg->in_channels);
     SD_REQUIRE(cfg->out_channels >= 1 && cfg->out_channels <= 4, "%s: out_channels %d", who, cfg->out_channels);
+    {   // num_heads_per_level: all zeros (num_heads everywhere) or a positive count for every level
+        int set = 0;
+        for (int i = 0; i < 8; ++i) {
+            SD_REQUIRE(cfg->num_heads_per_level[i] >= 0 && (i < cfg->num_levels || cfg->num_heads_per_level[i] == 0),
+                       "%s: num_heads_per_level[%d]=%d (%d levels)", who, i, cfg->num_heads_per_level[i], cfg->num_levels);
+            set += cfg->num_heads_per_level[i] > 0;
+        }
+        SD_REQUIRE(set == 0 || set == cfg->num_levels, "%s: num_heads_per_level names %d of %d levels (all zeros, or every level)",
+                   who, set, cfg->num_levels);
+    }
     for (int i = 0; i < cfg->num_levels; ++i) {
         const int c = cfg->block_out_channels[i];
         SD_REQUIRE(c % 64 == 0 && c % cfg->norm_num_groups == 0 && c / cfg->norm_num_groups >= 8,
                    "%s: block_out_channels[%d]=%d must be a multiple of 64 with >= 8 channels per group", who, i, c);
         if (cfg->attn_levels[i]) {
-            const int d = c / cfg->num_heads;
-            SD_REQUIRE(c % cfg->num_heads == 0 && (d == 40 || d == 80 || d == 160),
-                       "%s: head dim %d at level %d not built (40/80/160)", who, d, i);
+            const int nh = level_heads(*cfg, i), d = nh > 0 ? c / nh : 0;
+            SD_REQUIRE(nh > 0 && c % nh == 0 && (d == 40 || d == 64 || d == 80 || d == 160),
+                       "%s: head dim %d at level %d (%d channels, %d heads) not built (40/64/80/160)", who, d, i, c, nh);
         }
     }
-    const int dmid = cfg->block_out_channels[cfg->num_levels - 1] / cfg->num_heads;
-    SD_REQUIRE(dmid == 40 || dmid == 80 || dmid == 160, "%s: mid-block head dim %d not built", who, dmid);
+    const int nhmid = level_heads(*cfg, cfg->num_levels - 1);
+    const int cmid = cfg->block_out_channels[cfg->num_levels - 1], dmid = nhmid > 0 ? cmid / nhmid : 0;
+    SD_REQUIRE(nhmid > 0 && cmid % nhmid == 0 && (dmid == 40 || dmid == 64 || dmid == 80 || dmid == 160),
+               "%s: mid-block head dim %d (%d channels, %d heads) not built (40/64/80/160)", who, dmid, cmid, nhmid);
     SD_REQUIRE(cfg->cross_attention_dim % 64 == 0, "%s: cross_attention_dim must be a multiple of 64", who);
     SD_REQUIRE(cfg->sample_size % (1 << (cfg->num_levels - 1)) == 0, "%s: sample_size not divisible", who);
     SD_REQUIRE(cfg->context_len >= 1, "%s: context_len", who);
@@ -306,9 +318,9 @@ static int check_unet_config(const sd_unet_config* cfg, const char* who) {
                    "%s: ip_adapter_embed_dim %d must be a positive multiple of 64", who, cfg->ip_adapter_embed_dim);
         SD_REQUIRE(cfg->cross_attention_dim <= 1536, "%s: an IP-Adapter needs cross_attention_dim <= 1536 (the token LayerNorm)", who);
         for (int i = 0; i < cfg->num_levels; ++i)
-            SD_REQUIRE(sd_ip_xattn_applicable(cfg->block_out_channels[i], cfg->num_heads, cfg->ip_adapter_tokens),
+            SD_REQUIRE(sd_ip_xattn_applicable(cfg->block_out_channels[i], level_heads(*cfg, i), cfg->ip_adapter_tokens),
                        "%s: an IP-Adapter needs 1, 2, 4 or 8 heads and channels that are a multiple of 32 up to 2048 "
-                       "(level %d: %d channels, %d heads)", who, i, cfg->block_out_channels[i], cfg->num_heads);
+                       "(level %d: %d channels, %d heads)", who, i, cfg->block_out_channels[i], level_heads(*cfg, i));
     }
     return 0;
 }
@@ -404,6 +416,8 @@ extern "C" int sd_clip_create(const sd_clip_config* cfg, sd_unet** out) {
     SD_REQUIRE(cfg->max_positions >= 1 && cfg->max_positions <= 128, "sd_clip_create: max_positions %d", cfg->max_positions);
     SD_REQUIRE(cfg->vocab_size >= 1 && cfg->num_layers >= 1, "sd_clip_create: vocab/layers");
     SD_REQUIRE(fabsf(cfg->layer_norm_eps - 1e-5f) < 1e-9f, "sd_clip_create: layer_norm_eps %g (1e-5 is built)", cfg->layer_norm_eps);
+    SD_REQUIRE(cfg->hidden_act == SD_ACT_QUICK_GELU || cfg->hidden_act == SD_ACT_GELU,
+               "sd_clip_create: hidden_act %d (0 = quick_gelu, 1 = gelu)", cfg->hidden_act);
     sd_unet* u = new_handle(2, nullptr);
     u->clip = *cfg;
     enumerate_params_clip(u);
@@ -644,9 +658,8 @@ extern "C" int sd_unet_set_context_hw(sd_unet* u, void* stream, const float* ehs
     for (size_t i = 0; i < pl.ctx_kv.size(); ++i)
         if ((rc = gemm(cb, M, CD, pl.ctx_w[i], 2 * pl.ctx_c[i], (bf16_t*)(ws + pl.tensors[pl.ctx_kv[i]].off)))) return rc;
     // folded prompt cross-attention: A^T = (scale K)_masked . W_q  and  B = W_o . V_masked^T per sample and layer
-    const int NH = u->cfg.num_heads, NP = NH * 80;
     for (const Plan::Fold& f : pl.ctx_fold) {
-        const int C = f.C, d = C / NH;
+        const int C = f.C, NH = f.heads, NP = NH * 80, d = C / NH;      // (heads of the level the layer sits on)
         const bf16_t* kvp = (const bf16_t*)(ws + pl.tensors[f.kv].off);
         bf16_t* kexp = (bf16_t*)(ws + pl.tensors[pl.ctx_fold_scratch].off);
         bf16_t* vexp = kexp + (size_t)unet_batch * NP * C;
@@ -767,7 +780,7 @@ extern "C" int sd_unet_set_ip_adapter_hw(sd_unet* u, void* stream, const float* 
         a.zero_page = g_zero_page;
         return sd_launch_gemm(a, 0, st);
     };
-    const int T = c.ip_adapter_tokens, E = c.ip_adapter_embed_dim, CD = c.cross_attention_dim, NH = c.num_heads, UB = unet_batch;
+    const int T = c.ip_adapter_tokens, E = c.ip_adapter_embed_dim, CD = c.cross_attention_dim, UB = unet_batch;
     const std::string ipj = "encoder_hid_proj.image_projection_layers.0.";
     // ImageProjection: tokens = LayerNorm(Linear(image_embeds).reshape(UB, T, CD))
     if ((rc = sd_launch_f32_to_bf16(image_embeds, TP(pl.ip_e), (long)UB * E, st))) return rc;
@@ -777,9 +790,8 @@ extern "C" int sd_unet_set_ip_adapter_hw(sd_unet* u, void* stream, const float* 
                                   CD, 1e-5f, st))) return rc;
     // per block: K_ip | V_ip, their per-head expansions over 32 key slots (32 / heads per head, T of them used), and the folds
     //   A [UB][32][C] = (K_ip / sqrt d)_expanded . W_q      Bt [UB][C][32] = ((scale V_ip)_expanded . W_o^T)^T
-    const int SPH = 32 / NH;
     for (const Plan::IpFold& f : pl.ip_fold) {
-        const int C = f.C, d = C / NH;
+        const int C = f.C, NH = f.heads, SPH = 32 / NH, d = C / NH;
         bf16_t* kexp = TP(pl.ctx_fold_scratch);
         bf16_t* vexp = kexp + (size_t)UB * 32 * C;
         bf16_t* tmp = vexp + (size_t)UB * 32 * C;

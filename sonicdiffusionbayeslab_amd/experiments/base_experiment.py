@@ -66,6 +66,9 @@ class BaseMethod(ABC):
             extra["weight_dtype"] = self.config.model.weight_dtype
         if self.config.model.get("time_cond_proj_dim", None) is not None:   # key of this build: shapes a hub name's stand-in
             extra["time_cond_proj_dim"] = int(self.config.model.time_cond_proj_dim)
+        for key in ("unet_arch", "sample_size", "prediction_type"):         # keys of this build: shape a hub name's stand-in ("sd2")
+            if self.config.model.get(key, None) is not None:
+                extra[key] = self.config.model[key]
         self.model = models_registry[model_name].from_pretrained(
             self.config.model.pretrained_model,
             timestamps=self.config.model.get("timestamps", None),

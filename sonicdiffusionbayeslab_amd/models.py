@@ -36,7 +36,8 @@ from .registry import models_registry
 from .schedulers import PNDMConfigStub
 from .unet import CACHE_FULL_AND_STORE, CACHE_OFF, CACHE_SKIP, LATENT_CHANNELS, HipUNet2DConditionModel
 from .vae import HipVaeDecoder, HipVaeEncoder, VaeConfig, load_vae_state_dict, make_synthetic_vae_state_dict
-from .weights import UNetConfig, load_scheduler_config, load_unet_config, load_unet_state_dict, make_synthetic_state_dict
+from .weights import (SD2_CONTEXT_DIM, SD2_HEADS, UNetConfig, check_projection_layout, load_scheduler_config, load_unet_config,
+                      load_unet_state_dict, make_synthetic_state_dict, sd2_unet_config)
 
 
 @dataclass
@@ -172,6 +173,14 @@ class StableDiffusionModel:
         # time_cond_proj_dim (YAML model.time_cond_proj_dim): shapes the synthetic stand-in of a hub name; a local checkpoint's
         # unet/config.json decides, and a different value is an error
         tcond = kwargs.pop("time_cond_proj_dim", None)
+        # unet_arch (YAML model.unet_arch: "sd15" | "sd2"), with sample_size and prediction_type (YAML model.sample_size /
+        # model.prediction_type): shape the stand-in of a hub name the same way -- "sd2" is the Stable Diffusion 2.x UNet
+        # (weights.sd2_unet_config); a local checkpoint's own files decide, and a conflicting key is an error
+        arch = kwargs.pop("unet_arch", None)
+        ssize = kwargs.pop("sample_size", None)
+        ptype = kwargs.pop("prediction_type", None)
+        if arch not in (None, "sd15", "sd2"):
+            raise ValueError(f"unet_arch={arch!r}: 'sd15' or 'sd2'")
         if os.path.isdir(path):
             has_clip = all(os.path.exists(os.path.join(path, *p)) for p in (("tokenizer", "vocab.json"),
                                                                             ("tokenizer", "merges.txt"),
@@ -181,9 +190,32 @@ class StableDiffusionModel:
             have = ucfg.time_cond_proj_dim if ucfg is not None else None
             if tcond is not None and tcond != have:
                 raise ValueError(f"time_cond_proj_dim={tcond} conflicts with the checkpoint {path!r} (its UNet has {have})")
-            return cls(unet_config=ucfg, state_dict=load_unet_state_dict(path), source=f"local:{path}",
-                       clip_dir=path if has_clip else None, **kwargs)
+            eff = ucfg or UNetConfig()
+            is_sd2 = eff.heads_per_level == SD2_HEADS and eff.cross_attention_dim == SD2_CONTEXT_DIM
+            if arch is not None and (arch == "sd2") != is_sd2:
+                raise ValueError(f"unet_arch={arch!r} conflicts with the checkpoint {path!r} (heads {eff.heads_per_level}, "
+                                 f"cross_attention_dim {eff.cross_attention_dim})")
+            if ssize is not None and int(ssize) != eff.sample_size:
+                raise ValueError(f"sample_size={ssize} conflicts with the checkpoint {path!r} (its UNet has {eff.sample_size})")
+            sched_cfg = getattr(kwargs["scheduler"], "config", None)          # (a caller's scheduler: dict- or attribute-style config)
+            have_p = (sched_cfg.get("prediction_type", "epsilon") if hasattr(sched_cfg, "get")
+                      else getattr(sched_cfg, "prediction_type", "epsilon"))
+            if ptype is not None and ptype != have_p:
+                raise ValueError(f"prediction_type={ptype!r} conflicts with the checkpoint {path!r} (its scheduler has {have_p!r})")
+            sd = load_unet_state_dict(path)
+            check_projection_layout(eff, sd)
+            return cls(unet_config=ucfg, state_dict=sd, source=f"local:{path}", clip_dir=path if has_clip else None, **kwargs)
         seed = int(os.environ.get("SD_AMD_WEIGHTS_SEED", "1234"))
+        if arch == "sd2":
+            if tcond is not None:
+                raise ValueError("unet_arch='sd2' with time_cond_proj_dim: no LCM-distilled Stable Diffusion 2.x stand-in is built")
+            kwargs.setdefault("unet_config", sd2_unet_config(sample_size=96 if ssize is None else int(ssize)))
+        elif ssize is not None:
+            kwargs.setdefault("unet_config", UNetConfig(sample_size=int(ssize), time_cond_proj_dim=tcond))
+            tcond = None
+        if ptype is not None:
+            from .schedulers import SD15_SCHEDULER_CONFIG
+            kwargs.setdefault("scheduler", PNDMConfigStub({**SD15_SCHEDULER_CONFIG, "prediction_type": str(ptype)}))
         if tcond is not None:
             kwargs.setdefault("unet_config", UNetConfig(time_cond_proj_dim=int(tcond)))
         return cls(weights_seed=seed, source=f"synthetic(seed={seed}) for {pretrained_model_name_or_path}", **kwargs)

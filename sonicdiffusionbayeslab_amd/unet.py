@@ -21,8 +21,8 @@ CACHE_OFF, CACHE_FULL_AND_STORE, CACHE_SKIP = 0, 1, 2
 LATENT_CHANNELS = 4         # channels of the latents crossing the ABI (an inpainting UNet's other 5 are set per call)
 
 
-def _c_config(cfg: UNetConfig, weight_dtype: str = "bf16", fp8_act_scales=(0.0, 0.0)) -> _lib.SdUnetConfig:
-    c = _lib.SdUnetConfig()
+def _c_config(cfg: UNetConfig, weight_dtype: str = "bf16", fp8_act_scales=(0.0, 0.0)) -> _lib.SdUnetConfigFull:
+    c = _lib.SdUnetConfigFull()
     if weight_dtype not in _lib.DTYPES:
         raise ValueError(f"weight_dtype {weight_dtype!r}: one of {sorted(_lib.DTYPES)}")
     c.weight_dtype = _lib.DTYPES[weight_dtype]
@@ -37,6 +37,8 @@ def _c_config(cfg: UNetConfig, weight_dtype: str = "bf16", fp8_act_scales=(0.0, 
     c.norm_num_groups, c.norm_eps, c.context_len = cfg.norm_num_groups, cfg.norm_eps, cfg.context_len
     c.time_cond_proj_dim = cfg.time_cond_proj_dim or 0
     c.ip_adapter_tokens, c.ip_adapter_embed_dim = cfg.ip_adapter_tokens or 0, cfg.ip_adapter_embed_dim or 0
+    for i, v in enumerate(cfg.num_heads_per_level or ()):       # (None: all zeros = num_heads at every level)
+        c.num_heads_per_level[i] = int(v)
     return c
 
 

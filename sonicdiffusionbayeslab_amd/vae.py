@@ -151,8 +151,8 @@ def load_vae_state_dict(model_dir: str) -> Dict[str, torch.Tensor]:
     raise FileNotFoundError(f"no local VAE weights under {model_dir!r}")
 
 
-def _c_config(cfg: VaeConfig) -> _lib.SdUnetConfig:
-    c = _lib.SdUnetConfig()
+def _c_config(cfg: VaeConfig) -> _lib.SdUnetConfigFull:
+    c = _lib.SdUnetConfigFull()
     c.sample_size, c.in_channels, c.out_channels = cfg.sample_size, cfg.in_channels, cfg.out_channels
     c.num_levels = len(cfg.block_out_channels)
     for i, v in enumerate(cfg.block_out_channels):

@@ -41,8 +41,28 @@ class UNetConfig:
     # number of image tokens per sample: IP_ADAPTER_TOKENS with an adapter, else None.  InitVars like the field above.
     ip_adapter_embed_dim: InitVar[Optional[int]] = None
     ip_adapter_tokens: InitVar[Optional[int]] = None
+    # Stable Diffusion 2.x.  ``num_heads_per_level``: the head COUNT of the transformer blocks per resolution level
+    # ((5, 10, 20, 20): head dim 64 everywhere; diffusers' ``attention_head_dim`` list), None = ``num_heads`` at every level.
+    # The mid block uses the last level's count, the up blocks mirror the down blocks (``heads_per_level``).
+    # ``use_linear_projection``: ``proj_in`` / ``proj_out`` are Linear layers, weights [C, C] instead of [C, C, 1, 1]; in the
+    # token-major layout both are the same GEMM, so only the shape a state dict is checked against differs.  InitVars like the
+    # fields above.
+    num_heads_per_level: InitVar[Optional[Tuple[int, ...]]] = None
+    use_linear_projection: InitVar[bool] = False
 
-    def __post_init__(self, time_cond_proj_dim, ip_adapter_embed_dim, ip_adapter_tokens):
+    def __post_init__(self, time_cond_proj_dim, ip_adapter_embed_dim, ip_adapter_tokens, num_heads_per_level=None,
+                      use_linear_projection=False):
+        hp = num_heads_per_level
+        if hp is not None:
+            hp = tuple(hp)
+            if len(hp) != len(self.block_out_channels) or any(isinstance(v, bool) or int(v) != v or int(v) <= 0 for v in hp):
+                raise ValueError(f"num_heads_per_level={num_heads_per_level!r}: one positive integer per level "
+                                 f"({len(self.block_out_channels)}) or None")
+            hp = tuple(int(v) for v in hp)
+        self.num_heads_per_level = hp
+        if not isinstance(use_linear_projection, bool):
+            raise ValueError(f"use_linear_projection={use_linear_projection!r}: a bool")
+        self.use_linear_projection = use_linear_projection
         if time_cond_proj_dim is not None and (isinstance(time_cond_proj_dim, bool) or int(time_cond_proj_dim) <= 0
                                                or int(time_cond_proj_dim) != time_cond_proj_dim):
             raise ValueError(f"time_cond_proj_dim={time_cond_proj_dim!r}: a positive integer or None")
@@ -63,11 +83,42 @@ class UNetConfig:
     def __eq__(self, other):            # (the generated one compares fields only)
         if other.__class__ is not self.__class__:
             return NotImplemented
-        return (_shared_fields(self) == _shared_fields(other) and self.time_cond_proj_dim == other.time_cond_proj_dim
+        a, b = _shared_fields(self), _shared_fields(other)
+        a.pop("num_heads"), b.pop("num_heads")          # (compared through heads_per_level)
+        return (a == b and self.heads_per_level == other.heads_per_level
+                and self.use_linear_projection == other.use_linear_projection
+                and self.time_cond_proj_dim == other.time_cond_proj_dim
                 and self.ip_adapter_embed_dim == other.ip_adapter_embed_dim)
+
+    @property
+    def heads_per_level(self) -> Tuple[int, ...]:
+        """The head count of every level: ``num_heads_per_level``, or ``num_heads`` at each."""
+        return self.num_heads_per_level or (self.num_heads,) * len(self.block_out_channels)
 
 
 IP_ADAPTER_TOKENS = 4
+
+# Stable Diffusion 2.x (stable-diffusion-2-base / -2 / -2-1-base / -2-1 / -2-inpainting): head dim 64 at every level, the
+# OpenCLIP ViT-H text tower's 1024-wide context, Linear proj_in / proj_out
+SD2_HEADS = (5, 10, 20, 20)
+SD2_CONTEXT_DIM = 1024
+
+
+def sd2_unet_config(sample_size: int = 96, in_channels: int = 4) -> "UNetConfig":
+    """The UNet of the Stable Diffusion 2.x family (``sample_size`` 96 for the 768-pixel checkpoints, 64 for the ``-base``
+    ones; ``in_channels`` 9 for ``-2-inpainting``)."""
+    return UNetConfig(sample_size=int(sample_size), in_channels=int(in_channels), cross_attention_dim=SD2_CONTEXT_DIM,
+                      num_heads=SD2_HEADS[0], num_heads_per_level=SD2_HEADS, use_linear_projection=True)
+
+
+def check_projection_layout(cfg: "UNetConfig", sd) -> None:
+    """A checkpoint's ``use_linear_projection`` and the rank of its ``proj_in`` / ``proj_out`` weights must agree ([C, C] for
+    Linear, [C, C, 1, 1] for the 1x1 conv): one whose config and weights disagree is refused by name, not reshaped."""
+    want = 2 if cfg.use_linear_projection else 4
+    for name, v in sd.items():
+        if name.endswith(("proj_in.weight", "proj_out.weight")) and v.dim() != want:
+            raise NotImplementedError(f"unet config use_linear_projection={cfg.use_linear_projection!r}, but {name} has shape "
+                                      f"{tuple(v.shape)}: the checkpoint's config and weights disagree")
 IP_PROJ = "encoder_hid_proj.image_projection_layers.0."       # diffusers: unet.encoder_hid_proj of one loaded adapter
 
 
@@ -91,7 +142,8 @@ def param_shapes(cfg: UNetConfig) -> List[Tuple[str, Tuple[int, ...]]]:
     def transformer(p, c):
         ctx = cfg.cross_attention_dim
         add(p + "norm.weight", (c,)); add(p + "norm.bias", (c,))
-        add(p + "proj_in.weight", (c, c, 1, 1)); add(p + "proj_in.bias", (c,))
+        proj = (c, c) if cfg.use_linear_projection else (c, c, 1, 1)
+        add(p + "proj_in.weight", proj); add(p + "proj_in.bias", (c,))
         t = p + "transformer_blocks.0."
         for i in (1, 2, 3):
             add(t + f"norm{i}.weight", (c,)); add(t + f"norm{i}.bias", (c,))
@@ -103,7 +155,7 @@ def param_shapes(cfg: UNetConfig) -> List[Tuple[str, Tuple[int, ...]]]:
             add(t + "attn2.processor.to_k_ip.0.weight", (c, ctx)); add(t + "attn2.processor.to_v_ip.0.weight", (c, ctx))
         add(t + "ff.net.0.proj.weight", (8 * c, c)); add(t + "ff.net.0.proj.bias", (8 * c,))
         add(t + "ff.net.2.weight", (c, 4 * c)); add(t + "ff.net.2.bias", (c,))
-        add(p + "proj_out.weight", (c, c, 1, 1)); add(p + "proj_out.bias", (c,))
+        add(p + "proj_out.weight", proj); add(p + "proj_out.bias", (c,))
 
     add("time_embedding.linear_1.weight", (temb, c0)); add("time_embedding.linear_1.bias", (temb,))
     if cfg.time_cond_proj_dim is not None:
@@ -276,8 +328,8 @@ def load_ip_adapter_state_dict(path: str, cfg: UNetConfig):
 
 # ---- ControlNet (diffusers ControlNetModel) ----------------------------------------------------------------
 CONTROLNET_EMBED_CHANNELS = (16, 32, 96, 256)        # conditioning_embedding_out_channels of the published SD-1.5 ControlNets
-CONTROLNET_SHARED_FIELDS = ("block_out_channels", "layers_per_block", "attn_levels", "cross_attention_dim", "num_heads",
-                            "norm_num_groups", "norm_eps", "context_len")
+CONTROLNET_SHARED_FIELDS = ("block_out_channels", "layers_per_block", "attn_levels", "cross_attention_dim", "heads_per_level",
+                            "norm_num_groups", "norm_eps", "context_len")       # heads_per_level: num_heads where no level differs
 CONTROLNET_SEED_OFFSET = 15485863
 CONTROLNET_SYNTHETIC_GAIN = 0.5                      # make_synthetic_controlnet_state_dict: see tests/test_controlnet_cpu.py
 
@@ -445,7 +497,8 @@ def make_synthetic_state_dict(cfg: UNetConfig, seed: int = 1234) -> Dict[str, to
     N(0, 0.1^2) (non-trivial affine so parity tests exercise it).  Rounding to bf16 here means
     the CPU oracle and the HIP path consume bit-identical parameters.
 
-    The values do not depend on ``sample_size`` (no parameter shape does); generating 0.86 G Gaussians takes ~10 s, so the
+    The values do not depend on ``sample_size`` or on the head counts (no parameter shape does), and a
+    ``use_linear_projection`` config draws the same numbers into [C, C] ``proj_in`` / ``proj_out``; generating 0.86 G Gaussians takes ~10 s, so the
     result is cached per (architecture, seed) for the life of the process and every call returns a NEW dict over the same
     read-only tensors (callers replace entries -- LoRA fusion, tests -- and never write into a tensor).
 
@@ -453,12 +506,13 @@ def make_synthetic_state_dict(cfg: UNetConfig, seed: int = 1234) -> Dict[str, to
     ``COND_PROJ_SEED_OFFSET + seed``), so every other parameter is bit-identical to the plain config's.
     """
     key = (cfg.in_channels, cfg.out_channels, tuple(cfg.block_out_channels), cfg.layers_per_block, tuple(cfg.attn_levels),
-           cfg.cross_attention_dim, int(seed))
+           cfg.cross_attention_dim, bool(cfg.use_linear_projection), int(seed))
     if key in _SYNTHETIC_CACHE:
         return _with_cond_proj(dict(_SYNTHETIC_CACHE[key]), cfg, seed)
     g = torch.Generator().manual_seed(seed)
     sd: Dict[str, torch.Tensor] = {}
-    for name, shape in param_shapes(UNetConfig(**_shared_fields(cfg))):     # (without cond_proj)
+    plain = UNetConfig(**_shared_fields(cfg), use_linear_projection=cfg.use_linear_projection)     # (without cond_proj)
+    for name, shape in param_shapes(plain):
         leaf = name.rsplit(".", 2)[-2]
         is_norm = leaf.startswith("norm") or leaf == "conv_norm_out"
         if name.endswith(".bias"):
@@ -511,8 +565,9 @@ def load_scheduler_config(model_dir: str) -> dict:
 def load_unet_config(model_dir: str) -> "UNetConfig | None":
     """``<dir>/unet/config.json`` of a LOCAL diffusers checkpoint -> ``UNetConfig`` (None if the file is absent: the
     SD-1.5 defaults then apply).  Only the keys this build implements are read; a checkpoint that needs anything else
-    (another block type, ``use_linear_projection``, per-level head counts that are not ``attention_head_dim`` heads
-    at every level, an activation other than silu) is refused here rather than mis-run."""
+    (another block type, class or added embeddings, several transformer blocks per layer, an activation other than silu)
+    is refused here rather than mis-run.  Stable Diffusion 2.x configs (per-level head counts, ``use_linear_projection``,
+    ``upcast_attention``) are read."""
     import json
     for cand in (os.path.join(model_dir, "unet", "config.json"), os.path.join(model_dir, "config.json")):
         if os.path.isfile(cand):
@@ -537,26 +592,46 @@ def read_unet_config(c: dict) -> UNetConfig:
     attn = tuple(known[d] for d in down)
     if [u == "CrossAttnUpBlock2D" for u in up] != list(reversed(attn)):
         raise NotImplementedError(f"up_block_types {up} do not mirror down_block_types {down}")
-    heads = c.get("attention_head_dim", 8)          # SD-1.5 quirk: this key holds the NUMBER of heads
+    # diffusers' rule: ``num_attention_heads`` wins where it is present and not null; otherwise ``attention_head_dim`` holds
+    # the NUMBER of heads (SD-1.5 quirk), an int or one entry per level (SD 2.x: [5, 10, 20, 20])
+    heads = c.get("num_attention_heads", None)
+    hkey = "num_attention_heads"
+    if heads is None:
+        heads, hkey = c.get("attention_head_dim", 8), "attention_head_dim"
+    per_level = None
     if isinstance(heads, (list, tuple)):
-        if len(set(heads)) != 1:
-            raise NotImplementedError("per-level head counts are not built")
+        if len(heads) != len(down) or any(isinstance(v, bool) or not isinstance(v, int) or v <= 0 for v in heads):
+            raise NotImplementedError(f"unet config {hkey}={heads!r}: one positive integer per level ({len(down)}) or an integer")
+        per_level = tuple(heads) if len(set(heads)) != 1 else None
         heads = heads[0]
+    elif isinstance(heads, bool) or not isinstance(heads, int) or heads <= 0:
+        raise NotImplementedError(f"unet config {hkey}={heads!r}: a positive integer or one per level")
+    tpb = c.get("transformer_layers_per_block", 1)
+    if tpb != 1 and not (isinstance(tpb, (list, tuple)) and all(v == 1 for v in tpb)):
+        raise NotImplementedError(f"unet config transformer_layers_per_block={tpb!r}: one transformer block per layer is built")
+    if c.get("num_class_embeds", None) is not None:
+        raise NotImplementedError(f"unet config num_class_embeds={c['num_class_embeds']!r}: class conditioning is not built")
+    for key in ("use_linear_projection", "upcast_attention"):
+        if not isinstance(c.get(key, False), bool):
+            raise NotImplementedError(f"unet config {key}={c[key]!r}: true or false")
     tcond = c.get("time_cond_proj_dim", None)
     if tcond is not None and (isinstance(tcond, bool) or not isinstance(tcond, int) or tcond <= 0):
         raise NotImplementedError(f"unet config time_cond_proj_dim={tcond!r}: a positive integer (LCM-distilled) or null")
-    for key, want in (("use_linear_projection", False), ("act_fn", "silu"), ("flip_sin_to_cos", True), ("freq_shift", 0),
+    # ``upcast_attention`` (SD 2.1) is accepted and changes nothing: upstream's flag computes the scores in fp32 because fp16
+    # scores overflow; here the scores ALWAYS accumulate in fp32 from bf16 operands and the softmax is fp32
+    for key, want in (("act_fn", "silu"), ("flip_sin_to_cos", True), ("freq_shift", 0),
                       ("class_embed_type", None), ("addition_embed_type", None),
-                      ("dual_cross_attention", False), ("only_cross_attention", False), ("upcast_attention", False)):
+                      ("dual_cross_attention", False), ("only_cross_attention", False)):
         if c.get(key, want) != want:
-            raise NotImplementedError(f"unet config {key}={c[key]!r}: this build implements {want!r} (SD-1.5)")
+            raise NotImplementedError(f"unet config {key}={c[key]!r}: this build implements {want!r}")
     return UNetConfig(sample_size=int(c.get("sample_size", 64)), in_channels=int(c.get("in_channels", 4)),
                       out_channels=int(c.get("out_channels", 4)),
                       block_out_channels=tuple(int(v) for v in c.get("block_out_channels", (320, 640, 1280, 1280))),
                       layers_per_block=int(c.get("layers_per_block", 2)), attn_levels=attn,
                       cross_attention_dim=int(c.get("cross_attention_dim", 768)), num_heads=int(heads),
                       norm_num_groups=int(c.get("norm_num_groups", 32)), norm_eps=float(c.get("norm_eps", 1e-5)),
-                      time_cond_proj_dim=tcond)
+                      time_cond_proj_dim=tcond, num_heads_per_level=per_level,
+                      use_linear_projection=bool(c.get("use_linear_projection", False)))
 
 
 def load_unet_state_dict(model_dir: str) -> Dict[str, torch.Tensor]:
