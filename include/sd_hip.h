@@ -330,6 +330,48 @@ int sd_clip_vision_encode(sd_clip_vision* v, void* stream, const unsigned char* 
                           float* image_embeds, void* workspace, long long workspace_bytes);
 int sd_clip_score(void* stream, const float* image_embeds, const float* text_embeds, int batch, int dim, float* raw,
                   float* score);
+/* ---- ImageReward (reference src/metrics/metrics.py:44-95, quality_metrics.image_reward: the ImageReward-v1.0 reward model) ----
+ * A kind-6 sd_unet handle: BLIP's ViT (timm layout: fused attn.qkv, a patch-embedding bias, no pre-LayerNorm, the final `norm`
+ * over all tokens, exact gelu), BLIP's BERT text encoder (post-LN layers: masked self-attention, cross-attention over the image
+ * tokens, gelu MLP) and the reward head (five Linears with no activation between them, folded into one vector at finalize).
+ * Parameters are enumerated / loaded / finalised through the sd_unet_* calls under these names:
+ *   visual_encoder.{cls_token [H], pos_embed [tokens, H], patch_embed.proj.{weight,bias}, blocks.N.{norm1,attn.qkv,attn.proj,
+ *   norm2,mlp.fc1,mlp.fc2}.{weight,bias}, norm.{weight,bias}};
+ *   text_encoder.embeddings.{word_embeddings,position_embeddings}.weight, text_encoder.embeddings.LayerNorm.*,
+ *   text_encoder.encoder.layer.N.{attention.self.{query,key,value}, attention.output.{dense,LayerNorm},
+ *   crossattention.self.{query,key,value}, crossattention.output.{dense,LayerNorm}, intermediate.dense,
+ *   output.{dense,LayerNorm}}.*;  mlp.layers.{0,2,4,6,7}.{weight,bias} (hidden -> 1024 -> 128 -> 64 -> 16 -> 1).
+ * sd_image_reward_score: device uint8 images [B,3,h,w] (any size; CLIP preprocessing to image_size), device int32 ids and key
+ * mask [B, L] (1 <= L <= max_text_len; mask 1 = token, 0 = padding; every row needs a valid key: the call copies the mask to
+ * the host to check, which synchronises the stream) -> device fp32 rewards [B] = (head(last_hidden_state[:, 0]) - mean) / std
+ * and, when features is not NULL, the fp32 class-token rows [B, hidden_size].  One plan per (B, L, h, w);
+ * sd_image_reward_workspace_bytes sizes the L = max_text_len plan. */
+typedef struct sd_image_reward_config {
+    int vision_hidden_size;        /* 1024 (ViT-L/16); also the text encoder's encoder_width */
+    int vision_num_layers;         /* 24 */
+    int vision_num_heads;          /* 16 (head dim 64) */
+    int vision_intermediate_size;  /* 4096 */
+    int image_size;                /* 224 */
+    int patch_size;                /* 16 */
+    float vision_layer_norm_eps;   /* 1e-6 */
+    int vocab_size;                /* 30524 */
+    int hidden_size;               /* 768 */
+    int num_layers;                /* 12 */
+    int num_heads;                 /* 12 (head dim 64) */
+    int intermediate_size;         /* 3072 */
+    int max_positions;             /* 512 */
+    float layer_norm_eps;          /* 1e-12 */
+    int hidden_act;                /* SD_ACT_GELU only */
+    int position_embedding_absolute; /* 1 only */
+    int max_text_len;              /* 35; at most 64 */
+    float reward_mean, reward_std; /* 0.16717362830052426, 1.0333394966054072 */
+} sd_image_reward_config;
+typedef struct sd_unet sd_image_reward;
+int sd_image_reward_create(const sd_image_reward_config* cfg, sd_image_reward** out);
+long long sd_image_reward_workspace_bytes(sd_image_reward* m, int batch, int height, int width);
+int sd_image_reward_score(sd_image_reward* m, void* stream, const unsigned char* images, const int* input_ids,
+                          const int* attention_mask, int batch, int text_len, int height, int width, float* rewards,
+                          float* features_or_null, void* workspace, long long workspace_bytes);
 /* Host only: Pillow's bicubic tap table (precompute_coeffs + normalize_coeffs_8bpc, 22 fractional bits) for a resize of
  * in_size -> out_size, output positions [first, first + count).  Returns the tap stride ksize; with non-NULL arrays also
  * writes xmin[count], xcnt[count] and coeffs[count][ksize]. */
@@ -543,6 +585,17 @@ int sd_op_attention_headmajor(void* stream, const void* Q, long long ldq, const 
 int sd_op_clip_attention(void* stream, const void* qkv, void* out, int B, int L, int H, int heads);
 /* non-causal ViT self-attention on the fused projection output qkv [B * L][3 H] -> out [B * L][H]; head dim 64, L <= 320 */
 int sd_op_vit_attention(void* stream, const void* qkv, void* out, int B, int L, int H, int heads);
+/* masked attention of a short query block (the BLIP text encoder's self- and cross-attention), head dim 64: q [B * Lq][ldq],
+ * k and v [B * Lk][ldkv] (bf16; each pointer at its own column offset, 16-byte aligned, pitches multiples of 8), key mask int32
+ * [B][Lk] or NULL (all valid) -> out [B * Lq][ldo]; 1 <= Lq <= 64, 1 <= Lk <= 320.  A masked key is excluded by select: whatever
+ * finite value its K / V rows hold does not reach the output.  Copies the mask to the host and refuses a sample without a valid
+ * key (synchronises the stream). */
+int sd_op_bert_attention(void* stream, const void* q, long long ldq, const void* k, const void* v, long long ldkv,
+                         const int* mask, void* out, long long ldo, int B, int heads, int Lq, int Lk);
+/* rewards[b] = (w . x_b + bias[0] - mean) / std over the fp32 of the bf16 row hidden[b * row_stride .. + H); features
+ * (or NULL) fp32 [B][H] = x_b */
+int sd_op_reward_head(void* stream, const void* hidden, long long row_stride, const float* w, const float* bias, float mean,
+                      float std, int B, int H, float* rewards, float* features);
 /* the CLIP preprocessing of sd_clip_vision_encode on its own: uint8 [B][3][H][W] -> uint8 crop [B][3][S][S] and bf16 patch
  * rows [B (S/P)^2][Kp], Kp = 3 P^2 rounded up to a multiple of 64 (zero columns past 3 P^2).  Synchronises the stream. */
 int sd_op_clip_preprocess(void* stream, const unsigned char* images, int B, int H, int W, int S, int P, unsigned char* crop,

@@ -65,6 +65,17 @@ class SdClipVisionConfig(C.Structure):
     ]
 
 
+class SdImageRewardConfig(C.Structure):
+    _fields_ = [
+        ("vision_hidden_size", C.c_int), ("vision_num_layers", C.c_int), ("vision_num_heads", C.c_int),
+        ("vision_intermediate_size", C.c_int), ("image_size", C.c_int), ("patch_size", C.c_int),
+        ("vision_layer_norm_eps", C.c_float),
+        ("vocab_size", C.c_int), ("hidden_size", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int),
+        ("intermediate_size", C.c_int), ("max_positions", C.c_int), ("layer_norm_eps", C.c_float), ("hidden_act", C.c_int),
+        ("position_embedding_absolute", C.c_int), ("max_text_len", C.c_int), ("reward_mean", C.c_float), ("reward_std", C.c_float),
+    ]
+
+
 class SdHipError(RuntimeError):
     pass
 
@@ -116,6 +127,11 @@ _SIGS = {
     "sd_clip_vision_workspace_bytes": (_ll, [_vp, _i, _i, _i]),
     "sd_clip_vision_encode": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _ll]),
     "sd_clip_score": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "sd_image_reward_create": (_i, [C.POINTER(SdImageRewardConfig), C.POINTER(_vp)]),
+    "sd_image_reward_workspace_bytes": (_ll, [_vp, _i, _i, _i]),
+    "sd_image_reward_score": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _ll]),
+    "sd_op_bert_attention": (_i, [_vp, _vp, _ll, _vp, _vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i]),
+    "sd_op_reward_head": (_i, [_vp, _vp, _ll, _vp, _vp, _f, _f, _i, _i, _vp, _vp]),
     "sd_clip_resize_taps": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
     "sd_op_vit_attention": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
     "sd_op_clip_preprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -245,6 +245,17 @@ int sd_launch_vit_attention(const bf16_t* qkv, bf16_t* out, int B, int L, int H,
 int sd_launch_pool_rows(const bf16_t* src, const int* ids, int B, int L, int H, int eos_id, bf16_t* dst, hipStream_t stream);
 int sd_launch_clip_score(const float* img, const float* txt, int B, int P, float* raw, float* score, hipStream_t stream);
 
+// bert.hip: the BLIP text encoder's attention and the ImageReward head
+// masked attention of a short query block, head dim 64: q [B * Lq][ldq], k / v [B * Lk][ldkv] (pointers at their column
+// offsets), key mask int32 [B][Lk] or null, 1 <= Lq <= 64, 1 <= Lk <= 320 -> out [B * Lq][ldo]
+int sd_bert_attention_check(int B, int Lq, int Lk, int heads);
+int sd_bert_mask_check(const int* host_mask, int B, int Lk);      // a HOST copy of the mask: every sample has a valid key
+int sd_launch_bert_attention(const bf16_t* q, long ldq, const bf16_t* k, const bf16_t* v, long ldkv, const int* mask, bf16_t* out,
+                             long ldo, int B, int heads, int Lq, int Lk, hipStream_t stream);
+// rewards[b] = (w . x_b + wb[0] - mean) / std over the fp32 of row hidden[b * row_stride]; features (optional) [B][H] = x_b
+int sd_launch_reward_head(const bf16_t* hidden, long row_stride, const float* w, const float* wb, float mean, float stdv, int B,
+                          int H, float* rewards, float* features, hipStream_t stream);
+
 // conv_in: NCHW fp32 latents [Bsrc,4,H,W] (batch index taken modulo Bsrc: CFG duplication is
 // fused) -> NHWC bf16 [B,H,W,Cout]
 int sd_launch_conv_in(const float* x, int Bsrc, const float* Wt /*[Cin*9][Cout] fp32*/, const float* bias,

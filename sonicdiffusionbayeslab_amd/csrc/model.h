@@ -44,7 +44,8 @@ struct Wrap {  // one DeepCache-wrapped module enclosing an op
 
 enum OpKind { OP_SINUSOID, OP_GEMV, OP_CONV_IN, OP_GN, OP_CONV3, OP_GEMM, OP_LN, OP_ATTN, OP_CONV_OUT, OP_SOFTMAX, OP_PQCONV,
               OP_CLIP_EMBED, OP_CLIP_ATTN, OP_QGELU, OP_TO_F32, OP_XATTN, OP_REPLICATE,
-              OP_VIT_PREP, OP_VIT_EMBED, OP_VIT_ATTN, OP_POOL, OP_CONV_IN_IMG, OP_ENC_OUT, OP_IP_XATTN, OP_RES_ADD };
+              OP_VIT_PREP, OP_VIT_EMBED, OP_VIT_ATTN, OP_POOL, OP_CONV_IN_IMG, OP_ENC_OUT, OP_IP_XATTN, OP_RES_ADD,
+              OP_BERT_ATTN, OP_REWARD_HEAD };
 
 constexpr int REP_TEXT_POOLED = 2;       // Plan::rep of a CLIP text handle's sd_clip_text_embeds plan
 
@@ -61,6 +62,7 @@ struct Op {
     long ldq = 0, ldk = 0, ldv = 0, ldo = 0, qoff = 0, koff = 0, voff = 0;
     int silu_in = 0, splitk = 1;
     int pool_by_ids = 0;          // OP_POOL: the row is the EOS position of the call's token ids (0: row 0, the class token)
+    int key_mask = 0;             // OP_BERT_ATTN: the keys carry the call's attention mask (self-attention; 0: all valid)
     // split-K producer + single-launch GroupNorm as ONE reduce (fuse_deferred_reduce): the producer (CONV3 / GEMM) sets `defer`
     // and launches no splitk_reduce_kernel; the GroupNorm reads the producer's slabs (slab_t, slab_k of them) with its bias /
     // time-embedding row / residual and writes the producer's output tensor on the way (GroupNormArgs::slab)
@@ -189,11 +191,18 @@ struct Plan {
 
 struct sd_unet {
     // 0 = UNet2DConditionModel, 1 = AutoencoderKL decoder, 2 = CLIP text encoder, 3 = CLIP vision tower, 4 = AutoencoderKL encoder,
-    // 5 = ControlNetModel (the UNet's time embedding, conv_in, down path and mid block + the zero convs)
+    // 5 = ControlNetModel (the UNet's time embedding, conv_in, down path and mid block + the zero convs),
+    // 6 = ImageReward (BLIP ViT + BLIP text encoder + reward head)
     int kind = 0;
     sd_unet_config cfg;
     sd_clip_config clip;
     sd_clip_vision_config vis;
+    sd_image_reward_config ir;         // kind 6
+    // kind 6: the text operands and the optional feature output of the call in flight (sd_image_reward_score sets them, the
+    // plan's embedding / attention / head ops read them; the images travel as the plan's input, the rewards as its output)
+    const int* ir_ids = nullptr;
+    const int* ir_mask = nullptr;
+    float* ir_features = nullptr;
     int text_proj = 0;                 // kind 2 with text_projection.weight [text_proj, hidden] (sd_clip_create_projected)
     int eos_id = -1;                   // pooled text row: first position of this id; < 0: argmax of the ids
     std::map<std::pair<int, int>, int*> prep_tabs;     // kind 3: device tap tables per input (H, W)
@@ -277,6 +286,7 @@ void enumerate_params_vae(sd_unet* u);
 void enumerate_params_vae_encoder(sd_unet* u);
 void enumerate_params_clip(sd_unet* u);
 void enumerate_params_vit(sd_unet* u);
+void enumerate_params_image_reward(sd_unet* u);
 int cond_embed_convs(const sd_unet* u, std::string names[8], int cin[8], int cout[8], int stride[8]);     // ControlNetConditioningEmbedding's chain
 int pack_all(sd_unet* u);
 double pack_alloc_seconds();      // staging-blob growth inside the last pack_all (SD_PACK_TIMING)
@@ -284,6 +294,12 @@ double pack_alloc_seconds();      // staging-blob growth inside the last pack_al
 inline std::string clip_layer(int i) { return "text_model.encoder.layers." + std::to_string(i) + "."; }
 // transformers CLIPVisionModelWithProjection names (`vision_model.` prefix; `pre_layrnorm` is transformers' spelling)
 inline std::string vit_layer(int i) { return "vision_model.encoder.layers." + std::to_string(i) + "."; }
+// ImageReward (kind 6) names: BLIP's own, without the checkpoint's `blip.` prefix
+inline std::string blip_block(int i) { return "visual_encoder.blocks." + std::to_string(i) + "."; }
+inline std::string blip_text_layer(int i) { return "text_encoder.encoder.layer." + std::to_string(i) + "."; }
+constexpr int kRewardHeadDims[5] = {1024, 128, 64, 16, 1};       // mlp.layers.{0,2,4,6,7}: hidden -> ... -> 1
+constexpr int kRewardHeadLayers[5] = {0, 2, 4, 6, 7};
+inline int blip_kp(const sd_image_reward_config& c) { return (3 * c.patch_size * c.patch_size + 63) / 64 * 64; }
 inline int vit_kp(const sd_clip_vision_config& c) { return (3 * c.patch_size * c.patch_size + 63) / 64 * 64; }
 
 // plan.hip

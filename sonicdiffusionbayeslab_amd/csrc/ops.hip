@@ -354,6 +354,25 @@ extern "C" int sd_op_vit_attention(void* stream, const void* qkv, void* out, int
     return sd_launch_vit_attention((const bf16_t*)qkv, (bf16_t*)out, B, L, H, heads, (hipStream_t)stream);
 }
 
+// the BLIP text encoder's attention on its own; the key mask is copied to the host to refuse a sample without a valid key
+extern "C" int sd_op_bert_attention(void* stream, const void* q, long long ldq, const void* k, const void* v, long long ldkv,
+                                    const int* mask, void* out, long long ldo, int B, int heads, int Lq, int Lk) {
+    if (sd_bert_attention_check(B, Lq, Lk, heads)) return -1;
+    if (mask) {
+        std::vector<int> hm((size_t)B * Lk);
+        SD_CHECK_HIP(hipMemcpyAsync(hm.data(), mask, hm.size() * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+        SD_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+        if (sd_bert_mask_check(hm.data(), B, Lk)) return -1;
+    }
+    return sd_launch_bert_attention((const bf16_t*)q, ldq, (const bf16_t*)k, (const bf16_t*)v, ldkv, mask, (bf16_t*)out, ldo, B, heads,
+                                    Lq, Lk, (hipStream_t)stream);
+}
+
+extern "C" int sd_op_reward_head(void* stream, const void* hidden, long long row_stride, const float* w, const float* bias,
+                                 float mean, float std, int B, int H, float* rewards, float* features) {
+    return sd_launch_reward_head((const bf16_t*)hidden, row_stride, w, bias, mean, std, B, H, rewards, features, (hipStream_t)stream);
+}
+
 // CLIPImageProcessor on device: uint8 images [B][3][H][W] -> the uint8 crop [B][3][S][S] and bf16 patch rows
 // [B * (S/P)^2][Kp] (Kp = 3 P^2 rounded up to 64).  Synchronises the stream (the tap tables and the intermediate are
 // allocated for the call).

@@ -1,4 +1,4 @@
-// libsdhip host side: parameter enumeration (the state_dict names of the six handle kinds) and the weight packer.  Pure host
+// libsdhip host side: parameter enumeration (the state_dict names of the seven handle kinds) and the weight packer.  Pure host
 // code: it runs on a box without a GPU too.
 #include "model.h"
 
@@ -205,6 +205,43 @@ void enumerate_params_vit(sd_unet* u) {
     for (int i = 0; i < c.num_layers; ++i) e.clip_encoder_layer(vit_layer(i), H, I);
     e.add("vision_model.post_layernorm.weight", {H}); e.add("vision_model.post_layernorm.bias", {H});
     e.add("visual_projection.weight", {c.projection_dim, H});
+}
+
+// ImageReward: BLIP ViT (timm names), BLIP text encoder (BERT names with crossattention), the reward head's five Linears
+void enumerate_params_image_reward(sd_unet* u) {
+    const sd_image_reward_config& c = u->ir;
+    Enum e{u};
+    auto lin = [&](const std::string& n, int out, int in) { e.add(n + ".weight", {out, in}); e.add(n + ".bias", {out}); };
+    auto norm = [&](const std::string& n, int h) { e.add(n + ".weight", {h}); e.add(n + ".bias", {h}); };
+    const int VH = c.vision_hidden_size, VI = c.vision_intermediate_size, G = c.image_size / c.patch_size;
+    e.add("visual_encoder.cls_token", {VH});
+    e.add("visual_encoder.pos_embed", {G * G + 1, VH});
+    e.add("visual_encoder.patch_embed.proj.weight", {VH, 3, c.patch_size, c.patch_size});
+    e.add("visual_encoder.patch_embed.proj.bias", {VH});
+    for (int i = 0; i < c.vision_num_layers; ++i) {
+        const std::string p = blip_block(i);
+        norm(p + "norm1", VH); lin(p + "attn.qkv", 3 * VH, VH); lin(p + "attn.proj", VH, VH);
+        norm(p + "norm2", VH); lin(p + "mlp.fc1", VI, VH); lin(p + "mlp.fc2", VH, VI);
+    }
+    norm("visual_encoder.norm", VH);
+    const int H = c.hidden_size, I = c.intermediate_size;
+    e.add("text_encoder.embeddings.word_embeddings.weight", {c.vocab_size, H});
+    e.add("text_encoder.embeddings.position_embeddings.weight", {c.max_positions, H});
+    norm("text_encoder.embeddings.LayerNorm", H);
+    for (int i = 0; i < c.num_layers; ++i) {
+        const std::string p = blip_text_layer(i);
+        for (const char* n : {"query", "key", "value"}) lin(p + "attention.self." + n, H, H);
+        lin(p + "attention.output.dense", H, H); norm(p + "attention.output.LayerNorm", H);
+        lin(p + "crossattention.self.query", H, H);
+        lin(p + "crossattention.self.key", H, VH); lin(p + "crossattention.self.value", H, VH);
+        lin(p + "crossattention.output.dense", H, H); norm(p + "crossattention.output.LayerNorm", H);
+        lin(p + "intermediate.dense", I, H); lin(p + "output.dense", H, I); norm(p + "output.LayerNorm", H);
+    }
+    int in = H;
+    for (int k = 0; k < 5; ++k) {
+        lin("mlp.layers." + std::to_string(kRewardHeadLayers[k]), kRewardHeadDims[k], in);
+        in = kRewardHeadDims[k];
+    }
 }
 
 // AutoencoderKL decoder (diffusers names): post_quant_conv + decoder.*  
@@ -793,6 +830,89 @@ int pack_vit(sd_unet* u) {
     return 0;
 }
 
+// ImageReward.  Vision: the fused attn.qkv rows as given; the patch-embedding bias folded into position rows 1..N (in fp32,
+// before the bf16 cast: the embedding kernel adds a position row to every patch row anyway).  Text: self-attention q | k | v
+// fused per layer; the cross-attention key | value weights of ALL layers concatenated ([layers][k | v] rows over the encoder
+// width), because every layer projects the same image tokens: one GEMM.  Head: the five Linears are a linear chain (no
+// activation, dropout is identity in eval), folded here in fp64 into one vector and one bias.
+int pack_image_reward(sd_unet* u) {
+    const sd_image_reward_config& c = u->ir;
+    Packer pk{u};
+    auto lin = [&](const std::string& n) { pk.bf16_same(n + ".weight"); pk.f32(n + ".bias"); };
+    auto norm = [&](const std::string& n) { pk.f32(n + ".weight"); pk.f32(n + ".bias"); };
+    auto cat_bias = [&](const std::string& key, const std::vector<std::string>& names) {
+        size_t total = 0;
+        for (auto& n : names) total += pk.P(n).size();
+        size_t off = pk.alloc(key, total * 4);
+        float* o = (float*)(u->hblob.data() + off);
+        for (auto& n : names)
+            for (float v : pk.P(n)) *o++ = v;
+    };
+    const int VH = c.vision_hidden_size, K = 3 * c.patch_size * c.patch_size, Kp = blip_kp(c);
+    const int G = c.image_size / c.patch_size, Np = G * G;
+    pk.f32("visual_encoder.cls_token");
+    {
+        const auto& d = pk.P("visual_encoder.patch_embed.proj.weight");
+        size_t off = pk.alloc("visual_encoder.patch_embed.proj.weight", (size_t)VH * Kp * 2);
+        unsigned short* o = (unsigned short*)(u->hblob.data() + off);
+        for (int n = 0; n < VH; ++n)
+            for (int k = 0; k < Kp; ++k) o[(size_t)n * Kp + k] = k < K ? f32_to_bf16_host(d[(size_t)n * K + k]) : 0;
+    }
+    {
+        const auto& pos = pk.P("visual_encoder.pos_embed");
+        const auto& pb = pk.P("visual_encoder.patch_embed.proj.bias");
+        size_t off = pk.alloc("visual_encoder.pos_embed", (size_t)(Np + 1) * VH * 2);
+        unsigned short* o = (unsigned short*)(u->hblob.data() + off);
+        for (int t = 0; t <= Np; ++t)
+            for (int k = 0; k < VH; ++k) o[(size_t)t * VH + k] = f32_to_bf16_host(pos[(size_t)t * VH + k] + (t ? pb[k] : 0.f));
+    }
+    for (int i = 0; i < c.vision_num_layers; ++i) {
+        const std::string p = blip_block(i);
+        norm(p + "norm1"); lin(p + "attn.qkv"); lin(p + "attn.proj"); norm(p + "norm2"); lin(p + "mlp.fc1"); lin(p + "mlp.fc2");
+    }
+    norm("visual_encoder.norm");
+    pk.bf16_same("text_encoder.embeddings.word_embeddings.weight");
+    pk.bf16_same("text_encoder.embeddings.position_embeddings.weight");
+    norm("text_encoder.embeddings.LayerNorm");
+    std::vector<std::string> kvw, kvb;
+    for (int i = 0; i < c.num_layers; ++i) {
+        const std::string p = blip_text_layer(i), a = p + "attention.self.", x = p + "crossattention.self.";
+        pk.concat_rows(a + "qkv.weight", {a + "query.weight", a + "key.weight", a + "value.weight"});
+        cat_bias(a + "qkv.bias", {a + "query.bias", a + "key.bias", a + "value.bias"});
+        lin(p + "attention.output.dense"); norm(p + "attention.output.LayerNorm");
+        lin(x + "query");
+        kvw.push_back(x + "key.weight"); kvw.push_back(x + "value.weight");
+        kvb.push_back(x + "key.bias"); kvb.push_back(x + "value.bias");
+        lin(p + "crossattention.output.dense"); norm(p + "crossattention.output.LayerNorm");
+        lin(p + "intermediate.dense"); lin(p + "output.dense"); norm(p + "output.LayerNorm");
+    }
+    pk.concat_rows("text_encoder.cross_kv.weight", kvw);
+    cat_bias("text_encoder.cross_kv.bias", kvb);
+    {   // r = W7 (W6 (W4 (W2 (W0 x + b0) + b2) + b4) + b6) + b7 = w . x + b: row vector times matrix, last layer first
+        const int H = c.hidden_size;
+        std::vector<double> w{1.0};      // [1][out of the layer below]
+        double b = 0.0;
+        for (int k = 4; k >= 0; --k) {
+            const std::string n = "mlp.layers." + std::to_string(kRewardHeadLayers[k]);
+            const auto& W = pk.P(n + ".weight");
+            const auto& B = pk.P(n + ".bias");
+            const int out = kRewardHeadDims[k], in = k ? kRewardHeadDims[k - 1] : H;
+            std::vector<double> nw((size_t)in, 0.0);
+            for (int o = 0; o < out; ++o) {
+                b += w[o] * (double)B[o];
+                for (int i = 0; i < in; ++i) nw[i] += w[o] * (double)W[(size_t)o * in + i];
+            }
+            w.swap(nw);
+        }
+        size_t off = pk.alloc("reward_head.weight", (size_t)H * 4);
+        float* o = (float*)(u->hblob.data() + off);
+        for (int i = 0; i < H; ++i) o[i] = (float)w[i];
+        off = pk.alloc("reward_head.bias", 4);
+        *(float*)(u->hblob.data() + off) = (float)b;
+    }
+    return 0;
+}
+
 }  // namespace
 
 double pack_alloc_seconds() { return g_alloc_s; }
@@ -803,6 +923,7 @@ int pack_all(sd_unet* u) {
     if (u->kind == 2) return pack_clip(u);
     if (u->kind == 3) return pack_vit(u);
     if (u->kind == 4) return pack_vae_encoder(u);
+    if (u->kind == 6) return pack_image_reward(u);
     const sd_unet_config& c = u->cfg;
     Packer pk{u};
     const int c0 = c.block_out_channels[0], nl = c.num_levels;

@@ -178,8 +178,8 @@ struct Builder {
         push(o);
         return o.out;
     }
-    int ln(int x, int M, int C, const std::string& g, const std::string& b, bool fq = false) {
-        Op o; o.kind = OP_LN; o.x1 = x; o.M = M; o.N = C; o.g = W(g); o.be = W(b); o.eps = 1e-5f;
+    int ln(int x, int M, int C, const std::string& g, const std::string& b, bool fq = false, float eps = 1e-5f) {
+        Op o; o.kind = OP_LN; o.x1 = x; o.M = M; o.N = C; o.g = W(g); o.be = W(b); o.eps = eps;
         if (fq) {
             o.out_fp8 = 1; o.Cpad = pad128(C); o.sname = u->act_id(stem(g), u->s_norm); o.os = u->act_scale[o.sname];
             o.out = tensor((size_t)M * o.Cpad); tscale[o.out] = o.os;
@@ -559,7 +559,94 @@ struct Builder {
         { Op o; o.kind = OP_TO_F32; o.x1 = e; o.out = T_EPS; o.M = UB; o.N = c.projection_dim; push(o); }
     }
 
+    // ---- ImageReward (kind 6): both towers in ONE plan per (batch, text length, image H, W) ----
+    // BLIP's ViT (timm VisionTransformer as BLIP's vit.py builds it): the patch embedding as a GEMM over the patch rows (its bias
+    // rides in the position rows, Packer), class token + position embedding, NO pre-LayerNorm, pre-LN blocks with the fused
+    // attn.qkv as given and the exact GELU, the final `norm` over ALL rows.  Returns the image tokens [UB * L][H], bf16.
+    int ln_eps(int x, int M, int C, const std::string& n, float eps) { return ln(x, M, C, n + ".weight", n + ".bias", false, eps); }
+    int lin(int x, int K, int M, int N, const std::string& n, int r = -1) { return gemm(x, K, -1, 0, M, N, n + ".weight", n + ".bias", r, 0); }
+    int build_blip_vision(int* tokens) {
+        const sd_image_reward_config& c = u->ir;
+        const int S = c.image_size, P = c.patch_size, G = S / P, Np = G * G, L = Np + 1;
+        const int H = c.vision_hidden_size, I = c.vision_intermediate_size, Kp = blip_kp(c), M = UB * L;
+        const float eps = c.vision_layer_norm_eps;
+        *tokens = L;
+        if (sd_clip_prep_tables(pl.lh, pl.lw, S, pl.prep_tab, pl.geom)) { error = sd_last_error(); return -1; }
+        int patches;
+        { Op o; o.kind = OP_VIT_PREP; o.x1 = T_LATENTS; o.B = UB; o.K = Kp; o.Cin = P;
+          o.aux = tensor((size_t)UB * 3 * pl.geom.R * S); o.out = tensor((size_t)UB * Np * Kp * 2); push(o); patches = o.out; }
+        int pe = gemm(patches, Kp, -1, 0, UB * Np, H, "visual_encoder.patch_embed.proj.weight", "", -1, 0);
+        int t;
+        { Op o; o.kind = OP_VIT_EMBED; o.x1 = pe; o.B = UB; o.Nq = Np; o.N = H;
+          o.b = W("visual_encoder.cls_token"); o.g = W("visual_encoder.pos_embed");
+          o.out = tensor((size_t)M * H * 2); push(o); t = o.out; }
+        for (int i = 0; i < c.vision_num_layers; ++i) {
+            const std::string p = blip_block(i);
+            int n1 = ln_eps(t, M, H, p + "norm1", eps);
+            int qkv = lin(n1, H, M, 3 * H, p + "attn.qkv");
+            int at;
+            { Op o; o.kind = OP_VIT_ATTN; o.x1 = qkv; o.B = UB; o.Nq = L; o.N = H; o.heads = c.vision_num_heads;
+              o.out = tensor((size_t)M * H * 2); push(o); at = o.out; }
+            t = lin(at, H, M, H, p + "attn.proj", t);
+            int n2 = ln_eps(t, M, H, p + "norm2", eps);
+            int f = lin(n2, H, M, I, p + "mlp.fc1");
+            { Op o; o.kind = OP_QGELU; o.x1 = f; o.out = f; o.M = M; o.N = I; o.epi = 1; push(o); }
+            t = lin(f, I, M, H, p + "mlp.fc2", t);
+        }
+        return ln_eps(t, M, H, "visual_encoder.norm", eps);
+    }
+    // masked attention of the text encoder (bert.hip): q at column qoff of tensor q (pitch ldq), k / v at columns koff / voff
+    // of tensor kv (pitch ldkv); mask: the keys carry the call's attention mask
+    int bert_attn(int q, long qoff, long ldq, int kv, long koff, long voff, long ldkv, int nq, int nk, int H, int heads, int mask) {
+        Op o; o.kind = OP_BERT_ATTN; o.x1 = q; o.x2 = kv; o.qoff = qoff; o.koff = koff; o.voff = voff;
+        o.ldq = ldq; o.ldk = o.ldv = ldkv; o.ldo = H; o.B = UB; o.heads = heads; o.D = H / heads; o.Nq = nq; o.Nk = nk;
+        o.key_mask = mask;
+        o.out = tensor((size_t)UB * nq * H * 2);
+        push(o);
+        return o.out;
+    }
+    // BLIP's text encoder (its med.py BertModel in multimodal mode) over Lt = Plan::rep tokens per prompt: word + position
+    // embedding and LayerNorm, then post-LN layers -- self-attention under the key-padding mask, cross-attention over the image
+    // tokens (no mask), GELU MLP -- and the reward head on the class-token rows.  The image tokens are the same for every layer,
+    // so K | V of ALL layers' cross-attentions come from one GEMM (N = layers * 2 * H, K = encoder width) and each layer's
+    // attention reads its slice through the column offset.
+    void build_blip_text(int img, int Lv) {
+        const sd_image_reward_config& c = u->ir;
+        const int Lt = pl.rep, H = c.hidden_size, I = c.intermediate_size, EW = c.vision_hidden_size, M = UB * Lt, NL = c.num_layers;
+        const float eps = c.layer_norm_eps;
+        const long ldkv = (long)NL * 2 * H;
+        int kvall = lin(img, EW, UB * Lv, NL * 2 * H, "text_encoder.cross_kv");
+        int h;
+        { Op o; o.kind = OP_CLIP_EMBED; o.x1 = T_LATENTS; o.M = M; o.N = H; o.Nk = Lt;
+          o.w = W("text_encoder.embeddings.word_embeddings.weight"); o.g = W("text_encoder.embeddings.position_embeddings.weight");
+          o.out = tensor((size_t)M * H * 2); push(o); h = o.out; }
+        h = ln_eps(h, M, H, "text_encoder.embeddings.LayerNorm", eps);
+        for (int i = 0; i < NL; ++i) {
+            const std::string p = blip_text_layer(i);
+            int qkv = lin(h, H, M, 3 * H, p + "attention.self.qkv");
+            int a1 = bert_attn(qkv, 0, 3 * H, qkv, H, 2 * H, 3 * H, Lt, Lt, H, c.num_heads, 1);
+            h = ln_eps(lin(a1, H, M, H, p + "attention.output.dense", h), M, H, p + "attention.output.LayerNorm", eps);
+            int q2 = lin(h, H, M, H, p + "crossattention.self.query");
+            int a2 = bert_attn(q2, 0, H, kvall, (long)i * 2 * H, (long)i * 2 * H + H, ldkv, Lt, Lv, H, c.num_heads, 0);
+            h = ln_eps(lin(a2, H, M, H, p + "crossattention.output.dense", h), M, H, p + "crossattention.output.LayerNorm", eps);
+            int f = lin(h, H, M, I, p + "intermediate.dense");
+            { Op o; o.kind = OP_QGELU; o.x1 = f; o.out = f; o.M = M; o.N = I; o.epi = 1; push(o); }
+            h = ln_eps(lin(f, I, M, H, p + "output.dense", h), M, H, p + "output.LayerNorm", eps);
+            pl.taps["text_layer" + std::to_string(i)] = h;
+        }
+        { Op o; o.kind = OP_REWARD_HEAD; o.x1 = h; o.out = T_EPS; o.B = UB; o.N = H; o.Nq = Lt;
+          o.w = W("reward_head.weight"); o.b = W("reward_head.bias"); push(o); }
+    }
+    void build_image_reward() {
+        int Lv = 0;
+        const int img = build_blip_vision(&Lv);
+        if (img < 0) return;
+        pl.taps["image_tokens"] = img;
+        build_blip_text(img, Lv);
+    }
+
     void build() {
+        if (u->kind == 6) { build_image_reward(); return; }
         if (u->kind == 1) { build_vae(); return; }
         if (u->kind == 2) { build_clip(); return; }
         if (u->kind == 3) { build_vit(); return; }
@@ -898,7 +985,7 @@ int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw
                    b.error.c_str());
         fuse_deferred_reduce(u, pl);
         assign_memory(u, pl);
-        if (u->kind == 3) {     // tap tables of this input size: uploaded once, owned by the handle
+        if (u->kind == 3 || u->kind == 6) {     // tap tables of this input size: uploaded once, owned by the handle
             int*& d = u->prep_tabs[std::make_pair(lh, lw)];
             if (!d) {
                 SD_CHECK_HIP(hipMalloc((void**)&d, pl.prep_tab.size() * sizeof(int)));

@@ -186,8 +186,18 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
         case OP_REPLICATE:
             return sd_launch_replicate(T(o.x1), T(o.out), (long)o.M * 16, o.N, stream);
         case OP_CLIP_EMBED:
+            if (u->kind == 6)       // (the plan's input is the image batch: the ids are the call's, on the handle)
+                return sd_launch_clip_embed(u->ir_ids, (const bf16_t*)(wb + o.w), (const bf16_t*)(wb + o.g), (bf16_t*)T(o.out),
+                                            o.M, o.Nk, o.N, u->ir.vocab_size, stream);
             return sd_launch_clip_embed((const int*)latents, (const bf16_t*)(wb + o.w), (const bf16_t*)(wb + o.g),
                                         (bf16_t*)T(o.out), o.M, o.Nk, o.N, u->clip.vocab_size, stream);
+        case OP_BERT_ATTN:
+            return sd_launch_bert_attention((const bf16_t*)T(o.x1) + o.qoff, o.ldq, (const bf16_t*)T(o.x2) + o.koff,
+                                            (const bf16_t*)T(o.x2) + o.voff, o.ldk, o.key_mask ? u->ir_mask : nullptr,
+                                            (bf16_t*)T(o.out), o.ldo, o.B, o.heads, o.Nq, o.Nk, stream);
+        case OP_REWARD_HEAD:
+            return sd_launch_reward_head((const bf16_t*)T(o.x1), (long)o.Nq * o.N, (const float*)(wb + o.w), (const float*)(wb + o.b),
+                                         u->ir.reward_mean, u->ir.reward_std, o.B, o.N, eps_out, u->ir_features, stream);
         case OP_CLIP_ATTN:
             return sd_launch_clip_attention((const bf16_t*)T(o.x1), (bf16_t*)T(o.out), o.B, o.Nq, o.N, o.heads, stream);
         case OP_QGELU:
@@ -517,6 +527,77 @@ extern "C" int sd_clip_vision_encode(sd_unet* u, void* stream, const unsigned ch
     int rc = get_plan(u, batch, -1, &pl, 1, height, width);
     if (rc) return rc;
     return run_plan(u, *pl, "clip_vision", workspace, workspace_bytes, images, batch, image_embeds, 0.f, stream);
+}
+
+// ---- ImageReward (quality_metrics.image_reward): BLIP ViT + BLIP text encoder + reward head, one plan ----
+extern "C" int sd_image_reward_create(const sd_image_reward_config* cfg, sd_unet** out) {
+    SD_REQUIRE(cfg && out, "sd_image_reward_create: null argument");
+    const sd_image_reward_config& c = *cfg;
+    SD_REQUIRE(c.vision_hidden_size > 0 && c.vision_hidden_size % 64 == 0 && c.vision_hidden_size <= 1536,
+               "sd_image_reward_create: vision_hidden_size %d (a multiple of 64 up to 1536 is built)", c.vision_hidden_size);
+    SD_REQUIRE(c.hidden_size > 0 && c.hidden_size % 64 == 0 && c.hidden_size <= 1536,
+               "sd_image_reward_create: hidden_size %d (a multiple of 64 up to 1536 is built)", c.hidden_size);
+    SD_REQUIRE(c.vision_intermediate_size > 0 && c.vision_intermediate_size % 64 == 0 && c.intermediate_size > 0 &&
+                   c.intermediate_size % 64 == 0,
+               "sd_image_reward_create: vision_intermediate_size %d / intermediate_size %d must be positive multiples of 64",
+               c.vision_intermediate_size, c.intermediate_size);
+    SD_REQUIRE(c.vision_num_heads > 0 && c.vision_hidden_size == 64 * c.vision_num_heads,
+               "sd_image_reward_create: vision_num_heads %d at vision_hidden_size %d (head dim 64 is built)", c.vision_num_heads,
+               c.vision_hidden_size);
+    SD_REQUIRE(c.num_heads > 0 && c.hidden_size == 64 * c.num_heads,
+               "sd_image_reward_create: num_heads %d at hidden_size %d (head dim 64 is built)", c.num_heads, c.hidden_size);
+    SD_REQUIRE(c.patch_size >= 1 && c.image_size >= c.patch_size && c.image_size % c.patch_size == 0,
+               "sd_image_reward_create: image_size %d / patch_size %d", c.image_size, c.patch_size);
+    const int G = c.image_size / c.patch_size;
+    SD_REQUIRE(G * G + 1 <= 320, "sd_image_reward_create: image_size %d gives %d image tokens (at most 320 are built)", c.image_size,
+               G * G + 1);
+    SD_REQUIRE(c.max_text_len >= 1 && c.max_text_len <= 64 && c.max_text_len <= c.max_positions,
+               "sd_image_reward_create: max_text_len %d (1..64 and at most max_positions = %d)", c.max_text_len, c.max_positions);
+    SD_REQUIRE(c.hidden_act == SD_ACT_GELU, "sd_image_reward_create: hidden_act %d (only gelu = %d is built)", c.hidden_act, SD_ACT_GELU);
+    SD_REQUIRE(c.position_embedding_absolute == 1, "sd_image_reward_create: position_embedding_absolute %d (only absolute positions are built)",
+               c.position_embedding_absolute);
+    SD_REQUIRE(c.vision_num_layers >= 1 && c.num_layers >= 1 && c.vocab_size >= 1,
+               "sd_image_reward_create: vision_num_layers %d / num_layers %d / vocab_size %d", c.vision_num_layers, c.num_layers, c.vocab_size);
+    SD_REQUIRE(c.vision_layer_norm_eps > 0.f && c.layer_norm_eps > 0.f && c.reward_std > 0.f,
+               "sd_image_reward_create: vision_layer_norm_eps %g / layer_norm_eps %g / reward_std %g must be positive",
+               c.vision_layer_norm_eps, c.layer_norm_eps, c.reward_std);
+    sd_unet* u = new_handle(6, nullptr);
+    u->ir = c;
+    enumerate_params_image_reward(u);
+    *out = u;
+    return 0;
+}
+
+extern "C" long long sd_image_reward_workspace_bytes(sd_unet* u, int batch, int height, int width) {
+    SD_REQUIRE(u && u->kind == 6, "image_reward: not an ImageReward handle");
+    if (check_image_size(height, width, "image_reward")) return -1;
+    Plan* pl;
+    if (get_plan(u, batch, -1, &pl, u->ir.max_text_len, height, width)) return -1;
+    return (long long)pl->total_bytes;
+}
+
+extern "C" int sd_image_reward_score(sd_unet* u, void* stream, const unsigned char* images, const int* input_ids,
+                                     const int* attention_mask, int batch, int text_len, int height, int width, float* rewards,
+                                     float* features_or_null, void* workspace, long long workspace_bytes) {
+    SD_REQUIRE(u && u->kind == 6, "image_reward: not an ImageReward handle");
+    SD_REQUIRE(images && input_ids && attention_mask && rewards && workspace && batch > 0, "image_reward: null argument");
+    SD_REQUIRE(text_len >= 1 && text_len <= u->ir.max_text_len, "image_reward: text_len %d (1..max_text_len = %d)", text_len,
+               u->ir.max_text_len);
+    if (check_image_size(height, width, "image_reward")) return -1;
+    Plan* pl;
+    int rc = get_plan(u, batch, -1, &pl, text_len, height, width);
+    if (rc) return rc;
+    if (check_workspace(*pl, "image_reward", workspace, workspace_bytes)) return -1;
+    {   // a prompt whose mask row is all zero has no key to attend to: refused here, before anything is launched
+        std::vector<int> hm((size_t)batch * text_len);
+        SD_CHECK_HIP(hipMemcpyAsync(hm.data(), attention_mask, hm.size() * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+        SD_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+        if (sd_bert_mask_check(hm.data(), batch, text_len)) return -1;
+    }
+    u->ir_ids = input_ids; u->ir_mask = attention_mask; u->ir_features = features_or_null;
+    rc = run_plan(u, *pl, "image_reward", workspace, workspace_bytes, images, batch, rewards, 0.f, stream);
+    u->ir_ids = u->ir_mask = nullptr; u->ir_features = nullptr;
+    return rc;
 }
 
 extern "C" int sd_clip_score(void* stream, const float* image_embeds, const float* text_embeds, int batch, int dim,

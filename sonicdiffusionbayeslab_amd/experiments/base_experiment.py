@@ -157,7 +157,9 @@ class BaseMethod(ABC):
         ``quality_metrics.clip_score.model_name_or_path`` is a LOCAL checkpoint directory -- a hub name is a network
         fetch and the metric is then reported as not computable.  ``fid`` (``:105-109``) when the key of this
         build ``quality_metrics.fid.weights`` names a LOCAL Inception checkpoint file (beside the reference's ``feature`` /
-        ``input_img_size`` / ``normalize``).  ImageReward is not built."""
+        ``input_img_size`` / ``normalize``).  ``image_reward`` (``:99-104``) when the key of this build
+        ``quality_metrics.image_reward.model_path`` names a LOCAL ImageReward directory (beside the reference's
+        ``model_name``); the hub name alone is a network fetch."""
         self.metric_dict = defaultdict(list)
         self.time_metric = metrics_registry["time_metric"]()
         self.clip_score_gen_metric = None
@@ -182,6 +184,17 @@ class BaseMethod(ABC):
                                                       normalize=bool(fq.get("normalize", False)), weights=str(fw), **kw)
         self.fid_source = str(fw) if self.fid_metric is not None else (
             f"not computable offline ({fw!r} is not a local file)" if fw else "not configured")
+        self.image_reward_metric = None
+        iq = qm.get("image_reward", None) if qm else None
+        self.image_reward_configured = bool(iq)
+        ip = iq.get("model_path", None) if iq else None
+        if ip and os.path.isdir(str(ip)):
+            kw = {"device": self.device} if str(self.device).startswith("cuda") else {}
+            self.image_reward_metric = metrics_registry["image_reward"](
+                model_name=str(iq.get("model_name", "ImageReward-v1.0")), model_path=str(ip), **kw)
+        self.image_reward_source = str(ip) if self.image_reward_metric is not None else (
+            f"not computable offline (model_path {ip!r} is not a local directory; "
+            f"{iq.get('model_name', 'ImageReward-v1.0')!r} is a network fetch)" if iq else "not configured")
 
     def setup_loggers(self):
         self.logger = None
@@ -298,10 +311,30 @@ class BaseMethod(ABC):
             m.update((self.load_images(image_files[s:s + batch_size]) * 255).to(torch.uint8), real=True)
         return float(m.compute())
 
+    def image_reward(self, images, prompts, image_files, batch_size: int = 32):
+        """``validate`` of the reference for ImageReward (``:198-206,249``): per batch the dataset's images of the batch's
+        files (real) and the generated images, both ``(img * 255).to(uint8)``, with the prompts -> the win rate of the
+        generated image.  None when no local ImageReward directory was configured, the run produced latents, or a file of
+        the batch is not under ``dataset.img_dataset``."""
+        m = self.image_reward_metric
+        if m is None or not images or images[0].dim() != 3 or images[0].shape[0] != 3:
+            return None
+        root = str(self.config.dataset.img_dataset)
+        if (not image_files or len(image_files) != len(images) or not prompts or len(prompts) != len(images) or
+                not all(os.path.isfile(os.path.join(root, f)) for f in image_files)):
+            self.image_reward_source = f"not computable: the batch's image files are not under dataset.img_dataset = {root!r}"
+            return None
+        m.reset()
+        for s in range(0, len(images), batch_size):
+            gen = (torch.stack(images[s:s + batch_size]) * 255).to(torch.uint8)
+            real = (self.load_images(image_files[s:s + batch_size]) * 255).to(torch.uint8)
+            m.update(real, gen, prompts[s:s + batch_size])
+        return float(m.compute())
+
     def validate(self, name_images, additional_values=None, n_images=0, images=None, prompts=None, image_files=None):
         """The hot-path metric, seconds / image over the loop (``time_metric``), and -- with a local CLIP checkpoint and
         decoded images -- the reference's parity metric ``clip_score``; with a local Inception checkpoint and the batch's
-        dataset images, ``fid``."""
+        dataset images, ``fid`` and, with a local ImageReward directory, the ``image_reward`` win rate."""
         if additional_values:
             for k, v in additional_values.items():
                 self.metric_dict[k].append(v)
@@ -311,18 +344,24 @@ class BaseMethod(ABC):
         fid = self.fid(images, image_files) if (images is not None and self.rank == 0) else None
         if fid is not None:
             self.metric_dict["fid"].append(fid)
+        ir = self.image_reward(images, prompts, image_files) if (images is not None and self.rank == 0) else None
+        if ir is not None:
+            self.metric_dict["image_reward"].append(ir)
         t = float(self.time_metric.compute())
         self.metric_dict["nfe"].append(self.model.num_timesteps)
         self.metric_dict["time_metric"].append(t)
         self.time_metric.reset()
         if self.rank != 0:
             return
-        print(json.dumps({"experiment": self.config.experiment_name, "run": name_images, "nfe": self.model.num_timesteps,
-                          "images": n_images, "time_metric_s_per_image": t,
-                          "images_per_s": (1.0 / t if t > 0 else None), "weights": self.model.weights_source,
-                          "clip_score": cs, "clip_score_model": self.clip_score_source, "n_gpus": self.world,
-                          "fp8_activation_scales": self._fp8_scale_report(),
-                          "fid": fid, "fid_weights": self.fid_source}), flush=True)
+        line = {"experiment": self.config.experiment_name, "run": name_images, "nfe": self.model.num_timesteps,
+                "images": n_images, "time_metric_s_per_image": t,
+                "images_per_s": (1.0 / t if t > 0 else None), "weights": self.model.weights_source,
+                "clip_score": cs, "clip_score_model": self.clip_score_source, "n_gpus": self.world,
+                "fp8_activation_scales": self._fp8_scale_report(),
+                "fid": fid, "fid_weights": self.fid_source}
+        if getattr(self, "image_reward_configured", False):      # (a config without the key reports exactly what it did before)
+            line.update({"image_reward": ir, "image_reward_model": self.image_reward_source})
+        print(json.dumps(line), flush=True)
 
     def _fp8_scale_report(self):
         """The e4m3 activation scales the run used (fp8 handles; None otherwise): count, range and a digest, so that two

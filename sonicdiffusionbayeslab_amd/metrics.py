@@ -5,7 +5,9 @@ needs CLIP ViT-B/16 weights that only exist as a network fetch, so it is registe
 unless a LOCAL checkpoint directory is given.  ``BaseMethod.setup_metrics`` builds it when
 ``quality_metrics.clip_score.model_name_or_path`` is such a directory and ``validate`` then reports it
 (``src/experiments/base_experiment.py:96-98,198-201``).  ``fid`` (``:98-112``) runs the FID Inception-v3 on libsdhip from a
-LOCAL checkpoint file (``quality_metrics.fid.weights``); there is no host network behind it."""
+LOCAL checkpoint file (``quality_metrics.fid.weights``); there is no host network behind it.  ``image_reward``
+(``:44-95``) is the ImageReward-v1.0 win rate of the generated image over the dataset's real one, on libsdhip from a LOCAL
+model directory (``quality_metrics.image_reward.model_path``)."""
 from __future__ import annotations
 
 import os
@@ -176,3 +178,53 @@ class FID:
                 img = torch.from_numpy(np.asarray(img.convert("RGB"), dtype=np.uint8).copy()).permute(2, 0, 1).contiguous()
             self.update(imgs=img, real=real)
         return self.compute().item()
+
+
+@metrics_registry.add_to_registry("image_reward")
+class RewardModel:
+    """The reference's ``RewardModel`` (``src/metrics/metrics.py:44-95``): ImageReward-v1.0 scores the dataset's real image and
+    the generated one against the prompt; the metric is the share of prompts whose generated image scores at least as high."""
+
+    def __init__(self, model_name: str = "ImageReward-v1.0", device=None, model_path=None):
+        """``model_path``: a LOCAL directory with ``ImageReward.pt`` (or ``.safetensors``), ``med_config.json`` and
+        ``vocab.txt``; upstream's ``RM.load(model_name)`` is a hub download.  The config is checked here, the model is built
+        on ``device`` (``None``: the current device) at the first ``update``, so a process that never scores puts no weights
+        on a GPU."""
+        if model_path is None or not os.path.isdir(str(model_path)):
+            raise FileNotFoundError(
+                f"ImageReward checkpoint {model_name!r} (model_path={model_path!r}) is a network fetch and unavailable offline; "
+                "pass a local directory to compute the ImageReward win rate")
+        from .image_reward import read_image_reward_dir
+        read_image_reward_dir(str(model_path))                  # unsupported configs fail here, before any GPU work
+        self.model_name, self.path, self.device, self.model = model_name, str(model_path), device, None
+        self.reset()
+
+    def _scorer(self):
+        if self.model is None:
+            from .image_reward import HipImageReward
+            self.model = HipImageReward.from_pretrained(self.path, device=self.device)
+        return self.model
+
+    @torch.no_grad()
+    def update(self, real_imgs, gen_imgs, prompts) -> None:
+        """uint8 images (``[B,3,H,W]`` or lists of ``[3,H,W]``), one prompt per pair.  A tie is a win, as in the reference
+        (``reward_real <= reward_gen``)."""
+        prompts = list(prompts)
+        m = self._scorer()
+        real = m.score(prompts, real_imgs)
+        gen = m.score(prompts, gen_imgs)
+        self.wins += int((real <= gen).sum().item())
+        self.total += len(prompts)
+
+    def compute(self):
+        return torch.tensor(self.wins / self.total if self.total else float("nan"))
+
+    def reset(self) -> None:
+        self.wins, self.total = 0, 0
+
+    @torch.no_grad()
+    def calc_metric(self, imgs, prompts) -> float:
+        """Mean reward of ``imgs`` under their prompts.  DEVIATION: the reference's line (``src/metrics/metrics.py:87``)
+        unpacks the list of rewards that ``score`` returns into two names and cannot run as written; the mean of the
+        rewards is what its caller reports."""
+        return float(self._scorer().score(list(prompts), imgs).double().mean().item())
