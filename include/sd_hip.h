@@ -266,6 +266,38 @@ int sd_vae_encode_hw(sd_vae* v, void* stream, const float* images, int batch, in
 int sd_vae_posterior_sample(void* stream, const float* moments, const float* noise_or_null, float scale, float* latents_out,
                             int batch, long long hw);
 
+/* ---- AutoencoderTiny (TAESD; diffusers 0.32 AutoencoderTiny, upstream-recall).  Additions under ABI 3: resolve them by name.
+ * The structure is fixed (all widths 64, num_encoder_blocks 1,3,3,3, num_decoder_blocks 3,3,3,1, relu, nearest, 4 latent
+ * channels), so the create calls take no config.  The handle is again an `sd_unet`: parameters (diffusers names
+ * decoder.layers.N.* / encoder.layers.N.*, blocks as <layer>.conv.{0,2,4}.{weight,bias}) are enumerated / loaded / finalised
+ * through the sd_unet_* functions, and the workspace is sized with sd_unet_workspace_bytes_hw (cache_branch_id = -1, the
+ * LATENT size).  Latent sides are multiples of 8 in [8, 128].  Either half is a flat list of 35 launches: entry, 10 blocks of
+ * three 64-channel convs, three up- / down-sampling convs, exit.
+ * decode: fp32 NCHW latents [batch,4,h,w] (the UNet's scaled latents as they are: scaling_factor is 1) -> tanh(z / 3) * 3 ->
+ *   decoder -> fp32 NCHW images [batch,3,8h,8w]; out_mode 0: y * 2 - 1 in [-1, 1], 1: clamp(y, 0, 1).
+ * encode: fp32 NCHW images [batch,3,8h,8w] in [0,1] -> encoder -> fp32 NCHW latents [batch,4,h,w] (no posterior). */
+typedef struct sd_unet sd_taesd;
+int sd_taesd_decoder_create(sd_taesd** out);
+int sd_taesd_encoder_create(sd_taesd** out);
+int sd_taesd_decode_hw(sd_taesd* v, void* stream, const float* latents, int batch, int latent_h, int latent_w, int out_mode,
+                       float* images_out, void* workspace, long long workspace_bytes);
+int sd_taesd_encode_hw(sd_taesd* v, void* stream, const float* images01, int batch, int latent_h, int latent_w, float* latents_out,
+                       void* workspace, long long workspace_bytes);
+/* The tiny autoencoder's kernels one by one (parity tests, tools).  sd_op_conv64: 3x3 conv at 64 -> 64 channels on bf16 NHWC
+ * X [B,Hin,Win,64] with the weights packed by sd_op_conv64_pack (host; OIHW fp32 [64][64][3][3] -> 73,728 bytes, which it
+ * returns; out NULL: the size only); bias [64] fp32 or NULL; R [B,Hout,Wout,64] or NULL, added before the ReLU; mode 0: pad 1,
+ * 1: nearest-2x upsample first, 2: stride 2 with pad 1 on all sides.  sd_op_taesd_entry: fp32 NCHW [B,Cin,H,W] -> conv3x3 in
+ * fp32 (Wt [Cin*9][64] fp32) -> bf16 NHWC; decoder (Cin 4): tanh(x / 3) * 3 in the load, ReLU; encoder (Cin 3): neither.
+ * sd_op_taesd_exit: bf16 NHWC -> conv3x3 64 -> Cout <= 4 (Wp [Cout][9][64] bf16) -> fp32 NCHW; out_mode 0: y * 2 - 1,
+ * 1: clamp(y, 0, 1), 2: y. */
+int sd_op_conv64(void* stream, const void* X, const void* Wpacked, const float* bias, const void* R, void* Y, int B, int Hin,
+                 int Win, int mode, int relu);
+long long sd_op_conv64_pack(const float* w_oihw, void* out);
+int sd_op_taesd_entry(void* stream, const float* x, const float* Wt, const float* bias, void* y, int B, int H, int W, int Cin,
+                      int decoder);
+int sd_op_taesd_exit(void* stream, const void* x, const void* Wp, const float* bias, float* y, int B, int H, int W, int Cout,
+                     int out_mode);
+
 /* ---- CLIP text encoder: replaces `self.text_encoder(text_input_ids)[0]` inside
  * `encode_prompt` (src/models.py:139-155; transformers CLIPTextModel, quick_gelu, causal mask).  `sd_clip` IS the
  * `sd_unet` handle type: parameters (transformers names, `text_model.` prefix: embeddings.token_embedding.weight,

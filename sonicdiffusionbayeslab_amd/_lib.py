@@ -118,6 +118,14 @@ _SIGS = {
     "sd_vae_encoder_create": (_i, [C.POINTER(SdUnetConfigFull), C.POINTER(_vp)]),
     "sd_vae_encode_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _ll]),
     "sd_vae_posterior_sample": (_i, [_vp, _vp, _vp, _f, _vp, _i, _ll]),
+    "sd_taesd_decoder_create": (_i, [C.POINTER(_vp)]),
+    "sd_taesd_encoder_create": (_i, [C.POINTER(_vp)]),
+    "sd_taesd_decode_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _ll]),
+    "sd_taesd_encode_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _ll]),
+    "sd_op_conv64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "sd_op_conv64_pack": (_ll, [_vp, _vp]),
+    "sd_op_taesd_entry": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "sd_op_taesd_exit": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "sd_clip_create": (_i, [C.POINTER(SdClipConfig), C.POINTER(_vp)]),
     "sd_clip_encode": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _ll]),
     "sd_clip_create_projected": (_i, [C.POINTER(SdClipConfig), _i, _i, C.POINTER(_vp)]),

@@ -102,6 +102,33 @@ int sd_launch_conv3x3_halo(const GemmArgs& a, hipStream_t stream);
 // the 1x1 shortcut fields of `a` (Xs1 ... Csc2) can ride on the launch sd_launch_conv3x3 makes for the conv of `a`
 bool sd_conv_halo_shortcut_applicable(const GemmArgs& a);
 
+// conv64.hip: 3x3 conv at 64 -> 64 channels with all nine taps' weights resident in LDS, on rectangular pixel tiles (the
+// tiny autoencoder's only conv shape), and that autoencoder's entry / exit kernels
+constexpr int SD_CONV64_PACKED_BYTES = 9 * 2 * 4 * 1024;      // sd_conv64_pack's output: [tap][k-step][row tile][lane][8] bf16
+struct Conv64Args {
+    const bf16_t* X = nullptr;      // NHWC bf16 [B, Hin, Win, 64]
+    const bf16_t* Wp = nullptr;     // sd_conv64_pack'ed weights, SD_CONV64_PACKED_BYTES
+    const float* bias = nullptr;    // [64] fp32, optional
+    const bf16_t* R = nullptr;      // residual [B, Hout, Wout, 64], optional: added before the ReLU
+    bf16_t* Y = nullptr;            // [B, Hout, Wout, 64]
+    int B = 0, Hin = 0, Win = 0;
+    int mode = 0;                   // 0: pad 1;  1: nearest-2x upsample, then pad 1 (Hout = 2 Hin);  2: stride 2, pad 1 (Hout = (Hin - 1) / 2 + 1)
+    int relu = 0;
+    int Hout = 0, Wout = 0, tiles_y = 0, tiles_x = 0, ntiles = 0;   // filled by the launcher
+    unsigned xbytes = 0;
+};
+int sd_conv64_out_size(int in, int mode);
+void sd_conv64_pack(const float* w_oihw /*[64][64][3][3]*/, bf16_t* out);      // host
+int sd_launch_conv64(const Conv64Args& a, hipStream_t stream);
+// entry: fp32 NCHW [B, Cin, H, W] -> conv3x3 Cin -> 64 (fp32, Wt [Cin * 9][64]) + bias -> bf16 NHWC.  decoder (Cin = 4): the
+// input is tanh(x / 3) * 3 and a ReLU follows; encoder (Cin = 3): the [0, 1] image as it is, no activation
+int sd_launch_taesd_entry(const float* x, const float* Wt, const float* bias, bf16_t* y, int B, int H, int W, int Cin, int decoder,
+                          hipStream_t stream);
+// exit: bf16 NHWC [B, H, W, 64] -> conv3x3 64 -> Cout <= 4 (Wp [Cout][9][64] bf16) + bias -> fp32 NCHW; out_mode 0: y * 2 - 1,
+// 1: clamp(y, 0, 1), 2: y
+int sd_launch_taesd_exit(const bf16_t* x, const bf16_t* Wp, const float* bias, float* y, int B, int H, int W, int Cout, int out_mode,
+                         hipStream_t stream);
+
 // GroupNorm over NHWC (optionally a two-tensor channel concat) -> bf16 [B, HW, C1+C2]
 struct GroupNormArgs {
     const bf16_t* x1 = nullptr; int C1 = 0;

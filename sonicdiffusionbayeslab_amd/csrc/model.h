@@ -192,7 +192,8 @@ struct Plan {
 struct sd_unet {
     // 0 = UNet2DConditionModel, 1 = AutoencoderKL decoder, 2 = CLIP text encoder, 3 = CLIP vision tower, 4 = AutoencoderKL encoder,
     // 5 = ControlNetModel (the UNet's time embedding, conv_in, down path and mid block + the zero convs),
-    // 6 = ImageReward (BLIP ViT + BLIP text encoder + reward head)
+    // 6 = ImageReward (BLIP ViT + BLIP text encoder + reward head),
+    // 7 / 8 = AutoencoderTiny decoder / encoder (taesd.hip: flat launch lists, no Plan)
     int kind = 0;
     sd_unet_config cfg;
     sd_clip_config clip;
@@ -301,6 +302,11 @@ constexpr int kRewardHeadDims[5] = {1024, 128, 64, 16, 1};       // mlp.layers.{
 constexpr int kRewardHeadLayers[5] = {0, 2, 4, 6, 7};
 inline int blip_kp(const sd_image_reward_config& c) { return (3 * c.patch_size * c.patch_size + 63) / 64 * 64; }
 inline int vit_kp(const sd_clip_vision_config& c) { return (3 * c.patch_size * c.patch_size + 63) / 64 * 64; }
+
+// taesd.hip (handle kinds 7 / 8)
+void enumerate_params_taesd(sd_unet* u);
+int pack_taesd(sd_unet* u);
+long long taesd_workspace_bytes(const sd_unet* u, int batch, int lh, int lw);
 
 // plan.hip
 int plan_rep(const sd_unet* u, int latent_batch, int unet_batch);

@@ -142,6 +142,38 @@ extern "C" int sd_op_conv3x3(void* stream, const void* X, const void* W, const f
     return sd_launch_conv3x3(a, (hipStream_t)stream);
 }
 
+// The 64 -> 64 channel conv with LDS-resident weights (conv64.hip): X [B, Hin, Win, 64] bf16 NHWC, Wpacked = sd_op_conv64_pack's
+// output, bias [64] fp32 or null, R [B, Hout, Wout, 64] or null (added before the ReLU) -> Y [B, Hout, Wout, 64];
+// mode 0: pad 1, 1: nearest-2x upsample first (Hout = 2 Hin), 2: stride 2, pad 1 on all sides (Hout = (Hin - 1) / 2 + 1)
+extern "C" int sd_op_conv64(void* stream, const void* X, const void* Wpacked, const float* bias, const void* R, void* Y, int B,
+                            int Hin, int Win, int mode, int relu) {
+    Conv64Args a;
+    a.X = (const bf16_t*)X; a.Wp = (const bf16_t*)Wpacked; a.bias = bias; a.R = (const bf16_t*)R; a.Y = (bf16_t*)Y;
+    a.B = B; a.Hin = Hin; a.Win = Win; a.mode = mode; a.relu = relu ? 1 : 0;
+    return sd_launch_conv64(a, (hipStream_t)stream);
+}
+
+// host: OIHW fp32 [64][64][3][3] -> the 73,728 bytes sd_op_conv64 reads (returns that size; out null: the size only)
+extern "C" long long sd_op_conv64_pack(const float* w_oihw, void* out) {
+    if (out) {
+        SD_REQUIRE(w_oihw, "conv64_pack: null weights");
+        sd_conv64_pack(w_oihw, (bf16_t*)out);
+    }
+    return SD_CONV64_PACKED_BYTES;
+}
+
+// The tiny autoencoder's entry (fp32 NCHW [B, Cin, H, W] -> bf16 NHWC [B, H, W, 64]; Wt [Cin * 9][64] fp32; decoder: Cin = 4,
+// tanh(x / 3) * 3 in the load and a ReLU; encoder: Cin = 3, neither) and exit (bf16 NHWC -> fp32 NCHW [B, Cout, H, W]; Wp
+// [Cout][9][64] bf16; out_mode 0: y * 2 - 1, 1: clamp(y, 0, 1), 2: y) kernels
+extern "C" int sd_op_taesd_entry(void* stream, const float* x, const float* Wt, const float* bias, void* y, int B, int H, int W,
+                                 int Cin, int decoder) {
+    return sd_launch_taesd_entry(x, Wt, bias, (bf16_t*)y, B, H, W, Cin, decoder, (hipStream_t)stream);
+}
+extern "C" int sd_op_taesd_exit(void* stream, const void* x, const void* Wp, const float* bias, float* y, int B, int H, int W,
+                                int Cout, int out_mode) {
+    return sd_launch_taesd_exit((const bf16_t*)x, (const bf16_t*)Wp, bias, y, B, H, W, Cout, out_mode, (hipStream_t)stream);
+}
+
 // A resnet's conv2 with its 1x1 shortcut folded in, as the plan runs the pair (conv_halo.hip SC):
 //   Y = conv3x3(X, W) + [Xs1 | Xs2] . Wsc^T + bias,  X = [B, H, W, Cin], Xs1 / Xs2 = [B, H, W, Cs1 / Cs2] (Xs2 null when Cs2 =
 //   0), Wsc = [Cout, Cs1 + Cs2], bias = the sum of the two biases.  Cin is independent of Cout (small sizes reach split-K).

@@ -924,6 +924,7 @@ int pack_all(sd_unet* u) {
     if (u->kind == 3) return pack_vit(u);
     if (u->kind == 4) return pack_vae_encoder(u);
     if (u->kind == 6) return pack_image_reward(u);
+    if (u->kind == 7 || u->kind == 8) return pack_taesd(u);
     const sd_unet_config& c = u->cfg;
     Packer pk{u};
     const int c0 = c.block_out_channels[0], nl = c.num_levels;

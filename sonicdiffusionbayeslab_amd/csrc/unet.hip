@@ -691,6 +691,7 @@ extern "C" long long sd_unet_workspace_bytes(sd_unet* u, int unet_batch, int cac
 
 extern "C" long long sd_unet_workspace_bytes_hw(sd_unet* u, int unet_batch, int cache_branch_id, int latent_h, int latent_w) {
     SD_REQUIRE(u, "workspace_bytes: null handle");
+    if (u->kind == 7 || u->kind == 8) return taesd_workspace_bytes(u, unet_batch, latent_h, latent_w);
     if (check_latent_size(u, latent_h, latent_w, "workspace_bytes")) return -1;
     Plan* pl;
     if (get_plan(u, unet_batch, cache_branch_id, &pl, 1, latent_h, latent_w)) return -1;

@@ -79,6 +79,8 @@ class BaseMethod(ABC):
         )
         if self.config.model.get("controlnet", None) is not None:      # key of this build: a local ControlNet directory or a hub name
             self.model.load_controlnet(str(self.config.model.controlnet))
+        if self.config.model.get("tiny_vae", None) is not None:        # key of this build: a local AutoencoderTiny directory or a hub name
+            self.model.load_tiny_vae(str(self.config.model.tiny_vae), use_for=str(self.config.model.get("tiny_vae_use", "all")))
         self.model.to(self.device)
 
     def setup_scheduler(self, **kwargs):

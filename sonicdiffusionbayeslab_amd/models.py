@@ -159,6 +159,14 @@ class StableDiffusionModel:
         self.controlnet = None
         self._cn_run = None
         self.control_image = None       # the control image of the last conditioned call, at the call's size
+        # AutoencoderTiny (load_tiny_vae): its weights (or the seed of a hub name's stand-in) until the handles are built,
+        # what it is used for ("all" | "previews" | None = not loaded) and the two handles
+        self._tiny_sd = None
+        self._tiny_seed = None
+        self._tiny_source = None
+        self.tiny_vae_use = None
+        self.tiny_vae_decoder = None
+        self.tiny_vae_encoder = None
 
     # -- loading ---------------------------------------------------------------------------
     @classmethod
@@ -268,6 +276,73 @@ class StableDiffusionModel:
             sd = sd or make_synthetic_vae_state_dict(cfg)
             self.vae_encoder = HipVaeEncoder(cfg, sd, device=str(self.unet.device))
         return self.vae_encoder
+
+    # -- AutoencoderTiny (diffusers AutoencoderTiny = TAESD, upstream-recall) --------------------------------
+    TINY_VAE_USES = ("all", "previews")
+
+    def load_tiny_vae(self, pretrained_model_name_or_path, use_for: str = "all"):
+        """A tiny autoencoder beside the AutoencoderKL, before or after the model moves to the GPU.  ``use_for="all"``: the
+        final latents and every stored x0 preview are decoded by it (from the UNet's latents as they are: its scaling factor
+        is 1), and image-to-image / inpainting take their image latents from its encoder, which has no posterior -- nothing
+        is drawn for it, so the forward noise is the generator's FIRST draw (as diffusers with ``.latents``) and
+        ``sample_mode`` is ignored.  ``use_for="previews"``: only the x0 previews use it; the final image and all encoding
+        stay on the AutoencoderKL.  A local directory (``config.json`` + ``diffusion_pytorch_model.safetensors``) is read for
+        real and must be the one structure that is built (``vae.check_tiny_vae_config``); a hub NAME is a network fetch, for
+        which a seeded stand-in is used (``weights_source`` says so)."""
+        from .vae import load_tiny_vae_state_dict
+        if use_for not in self.TINY_VAE_USES:
+            raise ValueError(f"use_for={use_for!r}: one of {self.TINY_VAE_USES}")
+        if self.tiny_vae_use is not None:
+            raise NotImplementedError("load_tiny_vae: a tiny VAE is already loaded (unload_tiny_vae first)")
+        path = str(pretrained_model_name_or_path)
+        if os.path.isdir(path):
+            self._tiny_sd = load_tiny_vae_state_dict(path)
+            self._tiny_source = f" + AutoencoderTiny(local:{path}, {use_for})"
+        elif not self._looks_like_hub_name(path):
+            raise FileNotFoundError(f"load_tiny_vae: no AutoencoderTiny directory at {path!r}")
+        else:
+            self._tiny_seed = int.from_bytes(hashlib.sha256(path.encode()).digest()[:4], "little")
+            self._tiny_source = f" + SYNTHETIC stand-in for the hub AutoencoderTiny {path} (seed={self._tiny_seed}, {use_for})"
+        self.tiny_vae_use = use_for
+        self.weights_source += self._tiny_source
+
+    def unload_tiny_vae(self):
+        """Every path is the AutoencoderKL's again, bit for bit; the handles and their memory are dropped."""
+        if self._tiny_source:
+            self.weights_source = self.weights_source.replace(self._tiny_source, "", 1)
+        self._tiny_sd = self._tiny_seed = self._tiny_source = None
+        self.tiny_vae_use = None
+        self.tiny_vae_decoder = self.tiny_vae_encoder = None
+
+    def _tiny_state_dict(self):
+        from .vae import make_synthetic_tiny_vae_state_dict
+        if self._tiny_sd is None:
+            self._tiny_sd = make_synthetic_tiny_vae_state_dict(seed=self._tiny_seed)
+        return self._tiny_sd
+
+    def _ensure_tiny_vae(self):
+        if self.tiny_vae_decoder is None:
+            from .vae import HipTinyVaeDecoder
+            self._ensure_unet()
+            self.tiny_vae_decoder = HipTinyVaeDecoder(self._tiny_state_dict(), device=str(self.unet.device))
+        return self.tiny_vae_decoder
+
+    def _ensure_tiny_vae_encoder(self):
+        if self.tiny_vae_encoder is None:
+            from .vae import HipTinyVaeEncoder
+            self._ensure_unet()
+            self.tiny_vae_encoder = HipTinyVaeEncoder(self._tiny_state_dict(), device=str(self.unet.device))
+        return self.tiny_vae_encoder
+
+    def _image_latents(self, img, shape, sample_mode, generator):
+        """The scaled latents of an image in [0, 1] on the device: the AutoencoderKL's posterior (one draw of ``shape`` for
+        ``sample_mode="sample"``), or, with a tiny VAE loaded for "all", its encoder's output as it is (no draw)."""
+        if self.tiny_vae_use == "all":
+            return self._ensure_tiny_vae_encoder().encode(img)
+        enc = self._ensure_vae_encoder()
+        moments = enc.encode(img)
+        post = sdist.randn(shape, generator) if sample_mode == "sample" else None
+        return enc.sample(moments, post, mode=sample_mode, scale=self.vae_config.scaling_factor)
 
     def to(self, device):
         """``model.to(device)`` (``base_experiment.py:64``; ``ddim.py:31,33``).  The UNet weights
@@ -811,11 +886,19 @@ class StableDiffusionModel:
             image = latents
             image_x0 = x0_preds
         elif output_type in ("pt", "np", "pil"):
-            vae = self._ensure_vae()
             inv = 1.0 / self.vae_config.scaling_factor
-            image = postprocess_images((vae.decode(latents, inv) / 2 + 0.5).clamp(0, 1), output_type)   # :288,:312
+            # a tiny VAE (load_tiny_vae) decodes the UNet's latents as they are, straight to the clamped [0, 1] picture
+            tiny = self._ensure_tiny_vae() if self.tiny_vae_use is not None else None
+            if self.tiny_vae_use == "all":
+                image = postprocess_images(tiny.decode(latents, unit_range=True), output_type)
+            else:
+                vae = self._ensure_vae()
+                image = postprocess_images((vae.decode(latents, inv) / 2 + 0.5).clamp(0, 1), output_type)   # :288,:312
             # the reference decodes EVERY stored x0 prediction as well (:296-302)
-            image_x0 = [postprocess_images((vae.decode(x, inv) / 2 + 0.5).clamp(0, 1), output_type) for x in x0_preds]
+            if tiny is not None:
+                image_x0 = [postprocess_images(tiny.decode(x, unit_range=True), output_type) for x in x0_preds]
+            else:
+                image_x0 = [postprocess_images((vae.decode(x, inv) / 2 + 0.5).clamp(0, 1), output_type) for x in x0_preds]
         else:
             raise NotImplementedError(f"output_type {output_type!r}: 'latent', 'pt', 'np' and 'pil' are built")
         if not return_dict:
@@ -939,11 +1022,8 @@ class StableDiffusionModel:
         """Steps of StableDiffusionImg2ImgPipeline.prepare_latents, in upstream's order: encode, draw the posterior noise,
         draw the forward noise, ``add_noise`` at the first timestep that runs.  Both draws go through ``dist.randn`` (the
         global batch's draws under a sharded harness call).  Returns (noised start latents, clean scaled latents)."""
-        enc = self._ensure_vae_encoder()
-        moments = enc.encode(img.to(device))
-        shape = (moments.shape[0], moments.shape[1] // 2, moments.shape[2], moments.shape[3])
-        post = sdist.randn(shape, generator) if sample_mode == "sample" else None
-        init = enc.sample(moments, post, mode=sample_mode, scale=self.vae_config.scaling_factor)
+        shape = (img.shape[0], LATENT_CHANNELS, img.shape[2] // self.vae_scale_factor, img.shape[3] // self.vae_scale_factor)
+        init = self._image_latents(img.to(device), shape, sample_mode, generator)
         noise = sdist.randn(shape, generator)
         return self.scheduler.add_noise(init, noise, first_timestep), init
 
@@ -1079,20 +1159,15 @@ class StableDiffusionModel:
         ts_host = list(self.scheduler._timesteps_list)[t_start * self.scheduler.order:]
         dc = self._deepcache
         # mask processing, encoding and noising sit outside the timed region, as text encoding does
-        enc = self._ensure_vae_encoder()
-        scale = self.vae_config.scaling_factor
         img = img.to(device)
         masked_img, lmask = self.inpaint_prepare(img, mask)
         shape = (batch_size, LATENT_CHANNELS, ih // self.vae_scale_factor, iw // self.vae_scale_factor)
         init = None
         if not (nine and latents is not None):          # (9 channels from given noise at strength 1: nothing reads them)
-            moments = enc.encode(img)
-            post = sdist.randn(shape, generator) if sample_mode == "sample" else None
-            init = enc.sample(moments, post, mode=sample_mode, scale=scale)
+            init = self._image_latents(img, shape, sample_mode, generator)
         noise = (latents if latents is not None else sdist.randn(shape, generator)).to(device, torch.float32).contiguous()
         if nine:
-            post = sdist.randn(shape, generator) if sample_mode == "sample" else None
-            masked_latents = enc.sample(enc.encode(masked_img), post, mode=sample_mode, scale=scale)
+            masked_latents = self._image_latents(masked_img, shape, sample_mode, generator)
             self.unet.set_inpaint_cond(lmask, masked_latents)
         # upstream: pure noise (times init_noise_sigma, in _start_loop) at strength 1, the noised image latents below it
         start = noise if float(strength) == 1.0 else self.scheduler.add_noise(init, noise, ts_host[0])
@@ -1151,7 +1226,8 @@ class StableDiffusionModel:
         ``image`` ([B,3,H,W] floats in [0,1], or a list of PIL images of one size): image-to-image with the semantics
         of diffusers' StableDiffusionImg2ImgPipeline -- the image defines the size, ``strength`` in [0, 1] how far up the
         schedule its encoding is noised (``img2img_steps``), ``sample_mode`` whether the posterior is sampled or its mode
-        taken.  ``mask_image`` ([B,1,H,W] or [B,H,W] floats in [0,1], or PIL images; 1 = repaint, 0 = keep) beside ``image``:
+        taken (ignored with a tiny VAE loaded for "all": its encoder has no posterior, see ``load_tiny_vae``).
+        ``mask_image`` ([B,1,H,W] or [B,H,W] floats in [0,1], or PIL images; 1 = repaint, 0 = keep) beside ``image``:
         inpainting with the semantics of StableDiffusionInpaintPipeline (``_call_inpaint``); ``strength`` then defaults to 1.0
         instead of 0.8, and ``latents`` is the forward noise (strength 1.0 only).  A UNet with 9 input channels runs only with
         ``mask_image``.  ``image is None``: text-to-image, the path below."""

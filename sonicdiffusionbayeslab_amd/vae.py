@@ -14,6 +14,7 @@ kernels of their own; the resnets and the mid attention run on the decoder's ops
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
 import os
 from dataclasses import dataclass
@@ -306,6 +307,215 @@ class HipVaeEncoder:
         sc = self.config.scaling_factor if scale is None else float(scale)
         _lib.check(self._lib.sd_vae_posterior_sample(_lib.current_stream(), m.data_ptr(), _lib.ptr(z), float(sc),
                                                      out.data_ptr(), b, h * w), "sd_vae_posterior_sample")
+        return out
+
+    __call__ = encode
+
+
+# ---- AutoencoderTiny (TAESD: diffusers 0.32 AutoencoderTiny / EncoderTiny / DecoderTiny / AutoencoderTinyBlock, upstream-recall) ----
+# A 2.4 M-parameter all-convolutional autoencoder in the UNet's OWN scaled latent space (scaling_factor 1.0): no
+# normalisation, no attention, every hidden conv 64 -> 64 channels.  DESIGN.md 4m; csrc/conv64.hip, csrc/taesd.hip.
+
+@dataclass
+class TinyVaeConfig:
+    """The one structure that is built; ``check_tiny_vae_config`` refuses any other by the name of the field."""
+    in_channels: int = 3
+    out_channels: int = 3
+    latent_channels: int = 4
+    encoder_block_out_channels: Tuple[int, ...] = (64, 64, 64, 64)
+    decoder_block_out_channels: Tuple[int, ...] = (64, 64, 64, 64)
+    num_encoder_blocks: Tuple[int, ...] = (1, 3, 3, 3)
+    num_decoder_blocks: Tuple[int, ...] = (3, 3, 3, 1)
+    act_fn: str = "relu"
+    upsample_fn: str = "nearest"
+    scaling_factor: float = 1.0
+
+
+# THE table of both halves, in module order: (kind, index in ``<half>.layers``).  csrc/taesd.hip holds the same table.
+TINY_DECODER_LAYERS = (("entry", 0), ("block", 2), ("block", 3), ("block", 4), ("up", 6), ("block", 7), ("block", 8), ("block", 9),
+                       ("up", 11), ("block", 12), ("block", 13), ("block", 14), ("up", 16), ("block", 17), ("exit", 18))
+TINY_ENCODER_LAYERS = (("entry", 0), ("block", 1), ("down", 2), ("block", 3), ("block", 4), ("block", 5), ("down", 6), ("block", 7),
+                       ("block", 8), ("block", 9), ("down", 10), ("block", 11), ("block", 12), ("block", 13), ("exit", 14))
+
+
+def check_tiny_vae_config(cfg) -> TinyVaeConfig:
+    """A ``TinyVaeConfig`` or the dict of a ``config.json`` -> the config, or ``NotImplementedError`` naming the field that
+    differs from the structure the kernels are built for."""
+    want = TinyVaeConfig()
+    if isinstance(cfg, TinyVaeConfig):
+        cfg = dataclasses.asdict(cfg)
+    for f in dataclasses.fields(TinyVaeConfig):
+        if f.name not in cfg:
+            continue
+        got, exp = cfg[f.name], getattr(want, f.name)
+        if isinstance(exp, tuple):
+            got = tuple(got)
+        if got != exp:
+            raise NotImplementedError(f"AutoencoderTiny with {f.name}={cfg[f.name]!r} is not built ({f.name}={list(exp) if isinstance(exp, tuple) else exp!r} "
+                                      "is: 64-channel blocks, encoder 1,3,3,3 / decoder 3,3,3,1, relu, nearest, 4 latent channels)")
+    return want
+
+
+def _tiny_half_shapes(half: str, layers, cin: int, cout: int) -> List[Tuple[str, Tuple[int, ...]]]:
+    out: List[Tuple[str, Tuple[int, ...]]] = []
+    for kind, n in layers:
+        p = f"{half}.layers.{n}."
+        if kind == "entry":
+            out += [(p + "weight", (64, cin, 3, 3)), (p + "bias", (64,))]
+        elif kind == "block":
+            for k in (0, 2, 4):
+                out += [(f"{p}conv.{k}.weight", (64, 64, 3, 3)), (f"{p}conv.{k}.bias", (64,))]
+        elif kind == "exit":
+            out += [(p + "weight", (cout, 64, 3, 3)), (p + "bias", (cout,))]
+        else:                        # the convs behind an upsample / the stride-2 convs: no bias
+            out += [(p + "weight", (64, 64, 3, 3))]
+    return out
+
+
+def tiny_vae_decoder_param_shapes(cfg: Optional[TinyVaeConfig] = None):
+    return _tiny_half_shapes("decoder", TINY_DECODER_LAYERS, 4, 3)
+
+
+def tiny_vae_encoder_param_shapes(cfg: Optional[TinyVaeConfig] = None):
+    return _tiny_half_shapes("encoder", TINY_ENCODER_LAYERS, 3, 4)
+
+
+def tiny_vae_param_shapes(cfg: Optional[TinyVaeConfig] = None) -> List[Tuple[str, Tuple[int, ...]]]:
+    """diffusers' AutoencoderTiny state dict: 134 tensors, 2,445,063 values (encoder first, as the module registers them)."""
+    if cfg is not None:
+        check_tiny_vae_config(cfg)
+    return tiny_vae_encoder_param_shapes() + tiny_vae_decoder_param_shapes()
+
+
+TINY_SYNTHETIC_SEED = 4
+TINY_EXIT_IMAGE_FACTOR = 0.1        # the stand-in's 64 -> 3 exit: N(0, 1 / fan_in) x this, bias 0.5 + 0.05 N
+
+
+def make_synthetic_tiny_vae_state_dict(cfg: Optional[TinyVaeConfig] = None, seed: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for a hub AutoencoderTiny, on the bf16 grid (no such weights exist offline).  Conv weights are
+    N(0, 2 / fan_in) (ReLU networks keep their activation scale with it), each block's last conv (``conv.4``) x 0.5 so that
+    the residual sums stay bounded through 10 blocks, the 64 -> 4 exit N(0, 1 / fan_in); the 64 -> 3 exit N(0, 1 / fan_in) x
+    ``TINY_EXIT_IMAGE_FACTOR`` with bias 0.5 + 0.05 N, which puts the picture around mid-grey with few clamped pixels; every
+    other bias 0.05 N.  Drawn in the order of ``tiny_vae_param_shapes``.  The picture's spread depends on the seed (the
+    residual stream's scale after 10 blocks does): at the default seed the decoded picture has std 0.16 .. 0.19 with under 1 %
+    of its pixels clamped (tests/test_taesd_cpu.py holds it to std >= 0.1 and < 2 %)."""
+    if cfg is not None:
+        check_tiny_vae_config(cfg)
+    if seed is None:
+        seed = TINY_SYNTHETIC_SEED
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for name, shape in tiny_vae_param_shapes():
+        if name.endswith(".bias"):
+            t = 0.05 * torch.randn(shape, generator=g)
+            if name == "decoder.layers.18.bias":
+                t = t + 0.5
+        else:
+            fan_in = math.prod(shape[1:])
+            t = torch.randn(shape, generator=g) * math.sqrt(2.0 / fan_in)
+            if name.endswith("conv.4.weight"):
+                t = t * 0.5
+            elif name == "encoder.layers.14.weight":
+                t = t * math.sqrt(0.5)
+            elif name == "decoder.layers.18.weight":
+                t = t * math.sqrt(0.5) * TINY_EXIT_IMAGE_FACTOR
+        sd[name] = t.to(torch.bfloat16).float()
+    return sd
+
+
+def load_tiny_vae_state_dict(model_dir: str) -> Dict[str, torch.Tensor]:
+    """A LOCAL AutoencoderTiny directory (``config.json`` + ``diffusion_pytorch_model.safetensors``).  The config must be
+    the structure that is built (``check_tiny_vae_config``); key names and shapes are checked strictly, both ways."""
+    import json
+    from safetensors.torch import load_file
+    cfg_path = os.path.join(model_dir, "config.json")
+    w_path = os.path.join(model_dir, "diffusion_pytorch_model.safetensors")
+    if not os.path.isfile(cfg_path) or not os.path.isfile(w_path):
+        raise FileNotFoundError(f"no local AutoencoderTiny under {model_dir!r} (config.json + diffusion_pytorch_model.safetensors)")
+    check_tiny_vae_config(json.load(open(cfg_path)))
+    sd = {k: v.float() for k, v in load_file(w_path).items()}
+    shapes = dict(tiny_vae_param_shapes())
+    missing, extra = sorted(set(shapes) - set(sd)), sorted(set(sd) - set(shapes))
+    if missing or extra:
+        raise KeyError(f"AutoencoderTiny state dict: missing {missing[:4]}{'...' if len(missing) > 4 else ''}, "
+                       f"unexpected {extra[:4]}{'...' if len(extra) > 4 else ''}")
+    for k, s in shapes.items():
+        if tuple(sd[k].shape) != s:
+            raise ValueError(f"{k}: expected shape {s}, got {tuple(sd[k].shape)}")
+    return sd
+
+
+class _HipTinyHalf:
+    _create = ""
+    _shapes = staticmethod(lambda: [])
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], config: Optional[TinyVaeConfig] = None, device: str = "cuda:0"):
+        if not torch.cuda.is_available():
+            raise _lib.SdHipError(f"{type(self).__name__} needs an MI355X (no CPU fallback exists)")
+        self.config = check_tiny_vae_config(config or TinyVaeConfig())
+        self.device = torch.device(device)
+        self._lib = _lib.load()
+        self._handle = C.c_void_p()
+        torch.cuda.set_device(self.device)
+        _lib.check(getattr(self._lib, self._create)(C.byref(self._handle)), self._create)
+        _load_params(self._lib, self._handle, self._shapes(), state_dict, type(self).__name__)
+        self._ws: Optional[torch.Tensor] = None
+        self._ws_key = None
+
+    __del__ = HipVaeDecoder.__del__
+    _workspace = HipVaeDecoder._workspace
+
+
+class HipTinyVaeDecoder(_HipTinyHalf):
+    """``AutoencoderTiny.decode`` on libsdhip: UNet latents AS THEY ARE (scaling_factor 1.0) -> images, 35 launches."""
+    _create = "sd_taesd_decoder_create"
+    _shapes = staticmethod(tiny_vae_decoder_param_shapes)
+
+    def decode(self, latents: torch.Tensor, unit_range: bool = False, chunk: int = 8) -> torch.Tensor:
+        """[B,4,h,w] -> [B,3,8h,8w] fp32 on the GPU: in [-1, 1] as diffusers returns it (``y * 2 - 1``), or with
+        ``unit_range`` the picture itself clamped to [0, 1] (what ``/ 2 + 0.5`` and ``clamp`` make of the former, without
+        those two passes).  Latent sides: multiples of 8 in [8, 128]; ``chunk`` images per call of the library."""
+        lat = latents.to(self.device, torch.float32).contiguous()
+        if lat.dim() != 4 or lat.shape[1] != 4:
+            raise ValueError(f"latents must be [B,4,h,w], got {tuple(lat.shape)}")
+        b, _, h, w = lat.shape
+        if not (8 <= h <= 128 and 8 <= w <= 128 and h % 8 == 0 and w % 8 == 0):
+            raise ValueError(f"latents {h}x{w}: the tiny decoder takes sides that are multiples of 8 in [8, 128]")
+        out = torch.empty((b, 3, 8 * h, 8 * w), dtype=torch.float32, device=self.device)
+        for s in range(0, b, chunk):
+            n = min(chunk, b - s)
+            ws = self._workspace(n, h, w)
+            wsp = (ws.data_ptr() + 255) // 256 * 256
+            _lib.check(self._lib.sd_taesd_decode_hw(self._handle, _lib.current_stream(), lat[s:s + n].data_ptr(), n, h, w,
+                                                    1 if unit_range else 0, out[s:s + n].data_ptr(), wsp, ws.numel() - 256),
+                       "sd_taesd_decode_hw")
+        return out
+
+    __call__ = decode
+
+
+class HipTinyVaeEncoder(_HipTinyHalf):
+    """``AutoencoderTiny.encode(...).latents`` on libsdhip: images in [0, 1] -> latents in the UNet's scaled space."""
+    _create = "sd_taesd_encoder_create"
+    _shapes = staticmethod(tiny_vae_encoder_param_shapes)
+
+    def encode(self, images01: torch.Tensor, chunk: int = 8) -> torch.Tensor:
+        """[B,3,H,W] in [0, 1] -> [B,4,H/8,W/8] fp32 on the GPU (no posterior, nothing is drawn).  H and W: multiples of 64
+        in [64, 1024]."""
+        img = images01.to(self.device, torch.float32).contiguous()
+        if img.dim() != 4 or img.shape[1] != 3:
+            raise ValueError(f"images must be [B,3,H,W], got {tuple(img.shape)}")
+        b, _, hh, ww = img.shape
+        if hh % 64 or ww % 64 or not (64 <= hh <= 1024 and 64 <= ww <= 1024):
+            raise ValueError(f"images {hh}x{ww}: the tiny encoder takes sides that are multiples of 64 in [64, 1024]")
+        h, w = hh // 8, ww // 8
+        out = torch.empty((b, 4, h, w), dtype=torch.float32, device=self.device)
+        for s in range(0, b, chunk):
+            n = min(chunk, b - s)
+            ws = self._workspace(n, h, w)
+            wsp = (ws.data_ptr() + 255) // 256 * 256
+            _lib.check(self._lib.sd_taesd_encode_hw(self._handle, _lib.current_stream(), img[s:s + n].data_ptr(), n, h, w,
+                                                    out[s:s + n].data_ptr(), wsp, ws.numel() - 256), "sd_taesd_encode_hw")
         return out
 
     __call__ = encode
