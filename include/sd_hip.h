@@ -216,6 +216,23 @@ int sd_controlnet_forward_hw(sd_unet* u, void* stream, const float* latents, int
  * offsets, so a larger workspace may be filled by copying the old one); a forward whose workspace is too small fails and says so. */
 int sd_unet_set_control_residuals_hw(sd_unet* u, const void* residuals, float scale, int unet_batch, int latent_h, int latent_w);
 
+/* Token Merging around the self-attention of the transformer blocks whose level is at most max_downsample (1 or 2) times
+ * coarser than the latent: each merges r = min(num_src, int(tokens * ratio)) src tokens (0 < ratio <= 0.75).  The setting is
+ * part of the plan key; ratio 0 = off = the plans, workspace sizes and results of a handle that never saw it.  After a change
+ * call sd_unet_workspace_bytes_hw and sd_unet_set_context_hw again.  bf16 UNet handles only.
+ * set_tome_choice: the dst choice (one byte 0..3 per 2x2 cell) of all merging blocks at this latent size, concatenated in plan
+ * order (block_info: each block's token grid, r and offset), copied asynchronously on the stream from host or device memory;
+ * shared by all samples; zero until set.
+ * tome_matching: reads back what the last forward matched in one block (synchronises the stream): kept [B][num_src - r],
+ * merged [B][r], dst_idx [B][r], tok [h w] into host buffers (any may be NULL), *batch = B (half the UNet batch for the first
+ * block of a classifier-free-guidance pair, which runs once per latent). */
+int sd_unet_set_tome(sd_unet* u, double ratio, int max_downsample);
+int sd_unet_tome_block_count_hw(sd_unet* u, int latent_h, int latent_w);
+int sd_unet_tome_block_info_hw(sd_unet* u, int block, int latent_h, int latent_w, int* h, int* w, int* r, long long* choice_off);
+int sd_unet_set_tome_choice_hw(sd_unet* u, void* stream, const unsigned char* choice, long long n, int latent_h, int latent_w);
+int sd_unet_tome_matching_hw(sd_unet* u, void* stream, int block, int unet_batch, int cache_branch_id, void* workspace, int* kept,
+                             int* merged, int* dst_idx, int* tok, int* r, int* batch);
+
 enum { SD_CACHE_OFF = 0, SD_CACHE_FULL_AND_STORE = 1, SD_CACHE_SKIP = 2 };
 
 /* eps = UNet(latent_model_input, t, encoder_hidden_states)  (src/models.py:217-235).
@@ -603,6 +620,28 @@ int sd_op_conv3x3_groupnorm(void* stream, const void* X, const void* W, const fl
 int sd_op_conv3x3_splitk(int M, int Cout, int Cin, int Hin, int Win, int stride, int upsample);
 int sd_op_layernorm(void* stream, const void* x, const float* gamma, const float* beta, void* y, int rows, int C,
                     float eps);
+/* Token Merging for Stable Diffusion (tomesd; csrc/tome.hip), kernel by kernel.  A level of h x w tokens (even
+ * sides, at most 16384 tokens) is cut into 2x2 cells; choice [h/2 * w/2] bytes names the dst token of each cell (0..3, row-major
+ * in the cell), the other three are src tokens: num_dst = h w / 4, num_src = 3 num_dst.  dst slots are numbered by cell, src
+ * slots by ascending token index; every index list below holds slot numbers.  C: a multiple of 64 up to 1536.
+ * match: x [B][h w][C] bf16 -> per src slot the largest cosine similarity to a dst token (node_max fp32 [B][num_src]) and that
+ *   dst slot (node_idx; ties: the lowest slot), on MFMAs over the raw rows, scaled by the fp32 inverse norms afterwards
+ *   (|error| <= 4 C 2^-24; a zero row scores 0).  Also writes tok [h w]: the token index of every src slot, then of every dst slot.
+ * select: the r largest of num_src (<= 12288) scores per sample, radix select, ties at the cut to the lowest slot ->
+ *   kept [B][num_src - r] and merged [B][r] (ascending slots), dst_idx [B][r] = node_idx of the merged.
+ * merge: out [B][h w - r] rows of pitch ldo = the kept src rows, then every dst row averaged with the src rows merged into it
+ *   (fp32, ascending src slot, one rounding).
+ * unmerge: out [B][h w][C] = y[row of the token] + residual (NULL: no residual); y [B][h w - r] rows of pitch ldy; a merged
+ *   src token reads its dst's row.
+ * All four are deterministic. */
+int sd_op_tome_match(void* stream, const void* x, const unsigned char* choice, int B, int h, int w, int C, float* node_max,
+                     int* node_idx, int* tok);
+int sd_op_tome_select(void* stream, const float* node_max, const int* node_idx, int B, int num_src, int r, int* kept, int* merged,
+                      int* dst_idx);
+int sd_op_tome_merge(void* stream, const void* x, const int* tok, const int* kept, const int* merged, const int* dst_idx, void* out,
+                     long long ldo, int B, int h, int w, int C, int r);
+int sd_op_tome_unmerge(void* stream, const void* y, long long ldy, const void* residual, const int* tok, const int* kept,
+                       const int* merged, const int* dst_idx, void* out, int B, int h, int w, int C, int r);
 /* flash-style attention on token-major [B, N, heads * D] views; D = 40, 64, 80 or 160 (64: Stable Diffusion 2.x), any Nq / Nk */
 int sd_op_attention(void* stream, const void* Q, long long ldq, const void* K, long long ldk, const void* V,
                     long long ldv, void* O, long long ldo, int B, int heads, int Nq, int Nk, int D, float scale);

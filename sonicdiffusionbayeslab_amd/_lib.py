@@ -217,6 +217,15 @@ _SIGS = {
     "sd_op_layernorm_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f]),
     "sd_op_quantize_fp8": (_i, [_vp, _vp, _vp, _ll, _i, _i, _f]),
     "sd_op_amax_e4m3": (_i, [_vp, _vp, _ll, _vp]),
+    "sd_unet_set_tome": (_i, [_vp, C.c_double, _i]),
+    "sd_unet_tome_block_count_hw": (_i, [_vp, _i, _i]),
+    "sd_unet_tome_block_info_hw": (_i, [_vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_ll)]),
+    "sd_unet_set_tome_choice_hw": (_i, [_vp, _vp, _vp, _ll, _i, _i]),
+    "sd_unet_tome_matching_hw": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
+    "sd_op_tome_match": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "sd_op_tome_select": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sd_op_tome_merge": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i]),
+    "sd_op_tome_unmerge": (_i, [_vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
 }
 
 

@@ -211,6 +211,24 @@ int sd_launch_transpose_bf16(const bf16_t* src, bf16_t* dst, int B, int R, int C
 int sd_launch_retile32(const bf16_t* src, bf16_t* dst, int B, int R, int K, int RT, hipStream_t stream);
 int sd_launch_replicate(const void* src, void* dst, long bytes, int rep, hipStream_t stream);   // dst[r][i] = src[i], r < rep
 
+// tome.hip: Token Merging around a block's self-attention on a level of h x w tokens (2x2 cells, one dst token per cell:
+// position choice[cell] in 0..3; num_dst = h w / 4, num_src = 3 num_dst).  Index lists hold src / dst SLOT numbers (dst slots by
+// cell, src slots by ascending token index); tok[N] maps slots to token indices, the src slots first.
+int sd_tome_check(int h, int w, int C, const char* who);      // even sides, <= 16384 tokens, C % 64 == 0, C <= 1536
+int sd_launch_tome_partition(const unsigned char* choice, int h, int w, int* tok, hipStream_t stream);
+// x [B][N][C] -> node_max / node_idx [B][num_src]; writes tok [N] and the scratch inv [B][N] (fp32 inverse row norms)
+int sd_launch_tome_match(const bf16_t* x, const unsigned char* choice, int B, int h, int w, int C, float* node_max, int* node_idx,
+                         int* tok, float* inv, hipStream_t stream);
+// top r of num_src (<= 12288) per sample -> kept [B][num_src - r], merged [B][r] (both ascending), dst_idx [B][r]
+int sd_launch_tome_select(const float* node_max, const int* node_idx, int B, int num_src, int r, int* kept, int* merged, int* dst_idx,
+                          hipStream_t stream);
+// x [B][N][C] -> out [B][N - r] rows of pitch ldo: the kept src rows, then every dst row averaged with its members
+int sd_launch_tome_merge(const bf16_t* x, const int* tok, const int* kept, const int* merged, const int* dst_idx, bf16_t* out,
+                         long ldo, int B, int h, int w, int C, int r, hipStream_t stream);
+// y [B][N - r] rows of pitch ldy -> out [B][N][C] = y[row of the token] + residual (residual may be null)
+int sd_launch_tome_unmerge(const bf16_t* y, long ldy, const bf16_t* residual, const int* tok, const int* kept, const int* merged,
+                           const int* dst_idx, bf16_t* out, int B, int h, int w, int C, int r, hipStream_t stream);
+
 // xattn.hip: fused prompt cross-attention  Y = R + sum_h softmax_L(X A_h) B_h + b_o  (one launch per block)
 struct XattnArgs {
     const bf16_t* X = nullptr;    // [M, C] LayerNorm output

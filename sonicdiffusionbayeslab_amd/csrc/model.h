@@ -45,7 +45,8 @@ struct Wrap {  // one DeepCache-wrapped module enclosing an op
 enum OpKind { OP_SINUSOID, OP_GEMV, OP_CONV_IN, OP_GN, OP_CONV3, OP_GEMM, OP_LN, OP_ATTN, OP_CONV_OUT, OP_SOFTMAX, OP_PQCONV,
               OP_CLIP_EMBED, OP_CLIP_ATTN, OP_QGELU, OP_TO_F32, OP_XATTN, OP_REPLICATE,
               OP_VIT_PREP, OP_VIT_EMBED, OP_VIT_ATTN, OP_POOL, OP_CONV_IN_IMG, OP_ENC_OUT, OP_IP_XATTN, OP_RES_ADD,
-              OP_BERT_ATTN, OP_REWARD_HEAD };
+              OP_BERT_ATTN, OP_REWARD_HEAD,
+              OP_TOME_MATCH, OP_TOME_SELECT, OP_TOME_MERGE, OP_TOME_UNMERGE };
 
 constexpr int REP_TEXT_POOLED = 2;       // Plan::rep of a CLIP text handle's sd_clip_text_embeds plan
 
@@ -167,6 +168,11 @@ struct Plan {
     int cn = 0;
     std::vector<size_t> cn_off;           // UNet / ControlNet plans: the residual segments' byte offsets and bf16 element
     std::vector<long> cn_count;           // counts for this batch and size (control_segments)
+    // Token Merging variant (the handle's setting is part of the plan key): the merging blocks in plan order.  Each owns its
+    // index tensors (persistent: readable after the forward, sd_unet_tome_matching_hw) and a slice of the handle's choice array.
+    struct TomeBlock { int tok, kept, merged, dst_idx, B, h, w, r; long choice_off; };
+    std::vector<TomeBlock> tome;
+    long tome_choice_bytes = 0;
     std::vector<Tn> tensors;
     std::vector<Op> ops;
     std::vector<char> skipped;            // per op: skipped on a DeepCache skip step
@@ -229,7 +235,9 @@ struct sd_unet {
         act_names.push_back(name); act_scale.push_back(dflt); act_amax.push_back(0.f);
         return (int)act_names.size() - 1;
     }
-    std::map<std::tuple<int, int, int, int, int, int, int>, sdhip::Plan> plans;   // (UNet batch, DeepCache branch, prefix replication, latent H, W, IP-Adapter variant, control variant)
+    // (UNet batch, DeepCache branch, prefix replication, latent H, W, IP-Adapter variant, control variant, Token Merging: the
+    // bits of the ratio and max_downsample, both 0 = off)
+    std::map<std::tuple<int, int, int, int, int, int, int, long long, int>, sdhip::Plan> plans;
     int last_rep = 1, last_ip = 0, last_cn = 0;                       // variant of the last forward (sd_unet_debug_tensor)
     int last_h = 0, last_w = 0;                          // latent size of the last forward (sd_unet_debug_tensor)
     std::unordered_map<std::string, long> tproj_off;  // resnet prefix -> float index into tproj vector
@@ -264,6 +272,14 @@ struct sd_unet {
     size_t cn_embed_cap = 0, cn_scratch_cap = 0;
     int cn_b = 0, cn_h = 0, cn_w = 0;
     int cond_embed[4] = {0, 0, 0, 0};       // conditioning_embedding_out_channels
+    // Token Merging (sd_unet_set_tome; kind 0, bf16): ratio 0 = off = the plans of a handle that never saw it.  The dst choice of
+    // every merging block (one byte per 2x2 cell, blocks concatenated in plan order) is owned by the handle like dinpaint and
+    // zero (position 0 of every cell) until sd_unet_set_tome_choice_hw writes it.
+    double tome_ratio = 0.0;
+    int tome_max_downsample = 0;
+    unsigned char* tome_choice = nullptr;
+    size_t tome_choice_cap = 0;
+    long tome_choice_n = 0;
     bool unet_like() const { return kind == 0 || kind == 5; }      // runs the UNet's encoder ops (plan.hip Builder::build)
 };
 

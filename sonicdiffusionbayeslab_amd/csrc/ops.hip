@@ -462,6 +462,32 @@ extern "C" int sd_op_attention_headmajor(void* stream, const void* Q, long long 
     return sd_launch_attention(a, (hipStream_t)stream);
 }
 
+// Token Merging, kernel by kernel (tome.hip); index lists in src / dst slot numbers, tok [h * w] from sd_op_tome_match
+extern "C" int sd_op_tome_match(void* stream, const void* x, const unsigned char* choice, int B, int h, int w, int C,
+                                float* node_max, int* node_idx, int* tok) {
+    if (sd_tome_check(h, w, C, "sd_op_tome_match")) return -1;
+    SD_REQUIRE(B >= 1, "sd_op_tome_match: B=%d", B);
+    float* inv = (float*)op_scratch((size_t)B * h * w * 4);
+    SD_REQUIRE(inv, "sd_op_tome_match: cannot allocate scratch");
+    return sd_launch_tome_match((const bf16_t*)x, choice, B, h, w, C, node_max, node_idx, tok, inv, (hipStream_t)stream);
+}
+
+extern "C" int sd_op_tome_select(void* stream, const float* node_max, const int* node_idx, int B, int num_src, int r, int* kept,
+                                 int* merged, int* dst_idx) {
+    return sd_launch_tome_select(node_max, node_idx, B, num_src, r, kept, merged, dst_idx, (hipStream_t)stream);
+}
+
+extern "C" int sd_op_tome_merge(void* stream, const void* x, const int* tok, const int* kept, const int* merged, const int* dst_idx,
+                                void* out, long long ldo, int B, int h, int w, int C, int r) {
+    return sd_launch_tome_merge((const bf16_t*)x, tok, kept, merged, dst_idx, (bf16_t*)out, (long)ldo, B, h, w, C, r, (hipStream_t)stream);
+}
+
+extern "C" int sd_op_tome_unmerge(void* stream, const void* y, long long ldy, const void* residual, const int* tok, const int* kept,
+                                  const int* merged, const int* dst_idx, void* out, int B, int h, int w, int C, int r) {
+    return sd_launch_tome_unmerge((const bf16_t*)y, (long)ldy, (const bf16_t*)residual, tok, kept, merged, dst_idx, (bf16_t*)out, B, h, w,
+                                  C, r, (hipStream_t)stream);
+}
+
 extern "C" int sd_op_conv_in_cond(void* stream, const float* x, int Bsrc, const float* cond, int Bcond, const float* Wt,
                                   const float* bias, void* y, int B, int H, int W, int Cout) {
     return sd_launch_conv_in_cond(x, Bsrc, cond, Bcond, Wt, bias, (bf16_t*)y, B, H, W, Cout, (hipStream_t)stream);

@@ -223,6 +223,18 @@ struct Builder {
         }
         return conv3(t3, rh, rw, cout, cout, 1, 0, p + "conv2.weight", p + "conv2.bias", 0, -1, sc, fq);
     }
+    // Token Merging: how many src tokens a block on a level of rh x rw tokens merges; 0 = the block does not merge (the setting
+    // is off, or the level is past max_downsample).  r = min(num_src, int(N ratio)) as tomesd computes it.
+    int tome_r(int rh, int rw, int C) {
+        if (u->kind != 0 || u->fp8 || !(u->tome_ratio > 0.0) || rh <= 0 || pl.lh / rh > u->tome_max_downsample) return 0;
+        const int N = rh * rw;
+        if (rh % 2 || rw % 2 || N > 16384 || C % 64 || C > 1536) {
+            if (error.empty()) error = "Token Merging needs even token-grid sides, at most 16384 tokens and C a multiple of 64 up to 1536 on "
+                                       "every merging level (" + std::to_string(rh) + "x" + std::to_string(rw) + ", C = " + std::to_string(C) + ")";
+            return 0;
+        }
+        return std::min(N - N / 4, (int)((double)N * u->tome_ratio));
+    }
     // Transformer2DModel with one BasicTransformerBlock (A.4)
     int n_transformers = 0;
     int transformer(const std::string& p, int x, int C, int rh, int rw) {
@@ -233,8 +245,35 @@ struct Builder {
         const bool fq = u->fp8;
         int g = gn(x, C, -1, 0, hw, p + "norm.weight", p + "norm.bias", 1e-6f, 0, fq);
         int h0 = gemm(g, C, -1, 0, M, C, p + "proj_in.weight", p + "proj_in.bias", -1, 0, fq);
+        // Token Merging (tome.hip): norm1 as its own launch, the matching on h0, the merge of norm1's rows; attn1 then runs on
+        // Nm = hw - r rows per sample and the unmerge below writes h1 = attn1 output (copied to every member) + h0
+        const int tr = tome_r(rh, rw, C);
+        const int Nm = hw - tr, Mm = UB * Nm;
+        int tome_i = -1;
         int qkv, rs = -1, np = 0;
-        if (!fq && (np = want_rowstats(pl.ops.back(), M, C, rs)) > 0) {       // norm1 folded into the projection
+        if (tr > 0) {
+            const int num_dst = hw / 4, num_src = hw - num_dst;
+            Plan::TomeBlock tb;
+            tb.B = UB; tb.h = rh; tb.w = rw; tb.r = tr; tb.choice_off = pl.tome_choice_bytes;
+            pl.tome_choice_bytes += num_dst;
+            tb.tok = tensor((size_t)hw * 4, true);
+            tb.kept = tensor((size_t)UB * std::max(num_src - tr, 1) * 4, true);
+            tb.merged = tensor((size_t)UB * tr * 4, true);
+            tb.dst_idx = tensor((size_t)UB * tr * 4, true);
+            int n1 = ln(h0, M, C, t + "norm1.weight", t + "norm1.bias");
+            int nmax, nidx;
+            { Op o; o.kind = OP_TOME_MATCH; o.x1 = h0; o.B = UB; o.Hin = rh; o.Win = rw; o.N = C; o.b2idx = tb.choice_off;
+              o.out = nmax = tensor((size_t)UB * num_src * 4); o.aux = nidx = tensor((size_t)UB * num_src * 4);
+              o.stats = tb.tok; o.rs = tensor((size_t)UB * hw * 4); push(o); }
+            { Op o; o.kind = OP_TOME_SELECT; o.x1 = nmax; o.x2 = nidx; o.B = UB; o.M = num_src; o.K = tr;
+              o.out = tb.kept; o.aux = tb.merged; o.stats = tb.dst_idx; push(o); }
+            int m;
+            { Op o; o.kind = OP_TOME_MERGE; o.x1 = n1; o.x2 = tb.tok; o.r = tb.kept; o.wt = tb.merged; o.s1 = tb.dst_idx;
+              o.B = UB; o.Hin = rh; o.Win = rw; o.N = C; o.K = tr; o.out = m = tensor((size_t)Mm * C * 2); push(o); }
+            tome_i = (int)pl.tome.size();
+            pl.tome.push_back(tb);
+            qkv = gemm(m, C, -1, 0, Mm, 3 * C, t + "attn1.qkv.weight", "", -1, 0);
+        } else if (!fq && (np = want_rowstats(pl.ops.back(), M, C, rs)) > 0) {       // norm1 folded into the projection
             qkv = gemm_ln(h0, rs, np, M, 3 * C, C, t + "attn1.qkv.weight", 0);
         } else {
             int n1 = ln(h0, M, C, t + "norm1.weight", t + "norm1.bias", fq);
@@ -244,20 +283,27 @@ struct Builder {
         // token-major Q block, so that the self-attention's LDS-DMA pieces are contiguous (SD_ATTN_HEADMAJOR=0: off)
         static const bool hm_off = (getenv("SD_ATTN_HEADMAJOR") && atoi(getenv("SD_ATTN_HEADMAJOR")) == 0) ||
                                    getenv("SD_ATTN_NO_PIPE") || getenv("SD_ATTN_NO_DMA") || getenv("SD_GEMM_BIG");
-        const bool hm = !hm_off && C / NH == 40 && C % 160 == 0 && hw % 128 == 0 && hw >= 256 &&
-                        sd_gemm_tile_rows(M, 3 * C) == 128 && pl.ops.back().splitk == 1;
+        // (a merging block: the same conditions on its Nm tokens per sample)
+        const bool hm = !hm_off && C / NH == 40 && C % 160 == 0 && Nm % 128 == 0 && Nm >= 256 &&
+                        sd_gemm_tile_rows(Mm, 3 * C) == 128 && pl.ops.back().splitk == 1;
         int a1;
         if (hm) {
             pl.ops.back().hm = 1;
-            pl.ops.back().HW = hw;
-            a1 = attn(qkv, 0, C, qkv, (long)M * C, 2l * M * C, C, hw, hw, C, NH);
+            pl.ops.back().HW = Nm;
+            a1 = attn(qkv, 0, C, qkv, (long)Mm * C, 2l * Mm * C, C, Nm, Nm, C, NH);
             pl.ops.back().hm = 1;
         } else {
-            a1 = attn(qkv, 0, 3 * C, qkv, C, 2 * C, 3 * C, hw, hw, C, NH);
+            a1 = attn(qkv, 0, 3 * C, qkv, C, 2 * C, 3 * C, Nm, Nm, C, NH);
         }
         pl.ops.back().qps = 1;          // W_q of attn1 carries the scale (Packer::transformer)
-        int h1 = gemm(a1, C, -1, 0, M, C, t + "attn1.to_out.0.weight", t + "attn1.to_out.0.bias", h0, 0);
+        int h1 = gemm(a1, C, -1, 0, Mm, C, t + "attn1.to_out.0.weight", t + "attn1.to_out.0.bias", tr > 0 ? -1 : h0, 0);
         const int to_out_op = (int)pl.ops.size() - 1;
+        if (tr > 0) {
+            const Plan::TomeBlock& tb = pl.tome[tome_i];
+            Op o; o.kind = OP_TOME_UNMERGE; o.x1 = h1; o.r = h0; o.x2 = tb.tok; o.wt = tb.kept; o.s1 = tb.merged; o.s2 = tb.dst_idx;
+            o.B = UB; o.Hin = rh; o.Win = rw; o.N = C; o.K = tr; o.out = tensor((size_t)M * C * 2); push(o);
+            h1 = o.out;
+        }
         if (prefix_rep > 1) {        // end of the prompt-independent prefix: both CFG halves continue from copies
             x = replicate(x, (size_t)M * C * 2, prefix_rep);
             h1 = replicate(h1, (size_t)M * C * 2, prefix_rep);
@@ -287,7 +333,8 @@ struct Builder {
         // rows after attn1.to_out of the FIRST transformer only -- the fused kernel reads its partials modulo their rows, the
         // GEMM consumers do not, so in the two GEMM forms that block keeps its LayerNorm in EVERY plan variant)
         const bool first_tf = n_transformers++ == 0;
-        if (!fq && !xln_off && (xmode == 0 || (!first_tf && rs2_rows == M)) &&
+        // (a merging block keeps norm2 as the separate LayerNorm launch: its rows come from the unmerge, not from a GEMM epilogue)
+        if (!fq && !xln_off && tr == 0 && (xmode == 0 || (!first_tf && rs2_rows == M)) &&
             u->woff.count(t + (xmode == 2 ? "attn2.to_q.weight.ln" : "attn2.to_q.weight.T.ln"))) {
             if (first_tf) pl.ops[to_out_op].splitk = 1;      // (its row count differs between the plan variants: the split heuristic must not)
             np2 = want_rowstats(pl.ops[to_out_op], (int)rs2_rows, C, rs2);
@@ -966,7 +1013,9 @@ int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw
     if (branch < 0) branch = -1;
     if (lh < 0) lh = u->cfg.sample_size;
     if (lw < 0) lw = u->cfg.sample_size;
-    auto key = std::make_tuple(UB, branch, rep, lh, lw, ip, cn);
+    long long tome_bits = 0;
+    if (u->kind == 0 && u->tome_ratio > 0.0) memcpy(&tome_bits, &u->tome_ratio, sizeof(tome_bits));
+    auto key = std::make_tuple(UB, branch, rep, lh, lw, ip, cn, tome_bits, tome_bits ? u->tome_max_downsample : 0);
     auto it = u->plans.find(key);
     if (it == u->plans.end()) {
         if (lh != u->cfg.sample_size || lw != u->cfg.sample_size)

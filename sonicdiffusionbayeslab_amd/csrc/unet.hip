@@ -185,6 +185,19 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
         }
         case OP_REPLICATE:
             return sd_launch_replicate(T(o.x1), T(o.out), (long)o.M * 16, o.N, stream);
+        case OP_TOME_MATCH:
+            SD_REQUIRE(u->tome_choice && o.b2idx + (long)(o.Hin / 2) * (o.Win / 2) <= u->tome_choice_n, "forward: no Token Merging choice array");
+            return sd_launch_tome_match((const bf16_t*)T(o.x1), u->tome_choice + o.b2idx, o.B, o.Hin, o.Win, o.N, (float*)T(o.out),
+                                        (int*)T(o.aux), (int*)T(o.stats), (float*)T(o.rs), stream);
+        case OP_TOME_SELECT:
+            return sd_launch_tome_select((const float*)T(o.x1), (const int*)T(o.x2), o.B, o.M, o.K, (int*)T(o.out), (int*)T(o.aux),
+                                         (int*)T(o.stats), stream);
+        case OP_TOME_MERGE:
+            return sd_launch_tome_merge((const bf16_t*)T(o.x1), (const int*)T(o.x2), (const int*)T(o.r), (const int*)T(o.wt),
+                                        (const int*)T(o.s1), (bf16_t*)T(o.out), o.N, o.B, o.Hin, o.Win, o.N, o.K, stream);
+        case OP_TOME_UNMERGE:
+            return sd_launch_tome_unmerge((const bf16_t*)T(o.x1), o.N, (const bf16_t*)T(o.r), (const int*)T(o.x2), (const int*)T(o.wt),
+                                          (const int*)T(o.s1), (const int*)T(o.s2), (bf16_t*)T(o.out), o.B, o.Hin, o.Win, o.N, o.K, stream);
         case OP_CLIP_EMBED:
             if (u->kind == 6)       // (the plan's input is the image batch: the ids are the call's, on the handle)
                 return sd_launch_clip_embed(u->ir_ids, (const bf16_t*)(wb + o.w), (const bf16_t*)(wb + o.g), (bf16_t*)T(o.out),
@@ -610,6 +623,7 @@ extern "C" void sd_unet_destroy(sd_unet* u) {
     if (u->dweights) (void)hipFree(u->dweights);
     if (u->dcond) (void)hipFree(u->dcond);
     if (u->dinpaint) (void)hipFree(u->dinpaint);
+    if (u->tome_choice) (void)hipFree(u->tome_choice);
     if (u->cn_embed) (void)hipFree(u->cn_embed);
     if (u->cn_scratch) (void)hipFree(u->cn_scratch);
     for (auto& kv : u->prep_tabs)
@@ -1025,6 +1039,20 @@ static int check_control_set(const sd_unet* u, const char* who, int unet_batch, 
     return 0;
 }
 
+// the handle's dst-choice array for the plan about to run: n bytes, zero (position 0 of every cell) unless set for this size
+static int ensure_tome_choice(sd_unet* u, long n, void* stream) {
+    if (n <= 0 || (u->tome_choice && u->tome_choice_n == n)) return 0;
+    if ((size_t)n > u->tome_choice_cap) {
+        if (u->tome_choice) (void)hipFree(u->tome_choice);      // (synchronises: no earlier forward still reads it)
+        u->tome_choice = nullptr; u->tome_choice_cap = 0;
+        SD_CHECK_HIP(hipMalloc((void**)&u->tome_choice, (size_t)n));
+        u->tome_choice_cap = (size_t)n;
+    }
+    SD_CHECK_HIP(hipMemsetAsync(u->tome_choice, 0, (size_t)n, (hipStream_t)stream));
+    u->tome_choice_n = n;
+    return 0;
+}
+
 extern "C" int sd_unet_forward(sd_unet* u, void* stream, const float* latents, int latent_batch, int unet_batch,
                                float timestep, float* eps_out, void* workspace, long long workspace_bytes,
                                int cache_mode, int cache_branch_id) {
@@ -1053,7 +1081,88 @@ extern "C" int sd_unet_forward_hw(sd_unet* u, void* stream, const float* latents
     u->last_h = latent_h; u->last_w = latent_w;
     int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, latent_h, latent_w, ip, cn);
     if (rc) return rc;
+    if ((rc = ensure_tome_choice(u, pl->tome_choice_bytes, stream))) return rc;
     return run_plan(u, *pl, "forward", workspace, workspace_bytes, latents, latent_batch, eps_out, timestep, stream, cache_mode);
+}
+
+// ---- Token Merging (tome.hip; the plan side is Builder::transformer) -----------------------------------------------------
+extern "C" int sd_unet_set_tome(sd_unet* u, double ratio, int max_downsample) {
+    SD_REQUIRE(u && u->kind == 0, "set_tome: not a UNet handle");
+    if (!(ratio > 0.0)) {          // off: the plans of a handle that never saw Token Merging
+        SD_REQUIRE(ratio == 0.0, "set_tome: ratio %g (0 .. 0.75)", ratio);
+        u->tome_ratio = 0.0; u->tome_max_downsample = 0;
+        return 0;
+    }
+    SD_REQUIRE(ratio <= 0.75, "set_tome: ratio %g (0 .. 0.75: a 2x2 cell has three src tokens)", ratio);
+    SD_REQUIRE(max_downsample == 1 || max_downsample == 2, "set_tome: max_downsample %d (1 or 2)", max_downsample);
+    SD_REQUIRE(!u->fp8, "set_tome: Token Merging is not built for fp8 handles");
+    u->tome_ratio = ratio; u->tome_max_downsample = max_downsample;
+    return 0;
+}
+
+// the plan whose merging blocks the entry points below describe: the plain variant of (batch 1, latent size) -- the blocks,
+// their order and their choice slices depend on the latent size and the setting alone
+static int tome_layout(sd_unet* u, const char* who, int latent_h, int latent_w, Plan** pl) {
+    SD_REQUIRE(u && u->kind == 0, "%s: not a UNet handle", who);
+    if (check_latent_size(u, latent_h, latent_w, who)) return -1;
+    return get_plan(u, 1, -1, pl, 1, latent_h, latent_w);
+}
+
+extern "C" int sd_unet_tome_block_count_hw(sd_unet* u, int latent_h, int latent_w) {
+    Plan* pl;
+    if (tome_layout(u, "tome_block_count", latent_h, latent_w, &pl)) return -1;
+    return (int)pl->tome.size();
+}
+
+extern "C" int sd_unet_tome_block_info_hw(sd_unet* u, int block, int latent_h, int latent_w, int* h, int* w, int* r, long long* choice_off) {
+    Plan* pl;
+    if (tome_layout(u, "tome_block_info", latent_h, latent_w, &pl)) return -1;
+    SD_REQUIRE(block >= 0 && block < (int)pl->tome.size(), "tome_block_info: block %d of %zu", block, pl->tome.size());
+    const Plan::TomeBlock& tb = pl->tome[block];
+    if (h) *h = tb.h;
+    if (w) *w = tb.w;
+    if (r) *r = tb.r;
+    if (choice_off) *choice_off = tb.choice_off;
+    return 0;
+}
+
+extern "C" int sd_unet_set_tome_choice_hw(sd_unet* u, void* stream, const unsigned char* choice, long long n, int latent_h, int latent_w) {
+    Plan* pl;
+    if (tome_layout(u, "set_tome_choice", latent_h, latent_w, &pl)) return -1;
+    SD_REQUIRE(pl->tome_choice_bytes > 0, "set_tome_choice: Token Merging is off (sd_unet_set_tome)");
+    SD_REQUIRE(choice && n == pl->tome_choice_bytes, "set_tome_choice: %lld bytes, the merging blocks at %dx%d take %ld", n, latent_h, latent_w,
+               pl->tome_choice_bytes);
+    if (int rc = ensure_tome_choice(u, n, stream)) return rc;
+    SD_CHECK_HIP(hipMemcpyAsync(u->tome_choice, choice, (size_t)n, hipMemcpyDefault, (hipStream_t)stream));
+    return 0;
+}
+
+// The matching of merging block `block` in the last forward (synchronises the stream): kept [B][num_src - r], merged [B][r],
+// dst_idx [B][r] in src / dst slot numbers and tok [h * w] (host pointers, any may be null); *batch = B, the samples the block
+// matched (half the UNet batch for the first block of a CFG pair: the prompt-independent prefix runs once per latent).
+extern "C" int sd_unet_tome_matching_hw(sd_unet* u, void* stream, int block, int unet_batch, int cache_branch_id, void* workspace,
+                                        int* kept, int* merged, int* dst_idx, int* tok, int* r, int* batch) {
+    SD_REQUIRE(u && u->kind == 0 && workspace, "tome_matching: not a UNet handle, or null workspace");
+    SD_REQUIRE(u->last_h > 0, "tome_matching: no forward has run");
+    Plan* pl;
+    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, u->last_rep, u->last_h, u->last_w, u->last_ip, u->last_cn);
+    if (rc) return rc;
+    SD_REQUIRE(block >= 0 && block < (int)pl->tome.size(), "tome_matching: block %d of %zu", block, pl->tome.size());
+    const Plan::TomeBlock& tb = pl->tome[block];
+    const int N = tb.h * tb.w, num_src = N - N / 4;
+    SD_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    auto get = [&](int* dst, int t, size_t count) -> int {
+        if (!dst || !count) return 0;
+        SD_CHECK_HIP(hipMemcpy(dst, (char*)workspace + pl->tensors[t].off, count * 4, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    if ((rc = get(kept, tb.kept, (size_t)tb.B * (num_src - tb.r)))) return rc;
+    if ((rc = get(merged, tb.merged, (size_t)tb.B * tb.r))) return rc;
+    if ((rc = get(dst_idx, tb.dst_idx, (size_t)tb.B * tb.r))) return rc;
+    if ((rc = get(tok, tb.tok, (size_t)N))) return rc;
+    if (r) *r = tb.r;
+    if (batch) *batch = tb.B;
+    return 0;
 }
 
 // ---- fp8 activation-scale calibration (SD_DTYPE_FP8_E4M3 handles) -------------------------------------------------------
@@ -1185,6 +1294,16 @@ static void op_work(const Op& o, double* flops, double* bytes) {
         case OP_REPLICATE:
             *bytes = 16.0 * o.M * (1.0 + o.N);
             break;
+        case OP_TOME_MATCH: {     // src x dst cosine scores
+            const double N = (double)o.Hin * o.Win;
+            *flops = 2.0 * o.B * (0.75 * N) * (0.25 * N) * o.N;
+            *bytes = 2.0 * o.B * N * o.N;
+            break;
+        }
+        case OP_TOME_MERGE:
+        case OP_TOME_UNMERGE:
+            *bytes = 2.0 * o.B * (2.0 * o.Hin * o.Win - o.K) * (double)o.N;
+            break;
         case OP_RES_ADD:    // x and r in, x out
             *bytes = 3.0 * 2.0 * (double)o.M;      // (M: the elements of all segments)
             break;
@@ -1216,6 +1335,7 @@ static int profiled_run(sd_unet* u, void* stream, const float* latents, int late
     int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, -1, -1, ip, cn);
     if (rc) return rc;
     *plan = pl;
+    if ((rc = ensure_tome_choice(u, pl->tome_choice_bytes, stream))) return rc;
     SD_REQUIRE((long long)pl->total_bytes <= workspace_bytes, "forward_profiled: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     std::vector<hipEvent_t> ev;

@@ -81,7 +81,22 @@ class BaseMethod(ABC):
             self.model.load_controlnet(str(self.config.model.controlnet))
         if self.config.model.get("tiny_vae", None) is not None:        # key of this build: a local AutoencoderTiny directory or a hub name
             self.model.load_tiny_vae(str(self.config.model.tiny_vae), use_for=str(self.config.model.get("tiny_vae_use", "all")))
+        tome = self.parse_tome(self.config.model)      # keys of this build: model.tome_ratio (+ tome_max_downsample, tome_use_rand, tome_seed)
+        if tome is not None:
+            self.model.apply_tome(**tome)
         self.model.to(self.device)
+
+    @staticmethod
+    def parse_tome(model_cfg):
+        """``model.tome_ratio`` / ``tome_max_downsample`` / ``tome_use_rand`` / ``tome_seed`` -> the arguments of
+        ``apply_tome``, or None when ``tome_ratio`` is absent (Token Merging for any method)."""
+        if model_cfg.get("tome_ratio", None) is None:
+            for key in ("tome_max_downsample", "tome_use_rand", "tome_seed"):
+                if model_cfg.get(key, None) is not None:
+                    raise ValueError(f"model.{key} is set but model.tome_ratio is not")
+            return None
+        return dict(ratio=float(model_cfg.tome_ratio), max_downsample=int(model_cfg.get("tome_max_downsample", 1)),
+                    use_rand=bool(model_cfg.get("tome_use_rand", True)), seed=int(model_cfg.get("tome_seed", 0)))
 
     def setup_scheduler(self, **kwargs):
         scheduler_name = self.config.scheduler.scheduler_name

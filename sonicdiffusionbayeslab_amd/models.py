@@ -167,6 +167,96 @@ class StableDiffusionModel:
         self.tiny_vae_use = None
         self.tiny_vae_decoder = None
         self.tiny_vae_encoder = None
+        # Token Merging (apply_tome): dict(ratio, max_downsample, use_rand, seed, rand_every) or None = off; the generator of
+        # the dst choices and the cell count of the call in progress
+        self._tome = None
+        self._tome_gen = None
+        self._tome_cells = 0
+        self._tome_first = False        # the call's first forward uses the choice array _tome_begin uploaded
+
+    # -- Token Merging (tomesd.apply_patch) ----------------------------------------------------------
+    TOME_MAX_RATIO = 0.75
+
+    @staticmethod
+    def check_tome_args(ratio=0.5, max_downsample=1, sx=2, sy=2, use_rand=True, merge_attn=True, merge_crossattn=False,
+                        merge_mlp=False, seed=0, rand_every="step", weight_dtype="bf16"):
+        """The arguments of ``apply_tome`` checked, by name, without touching the GPU.  Returns the setting as a dict, or
+        None for ``ratio == 0`` (off)."""
+        if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0.0 <= float(ratio) <= StableDiffusionModel.TOME_MAX_RATIO:
+            raise ValueError(f"ratio={ratio!r}: Token Merging takes a ratio in [0, {StableDiffusionModel.TOME_MAX_RATIO}] "
+                             "(a 2x2 cell has three src tokens)")
+        if sx != 2 or sy != 2:
+            raise NotImplementedError(f"sx={sx!r}, sy={sy!r}: only 2x2 cells are built")
+        if max_downsample not in (1, 2):
+            raise NotImplementedError(f"max_downsample={max_downsample!r}: 1 (the first level) or 2 (the first two) are built")
+        if not merge_attn:
+            raise NotImplementedError("merge_attn=False: merging around the self-attention is the only form built")
+        if merge_crossattn:
+            raise NotImplementedError("merge_crossattn=True: merging around the cross-attention is not built")
+        if merge_mlp:
+            raise NotImplementedError("merge_mlp=True: merging around the feed-forward is not built")
+        if rand_every not in ("step", "call"):
+            raise ValueError(f"rand_every={rand_every!r}: 'step' (a fresh dst choice before every UNet forward) or 'call'")
+        if float(ratio) > 0.0 and _lib_dtype_is_fp8(weight_dtype):
+            raise NotImplementedError("Token Merging on an fp8 UNet handle is not built (weight_dtype='fp8')")
+        if float(ratio) == 0.0:
+            return None
+        return dict(ratio=float(ratio), max_downsample=int(max_downsample), use_rand=bool(use_rand), seed=int(seed),
+                    rand_every=rand_every)
+
+    def apply_tome(self, ratio: float = 0.5, max_downsample: int = 1, sx: int = 2, sy: int = 2, use_rand: bool = True,
+                   merge_attn: bool = True, merge_crossattn: bool = False, merge_mlp: bool = False, seed: int = 0,
+                   rand_every: str = "step"):
+        """Token Merging for Stable Diffusion (``tomesd.apply_patch``): every later call merges
+        ``min(num_src, int(tokens * ratio))`` tokens around the self-attention of the transformer blocks at the first
+        ``max_downsample`` levels.  The dst token of each 2x2 cell is drawn on the host with ``torch.randint`` from a CPU
+        generator seeded by ``seed`` at the start of a call -- before every UNet forward (``rand_every="step"``) or once per call
+        (``"call"``); ``use_rand=False`` takes the top-left token of every cell.  ``ratio=0`` is ``remove_tome()``."""
+        self._tome = self.check_tome_args(ratio, max_downsample, sx, sy, use_rand, merge_attn, merge_crossattn, merge_mlp, seed,
+                                          rand_every, self.weight_dtype)
+        return self
+
+    def remove_tome(self):
+        """Later calls are those of a model that never saw Token Merging, bit for bit."""
+        self._tome = None
+        return self
+
+    @staticmethod
+    def draw_tome_choice(generator: torch.Generator, cells: int) -> torch.Tensor:
+        """The dst positions (0..3) of all merging blocks of one forward: one draw, whatever the rank or world size."""
+        return torch.randint(4, (cells,), generator=generator, dtype=torch.uint8)
+
+    def _tome_upload(self):
+        choice = self.draw_tome_choice(self._tome_gen, self._tome_cells) if self._tome["use_rand"] else \
+            torch.zeros(self._tome_cells, dtype=torch.uint8)
+        self.unet.set_tome_choice(choice.pin_memory().to(self.unet.device, non_blocking=True), *self.latent_size)
+
+    def _tome_begin(self):
+        """Start of a sampling loop: the setting onto the UNet handle, a fresh generator, the call's first choice array."""
+        t = self._tome
+        self._tome_gen = None
+        if t is None:
+            self.unet.set_tome(0.0)
+            return
+        self.unet.set_tome(t["ratio"], t["max_downsample"])
+        blocks = self.unet.tome_blocks(*self.latent_size)
+        self._tome_cells = sum((b["h"] // 2) * (b["w"] // 2) for b in blocks)
+        self._tome_gen = torch.Generator().manual_seed(t["seed"])
+        if self._tome_cells:
+            self._tome_upload()
+        self._tome_first = True
+
+    def _tome_step(self):
+        """Before every UNet forward: ``rand_every="step"`` uploads a fresh dst choice (the first forward uses the one
+        ``_tome_begin`` drew)."""
+        t = self._tome
+        if t is None or self._tome_gen is None or not self._tome_cells:
+            return
+        if self._tome_first:
+            self._tome_first = False
+            return
+        if t["use_rand"] and t["rand_every"] == "step":
+            self._tome_upload()
 
     # -- loading ---------------------------------------------------------------------------
     @classmethod
@@ -869,6 +959,7 @@ class StableDiffusionModel:
         """Initial latents at the call's size, DeepCache branch and prompt context of the UNet."""
         c = self.unet_config
         latents = self.prepare_latents(batch_size, LATENT_CHANNELS, self._size[0], self._size[1], device, generator, latents)
+        self._tome_begin()              # (before the context: the setting is part of the UNet's plans)
         self.unet.set_deepcache(cache_branch_id)
         self.unet.set_context(ctx, *self.latent_size)
         self._apply_ip_adapter(ctx.shape[0] == 2 * batch_size and self.do_classifier_free_guidance)
@@ -1062,6 +1153,7 @@ class StableDiffusionModel:
             if dc is not None:
                 mode = CACHE_FULL_AND_STORE if ts_host.index(t) % dc.cache_interval == 0 else CACHE_SKIP
             self._control_step(i, len(ts_host), latents, unet_batch, t)
+            self._tome_step()
             self.unet.forward_latents(latents, unet_batch, float(t), out=eps, cache_mode=mode)
             kw = {}
             if is_lcm and step_noise is not None and i < len(ts_host) - 1:
@@ -1185,6 +1277,7 @@ class StableDiffusionModel:
             mode = CACHE_OFF
             if dc is not None:
                 mode = CACHE_FULL_AND_STORE if ts_host.index(t) % dc.cache_interval == 0 else CACHE_SKIP
+            self._tome_step()
             self.unet.forward_latents(latents, unet_batch, float(t), out=eps, cache_mode=mode)
             kw = {}
             if is_lcm and step_noise is not None and i < len(ts_host) - 1:
@@ -1282,6 +1375,7 @@ class StableDiffusionModel:
                 cur = ts_host.index(t)      # first match, as DeepCache's list.index (duplicate PNDM timestep quirk)
                 mode = CACHE_FULL_AND_STORE if (cur - 0) % dc.cache_interval == 0 else CACHE_SKIP
             self._control_step(i, len(ts_host), latents, unet_batch, t)
+            self._tome_step()
             self.unet.forward_latents(latents, unet_batch, float(t), out=eps, cache_mode=mode)     # :217-235
             kw = {}
             if is_lcm and step_noise is not None and i < len(ts_host) - 1:
@@ -1332,6 +1426,7 @@ class _VariantBase(StableDiffusionModel):
 
     def _step_with(self, sched, eps, latents, t, unet_batch, do_cfg, guidance_scale, eta, generator, x0_preds,
                    guidance_rescale=0.0):
+        self._tome_step()
         self.unet.forward_latents(latents, unet_batch, float(t), out=eps, cache_mode=CACHE_OFF)
         kw = {"guidance_rescale": guidance_rescale} if do_cfg and guidance_rescale > 0.0 else {}   # :583-590
         step = sched.step_fused(eps, guidance_scale, latents, t, cfg=do_cfg, eta=eta, generator=generator, **kw)

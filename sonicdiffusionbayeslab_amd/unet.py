@@ -92,6 +92,8 @@ class HipUNet2DConditionModel:
         self.ip_adapter_scale = 1.0         # scale __call__(added_cond_kwargs=...) applies (diffusers: set_ip_adapter_scale)
         # ControlNet residuals on the handle: (buffer kept alive, scale, unet batch, h, w) or None (the plain plans)
         self._control = None
+        self._tome = None                   # (ratio, max_downsample) of the Token Merging setting on the handle, None = off
+        self._tome_choice_keepalive = None
         self.cache_branch_id = -1
 
     def __del__(self):
@@ -284,6 +286,69 @@ class HipUNet2DConditionModel:
             _lib.check(self._lib.sd_unet_set_control_residuals_hw(self._handle, None, 0.0, 0, 0, 0), "sd_unet_set_control_residuals_hw")
             self._control = None
 
+    # -- Token Merging (include/sd_hip.h::sd_unet_set_tome) -----------------------------------------
+    def set_tome(self, ratio: float, max_downsample: int = 1) -> None:
+        """Merge ``r = min(num_src, int(tokens * ratio))`` src tokens around the self-attention of every transformer block
+        whose level is at most ``max_downsample`` times coarser than the latent (``ratio`` 0: off, the handle of before).  A
+        change needs a new workspace and a new ``set_context``; both follow from dropping the workspace key here."""
+        ratio = float(ratio)
+        if ratio > 0.0 and self.weight_dtype != "bf16":
+            raise NotImplementedError("Token Merging on an fp8 UNet handle is not built")
+        _lib.check(self._lib.sd_unet_set_tome(self._handle, ratio, int(max_downsample) if ratio > 0.0 else 0), "sd_unet_set_tome")
+        new = (ratio, int(max_downsample)) if ratio > 0.0 else None
+        if new != self._tome:
+            self._tome = new
+            self._ws_key = None
+            self._tome_choice_keepalive = None
+
+    def tome_blocks(self, height: Optional[int] = None, width: Optional[int] = None):
+        """The merging blocks at a latent size, in plan order: dicts of ``h``, ``w`` (token grid), ``r`` and ``choice_off``
+        (where the block's ``h/2 * w/2`` choice bytes start in the array of ``set_tome_choice``).  Empty while off."""
+        lh, lw = self.latent_size(height, width)
+        n = self._lib.sd_unet_tome_block_count_hw(self._handle, lh, lw)
+        if n < 0:
+            _lib.check(-1, "sd_unet_tome_block_count_hw")
+        out = []
+        for i in range(n):
+            h, w, r, off = C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
+            _lib.check(self._lib.sd_unet_tome_block_info_hw(self._handle, i, lh, lw, C.byref(h), C.byref(w), C.byref(r), C.byref(off)),
+                       "sd_unet_tome_block_info_hw")
+            out.append(dict(h=h.value, w=w.value, r=r.value, choice_off=off.value))
+        return out
+
+    def set_tome_choice(self, choice: torch.Tensor, height: Optional[int] = None, width: Optional[int] = None) -> None:
+        """``choice``: uint8, the dst position (0..3) of every 2x2 cell of every merging block, concatenated in plan order
+        (``tome_blocks``); one asynchronous copy on the current stream.  A host tensor should be pinned and is kept alive until
+        the next call."""
+        lh, lw = self.latent_size(height, width)
+        if not torch.is_tensor(choice) or choice.dtype != torch.uint8 or choice.dim() != 1 or not choice.is_contiguous():
+            raise ValueError("choice must be a contiguous 1-D uint8 tensor")
+        _lib.check(self._lib.sd_unet_set_tome_choice_hw(self._handle, _lib.current_stream(), choice.data_ptr(), choice.numel(), lh, lw),
+                   "sd_unet_set_tome_choice_hw")
+        self._tome_choice_keepalive = choice
+
+    def tome_matching(self, block: int, unet_batch: int, height: Optional[int] = None, width: Optional[int] = None):
+        """What the last forward matched in merging block ``block``: dict of int32 CPU tensors ``kept`` [B, num_src - r],
+        ``merged`` [B, r], ``dst_idx`` [B, r] (src / dst slot numbers), ``tok`` [h * w] (token index of every src slot, then
+        of every dst slot) and ``r``; B is half the UNet batch for the first block of a CFG pair.  Synchronises."""
+        lh, lw = self.latent_size(height, width)
+        info = self.tome_blocks(lh, lw)[block]
+        n = info["h"] * info["w"]
+        num_src, r = n - n // 4, info["r"]
+        kept = torch.full((unet_batch, num_src - r), -1, dtype=torch.int32)
+        merged = torch.full((unet_batch, r), -1, dtype=torch.int32)
+        dst_idx = torch.full((unet_batch, r), -1, dtype=torch.int32)
+        tok = torch.full((n,), -1, dtype=torch.int32)
+        rr, bb = C.c_int(), C.c_int()
+        ws = self._workspace(unet_batch, lh, lw)
+        _lib.check(self._lib.sd_unet_tome_matching_hw(self._handle, _lib.current_stream(), block, unet_batch, self.cache_branch_id,
+                                                      self._ws_ptr(ws), kept.data_ptr(), merged.data_ptr(), dst_idx.data_ptr(),
+                                                      tok.data_ptr(), C.byref(rr), C.byref(bb)), "sd_unet_tome_matching_hw")
+        b = bb.value
+        # (the library wrote B rows contiguously at the row lengths above)
+        return dict(kept=kept.reshape(-1)[:b * (num_src - r)].reshape(b, num_src - r), merged=merged.reshape(-1)[:b * r].reshape(b, r),
+                    dst_idx=dst_idx.reshape(-1)[:b * r].reshape(b, r), tok=tok, r=rr.value)
+
     # -- forward ---------------------------------------------------------------------------
     def forward_latents(self, latents: torch.Tensor, unet_batch: int, timestep: float,
                         out: Optional[torch.Tensor] = None, cache_mode: int = CACHE_OFF) -> torch.Tensor:
@@ -360,7 +425,8 @@ class HipUNet2DConditionModel:
 
     KIND_NAMES = {0: "sinusoid", 1: "gemv", 2: "conv_in", 3: "groupnorm", 4: "conv3x3", 5: "gemm", 6: "layernorm",
                   7: "attention", 8: "conv_out", 16: "conv3x3_fp8", 17: "gemm_fp8", 18: "xattn_fused",
-                  19: "replicate", 20: "conv3x3_gemm", 21: "conv3x3_halo_subpix", 22: "ip_xattn", 23: "residual_add"}
+                  19: "replicate", 20: "conv3x3_gemm", 21: "conv3x3_halo_subpix", 22: "ip_xattn", 23: "residual_add",
+                  27: "tome_match", 28: "tome_select", 29: "tome_merge", 30: "tome_unmerge"}
 
     def forward_profiled(self, latents: torch.Tensor, unet_batch: int, timestep: float, cache_mode: int = CACHE_OFF):
         """One forward with a hipEvent pair around every launch (measurement only, synchronises).

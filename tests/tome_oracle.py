@@ -1,0 +1,211 @@
+"""Token Merging for Stable Diffusion (``tomesd``) restated in fp32 / fp64 torch: TEST INFRASTRUCTURE.
+
+Semantics.  A level of ``h x w`` tokens is cut into 2x2 cells; ``choice[cell]`` in 0..3 (row-major inside the
+cell) names the cell's *dst* token, the other three are *src* tokens.  dst slots are numbered by cell (row-major), src slots by
+ascending token index.  Every src token is matched to the dst token of largest cosine similarity (ties: the lowest dst slot);
+the ``r`` src tokens with the largest similarity (ties at the cut: the lowest src slot) are merged into their dst token by a
+mean that includes the dst itself; the merged sequence is ``[kept src (ascending slot) | all dst]``; unmerge copies every row
+back to its token and gives a merged src token its dst's row.
+
+``transformer_block`` / ``unet_forward`` run the oracle's UNet (``oracle.unet``, and ``tests.sd2_oracle`` for per-level head
+counts) with the merge around ``attn1`` of the blocks whose level is at most ``max_downsample`` times coarser than the sample.
+``TomeRun`` carries, per merging block in call order (down, mid, up: the library's plan order), either the matching to use
+(``kept`` / ``merged`` / ``dst_idx`` read back from the library) or nothing, in which case the oracle matches on its own.
+"""
+from __future__ import annotations
+
+import contextlib
+from typing import List, Optional
+
+import torch
+import torch.nn.functional as F
+
+
+def partition(choice: torch.Tensor, h: int, w: int):
+    """(src_tok [num_src], dst_tok [num_dst]) int64 token indices from ``choice`` [h/2 * w/2] (values 0..3)."""
+    assert h % 2 == 0 and w % 2 == 0 and choice.numel() == (h // 2) * (w // 2)
+    c = choice.reshape(h // 2, w // 2).long()
+    cy, cx = torch.meshgrid(torch.arange(h // 2), torch.arange(w // 2), indexing="ij")
+    dst_tok = ((2 * cy + c // 2) * w + 2 * cx + c % 2).reshape(-1)
+    is_dst = torch.zeros(h * w, dtype=torch.bool)
+    is_dst[dst_tok] = True
+    src_tok = torch.nonzero(~is_dst).reshape(-1)
+    return src_tok, dst_tok
+
+
+def num_merged(n_tokens: int, ratio: float) -> int:
+    return min(n_tokens - n_tokens // 4, int(n_tokens * ratio))
+
+
+def scores(x: torch.Tensor, src_tok, dst_tok, dtype=torch.float64) -> torch.Tensor:
+    """Cosine similarities [B, num_src, num_dst]; an all-zero row gives zeros, never NaN."""
+    xx = x.to(dtype)
+    nrm = xx.norm(dim=-1, keepdim=True)
+    m = torch.where(nrm > 0, xx / nrm.clamp_min(torch.finfo(dtype).tiny), torch.zeros_like(xx))
+    return m[:, src_tok] @ m[:, dst_tok].transpose(1, 2)
+
+
+def first_argmax(s: torch.Tensor):
+    """(max, index of the FIRST maximum) along the last dim."""
+    mx = s.max(dim=-1, keepdim=True).values
+    idx = torch.where(s == mx, torch.arange(s.shape[-1]).expand_as(s), torch.full_like(s, s.shape[-1], dtype=torch.long)).min(-1).values
+    return mx.squeeze(-1), idx
+
+
+def select(node_max: torch.Tensor, r: int):
+    """Top ``r`` per sample with ties to the lowest src slot -> (kept [B, num_src - r], merged [B, r]), both ascending."""
+    order = torch.argsort(-(node_max.double() + 0.0), dim=-1, stable=True)        # (+ 0.0: -0 and +0 compare equal anyway)
+    return order[:, r:].sort(-1).values, order[:, :r].sort(-1).values
+
+
+def match(x: torch.Tensor, choice: torch.Tensor, h: int, w: int, r: int, dtype=torch.float64):
+    """The whole matching of one block: dict(src_tok, dst_tok, node_max, node_idx, kept, merged, dst_idx, r)."""
+    src_tok, dst_tok = partition(choice, h, w)
+    node_max, node_idx = first_argmax(scores(x, src_tok, dst_tok, dtype))
+    kept, merged = select(node_max, r)
+    return dict(src_tok=src_tok, dst_tok=dst_tok, node_max=node_max, node_idx=node_idx, kept=kept, merged=merged,
+                dst_idx=torch.gather(node_idx, 1, merged), r=r)
+
+
+def merge(x: torch.Tensor, src_tok, dst_tok, kept, merged, dst_idx) -> torch.Tensor:
+    """[B, N, C] -> [B, N - r, C]: kept src rows, then every dst row averaged with its members (the mean includes the dst)."""
+    B, N, C = x.shape
+    out = []
+    for b in range(B):
+        dst = x[b, dst_tok].clone()
+        cnt = torch.ones(dst_tok.numel(), dtype=x.dtype)
+        if merged.shape[1]:
+            dst.index_add_(0, dst_idx[b].long(), x[b, src_tok[merged[b].long()]])
+            cnt.index_add_(0, dst_idx[b].long(), torch.ones(merged.shape[1], dtype=x.dtype))
+        out.append(torch.cat([x[b, src_tok[kept[b].long()]], dst / cnt[:, None]]))
+    return torch.stack(out)
+
+
+def member_counts(dst_idx: torch.Tensor, num_dst: int) -> torch.Tensor:
+    """[B, num_dst]: 1 + the number of src tokens merged into each dst."""
+    cnt = torch.ones(dst_idx.shape[0], num_dst, dtype=torch.long)
+    for b in range(dst_idx.shape[0]):
+        cnt[b].index_add_(0, dst_idx[b].long(), torch.ones(dst_idx.shape[1], dtype=torch.long))
+    return cnt
+
+
+def row_of(src_tok, dst_tok, kept, merged, dst_idx) -> torch.Tensor:
+    """[B, N]: the row of the merged sequence every token reads at unmerge."""
+    B, nk = kept.shape
+    N = src_tok.numel() + dst_tok.numel()
+    rows = torch.full((B, N), -1, dtype=torch.long)
+    for b in range(B):
+        rows[b, src_tok[kept[b].long()]] = torch.arange(nk)
+        rows[b, dst_tok] = nk + torch.arange(dst_tok.numel())
+        rows[b, src_tok[merged[b].long()]] = nk + dst_idx[b].long()
+    assert (rows >= 0).all()
+    return rows
+
+
+def unmerge(y: torch.Tensor, src_tok, dst_tok, kept, merged, dst_idx) -> torch.Tensor:
+    """[B, N - r, C] -> [B, N, C]."""
+    rows = row_of(src_tok, dst_tok, kept, merged, dst_idx)
+    return torch.stack([y[b, rows[b]] for b in range(y.shape[0])])
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the UNet with Token Merging
+# ----------------------------------------------------------------------------------------------------------------------
+class TomeRun:
+    """State of one oracle forward.  ``choices``: per merging block the uint8 choice array; ``given``: per merging block a dict
+    with ``kept`` / ``merged`` / ``dst_idx`` [B, ...] to use, or None (or a shorter list) to let the oracle match itself.
+    ``used`` collects the matching every merging block ran with."""
+
+    def __init__(self, sample_hw, ratio: float, max_downsample: int, choices: List[torch.Tensor], given: Optional[list] = None):
+        self.sample_hw, self.ratio, self.max_downsample = sample_hw, ratio, max_downsample
+        self.choices, self.given = list(choices), list(given or [])
+        self.used = []
+
+    def merges(self, hh: int) -> bool:
+        return self.ratio > 0 and self.sample_hw[0] // hh <= self.max_downsample
+
+
+def transformer_block(w, p: str, x: torch.Tensor, ctx: torch.Tensor, cfg, fq=None, run: Optional[TomeRun] = None) -> torch.Tensor:
+    """``oracle.unet.transformer_block`` with the merge around attn1 on a merging level."""
+    import oracle.unet as ou
+    b, c, hh, ww = x.shape
+    if run is None or not run.merges(hh):
+        return _ORIG["unet"](w, p, x, ctx, cfg, fq)
+    assert fq is None, "Token Merging on fp8 handles is not built"
+    ou._tick()
+    i = len(run.used)
+    res = x
+    h = F.group_norm(x, cfg.norm_num_groups, w[p + "norm.weight"], w[p + "norm.bias"], 1e-6)
+    h = F.conv2d(h, w[p + "proj_in.weight"], w[p + "proj_in.bias"])
+    h = h.permute(0, 2, 3, 1).reshape(b, hh * ww, c)
+    t = p + "transformer_blocks.0."
+    r = num_merged(hh * ww, run.ratio)
+    given = run.given[i] if i < len(run.given) else None
+    if given is None:
+        m = match(h, run.choices[i], hh, ww, r, dtype=torch.float32)
+    else:
+        src_tok, dst_tok = partition(run.choices[i], hh, ww)
+        m = dict(src_tok=src_tok, dst_tok=dst_tok, r=r, **{k: given[k].long() for k in ("kept", "merged", "dst_idx")})
+        assert m["merged"].shape == (b, r) and m["kept"].shape == (b, src_tok.numel() - r)
+    run.used.append(m)
+    args = (m["src_tok"], m["dst_tok"], m["kept"], m["merged"], m["dst_idx"])
+    n1 = F.layer_norm(h, (c,), w[t + "norm1.weight"], w[t + "norm1.bias"], 1e-5)
+    n1m = merge(n1, *args)
+    h = h + unmerge(ou._attention(w, t + "attn1.", n1m, n1m, cfg.num_heads), *args)
+    n2 = F.layer_norm(h, (c,), w[t + "norm2.weight"], w[t + "norm2.bias"], 1e-5)
+    h = h + ou._attention(w, t + "attn2.", n2, ctx, cfg.num_heads)
+    n3 = F.layer_norm(h, (c,), w[t + "norm3.weight"], w[t + "norm3.bias"], 1e-5)
+    proj = F.linear(n3, w[t + "ff.net.0.proj.weight"], w[t + "ff.net.0.proj.bias"])
+    a, gate = proj.chunk(2, dim=-1)
+    h = h + F.linear(a * F.gelu(gate), w[t + "ff.net.2.weight"], w[t + "ff.net.2.bias"])
+    h = h.reshape(b, hh, ww, c).permute(0, 3, 1, 2)
+    h = F.conv2d(h, w[p + "proj_out.weight"], w[p + "proj_out.bias"])
+    return h + res
+
+
+_ORIG = {}
+
+
+@contextlib.contextmanager
+def _patched(run: TomeRun):
+    """``oracle.unet.unet_forward`` and ``tests.sd2_oracle.sd2_unet_forward`` look ``transformer_block`` up in their module:
+    for the duration of one forward it is the function above."""
+    import oracle.unet as ou
+    import tests.sd2_oracle as s2
+    _ORIG["unet"] = ou.transformer_block
+    orig2 = s2.transformer_block
+
+    def tb(w, p, x, ctx, cfg, fq=None):
+        return transformer_block(w, p, x, ctx, cfg, fq, run)
+    ou.transformer_block = tb
+    s2.transformer_block = tb
+    try:
+        yield
+    finally:
+        ou.transformer_block = _ORIG.pop("unet")
+        s2.transformer_block = orig2
+
+
+ATTN1_GAIN = 4.0
+
+
+def tome_test_weights(sd):
+    """The synthetic weights with every ``attn1.to_out.0.weight`` times ATTN1_GAIN (a power of two: still on the bf16 grid).
+    With the plain synthetic weights the self-attention moves the residual stream so little that merging half the tokens
+    changes eps by 0.12 .. 0.19 rel-L2 at 16x16 / 16x24 latents, whatever the seed, timestep or ratio: below the 10 x UNET_TOL
+    a test wants between "with" and "without".  At gain 4 the oracle's own distance is 0.25 .. 0.31 (tests/test_tome_cpu.py)."""
+    out = dict(sd)
+    for k in sd:
+        if k.endswith("attn1.to_out.0.weight"):
+            out[k] = sd[k] * ATTN1_GAIN
+    return out
+
+
+def unet_forward(w, cfg, sample, t, ctx, run: TomeRun, heads_per_level=None, **kw):
+    """eps of the oracle UNet with Token Merging as ``run`` describes it (``heads_per_level``: the SD 2.x-shaped oracle)."""
+    with _patched(run), torch.no_grad():
+        if heads_per_level is not None:
+            from tests.sd2_oracle import sd2_unet_forward
+            return sd2_unet_forward(w, cfg, heads_per_level, sample, t, ctx, **kw)
+        from oracle.unet import unet_forward as plain
+        return plain(w, cfg, sample, t, ctx, **kw)
