@@ -61,6 +61,30 @@ CONV64_CASES = [
     ("s2 9x35", 2, 9, 35, 2, False, False, False),
 ]
 
+# Past one round.  The grid is min(ntiles, 256) and every case above has at most 18 tiles: no workgroup there takes a second
+# tile, so neither the prefetch into the other halo buffer nor the buffer flip is exercised.  The cases below have 2 x 19 x 14
+# = 532 tiles each: work indices 0 .. 19 run three rounds (the third is the first that reads a halo buffer after a refill),
+# the others two (the `t + nblk < ntiles` guard decides), the sample boundary falls at tile 266 in the middle of round 2, and
+# the bottom and right tiles are ragged (150 = 18 x 8 + 6, 420 = 13 x 32 + 4; mode 2: 75 = 18 x 4 + 3, 210 = 13 x 16 + 2).
+CONV64_THREE_ROUNDS = [
+    ("plain+b+R+relu 150x420 3 rounds", 2, 150, 420, 0, True, True, True),
+    ("plain+b+relu 150x420 3 rounds", 2, 150, 420, 0, True, False, True),
+    ("up 75x210 3 rounds", 2, 75, 210, 1, False, False, False),
+    ("s2 149x419 3 rounds", 2, 149, 419, 2, False, False, False),
+]
+CONV64_CASES += CONV64_THREE_ROUNDS
+CONV64_GRID_CAP = 256
+
+
+def _conv64_out(n, mode):
+    return 2 * n if mode == 1 else (n - 1) // 2 + 1 if mode == 2 else n
+
+
+def _conv64_ntiles(B, Hin, Win, mode):
+    """The tile count of csrc/conv64.hip restated: output tiles of 8 rows x 32 columns (modes 0 and 1) or 4 x 16 (mode 2)."""
+    tr, tc = (4, 16) if mode == 2 else (8, 32)
+    return B * (-(-_conv64_out(Hin, mode) // tr)) * (-(-_conv64_out(Win, mode) // tc))
+
 
 def _pack64(sdlib, w):
     n = sdlib.sd_op_conv64_pack(None, None)
@@ -73,6 +97,10 @@ def _pack64(sdlib, w):
 
 @pytest.mark.parametrize("name,B,H,W,mode,has_b,has_r,relu", CONV64_CASES, ids=[c[0] for c in CONV64_CASES])
 def test_conv64_per_element(sdlib, name, B, H, W, mode, has_b, has_r, relu):
+    if any(name == c[0] for c in CONV64_THREE_ROUNDS):
+        ntiles = _conv64_ntiles(B, H, W, mode)
+        assert ntiles > 2 * CONV64_GRID_CAP, ntiles              # some workgroups run three rounds ...
+        assert ntiles % CONV64_GRID_CAP != 0, ntiles             # ... and the others one fewer: the prefetch guard matters
     g = torch.Generator().manual_seed(1000 * mode + H * W + B)
     x = r16(torch.randn(B, 64, H, W, generator=g))
     w = r16(torch.randn(64, 64, 3, 3, generator=g) / math.sqrt(576))
@@ -106,6 +134,79 @@ def test_conv64_refuses_bad_arguments(sdlib):
     assert sdlib.sd_op_conv64(stream(), x.data_ptr(), w.data_ptr(), None, None, x.data_ptr(), 1, 8, 8, 0, 0) != 0     # in place
     assert sdlib.sd_op_conv64(stream(), x.data_ptr(), w.data_ptr(), None, None, y.data_ptr(), 0, 8, 8, 0, 0) != 0
     assert sdlib.sd_op_conv64(stream(), x.data_ptr(), None, None, None, y.data_ptr(), 1, 8, 8, 0, 0) != 0
+    # 31 x 1024 x 1024 pixels x 128 bytes = 4.16e9 > 0xf0000000: past the 32-bit DMA offsets, refused before any launch
+    assert sdlib.sd_op_conv64(stream(), x.data_ptr(), w.data_ptr(), None, None, y.data_ptr(), 31, 1024, 1024, 0, 0) != 0
+    msg = sdlib.sd_last_error().decode()
+    assert str(31 * 1024 * 1024 * 128) in msg and str(0xf0000000) in msg, msg
+
+
+# ---------------------------------------------------------------- sd_op_conv64 with DMA offsets at and above 2^31
+def _conv64_crop_check(what, xs, ys, w, b, relu, mode, oy0, oy1, ox0, ox1):
+    """Outputs [oy0, oy1) x [ox0, ox1) of one sample per element on the host: xs [H, W, 64] and ys [Ho, Wo, 64] stay on the
+    device, only the input window with its one-pixel rim and the output window come back.  The reference pads the window
+    with zeros, which is the image's padding only where the window ends at the image's edge: an output is compared if every
+    row and column of its 3x3 support lies inside the window or outside the image."""
+    H, W = xs.shape[:2]
+    st = 2 if mode == 2 else 1
+
+    def window(o0, o1, n):
+        i0 = max(st * o0 - st, 0)                                 # (a multiple of the stride: reference row r is output i0 / st + r)
+        i1 = min(st * (o1 - 1) + 2, n)
+        r = torch.arange((i1 - i0 - 1) // st + 1)
+        ok = ((st * r - 1 >= 0) | (i0 == 0)) & ((st * r + 1 <= i1 - i0 - 1) | (i1 == n))
+        return i0, i1, i0 // st, ok
+
+    iy0, iy1, ry0, oky = window(oy0, oy1, H)
+    ix0, ix1, rx0, okx = window(ox0, ox1, W)
+    ref, mag = conv3x3_nhwc_ref(xs[iy0:iy1, ix0:ix1].float().cpu().permute(2, 0, 1)[None], w, b, stride=st)
+    got = ys[ry0:ry0 + ref.shape[1], rx0:rx0 + ref.shape[2]].float().cpu()[None]
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    rows, cols = torch.nonzero(oky).flatten() + ry0, torch.nonzero(okx).flatten() + rx0
+    assert set(range(oy0, oy1)) <= set(rows.tolist()) and set(range(ox0, ox1)) <= set(cols.tolist())
+    ref, mag, got = (t[:, oky][:, :, okx] for t in (ref, mag, got))
+    if relu:
+        clipped = float((ref <= 0).double().mean())
+        assert 0.35 < clipped < 0.65, clipped
+        ref = ref.clamp(min=0.0)
+    print(f"conv64 {what} rows {int(rows[0])}..{int(rows[-1])} cols {int(cols[0])}..{int(cols[-1])}: rel-L2 {rel_l2(got, ref):.3e}")
+    assert_elementwise(got, ref, linear_bound(ref, mag, 576), f"conv64 {what}", NHWC)
+
+
+def test_conv64_offsets_past_2g(sdlib):
+    """A halo's source offset is a 32-bit byte offset into the input.  17 images of 1024 x 1024 pixels are 2.28e9 bytes and
+    sample 16 starts at byte 2^31 exactly: every offset of that sample has its top bit set.  Samples 0, 15 and 16 alone (all
+    offsets below 2^27, the arithmetic test_conv64_per_element checks) must give their slices of the batched output bit for
+    bit; three windows of sample 16 are checked per element on the host.  Nothing of full size leaves the device."""
+    B, S = 17, 1024
+    assert (B - 1) * S * S * 128 == 2 ** 31 and B * S * S * 128 <= 0xf0000000
+    g = torch.Generator().manual_seed(2031)
+    w = r16(torch.randn(64, 64, 3, 3, generator=g) / math.sqrt(576))
+    b = 0.1 * torch.randn(64, generator=g)
+    x = torch.randn(B, S, S, 64, device="cuda", dtype=torch.bfloat16, generator=torch.Generator(device="cuda").manual_seed(2031))
+    xd = guarded_input(x, torch.bfloat16)
+    del x
+    wd, bd = guarded_input(_pack64(sdlib, w), torch.bfloat16), guarded_input(b)
+    # mode 0 with bias and ReLU, mode 2 with no epilogue
+    for mode, relu in ((0, True), (2, False)):
+        So = _conv64_out(S, mode)
+        out = guarded((B, So, So, 64), torch.bfloat16)
+        _lib.check(sdlib.sd_op_conv64(stream(), xd.data_ptr(), wd.data_ptr(), _lib.ptr(bd if relu else None), None, out.data_ptr(),
+                                      B, S, S, mode, 1 if relu else 0))
+        torch.cuda.synchronize()
+        assert not bool(torch.isnan(out).any()), f"mode {mode}: NaN left in the output"
+        for s in (0, 15, 16):
+            one = guarded((1, So, So, 64), torch.bfloat16)
+            _lib.check(sdlib.sd_op_conv64(stream(), xd[s:s + 1].data_ptr(), wd.data_ptr(), _lib.ptr(bd if relu else None), None,
+                                          one.data_ptr(), 1, S, S, mode, 1 if relu else 0))
+            torch.cuda.synchronize()
+            assert torch.equal(one, out[s:s + 1]), f"mode {mode}: sample {s} alone differs from its slice of the batch"
+        # the top-left and bottom-right corners of the image and a window across the tile corner at the output's centre
+        # (a multiple of 8 x 32 and of 4 x 16)
+        c = So // 2
+        for tag, (oy0, ox0) in (("top left", (0, 0)), ("bottom right", (So - 24, So - 48)), ("tile corner", (c - 12, c - 24))):
+            _conv64_crop_check(f"mode {mode} past 2^31, {tag}", xd[16], out[16], w, b if relu else None, relu, mode,
+                               oy0, oy0 + 24, ox0, ox0 + 48)
+    check_guards()
 
 
 # ---------------------------------------------------------------- entry and exit kernels per element
@@ -193,7 +294,7 @@ def _gate(what, got, ref32, ref_bf16):
     assert e <= 2 * floor and c > 0.999, (what, e, floor, c)
 
 
-@pytest.mark.parametrize("shape,seed", [((2, 4, 8, 8), 5), ((2, 4, 16, 24), 6)])
+@pytest.mark.parametrize("shape,seed", [((2, 4, 8, 8), 5), ((2, 4, 16, 24), 6), ((1, 4, 64, 64), 11)])      # (512 pixels: 4 rounds)
 def test_decoder_matches_oracle(tiny, shape, seed):
     sd, oracle, dec, _ = tiny
     z = torch.randn(shape, generator=torch.Generator().manual_seed(seed))
@@ -206,7 +307,7 @@ def test_decoder_matches_oracle(tiny, shape, seed):
     assert float((unit - (got / 2 + 0.5).clamp(0, 1)).abs().max()) <= 2.0 ** -22
 
 
-@pytest.mark.parametrize("shape,seed", [((2, 3, 64, 64), 7), ((2, 3, 128, 192), 8)])
+@pytest.mark.parametrize("shape,seed", [((2, 3, 64, 64), 7), ((2, 3, 128, 192), 8), ((1, 3, 512, 512), 12)])
 def test_encoder_matches_oracle(tiny, shape, seed):
     sd, oracle, _, enc = tiny
     img = _image(shape[0], shape[2], shape[3], seed)
@@ -240,6 +341,15 @@ def test_batch_and_order_independence(tiny):
     assert torch.equal(e, enc.encode(img))
     assert torch.equal(enc.encode(img[1:2]), e[1:2])
     assert torch.equal(enc.encode(img, chunk=1), e)
+    # three full rounds against one: 256 top-level tiles per image, so a B = 1 call never loops and the B = 3 call takes every
+    # workgroup through the work loop exactly three times
+    z = torch.randn((3, 4, 32, 32), generator=torch.Generator().manual_seed(13)).cuda()
+    a = dec.decode(z)
+    img = _image(3, 256, 256, 14).cuda()
+    e = enc.encode(img)
+    for i in range(3):
+        assert torch.equal(dec.decode(z[i:i + 1]), a[i:i + 1]), i
+        assert torch.equal(enc.encode(img[i:i + 1]), e[i:i + 1]), i
 
 
 # ---------------------------------------------------------------- pipeline
