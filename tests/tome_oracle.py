@@ -15,7 +15,7 @@ counts) with the merge around ``attn1`` of the blocks whose level is at most ``m
 from __future__ import annotations
 
 import contextlib
-from typing import List, Optional
+from typing import Optional
 
 import torch
 import torch.nn.functional as F
@@ -112,17 +112,52 @@ def unmerge(y: torch.Tensor, src_tok, dst_tok, kept, merged, dst_idx) -> torch.T
 # the UNet with Token Merging
 # ----------------------------------------------------------------------------------------------------------------------
 class TomeRun:
-    """State of one oracle forward.  ``choices``: per merging block the uint8 choice array; ``given``: per merging block a dict
-    with ``kept`` / ``merged`` / ``dst_idx`` [B, ...] to use, or None (or a shorter list) to let the oracle match itself.
-    ``used`` collects the matching every merging block ran with."""
+    """State of one oracle forward.  ``choices``: per merging block the uint8 choice array -- or ONE 1-D uint8 tensor, the
+    library's layout (``set_tome_choice``): every merging block takes its ``h/2 * w/2`` bytes in call order; ``given``: per
+    merging block a dict with ``kept`` / ``merged`` / ``dst_idx`` [B, ...] to use, or None (or a shorter list) to let the oracle
+    match itself.  ``used`` collects the matching every merging block ran with."""
 
-    def __init__(self, sample_hw, ratio: float, max_downsample: int, choices: List[torch.Tensor], given: Optional[list] = None):
+    def __init__(self, sample_hw, ratio: float, max_downsample: int, choices, given: Optional[list] = None):
         self.sample_hw, self.ratio, self.max_downsample = sample_hw, ratio, max_downsample
-        self.choices, self.given = list(choices), list(given or [])
+        self.flat = choices if torch.is_tensor(choices) else None
+        self.choices, self.given = ([] if self.flat is not None else list(choices)), list(given or [])
         self.used = []
 
     def merges(self, hh: int) -> bool:
         return self.ratio > 0 and self.sample_hw[0] // hh <= self.max_downsample
+
+    def choice(self, i: int, hh: int, ww: int) -> torch.Tensor:
+        """The choice array of merging block ``i`` (called once per block, in order)."""
+        if self.flat is not None:
+            assert i == len(self.choices)
+            off = sum(c.numel() for c in self.choices)
+            cells = (hh // 2) * (ww // 2)
+            assert off + cells <= self.flat.numel(), "the flat choice array is shorter than the merging blocks need"
+            self.choices.append(self.flat[off:off + cells])
+        return self.choices[i]
+
+
+def merging_grids(cfg, h: int, w: int, max_downsample: int):
+    """The (h, w) token grid of every merging block of a ``h x w`` latent in call order -- down blocks, mid block, up blocks --
+    from the config alone (``cfg``: the library's or the oracle's UNetConfig)."""
+    nlev = len(cfg.block_out_channels)
+    on = [cfg.attn_levels[i] and 2 ** i <= max_downsample for i in range(nlev)]
+    grid = lambda i: (h >> i, w >> i)
+    out = [grid(i) for i in range(nlev) if on[i] for _ in range(cfg.layers_per_block)]
+    if 2 ** (nlev - 1) <= max_downsample:
+        out.append(grid(nlev - 1))
+    return out + [grid(i) for i in reversed(range(nlev)) if on[i] for _ in range(cfg.layers_per_block + 1)]
+
+
+def unet_inputs(cfg, h: int, w: int, lb: int, ub: int, md: int, seed: int = 29):
+    """(latents [lb], prompt rows [ub], UNet sample [ub] = the latents repeated, flat dst choice): the inputs of the UNet cases,
+    the same for the GPU test and for the CPU test that checks the oracle's own with / without distance at them first."""
+    g = torch.Generator().manual_seed(seed)
+    lat = torch.randn(lb, 4, h, w, generator=g)
+    ctx = torch.randn(ub, cfg.context_len, cfg.cross_attention_dim, generator=g)
+    cells = sum((a // 2) * (b // 2) for a, b in merging_grids(cfg, h, w, md))
+    choice = torch.randint(4, (cells,), generator=torch.Generator().manual_seed(5), dtype=torch.uint8)
+    return lat, ctx, torch.cat([lat] * (ub // lb)), choice
 
 
 def transformer_block(w, p: str, x: torch.Tensor, ctx: torch.Tensor, cfg, fq=None, run: Optional[TomeRun] = None) -> torch.Tensor:
@@ -141,10 +176,11 @@ def transformer_block(w, p: str, x: torch.Tensor, ctx: torch.Tensor, cfg, fq=Non
     t = p + "transformer_blocks.0."
     r = num_merged(hh * ww, run.ratio)
     given = run.given[i] if i < len(run.given) else None
+    choice = run.choice(i, hh, ww)
     if given is None:
-        m = match(h, run.choices[i], hh, ww, r, dtype=torch.float32)
+        m = match(h, choice, hh, ww, r, dtype=torch.float32)
     else:
-        src_tok, dst_tok = partition(run.choices[i], hh, ww)
+        src_tok, dst_tok = partition(choice, hh, ww)
         m = dict(src_tok=src_tok, dst_tok=dst_tok, r=r, **{k: given[k].long() for k in ("kept", "merged", "dst_idx")})
         assert m["merged"].shape == (b, r) and m["kept"].shape == (b, src_tok.numel() - r)
     run.used.append(m)
@@ -199,6 +235,47 @@ def tome_test_weights(sd):
         if k.endswith("attn1.to_out.0.weight"):
             out[k] = sd[k] * ATTN1_GAIN
     return out
+
+
+def unet_env(name: str):
+    """(library config, gain-4 test weights, oracle config, heads per level or None) of the UNets the Token Merging cases run on:
+    "sd15" (four levels, sample 16), "sd2" (SD 2.x-shaped: 5 / 10 / 20 / 20 heads of 64) and "two_level" (320 / 640 channels
+    with attention on both levels, sample 32: the smallest UNet whose first level reaches 1024 tokens)."""
+    from sonicdiffusionbayeslab_amd.weights import UNetConfig, make_synthetic_state_dict, sd2_unet_config
+    heads = None
+    if name == "sd2":
+        from tests.sd2_oracle import oracle_config
+        cfg = sd2_unet_config(16)
+        ocfg, heads = oracle_config(cfg), cfg.heads_per_level
+    else:
+        from tests.util import oracle_cfg
+        cfg = {"sd15": lambda: UNetConfig(sample_size=16),
+               "two_level": lambda: UNetConfig(sample_size=32, block_out_channels=(320, 640), attn_levels=(True, True))}[name]()
+        ocfg = oracle_cfg(cfg)
+    return cfg, tome_test_weights(make_synthetic_state_dict(cfg, seed=1234)), ocfg, heads
+
+
+UNET_TOL = 2e-2                     # tests/test_unet_gpu.py
+
+
+def moved_floor(ratio: float) -> float:
+    """What the oracle's own with / without distance must exceed for "merging moved the output" to mean something: 10 x UNET_TOL
+    from ratio 0.5 on; 5 x below it -- with the oracle alone, at gain 4, ratios 0.25 / 0.3 give 0.13 .. 0.18 at these shapes (a
+    larger gain lowers it), so a forward that ignored the merge still misses UNET_TOL by a factor of five."""
+    return (10 if ratio >= 0.5 else 5) * UNET_TOL
+
+
+#             env     h   w   lb ub md ratio  merging blocks, input seed, timestep
+UNET_CASES = [("sd15", 16, 16, 2, 4, 2, 0.25, 10, 29, 981.0), ("sd15", 16, 16, 2, 4, 2, 0.3, 10, 29, 981.0),
+              ("sd15", 16, 16, 2, 4, 2, 0.75, 10, 29, 981.0), ("sd15", 16, 24, 2, 4, 2, 0.25, 10, 29, 981.0),
+              ("sd15", 16, 24, 2, 4, 2, 0.3, 10, 29, 981.0), ("sd15", 16, 24, 2, 4, 2, 0.75, 10, 29, 981.0),
+              ("sd2", 16, 16, 1, 2, 2, 0.3, 10, 29, 981.0),
+              # the head-major K / V path under merging (csrc/plan.hip, Builder::transformer): level 0 has 1024 tokens; level 1 and
+              # the mid block (256 tokens) merge too: 2 + 2 down, 1 mid, 3 + 3 up = 11 blocks.  Seed 7 at t = 501: with the seed and
+              # timestep of the cases above the oracle's own distance at ratio 0.5 is 0.198 (batch 16/16) and 0.210 (8/16), at and
+              # barely above its floor; here it is 0.228 and 0.235 (0.148 and 0.161 at ratio 0.25)
+              ("two_level", 32, 32, 16, 16, 2, 0.5, 11, 7, 501.0), ("two_level", 32, 32, 8, 16, 2, 0.5, 11, 7, 501.0),
+              ("two_level", 32, 32, 16, 16, 2, 0.25, 11, 7, 501.0), ("two_level", 32, 32, 8, 16, 2, 0.25, 11, 7, 501.0)]
 
 
 def unet_forward(w, cfg, sample, t, ctx, run: TomeRun, heads_per_level=None, **kw):
