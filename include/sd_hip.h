@@ -233,6 +233,23 @@ int sd_unet_set_tome_choice_hw(sd_unet* u, void* stream, const unsigned char* ch
 int sd_unet_tome_matching_hw(sd_unet* u, void* stream, int block, int unet_batch, int cache_branch_id, void* workspace, int* kept,
                              int* merged, int* dst_idx, int* tok, int* r, int* batch);
 
+/* FreeU (Si et al.; diffusers enable_freeu(s1, s2, b1, b2)): while set, every forward of the handle runs the "freeu" plan variant --
+ * in up blocks 0 and 1, in front of each of the three resnets, ONE launch (profile kind 31; csrc/freeu.hip) writes new tensors
+ * hidden' = hidden with its first half of the channels times b and skip' = fourier_filter(skip, threshold 1, scale s), and the
+ * resnet reads [hidden' | skip']; (b, s) = (b1, s1) in block 0 and (b2, s2) in block 1.  The GroupNorms of those resnets compute
+ * their own statistics.  The four factors live on the handle and are read at launch: changing them builds no plan; switching
+ * FreeU on or off selects other plans, so call sd_unet_workspace_bytes_hw and sd_unet_set_context_hw again.  On a DeepCache skip
+ * step whose branch reaches into those blocks the op runs on the cached feature each time it is consumed; the cached feature
+ * itself stays raw.  With ControlNet residuals the filter sees the skips after the residual add.  All four factors must be
+ * finite and > 0 (diffusers switches FreeU off silently when one is 0; here that is an error).  fp8 handles refuse: their
+ * calibrated activation scales do not describe the scaled tensors.  disable_freeu: the plans, workspace sizes and results of a
+ * handle that never saw it, bit for bit. */
+int sd_unet_set_freeu(sd_unet* u, float s1, float s2, float b1, float b2);
+int sd_unet_disable_freeu(sd_unet* u);
+/* How many execution plans the handle has built so far (one per batch, DeepCache branch, latent size and variant); < 0 on a
+ * null handle.  For tests of "this setting builds no new plan". */
+int sd_unet_plan_count(const sd_unet* u);
+
 enum { SD_CACHE_OFF = 0, SD_CACHE_FULL_AND_STORE = 1, SD_CACHE_SKIP = 2 };
 
 /* eps = UNet(latent_model_input, t, encoder_hidden_states)  (src/models.py:217-235).
@@ -642,6 +659,14 @@ int sd_op_tome_merge(void* stream, const void* x, const int* tok, const int* kep
                      long long ldo, int B, int h, int w, int C, int r);
 int sd_op_tome_unmerge(void* stream, const void* y, long long ldy, const void* residual, const int* tok, const int* kept,
                        const int* merged, const int* dst_idx, void* out, int B, int h, int w, int C, int r);
+/* FreeU on the inputs of one resnet (csrc/freeu.hip), one launch on bf16 NHWC tensors: skip_out [B][H][W][C_skip] =
+ * fourier_filter(skip, threshold = 1, scale = s) -- per (sample, channel) plane the Fourier modes {-1, 0} x {-1, 0} times s, real
+ * part, as the closed form  y[n] = x[n] + (s - 1) / (H W) (S0 + sum_k C_k cos a_k(n) + S_k sin a_k(n)),  k in {(1,0), (0,1), (1,1)}
+ * in fp32 with one rounding -- and hidden_out [B][H][W][C_hidden] = hidden with channels [0, C_hidden / 2) times b (one rounding),
+ * the others copied.  The outputs must be new tensors.  H, W in [2, 128]; C_hidden, C_skip multiples of 32; b, s finite and > 0.
+ * Deterministic. */
+int sd_op_freeu(void* stream, const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W,
+                int C_hidden, int C_skip, float b, float s);
 /* flash-style attention on token-major [B, N, heads * D] views; D = 40, 64, 80 or 160 (64: Stable Diffusion 2.x), any Nq / Nk */
 int sd_op_attention(void* stream, const void* Q, long long ldq, const void* K, long long ldk, const void* V,
                     long long ldv, void* O, long long ldo, int B, int heads, int Nq, int Nk, int D, float scale);

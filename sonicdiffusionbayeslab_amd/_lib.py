@@ -226,6 +226,10 @@ _SIGS = {
     "sd_op_tome_select": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sd_op_tome_merge": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i]),
     "sd_op_tome_unmerge": (_i, [_vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "sd_unet_set_freeu": (_i, [_vp, _f, _f, _f, _f]),
+    "sd_unet_disable_freeu": (_i, [_vp]),
+    "sd_unet_plan_count": (_i, [_vp]),
+    "sd_op_freeu": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f]),
 }
 
 

@@ -229,6 +229,13 @@ int sd_launch_tome_merge(const bf16_t* x, const int* tok, const int* kept, const
 int sd_launch_tome_unmerge(const bf16_t* y, long ldy, const bf16_t* residual, const int* tok, const int* kept, const int* merged,
                            const int* dst_idx, bf16_t* out, int B, int h, int w, int C, int r, hipStream_t stream);
 
+// freeu.hip: FreeU on the inputs of one up-block resnet, one launch: skip_out [B][H][W][C_skip] = fourier_filter(skip, threshold 1,
+// scale s) per (sample, channel) plane, hidden_out [B][H][W][C_hidden] = hidden with its first C_hidden / 2 channels times b.  The
+// outputs are new tensors.  H, W in [2, 128]; both channel counts multiples of 32; b, s finite and > 0.
+int sd_freeu_check(int B, int H, int W, int C_hidden, int C_skip, const char* who);
+int sd_launch_freeu(const bf16_t* hidden, const bf16_t* skip, bf16_t* hidden_out, bf16_t* skip_out, int B, int H, int W, int C_hidden,
+                    int C_skip, float b, float s, hipStream_t stream);
+
 // xattn.hip: fused prompt cross-attention  Y = R + sum_h softmax_L(X A_h) B_h + b_o  (one launch per block)
 struct XattnArgs {
     const bf16_t* X = nullptr;    // [M, C] LayerNorm output

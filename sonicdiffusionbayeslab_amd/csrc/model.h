@@ -46,7 +46,8 @@ enum OpKind { OP_SINUSOID, OP_GEMV, OP_CONV_IN, OP_GN, OP_CONV3, OP_GEMM, OP_LN,
               OP_CLIP_EMBED, OP_CLIP_ATTN, OP_QGELU, OP_TO_F32, OP_XATTN, OP_REPLICATE,
               OP_VIT_PREP, OP_VIT_EMBED, OP_VIT_ATTN, OP_POOL, OP_CONV_IN_IMG, OP_ENC_OUT, OP_IP_XATTN, OP_RES_ADD,
               OP_BERT_ATTN, OP_REWARD_HEAD,
-              OP_TOME_MATCH, OP_TOME_SELECT, OP_TOME_MERGE, OP_TOME_UNMERGE };
+              OP_TOME_MATCH, OP_TOME_SELECT, OP_TOME_MERGE, OP_TOME_UNMERGE,
+              OP_FREEU };
 
 constexpr int REP_TEXT_POOLED = 2;       // Plan::rep of a CLIP text handle's sd_clip_text_embeds plan
 
@@ -173,6 +174,9 @@ struct Plan {
     struct TomeBlock { int tok, kept, merged, dst_idx, B, h, w, r; long choice_off; };
     std::vector<TomeBlock> tome;
     long tome_choice_bytes = 0;
+    // FreeU variant (part of the plan key): one OP_FREEU in front of every resnet of up blocks 0 and 1 (x1 = hidden, x2 = skip ->
+    // out = the scaled hidden, aux = the filtered skip, epi = the up block: which pair of the handle's factors the launch reads)
+    int freeu = 0;
     std::vector<Tn> tensors;
     std::vector<Op> ops;
     std::vector<char> skipped;            // per op: skipped on a DeepCache skip step
@@ -236,8 +240,8 @@ struct sd_unet {
         return (int)act_names.size() - 1;
     }
     // (UNet batch, DeepCache branch, prefix replication, latent H, W, IP-Adapter variant, control variant, Token Merging: the
-    // bits of the ratio and max_downsample, both 0 = off)
-    std::map<std::tuple<int, int, int, int, int, int, int, long long, int>, sdhip::Plan> plans;
+    // bits of the ratio and max_downsample, both 0 = off; FreeU on / off)
+    std::map<std::tuple<int, int, int, int, int, int, int, long long, int, int>, sdhip::Plan> plans;
     int last_rep = 1, last_ip = 0, last_cn = 0;                       // variant of the last forward (sd_unet_debug_tensor)
     int last_h = 0, last_w = 0;                          // latent size of the last forward (sd_unet_debug_tensor)
     std::unordered_map<std::string, long> tproj_off;  // resnet prefix -> float index into tproj vector
@@ -280,6 +284,9 @@ struct sd_unet {
     unsigned char* tome_choice = nullptr;
     size_t tome_choice_cap = 0;
     long tome_choice_n = 0;
+    // FreeU (sd_unet_set_freeu; kind 0, bf16): on = the "freeu" plan variants; the factors are read when OP_FREEU is launched
+    bool freeu_on = false;
+    float freeu_s[2] = {1.f, 1.f}, freeu_b[2] = {1.f, 1.f};       // (s1, s2), (b1, b2): up block 0, up block 1
     bool unet_like() const { return kind == 0 || kind == 5; }      // runs the UNet's encoder ops (plan.hip Builder::build)
 };
 

@@ -462,6 +462,13 @@ extern "C" int sd_op_attention_headmajor(void* stream, const void* Q, long long 
     return sd_launch_attention(a, (hipStream_t)stream);
 }
 
+// FreeU on one resnet's inputs (freeu.hip)
+extern "C" int sd_op_freeu(void* stream, const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W,
+                           int C_hidden, int C_skip, float b, float s) {
+    return sd_launch_freeu((const bf16_t*)hidden, (const bf16_t*)skip, (bf16_t*)hidden_out, (bf16_t*)skip_out, B, H, W, C_hidden, C_skip,
+                           b, s, (hipStream_t)stream);
+}
+
 // Token Merging, kernel by kernel (tome.hip); index lists in src / dst slot numbers, tok [h * w] from sd_op_tome_match
 extern "C" int sd_op_tome_match(void* stream, const void* x, const unsigned char* choice, int B, int h, int w, int C,
                                 float* node_max, int* node_idx, int* tok) {

@@ -812,7 +812,17 @@ struct Builder {
                 skips.pop_back(); skip_ch.pop_back();
                 const int rl = nres - 1 - j;
                 wrapstack.push_back(Wrap{2, rb, rl});
-                h = resnet(bp + "resnets." + std::to_string(j) + ".", h, ch, s, sc, co, rh, rw, t_proj);
+                int hin = h, sin = s;
+                if (pl.freeu && i < 2) {
+                    // FreeU (freeu.hip) inside the resnet's own Wrap: it runs whenever the resnet runs, on new tensors -- a DeepCache
+                    // skip step reads the cached feature through it and leaves the feature raw.  The new tensors have no entry in
+                    // stats_of: the producers' statistics do not describe them, norm1 runs its own pass.
+                    if (sd_freeu_check(UB, rh, rw, ch, sc, "FreeU")) { if (error.empty()) error = sd_last_error(); }
+                    Op o; o.kind = OP_FREEU; o.x1 = h; o.x2 = s; o.B = UB; o.Hin = rh; o.Win = rw; o.C1 = ch; o.C2 = sc; o.epi = i;
+                    o.out = hin = tensor((size_t)UB * rh * rw * ch * 2); o.aux = sin = tensor((size_t)UB * rh * rw * sc * 2);
+                    push(o);
+                }
+                h = resnet(bp + "resnets." + std::to_string(j) + ".", hin, ch, sin, sc, co, rh, rw, t_proj);
                 ch = co;
                 if (c.attn_levels[lev]) h = transformer(bp + "attentions." + std::to_string(j) + ".", h, co, rh, rw);
                 wrapstack.pop_back();
@@ -1015,7 +1025,8 @@ int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw
     if (lw < 0) lw = u->cfg.sample_size;
     long long tome_bits = 0;
     if (u->kind == 0 && u->tome_ratio > 0.0) memcpy(&tome_bits, &u->tome_ratio, sizeof(tome_bits));
-    auto key = std::make_tuple(UB, branch, rep, lh, lw, ip, cn, tome_bits, tome_bits ? u->tome_max_downsample : 0);
+    const int freeu = u->kind == 0 && u->freeu_on ? 1 : 0;
+    auto key = std::make_tuple(UB, branch, rep, lh, lw, ip, cn, tome_bits, tome_bits ? u->tome_max_downsample : 0, freeu);
     auto it = u->plans.find(key);
     if (it == u->plans.end()) {
         if (lh != u->cfg.sample_size || lw != u->cfg.sample_size)
@@ -1028,6 +1039,7 @@ int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw
         pl.lw = lw;
         pl.ip = ip;
         pl.cn = cn;
+        pl.freeu = freeu;
         Builder b{u, pl, UB, {}};
         b.build();
         SD_REQUIRE(b.error.empty(), "unet: cannot build the plan for batch %d (cache branch %d, latent %dx%d): %s", UB, branch, lh, lw,

@@ -183,6 +183,10 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
             }
             return sd_launch_residual_add(x, r, n, o.nres, u->ctrl_scale, stream);
         }
+        case OP_FREEU:      // (the factors of the handle as they are NOW: a change between two forwards rebuilds nothing)
+            SD_REQUIRE(u->freeu_on && (o.epi == 0 || o.epi == 1), "forward: FreeU is off (sd_unet_set_freeu)");
+            return sd_launch_freeu((const bf16_t*)T(o.x1), (const bf16_t*)T(o.x2), (bf16_t*)T(o.out), (bf16_t*)T(o.aux), o.B, o.Hin, o.Win,
+                                   o.C1, o.C2, u->freeu_b[o.epi], u->freeu_s[o.epi], stream);
         case OP_REPLICATE:
             return sd_launch_replicate(T(o.x1), T(o.out), (long)o.M * 16, o.N, stream);
         case OP_TOME_MATCH:
@@ -1085,6 +1089,29 @@ extern "C" int sd_unet_forward_hw(sd_unet* u, void* stream, const float* latents
     return run_plan(u, *pl, "forward", workspace, workspace_bytes, latents, latent_batch, eps_out, timestep, stream, cache_mode);
 }
 
+// ---- FreeU (freeu.hip; the plan side is the up loop of Builder::build) ----------------------------------------------------
+extern "C" int sd_unet_set_freeu(sd_unet* u, float s1, float s2, float b1, float b2) {
+    SD_REQUIRE(u && u->kind == 0, "set_freeu: not a UNet handle");
+    SD_REQUIRE(!u->fp8, "set_freeu: FreeU is refused on fp8 handles (the calibrated activation scales do not describe the scaled tensors)");
+    const float f[4] = {s1, s2, b1, b2};
+    for (int i = 0; i < 4; ++i)
+        SD_REQUIRE(f[i] > 0.f && f[i] <= 3.0e38f, "set_freeu: s1=%g s2=%g b1=%g b2=%g (all four must be finite and > 0)", s1, s2, b1, b2);
+    u->freeu_s[0] = s1; u->freeu_s[1] = s2; u->freeu_b[0] = b1; u->freeu_b[1] = b2;
+    u->freeu_on = true;
+    return 0;
+}
+
+extern "C" int sd_unet_disable_freeu(sd_unet* u) {
+    SD_REQUIRE(u && u->kind == 0, "disable_freeu: not a UNet handle");
+    u->freeu_on = false;
+    return 0;
+}
+
+extern "C" int sd_unet_plan_count(const sd_unet* u) {
+    SD_REQUIRE(u, "plan_count: null handle");
+    return (int)u->plans.size();
+}
+
 // ---- Token Merging (tome.hip; the plan side is Builder::transformer) -----------------------------------------------------
 extern "C" int sd_unet_set_tome(sd_unet* u, double ratio, int max_downsample) {
     SD_REQUIRE(u && u->kind == 0, "set_tome: not a UNet handle");
@@ -1303,6 +1330,10 @@ static void op_work(const Op& o, double* flops, double* bytes) {
         case OP_TOME_MERGE:
         case OP_TOME_UNMERGE:
             *bytes = 2.0 * o.B * (2.0 * o.Hin * o.Win - o.K) * (double)o.N;
+            break;
+        case OP_FREEU:      // hidden and skip in (the skip twice: the sums, then the apply pass), both out
+            *flops = 2.0 * 14.0 * o.B * (double)o.Hin * o.Win * o.C2;
+            *bytes = 2.0 * o.B * (double)o.Hin * o.Win * (2.0 * o.C1 + 3.0 * o.C2);
             break;
         case OP_RES_ADD:    // x and r in, x out
             *bytes = 3.0 * 2.0 * (double)o.M;      // (M: the elements of all segments)

@@ -84,7 +84,26 @@ class BaseMethod(ABC):
         tome = self.parse_tome(self.config.model)      # keys of this build: model.tome_ratio (+ tome_max_downsample, tome_use_rand, tome_seed)
         if tome is not None:
             self.model.apply_tome(**tome)
+        freeu = self.parse_freeu(self.config.model, self.config.model.get("weight_dtype", None) or "bf16")     # key of this build: model.freeu
+        if freeu is not None:
+            self.model.enable_freeu(**freeu)
         self.model.to(self.device)
+
+    @staticmethod
+    def parse_freeu(model_cfg, weight_dtype="bf16"):
+        """``model.freeu: {s1, s2, b1, b2}`` -> the arguments of ``enable_freeu`` (FreeU for any method), or None when the key
+        is absent or null.  All four factors are required; unknown keys, factors <= 0 and fp8 UNets are refused by name."""
+        f = model_cfg.get("freeu", None)
+        if f is None:
+            return None
+        if not hasattr(f, "keys"):
+            raise ValueError(f"model.freeu must be a mapping {{s1, s2, b1, b2}}, got {f!r}")
+        keys = set(f.keys())
+        if keys != {"s1", "s2", "b1", "b2"}:
+            raise ValueError(f"model.freeu takes exactly the keys s1, s2, b1, b2 (got {sorted(keys)})")
+        from ..models import StableDiffusionModel
+        s1, s2, b1, b2 = StableDiffusionModel.check_freeu_args(f["s1"], f["s2"], f["b1"], f["b2"], weight_dtype)
+        return dict(s1=s1, s2=s2, b1=b1, b2=b2)
 
     @staticmethod
     def parse_tome(model_cfg):

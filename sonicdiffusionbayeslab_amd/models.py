@@ -173,6 +173,7 @@ class StableDiffusionModel:
         self._tome_gen = None
         self._tome_cells = 0
         self._tome_first = False        # the call's first forward uses the choice array _tome_begin uploaded
+        self._freeu = None              # FreeU (enable_freeu): (s1, s2, b1, b2) or None = off
 
     # -- Token Merging (tomesd.apply_patch) ----------------------------------------------------------
     TOME_MAX_RATIO = 0.75
@@ -257,6 +258,34 @@ class StableDiffusionModel:
             return
         if t["use_rand"] and t["rand_every"] == "step":
             self._tome_upload()
+
+    # -- FreeU (diffusers enable_freeu) -----------------------------------------------------------------
+    @staticmethod
+    def check_freeu_args(s1, s2, b1, b2, weight_dtype="bf16"):
+        """The arguments of ``enable_freeu`` checked, by name, without touching the GPU: four finite numbers > 0 (diffusers
+        switches FreeU off silently when a factor is 0; here a factor <= 0 raises), and no fp8 UNet.  Returns
+        ``(s1, s2, b1, b2)`` as floats."""
+        return HipUNet2DConditionModel.check_freeu_args(s1, s2, b1, b2, weight_dtype)
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """FreeU (Si et al.; diffusers ``enable_freeu``): in every later call the resnets of up blocks 0 and 1 read the
+        backbone features with their first half of the channels times ``b1`` / ``b2`` and the skip features with their four
+        lowest Fourier modes times ``s1`` / ``s2`` (SD 1.x preset: 0.9, 0.2, 1.5, 1.6).  Valid with every pipeline, DeepCache,
+        IP-Adapter, ControlNet, Token Merging, TAESD, every image size and batch sharding; refused on fp8 UNets."""
+        self._freeu = self.check_freeu_args(s1, s2, b1, b2, self.weight_dtype)
+        return self
+
+    def disable_freeu(self):
+        """Later calls are those of a model that never saw FreeU, bit for bit."""
+        self._freeu = None
+        return self
+
+    def _freeu_begin(self):
+        """Start of a sampling loop: the setting onto the UNet handle."""
+        if self._freeu is None:
+            self.unet.disable_freeu()
+        else:
+            self.unet.set_freeu(*self._freeu)
 
     # -- loading ---------------------------------------------------------------------------
     @classmethod
@@ -960,6 +989,7 @@ class StableDiffusionModel:
         c = self.unet_config
         latents = self.prepare_latents(batch_size, LATENT_CHANNELS, self._size[0], self._size[1], device, generator, latents)
         self._tome_begin()              # (before the context: the setting is part of the UNet's plans)
+        self._freeu_begin()             # (likewise)
         self.unet.set_deepcache(cache_branch_id)
         self.unet.set_context(ctx, *self.latent_size)
         self._apply_ip_adapter(ctx.shape[0] == 2 * batch_size and self.do_classifier_free_guidance)

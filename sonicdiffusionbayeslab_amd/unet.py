@@ -10,6 +10,7 @@ only owns the device buffers.  There is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, Optional
 
 import torch
@@ -94,6 +95,7 @@ class HipUNet2DConditionModel:
         self._control = None
         self._tome = None                   # (ratio, max_downsample) of the Token Merging setting on the handle, None = off
         self._tome_choice_keepalive = None
+        self._freeu = None                  # (s1, s2, b1, b2) on the handle, None = off
         self.cache_branch_id = -1
 
     def __del__(self):
@@ -349,6 +351,44 @@ class HipUNet2DConditionModel:
         return dict(kept=kept.reshape(-1)[:b * (num_src - r)].reshape(b, num_src - r), merged=merged.reshape(-1)[:b * r].reshape(b, r),
                     dst_idx=dst_idx.reshape(-1)[:b * r].reshape(b, r), tok=tok, r=rr.value)
 
+    # -- FreeU (include/sd_hip.h::sd_unet_set_freeu) -------------------------------------------------
+    @staticmethod
+    def check_freeu_args(s1, s2, b1, b2, weight_dtype="bf16"):
+        """The arguments of ``set_freeu`` checked, by name, without touching the GPU; returns them as four floats."""
+        out = []
+        for name, v in (("s1", s1), ("s2", s2), ("b1", b1), ("b2", b2)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(float(v)) or not float(v) > 0.0 \
+                    or float(v) > 3.0e38:
+                raise ValueError(f"{name}={v!r}: every FreeU factor must be a finite number > 0 (diffusers switches FreeU off "
+                                 "silently when a factor is 0; here that is an error: use disable_freeu())")
+            out.append(float(v))
+        if _lib.DTYPES.get(weight_dtype) == _lib.DTYPE_FP8_E4M3:
+            raise NotImplementedError("FreeU on an fp8 UNet handle is refused (weight_dtype='fp8'): the calibrated activation "
+                                      "scales do not describe the scaled tensors")
+        return tuple(out)
+
+    def set_freeu(self, s1: float, s2: float, b1: float, b2: float) -> None:
+        """diffusers ``enable_freeu``: in up blocks 0 and 1 every resnet reads the hidden tensor with its first half of the
+        channels times ``b1`` / ``b2`` and the skip tensor with its four lowest Fourier modes times ``s1`` / ``s2``.  The
+        factors are read at launch: changing them builds no plan.  Switching on needs a new workspace and a new
+        ``set_context``; both follow from dropping the workspace key here."""
+        f = self.check_freeu_args(s1, s2, b1, b2, self.weight_dtype)
+        _lib.check(self._lib.sd_unet_set_freeu(self._handle, *f), "sd_unet_set_freeu")
+        if self._freeu is None:
+            self._ws_key = None
+        self._freeu = f
+
+    def disable_freeu(self) -> None:
+        """Forwards are again those of a UNet that never saw FreeU, bit for bit."""
+        _lib.check(self._lib.sd_unet_disable_freeu(self._handle), "sd_unet_disable_freeu")
+        if self._freeu is not None:
+            self._ws_key = None
+        self._freeu = None
+
+    def plan_count(self) -> int:
+        """Execution plans the handle has built so far."""
+        return int(self._lib.sd_unet_plan_count(self._handle))
+
     # -- forward ---------------------------------------------------------------------------
     def forward_latents(self, latents: torch.Tensor, unet_batch: int, timestep: float,
                         out: Optional[torch.Tensor] = None, cache_mode: int = CACHE_OFF) -> torch.Tensor:
@@ -426,7 +466,7 @@ class HipUNet2DConditionModel:
     KIND_NAMES = {0: "sinusoid", 1: "gemv", 2: "conv_in", 3: "groupnorm", 4: "conv3x3", 5: "gemm", 6: "layernorm",
                   7: "attention", 8: "conv_out", 16: "conv3x3_fp8", 17: "gemm_fp8", 18: "xattn_fused",
                   19: "replicate", 20: "conv3x3_gemm", 21: "conv3x3_halo_subpix", 22: "ip_xattn", 23: "residual_add",
-                  27: "tome_match", 28: "tome_select", 29: "tome_merge", 30: "tome_unmerge"}
+                  27: "tome_match", 28: "tome_select", 29: "tome_merge", 30: "tome_unmerge", 31: "freeu"}
 
     def forward_profiled(self, latents: torch.Tensor, unet_batch: int, timestep: float, cache_mode: int = CACHE_OFF):
         """One forward with a hipEvent pair around every launch (measurement only, synchronises).
