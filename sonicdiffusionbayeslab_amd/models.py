@@ -27,6 +27,7 @@ import math
 import os
 import time
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Callable, List, Optional, Union
 
 import torch
@@ -108,6 +109,27 @@ def postprocess_images(image01: torch.Tensor, output_type: str):
         from PIL import Image
         return [Image.fromarray(a) for a in (arr * 255.0).round().astype("uint8")]
     raise NotImplementedError(f"output_type {output_type!r}")
+
+
+def _prompt_batch(prompt, prompt_embeds) -> int:
+    """The number of prompts of a call: one string, a list of them, or the rows of ``prompt_embeds``."""
+    if prompt is None:
+        return int(prompt_embeds.shape[0])
+    return 1 if isinstance(prompt, str) else len(prompt)
+
+
+def _is_pil_list(v) -> bool:
+    return isinstance(v, (list, tuple)) and len(v) > 0 and all(hasattr(im, "convert") for im in v)
+
+
+def _pil_stack(images, mode: str, dtype, what: str):
+    """A list of PIL images of one size -> one numpy array [B, H, W(, 3)] of ``dtype`` in ``mode`` ("RGB" | "L").
+    ``what`` names the argument in the refusal of mixed sizes."""
+    import numpy as np
+    sizes = {im.size for im in images}
+    if len(sizes) != 1:
+        raise ValueError(f"{what} of one call must have one size, got {sorted(sizes)}")
+    return np.stack([np.asarray(im.convert(mode), dtype=dtype) for im in images])
 
 
 @models_registry.add_to_registry("stable_diffusion_model")
@@ -630,12 +652,8 @@ class StableDiffusionModel:
             raise NotImplementedError("ip_adapter_image: nested lists (several IP-Adapters or several images per sample) are not built")
         if hasattr(img, "convert"):
             img = [img]
-        if isinstance(img, (list, tuple)) and len(img) > 0 and all(hasattr(im, "convert") for im in img):
-            import numpy as np
-            sizes = {im.size for im in img}
-            if len(sizes) != 1:
-                raise ValueError(f"ip_adapter_image: the PIL images of one call must have one size, got {sorted(sizes)}")
-            img = torch.from_numpy(np.stack([np.asarray(im.convert("RGB"), dtype=np.uint8) for im in img])).permute(0, 3, 1, 2)
+        if _is_pil_list(img):
+            img = torch.from_numpy(_pil_stack(img, "RGB", "uint8", "ip_adapter_image: the PIL images")).permute(0, 3, 1, 2)
         if not torch.is_tensor(img) or img.dim() != 4 or img.shape[1] != 3:
             raise ValueError("ip_adapter_image must be a list of PIL images of one size or a uint8 / float [B,3,H,W] tensor")
         if img.is_floating_point():
@@ -957,8 +975,8 @@ class StableDiffusionModel:
         if num_images_per_prompt != 1 or timesteps is not None or sigmas is not None:
             raise NotImplementedError("custom timesteps / num_images_per_prompt are outside the reference's use")
         height, width = self.check_size(height, width)          # before any GPU work
-        n_prompt = 1 if isinstance(prompt, str) else len(prompt) if prompt is not None else int(prompt_embeds.shape[0])
-        self._ip_pending = self._ip_adapter_args(ip_adapter_image, ip_adapter_image_embeds, n_prompt,
+        batch_size = _prompt_batch(prompt, prompt_embeds)
+        self._ip_pending = self._ip_adapter_args(ip_adapter_image, ip_adapter_image_embeds, batch_size,
                                                  guidance_scale > 1 and self.unet_config.time_cond_proj_dim is None)
         self._size = (height, width)
         self._ensure_unet()
@@ -967,12 +985,6 @@ class StableDiffusionModel:
         device = self.unet.device
         self._guidance_scale = guidance_scale
         self.unet.set_timestep_cond(self.guidance_condition(guidance_scale))      # (None clears it)
-        if prompt is not None and isinstance(prompt, str):
-            batch_size = 1
-        elif prompt is not None:
-            batch_size = len(prompt)
-        else:
-            batch_size = prompt_embeds.shape[0]
         do_cfg = self.do_classifier_free_guidance
         prompt_embeds, negative_prompt_embeds = self.encode_prompt(
             prompt, device, do_cfg, negative_prompt, prompt_embeds, negative_prompt_embeds)
@@ -986,7 +998,6 @@ class StableDiffusionModel:
 
     def _start_loop(self, batch_size, device, generator, latents, ctx, cache_branch_id, control=None):
         """Initial latents at the call's size, DeepCache branch and prompt context of the UNet."""
-        c = self.unet_config
         latents = self.prepare_latents(batch_size, LATENT_CHANNELS, self._size[0], self._size[1], device, generator, latents)
         self._tome_begin()              # (before the context: the setting is part of the UNet's plans)
         self._freeu_begin()             # (likewise)
@@ -1001,25 +1012,72 @@ class StableDiffusionModel:
         h, w = self.latent_size
         return torch.empty((unet_batch, c.out_channels, h, w), dtype=torch.float32, device=device)
 
+    def _sample(self, steps, latents, unet_batch, do_cfg, guidance_scale, eta=0.0, generator=None, guidance_rescale=0.0,
+                step_noise=None, collect_x0=True, deepcache=None, inpaint=None):
+        """THE denoising loop (``src/models.py:210-282``) of all four pipelines, after ``_start_loop``.  ``steps``: the steps
+        that run, each ``(t, scheduler, hand_off)`` -- ``hand_off`` is the scheduler whose multistep history receives the
+        step's noise prediction (``_push_history``), or None.  ``deepcache``: the helper, whose plan indexes the timesteps
+        that run (first match, as DeepCache's ``list.index``: both steps of PNDM's duplicated timestep get its first index).
+        ``inpaint = (image latents, noise, latent mask)``: the step blends the kept region back in, noised to the next
+        timestep that runs.  Returns (latents, x0 predictions of the first sample, seconds): the wall-clock of the loop only
+        (``:208,284-285``), bracketed by device synchronisation."""
+        device = self.unet.device
+        eps = self._eps_buffer(unet_batch, device)
+        ts = [s[0] for s in steps]
+        n = len(steps)
+        x0_preds = []
+        torch.cuda.synchronize(device)
+        start_time = time.time()                                                                   # :208
+        for i, (t, sched, hand_off) in enumerate(steps):                                           # :211
+            mode = CACHE_OFF
+            if deepcache is not None:
+                mode = CACHE_FULL_AND_STORE if ts.index(t) % deepcache.cache_interval == 0 else CACHE_SKIP     # (A.5)
+            self._control_step(i, n, latents, unet_batch, t)
+            self._tome_step()
+            self.unet.forward_latents(latents, unet_batch, float(t), out=eps, cache_mode=mode)     # :217-235
+            kw = {}
+            if step_noise is not None and i < n - 1 and "timestep_scaling" in getattr(sched, "config", ()):    # (LCM)
+                kw["noise"] = step_noise[i]             # indexed by EXECUTED step
+            if do_cfg and guidance_rescale > 0.0:                                                  # :244-250
+                kw["guidance_rescale"] = guidance_rescale
+            if inpaint is not None:
+                kw["inpaint"] = (*inpaint, ts[i + 1] if i + 1 < n else None)
+            step = sched.step_fused(eps, guidance_scale, latents, t, cfg=do_cfg, eta=eta, generator=generator, **kw)   # :238-261
+            latents = step[0]
+            if collect_x0 and len(step) > 1:            # (PNDM returns no x0, :257-261)
+                x0_preds.append(step[1][0:1])
+            if hand_off is not None:                    # :603-611, :1025-1033, :1045-1053
+                _push_history(hand_off, _combined(eps, do_cfg, guidance_scale, sched), latents)
+        self._control_end()
+        torch.cuda.synchronize(device)
+        return latents, x0_preds, time.time() - start_time                                        # :284-285
+
+    def _run(self, a, ts_host, latents, unet_batch, do_cfg, inpaint=None):
+        """The loop of this class's three kinds of call over ``ts_host`` with ``self.scheduler``, and the decode."""
+        self._num_timesteps = len(ts_host)
+        latents, x0_preds, execution_time = self._sample(
+            [(t, self.scheduler, None) for t in ts_host], latents, unet_batch, do_cfg, a.guidance_scale, a.eta, a.generator,
+            a.guidance_rescale, a.step_noise, a.collect_x0, self._deepcache, inpaint)
+        return self._finish(latents, x0_preds, a.output_type, a.return_dict, execution_time)
+
     def _finish(self, latents, x0_preds, output_type, return_dict, execution_time):
         """``src/models.py:287-335``: decode (outside the timed loop), post-process, 3-tuple."""
         if output_type == "latent":
             image = latents
             image_x0 = x0_preds
         elif output_type in ("pt", "np", "pil"):
-            inv = 1.0 / self.vae_config.scaling_factor
-            # a tiny VAE (load_tiny_vae) decodes the UNet's latents as they are, straight to the clamped [0, 1] picture
-            tiny = self._ensure_tiny_vae() if self.tiny_vae_use is not None else None
-            if self.tiny_vae_use == "all":
-                image = postprocess_images(tiny.decode(latents, unit_range=True), output_type)
-            else:
-                vae = self._ensure_vae()
-                image = postprocess_images((vae.decode(latents, inv) / 2 + 0.5).clamp(0, 1), output_type)   # :288,:312
+            def decoder(tiny: bool):
+                """Latents -> the clamped [0, 1] picture.  A tiny VAE (load_tiny_vae) decodes the UNet's latents as they are."""
+                if tiny:
+                    vae = self._ensure_tiny_vae()
+                    return lambda x: vae.decode(x, unit_range=True)
+                vae, inv = self._ensure_vae(), 1.0 / self.vae_config.scaling_factor
+                return lambda x: (vae.decode(x, inv) / 2 + 0.5).clamp(0, 1)                                  # :288,:312
+            preview = decoder(True) if self.tiny_vae_use == "previews" else None
+            decode = decoder(self.tiny_vae_use == "all")
+            image = postprocess_images(decode(latents), output_type)
             # the reference decodes EVERY stored x0 prediction as well (:296-302)
-            if tiny is not None:
-                image_x0 = [postprocess_images(tiny.decode(x, unit_range=True), output_type) for x in x0_preds]
-            else:
-                image_x0 = [postprocess_images((vae.decode(x, inv) / 2 + 0.5).clamp(0, 1), output_type) for x in x0_preds]
+            image_x0 = [postprocess_images((preview or decode)(x), output_type) for x in x0_preds]
         else:
             raise NotImplementedError(f"output_type {output_type!r}: 'latent', 'pt', 'np' and 'pil' are built")
         if not return_dict:
@@ -1104,19 +1162,14 @@ class StableDiffusionModel:
             if image.dim() != 4 or image.shape[1] != 3 or not image.is_floating_point():
                 raise ValueError(f"image must be a float tensor [B,3,H,W] in [0,1], got {tuple(image.shape)} {image.dtype}")
             return image
-        if isinstance(image, (list, tuple)) and len(image) > 0 and all(hasattr(im, "convert") for im in image):
-            import numpy as np
-            sizes = {im.size for im in image}
-            if len(sizes) != 1:
-                raise ValueError(f"image: the PIL images of one call must have one size, got {sorted(sizes)}")
-            arr = np.stack([np.asarray(im.convert("RGB"), dtype=np.float32) / 255.0 for im in image])
+        if _is_pil_list(image):
+            arr = _pil_stack(image, "RGB", "float32", "image: the PIL images") / 255.0
             return torch.from_numpy(arr).permute(0, 3, 1, 2).contiguous()
         raise ValueError("image must be a float tensor [B,3,H,W] in [0,1] or a list of PIL images of one size")
 
-    def _img2img_args(self, image, strength, sample_mode, prompt, prompt_embeds, height, width, latents,
-                      num_inference_steps):
-        """Every argument check of an image-to-image call, before any GPU work.  Returns (image tensor on the host, height,
-        width, t_start)."""
+    def _img2img_args(self, prompt, image, strength, a, latents):
+        """Every argument check of an image-to-image call (``a``: the arguments of ``call``), before any GPU work.  Returns
+        (image tensor on the host, height, width, t_start)."""
         from .schedulers import PNDMScheduler
         if latents is not None:
             raise ValueError("image and latents are exclusive: the start latents of an image-to-image call are the noised "
@@ -1125,16 +1178,16 @@ class StableDiffusionModel:
             raise NotImplementedError(f"image= with {type(self.scheduler).__name__} is not built: PNDMScheduler duplicates its "
                                       "second timestep, and a schedule sliced at t_start changes what its PLMS warm-up means "
                                       "(DDIM, DPM-Solver and LCM are built)")
-        if sample_mode not in ("sample", "argmax"):
-            raise ValueError(f"sample_mode={sample_mode!r}: 'sample' or 'argmax'")
-        t_start, _ = self.img2img_steps(num_inference_steps, strength)
+        if a.sample_mode not in ("sample", "argmax"):
+            raise ValueError(f"sample_mode={a.sample_mode!r}: 'sample' or 'argmax'")
+        t_start, _ = self.img2img_steps(a.num_inference_steps, strength)
         img = self._image_tensor(image)
         ih, iw = int(img.shape[2]), int(img.shape[3])
         self.check_size(ih, iw)                  # the image's sides obey SIZE_RULE like height / width
-        for name, v, iv in (("height", height, ih), ("width", width, iw)):
+        for name, v, iv in (("height", a.height, ih), ("width", a.width, iw)):
             if v is not None and v != iv:
                 raise ValueError(f"{name}={v} disagrees with the image ({ih}x{iw}): the image defines the size of the call")
-        n_prompt = 1 if isinstance(prompt, str) else len(prompt) if prompt is not None else int(prompt_embeds.shape[0])
+        n_prompt = _prompt_batch(prompt, a.prompt_embeds)
         if img.shape[0] != n_prompt:
             raise ValueError(f"image batch {img.shape[0]} does not match the prompt batch {n_prompt}")
         return img, ih, iw, t_start
@@ -1148,57 +1201,33 @@ class StableDiffusionModel:
         noise = sdist.randn(shape, generator)
         return self.scheduler.add_noise(init, noise, first_timestep), init
 
+    def _begin_call(self, prompt, height, width, a):
+        """``_begin`` with the arguments ``a`` of ``call``, then the schedule.  Returns (device, batch, do_cfg, ctx)."""
+        begun = self._begin(prompt, height, width, a.guidance_scale, a.negative_prompt, a.num_images_per_prompt, a.prompt_embeds,
+                            a.negative_prompt_embeds, a.guidance_rescale, a.timesteps, a.sigmas, a.ip_adapter_image,
+                            a.ip_adapter_image_embeds)
+        self.scheduler.set_timesteps(a.num_inference_steps, device=begun[0])                    # :167-169
+        return begun
+
+    def _cache_branch(self) -> int:
+        dc = self._deepcache
+        return dc.cache_branch_id if dc is not None else -1
+
     @torch.no_grad()
-    def _call_img2img(self, prompt, image, strength, sample_mode, height, width, num_inference_steps, timesteps, sigmas,
-                      guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents, prompt_embeds,
-                      negative_prompt_embeds, output_type, return_dict, guidance_rescale, step_noise, collect_x0,
-                      ip_args=(None, None), control=None):
-        """The loop of ``call`` started part-way down the schedule from a noised encoding of ``image`` (SDEdit).  The
-        schedule is the full ``num_inference_steps`` one; the last ``N - t_start`` of its timesteps run.  A multistep
-        scheduler starts with a fresh history at that index (``_index_of`` resolves it from the timestep) while its
+    def _call_img2img(self, prompt, image, strength, a):
+        """The loop of ``call`` (``a``: its arguments) started part-way down the schedule from a noised encoding of ``image``
+        (SDEdit).  The schedule is the full ``num_inference_steps`` one; the last ``N - t_start`` of its timesteps run.  A
+        multistep scheduler starts with a fresh history at that index (``_index_of`` resolves it from the timestep) while its
         lower-order rules at the end still count against the full schedule.  DeepCache's plan indexes the list that runs,
         so the first executed step is a full one."""
-        img, ih, iw, t_start = self._img2img_args(image, strength, sample_mode, prompt, prompt_embeds, height, width, latents,
-                                                  num_inference_steps)
-        device, batch_size, do_cfg, ctx = self._begin(prompt, ih, iw, guidance_scale, negative_prompt,
-                                                      num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
-                                                      guidance_rescale, timesteps, sigmas, *ip_args)
-        unet_batch = ctx.shape[0]
-        self.scheduler.set_timesteps(num_inference_steps, device=device)
+        img, ih, iw, t_start = self._img2img_args(prompt, image, strength, a, a.latents)
+        device, batch_size, do_cfg, ctx = self._begin_call(prompt, ih, iw, a)
         ts_host = list(self.scheduler._timesteps_list)[t_start * self.scheduler.order:]
-        dc = self._deepcache
         # encoding and noising sit outside the timed region, as text encoding does
-        start, _ = self._img2img_start(img, sample_mode, generator, device, ts_host[0])
+        start, _ = self._img2img_start(img, a.sample_mode, a.generator, device, ts_host[0])
         self.img2img_start_latents = start
-        latents = self._start_loop(batch_size, device, None, start, ctx, dc.cache_branch_id if dc is not None else -1, control)
-        eps = self._eps_buffer(unet_batch, device)
-        self._num_timesteps = len(ts_host)
-        x0_preds = []
-        is_lcm = hasattr(self.scheduler, "config") and "timestep_scaling" in self.scheduler.config
-
-        torch.cuda.synchronize(device)
-        start_time = time.time()
-        for i, t in enumerate(ts_host):
-            mode = CACHE_OFF
-            if dc is not None:
-                mode = CACHE_FULL_AND_STORE if ts_host.index(t) % dc.cache_interval == 0 else CACHE_SKIP
-            self._control_step(i, len(ts_host), latents, unet_batch, t)
-            self._tome_step()
-            self.unet.forward_latents(latents, unet_batch, float(t), out=eps, cache_mode=mode)
-            kw = {}
-            if is_lcm and step_noise is not None and i < len(ts_host) - 1:
-                kw["noise"] = step_noise[i]             # indexed by EXECUTED step
-            if do_cfg and guidance_rescale > 0.0:
-                kw["guidance_rescale"] = guidance_rescale
-            step = self.scheduler.step_fused(eps, guidance_scale, latents, t, cfg=do_cfg, eta=eta, generator=generator, **kw)
-            latents, x0 = step[0], step[1]
-            if collect_x0:
-                x0_preds.append(x0[0:1])
-        self._control_end()
-        torch.cuda.synchronize(device)
-        execution_time = time.time() - start_time
-        return self._finish(latents, x0_preds, output_type, return_dict, execution_time)
-
+        latents = self._start_loop(batch_size, device, None, start, ctx, self._cache_branch(), a.control)
+        return self._run(a, ts_host, latents, ctx.shape[0], do_cfg)
     # -- inpainting (diffusers StableDiffusionInpaintPipeline, upstream-recall; DESIGN.md "Inpainting") ------------------
     @staticmethod
     def _mask_tensor(mask_image) -> torch.Tensor:
@@ -1212,22 +1241,16 @@ class StableDiffusionModel:
                 raise ValueError(f"mask_image must be a float tensor [B,1,H,W] or [B,H,W] in [0,1], got "
                                  f"{tuple(mask_image.shape)} {mask_image.dtype}")
             return m.to(torch.float32)
-        if isinstance(mask_image, (list, tuple)) and len(mask_image) > 0 and all(hasattr(im, "convert") for im in mask_image):
-            import numpy as np
-            sizes = {im.size for im in mask_image}
-            if len(sizes) != 1:
-                raise ValueError(f"mask_image: the PIL masks of one call must have one size, got {sorted(sizes)}")
-            arr = np.stack([np.asarray(im.convert("L"), dtype=np.float32) / 255.0 for im in mask_image])
+        if _is_pil_list(mask_image):
+            arr = _pil_stack(mask_image, "L", "float32", "mask_image: the PIL masks") / 255.0
             return torch.from_numpy(arr)[:, None].contiguous()
         raise ValueError("mask_image must be a float tensor [B,1,H,W] or [B,H,W] in [0,1] or a list of PIL images of one size")
 
-    def _inpaint_args(self, image, mask_image, strength, sample_mode, prompt, prompt_embeds, height, width, latents,
-                      num_inference_steps):
+    def _inpaint_args(self, prompt, image, mask_image, strength, a):
         """Every argument check of an inpainting call, before any GPU work: those of image-to-image, then the mask's.
         Returns (image, mask [B,1,H,W], height, width, t_start), tensors on the host."""
-        img, ih, iw, t_start = self._img2img_args(image, strength, sample_mode, prompt, prompt_embeds, height, width, None,
-                                                  num_inference_steps)
-        mask = self._mask_tensor(mask_image)
+        img, ih, iw, t_start = self._img2img_args(prompt, image, strength, a, None)
+        mask, latents = self._mask_tensor(mask_image), a.latents
         if tuple(mask.shape[2:]) != (ih, iw):
             raise ValueError(f"mask_image size {int(mask.shape[2])}x{int(mask.shape[3])} does not match the image size {ih}x{iw}")
         if mask.shape[0] != img.shape[0]:
@@ -1260,69 +1283,34 @@ class StableDiffusionModel:
         return masked, lmask
 
     @torch.no_grad()
-    def _call_inpaint(self, prompt, image, mask_image, strength, sample_mode, height, width, num_inference_steps, timesteps,
-                      sigmas, guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents, prompt_embeds,
-                      negative_prompt_embeds, output_type, return_dict, guidance_rescale, step_noise, collect_x0,
-                      ip_args=(None, None)):
+    def _call_inpaint(self, prompt, image, mask_image, strength, a):
         """The loop of ``_call_img2img`` with a mask (1 = repaint, 0 = keep).  A 4-channel UNet: after every step the kept
         region is replaced by the image's latents noised to the NEXT timestep (the image's latents themselves after the last
-        step) -- inside the step's launch (``step_fused(inpaint=...)``).  A 9-channel UNet reads the latent mask and the
-        masked image's latents as input channels 4..8 (``set_inpaint_cond``, once per call) and the loop does not blend.
+        step) -- inside the step's launch (the ``inpaint`` blend of ``_sample``).  A 9-channel UNet reads the latent mask and
+        the masked image's latents as input channels 4..8 (``set_inpaint_cond``, once per call) and the loop does not blend.
         Draws, in order: posterior noise of the image latents, forward noise (or ``latents``), and for a 9-channel UNet the
         posterior noise of the masked-image latents."""
-        img, mask, ih, iw, t_start = self._inpaint_args(image, mask_image, strength, sample_mode, prompt, prompt_embeds, height,
-                                                        width, latents, num_inference_steps)
-        device, batch_size, do_cfg, ctx = self._begin(prompt, ih, iw, guidance_scale, negative_prompt,
-                                                      num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
-                                                      guidance_rescale, timesteps, sigmas, *ip_args)
+        img, mask, ih, iw, t_start = self._inpaint_args(prompt, image, mask_image, strength, a)
+        device, batch_size, do_cfg, ctx = self._begin_call(prompt, ih, iw, a)
         nine = self.unet_config.in_channels == 9
-        unet_batch = ctx.shape[0]
-        self.scheduler.set_timesteps(num_inference_steps, device=device)
         ts_host = list(self.scheduler._timesteps_list)[t_start * self.scheduler.order:]
-        dc = self._deepcache
         # mask processing, encoding and noising sit outside the timed region, as text encoding does
         img = img.to(device)
         masked_img, lmask = self.inpaint_prepare(img, mask)
         shape = (batch_size, LATENT_CHANNELS, ih // self.vae_scale_factor, iw // self.vae_scale_factor)
         init = None
-        if not (nine and latents is not None):          # (9 channels from given noise at strength 1: nothing reads them)
-            init = self._image_latents(img, shape, sample_mode, generator)
-        noise = (latents if latents is not None else sdist.randn(shape, generator)).to(device, torch.float32).contiguous()
+        if not (nine and a.latents is not None):        # (9 channels from given noise at strength 1: nothing reads them)
+            init = self._image_latents(img, shape, a.sample_mode, a.generator)
+        noise = (a.latents if a.latents is not None else sdist.randn(shape, a.generator)).to(device, torch.float32).contiguous()
         if nine:
-            masked_latents = self._image_latents(masked_img, shape, sample_mode, generator)
+            masked_latents = self._image_latents(masked_img, shape, a.sample_mode, a.generator)
             self.unet.set_inpaint_cond(lmask, masked_latents)
         # upstream: pure noise (times init_noise_sigma, in _start_loop) at strength 1, the noised image latents below it
         start = noise if float(strength) == 1.0 else self.scheduler.add_noise(init, noise, ts_host[0])
         self.inpaint_image_latents, self.inpaint_latent_mask = init, lmask
-        latents = self._start_loop(batch_size, device, None, start, ctx, dc.cache_branch_id if dc is not None else -1)
+        latents = self._start_loop(batch_size, device, None, start, ctx, self._cache_branch())
         self.img2img_start_latents = latents
-        eps = self._eps_buffer(unet_batch, device)
-        self._num_timesteps = len(ts_host)
-        x0_preds = []
-        is_lcm = hasattr(self.scheduler, "config") and "timestep_scaling" in self.scheduler.config
-
-        torch.cuda.synchronize(device)
-        start_time = time.time()
-        for i, t in enumerate(ts_host):
-            mode = CACHE_OFF
-            if dc is not None:
-                mode = CACHE_FULL_AND_STORE if ts_host.index(t) % dc.cache_interval == 0 else CACHE_SKIP
-            self._tome_step()
-            self.unet.forward_latents(latents, unet_batch, float(t), out=eps, cache_mode=mode)
-            kw = {}
-            if is_lcm and step_noise is not None and i < len(ts_host) - 1:
-                kw["noise"] = step_noise[i]             # indexed by EXECUTED step
-            if do_cfg and guidance_rescale > 0.0:
-                kw["guidance_rescale"] = guidance_rescale
-            if not nine:
-                kw["inpaint"] = (init, noise, lmask, ts_host[i + 1] if i + 1 < len(ts_host) else None)
-            step = self.scheduler.step_fused(eps, guidance_scale, latents, t, cfg=do_cfg, eta=eta, generator=generator, **kw)
-            latents, x0 = step[0], step[1]
-            if collect_x0:
-                x0_preds.append(x0[0:1])
-        torch.cuda.synchronize(device)
-        execution_time = time.time() - start_time
-        return self._finish(latents, x0_preds, output_type, return_dict, execution_time)
+        return self._run(a, ts_host, latents, ctx.shape[0], do_cfg, None if nine else (init, noise, lmask))
 
     # -- the sampling loop (src/models.py:32-335) ----------------------------------------------
     @torch.no_grad()
@@ -1357,73 +1345,30 @@ class StableDiffusionModel:
         if padding_mask_crop is not None:
             raise NotImplementedError("padding_mask_crop is not built (the crop-and-paste of StableDiffusionInpaintPipeline; "
                                       "without it upstream composites nothing in pixel space, and neither does this)")
-        n_prompt = 1 if isinstance(prompt, str) else len(prompt) if prompt is not None else \
-            int(prompt_embeds.shape[0]) if prompt_embeds is not None else None      # (None: _begin refuses the call by name)
+        # (neither a prompt nor embeds: _begin refuses the call by name)
+        n_prompt = None if prompt is None and prompt_embeds is None else _prompt_batch(prompt, prompt_embeds)
         control = self._control_args(control_image, controlnet_conditioning_scale, control_guidance_start,
                                      control_guidance_end, guess_mode, mask_image, n_prompt)
+        a = SimpleNamespace(height=height, width=width, num_inference_steps=num_inference_steps, timesteps=timesteps,
+                            sigmas=sigmas, guidance_scale=guidance_scale, negative_prompt=negative_prompt,
+                            num_images_per_prompt=num_images_per_prompt, eta=eta, generator=generator, latents=latents,
+                            prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, output_type=output_type,
+                            return_dict=return_dict, guidance_rescale=guidance_rescale, step_noise=step_noise,
+                            collect_x0=collect_x0, sample_mode=sample_mode, ip_adapter_image=ip_adapter_image,
+                            ip_adapter_image_embeds=ip_adapter_image_embeds, control=control)
         if mask_image is not None:
             if image is None:
                 raise ValueError("mask_image without image: inpainting needs the image the mask refers to")
-            return self._call_inpaint(prompt, image, mask_image, 1.0 if strength is STRENGTH_UNSET else strength, sample_mode,
-                                      height, width, num_inference_steps, timesteps, sigmas, guidance_scale, negative_prompt,
-                                      num_images_per_prompt, eta, generator, latents, prompt_embeds, negative_prompt_embeds,
-                                      output_type, return_dict, guidance_rescale, step_noise, collect_x0,
-                                      (ip_adapter_image, ip_adapter_image_embeds))
+            return self._call_inpaint(prompt, image, mask_image, 1.0 if strength is STRENGTH_UNSET else strength, a)
         if self.unet_config.in_channels == 9:
             raise ValueError("this UNet has 9 input channels (an inpainting checkpoint: latents | mask | masked-image latents): "
                              "it runs only with image= and mask_image=, not as " +
                              ("plain image-to-image" if image is not None else "text-to-image"))
-        if strength is STRENGTH_UNSET:
-            strength = 0.8
         if image is not None:
-            return self._call_img2img(prompt, image, strength, sample_mode, height, width, num_inference_steps, timesteps,
-                                      sigmas, guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents,
-                                      prompt_embeds, negative_prompt_embeds, output_type, return_dict, guidance_rescale,
-                                      step_noise, collect_x0, (ip_adapter_image, ip_adapter_image_embeds), control)
-        device, batch_size, do_cfg, ctx = self._begin(prompt, height, width, guidance_scale, negative_prompt,
-                                                      num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
-                                                      guidance_rescale, timesteps, sigmas, ip_adapter_image, ip_adapter_image_embeds)
-        cfgu = self.unet_config
-        unet_batch = ctx.shape[0]
-
-        self.scheduler.set_timesteps(num_inference_steps, device=device)                        # :167-169
-        ts_host = list(self.scheduler._timesteps_list)
-        dc = self._deepcache
-        latents = self._start_loop(batch_size, device, generator, latents, ctx, dc.cache_branch_id if dc is not None else -1,
-                                   control)
-        eps = self._eps_buffer(unet_batch, device)
-        self._num_timesteps = len(ts_host)
-        x0_preds = []
-        is_lcm = hasattr(self.scheduler, "config") and "timestep_scaling" in self.scheduler.config
-
-        torch.cuda.synchronize(device)
-        start_time = time.time()                                                                   # :208
-        for i, t in enumerate(ts_host):                                                            # :211
-            mode = CACHE_OFF
-            if dc is not None:
-                # DeepCache: index of t in scheduler.timesteps, first step always full (A.5)
-                cur = ts_host.index(t)      # first match, as DeepCache's list.index (duplicate PNDM timestep quirk)
-                mode = CACHE_FULL_AND_STORE if (cur - 0) % dc.cache_interval == 0 else CACHE_SKIP
-            self._control_step(i, len(ts_host), latents, unet_batch, t)
-            self._tome_step()
-            self.unet.forward_latents(latents, unet_batch, float(t), out=eps, cache_mode=mode)     # :217-235
-            kw = {}
-            if is_lcm and step_noise is not None and i < len(ts_host) - 1:
-                kw["noise"] = step_noise[i]
-            if do_cfg and guidance_rescale > 0.0:                                                 # :244-250
-                kw["guidance_rescale"] = guidance_rescale
-            step = self.scheduler.step_fused(eps, guidance_scale, latents, t, cfg=do_cfg,          # :238-261
-                                             eta=eta, generator=generator, **kw)
-            if len(step) == 1:                                                                      # :257-261
-                latents = step[0]
-            else:
-                latents, x0 = step[0], step[1]
-                if collect_x0:
-                    x0_preds.append(x0[0:1])
-        self._control_end()
-        torch.cuda.synchronize(device)
-        execution_time = time.time() - start_time                                                 # :284-285
-        return self._finish(latents, x0_preds, output_type, return_dict, execution_time)
+            return self._call_img2img(prompt, image, 0.8 if strength is STRENGTH_UNSET else strength, a)
+        device, batch_size, do_cfg, ctx = self._begin_call(prompt, height, width, a)
+        latents = self._start_loop(batch_size, device, generator, latents, ctx, self._cache_branch(), control)
+        return self._run(a, list(self.scheduler._timesteps_list), latents, ctx.shape[0], do_cfg)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1449,20 +1394,19 @@ def _push_history(sched, noise_pred, latents):
     sched.model_outputs[-1] = model_output
 
 
-class _VariantBase(StableDiffusionModel):
-    """Shared step of the variant loops: UNet forward, then CFG combine (+ rescale) + ``scheduler.step`` in the fused
-    launches, returning the new latents; ``_combined`` gives the (rescaled) CFG-combined noise prediction the hand-off
-    needs."""
+def _combined(eps, do_cfg, guidance_scale, sched=None):
+    """The noise prediction the step saw: CFG combine, scaled by the rescale factors ``sched``'s last step computed
+    (``rescale_factors``; None when it did not rescale)."""
+    if not do_cfg:
+        return eps
+    u, c = eps.chunk(2)
+    g = u + guidance_scale * (c - u)                                                            # :238-242
+    k = getattr(sched, "rescale_factors", None)
+    return g if k is None else g * k.view(-1, *([1] * (g.dim() - 1)))
 
-    def _step_with(self, sched, eps, latents, t, unet_batch, do_cfg, guidance_scale, eta, generator, x0_preds,
-                   guidance_rescale=0.0):
-        self._tome_step()
-        self.unet.forward_latents(latents, unet_batch, float(t), out=eps, cache_mode=CACHE_OFF)
-        kw = {"guidance_rescale": guidance_rescale} if do_cfg and guidance_rescale > 0.0 else {}   # :583-590
-        step = sched.step_fused(eps, guidance_scale, latents, t, cfg=do_cfg, eta=eta, generator=generator, **kw)
-        if len(step) == 2:
-            x0_preds.append(step[1][0:1])
-        return step[0]
+
+class _VariantBase(StableDiffusionModel):
+    """The variants run ``_sample`` over their own list of steps, without DeepCache, and refuse the image arguments."""
 
     def _refuse_image(self, kwargs):
         if kwargs.get("control_image") is not None or kwargs.get("guess_mode"):
@@ -1474,17 +1418,6 @@ class _VariantBase(StableDiffusionModel):
         if kwargs.get("image") is not None:
             raise NotImplementedError(f"image= (image-to-image) is not built for {type(self).__name__}; "
                                       "StableDiffusionModel runs it")
-
-    @staticmethod
-    def _combined(eps, do_cfg, guidance_scale, sched=None):
-        """The noise prediction the step saw: CFG combine, scaled by the rescale factors ``sched``'s last step computed
-        (``rescale_factors``; None when it did not rescale)."""
-        if not do_cfg:
-            return eps
-        u, c = eps.chunk(2)
-        g = u + guidance_scale * (c - u)                                                            # :238-242
-        k = getattr(sched, "rescale_factors", None)
-        return g if k is None else g * k.view(-1, *([1] * (g.dim() - 1)))
 
 
 @models_registry.add_to_registry("stable_diffusion_model_two_schedulers")
@@ -1526,29 +1459,18 @@ class StableDiffusionModelTwoSchedulers(_VariantBase):
         device, batch_size, do_cfg, ctx = self._begin(prompt, height, width, guidance_scale, negative_prompt,
                                                       num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
                                                       guidance_rescale, timesteps, sigmas, ip_adapter_image, ip_adapter_image_embeds)
-        c = self.unet_config
-        unet_batch = ctx.shape[0]
         self.scheduler_first.set_timesteps(num_inference_steps_first, device=device)               # :484-487
         self.scheduler_second.set_timesteps(device=device, timesteps=self.scheduler_first._timesteps_list)  # :488-492
         first, second = self.switch_timestamp(self.scheduler_first._timesteps_list,
                                               self.scheduler_second._timesteps_list, num_step_switch, type_switch)
         self.scheduler = self.scheduler_first                     # prepare_latents reads init_noise_sigma
         latents = self._start_loop(batch_size, device, generator, latents, ctx, -1)
-        eps = self._eps_buffer(unet_batch, device)
         self._num_timesteps = len(first) + len(second)                                              # :545
-        x0_preds = []
-        hand_off = _is_dpm(self.scheduler_second)
-        torch.cuda.synchronize(device)
-        start_time = time.time()
-        for i, t in enumerate(first + second):                                                      # :550
-            in_first = i < len(first)
-            sched = self.scheduler_first if in_first else self.scheduler_second
-            latents = self._step_with(sched, eps, latents, t, unet_batch, do_cfg, guidance_scale, eta, generator,
-                                      x0_preds, guidance_rescale)
-            if in_first and hand_off:                                                               # :603-611
-                _push_history(self.scheduler_second, self._combined(eps, do_cfg, guidance_scale, sched), latents)
-        torch.cuda.synchronize(device)
-        return self._finish(latents, x0_preds, output_type, return_dict, time.time() - start_time)
+        hand_off = self.scheduler_second if _is_dpm(self.scheduler_second) else None                # :603-611
+        steps = [(t, self.scheduler_first, hand_off) for t in first] + [(t, self.scheduler_second, None) for t in second]  # :550
+        latents, x0_preds, execution_time = self._sample(steps, latents, ctx.shape[0], do_cfg, guidance_scale, eta, generator,
+                                                         guidance_rescale)
+        return self._finish(latents, x0_preds, output_type, return_dict, execution_time)
 
 
 @models_registry.add_to_registry("stable_diffusion_model_interliving_schedulers")
@@ -1584,33 +1506,20 @@ class StableDiffusionModelInterlivingSchedulers(_VariantBase):
         device, batch_size, do_cfg, ctx = self._begin(prompt, height, width, guidance_scale, negative_prompt,
                                                       num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
                                                       guidance_rescale, timesteps, sigmas, ip_adapter_image, ip_adapter_image_embeds)
-        c = self.unet_config
-        unet_batch = ctx.shape[0]
         order = self.scheduler_main.config.solver_order
         self.scheduler_main.set_timesteps(num_inference_steps, device=device)                       # :880-886
         self.scheduler_inter.set_timesteps(num_inference_steps // order, device=device)             # :888-894
         keep, t_inter = self.interleave_plan(self.scheduler_main._timesteps_list, order, interliving_steps)
         self.scheduler = self.scheduler_main
         latents = self._start_loop(batch_size, device, generator, latents, ctx, -1)
-        eps = self._eps_buffer(unet_batch, device)
         self._num_timesteps = len(self.scheduler_main._timesteps_list) - len(interliving_steps)     # :946
-        x0_preds = []
-        torch.cuda.synchronize(device)
-        start_time = time.time()
-        for t in keep:
-            if t in t_inter:                                                                        # :1008-1034
-                latents = self._step_with(self.scheduler_inter, eps, latents, t, unet_batch, do_cfg, guidance_scale,
-                                          eta, generator, x0_preds, guidance_rescale)
-                _push_history(self.scheduler_main, self._combined(eps, do_cfg, guidance_scale, self.scheduler_inter),
-                              latents)
-            else:                                                                                   # :1035-1054
-                latents = self._step_with(self.scheduler_main, eps, latents, t, unet_batch, do_cfg, guidance_scale,
-                                          eta, generator, x0_preds, guidance_rescale)
-                if _is_dpm(self.scheduler_inter):
-                    _push_history(self.scheduler_inter, self._combined(eps, do_cfg, guidance_scale, self.scheduler_main),
-                                  latents)
-        torch.cuda.synchronize(device)
-        return self._finish(latents, x0_preds, output_type, return_dict, time.time() - start_time)
+        main, inter = self.scheduler_main, self.scheduler_inter
+        to_inter = inter if _is_dpm(inter) else None
+        # an inter step feeds the main scheduler's history (:1008-1034), a main step the inter scheduler's (:1035-1054)
+        steps = [(t, inter, main) if t in t_inter else (t, main, to_inter) for t in keep]
+        latents, x0_preds, execution_time = self._sample(steps, latents, ctx.shape[0], do_cfg, guidance_scale, eta, generator,
+                                                         guidance_rescale)
+        return self._finish(latents, x0_preds, output_type, return_dict, execution_time)
 
 
 @models_registry.add_to_registry("stable_diffusion_model_skip_timesteps")
@@ -1630,23 +1539,14 @@ class StableDiffusionModelSkipTimesteps(_VariantBase):
         device, batch_size, do_cfg, ctx = self._begin(prompt, height, width, guidance_scale, negative_prompt,
                                                       num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
                                                       guidance_rescale, timesteps, sigmas, ip_adapter_image, ip_adapter_image_embeds)
-        c = self.unet_config
-        unet_batch = ctx.shape[0]
         self.scheduler.set_timesteps(num_inference_steps, device=device)
         ts_host = list(self.scheduler._timesteps_list)
         latents = self._start_loop(batch_size, device, generator, latents, ctx, -1)
-        eps = self._eps_buffer(unet_batch, device)
         self._num_timesteps = len(ts_host)                                                          # :1322
-        x0_preds = []
-        torch.cuda.synchronize(device)
-        start_time = time.time()
-        for i, t in enumerate(ts_host):
-            if i in skip:                                                                           # :1327-1330
-                continue
-            latents = self._step_with(self.scheduler, eps, latents, t, unet_batch, do_cfg, guidance_scale, eta,
-                                      generator, x0_preds, guidance_rescale)
-        torch.cuda.synchronize(device)
-        return self._finish(latents, x0_preds, output_type, return_dict, time.time() - start_time)
+        steps = [(t, self.scheduler, None) for i, t in enumerate(ts_host) if i not in skip]         # :1327-1330
+        latents, x0_preds, execution_time = self._sample(steps, latents, ctx.shape[0], do_cfg, guidance_scale, eta, generator,
+                                                         guidance_rescale)
+        return self._finish(latents, x0_preds, output_type, return_dict, execution_time)
 
 
 def _fuse_synthetic_lora(sd, seed: int, scale: float, rank: int):
