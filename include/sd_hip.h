@@ -246,6 +246,26 @@ int sd_unet_tome_matching_hw(sd_unet* u, void* stream, int block, int unet_batch
  * handle that never saw it, bit for bit. */
 int sd_unet_set_freeu(sd_unet* u, float s1, float s2, float b1, float b2);
 int sd_unet_disable_freeu(sd_unet* u);
+/* T-GATE (Zhang et al. 2024): temporal gating of the prompt cross-attention.  The handle has three states.
+ * mode 1, capture: forwards run today's plan for their batch with every cross-attention form computed WITHOUT its residual
+ * operand (the one-launch fused form reads a zeroed residual tensor) and one launch behind it (profile kind 24; csrc/tgate.hip)
+ * that writes h2 = h1 + y and the block's slice of `cache`: y itself when the UNet batch equals latent_batch, the mean of the
+ * [uncond | cond] pair's two rows (summed in fp32, stored as bf16) when it is twice that.  mode 2, reuse: forwards run at UNet
+ * batch = latent_batch on plans without norm2, attn2 and any context tensor -- sd_unet_set_context_hw is not needed and is
+ * refused -- where one launch per block (profile kind 25) writes h2 = h1 + slice.  Both launches deliver the row partials that
+ * keep norm3 folded into the GEGLU projection.  mode 0 with cache = NULL clears: the plans, workspace sizes and results of a
+ * handle that never saw it, bit for bit.
+ * `cache` is the CALLER's device buffer (256-byte aligned, at least sd_unet_tgate_bytes_hw bytes), borrowed until the next call:
+ * one [latent_batch * tokens][C] bf16 slice per transformer block in plan order (down, mid, up; sd_unet_tgate_block_info_hw:
+ * offset, rows and channels of one block, returns the block count, also for block < 0).  The capture and the reuse plans are
+ * other plans than the plain ones: call sd_unet_workspace_bytes_hw for each mode and batch that will run.  Reuse before a capture
+ * into the same buffer for the same latent batch and size fails and says so, at this call and at the forward.  Refused by name:
+ * fp8 handles, 9-channel inpainting UNets, UNets with an IP-Adapter, ControlNet residuals, DeepCache (its cached features are
+ * stored at the CFG batch). */
+long long sd_unet_tgate_bytes_hw(sd_unet* u, int latent_batch, int latent_h, int latent_w);
+int sd_unet_tgate_block_info_hw(sd_unet* u, int block, int latent_batch, int latent_h, int latent_w, long long* offset, long long* rows,
+                                int* channels);
+int sd_unet_set_tgate_hw(sd_unet* u, int mode, void* cache, long long bytes, int latent_batch, int latent_h, int latent_w);
 /* How many execution plans the handle has built so far (one per batch, DeepCache branch, latent size and variant); < 0 on a
  * null handle.  For tests of "this setting builds no new plan". */
 int sd_unet_plan_count(const sd_unet* u);
@@ -486,7 +506,8 @@ int sd_op_inception_resize(void* stream, const unsigned char* images, int B, int
 /* Measurement hook for bench.py: the same forward with a hipEvent pair around every launch.  Per
  * op kind (0 sinusoid, 1 gemv, 2 conv_in, 3 groupnorm, 4 conv3x3, 5 gemm, 6 layernorm,
  * 7 attention, 8 conv_out; 16 conv3x3 with fp8 operands, 17 gemm with fp8 operands, 18 fused prompt cross-attention,
- * 22 IP-Adapter image branch, 23 ControlNet residual add) it returns summed
+ * 22 IP-Adapter image branch, 23 ControlNet residual add, 24 T-GATE capture, 25 T-GATE apply, 26 the zero fill of a T-GATE
+ * capture plan's fused cross-attention residual) it returns summed
  * milliseconds, launch count, algorithmic FLOPs and algorithmic HBM bytes in arrays of SD_PROFILE_KINDS = 32
  * entries.  Synchronises the stream; never used inside a timed region. */
 #define SD_PROFILE_KINDS 32
@@ -665,6 +686,14 @@ int sd_op_tome_unmerge(void* stream, const void* y, long long ldy, const void* r
  * in fp32 with one rounding -- and hidden_out [B][H][W][C_hidden] = hidden with channels [0, C_hidden / 2) times b (one rounding),
  * the others copied.  The outputs must be new tensors.  H, W in [2, 128]; C_hidden, C_skip multiples of 32; b, s finite and > 0.
  * Deterministic. */
+/* T-GATE's two kernels (csrc/tgate.hip) on bf16 rows of C channels, C a multiple of 8, any row count; fp32 sums rounded
+ * once to bf16.  capture: y, res [pair * rows][C] -> h2 = res + y for every row and cache [rows][C] = (y[m] + y[rows + m]) / 2
+ * (pair 2: a CFG pair) or y (pair 1).  apply: h2 [rows][C] = h1 + cache.  rowstats (NULL = off): [2][rows of h2][2] fp32, the (sum, sum
+ * of squares) of the stored h2 row's first ceil(C / 16) 16-byte vectors and of the rest (the LayerNorm-fold partials of
+ * sd_op_gemm_ln).  The outputs are new tensors; anything else is refused by name and nothing is written. */
+int sd_op_tgate_capture(void* stream, const void* y, const void* res, void* h2, void* cache, float* rowstats, long long rows, int C,
+                        int pair);
+int sd_op_tgate_apply(void* stream, const void* h1, const void* cache, void* h2, float* rowstats, long long rows, int C);
 int sd_op_freeu(void* stream, const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W,
                 int C_hidden, int C_skip, float b, float s);
 /* flash-style attention on token-major [B, N, heads * D] views; D = 40, 64, 80 or 160 (64: Stable Diffusion 2.x), any Nq / Nk */

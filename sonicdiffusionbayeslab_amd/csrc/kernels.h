@@ -236,6 +236,16 @@ int sd_freeu_check(int B, int H, int W, int C_hidden, int C_skip, const char* wh
 int sd_launch_freeu(const bf16_t* hidden, const bf16_t* skip, bf16_t* hidden_out, bf16_t* skip_out, int B, int H, int W, int C_hidden,
                     int C_skip, float b, float s, hipStream_t stream);
 
+// tgate.hip: T-GATE's two elementwise kernels (bf16 rows of C channels, C a multiple of 8; fp32 sums rounded once).  capture: y and
+// res [pair * rows][C] -> h2 = res + y for every row, cache [rows][C] = the mean of the pair's two y rows (pair == 1: y itself).
+// apply: h2 [rows][C] = h1 + cache.  rowstats (may be null): [SD_TGATE_PARTS][rows of h2][2] fp32 LayerNorm partials of the stored h2
+// (GemmArgs::ln_rs).  The outputs are new tensors.
+constexpr int SD_TGATE_PARTS = 2;
+int sd_tgate_check(long rows, int C, const char* who);
+int sd_launch_tgate_capture(const bf16_t* y, const bf16_t* res, bf16_t* h2, bf16_t* cache, float* rowstats, long rows, int C, int pair,
+                            hipStream_t stream);
+int sd_launch_tgate_apply(const bf16_t* h1, const bf16_t* cache, bf16_t* h2, float* rowstats, long rows, int C, hipStream_t stream);
+
 // xattn.hip: fused prompt cross-attention  Y = R + sum_h softmax_L(X A_h) B_h + b_o  (one launch per block)
 struct XattnArgs {
     const bf16_t* X = nullptr;    // [M, C] LayerNorm output

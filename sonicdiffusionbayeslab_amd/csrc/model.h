@@ -47,7 +47,10 @@ enum OpKind { OP_SINUSOID, OP_GEMV, OP_CONV_IN, OP_GN, OP_CONV3, OP_GEMM, OP_LN,
               OP_VIT_PREP, OP_VIT_EMBED, OP_VIT_ATTN, OP_POOL, OP_CONV_IN_IMG, OP_ENC_OUT, OP_IP_XATTN, OP_RES_ADD,
               OP_BERT_ATTN, OP_REWARD_HEAD,
               OP_TOME_MATCH, OP_TOME_SELECT, OP_TOME_MERGE, OP_TOME_UNMERGE,
-              OP_FREEU };
+              OP_FREEU,
+              OP_TGATE_CAPTURE, OP_TGATE_APPLY, OP_TGATE_ZERO };
+
+constexpr int TGATE_OFF = 0, TGATE_CAPTURE = 1, TGATE_REUSE = 2;      // sd_unet_set_tgate_hw modes
 
 constexpr int REP_TEXT_POOLED = 2;       // Plan::rep of a CLIP text handle's sd_clip_text_embeds plan
 
@@ -177,6 +180,16 @@ struct Plan {
     // FreeU variant (part of the plan key): one OP_FREEU in front of every resnet of up blocks 0 and 1 (x1 = hidden, x2 = skip ->
     // out = the scaled hidden, aux = the filtered skip, epi = the up block: which pair of the handle's factors the launch reads)
     int freeu = 0;
+    // T-GATE variant (part of the plan key; tgate.hip): TGATE_CAPTURE = every prompt cross-attention form runs WITHOUT its residual
+    // operand and one OP_TGATE_CAPTURE behind it writes h2 = h1 + y and the block's slice of the handle's cache (tg_pair = rows of
+    // y per cache row: 2 for a CFG pair [uncond | cond]); TGATE_REUSE = norm2, attn2 and every context tensor are gone and one
+    // OP_TGATE_APPLY writes h2 = h1 + slice.  tg_off / tg_rows / tg_ch: the slices in plan order (tgate_segments), for tg_batch
+    // latents; Op::b2idx of the two ops = the block's index.
+    int tgate = 0, tg_pair = 1, tg_batch = 0;
+    std::vector<size_t> tg_off;
+    std::vector<long> tg_rows;
+    std::vector<int> tg_ch;
+    int tg_blocks = 0;                    // blocks the builder has wired so far
     std::vector<Tn> tensors;
     std::vector<Op> ops;
     std::vector<char> skipped;            // per op: skipped on a DeepCache skip step
@@ -240,8 +253,9 @@ struct sd_unet {
         return (int)act_names.size() - 1;
     }
     // (UNet batch, DeepCache branch, prefix replication, latent H, W, IP-Adapter variant, control variant, Token Merging: the
-    // bits of the ratio and max_downsample, both 0 = off; FreeU on / off)
-    std::map<std::tuple<int, int, int, int, int, int, int, long long, int, int>, sdhip::Plan> plans;
+    // bits of the ratio and max_downsample, both 0 = off; FreeU on / off; T-GATE mode: TGATE_OFF / CAPTURE / REUSE; T-GATE pair: y rows per
+    // cache row of a capture, 2 for a CFG pair, else 1)
+    std::map<std::tuple<int, int, int, int, int, int, int, long long, int, int, int, int>, sdhip::Plan> plans;
     int last_rep = 1, last_ip = 0, last_cn = 0;                       // variant of the last forward (sd_unet_debug_tensor)
     int last_h = 0, last_w = 0;                          // latent size of the last forward (sd_unet_debug_tensor)
     std::unordered_map<std::string, long> tproj_off;  // resnet prefix -> float index into tproj vector
@@ -287,6 +301,14 @@ struct sd_unet {
     // FreeU (sd_unet_set_freeu; kind 0, bf16): on = the "freeu" plan variants; the factors are read when OP_FREEU is launched
     bool freeu_on = false;
     float freeu_s[2] = {1.f, 1.f}, freeu_b[2] = {1.f, 1.f};       // (s1, s2), (b1, b2): up block 0, up block 1
+    // T-GATE (sd_unet_set_tgate_hw; kind 0, bf16): mode off = the plans of a handle that never saw it.  The cache is the caller's
+    // buffer, borrowed like ctrl_res (the capture plan at the CFG batch and the reuse plan at the latent batch share it), laid out
+    // for tg_b latents at tg_h x tg_w; tg_captured: a capture forward has filled it for exactly that layout.
+    int tg_mode = 0;
+    char* tg_cache = nullptr;
+    long long tg_bytes = 0;
+    int tg_b = 0, tg_h = 0, tg_w = 0;
+    bool tg_captured = false;
     bool unet_like() const { return kind == 0 || kind == 5; }      // runs the UNet's encoder ops (plan.hip Builder::build)
 };
 
@@ -334,11 +356,17 @@ long long taesd_workspace_bytes(const sd_unet* u, int batch, int lh, int lw);
 // plan.hip
 int plan_rep(const sd_unet* u, int latent_batch, int unet_batch);
 int check_latent_size(const sd_unet* u, int lh, int lw, const char* who);
-int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep = 1, int lh = -1, int lw = -1, int ip = 0, int cn = 0);     // lh / lw < 0: the handle's sample_size (square)
+// lh / lw < 0: the handle's sample_size (square); tgate < 0: the handle's T-GATE mode (tgate_variant), 0 = the plain plan
+int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep = 1, int lh = -1, int lw = -1, int ip = 0, int cn = 0, int tgate = -1);
+int tgate_variant(const sd_unet* u);              // the T-GATE mode of the handle's plans (TGATE_OFF unless a UNet handle has one set)
+int tgate_pair(const sd_unet* u, int UB);         // y rows per cache row of a capture forward at batch UB (2 = a CFG pair)
 bool ip_active(const sd_unet* u, int UB, int branch, int lh, int lw);     // is this forward's IP-Adapter key set?
 // the ControlNet residual segments of a (UNet batch, latent size), in order: byte offset into the residual buffer and bf16
 // element count of each (include/sd_hip.h: the layout); returns the buffer's bytes
 size_t control_segments(const sd_unet_config& c, int UB, int lh, int lw, std::vector<size_t>* off, std::vector<long>* count);
+// the T-GATE cache slices of `batch` latents at a latent size, one per transformer block in plan order (down, mid, up): byte
+// offset into the cache buffer, rows (batch * tokens) and channels of each; returns the buffer's bytes
+size_t tgate_segments(const sd_unet_config& c, int batch, int lh, int lw, std::vector<size_t>* off, std::vector<long>* rows, std::vector<int>* ch);
 
 // unet.hip
 int ensure_zero_page();

@@ -469,6 +469,16 @@ extern "C" int sd_op_freeu(void* stream, const void* hidden, const void* skip, v
                            b, s, (hipStream_t)stream);
 }
 
+// T-GATE's capture and apply kernels (tgate.hip); rowstats may be null
+extern "C" int sd_op_tgate_capture(void* stream, const void* y, const void* res, void* h2, void* cache, float* rowstats, long long rows,
+                                   int C, int pair) {
+    return sd_launch_tgate_capture((const bf16_t*)y, (const bf16_t*)res, (bf16_t*)h2, (bf16_t*)cache, rowstats, (long)rows, C, pair,
+                                   (hipStream_t)stream);
+}
+extern "C" int sd_op_tgate_apply(void* stream, const void* h1, const void* cache, void* h2, float* rowstats, long long rows, int C) {
+    return sd_launch_tgate_apply((const bf16_t*)h1, (const bf16_t*)cache, (bf16_t*)h2, rowstats, (long)rows, C, (hipStream_t)stream);
+}
+
 // Token Merging, kernel by kernel (tome.hip); index lists in src / dst slot numbers, tok [h * w] from sd_op_tome_match
 extern "C" int sd_op_tome_match(void* stream, const void* x, const unsigned char* choice, int B, int h, int w, int C,
                                 float* node_max, int* node_idx, int* tok) {

@@ -52,6 +52,15 @@ struct Builder {
         push(o);
         return o.out;
     }
+    // T-GATE capture: a zeroed tensor of at least `bytes`, the residual operand of the fused cross-attention form (filled by an
+    // op of its own in front of its first reader; a later, larger request gets a new one)
+    int tg_zero = -1;
+    int tgate_zero(size_t bytes) {
+        if (tg_zero < 0 || pl.tensors[tg_zero].bytes < bytes) {
+            Op o; o.kind = OP_TGATE_ZERO; o.out = tg_zero = tensor(bytes); push(o);
+        }
+        return tg_zero;
+    }
     // SD_LN_FOLD=0: every LayerNorm is its own launch (round-1 behaviour)
     bool ln_fold = !(getenv("SD_LN_FOLD") && atoi(getenv("SD_LN_FOLD")) == 0);
     // Ask the op that produced a residual-stream tensor for per-row LayerNorm partials; returns the partial count (0 =
@@ -60,6 +69,7 @@ struct Builder {
         int np = 0;
         if (o.kind == OP_GEMM && o.epi == 0 && o.splitk == 1 && !o.out_fp8 && o.N == C && o.M == M && o.ldc_o == 0) np = (C + 159) / 160 * 2;
         else if (o.kind == OP_XATTN && o.N == C && o.M == M) np = 2 * sd_xattn_slices(M, C);
+        else if ((o.kind == OP_TGATE_CAPTURE || o.kind == OP_TGATE_APPLY) && o.N == C && o.M == M) np = SD_TGATE_PARTS;
         // the consumer's preconditions (gemm_conv.hip::check_ln): K = C >= 128 (two K tiles: with one, the c1 | c2 LDS-DMA is
         // never waited for), at most 16 partials per row, 128-row tiles -- otherwise the plan keeps the separate LayerNorm
         static const bool big_tiles = getenv("SD_GEMM_BIG") != nullptr;
@@ -322,6 +332,19 @@ struct Builder {
         // norm2 (round 5): folded into the first kernel of whichever form runs -- rstd from the row partials attn1.to_out's
         // epilogue delivers, gamma in the operand (A^T centred over the channel: the row mean drops out; the plain to_q weights
         // with the c1 correction), beta as a constant per key slot / output column.  SD_XATTN_LN=0: the separate LayerNorm launch.
+        // T-GATE (tgate.hip).  Reuse: norm2, attn2 and their context tensors are gone -- h2 = h1 + the block's cache slice, one
+        // launch, which also delivers the row partials norm3's fold reads.  Capture (below): whichever form runs, runs WITHOUT
+        // its residual operand, so that its output is y = to_out(attention) + b_o alone, and OP_TGATE_CAPTURE adds the residual.
+        const int tg_i = pl.tgate ? pl.tg_blocks++ : -1;
+        if (pl.tgate && (tg_i >= (int)pl.tg_rows.size() || pl.tg_rows[tg_i] != (long)(M / pl.tg_pair) || pl.tg_ch[tg_i] != C)) {
+            if (error.empty()) error = "T-GATE cache layout (block " + std::to_string(tg_i) + ")";
+            return x;
+        }
+        if (pl.tgate == TGATE_REUSE) {
+            Op o; o.kind = OP_TGATE_APPLY; o.x1 = h1; o.M = M; o.N = C; o.b2idx = tg_i;
+            o.out = tensor((size_t)M * C * 2); push(o);
+            return transformer_ff(p, t, x, o.out, M, C, fq);
+        }
         static const int fused_min_hw = getenv("SD_XATTN_FUSED") ? atoi(getenv("SD_XATTN_FUSED")) : 1024;
         static const int fold_max_hw = getenv("SD_XATTN_FOLD") ? atoi(getenv("SD_XATTN_FOLD")) : 1024;
         static const bool xln_off = getenv("SD_XATTN_LN") && atoi(getenv("SD_XATTN_LN")) == 0;
@@ -356,13 +379,15 @@ struct Builder {
             o.g = W(t + "norm2.weight"); o.be = W(t + "norm2.bias"); o.eps = 1e-5f;
             o.out = tensor((size_t)M * C * 2); push(o); res = o.out;
         }
+        const bool tg_cap = pl.tgate == TGATE_CAPTURE;
         int h2;
         if (xmode == 0) {
             int at = ctx_tensor((size_t)UB * NP * C * 2), bw = ctx_tensor((size_t)UB * C * NP * 2);
             Plan::Fold fd{kv, at, bw, C, NH, W(t + (np2 > 0 ? "attn2.to_q.weight.T.ln" : "attn2.to_q.weight.T")), W(t + "attn2.to_out.0.weight"), true};
             if (np2 > 0) { fd.c2 = ctx_tensor((size_t)UB * NP * 4); fd.lnu = W(t + "attn2.to_q.lnu"); }
             pl.ctx_fold.push_back(fd);
-            Op o; o.kind = OP_XATTN; o.x1 = n2; o.r = res; o.wt = at; o.x2 = bw; o.M = M; o.N = C; o.K = NP; o.rpb = hw;
+            // (the fused kernel always adds a residual tensor: under a T-GATE capture it reads a zeroed one, OP_TGATE_ZERO)
+            Op o; o.kind = OP_XATTN; o.x1 = n2; o.r = tg_cap ? tgate_zero((size_t)M * C * 2) : res; o.wt = at; o.x2 = bw; o.M = M; o.N = C; o.K = NP; o.rpb = hw;
             o.sm_valid = L; o.b = W(t + "attn2.to_out.0.bias"); o.heads = NH;
             if (np2 > 0) { o.lnrs = rs2; o.lnnp = np2; o.s1 = fd.c2; o.ldx_o = rs2_rows; }   // (s1: the c2 tensor; ldx_o: rows of the partials)
             o.out = tensor((size_t)M * C * 2); push(o); h2 = o.out;
@@ -380,14 +405,24 @@ struct Builder {
               if (np2 > 0) { o.lnrs = rs2; o.lnnp = np2; o.s1 = fd.c1; o.s2 = fd.c2; }          // (s1 / s2: the per-sample c1 / c2 tensors)
               o.out = tensor((size_t)M * NP * 2); push(o); pr = o.out; }
             { Op o; o.kind = OP_GEMM; o.x1 = pr; o.K1 = NP; o.K = NP; o.M = M; o.N = C; o.epi = 0;
-              o.wt = bw; o.wbs = (long)C * NP; o.rpb = hw; o.b = W(t + "attn2.to_out.0.bias"); o.r = res;
+              o.wt = bw; o.wbs = (long)C * NP; o.rpb = hw; o.b = W(t + "attn2.to_out.0.bias"); o.r = tg_cap ? -1 : res;
               o.out = tensor((size_t)M * C * 2); push(o); h2 = o.out; }
         } else {
             int q2 = np2 > 0 ? gemm_ln(h1, rs2, np2, M, C, C, t + "attn2.to_q.weight", 0)
                              : gemm(n2, C, -1, 0, M, C, t + "attn2.to_q.weight", "", -1, 0);
             int a2 = attn(q2, 0, C, kv, 0, C, 2 * C, hw, L, C, NH);
-            h2 = gemm(a2, C, -1, 0, M, C, t + "attn2.to_out.0.weight", t + "attn2.to_out.0.bias", res, 0);
+            h2 = gemm(a2, C, -1, 0, M, C, t + "attn2.to_out.0.weight", t + "attn2.to_out.0.bias", tg_cap ? -1 : res, 0);
         }
+        if (tg_cap) {
+            Op o; o.kind = OP_TGATE_CAPTURE; o.x1 = h2; o.r = res; o.M = M; o.N = C; o.K = pl.tg_pair; o.b2idx = tg_i;
+            o.out = tensor((size_t)M * C * 2); push(o); h2 = o.out;
+        }
+        return transformer_ff(p, t, x, h2, M, C, fq);
+    }
+    // the feed-forward half of a BasicTransformerBlock and the Transformer2DModel's exit (h2 = the residual stream after attn2,
+    // produced by the op pushed last; x = the block's input)
+    int transformer_ff(const std::string& p, const std::string& t, int x, int h2, int M, int C, bool fq) {
+        int rs = -1, np = 0;
         int ff;
         if (!fq && (np = want_rowstats(pl.ops.back(), M, C, rs)) > 0) {       // norm3 folded into the GEGLU projection
             ff = gemm_ln(h2, rs, np, M, 8 * C, C, t + "ff.geglu.weight", 1);
@@ -409,7 +444,6 @@ struct Builder {
         if (pl.ops.back().splitk == 1 && sd_gemm_tile_rows(M, C, pl.ops.back().K) == 128) want_stats(pl.ops.back(), M, C);
         return out;
     }
-
     // ---- AutoencoderKL decoder: latents/scale -> post_quant_conv -> decoder -> image ----
     int vae_resnet(const std::string& p, int x, int cin, int cout, int rh, int rw) {
         const int hw = rh * rw, M = UB * hw;
@@ -701,13 +735,18 @@ struct Builder {
         const sd_unet_config& c = u->cfg;
         const int nl = c.num_levels, c0 = c.block_out_channels[0], temb = 4 * c0;
         const int L = c.context_len;
-        pl.ctx_bf16 = ctx_tensor((size_t)UB * L * c.cross_attention_dim * 2);
+        if (pl.tgate) {
+            pl.tg_batch = UB / pl.tg_pair;
+            tgate_segments(c, pl.tg_batch, pl.lh, pl.lw, &pl.tg_off, &pl.tg_rows, &pl.tg_ch);
+        }
+        // (a T-GATE reuse plan has no prompt cross-attention: no context tensor at all, sd_unet_set_context_hw is not needed for it)
+        if (pl.tgate != TGATE_REUSE) pl.ctx_bf16 = ctx_tensor((size_t)UB * L * c.cross_attention_dim * 2);
         // masked K / V expansions used by sd_unet_set_context for the folded cross-attention: sized for the level with the most
         // (head, key slot) rows x channels (the mid block sits on the last level)
         size_t fold_max = 0;
         for (int i = 0; i < nl; ++i)
             if (c.attn_levels[i] || i == nl - 1) fold_max = std::max(fold_max, (size_t)level_heads(c, i) * 80 * c.block_out_channels[i]);
-        pl.ctx_fold_scratch = ctx_tensor((size_t)3 * UB * fold_max * 2);
+        if (pl.tgate != TGATE_REUSE) pl.ctx_fold_scratch = ctx_tensor((size_t)3 * UB * fold_max * 2);
         if (pl.ip) {      // what sd_unet_set_ip_adapter_hw computes on the way to the folded operands (its expansions reuse the scratch above)
             const int T = c.ip_adapter_tokens, CD = c.cross_attention_dim;
             int cmax = 0;
@@ -837,6 +876,7 @@ struct Builder {
             wrapstack.pop_back();
             pl.taps["up" + std::to_string(i)] = h;
         }
+        if (pl.tgate && pl.tg_blocks != (int)pl.tg_rows.size() && error.empty()) error = "T-GATE cache layout (block count)";
         // ---- out ----
         int g = gn(h, ch, -1, 0, rh * rw, "conv_norm_out.weight", "conv_norm_out.bias", c.norm_eps, 1);
         { Op o; o.kind = OP_CONV_OUT; o.x1 = g; o.out = T_EPS; o.B = UB; o.Hin = rh; o.Win = rw; o.Cin = ch; o.N = c.out_channels;
@@ -1012,11 +1052,46 @@ size_t control_segments(const sd_unet_config& c, int UB, int lh, int lw, std::ve
     return bytes;
 }
 
+size_t tgate_segments(const sd_unet_config& c, int batch, int lh, int lw, std::vector<size_t>* off, std::vector<long>* rows, std::vector<int>* ch) {
+    off->clear(); rows->clear(); ch->clear();
+    size_t bytes = 0;
+    auto seg = [&](int C, int h, int w) {
+        const long m = (long)batch * h * w;
+        off->push_back(bytes); rows->push_back(m); ch->push_back(C);
+        bytes = (bytes + (size_t)m * C * 2 + 255) / 256 * 256;
+    };
+    const int nl = c.num_levels;
+    int h = lh, w = lw;
+    for (int i = 0; i < nl; ++i) {
+        for (int j = 0; j < c.layers_per_block; ++j)
+            if (c.attn_levels[i]) seg(c.block_out_channels[i], h, w);
+        if (i < nl - 1) { h /= 2; w /= 2; }
+    }
+    seg(c.block_out_channels[nl - 1], h, w);
+    for (int i = 0; i < nl; ++i) {
+        const int lev = nl - 1 - i;
+        for (int j = 0; j < c.layers_per_block + 1; ++j)
+            if (c.attn_levels[lev]) seg(c.block_out_channels[lev], h, w);
+        if (i < nl - 1) { h *= 2; w *= 2; }
+    }
+    return bytes;
+}
+
+// the T-GATE mode of the handle's plans (only UNet handles have one)
+int tgate_variant(const sd_unet* u) {
+    return u->kind == 0 ? u->tg_mode : TGATE_OFF;
+}
+
+// y rows per cache row of a capture at batch UB: 2 for a CFG pair (the forward's batch is twice the batch the cache was laid out for)
+int tgate_pair(const sd_unet* u, int UB) {
+    return UB == 2 * u->tg_b ? 2 : 1;
+}
+
 bool ip_active(const sd_unet* u, int UB, int branch, int lh, int lw) {
     return u->ip_keys.count(std::make_tuple(UB, branch < 0 ? -1 : branch, lh, lw)) != 0;
 }
 
-int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw, int ip, int cn) {
+int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw, int ip, int cn, int tgate) {
     SD_REQUIRE(u && u->finalized, "unet: parameters not finalized");
     SD_REQUIRE(UB > 0 && UB <= 4096, "unet: bad batch %d", UB);
     SD_REQUIRE(branch < 3 * u->cfg.num_levels, "unet: cache_branch_id %d out of range", branch);
@@ -1026,7 +1101,11 @@ int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw
     long long tome_bits = 0;
     if (u->kind == 0 && u->tome_ratio > 0.0) memcpy(&tome_bits, &u->tome_ratio, sizeof(tome_bits));
     const int freeu = u->kind == 0 && u->freeu_on ? 1 : 0;
-    auto key = std::make_tuple(UB, branch, rep, lh, lw, ip, cn, tome_bits, tome_bits ? u->tome_max_downsample : 0, freeu);
+    if (tgate < 0) tgate = tgate_variant(u);
+    const int tg_pair = tgate == TGATE_CAPTURE ? tgate_pair(u, UB) : 1;
+    SD_REQUIRE(!tgate || (branch < 0 && !ip && !cn && !u->fp8), "unet: T-GATE with DeepCache, an IP-Adapter, ControlNet residuals or fp8 is not built");
+    SD_REQUIRE(tg_pair == 1 || UB % 2 == 0, "unet: a T-GATE capture of a CFG pair needs an even batch (%d)", UB);
+    auto key = std::make_tuple(UB, branch, rep, lh, lw, ip, cn, tome_bits, tome_bits ? u->tome_max_downsample : 0, freeu, tgate, tg_pair);
     auto it = u->plans.find(key);
     if (it == u->plans.end()) {
         if (lh != u->cfg.sample_size || lw != u->cfg.sample_size)
@@ -1040,6 +1119,8 @@ int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw
         pl.ip = ip;
         pl.cn = cn;
         pl.freeu = freeu;
+        pl.tgate = tgate;
+        pl.tg_pair = tg_pair;
         Builder b{u, pl, UB, {}};
         b.build();
         SD_REQUIRE(b.error.empty(), "unet: cannot build the plan for batch %d (cache branch %d, latent %dx%d): %s", UB, branch, lh, lw,

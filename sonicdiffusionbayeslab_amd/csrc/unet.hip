@@ -187,6 +187,20 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
             SD_REQUIRE(u->freeu_on && (o.epi == 0 || o.epi == 1), "forward: FreeU is off (sd_unet_set_freeu)");
             return sd_launch_freeu((const bf16_t*)T(o.x1), (const bf16_t*)T(o.x2), (bf16_t*)T(o.out), (bf16_t*)T(o.aux), o.B, o.Hin, o.Win,
                                    o.C1, o.C2, u->freeu_b[o.epi], u->freeu_s[o.epi], stream);
+        case OP_TGATE_ZERO:
+            SD_CHECK_HIP(hipMemsetAsync(T(o.out), 0, pl.tensors[o.out].bytes, stream));
+            return 0;
+        case OP_TGATE_CAPTURE:
+        case OP_TGATE_APPLY: {      // (sd_unet_forward_hw has checked the handle's cache against this plan's layout)
+            SD_REQUIRE(u->tg_cache && o.b2idx >= 0 && o.b2idx < (long)pl.tg_off.size() &&
+                           pl.tg_off[o.b2idx] + (size_t)pl.tg_rows[o.b2idx] * o.N * 2 <= (size_t)u->tg_bytes,
+                       "forward: no T-GATE cache for block %ld (sd_unet_set_tgate_hw)", o.b2idx);
+            bf16_t* slice = (bf16_t*)(u->tg_cache + pl.tg_off[o.b2idx]);
+            if (o.kind == OP_TGATE_APPLY)
+                return sd_launch_tgate_apply((const bf16_t*)T(o.x1), slice, (bf16_t*)T(o.out), (float*)T(o.rs), o.M, o.N, stream);
+            return sd_launch_tgate_capture((const bf16_t*)T(o.x1), (const bf16_t*)T(o.r), (bf16_t*)T(o.out), slice, (float*)T(o.rs),
+                                           o.M / o.K, o.N, o.K, stream);
+        }
         case OP_REPLICATE:
             return sd_launch_replicate(T(o.x1), T(o.out), (long)o.M * 16, o.N, stream);
         case OP_TOME_MATCH:
@@ -715,9 +729,10 @@ extern "C" long long sd_unet_workspace_bytes_hw(sd_unet* u, int unet_batch, int 
     if (get_plan(u, unet_batch, cache_branch_id, &pl, 1, latent_h, latent_w)) return -1;
     size_t bytes = pl->total_bytes;
     const bool pair = unet_batch % 2 == 0 && plan_rep(u, unet_batch / 2, unet_batch) == 2;      // the CFG-pair variant of the plan
-    for (int ip = 0; ip <= (u->kind == 0 && u->cfg.ip_adapter_tokens > 0 ? 1 : 0); ++ip)         // ... and the IP-Adapter variants
+    const bool tg = tgate_variant(u) != TGATE_OFF;       // (T-GATE capture / reuse: no IP-Adapter and no control variants exist)
+    for (int ip = 0; ip <= (u->kind == 0 && u->cfg.ip_adapter_tokens > 0 && !tg ? 1 : 0); ++ip)         // ... and the IP-Adapter variants
         for (int rep = 1; rep <= (pair ? 2 : 1); ++rep)
-            for (int cn = 0; cn <= (u->kind == 0 && u->ctrl_enabled && cache_branch_id < 0 ? 1 : 0); ++cn) {      // ... and, once a ControlNet's residuals were set, the control variants
+            for (int cn = 0; cn <= (u->kind == 0 && u->ctrl_enabled && cache_branch_id < 0 && !tg ? 1 : 0); ++cn) {      // ... and, once a ControlNet's residuals were set, the control variants
                 if (get_plan(u, unet_batch, cache_branch_id, &pl, rep, latent_h, latent_w, ip, cn)) return -1;
                 bytes = std::max(bytes, pl->total_bytes);
             }
@@ -737,6 +752,8 @@ extern "C" int sd_unet_set_context_hw(sd_unet* u, void* stream, const float* ehs
                                       int latent_h, int latent_w, void* workspace, long long workspace_bytes) {
     SD_REQUIRE(u && u->unet_like(), "set_context: not a UNet or ControlNet handle");
     SD_REQUIRE(ehs && workspace, "set_context: null argument");
+    SD_REQUIRE(u->tg_mode != TGATE_REUSE, "set_context: the handle is in T-GATE reuse mode, whose plans read no prompt context "
+                                         "(sd_unet_set_tgate_hw: mode 0 or 1 first)");
     if (check_latent_size(u, latent_h, latent_w, "set_context")) return -1;
     Plan* plp;
     int rc = get_plan(u, unet_batch, cache_branch_id, &plp, 1, latent_h, latent_w);
@@ -1043,6 +1060,29 @@ static int check_control_set(const sd_unet* u, const char* who, int unet_batch, 
     return 0;
 }
 
+// a forward of a handle in a T-GATE mode must be the one its cache is laid out for; reuse needs a capture before it
+// (batch 2 b of a capture = the CFG pair [uncond | cond] of b latents, whether the caller passes b latents or all 2 b rows)
+static int check_tgate_forward(const sd_unet* u, const char* who, int latent_batch, int unet_batch, int latent_h, int latent_w,
+                               int cache_mode, int branch, int ip, int cn) {
+    SD_REQUIRE(cache_mode == SD_CACHE_OFF && branch < 0, "%s: T-GATE with DeepCache is not built (the cached features are stored at the CFG batch)", who);
+    SD_REQUIRE(!ip && !cn, "%s: T-GATE with an IP-Adapter image prompt or ControlNet residuals is not built", who);
+    SD_REQUIRE(u->tg_h == latent_h && u->tg_w == latent_w,
+               "%s: the T-GATE cache was set for %d latents at %dx%d, the forward runs at %dx%d (sd_unet_set_tgate_hw)", who,
+               u->tg_b, u->tg_h, u->tg_w, latent_h, latent_w);
+    SD_REQUIRE(latent_batch > 0 && unet_batch % latent_batch == 0, "%s: unet batch %d not a multiple of latent batch %d (T-GATE cache set "
+               "for %d latents)", who, unet_batch, latent_batch, u->tg_b);
+    if (u->tg_mode == TGATE_REUSE) {
+        SD_REQUIRE(u->tg_captured, "%s: T-GATE reuse before any capture: the cache holds nothing for %d latents at %dx%d (run one forward "
+                   "in capture mode first)", who, u->tg_b, u->tg_h, u->tg_w);
+        SD_REQUIRE(unet_batch == u->tg_b, "%s: a T-GATE reuse forward runs at the batch of the capture's latents (%d), not %d: there is no "
+                   "classifier-free guidance behind the gate", who, u->tg_b, unet_batch);
+    } else {
+        SD_REQUIRE(unet_batch == u->tg_b || unet_batch == 2 * u->tg_b, "%s: a T-GATE capture forward runs at the latent batch or twice it "
+                   "(%d latents, UNet batch %d)", who, u->tg_b, unet_batch);
+    }
+    return 0;
+}
+
 // the handle's dst-choice array for the plan about to run: n bytes, zero (position 0 of every cell) unless set for this size
 static int ensure_tome_choice(sd_unet* u, long n, void* stream) {
     if (n <= 0 || (u->tome_choice && u->tome_choice_n == n)) return 0;
@@ -1081,12 +1121,15 @@ extern "C" int sd_unet_forward_hw(sd_unet* u, void* stream, const float* latents
     if (ip && check_ip_set(u, "forward", unet_batch, cache_branch_id, latent_h, latent_w)) return -1;
     const int cn = u->ctrl_res ? 1 : 0;
     if (cn && check_control_set(u, "forward", unet_batch, latent_h, latent_w, cache_mode, cache_branch_id)) return -1;
+    if (u->tg_mode && check_tgate_forward(u, "forward", latent_batch, unet_batch, latent_h, latent_w, cache_mode, cache_branch_id, ip, cn)) return -1;
     u->last_rep = rep; u->last_ip = ip; u->last_cn = cn;
     u->last_h = latent_h; u->last_w = latent_w;
     int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, latent_h, latent_w, ip, cn);
     if (rc) return rc;
     if ((rc = ensure_tome_choice(u, pl->tome_choice_bytes, stream))) return rc;
-    return run_plan(u, *pl, "forward", workspace, workspace_bytes, latents, latent_batch, eps_out, timestep, stream, cache_mode);
+    rc = run_plan(u, *pl, "forward", workspace, workspace_bytes, latents, latent_batch, eps_out, timestep, stream, cache_mode);
+    if (u->tg_mode == TGATE_CAPTURE) u->tg_captured = rc == 0;
+    return rc;
 }
 
 // ---- FreeU (freeu.hip; the plan side is the up loop of Builder::build) ----------------------------------------------------
@@ -1104,6 +1147,66 @@ extern "C" int sd_unet_set_freeu(sd_unet* u, float s1, float s2, float b1, float
 extern "C" int sd_unet_disable_freeu(sd_unet* u) {
     SD_REQUIRE(u && u->kind == 0, "disable_freeu: not a UNet handle");
     u->freeu_on = false;
+    return 0;
+}
+
+// ---- T-GATE (tgate.hip; the plan side is Builder::transformer) ------------------------------------------------------------
+static int check_tgate_handle(const sd_unet* u, const char* who) {
+    SD_REQUIRE(u && u->kind == 0, "%s: not a UNet handle", who);
+    SD_REQUIRE(!u->fp8, "%s: T-GATE is refused on fp8 handles (the calibrated activation scales do not describe the gated tensors)", who);
+    SD_REQUIRE(u->cfg.in_channels == 4, "%s: T-GATE is refused on a 9-channel inpainting UNet", who);
+    SD_REQUIRE(u->cfg.ip_adapter_tokens == 0, "%s: T-GATE is refused on a UNet with an IP-Adapter (its image branch is not cached)", who);
+    return 0;
+}
+
+extern "C" long long sd_unet_tgate_bytes_hw(sd_unet* u, int latent_batch, int latent_h, int latent_w) {
+    if (check_tgate_handle(u, "tgate_bytes")) return -1;
+    SD_REQUIRE(latent_batch > 0 && latent_batch <= 4096, "tgate_bytes: bad batch %d", latent_batch);
+    if (check_latent_size(u, latent_h, latent_w, "tgate_bytes")) return -1;
+    std::vector<size_t> off; std::vector<long> rows; std::vector<int> ch;
+    return (long long)tgate_segments(u->cfg, latent_batch, latent_h, latent_w, &off, &rows, &ch);
+}
+
+extern "C" int sd_unet_tgate_block_info_hw(sd_unet* u, int block, int latent_batch, int latent_h, int latent_w, long long* offset,
+                                           long long* rows, int* channels) {
+    if (check_tgate_handle(u, "tgate_block_info")) return -1;
+    SD_REQUIRE(latent_batch > 0 && latent_batch <= 4096, "tgate_block_info: bad batch %d", latent_batch);
+    if (check_latent_size(u, latent_h, latent_w, "tgate_block_info")) return -1;
+    std::vector<size_t> off; std::vector<long> r; std::vector<int> ch;
+    tgate_segments(u->cfg, latent_batch, latent_h, latent_w, &off, &r, &ch);
+    if (block < 0) return (int)off.size();          // (the block count)
+    SD_REQUIRE(block < (int)off.size(), "tgate_block_info: block %d of %zu", block, off.size());
+    if (offset) *offset = (long long)off[block];
+    if (rows) *rows = r[block];
+    if (channels) *channels = ch[block];
+    return (int)off.size();
+}
+
+extern "C" int sd_unet_set_tgate_hw(sd_unet* u, int mode, void* cache, long long bytes, int latent_batch, int latent_h, int latent_w) {
+    SD_REQUIRE(u && u->kind == 0, "set_tgate: not a UNet handle");
+    if (mode == TGATE_OFF) {
+        SD_REQUIRE(!cache, "set_tgate: mode 0 takes cache = NULL (it clears the setting)");
+        u->tg_mode = TGATE_OFF; u->tg_cache = nullptr; u->tg_bytes = 0; u->tg_b = u->tg_h = u->tg_w = 0; u->tg_captured = false;
+        return 0;
+    }
+    SD_REQUIRE(mode == TGATE_CAPTURE || mode == TGATE_REUSE, "set_tgate: mode %d (0 = off, 1 = capture, 2 = reuse)", mode);
+    if (check_tgate_handle(u, "set_tgate")) return -1;
+    SD_REQUIRE(!u->ctrl_res && u->ip_keys.empty(), "set_tgate: T-GATE with ControlNet residuals or an IP-Adapter image prompt set is not built");
+    SD_REQUIRE(cache && ((uintptr_t)cache & 255) == 0, "set_tgate: the cache buffer must be a 256-byte aligned device pointer");
+    const long long need = sd_unet_tgate_bytes_hw(u, latent_batch, latent_h, latent_w);
+    if (need < 0) return -1;
+    SD_REQUIRE(bytes >= need, "set_tgate: the cache buffer holds %lld bytes, %d latents at %dx%d need %lld (sd_unet_tgate_bytes_hw)", bytes,
+               latent_batch, latent_h, latent_w, need);
+    // what a capture wrote stays valid only for the same buffer and layout
+    const bool captured = u->tg_captured && (char*)cache == u->tg_cache && latent_batch == u->tg_b && latent_h == u->tg_h && latent_w == u->tg_w;
+    if (mode == TGATE_REUSE) {
+        SD_REQUIRE(u->tg_captured, "set_tgate: reuse before any capture (set mode 1 and run one forward first)");
+        SD_REQUIRE(captured, "set_tgate: reuse for %d latents at %dx%d, but the capture filled its buffer for %d latents at %dx%d", latent_batch,
+                   latent_h, latent_w, u->tg_b, u->tg_h, u->tg_w);
+    }
+    u->tg_captured = captured;
+    u->tg_mode = mode; u->tg_cache = (char*)cache; u->tg_bytes = bytes;
+    u->tg_b = latent_batch; u->tg_h = latent_h; u->tg_w = latent_w;
     return 0;
 }
 
@@ -1338,6 +1441,12 @@ static void op_work(const Op& o, double* flops, double* bytes) {
         case OP_RES_ADD:    // x and r in, x out
             *bytes = 3.0 * 2.0 * (double)o.M;      // (M: the elements of all segments)
             break;
+        case OP_TGATE_CAPTURE:      // y and res in, h2 and one cache row per `pair` rows out
+            *bytes = 2.0 * (double)o.M * o.N * (3.0 + 1.0 / o.K);
+            break;
+        case OP_TGATE_APPLY:        // h1 and the cache in, h2 out
+            *bytes = 3.0 * 2.0 * (double)o.M * o.N;
+            break;
         case OP_IP_XATTN:   // scores and P B over the 32 image-key slots; R in, R' out
             *flops = 4.0 * o.M * 32.0 * o.N;
             *bytes = 2.0 * 2.0 * o.M * o.N;
@@ -1361,6 +1470,8 @@ static int profiled_run(sd_unet* u, void* stream, const float* latents, int late
     if (ip && check_ip_set(u, "forward_profiled", unet_batch, cache_branch_id, u->cfg.sample_size, u->cfg.sample_size)) return -1;
     const int cn = u->ctrl_res ? 1 : 0;
     if (cn && check_control_set(u, "forward_profiled", unet_batch, u->cfg.sample_size, u->cfg.sample_size, cache_mode, cache_branch_id)) return -1;
+    if (u->tg_mode && check_tgate_forward(u, "forward_profiled", latent_batch, unet_batch, u->cfg.sample_size, u->cfg.sample_size, cache_mode,
+                                          cache_branch_id, ip, cn)) return -1;
     u->last_rep = rep; u->last_ip = ip; u->last_cn = cn;
     u->last_h = u->last_w = u->cfg.sample_size;
     int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, -1, -1, ip, cn);
@@ -1387,6 +1498,7 @@ static int profiled_run(sd_unet* u, void* stream, const float* latents, int late
         if (rc) break;
     }
     SD_CHECK_HIP(hipStreamSynchronize(st));
+    if (u->tg_mode == TGATE_CAPTURE) u->tg_captured = rc == 0;
     for (size_t j = 0; j < which.size(); ++j) {
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, ev[j], ev[j + 1]);
@@ -1423,7 +1535,8 @@ extern "C" int sd_unet_forward_profiled(sd_unet* u, void* stream, const float* l
             a.w_batch_stride = (long)o.N * 4 * o.Cin;
             halo4 = sd_conv_halo_subpix_applicable(a);
         }
-        const int kd = o.kind == OP_XATTN ? 18 : o.kind == OP_REPLICATE ? 19 : o.kind == OP_IP_XATTN ? 22 : o.kind == OP_RES_ADD ? 23 : halo4 ? 21 :
+        // (24 / 25 / 26: T-GATE's capture, apply and the capture plan's zero fill -- the op kinds of those numbers never run on a UNet)
+        const int kd = o.kind == OP_TGATE_CAPTURE ? 24 : o.kind == OP_TGATE_APPLY ? 25 : o.kind == OP_TGATE_ZERO ? 26 : o.kind == OP_XATTN ? 18 : o.kind == OP_REPLICATE ? 19 : o.kind == OP_IP_XATTN ? 22 : o.kind == OP_RES_ADD ? 23 : halo4 ? 21 :
                        (o.kind == OP_CONV3 && !o.dt && (o.subpix || o.stride != 1)) ? 20 :
                        (o.dt ? (o.kind == OP_CONV3 ? 16 : 17) : o.kind);
         kind_ms[kd] += ms; kind_launches[kd] += 1; kind_flops[kd] += fl; kind_bytes[kd] += by;

@@ -87,7 +87,20 @@ class BaseMethod(ABC):
         freeu = self.parse_freeu(self.config.model, self.config.model.get("weight_dtype", None) or "bf16")     # key of this build: model.freeu
         if freeu is not None:
             self.model.enable_freeu(**freeu)
+        gate = self.parse_tgate(self.config.model)     # key of this build: model.tgate_step
+        if gate is not None:
+            self.model.enable_tgate(gate)
         self.model.to(self.device)
+
+    @staticmethod
+    def parse_tgate(model_cfg):
+        """``model.tgate_step`` -> the argument of ``enable_tgate`` (T-GATE for any method), or None when the key is absent or
+        null.  Anything but an integer >= 1 is refused by name."""
+        g = model_cfg.get("tgate_step", None)
+        if g is None:
+            return None
+        from ..models import StableDiffusionModel
+        return StableDiffusionModel.check_tgate_step(g)
 
     @staticmethod
     def parse_freeu(model_cfg, weight_dtype="bf16"):

@@ -196,6 +196,8 @@ class StableDiffusionModel:
         self._tome_cells = 0
         self._tome_first = False        # the call's first forward uses the choice array _tome_begin uploaded
         self._freeu = None              # FreeU (enable_freeu): (s1, s2, b1, b2) or None = off
+        self._tgate_step = None         # T-GATE (enable_tgate): the gate step, or None = off
+        self._tgate_reserved = False    # the UNet's workspaces are sized for the capture plans as well
 
     # -- Token Merging (tomesd.apply_patch) ----------------------------------------------------------
     TOME_MAX_RATIO = 0.75
@@ -308,6 +310,66 @@ class StableDiffusionModel:
             self.unet.disable_freeu()
         else:
             self.unet.set_freeu(*self._freeu)
+
+    # -- T-GATE (Zhang et al. 2024) --------------------------------------------------------
+    TGATE_VARIANT_RULE = None       # the variant pipelines set a sentence: they refuse T-GATE by name
+
+    @staticmethod
+    def check_tgate_step(gate_step):
+        """``gate_step`` of ``enable_tgate``: an integer >= 1 (``ValueError`` otherwise)."""
+        if isinstance(gate_step, bool) or not isinstance(gate_step, int) or gate_step < 1:
+            raise ValueError(f"gate_step={gate_step!r}: T-GATE takes an integer gate step >= 1 (steps 0 .. gate_step - 1 run with "
+                             "cross-attention; a gate at or past the last step is the plain pipeline)")
+        return gate_step
+
+    @classmethod
+    def check_tgate_args(cls, gate_step, unet_config=None, weight_dtype="bf16"):
+        """Everything ``enable_tgate`` can refuse from the model alone, by name, without touching the GPU."""
+        gate_step = cls.check_tgate_step(gate_step)
+        if cls.TGATE_VARIANT_RULE is not None:
+            raise NotImplementedError(cls.TGATE_VARIANT_RULE)
+        if unet_config is not None:
+            HipUNet2DConditionModel.check_tgate_support(unet_config, weight_dtype)
+        return gate_step
+
+    def enable_tgate(self, gate_step: int = 10):
+        """T-GATE: every later call computes the prompt cross-attention in its first ``gate_step`` executed steps only.  The
+        last of them also stores, per transformer block, the mean of the CFG pair's two cross-attention outputs; from step
+        ``gate_step`` on the UNet runs on the latents alone -- half the batch under CFG, the stored tensor in place of
+        norm2 and attn2, no classifier-free guidance and no ``guidance_rescale`` in the step.  ``gate_step`` at or past the
+        number of steps that run is the plain pipeline.  Valid with text-to-image, image-to-image (the steps that run count)
+        and 4-channel inpainting, every scheduler, LCM-distilled UNets, SD 2.x, Token Merging, FreeU and TAESD; refused by
+        name with DeepCache, ControlNet, IP-Adapter, fp8 and 9-channel inpainting UNets and on the variant pipelines."""
+        self._tgate_step = self.check_tgate_args(gate_step, self.unet_config, self.weight_dtype)
+        return self
+
+    def disable_tgate(self):
+        """Later calls are those of a model that never saw T-GATE, bit for bit."""
+        self._tgate_step = None
+        return self
+
+    def _tgate_check_call(self, control=None, ip_adapter_image=None, ip_adapter_image_embeds=None):
+        """What a call with T-GATE on refuses, by name, before any GPU work."""
+        if self._tgate_step is None:
+            return
+        self.check_tgate_args(self._tgate_step, self.unet_config, self.weight_dtype)
+        if self._deepcache is not None:
+            raise NotImplementedError("T-GATE with DeepCache is refused: DeepCache's cached features are stored at the CFG batch "
+                                      "(gating at a multiple of cache_interval is not built)")
+        if control is not None or getattr(self, "_cn_cfg", None) is not None:
+            raise NotImplementedError("T-GATE with ControlNet is refused: the residuals are computed for the CFG batch")
+        if ip_adapter_image is not None or ip_adapter_image_embeds is not None or self._ip_loaded:
+            raise NotImplementedError("T-GATE with an IP-Adapter is refused: the image branch of the cross-attention is not cached")
+
+    def _tgate_begin(self, latent_batch):
+        """Start of a sampling loop: the UNet's workspace covers the capture plans while T-GATE is on.  A model that never
+        enabled it asks nothing of the handle."""
+        if self._tgate_step is not None:
+            self.unet.reserve_tgate(latent_batch, *self.latent_size)
+            self._tgate_reserved = True
+        elif self._tgate_reserved:
+            self.unet.reserve_tgate(None)
+            self._tgate_reserved = False
 
     # -- loading ---------------------------------------------------------------------------
     @classmethod
@@ -1001,6 +1063,7 @@ class StableDiffusionModel:
         latents = self.prepare_latents(batch_size, LATENT_CHANNELS, self._size[0], self._size[1], device, generator, latents)
         self._tome_begin()              # (before the context: the setting is part of the UNet's plans)
         self._freeu_begin()             # (likewise)
+        self._tgate_begin(batch_size)   # (before the context: the workspace that holds it)
         self.unet.set_deepcache(cache_branch_id)
         self.unet.set_context(ctx, *self.latent_size)
         self._apply_ip_adapter(ctx.shape[0] == 2 * batch_size and self.do_classifier_free_guidance)
@@ -1025,29 +1088,45 @@ class StableDiffusionModel:
         eps = self._eps_buffer(unet_batch, device)
         ts = [s[0] for s in steps]
         n = len(steps)
+        # T-GATE: steps 0 .. g - 1 as ever (step g - 1 also captures), steps g .. n - 1 gated: the UNet at the latent batch,
+        # no CFG in the step, the model output in the first rows of the eps buffer.  g = None: off, or a gate the run never reaches.
+        g = self._tgate_step if self._tgate_step is not None and self._tgate_step < n else None
+        lb = latents.shape[0]
         x0_preds = []
         torch.cuda.synchronize(device)
         start_time = time.time()                                                                   # :208
-        for i, (t, sched, hand_off) in enumerate(steps):                                           # :211
-            mode = CACHE_OFF
-            if deepcache is not None:
-                mode = CACHE_FULL_AND_STORE if ts.index(t) % deepcache.cache_interval == 0 else CACHE_SKIP     # (A.5)
-            self._control_step(i, n, latents, unet_batch, t)
-            self._tome_step()
-            self.unet.forward_latents(latents, unet_batch, float(t), out=eps, cache_mode=mode)     # :217-235
-            kw = {}
-            if step_noise is not None and i < n - 1 and "timestep_scaling" in getattr(sched, "config", ()):    # (LCM)
-                kw["noise"] = step_noise[i]             # indexed by EXECUTED step
-            if do_cfg and guidance_rescale > 0.0:                                                  # :244-250
-                kw["guidance_rescale"] = guidance_rescale
-            if inpaint is not None:
-                kw["inpaint"] = (*inpaint, ts[i + 1] if i + 1 < n else None)
-            step = sched.step_fused(eps, guidance_scale, latents, t, cfg=do_cfg, eta=eta, generator=generator, **kw)   # :238-261
-            latents = step[0]
-            if collect_x0 and len(step) > 1:            # (PNDM returns no x0, :257-261)
-                x0_preds.append(step[1][0:1])
-            if hand_off is not None:                    # :603-611, :1025-1033, :1045-1053
-                _push_history(hand_off, _combined(eps, do_cfg, guidance_scale, sched), latents)
+        try:
+            for i, (t, sched, hand_off) in enumerate(steps):                                       # :211
+                ub, cfg, out = unet_batch, do_cfg, eps
+                if g is not None:
+                    if i == g - 1:
+                        self.unet.set_tgate(self.unet.TGATE_CAPTURE, lb, *self.latent_size)
+                    elif i == g:
+                        self.unet.set_tgate(self.unet.TGATE_REUSE, lb, *self.latent_size)
+                    if i >= g:
+                        ub, cfg, out = lb, False, eps[:lb]
+                mode = CACHE_OFF
+                if deepcache is not None:
+                    mode = CACHE_FULL_AND_STORE if ts.index(t) % deepcache.cache_interval == 0 else CACHE_SKIP     # (A.5)
+                self._control_step(i, n, latents, ub, t)
+                self._tome_step()
+                self.unet.forward_latents(latents, ub, float(t), out=out, cache_mode=mode)         # :217-235
+                kw = {}
+                if step_noise is not None and i < n - 1 and "timestep_scaling" in getattr(sched, "config", ()):    # (LCM)
+                    kw["noise"] = step_noise[i]             # indexed by EXECUTED step
+                if cfg and guidance_rescale > 0.0:                                                 # :244-250
+                    kw["guidance_rescale"] = guidance_rescale
+                if inpaint is not None:
+                    kw["inpaint"] = (*inpaint, ts[i + 1] if i + 1 < n else None)
+                step = sched.step_fused(out, guidance_scale, latents, t, cfg=cfg, eta=eta, generator=generator, **kw)   # :238-261
+                latents = step[0]
+                if collect_x0 and len(step) > 1:            # (PNDM returns no x0, :257-261)
+                    x0_preds.append(step[1][0:1])
+                if hand_off is not None:                    # :603-611, :1025-1033, :1045-1053
+                    _push_history(hand_off, _combined(out, cfg, guidance_scale, sched), latents)
+        finally:
+            if g is not None:
+                self.unet.set_tgate(self.unet.TGATE_OFF)
         self._control_end()
         torch.cuda.synchronize(device)
         return latents, x0_preds, time.time() - start_time                                        # :284-285
@@ -1347,6 +1426,7 @@ class StableDiffusionModel:
                                       "without it upstream composites nothing in pixel space, and neither does this)")
         # (neither a prompt nor embeds: _begin refuses the call by name)
         n_prompt = None if prompt is None and prompt_embeds is None else _prompt_batch(prompt, prompt_embeds)
+        self._tgate_check_call(control_image, ip_adapter_image, ip_adapter_image_embeds)
         control = self._control_args(control_image, controlnet_conditioning_scale, control_guidance_start,
                                      control_guidance_end, guess_mode, mask_image, n_prompt)
         a = SimpleNamespace(height=height, width=width, num_inference_steps=num_inference_steps, timesteps=timesteps,
@@ -1407,6 +1487,8 @@ def _combined(eps, do_cfg, guidance_scale, sched=None):
 
 class _VariantBase(StableDiffusionModel):
     """The variants run ``_sample`` over their own list of steps, without DeepCache, and refuse the image arguments."""
+    TGATE_VARIANT_RULE = ("T-GATE is refused on the variant pipelines (two schedulers, interleaving, skipped steps): their step "
+                          "lists are not one schedule to place a gate in; StableDiffusionModel runs it")
 
     def _refuse_image(self, kwargs):
         if kwargs.get("control_image") is not None or kwargs.get("guess_mode"):

@@ -96,6 +96,12 @@ class HipUNet2DConditionModel:
         self._tome = None                   # (ratio, max_downsample) of the Token Merging setting on the handle, None = off
         self._tome_choice_keepalive = None
         self._freeu = None                  # (s1, s2, b1, b2) on the handle, None = off
+        # T-GATE: _tgate = (mode, latent batch, h, w) on the handle or None = off; _tgate_cache = the buffer the handle borrows;
+        # _tgate_ws = workspaces of the gated (reuse) plans by (batch, h, w): the main workspace keeps the prompt context
+        self._tgate = None
+        self._tgate_cache = None
+        self._tgate_ws = {}
+        self._tgate_reserve = None          # (latent batch, h, w): _workspace also covers the capture plans of that layout
         self.cache_branch_id = -1
 
     def __del__(self):
@@ -119,6 +125,8 @@ class HipUNet2DConditionModel:
             n = self._lib.sd_unet_workspace_bytes_hw(self._handle, unet_batch, self.cache_branch_id, h, w)
             if n < 0:
                 _lib.check(-1, "sd_unet_workspace_bytes_hw")
+            if self._tgate_reserve is not None and self._tgate_reserve[1:] == (h, w) and self._tgate is None:
+                n = max(n, self._tgate_capture_bytes(unet_batch, *self._tgate_reserve))
             self._drop_ip_keys()            # (the folded image operands lived in the old workspace, like the context)
             self._ws = None
             self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
@@ -268,7 +276,7 @@ class HipUNet2DConditionModel:
         """The handle sizes the control plan variants only once residuals were set on it: if the live workspace is smaller
         than they need, move it into a larger one.  The context tensors (prompt, image prompt) lie at the same offsets in
         every variant, at the front of the workspace, so the copy keeps them."""
-        if self._ws is None:
+        if self._ws is None or self._ws_key is None:    # (no key: the next _workspace sizes a new one anyway)
             return
         ub, branch, h, w = self._ws_key
         n = self._lib.sd_unet_workspace_bytes_hw(self._handle, ub, branch, h, w)
@@ -385,6 +393,112 @@ class HipUNet2DConditionModel:
             self._ws_key = None
         self._freeu = None
 
+    # -- T-GATE (include/sd_hip.h::sd_unet_set_tgate_hw) -----------------------------------------------
+    TGATE_OFF, TGATE_CAPTURE, TGATE_REUSE = 0, 1, 2
+
+    @staticmethod
+    def check_tgate_support(config, weight_dtype="bf16"):
+        """What T-GATE refuses on the UNet's side, by name, without touching the GPU."""
+        if _lib.DTYPES.get(weight_dtype) == _lib.DTYPE_FP8_E4M3 or weight_dtype == "fp8_e4m3":
+            raise NotImplementedError("T-GATE on an fp8 UNet handle is refused (weight_dtype='fp8'): the calibrated activation "
+                                      "scales do not describe the gated tensors")
+        if config.in_channels == 9:
+            raise NotImplementedError("T-GATE on a 9-channel inpainting UNet is refused (in_channels = 9)")
+        if getattr(config, "ip_adapter_embed_dim", None) is not None:
+            raise NotImplementedError("T-GATE with an IP-Adapter is refused: the image branch of the cross-attention is not cached")
+
+    def tgate_blocks(self, latent_batch: int, height: Optional[int] = None, width: Optional[int] = None):
+        """The cache slices of ``latent_batch`` latents, one per transformer block in plan order (down, mid, up): dicts of
+        ``offset`` (bytes into the cache buffer), ``rows`` (= latent_batch * tokens) and ``channels``."""
+        lh, lw = self.latent_size(height, width)
+        n = self._lib.sd_unet_tgate_block_info_hw(self._handle, -1, latent_batch, lh, lw, None, None, None)
+        if n < 0:
+            _lib.check(-1, "sd_unet_tgate_block_info_hw")
+        out = []
+        for i in range(n):
+            off, rows, ch = C.c_longlong(), C.c_longlong(), C.c_int()
+            if self._lib.sd_unet_tgate_block_info_hw(self._handle, i, latent_batch, lh, lw, C.byref(off), C.byref(rows), C.byref(ch)) < 0:
+                _lib.check(-1, "sd_unet_tgate_block_info_hw")
+            out.append(dict(offset=off.value, rows=rows.value, channels=ch.value))
+        return out
+
+    def tgate_cache(self, latent_batch: int, height: Optional[int] = None, width: Optional[int] = None) -> torch.Tensor:
+        """The cache buffer for ``latent_batch`` latents at this size (uint8, 256-byte aligned; kept and reused while it fits)."""
+        lh, lw = self.latent_size(height, width)
+        n = self._lib.sd_unet_tgate_bytes_hw(self._handle, latent_batch, lh, lw)
+        if n < 0:
+            _lib.check(-1, "sd_unet_tgate_bytes_hw")
+        if self._tgate_cache is None or self._tgate_cache.numel() < n + 256:
+            self._tgate_cache = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+        return self._tgate_cache
+
+    def tgate_cache_block(self, block: int, latent_batch: int, height: Optional[int] = None, width: Optional[int] = None) -> torch.Tensor:
+        """Slice ``block`` of the cache as a bf16 tensor [rows, channels] (a view of the buffer)."""
+        info = self.tgate_blocks(latent_batch, height, width)[block]
+        buf = self._tgate_cache
+        off = (-buf.data_ptr()) % 256 + info["offset"]
+        return buf[off:off + info["rows"] * info["channels"] * 2].view(torch.bfloat16).view(info["rows"], info["channels"])
+
+    def _tgate_capture_bytes(self, unet_batch: int, latent_batch: int, h: int, w: int) -> int:
+        """Workspace bytes of the capture plans of ``unet_batch`` (the handle is left off)."""
+        buf = self.tgate_cache(latent_batch, h, w)
+        p = self._ws_ptr(buf)
+        _lib.check(self._lib.sd_unet_set_tgate_hw(self._handle, self.TGATE_CAPTURE, p, buf.numel() - 256, latent_batch, h, w),
+                   "sd_unet_set_tgate_hw")
+        try:
+            n = self._lib.sd_unet_workspace_bytes_hw(self._handle, unet_batch, self.cache_branch_id, h, w)
+            if n < 0:
+                _lib.check(-1, "sd_unet_workspace_bytes_hw")
+        finally:
+            _lib.check(self._lib.sd_unet_set_tgate_hw(self._handle, self.TGATE_OFF, None, 0, 0, 0, 0), "sd_unet_set_tgate_hw")
+        return n
+
+    def reserve_tgate(self, latent_batch: Optional[int], height: Optional[int] = None, width: Optional[int] = None) -> None:
+        """Before ``set_context``: size the next workspace for the capture plans of ``latent_batch`` latents at this size as well,
+        so that ``set_tgate(TGATE_CAPTURE, ...)`` in the middle of a run keeps the workspace and the prompt context in it.
+        ``None``: the workspaces are again those of a UNet that never saw T-GATE."""
+        new = None if latent_batch is None else (int(latent_batch), *self.latent_size(height, width))
+        if new != self._tgate_reserve:
+            self._tgate_reserve = new
+            self._ws_key = None
+            if new is None:
+                self._tgate_ws = {}
+                self._tgate_cache = None
+
+    def set_tgate(self, mode: int, latent_batch: int = 0, height: Optional[int] = None, width: Optional[int] = None) -> None:
+        """T-GATE state of the handle.  ``TGATE_CAPTURE``: the next forward (UNet batch ``latent_batch``, or twice it for a CFG
+        pair) also fills the cache: per transformer block the mean of the pair's cross-attention outputs.  ``TGATE_REUSE``:
+        forwards run at UNet batch ``latent_batch`` on the latents alone, with the cached tensor in place of norm2 and attn2;
+        they need no ``set_context``.  ``TGATE_OFF``: forwards are again those of a UNet that never saw it, bit for bit."""
+        if mode == self.TGATE_OFF:
+            _lib.check(self._lib.sd_unet_set_tgate_hw(self._handle, 0, None, 0, 0, 0, 0), "sd_unet_set_tgate_hw")
+            self._tgate = None
+            self._grow_workspace_for_control()      # (a workspace sized while capturing: the plain plans must fit it too)
+            return
+        self.check_tgate_support(self.config, self.weight_dtype)
+        if self.cache_branch_id != -1:
+            raise NotImplementedError("T-GATE with DeepCache is refused: the cached features are stored at the CFG batch")
+        if self._control is not None or self._ip_on:
+            raise NotImplementedError("T-GATE with ControlNet residuals or an IP-Adapter image prompt set is refused")
+        h, w = self.latent_size(height, width)
+        buf = self.tgate_cache(latent_batch, h, w)
+        _lib.check(self._lib.sd_unet_set_tgate_hw(self._handle, int(mode), self._ws_ptr(buf), buf.numel() - 256, int(latent_batch), h, w),
+                   "sd_unet_set_tgate_hw")
+        self._tgate = (int(mode), int(latent_batch), h, w)
+        if mode == self.TGATE_CAPTURE and self._ws is not None and self._ws_key is not None and self._ws_key[2:] == (h, w):
+            self._grow_workspace_for_control()      # (a workspace sized before the capture plans were asked for: keep its context)
+
+    def _tgate_workspace(self, unet_batch: int, h: int, w: int) -> torch.Tensor:
+        key = (unet_batch, h, w)
+        ws = self._tgate_ws.get(key)
+        if ws is None:
+            n = self._lib.sd_unet_workspace_bytes_hw(self._handle, unet_batch, -1, h, w)
+            if n < 0:
+                _lib.check(-1, "sd_unet_workspace_bytes_hw")
+            self._tgate_ws = {key: torch.empty(n + 256, dtype=torch.uint8, device=self.device)}
+            ws = self._tgate_ws[key]
+        return ws
+
     def plan_count(self) -> int:
         """Execution plans the handle has built so far."""
         return int(self._lib.sd_unet_plan_count(self._handle))
@@ -402,7 +516,8 @@ class HipUNet2DConditionModel:
                                              or unet_batch % self._inpaint_key[0]):
             raise _lib.SdHipError(f"this UNet has in_channels = 9: set_inpaint_cond(mask, masked_latents) must be called for "
                                   f"this batch and size ({h}x{w}) first")
-        if self._ctx_key is None or self._ctx_key[2:] != (unet_batch, h, w):
+        gated = self._tgate is not None and self._tgate[0] == self.TGATE_REUSE      # (no prompt context behind the gate)
+        if not gated and (self._ctx_key is None or self._ctx_key[2:] != (unet_batch, h, w)):
             raise _lib.SdHipError(f"set_context(encoder_hidden_states, {h}, {w}) must be called for this batch and size first")
         if self._ip_on and (unet_batch, self.cache_branch_id, h, w) not in self._ip_keys:
             raise _lib.SdHipError(f"this UNet runs with an IP-Adapter image prompt: set_ip_adapter(image_embeds, scale, {h}, {w}) must "
@@ -414,7 +529,7 @@ class HipUNet2DConditionModel:
             latents = latents.to(self.device, torch.float32).contiguous()
         if out is None:
             out = torch.empty((unet_batch, self.config.out_channels, h, w), dtype=torch.float32, device=self.device)
-        ws = self._workspace(unet_batch, h, w)
+        ws = self._tgate_workspace(unet_batch, h, w) if gated else self._workspace(unet_batch, h, w)
         _lib.check(self._lib.sd_unet_forward_hw(self._handle, _lib.current_stream(), latents.data_ptr(), b, unet_batch, h, w,
                                                 float(timestep), out.data_ptr(), self._ws_ptr(ws), ws.numel() - 256,
                                                 cache_mode, self.cache_branch_id), "sd_unet_forward_hw")
@@ -466,6 +581,7 @@ class HipUNet2DConditionModel:
     KIND_NAMES = {0: "sinusoid", 1: "gemv", 2: "conv_in", 3: "groupnorm", 4: "conv3x3", 5: "gemm", 6: "layernorm",
                   7: "attention", 8: "conv_out", 16: "conv3x3_fp8", 17: "gemm_fp8", 18: "xattn_fused",
                   19: "replicate", 20: "conv3x3_gemm", 21: "conv3x3_halo_subpix", 22: "ip_xattn", 23: "residual_add",
+                  24: "tgate_capture", 25: "tgate_apply", 26: "tgate_zero",
                   27: "tome_match", 28: "tome_select", 29: "tome_merge", 30: "tome_unmerge", 31: "freeu"}
 
     def forward_profiled(self, latents: torch.Tensor, unet_batch: int, timestep: float, cache_mode: int = CACHE_OFF):
@@ -477,7 +593,8 @@ class HipUNet2DConditionModel:
             raise ValueError(f"forward_profiled: {s}x{s} latents only, got {tuple(latents.shape)}")
         out = torch.empty((unet_batch, self.config.out_channels, latents.shape[2], latents.shape[3]),
                           dtype=torch.float32, device=self.device)
-        ws = self._workspace(unet_batch)
+        gated = self._tgate is not None and self._tgate[0] == self.TGATE_REUSE
+        ws = self._tgate_workspace(unet_batch, s, s) if gated else self._workspace(unet_batch)
         ms, fl, by = (C.c_double * 32)(), (C.c_double * 32)(), (C.c_double * 32)()
         ln = (C.c_longlong * 32)()
         _lib.check(self._lib.sd_unet_forward_profiled(
