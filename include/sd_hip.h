@@ -568,6 +568,30 @@ int sd_sched_step_inpaint(void* stream, const float* eps, int cfg, float guidanc
                           const float* m2, const float* m3, const float* noise, float* prev, float* y2, float* m_out,
                           const float coef[10], long long n, const float* k, long long n_per_sample, const float* init,
                           const float* blend_noise, const float* mask, float a, float s, long long hw);
+
+/* ---- UniPC (Zhao et al. 2023; diffusers' UniPCMultistepScheduler): corrector + predictor of one step in ONE launch ----
+ * Per element, with coef = [cm0 cm1 | cy0 cy1 | cc0 cc1 cc2 cc3 cc4 | cp0 cp1 cp2 cp3]:
+ *   e     = cfg ? u + guidance*(c - u) : eps[0:n]      formed exactly as sd_sched_step forms it
+ *   e     = k[b] * e                                   only when k != NULL (b = i / n_per_sample; as sd_sched_step_rescaled)
+ *   m_t   = cm[0]*x + cm[1]*e                          history entry (x0 when predict_x0, else eps)
+ *   y2    = cy[0]*x + cy[1]*e                          x0 prediction, optional output
+ *   xc    = cc[0]*x_last + cc[1]*h1 + cc[2]*h2 + cc[3]*h3 + cc[4]*m_t     corrector
+ *           (x_last == NULL: no corrector, xc = x bit for bit; nothing of cc is read)
+ *   prev  = cp[0]*xc + cp[1]*m_t + cp[2]*h1 + cp[3]*h2                    predictor
+ *   prev  = mask ? prev : a*init + s*blend_noise       only when init != NULL; same rule, operands and argument checks
+ *                                                      as sd_sched_step_inpaint
+ *   outputs: prev, x_corr (= xc, optional), y2 (optional), m_out (= m_t, optional)
+ * h1, h2, h3: the history entries BEFORE this step's shift, newest first; the corrector of order o reads h1..h_o and m_t, the
+ * predictor of order o reads m_t and h1..h_(o-1).  Sums run left to right in fp32; a NULL history entry is skipped and must
+ * have zero coefficients (refused otherwise).  Refused before any launch: null eps / x / prev / coef; n not a positive multiple
+ * of 4; n_per_sample not a positive multiple of 4 dividing n; with init: a null mask, s != 0 without blend_noise, hw not a
+ * positive multiple of 4 dividing n_per_sample; a coefficient (or guidance, a, s) that is not finite; an output that overlaps
+ * an input or another output (named in the message).  x_corr, y2 and m_out do not see the mask. */
+int sd_sched_step_pc(void* stream, const float* eps, int cfg, float guidance, const float* x, const float* x_last,
+                     const float* h1, const float* h2, const float* h3, float* prev, float* x_corr, float* y2, float* m_out,
+                     const float coef[13], long long n, const float* k, long long n_per_sample, const float* init,
+                     const float* blend_noise, const float* mask, float a, float s, long long hw);
+
 /* One launch: image [batch,3,height,width] fp32 in [0,1] and mask [batch,1,height,width] fp32 ->
  *   masked_image [batch,3,height,width] = mask >= 0.5 ? 0.5 : image   (the encoder's input domain: 2 * 0.5 - 1 is exactly 0,
  *                                                                      upstream's (2 image - 1) * (mask < 0.5))

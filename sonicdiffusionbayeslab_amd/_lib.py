@@ -163,6 +163,8 @@ _SIGS = {
     "sd_sched_step_rescaled": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _ll, _vp, _ll]),
     "sd_sched_step_inpaint": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _ll, _vp, _ll,
                                    _vp, _vp, _vp, _f, _f, _ll]),
+    "sd_sched_step_pc": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _ll, _vp, _ll,
+                              _vp, _vp, _vp, _f, _f, _ll]),
     "sd_inpaint_prepare": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
     "sd_unet_set_inpaint_cond_hw": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
     "sd_unet_set_ip_adapter_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _ll]),

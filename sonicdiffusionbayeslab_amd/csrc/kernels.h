@@ -379,6 +379,18 @@ int sd_launch_sched_step_inpaint(const float* eps, int cfg, float guidance, cons
                                  const float* m2, const float* m3, const float* noise, float* prev, float* y2,
                                  float* m_out, StepCoef c, const float* k, long n_per_sample, long n, const float* init,
                                  const float* blend_noise, const float* mask, float a, float s, long hw, hipStream_t stream);
+// UniPC's predictor-corrector step (include/sd_hip.h::sd_sched_step_pc): corrector, predictor, history entry, x0 and the
+// optional rescale / latent blend in one launch
+struct PcCoef {
+    float cm[2];  // m_t  = cm0*x + cm1*e
+    float cy[2];  // y2   = cy0*x + cy1*e
+    float cc[5];  // xc   = cc0*x_last + cc1*h1 + cc2*h2 + cc3*h3 + cc4*m_t
+    float cp[4];  // prev = cp0*xc + cp1*m_t + cp2*h1 + cp3*h2
+};
+int sd_launch_sched_step_pc(const float* eps, int cfg, float guidance, const float* x, const float* x_last, const float* h1,
+                            const float* h2, const float* h3, float* prev, float* x_corr, float* y2, float* m_out, PcCoef c,
+                            const float* k, long n_per_sample, long n, const float* init, const float* blend_noise,
+                            const float* mask, float a, float s, long hw, hipStream_t stream);
 
 // inception.hip: FID Inception-v3 pieces (general implicit-GEMM conv, 3x3 pools, global mean, TF1 bilinear preprocessing)
 int sd_launch_inception_conv(const bf16_t* x, const bf16_t* w, const float* bias, bf16_t* y, int B, int Hin, int Win, int Cin,

@@ -557,6 +557,62 @@ __global__ void sched_step_inpaint_kernel(const float* __restrict__ eps, int cfg
     ((f32x4*)prev)[i] = p;
 }
 
+// ---- UniPC: corrector and predictor of one step in one launch -----------------------------------------------------------
+// e as the kernels above form it (RESCALED: cfg_combine, then k[b]; else sched_step_kernel's expression), then
+//   m_t  = cm0 x + cm1 e                                        (history entry)
+//   y2   = cy0 x + cy1 e                                        (x0 prediction)
+//   xc   = cc0 x_last + cc1 h1 + cc2 h2 + cc3 h3 + cc4 m_t      (corrector; x_last null: xc = x, the bits of x)
+//   prev = cp0 xc + cp1 m_t + cp2 h1 + cp3 h2                   (predictor)
+// and BLEND: sched_step_inpaint_kernel's blend of prev.  Terms are added left to right; a null h term is skipped (the host
+// side has checked that its coefficients are 0).  x_corr, y2 and m_out do not see the mask.
+template <bool RESCALED, bool BLEND>
+__global__ void sched_step_pc_kernel(const float* __restrict__ eps, int cfg, float guidance, const float* __restrict__ x,
+                                     const float* __restrict__ x_last, const float* __restrict__ h1,
+                                     const float* __restrict__ h2, const float* __restrict__ h3, float* __restrict__ prev,
+                                     float* __restrict__ x_corr, float* __restrict__ y2, float* __restrict__ m_out,
+                                     PcCoef c, const float* __restrict__ k, long n4s, long n4,
+                                     const float* __restrict__ init, const float* __restrict__ blend_noise,
+                                     const float* __restrict__ mask, float a, float s, long hw4) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    f32x4 e = ((const f32x4*)eps)[i];
+    if (RESCALED) {
+        if (cfg) e = cfg_combine(e, ((const f32x4*)eps)[i + n4], guidance);
+        e = k[i / n4s] * e;
+    } else if (cfg) {
+        const f32x4 et = ((const f32x4*)eps)[i + n4];
+        e = e + guidance * (et - e);
+    }
+    const f32x4 xv = ((const f32x4*)x)[i];
+    const f32x4 mt = c.cm[0] * xv + c.cm[1] * e;
+    f32x4 v1 = {0.f, 0.f, 0.f, 0.f}, v2 = v1;
+    if (h1) v1 = ((const f32x4*)h1)[i];
+    if (h2) v2 = ((const f32x4*)h2)[i];
+    f32x4 xc = xv;
+    if (x_last) {
+        xc = c.cc[0] * ((const f32x4*)x_last)[i];
+        if (h1) xc += c.cc[1] * v1;
+        if (h2) xc += c.cc[2] * v2;
+        if (h3) xc += c.cc[3] * ((const f32x4*)h3)[i];
+        xc += c.cc[4] * mt;
+    }
+    f32x4 p = c.cp[0] * xc + c.cp[1] * mt;
+    if (h1) p += c.cp[2] * v1;
+    if (h2) p += c.cp[3] * v2;
+    if (x_corr) ((f32x4*)x_corr)[i] = xc;
+    if (y2) ((f32x4*)y2)[i] = c.cy[0] * xv + c.cy[1] * e;
+    if (m_out) ((f32x4*)m_out)[i] = mt;
+    if (BLEND) {
+        const long b = i / n4s;
+        const f32x4 mk = ((const f32x4*)mask)[b * hw4 + (i - b * n4s) % hw4];
+        f32x4 keep = a * ((const f32x4*)init)[i];
+        if (s != 0.f) keep += s * ((const f32x4*)blend_noise)[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[j] = mk[j] >= 0.5f ? p[j] : keep[j];
+    }
+    ((f32x4*)prev)[i] = p;
+}
+
 __global__ void f32_to_bf16_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, long n4) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
@@ -987,6 +1043,68 @@ int sd_launch_sched_step_inpaint(const float* eps, int cfg, float guidance, cons
     else
         hipLaunchKernelGGL(sched_step_inpaint_kernel<false>, grid, dim3(256), 0, stream, eps, cfg, guidance, x, m1, m2, m3, noise,
                            prev, y2, m_out, c, k, n_per_sample / 4, n4, init, blend_noise, mask, a, s, hw / 4);
+    SD_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// [p, p + bytes) and [q, q + bytes_q) share a byte
+static bool pc_overlap(const void* p, size_t bytes, const void* q, size_t bytes_q) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return p && q && a < b + bytes_q && b < a + bytes;
+}
+
+int sd_launch_sched_step_pc(const float* eps, int cfg, float guidance, const float* x, const float* x_last, const float* h1,
+                            const float* h2, const float* h3, float* prev, float* x_corr, float* y2, float* m_out, PcCoef c,
+                            const float* k, long n_per_sample, long n, const float* init, const float* blend_noise,
+                            const float* mask, float a, float s, long hw, hipStream_t stream) {
+    SD_REQUIRE(eps && x && prev, "sched_step_pc: null operand");
+    SD_REQUIRE(n > 0 && n % 4 == 0, "sched_step_pc: n=%ld must be a positive multiple of 4", n);
+    SD_REQUIRE(n_per_sample > 0 && n_per_sample % 4 == 0 && n % n_per_sample == 0,
+               "sched_step_pc: n_per_sample=%ld must be a positive multiple of 4 dividing n=%ld", n_per_sample, n);
+    if (init) {
+        SD_REQUIRE(mask, "sched_step_pc: null operand (mask)");
+        SD_REQUIRE(blend_noise || s == 0.f, "sched_step_pc: s=%g needs blend_noise", (double)s);
+        SD_REQUIRE(hw > 0 && hw % 4 == 0, "sched_step_pc: hw=%ld must be a positive multiple of 4", hw);
+        SD_REQUIRE(n_per_sample % hw == 0, "sched_step_pc: n_per_sample=%ld must be a multiple of hw=%ld", n_per_sample, hw);
+        SD_REQUIRE(std::isfinite(a) && std::isfinite(s), "sched_step_pc: blend coefficients a=%g s=%g must be finite",
+                   (double)a, (double)s);
+    }
+    SD_REQUIRE(std::isfinite(guidance), "sched_step_pc: guidance=%g must be finite", (double)guidance);
+    const float* rows[4] = {c.cm, c.cy, c.cc, c.cp};
+    const char* row_names[4] = {"cm", "cy", "cc", "cp"};
+    const int row_len[4] = {2, 2, 5, 4};
+    for (int r = 0; r < 4; ++r)
+        for (int j = 0; j < row_len[r]; ++j)
+            SD_REQUIRE(std::isfinite(rows[r][j]), "sched_step_pc: coefficient %s[%d]=%g must be finite", row_names[r], j,
+                       (double)rows[r][j]);
+    // a null history entry carries no weight (the corrector's row is not read without x_last)
+    SD_REQUIRE(h1 || (c.cp[2] == 0.f && (!x_last || c.cc[1] == 0.f)), "sched_step_pc: h1 is null but has a coefficient");
+    SD_REQUIRE(h2 || (c.cp[3] == 0.f && (!x_last || c.cc[2] == 0.f)), "sched_step_pc: h2 is null but has a coefficient");
+    SD_REQUIRE(h3 || !x_last || c.cc[3] == 0.f, "sched_step_pc: h3 is null but has a coefficient");
+    const size_t nb = (size_t)n * 4, batch = (size_t)(n / n_per_sample);
+    const void* outs[4] = {prev, x_corr, y2, m_out};
+    const char* out_names[4] = {"prev", "x_corr", "y2", "m_out"};
+    const void* ins[10] = {eps, x, x_last, h1, h2, h3, k, init, blend_noise, mask};
+    const char* in_names[10] = {"eps", "x", "x_last", "h1", "h2", "h3", "k", "init", "blend_noise", "mask"};
+    const size_t in_bytes[10] = {cfg ? 2 * nb : nb, nb, nb, nb, nb, nb, batch * 4, nb, nb, init ? batch * (size_t)hw * 4 : 0};
+    for (int o = 0; o < 4; ++o) {
+        for (int j = 0; j < 10; ++j)
+            SD_REQUIRE(!pc_overlap(outs[o], nb, ins[j], in_bytes[j]), "sched_step_pc: output %s aliases input %s", out_names[o],
+                       in_names[j]);
+        for (int q = 0; q < o; ++q)
+            SD_REQUIRE(!pc_overlap(outs[o], nb, outs[q], nb), "sched_step_pc: output %s aliases output %s", out_names[o],
+                       out_names[q]);
+    }
+    const long n4 = n / 4, n4s = n_per_sample / 4, hw4 = init ? hw / 4 : 1;
+    const dim3 grid((unsigned)((n4 + 255) / 256));
+#define SD_PC_LAUNCH(R, B)                                                                                                   \
+    hipLaunchKernelGGL((sched_step_pc_kernel<R, B>), grid, dim3(256), 0, stream, eps, cfg, guidance, x, x_last, h1, h2, h3,  \
+                       prev, x_corr, y2, m_out, c, k, n4s, n4, init, blend_noise, mask, a, s, hw4)
+    if (k && init) SD_PC_LAUNCH(true, true);
+    else if (k) SD_PC_LAUNCH(true, false);
+    else if (init) SD_PC_LAUNCH(false, true);
+    else SD_PC_LAUNCH(false, false);
+#undef SD_PC_LAUNCH
     SD_CHECK_HIP(hipGetLastError());
     return 0;
 }

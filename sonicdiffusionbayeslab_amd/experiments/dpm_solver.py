@@ -15,10 +15,11 @@ class DPMSolverMethod(BaseMethod):
         self.solver_order = ep.solver_order
         self.algorithm_type = ep.get("algorithm_type", "dpmsolver++")
         self.final_sigmas_type = ep.get("final_sigmas_type", "zero" if self.algorithm_type.endswith("++") else "sigma_min")
+        self.use_karras_sigmas = bool(ep.get("use_karras_sigmas", False))      # (key of this build: "DPM++ 2M Karras")
 
     def setup_scheduler(self, **kwargs):
         return super().setup_scheduler(solver_order=self.solver_order, algorithm_type=self.algorithm_type,
-                                       final_sigmas_type=self.final_sigmas_type)
+                                       final_sigmas_type=self.final_sigmas_type, use_karras_sigmas=self.use_karras_sigmas)
 
     def run_experiment(self):
         self.sweep(self.num_inference_steps, lambda n: {"num_inference_steps": n},

@@ -1501,6 +1501,16 @@ class _VariantBase(StableDiffusionModel):
             raise NotImplementedError(f"image= (image-to-image) is not built for {type(self).__name__}; "
                                       "StableDiffusionModel runs it")
 
+    def _refuse_unipc(self, *schedulers):
+        """Before any GPU work: the variants hand a DPM-style history entry from one scheduler to the other (or skip steps
+        under a scheduler's feet) and have nothing to give UniPC's ``last_sample``."""
+        from .schedulers import UniPCScheduler
+        for s in schedulers:
+            if isinstance(s, UniPCScheduler):
+                raise NotImplementedError(f"UniPCScheduler is not built for {type(self).__name__}: its corrector needs the "
+                                          "sample its own previous step corrected, which the hand-off between schedulers "
+                                          "(or a skipped step) does not provide; StableDiffusionModel runs it")
+
 
 @models_registry.add_to_registry("stable_diffusion_model_two_schedulers")
 class StableDiffusionModelTwoSchedulers(_VariantBase):
@@ -1538,6 +1548,7 @@ class StableDiffusionModelTwoSchedulers(_VariantBase):
         self._refuse_image(kwargs)
         if self.scheduler_first is None or self.scheduler_second is None:
             raise ValueError("scheduler_first / scheduler_second must be set (two_schedulers.py:44-62)")
+        self._refuse_unipc(self.scheduler_first, self.scheduler_second)
         device, batch_size, do_cfg, ctx = self._begin(prompt, height, width, guidance_scale, negative_prompt,
                                                       num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
                                                       guidance_rescale, timesteps, sigmas, ip_adapter_image, ip_adapter_image_embeds)
@@ -1584,6 +1595,7 @@ class StableDiffusionModelInterlivingSchedulers(_VariantBase):
         self._refuse_image(kwargs)
         if self.scheduler_main is None or self.scheduler_inter is None:
             raise ValueError("scheduler_main / scheduler_inter must be set (interliving_exp.py:41-62)")
+        self._refuse_unipc(self.scheduler_main, self.scheduler_inter)
         interliving_steps = list(interliving_steps or [])
         device, batch_size, do_cfg, ctx = self._begin(prompt, height, width, guidance_scale, negative_prompt,
                                                       num_images_per_prompt, prompt_embeds, negative_prompt_embeds,
@@ -1617,6 +1629,7 @@ class StableDiffusionModelSkipTimesteps(_VariantBase):
              negative_prompt_embeds=None, output_type: str = "pil", return_dict: bool = True,
              guidance_rescale: float = 0.0, ip_adapter_image=None, ip_adapter_image_embeds=None, **kwargs):
         self._refuse_image(kwargs)
+        self._refuse_unipc(self.scheduler)
         skip = set(int(i) for i in (skip_timesteps or []))
         device, batch_size, do_cfg, ctx = self._begin(prompt, height, width, guidance_scale, negative_prompt,
                                                       num_images_per_prompt, prompt_embeds, negative_prompt_embeds,

@@ -6,6 +6,7 @@ Same registry keys, class names and call protocol as ``src/schedulers.py`` of th
 * ``"ddim_scheduler"``       -> ``DDIMSchedulerMy``     (``src/schedulers.py:190-192``)
 * ``"lcm_scheduler"``        -> ``LCMScheduler``        (``src/schedulers.py:195-197``)
 * ``"pndm_scheduler"``       -> ``PNDMScheduler``       (the checkpoint's own scheduler)
+* ``"unipc_scheduler"``      -> ``UniPCScheduler``      (diffusers' UniPCMultistepScheduler; its step is ``sd_sched_step_pc``)
 
 Protocol kept: ``from_config(config, **overrides)``, ``.config``, ``.order``,
 ``.init_noise_sigma``, ``set_timesteps(n, device=)``, ``.timesteps``, ``scale_model_input``,
@@ -200,14 +201,15 @@ class _FusedStepScheduler:
             raise NotImplementedError(f"prediction_type {self.config.prediction_type!r} is not built for "
                                       f"{type(self).__name__} (built: {PREDICTION_TYPES})")
 
-    def _refuse_epsilon_at_zero_snr(self, ts):
+    def _refuse_epsilon_at_zero_snr(self, ts, floor: float = 0.0):
         """Deliberate deviation from upstream: epsilon prediction at a step whose alpha_bar is 0 (a zero-terminal-SNR
         schedule reaching its last training timestep) divides by zero there, and upstream returns NaN latents.  This
-        refuses the combination before any GPU work."""
+        refuses the combination before any GPU work.  ``floor``: the value a scheduler has put in place of that 0
+        (UniPC's 2^-24), which is refused like the 0 it stands for."""
         if self.config.prediction_type != "epsilon":
             return
         for t in ts:
-            if float(self.alphas_cumprod[int(t)]) == 0.0:
+            if float(self.alphas_cumprod[int(t)]) <= floor:
                 raise ValueError(f"prediction_type='epsilon' with rescale_betas_zero_snr=True and timestep_spacing="
                                  f"{self.config.get('timestep_spacing')!r}: alpha_bar is 0 at timestep {int(t)}, where an "
                                  "epsilon prediction determines no x0; use prediction_type='v_prediction' (or 'sample')")
@@ -328,8 +330,96 @@ class DDIMSchedulerMy(_FusedStepScheduler):
         return prev, x0
 
 
+def alpha_sigma_lambda(sigma: float):
+    """(alpha_t, sigma_t, lambda_t) of a sigma of the table: alpha_t = 1 / sqrt(sigma^2 + 1), sigma_t = sigma alpha_t,
+    lambda_t = log alpha_t - log sigma_t (inf at sigma 0)."""
+    alpha = 1.0 / math.sqrt(sigma * sigma + 1.0)
+    sh = sigma * alpha
+    lam = math.log(alpha) - math.log(sh) if sh > 0 else math.inf
+    return alpha, sh, lam
+
+
+def sigma_to_t(sigma, log_sigmas: np.ndarray) -> np.ndarray:
+    """upstream's ``_sigma_to_t``: the (fractional) training timestep of a sigma, by piecewise-linear interpolation in
+    log-sigma over the training table ``log_sigmas`` (ascending in t)."""
+    log_sigma = np.log(np.maximum(np.atleast_1d(np.asarray(sigma, dtype=np.float64)), 1e-10))
+    dists = log_sigma[np.newaxis, :] - log_sigmas[:, np.newaxis]
+    low_idx = np.cumsum(dists >= 0, axis=0).argmax(axis=0).clip(max=log_sigmas.shape[0] - 2)
+    high_idx = low_idx + 1
+    low, high = log_sigmas[low_idx], log_sigmas[high_idx]
+    w = np.clip((low - log_sigma) / (low - high), 0, 1)
+    return (1 - w) * low_idx + w * high_idx
+
+
+def karras_schedule(train_sigmas: np.ndarray, n: int, rho: float = 7.0):
+    """``use_karras_sigmas`` (Karras et al. 2022, eq. 5, rho = 7, as upstream's ``_convert_to_karras``): n sigmas from
+    sigma_max = train_sigmas[-1] (t = T - 1) down to sigma_min = train_sigmas[0] (t = 0), and their rounded timesteps
+    (``sigma_to_t``; duplicates are legal).  Returns (timesteps int64, sigmas float64)."""
+    smax, smin = float(train_sigmas[-1]), float(train_sigmas[0])
+    ramp = np.linspace(0, 1, n)
+    lo, hi = smin ** (1.0 / rho), smax ** (1.0 / rho)
+    sig = (hi + ramp * (lo - hi)) ** rho
+    ts = sigma_to_t(sig, np.log(np.asarray(train_sigmas, dtype=np.float64))).round().astype(np.int64)
+    return ts, sig
+
+
+class _SigmaTableScheduler(_FusedStepScheduler):
+    """What DPM-Solver and UniPC share: the sigma table over the inference timesteps (the three spacings or Karras sigmas,
+    then the final sigma), the zero-terminal-SNR floor, and ``add_noise`` from that table."""
+    sigmas: Optional[np.ndarray] = None
+
+    def _floor_zero_snr(self):
+        if self.config.rescale_betas_zero_snr:
+            # as upstream: close to 0 without being 0, so that the first sigma is finite
+            self.alphas_cumprod[-1] = 2 ** -24
+
+    def _sigma_table(self, num_inference_steps: Optional[int], timesteps=None):
+        """(timesteps int64, sigmas float32 with the final sigma appended) as upstream's ``set_timesteps`` builds them."""
+        c = self.config
+        T = c.num_train_timesteps
+        last = T
+        if num_inference_steps is None and timesteps is None:
+            raise ValueError("Must pass exactly one of `num_inference_steps` or `timesteps`.")
+        karras = bool(c.get("use_karras_sigmas", False))
+        if timesteps is not None and karras:
+            raise ValueError("Cannot use `timesteps` with `config.use_karras_sigmas = True`")
+        ac = self.alphas_cumprod
+        sig = np.array(((1 - ac) / ac) ** 0.5)
+        if karras:
+            ts, sig = karras_schedule(sig, num_inference_steps)      # (timestep_spacing is not read, as upstream)
+        else:
+            if timesteps is not None:
+                ts = np.array([int(t) for t in timesteps]).astype(np.int64)
+            elif c.timestep_spacing == "linspace":
+                ts = np.linspace(0, last - 1, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
+            elif c.timestep_spacing == "leading":
+                ratio = last // (num_inference_steps + 1)
+                ts = (np.arange(0, num_inference_steps + 1) * ratio).round()[::-1][:-1].copy().astype(np.int64) + c.steps_offset
+            elif c.timestep_spacing == "trailing":
+                ts = np.arange(last, 0, -T / num_inference_steps).round().copy().astype(np.int64) - 1
+            else:
+                raise ValueError(c.timestep_spacing)
+            sig = np.interp(ts, np.arange(0, len(sig)), sig)
+        if c.final_sigmas_type == "sigma_min":
+            sig_last = ((1 - ac[0]) / ac[0]) ** 0.5
+        elif c.final_sigmas_type == "zero":
+            sig_last = 0
+        else:
+            raise ValueError(c.final_sigmas_type)
+        return ts, np.concatenate([sig, [sig_last]]).astype(np.float32)
+
+    _alpha_sigma_lambda = staticmethod(alpha_sigma_lambda)
+
+    def _add_noise_coefs(self, timestep):
+        """alpha_t, sigma_t of the scheduler's OWN sigma table at the index the loop begins at (upstream's
+        DPMSolverMultistepScheduler.add_noise with begin_index set; the table is interpolated, so this is not
+        sqrt(alpha_bar) of the fp32 table bit for bit)."""
+        alpha, sigma, _ = self._alpha_sigma_lambda(float(self.sigmas[self._index_of(timestep)]))
+        return alpha, sigma
+
+
 @schedulers_registry.add_to_registry("dpm_solver_scheduler")
-class DPMSolverScheduler(_FusedStepScheduler):
+class DPMSolverScheduler(_SigmaTableScheduler):
     """The reference's ``DPMSolverScheduler`` (``src/schedulers.py:12-187``): multistep
     DPM-Solver / DPM-Solver++ orders 1-3 whose ``step`` also returns the x0 prediction.
 
@@ -344,7 +434,7 @@ class DPMSolverScheduler(_FusedStepScheduler):
                          trained_betas=None, solver_order=2, prediction_type="epsilon", thresholding=False,
                          algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True,
                          euler_at_final=False, final_sigmas_type="zero", timestep_spacing="linspace", steps_offset=0,
-                         rescale_betas_zero_snr=False)
+                         rescale_betas_zero_snr=False, use_karras_sigmas=False)
     _accepted = tuple(_own_defaults)
 
     def __init__(self, **kwargs):
@@ -358,9 +448,7 @@ class DPMSolverScheduler(_FusedStepScheduler):
         if c.solver_type != "midpoint" or c.thresholding:
             raise NotImplementedError("only midpoint / no thresholding is on the hot path")
         self._check_prediction_type()
-        if c.rescale_betas_zero_snr:
-            # as upstream: close to 0 without being 0, so that the first sigma is finite
-            self.alphas_cumprod[-1] = 2 ** -24
+        self._floor_zero_snr()
         if c.solver_order not in (1, 2, 3):
             raise ValueError("solver_order must be 1, 2 or 3")
         self.model_outputs: List[Optional[torch.Tensor]] = [None] * c.solver_order
@@ -369,51 +457,13 @@ class DPMSolverScheduler(_FusedStepScheduler):
 
     def set_timesteps(self, num_inference_steps: Optional[int] = None, device=None, timesteps=None):
         """``timesteps``: custom schedule, as diffusers 0.32.1 accepts it and the two-scheduler pipeline uses it
-        (``src/models.py:488-492``)."""
+        (``src/models.py:488-492``).  ``use_karras_sigmas``: the Karras table of ``karras_schedule`` (upstream-recall)."""
         c = self.config
-        T = c.num_train_timesteps
-        last = T
-        if num_inference_steps is None and timesteps is None:
-            raise ValueError("Must pass exactly one of `num_inference_steps` or `timesteps`.")
-        if timesteps is not None:
-            ts = np.array([int(t) for t in timesteps]).astype(np.int64)
-        elif c.timestep_spacing == "linspace":
-            ts = np.linspace(0, last - 1, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
-        elif c.timestep_spacing == "leading":
-            ratio = last // (num_inference_steps + 1)
-            ts = (np.arange(0, num_inference_steps + 1) * ratio).round()[::-1][:-1].copy().astype(np.int64) + c.steps_offset
-        elif c.timestep_spacing == "trailing":
-            ts = np.arange(last, 0, -T / num_inference_steps).round().copy().astype(np.int64) - 1
-        else:
-            raise ValueError(c.timestep_spacing)
-        ac = self.alphas_cumprod
-        sig = np.array(((1 - ac) / ac) ** 0.5)
-        sig = np.interp(ts, np.arange(0, len(sig)), sig)
-        if c.final_sigmas_type == "sigma_min":
-            sig_last = ((1 - ac[0]) / ac[0]) ** 0.5
-        elif c.final_sigmas_type == "zero":
-            sig_last = 0
-        else:
-            raise ValueError(c.final_sigmas_type)
-        self.sigmas = np.concatenate([sig, [sig_last]]).astype(np.float32)
+        ts, self.sigmas = self._sigma_table(num_inference_steps, timesteps)
         self._refuse_epsilon_at_zero_snr(ts)
         self._set(ts, device)
         self.model_outputs = [None] * c.solver_order
         self.lower_order_nums = 0
-
-    @staticmethod
-    def _alpha_sigma_lambda(sigma: float):
-        alpha = 1.0 / math.sqrt(sigma * sigma + 1.0)
-        sh = sigma * alpha
-        lam = math.log(alpha) - math.log(sh) if sh > 0 else math.inf
-        return alpha, sh, lam
-
-    def _add_noise_coefs(self, timestep):
-        """alpha_t, sigma_t of the scheduler's OWN sigma table at the index the loop begins at (upstream's
-        DPMSolverMultistepScheduler.add_noise with begin_index set; the table is interpolated, so this is not
-        sqrt(alpha_bar) of the fp32 table bit for bit)."""
-        alpha, sigma, _ = self._alpha_sigma_lambda(float(self.sigmas[self._index_of(timestep)]))
-        return alpha, sigma
 
     def _convert_coefs(self, i: int):
         a0, s0, _ = self._alpha_sigma_lambda(float(self.sigmas[i]))
@@ -686,9 +736,203 @@ class PNDMScheduler(_FusedStepScheduler):
         return (prev.to(out_dtype),)
 
 
+UNIPC_SOLVER_TYPES = ("bh1", "bh2")
+
+
+def _unipc_update(lam_s0: float, lam_t: float, lam_hist, order: int, solver_type: str, predict_x0: bool, corrector: bool,
+                  a_t: float, s_t: float, a_s0: float, s_s0: float):
+    """One UniPC update from (lambda_s0) to (lambda_t) as coefficients: returns (A, c_m0, [c_m1, c_m2], c_new) with
+        out = A*x + c_m0*m0 + sum_k c_mk*m_k + c_new*m_new
+    m0 the model output at s0, m_k the ones before it (``lam_hist``: their lambdas, ``order - 1`` of them), m_new the model
+    output at t (corrector only; 0 for the predictor).  upstream's recurrences (rks, R, b, B_h, h_phi_k), with the D1
+    differences (m_k - m0) / r_k folded into the coefficients.  fp64, no torch."""
+    h = lam_t - lam_s0
+    if not math.isfinite(h):
+        # the step onto sigma 0 (lambda_t = inf), in the limit: sigma_t -> 0, e^{-h} -> 0, sigma_t e^{h} -> alpha_t sigma_s0 /
+        # alpha_s0.  First order only: the higher-order terms diverge there (upstream returns NaN).
+        if corrector or order != 1:
+            raise ValueError("UniPC: a step onto sigma 0 is first-order (lower_order_final=False with final_sigmas_type="
+                             "'zero' and solver_order > 1 has no finite update; use final_sigmas_type='sigma_min')")
+        if predict_x0:
+            return 0.0, a_t, [], 0.0
+        return a_t / a_s0, -(a_t * s_s0 / a_s0), [], 0.0
+    hh = -h if predict_x0 else h
+    h_phi_1 = math.expm1(hh)
+    if solver_type == "bh1":
+        B_h = hh
+    elif solver_type == "bh2":
+        B_h = h_phi_1
+    else:
+        raise NotImplementedError(f"solver_type {solver_type!r}: {UNIPC_SOLVER_TYPES} are built")
+    rks = [(l - lam_s0) / h for l in lam_hist] + [1.0]
+    R, b = [], []
+    h_phi_k = h_phi_1 / hh - 1.0
+    factorial_i = 1
+    for i in range(1, order + 1):
+        R.append([rk ** (i - 1) for rk in rks])
+        b.append(h_phi_k * factorial_i / B_h)
+        factorial_i *= i + 1
+        h_phi_k = h_phi_k / hh - 1.0 / factorial_i
+    if corrector:
+        rhos = [0.5] if order == 1 else list(np.linalg.solve(np.array(R, dtype=np.float64), np.array(b, dtype=np.float64)))
+        rho_hist, rho_new = rhos[:-1], rhos[-1]
+    else:
+        if order == 1:
+            rho_hist = []
+        elif order == 2:
+            rho_hist = [0.5]
+        else:
+            rho_hist = list(np.linalg.solve(np.array(R, dtype=np.float64)[:-1, :-1], np.array(b, dtype=np.float64)[:-1]))
+        rho_new = 0.0
+    A, S = (s_t / s_s0, a_t) if predict_x0 else (a_t / a_s0, s_t)
+    c_hist = [-S * B_h * rho / rk for rho, rk in zip(rho_hist, rks[:-1])]
+    c_new = -S * B_h * rho_new
+    c_m0 = -S * h_phi_1 - sum(c_hist) - c_new
+    return A, c_m0, [float(v) for v in c_hist], float(c_new)
+
+
+def unipc_rows(sigmas, i: int, corrector_order: int, predictor_order: int, solver_type: str = "bh2", predict_x0: bool = True,
+               prediction_type: str = "epsilon"):
+    """The coefficient rows (cm, cy, cc, cp) of ``sd_sched_step_pc`` for step ``i`` of the sigma table ``sigmas`` (n + 1
+    entries): the conversion at sigma_i, the corrector of order ``corrector_order`` from sigma_(i-1) to sigma_i (0: no
+    corrector, cc is None) and the predictor of order ``predictor_order`` from sigma_i to sigma_(i+1).  Pure host
+    arithmetic in fp64."""
+    asl = {j: alpha_sigma_lambda(float(sigmas[j])) for j in range(max(i - 3, 0), i + 2)}      # (the entries a step can read)
+    a0, s0, l0 = asl[i]
+    dx, de, ex, ee = prediction_coefs(prediction_type, a0, s0)
+    cy = (dx, de)
+    cm = (dx, de) if predict_x0 else (ex, ee)
+    cc = None
+    if corrector_order:
+        o = corrector_order
+        if not 1 <= o <= 3 or i - o < 0:
+            raise ValueError(f"UniPC corrector of order {o} at step {i}")
+        ap, sp, lp = asl[i - 1]
+        A, c0, ch, cn = _unipc_update(lp, l0, [asl[i - 1 - k][2] for k in range(1, o)], o, solver_type, predict_x0, True,
+                                      a0, s0, ap, sp)
+        ch = ch + [0.0] * (2 - len(ch))
+        cc = (A, c0, ch[0], ch[1], cn)                # x_last, h1, h2, h3, m_t
+    o = predictor_order
+    if not 1 <= o <= 3 or i - (o - 1) < 0:
+        raise ValueError(f"UniPC predictor of order {o} at step {i}")
+    at, st, lt = asl[i + 1]
+    A, c0, ch, _ = _unipc_update(l0, lt, [asl[i - k][2] for k in range(1, o)], o, solver_type, predict_x0, False,
+                                 at, st, a0, s0)
+    ch = ch + [0.0] * (2 - len(ch))
+    cp = (A, c0, ch[0], ch[1])                        # xc, m_t, h1, h2
+    return cm, cy, cc, cp
+
+
+@schedulers_registry.add_to_registry("unipc_scheduler")
+class UniPCScheduler(_SigmaTableScheduler):
+    """diffusers' ``UniPCMultistepScheduler`` (Zhao et al. 2023), upstream-recall: restated from the paper and from memory of
+    upstream's code, not checked against an installed diffusers.  A step corrects the sample the previous step predicted
+    (with this step's model output, so for no extra UNet evaluation) and predicts the next one from the corrected sample;
+    both are linear in the sample, the model output and the history, so the step is ONE ``sd_sched_step_pc`` launch whose
+    coefficient rows ``unipc_rows`` derives in fp64.  The sigma table, spacings, final sigma and zero-SNR handling are
+    ``DPMSolverScheduler``'s.  Not built: thresholding, ``solver_p``, the beta / exponential / flow sigma options."""
+    _own_defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                         trained_betas=None, solver_order=2, prediction_type="epsilon", thresholding=False,
+                         predict_x0=True, solver_type="bh2", lower_order_final=True, disable_corrector=[],
+                         timestep_spacing="linspace", steps_offset=0, final_sigmas_type="zero",
+                         rescale_betas_zero_snr=False, use_karras_sigmas=False)
+    _accepted = tuple(_own_defaults)
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        c = self.config
+        if c.thresholding:
+            raise NotImplementedError("thresholding is not on the hot path")
+        if c.solver_type not in UNIPC_SOLVER_TYPES:
+            raise NotImplementedError(f"solver_type {c.solver_type!r}: {UNIPC_SOLVER_TYPES} are built")
+        if c.solver_order not in (1, 2, 3):
+            raise ValueError(f"solver_order={c.solver_order!r} must be 1, 2 or 3")
+        if c.final_sigmas_type not in ("zero", "sigma_min"):
+            raise ValueError(f"final_sigmas_type {c.final_sigmas_type!r}: 'zero' or 'sigma_min'")
+        self._check_prediction_type()
+        self._floor_zero_snr()
+        self.config["disable_corrector"] = [int(v) for v in (c.disable_corrector or [])]
+        self._reset()
+
+    def _reset(self):
+        self.model_outputs: List[Optional[torch.Tensor]] = [None] * self.config.solver_order      # oldest ... newest
+        self.last_sample: Optional[torch.Tensor] = None
+        self.this_order = 0
+        self.lower_order_nums = 0
+
+    def set_timesteps(self, num_inference_steps: Optional[int] = None, device=None, timesteps=None):
+        ts, self.sigmas = self._sigma_table(num_inference_steps, timesteps)
+        # (the 2^-24 that stands for alpha_bar = 0 is refused like the 0: x0 = (x - sigma eps) / 2^-12 there)
+        self._refuse_epsilon_at_zero_snr(ts, floor=2 ** -24 if self.config.rescale_betas_zero_snr else 0.0)
+        self._set(ts, device)
+        self._reset()
+
+    def step_orders(self, i: int):
+        """(corrector order or 0, predictor order) of step ``i`` given the state, in upstream's order: the corrector runs
+        unless this is the first executed step of the call or step i - 1 is in ``disable_corrector``, at the previous step's
+        order; the predictor's order is min(solver_order, steps left) under ``lower_order_final``, capped by the history."""
+        c = self.config
+        use_corrector = self.last_sample is not None and i > 0 and (i - 1) not in c.disable_corrector
+        this_order = min(c.solver_order, len(self._timesteps_list) - i) if c.lower_order_final else c.solver_order
+        return (self.this_order if use_corrector else 0), min(this_order, self.lower_order_nums + 1)
+
+    def rows(self, i: int, corrector_order: int, predictor_order: int):
+        c = self.config
+        return unipc_rows(self.sigmas, i, corrector_order, predictor_order, c.solver_type, c.predict_x0, c.prediction_type)
+
+    @staticmethod
+    def _launch_pc(eps, cfg, guidance, x, x_last, hist, rows, k=None, blend=None):
+        """ONE ``sd_sched_step_pc`` launch.  ``hist``: (h1, h2, h3), newest first, None where the row has no weight;
+        ``rows`` = (cm, cy, cc, cp) of ``unipc_rows``.  Returns (prev, x_corr, y2, m_t)."""
+        lib = _lib.load()
+        cm, cy, cc, cp = rows
+        n = x.numel()
+        prev, xc, y2, mo = (torch.empty_like(x) for _ in range(4))
+        carr = (C.c_float * 13)(*[float(v) for v in (*cm, *cy, *(cc if cc is not None else (0.0,) * 5), *cp)])
+        init = bnoise = mask = None
+        a, s, hw = 1.0, 0.0, 0
+        if blend is not None:
+            init, bnoise, mask, a, s = blend
+            hw = mask.numel() // mask.shape[0]
+        _lib.check(lib.sd_sched_step_pc(_lib.current_stream(), eps.data_ptr(), int(cfg), float(guidance), x.data_ptr(),
+                                        _lib.ptr(x_last), _lib.ptr(hist[0]), _lib.ptr(hist[1]), _lib.ptr(hist[2]),
+                                        prev.data_ptr(), xc.data_ptr(), y2.data_ptr(), mo.data_ptr(), carr, n, _lib.ptr(k),
+                                        n // x.shape[0], _lib.ptr(init), _lib.ptr(bnoise), _lib.ptr(mask), float(a), float(s),
+                                        int(hw)), "sd_sched_step_pc")
+        return prev, xc, y2, mo
+
+    def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
+                   guidance_rescale: float = 0.0, inpaint=None):
+        """``eta`` and ``generator`` are not read (the solver is deterministic)."""
+        c = self.config
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if self._step_index is None:
+            self._step_index = self._index_of(timestep)
+        i = self._step_index
+        order_c, order_p = self.step_orders(i)
+        rows = self.rows(i, order_c, order_p)
+        newest_first = self.model_outputs[::-1]
+        depth = max(order_c, order_p - 1)                       # the corrector reads h1..h_o, the predictor h1..h_(o-1)
+        hist = [newest_first[j] if j < min(depth, len(newest_first)) else None for j in range(3)]
+        e, x = self._prep(model_output), self._prep(sample)
+        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x)
+        # (inpainting: the corrected sample, the history entry and x0 are taken before the blend, as upstream steps first)
+        prev, xc, x0, m_t = self._launch_pc(e, cfg, guidance_scale, x, self.last_sample if order_c else None, hist, rows,
+                                            k=k, blend=self._blend(inpaint, x))
+        self.model_outputs = self.model_outputs[1:] + [m_t]
+        self.last_sample = xc
+        self.this_order = order_p
+        if self.lower_order_nums < c.solver_order:
+            self.lower_order_nums += 1
+        self._step_index += 1
+        return prev, x0
+
+
 # the checkpoint's scheduler class (``_class_name`` of scheduler/scheduler_config.json) -> its registry key
 CHECKPOINT_SCHEDULERS = {"PNDMScheduler": "pndm_scheduler", "DDIMScheduler": "ddim_scheduler",
-                         "DPMSolverMultistepScheduler": "dpm_solver_scheduler", "LCMScheduler": "lcm_scheduler"}
+                         "DPMSolverMultistepScheduler": "dpm_solver_scheduler", "LCMScheduler": "lcm_scheduler",
+                         "UniPCMultistepScheduler": "unipc_scheduler"}
 
 
 def checkpoint_scheduler_name(config) -> str:

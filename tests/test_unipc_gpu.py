@@ -1,0 +1,489 @@
+"""UniPC on the GPU: ``sd_sched_step_pc`` per element between guard bands, teacher-forced trajectories of ``UniPCScheduler``
+(and of DPM-Solver++ on Karras sigmas) against the fp64 restatements, free-running loops on the small synthetic UNet against
+the oracle UNet stepped by tests/unipc_ref.py, and the launch count of a call."""
+import ctypes as C
+import dataclasses
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+from sonicdiffusionbayeslab_amd import _lib
+from tests import bounds as BD
+from tests import sched_ref as R
+from tests import unipc_ref as UR
+from tests.util import cosine, oracle_cfg, rel_l2, synth_inputs
+
+F64 = torch.float64
+# The longest input-to-output path of sched_step_pc_kernel (csrc/small.hip), counted in fp32 operations, eps -> prev with CFG, k
+# and the corrector:  et - e, guidance * (.), e + (.)  [3];  k[b] * e  [1];  cm1 * e, (cm0 x) + (.)  [2];
+# cc4 * m_t, xc + (.)  [2];  cp0 * xc, (.) + cp1 m_t, + cp2 h1, + cp3 h2  [4]  = 12.  Every other path is shorter (x_last -> prev:
+# 1 + 4 + 4 = 9; the blend's a * init + s * blend_noise: 3), and a contraction to fma only removes roundings.
+K_EFF = 12
+# A scheduler step on top of that: the fp64 rows are rounded to fp32 on the way to the kernel, at most three coefficients deep on a
+# path (cm1, cc4, cp0), each one more factor (1 + delta), |delta| <= 2^-24.
+K_STEP = K_EFF + 3
+# the free-running gates of tests/test_pipeline_gpu.py (FREE_TOL, FREE_COS there), by value
+FREE_TOL, FREE_COS = 6e-2, 0.998
+GS = 7.5
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def f32(v):
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+# ------------------------------------------------------------------------------------------------ 1. the kernel, per element
+def _operands(shape, cfg, seed):
+    g = torch.Generator().manual_seed(seed)
+    B = shape[0]
+    t = {n: torch.randn(shape, generator=g) for n in ("x", "x_last", "h1", "h2", "h3", "init", "bnoise")}
+    t["eps"] = torch.randn(((2 if cfg else 1) * shape[0],) + tuple(shape[1:]), generator=g)
+    t["eps"][shape[0] if cfg else 0:] *= 1.7
+    t["k"] = 0.6 + 0.5 * torch.rand(B, generator=g)
+    t["mask"] = (torch.rand(B, 1, shape[2], shape[3], generator=g) > 0.5).float()
+    t["mask"][:, :, 0, 0], t["mask"][:, :, -1, -1] = 1.0, 0.0          # both sides of the blend in every sample
+    coef = [f32(v) for v in (torch.rand(13, generator=g) * 2 - 1).tolist()]
+    return t, coef
+
+
+def _launch(sdlib, t, coef, cfg, use_k, blend, x_last=True, depth=3, outs=("prev", "x_corr", "y2", "m_out"), nps=None, hw=None):
+    """One sd_sched_step_pc launch on guarded operands; returns {name: cpu tensor} of the outputs asked for."""
+    shape = tuple(t["x"].shape)
+    n = t["x"].numel()
+    nps = nps or n // shape[0]
+    d = {k: BD.guarded_input(v, label=k) for k, v in t.items()}
+    o = {k: BD.guarded(shape, torch.float32, label=k) for k in outs}
+    hist = [d[f"h{j + 1}"].data_ptr() if j < depth else None for j in range(3)]
+    c = list(coef)
+    for j in range(3):                                   # a null history entry carries no weight
+        if j >= depth:
+            c[5 + j] = 0.0
+            if j < 2:
+                c[11 + j] = 0.0
+    a, s = blend if blend is not None else (1.0, 0.0)
+    hw = hw or shape[2] * shape[3]
+    ptr = lambda k: o[k].data_ptr() if k in o else None          # noqa: E731
+    _lib.check(sdlib.sd_sched_step_pc(
+        _lib.current_stream(), d["eps"].data_ptr(), int(cfg), GS, d["x"].data_ptr(), d["x_last"].data_ptr() if x_last else None,
+        hist[0], hist[1], hist[2], o["prev"].data_ptr(), ptr("x_corr"), ptr("y2"), ptr("m_out"), (C.c_float * 13)(*c), n,
+        d["k"].data_ptr() if use_k else None, nps, d["init"].data_ptr() if blend is not None else None,
+        d["bnoise"].data_ptr() if blend is not None and s != 0.0 else None, d["mask"].data_ptr() if blend is not None else None,
+        a, s, hw if blend is not None else 0), "sd_sched_step_pc")
+    torch.cuda.synchronize()
+    out = {k: v.cpu().clone() for k, v in o.items()}
+    BD.check_guards()
+    return out, c
+
+
+def _chain(t, c, cfg, use_k, blend, x_last, depth, k=None):
+    """The documented formula in fp64 from the fp32 inputs, and the same chain on absolute values and coefficients:
+    {name: (ref, mag)}."""
+    d = {n: v.double() for n, v in t.items()}
+    if cfg:
+        u, cc_ = d["eps"].chunk(2)
+        e, me = u + GS * (cc_ - u), u.abs() + GS * (cc_.abs() + u.abs())
+    else:
+        e, me = d["eps"], d["eps"].abs()
+    if use_k:
+        kk = (d["k"] if k is None else k.double()).view(-1, 1, 1, 1)
+        e, me = kk * e, kk.abs() * me
+    x = d["x"]
+    cm, cy, cc, cp = c[0:2], c[2:4], c[4:9], c[9:13]
+    mt, mmt = cm[0] * x + cm[1] * e, abs(cm[0]) * x.abs() + abs(cm[1]) * me
+    y2, my2 = cy[0] * x + cy[1] * e, abs(cy[0]) * x.abs() + abs(cy[1]) * me
+    h = [d[f"h{j + 1}"] if j < depth else None for j in range(3)]
+    if x_last:
+        xc, mxc = cc[0] * d["x_last"], abs(cc[0]) * d["x_last"].abs()
+        for j in range(3):
+            if h[j] is not None:
+                xc, mxc = xc + cc[1 + j] * h[j], mxc + abs(cc[1 + j]) * h[j].abs()
+        xc, mxc = xc + cc[4] * mt, mxc + abs(cc[4]) * mmt
+    else:
+        xc, mxc = x, x.abs()
+    p, mp = cp[0] * xc + cp[1] * mt, abs(cp[0]) * mxc + abs(cp[1]) * mmt
+    for j in range(2):
+        if h[j] is not None:
+            p, mp = p + cp[2 + j] * h[j], mp + abs(cp[2 + j]) * h[j].abs()
+    if blend is not None:
+        a, s = f32(blend[0]), f32(blend[1])
+        keep, mkeep = a * d["init"], abs(a) * d["init"].abs()
+        if s != 0.0:
+            keep, mkeep = keep + s * d["bnoise"], mkeep + abs(s) * d["bnoise"].abs()
+        rep = (t["mask"] >= 0.5).expand_as(p)
+        p, mp = torch.where(rep, p, keep), torch.where(rep, mp, mkeep)
+    return {"prev": (p, mp), "x_corr": (xc, mxc), "y2": (y2, my2), "m_out": (mt, mmt)}
+
+
+def _bound(ref, mag, k_eff=K_EFF):
+    """tests/bounds.py's rule for an fp32 output: one fp32 ulp at |ref| + 2^-24 * K_eff * mag."""
+    return BD.linear_bound(ref, mag, k_eff, out=torch.float32)
+
+
+SHAPES = [(1, 1, 1, 4), (1, 4, 16, 16), (2, 4, 40, 56), (7, 4, 40, 56), (8, 4, 64, 64)]
+WORST = {}
+
+
+@pytest.mark.parametrize("variant", ["plain", "cfg", "cfg-k", "k", "cfg-k-blend", "blend-s0", "cfg-blend"])
+@pytest.mark.parametrize("shape", SHAPES, ids=["n4", "1x4x16x16", "2x4x40x56", "7x4x40x56", "8x4x64x64"])
+def test_kernel_per_element(sdlib, shape, variant):
+    cfg, use_k = "cfg" in variant, "k" in variant.split("-")
+    blend = None
+    if "blend" in variant:
+        blend = (1.0, 0.0) if variant == "blend-s0" else (0.8125 + 2.0 ** -12, 0.58203125 + 2.0 ** -13)
+    t, coef = _operands(shape, cfg, seed=sum(shape) + len(variant))
+    got, c = _launch(sdlib, t, coef, cfg, use_k, blend)
+    ref = _chain(t, c, cfg, use_k, blend, True, 3)
+    for name in ("prev", "x_corr", "y2", "m_out"):
+        r = BD.assert_elementwise(got[name], ref[name][0], _bound(*ref[name]), f"{name} {shape} {variant}")
+        WORST[name] = max(WORST.get(name, 0.0), r)
+    if blend is not None:
+        rep = (t["mask"] >= 0.5).expand_as(got["prev"])
+        assert (~rep).any() and rep.any()
+        if variant == "blend-s0":                          # (a, s) = (1, 0) with blend_noise NULL: the kept side is init's bits
+            assert torch.equal(bits(got["prev"])[~rep], bits(t["init"])[~rep])
+        plain, _ = _launch(sdlib, t, coef, cfg, use_k, None)
+        assert torch.equal(bits(got["prev"])[rep], bits(plain["prev"])[rep])
+        for name in ("x_corr", "y2", "m_out"):             # these do not see the mask
+            assert torch.equal(bits(got[name]), bits(plain[name]))
+    print("worst error / bound so far:", {k: f"{v:.3f}" for k, v in WORST.items()})
+
+
+@pytest.mark.parametrize("depth", [0, 1, 2, 3])
+@pytest.mark.parametrize("x_last", [True, False])
+def test_kernel_history_depth_and_no_corrector(sdlib, depth, x_last):
+    shape = (2, 4, 40, 56)
+    t, coef = _operands(shape, True, seed=40 + depth)
+    got, c = _launch(sdlib, t, coef, True, True, None, x_last=x_last, depth=depth)
+    ref = _chain(t, c, True, True, None, x_last, depth)
+    for name in ("prev", "x_corr", "y2", "m_out"):
+        BD.assert_elementwise(got[name], ref[name][0], _bound(*ref[name]), f"{name} depth {depth} x_last {x_last}")
+    if not x_last:
+        assert torch.equal(bits(got["x_corr"]), bits(t["x"]))              # xc = x bit for bit
+        # the same launch given the identity corrector row: x_last := x, cc = (1, 0, 0, 0, 0)
+        ident = list(c)
+        ident[4:9] = [1.0, 0.0, 0.0, 0.0, 0.0]
+        same, _ = _launch(sdlib, dict(t, x_last=t["x"]), ident, True, True, None, x_last=True, depth=depth)
+        assert torch.equal(bits(same["prev"]), bits(got["prev"])) and torch.equal(bits(same["x_corr"]), bits(got["x_corr"]))
+    # optional outputs NULL: prev keeps its bits
+    only, _ = _launch(sdlib, t, coef, True, True, None, x_last=x_last, depth=depth, outs=("prev",))
+    assert torch.equal(bits(only["prev"]), bits(got["prev"]))
+
+
+def test_kernel_batch_invariance(sdlib):
+    """A sample's outputs are bit-identical alone and at position 5 of 7 (k and the mask are per sample)."""
+    shape = (7, 4, 40, 56)
+    t, coef = _operands(shape, True, seed=77)
+    blend = (0.75, 0.5)
+    full, _ = _launch(sdlib, t, coef, True, True, blend)
+    b = 5
+    one = {n: v[b:b + 1] for n, v in t.items() if n != "eps"}
+    one["eps"] = torch.cat([t["eps"][b:b + 1], t["eps"][7 + b:8 + b]])
+    alone, _ = _launch(sdlib, one, coef, True, True, blend)
+    for name in ("prev", "x_corr", "y2", "m_out"):
+        assert torch.equal(bits(alone[name]), bits(full[name][b:b + 1])), name
+
+
+# ------------------------------------------------------------------------------------------------ 2. trajectories, teacher-forced
+def _sched(name, **kw):
+    from sonicdiffusionbayeslab_amd.registry import schedulers_registry
+    from sonicdiffusionbayeslab_amd.schedulers import PNDMConfigStub
+    return schedulers_registry[name].from_config(PNDMConfigStub().config, **kw)
+
+
+def _unipc_pair(n, **kw):
+    s = _sched("unipc_scheduler", **kw)
+    s.set_timesteps(n, device="cuda")
+    c = s.config
+    ref = UR.UniPC(s.sigmas, s._timesteps_list, c.prediction_type, c.solver_order, c.solver_type, c.predict_x0,
+                   c.lower_order_final, c.disable_corrector)
+    return s, ref
+
+
+TRAJ = [("order2-bh2", dict(solver_order=2, solver_type="bh2"), 10, 0.0, False),
+        ("order3-bh1", dict(solver_order=3, solver_type="bh1"), 8, 0.0, False),
+        ("v-zsnr-trailing-rescale", dict(prediction_type="v_prediction", rescale_betas_zero_snr=True,
+                                         timestep_spacing="trailing"), 10, 0.7, False),
+        ("karras", dict(solver_order=2, use_karras_sigmas=True), 10, 0.0, False),
+        ("disable-corrector-0", dict(solver_order=2, disable_corrector=[0]), 10, 0.0, False),
+        ("inpaint-blend", dict(solver_order=2), 10, 0.0, True)]
+
+
+@pytest.mark.parametrize("name,kw,n,rescale,blend", TRAJ, ids=[t[0] for t in TRAJ])
+def test_unipc_trajectory_matches_restatement(name, kw, n, rescale, blend):
+    """Every step of a full schedule on seeded random model outputs.  Each step starts from the restatement's state rounded to
+    fp32 (sample, history, last_sample -- the product's own are replaced by it), so both sides compute one step from the same
+    fp32 inputs and the gate is the kernel's a-priori bound with K_STEP.  guidance_rescale: the factors are the product's own
+    (sd_cfg_rescale_factors has its per-element test in test_rescale_gpu.py); the restatement scales by them."""
+    shape = (2, 4, 16, 16)
+    s, ref = _unipc_pair(n, **kw)
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(shape, generator=g)
+    init, bnoise = torch.randn(shape, generator=g), torch.randn(shape, generator=g)
+    mask = (torch.rand(2, 1, 16, 16, generator=g) > 0.5).float()
+    ts = list(s._timesteps_list)
+    worst = 0.0
+    for i, t in enumerate(ts):
+        e2 = torch.randn((4,) + shape[1:], generator=g)
+        oc, op = s.step_orders(i)
+        rows = s.rows(i, oc, op)
+        hist = [h for h in s.model_outputs[::-1] if h is not None]
+        x_last = s.last_sample
+        kws = {}
+        if blend:
+            t_next = ts[i + 1] if i + 1 < n else None
+            kws["inpaint"] = (init.cuda(), bnoise.cuda(), mask.cuda(), t_next)
+        got = s.step_fused(e2.cuda(), GS, x.cuda(), t, cfg=True, guidance_rescale=rescale, **kws)
+        gd = R.cfg_combine(*e2.double().chunk(2), GS)
+        if rescale > 0:
+            assert s.rescale_factors is not None and s.rescale_factors.shape == (2,)
+            gd = s.rescale_factors.double().cpu().view(-1, 1, 1, 1) * gd
+        want_prev, want_x0 = ref.step(gd, t, x)
+        # magnitudes: the formula's chain on absolute values, with the product's rows
+        tt = {"x": x, "eps": e2, "k": s.rescale_factors.cpu() if rescale > 0 else torch.ones(2),
+              "x_last": x_last.cpu() if x_last is not None else x, "init": init, "bnoise": bnoise, "mask": mask}
+        depth = len(hist)
+        for j in range(3):
+            tt[f"h{j + 1}"] = hist[j].cpu() if j < depth else x
+        cm, cy, cc, cp = rows
+        c = [*cm, *cy, *(cc if cc is not None else (0.0,) * 5), *cp]
+        bl = None
+        if blend:
+            bl = (1.0, 0.0) if t_next is None else s._add_noise_coefs(t_next)
+        mags = _chain(tt, c, True, rescale > 0, bl, oc > 0, depth)
+        if blend:
+            rep = (mask >= 0.5).expand_as(want_prev)
+            a, sg = f32(bl[0]), f32(bl[1])
+            want_prev = torch.where(rep, want_prev, a * init.double() + sg * bnoise.double())
+        for nm, a, b in (("prev", got[0], want_prev), ("x0", got[1], want_x0), ("x_corr", s.last_sample, ref.last_sample),
+                         ("m_t", s.model_outputs[-1], ref.m_t)):
+            mag = mags[{"x0": "y2", "m_t": "m_out"}.get(nm, nm)][1]
+            bound = _bound(b, mag, K_STEP) + 1e-10 * mag            # (+ rows vs restatement: fp64 association, test_unipc_cpu)
+            worst = max(worst, BD.assert_elementwise(a.cpu(), b, bound, f"{name} step {i} {nm}"))
+        # restart from the restatement's fp32-rounded state, on both sides
+        ref.outs = [None if o is None else o.float().double() for o in ref.outs]
+        ref.last_sample = ref.last_sample.float().double()
+        s.model_outputs = [None if o is None else o.float().cuda() for o in ref.outs]
+        s.last_sample = ref.last_sample.float().cuda()
+        x = want_prev.float()
+    print(f"{name}: worst error / bound over {n} steps {worst:.3f}")
+
+
+def test_dpm_solver_on_karras_sigmas_matches_restatement():
+    """DPM-Solver++ 2M on the Karras table (n = 10) against sched_ref's DPM fed that table, teacher-forced; per element with
+    the bound of sd_sched_step's chain: CFG 3 + pe * e, px x + (.), + p1 m1 = 3, one coefficient rounding = 7."""
+    s = _sched("dpm_solver_scheduler", solver_order=2, algorithm_type="dpmsolver++", use_karras_sigmas=True)
+    s.set_timesteps(10, device="cuda")
+    ts, sig = UR.karras_table(torch.from_numpy(s.alphas_cumprod), 10, "zero")
+    assert s._timesteps_list == ts
+    ref = R.DPM(torch.from_numpy(s.alphas_cumprod), ts, "epsilon", "dpmsolver++", 2, "zero")
+    ref.sig = [float(v) for v in s.sigmas]                  # the Karras table as the product holds it (fp32; its distance to
+    assert max(abs(a - b) for a, b in zip(ref.sig, sig)) <= 1e-6 * max(sig)      # the fp64 table is test_unipc_cpu's subject)
+    g = torch.Generator().manual_seed(9)
+    shape = (2, 4, 16, 16)
+    x = torch.randn(shape, generator=g)
+    for i, t in enumerate(ts):
+        e2 = torch.randn((4,) + shape[1:], generator=g)
+        m1 = s.model_outputs[-1]
+        got = s.step_fused(e2.cuda(), GS, x.cuda(), t, cfg=True)
+        u, c = e2.double().chunk(2)
+        want = ref.step(R.cfg_combine(u, c, GS), t, x)
+        me = u.abs() + GS * (c.abs() + u.abs())
+        yx, ye, mx, mee = s._convert_coefs(i)
+        mag_x0 = abs(yx) * x.double().abs() + abs(ye) * me
+        order = 1 if (i == 0 or i == 9) else 2
+        px, pe, p1, p2, pn = s._update_coefs(i, order, mx, mee)
+        mag = abs(px) * x.double().abs() + abs(pe) * me + (abs(p1) * m1.double().abs().cpu() if order == 2 else 0.0)
+        BD.assert_elementwise(got[0].cpu(), want[0], _bound(want[0], mag, 7) + 1e-10 * mag, f"dpm karras step {i} prev")
+        BD.assert_elementwise(got[1].cpu(), want[1], _bound(want[1], mag_x0, 7) + 1e-10 * mag_x0, f"dpm karras step {i} x0")
+        ref.outs = [None if o is None else o.float().double() for o in ref.outs]
+        s.model_outputs = [None if o is None else o.float().cuda() for o in ref.outs]
+        x = want[0].float()
+
+
+# ------------------------------------------------------------------------------------------------ 3. free-running loops
+class UniPCOracle:
+    """The oracle loops' scheduler protocol (oracle/schedulers.py) over tests/unipc_ref.py, on the product's sigma table."""
+    init_noise_sigma = 1.0
+
+    def __init__(self, **kw):
+        self.kw = kw
+        self.alphas_cumprod = torch.from_numpy(_sched("unipc_scheduler", **kw).alphas_cumprod)
+
+    def set_timesteps(self, n):
+        s = _sched("unipc_scheduler", **self.kw)
+        s.set_timesteps(n)
+        c = s.config
+        self.timesteps = torch.tensor(s._timesteps_list)
+        self.sigmas = torch.from_numpy(s.sigmas).double()
+        self.ref = UR.UniPC(s.sigmas, s._timesteps_list, c.prediction_type, c.solver_order, c.solver_type, c.predict_x0,
+                            c.lower_order_final, c.disable_corrector)
+
+    def scale_model_input(self, x, t=None):
+        return x
+
+    @staticmethod
+    def _sigma_to_alpha_sigma_t(sigma):
+        a = 1.0 / (sigma * sigma + 1.0) ** 0.5
+        return a, sigma * a
+
+    def step(self, m, t, x, return_dict=False, **_):
+        prev, x0 = self.ref.step(m, int(t), x)
+        return prev.float(), x0.float()
+
+
+@pytest.fixture(scope="module")
+def env():
+    from sonicdiffusionbayeslab_amd.models import StableDiffusionModel
+    from sonicdiffusionbayeslab_amd.weights import UNetConfig, make_synthetic_state_dict
+    cfg = UNetConfig(sample_size=16)
+    sd = make_synthetic_state_dict(cfg, seed=1234)
+    model = StableDiffusionModel(unet_config=cfg, state_dict=dict(sd)).to("cuda:0")
+    return cfg, sd, model
+
+
+UNI_KW = dict(solver_order=2, solver_type="bh2")
+N_FREE = 8
+
+
+def _plain_call(model, lat, pe, ne, n=N_FREE, **kw):
+    model.scheduler = _sched("unipc_scheduler", **UNI_KW)
+    return model(prompt_embeds=pe, negative_prompt_embeds=ne, latents=lat, num_inference_steps=n, guidance_scale=GS,
+                 output_type="latent", **kw)
+
+
+def test_free_running_loop_matches_the_oracle_loop(env):
+    from oracle.pipeline import sample_loop
+    cfg, sd, model = env
+    lat, pe, ne = synth_inputs(cfg, 2, seed=71)
+    out, _, x0s = _plain_call(model, lat, pe, ne)
+    assert len(x0s) == N_FREE and model.num_timesteps == N_FREE
+    ref, _, ref_x0s, _ = sample_loop(sd, oracle_cfg(cfg), UniPCOracle(**UNI_KW), pe, ne, lat, N_FREE, GS)
+    err, cs = rel_l2(out.images, ref), cosine(out.images, ref)
+    print(f"UniPC order 2 bh2, {N_FREE} steps, CFG {GS}: rel-L2 {err:.3e} cos {cs:.5f}; last x0 rel-L2 "
+          f"{rel_l2(x0s[-1], ref_x0s[-1]):.3e}")
+    assert torch.isfinite(out.images).all() and err < FREE_TOL and cs > FREE_COS
+    again, _, _ = _plain_call(model, lat, pe, ne)
+    assert torch.equal(again.images, out.images)
+
+
+def _image(b, h, w, seed):
+    g = torch.Generator().manual_seed(seed)
+    low = F.interpolate(torch.rand(b, 3, h // 16, w // 16, generator=g), size=(h, w), mode="bilinear", align_corners=False)
+    return (0.8 * low + 0.2 * torch.rand(b, 3, h, w, generator=g)).clamp(0, 1)
+
+
+def test_image_to_image_starts_without_a_corrector(env):
+    """strength 0.6 of 10 steps: 6 run, the first of them (schedule index 4) with no ``last_sample``.  Compared with the oracle
+    img2img loop as tests/test_img2img_gpu.py builds it."""
+    from oracle.vae import VaeConfig as OC
+    from sonicdiffusionbayeslab_amd.vae import VaeConfig, make_synthetic_vae_state_dict
+    from tests.vae_encoder_oracle import img2img_loop
+    cfg, sd, model = env
+    vcfg = VaeConfig(sample_size=16)
+    vsd = make_synthetic_vae_state_dict(vcfg)
+    _, pe, ne = synth_inputs(cfg, 1, seed=73)
+    img = _image(1, 128, 128, seed=74)
+    model.scheduler = _sched("unipc_scheduler", **UNI_KW)
+    out, _, x0s = model(prompt_embeds=pe, negative_prompt_embeds=ne, image=img, strength=0.6, num_inference_steps=10,
+                        guidance_scale=GS, generator=torch.Generator().manual_seed(75), output_type="latent")
+    ref, ref_start, steps = img2img_loop(sd, oracle_cfg(cfg), vsd, OC(**dataclasses.asdict(vcfg)), UniPCOracle(**UNI_KW), pe, ne,
+                                         img, 10, 0.6, GS, torch.Generator().manual_seed(75))
+    assert steps == 6 == len(x0s) == model.num_timesteps
+    es, err, cs = rel_l2(model.img2img_start_latents, ref_start), rel_l2(out.images, ref), cosine(out.images, ref)
+    print(f"UniPC img2img strength 0.6 of 10: start rel-L2 {es:.3e}; final rel-L2 {err:.3e} cos {cs:.5f}")
+    assert es < 2e-2                                         # the encoder's gate of tests/test_img2img_gpu.py (ENC_TOL)
+    assert err < FREE_TOL and cs > FREE_COS
+
+
+def test_deepcache_interval_2(env):
+    from oracle.pipeline import sample_loop
+    from oracle.unet import DeepCacheState
+    from sonicdiffusionbayeslab_amd.deepcache import DeepCacheSDHelper
+    cfg, sd, model = env
+    lat, pe, ne = synth_inputs(cfg, 1, seed=77)
+    helper = DeepCacheSDHelper(pipe=model)
+    helper.set_params(cache_interval=2, cache_branch_id=0)
+    helper.enable()
+    try:
+        out, _, _ = _plain_call(model, lat, pe, ne)
+    finally:
+        helper.disable()
+    dc = DeepCacheState(cache_interval=2, cache_branch_id=0, enabled=True)
+    ref, _, _, _ = sample_loop(sd, oracle_cfg(cfg), UniPCOracle(**UNI_KW), pe, ne, lat, N_FREE, GS, deepcache=dc)
+    plain, _, _, _ = sample_loop(sd, oracle_cfg(cfg), UniPCOracle(**UNI_KW), pe, ne, lat, N_FREE, GS)
+    err, cs = rel_l2(out.images, ref), cosine(out.images, ref)
+    print(f"UniPC + DeepCache interval 2: rel-L2 {err:.3e} cos {cs:.5f}; cached vs plain oracle {rel_l2(ref, plain):.3e}")
+    assert err < FREE_TOL and cs > FREE_COS and model._deepcache is None
+
+
+def test_tgate_at_step_3(env):
+    from tests import tgate_oracle as tg
+    cfg, sd, model = env
+    lat, pe, ne = synth_inputs(cfg, 1, seed=79)
+    model.enable_tgate(3)
+    try:
+        out, _, _ = _plain_call(model, lat, pe, ne)
+        again, _, _ = _plain_call(model, lat, pe, ne)
+    finally:
+        model.disable_tgate()
+    with torch.no_grad():
+        ref = tg.sample_loop(sd, oracle_cfg(cfg), UniPCOracle(**UNI_KW), pe, ne, lat, N_FREE, GS, 3)
+    err, cs = rel_l2(out.images, ref), cosine(out.images, ref)
+    print(f"UniPC + T-GATE at step 3: rel-L2 {err:.3e} cos {cs:.5f}")
+    assert torch.equal(again.images, out.images)
+    assert err < FREE_TOL and cs > FREE_COS
+
+
+# ------------------------------------------------------------------------------------------------ 4. launch count
+ALLOCATION_AND_VIEWS = ("empty", "slice", "select", "view", "alias", "detach", "as_strided", "unsqueeze", "squeeze", "expand",
+                        "reshape", "narrow", "split", "chunk", "unbind", "t.default", "transpose", "permute", "lift_fresh",
+                        "_local_scalar_dense", "item")
+
+
+def test_one_step_launch_per_step_and_no_torch_arithmetic_on_the_latents(env, monkeypatch):
+    """Each step of an 8-step call is ONE sd_sched_step_pc launch (no sd_sched_step), and between the UNet's output and the next
+    UNet's input no torch operator runs but allocations and views (recorded with a TorchDispatchMode round ``step_fused``)."""
+    from torch.utils._python_dispatch import TorchDispatchMode
+    from sonicdiffusionbayeslab_amd import schedulers as S
+    cfg, sd, model = env
+    lat, pe, ne = synth_inputs(cfg, 2, seed=81)
+    calls = {"pc": 0, "step": 0, "fused": 0}
+    ops = []
+    launch_pc, launch, step_fused = S.UniPCScheduler._launch_pc, S._FusedStepScheduler._launch, S.UniPCScheduler.step_fused
+
+    def count_pc(*a, **k):
+        calls["pc"] += 1
+        return launch_pc(*a, **k)
+
+    def count_step(*a, **k):
+        calls["step"] += 1
+        return launch(*a, **k)
+
+    class Record(TorchDispatchMode):
+        def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+            ops.append(str(func))
+            return func(*args, **(kwargs or {}))
+
+    def recorded(self, *a, **k):
+        calls["fused"] += 1
+        with Record():
+            return step_fused(self, *a, **k)
+
+    monkeypatch.setattr(S.UniPCScheduler, "_launch_pc", staticmethod(count_pc))
+    monkeypatch.setattr(S._FusedStepScheduler, "_launch", staticmethod(count_step))
+    monkeypatch.setattr(S.UniPCScheduler, "step_fused", recorded)
+    out, _, _ = _plain_call(model, lat, pe, ne)
+    assert calls == {"pc": N_FREE, "step": 0, "fused": N_FREE}, calls
+    arithmetic = [o for o in ops if not any(w in o for w in ALLOCATION_AND_VIEWS)]
+    print(f"torch operators inside the {N_FREE} steps: {sorted(set(ops))}")
+    assert not arithmetic, sorted(set(arithmetic))
+    assert any("empty" in o for o in ops)                             # (the recorder saw the steps' allocations)
+    monkeypatch.undo()
+    plain, _, _ = _plain_call(model, lat, pe, ne)
+    assert torch.equal(plain.images, out.images)
