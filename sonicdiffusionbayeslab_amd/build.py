@@ -23,7 +23,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libsdhip.so")
 ABLATE_LIB_PATH = os.path.join(LIB_DIR, "libsdhip_ablate.so")
 ABLATE_SOURCES = ("gemm_conv.hip", "conv_halo.hip")     # the translation units with SD_ABLATE code
-SOURCES = ["gemm_conv.hip", "gemm_lean.hip", "conv_halo.hip", "conv64.hip", "norm.hip", "attention.hip", "xattn.hip", "ip_xattn.hip", "small.hip", "clip.hip", "vit.hip", "bert.hip", "inception.hip", "unet.hip", "pack.hip", "plan.hip", "taesd.hip", "tome.hip", "freeu.hip", "tgate.hip", "ops.hip"]
+SOURCES = ["gemm_conv.hip", "gemm_lean.hip", "conv_halo.hip", "conv64.hip", "norm.hip", "attention.hip", "xattn.hip", "ip_xattn.hip", "small.hip", "sched.hip", "clip.hip", "vit.hip", "bert.hip", "inception.hip", "unet.hip", "pack.hip", "plan.hip", "taesd.hip", "tome.hip", "freeu.hip", "tgate.hip", "ops.hip"]
 HEADERS = ["common.h", "kernels.h", "model.h",os.path.join("..", "..", "include", "sd_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # No packed fp32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) in these units: hipcc broadcasts a scalar
@@ -43,7 +43,7 @@ EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-ffinite-m
                # into the op_sel form is written as a scalar add in the source, and the lint holds the unit to that)
                "xattn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
                "ip_xattn.hip": NO_PACKED_FP32,      # (scalar fp32 normalisation / softmax beside its MFMAs)
-               "small.hip": NO_PACKED_FP32, "clip.hip": NO_PACKED_FP32, "vit.hip": NO_PACKED_FP32, "bert.hip": NO_PACKED_FP32, "norm.hip": NO_PACKED_FP32,      # (HBM-bound elementwise kernels)
+               "small.hip": NO_PACKED_FP32, "sched.hip": NO_PACKED_FP32, "clip.hip": NO_PACKED_FP32, "vit.hip": NO_PACKED_FP32, "bert.hip": NO_PACKED_FP32, "norm.hip": NO_PACKED_FP32,      # (HBM-bound elementwise kernels)
                # the FID Inception convs, pools and preprocessing: scalar fp32 epilogues beside MFMAs, nothing gains from packing
                "inception.hip": NO_PACKED_FP32,
                # the 64-channel conv and the tiny autoencoder's entry / exit: scalar fp32 epilogues (bias, residual, ReLU) beside MFMAs

@@ -356,29 +356,23 @@ int sd_launch_vae_posterior(const float* moments, const float* noise, float scal
 int sd_launch_conv_out(const bf16_t* x, const bf16_t* Wp /*[Cout][9][Cin]*/, const float* bias, float* y, int B,
                        int H, int W, int Cin, int Cout, hipStream_t stream);
 
-// fused CFG combine + linear multistep scheduler update (DDIM / DPM-Solver(++) / LCM)
+// sched.hip: fused CFG combine + linear multistep scheduler update (DDIM / DPM-Solver(++) / LCM / PNDM)
 struct StepCoef {
     float px, pe, p1, p2, pn;  // prev = px*x + pe*eps + p1*m1 + p2*m2 + p3*m3 + pn*noise
     float yx, ye;              // y2   = yx*x + ye*eps           (x0_pred / denoised)
     float mx, me;              // m0   = mx*x + me*eps           (history entry)
     float p3;                  // third history term (PNDM/PLMS order 4)
 };
-int sd_launch_sched_step(const float* eps, int cfg, float guidance, const float* x, const float* m1,
+// k given: e := k[i / n_per_sample] * e (after the CFG combine, before every use).  init given: prev := mask ? prev :
+// a * init + s * blend_noise; mask [n / n_per_sample][hw] fp32 0 / 1, broadcast over the n_per_sample / hw channels of its
+// sample.  Neither: n_per_sample is not read.  `who`: the entry's name, the prefix of every refusal.
+int sd_launch_sched_step(const char* who, const float* eps, int cfg, float guidance, const float* x, const float* m1,
                          const float* m2, const float* m3, const float* noise, float* prev, float* y2, float* m_out,
-                         StepCoef c, long n, hipStream_t stream);
+                         StepCoef c, const float* k, long n_per_sample, long n, const float* init, const float* blend_noise,
+                         const float* mask, float a, float s, long hw, hipStream_t stream);
 // guidance_rescale: k_out[b] = r * std(c_b) / std(g_b) + (1 - r), g = u + s (c - u); eps = [u: batch | c: batch] samples
 int sd_launch_cfg_rescale_factors(const float* eps, int batch, long n_per_sample, float guidance, float rescale, float* k_out,
                                   hipStream_t stream);
-// sd_launch_sched_step with e := k[i / n_per_sample] * e (after the CFG combine, before every use)
-int sd_launch_sched_step_rescaled(const float* eps, int cfg, float guidance, const float* x, const float* m1,
-                                  const float* m2, const float* m3, const float* noise, float* prev, float* y2,
-                                  float* m_out, StepCoef c, const float* k, long n_per_sample, long n, hipStream_t stream);
-// sd_launch_sched_step (k null) / sd_launch_sched_step_rescaled with prev := mask ? prev : a * init + s * blend_noise;
-// mask [n / n_per_sample][hw] fp32 0 / 1, broadcast over the n_per_sample / hw channels of its sample
-int sd_launch_sched_step_inpaint(const float* eps, int cfg, float guidance, const float* x, const float* m1,
-                                 const float* m2, const float* m3, const float* noise, float* prev, float* y2,
-                                 float* m_out, StepCoef c, const float* k, long n_per_sample, long n, const float* init,
-                                 const float* blend_noise, const float* mask, float a, float s, long hw, hipStream_t stream);
 // UniPC's predictor-corrector step (include/sd_hip.h::sd_sched_step_pc): corrector, predictor, history entry, x0 and the
 // optional rescale / latent blend in one launch
 struct PcCoef {

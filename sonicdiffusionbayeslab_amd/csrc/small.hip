@@ -1,6 +1,6 @@
 // Small gfx950 kernels around the UNet body: timestep embedding (sinusoid + M=1 GEMV chain),
-// conv_in (NCHW fp32 latents -> NHWC bf16, CFG batch duplication fused), conv_out (NHWC bf16 ->
-// NCHW fp32 noise prediction) and the fused CFG-combine + scheduler.step update.
+// conv_in (NCHW fp32 latents -> NHWC bf16, CFG batch duplication fused) and conv_out (NHWC bf16 ->
+// NCHW fp32 noise prediction).  (The fused CFG-combine + scheduler.step update is sched.hip.)
 #include "common.h"
 #include "kernels.h"
 
@@ -401,218 +401,6 @@ __global__ __launch_bounds__(256) void conv_out_mfma_kernel(const bf16_t* __rest
     }
 }
 
-// ---- fused CFG + scheduler update ---------------------------------------------------------
-__global__ void sched_step_kernel(const float* __restrict__ eps, int cfg, float guidance,
-                                  const float* __restrict__ x, const float* __restrict__ m1,
-                                  const float* __restrict__ m2, const float* __restrict__ m3,
-                                  const float* __restrict__ noise, float* __restrict__ prev,
-                                  float* __restrict__ y2, float* __restrict__ m_out, StepCoef c, long n4) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    f32x4 e = ((const f32x4*)eps)[i];
-    if (cfg) {
-        const f32x4 et = ((const f32x4*)eps)[i + n4];
-        e = e + guidance * (et - e);
-    }
-    const f32x4 xv = ((const f32x4*)x)[i];
-    f32x4 p = c.px * xv + c.pe * e;
-    if (m1) p += c.p1 * ((const f32x4*)m1)[i];
-    if (m2) p += c.p2 * ((const f32x4*)m2)[i];
-    if (m3) p += c.p3 * ((const f32x4*)m3)[i];
-    if (noise) p += c.pn * ((const f32x4*)noise)[i];
-    if (y2) ((f32x4*)y2)[i] = c.yx * xv + c.ye * e;
-    if (m_out) ((f32x4*)m_out)[i] = c.mx * xv + c.me * e;
-    ((f32x4*)prev)[i] = p;
-}
-
-// ---- rescaled CFG (guidance_rescale): per-sample factor k_b, then the step with e := k_b * e ---------------------------
-// g = u + s (c - u) is formed exactly as the step below forms it (same expression, same unit), so the std the factor sees
-// is the std of the values the step scales.  One block per sample, fixed thread -> element assignment, double partials,
-// wave butterflies and an in-order sum of the wave partials: k_b depends on sample b's data and n_per_sample only (not on
-// the batch, the sample's position or the grid) -- dist.py's sharding invariant.  Two passes (mean, then centred sum).
-constexpr int RESCALE_THREADS = 512;
-
-__device__ __forceinline__ f32x4 cfg_combine(f32x4 e, f32x4 et, float guidance) { return e + guidance * (et - e); }
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// in-order block sum of two doubles; every thread gets the totals
-__device__ __forceinline__ void block_sum2_f64(double& a, double& b, double (*red)[RESCALE_THREADS / 64]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    a = wave_sum_f64(a);
-    b = wave_sum_f64(b);
-    if (lane == 0) {
-        red[0][wave] = a;
-        red[1][wave] = b;
-    }
-    __syncthreads();
-    a = 0.0;
-    b = 0.0;
-#pragma unroll
-    for (int w = 0; w < RESCALE_THREADS / 64; ++w) {
-        a += red[0][w];
-        b += red[1][w];
-    }
-    __syncthreads();
-}
-
-__global__ __launch_bounds__(RESCALE_THREADS) void cfg_rescale_factors_kernel(const float* __restrict__ eps, int batch,
-                                                                              long n4s, float guidance, float rescale,
-                                                                              float* __restrict__ k_out) {
-    __shared__ double red[2][RESCALE_THREADS / 64];
-    const int b = blockIdx.x;
-    const f32x4* u = (const f32x4*)eps + (long)b * n4s;
-    const f32x4* c = (const f32x4*)eps + ((long)batch + b) * n4s;
-    double sc = 0.0, sg = 0.0;
-    for (long i = threadIdx.x; i < n4s; i += RESCALE_THREADS) {
-        const f32x4 et = c[i], g = cfg_combine(u[i], et, guidance);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            sc += (double)et[j];
-            sg += (double)g[j];
-        }
-    }
-    block_sum2_f64(sc, sg, red);
-    const double n = 4.0 * (double)n4s;
-    const double mc = sc / n, mg = sg / n;
-    double qc = 0.0, qg = 0.0;
-    for (long i = threadIdx.x; i < n4s; i += RESCALE_THREADS) {
-        const f32x4 et = c[i], g = cfg_combine(u[i], et, guidance);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const double dc = (double)et[j] - mc, dg = (double)g[j] - mg;
-            qc += dc * dc;
-            qg += dg * dg;
-        }
-    }
-    block_sum2_f64(qc, qg, red);
-    // std(c) / std(g): the (n - 1) of torch.std cancels in the ratio
-    if (threadIdx.x == 0) k_out[b] = (float)((double)rescale * sqrt(qc / qg) + (1.0 - (double)rescale));
-}
-
-// sched_step_kernel with the CFG-combined prediction scaled by its sample's factor: e := k[b] * e before every use
-__global__ void sched_step_rescaled_kernel(const float* __restrict__ eps, int cfg, float guidance,
-                                           const float* __restrict__ x, const float* __restrict__ m1,
-                                           const float* __restrict__ m2, const float* __restrict__ m3,
-                                           const float* __restrict__ noise, float* __restrict__ prev,
-                                           float* __restrict__ y2, float* __restrict__ m_out, StepCoef c,
-                                           const float* __restrict__ k, long n4s, long n4) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    f32x4 e = ((const f32x4*)eps)[i];
-    if (cfg) e = cfg_combine(e, ((const f32x4*)eps)[i + n4], guidance);
-    e = k[i / n4s] * e;
-    const f32x4 xv = ((const f32x4*)x)[i];
-    f32x4 p = c.px * xv + c.pe * e;
-    if (m1) p += c.p1 * ((const f32x4*)m1)[i];
-    if (m2) p += c.p2 * ((const f32x4*)m2)[i];
-    if (m3) p += c.p3 * ((const f32x4*)m3)[i];
-    if (noise) p += c.pn * ((const f32x4*)noise)[i];
-    if (y2) ((f32x4*)y2)[i] = c.yx * xv + c.ye * e;
-    if (m_out) ((f32x4*)m_out)[i] = c.mx * xv + c.me * e;
-    ((f32x4*)prev)[i] = p;
-}
-
-// ---- inpainting with a 4-channel UNet: the step and the latent blend in one launch --------------------------------------
-// prev = mask ? step : a * init + s * blend_noise, mask [B][1][hw] broadcast over the channels.  The step side is
-// sched_step_kernel's (RESCALED: sched_step_rescaled_kernel's) expression, statement for statement; y2 and m_out do not see
-// the mask.  s == 0 (after the last step: a = 1) skips the noise term, so the kept side is then a * init alone.
-template <bool RESCALED>
-__global__ void sched_step_inpaint_kernel(const float* __restrict__ eps, int cfg, float guidance,
-                                          const float* __restrict__ x, const float* __restrict__ m1,
-                                          const float* __restrict__ m2, const float* __restrict__ m3,
-                                          const float* __restrict__ noise, float* __restrict__ prev,
-                                          float* __restrict__ y2, float* __restrict__ m_out, StepCoef c,
-                                          const float* __restrict__ k, long n4s, long n4, const float* __restrict__ init,
-                                          const float* __restrict__ blend_noise, const float* __restrict__ mask, float a,
-                                          float s, long hw4) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    f32x4 e = ((const f32x4*)eps)[i];
-    if (RESCALED) {
-        if (cfg) e = cfg_combine(e, ((const f32x4*)eps)[i + n4], guidance);
-        e = k[i / n4s] * e;
-    } else if (cfg) {
-        const f32x4 et = ((const f32x4*)eps)[i + n4];
-        e = e + guidance * (et - e);
-    }
-    const f32x4 xv = ((const f32x4*)x)[i];
-    f32x4 p = c.px * xv + c.pe * e;
-    if (m1) p += c.p1 * ((const f32x4*)m1)[i];
-    if (m2) p += c.p2 * ((const f32x4*)m2)[i];
-    if (m3) p += c.p3 * ((const f32x4*)m3)[i];
-    if (noise) p += c.pn * ((const f32x4*)noise)[i];
-    if (y2) ((f32x4*)y2)[i] = c.yx * xv + c.ye * e;
-    if (m_out) ((f32x4*)m_out)[i] = c.mx * xv + c.me * e;
-    const long b = i / n4s;
-    const f32x4 mk = ((const f32x4*)mask)[b * hw4 + (i - b * n4s) % hw4];
-    f32x4 keep = a * ((const f32x4*)init)[i];
-    if (s != 0.f) keep += s * ((const f32x4*)blend_noise)[i];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) p[j] = mk[j] >= 0.5f ? p[j] : keep[j];
-    ((f32x4*)prev)[i] = p;
-}
-
-// ---- UniPC: corrector and predictor of one step in one launch -----------------------------------------------------------
-// e as the kernels above form it (RESCALED: cfg_combine, then k[b]; else sched_step_kernel's expression), then
-//   m_t  = cm0 x + cm1 e                                        (history entry)
-//   y2   = cy0 x + cy1 e                                        (x0 prediction)
-//   xc   = cc0 x_last + cc1 h1 + cc2 h2 + cc3 h3 + cc4 m_t      (corrector; x_last null: xc = x, the bits of x)
-//   prev = cp0 xc + cp1 m_t + cp2 h1 + cp3 h2                   (predictor)
-// and BLEND: sched_step_inpaint_kernel's blend of prev.  Terms are added left to right; a null h term is skipped (the host
-// side has checked that its coefficients are 0).  x_corr, y2 and m_out do not see the mask.
-template <bool RESCALED, bool BLEND>
-__global__ void sched_step_pc_kernel(const float* __restrict__ eps, int cfg, float guidance, const float* __restrict__ x,
-                                     const float* __restrict__ x_last, const float* __restrict__ h1,
-                                     const float* __restrict__ h2, const float* __restrict__ h3, float* __restrict__ prev,
-                                     float* __restrict__ x_corr, float* __restrict__ y2, float* __restrict__ m_out,
-                                     PcCoef c, const float* __restrict__ k, long n4s, long n4,
-                                     const float* __restrict__ init, const float* __restrict__ blend_noise,
-                                     const float* __restrict__ mask, float a, float s, long hw4) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    f32x4 e = ((const f32x4*)eps)[i];
-    if (RESCALED) {
-        if (cfg) e = cfg_combine(e, ((const f32x4*)eps)[i + n4], guidance);
-        e = k[i / n4s] * e;
-    } else if (cfg) {
-        const f32x4 et = ((const f32x4*)eps)[i + n4];
-        e = e + guidance * (et - e);
-    }
-    const f32x4 xv = ((const f32x4*)x)[i];
-    const f32x4 mt = c.cm[0] * xv + c.cm[1] * e;
-    f32x4 v1 = {0.f, 0.f, 0.f, 0.f}, v2 = v1;
-    if (h1) v1 = ((const f32x4*)h1)[i];
-    if (h2) v2 = ((const f32x4*)h2)[i];
-    f32x4 xc = xv;
-    if (x_last) {
-        xc = c.cc[0] * ((const f32x4*)x_last)[i];
-        if (h1) xc += c.cc[1] * v1;
-        if (h2) xc += c.cc[2] * v2;
-        if (h3) xc += c.cc[3] * ((const f32x4*)h3)[i];
-        xc += c.cc[4] * mt;
-    }
-    f32x4 p = c.cp[0] * xc + c.cp[1] * mt;
-    if (h1) p += c.cp[2] * v1;
-    if (h2) p += c.cp[3] * v2;
-    if (x_corr) ((f32x4*)x_corr)[i] = xc;
-    if (y2) ((f32x4*)y2)[i] = c.cy[0] * xv + c.cy[1] * e;
-    if (m_out) ((f32x4*)m_out)[i] = mt;
-    if (BLEND) {
-        const long b = i / n4s;
-        const f32x4 mk = ((const f32x4*)mask)[b * hw4 + (i - b * n4s) % hw4];
-        f32x4 keep = a * ((const f32x4*)init)[i];
-        if (s != 0.f) keep += s * ((const f32x4*)blend_noise)[i];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) p[j] = mk[j] >= 0.5f ? p[j] : keep[j];
-    }
-    ((f32x4*)prev)[i] = p;
-}
-
 __global__ void f32_to_bf16_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, long n4) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
@@ -983,128 +771,6 @@ int sd_launch_conv_out(const bf16_t* x, const bf16_t* Wp, const float* bias, flo
     }
     hipLaunchKernelGGL(conv_out_kernel, dim3((unsigned)((npix + 3) / 4)), dim3(256), 0, stream, x, Wp, bias, y, B, H, W,
                        Cin, Cout);
-    SD_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-int sd_launch_sched_step(const float* eps, int cfg, float guidance, const float* x, const float* m1,
-                         const float* m2, const float* m3, const float* noise, float* prev, float* y2, float* m_out,
-                         StepCoef c, long n, hipStream_t stream) {
-    SD_REQUIRE(eps && x && prev, "sched_step: null operand");
-    SD_REQUIRE(n > 0 && n % 4 == 0, "sched_step: n=%ld must be a positive multiple of 4", n);
-    const long n4 = n / 4;
-    hipLaunchKernelGGL(sched_step_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, eps, cfg, guidance,
-                       x, m1, m2, m3, noise, prev, y2, m_out, c, n4);
-    SD_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-int sd_launch_cfg_rescale_factors(const float* eps, int batch, long n_per_sample, float guidance, float rescale, float* k_out,
-                                  hipStream_t stream) {
-    SD_REQUIRE(eps && k_out, "cfg_rescale_factors: null operand");
-    SD_REQUIRE(batch > 0 && batch <= 65535, "cfg_rescale_factors: batch=%d", batch);
-    SD_REQUIRE(n_per_sample >= 4 && n_per_sample % 4 == 0,
-               "cfg_rescale_factors: n_per_sample=%ld must be a positive multiple of 4", n_per_sample);
-    hipLaunchKernelGGL(cfg_rescale_factors_kernel, dim3(batch), dim3(RESCALE_THREADS), 0, stream, eps, batch,
-                       n_per_sample / 4, guidance, rescale, k_out);
-    SD_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-int sd_launch_sched_step_rescaled(const float* eps, int cfg, float guidance, const float* x, const float* m1,
-                                  const float* m2, const float* m3, const float* noise, float* prev, float* y2,
-                                  float* m_out, StepCoef c, const float* k, long n_per_sample, long n, hipStream_t stream) {
-    SD_REQUIRE(eps && x && prev && k, "sched_step_rescaled: null operand");
-    SD_REQUIRE(n > 0 && n % 4 == 0, "sched_step_rescaled: n=%ld must be a positive multiple of 4", n);
-    SD_REQUIRE(n_per_sample > 0 && n_per_sample % 4 == 0 && n % n_per_sample == 0,
-               "sched_step_rescaled: n_per_sample=%ld must be a positive multiple of 4 dividing n=%ld", n_per_sample, n);
-    const long n4 = n / 4;
-    hipLaunchKernelGGL(sched_step_rescaled_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, eps, cfg,
-                       guidance, x, m1, m2, m3, noise, prev, y2, m_out, c, k, n_per_sample / 4, n4);
-    SD_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-int sd_launch_sched_step_inpaint(const float* eps, int cfg, float guidance, const float* x, const float* m1,
-                                 const float* m2, const float* m3, const float* noise, float* prev, float* y2,
-                                 float* m_out, StepCoef c, const float* k, long n_per_sample, long n, const float* init,
-                                 const float* blend_noise, const float* mask, float a, float s, long hw, hipStream_t stream) {
-    SD_REQUIRE(eps && x && prev && init && mask, "sched_step_inpaint: null operand");
-    SD_REQUIRE(blend_noise || s == 0.f, "sched_step_inpaint: s=%g needs blend_noise", (double)s);
-    SD_REQUIRE(n > 0 && n % 4 == 0, "sched_step_inpaint: n=%ld must be a positive multiple of 4", n);
-    SD_REQUIRE(hw > 0 && hw % 4 == 0, "sched_step_inpaint: hw=%ld must be a positive multiple of 4", hw);
-    SD_REQUIRE(n_per_sample > 0 && n_per_sample % hw == 0 && n % n_per_sample == 0,
-               "sched_step_inpaint: n_per_sample=%ld must be a multiple of hw=%ld dividing n=%ld", n_per_sample, hw, n);
-    const long n4 = n / 4;
-    const dim3 grid((unsigned)((n4 + 255) / 256));
-    if (k)
-        hipLaunchKernelGGL(sched_step_inpaint_kernel<true>, grid, dim3(256), 0, stream, eps, cfg, guidance, x, m1, m2, m3, noise,
-                           prev, y2, m_out, c, k, n_per_sample / 4, n4, init, blend_noise, mask, a, s, hw / 4);
-    else
-        hipLaunchKernelGGL(sched_step_inpaint_kernel<false>, grid, dim3(256), 0, stream, eps, cfg, guidance, x, m1, m2, m3, noise,
-                           prev, y2, m_out, c, k, n_per_sample / 4, n4, init, blend_noise, mask, a, s, hw / 4);
-    SD_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-// [p, p + bytes) and [q, q + bytes_q) share a byte
-static bool pc_overlap(const void* p, size_t bytes, const void* q, size_t bytes_q) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return p && q && a < b + bytes_q && b < a + bytes;
-}
-
-int sd_launch_sched_step_pc(const float* eps, int cfg, float guidance, const float* x, const float* x_last, const float* h1,
-                            const float* h2, const float* h3, float* prev, float* x_corr, float* y2, float* m_out, PcCoef c,
-                            const float* k, long n_per_sample, long n, const float* init, const float* blend_noise,
-                            const float* mask, float a, float s, long hw, hipStream_t stream) {
-    SD_REQUIRE(eps && x && prev, "sched_step_pc: null operand");
-    SD_REQUIRE(n > 0 && n % 4 == 0, "sched_step_pc: n=%ld must be a positive multiple of 4", n);
-    SD_REQUIRE(n_per_sample > 0 && n_per_sample % 4 == 0 && n % n_per_sample == 0,
-               "sched_step_pc: n_per_sample=%ld must be a positive multiple of 4 dividing n=%ld", n_per_sample, n);
-    if (init) {
-        SD_REQUIRE(mask, "sched_step_pc: null operand (mask)");
-        SD_REQUIRE(blend_noise || s == 0.f, "sched_step_pc: s=%g needs blend_noise", (double)s);
-        SD_REQUIRE(hw > 0 && hw % 4 == 0, "sched_step_pc: hw=%ld must be a positive multiple of 4", hw);
-        SD_REQUIRE(n_per_sample % hw == 0, "sched_step_pc: n_per_sample=%ld must be a multiple of hw=%ld", n_per_sample, hw);
-        SD_REQUIRE(std::isfinite(a) && std::isfinite(s), "sched_step_pc: blend coefficients a=%g s=%g must be finite",
-                   (double)a, (double)s);
-    }
-    SD_REQUIRE(std::isfinite(guidance), "sched_step_pc: guidance=%g must be finite", (double)guidance);
-    const float* rows[4] = {c.cm, c.cy, c.cc, c.cp};
-    const char* row_names[4] = {"cm", "cy", "cc", "cp"};
-    const int row_len[4] = {2, 2, 5, 4};
-    for (int r = 0; r < 4; ++r)
-        for (int j = 0; j < row_len[r]; ++j)
-            SD_REQUIRE(std::isfinite(rows[r][j]), "sched_step_pc: coefficient %s[%d]=%g must be finite", row_names[r], j,
-                       (double)rows[r][j]);
-    // a null history entry carries no weight (the corrector's row is not read without x_last)
-    SD_REQUIRE(h1 || (c.cp[2] == 0.f && (!x_last || c.cc[1] == 0.f)), "sched_step_pc: h1 is null but has a coefficient");
-    SD_REQUIRE(h2 || (c.cp[3] == 0.f && (!x_last || c.cc[2] == 0.f)), "sched_step_pc: h2 is null but has a coefficient");
-    SD_REQUIRE(h3 || !x_last || c.cc[3] == 0.f, "sched_step_pc: h3 is null but has a coefficient");
-    const size_t nb = (size_t)n * 4, batch = (size_t)(n / n_per_sample);
-    const void* outs[4] = {prev, x_corr, y2, m_out};
-    const char* out_names[4] = {"prev", "x_corr", "y2", "m_out"};
-    const void* ins[10] = {eps, x, x_last, h1, h2, h3, k, init, blend_noise, mask};
-    const char* in_names[10] = {"eps", "x", "x_last", "h1", "h2", "h3", "k", "init", "blend_noise", "mask"};
-    const size_t in_bytes[10] = {cfg ? 2 * nb : nb, nb, nb, nb, nb, nb, batch * 4, nb, nb, init ? batch * (size_t)hw * 4 : 0};
-    for (int o = 0; o < 4; ++o) {
-        for (int j = 0; j < 10; ++j)
-            SD_REQUIRE(!pc_overlap(outs[o], nb, ins[j], in_bytes[j]), "sched_step_pc: output %s aliases input %s", out_names[o],
-                       in_names[j]);
-        for (int q = 0; q < o; ++q)
-            SD_REQUIRE(!pc_overlap(outs[o], nb, outs[q], nb), "sched_step_pc: output %s aliases output %s", out_names[o],
-                       out_names[q]);
-    }
-    const long n4 = n / 4, n4s = n_per_sample / 4, hw4 = init ? hw / 4 : 1;
-    const dim3 grid((unsigned)((n4 + 255) / 256));
-#define SD_PC_LAUNCH(R, B)                                                                                                   \
-    hipLaunchKernelGGL((sched_step_pc_kernel<R, B>), grid, dim3(256), 0, stream, eps, cfg, guidance, x, x_last, h1, h2, h3,  \
-                       prev, x_corr, y2, m_out, c, k, n4s, n4, init, blend_noise, mask, a, s, hw4)
-    if (k && init) SD_PC_LAUNCH(true, true);
-    else if (k) SD_PC_LAUNCH(true, false);
-    else if (init) SD_PC_LAUNCH(false, true);
-    else SD_PC_LAUNCH(false, false);
-#undef SD_PC_LAUNCH
     SD_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -1602,52 +1602,6 @@ extern "C" int sd_unet_debug_tensor(sd_unet* u, void* stream, const char* name, 
     return 0;
 }
 
-extern "C" int sd_sched_step(void* stream, const float* eps, int cfg, float guidance, const float* x, const float* m1,
-                             const float* m2, const float* m3, const float* noise, float* prev, float* y2, float* m_out,
-                             const float coef[10], long long n) {
-    SD_REQUIRE(coef, "sched_step: null coefficients");
-    StepCoef c{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7], coef[8], coef[9]};
-    return sd_launch_sched_step(eps, cfg, guidance, x, m1, m2, m3, noise, prev, y2, m_out, c, (long)n, (hipStream_t)stream);
-}
-
-extern "C" int sd_cfg_rescale_factors(void* stream, const float* eps, int batch, long long n_per_sample, float guidance,
-                                      float rescale, float* k_out) {
-    return sd_launch_cfg_rescale_factors(eps, batch, (long)n_per_sample, guidance, rescale, k_out, (hipStream_t)stream);
-}
-
-extern "C" int sd_sched_step_rescaled(void* stream, const float* eps, int cfg, float guidance, const float* x,
-                                      const float* m1, const float* m2, const float* m3, const float* noise, float* prev,
-                                      float* y2, float* m_out, const float coef[10], long long n, const float* k,
-                                      long long n_per_sample) {
-    SD_REQUIRE(coef, "sched_step_rescaled: null coefficients");
-    StepCoef c{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7], coef[8], coef[9]};
-    return sd_launch_sched_step_rescaled(eps, cfg, guidance, x, m1, m2, m3, noise, prev, y2, m_out, c, k, (long)n_per_sample,
-                                         (long)n, (hipStream_t)stream);
-}
-
-extern "C" int sd_sched_step_inpaint(void* stream, const float* eps, int cfg, float guidance, const float* x, const float* m1,
-                                     const float* m2, const float* m3, const float* noise, float* prev, float* y2,
-                                     float* m_out, const float coef[10], long long n, const float* k, long long n_per_sample,
-                                     const float* init, const float* blend_noise, const float* mask, float a, float s,
-                                     long long hw) {
-    SD_REQUIRE(coef, "sched_step_inpaint: null coefficients");
-    StepCoef c{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7], coef[8], coef[9]};
-    return sd_launch_sched_step_inpaint(eps, cfg, guidance, x, m1, m2, m3, noise, prev, y2, m_out, c, k, (long)n_per_sample,
-                                        (long)n, init, blend_noise, mask, a, s, (long)hw, (hipStream_t)stream);
-}
-
-extern "C" int sd_sched_step_pc(void* stream, const float* eps, int cfg, float guidance, const float* x, const float* x_last,
-                                const float* h1, const float* h2, const float* h3, float* prev, float* x_corr, float* y2,
-                                float* m_out, const float coef[13], long long n, const float* k, long long n_per_sample,
-                                const float* init, const float* blend_noise, const float* mask, float a, float s,
-                                long long hw) {
-    SD_REQUIRE(coef, "sched_step_pc: null coefficients");
-    PcCoef c{{coef[0], coef[1]}, {coef[2], coef[3]}, {coef[4], coef[5], coef[6], coef[7], coef[8]},
-             {coef[9], coef[10], coef[11], coef[12]}};
-    return sd_launch_sched_step_pc(eps, cfg, guidance, x, x_last, h1, h2, h3, prev, x_corr, y2, m_out, c, k, (long)n_per_sample,
-                                   (long)n, init, blend_noise, mask, a, s, (long)hw, (hipStream_t)stream);
-}
-
 extern "C" int sd_inpaint_prepare(void* stream, const float* image, const float* mask, float* masked_image, float* latent_mask,
                                   int batch, int height, int width) {
     return sd_launch_inpaint_prepare(image, mask, masked_image, latent_mask, batch, height, width, (hipStream_t)stream);

@@ -123,6 +123,8 @@ class _FusedStepScheduler:
         cfg.update(kwargs)
         self.config = SchedulerConfig(cfg)
         self.alphas_cumprod = _alphas_cumprod_fp32(self.config)      # fp32 table, as upstream
+        if "set_alpha_to_one" in self.config:                        # (DDIM, LCM, PNDM: alpha_bar before the first timestep)
+            self.final_alpha_cumprod = 1.0 if self.config.set_alpha_to_one else float(self.alphas_cumprod[0])
         self.timesteps: Optional[torch.Tensor] = None
         self.num_inference_steps: Optional[int] = None
         self._timesteps_list: List[int] = []
@@ -169,23 +171,17 @@ class _FusedStepScheduler:
         y2 = torch.empty_like(x) if want_y2 else None
         mo = torch.empty_like(x) if want_m else None
         c10 = [float(v) for v in coef] + [0.0] * (10 - len(coef))
-        carr = (C.c_float * 10)(*c10)
+        head = (_lib.current_stream(), eps.data_ptr(), int(cfg), float(guidance), x.data_ptr(), _lib.ptr(m1), _lib.ptr(m2),
+                _lib.ptr(m3), _lib.ptr(noise), prev.data_ptr(), _lib.ptr(y2), _lib.ptr(mo), (C.c_float * 10)(*c10), n)
         if blend is not None:
             init, bnoise, mask, a, s = blend
-            _lib.check(lib.sd_sched_step_inpaint(_lib.current_stream(), eps.data_ptr(), int(cfg), float(guidance), x.data_ptr(),
-                                                 _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(m3), _lib.ptr(noise), prev.data_ptr(),
-                                                 _lib.ptr(y2), _lib.ptr(mo), carr, n, _lib.ptr(k), n // x.shape[0],
-                                                 init.data_ptr(), bnoise.data_ptr(), mask.data_ptr(), float(a), float(s),
-                                                 mask.numel() // mask.shape[0]), "sd_sched_step_inpaint")
-        elif k is None:
-            _lib.check(lib.sd_sched_step(_lib.current_stream(), eps.data_ptr(), int(cfg), float(guidance), x.data_ptr(),
-                                         _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(m3), _lib.ptr(noise), prev.data_ptr(),
-                                         _lib.ptr(y2), _lib.ptr(mo), carr, n), "sd_sched_step")
+            name, tail = "sd_sched_step_inpaint", (_lib.ptr(k), n // x.shape[0], init.data_ptr(), bnoise.data_ptr(),
+                                                   mask.data_ptr(), float(a), float(s), mask.numel() // mask.shape[0])
+        elif k is not None:
+            name, tail = "sd_sched_step_rescaled", (k.data_ptr(), n // x.shape[0])
         else:
-            _lib.check(lib.sd_sched_step_rescaled(_lib.current_stream(), eps.data_ptr(), int(cfg), float(guidance),
-                                                  x.data_ptr(), _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(m3), _lib.ptr(noise),
-                                                  prev.data_ptr(), _lib.ptr(y2), _lib.ptr(mo), carr, n, k.data_ptr(),
-                                                  n // x.shape[0]), "sd_sched_step_rescaled")
+            name, tail = "sd_sched_step", ()
+        _lib.check(getattr(lib, name)(*head, *tail), name)
         return prev, y2, mo
 
     def _rescale(self, eps, cfg, guidance, guidance_rescale, x):
@@ -223,7 +219,8 @@ class _FusedStepScheduler:
     rescale_factors: Optional[torch.Tensor] = None
 
     def _blend_kw(self, inpaint, x):
-        """``blend=`` of ``_launch`` for an inpainting step; nothing otherwise (the launch is then called as before)."""
+        """``blend=`` of ``_launch`` for an inpainting step; nothing otherwise: a CPU stand-in for ``_launch`` that knows no
+        blend (tests/test_prediction_cpu.py) is then called as before."""
         return {} if inpaint is None else {"blend": self._blend(inpaint, x)}
 
     def _blend(self, inpaint, x):
@@ -286,7 +283,6 @@ class DDIMSchedulerMy(_FusedStepScheduler):
         if self.config.clip_sample or self.config.thresholding:
             raise NotImplementedError("clip_sample / thresholding are not on the hot path")
         self._check_prediction_type()
-        self.final_alpha_cumprod = 1.0 if self.config.set_alpha_to_one else float(self.alphas_cumprod[0])
 
     def set_timesteps(self, num_inference_steps: int, device=None):
         T = self.config.num_train_timesteps
@@ -365,13 +361,44 @@ def karras_schedule(train_sigmas: np.ndarray, n: int, rho: float = 7.0):
 
 class _SigmaTableScheduler(_FusedStepScheduler):
     """What DPM-Solver and UniPC share: the sigma table over the inference timesteps (the three spacings or Karras sigmas,
-    then the final sigma), the zero-terminal-SNR floor, and ``add_noise`` from that table."""
+    then the final sigma), the zero-terminal-SNR floor, ``add_noise`` from that table, and the multistep bookkeeping
+    (``model_outputs`` oldest ... newest, ``lower_order_nums``, the step index)."""
     sigmas: Optional[np.ndarray] = None
+    # with rescale_betas_zero_snr and epsilon prediction: the alpha_bar at or below which ``set_timesteps`` refuses a
+    # schedule.  0.0 is below the 2^-24 that ``_floor_zero_snr`` writes, so it never refuses there.
+    _zero_snr_refusal = 0.0
 
     def _floor_zero_snr(self):
         if self.config.rescale_betas_zero_snr:
             # as upstream: close to 0 without being 0, so that the first sigma is finite
             self.alphas_cumprod[-1] = 2 ** -24
+
+    def _reset(self):
+        self.model_outputs: List[Optional[torch.Tensor]] = [None] * self.config.solver_order
+        self.lower_order_nums = 0
+
+    def set_timesteps(self, num_inference_steps: Optional[int] = None, device=None, timesteps=None):
+        """``timesteps``: custom schedule, as diffusers 0.32.1 accepts it and the two-scheduler pipeline uses it
+        (``src/models.py:488-492``).  ``use_karras_sigmas``: the Karras table of ``karras_schedule`` (upstream-recall)."""
+        ts, self.sigmas = self._sigma_table(num_inference_steps, timesteps)
+        self._refuse_epsilon_at_zero_snr(ts, floor=self._zero_snr_refusal if self.config.rescale_betas_zero_snr else 0.0)
+        self._set(ts, device)
+        self._reset()
+
+    def _begin_step(self, timestep) -> int:
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if self._step_index is None:
+            self._step_index = self._index_of(timestep)
+        return self._step_index
+
+    def _end_step(self, m):
+        """Push the step's history entry (in place: ``models._push_history`` shifts the same list) and advance."""
+        self.model_outputs.pop(0)
+        self.model_outputs.append(m)
+        if self.lower_order_nums < self.config.solver_order:
+            self.lower_order_nums += 1
+        self._step_index += 1
 
     def _sigma_table(self, num_inference_steps: Optional[int], timesteps=None):
         """(timesteps int64, sigmas float32 with the final sigma appended) as upstream's ``set_timesteps`` builds them."""
@@ -451,19 +478,7 @@ class DPMSolverScheduler(_SigmaTableScheduler):
         self._floor_zero_snr()
         if c.solver_order not in (1, 2, 3):
             raise ValueError("solver_order must be 1, 2 or 3")
-        self.model_outputs: List[Optional[torch.Tensor]] = [None] * c.solver_order
-        self.lower_order_nums = 0
-        self.sigmas: Optional[np.ndarray] = None
-
-    def set_timesteps(self, num_inference_steps: Optional[int] = None, device=None, timesteps=None):
-        """``timesteps``: custom schedule, as diffusers 0.32.1 accepts it and the two-scheduler pipeline uses it
-        (``src/models.py:488-492``).  ``use_karras_sigmas``: the Karras table of ``karras_schedule`` (upstream-recall)."""
-        c = self.config
-        ts, self.sigmas = self._sigma_table(num_inference_steps, timesteps)
-        self._refuse_epsilon_at_zero_snr(ts)
-        self._set(ts, device)
-        self.model_outputs = [None] * c.solver_order
-        self.lower_order_nums = 0
+        self._reset()
 
     def _convert_coefs(self, i: int):
         a0, s0, _ = self._alpha_sigma_lambda(float(self.sigmas[i]))
@@ -546,11 +561,7 @@ class DPMSolverScheduler(_SigmaTableScheduler):
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
                    variance_noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0, inpaint=None):
         c = self.config
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
-        if self._step_index is None:
-            self._step_index = self._index_of(timestep)
-        i, n = self._step_index, len(self._timesteps_list)
+        i, n = self._begin_step(timestep), len(self._timesteps_list)
         lower_order_final = (i == n - 1) and (c.euler_at_final or (c.lower_order_final and n < 15)
                                               or c.final_sigmas_type == "zero")
         lower_order_second = (i == n - 2) and c.lower_order_final and n < 15
@@ -576,12 +587,7 @@ class DPMSolverScheduler(_SigmaTableScheduler):
         # (inpainting: the history entry m0 and x0 are taken before the blend, as upstream steps first and blends after)
         prev, x0, m0 = self._launch(e, cfg, guidance_scale, x, m1, m2, z, (px, pe, p1, p2, pn, yx, ye, mx, me),
                                     want_y2=True, want_m=True, k=k, **self._blend_kw(inpaint, x))
-        for k in range(c.solver_order - 1):
-            self.model_outputs[k] = self.model_outputs[k + 1]
-        self.model_outputs[-1] = m0
-        if self.lower_order_nums < c.solver_order:
-            self.lower_order_nums += 1
-        self._step_index += 1
+        self._end_step(m0)
         return prev, x0
 
 
@@ -600,7 +606,6 @@ class LCMScheduler(_FusedStepScheduler):
         if self.config.clip_sample or self.config.thresholding:
             raise NotImplementedError("clip_sample / thresholding are not on the hot path")
         self._check_prediction_type()
-        self.final_alpha_cumprod = 1.0 if self.config.set_alpha_to_one else float(self.alphas_cumprod[0])
 
     def set_timesteps(self, num_inference_steps: int, device=None, original_inference_steps=None):
         c = self.config
@@ -665,7 +670,6 @@ class PNDMScheduler(_FusedStepScheduler):
         if self.config.prediction_type not in ("epsilon", "v_prediction"):       # as upstream's _get_prev_sample
             raise ValueError(f"prediction_type given as {self.config.prediction_type} must be one of `epsilon` or "
                              "`v_prediction`")
-        self.final_alpha_cumprod = 1.0 if self.config.set_alpha_to_one else float(self.alphas_cumprod[0])
         self.ets: List[torch.Tensor] = []
         self.counter = 0
         self.cur_sample = None
@@ -837,6 +841,8 @@ class UniPCScheduler(_SigmaTableScheduler):
                          timestep_spacing="linspace", steps_offset=0, final_sigmas_type="zero",
                          rescale_betas_zero_snr=False, use_karras_sigmas=False)
     _accepted = tuple(_own_defaults)
+    # (the 2^-24 that stands for alpha_bar = 0 is refused like the 0: x0 = (x - sigma eps) / 2^-12 there)
+    _zero_snr_refusal = 2 ** -24
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
@@ -855,17 +861,9 @@ class UniPCScheduler(_SigmaTableScheduler):
         self._reset()
 
     def _reset(self):
-        self.model_outputs: List[Optional[torch.Tensor]] = [None] * self.config.solver_order      # oldest ... newest
+        super()._reset()
         self.last_sample: Optional[torch.Tensor] = None
         self.this_order = 0
-        self.lower_order_nums = 0
-
-    def set_timesteps(self, num_inference_steps: Optional[int] = None, device=None, timesteps=None):
-        ts, self.sigmas = self._sigma_table(num_inference_steps, timesteps)
-        # (the 2^-24 that stands for alpha_bar = 0 is refused like the 0: x0 = (x - sigma eps) / 2^-12 there)
-        self._refuse_epsilon_at_zero_snr(ts, floor=2 ** -24 if self.config.rescale_betas_zero_snr else 0.0)
-        self._set(ts, device)
-        self._reset()
 
     def step_orders(self, i: int):
         """(corrector order or 0, predictor order) of step ``i`` given the state, in upstream's order: the corrector runs
@@ -904,12 +902,7 @@ class UniPCScheduler(_SigmaTableScheduler):
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
                    guidance_rescale: float = 0.0, inpaint=None):
         """``eta`` and ``generator`` are not read (the solver is deterministic)."""
-        c = self.config
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
-        if self._step_index is None:
-            self._step_index = self._index_of(timestep)
-        i = self._step_index
+        i = self._begin_step(timestep)
         order_c, order_p = self.step_orders(i)
         rows = self.rows(i, order_c, order_p)
         newest_first = self.model_outputs[::-1]
@@ -920,12 +913,9 @@ class UniPCScheduler(_SigmaTableScheduler):
         # (inpainting: the corrected sample, the history entry and x0 are taken before the blend, as upstream steps first)
         prev, xc, x0, m_t = self._launch_pc(e, cfg, guidance_scale, x, self.last_sample if order_c else None, hist, rows,
                                             k=k, blend=self._blend(inpaint, x))
-        self.model_outputs = self.model_outputs[1:] + [m_t]
         self.last_sample = xc
         self.this_order = order_p
-        if self.lower_order_nums < c.solver_order:
-            self.lower_order_nums += 1
-        self._step_index += 1
+        self._end_step(m_t)
         return prev, x0
 
 

@@ -17,7 +17,7 @@ from tests import unipc_ref as UR
 from tests.util import cosine, oracle_cfg, rel_l2, synth_inputs
 
 F64 = torch.float64
-# The longest input-to-output path of sched_step_pc_kernel (csrc/small.hip), counted in fp32 operations, eps -> prev with CFG, k
+# The longest input-to-output path of sched_step_pc_kernel (csrc/sched.hip), counted in fp32 operations, eps -> prev with CFG, k
 # and the corrector:  et - e, guidance * (.), e + (.)  [3];  k[b] * e  [1];  cm1 * e, (cm0 x) + (.)  [2];
 # cc4 * m_t, xc + (.)  [2];  cp0 * xc, (.) + cp1 m_t, + cp2 h1, + cp3 h2  [4]  = 12.  Every other path is shorter (x_last -> prev:
 # 1 + 4 + 4 = 9; the blend's a * init + s * blend_noise: 3), and a contraction to fma only removes roundings.
