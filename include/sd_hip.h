@@ -730,10 +730,26 @@ int sd_op_gemm_qkv_headmajor(void* stream, const void* X, long long ldx, const v
 int sd_op_attention_headmajor(void* stream, const void* Q, long long ldq, const void* K, const void* V, void* O,
                               long long ldo, int B, int heads, int Nq, int Nk, int D, float scale);
 /* causal self-attention of the CLIP text tower (transformers CLIPAttention, reached from src/models.py:139-155) on the fused
- * projection output qkv [B * L][3 H] (q | k | v, bf16) -> out [B * L][H]; L <= 128, head dim 64 (16 in the reduced tests) */
+ * projection output qkv [B * L][3 H] (q | k | v, bf16) -> out [B * L][H]; 1 <= L <= 128, head dim 64 (16 in the reduced tests),
+ * B <= 65535, out 4-byte aligned */
 int sd_op_clip_attention(void* stream, const void* qkv, void* out, int B, int L, int H, int heads);
 /* non-causal ViT self-attention on the fused projection output qkv [B * L][3 H] -> out [B * L][H]; head dim 64, L <= 320 */
 int sd_op_vit_attention(void* stream, const void* qkv, void* out, int B, int L, int H, int heads);
+/* the text tower's embedding: out [rows][H] bf16 = tok [vocab][H] row ids[r] + pos [L][H] row r % L (fp32 sum, one rounding);
+ * ids int32 [rows], rows = B * L, H even.  An id outside [0, vocab) is CLAMPED to row 0 / vocab - 1 (the Python wrapper
+ * refuses such ids before the call). */
+int sd_op_clip_embed(void* stream, const int* ids, const void* tok, const void* pos, void* out, int rows, int L, int H,
+                     int vocab);
+/* the towers' MLP activation in place on n bf16 values (n even): kind SD_ACT_QUICK_GELU (x sigmoid(1.702 x)) or SD_ACT_GELU
+ * (x Phi(x), within 1.3e-5 |x| before the output rounding); any other kind is refused */
+int sd_op_activation(void* stream, void* x, long long n, int kind);
+/* dst [B][H] = src [B * L][H] row b * L + p_b (bf16, copied): ids NULL -> p_b = 0 (the class token); ids int32 [B][L] with
+ * eos_id >= 0 -> the first position holding eos_id (0 when there is none), eos_id < 0 -> the first maximum of ids[b]
+ * (transformers' two pooling rules of CLIPTextModel) */
+int sd_op_pool_rows(void* stream, const void* src, const int* ids, int B, int L, int H, int eos_id, void* dst);
+/* the vision tower's embedding: out [B][Np + 1][H] bf16; row 0 = cls [H] (fp32) + pos row 0, row 1 + p = patch_rows
+ * [B * Np][H] row b * Np + p + pos [Np + 1][H] row 1 + p (fp32 sum, one rounding) */
+int sd_op_vit_embed(void* stream, const void* patch_rows, const float* cls, const void* pos, void* out, int B, int Np, int H);
 /* masked attention of a short query block (the BLIP text encoder's self- and cross-attention), head dim 64: q [B * Lq][ldq],
  * k and v [B * Lk][ldkv] (bf16; each pointer at its own column offset, 16-byte aligned, pitches multiples of 8), key mask int32
  * [B][Lk] or NULL (all valid) -> out [B * Lq][ldo]; 1 <= Lq <= 64, 1 <= Lk <= 320.  A masked key is excluded by select: whatever

@@ -143,6 +143,10 @@ _SIGS = {
     "sd_clip_resize_taps": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
     "sd_op_vit_attention": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
     "sd_op_clip_preprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sd_op_clip_embed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "sd_op_activation": (_i, [_vp, _vp, _ll, _i]),
+    "sd_op_pool_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "sd_op_vit_embed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
     "sd_inception_create": (_i, [C.POINTER(_vp)]),
     "sd_inception_destroy": (None, [_vp]),
     "sd_inception_num_convs": (_i, [_vp]),

@@ -102,7 +102,7 @@ __global__ void bf16_to_f32_kernel(const bf16_t* __restrict__ src, float* __rest
 int sd_launch_clip_embed(const int* ids, const bf16_t* tok, const bf16_t* pos, bf16_t* out, int rows, int L, int H,
                          int vocab, hipStream_t stream) {
     SD_REQUIRE(ids && tok && pos && out, "clip_embed: null operand");
-    SD_REQUIRE(H % 2 == 0 && rows > 0 && L > 0, "clip_embed: rows=%d L=%d H=%d", rows, L, H);
+    SD_REQUIRE(H % 2 == 0 && H > 0 && rows > 0 && L > 0 && vocab > 0, "clip_embed: rows=%d L=%d H=%d vocab=%d", rows, L, H, vocab);
     hipLaunchKernelGGL(clip_embed_kernel, dim3(rows), dim3(128), 0, stream, ids, tok, pos, out, L, H, vocab);
     SD_CHECK_HIP(hipGetLastError());
     return 0;
@@ -113,6 +113,9 @@ int sd_launch_clip_attention(const bf16_t* qkv, bf16_t* out, int B, int L, int H
     SD_REQUIRE(heads > 0 && H % heads == 0, "clip_attention: H=%d heads=%d", H, heads);
     const int D = H / heads;
     SD_REQUIRE(L >= 1 && L <= 128, "clip_attention: %d tokens (1..128 are built)", L);
+    SD_REQUIRE(B >= 1 && B <= 65535 && heads <= 65535, "clip_attention: B=%d heads=%d", B, heads);
+    // (scalar bf16 loads of qkv, packed pairs stored to out)
+    SD_REQUIRE(((uintptr_t)qkv & 1) == 0 && ((uintptr_t)out & 3) == 0, "clip_attention: qkv must be 2-byte, out 4-byte aligned");
     const int threads = (L + 63) / 64 * 64;
     const size_t smem = ((size_t)2 * L * (D + 1) + (size_t)threads * L) * sizeof(float);
     const float scale = 1.0f / sqrtf((float)D);

@@ -386,6 +386,29 @@ extern "C" int sd_op_vit_attention(void* stream, const void* qkv, void* out, int
     return sd_launch_vit_attention((const bf16_t*)qkv, (bf16_t*)out, B, L, H, heads, (hipStream_t)stream);
 }
 
+// the small kernels of the text / vision towers on their own (clip.hip, vit.hip).  sd_op_clip_embed CLAMPS an id outside
+// [0, vocab) to the nearest row, as the kernel does; the Python wrapper (clip.py) refuses such ids before they get here.
+extern "C" int sd_op_clip_embed(void* stream, const int* ids, const void* tok, const void* pos, void* out, int rows, int L, int H,
+                                int vocab) {
+    return sd_launch_clip_embed(ids, (const bf16_t*)tok, (const bf16_t*)pos, (bf16_t*)out, rows, L, H, vocab, (hipStream_t)stream);
+}
+
+extern "C" int sd_op_activation(void* stream, void* x, long long n, int kind) {
+    SD_REQUIRE(kind == SD_ACT_QUICK_GELU || kind == SD_ACT_GELU, "sd_op_activation: kind %d (%d = quick_gelu, %d = gelu)", kind,
+               SD_ACT_QUICK_GELU, SD_ACT_GELU);
+    if (kind == SD_ACT_GELU) return sd_launch_gelu_erf((bf16_t*)x, (long)n, (hipStream_t)stream);
+    return sd_launch_quick_gelu((bf16_t*)x, (long)n, (hipStream_t)stream);
+}
+
+extern "C" int sd_op_pool_rows(void* stream, const void* src, const int* ids, int B, int L, int H, int eos_id, void* dst) {
+    return sd_launch_pool_rows((const bf16_t*)src, ids, B, L, H, eos_id, (bf16_t*)dst, (hipStream_t)stream);
+}
+
+extern "C" int sd_op_vit_embed(void* stream, const void* patch_rows, const float* cls, const void* pos, void* out, int B, int Np,
+                               int H) {
+    return sd_launch_vit_embed((const bf16_t*)patch_rows, cls, (const bf16_t*)pos, (bf16_t*)out, B, Np, H, (hipStream_t)stream);
+}
+
 // the BLIP text encoder's attention on its own; the key mask is copied to the host to refuse a sample without a valid key
 extern "C" int sd_op_bert_attention(void* stream, const void* q, long long ldq, const void* k, const void* v, long long ldkv,
                                     const int* mask, void* out, long long ldo, int B, int heads, int Lq, int Lk) {
