@@ -825,6 +825,33 @@ int sd_op_xattn_fused_rowstats(void* stream, const void* X, const void* R, void*
  * rows_per_sample >= 1 (a tile of 32 rows never spans two samples), M a multiple of rows_per_sample; 16-byte aligned. */
 int sd_op_ip_xattn(void* stream, const void* R, void* Rout, const void* A, const void* Bt, const float* gamma, const float* beta,
                    float eps, long long M, int C, int rows_per_sample, int heads, int T);
+/* The builders of the prompt-side operands of cross-attention on their own (what sd_unet_set_context_hw and
+ * sd_unet_set_ip_adapter_hw run per layer; all tensors bf16 unless said otherwise).
+ * sd_op_xattn_expand: out [B * heads * slots][C], row (b, h, j) = scale * kv [b * L + j][col_off + c] (fp32
+ *   product, one rounding) for j < L and c in head h, +0 elsewhere.  kv rows are 2 C wide (K | V): col_off 0 or C.  1 <= L <=
+ *   slots, heads divides C, C / heads even.
+ * sd_op_transpose_bf16: dst [b][c][r'] = src [b][r][c] (B <= 65535); perm16: r' = r with bits 2 and 3 swapped
+ *   ((r & ~12) | ((r & 4) << 1) | ((r & 8) >> 1), R % 16 == 0), else r' = r.
+ * sd_op_retile32: dst [b][R / RT][K / 32][RT][32] = src [b][R][K]; K % 32 == 0, R % RT == 0, 16-byte aligned. */
+int sd_op_xattn_expand(void* stream, const void* kv, void* out, int B, int L, int C, int heads, int slots, int col_off, float scale);
+int sd_op_transpose_bf16(void* stream, const void* src, void* dst, int B, int R, int Cc, int perm16);
+int sd_op_retile32(void* stream, const void* src, void* dst, int B, int R, int K, int RT);
+/* sd_op_xattn_fold: every operand of one folded prompt cross-attention layer.  kv [UB * L][2 C] = the projected prompt (K | V),
+ *   wqT [C][C] = to_q transposed ([in][out]; with norm2 folded: gamma-scaled and centred over the input channel), wo [C][C] =
+ *   to_out.  NP = heads * 80 key slots, slot h * 80 + j = key j of head h, slots j >= L are zero rows.
+ *   at = rows of (K_h / sqrt d) . W_q,h, bw = columns of V_h . W_o,h^T.  perm = 1: the layouts sd_op_xattn_fused reads (at
+ *   [UB][C / 32][NP][32], bw [UB][C / 32][NP / 32][32][32] with the slot permutation of sd_op_transpose_bf16); perm = 0: at
+ *   [UB][NP][C], bw [UB][C][NP] (sd_op_gemm_batched's per-sample W).  c2 [UB][NP] fp32 = (K_h / sqrt d) . lnu (lnu fp32 [C]; both
+ *   null or neither), c1 [UB][NP] fp32 = ones . the stored rows of at (perm = 0 only; ones fp32 [C]; both null or neither).
+ *   scratch: 3 * UB * NP * C bf16; afterwards its first third holds bw before the transpose ([UB * NP][C]), the second the V
+ *   expansion.  1 <= L <= 80, C % 64 == 0, C / heads even.
+ * sd_op_ip_fold: the same for one IP-Adapter block over 32 key slots (32 / heads per head, T <= 32 / heads image tokens): ip_kv
+ *   [UB * T][2 C] -> at [UB][32][C], bt [UB][C][32] (sd_op_ip_xattn's A and Bt; V is multiplied by scale before its rounding).
+ *   scratch: 3 * UB * 32 * C bf16: the K expansion, the V expansion, bt before the transpose. */
+int sd_op_xattn_fold(void* stream, const void* kv, const void* wqT, const void* wo, const float* lnu, const float* ones, void* at,
+                     void* bw, float* c1, float* c2, void* scratch, int UB, int L, int C, int heads, int perm);
+int sd_op_ip_fold(void* stream, const void* ip_kv, const void* wqT, const void* wo, void* at, void* bt, void* scratch, int UB, int T,
+                  int C, int heads, float scale);
 int sd_op_xattn_fused(void* stream, const void* X, const void* R, void* Y, const void* At, const void* Bw,
                       const float* bias, int M, int C, int rows_per_sample, int L);
 /* The same with the block's norm2 folded in (how the plan runs it at the 64x64 / 32x32 levels): X holds the UN-normalised rows

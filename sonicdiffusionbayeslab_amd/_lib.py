@@ -147,6 +147,11 @@ _SIGS = {
     "sd_op_activation": (_i, [_vp, _vp, _ll, _i]),
     "sd_op_pool_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "sd_op_vit_embed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
+    "sd_op_xattn_expand": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f]),
+    "sd_op_transpose_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
+    "sd_op_retile32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
+    "sd_op_xattn_fold": (_i, [_vp] * 11 + [_i] * 5),
+    "sd_op_ip_fold": (_i, [_vp] * 7 + [_i] * 4 + [_f]),
     "sd_inception_create": (_i, [C.POINTER(_vp)]),
     "sd_inception_destroy": (None, [_vp]),
     "sd_inception_num_convs": (_i, [_vp]),

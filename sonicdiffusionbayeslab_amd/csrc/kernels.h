@@ -273,6 +273,19 @@ int sd_launch_xattn_fused(const XattnArgs& a, hipStream_t stream);
 // slots: key slots per head of the expansion (80 for the prompt; the IP-Adapter's image tokens use their own count)
 int sd_launch_xattn_expand(const bf16_t* kv, bf16_t* out, int B, int L, int C, int NH, int col_off, float scale,
                            hipStream_t stream, int slots = 80);
+// unet.hip: every operand of one folded prompt cross-attention layer (what sd_unet_set_context_hw runs per layer) from kv
+// [UB * L][K | V] (2 C wide), wqT = attn2.to_q.weight.T (or .T.ln) [C][C], wo = attn2.to_out.0.weight [C][C]:
+//   at_dst = rows (sample, head, slot) of (scale K)_masked . wqT^T, bw_dst = the per-sample transpose of V_masked . wo^T;
+//   perm = 1: the fused kernel's layouts (XattnArgs::At / Bw: re-tiled, slots of Bw permuted), 0: [UB][NP][C] and [UB][C][NP];
+//   c1 [UB][NP] = ones . rows of the stored at_dst (perm = 0 only), c2 [UB][NP] = lnu . rows of the K expansion; each may be null
+//   together with its fp32 [C] vector.  scratch: three slabs of UB * NP * C bf16, NP = heads * 80.  1 <= L <= 80, C % 64 == 0.
+int sd_launch_xattn_fold(const bf16_t* kv, const bf16_t* wqT, const bf16_t* wo, const float* lnu, const float* ones, bf16_t* at_dst,
+                         bf16_t* bw_dst, float* c1, float* c2, bf16_t* scratch, int UB, int L, int C, int heads, int perm,
+                         hipStream_t stream);
+// ... and of one IP-Adapter block (sd_unet_set_ip_adapter_hw) from ip_kv [UB * T][K_ip | V_ip]: at [UB][32][C], bt [UB][C][32]
+// (sd_launch_ip_xattn's A and Bt; V times the adapter scale).  scratch: three slabs of UB * 32 * C bf16.
+int sd_launch_ip_fold(const bf16_t* ip_kv, const bf16_t* wqT, const bf16_t* wo, bf16_t* at, bf16_t* bt, bf16_t* scratch, int UB, int T,
+                      int C, int heads, float scale, hipStream_t stream);
 // ip_xattn.hip: the IP-Adapter image branch  Y = R + sum_h softmax_T(LN(R) A_h^T) B_h  (one launch per transformer block)
 //   R, Y [M][C] (Y != R); A [samples][32][C]: row (head * (32 / heads) + token) = (K_ip,h[token] / sqrt(d)) . W_q,h, the other
 //   rows zero; Bt [samples][C][32]: the same slots as columns = scale * V_ip,h[token] . W_o,h^T; gamma / beta [C]: norm2, applied

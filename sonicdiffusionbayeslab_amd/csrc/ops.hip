@@ -701,6 +701,38 @@ extern "C" int sd_op_ip_xattn(void* stream, const void* R, void* Rout, const voi
                               rows_per_sample, heads, T, (hipStream_t)stream);
 }
 
+// the builders of the prompt-side operands on their own (small.hip; sd_launch_xattn_fold / sd_launch_ip_fold of unet.hip: what
+// sd_unet_set_context_hw / sd_unet_set_ip_adapter_hw run per layer)
+extern "C" int sd_op_xattn_expand(void* stream, const void* kv, void* out, int B, int L, int C, int heads, int slots, int col_off,
+                                  float scale) {
+    SD_REQUIRE(col_off == 0 || col_off == C, "sd_op_xattn_expand: col_off %d (0 = the K half, C = the V half of a row)", col_off);
+    return sd_launch_xattn_expand((const bf16_t*)kv, (bf16_t*)out, B, L, C, heads, col_off, scale, (hipStream_t)stream, slots);
+}
+
+extern "C" int sd_op_transpose_bf16(void* stream, const void* src, void* dst, int B, int R, int Cc, int perm16) {
+    return sd_launch_transpose_bf16((const bf16_t*)src, (bf16_t*)dst, B, R, Cc, (hipStream_t)stream, perm16);
+}
+
+extern "C" int sd_op_retile32(void* stream, const void* src, void* dst, int B, int R, int K, int RT) {
+    SD_REQUIRE(R > 0 && K > 0, "sd_op_retile32: R=%d K=%d", R, K);
+    SD_REQUIRE(((((uintptr_t)src) | (uintptr_t)dst) & 15) == 0, "sd_op_retile32: operands must be 16-byte aligned");
+    return sd_launch_retile32((const bf16_t*)src, (bf16_t*)dst, B, R, K, RT, (hipStream_t)stream);
+}
+
+extern "C" int sd_op_xattn_fold(void* stream, const void* kv, const void* wqT, const void* wo, const float* lnu, const float* ones,
+                                void* at, void* bw, float* c1, float* c2, void* scratch, int UB, int L, int C, int heads, int perm) {
+    if (ensure_zero_page()) return -2;
+    return sd_launch_xattn_fold((const bf16_t*)kv, (const bf16_t*)wqT, (const bf16_t*)wo, lnu, ones, (bf16_t*)at, (bf16_t*)bw, c1, c2,
+                                (bf16_t*)scratch, UB, L, C, heads, perm, (hipStream_t)stream);
+}
+
+extern "C" int sd_op_ip_fold(void* stream, const void* ip_kv, const void* wqT, const void* wo, void* at, void* bt, void* scratch,
+                             int UB, int T, int C, int heads, float scale) {
+    if (ensure_zero_page()) return -2;
+    return sd_launch_ip_fold((const bf16_t*)ip_kv, (const bf16_t*)wqT, (const bf16_t*)wo, (bf16_t*)at, (bf16_t*)bt, (bf16_t*)scratch,
+                             UB, T, C, heads, scale, (hipStream_t)stream);
+}
+
 extern "C" int sd_op_xattn_fused(void* stream, const void* X, const void* R, void* Y, const void* At, const void* Bw,
                                  const float* bias, int M, int C, int rows_per_sample, int L) {
     SD_REQUIRE(sd_xattn_fused_applicable(rows_per_sample, C, 8, L) || getenv("SD_XATTN_FUSED"),

@@ -739,6 +739,84 @@ extern "C" long long sd_unet_workspace_bytes_hw(sd_unet* u, int unet_batch, int 
     return (long long)bytes;
 }
 
+// out [rows][N] = X [rows][K] . W [N][K]^T (bf16, the plain GEMM of the operand builders below)
+static int fold_gemm(const bf16_t* X, int rows, int K, const bf16_t* W, int N, const float* bias, bf16_t* out, hipStream_t stream) {
+    GemmArgs a;
+    a.X = X; a.ldx = K; a.K1 = K; a.K = K; a.M = rows; a.N = N;
+    a.W = W; a.bias = bias;
+    a.C = out; a.ldc = N;
+    a.zero_page = g_zero_page;
+    return sd_launch_gemm(a, 0, stream);
+}
+
+// The operands of ONE folded prompt cross-attention layer from its projected prompt kv [UB * L][K | V] (kernels.h).  scratch =
+// three slabs of UB * NP * C bf16 (NP = heads * 80).  What they hold when the last launch has run: slab 0 = B^T [UB * NP][C] in
+// natural slot order (the second GEMM overwrites the K expansion there AFTER the c2 GEMV has read it), slab 1 = the V expansion,
+// slab 2 = the permuted transpose of B^T before its re-tiling (perm; untouched otherwise).  (Slabs counted from 0.)
+int sd_launch_xattn_fold(const bf16_t* kv, const bf16_t* wqT, const bf16_t* wo, const float* lnu, const float* ones, bf16_t* at_dst,
+                         bf16_t* bw_dst, float* c1, float* c2, bf16_t* scratch, int UB, int L, int C, int heads, int perm,
+                         hipStream_t stream) {
+    SD_REQUIRE(kv && wqT && wo && at_dst && bw_dst && scratch, "xattn_fold: null operand");
+    SD_REQUIRE((c1 != nullptr) == (ones != nullptr) && (c2 != nullptr) == (lnu != nullptr),
+               "xattn_fold: null operand (c1 goes with ones, c2 with lnu)");
+    SD_REQUIRE(UB > 0 && L > 0 && L <= 80, "xattn_fold: UB=%d, %d prompt keys (1..80 fit the 80 key slots of a head)", UB, L);
+    SD_REQUIRE(heads > 0 && C > 0 && C % heads == 0, "xattn_fold: heads=%d does not divide C=%d", heads, C);
+    SD_REQUIRE((C / heads) % 2 == 0, "xattn_fold: odd head dim %d (C=%d heads=%d)", C / heads, C, heads);
+    SD_REQUIRE(C % 64 == 0, "xattn_fold: C=%d must be a multiple of 64 (the GEMMs' K)", C);
+    SD_REQUIRE(!perm || c1 == nullptr, "xattn_fold: c1 is read from the natural layout of A^T (the tiled form takes none)");
+    int rc;
+    const int NH = heads, NP = NH * 80, d = C / NH;
+    bf16_t* kexp = scratch;
+    bf16_t* vexp = kexp + (size_t)UB * NP * C;
+    if ((rc = sd_launch_xattn_expand(kv, kexp, UB, L, C, NH, 0, 1.0f / sqrtf((float)d), stream))) return rc;
+    if ((rc = sd_launch_xattn_expand(kv, vexp, UB, L, C, NH, C, 1.0f, stream))) return rc;
+    // fused kernel: both operands are re-tiled ([32-column slice][rows][64 B]) so that its DMA pieces are contiguous;
+    // the plain layouts land in the third scratch slab first
+    bf16_t* tmp = scratch + (size_t)2 * UB * NP * C;
+    {   // A^T [UB*NP, C]: rows (sample, head, key), K-contiguous over the UNet channel -> W operand of GEMM 1
+        if ((rc = fold_gemm(kexp, UB * NP, C, wqT, C, nullptr, perm ? tmp : at_dst, stream))) return rc;
+        if (perm && (rc = sd_launch_retile32(tmp, at_dst, UB, NP, C, NP, stream))) return rc;
+    }
+    if (c1) {    // what is left of the mean term: c1[sample][slot] = sum over the channel of the ROUNDED centred row
+        if ((rc = sd_launch_gemv(ones, at_dst, nullptr, c1, UB * NP, C, 0, stream))) return rc;
+    }
+    if (c2) {    // beta term of every key slot: c2[sample][slot] = (scale K_h[slot]) . u   (fp32 GEMV over the expanded rows)
+        if ((rc = sd_launch_gemv(lnu, kexp, nullptr, c2, UB * NP, C, 0, stream))) return rc;
+    }
+    {   // B^T [UB*NP, C] = V_masked . W_o^T (one GEMM, into the K expansion's scratch), then transposed per sample
+        // to [C, NP]: K-contiguous over (head, key) -> W operand of GEMM 2
+        if ((rc = fold_gemm(vexp, UB * NP, C, wo, C, nullptr, kexp, stream))) return rc;
+        if ((rc = sd_launch_transpose_bf16(kexp, perm ? tmp : bw_dst, UB, NP, C, stream, perm ? 1 : 0))) return rc;
+        if (perm && (rc = sd_launch_retile32(tmp, bw_dst, UB, C, NP, 32, stream))) return rc;
+    }
+    return 0;
+}
+
+// The operands of ONE IP-Adapter block from its projected image tokens ip_kv [UB * T][K_ip | V_ip]: per-head expansions over 32
+// key slots (32 / heads per head, T of them used) and the folds
+//   at [UB][32][C] = (K_ip / sqrt d)_expanded . W_q      bt [UB][C][32] = ((scale V_ip)_expanded . W_o^T)^T
+// scratch = three slabs of UB * 32 * C bf16 (counted from 0); afterwards slab 0 = the K expansion, slab 1 = the V expansion (times scale),
+// slab 2 = bt before the transpose ([UB * 32][C]).
+int sd_launch_ip_fold(const bf16_t* ip_kv, const bf16_t* wqT, const bf16_t* wo, bf16_t* at, bf16_t* bt, bf16_t* scratch, int UB, int T,
+                      int C, int heads, float scale, hipStream_t stream) {
+    SD_REQUIRE(ip_kv && wqT && wo && at && bt && scratch, "ip_fold: null operand");
+    SD_REQUIRE(heads > 0 && C > 0 && C % heads == 0, "ip_fold: heads=%d does not divide C=%d", heads, C);
+    SD_REQUIRE((C / heads) % 2 == 0, "ip_fold: odd head dim %d (C=%d heads=%d)", C / heads, C, heads);
+    SD_REQUIRE(32 % heads == 0 && UB > 0 && T > 0 && T <= 32 / heads, "ip_fold: UB=%d, %d image tokens in the %d key slots of a head "
+               "(32 slots over %d heads)", UB, T, 32 % heads == 0 ? 32 / heads : 0, heads);
+    SD_REQUIRE(C % 64 == 0, "ip_fold: C=%d must be a multiple of 64 (the GEMMs' K)", C);
+    int rc;
+    const int NH = heads, SPH = 32 / NH, d = C / NH;
+    bf16_t* kexp = scratch;
+    bf16_t* vexp = kexp + (size_t)UB * 32 * C;
+    bf16_t* tmp = vexp + (size_t)UB * 32 * C;
+    if ((rc = sd_launch_xattn_expand(ip_kv, kexp, UB, T, C, NH, 0, 1.0f / sqrtf((float)d), stream, SPH))) return rc;
+    if ((rc = sd_launch_xattn_expand(ip_kv, vexp, UB, T, C, NH, C, scale, stream, SPH))) return rc;
+    if ((rc = fold_gemm(kexp, UB * 32, C, wqT, C, nullptr, at, stream))) return rc;
+    if ((rc = fold_gemm(vexp, UB * 32, C, wo, C, nullptr, tmp, stream))) return rc;
+    return sd_launch_transpose_bf16(tmp, bt, UB, 32, C, stream);
+}
+
 extern "C" int sd_unet_set_context(sd_unet* u, void* stream, const float* ehs, int unet_batch, int cache_branch_id,
                                    void* workspace, long long workspace_bytes) {
     SD_REQUIRE(u, "set_context: null handle");
@@ -776,37 +854,14 @@ extern "C" int sd_unet_set_context_hw(sd_unet* u, void* stream, const float* ehs
         if ((rc = gemm(cb, M, CD, pl.ctx_w[i], 2 * pl.ctx_c[i], (bf16_t*)(ws + pl.tensors[pl.ctx_kv[i]].off)))) return rc;
     // folded prompt cross-attention: A^T = (scale K)_masked . W_q  and  B = W_o . V_masked^T per sample and layer
     for (const Plan::Fold& f : pl.ctx_fold) {
-        const int C = f.C, NH = f.heads, NP = NH * 80, d = C / NH;      // (heads of the level the layer sits on)
-        const bf16_t* kvp = (const bf16_t*)(ws + pl.tensors[f.kv].off);
-        bf16_t* kexp = (bf16_t*)(ws + pl.tensors[pl.ctx_fold_scratch].off);
-        bf16_t* vexp = kexp + (size_t)unet_batch * NP * C;
-        if ((rc = sd_launch_xattn_expand(kvp, kexp, unet_batch, L, C, NH, 0, 1.0f / sqrtf((float)d), (hipStream_t)stream))) return rc;
-        if ((rc = sd_launch_xattn_expand(kvp, vexp, unet_batch, L, C, NH, C, 1.0f, (hipStream_t)stream))) return rc;
-        // fused kernel: both operands are re-tiled ([32-column slice][rows][64 B]) so that its DMA pieces are contiguous;
-        // the plain layouts land in the V expansion's scratch first (free after the second GEMM below has read it ... the
-        // A^T GEMM output goes there BEFORE that GEMM runs, so it is re-tiled right away)
-        bf16_t* at_dst = (bf16_t*)(ws + pl.tensors[f.at].off);
-        bf16_t* tmp = (bf16_t*)(ws + pl.tensors[pl.ctx_fold_scratch].off) + (size_t)2 * unet_batch * NP * C;   // third scratch slab
-        {   // A^T [UB*NP, C]: rows (sample, head, key), K-contiguous over the UNet channel -> W operand of GEMM 1
-            if ((rc = gemm(kexp, unet_batch * NP, C, f.wqT, C, f.perm ? tmp : at_dst))) return rc;
-            if (f.perm && (rc = sd_launch_retile32(tmp, at_dst, unet_batch, NP, C, NP, (hipStream_t)stream))) return rc;
-        }
-        if (f.c1 >= 0) {    // what is left of the mean term: c1[sample][slot] = sum over the channel of the ROUNDED centred row
-            if ((rc = sd_launch_gemv((const float*)(u->dweights + f.ones), at_dst, nullptr, (float*)(ws + pl.tensors[f.c1].off),
-                                     unet_batch * NP, C, 0, (hipStream_t)stream))) return rc;
-        }
-        if (f.c2 >= 0) {    // beta term of every key slot: c2[sample][slot] = (scale K_h[slot]) . u   (fp32 GEMV over the expanded rows)
-            if ((rc = sd_launch_gemv((const float*)(u->dweights + f.lnu), kexp, nullptr, (float*)(ws + pl.tensors[f.c2].off),
-                                     unet_batch * NP, C, 0, (hipStream_t)stream))) return rc;
-        }
-        {   // B^T [UB*NP, C] = V_masked . W_o^T (one GEMM, into the K expansion's scratch), then transposed per sample
-            // to [C, NP]: K-contiguous over (head, key) -> W operand of GEMM 2
-            if ((rc = gemm(vexp, unet_batch * NP, C, f.wo, C, kexp))) return rc;
-            bf16_t* bw_dst = (bf16_t*)(ws + pl.tensors[f.bw].off);
-            if ((rc = sd_launch_transpose_bf16(kexp, f.perm ? tmp : bw_dst, unet_batch, NP, C, (hipStream_t)stream, f.perm ? 1 : 0)))
-                return rc;
-            if (f.perm && (rc = sd_launch_retile32(tmp, bw_dst, unet_batch, C, NP, 32, (hipStream_t)stream))) return rc;
-        }
+        auto WB = [&](size_t off) { return (const bf16_t*)(u->dweights + off); };
+        auto WF = [&](size_t off) { return (const float*)(u->dweights + off); };
+        if ((rc = sd_launch_xattn_fold((const bf16_t*)(ws + pl.tensors[f.kv].off), WB(f.wqT), WB(f.wo), f.c2 >= 0 ? WF(f.lnu) : nullptr,
+                                       f.c1 >= 0 ? WF(f.ones) : nullptr, (bf16_t*)(ws + pl.tensors[f.at].off),
+                                       (bf16_t*)(ws + pl.tensors[f.bw].off), f.c1 >= 0 ? (float*)(ws + pl.tensors[f.c1].off) : nullptr,
+                                       f.c2 >= 0 ? (float*)(ws + pl.tensors[f.c2].off) : nullptr,
+                                       (bf16_t*)(ws + pl.tensors[pl.ctx_fold_scratch].off), unet_batch, L, f.C, f.heads, f.perm ? 1 : 0,
+                                       (hipStream_t)stream))) return rc;
     }
     return 0;
 }
@@ -908,16 +963,10 @@ extern "C" int sd_unet_set_ip_adapter_hw(sd_unet* u, void* stream, const float* 
     // per block: K_ip | V_ip, their per-head expansions over 32 key slots (32 / heads per head, T of them used), and the folds
     //   A [UB][32][C] = (K_ip / sqrt d)_expanded . W_q      Bt [UB][C][32] = ((scale V_ip)_expanded . W_o^T)^T
     for (const Plan::IpFold& f : pl.ip_fold) {
-        const int C = f.C, NH = f.heads, SPH = 32 / NH, d = C / NH;
-        bf16_t* kexp = TP(pl.ctx_fold_scratch);
-        bf16_t* vexp = kexp + (size_t)UB * 32 * C;
-        bf16_t* tmp = vexp + (size_t)UB * 32 * C;
-        if ((rc = gemm(TP(pl.ip_tok), UB * T, CD, f.wkv, 2 * C, nullptr, TP(pl.ip_kv)))) return rc;
-        if ((rc = sd_launch_xattn_expand(TP(pl.ip_kv), kexp, UB, T, C, NH, 0, 1.0f / sqrtf((float)d), st, SPH))) return rc;
-        if ((rc = sd_launch_xattn_expand(TP(pl.ip_kv), vexp, UB, T, C, NH, C, scale, st, SPH))) return rc;
-        if ((rc = gemm(kexp, UB * 32, C, f.wqT, C, nullptr, TP(f.at)))) return rc;
-        if ((rc = gemm(vexp, UB * 32, C, f.wo, C, nullptr, tmp))) return rc;
-        if ((rc = sd_launch_transpose_bf16(tmp, TP(f.bt), UB, 32, C, st))) return rc;
+        auto WB = [&](size_t off) { return (const bf16_t*)(u->dweights + off); };
+        if ((rc = gemm(TP(pl.ip_tok), UB * T, CD, f.wkv, 2 * f.C, nullptr, TP(pl.ip_kv)))) return rc;
+        if ((rc = sd_launch_ip_fold(TP(pl.ip_kv), WB(f.wqT), WB(f.wo), TP(f.at), TP(f.bt), TP(pl.ctx_fold_scratch), UB, T, f.C, f.heads,
+                                    scale, st))) return rc;
     }
     u->ip_keys.insert(key);
     return 0;

@@ -198,6 +198,29 @@ def test_identity_and_launch_accounting(weights, nets):
     net.clear_ip_adapter()
 
 
+def test_forward_with_image_prompt_ignores_old_workspace_contents(weights, nets):
+    """The context operands, the folded image operands, their pad slots and the scratch live in a workspace that comes from
+    torch.empty: with every byte of it zero, 0xFF or NaN before set_context + set_ip_adapter, a full forward gives the same bits
+    (tests/test_context_fold_gpu.py has the other handles).  32x32 latents at SD-1.5 widths: all three prompt-attention forms."""
+    from tests.test_context_fold_gpu import assert_same_after_every_fill, unet_after_every_fill
+    cfg, sd, ipsd = weights
+    net, _ = nets
+    lat, pe, ne = synth_inputs(cfg, 1, seed=15)
+    ctx, x = torch.cat([ne, pe]).cuda(), lat.cuda()
+    emb = cfg_image_embeds(_embeds(1, seed=16))
+    net.set_deepcache(-1)
+    net.clear_ip_adapter()
+    try:
+        outs = unet_after_every_fill(net, x, ctx, 501.0, image=(emb, 0.8))
+        prof = net.forward_profiled(x, 2, 501.0)
+    finally:
+        net.clear_ip_adapter()
+    launches = {k: v["launches"] for k, v in prof.items()}
+    assert launches["ip_xattn"] == 16 and launches["xattn_fused"] == 5          # the five blocks of the 1024-token level
+    assert launches["attention"] == 16 + 6                                       # 64 and 16 tokens: a prompt attention launch of their own
+    assert_same_after_every_fill(outs, "IP-Adapter UNet at 32x32")
+
+
 def test_diffusers_style_call_with_added_cond_kwargs(weights, nets):
     cfg, sd, ipsd = weights
     net, plain = nets
