@@ -249,39 +249,33 @@ _SIGS = {
 }
 
 
-def load() -> C.CDLL:
-    """Load libsdhip.so (RTLD_GLOBAL not needed); raises SdHipError if it is not built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise SdHipError(
-            f"{LIB_PATH} is missing: build it with `python -m sonicdiffusionbayeslab_amd.build` "
-            "(or __graft_entry__.build()).  There is no CPU/PyTorch fallback for the hot path.")
-    lib = C.CDLL(LIB_PATH)
+def _open(path: str, missing_message: str) -> C.CDLL:
+    if not os.path.exists(path):
+        raise SdHipError(missing_message)
+    lib = C.CDLL(path)
     for name, (res, args) in _SIGS.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    _lib = lib
     return lib
+
+
+def load() -> C.CDLL:
+    """Load libsdhip.so (RTLD_GLOBAL not needed); raises SdHipError if it is not built."""
+    global _lib
+    if _lib is None:
+        _lib = _open(LIB_PATH, f"{LIB_PATH} is missing: build it with `python -m sonicdiffusionbayeslab_amd.build` "
+                               "(or __graft_entry__.build()).  There is no CPU/PyTorch fallback for the hot path.")
+    return _lib
 
 
 def load_ablate() -> C.CDLL:
     """libsdhip_ablate.so: a SECOND, independent instance of the library built with -DSD_ABLATE (its own globals).  Never
     used by the product path; raises if it is not built."""
     global _ablate
-    if _ablate is not None:
-        return _ablate
-    if not os.path.exists(ABLATE_LIB_PATH):
-        raise SdHipError(f"{ABLATE_LIB_PATH} is missing: build it with `python -m sonicdiffusionbayeslab_amd.build`")
-    lib = C.CDLL(ABLATE_LIB_PATH)
-    for name, (res, args) in _SIGS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _ablate = lib
-    return lib
+    if _ablate is None:
+        _ablate = _open(ABLATE_LIB_PATH, f"{ABLATE_LIB_PATH} is missing: build it with `python -m sonicdiffusionbayeslab_amd.build`")
+    return _ablate
 
 
 def check(rc: int, what: str = "libsdhip call", lib: Optional[C.CDLL] = None) -> None:

@@ -29,6 +29,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
+from .handle import HipHandle, Workspace, load_params
 
 
 @dataclass
@@ -110,23 +111,16 @@ def load_clip_state_dict(model_dir: str) -> Dict[str, torch.Tensor]:
     raise FileNotFoundError(f"no local CLIP text-encoder weights under {model_dir!r}")
 
 
-class HipClipTextModel:
+class HipClipTextModel(HipHandle):
     """``text_encoder(input_ids)[0]`` replacement: int token ids ``[B,77]`` -> fp32 ``[B,77,768]`` on the GPU."""
 
     def __init__(self, config: ClipTextConfig, state_dict: Dict[str, torch.Tensor], device: str = "cuda:0",
                  text_projection: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None):
         """``text_projection`` ([projection_dim, hidden], CLIPModel's ``text_projection.weight``) enables ``embeds``: the
         pooled, projected text features.  Pooling row: the first ``eos_token_id``; ``None``: the argmax of the ids."""
-        if not torch.cuda.is_available():
-            raise _lib.SdHipError("HipClipTextModel needs an MI355X (no CPU fallback exists)")
+        super().__init__(device)
         self.config = config
-        self.device = torch.device(device)
-        self._lib = _lib.load()
-        self._handle = C.c_void_p()
-        self._ws: Optional[torch.Tensor] = None
-        self._ws_batch = None
-        self._ews: Optional[torch.Tensor] = None
-        self._ews_batch = None
+        self._ews = Workspace(self.device)      # the workspace of ``embeds``, keyed by the batch like the main one
         # the weights go to self.device; the process's current device is left as it is (a device guard per call)
         with torch.cuda.device(self.device):
             self._build(config, state_dict, text_projection, eos_token_id)
@@ -145,34 +139,8 @@ class HipClipTextModel:
             t = text_projection.detach().to("cpu", torch.float32).contiguous()
             _lib.check(self._lib.sd_unet_load_param(self._handle, b"text_projection.weight", t.data_ptr(), t.numel()),
                        "load_param(text_projection.weight)")
-        sd = normalise_clip_state_dict(state_dict)
-        for name, shape in clip_param_shapes(config):
-            if name not in sd:
-                raise KeyError(f"state_dict lacks CLIP parameter {name!r}")
-            t = sd[name].detach().to("cpu", torch.float32).contiguous()
-            if tuple(t.shape) != tuple(shape):
-                raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
-            _lib.check(self._lib.sd_unet_load_param(self._handle, name.encode(), t.data_ptr(), t.numel()),
-                       f"load_param({name})")
-        _lib.check(self._lib.sd_unet_finalize(self._handle), "finalize")
-
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None):
-                self._lib.sd_unet_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
-
-    def _workspace(self, batch: int) -> torch.Tensor:
-        if self._ws is None or self._ws_batch != batch:
-            n = self._lib.sd_unet_workspace_bytes(self._handle, batch, -1)
-            if n < 0:
-                _lib.check(-1, "sd_unet_workspace_bytes")
-            self._ws = None
-            self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
-            self._ws_batch = batch
-        return self._ws
+        load_params(self._lib, self._handle, clip_param_shapes(config), normalise_clip_state_dict(state_dict), "CLIP")
+        self._finalize()
 
     def encode(self, input_ids: torch.Tensor) -> torch.Tensor:
         with torch.cuda.device(self.device):
@@ -187,10 +155,11 @@ class HipClipTextModel:
             raise ValueError("token id outside the vocabulary")
         b = ids.shape[0]
         out = torch.empty((b, L, H), dtype=torch.float32, device=self.device)
-        ws = self._workspace(b)
-        wsp = (ws.data_ptr() + 255) // 256 * 256
-        _lib.check(self._lib.sd_clip_encode(self._handle, _lib.current_stream(), ids.data_ptr(), b, out.data_ptr(), wsp,
-                                            ws.numel() - 256), "sd_clip_encode")
+        ws = self._wsp
+        if not ws.holds(b):
+            ws.reserve(Workspace.bytes_or_raise(self._lib.sd_unet_workspace_bytes(self._handle, b, -1), "sd_unet_workspace_bytes"), b)
+        _lib.check(self._lib.sd_clip_encode(self._handle, _lib.current_stream(), ids.data_ptr(), b, out.data_ptr(), ws.ptr,
+                                            ws.nbytes), "sd_clip_encode")
         return out
 
     __call__ = encode
@@ -211,17 +180,13 @@ class HipClipTextModel:
         if int(ids.min()) < 0 or int(ids.max()) >= self.config.vocab_size:
             raise ValueError("token id outside the vocabulary")
         b = ids.shape[0]
-        if self._ews is None or self._ews_batch != b:
-            n = self._lib.sd_clip_text_embeds_workspace_bytes(self._handle, b)
-            if n < 0:
-                _lib.check(-1, "sd_clip_text_embeds_workspace_bytes")
-            self._ews = None
-            self._ews = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
-            self._ews_batch = b
+        ws = self._ews
+        if not ws.holds(b):
+            ws.reserve(Workspace.bytes_or_raise(self._lib.sd_clip_text_embeds_workspace_bytes(self._handle, b),
+                                                "sd_clip_text_embeds_workspace_bytes"), b)
         out = torch.empty((b, self.projection_dim), dtype=torch.float32, device=self.device)
-        wsp = (self._ews.data_ptr() + 255) // 256 * 256
-        _lib.check(self._lib.sd_clip_text_embeds(self._handle, _lib.current_stream(), ids.data_ptr(), b, out.data_ptr(), wsp,
-                                                 self._ews.numel() - 256), "sd_clip_text_embeds")
+        _lib.check(self._lib.sd_clip_text_embeds(self._handle, _lib.current_stream(), ids.data_ptr(), b, out.data_ptr(), ws.ptr,
+                                                 ws.nbytes), "sd_clip_text_embeds")
         return out
 
 

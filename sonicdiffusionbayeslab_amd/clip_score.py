@@ -22,6 +22,7 @@ import torch
 
 from . import _lib
 from .clip import ClipBpeTokenizer, ClipTextConfig, HipClipTextModel
+from .handle import HipHandle, Workspace, load_params, resolve_device
 
 OPENAI_CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 OPENAI_CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
@@ -129,7 +130,7 @@ def check_text_config(cfg: ClipTextConfig, hidden_act: str = "quick_gelu") -> No
         raise ValueError(f"text_config.layer_norm_eps={cfg.layer_norm_eps}: 1e-5 is built")
 
 
-class HipClipVisionModel:
+class HipClipVisionModel(HipHandle):
     """``CLIPModel.get_image_features(processor(images).pixel_values)`` on libsdhip: uint8 ``[B,3,H,W]`` -> fp32
     ``[B, projection_dim]``.  One plan (and workspace size) per (batch, H, W)."""
 
@@ -137,14 +138,9 @@ class HipClipVisionModel:
         """``device``: where the weights live and the tower runs (``None``: the current device); the process's current
         device is left as it is."""
         check_vision_config(config, extended=True)
-        if not torch.cuda.is_available():
-            raise _lib.SdHipError("HipClipVisionModel needs an MI355X (no CPU fallback exists)")
+        super().__init__(device, resolve=True)
         self.config = config
-        self.device = resolve_device(device)
-        self._lib = _lib.load()
-        self._handle = C.c_void_p()
-        self._ws: Optional[torch.Tensor] = None
-        self._ws_key = None
+        self._sized = None                  # the (batch, H, W) the workspace was last sized for (grow-only: it may be larger)
         with torch.cuda.device(self.device):
             self._build(config, state_dict)
 
@@ -153,23 +149,8 @@ class HipClipVisionModel:
                                     config.intermediate_size, config.image_size, config.patch_size, config.projection_dim,
                                     config.layer_norm_eps, HIDDEN_ACTS[config.hidden_act])
         _lib.check(self._lib.sd_clip_vision_create(C.byref(c), C.byref(self._handle)), "sd_clip_vision_create")
-        for name, shape in clip_vision_param_shapes(config):
-            if name not in state_dict:
-                raise KeyError(f"state_dict lacks CLIP vision parameter {name!r}")
-            t = state_dict[name].detach().to("cpu", torch.float32).contiguous()
-            if tuple(t.shape) != tuple(shape):
-                raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
-            _lib.check(self._lib.sd_unet_load_param(self._handle, name.encode(), t.data_ptr(), t.numel()),
-                       f"load_param({name})")
-        _lib.check(self._lib.sd_unet_finalize(self._handle), "finalize")
-
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None):
-                self._lib.sd_unet_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
+        load_params(self._lib, self._handle, clip_vision_param_shapes(config), state_dict, "CLIP vision")
+        self._finalize()
 
     def encode(self, images: torch.Tensor) -> torch.Tensor:
         with torch.cuda.device(self.device):
@@ -180,19 +161,13 @@ class HipClipVisionModel:
             raise ValueError(f"images must be uint8 [B,3,H,W], got {images.dtype} {tuple(images.shape)}")
         x = images.to(self.device).contiguous()
         b, _, h, w = x.shape
-        key = (b, h, w)
-        if self._ws is None or self._ws_key != key:
-            n = self._lib.sd_clip_vision_workspace_bytes(self._handle, b, h, w)
-            if n < 0:
-                _lib.check(-1, "sd_clip_vision_workspace_bytes")
-            if self._ws is None or self._ws.numel() < n + 256:
-                self._ws = None
-                self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
-            self._ws_key = key
+        if self._sized != (b, h, w):
+            self._wsp.reserve(Workspace.bytes_or_raise(self._lib.sd_clip_vision_workspace_bytes(self._handle, b, h, w),
+                                                       "sd_clip_vision_workspace_bytes"))
+            self._sized = (b, h, w)
         out = torch.empty((b, self.config.projection_dim), dtype=torch.float32, device=self.device)
-        wsp = (self._ws.data_ptr() + 255) // 256 * 256
         _lib.check(self._lib.sd_clip_vision_encode(self._handle, _lib.current_stream(), x.data_ptr(), b, h, w, out.data_ptr(),
-                                                   wsp, self._ws.numel() - 256), "sd_clip_vision_encode")
+                                                   self._wsp.ptr, self._wsp.nbytes), "sd_clip_vision_encode")
         return out
 
     __call__ = encode
@@ -215,14 +190,6 @@ def _clip_score_pairs(image_embeds: torch.Tensor, text_embeds: torch.Tensor) -> 
     _lib.check(lib.sd_clip_score(_lib.current_stream(), a.data_ptr(), t.data_ptr(), a.shape[0], a.shape[1], raw.data_ptr(),
                                  score.data_ptr()), "sd_clip_score")
     return raw, score
-
-
-def resolve_device(device=None) -> torch.device:
-    """``device`` as a torch.device; ``None``: the process's current CUDA device."""
-    if device is None:
-        return torch.device("cuda", torch.cuda.current_device())
-    d = torch.device(device)
-    return torch.device("cuda", torch.cuda.current_device()) if d.type == "cuda" and d.index is None else d
 
 
 def _read_json(path: str) -> dict:

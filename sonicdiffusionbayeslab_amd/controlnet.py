@@ -14,6 +14,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
+from .handle import HipHandle, Workspace, load_params as _load_params
 from .unet import LATENT_CHANNELS, _c_config
 from .weights import ControlNetConfig, controlnet_param_shapes, controlnet_residual_shapes
 
@@ -31,9 +32,9 @@ def residual_layout(cfg, unet_batch: int, height: int, width: int) -> Tuple[List
 
 def new_residual_buffer(nbytes: int, device) -> torch.Tensor:
     """A 256-byte aligned uint8 view of ``nbytes`` device bytes."""
-    raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-    skew = (-raw.data_ptr()) % 256
-    return raw[skew:skew + nbytes]
+    ws = Workspace(device)
+    ws.reserve(nbytes)
+    return ws.view
 
 
 def unpack_residuals(buf: torch.Tensor, cfg, unet_batch: int, height: int, width: int):
@@ -64,16 +65,10 @@ def pack_residuals(down, mid, cfg, device) -> torch.Tensor:
 
 
 def load_params(lib, handle, config: ControlNetConfig, state_dict: Dict[str, torch.Tensor]) -> None:
-    for name, shape in controlnet_param_shapes(config):
-        if name not in state_dict:
-            raise KeyError(f"state_dict lacks ControlNet parameter {name!r}")
-        t = state_dict[name].detach().to("cpu", torch.float32).contiguous()
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
-        _lib.check(lib.sd_unet_load_param(handle, name.encode(), t.data_ptr(), t.numel()), f"sd_unet_load_param({name})")
+    _load_params(lib, handle, controlnet_param_shapes(config), state_dict, "ControlNet")
 
 
-class HipControlNetModel:
+class HipControlNetModel(HipHandle):
     """One ControlNet running on libsdhip.  ``set_context`` (the prompt) and ``set_cond`` (the control image) once per call,
     ``forward_residuals`` once per step."""
 
@@ -81,20 +76,14 @@ class HipControlNetModel:
                  weight_dtype: str = "bf16"):
         if _lib.DTYPES.get(weight_dtype, weight_dtype) != _lib.DTYPE_BF16:
             raise NotImplementedError(f"HipControlNetModel: weight_dtype={weight_dtype!r} is not built (a ControlNet runs in bf16)")
-        if not torch.cuda.is_available():
-            raise _lib.SdHipError("HipControlNetModel needs an MI355X (no CPU fallback exists)")
+        super().__init__(device)
         self.config = config
-        self.device = torch.device(device)
-        self._lib = _lib.load()
-        self._handle = C.c_void_p()
         torch.cuda.set_device(self.device)
         ccfg = _c_config(config.unet)
         embed = (C.c_int * 4)(*config.conditioning_embedding_out_channels)
         _lib.check(self._lib.sd_controlnet_create(C.byref(ccfg), embed, C.byref(self._handle)), "sd_controlnet_create")
         load_params(self._lib, self._handle, config, state_dict)
-        _lib.check(self._lib.sd_unet_finalize(self._handle), "sd_unet_finalize")
-        self._ws: Optional[torch.Tensor] = None
-        self._ws_key = None
+        self._finalize()
         self._ctx_key = None
         self._ctx_keepalive = None
         self._cond_key = None               # (batch, h, w) of the conditioning embedding on the handle
@@ -103,32 +92,21 @@ class HipControlNetModel:
         self._res_key = None
         self._tcond = None
 
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None):
-                self._lib.sd_unet_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
-
     def latent_size(self, height: Optional[int] = None, width: Optional[int] = None):
         s = self.config.unet.sample_size
         return (s if height is None else int(height)), (s if width is None else int(width))
 
-    def _workspace(self, unet_batch: int, h: int, w: int) -> torch.Tensor:
-        key = (unet_batch, h, w)
-        if self._ws is None or self._ws_key != key:
-            n = self._lib.sd_unet_workspace_bytes_hw(self._handle, unet_batch, -1, h, w)
-            if n < 0:
-                _lib.check(-1, "sd_unet_workspace_bytes_hw")
-            self._ws = None
-            self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
-            self._ws_key = key
+    def _reserve(self, unet_batch: int, h: int, w: int) -> Workspace:
+        key = (unet_batch, h, w)                # (exact key: the context lives in the workspace)
+        if not self._wsp.holds(key):
+            n = Workspace.bytes_or_raise(self._lib.sd_unet_workspace_bytes_hw(self._handle, unet_batch, -1, h, w),
+                                         "sd_unet_workspace_bytes_hw")
+            self._wsp.reserve(n, key)
             self._ctx_key = None
-        return self._ws
+        return self._wsp
 
-    def _ws_ptr(self, ws: torch.Tensor) -> int:
-        return (ws.data_ptr() + 255) // 256 * 256
+    def _workspace(self, unet_batch: int, h: int, w: int) -> torch.Tensor:
+        return self._reserve(unet_batch, h, w).tensor
 
     def set_context(self, encoder_hidden_states: torch.Tensor, height: Optional[int] = None, width: Optional[int] = None) -> None:
         """The prompt of the ControlNet's cross-attention layers, as ``HipUNet2DConditionModel.set_context``."""
@@ -138,9 +116,9 @@ class HipControlNetModel:
         if ehs.dim() != 3 or ehs.shape[1] != u.context_len or ehs.shape[2] != u.cross_attention_dim:
             raise ValueError(f"encoder_hidden_states must be [N,{u.context_len},{u.cross_attention_dim}], got {tuple(ehs.shape)}")
         ub = ehs.shape[0]
-        ws = self._workspace(ub, h, w)
+        ws = self._reserve(ub, h, w)
         _lib.check(self._lib.sd_unet_set_context_hw(self._handle, _lib.current_stream(), ehs.data_ptr(), ub, -1, h, w,
-                                                    self._ws_ptr(ws), ws.numel() - 256), "sd_unet_set_context_hw")
+                                                    ws.ptr, ws.nbytes), "sd_unet_set_context_hw")
         self._ctx_keepalive = ehs
         self._ctx_key = (ub, h, w)
 
@@ -187,9 +165,8 @@ class HipControlNetModel:
     def residual_buffer(self, unet_batch: int, h: int, w: int) -> torch.Tensor:
         key = (unet_batch, h, w)
         if self._res is None or self._res_key != key:
-            n = self._lib.sd_controlnet_residual_bytes_hw(self._handle, unet_batch, h, w)
-            if n < 0:
-                _lib.check(-1, "sd_controlnet_residual_bytes_hw")
+            n = Workspace.bytes_or_raise(self._lib.sd_controlnet_residual_bytes_hw(self._handle, unet_batch, h, w),
+                                         "sd_controlnet_residual_bytes_hw")
             assert n == residual_layout(self.config, unet_batch, h, w)[1]
             self._res = None
             self._res = new_residual_buffer(n, self.device)
@@ -211,9 +188,9 @@ class HipControlNetModel:
         if latents.dtype != torch.float32 or not latents.is_contiguous() or latents.device != self.device:
             latents = latents.to(self.device, torch.float32).contiguous()
         buf = self.residual_buffer(unet_batch, h, w) if out is None else out
-        ws = self._workspace(unet_batch, h, w)
+        ws = self._reserve(unet_batch, h, w)
         _lib.check(self._lib.sd_controlnet_forward_hw(self._handle, _lib.current_stream(), latents.data_ptr(), b, unet_batch, h, w,
-                                                      float(timestep), buf.data_ptr(), self._ws_ptr(ws), ws.numel() - 256),
+                                                      float(timestep), buf.data_ptr(), ws.ptr, ws.nbytes),
                    "sd_controlnet_forward_hw")
         return buf
 

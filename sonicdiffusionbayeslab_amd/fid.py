@@ -16,6 +16,7 @@ from typing import Dict, List, Tuple
 import torch
 
 from . import _lib
+from .handle import HipHandle, Workspace
 
 TAPS = (64, 192, 768, 2048)
 BN_EPS = 1e-3
@@ -69,18 +70,14 @@ def fold_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, Tuple[torch.Tensor
     return out
 
 
-class HipInceptionFeatures:
+class HipInceptionFeatures(HipHandle):
     """uint8 images ``[B,3,H,W]`` (any size) -> fp32 features ``[B, feature]`` on the GPU."""
+    _destroy = "sd_inception_destroy"
 
     def __init__(self, folded: Dict[str, Tuple[torch.Tensor, torch.Tensor]], device=None):
-        from .clip_score import resolve_device
-        self._handle = None
-        self._lib = _lib.load()
-        self.device = resolve_device(device)
-        h = C.c_void_p()
+        super().__init__(device, resolve=True)
+        h = self._handle
         _lib.check(self._lib.sd_inception_create(C.byref(h)), "sd_inception_create")
-        self._handle = h
-        self._ws = None
         with torch.cuda.device(self.device):
             for name, (w, b) in folded.items():
                 _lib.check(self._lib.sd_inception_load_conv(h, name.encode(), w.data_ptr(), w.numel(), b.data_ptr(), b.numel()),
@@ -95,14 +92,6 @@ class HipInceptionFeatures:
     def from_file(cls, path: str, device=None) -> "HipInceptionFeatures":
         return cls.from_state_dict(load_state_dict(path), device=device)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None):
-                self._lib.sd_inception_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
-
     def features(self, images: torch.Tensor, feature: int = 2048) -> torch.Tensor:
         check_feature(feature)
         if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[1] != 3:
@@ -110,16 +99,11 @@ class HipInceptionFeatures:
         with torch.cuda.device(self.device):
             x = images.to(self.device).contiguous()
             b, _, h, w = x.shape
-            n = self._lib.sd_inception_workspace_bytes(self._handle, b, feature)
-            if n < 0:
-                _lib.check(-1, "sd_inception_workspace_bytes")
-            if self._ws is None or self._ws.numel() < n + 256:
-                self._ws = None
-                self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+            self._wsp.reserve(Workspace.bytes_or_raise(self._lib.sd_inception_workspace_bytes(self._handle, b, feature),
+                                                       "sd_inception_workspace_bytes"))        # (grow-only)
             out = torch.empty((b, feature), dtype=torch.float32, device=self.device)
-            wsp = (self._ws.data_ptr() + 255) // 256 * 256
             _lib.check(self._lib.sd_inception_features(self._handle, _lib.current_stream(), x.data_ptr(), b, h, w, feature,
-                                                       out.data_ptr(), wsp, self._ws.numel() - 256), "sd_inception_features")
+                                                       out.data_ptr(), self._wsp.ptr, self._wsp.nbytes), "sd_inception_features")
             return out
 
     __call__ = features

@@ -22,12 +22,12 @@ import math
 import os
 import unicodedata
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Sequence, Tuple
 
 import torch
 
 from . import _lib
-from .clip_score import resolve_device
+from .handle import HipHandle, Workspace, load_params
 
 REWARD_MEAN, REWARD_STD = 0.16717362830052426, 1.0333394966054072
 HEAD_LAYERS = (0, 2, 4, 6, 7)                    # mlp.layers.N that are Linears (the others are Dropouts)
@@ -356,7 +356,7 @@ def load_image_reward_weights(path: str) -> Dict[str, torch.Tensor]:
 # the model
 # ---------------------------------------------------------------------------------------------------------------------
 
-class HipImageReward:
+class HipImageReward(HipHandle):
     """``ImageReward.score`` / ``inference_rank`` on libsdhip: uint8 images + prompts -> rewards."""
 
     def __init__(self, config: ImageRewardConfig, state_dict: Dict[str, torch.Tensor], tokenizer: BertWordPieceTokenizer,
@@ -367,14 +367,9 @@ class HipImageReward:
         params = map_image_reward_state_dict(config, state_dict)       # key / shape errors before any GPU work
         if tokenizer.max_length != config.max_text_len:
             raise ValueError(f"tokenizer max_length {tokenizer.max_length} != max_text_len {config.max_text_len}")
-        if not torch.cuda.is_available():
-            raise _lib.SdHipError("HipImageReward needs an MI355X (no CPU fallback exists)")
+        super().__init__(device, resolve=True)
         self.config, self.tokenizer = config, tokenizer
-        self.device = resolve_device(device)
-        self._lib = _lib.load()
-        self._handle = C.c_void_p()
-        self._ws: Optional[torch.Tensor] = None
-        self._ws_key = None
+        self._sized = None                  # the (batch, H, W) the workspace was last sized for (grow-only: it may be larger)
         with torch.cuda.device(self.device):
             self._build(config, params)
 
@@ -385,24 +380,14 @@ class HipImageReward:
             cfg.num_attention_heads, cfg.intermediate_size, cfg.max_position_embeddings, cfg.layer_norm_eps, 1, 1,
             cfg.max_text_len, cfg.reward_mean, cfg.reward_std)
         _lib.check(self._lib.sd_image_reward_create(C.byref(c), C.byref(self._handle)), "sd_image_reward_create")
-        for name, _ in image_reward_param_shapes(cfg):
-            t = params[name]
-            _lib.check(self._lib.sd_unet_load_param(self._handle, name.encode(), t.data_ptr(), t.numel()), f"load_param({name})")
-        _lib.check(self._lib.sd_unet_finalize(self._handle), "finalize")
+        load_params(self._lib, self._handle, image_reward_param_shapes(cfg), params, "ImageReward")
+        self._finalize()
 
     @classmethod
     def from_pretrained(cls, model_dir: str, device=None) -> "HipImageReward":
         cfg, weights, vocab = read_image_reward_dir(model_dir)           # config errors before any GPU work
         tok = BertWordPieceTokenizer.from_file(vocab, max_length=cfg.max_text_len)
         return cls(cfg, load_image_reward_weights(weights), tok, device=device)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None):
-                self._lib.sd_unet_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
 
     def _score_batch(self, images: torch.Tensor, ids: torch.Tensor, mask: torch.Tensor):
         if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[1] != 3:
@@ -412,21 +397,15 @@ class HipImageReward:
         L = ids.shape[1]
         ids = ids.to(self.device, torch.int32).contiguous()
         mask = mask.to(self.device, torch.int32).contiguous()
-        key = (b, h, w)
-        if self._ws is None or self._ws_key != key:
-            n = self._lib.sd_image_reward_workspace_bytes(self._handle, b, h, w)
-            if n < 0:
-                _lib.check(-1, "sd_image_reward_workspace_bytes")
-            if self._ws is None or self._ws.numel() < n + 256:
-                self._ws = None
-                self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
-            self._ws_key = key
+        if self._sized != (b, h, w):
+            self._wsp.reserve(Workspace.bytes_or_raise(self._lib.sd_image_reward_workspace_bytes(self._handle, b, h, w),
+                                                       "sd_image_reward_workspace_bytes"))
+            self._sized = (b, h, w)
         rewards = torch.empty(b, dtype=torch.float32, device=self.device)
         feats = torch.empty((b, self.config.hidden_size), dtype=torch.float32, device=self.device)
-        wsp = (self._ws.data_ptr() + 255) // 256 * 256
         _lib.check(self._lib.sd_image_reward_score(self._handle, _lib.current_stream(), x.data_ptr(), ids.data_ptr(),
-                                                   mask.data_ptr(), b, L, h, w, rewards.data_ptr(), feats.data_ptr(), wsp,
-                                                   self._ws.numel() - 256), "sd_image_reward_score")
+                                                   mask.data_ptr(), b, L, h, w, rewards.data_ptr(), feats.data_ptr(), self._wsp.ptr,
+                                                   self._wsp.nbytes), "sd_image_reward_score")
         return rewards, feats
 
     def _run(self, prompts, images) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -16,6 +16,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib
+from .handle import ALIGN, HipHandle, Workspace, load_params as _load_params
 from .weights import UNetConfig, param_shapes
 
 CACHE_OFF, CACHE_FULL_AND_STORE, CACHE_SKIP = 0, 1, 2
@@ -47,16 +48,10 @@ def load_params(lib, handle, config: UNetConfig, state_dict: Dict[str, torch.Ten
     """Every parameter ``param_shapes(config)`` names, checked for presence and shape, into the handle
     (``sd_unet_load_param`` copies; host-only, runs without a GPU).  Tensors of any float dtype are accepted --
     diffusers checkpoints are fp16 on disk."""
-    for name, shape in param_shapes(config):
-        if name not in state_dict:
-            raise KeyError(f"state_dict lacks UNet parameter {name!r}")
-        t = state_dict[name].detach().to("cpu", torch.float32).contiguous()
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
-        _lib.check(lib.sd_unet_load_param(handle, name.encode(), t.data_ptr(), t.numel()), f"sd_unet_load_param({name})")
+    _load_params(lib, handle, param_shapes(config), state_dict, "UNet")
 
 
-class HipUNet2DConditionModel:
+class HipUNet2DConditionModel(HipHandle):
     """SD-1.5 UNet running on libsdhip.  ``config`` mirrors the diffusers attributes the
     reference loop reads (``in_channels``, ``sample_size``, ``time_cond_proj_dim``)."""
 
@@ -65,21 +60,15 @@ class HipUNet2DConditionModel:
         """``weight_dtype="fp8"``: OCP e4m3 weights (per-output-channel scales) and e4m3 activations with static
         per-tensor scales for the resnet 3x3 convs, proj_in, the self-attention QKV projection and the feed-forward
         GEMMs (include/sd_hip.h::sd_unet_config.weight_dtype; BASELINE configs[4])."""
-        if not torch.cuda.is_available():
-            raise _lib.SdHipError("HipUNet2DConditionModel needs an MI355X (no CPU fallback exists)")
+        super().__init__(device)
         self.config = config
-        self.device = torch.device(device)
         self.dtype = torch.float32          # dtype of latents / eps crossing the ABI
-        self._lib = _lib.load()
-        self._handle = C.c_void_p()
         torch.cuda.set_device(self.device)
         self.weight_dtype = "fp8_e4m3" if _lib.DTYPES.get(weight_dtype) == _lib.DTYPE_FP8_E4M3 else "bf16"
         ccfg = _c_config(config, weight_dtype, fp8_act_scales)
         _lib.check(self._lib.sd_unet_create(C.byref(ccfg), C.byref(self._handle)), "sd_unet_create")
         load_params(self._lib, self._handle, config, state_dict)
-        _lib.check(self._lib.sd_unet_finalize(self._handle), "sd_unet_finalize")
-        self._ws: Optional[torch.Tensor] = None
-        self._ws_key = None
+        self._finalize()
         self._ctx_key = None
         self._ctx_keepalive = None
         self._cond = None                   # the condition set on the handle (device fp32 [time_cond_proj_dim]) or None
@@ -97,20 +86,12 @@ class HipUNet2DConditionModel:
         self._tome_choice_keepalive = None
         self._freeu = None                  # (s1, s2, b1, b2) on the handle, None = off
         # T-GATE: _tgate = (mode, latent batch, h, w) on the handle or None = off; _tgate_cache = the buffer the handle borrows;
-        # _tgate_ws = workspaces of the gated (reuse) plans by (batch, h, w): the main workspace keeps the prompt context
+        # _tgate_ws = workspace of the gated (reuse) plans, keyed (batch, h, w): the main workspace keeps the prompt context
         self._tgate = None
-        self._tgate_cache = None
-        self._tgate_ws = {}
+        self._tgate_cache = Workspace(self.device)
+        self._tgate_ws = Workspace(self.device)
         self._tgate_reserve = None          # (latent batch, h, w): _workspace also covers the capture plans of that layout
         self.cache_branch_id = -1
-
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None):
-                self._lib.sd_unet_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
 
     # -- workspace / context ---------------------------------------------------------------
     def latent_size(self, height: Optional[int] = None, width: Optional[int] = None):
@@ -118,24 +99,25 @@ class HipUNet2DConditionModel:
         s = self.config.sample_size
         return (s if height is None else int(height)), (s if width is None else int(width))
 
-    def _workspace(self, unet_batch: int, h: Optional[int] = None, w: Optional[int] = None) -> torch.Tensor:
+    def _workspace_bytes(self, unet_batch: int, branch: int, h: int, w: int) -> int:
+        return Workspace.bytes_or_raise(self._lib.sd_unet_workspace_bytes_hw(self._handle, unet_batch, branch, h, w),
+                                        "sd_unet_workspace_bytes_hw")
+
+    def _reserve(self, unet_batch: int, h: Optional[int] = None, w: Optional[int] = None) -> Workspace:
+        """The main workspace for this batch, DeepCache branch and size (exact key: the context lives in it)."""
         h, w = self.latent_size(h, w)
         key = (unet_batch, self.cache_branch_id, h, w)
-        if self._ws is None or self._ws_key != key:
-            n = self._lib.sd_unet_workspace_bytes_hw(self._handle, unet_batch, self.cache_branch_id, h, w)
-            if n < 0:
-                _lib.check(-1, "sd_unet_workspace_bytes_hw")
+        if not self._wsp.holds(key):
+            n = self._workspace_bytes(unet_batch, self.cache_branch_id, h, w)
             if self._tgate_reserve is not None and self._tgate_reserve[1:] == (h, w) and self._tgate is None:
                 n = max(n, self._tgate_capture_bytes(unet_batch, *self._tgate_reserve))
             self._drop_ip_keys()            # (the folded image operands lived in the old workspace, like the context)
-            self._ws = None
-            self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
-            self._ws_key = key
+            self._wsp.reserve(n, key)
             self._ctx_key = None
-        return self._ws
+        return self._wsp
 
-    def _ws_ptr(self, ws: torch.Tensor) -> int:
-        return (ws.data_ptr() + 255) // 256 * 256
+    def _workspace(self, unet_batch: int, h: Optional[int] = None, w: Optional[int] = None) -> torch.Tensor:
+        return self._reserve(unet_batch, h, w).tensor
 
     def set_deepcache(self, cache_branch_id: int) -> None:
         """-1 disables the DeepCache plan; >= 0 reserves that branch's cached tensors."""
@@ -153,9 +135,9 @@ class HipUNet2DConditionModel:
         if ehs.shape[1] != self.config.context_len or ehs.shape[2] != self.config.cross_attention_dim:
             raise ValueError(f"encoder_hidden_states must be [N,{self.config.context_len},"
                              f"{self.config.cross_attention_dim}], got {tuple(ehs.shape)}")
-        ws = self._workspace(ub, h, w)
+        ws = self._reserve(ub, h, w)
         _lib.check(self._lib.sd_unet_set_context_hw(self._handle, _lib.current_stream(), ehs.data_ptr(), ub,
-                                                    self.cache_branch_id, h, w, self._ws_ptr(ws), ws.numel() - 256),
+                                                    self.cache_branch_id, h, w, ws.ptr, ws.nbytes),
                    "sd_unet_set_context_hw")
         self._ctx_keepalive = ehs
         self._ctx_key = (encoder_hidden_states.data_ptr(), encoder_hidden_states._version, ub, h, w)
@@ -235,9 +217,9 @@ class HipUNet2DConditionModel:
         emb = image_embeds.detach().to(self.device, torch.float32).contiguous()
         if emb.data_ptr() % 16:
             emb = emb.clone()
-        ws = self._workspace(ub, h, w)
+        ws = self._reserve(ub, h, w)
         _lib.check(self._lib.sd_unet_set_ip_adapter_hw(self._handle, _lib.current_stream(), emb.data_ptr(), ub, self.cache_branch_id,
-                                                       h, w, float(scale), self._ws_ptr(ws), ws.numel() - 256),
+                                                       h, w, float(scale), ws.ptr, ws.nbytes),
                    "sd_unet_set_ip_adapter_hw")
         self._ip_keepalive = emb
         self._ip_keys.add((ub, self.cache_branch_id, h, w))
@@ -264,8 +246,8 @@ class HipUNet2DConditionModel:
         h, w = self.latent_size(height, width)
         need = residual_layout(self.config, unet_batch, h, w)[1]
         if not torch.is_tensor(residuals) or residuals.dtype != torch.uint8 or residuals.device != self.device or \
-                residuals.numel() < need or residuals.data_ptr() % 256:
-            raise ValueError(f"residuals must be a 256-byte aligned uint8 device tensor of at least {need} bytes "
+                residuals.numel() < need or residuals.data_ptr() % ALIGN:
+            raise ValueError(f"residuals must be a {ALIGN}-byte aligned uint8 device tensor of at least {need} bytes "
                              "(controlnet.new_residual_buffer)")
         _lib.check(self._lib.sd_unet_set_control_residuals_hw(self._handle, residuals.data_ptr(), float(scale), unet_batch, h, w),
                    "sd_unet_set_control_residuals_hw")
@@ -276,19 +258,14 @@ class HipUNet2DConditionModel:
         """The handle sizes the control plan variants only once residuals were set on it: if the live workspace is smaller
         than they need, move it into a larger one.  The context tensors (prompt, image prompt) lie at the same offsets in
         every variant, at the front of the workspace, so the copy keeps them."""
-        if self._ws is None or self._ws_key is None:    # (no key: the next _workspace sizes a new one anyway)
+        old = self._wsp
+        if old.tensor is None or old.key is None:       # (no key: the next _workspace sizes a new one anyway)
             return
-        ub, branch, h, w = self._ws_key
-        n = self._lib.sd_unet_workspace_bytes_hw(self._handle, ub, branch, h, w)
-        if n < 0:
-            _lib.check(-1, "sd_unet_workspace_bytes_hw")
-        have = self._ws.numel() - 256
-        if n > have:
-            old, off = self._ws, self._ws_ptr(self._ws) - self._ws.data_ptr()
-            new = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
-            noff = (-new.data_ptr()) % 256
-            new[noff:noff + have].copy_(old[off:off + have])
-            self._ws = new
+        n = self._workspace_bytes(*old.key)
+        if n > old.nbytes:
+            self._wsp = Workspace(self.device)
+            self._wsp.reserve(n, old.key)
+            self._wsp.view[:old.nbytes].copy_(old.view)
 
     def clear_control_residuals(self) -> None:
         """Forwards are again those of a UNet that never saw a ControlNet, bit for bit."""
@@ -350,9 +327,9 @@ class HipUNet2DConditionModel:
         dst_idx = torch.full((unet_batch, r), -1, dtype=torch.int32)
         tok = torch.full((n,), -1, dtype=torch.int32)
         rr, bb = C.c_int(), C.c_int()
-        ws = self._workspace(unet_batch, lh, lw)
+        ws = self._reserve(unet_batch, lh, lw)
         _lib.check(self._lib.sd_unet_tome_matching_hw(self._handle, _lib.current_stream(), block, unet_batch, self.cache_branch_id,
-                                                      self._ws_ptr(ws), kept.data_ptr(), merged.data_ptr(), dst_idx.data_ptr(),
+                                                      ws.ptr, kept.data_ptr(), merged.data_ptr(), dst_idx.data_ptr(),
                                                       tok.data_ptr(), C.byref(rr), C.byref(bb)), "sd_unet_tome_matching_hw")
         b = bb.value
         # (the library wrote B rows contiguously at the row lengths above)
@@ -422,36 +399,30 @@ class HipUNet2DConditionModel:
             out.append(dict(offset=off.value, rows=rows.value, channels=ch.value))
         return out
 
-    def tgate_cache(self, latent_batch: int, height: Optional[int] = None, width: Optional[int] = None) -> torch.Tensor:
-        """The cache buffer for ``latent_batch`` latents at this size (uint8, 256-byte aligned; kept and reused while it fits)."""
-        lh, lw = self.latent_size(height, width)
-        n = self._lib.sd_unet_tgate_bytes_hw(self._handle, latent_batch, lh, lw)
-        if n < 0:
-            _lib.check(-1, "sd_unet_tgate_bytes_hw")
-        if self._tgate_cache is None or self._tgate_cache.numel() < n + 256:
-            self._tgate_cache = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+    def _reserve_tgate_cache(self, latent_batch: int, h: int, w: int) -> Workspace:
+        n = Workspace.bytes_or_raise(self._lib.sd_unet_tgate_bytes_hw(self._handle, latent_batch, h, w), "sd_unet_tgate_bytes_hw")
+        self._tgate_cache.reserve(n)        # (grow-only: kept and reused while it fits)
         return self._tgate_cache
+
+    def tgate_cache(self, latent_batch: int, height: Optional[int] = None, width: Optional[int] = None) -> torch.Tensor:
+        """The cache buffer for ``latent_batch`` latents at this size (uint8, with slack to align it; kept while it fits)."""
+        return self._reserve_tgate_cache(latent_batch, *self.latent_size(height, width)).tensor
 
     def tgate_cache_block(self, block: int, latent_batch: int, height: Optional[int] = None, width: Optional[int] = None) -> torch.Tensor:
         """Slice ``block`` of the cache as a bf16 tensor [rows, channels] (a view of the buffer)."""
         info = self.tgate_blocks(latent_batch, height, width)[block]
-        buf = self._tgate_cache
-        off = (-buf.data_ptr()) % 256 + info["offset"]
+        buf, off = self._tgate_cache.view, info["offset"]
         return buf[off:off + info["rows"] * info["channels"] * 2].view(torch.bfloat16).view(info["rows"], info["channels"])
 
     def _tgate_capture_bytes(self, unet_batch: int, latent_batch: int, h: int, w: int) -> int:
         """Workspace bytes of the capture plans of ``unet_batch`` (the handle is left off)."""
-        buf = self.tgate_cache(latent_batch, h, w)
-        p = self._ws_ptr(buf)
-        _lib.check(self._lib.sd_unet_set_tgate_hw(self._handle, self.TGATE_CAPTURE, p, buf.numel() - 256, latent_batch, h, w),
+        buf = self._reserve_tgate_cache(latent_batch, h, w)
+        _lib.check(self._lib.sd_unet_set_tgate_hw(self._handle, self.TGATE_CAPTURE, buf.ptr, buf.nbytes, latent_batch, h, w),
                    "sd_unet_set_tgate_hw")
         try:
-            n = self._lib.sd_unet_workspace_bytes_hw(self._handle, unet_batch, self.cache_branch_id, h, w)
-            if n < 0:
-                _lib.check(-1, "sd_unet_workspace_bytes_hw")
+            return self._workspace_bytes(unet_batch, self.cache_branch_id, h, w)
         finally:
             _lib.check(self._lib.sd_unet_set_tgate_hw(self._handle, self.TGATE_OFF, None, 0, 0, 0, 0), "sd_unet_set_tgate_hw")
-        return n
 
     def reserve_tgate(self, latent_batch: Optional[int], height: Optional[int] = None, width: Optional[int] = None) -> None:
         """Before ``set_context``: size the next workspace for the capture plans of ``latent_batch`` latents at this size as well,
@@ -462,8 +433,8 @@ class HipUNet2DConditionModel:
             self._tgate_reserve = new
             self._ws_key = None
             if new is None:
-                self._tgate_ws = {}
-                self._tgate_cache = None
+                self._tgate_ws.clear()
+                self._tgate_cache.clear()
 
     def set_tgate(self, mode: int, latent_batch: int = 0, height: Optional[int] = None, width: Optional[int] = None) -> None:
         """T-GATE state of the handle.  ``TGATE_CAPTURE``: the next forward (UNet batch ``latent_batch``, or twice it for a CFG
@@ -481,23 +452,18 @@ class HipUNet2DConditionModel:
         if self._control is not None or self._ip_on:
             raise NotImplementedError("T-GATE with ControlNet residuals or an IP-Adapter image prompt set is refused")
         h, w = self.latent_size(height, width)
-        buf = self.tgate_cache(latent_batch, h, w)
-        _lib.check(self._lib.sd_unet_set_tgate_hw(self._handle, int(mode), self._ws_ptr(buf), buf.numel() - 256, int(latent_batch), h, w),
+        buf = self._reserve_tgate_cache(latent_batch, h, w)
+        _lib.check(self._lib.sd_unet_set_tgate_hw(self._handle, int(mode), buf.ptr, buf.nbytes, int(latent_batch), h, w),
                    "sd_unet_set_tgate_hw")
         self._tgate = (int(mode), int(latent_batch), h, w)
         if mode == self.TGATE_CAPTURE and self._ws is not None and self._ws_key is not None and self._ws_key[2:] == (h, w):
             self._grow_workspace_for_control()      # (a workspace sized before the capture plans were asked for: keep its context)
 
-    def _tgate_workspace(self, unet_batch: int, h: int, w: int) -> torch.Tensor:
+    def _tgate_workspace(self, unet_batch: int, h: int, w: int) -> Workspace:
         key = (unet_batch, h, w)
-        ws = self._tgate_ws.get(key)
-        if ws is None:
-            n = self._lib.sd_unet_workspace_bytes_hw(self._handle, unet_batch, -1, h, w)
-            if n < 0:
-                _lib.check(-1, "sd_unet_workspace_bytes_hw")
-            self._tgate_ws = {key: torch.empty(n + 256, dtype=torch.uint8, device=self.device)}
-            ws = self._tgate_ws[key]
-        return ws
+        if not self._tgate_ws.holds(key):
+            self._tgate_ws.reserve(self._workspace_bytes(unet_batch, -1, h, w), key)
+        return self._tgate_ws
 
     def plan_count(self) -> int:
         """Execution plans the handle has built so far."""
@@ -529,9 +495,9 @@ class HipUNet2DConditionModel:
             latents = latents.to(self.device, torch.float32).contiguous()
         if out is None:
             out = torch.empty((unet_batch, self.config.out_channels, h, w), dtype=torch.float32, device=self.device)
-        ws = self._tgate_workspace(unet_batch, h, w) if gated else self._workspace(unet_batch, h, w)
+        ws = self._tgate_workspace(unet_batch, h, w) if gated else self._reserve(unet_batch, h, w)
         _lib.check(self._lib.sd_unet_forward_hw(self._handle, _lib.current_stream(), latents.data_ptr(), b, unet_batch, h, w,
-                                                float(timestep), out.data_ptr(), self._ws_ptr(ws), ws.numel() - 256,
+                                                float(timestep), out.data_ptr(), ws.ptr, ws.nbytes,
                                                 cache_mode, self.cache_branch_id), "sd_unet_forward_hw")
         return out
 
@@ -554,10 +520,10 @@ class HipUNet2DConditionModel:
         latents = latents.to(self.device, torch.float32).contiguous()
         if tuple(latents.shape[1:]) != (LATENT_CHANNELS, s, s):
             raise ValueError(f"calibrate_fp8: latents must be [B,{LATENT_CHANNELS},{s},{s}] (sample_size), got {tuple(latents.shape)}")
-        ws = self._workspace(unet_batch)
+        ws = self._reserve(unet_batch)
         for t in timesteps:
             _lib.check(self._lib.sd_unet_calibrate_fp8(self._handle, _lib.current_stream(), latents.data_ptr(), latents.shape[0],
-                                                       unet_batch, float(t), float(margin), self._ws_ptr(ws), ws.numel() - 256),
+                                                       unet_batch, float(t), float(margin), ws.ptr, ws.nbytes),
                        "sd_unet_calibrate_fp8")
         return self.fp8_scales()
 
@@ -594,12 +560,12 @@ class HipUNet2DConditionModel:
         out = torch.empty((unet_batch, self.config.out_channels, latents.shape[2], latents.shape[3]),
                           dtype=torch.float32, device=self.device)
         gated = self._tgate is not None and self._tgate[0] == self.TGATE_REUSE
-        ws = self._tgate_workspace(unet_batch, s, s) if gated else self._workspace(unet_batch)
+        ws = self._tgate_workspace(unet_batch, s, s) if gated else self._reserve(unet_batch)
         ms, fl, by = (C.c_double * 32)(), (C.c_double * 32)(), (C.c_double * 32)()
         ln = (C.c_longlong * 32)()
         _lib.check(self._lib.sd_unet_forward_profiled(
             self._handle, _lib.current_stream(), latents.data_ptr(), latents.shape[0], unet_batch, float(timestep),
-            out.data_ptr(), self._ws_ptr(ws), ws.numel() - 256, cache_mode, self.cache_branch_id, ms, ln, fl, by),
+            out.data_ptr(), ws.ptr, ws.nbytes, cache_mode, self.cache_branch_id, ms, ln, fl, by),
             "sd_unet_forward_profiled")
         return {n: dict(ms=ms[i], launches=ln[i], flops=fl[i], bytes=by[i]) for i, n in self.KIND_NAMES.items()
                 if ln[i] or i < 9}
@@ -691,8 +657,8 @@ class HipUNet2DConditionModel:
                      width: Optional[int] = None) -> torch.Tensor:
         """Tap ``name`` of the last forward; ``height`` / ``width``: its latent size (default ``sample_size``)."""
         out = torch.empty(numel, dtype=torch.float32)
-        ws = self._workspace(unet_batch, height, width)
+        ws = self._reserve(unet_batch, height, width)
         _lib.check(self._lib.sd_unet_debug_tensor(self._handle, _lib.current_stream(), name.encode(), out.data_ptr(),
-                                                  numel, self._ws_ptr(ws), unet_batch, self.cache_branch_id),
+                                                  numel, ws.ptr, unet_batch, self.cache_branch_id),
                    "sd_unet_debug_tensor")
         return out

@@ -23,6 +23,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
+from .handle import HipHandle, Workspace, load_params
 
 
 @dataclass
@@ -164,49 +165,34 @@ def _c_config(cfg: VaeConfig) -> _lib.SdUnetConfigFull:
     return c
 
 
-class HipVaeDecoder:
+class _VaeHandle(HipHandle):
+    """What the four autoencoder halves share: the parameter loop with the legacy reshape, and one workspace per
+    (batch, h, w) (exact key)."""
+
+    def _load(self, shapes, state_dict: Dict[str, torch.Tensor]) -> None:
+        load_params(self._lib, self._handle, shapes, state_dict, "VAE", reshape_legacy=True)
+        self._finalize()
+
+    def _reserve(self, batch: int, h: int, w: int) -> Workspace:
+        if not self._wsp.holds((batch, h, w)):
+            n = Workspace.bytes_or_raise(self._lib.sd_unet_workspace_bytes_hw(self._handle, batch, -1, h, w),
+                                         "sd_unet_workspace_bytes_hw")
+            self._wsp.reserve(n, (batch, h, w))
+        return self._wsp
+
+    def _workspace(self, batch: int, h: int, w: int) -> torch.Tensor:
+        return self._reserve(batch, h, w).tensor
+
+
+class HipVaeDecoder(_VaeHandle):
     """``vae.decode`` replacement: ``decoder(latents) -> [B,3,8h,8w]`` fp32 on the GPU."""
 
     def __init__(self, config: VaeConfig, state_dict: Dict[str, torch.Tensor], device: str = "cuda:0"):
-        if not torch.cuda.is_available():
-            raise _lib.SdHipError("HipVaeDecoder needs an MI355X (no CPU fallback exists)")
+        super().__init__(device)
         self.config = config
-        self.device = torch.device(device)
-        self._lib = _lib.load()
-        self._handle = C.c_void_p()
         torch.cuda.set_device(self.device)
         _lib.check(self._lib.sd_vae_create(C.byref(_c_config(config)), C.byref(self._handle)), "sd_vae_create")
-        for name, shape in vae_param_shapes(config):
-            if name not in state_dict:
-                raise KeyError(f"state_dict lacks VAE parameter {name!r}")
-            t = state_dict[name].detach().to("cpu", torch.float32).contiguous()
-            if t.dim() == 4 and len(shape) == 2:       # legacy attention weights stored as 1x1 convs
-                t = t.reshape(shape)
-            if tuple(t.shape) != tuple(shape):
-                raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
-            _lib.check(self._lib.sd_unet_load_param(self._handle, name.encode(), t.data_ptr(), t.numel()),
-                       f"load_param({name})")
-        _lib.check(self._lib.sd_unet_finalize(self._handle), "finalize")
-        self._ws: Optional[torch.Tensor] = None
-        self._ws_key = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None):
-                self._lib.sd_unet_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
-
-    def _workspace(self, batch: int, h: int, w: int) -> torch.Tensor:
-        if self._ws is None or self._ws_key != (batch, h, w):
-            n = self._lib.sd_unet_workspace_bytes_hw(self._handle, batch, -1, h, w)
-            if n < 0:
-                _lib.check(-1, "sd_unet_workspace_bytes_hw")
-            self._ws = None
-            self._ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
-            self._ws_key = (batch, h, w)
-        return self._ws
+        self._load(vae_param_shapes(config), state_dict)
 
     def decode(self, latents: torch.Tensor, latent_scale: float = 1.0, chunk: int = 8) -> torch.Tensor:
         """``latents * latent_scale`` -> decoded images (pass ``1 / scaling_factor`` to fuse the division
@@ -221,48 +207,25 @@ class HipVaeDecoder:
         out = torch.empty((b, self.config.out_channels, 8 * h, 8 * w), dtype=torch.float32, device=self.device)
         for s in range(0, b, chunk):
             n = min(chunk, b - s)
-            ws = self._workspace(n, h, w)
-            wsp = (ws.data_ptr() + 255) // 256 * 256
+            ws = self._reserve(n, h, w)
             _lib.check(self._lib.sd_vae_decode_hw(self._handle, _lib.current_stream(), lat[s:s + n].data_ptr(), n, h, w,
-                                                  float(latent_scale), out[s:s + n].data_ptr(), wsp, ws.numel() - 256),
+                                                  float(latent_scale), out[s:s + n].data_ptr(), ws.ptr, ws.nbytes),
                        "sd_vae_decode_hw")
         return out
 
     __call__ = decode
 
 
-def _load_params(lib, handle, shapes, state_dict, what: str):
-    for name, shape in shapes:
-        if name not in state_dict:
-            raise KeyError(f"state_dict lacks VAE parameter {name!r}")
-        t = state_dict[name].detach().to("cpu", torch.float32).contiguous()
-        if t.dim() == 4 and len(shape) == 2:       # legacy attention weights stored as 1x1 convs
-            t = t.reshape(shape)
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
-        _lib.check(lib.sd_unet_load_param(handle, name.encode(), t.data_ptr(), t.numel()), f"load_param({name})")
-    _lib.check(lib.sd_unet_finalize(handle), f"finalize({what})")
-
-
-class HipVaeEncoder:
+class HipVaeEncoder(_VaeHandle):
     """``vae.encode`` replacement: ``encode(images) -> moments [B, 8, H/8, W/8]`` (``[mean | logvar]``, fp32, on the GPU) and
     ``sample(moments)`` = ``DiagonalGaussianDistribution.sample() / .mode()`` times the scaling factor."""
 
     def __init__(self, config: VaeConfig, state_dict: Dict[str, torch.Tensor], device: str = "cuda:0"):
-        if not torch.cuda.is_available():
-            raise _lib.SdHipError("HipVaeEncoder needs an MI355X (no CPU fallback exists)")
+        super().__init__(device)
         self.config = config
-        self.device = torch.device(device)
-        self._lib = _lib.load()
-        self._handle = C.c_void_p()
         torch.cuda.set_device(self.device)
         _lib.check(self._lib.sd_vae_encoder_create(C.byref(_c_config(config)), C.byref(self._handle)), "sd_vae_encoder_create")
-        _load_params(self._lib, self._handle, vae_encoder_param_shapes(config), state_dict, "vae encoder")
-        self._ws: Optional[torch.Tensor] = None
-        self._ws_key = None
-
-    __del__ = HipVaeDecoder.__del__
-    _workspace = HipVaeDecoder._workspace
+        self._load(vae_encoder_param_shapes(config), state_dict)
 
     def encode(self, images: torch.Tensor, chunk: int = 8) -> torch.Tensor:
         """``images`` [B, 3, H, W] in [0, 1] (the ``2x - 1`` of diffusers' VaeImageProcessor happens in the entry kernel) ->
@@ -278,10 +241,9 @@ class HipVaeEncoder:
         out = torch.empty((b, 2 * self.config.in_channels, h, w), dtype=torch.float32, device=self.device)
         for s in range(0, b, chunk):
             n = min(chunk, b - s)
-            ws = self._workspace(n, h, w)
-            wsp = (ws.data_ptr() + 255) // 256 * 256
+            ws = self._reserve(n, h, w)
             _lib.check(self._lib.sd_vae_encode_hw(self._handle, _lib.current_stream(), img[s:s + n].data_ptr(), n, h, w,
-                                                  out[s:s + n].data_ptr(), wsp, ws.numel() - 256), "sd_vae_encode_hw")
+                                                  out[s:s + n].data_ptr(), ws.ptr, ws.nbytes), "sd_vae_encode_hw")
         return out
 
     def sample(self, moments: torch.Tensor, noise: Optional[torch.Tensor] = None, mode: str = "sample",
@@ -445,25 +407,16 @@ def load_tiny_vae_state_dict(model_dir: str) -> Dict[str, torch.Tensor]:
     return sd
 
 
-class _HipTinyHalf:
+class _HipTinyHalf(_VaeHandle):
     _create = ""
     _shapes = staticmethod(lambda: [])
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], config: Optional[TinyVaeConfig] = None, device: str = "cuda:0"):
-        if not torch.cuda.is_available():
-            raise _lib.SdHipError(f"{type(self).__name__} needs an MI355X (no CPU fallback exists)")
+        super().__init__(device)
         self.config = check_tiny_vae_config(config or TinyVaeConfig())
-        self.device = torch.device(device)
-        self._lib = _lib.load()
-        self._handle = C.c_void_p()
         torch.cuda.set_device(self.device)
         _lib.check(getattr(self._lib, self._create)(C.byref(self._handle)), self._create)
-        _load_params(self._lib, self._handle, self._shapes(), state_dict, type(self).__name__)
-        self._ws: Optional[torch.Tensor] = None
-        self._ws_key = None
-
-    __del__ = HipVaeDecoder.__del__
-    _workspace = HipVaeDecoder._workspace
+        self._load(self._shapes(), state_dict)
 
 
 class HipTinyVaeDecoder(_HipTinyHalf):
@@ -484,10 +437,9 @@ class HipTinyVaeDecoder(_HipTinyHalf):
         out = torch.empty((b, 3, 8 * h, 8 * w), dtype=torch.float32, device=self.device)
         for s in range(0, b, chunk):
             n = min(chunk, b - s)
-            ws = self._workspace(n, h, w)
-            wsp = (ws.data_ptr() + 255) // 256 * 256
+            ws = self._reserve(n, h, w)
             _lib.check(self._lib.sd_taesd_decode_hw(self._handle, _lib.current_stream(), lat[s:s + n].data_ptr(), n, h, w,
-                                                    1 if unit_range else 0, out[s:s + n].data_ptr(), wsp, ws.numel() - 256),
+                                                    1 if unit_range else 0, out[s:s + n].data_ptr(), ws.ptr, ws.nbytes),
                        "sd_taesd_decode_hw")
         return out
 
@@ -512,10 +464,9 @@ class HipTinyVaeEncoder(_HipTinyHalf):
         out = torch.empty((b, 4, h, w), dtype=torch.float32, device=self.device)
         for s in range(0, b, chunk):
             n = min(chunk, b - s)
-            ws = self._workspace(n, h, w)
-            wsp = (ws.data_ptr() + 255) // 256 * 256
+            ws = self._reserve(n, h, w)
             _lib.check(self._lib.sd_taesd_encode_hw(self._handle, _lib.current_stream(), img[s:s + n].data_ptr(), n, h, w,
-                                                    out[s:s + n].data_ptr(), wsp, ws.numel() - 256), "sd_taesd_encode_hw")
+                                                    out[s:s + n].data_ptr(), ws.ptr, ws.nbytes), "sd_taesd_encode_hw")
         return out
 
     __call__ = encode

@@ -15,13 +15,13 @@ u.set_context(torch.randn(ub, 77, 768, device="cuda"))
 for _ in range(2):
     u.forward_latents(x, ub, 501.0)
 out = torch.empty(ub, 4, 64, 64, device="cuda")
-ws = u._workspace(ub)
+ws = u._reserve(ub)
 buf = C.create_string_buffer(1 << 20)
 acc = collections.OrderedDict()
 REP = 5
 for _ in range(REP):
     n = u._lib.sd_unet_forward_op_times(u._handle, _lib.current_stream(), x.data_ptr(), x.shape[0], ub, 501.0, out.data_ptr(),
-                                        u._ws_ptr(ws), ws.numel() - 256, 0, u.cache_branch_id, buf, len(buf))
+                                        ws.ptr, ws.nbytes, 0, u.cache_branch_id, buf, len(buf))
     assert n > 0, u._lib.sd_last_error()
     for line in buf.value.decode().splitlines():
         i, kind, M, N, K, ms, gf, mb = line.split()
