@@ -270,6 +270,20 @@ int sd_unet_set_tgate_hw(sd_unet* u, int mode, void* cache, long long bytes, int
  * null handle.  For tests of "this setting builds no new plan". */
 int sd_unet_plan_count(const sd_unet* u);
 
+/* HyperTile (tfernd/HyperTile, swap_size = 1): tiled self-attention.  tile_tokens = the tile side T in tokens (tile_size / 8), 8 or
+ * more; max_depth 0..3; tile_tokens 0 = off = the plans, workspace sizes and results of a handle that never saw it.  A transformer
+ * block on rh x rw tokens at depth d = log2(latent_h / rh) <= max_depth is cut into nh x nw tiles of th x tw tokens, th = the smallest
+ * divisor of rh that is >= min(T, rh) (tw likewise); it is tiled when nh nw > 1.  A tiled block gathers its input into tile order
+ * (profile kind 9), runs WHOLE in that order with every fold of the plain plan -- only attn1 changes, to batch * nh nw samples of
+ * th tw keys -- and scatters the exit GEMM's output back (kind 10).  The setting is part of the plan key; after a change call
+ * sd_unet_workspace_bytes_hw and sd_unet_set_context_hw again.  bf16 UNet handles only, not together with Token Merging.
+ * block_count / block_info: the tiled blocks at a latent size in plan order (down, mid, up) with their token grid and tile counts.
+ * They report the FULL plan: which blocks tile depends on the latent size and the setting alone, and a DeepCache skip step runs
+ * the subset of these blocks its branch keeps, tiled the same way (there is no per-branch view). */
+int sd_unet_set_hypertile(sd_unet* u, int tile_tokens, int max_depth);
+int sd_unet_hypertile_block_count_hw(sd_unet* u, int latent_h, int latent_w);
+int sd_unet_hypertile_block_info_hw(sd_unet* u, int block, int latent_h, int latent_w, int* rh, int* rw, int* nh, int* nw);
+
 enum { SD_CACHE_OFF = 0, SD_CACHE_FULL_AND_STORE = 1, SD_CACHE_SKIP = 2 };
 
 /* eps = UNet(latent_model_input, t, encoder_hidden_states)  (src/models.py:217-235).
@@ -720,6 +734,16 @@ int sd_op_tgate_capture(void* stream, const void* y, const void* res, void* h2, 
 int sd_op_tgate_apply(void* stream, const void* h1, const void* cache, void* h2, float* rowstats, long long rows, int C);
 int sd_op_freeu(void* stream, const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W,
                 int C_hidden, int C_skip, float b, float s);
+/* HyperTile's copy kernel on its own (csrc/hypertile.hip).  Raster order: [B][rh][rw] rows of C bf16 channels with a row
+ * pitch of `pitch` elements; tile order: [B][nh][nw][rh / nh][rw / nw] dense rows of C -- tile (i, j) holds the tokens
+ * (i th + y, j tw + x), row-major inside the tile, the tiles row-major in the sample.  gather: raster x -> tile-order out; scatter:
+ * tile-order y -> raster out.  16-byte accesses and 64-bit offsets; bit-exact copies.
+ * sd_hypertile_check: the shape rule of both (and of the plan builder), no GPU work: 1 <= B <= 65535, sides in 1..256, nh | rh and
+ * nw | rw, C a multiple of 8 up to 16384, pitch a multiple of 8, >= C and <= 2^30 (so that no element offset leaves 63 bits).  What it refuses the ops refuse by name, writing nothing;
+ * they also want 16-byte-aligned pointers. */
+int sd_hypertile_check(int B, int rh, int rw, int C, int nh, int nw, long long pitch);
+int sd_op_hypertile_gather(void* stream, const void* x, long long pitch, void* out, int B, int rh, int rw, int C, int nh, int nw);
+int sd_op_hypertile_scatter(void* stream, const void* y, void* out, long long pitch, int B, int rh, int rw, int C, int nh, int nw);
 /* flash-style attention on token-major [B, N, heads * D] views; D = 40, 64, 80 or 160 (64: Stable Diffusion 2.x), any Nq / Nk */
 int sd_op_attention(void* stream, const void* Q, long long ldq, const void* K, long long ldk, const void* V,
                     long long ldv, void* O, long long ldo, int B, int heads, int Nq, int Nk, int D, float scale);

@@ -246,6 +246,12 @@ _SIGS = {
     "sd_unet_set_tgate_hw": (_i, [_vp, _i, _vp, _ll, _i, _i, _i]),
     "sd_op_tgate_capture": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i]),
     "sd_op_tgate_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _i]),
+    "sd_unet_set_hypertile": (_i, [_vp, _i, _i]),
+    "sd_unet_hypertile_block_count_hw": (_i, [_vp, _i, _i]),
+    "sd_unet_hypertile_block_info_hw": (_i, [_vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "sd_hypertile_check": (_i, [_i, _i, _i, _i, _i, _i, _ll]),
+    "sd_op_hypertile_gather": (_i, [_vp, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i]),
+    "sd_op_hypertile_scatter": (_i, [_vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i]),
 }
 
 

@@ -246,6 +246,13 @@ int sd_launch_tgate_capture(const bf16_t* y, const bf16_t* res, bf16_t* h2, bf16
                             hipStream_t stream);
 int sd_launch_tgate_apply(const bf16_t* h1, const bf16_t* cache, bf16_t* h2, float* rowstats, long rows, int C, hipStream_t stream);
 
+// hypertile.hip: HyperTile's gather / scatter (one kernel): raster [B][rh][rw] rows of C bf16 channels and row pitch `pitch`
+// <-> tile order [B][nh][nw][rh / nh][rw / nw] dense rows.  C a multiple of 8 (16-byte accesses), nh | rh, nw | rw, sides up to
+// 256, pitch up to 2^30; 64-bit offsets.  shape_ok: the shape rule of both launchers and of the plan builder (no GPU work).
+int sd_hypertile_shape_ok(int B, int rh, int rw, int C, int nh, int nw, long pitch, const char* who);
+int sd_launch_hypertile_gather(const bf16_t* x, long pitch, bf16_t* out, int B, int rh, int rw, int C, int nh, int nw, hipStream_t stream);
+int sd_launch_hypertile_scatter(const bf16_t* y, bf16_t* out, long pitch, int B, int rh, int rw, int C, int nh, int nw, hipStream_t stream);
+
 // xattn.hip: fused prompt cross-attention  Y = R + sum_h softmax_L(X A_h) B_h + b_o  (one launch per block)
 struct XattnArgs {
     const bf16_t* X = nullptr;    // [M, C] LayerNorm output

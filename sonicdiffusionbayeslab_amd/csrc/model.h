@@ -48,7 +48,8 @@ enum OpKind { OP_SINUSOID, OP_GEMV, OP_CONV_IN, OP_GN, OP_CONV3, OP_GEMM, OP_LN,
               OP_BERT_ATTN, OP_REWARD_HEAD,
               OP_TOME_MATCH, OP_TOME_SELECT, OP_TOME_MERGE, OP_TOME_UNMERGE,
               OP_FREEU,
-              OP_TGATE_CAPTURE, OP_TGATE_APPLY, OP_TGATE_ZERO };
+              OP_TGATE_CAPTURE, OP_TGATE_APPLY, OP_TGATE_ZERO,
+              OP_HT_GATHER, OP_HT_SCATTER };
 
 constexpr int TGATE_OFF = 0, TGATE_CAPTURE = 1, TGATE_REUSE = 2;      // sd_unet_set_tgate_hw modes
 
@@ -177,6 +178,10 @@ struct Plan {
     struct TomeBlock { int tok, kept, merged, dst_idx, B, h, w, r; long choice_off; };
     std::vector<TomeBlock> tome;
     long tome_choice_bytes = 0;
+    // HyperTile variant (the handle's setting is part of the plan key): the tiled transformer blocks in plan order, each with its
+    // token grid and tile counts (sd_unet_hypertile_block_info_hw)
+    struct HtBlock { int rh, rw, nh, nw; };
+    std::vector<HtBlock> hypertile;
     // FreeU variant (part of the plan key): one OP_FREEU in front of every resnet of up blocks 0 and 1 (x1 = hidden, x2 = skip ->
     // out = the scaled hidden, aux = the filtered skip, epi = the up block: which pair of the handle's factors the launch reads)
     int freeu = 0;
@@ -254,8 +259,8 @@ struct sd_unet {
     }
     // (UNet batch, DeepCache branch, prefix replication, latent H, W, IP-Adapter variant, control variant, Token Merging: the
     // bits of the ratio and max_downsample, both 0 = off; FreeU on / off; T-GATE mode: TGATE_OFF / CAPTURE / REUSE; T-GATE pair: y rows per
-    // cache row of a capture, 2 for a CFG pair, else 1)
-    std::map<std::tuple<int, int, int, int, int, int, int, long long, int, int, int, int>, sdhip::Plan> plans;
+    // cache row of a capture, 2 for a CFG pair, else 1; HyperTile: tile side in tokens and max_depth, both 0 = off)
+    std::map<std::tuple<int, int, int, int, int, int, int, long long, int, int, int, int, int, int>, sdhip::Plan> plans;
     int last_rep = 1, last_ip = 0, last_cn = 0;                       // variant of the last forward (sd_unet_debug_tensor)
     int last_h = 0, last_w = 0;                          // latent size of the last forward (sd_unet_debug_tensor)
     std::unordered_map<std::string, long> tproj_off;  // resnet prefix -> float index into tproj vector
@@ -298,6 +303,8 @@ struct sd_unet {
     unsigned char* tome_choice = nullptr;
     size_t tome_choice_cap = 0;
     long tome_choice_n = 0;
+    // HyperTile (sd_unet_set_hypertile; kind 0, bf16): the tile side in tokens, 0 = off = the plans of a handle that never saw it
+    int ht_tokens = 0, ht_max_depth = 0;
     // FreeU (sd_unet_set_freeu; kind 0, bf16): on = the "freeu" plan variants; the factors are read when OP_FREEU is launched
     bool freeu_on = false;
     float freeu_s[2] = {1.f, 1.f}, freeu_b[2] = {1.f, 1.f};       // (s1, s2), (b1, b2): up block 0, up block 1

@@ -502,6 +502,17 @@ extern "C" int sd_op_tgate_apply(void* stream, const void* h1, const void* cache
     return sd_launch_tgate_apply((const bf16_t*)h1, (const bf16_t*)cache, (bf16_t*)h2, rowstats, (long)rows, C, (hipStream_t)stream);
 }
 
+// HyperTile's tile gather / scatter (hypertile.hip) and their shape rule
+extern "C" int sd_hypertile_check(int B, int rh, int rw, int C, int nh, int nw, long long pitch) {
+    return sd_hypertile_shape_ok(B, rh, rw, C, nh, nw, (long)pitch, "sd_hypertile_check");
+}
+extern "C" int sd_op_hypertile_gather(void* stream, const void* x, long long pitch, void* out, int B, int rh, int rw, int C, int nh, int nw) {
+    return sd_launch_hypertile_gather((const bf16_t*)x, (long)pitch, (bf16_t*)out, B, rh, rw, C, nh, nw, (hipStream_t)stream);
+}
+extern "C" int sd_op_hypertile_scatter(void* stream, const void* y, void* out, long long pitch, int B, int rh, int rw, int C, int nh, int nw) {
+    return sd_launch_hypertile_scatter((const bf16_t*)y, (bf16_t*)out, (long)pitch, B, rh, rw, C, nh, nw, (hipStream_t)stream);
+}
+
 // Token Merging, kernel by kernel (tome.hip); index lists in src / dst slot numbers, tok [h * w] from sd_op_tome_match
 extern "C" int sd_op_tome_match(void* stream, const void* x, const unsigned char* choice, int B, int h, int w, int C,
                                 float* node_max, int* node_idx, int* tok) {

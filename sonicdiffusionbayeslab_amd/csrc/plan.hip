@@ -197,11 +197,12 @@ struct Builder {
         push(o);
         return o.out;
     }
-    int attn(int q, long qoff, long ldq, int kv, long koff, long voff, long ldkv, int nq, int nk, int C, int heads) {
+    // B: the samples the kernel sees (UB, or UB x tiles for the self-attention of a HyperTile block)
+    int attn(int q, long qoff, long ldq, int kv, long koff, long voff, long ldkv, int nq, int nk, int C, int heads, int B) {
         Op o; o.kind = OP_ATTN; o.x1 = q; o.x2 = kv; o.qoff = qoff; o.koff = koff; o.voff = voff;
-        o.ldq = ldq; o.ldk = o.ldv = ldkv; o.ldo = C; o.B = UB; o.heads = heads; o.D = C / heads;
+        o.ldq = ldq; o.ldk = o.ldv = ldkv; o.ldo = C; o.B = B; o.heads = heads; o.D = C / heads;
         o.Nq = nq; o.Nk = nk;
-        o.out = tensor((size_t)UB * nq * C * 2);
+        o.out = tensor((size_t)B * nq * C * 2);
         push(o);
         return o.out;
     }
@@ -245,9 +246,48 @@ struct Builder {
         }
         return std::min(N - N / 4, (int)((double)N * u->tome_ratio));
     }
-    // Transformer2DModel with one BasicTransformerBlock (A.4)
+    // HyperTile: the tile counts (nh, nw) of a block on rh x rw tokens; 1 x 1 = the block is not tiled (the setting is off, the
+    // level is deeper than max_depth, or no divisor gives more than one tile).  The tile side th is the smallest divisor of rh
+    // that is >= min(T, rh) -- upstream's first option, what swap_size = 1 selects -- and tw likewise.  UNet handles only (a
+    // ControlNet's own handle never tiles).
+    static int ht_tile_side(int r, int T) {
+        for (int d = std::min(T, r); d <= r; ++d)
+            if (r % d == 0) return d;
+        return r;
+    }
+    void hypertile_tiles(int rh, int rw, int* nh, int* nw) {
+        *nh = *nw = 1;
+        if (u->kind != 0 || u->fp8 || u->ht_tokens <= 0 || rh <= 0 || rw <= 0 || pl.lh / rh > (1 << u->ht_max_depth)) return;
+        *nh = rh / ht_tile_side(rh, u->ht_tokens);
+        *nw = rw / ht_tile_side(rw, u->ht_tokens);
+    }
+    // Transformer2DModel with one BasicTransformerBlock (A.4).  A HyperTile block (hypertile.hip): ONE gather of the block input
+    // into tile order, the whole block on it exactly as the plain plan runs it on x -- every op but attn1 is row-wise or per
+    // sample, and the tile order permutes rows inside a sample -- and ONE scatter of the exit GEMM's output (which carries the
+    // gathered residual).  The producers' GroupNorm statistics are per 64-row block, summed per sample: they describe a
+    // permuted tensor as well as the original, so the entry GroupNorm keeps x's statistics and the next resnet's GroupNorm
+    // gets the exit GEMM's.
     int n_transformers = 0;
     int transformer(const std::string& p, int x, int C, int rh, int rw) {
+        int ht_nh, ht_nw;
+        hypertile_tiles(rh, rw, &ht_nh, &ht_nw);
+        if (ht_nh * ht_nw == 1) return transformer_block(p, x, C, rh, rw, 1);
+        if (u->tome_ratio > 0.0) { if (error.empty()) error = "HyperTile and Token Merging together are not built"; return x; }
+        if (sd_hypertile_shape_ok(UB, rh, rw, C, ht_nh, ht_nw, C, "HyperTile")) { if (error.empty()) error = sd_last_error(); return x; }
+        pl.hypertile.push_back(Plan::HtBlock{rh, rw, ht_nh, ht_nw});
+        int xp;
+        { Op o; o.kind = OP_HT_GATHER; o.x1 = x; o.B = UB; o.Hin = rh; o.Win = rw; o.N = C; o.K = ht_nh; o.K1 = ht_nw;
+          o.out = xp = tensor((size_t)UB * rh * rw * C * 2); push(o); }
+        if (stats_of.count(x)) stats_of[xp] = stats_of[x];
+        const int yp = transformer_block(p, xp, C, rh, rw, ht_nh * ht_nw);
+        // (UB here: the block may have ended the CFG prefix and doubled it)
+        Op o; o.kind = OP_HT_SCATTER; o.x1 = yp; o.B = UB; o.Hin = rh; o.Win = rw; o.N = C; o.K = ht_nh; o.K1 = ht_nw;
+        o.out = tensor((size_t)UB * rh * rw * C * 2); push(o);
+        if (stats_of.count(yp)) stats_of[o.out] = stats_of[yp];
+        return o.out;
+    }
+    // nt: the tiles per sample (1 = not tiled): attn1 sees UB * nt samples of hw / nt tokens
+    int transformer_block(const std::string& p, int x, int C, int rh, int rw, int nt) {
         const int hw = rh * rw, L = u->cfg.context_len;
         const int NH = block_heads(u->cfg, p), NP = NH * 80;      // heads of the level the block sits on
         int M = UB * hw;
@@ -294,16 +334,18 @@ struct Builder {
         static const bool hm_off = (getenv("SD_ATTN_HEADMAJOR") && atoi(getenv("SD_ATTN_HEADMAJOR")) == 0) ||
                                    getenv("SD_ATTN_NO_PIPE") || getenv("SD_ATTN_NO_DMA") || getenv("SD_GEMM_BIG");
         // (a merging block: the same conditions on its Nm tokens per sample)
-        const bool hm = !hm_off && C / NH == 40 && C % 160 == 0 && Nm % 128 == 0 && Nm >= 256 &&
+        // (a HyperTile block: on the tokens of one tile -- tr == 0 there, so Nm = hw and Na = hw / nt)
+        const int Na = Nm / nt;
+        const bool hm = !hm_off && C / NH == 40 && C % 160 == 0 && Na % 128 == 0 && Na >= 256 &&
                         sd_gemm_tile_rows(Mm, 3 * C) == 128 && pl.ops.back().splitk == 1;
         int a1;
         if (hm) {
             pl.ops.back().hm = 1;
-            pl.ops.back().HW = Nm;
-            a1 = attn(qkv, 0, C, qkv, (long)Mm * C, 2l * Mm * C, C, Nm, Nm, C, NH);
+            pl.ops.back().HW = Na;
+            a1 = attn(qkv, 0, C, qkv, (long)Mm * C, 2l * Mm * C, C, Na, Na, C, NH, UB * nt);
             pl.ops.back().hm = 1;
         } else {
-            a1 = attn(qkv, 0, 3 * C, qkv, C, 2 * C, 3 * C, Nm, Nm, C, NH);
+            a1 = attn(qkv, 0, 3 * C, qkv, C, 2 * C, 3 * C, Na, Na, C, NH, UB * nt);
         }
         pl.ops.back().qps = 1;          // W_q of attn1 carries the scale (Packer::transformer)
         int h1 = gemm(a1, C, -1, 0, Mm, C, t + "attn1.to_out.0.weight", t + "attn1.to_out.0.bias", tr > 0 ? -1 : h0, 0);
@@ -410,7 +452,7 @@ struct Builder {
         } else {
             int q2 = np2 > 0 ? gemm_ln(h1, rs2, np2, M, C, C, t + "attn2.to_q.weight", 0)
                              : gemm(n2, C, -1, 0, M, C, t + "attn2.to_q.weight", "", -1, 0);
-            int a2 = attn(q2, 0, C, kv, 0, C, 2 * C, hw, L, C, NH);
+            int a2 = attn(q2, 0, C, kv, 0, C, 2 * C, hw, L, C, NH, UB);
             h2 = gemm(a2, C, -1, 0, M, C, t + "attn2.to_out.0.weight", t + "attn2.to_out.0.bias", tg_cap ? -1 : res, 0);
         }
         if (tg_cap) {
@@ -1105,7 +1147,8 @@ int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw
     const int tg_pair = tgate == TGATE_CAPTURE ? tgate_pair(u, UB) : 1;
     SD_REQUIRE(!tgate || (branch < 0 && !ip && !cn && !u->fp8), "unet: T-GATE with DeepCache, an IP-Adapter, ControlNet residuals or fp8 is not built");
     SD_REQUIRE(tg_pair == 1 || UB % 2 == 0, "unet: a T-GATE capture of a CFG pair needs an even batch (%d)", UB);
-    auto key = std::make_tuple(UB, branch, rep, lh, lw, ip, cn, tome_bits, tome_bits ? u->tome_max_downsample : 0, freeu, tgate, tg_pair);
+    auto key = std::make_tuple(UB, branch, rep, lh, lw, ip, cn, tome_bits, tome_bits ? u->tome_max_downsample : 0, freeu, tgate, tg_pair,
+                               u->kind == 0 ? u->ht_tokens : 0, u->kind == 0 && u->ht_tokens ? u->ht_max_depth : 0);
     auto it = u->plans.find(key);
     if (it == u->plans.end()) {
         if (lh != u->cfg.sample_size || lw != u->cfg.sample_size)

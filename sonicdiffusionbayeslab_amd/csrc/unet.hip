@@ -203,6 +203,10 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
         }
         case OP_REPLICATE:
             return sd_launch_replicate(T(o.x1), T(o.out), (long)o.M * 16, o.N, stream);
+        case OP_HT_GATHER:       // (K = nh, K1 = nw; the raster side is dense here: pitch = C)
+            return sd_launch_hypertile_gather((const bf16_t*)T(o.x1), o.N, (bf16_t*)T(o.out), o.B, o.Hin, o.Win, o.N, o.K, o.K1, stream);
+        case OP_HT_SCATTER:
+            return sd_launch_hypertile_scatter((const bf16_t*)T(o.x1), (bf16_t*)T(o.out), o.N, o.B, o.Hin, o.Win, o.N, o.K, o.K1, stream);
         case OP_TOME_MATCH:
             SD_REQUIRE(u->tome_choice && o.b2idx + (long)(o.Hin / 2) * (o.Win / 2) <= u->tome_choice_n, "forward: no Token Merging choice array");
             return sd_launch_tome_match((const bf16_t*)T(o.x1), u->tome_choice + o.b2idx, o.B, o.Hin, o.Win, o.N, (float*)T(o.out),
@@ -1264,6 +1268,46 @@ extern "C" int sd_unet_plan_count(const sd_unet* u) {
     return (int)u->plans.size();
 }
 
+// ---- HyperTile (hypertile.hip; the plan side is Builder::transformer) --------------------------------------------------------
+extern "C" int sd_unet_set_hypertile(sd_unet* u, int tile_tokens, int max_depth) {
+    SD_REQUIRE(u && u->kind == 0, "set_hypertile: not a UNet handle");
+    if (tile_tokens == 0) {         // off: the plans of a handle that never saw HyperTile
+        u->ht_tokens = 0; u->ht_max_depth = 0;
+        return 0;
+    }
+    SD_REQUIRE(tile_tokens >= 8 && tile_tokens <= 256, "set_hypertile: tile side of %d tokens (8 .. 256, or 0 = off)", tile_tokens);
+    SD_REQUIRE(max_depth >= 0 && max_depth <= 3, "set_hypertile: max_depth %d (0 .. 3)", max_depth);
+    SD_REQUIRE(!u->fp8, "set_hypertile: HyperTile is not built for fp8 handles");
+    SD_REQUIRE(!(u->tome_ratio > 0.0), "set_hypertile: Token Merging is on (HyperTile and Token Merging together are not built)");
+    u->ht_tokens = tile_tokens; u->ht_max_depth = max_depth;
+    return 0;
+}
+
+// the tiled blocks depend on the latent size and the setting alone: read them from the plain plan of batch 1
+static int hypertile_layout(sd_unet* u, const char* who, int latent_h, int latent_w, Plan** pl) {
+    SD_REQUIRE(u && u->kind == 0, "%s: not a UNet handle", who);
+    if (check_latent_size(u, latent_h, latent_w, who)) return -1;
+    return get_plan(u, 1, -1, pl, 1, latent_h, latent_w, 0, 0, TGATE_OFF);
+}
+
+extern "C" int sd_unet_hypertile_block_count_hw(sd_unet* u, int latent_h, int latent_w) {
+    Plan* pl;
+    if (hypertile_layout(u, "hypertile_block_count", latent_h, latent_w, &pl)) return -1;
+    return (int)pl->hypertile.size();
+}
+
+extern "C" int sd_unet_hypertile_block_info_hw(sd_unet* u, int block, int latent_h, int latent_w, int* rh, int* rw, int* nh, int* nw) {
+    Plan* pl;
+    if (hypertile_layout(u, "hypertile_block_info", latent_h, latent_w, &pl)) return -1;
+    SD_REQUIRE(block >= 0 && block < (int)pl->hypertile.size(), "hypertile_block_info: block %d of %zu", block, pl->hypertile.size());
+    const Plan::HtBlock& hb = pl->hypertile[block];
+    if (rh) *rh = hb.rh;
+    if (rw) *rw = hb.rw;
+    if (nh) *nh = hb.nh;
+    if (nw) *nw = hb.nw;
+    return 0;
+}
+
 // ---- Token Merging (tome.hip; the plan side is Builder::transformer) -----------------------------------------------------
 extern "C" int sd_unet_set_tome(sd_unet* u, double ratio, int max_downsample) {
     SD_REQUIRE(u && u->kind == 0, "set_tome: not a UNet handle");
@@ -1275,6 +1319,7 @@ extern "C" int sd_unet_set_tome(sd_unet* u, double ratio, int max_downsample) {
     SD_REQUIRE(ratio <= 0.75, "set_tome: ratio %g (0 .. 0.75: a 2x2 cell has three src tokens)", ratio);
     SD_REQUIRE(max_downsample == 1 || max_downsample == 2, "set_tome: max_downsample %d (1 or 2)", max_downsample);
     SD_REQUIRE(!u->fp8, "set_tome: Token Merging is not built for fp8 handles");
+    SD_REQUIRE(u->ht_tokens == 0, "set_tome: HyperTile is on (HyperTile and Token Merging together are not built)");
     u->tome_ratio = ratio; u->tome_max_downsample = max_downsample;
     return 0;
 }
@@ -1487,6 +1532,10 @@ static void op_work(const Op& o, double* flops, double* bytes) {
             *flops = 2.0 * 14.0 * o.B * (double)o.Hin * o.Win * o.C2;
             *bytes = 2.0 * o.B * (double)o.Hin * o.Win * (2.0 * o.C1 + 3.0 * o.C2);
             break;
+        case OP_HT_GATHER:
+        case OP_HT_SCATTER:     // every row in, every row out
+            *bytes = 2.0 * 2.0 * o.B * (double)o.Hin * o.Win * o.N;
+            break;
         case OP_RES_ADD:    // x and r in, x out
             *bytes = 3.0 * 2.0 * (double)o.M;      // (M: the elements of all segments)
             break;
@@ -1585,7 +1634,8 @@ extern "C" int sd_unet_forward_profiled(sd_unet* u, void* stream, const float* l
             halo4 = sd_conv_halo_subpix_applicable(a);
         }
         // (24 / 25 / 26: T-GATE's capture, apply and the capture plan's zero fill -- the op kinds of those numbers never run on a UNet)
-        const int kd = o.kind == OP_TGATE_CAPTURE ? 24 : o.kind == OP_TGATE_APPLY ? 25 : o.kind == OP_TGATE_ZERO ? 26 : o.kind == OP_XATTN ? 18 : o.kind == OP_REPLICATE ? 19 : o.kind == OP_IP_XATTN ? 22 : o.kind == OP_RES_ADD ? 23 : halo4 ? 21 :
+        // (9 / 10: HyperTile's gather and scatter, likewise)
+        const int kd = o.kind == OP_HT_GATHER ? 9 : o.kind == OP_HT_SCATTER ? 10 : o.kind == OP_TGATE_CAPTURE ? 24 : o.kind == OP_TGATE_APPLY ? 25 : o.kind == OP_TGATE_ZERO ? 26 : o.kind == OP_XATTN ? 18 : o.kind == OP_REPLICATE ? 19 : o.kind == OP_IP_XATTN ? 22 : o.kind == OP_RES_ADD ? 23 : halo4 ? 21 :
                        (o.kind == OP_CONV3 && !o.dt && (o.subpix || o.stride != 1)) ? 20 :
                        (o.dt ? (o.kind == OP_CONV3 ? 16 : 17) : o.kind);
         kind_ms[kd] += ms; kind_launches[kd] += 1; kind_flops[kd] += fl; kind_bytes[kd] += by;

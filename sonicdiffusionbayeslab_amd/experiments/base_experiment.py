@@ -87,6 +87,9 @@ class BaseMethod(ABC):
         freeu = self.parse_freeu(self.config.model, self.config.model.get("weight_dtype", None) or "bf16")     # key of this build: model.freeu
         if freeu is not None:
             self.model.enable_freeu(**freeu)
+        hypertile = self.parse_hypertile(self.config.model, self.config.model.get("weight_dtype", None) or "bf16")    # key of this build: model.hypertile
+        if hypertile is not None:
+            self.model.enable_hypertile(**hypertile)
         gate = self.parse_tgate(self.config.model)     # key of this build: model.tgate_step
         if gate is not None:
             self.model.enable_tgate(gate)
@@ -101,6 +104,24 @@ class BaseMethod(ABC):
             return None
         from ..models import StableDiffusionModel
         return StableDiffusionModel.check_tgate_step(g)
+
+    @staticmethod
+    def parse_hypertile(model_cfg, weight_dtype="bf16"):
+        """``model.hypertile: {tile_size, max_depth}`` -> the arguments of ``enable_hypertile`` (HyperTile for any method), or
+        None when the key is absent or null.  ``tile_size`` is required, ``max_depth`` defaults to 0; unknown keys, bad values
+        and fp8 UNets are refused by name."""
+        h = model_cfg.get("hypertile", None)
+        if h is None:
+            return None
+        if not hasattr(h, "keys"):
+            raise ValueError(f"model.hypertile must be a mapping {{tile_size, max_depth}}, got {h!r}")
+        keys = set(h.keys())
+        if "tile_size" not in keys or not keys <= {"tile_size", "max_depth"}:
+            raise ValueError(f"model.hypertile takes the keys tile_size and (optionally) max_depth (got {sorted(keys)})")
+        from ..models import StableDiffusionModel
+        tile_size, max_depth = h["tile_size"], h.get("max_depth", 0)
+        StableDiffusionModel.check_hypertile_args(tile_size, max_depth, 1, weight_dtype)
+        return dict(tile_size=tile_size, max_depth=max_depth)
 
     @staticmethod
     def parse_freeu(model_cfg, weight_dtype="bf16"):
@@ -291,7 +312,7 @@ class BaseMethod(ABC):
                                                            generator=self.generator, output_type=out_type, **call_kwargs)
                 local = result.images
             else:                       # more ranks than prompts in a ragged last batch
-                local, seconds = self._empty_result(out_type), 0.0
+                local, seconds = self._empty_result(out_type, call_kwargs.get("height"), call_kwargs.get("width")), 0.0
             if sharded:                 # the ONE data-path collective; the slowest rank's loop time rides along (and, when a
                                         # rank had no prompt and therefore drew nothing, rank 0's generator state)
                 local, seconds = sdist.gather_latents(local, self.world, len(prompts), seconds=seconds,
@@ -301,11 +322,16 @@ class BaseMethod(ABC):
             self.time_metric.update(seconds, batch_size)                 # configured size, as :161
         return images, x0_preds
 
-    def _empty_result(self, out_type: str) -> torch.Tensor:
+    def _empty_result(self, out_type: str, height=None, width=None) -> torch.Tensor:
+        """What a rank without a prompt hands to the all-gather: no rows, at the size of the call the other ranks ran
+        (``height`` / ``width`` in pixels as the call got them; None = the UNet's ``sample_size``) -- every rank must enter
+        the collective with the same row size."""
         ucfg = self.model.unet_config
+        h = ucfg.sample_size * 8 if height is None else int(height)
+        w = ucfg.sample_size * 8 if width is None else int(width)
         if out_type == "latent":
-            return torch.empty((0, ucfg.out_channels, ucfg.sample_size, ucfg.sample_size), device=self.device)
-        return torch.empty((0, 3, ucfg.sample_size * 8, ucfg.sample_size * 8), device=self.device)
+            return torch.empty((0, ucfg.out_channels, h // 8, w // 8), device=self.device)
+        return torch.empty((0, 3, h, w), device=self.device)
 
     def sweep(self, points, call_kwargs, label, extra=None, guidance_scale: float = 7.5):
         """The loop every method's ``run_experiment`` is: for each sweep point move the model to the device,

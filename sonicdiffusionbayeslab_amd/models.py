@@ -196,6 +196,7 @@ class StableDiffusionModel:
         self._tome_cells = 0
         self._tome_first = False        # the call's first forward uses the choice array _tome_begin uploaded
         self._freeu = None              # FreeU (enable_freeu): (s1, s2, b1, b2) or None = off
+        self._hypertile = None          # HyperTile (enable_hypertile): (tile_tokens, max_depth) or None = off
         self._tgate_step = None         # T-GATE (enable_tgate): the gate step, or None = off
         self._tgate_reserved = False    # the UNet's workspaces are sized for the capture plans as well
 
@@ -237,8 +238,11 @@ class StableDiffusionModel:
         ``max_downsample`` levels.  The dst token of each 2x2 cell is drawn on the host with ``torch.randint`` from a CPU
         generator seeded by ``seed`` at the start of a call -- before every UNet forward (``rand_every="step"``) or once per call
         (``"call"``); ``use_rand=False`` takes the top-left token of every cell.  ``ratio=0`` is ``remove_tome()``."""
-        self._tome = self.check_tome_args(ratio, max_downsample, sx, sy, use_rand, merge_attn, merge_crossattn, merge_mlp, seed,
-                                          rand_every, self.weight_dtype)
+        new = self.check_tome_args(ratio, max_downsample, sx, sy, use_rand, merge_attn, merge_crossattn, merge_mlp, seed,
+                                   rand_every, self.weight_dtype)
+        if new is not None and self._hypertile is not None:
+            raise NotImplementedError("Token Merging and HyperTile on together are not built: disable_hypertile() first")
+        self._tome = new
         return self
 
     def remove_tome(self):
@@ -282,6 +286,49 @@ class StableDiffusionModel:
             return
         if t["use_rand"] and t["rand_every"] == "step":
             self._tome_upload()
+
+    # -- HyperTile (tfernd/HyperTile) ------------------------------------------------------
+    @staticmethod
+    def check_hypertile_args(tile_size=256, max_depth=0, swap_size=1, weight_dtype="bf16"):
+        """The arguments of ``enable_hypertile`` checked, by name, without touching the GPU.  Returns ``(tile_tokens,
+        max_depth)``: the tile side in tokens is ``tile_size // 8``."""
+        if isinstance(tile_size, bool) or not isinstance(tile_size, int) or tile_size % 8 != 0 or not 64 <= tile_size <= 2048:
+            raise ValueError(f"tile_size={tile_size!r}: HyperTile takes a tile size in pixels that is a multiple of 8, "
+                             "at least 64 and at most 2048")
+        if isinstance(max_depth, bool) or not isinstance(max_depth, int) or not 0 <= max_depth <= 3:
+            raise ValueError(f"max_depth={max_depth!r}: HyperTile takes an integer max_depth of 0 .. 3")
+        if isinstance(swap_size, bool) or swap_size != 1:
+            raise NotImplementedError(f"swap_size={swap_size!r}: only swap_size=1 is built (upstream's per-step random choice "
+                                      "among several tile sizes is not)")
+        return HipUNet2DConditionModel.check_hypertile_args(tile_size // 8, max_depth, weight_dtype)
+
+    def enable_hypertile(self, tile_size: int = 256, max_depth: int = 0, swap_size: int = 1):
+        """HyperTile: in every later call the transformer blocks at depth ``<= max_depth`` (0 = the latent's own level) run
+        their self-attention inside tiles of about ``tile_size`` pixels: the tile side in tokens is the smallest divisor of
+        the level's side that is ``>= tile_size // 8``; a level that the rule leaves in one tile is not tiled.  Valid with
+        every pipeline and scheduler, DeepCache, T-GATE, FreeU, LCM-distilled UNets, SD 2.x, IP-Adapter, ControlNet, TAESD,
+        every image size and batch sharding; refused by name with Token Merging and on fp8 UNets."""
+        new = self.check_hypertile_args(tile_size, max_depth, swap_size, self.weight_dtype)
+        if self._tome is not None:
+            raise NotImplementedError("HyperTile and Token Merging on together are not built: remove_tome() first")
+        self._hypertile = new
+        return self
+
+    def disable_hypertile(self):
+        """Later calls are those of a model that never saw HyperTile, bit for bit."""
+        self._hypertile = None
+        return self
+
+    def _hypertile_begin(self, after_tome: bool):
+        """Start of a sampling loop: the setting onto the UNet handle -- off before Token Merging's setting goes on, on after it
+        went off (the handle refuses the two together).  A handle that never had the setting on is not touched while it is off."""
+        on = self._hypertile is not None
+        if on != after_tome:
+            return
+        if on:
+            self.unet.set_hypertile(*self._hypertile)
+        elif getattr(self.unet, "_hypertile", None) is not None:
+            self.unet.set_hypertile(0)
 
     # -- FreeU (diffusers enable_freeu) -----------------------------------------------------------------
     @staticmethod
@@ -1061,7 +1108,9 @@ class StableDiffusionModel:
     def _start_loop(self, batch_size, device, generator, latents, ctx, cache_branch_id, control=None):
         """Initial latents at the call's size, DeepCache branch and prompt context of the UNet."""
         latents = self.prepare_latents(batch_size, LATENT_CHANNELS, self._size[0], self._size[1], device, generator, latents)
+        self._hypertile_begin(False)
         self._tome_begin()              # (before the context: the setting is part of the UNet's plans)
+        self._hypertile_begin(True)     # (likewise)
         self._freeu_begin()             # (likewise)
         self._tgate_begin(batch_size)   # (before the context: the workspace that holds it)
         self.unet.set_deepcache(cache_branch_id)

@@ -85,6 +85,7 @@ class HipUNet2DConditionModel(HipHandle):
         self._tome = None                   # (ratio, max_downsample) of the Token Merging setting on the handle, None = off
         self._tome_choice_keepalive = None
         self._freeu = None                  # (s1, s2, b1, b2) on the handle, None = off
+        self._hypertile = None              # (tile_tokens, max_depth) of the HyperTile setting on the handle, None = off
         # T-GATE: _tgate = (mode, latent batch, h, w) on the handle or None = off; _tgate_cache = the buffer the handle borrows;
         # _tgate_ws = workspace of the gated (reuse) plans, keyed (batch, h, w): the main workspace keeps the prompt context
         self._tgate = None
@@ -281,6 +282,8 @@ class HipUNet2DConditionModel(HipHandle):
         ratio = float(ratio)
         if ratio > 0.0 and self.weight_dtype != "bf16":
             raise NotImplementedError("Token Merging on an fp8 UNet handle is not built")
+        if ratio > 0.0 and self._hypertile is not None:
+            raise NotImplementedError("Token Merging and HyperTile on together are not built: set_hypertile(0) first")
         _lib.check(self._lib.sd_unet_set_tome(self._handle, ratio, int(max_downsample) if ratio > 0.0 else 0), "sd_unet_set_tome")
         new = (ratio, int(max_downsample)) if ratio > 0.0 else None
         if new != self._tome:
@@ -335,6 +338,53 @@ class HipUNet2DConditionModel(HipHandle):
         # (the library wrote B rows contiguously at the row lengths above)
         return dict(kept=kept.reshape(-1)[:b * (num_src - r)].reshape(b, num_src - r), merged=merged.reshape(-1)[:b * r].reshape(b, r),
                     dst_idx=dst_idx.reshape(-1)[:b * r].reshape(b, r), tok=tok, r=rr.value)
+
+    # -- HyperTile (include/sd_hip.h::sd_unet_set_hypertile) -----------------------------------------
+    HYPERTILE_MIN_TOKENS = 8
+
+    @staticmethod
+    def check_hypertile_args(tile_tokens, max_depth, weight_dtype="bf16"):
+        """The arguments of ``set_hypertile`` checked, by name, without touching the GPU; returns ``(tile_tokens, max_depth)``
+        as ints, or None for ``tile_tokens == 0`` (off)."""
+        if isinstance(tile_tokens, bool) or not isinstance(tile_tokens, int) or \
+                (tile_tokens != 0 and not HipUNet2DConditionModel.HYPERTILE_MIN_TOKENS <= tile_tokens <= 256):
+            raise ValueError(f"tile_tokens={tile_tokens!r}: the HyperTile tile side is an integer of 8 .. 256 tokens (0 = off)")
+        if tile_tokens == 0:
+            return None
+        if isinstance(max_depth, bool) or not isinstance(max_depth, int) or not 0 <= max_depth <= 3:
+            raise ValueError(f"max_depth={max_depth!r}: HyperTile takes an integer max_depth of 0 .. 3")
+        if _lib.DTYPES.get(weight_dtype) == _lib.DTYPE_FP8_E4M3:
+            raise NotImplementedError("HyperTile on an fp8 UNet handle is not built (weight_dtype='fp8')")
+        return tile_tokens, max_depth
+
+    def set_hypertile(self, tile_tokens: int, max_depth: int = 0) -> None:
+        """Tiled self-attention (HyperTile): every transformer block at depth ``<= max_depth`` whose token grid is cut into
+        more than one tile -- the tile side is the smallest divisor of the grid's side that is ``>= min(tile_tokens, side)`` --
+        runs in tile order, its self-attention inside each tile (``tile_tokens`` 0: off, the handle of before).  A change needs a new workspace and a new ``set_context``; both follow
+        from dropping the workspace key here.  Refused together with Token Merging."""
+        new = self.check_hypertile_args(tile_tokens, max_depth, self.weight_dtype)
+        if new is not None and self._tome is not None:
+            raise NotImplementedError("HyperTile and Token Merging on together are not built: set_tome(0.0) first")
+        _lib.check(self._lib.sd_unet_set_hypertile(self._handle, *(new or (0, 0))), "sd_unet_set_hypertile")
+        if new != self._hypertile:
+            self._hypertile = new
+            self._ws_key = None
+            self._tgate_ws.clear()          # (the gated plans of the other setting sized it)
+
+    def hypertile_blocks(self, height: Optional[int] = None, width: Optional[int] = None):
+        """The tiled blocks at a latent size, in plan order (down, mid, up): dicts of ``rh``, ``rw`` (token grid) and ``nh``,
+        ``nw`` (tile counts).  Empty while off."""
+        lh, lw = self.latent_size(height, width)
+        n = self._lib.sd_unet_hypertile_block_count_hw(self._handle, lh, lw)
+        if n < 0:
+            _lib.check(-1, "sd_unet_hypertile_block_count_hw")
+        out = []
+        for i in range(n):
+            v = [C.c_int() for _ in range(4)]
+            _lib.check(self._lib.sd_unet_hypertile_block_info_hw(self._handle, i, lh, lw, *[C.byref(x) for x in v]),
+                       "sd_unet_hypertile_block_info_hw")
+            out.append(dict(rh=v[0].value, rw=v[1].value, nh=v[2].value, nw=v[3].value))
+        return out
 
     # -- FreeU (include/sd_hip.h::sd_unet_set_freeu) -------------------------------------------------
     @staticmethod
@@ -545,7 +595,7 @@ class HipUNet2DConditionModel(HipHandle):
             _lib.check(self._lib.sd_unet_set_fp8_scale(self._handle, k.encode(), float(v)), f"sd_unet_set_fp8_scale({k})")
 
     KIND_NAMES = {0: "sinusoid", 1: "gemv", 2: "conv_in", 3: "groupnorm", 4: "conv3x3", 5: "gemm", 6: "layernorm",
-                  7: "attention", 8: "conv_out", 16: "conv3x3_fp8", 17: "gemm_fp8", 18: "xattn_fused",
+                  7: "attention", 8: "conv_out", 9: "hypertile_gather", 10: "hypertile_scatter", 16: "conv3x3_fp8", 17: "gemm_fp8", 18: "xattn_fused",
                   19: "replicate", 20: "conv3x3_gemm", 21: "conv3x3_halo_subpix", 22: "ip_xattn", 23: "residual_add",
                   24: "tgate_capture", 25: "tgate_apply", 26: "tgate_zero",
                   27: "tome_match", 28: "tome_select", 29: "tome_merge", 30: "tome_unmerge", 31: "freeu"}
