@@ -284,6 +284,18 @@ int sd_unet_set_hypertile(sd_unet* u, int tile_tokens, int max_depth);
 int sd_unet_hypertile_block_count_hw(sd_unet* u, int latent_h, int latent_w);
 int sd_unet_hypertile_block_info_hw(sd_unet* u, int block, int latent_h, int latent_w, int* rh, int* rw, int* nh, int* nw);
 
+/* Perturbed-attention guidance (Ahn et al. 2024; diffusers' PAGMixin).  layer_mask: bit i = transformer block i in
+ * plan order (down, mid, up -- the order of the T-GATE cache slices; sd_unet_pag_block_count of them) is perturbed; 0 = off = the
+ * plans, workspace sizes and results of a handle that never saw it.  With a mask set, a forward runs a UNet batch of 3 or 2 times
+ * the latent batch -- [uncond | cond | perturbed] or [cond | perturbed] over the SAME latents -- and in a perturbed block attn1 of
+ * the LAST latent_batch samples is to_out(to_v(norm1(h))): the attention kernel runs on the other samples and one identity launch
+ * (profile kind 11) fills the perturbed rows of its output, so to_out stays one GEMM.  The prompt-independent prefix ends at the
+ * entry of the first transformer block when that block is perturbed, else where the plain plan ends it.  The mask is part of the
+ * plan key; after a change call sd_unet_workspace_bytes_hw and sd_unet_set_context_hw again.  bf16 4-channel UNet handles without
+ * an IP-Adapter only; a forward with Token Merging, T-GATE, DeepCache or ControlNet residuals is refused by name. */
+int sd_unet_set_pag(sd_unet* u, long long layer_mask);
+int sd_unet_pag_block_count(const sd_unet* u);
+
 enum { SD_CACHE_OFF = 0, SD_CACHE_FULL_AND_STORE = 1, SD_CACHE_SKIP = 2 };
 
 /* eps = UNet(latent_model_input, t, encoder_hidden_states)  (src/models.py:217-235).
@@ -606,6 +618,29 @@ int sd_sched_step_pc(void* stream, const float* eps, int cfg, float guidance, co
                      const float coef[13], long long n, const float* k, long long n_per_sample, const float* init,
                      const float* blend_noise, const float* mask, float a, float s, long long hw);
 
+/* ---- perturbed-attention guidance (PAG; Ahn et al. 2024, diffusers' PAGMixin) ----
+ * The guidance modes of the PAG steps.  SD_GUIDE_CFG_PAG: eps = [u | c | p] (3 n elements), e = (u + guidance*(c - u)) +
+ * pag_scale*(c - p); SD_GUIDE_PAG: eps = [c | p] (2 n elements), e = c + pag_scale*(c - p).  Per element in fp32, the CFG
+ * part formed exactly as sd_sched_step forms it, the PAG term added to it.  p is the UNet output of the perturbed samples
+ * (sd_unet_set_pag).
+ * sd_sched_step_pag: sd_sched_step_inpaint with that e -- k and init may each be NULL (no rescale / no blend; with neither,
+ * n_per_sample is not read).  sd_sched_step_pc_pag: sd_sched_step_pc with that e.  Same operands, coefficients and argument
+ * checks as those two; besides, mode must be one of the two, and guidance and pag_scale finite.  pag_scale = 0 in
+ * SD_GUIDE_CFG_PAG gives the bits of the plain CFG step for finite eps.
+ * sd_cfg_rescale_factors_pag: sd_cfg_rescale_factors over eps = [u | c | p] with g = (u + guidance*(c - u)) +
+ * pag_scale*(c - p), the value the SD_GUIDE_CFG_PAG step scales (CFG mode only: guidance_rescale needs CFG). */
+enum { SD_GUIDE_CFG_PAG = 2, SD_GUIDE_PAG = 3 };
+int sd_sched_step_pag(void* stream, const float* eps, int mode, float guidance, float pag_scale, const float* x, const float* m1,
+                      const float* m2, const float* m3, const float* noise, float* prev, float* y2, float* m_out,
+                      const float coef[10], long long n, const float* k, long long n_per_sample, const float* init,
+                      const float* blend_noise, const float* mask, float a, float s, long long hw);
+int sd_sched_step_pc_pag(void* stream, const float* eps, int mode, float guidance, float pag_scale, const float* x,
+                         const float* x_last, const float* h1, const float* h2, const float* h3, float* prev, float* x_corr,
+                         float* y2, float* m_out, const float coef[13], long long n, const float* k, long long n_per_sample,
+                         const float* init, const float* blend_noise, const float* mask, float a, float s, long long hw);
+int sd_cfg_rescale_factors_pag(void* stream, const float* eps, int batch, long long n_per_sample, float guidance,
+                               float pag_scale, float rescale, float* k_out);
+
 /* One launch: image [batch,3,height,width] fp32 in [0,1] and mask [batch,1,height,width] fp32 ->
  *   masked_image [batch,3,height,width] = mask >= 0.5 ? 0.5 : image   (the encoder's input domain: 2 * 0.5 - 1 is exactly 0,
  *                                                                      upstream's (2 image - 1) * (mask < 0.5))
@@ -744,6 +779,16 @@ int sd_op_freeu(void* stream, const void* hidden, const void* skip, void* hidden
 int sd_hypertile_check(int B, int rh, int rw, int C, int nh, int nw, long long pitch);
 int sd_op_hypertile_gather(void* stream, const void* x, long long pitch, void* out, int B, int rh, int rw, int C, int nh, int nw);
 int sd_op_hypertile_scatter(void* stream, const void* y, void* out, long long pitch, int B, int rh, int rw, int C, int nh, int nw);
+/* PAG's identity self-attention on its own (csrc/pag.hip): the attention output of a perturbed sample is V.  Writes
+ * out[r][h * D + d] = V(r, h, d), D = C / heads, for the rows [row0, row0 + rows) of a token-major [rows_total][C] bf16 output and
+ * nothing else.  tok == 0: V token-major, row r at V + r * ldv (the q | k | v projection: V = qkv + 2 C, ldv = 3 C); tok > 0: V
+ * head-major [rows_total / tok][heads][tok][D] dense (ldv not read), sample = r / tok.  A bit-exact copy, 16-byte accesses, 64-bit
+ * offsets.  sd_pag_identity_check: the shape rule (and the plan builder's), no GPU work: rows_total in 1 .. 2^31, the row range
+ * inside it, D a multiple of 8, C <= 16384, token-major: ldv a multiple of 8 in C .. 2^30; head-major: tok divides rows_total,
+ * row0 and rows.  What it refuses the op refuses by name, writing nothing; the op also wants 16-byte-aligned pointers. */
+int sd_pag_identity_check(long long rows_total, long long row0, long long rows, int C, int heads, long long ldv, int tok);
+int sd_op_pag_identity(void* stream, const void* V, long long ldv, int tok, void* out, long long rows_total, long long row0,
+                       long long rows, int C, int heads);
 /* flash-style attention on token-major [B, N, heads * D] views; D = 40, 64, 80 or 160 (64: Stable Diffusion 2.x), any Nq / Nk */
 int sd_op_attention(void* stream, const void* Q, long long ldq, const void* K, long long ldk, const void* V,
                     long long ldv, void* O, long long ldo, int B, int heads, int Nq, int Nk, int D, float scale);

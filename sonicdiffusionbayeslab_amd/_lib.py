@@ -252,6 +252,13 @@ _SIGS = {
     "sd_hypertile_check": (_i, [_i, _i, _i, _i, _i, _i, _ll]),
     "sd_op_hypertile_gather": (_i, [_vp, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i]),
     "sd_op_hypertile_scatter": (_i, [_vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i]),
+    "sd_unet_set_pag": (_i, [_vp, _ll]),
+    "sd_unet_pag_block_count": (_i, [_vp]),
+    "sd_pag_identity_check": (_i, [_ll, _ll, _ll, _i, _i, _ll, _i]),
+    "sd_op_pag_identity": (_i, [_vp, _vp, _ll, _i, _vp, _ll, _ll, _ll, _i, _i]),
+    "sd_sched_step_pag": (_i, [_vp, _vp, _i, _f, _f] + [_vp] * 8 + [C.POINTER(_f), _ll, _vp, _ll, _vp, _vp, _vp, _f, _f, _ll]),
+    "sd_sched_step_pc_pag": (_i, [_vp, _vp, _i, _f, _f] + [_vp] * 9 + [C.POINTER(_f), _ll, _vp, _ll, _vp, _vp, _vp, _f, _f, _ll]),
+    "sd_cfg_rescale_factors_pag": (_i, [_vp, _vp, _i, _ll, _f, _f, _f, _vp]),
 }
 
 

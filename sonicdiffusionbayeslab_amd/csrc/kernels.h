@@ -253,6 +253,14 @@ int sd_hypertile_shape_ok(int B, int rh, int rw, int C, int nh, int nw, long pit
 int sd_launch_hypertile_gather(const bf16_t* x, long pitch, bf16_t* out, int B, int rh, int rw, int C, int nh, int nw, hipStream_t stream);
 int sd_launch_hypertile_scatter(const bf16_t* y, bf16_t* out, long pitch, int B, int rh, int rw, int C, int nh, int nw, hipStream_t stream);
 
+// pag.hip: the identity self-attention of PAG's perturbed samples: out[r][h * D + d] = V(r, h, d) for the rows [row0, row0 + rows)
+// of a token-major [rows_total][C] output, nothing else written.  tok == 0: token-major V with row pitch ldv; tok > 0: head-major
+// V [rows_total / tok][heads][tok][D] (ldv not read).  D = C / heads a multiple of 8 (16-byte accesses), 64-bit offsets.
+// shape_ok: the shape rule of the launcher and of the plan builder (no GPU work).
+int sd_pag_identity_shape_ok(long rows_total, long row0, long rows, int C, int heads, long ldv, int tok, const char* who);
+int sd_launch_pag_identity(const bf16_t* V, long ldv, int tok, bf16_t* out, long rows_total, long row0, long rows, int C, int heads,
+                           hipStream_t stream);
+
 // xattn.hip: fused prompt cross-attention  Y = R + sum_h softmax_L(X A_h) B_h + b_o  (one launch per block)
 struct XattnArgs {
     const bf16_t* X = nullptr;    // [M, C] LayerNorm output
@@ -385,14 +393,16 @@ struct StepCoef {
 };
 // k given: e := k[i / n_per_sample] * e (after the CFG combine, before every use).  init given: prev := mask ? prev :
 // a * init + s * blend_noise; mask [n / n_per_sample][hw] fp32 0 / 1, broadcast over the n_per_sample / hw channels of its
-// sample.  Neither: n_per_sample is not read.  `who`: the entry's name, the prefix of every refusal.
-int sd_launch_sched_step(const char* who, const float* eps, int cfg, float guidance, const float* x, const float* m1,
+// sample.  Neither: n_per_sample is not read.  `who`: the entry's name, the prefix of every refusal.  cfg: 0, 1 (CFG) or a PAG
+// mode (sd_hip.h::SD_GUIDE_CFG_PAG / SD_GUIDE_PAG: eps holds three / two thirds and `pag` is the PAG scale; else pag is not read).
+int sd_launch_sched_step(const char* who, const float* eps, int cfg, float guidance, float pag, const float* x, const float* m1,
                          const float* m2, const float* m3, const float* noise, float* prev, float* y2, float* m_out,
                          StepCoef c, const float* k, long n_per_sample, long n, const float* init, const float* blend_noise,
                          const float* mask, float a, float s, long hw, hipStream_t stream);
 // guidance_rescale: k_out[b] = r * std(c_b) / std(g_b) + (1 - r), g = u + s (c - u); eps = [u: batch | c: batch] samples
+// (with_pag: [u | c | p] and g += pag (c - p))
 int sd_launch_cfg_rescale_factors(const float* eps, int batch, long n_per_sample, float guidance, float rescale, float* k_out,
-                                  hipStream_t stream);
+                                  hipStream_t stream, int with_pag = 0, float pag = 0.f);
 // UniPC's predictor-corrector step (include/sd_hip.h::sd_sched_step_pc): corrector, predictor, history entry, x0 and the
 // optional rescale / latent blend in one launch
 struct PcCoef {
@@ -401,7 +411,7 @@ struct PcCoef {
     float cc[5];  // xc   = cc0*x_last + cc1*h1 + cc2*h2 + cc3*h3 + cc4*m_t
     float cp[4];  // prev = cp0*xc + cp1*m_t + cp2*h1 + cp3*h2
 };
-int sd_launch_sched_step_pc(const float* eps, int cfg, float guidance, const float* x, const float* x_last, const float* h1,
+int sd_launch_sched_step_pc(const char* who, const float* eps, int cfg, float guidance, float pag, const float* x, const float* x_last, const float* h1,
                             const float* h2, const float* h3, float* prev, float* x_corr, float* y2, float* m_out, PcCoef c,
                             const float* k, long n_per_sample, long n, const float* init, const float* blend_noise,
                             const float* mask, float a, float s, long hw, hipStream_t stream);

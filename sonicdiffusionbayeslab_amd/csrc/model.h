@@ -49,7 +49,8 @@ enum OpKind { OP_SINUSOID, OP_GEMV, OP_CONV_IN, OP_GN, OP_CONV3, OP_GEMM, OP_LN,
               OP_TOME_MATCH, OP_TOME_SELECT, OP_TOME_MERGE, OP_TOME_UNMERGE,
               OP_FREEU,
               OP_TGATE_CAPTURE, OP_TGATE_APPLY, OP_TGATE_ZERO,
-              OP_HT_GATHER, OP_HT_SCATTER };
+              OP_HT_GATHER, OP_HT_SCATTER,
+              OP_PAG_IDENTITY };
 
 constexpr int TGATE_OFF = 0, TGATE_CAPTURE = 1, TGATE_REUSE = 2;      // sd_unet_set_tgate_hw modes
 
@@ -182,6 +183,10 @@ struct Plan {
     // token grid and tile counts (sd_unet_hypertile_block_info_hw)
     struct HtBlock { int rh, rw, nh, nw; };
     std::vector<HtBlock> hypertile;
+    // PAG variant (the handle's layer mask is part of the plan key, pag.hip): pag_lb > 0 = the LAST pag_lb samples of the batch are
+    // the perturbed ones (rep = UB / pag_lb is 3 or 2); in the blocks the mask names attn1 runs on the other samples and one
+    // OP_PAG_IDENTITY fills the perturbed rows of its output.  pag_blocks: the transformer blocks the builder has seen so far.
+    int pag_lb = 0, pag_blocks = 0;
     // FreeU variant (part of the plan key): one OP_FREEU in front of every resnet of up blocks 0 and 1 (x1 = hidden, x2 = skip ->
     // out = the scaled hidden, aux = the filtered skip, epi = the up block: which pair of the handle's factors the launch reads)
     int freeu = 0;
@@ -259,8 +264,9 @@ struct sd_unet {
     }
     // (UNet batch, DeepCache branch, prefix replication, latent H, W, IP-Adapter variant, control variant, Token Merging: the
     // bits of the ratio and max_downsample, both 0 = off; FreeU on / off; T-GATE mode: TGATE_OFF / CAPTURE / REUSE; T-GATE pair: y rows per
-    // cache row of a capture, 2 for a CFG pair, else 1; HyperTile: tile side in tokens and max_depth, both 0 = off)
-    std::map<std::tuple<int, int, int, int, int, int, int, long long, int, int, int, int, int, int>, sdhip::Plan> plans;
+    // cache row of a capture, 2 for a CFG pair, else 1; HyperTile: tile side in tokens and max_depth, both 0 = off; PAG: the layer
+    // mask, 0 = off)
+    std::map<std::tuple<int, int, int, int, int, int, int, long long, int, int, int, int, int, int, long long>, sdhip::Plan> plans;
     int last_rep = 1, last_ip = 0, last_cn = 0;                       // variant of the last forward (sd_unet_debug_tensor)
     int last_h = 0, last_w = 0;                          // latent size of the last forward (sd_unet_debug_tensor)
     std::unordered_map<std::string, long> tproj_off;  // resnet prefix -> float index into tproj vector
@@ -305,6 +311,9 @@ struct sd_unet {
     long tome_choice_n = 0;
     // HyperTile (sd_unet_set_hypertile; kind 0, bf16): the tile side in tokens, 0 = off = the plans of a handle that never saw it
     int ht_tokens = 0, ht_max_depth = 0;
+    // PAG (sd_unet_set_pag; kind 0, bf16): bit i = transformer block i in plan order (down, mid, up) has identity attn1 for the
+    // perturbed samples; 0 = off = the plans of a handle that never saw it
+    long long pag_mask = 0;
     // FreeU (sd_unet_set_freeu; kind 0, bf16): on = the "freeu" plan variants; the factors are read when OP_FREEU is launched
     bool freeu_on = false;
     float freeu_s[2] = {1.f, 1.f}, freeu_b[2] = {1.f, 1.f};       // (s1, s2), (b1, b2): up block 0, up block 1
@@ -365,6 +374,7 @@ int plan_rep(const sd_unet* u, int latent_batch, int unet_batch);
 int check_latent_size(const sd_unet* u, int lh, int lw, const char* who);
 // lh / lw < 0: the handle's sample_size (square); tgate < 0: the handle's T-GATE mode (tgate_variant), 0 = the plain plan
 int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep = 1, int lh = -1, int lw = -1, int ip = 0, int cn = 0, int tgate = -1);
+int transformer_block_count(const sd_unet_config& c);      // transformer blocks of a UNet in plan order (down, mid, up)
 int tgate_variant(const sd_unet* u);              // the T-GATE mode of the handle's plans (TGATE_OFF unless a UNet handle has one set)
 int tgate_pair(const sd_unet* u, int UB);         // y rows per cache row of a capture forward at batch UB (2 = a CFG pair)
 bool ip_active(const sd_unet* u, int UB, int branch, int lh, int lw);     // is this forward's IP-Adapter key set?

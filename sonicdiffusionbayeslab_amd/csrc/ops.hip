@@ -513,6 +513,16 @@ extern "C" int sd_op_hypertile_scatter(void* stream, const void* y, void* out, l
     return sd_launch_hypertile_scatter((const bf16_t*)y, (bf16_t*)out, (long)pitch, B, rh, rw, C, nh, nw, (hipStream_t)stream);
 }
 
+// PAG's identity self-attention (pag.hip) and its shape rule
+extern "C" int sd_pag_identity_check(long long rows_total, long long row0, long long rows, int C, int heads, long long ldv, int tok) {
+    return sd_pag_identity_shape_ok((long)rows_total, (long)row0, (long)rows, C, heads, (long)ldv, tok, "sd_pag_identity_check");
+}
+extern "C" int sd_op_pag_identity(void* stream, const void* V, long long ldv, int tok, void* out, long long rows_total, long long row0,
+                                  long long rows, int C, int heads) {
+    return sd_launch_pag_identity((const bf16_t*)V, (long)ldv, tok, (bf16_t*)out, (long)rows_total, (long)row0, (long)rows, C, heads,
+                                  (hipStream_t)stream);
+}
+
 // Token Merging, kernel by kernel (tome.hip); index lists in src / dst slot numbers, tok [h * w] from sd_op_tome_match
 extern "C" int sd_op_tome_match(void* stream, const void* x, const unsigned char* choice, int B, int h, int w, int C,
                                 float* node_max, int* node_idx, int* tok) {

@@ -267,11 +267,22 @@ struct Builder {
     // gathered residual).  The producers' GroupNorm statistics are per 64-row block, summed per sample: they describe a
     // permuted tensor as well as the original, so the entry GroupNorm keeps x's statistics and the next resnet's GroupNorm
     // gets the exit GEMM's.
+    // A PAG block (pag.hip; Plan::pag_lb > 0 and the handle's mask names the block): attn1 of the last pag_lb samples is the
+    // identity, see transformer_block.  The prompt-independent prefix must end before the first perturbed attn1: when the first
+    // transformer block is perturbed the prefix ends at the block's ENTRY -- its input is replicated and the whole block runs at
+    // the full batch -- instead of behind attn1.to_out (the rows of attn1 then differ between the samples of one latent).
     int n_transformers = 0;
     int transformer(const std::string& p, int x, int C, int rh, int rw) {
+        const int blk = pl.pag_blocks++;
+        const bool pert = pl.pag_lb > 0 && ((u->pag_mask >> blk) & 1);
+        if (pert && prefix_rep > 1) {
+            x = replicate(x, (size_t)UB * rh * rw * C * 2, prefix_rep);
+            UB *= prefix_rep;
+            prefix_rep = 1;
+        }
         int ht_nh, ht_nw;
         hypertile_tiles(rh, rw, &ht_nh, &ht_nw);
-        if (ht_nh * ht_nw == 1) return transformer_block(p, x, C, rh, rw, 1);
+        if (ht_nh * ht_nw == 1) return transformer_block(p, x, C, rh, rw, 1, pert);
         if (u->tome_ratio > 0.0) { if (error.empty()) error = "HyperTile and Token Merging together are not built"; return x; }
         if (sd_hypertile_shape_ok(UB, rh, rw, C, ht_nh, ht_nw, C, "HyperTile")) { if (error.empty()) error = sd_last_error(); return x; }
         pl.hypertile.push_back(Plan::HtBlock{rh, rw, ht_nh, ht_nw});
@@ -279,15 +290,17 @@ struct Builder {
         { Op o; o.kind = OP_HT_GATHER; o.x1 = x; o.B = UB; o.Hin = rh; o.Win = rw; o.N = C; o.K = ht_nh; o.K1 = ht_nw;
           o.out = xp = tensor((size_t)UB * rh * rw * C * 2); push(o); }
         if (stats_of.count(x)) stats_of[xp] = stats_of[x];
-        const int yp = transformer_block(p, xp, C, rh, rw, ht_nh * ht_nw);
+        const int yp = transformer_block(p, xp, C, rh, rw, ht_nh * ht_nw, pert);
         // (UB here: the block may have ended the CFG prefix and doubled it)
         Op o; o.kind = OP_HT_SCATTER; o.x1 = yp; o.B = UB; o.Hin = rh; o.Win = rw; o.N = C; o.K = ht_nh; o.K1 = ht_nw;
         o.out = tensor((size_t)UB * rh * rw * C * 2); push(o);
         if (stats_of.count(yp)) stats_of[o.out] = stats_of[yp];
         return o.out;
     }
-    // nt: the tiles per sample (1 = not tiled): attn1 sees UB * nt samples of hw / nt tokens
-    int transformer_block(const std::string& p, int x, int C, int rh, int rw, int nt) {
+    // nt: the tiles per sample (1 = not tiled): attn1 sees UB * nt samples of hw / nt tokens.  pert: a PAG block -- the attention
+    // kernel sees the (UB - pag_lb) * nt samples in front, OP_PAG_IDENTITY copies V into the rows of the pag_lb samples behind them
+    // (tile order permutes rows inside a sample, so they stay the last pag_lb * hw rows), and to_out runs over all rows as ever
+    int transformer_block(const std::string& p, int x, int C, int rh, int rw, int nt, bool pert) {
         const int hw = rh * rw, L = u->cfg.context_len;
         const int NH = block_heads(u->cfg, p), NP = NH * 80;      // heads of the level the block sits on
         int M = UB * hw;
@@ -338,16 +351,29 @@ struct Builder {
         const int Na = Nm / nt;
         const bool hm = !hm_off && C / NH == 40 && C % 160 == 0 && Na % 128 == 0 && Na >= 256 &&
                         sd_gemm_tile_rows(Mm, 3 * C) == 128 && pl.ops.back().splitk == 1;
+        if (pert && (tr > 0 || fq || pl.pag_lb >= UB)) {
+            if (error.empty()) error = "PAG with Token Merging or fp8, or a batch without unperturbed samples, is not built";
+            return x;
+        }
+        const int Ba = (pert ? UB - pl.pag_lb : UB) * nt;      // the samples the attention kernel sees
         int a1;
         if (hm) {
             pl.ops.back().hm = 1;
             pl.ops.back().HW = Na;
-            a1 = attn(qkv, 0, C, qkv, (long)Mm * C, 2l * Mm * C, C, Na, Na, C, NH, UB * nt);
+            a1 = attn(qkv, 0, C, qkv, (long)Mm * C, 2l * Mm * C, C, Na, Na, C, NH, Ba);
             pl.ops.back().hm = 1;
         } else {
-            a1 = attn(qkv, 0, 3 * C, qkv, C, 2 * C, 3 * C, Na, Na, C, NH, UB * nt);
+            a1 = attn(qkv, 0, 3 * C, qkv, C, 2 * C, 3 * C, Na, Na, C, NH, Ba);
         }
         pl.ops.back().qps = 1;          // W_q of attn1 carries the scale (Packer::transformer)
+        if (pert) {
+            const long row0 = (long)(UB - pl.pag_lb) * hw, rows = (long)pl.pag_lb * hw;
+            if (sd_pag_identity_shape_ok(Mm, row0, rows, C, NH, 3 * C, hm ? Na : 0, "PAG")) { if (error.empty()) error = sd_last_error(); return x; }
+            pl.tensors[a1].bytes = ((size_t)Mm * C * 2 + 255) / 256 * 256;      // (the attention op sized it for its own samples)
+            Op o; o.kind = OP_PAG_IDENTITY; o.x1 = qkv; o.out = a1; o.M = Mm; o.N = C; o.heads = NH; o.qoff = row0; o.koff = rows;
+            o.hm = hm ? 1 : 0; o.HW = hm ? Na : 0; o.voff = hm ? 2l * Mm * C : 2 * C; o.ldv = 3 * C;
+            push(o);
+        }
         int h1 = gemm(a1, C, -1, 0, Mm, C, t + "attn1.to_out.0.weight", t + "attn1.to_out.0.bias", tr > 0 ? -1 : h0, 0);
         const int to_out_op = (int)pl.ops.size() - 1;
         if (tr > 0) {
@@ -808,7 +834,8 @@ struct Builder {
         // ---- conv_in ----
         int rh = pl.lh, rw = pl.lw;
         int h;
-        if (pl.rep > 1) { prefix_rep = pl.rep; UB /= pl.rep; }       // (restored by the first transformer block)
+        // (restored by the first transformer block; a PAG plan of a UNet without one on its first level runs without the prefix)
+        if (pl.rep > 1 && (!pl.pag_lb || c.attn_levels[0])) { prefix_rep = pl.rep; UB /= pl.rep; }
         { Op o; o.kind = OP_CONV_IN; o.x1 = T_LATENTS; o.B = UB; o.Hin = rh; o.Win = rw; o.Cin = c.in_channels; o.N = c0;
           o.w = W("conv_in.weight"); o.b = W("conv_in.bias"); o.out = tensor((size_t)UB * rh * rw * c0 * 2); push(o); h = o.out; }
         const int h_skip = prefix_rep > 1 ? replicate(h, (size_t)UB * rh * rw * c0 * 2, prefix_rep) : h;
@@ -1054,8 +1081,18 @@ void assign_memory(sd_unet* u, Plan& pl) {
 
 }  // namespace
 
-// CFG de-duplication applies to a forward whose UNet batch is exactly two copies of the latent batch (SD_CFG_DEDUP=0: off)
+int transformer_block_count(const sd_unet_config& c) {
+    int n = 1;      // (the mid block's)
+    for (int i = 0; i < c.num_levels; ++i)
+        if (c.attn_levels[i]) n += 2 * c.layers_per_block + 1;
+    return n;
+}
+
+// CFG de-duplication applies to a forward whose UNet batch is exactly two copies of the latent batch (SD_CFG_DEDUP=0: off).
+// A handle with a PAG mask: the copies of the latent batch in the UNet batch, 3 or 2 (the forward refuses any other batch).
 int plan_rep(const sd_unet* u, int latent_batch, int unet_batch) {
+    if (u->kind == 0 && u->pag_mask)
+        return (latent_batch > 0 && (unet_batch == 3 * latent_batch || unet_batch == 2 * latent_batch)) ? unet_batch / latent_batch : 1;
     static const bool off = getenv("SD_CFG_DEDUP") && atoi(getenv("SD_CFG_DEDUP")) == 0;
     return (!off && u->unet_like() && u->cfg.attn_levels[0] && latent_batch > 0 && unet_batch == 2 * latent_batch) ? 2 : 1;
 }
@@ -1148,7 +1185,12 @@ int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw
     SD_REQUIRE(!tgate || (branch < 0 && !ip && !cn && !u->fp8), "unet: T-GATE with DeepCache, an IP-Adapter, ControlNet residuals or fp8 is not built");
     SD_REQUIRE(tg_pair == 1 || UB % 2 == 0, "unet: a T-GATE capture of a CFG pair needs an even batch (%d)", UB);
     auto key = std::make_tuple(UB, branch, rep, lh, lw, ip, cn, tome_bits, tome_bits ? u->tome_max_downsample : 0, freeu, tgate, tg_pair,
-                               u->kind == 0 ? u->ht_tokens : 0, u->kind == 0 && u->ht_tokens ? u->ht_max_depth : 0);
+                               u->kind == 0 ? u->ht_tokens : 0, u->kind == 0 && u->ht_tokens ? u->ht_max_depth : 0,
+                               u->kind == 0 ? u->pag_mask : 0ll);
+    const bool pag = u->kind == 0 && u->pag_mask;
+    SD_REQUIRE(!pag || (branch < 0 && !ip && !cn && !tgate && !tome_bits && !u->fp8),
+               "unet: PAG with DeepCache, an IP-Adapter image prompt, ControlNet residuals, T-GATE, Token Merging or fp8 is not built");
+    SD_REQUIRE(!pag || rep == 1 || ((rep == 2 || rep == 3) && UB % rep == 0), "unet: a PAG forward runs 2 or 3 copies of the latent batch (%d of batch %d)", rep, UB);
     auto it = u->plans.find(key);
     if (it == u->plans.end()) {
         if (lh != u->cfg.sample_size || lw != u->cfg.sample_size)
@@ -1164,6 +1206,7 @@ int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw
         pl.freeu = freeu;
         pl.tgate = tgate;
         pl.tg_pair = tg_pair;
+        pl.pag_lb = pag && rep > 1 ? UB / rep : 0;      // (rep 1: the plan sd_unet_set_context_hw lays the prompt tensors out with)
         Builder b{u, pl, UB, {}};
         b.build();
         SD_REQUIRE(b.error.empty(), "unet: cannot build the plan for batch %d (cache branch %d, latent %dx%d): %s", UB, branch, lh, lw,

@@ -1,18 +1,29 @@
 // The end of every sampling step: the fused CFG-combine + scheduler.step update (optional per-sample rescale, optional
-// inpainting blend), the rescaled-CFG factors, UniPC's predictor-corrector step, and their five C entry points.
+// inpainting blend), the rescaled-CFG factors, UniPC's predictor-corrector step, and their C entry points: five plain ones and
+// the three perturbed-attention-guidance (PAG) forms of the step, the predictor-corrector step and the factors.
 #include "common.h"
 #include "kernels.h"
+#include "../../include/sd_hip.h"
 
 namespace {
 
 __device__ __forceinline__ f32x4 cfg_combine(f32x4 e, f32x4 et, float guidance) { return e + guidance * (et - e); }
 
-// the prediction a step works on: eps, CFG-combined when cfg is set, scaled by its sample's factor when RESCALED
+// perturbed-attention guidance on top of a combined prediction g: g + s (c - p), c the conditional and p the perturbed output
+__device__ __forceinline__ f32x4 pag_combine(f32x4 g, f32x4 c, f32x4 p, float pag) { return g + pag * (c - p); }
+
+// the prediction a step works on: eps, combined as the guidance mode `cfg` says, scaled by its sample's factor when RESCALED.
+//   0: eps as it is     1 (CFG): eps = [u | c], u + g (c - u)
+//   SD_GUIDE_CFG_PAG: eps = [u | c | p], (u + g (c - u)) + s (c - p)     SD_GUIDE_PAG: eps = [c | p], c + s (c - p)
 template <bool RESCALED>
-__device__ __forceinline__ f32x4 step_eps(const float* __restrict__ eps, int cfg, float guidance,
+__device__ __forceinline__ f32x4 step_eps(const float* __restrict__ eps, int cfg, float guidance, float pag,
                                           const float* __restrict__ k, long n4s, long n4, long i) {
     f32x4 e = ((const f32x4*)eps)[i];
-    if (cfg) e = cfg_combine(e, ((const f32x4*)eps)[i + n4], guidance);
+    if (cfg == 1) e = cfg_combine(e, ((const f32x4*)eps)[i + n4], guidance);
+    else if (cfg == SD_GUIDE_CFG_PAG) {
+        const f32x4 c = ((const f32x4*)eps)[i + n4];
+        e = pag_combine(cfg_combine(e, c, guidance), c, ((const f32x4*)eps)[i + 2 * n4], pag);
+    } else if (cfg == SD_GUIDE_PAG) e = pag_combine(e, e, ((const f32x4*)eps)[i + n4], pag);
     if (RESCALED) e = k[i / n4s] * e;
     return e;
 }
@@ -34,7 +45,7 @@ __device__ __forceinline__ f32x4 latent_blend(f32x4 p, const float* __restrict__
 // RESCALED: e := k[b] * e before every use.  BLEND: the latent blend of prev; y2 and m_out do not see the mask.  An
 // instantiation without one of them does not read that one's arguments.
 template <bool RESCALED, bool BLEND>
-__global__ void sched_step_kernel(const float* __restrict__ eps, int cfg, float guidance,
+__global__ void sched_step_kernel(const float* __restrict__ eps, int cfg, float guidance, float pag,
                                   const float* __restrict__ x, const float* __restrict__ m1,
                                   const float* __restrict__ m2, const float* __restrict__ m3,
                                   const float* __restrict__ noise, float* __restrict__ prev,
@@ -44,7 +55,7 @@ __global__ void sched_step_kernel(const float* __restrict__ eps, int cfg, float 
                                   float s, long hw4) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
-    const f32x4 e = step_eps<RESCALED>(eps, cfg, guidance, k, n4s, n4, i);
+    const f32x4 e = step_eps<RESCALED>(eps, cfg, guidance, pag, k, n4s, n4, i);
     const f32x4 xv = ((const f32x4*)x)[i];
     f32x4 p = c.px * xv + c.pe * e;
     if (m1) p += c.p1 * ((const f32x4*)m1)[i];
@@ -62,6 +73,7 @@ __global__ void sched_step_kernel(const float* __restrict__ eps, int cfg, float 
 // is the std of the values the step scales.  One block per sample, fixed thread -> element assignment, double partials,
 // wave butterflies and an in-order sum of the wave partials: k_b depends on sample b's data and n_per_sample only (not on
 // the batch, the sample's position or the grid) -- dist.py's sharding invariant.  Two passes (mean, then centred sum).
+// with_pag: eps = [u | c | p] and g carries the PAG term, as the step's does.
 constexpr int RESCALE_THREADS = 512;
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
@@ -92,14 +104,18 @@ __device__ __forceinline__ void block_sum2_f64(double& a, double& b, double (*re
 
 __global__ __launch_bounds__(RESCALE_THREADS) void cfg_rescale_factors_kernel(const float* __restrict__ eps, int batch,
                                                                               long n4s, float guidance, float rescale,
-                                                                              float* __restrict__ k_out) {
+                                                                              float* __restrict__ k_out, int with_pag,
+                                                                              float pag) {
     __shared__ double red[2][RESCALE_THREADS / 64];
     const int b = blockIdx.x;
     const f32x4* u = (const f32x4*)eps + (long)b * n4s;
     const f32x4* c = (const f32x4*)eps + ((long)batch + b) * n4s;
+    const f32x4* p = (const f32x4*)eps + (2l * batch + b) * n4s;      // (the perturbed third: read with_pag only)
     double sc = 0.0, sg = 0.0;
     for (long i = threadIdx.x; i < n4s; i += RESCALE_THREADS) {
-        const f32x4 et = c[i], g = cfg_combine(u[i], et, guidance);
+        const f32x4 et = c[i];
+        f32x4 g = cfg_combine(u[i], et, guidance);
+        if (with_pag) g = pag_combine(g, et, p[i], pag);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             sc += (double)et[j];
@@ -111,7 +127,9 @@ __global__ __launch_bounds__(RESCALE_THREADS) void cfg_rescale_factors_kernel(co
     const double mc = sc / n, mg = sg / n;
     double qc = 0.0, qg = 0.0;
     for (long i = threadIdx.x; i < n4s; i += RESCALE_THREADS) {
-        const f32x4 et = c[i], g = cfg_combine(u[i], et, guidance);
+        const f32x4 et = c[i];
+        f32x4 g = cfg_combine(u[i], et, guidance);
+        if (with_pag) g = pag_combine(g, et, p[i], pag);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const double dc = (double)et[j] - mc, dg = (double)g[j] - mg;
@@ -133,7 +151,8 @@ __global__ __launch_bounds__(RESCALE_THREADS) void cfg_rescale_factors_kernel(co
 // and BLEND: latent_blend of prev.  Terms are added left to right; a null h term is skipped (the host side has checked that
 // its coefficients are 0).  x_corr, y2 and m_out do not see the mask.
 template <bool RESCALED, bool BLEND>
-__global__ void sched_step_pc_kernel(const float* __restrict__ eps, int cfg, float guidance, const float* __restrict__ x,
+__global__ void sched_step_pc_kernel(const float* __restrict__ eps, int cfg, float guidance, float pag,
+                                     const float* __restrict__ x,
                                      const float* __restrict__ x_last, const float* __restrict__ h1,
                                      const float* __restrict__ h2, const float* __restrict__ h3, float* __restrict__ prev,
                                      float* __restrict__ x_corr, float* __restrict__ y2, float* __restrict__ m_out,
@@ -142,7 +161,7 @@ __global__ void sched_step_pc_kernel(const float* __restrict__ eps, int cfg, flo
                                      const float* __restrict__ mask, float a, float s, long hw4) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
-    const f32x4 e = step_eps<RESCALED>(eps, cfg, guidance, k, n4s, n4, i);
+    const f32x4 e = step_eps<RESCALED>(eps, cfg, guidance, pag, k, n4s, n4, i);
     const f32x4 xv = ((const f32x4*)x)[i];
     const f32x4 mt = c.cm[0] * xv + c.cm[1] * e;
     f32x4 v1 = {0.f, 0.f, 0.f, 0.f}, v2 = v1;
@@ -199,7 +218,7 @@ static int check_blend(const char* who, const float* blend_noise, const float* m
         else hipLaunchKernelGGL((kernel<false, false>), grid, dim3(256), 0, stream, __VA_ARGS__);                     \
     } while (0)
 
-int sd_launch_sched_step(const char* who, const float* eps, int cfg, float guidance, const float* x, const float* m1,
+int sd_launch_sched_step(const char* who, const float* eps, int cfg, float guidance, float pag, const float* x, const float* m1,
                          const float* m2, const float* m3, const float* noise, float* prev, float* y2, float* m_out,
                          StepCoef c, const float* k, long n_per_sample, long n, const float* init, const float* blend_noise,
                          const float* mask, float a, float s, long hw, hipStream_t stream) {
@@ -210,20 +229,20 @@ int sd_launch_sched_step(const char* who, const float* eps, int cfg, float guida
     if (init)
         if (int rc = check_blend(who, blend_noise, mask, s, hw, n_per_sample)) return rc;
     const long n4 = n / 4, n4s = per_sample ? n_per_sample / 4 : n4, hw4 = init ? hw / 4 : 1;
-    SD_LAUNCH_STEP(sched_step_kernel, n4, eps, cfg, guidance, x, m1, m2, m3, noise, prev, y2, m_out, c, k, n4s, n4, init,
+    SD_LAUNCH_STEP(sched_step_kernel, n4, eps, cfg, guidance, pag, x, m1, m2, m3, noise, prev, y2, m_out, c, k, n4s, n4, init,
                    blend_noise, mask, a, s, hw4);
     SD_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
 int sd_launch_cfg_rescale_factors(const float* eps, int batch, long n_per_sample, float guidance, float rescale, float* k_out,
-                                  hipStream_t stream) {
+                                  hipStream_t stream, int with_pag, float pag) {
     SD_REQUIRE(eps && k_out, "cfg_rescale_factors: null operand");
     SD_REQUIRE(batch > 0 && batch <= 65535, "cfg_rescale_factors: batch=%d", batch);
     SD_REQUIRE(n_per_sample >= 4 && n_per_sample % 4 == 0,
                "cfg_rescale_factors: n_per_sample=%ld must be a positive multiple of 4", n_per_sample);
     hipLaunchKernelGGL(cfg_rescale_factors_kernel, dim3(batch), dim3(RESCALE_THREADS), 0, stream, eps, batch,
-                       n_per_sample / 4, guidance, rescale, k_out);
+                       n_per_sample / 4, guidance, rescale, k_out, with_pag, pag);
     SD_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -234,46 +253,45 @@ static bool pc_overlap(const void* p, size_t bytes, const void* q, size_t bytes_
     return p && q && a < b + bytes_q && b < a + bytes;
 }
 
-int sd_launch_sched_step_pc(const float* eps, int cfg, float guidance, const float* x, const float* x_last, const float* h1,
+int sd_launch_sched_step_pc(const char* who, const float* eps, int cfg, float guidance, float pag, const float* x, const float* x_last, const float* h1,
                             const float* h2, const float* h3, float* prev, float* x_corr, float* y2, float* m_out, PcCoef c,
                             const float* k, long n_per_sample, long n, const float* init, const float* blend_noise,
                             const float* mask, float a, float s, long hw, hipStream_t stream) {
-    const char* who = "sched_step_pc";
     if (int rc = check_size(who, eps, x, prev, n)) return rc;
     if (int rc = check_per_sample(who, n_per_sample, n)) return rc;
     if (init) {
         if (int rc = check_blend(who, blend_noise, mask, s, hw, n_per_sample)) return rc;
-        SD_REQUIRE(std::isfinite(a) && std::isfinite(s), "sched_step_pc: blend coefficients a=%g s=%g must be finite",
+        SD_REQUIRE(std::isfinite(a) && std::isfinite(s), "%s: blend coefficients a=%g s=%g must be finite", who,
                    (double)a, (double)s);
     }
-    SD_REQUIRE(std::isfinite(guidance), "sched_step_pc: guidance=%g must be finite", (double)guidance);
+    SD_REQUIRE(std::isfinite(guidance), "%s: guidance=%g must be finite", who, (double)guidance);
     const float* rows[4] = {c.cm, c.cy, c.cc, c.cp};
     const char* row_names[4] = {"cm", "cy", "cc", "cp"};
     const int row_len[4] = {2, 2, 5, 4};
     for (int r = 0; r < 4; ++r)
         for (int j = 0; j < row_len[r]; ++j)
-            SD_REQUIRE(std::isfinite(rows[r][j]), "sched_step_pc: coefficient %s[%d]=%g must be finite", row_names[r], j,
+            SD_REQUIRE(std::isfinite(rows[r][j]), "%s: coefficient %s[%d]=%g must be finite", who, row_names[r], j,
                        (double)rows[r][j]);
     // a null history entry carries no weight (the corrector's row is not read without x_last)
-    SD_REQUIRE(h1 || (c.cp[2] == 0.f && (!x_last || c.cc[1] == 0.f)), "sched_step_pc: h1 is null but has a coefficient");
-    SD_REQUIRE(h2 || (c.cp[3] == 0.f && (!x_last || c.cc[2] == 0.f)), "sched_step_pc: h2 is null but has a coefficient");
-    SD_REQUIRE(h3 || !x_last || c.cc[3] == 0.f, "sched_step_pc: h3 is null but has a coefficient");
+    SD_REQUIRE(h1 || (c.cp[2] == 0.f && (!x_last || c.cc[1] == 0.f)), "%s: h1 is null but has a coefficient", who);
+    SD_REQUIRE(h2 || (c.cp[3] == 0.f && (!x_last || c.cc[2] == 0.f)), "%s: h2 is null but has a coefficient", who);
+    SD_REQUIRE(h3 || !x_last || c.cc[3] == 0.f, "%s: h3 is null but has a coefficient", who);
     const size_t nb = (size_t)n * 4, batch = (size_t)(n / n_per_sample);
     const void* outs[4] = {prev, x_corr, y2, m_out};
     const char* out_names[4] = {"prev", "x_corr", "y2", "m_out"};
     const void* ins[10] = {eps, x, x_last, h1, h2, h3, k, init, blend_noise, mask};
     const char* in_names[10] = {"eps", "x", "x_last", "h1", "h2", "h3", "k", "init", "blend_noise", "mask"};
-    const size_t in_bytes[10] = {cfg ? 2 * nb : nb, nb, nb, nb, nb, nb, batch * 4, nb, nb, init ? batch * (size_t)hw * 4 : 0};
+    const size_t in_bytes[10] = {cfg == SD_GUIDE_CFG_PAG ? 3 * nb : cfg ? 2 * nb : nb, nb, nb, nb, nb, nb, batch * 4, nb, nb, init ? batch * (size_t)hw * 4 : 0};
     for (int o = 0; o < 4; ++o) {
         for (int j = 0; j < 10; ++j)
-            SD_REQUIRE(!pc_overlap(outs[o], nb, ins[j], in_bytes[j]), "sched_step_pc: output %s aliases input %s", out_names[o],
+            SD_REQUIRE(!pc_overlap(outs[o], nb, ins[j], in_bytes[j]), "%s: output %s aliases input %s", who, out_names[o],
                        in_names[j]);
         for (int q = 0; q < o; ++q)
-            SD_REQUIRE(!pc_overlap(outs[o], nb, outs[q], nb), "sched_step_pc: output %s aliases output %s", out_names[o],
+            SD_REQUIRE(!pc_overlap(outs[o], nb, outs[q], nb), "%s: output %s aliases output %s", who, out_names[o],
                        out_names[q]);
     }
     const long n4 = n / 4, n4s = n_per_sample / 4, hw4 = init ? hw / 4 : 1;
-    SD_LAUNCH_STEP(sched_step_pc_kernel, n4, eps, cfg, guidance, x, x_last, h1, h2, h3, prev, x_corr, y2, m_out, c, k, n4s,
+    SD_LAUNCH_STEP(sched_step_pc_kernel, n4, eps, cfg, guidance, pag, x, x_last, h1, h2, h3, prev, x_corr, y2, m_out, c, k, n4s,
                    n4, init, blend_noise, mask, a, s, hw4);
     SD_CHECK_HIP(hipGetLastError());
     return 0;
@@ -289,7 +307,7 @@ extern "C" int sd_sched_step(void* stream, const float* eps, int cfg, float guid
                              const float* m2, const float* m3, const float* noise, float* prev, float* y2, float* m_out,
                              const float coef[10], long long n) {
     SD_REQUIRE(coef, "sched_step: null coefficients");
-    return sd_launch_sched_step("sched_step", eps, cfg, guidance, x, m1, m2, m3, noise, prev, y2, m_out, step_coef(coef),
+    return sd_launch_sched_step("sched_step", eps, cfg != 0, guidance, 0.f, x, m1, m2, m3, noise, prev, y2, m_out, step_coef(coef),
                                 nullptr, 0, (long)n, nullptr, nullptr, nullptr, 1.f, 0.f, 0, (hipStream_t)stream);
 }
 
@@ -304,7 +322,7 @@ extern "C" int sd_sched_step_rescaled(void* stream, const float* eps, int cfg, f
                                       long long n_per_sample) {
     SD_REQUIRE(coef, "sched_step_rescaled: null coefficients");
     SD_REQUIRE(k, "sched_step_rescaled: null operand");
-    return sd_launch_sched_step("sched_step_rescaled", eps, cfg, guidance, x, m1, m2, m3, noise, prev, y2, m_out,
+    return sd_launch_sched_step("sched_step_rescaled", eps, cfg != 0, guidance, 0.f, x, m1, m2, m3, noise, prev, y2, m_out,
                                 step_coef(coef), k, (long)n_per_sample, (long)n, nullptr, nullptr, nullptr, 1.f, 0.f, 0,
                                 (hipStream_t)stream);
 }
@@ -316,7 +334,7 @@ extern "C" int sd_sched_step_inpaint(void* stream, const float* eps, int cfg, fl
                                      long long hw) {
     SD_REQUIRE(coef, "sched_step_inpaint: null coefficients");
     SD_REQUIRE(init && mask, "sched_step_inpaint: null operand");
-    return sd_launch_sched_step("sched_step_inpaint", eps, cfg, guidance, x, m1, m2, m3, noise, prev, y2, m_out,
+    return sd_launch_sched_step("sched_step_inpaint", eps, cfg != 0, guidance, 0.f, x, m1, m2, m3, noise, prev, y2, m_out,
                                 step_coef(coef), k, (long)n_per_sample, (long)n, init, blend_noise, mask, a, s, (long)hw,
                                 (hipStream_t)stream);
 }
@@ -329,6 +347,45 @@ extern "C" int sd_sched_step_pc(void* stream, const float* eps, int cfg, float g
     SD_REQUIRE(coef, "sched_step_pc: null coefficients");
     PcCoef c{{coef[0], coef[1]}, {coef[2], coef[3]}, {coef[4], coef[5], coef[6], coef[7], coef[8]},
              {coef[9], coef[10], coef[11], coef[12]}};
-    return sd_launch_sched_step_pc(eps, cfg, guidance, x, x_last, h1, h2, h3, prev, x_corr, y2, m_out, c, k, (long)n_per_sample,
-                                   (long)n, init, blend_noise, mask, a, s, (long)hw, (hipStream_t)stream);
+    return sd_launch_sched_step_pc("sched_step_pc", eps, cfg != 0, guidance, 0.f, x, x_last, h1, h2, h3, prev, x_corr, y2, m_out, c, k,
+                                   (long)n_per_sample, (long)n, init, blend_noise, mask, a, s, (long)hw, (hipStream_t)stream);
+}
+
+// ---- perturbed-attention guidance: the same launchers with a PAG guidance mode ----------------------------------------
+static int check_pag(const char* who, int mode, float guidance, float pag_scale) {
+    SD_REQUIRE(mode == SD_GUIDE_CFG_PAG || mode == SD_GUIDE_PAG, "%s: mode=%d (SD_GUIDE_CFG_PAG = %d or SD_GUIDE_PAG = %d)", who, mode,
+               SD_GUIDE_CFG_PAG, SD_GUIDE_PAG);
+    SD_REQUIRE(std::isfinite(guidance), "%s: guidance=%g must be finite", who, (double)guidance);
+    SD_REQUIRE(std::isfinite(pag_scale), "%s: pag_scale=%g must be finite", who, (double)pag_scale);
+    return 0;
+}
+
+extern "C" int sd_sched_step_pag(void* stream, const float* eps, int mode, float guidance, float pag_scale, const float* x,
+                                 const float* m1, const float* m2, const float* m3, const float* noise, float* prev, float* y2,
+                                 float* m_out, const float coef[10], long long n, const float* k, long long n_per_sample,
+                                 const float* init, const float* blend_noise, const float* mask, float a, float s, long long hw) {
+    SD_REQUIRE(coef, "sched_step_pag: null coefficients");
+    if (int rc = check_pag("sched_step_pag", mode, guidance, pag_scale)) return rc;
+    return sd_launch_sched_step("sched_step_pag", eps, mode, guidance, pag_scale, x, m1, m2, m3, noise, prev, y2, m_out,
+                                step_coef(coef), k, (long)n_per_sample, (long)n, init, blend_noise, mask, a, s, (long)hw,
+                                (hipStream_t)stream);
+}
+
+extern "C" int sd_sched_step_pc_pag(void* stream, const float* eps, int mode, float guidance, float pag_scale, const float* x,
+                                    const float* x_last, const float* h1, const float* h2, const float* h3, float* prev,
+                                    float* x_corr, float* y2, float* m_out, const float coef[13], long long n, const float* k,
+                                    long long n_per_sample, const float* init, const float* blend_noise, const float* mask,
+                                    float a, float s, long long hw) {
+    SD_REQUIRE(coef, "sched_step_pc_pag: null coefficients");
+    if (int rc = check_pag("sched_step_pc_pag", mode, guidance, pag_scale)) return rc;
+    PcCoef c{{coef[0], coef[1]}, {coef[2], coef[3]}, {coef[4], coef[5], coef[6], coef[7], coef[8]},
+             {coef[9], coef[10], coef[11], coef[12]}};
+    return sd_launch_sched_step_pc("sched_step_pc_pag", eps, mode, guidance, pag_scale, x, x_last, h1, h2, h3, prev, x_corr, y2, m_out, c,
+                                   k, (long)n_per_sample, (long)n, init, blend_noise, mask, a, s, (long)hw, (hipStream_t)stream);
+}
+
+extern "C" int sd_cfg_rescale_factors_pag(void* stream, const float* eps, int batch, long long n_per_sample, float guidance,
+                                          float pag_scale, float rescale, float* k_out) {
+    if (int rc = check_pag("cfg_rescale_factors_pag", SD_GUIDE_CFG_PAG, guidance, pag_scale)) return rc;
+    return sd_launch_cfg_rescale_factors(eps, batch, (long)n_per_sample, guidance, rescale, k_out, (hipStream_t)stream, 1, pag_scale);
 }

@@ -207,6 +207,8 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
             return sd_launch_hypertile_gather((const bf16_t*)T(o.x1), o.N, (bf16_t*)T(o.out), o.B, o.Hin, o.Win, o.N, o.K, o.K1, stream);
         case OP_HT_SCATTER:
             return sd_launch_hypertile_scatter((const bf16_t*)T(o.x1), (bf16_t*)T(o.out), o.N, o.B, o.Hin, o.Win, o.N, o.K, o.K1, stream);
+        case OP_PAG_IDENTITY:    // (qoff / koff: the first perturbed row and their count; HW: tokens of a head-major sample, 0 = token-major)
+            return sd_launch_pag_identity((const bf16_t*)T(o.x1) + o.voff, o.ldv, o.HW, (bf16_t*)T(o.out), o.M, o.qoff, o.koff, o.N, o.heads, stream);
         case OP_TOME_MATCH:
             SD_REQUIRE(u->tome_choice && o.b2idx + (long)(o.Hin / 2) * (o.Win / 2) <= u->tome_choice_n, "forward: no Token Merging choice array");
             return sd_launch_tome_match((const bf16_t*)T(o.x1), u->tome_choice + o.b2idx, o.B, o.Hin, o.Win, o.N, (float*)T(o.out),
@@ -734,6 +736,15 @@ extern "C" long long sd_unet_workspace_bytes_hw(sd_unet* u, int unet_batch, int 
     size_t bytes = pl->total_bytes;
     const bool pair = unet_batch % 2 == 0 && plan_rep(u, unet_batch / 2, unet_batch) == 2;      // the CFG-pair variant of the plan
     const bool tg = tgate_variant(u) != TGATE_OFF;       // (T-GATE capture / reuse: no IP-Adapter and no control variants exist)
+    if (u->kind == 0 && u->pag_mask) {       // PAG: the plans of 2 and of 3 copies of a latent batch, no other variant exists
+        SD_REQUIRE(cache_branch_id < 0, "workspace_bytes: PAG with DeepCache is not built");
+        for (int rep = 2; rep <= 3; ++rep)
+            if (unet_batch % rep == 0) {
+                if (get_plan(u, unet_batch, -1, &pl, rep, latent_h, latent_w)) return -1;
+                bytes = std::max(bytes, pl->total_bytes);
+            }
+        return (long long)bytes;
+    }
     for (int ip = 0; ip <= (u->kind == 0 && u->cfg.ip_adapter_tokens > 0 && !tg ? 1 : 0); ++ip)         // ... and the IP-Adapter variants
         for (int rep = 1; rep <= (pair ? 2 : 1); ++rep)
             for (int cn = 0; cn <= (u->kind == 0 && u->ctrl_enabled && cache_branch_id < 0 && !tg ? 1 : 0); ++cn) {      // ... and, once a ControlNet's residuals were set, the control variants
@@ -1136,6 +1147,18 @@ static int check_tgate_forward(const sd_unet* u, const char* who, int latent_bat
     return 0;
 }
 
+// a forward of a handle with a PAG mask runs [uncond | cond | perturbed] or [cond | perturbed] over ONE set of latents, alone
+static int check_pag_forward(const sd_unet* u, const char* who, int latent_batch, int unet_batch, int cache_mode, int branch, int ip, int cn) {
+    SD_REQUIRE(unet_batch == 3 * latent_batch || unet_batch == 2 * latent_batch, "%s: with PAG on the UNet batch is 3 or 2 times the latent "
+               "batch, [uncond | cond | perturbed] or [cond | perturbed] (UNet batch %d, %d latents; sd_unet_set_pag(u, 0) = off)", who,
+               unet_batch, latent_batch);
+    SD_REQUIRE(cache_mode == SD_CACHE_OFF && branch < 0, "%s: PAG with DeepCache is not built", who);
+    SD_REQUIRE(!ip && !cn, "%s: PAG with an IP-Adapter image prompt or ControlNet residuals is not built", who);
+    SD_REQUIRE(!u->tg_mode, "%s: PAG with T-GATE is not built", who);
+    SD_REQUIRE(!(u->tome_ratio > 0.0), "%s: PAG with Token Merging is not built", who);
+    return 0;
+}
+
 // the handle's dst-choice array for the plan about to run: n bytes, zero (position 0 of every cell) unless set for this size
 static int ensure_tome_choice(sd_unet* u, long n, void* stream) {
     if (n <= 0 || (u->tome_choice && u->tome_choice_n == n)) return 0;
@@ -1175,6 +1198,7 @@ extern "C" int sd_unet_forward_hw(sd_unet* u, void* stream, const float* latents
     const int cn = u->ctrl_res ? 1 : 0;
     if (cn && check_control_set(u, "forward", unet_batch, latent_h, latent_w, cache_mode, cache_branch_id)) return -1;
     if (u->tg_mode && check_tgate_forward(u, "forward", latent_batch, unet_batch, latent_h, latent_w, cache_mode, cache_branch_id, ip, cn)) return -1;
+    if (u->pag_mask && check_pag_forward(u, "forward", latent_batch, unet_batch, cache_mode, cache_branch_id, ip, cn)) return -1;
     u->last_rep = rep; u->last_ip = ip; u->last_cn = cn;
     u->last_h = latent_h; u->last_w = latent_w;
     int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, latent_h, latent_w, ip, cn);
@@ -1266,6 +1290,30 @@ extern "C" int sd_unet_set_tgate_hw(sd_unet* u, int mode, void* cache, long long
 extern "C" int sd_unet_plan_count(const sd_unet* u) {
     SD_REQUIRE(u, "plan_count: null handle");
     return (int)u->plans.size();
+}
+
+// ---- PAG (pag.hip; the plan side is Builder::transformer) ------------------------------------------------------------------
+extern "C" int sd_unet_pag_block_count(const sd_unet* u) {
+    SD_REQUIRE(u && u->kind == 0, "pag_block_count: not a UNet handle");
+    return transformer_block_count(u->cfg);
+}
+
+extern "C" int sd_unet_set_pag(sd_unet* u, long long layer_mask) {
+    SD_REQUIRE(u && u->kind == 0, "set_pag: not a UNet handle");
+    if (layer_mask == 0) {          // off: the plans of a handle that never saw PAG
+        u->pag_mask = 0;
+        return 0;
+    }
+    const int nb = transformer_block_count(u->cfg);
+    SD_REQUIRE(nb < 63 && layer_mask > 0 && (layer_mask >> nb) == 0, "set_pag: layer mask 0x%llx (bits 0 .. %d: the UNet has %d transformer "
+               "blocks; 0 = off)", (unsigned long long)layer_mask, nb - 1, nb);
+    SD_REQUIRE(!u->fp8, "set_pag: PAG is not built for fp8 handles");
+    SD_REQUIRE(u->cfg.in_channels == 4, "set_pag: PAG is refused on a 9-channel inpainting UNet");
+    SD_REQUIRE(u->cfg.ip_adapter_tokens == 0, "set_pag: PAG is refused on a UNet with an IP-Adapter");
+    SD_REQUIRE(!(u->tome_ratio > 0.0), "set_pag: Token Merging is on (PAG and Token Merging together are not built)");
+    SD_REQUIRE(!u->tg_mode, "set_pag: T-GATE is on (PAG and T-GATE together are not built)");
+    u->pag_mask = layer_mask;
+    return 0;
 }
 
 // ---- HyperTile (hypertile.hip; the plan side is Builder::transformer) --------------------------------------------------------
@@ -1532,6 +1580,9 @@ static void op_work(const Op& o, double* flops, double* bytes) {
             *flops = 2.0 * 14.0 * o.B * (double)o.Hin * o.Win * o.C2;
             *bytes = 2.0 * o.B * (double)o.Hin * o.Win * (2.0 * o.C1 + 3.0 * o.C2);
             break;
+        case OP_PAG_IDENTITY:   // the perturbed rows in and out
+            *bytes = 2.0 * 2.0 * (double)o.koff * o.N;
+            break;
         case OP_HT_GATHER:
         case OP_HT_SCATTER:     // every row in, every row out
             *bytes = 2.0 * 2.0 * o.B * (double)o.Hin * o.Win * o.N;
@@ -1570,6 +1621,7 @@ static int profiled_run(sd_unet* u, void* stream, const float* latents, int late
     if (cn && check_control_set(u, "forward_profiled", unet_batch, u->cfg.sample_size, u->cfg.sample_size, cache_mode, cache_branch_id)) return -1;
     if (u->tg_mode && check_tgate_forward(u, "forward_profiled", latent_batch, unet_batch, u->cfg.sample_size, u->cfg.sample_size, cache_mode,
                                           cache_branch_id, ip, cn)) return -1;
+    if (u->pag_mask && check_pag_forward(u, "forward_profiled", latent_batch, unet_batch, cache_mode, cache_branch_id, ip, cn)) return -1;
     u->last_rep = rep; u->last_ip = ip; u->last_cn = cn;
     u->last_h = u->last_w = u->cfg.sample_size;
     int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, -1, -1, ip, cn);
@@ -1635,7 +1687,8 @@ extern "C" int sd_unet_forward_profiled(sd_unet* u, void* stream, const float* l
         }
         // (24 / 25 / 26: T-GATE's capture, apply and the capture plan's zero fill -- the op kinds of those numbers never run on a UNet)
         // (9 / 10: HyperTile's gather and scatter, likewise)
-        const int kd = o.kind == OP_HT_GATHER ? 9 : o.kind == OP_HT_SCATTER ? 10 : o.kind == OP_TGATE_CAPTURE ? 24 : o.kind == OP_TGATE_APPLY ? 25 : o.kind == OP_TGATE_ZERO ? 26 : o.kind == OP_XATTN ? 18 : o.kind == OP_REPLICATE ? 19 : o.kind == OP_IP_XATTN ? 22 : o.kind == OP_RES_ADD ? 23 : halo4 ? 21 :
+        // (11: PAG's identity self-attention, likewise)
+        const int kd = o.kind == OP_PAG_IDENTITY ? 11 : o.kind == OP_HT_GATHER ? 9 : o.kind == OP_HT_SCATTER ? 10 : o.kind == OP_TGATE_CAPTURE ? 24 : o.kind == OP_TGATE_APPLY ? 25 : o.kind == OP_TGATE_ZERO ? 26 : o.kind == OP_XATTN ? 18 : o.kind == OP_REPLICATE ? 19 : o.kind == OP_IP_XATTN ? 22 : o.kind == OP_RES_ADD ? 23 : halo4 ? 21 :
                        (o.kind == OP_CONV3 && !o.dt && (o.subpix || o.stride != 1)) ? 20 :
                        (o.dt ? (o.kind == OP_CONV3 ? 16 : 17) : o.kind);
         kind_ms[kd] += ms; kind_launches[kd] += 1; kind_flops[kd] += fl; kind_bytes[kd] += by;

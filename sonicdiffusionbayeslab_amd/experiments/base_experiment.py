@@ -90,6 +90,9 @@ class BaseMethod(ABC):
         hypertile = self.parse_hypertile(self.config.model, self.config.model.get("weight_dtype", None) or "bf16")    # key of this build: model.hypertile
         if hypertile is not None:
             self.model.enable_hypertile(**hypertile)
+        pag = self.parse_pag(self.config.model, self.config.model.get("weight_dtype", None) or "bf16")    # key of this build: model.pag
+        if pag is not None:
+            self.model.enable_pag(**pag)
         gate = self.parse_tgate(self.config.model)     # key of this build: model.tgate_step
         if gate is not None:
             self.model.enable_tgate(gate)
@@ -104,6 +107,30 @@ class BaseMethod(ABC):
             return None
         from ..models import StableDiffusionModel
         return StableDiffusionModel.check_tgate_step(g)
+
+    @staticmethod
+    def parse_pag(model_cfg, weight_dtype="bf16"):
+        """``model.pag: {scale, adaptive_scale, applied_layers}`` -> the arguments of ``enable_pag`` (perturbed-attention
+        guidance for any method), or None when the key is absent or null.  Every key is optional (defaults 3.0, 0.0, "mid");
+        unknown keys, bad values and fp8 UNets are refused by name (the layer names are resolved when the model is built)."""
+        p = model_cfg.get("pag", None)
+        if p is None:
+            return None
+        if not hasattr(p, "keys"):
+            raise ValueError(f"model.pag must be a mapping {{scale, adaptive_scale, applied_layers}}, got {p!r}")
+        keys = set(p.keys())
+        if not keys <= {"scale", "adaptive_scale", "applied_layers"}:
+            raise ValueError(f"model.pag takes the keys scale, adaptive_scale and applied_layers (got {sorted(keys)})")
+        from ..models import StableDiffusionModel
+        layers = p.get("applied_layers", "mid")
+        layers = layers if isinstance(layers, str) else list(layers)
+        out = dict(pag_scale=p.get("scale", 3.0), pag_adaptive_scale=p.get("adaptive_scale", 0.0), pag_applied_layers=layers)
+        StableDiffusionModel.check_pag_args(out["pag_scale"], out["pag_adaptive_scale"], layers, None, weight_dtype)
+        if weight_dtype not in (None, "bf16"):
+            from ..unet import HipUNet2DConditionModel
+            from ..weights import UNetConfig
+            HipUNet2DConditionModel.check_pag_handle(UNetConfig(), weight_dtype)
+        return out
 
     @staticmethod
     def parse_hypertile(model_cfg, weight_dtype="bf16"):

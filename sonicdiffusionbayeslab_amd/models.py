@@ -34,7 +34,7 @@ import torch
 
 from . import dist as sdist
 from .registry import models_registry
-from .schedulers import PNDMConfigStub
+from .schedulers import PNDMConfigStub, pag_step_scale
 from .unet import CACHE_FULL_AND_STORE, CACHE_OFF, CACHE_SKIP, LATENT_CHANNELS, HipUNet2DConditionModel
 from .vae import HipVaeDecoder, HipVaeEncoder, VaeConfig, load_vae_state_dict, make_synthetic_vae_state_dict
 from .weights import (SD2_CONTEXT_DIM, SD2_HEADS, UNetConfig, check_projection_layout, load_scheduler_config, load_unet_config,
@@ -198,6 +198,8 @@ class StableDiffusionModel:
         self._freeu = None              # FreeU (enable_freeu): (s1, s2, b1, b2) or None = off
         self._hypertile = None          # HyperTile (enable_hypertile): (tile_tokens, max_depth) or None = off
         self._tgate_step = None         # T-GATE (enable_tgate): the gate step, or None = off
+        self._pag = None                # PAG (enable_pag): dict(scale, adaptive_scale, layers, mask) or None = off
+        self._pag_call = None           # the running call's (pag_scale, pag_adaptive_scale), None = a plain call
         self._tgate_reserved = False    # the UNet's workspaces are sized for the capture plans as well
 
     # -- Token Merging (tomesd.apply_patch) ----------------------------------------------------------
@@ -329,6 +331,89 @@ class StableDiffusionModel:
             self.unet.set_hypertile(*self._hypertile)
         elif getattr(self.unet, "_hypertile", None) is not None:
             self.unet.set_hypertile(0)
+
+    # -- perturbed-attention guidance (diffusers PAGMixin) -----------------------------------
+    PAG_VARIANT_RULE = None         # the variant pipelines set a sentence: they refuse PAG by name
+
+    @staticmethod
+    def check_pag_scales(pag_scale, pag_adaptive_scale):
+        """``pag_scale`` / ``pag_adaptive_scale`` of ``enable_pag`` or of a call: finite numbers, the adaptive scale >= 0
+        (``ValueError`` otherwise).  Returns them as floats."""
+        out = []
+        for name, v in (("pag_scale", pag_scale), ("pag_adaptive_scale", pag_adaptive_scale)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(float(v)):
+                raise ValueError(f"{name}={v!r}: a finite number (pag_scale <= 0 is the plain pipeline)")
+            out.append(float(v))
+        if out[1] < 0.0:
+            raise ValueError(f"pag_adaptive_scale={pag_adaptive_scale!r}: must be >= 0 (the scale falls by it per timestep below 1000)")
+        return out[0], out[1]
+
+    @classmethod
+    def check_pag_args(cls, pag_scale=3.0, pag_adaptive_scale=0.0, pag_applied_layers="mid", unet_config=None,
+                       weight_dtype="bf16"):
+        """Everything ``enable_pag`` can refuse from the model alone, by name, without touching the GPU.  Returns the setting:
+        dict(scale, adaptive_scale, layers, mask) -- ``mask`` is None without a ``unet_config`` to resolve the names against."""
+        scale, adaptive = cls.check_pag_scales(pag_scale, pag_adaptive_scale)
+        if cls.PAG_VARIANT_RULE is not None:
+            raise NotImplementedError(cls.PAG_VARIANT_RULE)
+        layers = [pag_applied_layers] if isinstance(pag_applied_layers, str) else list(pag_applied_layers)
+        mask = None
+        if unet_config is not None:
+            mask = HipUNet2DConditionModel.pag_layer_mask(unet_config, layers)
+            HipUNet2DConditionModel.check_pag_handle(unet_config, weight_dtype)
+        return dict(scale=scale, adaptive_scale=adaptive, layers=layers, mask=mask)
+
+    def enable_pag(self, pag_scale: float = 3.0, pag_adaptive_scale: float = 0.0, pag_applied_layers="mid"):
+        """Perturbed-attention guidance (Ahn et al. 2024; diffusers' ``StableDiffusionPAGPipeline``): every later call runs a
+        third UNet branch -- the conditional one with the self-attention of the transformer blocks ``pag_applied_layers``
+        names (``"mid"``, ``"down.block_i"``, ``"up.block_i"``, ``"...attentions_j"``, or a list) replaced by the identity --
+        and the step adds ``s_t * (cond - perturbed)`` to the guided prediction, ``s_t = pag_scale`` or, with
+        ``pag_adaptive_scale > 0``, ``max(pag_scale - pag_adaptive_scale * (1000 - t), 0)``.  Works with and without CFG (an
+        LCM-distilled UNet runs [cond | perturbed]).  ``pag_scale`` / ``pag_adaptive_scale`` given to a call override these
+        defaults; ``pag_scale <= 0`` is the plain pipeline, bit for bit.  Valid with text-to-image, image-to-image and
+        4-channel inpainting, every scheduler, ``guidance_rescale``, SD 2.x, HyperTile, FreeU, TAESD, every image size and
+        batch sharding; refused by name with Token Merging, T-GATE, DeepCache, IP-Adapter, ControlNet, 9-channel
+        inpainting UNets, fp8 and on the variant pipelines."""
+        self._pag = self.check_pag_args(pag_scale, pag_adaptive_scale, pag_applied_layers, self.unet_config, self.weight_dtype)
+        return self
+
+    def disable_pag(self):
+        """Later calls are those of a model that never saw PAG, bit for bit."""
+        self._pag = None
+        return self
+
+    def _pag_check_call(self, pag_scale, pag_adaptive_scale, control=None, ip_adapter_image=None, ip_adapter_image_embeds=None):
+        """The PAG setting of one call -- ``(pag_scale, pag_adaptive_scale)``, the call's own values over ``enable_pag``'s, or None
+        for a plain call (PAG off, or ``pag_scale <= 0``) -- and what a PAG call refuses, by name, before any GPU work."""
+        if self._pag is None:
+            if pag_scale is not None or pag_adaptive_scale is not None:
+                raise ValueError("pag_scale / pag_adaptive_scale given, but PAG is off: enable_pag(pag_applied_layers=...) first "
+                                 "(the perturbed layers are part of the UNet's plans)")
+            return None
+        scale, adaptive = self.check_pag_scales(self._pag["scale"] if pag_scale is None else pag_scale,
+                                                self._pag["adaptive_scale"] if pag_adaptive_scale is None else pag_adaptive_scale)
+        if scale <= 0.0:
+            return None
+        self.check_pag_args(scale, adaptive, self._pag["layers"], self.unet_config, self.weight_dtype)
+        if self._tome is not None:
+            raise NotImplementedError("PAG with Token Merging is refused: merged tokens have no identity attention (remove_tome() first)")
+        if self._tgate_step is not None:
+            raise NotImplementedError("PAG with T-GATE is refused: behind the gate the UNet runs at the latent batch alone")
+        if self._deepcache is not None:
+            raise NotImplementedError("PAG with DeepCache is refused: the cached features are stored at the CFG batch")
+        if control is not None or getattr(self, "_cn_cfg", None) is not None:
+            raise NotImplementedError("PAG with ControlNet is refused: the residuals are computed for the CFG batch")
+        if ip_adapter_image is not None or ip_adapter_image_embeds is not None or self._ip_loaded:
+            raise NotImplementedError("PAG with an IP-Adapter is refused: the image prompt has no third branch")
+        return scale, adaptive
+
+    def _pag_begin(self):
+        """Start of a sampling loop: the layer mask onto the UNet handle, or off it.  A handle that never had one is not touched
+        while PAG is off."""
+        if self._pag_call is not None:
+            self.unet.set_pag(self._pag["mask"])
+        elif getattr(self.unet, "_pag", 0):
+            self.unet.set_pag(0)
 
     # -- FreeU (diffusers enable_freeu) -----------------------------------------------------------------
     @staticmethod
@@ -1098,6 +1183,8 @@ class StableDiffusionModel:
         prompt_embeds, negative_prompt_embeds = self.encode_prompt(
             prompt, device, do_cfg, negative_prompt, prompt_embeds, negative_prompt_embeds)
         ctx = torch.cat([negative_prompt_embeds, prompt_embeds]) if do_cfg else prompt_embeds   # :154-155
+        if self._pag_call is not None:          # PAG: the perturbed branch, last, sees the positive prompt
+            ctx = torch.cat([ctx, prompt_embeds])
         return device, batch_size, do_cfg, ctx
 
     @property
@@ -1114,6 +1201,7 @@ class StableDiffusionModel:
         self._freeu_begin()             # (likewise)
         self._tgate_begin(batch_size)   # (before the context: the workspace that holds it)
         self.unet.set_deepcache(cache_branch_id)
+        self._pag_begin()               # (before the context: the layer mask is part of the UNet's plans)
         self.unet.set_context(ctx, *self.latent_size)
         self._apply_ip_adapter(ctx.shape[0] == 2 * batch_size and self.do_classifier_free_guidance)
         self._apply_controlnet(ctx, control)
@@ -1167,6 +1255,8 @@ class StableDiffusionModel:
                     kw["guidance_rescale"] = guidance_rescale
                 if inpaint is not None:
                     kw["inpaint"] = (*inpaint, ts[i + 1] if i + 1 < n else None)
+                if self._pag_call is not None:              # (the eps buffer holds the perturbed third behind the CFG pair)
+                    kw["pag_scale"] = pag_step_scale(*self._pag_call, t)
                 step = sched.step_fused(out, guidance_scale, latents, t, cfg=cfg, eta=eta, generator=generator, **kw)   # :238-261
                 latents = step[0]
                 if collect_x0 and len(step) > 1:            # (PNDM returns no x0, :257-261)
@@ -1451,7 +1541,7 @@ class StableDiffusionModel:
              collect_x0: bool = True, image=None, strength=STRENGTH_UNSET, sample_mode: str = "sample", mask_image=None,
              padding_mask_crop=None, ip_adapter_image=None, ip_adapter_image_embeds=None, control_image=None,
              controlnet_conditioning_scale=1.0, control_guidance_start=0.0, control_guidance_end=1.0, guess_mode=False,
-             **kwargs):
+             pag_scale=None, pag_adaptive_scale=None, **kwargs):
         """``control_image`` ([B,3,H,W] floats in [0,1], rgb, or a list of PIL images of one size; resized to the call's size
         as upstream resizes it, replicated over the batch, seen by both CFG halves): the structure condition of a loaded
         ControlNet (``load_controlnet``) for text-to-image and image-to-image.  Step i of N runs the ControlNet at
@@ -1476,6 +1566,7 @@ class StableDiffusionModel:
         # (neither a prompt nor embeds: _begin refuses the call by name)
         n_prompt = None if prompt is None and prompt_embeds is None else _prompt_batch(prompt, prompt_embeds)
         self._tgate_check_call(control_image, ip_adapter_image, ip_adapter_image_embeds)
+        self._pag_call = self._pag_check_call(pag_scale, pag_adaptive_scale, control_image, ip_adapter_image, ip_adapter_image_embeds)
         control = self._control_args(control_image, controlnet_conditioning_scale, control_guidance_start,
                                      control_guidance_end, guess_mode, mask_image, n_prompt)
         a = SimpleNamespace(height=height, width=width, num_inference_steps=num_inference_steps, timesteps=timesteps,
@@ -1539,7 +1630,12 @@ class _VariantBase(StableDiffusionModel):
     TGATE_VARIANT_RULE = ("T-GATE is refused on the variant pipelines (two schedulers, interleaving, skipped steps): their step "
                           "lists are not one schedule to place a gate in; StableDiffusionModel runs it")
 
+    PAG_VARIANT_RULE = ("PAG is refused on the variant pipelines (two schedulers, interleaving, skipped steps): their history "
+                        "hand-off combines a CFG pair, not three branches; StableDiffusionModel runs it")
+
     def _refuse_image(self, kwargs):
+        if self._pag is not None or kwargs.get("pag_scale") is not None or kwargs.get("pag_adaptive_scale") is not None:
+            raise NotImplementedError(self.PAG_VARIANT_RULE)
         if kwargs.get("control_image") is not None or kwargs.get("guess_mode"):
             raise NotImplementedError(f"control_image= (ControlNet) is not built for {type(self).__name__}; "
                                       "StableDiffusionModel runs it")

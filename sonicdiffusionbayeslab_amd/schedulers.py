@@ -101,12 +101,28 @@ def prediction_coefs(prediction_type: str, alpha: float, sigma: float):
     raise NotImplementedError(f"prediction_type {prediction_type!r}: {PREDICTION_TYPES} are built")
 
 
-def cfg_rescale_factors(eps: torch.Tensor, batch: int, guidance: float, rescale: float) -> torch.Tensor:
+GUIDE_CFG_PAG, GUIDE_PAG = 2, 3       # include/sd_hip.h::SD_GUIDE_CFG_PAG / SD_GUIDE_PAG
+
+
+def pag_step_scale(pag_scale: float, pag_adaptive_scale: float, timestep) -> float:
+    """The PAG scale of the step at ``timestep`` (diffusers' ``PAGMixin._get_pag_scale``): ``pag_scale`` when
+    ``pag_adaptive_scale == 0``, else ``max(pag_scale - pag_adaptive_scale * (1000 - t), 0)``."""
+    if pag_adaptive_scale == 0:
+        return float(pag_scale)
+    return max(float(pag_scale) - float(pag_adaptive_scale) * (1000.0 - float(timestep)), 0.0)
+
+
+def cfg_rescale_factors(eps: torch.Tensor, batch: int, guidance: float, rescale: float, pag=None) -> torch.Tensor:
     """``sd_cfg_rescale_factors``: k[b] = rescale * std(c_b) / std(g_b) + (1 - rescale), g = u + guidance*(c - u), for
-    eps = [u | c] (2*batch samples, fp32, contiguous).  diffusers' rescale_noise_cfg is g := k[b] * g."""
+    eps = [u | c] (2*batch samples, fp32, contiguous).  diffusers' rescale_noise_cfg is g := k[b] * g.  ``pag`` (a PAG step
+    scale): eps = [u | c | p] and g carries the PAG term, + pag*(c - p) (``sd_cfg_rescale_factors_pag``)."""
     lib = _lib.load()
-    n = eps.numel() // (2 * batch)
+    n = eps.numel() // ((2 if pag is None else 3) * batch)
     k = torch.empty(batch, dtype=torch.float32, device=eps.device)
+    if pag is not None:
+        _lib.check(lib.sd_cfg_rescale_factors_pag(_lib.current_stream(), eps.data_ptr(), int(batch), int(n), float(guidance),
+                                                  float(pag), float(rescale), k.data_ptr()), "sd_cfg_rescale_factors_pag")
+        return k
     _lib.check(lib.sd_cfg_rescale_factors(_lib.current_stream(), eps.data_ptr(), int(batch), int(n), float(guidance),
                                           float(rescale), k.data_ptr()), "sd_cfg_rescale_factors")
     return k
@@ -160,11 +176,13 @@ class _FusedStepScheduler:
 
     # --- the single fused launch ------------------------------------------------------------
     @staticmethod
-    def _launch(eps, cfg, guidance, x, m1, m2, noise, coef, want_y2=True, want_m=False, m3=None, k=None, blend=None):
+    def _launch(eps, cfg, guidance, x, m1, m2, noise, coef, want_y2=True, want_m=False, m3=None, k=None, blend=None, pag=None):
         """coef = (px, pe, p1, p2, pn, yx, ye, mx, me[, p3]) -- see include/sd_hip.h::sd_sched_step.  ``k`` (per-sample
         rescaled-CFG factors, ``cfg_rescale_factors``): the step scales the combined prediction by them
         (sd_sched_step_rescaled); None launches sd_sched_step.  ``blend`` = (init, blend_noise, mask, a, s), the latent
-        blend of inpainting (``_blend``): the same step as sd_sched_step_inpaint, with or without ``k`` -- still one launch."""
+        blend of inpainting (``_blend``): the same step as sd_sched_step_inpaint, with or without ``k`` -- still one launch.
+        ``pag`` (the step's PAG scale): eps = [u | c | p] under ``cfg``, else [c | p], and the prediction carries the PAG
+        term (sd_sched_step_pag, which takes ``k`` and ``blend`` as they come)."""
         lib = _lib.load()
         n = x.numel()
         prev = torch.empty_like(x)
@@ -173,7 +191,12 @@ class _FusedStepScheduler:
         c10 = [float(v) for v in coef] + [0.0] * (10 - len(coef))
         head = (_lib.current_stream(), eps.data_ptr(), int(cfg), float(guidance), x.data_ptr(), _lib.ptr(m1), _lib.ptr(m2),
                 _lib.ptr(m3), _lib.ptr(noise), prev.data_ptr(), _lib.ptr(y2), _lib.ptr(mo), (C.c_float * 10)(*c10), n)
-        if blend is not None:
+        if pag is not None:
+            init, bnoise, mask, a, s = blend if blend is not None else (None, None, None, 1.0, 0.0)
+            head = (*head[:2], GUIDE_CFG_PAG if cfg else GUIDE_PAG, float(guidance), float(pag), *head[4:])
+            name, tail = "sd_sched_step_pag", (_lib.ptr(k), n // x.shape[0], _lib.ptr(init), _lib.ptr(bnoise), _lib.ptr(mask),
+                                               float(a), float(s), mask.numel() // mask.shape[0] if mask is not None else 0)
+        elif blend is not None:
             init, bnoise, mask, a, s = blend
             name, tail = "sd_sched_step_inpaint", (_lib.ptr(k), n // x.shape[0], init.data_ptr(), bnoise.data_ptr(),
                                                    mask.data_ptr(), float(a), float(s), mask.numel() // mask.shape[0])
@@ -184,13 +207,20 @@ class _FusedStepScheduler:
         _lib.check(getattr(lib, name)(*head, *tail), name)
         return prev, y2, mo
 
-    def _rescale(self, eps, cfg, guidance, guidance_rescale, x):
+    def _rescale(self, eps, cfg, guidance, guidance_rescale, x, pag=None):
         """The rescaled-CFG factors of this step (``src/models.py:244-250``: only with CFG and guidance_rescale > 0),
-        kept in ``rescale_factors`` for the variant pipelines' history hand-off; None otherwise."""
+        kept in ``rescale_factors`` for the variant pipelines' history hand-off; None otherwise.  ``pag``: the step's PAG
+        scale -- the factors then describe the prediction with its PAG term."""
         self.rescale_factors = None
         if cfg and guidance_rescale > 0.0:
-            self.rescale_factors = cfg_rescale_factors(eps, x.shape[0], guidance, guidance_rescale)
+            kw = {} if pag is None else {"pag": pag}        # (a plain step calls it as ever)
+            self.rescale_factors = cfg_rescale_factors(eps, x.shape[0], guidance, guidance_rescale, **kw)
         return self.rescale_factors
+
+    @staticmethod
+    def _pag_kw(pag_scale):
+        """``pag=`` of ``_launch`` for a PAG step; nothing otherwise (as ``_blend_kw``)."""
+        return {} if pag_scale is None else {"pag": float(pag_scale)}
 
     def _check_prediction_type(self):
         if self.config.prediction_type not in PREDICTION_TYPES:
@@ -313,16 +343,16 @@ class DDIMSchedulerMy(_FusedStepScheduler):
         return cx, ce, dx, de
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   guidance_rescale: float = 0.0, inpaint=None):
+                   guidance_rescale: float = 0.0, inpaint=None, pag_scale=None):
         if eta != 0.0:
             raise NotImplementedError("DDIM eta != 0 is never used by the reference (src/models.py:43)")
         if self.num_inference_steps is None:
             raise ValueError("run set_timesteps first")
         cx, ce, dx, de = self.coefficients(timestep)
         e, x = self._prep(model_output), self._prep(sample)
-        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x)
+        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x, pag_scale)
         prev, x0, _ = self._launch(e, cfg, guidance_scale, x, None, None, None, (cx, ce, 0, 0, 0, dx, de, 0, 0), k=k,
-                                   **self._blend_kw(inpaint, x))
+                                   **self._blend_kw(inpaint, x), **self._pag_kw(pag_scale))
         return prev, x0
 
 
@@ -559,7 +589,7 @@ class DPMSolverScheduler(_SigmaTableScheduler):
         return ratio + c0 * mx, c0 * me, c1, c2, pn
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   variance_noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0, inpaint=None):
+                   variance_noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0, inpaint=None, pag_scale=None):
         c = self.config
         i, n = self._begin_step(timestep), len(self._timesteps_list)
         lower_order_final = (i == n - 1) and (c.euler_at_final or (c.lower_order_final and n < 15)
@@ -583,10 +613,10 @@ class DPMSolverScheduler(_SigmaTableScheduler):
                 variance_noise = sdist.randn(x.shape, generator)
             z = self._prep(variance_noise.to(x.device))
         e = self._prep(model_output)
-        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x)
+        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x, pag_scale)
         # (inpainting: the history entry m0 and x0 are taken before the blend, as upstream steps first and blends after)
         prev, x0, m0 = self._launch(e, cfg, guidance_scale, x, m1, m2, z, (px, pe, p1, p2, pn, yx, ye, mx, me),
-                                    want_y2=True, want_m=True, k=k, **self._blend_kw(inpaint, x))
+                                    want_y2=True, want_m=True, k=k, **self._blend_kw(inpaint, x), **self._pag_kw(pag_scale))
         self._end_step(m0)
         return prev, x0
 
@@ -619,7 +649,7 @@ class LCMScheduler(_FusedStepScheduler):
         self._set(origin[idx], device)
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0, inpaint=None):
+                   noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0, inpaint=None, pag_scale=None):
         if self.num_inference_steps is None:
             raise ValueError("run set_timesteps first")
         if self._step_index is None:
@@ -644,8 +674,9 @@ class LCMScheduler(_FusedStepScheduler):
             z = self._prep(noise.to(x.device))
             coef = (math.sqrt(ap) * yx, math.sqrt(ap) * ye, 0, 0, math.sqrt(1.0 - ap), yx, ye, 0, 0)
         e = self._prep(model_output)
-        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x)
-        prev, den, _ = self._launch(e, cfg, guidance_scale, x, None, None, z, coef, k=k, **self._blend_kw(inpaint, x))
+        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x, pag_scale)
+        prev, den, _ = self._launch(e, cfg, guidance_scale, x, None, None, z, coef, k=k, **self._blend_kw(inpaint, x),
+                                    **self._pag_kw(pag_scale))
         self._step_index += 1
         return prev, den
 
@@ -696,7 +727,7 @@ class PNDMScheduler(_FusedStepScheduler):
         return sample_coeff, k
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   guidance_rescale: float = 0.0, inpaint=None):
+                   guidance_rescale: float = 0.0, inpaint=None, pag_scale=None):
         if inpaint is not None:
             raise NotImplementedError("PNDMScheduler: the latent blend of inpainting is not built (its second timestep is "
                                       "duplicated; DDIM, DPM-Solver and LCM are built)")
@@ -707,7 +738,7 @@ class PNDMScheduler(_FusedStepScheduler):
         prev_t = t - ratio
         x = self._prep(sample)
         e = self._prep(model_output)
-        kr = self._rescale(e, cfg, guidance_scale, guidance_rescale, x)
+        kr = self._rescale(e, cfg, guidance_scale, guidance_rescale, x, pag_scale)
         hist = self.ets
         if self.counter != 1:
             n_hist = min(len(hist), 3)
@@ -717,7 +748,7 @@ class PNDMScheduler(_FusedStepScheduler):
             ws = [w[i + 1] if i < n_hist else 0.0 for i in range(3)]
             prev, _, e_out = self._launch(e, cfg, guidance_scale, x, ms[0], ms[1], None,
                                           (sc, k * w[0], k * ws[0], k * ws[1], 0, 0, 0, 0.0, 1.0, k * ws[2]),
-                                          want_y2=False, want_m=True, m3=ms[2], k=kr)
+                                          want_y2=False, want_m=True, m3=ms[2], k=kr, **self._pag_kw(pag_scale))
             self.ets = (hist + [e_out])[-4:]
             if self.counter == 0:
                 self.cur_sample = x
@@ -725,7 +756,7 @@ class PNDMScheduler(_FusedStepScheduler):
             # second call (same timestep again): average with the first prediction, restart from cur_sample
             sc, k = self._prev_coefs(t + ratio, t)
             prev, _, _ = self._launch(e, cfg, guidance_scale, self.cur_sample, hist[-1], None, None,
-                                      (sc, 0.5 * k, 0.5 * k, 0, 0, 0, 0, 0, 0, 0), want_y2=False, want_m=False, k=kr)
+                                      (sc, 0.5 * k, 0.5 * k, 0, 0, 0, 0, 0, 0, 0), want_y2=False, want_m=False, k=kr, **self._pag_kw(pag_scale))
             self.cur_sample = None
         self.counter += 1
         return (prev,)
@@ -879,8 +910,8 @@ class UniPCScheduler(_SigmaTableScheduler):
         return unipc_rows(self.sigmas, i, corrector_order, predictor_order, c.solver_type, c.predict_x0, c.prediction_type)
 
     @staticmethod
-    def _launch_pc(eps, cfg, guidance, x, x_last, hist, rows, k=None, blend=None):
-        """ONE ``sd_sched_step_pc`` launch.  ``hist``: (h1, h2, h3), newest first, None where the row has no weight;
+    def _launch_pc(eps, cfg, guidance, x, x_last, hist, rows, k=None, blend=None, pag=None):
+        """ONE ``sd_sched_step_pc`` launch (``pag``, the step's PAG scale: ``sd_sched_step_pc_pag``, eps = [u | c | p] or [c | p]).  ``hist``: (h1, h2, h3), newest first, None where the row has no weight;
         ``rows`` = (cm, cy, cc, cp) of ``unipc_rows``.  Returns (prev, x_corr, y2, m_t)."""
         lib = _lib.load()
         cm, cy, cc, cp = rows
@@ -892,15 +923,19 @@ class UniPCScheduler(_SigmaTableScheduler):
         if blend is not None:
             init, bnoise, mask, a, s = blend
             hw = mask.numel() // mask.shape[0]
-        _lib.check(lib.sd_sched_step_pc(_lib.current_stream(), eps.data_ptr(), int(cfg), float(guidance), x.data_ptr(),
-                                        _lib.ptr(x_last), _lib.ptr(hist[0]), _lib.ptr(hist[1]), _lib.ptr(hist[2]),
-                                        prev.data_ptr(), xc.data_ptr(), y2.data_ptr(), mo.data_ptr(), carr, n, _lib.ptr(k),
-                                        n // x.shape[0], _lib.ptr(init), _lib.ptr(bnoise), _lib.ptr(mask), float(a), float(s),
-                                        int(hw)), "sd_sched_step_pc")
+        tail = (x.data_ptr(), _lib.ptr(x_last), _lib.ptr(hist[0]), _lib.ptr(hist[1]), _lib.ptr(hist[2]), prev.data_ptr(), xc.data_ptr(),
+                y2.data_ptr(), mo.data_ptr(), carr, n, _lib.ptr(k), n // x.shape[0], _lib.ptr(init), _lib.ptr(bnoise), _lib.ptr(mask),
+                float(a), float(s), int(hw))
+        if pag is not None:
+            _lib.check(lib.sd_sched_step_pc_pag(_lib.current_stream(), eps.data_ptr(), GUIDE_CFG_PAG if cfg else GUIDE_PAG,
+                                                float(guidance), float(pag), *tail), "sd_sched_step_pc_pag")
+        else:
+            _lib.check(lib.sd_sched_step_pc(_lib.current_stream(), eps.data_ptr(), int(cfg), float(guidance), *tail),
+                       "sd_sched_step_pc")
         return prev, xc, y2, mo
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   guidance_rescale: float = 0.0, inpaint=None):
+                   guidance_rescale: float = 0.0, inpaint=None, pag_scale=None):
         """``eta`` and ``generator`` are not read (the solver is deterministic)."""
         i = self._begin_step(timestep)
         order_c, order_p = self.step_orders(i)
@@ -909,10 +944,10 @@ class UniPCScheduler(_SigmaTableScheduler):
         depth = max(order_c, order_p - 1)                       # the corrector reads h1..h_o, the predictor h1..h_(o-1)
         hist = [newest_first[j] if j < min(depth, len(newest_first)) else None for j in range(3)]
         e, x = self._prep(model_output), self._prep(sample)
-        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x)
+        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x, pag_scale)
         # (inpainting: the corrected sample, the history entry and x0 are taken before the blend, as upstream steps first)
         prev, xc, x0, m_t = self._launch_pc(e, cfg, guidance_scale, x, self.last_sample if order_c else None, hist, rows,
-                                            k=k, blend=self._blend(inpaint, x))
+                                            k=k, blend=self._blend(inpaint, x), **self._pag_kw(pag_scale))
         self.last_sample = xc
         self.this_order = order_p
         self._end_step(m_t)

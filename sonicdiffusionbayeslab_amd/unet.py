@@ -86,6 +86,7 @@ class HipUNet2DConditionModel(HipHandle):
         self._tome_choice_keepalive = None
         self._freeu = None                  # (s1, s2, b1, b2) on the handle, None = off
         self._hypertile = None              # (tile_tokens, max_depth) of the HyperTile setting on the handle, None = off
+        self._pag = 0                       # the PAG layer mask on the handle, 0 = off
         # T-GATE: _tgate = (mode, latent batch, h, w) on the handle or None = off; _tgate_cache = the buffer the handle borrows;
         # _tgate_ws = workspace of the gated (reuse) plans, keyed (batch, h, w): the main workspace keeps the prompt context
         self._tgate = None
@@ -284,6 +285,8 @@ class HipUNet2DConditionModel(HipHandle):
             raise NotImplementedError("Token Merging on an fp8 UNet handle is not built")
         if ratio > 0.0 and self._hypertile is not None:
             raise NotImplementedError("Token Merging and HyperTile on together are not built: set_hypertile(0) first")
+        if ratio > 0.0 and self._pag:
+            raise NotImplementedError("Token Merging and PAG on together are not built: set_pag(0) first")
         _lib.check(self._lib.sd_unet_set_tome(self._handle, ratio, int(max_downsample) if ratio > 0.0 else 0), "sd_unet_set_tome")
         new = (ratio, int(max_downsample)) if ratio > 0.0 else None
         if new != self._tome:
@@ -385,6 +388,78 @@ class HipUNet2DConditionModel(HipHandle):
                        "sd_unet_hypertile_block_info_hw")
             out.append(dict(rh=v[0].value, rw=v[1].value, nh=v[2].value, nw=v[3].value))
         return out
+
+    # -- PAG (include/sd_hip.h::sd_unet_set_pag) --------------------------------------------------------
+    @staticmethod
+    def pag_block_names(config) -> list:
+        """The transformer blocks of a UNet in plan order (down, mid, up), as diffusers' ``pag_applied_layers`` spells them:
+        ``down.block_i.attentions_j``, ``mid``, ``up.block_i.attentions_j``.  Bit ``k`` of a PAG layer mask is entry ``k``."""
+        nl = len(config.block_out_channels)
+        out = []
+        for i in range(nl):
+            if config.attn_levels[i]:
+                out += [f"down.block_{i}.attentions_{j}" for j in range(config.layers_per_block)]
+        out.append("mid")
+        for i in range(nl):
+            if config.attn_levels[nl - 1 - i]:
+                out += [f"up.block_{i}.attentions_{j}" for j in range(config.layers_per_block + 1)]
+        return out
+
+    @classmethod
+    def pag_layer_mask(cls, config, applied_layers) -> int:
+        """``pag_applied_layers`` -> the layer mask of ``set_pag``.  A name is ``"mid"``, ``"down.block_i"`` / ``"up.block_i"``
+        (every transformer block of that block) or ``"down.block_i.attentions_j"`` / ``"up.block_i.attentions_j"``; a string or a
+        list of them.  A name that matches no transformer block is a ``ValueError`` that lists the valid names."""
+        blocks = cls.pag_block_names(config)
+        groups = sorted({b.rsplit(".attentions_", 1)[0] for b in blocks if b != "mid"})
+        names = [applied_layers] if isinstance(applied_layers, str) else list(applied_layers)
+        if not names:
+            raise ValueError(f"pag_applied_layers is empty; valid names: {groups + blocks}")
+        mask = 0
+        for name in names:
+            hit = [k for k, b in enumerate(blocks) if isinstance(name, str) and (b == name or b.startswith(name + ".attentions_"))]
+            if not hit:
+                raise ValueError(f"pag_applied_layers: {name!r} matches no transformer block of this UNet; valid names: "
+                                 f"{groups + blocks}")
+            for k in hit:
+                mask |= 1 << k
+        return mask
+
+    @staticmethod
+    def check_pag_handle(config, weight_dtype="bf16"):
+        """What ``set_pag`` refuses about the handle, by name, without touching the GPU."""
+        if _lib.DTYPES.get(weight_dtype) == _lib.DTYPE_FP8_E4M3:
+            raise NotImplementedError("PAG on an fp8 UNet handle is not built (weight_dtype='fp8')")
+        if config.in_channels != LATENT_CHANNELS:
+            raise NotImplementedError(f"PAG on a {config.in_channels}-channel inpainting UNet is not built")
+        if getattr(config, "ip_adapter_embed_dim", None) is not None:
+            raise NotImplementedError("PAG on a UNet with an IP-Adapter is not built")
+
+    def set_pag(self, layer_mask: int) -> None:
+        """Perturbed-attention guidance: bit ``k`` of ``layer_mask`` = transformer block ``k`` in plan order
+        (``pag_block_names``) replaces the self-attention of the LAST third (or half) of the UNet batch by the identity; 0 =
+        off, the handle of before.  Forwards then take a UNet batch of 3 or 2 times the latent batch.  A change needs a new
+        workspace and a new ``set_context``; both follow from dropping the workspace key here.  Refused on fp8, 9-channel and
+        IP-Adapter handles and together with Token Merging, T-GATE, DeepCache and ControlNet residuals."""
+        if isinstance(layer_mask, bool) or not isinstance(layer_mask, int) or layer_mask < 0 or \
+                layer_mask >> len(self.pag_block_names(self.config)):
+            raise ValueError(f"layer_mask={layer_mask!r}: a PAG layer mask has one bit per transformer block "
+                             f"({len(self.pag_block_names(self.config))} here; 0 = off)")
+        if layer_mask:
+            self.check_pag_handle(self.config, self.weight_dtype)
+            if self._tome is not None:
+                raise NotImplementedError("PAG and Token Merging on together are not built: set_tome(0.0) first")
+            if self._tgate is not None:
+                raise NotImplementedError("PAG and T-GATE on together are not built: set_tgate(TGATE_OFF) first")
+            if self.cache_branch_id != -1:
+                raise NotImplementedError("PAG with DeepCache is not built: set_deepcache(-1) first")
+            if self._control is not None or self._ip_on:
+                raise NotImplementedError("PAG with ControlNet residuals or an IP-Adapter image prompt is not built")
+        _lib.check(self._lib.sd_unet_set_pag(self._handle, layer_mask), "sd_unet_set_pag")
+        if layer_mask != self._pag:
+            self._pag = layer_mask
+            self._ws_key = None
+            self._tgate_ws.clear()
 
     # -- FreeU (include/sd_hip.h::sd_unet_set_freeu) -------------------------------------------------
     @staticmethod
@@ -595,7 +670,7 @@ class HipUNet2DConditionModel(HipHandle):
             _lib.check(self._lib.sd_unet_set_fp8_scale(self._handle, k.encode(), float(v)), f"sd_unet_set_fp8_scale({k})")
 
     KIND_NAMES = {0: "sinusoid", 1: "gemv", 2: "conv_in", 3: "groupnorm", 4: "conv3x3", 5: "gemm", 6: "layernorm",
-                  7: "attention", 8: "conv_out", 9: "hypertile_gather", 10: "hypertile_scatter", 16: "conv3x3_fp8", 17: "gemm_fp8", 18: "xattn_fused",
+                  7: "attention", 8: "conv_out", 9: "hypertile_gather", 10: "hypertile_scatter", 11: "pag_identity", 16: "conv3x3_fp8", 17: "gemm_fp8", 18: "xattn_fused",
                   19: "replicate", 20: "conv3x3_gemm", 21: "conv3x3_halo_subpix", 22: "ip_xattn", 23: "residual_add",
                   24: "tgate_capture", 25: "tgate_apply", 26: "tgate_zero",
                   27: "tome_match", 28: "tome_select", 29: "tome_merge", 30: "tome_unmerge", 31: "freeu"}
