@@ -296,6 +296,18 @@ int sd_unet_hypertile_block_info_hw(sd_unet* u, int block, int latent_h, int lat
 int sd_unet_set_pag(sd_unet* u, long long layer_mask);
 int sd_unet_pag_block_count(const sd_unet* u);
 
+/* Self-attention guidance (Hong et al. 2023; diffusers' StableDiffusionSAGPipeline): capture of the attention mass.
+ * on != 0: the mid block's transformer block runs one more launch behind its q | k | v projection, which writes
+ *   mass[b][k] = (1 / heads) * sum_h sum_q softmax_k(Q_h K_h^T / sqrt(d))[q][k]     fp32 [unet_batch][mh * mw], mh x mw the mid grid
+ * of attn1 for every sample of the forward into the buffer sd_unet_set_sag_buffer names (the caller owns it; at least
+ * unet_batch * mh * mw floats, else the forward refuses; it must stay valid until the forward has run).  Nothing else in the plan
+ * changes: the forward's output is the output without capture bit for bit.  Capture is part of the plan key; off = the plans,
+ * workspace sizes and results of a handle that never saw it.  bf16 4-channel UNet handles without an IP-Adapter whose mid grid has
+ * 4 .. 16 tokens per side and head dim 64, 80 or 160; refused by name: PAG, Token Merging, T-GATE, DeepCache, ControlNet
+ * residuals, an IP-Adapter image prompt, fp8, and HyperTile settings that tile the mid block. */
+int sd_unet_set_sag(sd_unet* u, int on);
+int sd_unet_set_sag_buffer(sd_unet* u, float* mass, long long floats);
+
 enum { SD_CACHE_OFF = 0, SD_CACHE_FULL_AND_STORE = 1, SD_CACHE_SKIP = 2 };
 
 /* eps = UNet(latent_model_input, t, encoder_hidden_states)  (src/models.py:217-235).
@@ -641,6 +653,22 @@ int sd_sched_step_pc_pag(void* stream, const float* eps, int mode, float guidanc
 int sd_cfg_rescale_factors_pag(void* stream, const float* eps, int batch, long long n_per_sample, float guidance,
                                float pag_scale, float rescale, float* k_out);
 
+/* ---- self-attention guidance (SAG) ----
+ * SD_GUIDE_CFG_SAG: eps = [u | c | d] (3 n elements), e = (u + guidance*(c - u)) + sag_scale*(u - d); SD_GUIDE_SAG: eps = [c | d]
+ * (2 n elements), e = c + sag_scale*(c - d).  d is the UNet output on the degraded latents (sd_op_sag_degrade).  Per element in
+ * fp32, the CFG part formed exactly as sd_sched_step forms it.  Operands, coefficients and argument checks of the _pag twins;
+ * mode must be one of the two, guidance and sag_scale finite.  sag_scale = 0 in SD_GUIDE_CFG_SAG gives the bits of the plain CFG
+ * step for finite eps. */
+enum { SD_GUIDE_CFG_SAG = 4, SD_GUIDE_SAG = 5 };
+int sd_sched_step_sag(void* stream, const float* eps, int mode, float guidance, float sag_scale, const float* x, const float* m1,
+                      const float* m2, const float* m3, const float* noise, float* prev, float* y2, float* m_out,
+                      const float coef[10], long long n, const float* k, long long n_per_sample, const float* init,
+                      const float* blend_noise, const float* mask, float a, float s, long long hw);
+int sd_sched_step_pc_sag(void* stream, const float* eps, int mode, float guidance, float sag_scale, const float* x,
+                         const float* x_last, const float* h1, const float* h2, const float* h3, float* prev, float* x_corr,
+                         float* y2, float* m_out, const float coef[13], long long n, const float* k, long long n_per_sample,
+                         const float* init, const float* blend_noise, const float* mask, float a, float s, long long hw);
+
 /* One launch: image [batch,3,height,width] fp32 in [0,1] and mask [batch,1,height,width] fp32 ->
  *   masked_image [batch,3,height,width] = mask >= 0.5 ? 0.5 : image   (the encoder's input domain: 2 * 0.5 - 1 is exactly 0,
  *                                                                      upstream's (2 image - 1) * (mask < 0.5))
@@ -789,6 +817,24 @@ int sd_op_hypertile_scatter(void* stream, const void* y, void* out, long long pi
 int sd_pag_identity_check(long long rows_total, long long row0, long long rows, int C, int heads, long long ldv, int tok);
 int sd_op_pag_identity(void* stream, const void* V, long long ldv, int tok, void* out, long long rows_total, long long row0,
                        long long rows, int C, int heads);
+/* SAG's kernels on their own (csrc/sag.hip).
+ * sd_op_sag_attn_mass: mass[b][k] = (1 / heads) * sum_h sum_q softmax_k(Q_h K_h^T)[q][k], fp32 [B][N]; Q and K token-major bf16,
+ * sample b's row t at Q + (b N + t) ld (the q | k | v projection: K = Q + C, ld = 3 C, C = heads * D).  Q carries the softmax
+ * scale already: exp2_units = 0: 1 / sqrt(D), the softmax is the natural one; 1: log2(e) / sqrt(D), as attn1's packed W_q gives
+ * it, and the kernel exponentiates to base 2.  Exact two-pass fp32 softmax, fixed summation order, no atomics: the same bits on
+ * every run.  sd_sag_mass_check: the shape rule (and the plan builder's), no GPU work: B in 1 .. 65535, N in 16 .. 256, D 64, 80
+ * or 160, heads 1 .. 64, ld a multiple of 8 in 2 C .. 2^30, head_major must be 0 (head-major K is refused by name).
+ * sd_op_sag_degrade: x and m fp32 [LB][4][H][W] (latents and the model output on them), mass fp32 [>= LB][mh * mw] ->
+ *   x0 = coef[0] x + coef[1] m (pred_type 2: m),  eps = coef[2] x + coef[3] m (pred_type 0: m),
+ *   blur = 9x9 Gaussian of x0, sigma 1, reflect padding, separable (rows, then columns; each acc = fma(w_i, v_i, acc), i = -4 .. 4),
+ *   deg = mass[b][y / 8][x / 8] > 1 ? blur : x0,   out = coef[4] deg + coef[5] eps.
+ * pred_type 0 epsilon, 1 v_prediction, 2 sample; coef derived in fp64 by the caller from alphas_cumprod[t] (schedulers.py::
+ * sag_degrade_coef).  H, W multiples of 8 in 32 .. 128, mh = H / 8, mw = W / 8; out must not alias x or m. */
+int sd_sag_mass_check(int B, int heads, int N, int D, long long ld, int head_major);
+int sd_op_sag_attn_mass(void* stream, const void* Q, const void* K, long long ld, float* mass, int B, int heads, int N, int D,
+                        int exp2_units);
+int sd_op_sag_degrade(void* stream, const float* x, const float* m, const float* mass, int mh, int mw, int pred_type,
+                      const float coef[6], float* out, int LB, int H, int W);
 /* flash-style attention on token-major [B, N, heads * D] views; D = 40, 64, 80 or 160 (64: Stable Diffusion 2.x), any Nq / Nk */
 int sd_op_attention(void* stream, const void* Q, long long ldq, const void* K, long long ldk, const void* V,
                     long long ldv, void* O, long long ldo, int B, int heads, int Nq, int Nk, int D, float scale);

@@ -259,6 +259,13 @@ _SIGS = {
     "sd_sched_step_pag": (_i, [_vp, _vp, _i, _f, _f] + [_vp] * 8 + [C.POINTER(_f), _ll, _vp, _ll, _vp, _vp, _vp, _f, _f, _ll]),
     "sd_sched_step_pc_pag": (_i, [_vp, _vp, _i, _f, _f] + [_vp] * 9 + [C.POINTER(_f), _ll, _vp, _ll, _vp, _vp, _vp, _f, _f, _ll]),
     "sd_cfg_rescale_factors_pag": (_i, [_vp, _vp, _i, _ll, _f, _f, _f, _vp]),
+    "sd_unet_set_sag": (_i, [_vp, _i]),
+    "sd_unet_set_sag_buffer": (_i, [_vp, _vp, _ll]),
+    "sd_sag_mass_check": (_i, [_i, _i, _i, _i, _ll, _i]),
+    "sd_op_sag_attn_mass": (_i, [_vp, _vp, _vp, _ll, _vp, _i, _i, _i, _i, _i]),
+    "sd_op_sag_degrade": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(_f), _vp, _i, _i, _i]),
+    "sd_sched_step_sag": (_i, [_vp, _vp, _i, _f, _f] + [_vp] * 8 + [C.POINTER(_f), _ll, _vp, _ll, _vp, _vp, _vp, _f, _f, _ll]),
+    "sd_sched_step_pc_sag": (_i, [_vp, _vp, _i, _f, _f] + [_vp] * 9 + [C.POINTER(_f), _ll, _vp, _ll, _vp, _vp, _vp, _f, _f, _ll]),
 }
 
 

@@ -23,7 +23,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libsdhip.so")
 ABLATE_LIB_PATH = os.path.join(LIB_DIR, "libsdhip_ablate.so")
 ABLATE_SOURCES = ("gemm_conv.hip", "conv_halo.hip")     # the translation units with SD_ABLATE code
-SOURCES = ["gemm_conv.hip", "gemm_lean.hip", "conv_halo.hip", "conv64.hip", "norm.hip", "attention.hip", "xattn.hip", "ip_xattn.hip", "small.hip", "sched.hip", "clip.hip", "vit.hip", "bert.hip", "inception.hip", "unet.hip", "pack.hip", "plan.hip", "taesd.hip", "tome.hip", "freeu.hip", "tgate.hip", "hypertile.hip", "pag.hip", "ops.hip"]
+SOURCES = ["gemm_conv.hip", "gemm_lean.hip", "conv_halo.hip", "conv64.hip", "norm.hip", "attention.hip", "xattn.hip", "ip_xattn.hip", "small.hip", "sched.hip", "clip.hip", "vit.hip", "bert.hip", "inception.hip", "unet.hip", "pack.hip", "plan.hip", "taesd.hip", "tome.hip", "freeu.hip", "tgate.hip", "hypertile.hip", "pag.hip", "sag.hip", "ops.hip"]
 HEADERS = ["common.h", "kernels.h", "model.h",os.path.join("..", "..", "include", "sd_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # No packed fp32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) in these units: hipcc broadcasts a scalar
@@ -58,6 +58,8 @@ EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-ffinite-m
                "hypertile.hip": NO_PACKED_FP32,
                # PAG's identity self-attention: an HBM-bound copy, nothing to pack
                "pag.hip": NO_PACKED_FP32,
+               # SAG's attention mass and degrade pass: scalar fp32 softmax / blur arithmetic beside MFMAs
+               "sag.hip": NO_PACKED_FP32,
                # the GEMM epilogues: scalar fp32 stays scalar (common.h::ln_fold: SLP re-packs the LayerNorm fold into
                # v_pk_fma_f32 with op_sel -- the failing form above; packed fp32 is also slower beside MFMAs)
                "gemm_conv.hip": ["-fno-slp-vectorize"], "gemm_lean.hip": ["-fno-slp-vectorize"]}

@@ -261,6 +261,18 @@ int sd_pag_identity_shape_ok(long rows_total, long row0, long rows, int C, int h
 int sd_launch_pag_identity(const bf16_t* V, long ldv, int tok, bf16_t* out, long rows_total, long row0, long rows, int C, int heads,
                            hipStream_t stream);
 
+// sag.hip: self-attention guidance.  sag_attn_mass: mass[b][k] = (1 / heads) sum_h sum_q softmax_k(Q_h K_h^T)[q][k] from token-major
+// Q / K with one row pitch ld (Q already carries the softmax scale; exp2_units: it carries scale * log2 e, as W_q of attn1 does);
+// one workgroup per sample, fixed summation order, no atomics.  sag_degrade: x0 / eps from (x, m), 9x9 Gaussian blur of x0 with
+// reflect padding, blend where mass > 1 on the (H / 8) x (W / 8) grid, re-noise; coef = {x0 <- x, x0 <- m, eps <- x, eps <- m,
+// sqrt(a), sqrt(1 - a)}; pred 0 epsilon / 1 v_prediction / 2 sample.  shape_ok: the shape rules (no GPU work).
+int sd_sag_mass_shape_ok(int B, int heads, int N, int D, long ld, int head_major, const char* who);
+int sd_launch_sag_attn_mass(const bf16_t* Q, const bf16_t* K, long ld, float* mass, int B, int heads, int N, int D, int exp2_units,
+                            hipStream_t stream);
+int sd_sag_degrade_shape_ok(int LB, int H, int W, int mh, int mw, int pred, const char* who);
+int sd_launch_sag_degrade(const float* x, const float* m, const float* mass, int mh, int mw, int pred, const float coef[6], float* out,
+                          int LB, int H, int W, hipStream_t stream);
+
 // xattn.hip: fused prompt cross-attention  Y = R + sum_h softmax_L(X A_h) B_h + b_o  (one launch per block)
 struct XattnArgs {
     const bf16_t* X = nullptr;    // [M, C] LayerNorm output

@@ -50,7 +50,8 @@ enum OpKind { OP_SINUSOID, OP_GEMV, OP_CONV_IN, OP_GN, OP_CONV3, OP_GEMM, OP_LN,
               OP_FREEU,
               OP_TGATE_CAPTURE, OP_TGATE_APPLY, OP_TGATE_ZERO,
               OP_HT_GATHER, OP_HT_SCATTER,
-              OP_PAG_IDENTITY };
+              OP_PAG_IDENTITY,
+              OP_SAG_MASS };
 
 constexpr int TGATE_OFF = 0, TGATE_CAPTURE = 1, TGATE_REUSE = 2;      // sd_unet_set_tgate_hw modes
 
@@ -187,6 +188,9 @@ struct Plan {
     // the perturbed ones (rep = UB / pag_lb is 3 or 2); in the blocks the mask names attn1 runs on the other samples and one
     // OP_PAG_IDENTITY fills the perturbed rows of its output.  pag_blocks: the transformer blocks the builder has seen so far.
     int pag_lb = 0, pag_blocks = 0;
+    // SAG capture variant (part of the plan key, sag.hip): one OP_SAG_MASS behind the q | k | v projection of the mid block's
+    // transformer block writes the attention mass of every sample into the buffer the handle names; nothing else changes
+    int sag = 0;
     // FreeU variant (part of the plan key): one OP_FREEU in front of every resnet of up blocks 0 and 1 (x1 = hidden, x2 = skip ->
     // out = the scaled hidden, aux = the filtered skip, epi = the up block: which pair of the handle's factors the launch reads)
     int freeu = 0;
@@ -265,8 +269,8 @@ struct sd_unet {
     // (UNet batch, DeepCache branch, prefix replication, latent H, W, IP-Adapter variant, control variant, Token Merging: the
     // bits of the ratio and max_downsample, both 0 = off; FreeU on / off; T-GATE mode: TGATE_OFF / CAPTURE / REUSE; T-GATE pair: y rows per
     // cache row of a capture, 2 for a CFG pair, else 1; HyperTile: tile side in tokens and max_depth, both 0 = off; PAG: the layer
-    // mask, 0 = off)
-    std::map<std::tuple<int, int, int, int, int, int, int, long long, int, int, int, int, int, int, long long>, sdhip::Plan> plans;
+    // mask, 0 = off; SAG capture on / off)
+    std::map<std::tuple<int, int, int, int, int, int, int, long long, int, int, int, int, int, int, long long, int>, sdhip::Plan> plans;
     int last_rep = 1, last_ip = 0, last_cn = 0;                       // variant of the last forward (sd_unet_debug_tensor)
     int last_h = 0, last_w = 0;                          // latent size of the last forward (sd_unet_debug_tensor)
     std::unordered_map<std::string, long> tproj_off;  // resnet prefix -> float index into tproj vector
@@ -314,6 +318,11 @@ struct sd_unet {
     // PAG (sd_unet_set_pag; kind 0, bf16): bit i = transformer block i in plan order (down, mid, up) has identity attn1 for the
     // perturbed samples; 0 = off = the plans of a handle that never saw it
     long long pag_mask = 0;
+    // SAG (sd_unet_set_sag; kind 0, bf16): capture of the mid block's attention mass into sag_mass (the caller's buffer of
+    // sag_mass_floats floats, sd_unet_set_sag_buffer); off = the plans of a handle that never saw it
+    bool sag_on = false;
+    float* sag_mass = nullptr;
+    long long sag_mass_floats = 0;
     // FreeU (sd_unet_set_freeu; kind 0, bf16): on = the "freeu" plan variants; the factors are read when OP_FREEU is launched
     bool freeu_on = false;
     float freeu_s[2] = {1.f, 1.f}, freeu_b[2] = {1.f, 1.f};       // (s1, s2), (b1, b2): up block 0, up block 1

@@ -523,6 +523,19 @@ extern "C" int sd_op_pag_identity(void* stream, const void* V, long long ldv, in
                                   (hipStream_t)stream);
 }
 
+// SAG's two kernels (sag.hip) and the mass kernel's shape rule
+extern "C" int sd_sag_mass_check(int B, int heads, int N, int D, long long ld, int head_major) {
+    return sd_sag_mass_shape_ok(B, heads, N, D, (long)ld, head_major, "sd_sag_mass_check");
+}
+extern "C" int sd_op_sag_attn_mass(void* stream, const void* Q, const void* K, long long ld, float* mass, int B, int heads, int N, int D,
+                                   int exp2_units) {
+    return sd_launch_sag_attn_mass((const bf16_t*)Q, (const bf16_t*)K, (long)ld, mass, B, heads, N, D, exp2_units ? 1 : 0, (hipStream_t)stream);
+}
+extern "C" int sd_op_sag_degrade(void* stream, const float* x, const float* m, const float* mass, int mh, int mw, int pred_type,
+                                 const float coef[6], float* out, int LB, int H, int W) {
+    return sd_launch_sag_degrade(x, m, mass, mh, mw, pred_type, coef, out, LB, H, W, (hipStream_t)stream);
+}
+
 // Token Merging, kernel by kernel (tome.hip); index lists in src / dst slot numbers, tok [h * w] from sd_op_tome_match
 extern "C" int sd_op_tome_match(void* stream, const void* x, const unsigned char* choice, int B, int h, int w, int C,
                                 float* node_max, int* node_idx, int* tok) {

@@ -356,10 +356,25 @@ struct Builder {
             return x;
         }
         const int Ba = (pert ? UB - pl.pag_lb : UB) * nt;      // the samples the attention kernel sees
+        const int qkv_op = (int)pl.ops.size() - 1;             // the q | k | v projection (an OP_SAG_MASS may follow it)
+        // SAG capture (sag.hip): the mid block's attention mass of all UB samples, from Q and K as the projection left them
+        // (token-major, pitch 3 C; W_q carries scale * log2 e).  Reads qkv, writes the handle's buffer: no plan tensor changes.
+        if (pl.sag && p == "mid_block.attentions.0.") {
+            if (nt != 1) { if (error.empty()) error = "SAG with a HyperTile setting that tiles the mid block is not built"; return x; }
+            if (tr > 0 || fq || pert) { if (error.empty()) error = "SAG with Token Merging, fp8 or PAG is not built"; return x; }
+            if (rh < 4 || rh > 16 || rw < 4 || rw > 16) {
+                if (error.empty()) error = "SAG: the mid grid is " + std::to_string(rh) + "x" + std::to_string(rw) + " (4 .. 16 tokens per side)";
+                return x;
+            }
+            if (sd_sag_mass_shape_ok(UB, NH, hw, C / NH, 3 * C, hm ? 1 : 0, "SAG")) { if (error.empty()) error = sd_last_error(); return x; }
+            Op o; o.kind = OP_SAG_MASS; o.x1 = qkv; o.B = UB; o.heads = NH; o.D = C / NH; o.Nk = hw; o.Hin = rh; o.Win = rw;
+            o.koff = C; o.ldk = 3 * C;
+            push(o);
+        }
         int a1;
         if (hm) {
-            pl.ops.back().hm = 1;
-            pl.ops.back().HW = Na;
+            pl.ops[qkv_op].hm = 1;
+            pl.ops[qkv_op].HW = Na;
             a1 = attn(qkv, 0, C, qkv, (long)Mm * C, 2l * Mm * C, C, Na, Na, C, NH, Ba);
             pl.ops.back().hm = 1;
         } else {
@@ -1186,8 +1201,11 @@ int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw
     SD_REQUIRE(tg_pair == 1 || UB % 2 == 0, "unet: a T-GATE capture of a CFG pair needs an even batch (%d)", UB);
     auto key = std::make_tuple(UB, branch, rep, lh, lw, ip, cn, tome_bits, tome_bits ? u->tome_max_downsample : 0, freeu, tgate, tg_pair,
                                u->kind == 0 ? u->ht_tokens : 0, u->kind == 0 && u->ht_tokens ? u->ht_max_depth : 0,
-                               u->kind == 0 ? u->pag_mask : 0ll);
+                               u->kind == 0 ? u->pag_mask : 0ll, u->kind == 0 && u->sag_on ? 1 : 0);
     const bool pag = u->kind == 0 && u->pag_mask;
+    const bool sag = u->kind == 0 && u->sag_on;
+    SD_REQUIRE(!sag || (branch < 0 && !ip && !cn && !tgate && !tome_bits && !u->fp8 && !pag),
+               "unet: SAG with DeepCache, an IP-Adapter image prompt, ControlNet residuals, T-GATE, Token Merging, fp8 or PAG is not built");
     SD_REQUIRE(!pag || (branch < 0 && !ip && !cn && !tgate && !tome_bits && !u->fp8),
                "unet: PAG with DeepCache, an IP-Adapter image prompt, ControlNet residuals, T-GATE, Token Merging or fp8 is not built");
     SD_REQUIRE(!pag || rep == 1 || ((rep == 2 || rep == 3) && UB % rep == 0), "unet: a PAG forward runs 2 or 3 copies of the latent batch (%d of batch %d)", rep, UB);
@@ -1206,6 +1224,7 @@ int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw
         pl.freeu = freeu;
         pl.tgate = tgate;
         pl.tg_pair = tg_pair;
+        pl.sag = sag ? 1 : 0;
         pl.pag_lb = pag && rep > 1 ? UB / rep : 0;      // (rep 1: the plan sd_unet_set_context_hw lays the prompt tensors out with)
         Builder b{u, pl, UB, {}};
         b.build();

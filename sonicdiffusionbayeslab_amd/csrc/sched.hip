@@ -1,6 +1,7 @@
 // The end of every sampling step: the fused CFG-combine + scheduler.step update (optional per-sample rescale, optional
 // inpainting blend), the rescaled-CFG factors, UniPC's predictor-corrector step, and their C entry points: five plain ones and
-// the three perturbed-attention-guidance (PAG) forms of the step, the predictor-corrector step and the factors.
+// the three perturbed-attention-guidance (PAG) forms of the step, the predictor-corrector step and the factors, and the two
+// self-attention-guidance (SAG) forms of the step and the predictor-corrector step.
 #include "common.h"
 #include "kernels.h"
 #include "../../include/sd_hip.h"
@@ -15,6 +16,7 @@ __device__ __forceinline__ f32x4 pag_combine(f32x4 g, f32x4 c, f32x4 p, float pa
 // the prediction a step works on: eps, combined as the guidance mode `cfg` says, scaled by its sample's factor when RESCALED.
 //   0: eps as it is     1 (CFG): eps = [u | c], u + g (c - u)
 //   SD_GUIDE_CFG_PAG: eps = [u | c | p], (u + g (c - u)) + s (c - p)     SD_GUIDE_PAG: eps = [c | p], c + s (c - p)
+//   SD_GUIDE_CFG_SAG: eps = [u | c | d], (u + g (c - u)) + s (u - d)     SD_GUIDE_SAG: eps = [c | d], c + s (c - d)
 template <bool RESCALED>
 __device__ __forceinline__ f32x4 step_eps(const float* __restrict__ eps, int cfg, float guidance, float pag,
                                           const float* __restrict__ k, long n4s, long n4, long i) {
@@ -23,7 +25,9 @@ __device__ __forceinline__ f32x4 step_eps(const float* __restrict__ eps, int cfg
     else if (cfg == SD_GUIDE_CFG_PAG) {
         const f32x4 c = ((const f32x4*)eps)[i + n4];
         e = pag_combine(cfg_combine(e, c, guidance), c, ((const f32x4*)eps)[i + 2 * n4], pag);
-    } else if (cfg == SD_GUIDE_PAG) e = pag_combine(e, e, ((const f32x4*)eps)[i + n4], pag);
+    } else if (cfg == SD_GUIDE_CFG_SAG) {
+        e = pag_combine(cfg_combine(e, ((const f32x4*)eps)[i + n4], guidance), e, ((const f32x4*)eps)[i + 2 * n4], pag);
+    } else if (cfg == SD_GUIDE_PAG || cfg == SD_GUIDE_SAG) e = pag_combine(e, e, ((const f32x4*)eps)[i + n4], pag);
     if (RESCALED) e = k[i / n4s] * e;
     return e;
 }
@@ -281,7 +285,7 @@ int sd_launch_sched_step_pc(const char* who, const float* eps, int cfg, float gu
     const char* out_names[4] = {"prev", "x_corr", "y2", "m_out"};
     const void* ins[10] = {eps, x, x_last, h1, h2, h3, k, init, blend_noise, mask};
     const char* in_names[10] = {"eps", "x", "x_last", "h1", "h2", "h3", "k", "init", "blend_noise", "mask"};
-    const size_t in_bytes[10] = {cfg == SD_GUIDE_CFG_PAG ? 3 * nb : cfg ? 2 * nb : nb, nb, nb, nb, nb, nb, batch * 4, nb, nb, init ? batch * (size_t)hw * 4 : 0};
+    const size_t in_bytes[10] = {cfg == SD_GUIDE_CFG_PAG || cfg == SD_GUIDE_CFG_SAG ? 3 * nb : cfg ? 2 * nb : nb, nb, nb, nb, nb, nb, batch * 4, nb, nb, init ? batch * (size_t)hw * 4 : 0};
     for (int o = 0; o < 4; ++o) {
         for (int j = 0; j < 10; ++j)
             SD_REQUIRE(!pc_overlap(outs[o], nb, ins[j], in_bytes[j]), "%s: output %s aliases input %s", who, out_names[o],
@@ -388,4 +392,37 @@ extern "C" int sd_cfg_rescale_factors_pag(void* stream, const float* eps, int ba
                                           float pag_scale, float rescale, float* k_out) {
     if (int rc = check_pag("cfg_rescale_factors_pag", SD_GUIDE_CFG_PAG, guidance, pag_scale)) return rc;
     return sd_launch_cfg_rescale_factors(eps, batch, (long)n_per_sample, guidance, rescale, k_out, (hipStream_t)stream, 1, pag_scale);
+}
+
+// ---- self-attention guidance: the same launchers with a SAG guidance mode (the scale rides in the PAG slot) -----------------
+static int check_sag(const char* who, int mode, float guidance, float sag_scale) {
+    SD_REQUIRE(mode == SD_GUIDE_CFG_SAG || mode == SD_GUIDE_SAG, "%s: mode=%d (SD_GUIDE_CFG_SAG = %d or SD_GUIDE_SAG = %d)", who, mode,
+               SD_GUIDE_CFG_SAG, SD_GUIDE_SAG);
+    SD_REQUIRE(std::isfinite(guidance), "%s: guidance=%g must be finite", who, (double)guidance);
+    SD_REQUIRE(std::isfinite(sag_scale), "%s: sag_scale=%g must be finite", who, (double)sag_scale);
+    return 0;
+}
+
+extern "C" int sd_sched_step_sag(void* stream, const float* eps, int mode, float guidance, float sag_scale, const float* x,
+                                 const float* m1, const float* m2, const float* m3, const float* noise, float* prev, float* y2,
+                                 float* m_out, const float coef[10], long long n, const float* k, long long n_per_sample,
+                                 const float* init, const float* blend_noise, const float* mask, float a, float s, long long hw) {
+    SD_REQUIRE(coef, "sched_step_sag: null coefficients");
+    if (int rc = check_sag("sched_step_sag", mode, guidance, sag_scale)) return rc;
+    return sd_launch_sched_step("sched_step_sag", eps, mode, guidance, sag_scale, x, m1, m2, m3, noise, prev, y2, m_out,
+                                step_coef(coef), k, (long)n_per_sample, (long)n, init, blend_noise, mask, a, s, (long)hw,
+                                (hipStream_t)stream);
+}
+
+extern "C" int sd_sched_step_pc_sag(void* stream, const float* eps, int mode, float guidance, float sag_scale, const float* x,
+                                    const float* x_last, const float* h1, const float* h2, const float* h3, float* prev,
+                                    float* x_corr, float* y2, float* m_out, const float coef[13], long long n, const float* k,
+                                    long long n_per_sample, const float* init, const float* blend_noise, const float* mask,
+                                    float a, float s, long long hw) {
+    SD_REQUIRE(coef, "sched_step_pc_sag: null coefficients");
+    if (int rc = check_sag("sched_step_pc_sag", mode, guidance, sag_scale)) return rc;
+    PcCoef c{{coef[0], coef[1]}, {coef[2], coef[3]}, {coef[4], coef[5], coef[6], coef[7], coef[8]},
+             {coef[9], coef[10], coef[11], coef[12]}};
+    return sd_launch_sched_step_pc("sched_step_pc_sag", eps, mode, guidance, sag_scale, x, x_last, h1, h2, h3, prev, x_corr, y2, m_out, c,
+                                   k, (long)n_per_sample, (long)n, init, blend_noise, mask, a, s, (long)hw, (hipStream_t)stream);
 }

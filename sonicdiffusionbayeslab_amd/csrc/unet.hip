@@ -209,6 +209,11 @@ int run_op(sd_unet* u, const Plan& pl, const Op& o, char* ws, const float* laten
             return sd_launch_hypertile_scatter((const bf16_t*)T(o.x1), (bf16_t*)T(o.out), o.N, o.B, o.Hin, o.Win, o.N, o.K, o.K1, stream);
         case OP_PAG_IDENTITY:    // (qoff / koff: the first perturbed row and their count; HW: tokens of a head-major sample, 0 = token-major)
             return sd_launch_pag_identity((const bf16_t*)T(o.x1) + o.voff, o.ldv, o.HW, (bf16_t*)T(o.out), o.M, o.qoff, o.koff, o.N, o.heads, stream);
+        case OP_SAG_MASS:        // (koff / ldk: K's offset in a projection row and the row pitch; the mass goes to the handle's buffer)
+            SD_REQUIRE(u->sag_mass && (long long)o.B * o.Nk <= u->sag_mass_floats, "forward: SAG capture is on and the mass buffer holds %lld "
+                       "floats, batch %d at a %dx%d mid grid takes %lld (sd_unet_set_sag_buffer)", u->sag_mass ? u->sag_mass_floats : 0ll, o.B,
+                       o.Hin, o.Win, (long long)o.B * o.Nk);
+            return sd_launch_sag_attn_mass((const bf16_t*)T(o.x1), (const bf16_t*)T(o.x1) + o.koff, o.ldk, u->sag_mass, o.B, o.heads, o.Nk, o.D, 1, stream);
         case OP_TOME_MATCH:
             SD_REQUIRE(u->tome_choice && o.b2idx + (long)(o.Hin / 2) * (o.Win / 2) <= u->tome_choice_n, "forward: no Token Merging choice array");
             return sd_launch_tome_match((const bf16_t*)T(o.x1), u->tome_choice + o.b2idx, o.B, o.Hin, o.Win, o.N, (float*)T(o.out),
@@ -1159,6 +1164,17 @@ static int check_pag_forward(const sd_unet* u, const char* who, int latent_batch
     return 0;
 }
 
+// a forward with SAG capture on runs alone: no cache, no image prompt, no residuals, none of the other attention plug-ins
+static int check_sag_forward(const sd_unet* u, const char* who, int cache_mode, int branch, int ip, int cn) {
+    SD_REQUIRE(cache_mode == SD_CACHE_OFF && branch < 0, "%s: SAG with DeepCache is not built", who);
+    SD_REQUIRE(!ip && !cn, "%s: SAG with an IP-Adapter image prompt or ControlNet residuals is not built", who);
+    SD_REQUIRE(!u->tg_mode, "%s: SAG with T-GATE is not built", who);
+    SD_REQUIRE(!(u->tome_ratio > 0.0), "%s: SAG with Token Merging is not built", who);
+    SD_REQUIRE(!u->pag_mask, "%s: SAG with PAG is not built", who);
+    SD_REQUIRE(u->sag_mass, "%s: SAG capture is on and no mass buffer is set (sd_unet_set_sag_buffer)", who);
+    return 0;
+}
+
 // the handle's dst-choice array for the plan about to run: n bytes, zero (position 0 of every cell) unless set for this size
 static int ensure_tome_choice(sd_unet* u, long n, void* stream) {
     if (n <= 0 || (u->tome_choice && u->tome_choice_n == n)) return 0;
@@ -1199,6 +1215,7 @@ extern "C" int sd_unet_forward_hw(sd_unet* u, void* stream, const float* latents
     if (cn && check_control_set(u, "forward", unet_batch, latent_h, latent_w, cache_mode, cache_branch_id)) return -1;
     if (u->tg_mode && check_tgate_forward(u, "forward", latent_batch, unet_batch, latent_h, latent_w, cache_mode, cache_branch_id, ip, cn)) return -1;
     if (u->pag_mask && check_pag_forward(u, "forward", latent_batch, unet_batch, cache_mode, cache_branch_id, ip, cn)) return -1;
+    if (u->sag_on && check_sag_forward(u, "forward", cache_mode, cache_branch_id, ip, cn)) return -1;
     u->last_rep = rep; u->last_ip = ip; u->last_cn = cn;
     u->last_h = latent_h; u->last_w = latent_w;
     int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, latent_h, latent_w, ip, cn);
@@ -1312,7 +1329,33 @@ extern "C" int sd_unet_set_pag(sd_unet* u, long long layer_mask) {
     SD_REQUIRE(u->cfg.ip_adapter_tokens == 0, "set_pag: PAG is refused on a UNet with an IP-Adapter");
     SD_REQUIRE(!(u->tome_ratio > 0.0), "set_pag: Token Merging is on (PAG and Token Merging together are not built)");
     SD_REQUIRE(!u->tg_mode, "set_pag: T-GATE is on (PAG and T-GATE together are not built)");
+    SD_REQUIRE(!u->sag_on, "set_pag: SAG capture is on (PAG and SAG together are not built)");
     u->pag_mask = layer_mask;
+    return 0;
+}
+
+// ---- SAG (sag.hip; the plan side is Builder::transformer_block) ------------------------------------------------------------
+extern "C" int sd_unet_set_sag(sd_unet* u, int on) {
+    SD_REQUIRE(u && u->kind == 0, "set_sag: not a UNet handle");
+    if (!on) {                      // off: the plans of a handle that never saw SAG
+        u->sag_on = false;
+        return 0;
+    }
+    SD_REQUIRE(!u->fp8, "set_sag: SAG is not built for fp8 handles");
+    SD_REQUIRE(u->cfg.in_channels == 4, "set_sag: SAG is refused on a 9-channel inpainting UNet");
+    SD_REQUIRE(u->cfg.ip_adapter_tokens == 0, "set_sag: SAG is refused on a UNet with an IP-Adapter");
+    SD_REQUIRE(!u->pag_mask, "set_sag: PAG is on (SAG and PAG together are not built)");
+    SD_REQUIRE(!(u->tome_ratio > 0.0), "set_sag: Token Merging is on (SAG and Token Merging together are not built)");
+    SD_REQUIRE(!u->tg_mode, "set_sag: T-GATE is on (SAG and T-GATE together are not built)");
+    u->sag_on = true;
+    return 0;
+}
+
+extern "C" int sd_unet_set_sag_buffer(sd_unet* u, float* mass, long long floats) {
+    SD_REQUIRE(u && u->kind == 0, "set_sag_buffer: not a UNet handle");
+    SD_REQUIRE((mass && floats > 0) || (!mass && floats == 0), "set_sag_buffer: a buffer with its size in floats, or null and 0");
+    u->sag_mass = mass;
+    u->sag_mass_floats = floats;
     return 0;
 }
 
@@ -1580,6 +1623,10 @@ static void op_work(const Op& o, double* flops, double* bytes) {
             *flops = 2.0 * 14.0 * o.B * (double)o.Hin * o.Win * o.C2;
             *bytes = 2.0 * o.B * (double)o.Hin * o.Win * (2.0 * o.C1 + 3.0 * o.C2);
             break;
+        case OP_SAG_MASS:       // Q K^T of every head, Q and K in, the masses out
+            *flops = 2.0 * o.B * o.heads * (double)o.Nk * o.Nk * o.D;
+            *bytes = 2.0 * 2.0 * o.B * (double)o.Nk * o.heads * o.D + 4.0 * o.B * o.Nk;
+            break;
         case OP_PAG_IDENTITY:   // the perturbed rows in and out
             *bytes = 2.0 * 2.0 * (double)o.koff * o.N;
             break;
@@ -1622,6 +1669,7 @@ static int profiled_run(sd_unet* u, void* stream, const float* latents, int late
     if (u->tg_mode && check_tgate_forward(u, "forward_profiled", latent_batch, unet_batch, u->cfg.sample_size, u->cfg.sample_size, cache_mode,
                                           cache_branch_id, ip, cn)) return -1;
     if (u->pag_mask && check_pag_forward(u, "forward_profiled", latent_batch, unet_batch, cache_mode, cache_branch_id, ip, cn)) return -1;
+    if (u->sag_on && check_sag_forward(u, "forward_profiled", cache_mode, cache_branch_id, ip, cn)) return -1;
     u->last_rep = rep; u->last_ip = ip; u->last_cn = cn;
     u->last_h = u->last_w = u->cfg.sample_size;
     int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, -1, -1, ip, cn);
@@ -1688,7 +1736,8 @@ extern "C" int sd_unet_forward_profiled(sd_unet* u, void* stream, const float* l
         // (24 / 25 / 26: T-GATE's capture, apply and the capture plan's zero fill -- the op kinds of those numbers never run on a UNet)
         // (9 / 10: HyperTile's gather and scatter, likewise)
         // (11: PAG's identity self-attention, likewise)
-        const int kd = o.kind == OP_PAG_IDENTITY ? 11 : o.kind == OP_HT_GATHER ? 9 : o.kind == OP_HT_SCATTER ? 10 : o.kind == OP_TGATE_CAPTURE ? 24 : o.kind == OP_TGATE_APPLY ? 25 : o.kind == OP_TGATE_ZERO ? 26 : o.kind == OP_XATTN ? 18 : o.kind == OP_REPLICATE ? 19 : o.kind == OP_IP_XATTN ? 22 : o.kind == OP_RES_ADD ? 23 : halo4 ? 21 :
+        // (12: SAG's attention mass, likewise)
+        const int kd = o.kind == OP_SAG_MASS ? 12 : o.kind == OP_PAG_IDENTITY ? 11 : o.kind == OP_HT_GATHER ? 9 : o.kind == OP_HT_SCATTER ? 10 : o.kind == OP_TGATE_CAPTURE ? 24 : o.kind == OP_TGATE_APPLY ? 25 : o.kind == OP_TGATE_ZERO ? 26 : o.kind == OP_XATTN ? 18 : o.kind == OP_REPLICATE ? 19 : o.kind == OP_IP_XATTN ? 22 : o.kind == OP_RES_ADD ? 23 : halo4 ? 21 :
                        (o.kind == OP_CONV3 && !o.dt && (o.subpix || o.stride != 1)) ? 20 :
                        (o.dt ? (o.kind == OP_CONV3 ? 16 : 17) : o.kind);
         kind_ms[kd] += ms; kind_launches[kd] += 1; kind_flops[kd] += fl; kind_bytes[kd] += by;

@@ -93,6 +93,9 @@ class BaseMethod(ABC):
         pag = self.parse_pag(self.config.model, self.config.model.get("weight_dtype", None) or "bf16")    # key of this build: model.pag
         if pag is not None:
             self.model.enable_pag(**pag)
+        sag = self.parse_sag(self.config.model, self.config.model.get("weight_dtype", None) or "bf16")    # key of this build: model.sag
+        if sag is not None:
+            self.model.enable_sag(**sag)
         gate = self.parse_tgate(self.config.model)     # key of this build: model.tgate_step
         if gate is not None:
             self.model.enable_tgate(gate)
@@ -107,6 +110,24 @@ class BaseMethod(ABC):
             return None
         from ..models import StableDiffusionModel
         return StableDiffusionModel.check_tgate_step(g)
+
+    @staticmethod
+    def parse_sag(model_cfg, weight_dtype="bf16"):
+        """``model.sag: {scale}`` -> the arguments of ``enable_sag`` (self-attention guidance for any method), or None when the
+        key is absent or null.  ``scale`` is optional (default 0.75); unknown keys, bad values and fp8 UNets are refused by
+        name."""
+        p = model_cfg.get("sag", None)
+        if p is None:
+            return None
+        if not hasattr(p, "keys"):
+            raise ValueError(f"model.sag must be a mapping {{scale}}, got {p!r}")
+        keys = set(p.keys())
+        if not keys <= {"scale"}:
+            raise ValueError(f"model.sag takes the key scale (got {sorted(keys)})")
+        from ..models import StableDiffusionModel
+        out = dict(sag_scale=p.get("scale", 0.75))
+        StableDiffusionModel.check_sag_args(out["sag_scale"], None, weight_dtype)
+        return out
 
     @staticmethod
     def parse_pag(model_cfg, weight_dtype="bf16"):

@@ -34,7 +34,7 @@ import torch
 
 from . import dist as sdist
 from .registry import models_registry
-from .schedulers import PNDMConfigStub, pag_step_scale
+from .schedulers import PNDMConfigStub, pag_step_scale, sag_degrade
 from .unet import CACHE_FULL_AND_STORE, CACHE_OFF, CACHE_SKIP, LATENT_CHANNELS, HipUNet2DConditionModel
 from .vae import HipVaeDecoder, HipVaeEncoder, VaeConfig, load_vae_state_dict, make_synthetic_vae_state_dict
 from .weights import (SD2_CONTEXT_DIM, SD2_HEADS, UNetConfig, check_projection_layout, load_scheduler_config, load_unet_config,
@@ -200,6 +200,10 @@ class StableDiffusionModel:
         self._tgate_step = None         # T-GATE (enable_tgate): the gate step, or None = off
         self._pag = None                # PAG (enable_pag): dict(scale, adaptive_scale, layers, mask) or None = off
         self._pag_call = None           # the running call's (pag_scale, pag_adaptive_scale), None = a plain call
+        self._sag = None                # SAG (enable_sag): the default sag_scale, or None = off
+        self._sag_call = None           # the running call's sag_scale, None = a plain call
+        self._sag_keep = False          # keep the per-step attention masses of a call in sag_masses ([LB, mh, mw] fp32 each)
+        self.sag_masses = []
         self._tgate_reserved = False    # the UNet's workspaces are sized for the capture plans as well
 
     # -- Token Merging (tomesd.apply_patch) ----------------------------------------------------------
@@ -414,6 +418,94 @@ class StableDiffusionModel:
             self.unet.set_pag(self._pag["mask"])
         elif getattr(self.unet, "_pag", 0):
             self.unet.set_pag(0)
+
+    # -- self-attention guidance (diffusers StableDiffusionSAGPipeline) -------------------------
+    SAG_VARIANT_RULE = None         # the variant pipelines set a sentence: they refuse SAG by name
+
+    @staticmethod
+    def check_sag_scale(sag_scale):
+        """``sag_scale`` of ``enable_sag`` or of a call: a finite number (``ValueError`` otherwise).  Returns it as a float."""
+        if isinstance(sag_scale, bool) or not isinstance(sag_scale, (int, float)) or not math.isfinite(float(sag_scale)):
+            raise ValueError(f"sag_scale={sag_scale!r}: a finite number (upstream's range is [0, 1]; sag_scale <= 0 is the plain pipeline)")
+        return float(sag_scale)
+
+    @classmethod
+    def check_sag_args(cls, sag_scale=0.75, unet_config=None, weight_dtype="bf16"):
+        """Everything ``enable_sag`` can refuse from the model alone, by name, without touching the GPU.  Returns the scale."""
+        scale = cls.check_sag_scale(sag_scale)
+        if cls.SAG_VARIANT_RULE is not None:
+            raise NotImplementedError(cls.SAG_VARIANT_RULE)
+        if unet_config is not None:
+            HipUNet2DConditionModel.check_sag_handle(unet_config, weight_dtype)
+        elif _lib_dtype_is_fp8(weight_dtype):
+            raise NotImplementedError("SAG on an fp8 UNet handle is not built (weight_dtype='fp8')")
+        return scale
+
+    def enable_sag(self, sag_scale: float = 0.75):
+        """Self-attention guidance (Hong et al. 2023; diffusers' ``StableDiffusionSAGPipeline``): every later step blurs the
+        regions of the predicted x0 that the mid block's self-attention attends to (attention mass above its mean), re-noises
+        them, runs the UNet once more on these degraded latents at the latent batch, and adds ``sag_scale * (m - d)`` to the
+        guided prediction -- ``m`` the unconditional output under CFG, the conditional one without, ``d`` the output on the
+        degraded latents.  Needs no negative prompt, so it also guides LCM-distilled UNets.  ``sag_scale`` given to a call
+        overrides the default; ``sag_scale <= 0`` is the plain pipeline, bit for bit.  Valid with text-to-image,
+        image-to-image, the 4-channel inpainting blend, all three prediction types, every scheduler, SD 2.x, FreeU, TAESD,
+        HyperTile below the mid block, image sizes of 256 .. 1024 pixels per side in multiples of 64 and batch sharding;
+        refused by name with PAG, ``guidance_rescale > 0``, Token Merging, T-GATE, DeepCache, IP-Adapter, ControlNet,
+        HyperTile settings that tile the mid block, 9-channel inpainting UNets, fp8 and on the variant pipelines."""
+        self._sag = self.check_sag_args(sag_scale, self.unet_config, self.weight_dtype)
+        return self
+
+    def disable_sag(self):
+        """Later calls are those of a model that never saw SAG, bit for bit."""
+        self._sag = None
+        return self
+
+    def _sag_check_call(self, sag_scale, guidance_rescale=0.0, control=None, ip_adapter_image=None, ip_adapter_image_embeds=None):
+        """The SAG scale of one call -- the call's own value over ``enable_sag``'s, or None for a plain call (SAG off, or
+        ``sag_scale <= 0``) -- and what a SAG call refuses, by name, before any GPU work."""
+        if self._sag is None:
+            if sag_scale is not None:
+                raise ValueError("sag_scale given, but SAG is off: enable_sag() first")
+            return None
+        scale = self.check_sag_scale(self._sag if sag_scale is None else sag_scale)
+        if scale <= 0.0:
+            return None
+        self.check_sag_args(scale, self.unet_config, self.weight_dtype)
+        if self._pag_call is not None:
+            raise NotImplementedError("SAG with PAG is refused: one extra guidance branch per step is built (disable_pag() first)")
+        if guidance_rescale is not None and guidance_rescale > 0.0:
+            raise NotImplementedError("SAG with guidance_rescale > 0 is refused: upstream's SAG pipeline has no rescale")
+        if self._tome is not None:
+            raise NotImplementedError("SAG with Token Merging is refused: merged tokens have no attention mass (remove_tome() first)")
+        if self._tgate_step is not None:
+            raise NotImplementedError("SAG with T-GATE is refused: behind the gate the step has no pair to degrade from")
+        if self._deepcache is not None:
+            raise NotImplementedError("SAG with DeepCache is refused: a skip step does not run the mid block")
+        if control is not None or getattr(self, "_cn_cfg", None) is not None:
+            raise NotImplementedError("SAG with ControlNet is refused: the residuals are computed for the first forward alone")
+        if ip_adapter_image is not None or ip_adapter_image_embeds is not None or self._ip_loaded:
+            raise NotImplementedError("SAG with an IP-Adapter is refused: the image prompt has no branch on the degraded latents")
+        if self._hypertile is not None and self._hypertile[1] >= len(self.unet_config.block_out_channels) - 1:
+            raise NotImplementedError(f"SAG with HyperTile max_depth={self._hypertile[1]} is refused: it tiles the mid block, whose "
+                                      "whole-grid attention mass SAG reads")
+        return scale
+
+    def _sag_begin(self, batch_size, ctx):
+        """Start of a sampling loop, before the context: capture onto the UNet handle with a mass buffer for the call's UNet
+        batch, or off it.  A handle that never had it is not touched while SAG is off."""
+        if self._sag_call is None:
+            if getattr(self.unet, "_sag", False) or getattr(self.unet, "_sag_mass", None) is not None:
+                self.unet.clear_sag()
+            return
+        mh, mw = self.unet.sag_mid_grid(self.unet_config, *self.latent_size)
+        mass = torch.zeros((ctx.shape[0], mh * mw), dtype=torch.float32, device=self.unet.device)
+        self.unet.set_sag(True, mass)
+
+    def _sag_context(self, batch_size, ctx):
+        """After the context of the first forward: the context of the SAG forward, the first ``batch_size`` prompt rows (the
+        unconditional ones under CFG, else the conditional ones), in its own workspace -- once per call."""
+        if self._sag_call is not None:
+            self.unet.set_sag_context(ctx[:batch_size], *self.latent_size)
 
     # -- FreeU (diffusers enable_freeu) -----------------------------------------------------------------
     @staticmethod
@@ -1202,7 +1294,9 @@ class StableDiffusionModel:
         self._tgate_begin(batch_size)   # (before the context: the workspace that holds it)
         self.unet.set_deepcache(cache_branch_id)
         self._pag_begin()               # (before the context: the layer mask is part of the UNet's plans)
+        self._sag_begin(batch_size, ctx)    # (likewise: capture is part of the UNet's plans)
         self.unet.set_context(ctx, *self.latent_size)
+        self._sag_context(batch_size, ctx)
         self._apply_ip_adapter(ctx.shape[0] == 2 * batch_size and self.do_classifier_free_guidance)
         self._apply_controlnet(ctx, control)
         return latents
@@ -1222,7 +1316,14 @@ class StableDiffusionModel:
         timestep that runs.  Returns (latents, x0 predictions of the first sample, seconds): the wall-clock of the loop only
         (``:208,284-285``), bracketed by device synchronisation."""
         device = self.unet.device
-        eps = self._eps_buffer(unet_batch, device)
+        sag = self._sag_call
+        # SAG: the eps buffer holds the prediction on the degraded latents behind the first forward's rows
+        eps = self._eps_buffer(unet_batch + (latents.shape[0] if sag is not None else 0), device)
+        eps1 = eps[:unet_batch] if sag is not None else eps
+        if sag is not None:
+            mh, mw = self.unet.sag_mid_grid(self.unet_config, *self.latent_size)
+            x_deg = torch.empty_like(latents, dtype=torch.float32)
+            self.sag_masses = []
         ts = [s[0] for s in steps]
         n = len(steps)
         # T-GATE: steps 0 .. g - 1 as ever (step g - 1 also captures), steps g .. n - 1 gated: the UNet at the latent batch,
@@ -1234,7 +1335,7 @@ class StableDiffusionModel:
         start_time = time.time()                                                                   # :208
         try:
             for i, (t, sched, hand_off) in enumerate(steps):                                       # :211
-                ub, cfg, out = unet_batch, do_cfg, eps
+                ub, cfg, out = unet_batch, do_cfg, eps1
                 if g is not None:
                     if i == g - 1:
                         self.unet.set_tgate(self.unet.TGATE_CAPTURE, lb, *self.latent_size)
@@ -1247,8 +1348,22 @@ class StableDiffusionModel:
                     mode = CACHE_FULL_AND_STORE if ts.index(t) % deepcache.cache_interval == 0 else CACHE_SKIP     # (A.5)
                 self._control_step(i, n, latents, ub, t)
                 self._tome_step()
+                if sag is not None:
+                    self.unet.set_sag(True)
                 self.unet.forward_latents(latents, ub, float(t), out=out, cache_mode=mode)         # :217-235
                 kw = {}
+                if sag is not None:
+                    # the first LB rows of the forward (uncond under CFG, else cond) and their masses -> degraded latents ->
+                    # the UNet at the latent batch with those rows' prompt, capture off, into the last LB rows of eps
+                    x32 = latents if latents.dtype == torch.float32 and latents.is_contiguous() else latents.float().contiguous()
+                    sag_degrade(x32, eps[:lb], self.unet._sag_mass, mh, mw, sched.config.prediction_type,
+                                float(sched.alphas_cumprod[int(t)]), out=x_deg)
+                    if self._sag_keep:
+                        self.sag_masses.append(self.unet._sag_mass[:lb].view(lb, mh, mw).clone())
+                    self.unet.set_sag(False)
+                    self.unet.forward_latents(x_deg, lb, float(t), out=eps[unet_batch:], sag_forward=True)
+                    out = eps
+                    kw["sag_scale"] = sag
                 if step_noise is not None and i < n - 1 and "timestep_scaling" in getattr(sched, "config", ()):    # (LCM)
                     kw["noise"] = step_noise[i]             # indexed by EXECUTED step
                 if cfg and guidance_rescale > 0.0:                                                 # :244-250
@@ -1266,6 +1381,8 @@ class StableDiffusionModel:
         finally:
             if g is not None:
                 self.unet.set_tgate(self.unet.TGATE_OFF)
+            if sag is not None:
+                self.unet.set_sag(False)
         self._control_end()
         torch.cuda.synchronize(device)
         return latents, x0_preds, time.time() - start_time                                        # :284-285
@@ -1541,7 +1658,7 @@ class StableDiffusionModel:
              collect_x0: bool = True, image=None, strength=STRENGTH_UNSET, sample_mode: str = "sample", mask_image=None,
              padding_mask_crop=None, ip_adapter_image=None, ip_adapter_image_embeds=None, control_image=None,
              controlnet_conditioning_scale=1.0, control_guidance_start=0.0, control_guidance_end=1.0, guess_mode=False,
-             pag_scale=None, pag_adaptive_scale=None, **kwargs):
+             pag_scale=None, pag_adaptive_scale=None, sag_scale=None, **kwargs):
         """``control_image`` ([B,3,H,W] floats in [0,1], rgb, or a list of PIL images of one size; resized to the call's size
         as upstream resizes it, replicated over the batch, seen by both CFG halves): the structure condition of a loaded
         ControlNet (``load_controlnet``) for text-to-image and image-to-image.  Step i of N runs the ControlNet at
@@ -1567,6 +1684,7 @@ class StableDiffusionModel:
         n_prompt = None if prompt is None and prompt_embeds is None else _prompt_batch(prompt, prompt_embeds)
         self._tgate_check_call(control_image, ip_adapter_image, ip_adapter_image_embeds)
         self._pag_call = self._pag_check_call(pag_scale, pag_adaptive_scale, control_image, ip_adapter_image, ip_adapter_image_embeds)
+        self._sag_call = self._sag_check_call(sag_scale, guidance_rescale, control_image, ip_adapter_image, ip_adapter_image_embeds)
         control = self._control_args(control_image, controlnet_conditioning_scale, control_guidance_start,
                                      control_guidance_end, guess_mode, mask_image, n_prompt)
         a = SimpleNamespace(height=height, width=width, num_inference_steps=num_inference_steps, timesteps=timesteps,
@@ -1633,7 +1751,12 @@ class _VariantBase(StableDiffusionModel):
     PAG_VARIANT_RULE = ("PAG is refused on the variant pipelines (two schedulers, interleaving, skipped steps): their history "
                         "hand-off combines a CFG pair, not three branches; StableDiffusionModel runs it")
 
+    SAG_VARIANT_RULE = ("SAG is refused on the variant pipelines (two schedulers, interleaving, skipped steps): their history "
+                        "hand-off combines a CFG pair, not the SAG prediction; StableDiffusionModel runs it")
+
     def _refuse_image(self, kwargs):
+        if self._sag is not None or kwargs.get("sag_scale") is not None:
+            raise NotImplementedError(self.SAG_VARIANT_RULE)
         if self._pag is not None or kwargs.get("pag_scale") is not None or kwargs.get("pag_adaptive_scale") is not None:
             raise NotImplementedError(self.PAG_VARIANT_RULE)
         if kwargs.get("control_image") is not None or kwargs.get("guess_mode"):

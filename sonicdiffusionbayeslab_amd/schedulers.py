@@ -102,6 +102,36 @@ def prediction_coefs(prediction_type: str, alpha: float, sigma: float):
 
 
 GUIDE_CFG_PAG, GUIDE_PAG = 2, 3       # include/sd_hip.h::SD_GUIDE_CFG_PAG / SD_GUIDE_PAG
+GUIDE_CFG_SAG, GUIDE_SAG = 4, 5       # include/sd_hip.h::SD_GUIDE_CFG_SAG / SD_GUIDE_SAG
+PRED_TYPE_IDS = {"epsilon": 0, "v_prediction": 1, "sample": 2}        # the pred_type of sd_op_sag_degrade
+
+
+def sag_degrade_coef(prediction_type: str, alpha_prod_t: float):
+    """The six fp32 coefficients of ``sd_op_sag_degrade`` for a step at ``alphas_cumprod[t] = alpha_prod_t``, derived in
+    fp64: (x0 <- x, x0 <- m, eps <- x, eps <- m, sqrt(a), sqrt(1 - a)) with m the model output."""
+    a = float(alpha_prod_t)
+    sa, s1 = math.sqrt(a), math.sqrt(1.0 - a)
+    if prediction_type == "epsilon":
+        return (1.0 / sa, -s1 / sa, 0.0, 1.0, sa, s1)
+    if prediction_type == "v_prediction":
+        return (sa, -s1, s1, sa, sa, s1)
+    if prediction_type == "sample":
+        return (0.0, 1.0, 1.0 / s1, -sa / s1, sa, s1)
+    raise NotImplementedError(f"prediction_type {prediction_type!r}: {PREDICTION_TYPES} are built")
+
+
+def sag_degrade(x: torch.Tensor, m: torch.Tensor, mass: torch.Tensor, mh: int, mw: int, prediction_type: str, alpha_prod_t: float,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``sd_op_sag_degrade``: the degraded, re-noised latents of a SAG step from the latents ``x`` [LB,4,H,W], the model output
+    ``m`` on them and the attention masses ``mass`` [>= LB, mh * mw] (all fp32, contiguous, on one device)."""
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty_like(x)
+    coef = (C.c_float * 6)(*sag_degrade_coef(prediction_type, alpha_prod_t))
+    _lib.check(lib.sd_op_sag_degrade(_lib.current_stream(), x.data_ptr(), m.data_ptr(), mass.data_ptr(), int(mh), int(mw),
+                                     PRED_TYPE_IDS[prediction_type], coef, out.data_ptr(), x.shape[0], x.shape[2], x.shape[3]),
+               "sd_op_sag_degrade")
+    return out
 
 
 def pag_step_scale(pag_scale: float, pag_adaptive_scale: float, timestep) -> float:
@@ -176,13 +206,14 @@ class _FusedStepScheduler:
 
     # --- the single fused launch ------------------------------------------------------------
     @staticmethod
-    def _launch(eps, cfg, guidance, x, m1, m2, noise, coef, want_y2=True, want_m=False, m3=None, k=None, blend=None, pag=None):
+    def _launch(eps, cfg, guidance, x, m1, m2, noise, coef, want_y2=True, want_m=False, m3=None, k=None, blend=None, pag=None, sag=None):
         """coef = (px, pe, p1, p2, pn, yx, ye, mx, me[, p3]) -- see include/sd_hip.h::sd_sched_step.  ``k`` (per-sample
         rescaled-CFG factors, ``cfg_rescale_factors``): the step scales the combined prediction by them
         (sd_sched_step_rescaled); None launches sd_sched_step.  ``blend`` = (init, blend_noise, mask, a, s), the latent
         blend of inpainting (``_blend``): the same step as sd_sched_step_inpaint, with or without ``k`` -- still one launch.
         ``pag`` (the step's PAG scale): eps = [u | c | p] under ``cfg``, else [c | p], and the prediction carries the PAG
-        term (sd_sched_step_pag, which takes ``k`` and ``blend`` as they come)."""
+        term (sd_sched_step_pag, which takes ``k`` and ``blend`` as they come).  ``sag`` (the SAG scale): eps = [u | c | d]
+        under ``cfg``, else [c | d], d the prediction on the degraded latents (sd_sched_step_sag, same operands)."""
         lib = _lib.load()
         n = x.numel()
         prev = torch.empty_like(x)
@@ -191,10 +222,13 @@ class _FusedStepScheduler:
         c10 = [float(v) for v in coef] + [0.0] * (10 - len(coef))
         head = (_lib.current_stream(), eps.data_ptr(), int(cfg), float(guidance), x.data_ptr(), _lib.ptr(m1), _lib.ptr(m2),
                 _lib.ptr(m3), _lib.ptr(noise), prev.data_ptr(), _lib.ptr(y2), _lib.ptr(mo), (C.c_float * 10)(*c10), n)
-        if pag is not None:
+        if pag is not None or sag is not None:
             init, bnoise, mask, a, s = blend if blend is not None else (None, None, None, 1.0, 0.0)
-            head = (*head[:2], GUIDE_CFG_PAG if cfg else GUIDE_PAG, float(guidance), float(pag), *head[4:])
-            name, tail = "sd_sched_step_pag", (_lib.ptr(k), n // x.shape[0], _lib.ptr(init), _lib.ptr(bnoise), _lib.ptr(mask),
+            if sag is not None:
+                head = (*head[:2], GUIDE_CFG_SAG if cfg else GUIDE_SAG, float(guidance), float(sag), *head[4:])
+            else:
+                head = (*head[:2], GUIDE_CFG_PAG if cfg else GUIDE_PAG, float(guidance), float(pag), *head[4:])
+            name, tail = "sd_sched_step_sag" if sag is not None else "sd_sched_step_pag", (_lib.ptr(k), n // x.shape[0], _lib.ptr(init), _lib.ptr(bnoise), _lib.ptr(mask),
                                                float(a), float(s), mask.numel() // mask.shape[0] if mask is not None else 0)
         elif blend is not None:
             init, bnoise, mask, a, s = blend
@@ -207,19 +241,28 @@ class _FusedStepScheduler:
         _lib.check(getattr(lib, name)(*head, *tail), name)
         return prev, y2, mo
 
-    def _rescale(self, eps, cfg, guidance, guidance_rescale, x, pag=None):
+    def _rescale(self, eps, cfg, guidance, guidance_rescale, x, pag=None, sag=None):
         """The rescaled-CFG factors of this step (``src/models.py:244-250``: only with CFG and guidance_rescale > 0),
         kept in ``rescale_factors`` for the variant pipelines' history hand-off; None otherwise.  ``pag``: the step's PAG
         scale -- the factors then describe the prediction with its PAG term."""
         self.rescale_factors = None
+        self._pag_kw(pag, sag, guidance_rescale)        # (a SAG step refuses guidance_rescale before anything is launched)
         if cfg and guidance_rescale > 0.0:
             kw = {} if pag is None else {"pag": pag}        # (a plain step calls it as ever)
             self.rescale_factors = cfg_rescale_factors(eps, x.shape[0], guidance, guidance_rescale, **kw)
         return self.rescale_factors
 
     @staticmethod
-    def _pag_kw(pag_scale):
-        """``pag=`` of ``_launch`` for a PAG step; nothing otherwise (as ``_blend_kw``)."""
+    def _pag_kw(pag_scale, sag_scale=None, guidance_rescale=0.0):
+        """The extra guidance branch of a step: ``pag=`` of ``_launch`` for a PAG step, ``sag=`` for a SAG step; nothing otherwise
+        (as ``_blend_kw``).  A SAG step has no ``guidance_rescale`` (upstream's SAG pipeline has none, and the factors would be
+        taken over a buffer with a third block) and no PAG term: refused by name before the step's launch."""
+        if sag_scale is not None:
+            if pag_scale is not None:
+                raise NotImplementedError("a step with PAG and SAG together is not built")
+            if guidance_rescale is not None and guidance_rescale > 0.0:
+                raise NotImplementedError("a SAG step with guidance_rescale > 0 is not built (upstream's SAG pipeline has no rescale)")
+            return {"sag": float(sag_scale)}
         return {} if pag_scale is None else {"pag": float(pag_scale)}
 
     def _check_prediction_type(self):
@@ -343,16 +386,16 @@ class DDIMSchedulerMy(_FusedStepScheduler):
         return cx, ce, dx, de
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   guidance_rescale: float = 0.0, inpaint=None, pag_scale=None):
+                   guidance_rescale: float = 0.0, inpaint=None, pag_scale=None, sag_scale=None):
         if eta != 0.0:
             raise NotImplementedError("DDIM eta != 0 is never used by the reference (src/models.py:43)")
         if self.num_inference_steps is None:
             raise ValueError("run set_timesteps first")
         cx, ce, dx, de = self.coefficients(timestep)
         e, x = self._prep(model_output), self._prep(sample)
-        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x, pag_scale)
+        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x, pag_scale, sag_scale)
         prev, x0, _ = self._launch(e, cfg, guidance_scale, x, None, None, None, (cx, ce, 0, 0, 0, dx, de, 0, 0), k=k,
-                                   **self._blend_kw(inpaint, x), **self._pag_kw(pag_scale))
+                                   **self._blend_kw(inpaint, x), **self._pag_kw(pag_scale, sag_scale, guidance_rescale))
         return prev, x0
 
 
@@ -589,7 +632,7 @@ class DPMSolverScheduler(_SigmaTableScheduler):
         return ratio + c0 * mx, c0 * me, c1, c2, pn
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   variance_noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0, inpaint=None, pag_scale=None):
+                   variance_noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0, inpaint=None, pag_scale=None, sag_scale=None):
         c = self.config
         i, n = self._begin_step(timestep), len(self._timesteps_list)
         lower_order_final = (i == n - 1) and (c.euler_at_final or (c.lower_order_final and n < 15)
@@ -613,10 +656,10 @@ class DPMSolverScheduler(_SigmaTableScheduler):
                 variance_noise = sdist.randn(x.shape, generator)
             z = self._prep(variance_noise.to(x.device))
         e = self._prep(model_output)
-        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x, pag_scale)
+        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x, pag_scale, sag_scale)
         # (inpainting: the history entry m0 and x0 are taken before the blend, as upstream steps first and blends after)
         prev, x0, m0 = self._launch(e, cfg, guidance_scale, x, m1, m2, z, (px, pe, p1, p2, pn, yx, ye, mx, me),
-                                    want_y2=True, want_m=True, k=k, **self._blend_kw(inpaint, x), **self._pag_kw(pag_scale))
+                                    want_y2=True, want_m=True, k=k, **self._blend_kw(inpaint, x), **self._pag_kw(pag_scale, sag_scale, guidance_rescale))
         self._end_step(m0)
         return prev, x0
 
@@ -649,7 +692,7 @@ class LCMScheduler(_FusedStepScheduler):
         self._set(origin[idx], device)
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0, inpaint=None, pag_scale=None):
+                   noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0, inpaint=None, pag_scale=None, sag_scale=None):
         if self.num_inference_steps is None:
             raise ValueError("run set_timesteps first")
         if self._step_index is None:
@@ -674,9 +717,9 @@ class LCMScheduler(_FusedStepScheduler):
             z = self._prep(noise.to(x.device))
             coef = (math.sqrt(ap) * yx, math.sqrt(ap) * ye, 0, 0, math.sqrt(1.0 - ap), yx, ye, 0, 0)
         e = self._prep(model_output)
-        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x, pag_scale)
+        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x, pag_scale, sag_scale)
         prev, den, _ = self._launch(e, cfg, guidance_scale, x, None, None, z, coef, k=k, **self._blend_kw(inpaint, x),
-                                    **self._pag_kw(pag_scale))
+                                    **self._pag_kw(pag_scale, sag_scale, guidance_rescale))
         self._step_index += 1
         return prev, den
 
@@ -727,7 +770,7 @@ class PNDMScheduler(_FusedStepScheduler):
         return sample_coeff, k
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   guidance_rescale: float = 0.0, inpaint=None, pag_scale=None):
+                   guidance_rescale: float = 0.0, inpaint=None, pag_scale=None, sag_scale=None):
         if inpaint is not None:
             raise NotImplementedError("PNDMScheduler: the latent blend of inpainting is not built (its second timestep is "
                                       "duplicated; DDIM, DPM-Solver and LCM are built)")
@@ -738,7 +781,7 @@ class PNDMScheduler(_FusedStepScheduler):
         prev_t = t - ratio
         x = self._prep(sample)
         e = self._prep(model_output)
-        kr = self._rescale(e, cfg, guidance_scale, guidance_rescale, x, pag_scale)
+        kr = self._rescale(e, cfg, guidance_scale, guidance_rescale, x, pag_scale, sag_scale)
         hist = self.ets
         if self.counter != 1:
             n_hist = min(len(hist), 3)
@@ -748,7 +791,7 @@ class PNDMScheduler(_FusedStepScheduler):
             ws = [w[i + 1] if i < n_hist else 0.0 for i in range(3)]
             prev, _, e_out = self._launch(e, cfg, guidance_scale, x, ms[0], ms[1], None,
                                           (sc, k * w[0], k * ws[0], k * ws[1], 0, 0, 0, 0.0, 1.0, k * ws[2]),
-                                          want_y2=False, want_m=True, m3=ms[2], k=kr, **self._pag_kw(pag_scale))
+                                          want_y2=False, want_m=True, m3=ms[2], k=kr, **self._pag_kw(pag_scale, sag_scale, guidance_rescale))
             self.ets = (hist + [e_out])[-4:]
             if self.counter == 0:
                 self.cur_sample = x
@@ -756,7 +799,7 @@ class PNDMScheduler(_FusedStepScheduler):
             # second call (same timestep again): average with the first prediction, restart from cur_sample
             sc, k = self._prev_coefs(t + ratio, t)
             prev, _, _ = self._launch(e, cfg, guidance_scale, self.cur_sample, hist[-1], None, None,
-                                      (sc, 0.5 * k, 0.5 * k, 0, 0, 0, 0, 0, 0, 0), want_y2=False, want_m=False, k=kr, **self._pag_kw(pag_scale))
+                                      (sc, 0.5 * k, 0.5 * k, 0, 0, 0, 0, 0, 0, 0), want_y2=False, want_m=False, k=kr, **self._pag_kw(pag_scale, sag_scale, guidance_rescale))
             self.cur_sample = None
         self.counter += 1
         return (prev,)
@@ -910,7 +953,7 @@ class UniPCScheduler(_SigmaTableScheduler):
         return unipc_rows(self.sigmas, i, corrector_order, predictor_order, c.solver_type, c.predict_x0, c.prediction_type)
 
     @staticmethod
-    def _launch_pc(eps, cfg, guidance, x, x_last, hist, rows, k=None, blend=None, pag=None):
+    def _launch_pc(eps, cfg, guidance, x, x_last, hist, rows, k=None, blend=None, pag=None, sag=None):
         """ONE ``sd_sched_step_pc`` launch (``pag``, the step's PAG scale: ``sd_sched_step_pc_pag``, eps = [u | c | p] or [c | p]).  ``hist``: (h1, h2, h3), newest first, None where the row has no weight;
         ``rows`` = (cm, cy, cc, cp) of ``unipc_rows``.  Returns (prev, x_corr, y2, m_t)."""
         lib = _lib.load()
@@ -926,7 +969,10 @@ class UniPCScheduler(_SigmaTableScheduler):
         tail = (x.data_ptr(), _lib.ptr(x_last), _lib.ptr(hist[0]), _lib.ptr(hist[1]), _lib.ptr(hist[2]), prev.data_ptr(), xc.data_ptr(),
                 y2.data_ptr(), mo.data_ptr(), carr, n, _lib.ptr(k), n // x.shape[0], _lib.ptr(init), _lib.ptr(bnoise), _lib.ptr(mask),
                 float(a), float(s), int(hw))
-        if pag is not None:
+        if sag is not None:
+            _lib.check(lib.sd_sched_step_pc_sag(_lib.current_stream(), eps.data_ptr(), GUIDE_CFG_SAG if cfg else GUIDE_SAG,
+                                                float(guidance), float(sag), *tail), "sd_sched_step_pc_sag")
+        elif pag is not None:
             _lib.check(lib.sd_sched_step_pc_pag(_lib.current_stream(), eps.data_ptr(), GUIDE_CFG_PAG if cfg else GUIDE_PAG,
                                                 float(guidance), float(pag), *tail), "sd_sched_step_pc_pag")
         else:
@@ -935,7 +981,7 @@ class UniPCScheduler(_SigmaTableScheduler):
         return prev, xc, y2, mo
 
     def step_fused(self, model_output, guidance_scale, sample, timestep, cfg=True, eta=0.0, generator=None,
-                   guidance_rescale: float = 0.0, inpaint=None, pag_scale=None):
+                   guidance_rescale: float = 0.0, inpaint=None, pag_scale=None, sag_scale=None):
         """``eta`` and ``generator`` are not read (the solver is deterministic)."""
         i = self._begin_step(timestep)
         order_c, order_p = self.step_orders(i)
@@ -944,10 +990,10 @@ class UniPCScheduler(_SigmaTableScheduler):
         depth = max(order_c, order_p - 1)                       # the corrector reads h1..h_o, the predictor h1..h_(o-1)
         hist = [newest_first[j] if j < min(depth, len(newest_first)) else None for j in range(3)]
         e, x = self._prep(model_output), self._prep(sample)
-        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x, pag_scale)
+        k = self._rescale(e, cfg, guidance_scale, guidance_rescale, x, pag_scale, sag_scale)
         # (inpainting: the corrected sample, the history entry and x0 are taken before the blend, as upstream steps first)
         prev, xc, x0, m_t = self._launch_pc(e, cfg, guidance_scale, x, self.last_sample if order_c else None, hist, rows,
-                                            k=k, blend=self._blend(inpaint, x), **self._pag_kw(pag_scale))
+                                            k=k, blend=self._blend(inpaint, x), **self._pag_kw(pag_scale, sag_scale, guidance_rescale))
         self.last_sample = xc
         self.this_order = order_p
         self._end_step(m_t)

@@ -87,6 +87,13 @@ class HipUNet2DConditionModel(HipHandle):
         self._freeu = None                  # (s1, s2, b1, b2) on the handle, None = off
         self._hypertile = None              # (tile_tokens, max_depth) of the HyperTile setting on the handle, None = off
         self._pag = 0                       # the PAG layer mask on the handle, 0 = off
+        # SAG: _sag = capture of the mid block's attention mass is on; _sag_mass = the fp32 buffer the handle writes it to;
+        # _sag_ws = the workspace of the SAG forward (the degraded latents at the latent batch, capture off) with its own prompt
+        # context, keyed (batch, h, w): the main workspace keeps the context of the first forward
+        self._sag = False
+        self._sag_mass = None
+        self._sag_ws = Workspace(self.device)
+        self._sag_ctx_key = None
         # T-GATE: _tgate = (mode, latent batch, h, w) on the handle or None = off; _tgate_cache = the buffer the handle borrows;
         # _tgate_ws = workspace of the gated (reuse) plans, keyed (batch, h, w): the main workspace keeps the prompt context
         self._tgate = None
@@ -96,6 +103,20 @@ class HipUNet2DConditionModel(HipHandle):
         self.cache_branch_id = -1
 
     # -- workspace / context ---------------------------------------------------------------
+    # Every setting that changes the plans drops the main workspace's key (``self._ws_key = None``).  The workspace of the SAG
+    # forward was sized and laid out for the plans of the old setting as well, so it goes with it: the next ``set_sag_context``
+    # sizes a new one and folds its context again.
+    @property
+    def _ws_key(self):
+        return self._wsp.key
+
+    @_ws_key.setter
+    def _ws_key(self, key) -> None:
+        self._wsp.key = key
+        if key is None and getattr(self, "_sag_ws", None) is not None:
+            self._sag_ws.key = None
+            self._sag_ctx_key = None
+
     def latent_size(self, height: Optional[int] = None, width: Optional[int] = None):
         """(h, w) of the latent: ``sample_size`` where not given."""
         s = self.config.sample_size
@@ -287,6 +308,8 @@ class HipUNet2DConditionModel(HipHandle):
             raise NotImplementedError("Token Merging and HyperTile on together are not built: set_hypertile(0) first")
         if ratio > 0.0 and self._pag:
             raise NotImplementedError("Token Merging and PAG on together are not built: set_pag(0) first")
+        if ratio > 0.0 and self._sag:
+            raise NotImplementedError("Token Merging and SAG on together are not built: set_sag(False) first")
         _lib.check(self._lib.sd_unet_set_tome(self._handle, ratio, int(max_downsample) if ratio > 0.0 else 0), "sd_unet_set_tome")
         new = (ratio, int(max_downsample)) if ratio > 0.0 else None
         if new != self._tome:
@@ -455,11 +478,94 @@ class HipUNet2DConditionModel(HipHandle):
                 raise NotImplementedError("PAG with DeepCache is not built: set_deepcache(-1) first")
             if self._control is not None or self._ip_on:
                 raise NotImplementedError("PAG with ControlNet residuals or an IP-Adapter image prompt is not built")
+            if self._sag:
+                raise NotImplementedError("PAG and SAG on together are not built: set_sag(False) first")
         _lib.check(self._lib.sd_unet_set_pag(self._handle, layer_mask), "sd_unet_set_pag")
         if layer_mask != self._pag:
             self._pag = layer_mask
             self._ws_key = None
             self._tgate_ws.clear()
+
+    # -- SAG (include/sd_hip.h::sd_unet_set_sag) --------------------------------------------------------
+    @staticmethod
+    def check_sag_handle(config, weight_dtype="bf16"):
+        """What ``set_sag`` refuses about the handle, by name, without touching the GPU."""
+        if _lib.DTYPES.get(weight_dtype) == _lib.DTYPE_FP8_E4M3:
+            raise NotImplementedError("SAG on an fp8 UNet handle is not built (weight_dtype='fp8')")
+        if config.in_channels != LATENT_CHANNELS:
+            raise NotImplementedError(f"SAG on a {config.in_channels}-channel inpainting UNet is not built")
+        if getattr(config, "ip_adapter_embed_dim", None) is not None:
+            raise NotImplementedError("SAG on a UNet with an IP-Adapter is not built")
+
+    @staticmethod
+    def sag_mid_grid(config, h: int, w: int):
+        """(mh, mw) of the mid block's token grid under an ``h`` x ``w`` latent; SAG serves 4 .. 16 per side with the factor
+        exactly 8 (``ValueError`` otherwise, by name)."""
+        f = 2 ** (len(config.block_out_channels) - 1)
+        mh, mw = h // f, w // f
+        if f != 8 or h % 8 or w % 8 or not (4 <= mh <= 16 and 4 <= mw <= 16):
+            raise ValueError(f"SAG: a {h}x{w} latent with {len(config.block_out_channels)} UNet levels gives a {mh}x{mw} mid grid at "
+                             f"factor {f}; built for factor 8 and 4 .. 16 tokens per side (latents of 32 .. 128, multiples of 8)")
+        return mh, mw
+
+    def set_sag(self, on: bool, mass: Optional[torch.Tensor] = None) -> None:
+        """Self-attention guidance: with ``on`` every forward also writes the attention mass of the mid block's self-attention,
+        fp32 [unet_batch, mh * mw], into ``mass`` (a contiguous fp32 device tensor the caller keeps; the last one set is kept when
+        None).  The forward's output does not change.  Off: the handle of before.  The prompt context sits at the same place in
+        both kinds of plan, so toggling per forward keeps the workspace and its context.  Refused on fp8, 9-channel and IP-Adapter
+        handles and together with PAG, Token Merging, T-GATE, DeepCache, ControlNet residuals and an image prompt."""
+        if on:
+            self.check_sag_handle(self.config, self.weight_dtype)
+            if self._pag:
+                raise NotImplementedError("SAG and PAG on together are not built: set_pag(0) first")
+            if self._tome is not None:
+                raise NotImplementedError("SAG and Token Merging on together are not built: set_tome(0.0) first")
+            if self._tgate is not None:
+                raise NotImplementedError("SAG and T-GATE on together are not built: set_tgate(TGATE_OFF) first")
+            if self.cache_branch_id != -1:
+                raise NotImplementedError("SAG with DeepCache is not built: set_deepcache(-1) first")
+            if self._control is not None or self._ip_on:
+                raise NotImplementedError("SAG with ControlNet residuals or an IP-Adapter image prompt is not built")
+            if mass is not None:
+                if mass.dtype != torch.float32 or not mass.is_contiguous() or mass.device != self.device:
+                    raise ValueError("set_sag: mass must be a contiguous fp32 tensor on the UNet's device")
+                _lib.check(self._lib.sd_unet_set_sag_buffer(self._handle, mass.data_ptr(), mass.numel()), "sd_unet_set_sag_buffer")
+                self._sag_mass = mass
+            elif self._sag_mass is None:
+                raise ValueError("set_sag(True) needs a mass buffer the first time")
+        _lib.check(self._lib.sd_unet_set_sag(self._handle, 1 if on else 0), "sd_unet_set_sag")
+        self._sag = bool(on)
+
+    def clear_sag(self) -> None:
+        """Capture off, the mass buffer and the second workspace released."""
+        self.set_sag(False)
+        _lib.check(self._lib.sd_unet_set_sag_buffer(self._handle, None, 0), "sd_unet_set_sag_buffer")
+        self._sag_mass = None
+        self._sag_ws.clear()
+        self._sag_ctx_key = None
+
+    def set_sag_context(self, encoder_hidden_states: torch.Tensor, height: Optional[int] = None, width: Optional[int] = None) -> None:
+        """The prompt context of the SAG forward (``forward_latents(..., sag_forward=True)``), once per call: its own workspace,
+        so the two forwards of a step alternate without refolding either context."""
+        h, w = self.latent_size(height, width)
+        ehs = encoder_hidden_states.to(self.device, torch.float32).contiguous()
+        ub = ehs.shape[0]
+        if ehs.shape[1] != self.config.context_len or ehs.shape[2] != self.config.cross_attention_dim:
+            raise ValueError(f"encoder_hidden_states must be [N,{self.config.context_len},{self.config.cross_attention_dim}], "
+                             f"got {tuple(ehs.shape)}")
+        was = self._sag
+        if was:
+            self.set_sag(False)             # (the SAG forward runs the plain plan)
+        try:
+            key = (ub, h, w)
+            if not self._sag_ws.holds(key):
+                self._sag_ws.reserve(self._workspace_bytes(ub, -1, h, w), key)
+            _lib.check(self._lib.sd_unet_set_context_hw(self._handle, _lib.current_stream(), ehs.data_ptr(), ub, -1, h, w,
+                                                        self._sag_ws.ptr, self._sag_ws.nbytes), "sd_unet_set_context_hw")
+        finally:
+            if was:
+                self.set_sag(True)
+        self._sag_ctx_key = (ub, h, w)
 
     # -- FreeU (include/sd_hip.h::sd_unet_set_freeu) -------------------------------------------------
     @staticmethod
@@ -596,10 +702,11 @@ class HipUNet2DConditionModel(HipHandle):
 
     # -- forward ---------------------------------------------------------------------------
     def forward_latents(self, latents: torch.Tensor, unet_batch: int, timestep: float,
-                        out: Optional[torch.Tensor] = None, cache_mode: int = CACHE_OFF) -> torch.Tensor:
+                        out: Optional[torch.Tensor] = None, cache_mode: int = CACHE_OFF, sag_forward: bool = False) -> torch.Tensor:
         """eps [unet_batch,4,H,W] fp32 for fp32 NCHW ``latents`` [B,4,H,W]; ``unet_batch`` is B or
         a multiple of it (CFG: 2B, the duplication is fused).  H and W are taken from ``latents``: each a
-        multiple of 2^(levels - 1).  ``set_context`` must have run for this batch and size."""
+        multiple of 2^(levels - 1).  ``set_context`` must have run for this batch and size.  ``sag_forward``: the second
+        forward of a SAG step -- the workspace and context of ``set_sag_context``, capture off."""
         if latents.dim() != 4 or latents.shape[1] != LATENT_CHANNELS:
             raise ValueError(f"latents must be [B,{LATENT_CHANNELS},H,W], got {tuple(latents.shape)}")
         b, c, h, w = latents.shape
@@ -608,7 +715,12 @@ class HipUNet2DConditionModel(HipHandle):
             raise _lib.SdHipError(f"this UNet has in_channels = 9: set_inpaint_cond(mask, masked_latents) must be called for "
                                   f"this batch and size ({h}x{w}) first")
         gated = self._tgate is not None and self._tgate[0] == self.TGATE_REUSE      # (no prompt context behind the gate)
-        if not gated and (self._ctx_key is None or self._ctx_key[2:] != (unet_batch, h, w)):
+        if sag_forward:
+            if self._sag or gated or cache_mode != CACHE_OFF:
+                raise _lib.SdHipError("a SAG forward runs with capture off (set_sag(False)), without T-GATE and DeepCache")
+            if self._sag_ctx_key != (unet_batch, h, w):
+                raise _lib.SdHipError(f"set_sag_context(encoder_hidden_states, {h}, {w}) must be called for this batch and size first")
+        elif not gated and (self._ctx_key is None or self._ctx_key[2:] != (unet_batch, h, w)):
             raise _lib.SdHipError(f"set_context(encoder_hidden_states, {h}, {w}) must be called for this batch and size first")
         if self._ip_on and (unet_batch, self.cache_branch_id, h, w) not in self._ip_keys:
             raise _lib.SdHipError(f"this UNet runs with an IP-Adapter image prompt: set_ip_adapter(image_embeds, scale, {h}, {w}) must "
@@ -620,7 +732,7 @@ class HipUNet2DConditionModel(HipHandle):
             latents = latents.to(self.device, torch.float32).contiguous()
         if out is None:
             out = torch.empty((unet_batch, self.config.out_channels, h, w), dtype=torch.float32, device=self.device)
-        ws = self._tgate_workspace(unet_batch, h, w) if gated else self._reserve(unet_batch, h, w)
+        ws = self._sag_ws if sag_forward else self._tgate_workspace(unet_batch, h, w) if gated else self._reserve(unet_batch, h, w)
         _lib.check(self._lib.sd_unet_forward_hw(self._handle, _lib.current_stream(), latents.data_ptr(), b, unet_batch, h, w,
                                                 float(timestep), out.data_ptr(), ws.ptr, ws.nbytes,
                                                 cache_mode, self.cache_branch_id), "sd_unet_forward_hw")
@@ -670,7 +782,7 @@ class HipUNet2DConditionModel(HipHandle):
             _lib.check(self._lib.sd_unet_set_fp8_scale(self._handle, k.encode(), float(v)), f"sd_unet_set_fp8_scale({k})")
 
     KIND_NAMES = {0: "sinusoid", 1: "gemv", 2: "conv_in", 3: "groupnorm", 4: "conv3x3", 5: "gemm", 6: "layernorm",
-                  7: "attention", 8: "conv_out", 9: "hypertile_gather", 10: "hypertile_scatter", 11: "pag_identity", 16: "conv3x3_fp8", 17: "gemm_fp8", 18: "xattn_fused",
+                  7: "attention", 8: "conv_out", 9: "hypertile_gather", 10: "hypertile_scatter", 11: "pag_identity", 12: "sag_mass", 16: "conv3x3_fp8", 17: "gemm_fp8", 18: "xattn_fused",
                   19: "replicate", 20: "conv3x3_gemm", 21: "conv3x3_halo_subpix", 22: "ip_xattn", 23: "residual_add",
                   24: "tgate_capture", 25: "tgate_apply", 26: "tgate_zero",
                   27: "tome_match", 28: "tome_select", 29: "tome_merge", 30: "tome_unmerge", 31: "freeu"}
