@@ -269,6 +269,12 @@ int sd_unet_set_tgate_hw(sd_unet* u, int mode, void* cache, long long bytes, int
 /* How many execution plans the handle has built so far (one per batch, DeepCache branch, latent size and variant); < 0 on a
  * null handle.  For tests of "this setting builds no new plan". */
 int sd_unet_plan_count(const sd_unet* u);
+/* The options of a UNet and the pairs of them that are not built together: ONE table behind every setter, the forward and
+ * the workspace sizing, which all refuse a pair by the names of both.  sd_unet_option_name: the name of option i (0 .. count - 1),
+ * NULL past the end.  sd_unet_option_conflict: why options a and b are refused together, NULL when the pair is built (symmetric
+ * in a, b).  The Python layers hold the same rows (options.py); a test compares the two. */
+const char* sd_unet_option_name(int i);
+const char* sd_unet_option_conflict(int a, int b);
 
 /* HyperTile (tfernd/HyperTile, swap_size = 1): tiled self-attention.  tile_tokens = the tile side T in tokens (tile_size / 8), 8 or
  * more; max_depth 0..3; tile_tokens 0 = off = the plans, workspace sizes and results of a handle that never saw it.  A transformer

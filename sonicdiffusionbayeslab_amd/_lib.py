@@ -240,6 +240,8 @@ _SIGS = {
     "sd_unet_set_freeu": (_i, [_vp, _f, _f, _f, _f]),
     "sd_unet_disable_freeu": (_i, [_vp]),
     "sd_unet_plan_count": (_i, [_vp]),
+    "sd_unet_option_name": (C.c_char_p, [_i]),
+    "sd_unet_option_conflict": (C.c_char_p, [_i, _i]),
     "sd_op_freeu": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f]),
     "sd_unet_tgate_bytes_hw": (_ll, [_vp, _i, _i, _i]),
     "sd_unet_tgate_block_info_hw": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_ll), C.POINTER(_ll), C.POINTER(_i)]),

@@ -57,6 +57,94 @@ constexpr int TGATE_OFF = 0, TGATE_CAPTURE = 1, TGATE_REUSE = 2;      // sd_unet
 
 constexpr int REP_TEXT_POOLED = 2;       // Plan::rep of a CLIP text handle's sd_clip_text_embeds plan
 
+// ---- UNet options and the pairs of them that are not built ------------------------------------------------------------------
+// ONE table for the setters, the forward, get_plan and the workspace sizing (options.py holds the same rows for the Python
+// layers; tests/test_options_cpu.py compares the two through sd_unet_option_name / sd_unet_option_conflict).  The first three
+// are properties of a handle, DEEPCACHE / IP_PROMPT / CONTROL belong to a forward (or to what is set for the next one), the
+// rest are settings of the handle.
+enum UnetOption { OPT_FP8, OPT_INPAINT9, OPT_IP_MODEL, OPT_DEEPCACHE, OPT_IP_PROMPT, OPT_CONTROL, OPT_TOME, OPT_HYPERTILE, OPT_FREEU,
+                  OPT_TGATE, OPT_PAG, OPT_SAG, OPT_COUNT };
+constexpr unsigned opt_bit(int o) { return 1u << o; }
+
+inline const char* option_name(int i) {
+    static const char* const names[OPT_COUNT] = {"fp8", "9-channel UNet", "UNet with IP-Adapter weights", "DeepCache",
+                                                 "IP-Adapter image prompt", "ControlNet residuals", "Token Merging", "HyperTile",
+                                                 "FreeU", "T-GATE", "PAG", "SAG"};
+    return i >= 0 && i < OPT_COUNT ? names[i] : nullptr;
+}
+
+// the reason a pair is refused, null = the pair is built (symmetric)
+inline const char* option_conflict(int a, int b) {
+    static const struct { int a, b; const char* why; } refused[] = {
+        {OPT_FP8, OPT_CONTROL, "the calibrated activation scales do not describe the skip tensors with residuals added"},
+        {OPT_FP8, OPT_TOME, "the merge and unmerge kernels take bf16 tokens"},
+        {OPT_FP8, OPT_HYPERTILE, "the tile gather and scatter take bf16 tokens"},
+        {OPT_FP8, OPT_FREEU, "the calibrated activation scales do not describe the scaled tensors"},
+        {OPT_FP8, OPT_TGATE, "the calibrated activation scales do not describe the gated tensors"},
+        {OPT_FP8, OPT_PAG, "the identity kernel takes bf16 tokens"},
+        {OPT_FP8, OPT_SAG, "the attention-mass kernel takes bf16 q | k"},
+        {OPT_INPAINT9, OPT_TGATE, "an inpainting UNet is not gated"},
+        {OPT_INPAINT9, OPT_PAG, "an inpainting UNet has no perturbed branch"},
+        {OPT_INPAINT9, OPT_SAG, "the degraded latents have no mask channels"},
+        {OPT_IP_MODEL, OPT_TGATE, "the image branch of the cross-attention is not cached"},
+        {OPT_IP_MODEL, OPT_PAG, "the image prompt has no third branch"},
+        {OPT_IP_MODEL, OPT_SAG, "the image prompt has no branch on the degraded latents"},
+        {OPT_TOME, OPT_HYPERTILE, "merged tokens have no tile grid"},
+        {OPT_TOME, OPT_PAG, "merged tokens have no identity attention"},
+        {OPT_TOME, OPT_SAG, "merged tokens have no attention mass"},
+        {OPT_TGATE, OPT_DEEPCACHE, "the cached features are stored at the CFG batch"},
+        {OPT_TGATE, OPT_IP_PROMPT, "the image branch of the cross-attention is not cached"},
+        {OPT_TGATE, OPT_CONTROL, "the residuals are computed for the CFG batch"},
+        {OPT_TGATE, OPT_PAG, "behind the gate the UNet runs at the latent batch alone"},
+        {OPT_TGATE, OPT_SAG, "behind the gate the step has no pair to degrade from"},
+        {OPT_PAG, OPT_DEEPCACHE, "the cached features are stored at the CFG batch"},
+        {OPT_PAG, OPT_IP_PROMPT, "the image prompt has no third branch"},
+        {OPT_PAG, OPT_CONTROL, "the residuals are computed for the CFG batch"},
+        {OPT_PAG, OPT_SAG, "one extra guidance branch per step is built"},
+        {OPT_SAG, OPT_DEEPCACHE, "a skip step does not run the mid block"},
+        {OPT_SAG, OPT_IP_PROMPT, "the image prompt has no branch on the degraded latents"},
+        {OPT_SAG, OPT_CONTROL, "the residuals are computed for the first forward alone"},
+        {OPT_CONTROL, OPT_DEEPCACHE, "a skip step does not run the blocks the residuals are added in"},
+    };
+    for (const auto& p : refused)
+        if ((p.a == a && p.b == b) || (p.a == b && p.b == a)) return p.why;
+    return nullptr;
+}
+
+// fails (sd_set_error, -1) on the first refused pair among the options in `mask`
+inline int check_options(const char* who, unsigned mask) {
+    for (int a = 0; a < OPT_COUNT; ++a)
+        for (int b = a + 1; b < OPT_COUNT; ++b)
+            if ((mask & opt_bit(a)) && (mask & opt_bit(b)) && option_conflict(a, b)) {
+                sd_set_error("%s: %s with %s is not built (%s)", who, option_name(a), option_name(b), option_conflict(a, b));
+                return -1;
+            }
+    return 0;
+}
+
+// What names a plan of a handle, field by field (the key of sd_unet::plans, kept in the plan as Plan::v).  UNet (kind 0): rep
+// 2 = the prompt-independent prefix runs once per latent (CFG pair), see Builder::build; with a PAG mask rep = the copies of
+// the latent batch, 3 or 2.  CLIP text (kind 2): REP_TEXT_POOLED = the pooled + projected variant of sd_clip_text_embeds.
+// ip / cn: the IP-Adapter and the "control" variant; tome_bits: the bits of the merging ratio, with tome_max_downsample 0 = off;
+// freeu, sag: on / off; tgate: TGATE_OFF / CAPTURE / REUSE; tg_pair: y rows per cache row of a capture, 2 for a CFG pair, else
+// 1; ht_tokens / ht_max_depth: HyperTile's tile side in tokens and depth, 0 = off; pag_mask: the PAG layer mask, 0 = off.
+struct PlanVariant {
+    int UB = 0, branch = -1, rep = 1;
+    int lh = 0, lw = 0;
+    int ip = 0, cn = 0;
+    long long tome_bits = 0;
+    int tome_max_downsample = 0;
+    int freeu = 0, tgate = TGATE_OFF, tg_pair = 1;
+    int ht_tokens = 0, ht_max_depth = 0;
+    long long pag_mask = 0;
+    int sag = 0;
+    auto tied() const {
+        return std::tie(UB, branch, rep, lh, lw, ip, cn, tome_bits, tome_max_downsample, freeu, tgate, tg_pair, ht_tokens, ht_max_depth,
+                        pag_mask, sag);
+    }
+    bool operator<(const PlanVariant& o) const { return tied() < o.tied(); }
+};
+
 struct Op {
     int kind = 0;
     int x1 = -1, x2 = -1, r = -1, out = -1, aux = -1, b2t = -1;
@@ -155,51 +243,44 @@ struct Tn {
 };
 
 struct Plan {
-    int UB = 0, branch = -1;
-    // UNet (kind 0): 2 = the prompt-independent prefix runs once per latent (CFG pair), see Builder::build.  CLIP text
-    // (kind 2): REP_TEXT_POOLED = the pooled + projected output variant of sd_clip_text_embeds, see build_clip.  The field is
-    // part of the plan key, so the variants of one batch size are distinct plans.
-    int rep = 1;
-    int lh = 0, lw = 0;                   // latent height / width the plan is built for
-    // IP-Adapter variant (part of the plan key): one OP_IP_XATTN in front of every block's prompt cross-attention, whose
+    PlanVariant v;                        // what the plan was built for (its key)
+    // IP-Adapter variant (v.ip): one OP_IP_XATTN in front of every block's prompt cross-attention, whose
     // residual operand becomes that op's output.  ip_fold: per block the folded operands A [UB][32][C] and Bt [UB][C][32]
     // (ip_xattn.hip) with the packed weights they are folded from; ip_e / ip_proj / ip_tok / ip_kv: what
     // sd_unet_set_ip_adapter_hw computes on the way (bf16: embeds [UB][E], projection [UB][T * CD], tokens [UB * T][CD], and one
     // block's K_ip | V_ip [UB * T][2 C]).
-    int ip = 0;
     struct IpFold { int at, bt, C; size_t wqT, wo, wkv; int heads; };
     std::vector<IpFold> ip_fold;
     int ip_e = -1, ip_proj = -1, ip_tok = -1, ip_kv = -1;
-    // "control" variant (part of the plan key): one OP_RES_ADD after the mid block adds the ControlNet residuals in place to the
+    // "control" variant (v.cn): one OP_RES_ADD after the mid block adds the ControlNet residuals in place to the
     // twelve skip tensors and the mid output; up-block GroupNorms of those tensors compute their own statistics
-    int cn = 0;
     std::vector<size_t> cn_off;           // UNet / ControlNet plans: the residual segments' byte offsets and bf16 element
     std::vector<long> cn_count;           // counts for this batch and size (control_segments)
-    // Token Merging variant (the handle's setting is part of the plan key): the merging blocks in plan order.  Each owns its
+    // Token Merging variant (v.tome_bits): the merging blocks in plan order.  Each owns its
     // index tensors (persistent: readable after the forward, sd_unet_tome_matching_hw) and a slice of the handle's choice array.
     struct TomeBlock { int tok, kept, merged, dst_idx, B, h, w, r; long choice_off; };
     std::vector<TomeBlock> tome;
     long tome_choice_bytes = 0;
-    // HyperTile variant (the handle's setting is part of the plan key): the tiled transformer blocks in plan order, each with its
+    // HyperTile variant (v.ht_tokens): the tiled transformer blocks in plan order, each with its
     // token grid and tile counts (sd_unet_hypertile_block_info_hw)
     struct HtBlock { int rh, rw, nh, nw; };
     std::vector<HtBlock> hypertile;
-    // PAG variant (the handle's layer mask is part of the plan key, pag.hip): pag_lb > 0 = the LAST pag_lb samples of the batch are
-    // the perturbed ones (rep = UB / pag_lb is 3 or 2); in the blocks the mask names attn1 runs on the other samples and one
-    // OP_PAG_IDENTITY fills the perturbed rows of its output.  pag_blocks: the transformer blocks the builder has seen so far.
-    int pag_lb = 0, pag_blocks = 0;
-    // SAG capture variant (part of the plan key, sag.hip): one OP_SAG_MASS behind the q | k | v projection of the mid block's
+    // PAG variant (v.pag_mask, pag.hip): pag_lb() > 0 = the LAST pag_lb() samples of the batch are the perturbed ones (v.rep = UB /
+    // pag_lb() is 3 or 2; rep 1: the plan sd_unet_set_context_hw lays the prompt tensors out with); in the blocks the mask names
+    // attn1 runs on the other samples and one OP_PAG_IDENTITY fills the perturbed rows of its output.  pag_blocks: the
+    // transformer blocks the builder has seen so far.
+    int pag_lb() const { return v.pag_mask && v.rep > 1 ? v.UB / v.rep : 0; }
+    int pag_blocks = 0;
+    // SAG capture variant (v.sag, sag.hip): one OP_SAG_MASS behind the q | k | v projection of the mid block's
     // transformer block writes the attention mass of every sample into the buffer the handle names; nothing else changes
-    int sag = 0;
-    // FreeU variant (part of the plan key): one OP_FREEU in front of every resnet of up blocks 0 and 1 (x1 = hidden, x2 = skip ->
+    // FreeU variant (v.freeu): one OP_FREEU in front of every resnet of up blocks 0 and 1 (x1 = hidden, x2 = skip ->
     // out = the scaled hidden, aux = the filtered skip, epi = the up block: which pair of the handle's factors the launch reads)
-    int freeu = 0;
-    // T-GATE variant (part of the plan key; tgate.hip): TGATE_CAPTURE = every prompt cross-attention form runs WITHOUT its residual
-    // operand and one OP_TGATE_CAPTURE behind it writes h2 = h1 + y and the block's slice of the handle's cache (tg_pair = rows of
+    // T-GATE variant (v.tgate; tgate.hip): TGATE_CAPTURE = every prompt cross-attention form runs WITHOUT its residual
+    // operand and one OP_TGATE_CAPTURE behind it writes h2 = h1 + y and the block's slice of the handle's cache (v.tg_pair = rows of
     // y per cache row: 2 for a CFG pair [uncond | cond]); TGATE_REUSE = norm2, attn2 and every context tensor are gone and one
     // OP_TGATE_APPLY writes h2 = h1 + slice.  tg_off / tg_rows / tg_ch: the slices in plan order (tgate_segments), for tg_batch
     // latents; Op::b2idx of the two ops = the block's index.
-    int tgate = 0, tg_pair = 1, tg_batch = 0;
+    int tg_batch = 0;
     std::vector<size_t> tg_off;
     std::vector<long> tg_rows;
     std::vector<int> tg_ch;
@@ -266,13 +347,8 @@ struct sd_unet {
         act_names.push_back(name); act_scale.push_back(dflt); act_amax.push_back(0.f);
         return (int)act_names.size() - 1;
     }
-    // (UNet batch, DeepCache branch, prefix replication, latent H, W, IP-Adapter variant, control variant, Token Merging: the
-    // bits of the ratio and max_downsample, both 0 = off; FreeU on / off; T-GATE mode: TGATE_OFF / CAPTURE / REUSE; T-GATE pair: y rows per
-    // cache row of a capture, 2 for a CFG pair, else 1; HyperTile: tile side in tokens and max_depth, both 0 = off; PAG: the layer
-    // mask, 0 = off; SAG capture on / off)
-    std::map<std::tuple<int, int, int, int, int, int, int, long long, int, int, int, int, int, int, long long, int>, sdhip::Plan> plans;
-    int last_rep = 1, last_ip = 0, last_cn = 0;                       // variant of the last forward (sd_unet_debug_tensor)
-    int last_h = 0, last_w = 0;                          // latent size of the last forward (sd_unet_debug_tensor)
+    std::map<sdhip::PlanVariant, sdhip::Plan> plans;
+    sdhip::PlanVariant last;           // variant of the last forward (sd_unet_debug_tensor, sd_unet_tome_matching_hw); lh 0 = none yet
     std::unordered_map<std::string, long> tproj_off;  // resnet prefix -> float index into tproj vector
     long tproj_total = 0;
     // LCM-distilled UNets (cfg.time_cond_proj_dim > 0): cond_proj . condition, [c0] fp32, written by sd_unet_set_timestep_cond.
@@ -381,11 +457,13 @@ long long taesd_workspace_bytes(const sd_unet* u, int batch, int lh, int lw);
 // plan.hip
 int plan_rep(const sd_unet* u, int latent_batch, int unet_batch);
 int check_latent_size(const sd_unet* u, int lh, int lw, const char* who);
-// lh / lw < 0: the handle's sample_size (square); tgate < 0: the handle's T-GATE mode (tgate_variant), 0 = the plain plan
-int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep = 1, int lh = -1, int lw = -1, int ip = 0, int cn = 0, int tgate = -1);
+// the variant of (UB, branch, latent size) under the handle's option state: rep 1, no image prompt, no residuals (a call site
+// that runs another one sets the field).  lh / lw < 0: the handle's sample_size; branch < 0: -1; kinds other than 0 have no options
+PlanVariant plan_variant(const sd_unet* u, int UB, int branch = -1, int lh = -1, int lw = -1);
+unsigned variant_options(const sd_unet* u, const PlanVariant& v);     // the options a plan of this variant runs with (check_options)
+unsigned active_options(const sd_unet* u);        // ... and those on the handle now, residuals and image prompts that are set included
+int get_plan(sd_unet* u, const PlanVariant& v, Plan** out);
 int transformer_block_count(const sd_unet_config& c);      // transformer blocks of a UNet in plan order (down, mid, up)
-int tgate_variant(const sd_unet* u);              // the T-GATE mode of the handle's plans (TGATE_OFF unless a UNet handle has one set)
-int tgate_pair(const sd_unet* u, int UB);         // y rows per cache row of a capture forward at batch UB (2 = a CFG pair)
 bool ip_active(const sd_unet* u, int UB, int branch, int lh, int lw);     // is this forward's IP-Adapter key set?
 // the ControlNet residual segments of a (UNet batch, latent size), in order: byte offset into the residual buffer and bf16
 // element count of each (include/sd_hip.h: the layout); returns the buffer's bytes

@@ -237,7 +237,7 @@ struct Builder {
     // Token Merging: how many src tokens a block on a level of rh x rw tokens merges; 0 = the block does not merge (the setting
     // is off, or the level is past max_downsample).  r = min(num_src, int(N ratio)) as tomesd computes it.
     int tome_r(int rh, int rw, int C) {
-        if (u->kind != 0 || u->fp8 || !(u->tome_ratio > 0.0) || rh <= 0 || pl.lh / rh > u->tome_max_downsample) return 0;
+        if (u->kind != 0 || u->fp8 || !(u->tome_ratio > 0.0) || rh <= 0 || pl.v.lh / rh > u->tome_max_downsample) return 0;
         const int N = rh * rw;
         if (rh % 2 || rw % 2 || N > 16384 || C % 64 || C > 1536) {
             if (error.empty()) error = "Token Merging needs even token-grid sides, at most 16384 tokens and C a multiple of 64 up to 1536 on "
@@ -257,7 +257,7 @@ struct Builder {
     }
     void hypertile_tiles(int rh, int rw, int* nh, int* nw) {
         *nh = *nw = 1;
-        if (u->kind != 0 || u->fp8 || u->ht_tokens <= 0 || rh <= 0 || rw <= 0 || pl.lh / rh > (1 << u->ht_max_depth)) return;
+        if (u->kind != 0 || u->fp8 || u->ht_tokens <= 0 || rh <= 0 || rw <= 0 || pl.v.lh / rh > (1 << u->ht_max_depth)) return;
         *nh = rh / ht_tile_side(rh, u->ht_tokens);
         *nw = rw / ht_tile_side(rw, u->ht_tokens);
     }
@@ -274,7 +274,7 @@ struct Builder {
     int n_transformers = 0;
     int transformer(const std::string& p, int x, int C, int rh, int rw) {
         const int blk = pl.pag_blocks++;
-        const bool pert = pl.pag_lb > 0 && ((u->pag_mask >> blk) & 1);
+        const bool pert = pl.pag_lb() > 0 && ((u->pag_mask >> blk) & 1);
         if (pert && prefix_rep > 1) {
             x = replicate(x, (size_t)UB * rh * rw * C * 2, prefix_rep);
             UB *= prefix_rep;
@@ -351,15 +351,15 @@ struct Builder {
         const int Na = Nm / nt;
         const bool hm = !hm_off && C / NH == 40 && C % 160 == 0 && Na % 128 == 0 && Na >= 256 &&
                         sd_gemm_tile_rows(Mm, 3 * C) == 128 && pl.ops.back().splitk == 1;
-        if (pert && (tr > 0 || fq || pl.pag_lb >= UB)) {
+        if (pert && (tr > 0 || fq || pl.pag_lb() >= UB)) {
             if (error.empty()) error = "PAG with Token Merging or fp8, or a batch without unperturbed samples, is not built";
             return x;
         }
-        const int Ba = (pert ? UB - pl.pag_lb : UB) * nt;      // the samples the attention kernel sees
+        const int Ba = (pert ? UB - pl.pag_lb() : UB) * nt;      // the samples the attention kernel sees
         const int qkv_op = (int)pl.ops.size() - 1;             // the q | k | v projection (an OP_SAG_MASS may follow it)
         // SAG capture (sag.hip): the mid block's attention mass of all UB samples, from Q and K as the projection left them
         // (token-major, pitch 3 C; W_q carries scale * log2 e).  Reads qkv, writes the handle's buffer: no plan tensor changes.
-        if (pl.sag && p == "mid_block.attentions.0.") {
+        if (pl.v.sag && p == "mid_block.attentions.0.") {
             if (nt != 1) { if (error.empty()) error = "SAG with a HyperTile setting that tiles the mid block is not built"; return x; }
             if (tr > 0 || fq || pert) { if (error.empty()) error = "SAG with Token Merging, fp8 or PAG is not built"; return x; }
             if (rh < 4 || rh > 16 || rw < 4 || rw > 16) {
@@ -382,7 +382,7 @@ struct Builder {
         }
         pl.ops.back().qps = 1;          // W_q of attn1 carries the scale (Packer::transformer)
         if (pert) {
-            const long row0 = (long)(UB - pl.pag_lb) * hw, rows = (long)pl.pag_lb * hw;
+            const long row0 = (long)(UB - pl.pag_lb()) * hw, rows = (long)pl.pag_lb() * hw;
             if (sd_pag_identity_shape_ok(Mm, row0, rows, C, NH, 3 * C, hm ? Na : 0, "PAG")) { if (error.empty()) error = sd_last_error(); return x; }
             pl.tensors[a1].bytes = ((size_t)Mm * C * 2 + 255) / 256 * 256;      // (the attention op sized it for its own samples)
             Op o; o.kind = OP_PAG_IDENTITY; o.x1 = qkv; o.out = a1; o.M = Mm; o.N = C; o.heads = NH; o.qoff = row0; o.koff = rows;
@@ -418,12 +418,12 @@ struct Builder {
         // T-GATE (tgate.hip).  Reuse: norm2, attn2 and their context tensors are gone -- h2 = h1 + the block's cache slice, one
         // launch, which also delivers the row partials norm3's fold reads.  Capture (below): whichever form runs, runs WITHOUT
         // its residual operand, so that its output is y = to_out(attention) + b_o alone, and OP_TGATE_CAPTURE adds the residual.
-        const int tg_i = pl.tgate ? pl.tg_blocks++ : -1;
-        if (pl.tgate && (tg_i >= (int)pl.tg_rows.size() || pl.tg_rows[tg_i] != (long)(M / pl.tg_pair) || pl.tg_ch[tg_i] != C)) {
+        const int tg_i = pl.v.tgate ? pl.tg_blocks++ : -1;
+        if (pl.v.tgate && (tg_i >= (int)pl.tg_rows.size() || pl.tg_rows[tg_i] != (long)(M / pl.v.tg_pair) || pl.tg_ch[tg_i] != C)) {
             if (error.empty()) error = "T-GATE cache layout (block " + std::to_string(tg_i) + ")";
             return x;
         }
-        if (pl.tgate == TGATE_REUSE) {
+        if (pl.v.tgate == TGATE_REUSE) {
             Op o; o.kind = OP_TGATE_APPLY; o.x1 = h1; o.M = M; o.N = C; o.b2idx = tg_i;
             o.out = tensor((size_t)M * C * 2); push(o);
             return transformer_ff(p, t, x, o.out, M, C, fq);
@@ -455,14 +455,14 @@ struct Builder {
         // its own LayerNorm from the row itself, whatever form and fold the text attention below uses); R' then is the RESIDUAL
         // operand of that form, whose other operands stay as they are:  h2 = h1 + scale to_out(image) + to_out(text) + b_o
         int res = h1;
-        if (pl.ip) {
+        if (pl.v.ip) {
             const int at = ctx_ip_tensor((size_t)UB * 32 * C * 2), bt = ctx_ip_tensor((size_t)UB * C * 32 * 2);
             pl.ip_fold.push_back(Plan::IpFold{at, bt, C, W(t + "attn2.to_q.weight.T"), W(t + "attn2.to_out.0.weight"), W(t + "attn2.kv_ip.weight"), NH});
             Op o; o.kind = OP_IP_XATTN; o.x1 = h1; o.wt = at; o.x2 = bt; o.M = M; o.N = C; o.rpb = hw; o.heads = NH;
             o.g = W(t + "norm2.weight"); o.be = W(t + "norm2.bias"); o.eps = 1e-5f;
             o.out = tensor((size_t)M * C * 2); push(o); res = o.out;
         }
-        const bool tg_cap = pl.tgate == TGATE_CAPTURE;
+        const bool tg_cap = pl.v.tgate == TGATE_CAPTURE;
         int h2;
         if (xmode == 0) {
             int at = ctx_tensor((size_t)UB * NP * C * 2), bw = ctx_tensor((size_t)UB * C * NP * 2);
@@ -497,7 +497,7 @@ struct Builder {
             h2 = gemm(a2, C, -1, 0, M, C, t + "attn2.to_out.0.weight", t + "attn2.to_out.0.bias", tg_cap ? -1 : res, 0);
         }
         if (tg_cap) {
-            Op o; o.kind = OP_TGATE_CAPTURE; o.x1 = h2; o.r = res; o.M = M; o.N = C; o.K = pl.tg_pair; o.b2idx = tg_i;
+            Op o; o.kind = OP_TGATE_CAPTURE; o.x1 = h2; o.r = res; o.M = M; o.N = C; o.K = pl.v.tg_pair; o.b2idx = tg_i;
             o.out = tensor((size_t)M * C * 2); push(o); h2 = o.out;
         }
         return transformer_ff(p, t, x, h2, M, C, fq);
@@ -576,7 +576,7 @@ struct Builder {
     void build_vae() {
         const sd_unet_config& c = u->cfg;
         const int nl = c.num_levels, top = c.block_out_channels[nl - 1];
-        int rh = pl.lh, rw = pl.lw;
+        int rh = pl.v.lh, rw = pl.v.lw;
         int t_pq = tensor((size_t)UB * c.in_channels * rh * rw * 4);
         { Op o; o.kind = OP_PQCONV; o.x1 = T_LATENTS; o.out = t_pq; o.B = UB; o.HW = rh * rw;
           o.w = W("post_quant_conv.weight"); o.b = W("post_quant_conv.bias"); push(o); }
@@ -614,7 +614,7 @@ struct Builder {
     void build_vae_encoder() {
         const sd_unet_config& c = u->cfg;
         const int nl = c.num_levels, top = c.block_out_channels[nl - 1], c0 = c.block_out_channels[0];
-        int rh = pl.lh << (nl - 1), rw = pl.lw << (nl - 1);
+        int rh = pl.v.lh << (nl - 1), rw = pl.v.lw << (nl - 1);
         int h;
         { Op o; o.kind = OP_CONV_IN_IMG; o.x1 = T_LATENTS; o.B = UB; o.Hin = rh; o.Win = rw; o.Cin = c.out_channels; o.N = c0;
           o.w = W("encoder.conv_in.weight"); o.b = W("encoder.conv_in.bias"); o.out = tensor((size_t)UB * rh * rw * c0 * 2);
@@ -683,7 +683,7 @@ struct Builder {
             t = clip_encoder_layer(clip_layer(i), t, M, L, H, I, c.num_heads, OP_CLIP_ATTN, c.hidden_act == SD_ACT_GELU);
             pl.taps["layer" + std::to_string(i)] = t;
         }
-        if (pl.rep == REP_TEXT_POOLED) {      // pooled + projected variant (sd_clip_text_embeds): the EOS row, final LayerNorm, text_projection
+        if (pl.v.rep == REP_TEXT_POOLED) {      // pooled + projected variant (sd_clip_text_embeds): the EOS row, final LayerNorm, text_projection
             int pr;
             { Op o; o.kind = OP_POOL; o.x1 = t; o.pool_by_ids = 1; o.B = UB; o.Nq = L; o.N = H; o.out = tensor((size_t)UB * H * 2); push(o); pr = o.out; }
             int f = ln(pr, UB, H, "text_model.final_layer_norm.weight", "text_model.final_layer_norm.bias");
@@ -702,7 +702,7 @@ struct Builder {
         const sd_clip_vision_config& c = u->vis;
         const int S = c.image_size, P = c.patch_size, G = S / P, Np = G * G, L = Np + 1;
         const int H = c.hidden_size, I = c.intermediate_size, Kp = vit_kp(c), M = UB * L;
-        if (sd_clip_prep_tables(pl.lh, pl.lw, S, pl.prep_tab, pl.geom)) { error = sd_last_error(); return; }
+        if (sd_clip_prep_tables(pl.v.lh, pl.v.lw, S, pl.prep_tab, pl.geom)) { error = sd_last_error(); return; }
         int patches;
         { Op o; o.kind = OP_VIT_PREP; o.x1 = T_LATENTS; o.B = UB; o.K = Kp; o.Cin = P;
           o.aux = tensor((size_t)UB * 3 * pl.geom.R * S); o.out = tensor((size_t)UB * Np * Kp * 2); push(o); patches = o.out; }
@@ -735,7 +735,7 @@ struct Builder {
         const int H = c.vision_hidden_size, I = c.vision_intermediate_size, Kp = blip_kp(c), M = UB * L;
         const float eps = c.vision_layer_norm_eps;
         *tokens = L;
-        if (sd_clip_prep_tables(pl.lh, pl.lw, S, pl.prep_tab, pl.geom)) { error = sd_last_error(); return -1; }
+        if (sd_clip_prep_tables(pl.v.lh, pl.v.lw, S, pl.prep_tab, pl.geom)) { error = sd_last_error(); return -1; }
         int patches;
         { Op o; o.kind = OP_VIT_PREP; o.x1 = T_LATENTS; o.B = UB; o.K = Kp; o.Cin = P;
           o.aux = tensor((size_t)UB * 3 * pl.geom.R * S); o.out = tensor((size_t)UB * Np * Kp * 2); push(o); patches = o.out; }
@@ -776,7 +776,7 @@ struct Builder {
     // attention reads its slice through the column offset.
     void build_blip_text(int img, int Lv) {
         const sd_image_reward_config& c = u->ir;
-        const int Lt = pl.rep, H = c.hidden_size, I = c.intermediate_size, EW = c.vision_hidden_size, M = UB * Lt, NL = c.num_layers;
+        const int Lt = pl.v.rep, H = c.hidden_size, I = c.intermediate_size, EW = c.vision_hidden_size, M = UB * Lt, NL = c.num_layers;
         const float eps = c.layer_norm_eps;
         const long ldkv = (long)NL * 2 * H;
         int kvall = lin(img, EW, UB * Lv, NL * 2 * H, "text_encoder.cross_kv");
@@ -818,19 +818,19 @@ struct Builder {
         const sd_unet_config& c = u->cfg;
         const int nl = c.num_levels, c0 = c.block_out_channels[0], temb = 4 * c0;
         const int L = c.context_len;
-        if (pl.tgate) {
-            pl.tg_batch = UB / pl.tg_pair;
-            tgate_segments(c, pl.tg_batch, pl.lh, pl.lw, &pl.tg_off, &pl.tg_rows, &pl.tg_ch);
+        if (pl.v.tgate) {
+            pl.tg_batch = UB / pl.v.tg_pair;
+            tgate_segments(c, pl.tg_batch, pl.v.lh, pl.v.lw, &pl.tg_off, &pl.tg_rows, &pl.tg_ch);
         }
         // (a T-GATE reuse plan has no prompt cross-attention: no context tensor at all, sd_unet_set_context_hw is not needed for it)
-        if (pl.tgate != TGATE_REUSE) pl.ctx_bf16 = ctx_tensor((size_t)UB * L * c.cross_attention_dim * 2);
+        if (pl.v.tgate != TGATE_REUSE) pl.ctx_bf16 = ctx_tensor((size_t)UB * L * c.cross_attention_dim * 2);
         // masked K / V expansions used by sd_unet_set_context for the folded cross-attention: sized for the level with the most
         // (head, key slot) rows x channels (the mid block sits on the last level)
         size_t fold_max = 0;
         for (int i = 0; i < nl; ++i)
             if (c.attn_levels[i] || i == nl - 1) fold_max = std::max(fold_max, (size_t)level_heads(c, i) * 80 * c.block_out_channels[i]);
-        if (pl.tgate != TGATE_REUSE) pl.ctx_fold_scratch = ctx_tensor((size_t)3 * UB * fold_max * 2);
-        if (pl.ip) {      // what sd_unet_set_ip_adapter_hw computes on the way to the folded operands (its expansions reuse the scratch above)
+        if (pl.v.tgate != TGATE_REUSE) pl.ctx_fold_scratch = ctx_tensor((size_t)3 * UB * fold_max * 2);
+        if (pl.v.ip) {      // what sd_unet_set_ip_adapter_hw computes on the way to the folded operands (its expansions reuse the scratch above)
             const int T = c.ip_adapter_tokens, CD = c.cross_attention_dim;
             int cmax = 0;
             for (int i = 0; i < nl; ++i) cmax = std::max(cmax, c.block_out_channels[i]);
@@ -847,10 +847,10 @@ struct Builder {
         { Op o; o.kind = OP_GEMV; o.x1 = t_h1; o.out = t_emb; o.N = temb; o.K = temb; o.silu_in = 1; o.w = W("time_embedding.linear_2.weight"); o.b = W("time_embedding.linear_2.bias"); push(o); }
         { Op o; o.kind = OP_GEMV; o.x1 = t_emb; o.out = t_proj; o.N = (int)u->tproj_total; o.K = temb; o.silu_in = 1; o.w = W("tproj.weight"); o.b = W("tproj.bias"); push(o); }
         // ---- conv_in ----
-        int rh = pl.lh, rw = pl.lw;
+        int rh = pl.v.lh, rw = pl.v.lw;
         int h;
         // (restored by the first transformer block; a PAG plan of a UNet without one on its first level runs without the prefix)
-        if (pl.rep > 1 && (!pl.pag_lb || c.attn_levels[0])) { prefix_rep = pl.rep; UB /= pl.rep; }
+        if (pl.v.rep > 1 && (!pl.pag_lb() || c.attn_levels[0])) { prefix_rep = pl.v.rep; UB /= pl.v.rep; }
         { Op o; o.kind = OP_CONV_IN; o.x1 = T_LATENTS; o.B = UB; o.Hin = rh; o.Win = rw; o.Cin = c.in_channels; o.N = c0;
           o.w = W("conv_in.weight"); o.b = W("conv_in.bias"); o.out = tensor((size_t)UB * rh * rw * c0 * 2); push(o); h = o.out; }
         const int h_skip = prefix_rep > 1 ? replicate(h, (size_t)UB * rh * rw * c0 * 2, prefix_rep) : h;
@@ -889,8 +889,8 @@ struct Builder {
         wrapstack.pop_back();
         pl.taps["mid"] = h;
         skips.push_back(h); skip_ch.push_back(ch); skip_hw.push_back(rh * rw);       // (the mid output: the thirteenth residual)
-        if ((int)skips.size() > MAX_CONTROL_RES && (u->kind == 5 || pl.cn)) { error = "more than 16 ControlNet residuals"; return; }
-        control_segments(c, UB, pl.lh, pl.lw, &pl.cn_off, &pl.cn_count);
+        if ((int)skips.size() > MAX_CONTROL_RES && (u->kind == 5 || pl.v.cn)) { error = "more than 16 ControlNet residuals"; return; }
+        control_segments(c, UB, pl.v.lh, pl.v.lw, &pl.cn_off, &pl.cn_count);
         if (u->kind == 5) {
             // ---- ControlNet: the zero convs, one 1x1 GEMM per residual straight into the caller's buffer (T_EPS at the segment's
             // offset, unscaled: conditioning_scale is applied where the residuals are consumed) ----
@@ -908,7 +908,7 @@ struct Builder {
             }
             return;
         }
-        if (pl.cn) {
+        if (pl.v.cn) {
             // ---- "control" variant: x <- x + scale * r on the twelve skips (conv_in's is the replicated tensor under rep == 2)
             // and the mid output, in place, ONE launch.  Every reader of the unmodified tensors -- the down path and the mid
             // block, including a GroupNorm that finishes a producer's deferred split-K reduce -- has run (op_tensors lists the
@@ -936,7 +936,7 @@ struct Builder {
                 const int rl = nres - 1 - j;
                 wrapstack.push_back(Wrap{2, rb, rl});
                 int hin = h, sin = s;
-                if (pl.freeu && i < 2) {
+                if (pl.v.freeu && i < 2) {
                     // FreeU (freeu.hip) inside the resnet's own Wrap: it runs whenever the resnet runs, on new tensors -- a DeepCache
                     // skip step reads the cached feature through it and leaves the feature raw.  The new tensors have no entry in
                     // stats_of: the producers' statistics do not describe them, norm1 runs its own pass.
@@ -960,7 +960,7 @@ struct Builder {
             wrapstack.pop_back();
             pl.taps["up" + std::to_string(i)] = h;
         }
-        if (pl.tgate && pl.tg_blocks != (int)pl.tg_rows.size() && error.empty()) error = "T-GATE cache layout (block count)";
+        if (pl.v.tgate && pl.tg_blocks != (int)pl.tg_rows.size() && error.empty()) error = "T-GATE cache layout (block count)";
         // ---- out ----
         int g = gn(h, ch, -1, 0, rh * rw, "conv_norm_out.weight", "conv_norm_out.bias", c.norm_eps, 1);
         { Op o; o.kind = OP_CONV_OUT; o.x1 = g; o.out = T_EPS; o.B = UB; o.Hin = rh; o.Win = rw; o.Cin = ch; o.N = c.out_channels;
@@ -991,9 +991,9 @@ void fuse_deferred_reduce(sd_unet* u, Plan& pl) {
     if (getenv("SD_GN_SLAB") && atoi(getenv("SD_GN_SLAB")) == 0) return;       // (read when a plan is built: tests build both)
     const int nops = (int)pl.ops.size();
     auto skipped = [&](const Op& o) {
-        if (pl.branch < 0) return false;
+        if (pl.v.branch < 0) return false;
         for (int k = 0; k < o.nwrap; ++k)
-            if (wrap_skipped(o.wraps[k], pl.branch)) return true;
+            if (wrap_skipped(o.wraps[k], pl.v.branch)) return true;
         return false;
     };
     std::vector<int> producer(pl.tensors.size(), -1);
@@ -1027,10 +1027,10 @@ void assign_memory(sd_unet* u, Plan& pl) {
     const int nops = (int)pl.ops.size();
     // DeepCache: which ops are skipped on skip steps, and which tensors they leave behind for running ops
     pl.skipped.assign(nops, 0);
-    if (pl.branch >= 0) {
+    if (pl.v.branch >= 0) {
         for (int i = 0; i < nops; ++i)
             for (int k = 0; k < pl.ops[i].nwrap; ++k)
-                if (wrap_skipped(pl.ops[i].wraps[k], pl.branch)) pl.skipped[i] = 1;
+                if (wrap_skipped(pl.ops[i].wraps[k], pl.v.branch)) pl.skipped[i] = 1;
         std::vector<int> producer(pl.tensors.size(), -1);
         for (int i = 0; i < nops; ++i) {
             if (pl.ops[i].out >= 0) producer[pl.ops[i].out] = i;
@@ -1171,64 +1171,75 @@ size_t tgate_segments(const sd_unet_config& c, int batch, int lh, int lw, std::v
     return bytes;
 }
 
-// the T-GATE mode of the handle's plans (only UNet handles have one)
-int tgate_variant(const sd_unet* u) {
-    return u->kind == 0 ? u->tg_mode : TGATE_OFF;
-}
-
-// y rows per cache row of a capture at batch UB: 2 for a CFG pair (the forward's batch is twice the batch the cache was laid out for)
-int tgate_pair(const sd_unet* u, int UB) {
-    return UB == 2 * u->tg_b ? 2 : 1;
-}
-
 bool ip_active(const sd_unet* u, int UB, int branch, int lh, int lw) {
     return u->ip_keys.count(std::make_tuple(UB, branch < 0 ? -1 : branch, lh, lw)) != 0;
 }
 
-int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw, int ip, int cn, int tgate) {
+PlanVariant plan_variant(const sd_unet* u, int UB, int branch, int lh, int lw) {
+    PlanVariant v;
+    v.UB = UB;
+    v.branch = branch < 0 ? -1 : branch;
+    v.lh = lh < 0 ? u->cfg.sample_size : lh;
+    v.lw = lw < 0 ? u->cfg.sample_size : lw;
+    if (u->kind != 0) return v;
+    if (u->tome_ratio > 0.0) {
+        memcpy(&v.tome_bits, &u->tome_ratio, sizeof(v.tome_bits));
+        v.tome_max_downsample = u->tome_max_downsample;
+    }
+    v.freeu = u->freeu_on ? 1 : 0;
+    v.tgate = u->tg_mode;
+    // y rows per cache row of a capture: 2 for a CFG pair (the forward's batch is twice the batch the cache was laid out for)
+    v.tg_pair = v.tgate == TGATE_CAPTURE && UB == 2 * u->tg_b ? 2 : 1;
+    v.ht_tokens = u->ht_tokens;
+    v.ht_max_depth = u->ht_tokens ? u->ht_max_depth : 0;
+    v.pag_mask = u->pag_mask;
+    v.sag = u->sag_on ? 1 : 0;
+    return v;
+}
+
+unsigned variant_options(const sd_unet* u, const PlanVariant& v) {
+    unsigned m = 0;
+    if (u->kind != 0) return m;
+    if (u->fp8) m |= opt_bit(OPT_FP8);
+    if (u->cfg.in_channels == 9) m |= opt_bit(OPT_INPAINT9);
+    if (u->cfg.ip_adapter_tokens > 0) m |= opt_bit(OPT_IP_MODEL);
+    if (v.branch >= 0) m |= opt_bit(OPT_DEEPCACHE);
+    if (v.ip) m |= opt_bit(OPT_IP_PROMPT);
+    if (v.cn) m |= opt_bit(OPT_CONTROL);
+    if (v.tome_bits) m |= opt_bit(OPT_TOME);
+    if (v.ht_tokens) m |= opt_bit(OPT_HYPERTILE);
+    if (v.freeu) m |= opt_bit(OPT_FREEU);
+    if (v.tgate) m |= opt_bit(OPT_TGATE);
+    if (v.pag_mask) m |= opt_bit(OPT_PAG);
+    if (v.sag) m |= opt_bit(OPT_SAG);
+    return m;
+}
+
+unsigned active_options(const sd_unet* u) {
+    PlanVariant v = plan_variant(u, 1);
+    v.ip = u->ip_keys.empty() ? 0 : 1;
+    v.cn = u->ctrl_res ? 1 : 0;
+    return variant_options(u, v);
+}
+
+int get_plan(sd_unet* u, const PlanVariant& v, Plan** out) {
     SD_REQUIRE(u && u->finalized, "unet: parameters not finalized");
-    SD_REQUIRE(UB > 0 && UB <= 4096, "unet: bad batch %d", UB);
-    SD_REQUIRE(branch < 3 * u->cfg.num_levels, "unet: cache_branch_id %d out of range", branch);
-    if (branch < 0) branch = -1;
-    if (lh < 0) lh = u->cfg.sample_size;
-    if (lw < 0) lw = u->cfg.sample_size;
-    long long tome_bits = 0;
-    if (u->kind == 0 && u->tome_ratio > 0.0) memcpy(&tome_bits, &u->tome_ratio, sizeof(tome_bits));
-    const int freeu = u->kind == 0 && u->freeu_on ? 1 : 0;
-    if (tgate < 0) tgate = tgate_variant(u);
-    const int tg_pair = tgate == TGATE_CAPTURE ? tgate_pair(u, UB) : 1;
-    SD_REQUIRE(!tgate || (branch < 0 && !ip && !cn && !u->fp8), "unet: T-GATE with DeepCache, an IP-Adapter, ControlNet residuals or fp8 is not built");
-    SD_REQUIRE(tg_pair == 1 || UB % 2 == 0, "unet: a T-GATE capture of a CFG pair needs an even batch (%d)", UB);
-    auto key = std::make_tuple(UB, branch, rep, lh, lw, ip, cn, tome_bits, tome_bits ? u->tome_max_downsample : 0, freeu, tgate, tg_pair,
-                               u->kind == 0 ? u->ht_tokens : 0, u->kind == 0 && u->ht_tokens ? u->ht_max_depth : 0,
-                               u->kind == 0 ? u->pag_mask : 0ll, u->kind == 0 && u->sag_on ? 1 : 0);
-    const bool pag = u->kind == 0 && u->pag_mask;
-    const bool sag = u->kind == 0 && u->sag_on;
-    SD_REQUIRE(!sag || (branch < 0 && !ip && !cn && !tgate && !tome_bits && !u->fp8 && !pag),
-               "unet: SAG with DeepCache, an IP-Adapter image prompt, ControlNet residuals, T-GATE, Token Merging, fp8 or PAG is not built");
-    SD_REQUIRE(!pag || (branch < 0 && !ip && !cn && !tgate && !tome_bits && !u->fp8),
-               "unet: PAG with DeepCache, an IP-Adapter image prompt, ControlNet residuals, T-GATE, Token Merging or fp8 is not built");
-    SD_REQUIRE(!pag || rep == 1 || ((rep == 2 || rep == 3) && UB % rep == 0), "unet: a PAG forward runs 2 or 3 copies of the latent batch (%d of batch %d)", rep, UB);
-    auto it = u->plans.find(key);
+    SD_REQUIRE(v.UB > 0 && v.UB <= 4096, "unet: bad batch %d", v.UB);
+    SD_REQUIRE(v.branch < 3 * u->cfg.num_levels, "unet: cache_branch_id %d out of range", v.branch);
+    if (check_options("unet", variant_options(u, v))) return -1;
+    const int UB = v.UB, lh = v.lh, lw = v.lw;
+    SD_REQUIRE(v.tg_pair == 1 || UB % 2 == 0, "unet: a T-GATE capture of a CFG pair needs an even batch (%d)", UB);
+    SD_REQUIRE(!v.pag_mask || v.rep == 1 || ((v.rep == 2 || v.rep == 3) && UB % v.rep == 0),
+               "unet: a PAG forward runs 2 or 3 copies of the latent batch (%d of batch %d)", v.rep, UB);
+    auto it = u->plans.find(v);
     if (it == u->plans.end()) {
         if (lh != u->cfg.sample_size || lw != u->cfg.sample_size)
             if (check_latent_size(u, lh, lw, "unet")) return -1;
         Plan pl;
-        pl.UB = UB;
-        pl.branch = branch;
-        pl.rep = rep;
-        pl.lh = lh;
-        pl.lw = lw;
-        pl.ip = ip;
-        pl.cn = cn;
-        pl.freeu = freeu;
-        pl.tgate = tgate;
-        pl.tg_pair = tg_pair;
-        pl.sag = sag ? 1 : 0;
-        pl.pag_lb = pag && rep > 1 ? UB / rep : 0;      // (rep 1: the plan sd_unet_set_context_hw lays the prompt tensors out with)
+        pl.v = v;
         Builder b{u, pl, UB, {}};
         b.build();
-        SD_REQUIRE(b.error.empty(), "unet: cannot build the plan for batch %d (cache branch %d, latent %dx%d): %s", UB, branch, lh, lw,
+        SD_REQUIRE(b.error.empty(), "unet: cannot build the plan for batch %d (cache branch %d, latent %dx%d): %s", UB, v.branch, lh, lw,
                    b.error.c_str());
         fuse_deferred_reduce(u, pl);
         assign_memory(u, pl);
@@ -1241,7 +1252,7 @@ int get_plan(sd_unet* u, int UB, int branch, Plan** out, int rep, int lh, int lw
             pl.dtab = d;
             std::vector<int>().swap(pl.prep_tab);
         }
-        it = u->plans.emplace(key, std::move(pl)).first;
+        it = u->plans.emplace(v, std::move(pl)).first;
     }
     *out = &it->second;
     return 0;

@@ -416,7 +416,7 @@ extern "C" int sd_vae_decode_hw(sd_unet* u, void* stream, const float* latents, 
     SD_REQUIRE(latents && images_out && workspace && batch > 0, "vae_decode: null argument");
     if (check_latent_size(u, latent_h, latent_w, "vae_decode")) return -1;
     Plan* pl;
-    int rc = get_plan(u, batch, -1, &pl, 1, latent_h, latent_w);
+    int rc = get_plan(u, plan_variant(u, batch, -1, latent_h, latent_w), &pl);
     if (rc) return rc;
     return run_plan(u, *pl, "vae_decode", workspace, workspace_bytes, latents, batch, images_out, latent_scale, stream);
 }
@@ -445,7 +445,7 @@ extern "C" int sd_vae_encode_hw(sd_unet* u, void* stream, const float* images, i
     SD_REQUIRE(images && moments_out && workspace && batch > 0, "vae_encode: null argument");
     if (check_latent_size(u, latent_h, latent_w, "vae_encode")) return -1;
     Plan* pl;
-    int rc = get_plan(u, batch, -1, &pl, 1, latent_h, latent_w);
+    int rc = get_plan(u, plan_variant(u, batch, -1, latent_h, latent_w), &pl);
     if (rc) return rc;
     return run_plan(u, *pl, "vae_encode", workspace, workspace_bytes, images, batch, moments_out, 0.f, stream);
 }
@@ -482,7 +482,7 @@ extern "C" int sd_clip_encode(sd_unet* u, void* stream, const int* input_ids, in
     SD_REQUIRE(u && u->kind == 2, "clip_encode: not a CLIP handle");
     SD_REQUIRE(input_ids && hidden_out && workspace && batch > 0, "clip_encode: null argument");
     Plan* pl;
-    int rc = get_plan(u, batch, -1, &pl);
+    int rc = get_plan(u, plan_variant(u, batch), &pl);
     if (rc) return rc;
     return run_plan(u, *pl, "clip_encode", workspace, workspace_bytes, input_ids, batch, hidden_out, 0.f, stream);
 }
@@ -507,7 +507,9 @@ extern "C" int sd_clip_create_projected(const sd_clip_config* cfg, int projectio
 extern "C" long long sd_clip_text_embeds_workspace_bytes(sd_unet* u, int batch) {
     SD_REQUIRE(u && u->kind == 2 && u->text_proj > 0, "clip_text_embeds: not a projected CLIP text handle");
     Plan* pl;
-    if (get_plan(u, batch, -1, &pl, REP_TEXT_POOLED)) return -1;
+    PlanVariant v = plan_variant(u, batch);
+    v.rep = REP_TEXT_POOLED;
+    if (get_plan(u, v, &pl)) return -1;
     return (long long)pl->total_bytes;
 }
 
@@ -516,7 +518,9 @@ extern "C" int sd_clip_text_embeds(sd_unet* u, void* stream, const int* input_id
     SD_REQUIRE(u && u->kind == 2 && u->text_proj > 0, "clip_text_embeds: not a projected CLIP text handle");
     SD_REQUIRE(input_ids && text_embeds && workspace && batch > 0, "clip_text_embeds: null argument");
     Plan* pl;
-    int rc = get_plan(u, batch, -1, &pl, REP_TEXT_POOLED);
+    PlanVariant v = plan_variant(u, batch);
+    v.rep = REP_TEXT_POOLED;
+    int rc = get_plan(u, v, &pl);
     if (rc) return rc;
     return run_plan(u, *pl, "clip_text_embeds", workspace, workspace_bytes, input_ids, batch, text_embeds, 0.f, stream);
 }
@@ -556,7 +560,7 @@ extern "C" long long sd_clip_vision_workspace_bytes(sd_unet* u, int batch, int h
     SD_REQUIRE(u && u->kind == 3, "clip_vision: not a CLIP vision handle");
     if (check_image_size(height, width, "clip_vision")) return -1;
     Plan* pl;
-    if (get_plan(u, batch, -1, &pl, 1, height, width)) return -1;
+    if (get_plan(u, plan_variant(u, batch, -1, height, width), &pl)) return -1;
     return (long long)pl->total_bytes;
 }
 
@@ -566,7 +570,7 @@ extern "C" int sd_clip_vision_encode(sd_unet* u, void* stream, const unsigned ch
     SD_REQUIRE(images && image_embeds && workspace && batch > 0, "clip_vision: null argument");
     if (check_image_size(height, width, "clip_vision")) return -1;
     Plan* pl;
-    int rc = get_plan(u, batch, -1, &pl, 1, height, width);
+    int rc = get_plan(u, plan_variant(u, batch, -1, height, width), &pl);
     if (rc) return rc;
     return run_plan(u, *pl, "clip_vision", workspace, workspace_bytes, images, batch, image_embeds, 0.f, stream);
 }
@@ -614,7 +618,9 @@ extern "C" long long sd_image_reward_workspace_bytes(sd_unet* u, int batch, int 
     SD_REQUIRE(u && u->kind == 6, "image_reward: not an ImageReward handle");
     if (check_image_size(height, width, "image_reward")) return -1;
     Plan* pl;
-    if (get_plan(u, batch, -1, &pl, u->ir.max_text_len, height, width)) return -1;
+    PlanVariant v = plan_variant(u, batch, -1, height, width);
+    v.rep = u->ir.max_text_len;
+    if (get_plan(u, v, &pl)) return -1;
     return (long long)pl->total_bytes;
 }
 
@@ -627,7 +633,9 @@ extern "C" int sd_image_reward_score(sd_unet* u, void* stream, const unsigned ch
                u->ir.max_text_len);
     if (check_image_size(height, width, "image_reward")) return -1;
     Plan* pl;
-    int rc = get_plan(u, batch, -1, &pl, text_len, height, width);
+    PlanVariant v = plan_variant(u, batch, -1, height, width);
+    v.rep = text_len;
+    int rc = get_plan(u, v, &pl);
     if (rc) return rc;
     if (check_workspace(*pl, "image_reward", workspace, workspace_bytes)) return -1;
     {   // a prompt whose mask row is all zero has no key to attend to: refused here, before anything is launched
@@ -737,25 +745,25 @@ extern "C" long long sd_unet_workspace_bytes_hw(sd_unet* u, int unet_batch, int 
     if (u->kind == 7 || u->kind == 8) return taesd_workspace_bytes(u, unet_batch, latent_h, latent_w);
     if (check_latent_size(u, latent_h, latent_w, "workspace_bytes")) return -1;
     Plan* pl;
-    if (get_plan(u, unet_batch, cache_branch_id, &pl, 1, latent_h, latent_w)) return -1;
+    PlanVariant v = plan_variant(u, unet_batch, cache_branch_id, latent_h, latent_w);
+    if (check_options("workspace_bytes", variant_options(u, v)) || get_plan(u, v, &pl)) return -1;
     size_t bytes = pl->total_bytes;
-    const bool pair = unet_batch % 2 == 0 && plan_rep(u, unet_batch / 2, unet_batch) == 2;      // the CFG-pair variant of the plan
-    const bool tg = tgate_variant(u) != TGATE_OFF;       // (T-GATE capture / reuse: no IP-Adapter and no control variants exist)
-    if (u->kind == 0 && u->pag_mask) {       // PAG: the plans of 2 and of 3 copies of a latent batch, no other variant exists
-        SD_REQUIRE(cache_branch_id < 0, "workspace_bytes: PAG with DeepCache is not built");
-        for (int rep = 2; rep <= 3; ++rep)
-            if (unet_batch % rep == 0) {
-                if (get_plan(u, unet_batch, -1, &pl, rep, latent_h, latent_w)) return -1;
-                bytes = std::max(bytes, pl->total_bytes);
-            }
+    auto cover = [&]() {          // the largest of the variants so far
+        if (get_plan(u, v, &pl)) return -1;
+        bytes = std::max(bytes, pl->total_bytes);
+        return 0;
+    };
+    if (v.pag_mask) {       // PAG: the plans of 2 and of 3 copies of a latent batch, no other variant exists
+        for (v.rep = 2; v.rep <= 3; ++v.rep)
+            if (unet_batch % v.rep == 0 && cover()) return -1;
         return (long long)bytes;
     }
-    for (int ip = 0; ip <= (u->kind == 0 && u->cfg.ip_adapter_tokens > 0 && !tg ? 1 : 0); ++ip)         // ... and the IP-Adapter variants
-        for (int rep = 1; rep <= (pair ? 2 : 1); ++rep)
-            for (int cn = 0; cn <= (u->kind == 0 && u->ctrl_enabled && cache_branch_id < 0 && !tg ? 1 : 0); ++cn) {      // ... and, once a ControlNet's residuals were set, the control variants
-                if (get_plan(u, unet_batch, cache_branch_id, &pl, rep, latent_h, latent_w, ip, cn)) return -1;
-                bytes = std::max(bytes, pl->total_bytes);
-            }
+    const bool pair = unet_batch % 2 == 0 && plan_rep(u, unet_batch / 2, unet_batch) == 2;      // the CFG-pair variant of the plan
+    const bool tg = v.tgate != TGATE_OFF;       // (T-GATE capture / reuse: no IP-Adapter and no control variants exist)
+    for (v.ip = 0; v.ip <= (u->kind == 0 && u->cfg.ip_adapter_tokens > 0 && !tg ? 1 : 0); ++v.ip)         // ... and the IP-Adapter variants
+        for (v.rep = 1; v.rep <= (pair ? 2 : 1); ++v.rep)
+            for (v.cn = 0; v.cn <= (u->kind == 0 && u->ctrl_enabled && cache_branch_id < 0 && !tg ? 1 : 0); ++v.cn)      // ... and, once a ControlNet's residuals were set, the control variants
+                if (cover()) return -1;
     return (long long)bytes;
 }
 
@@ -854,7 +862,7 @@ extern "C" int sd_unet_set_context_hw(sd_unet* u, void* stream, const float* ehs
                                          "(sd_unet_set_tgate_hw: mode 0 or 1 first)");
     if (check_latent_size(u, latent_h, latent_w, "set_context")) return -1;
     Plan* plp;
-    int rc = get_plan(u, unet_batch, cache_branch_id, &plp, 1, latent_h, latent_w);
+    int rc = get_plan(u, plan_variant(u, unet_batch, cache_branch_id, latent_h, latent_w), &plp);
     if (rc) return rc;
     Plan& pl = *plp;
     if (check_workspace(pl, "set_context", workspace, workspace_bytes)) return -1;
@@ -955,7 +963,9 @@ extern "C" int sd_unet_set_ip_adapter_hw(sd_unet* u, void* stream, const float* 
     SD_REQUIRE(scale == scale && fabsf(scale) <= 1e4f, "set_ip_adapter: scale %g", scale);
     if (check_latent_size(u, latent_h, latent_w, "set_ip_adapter")) return -1;
     Plan* plp;
-    int rc = get_plan(u, unet_batch, cache_branch_id, &plp, 1, latent_h, latent_w, 1);
+    PlanVariant v = plan_variant(u, unet_batch, cache_branch_id, latent_h, latent_w);
+    v.ip = 1;
+    int rc = get_plan(u, v, &plp);
     if (rc) return rc;
     const Plan& pl = *plp;
     if (check_workspace(pl, "set_ip_adapter", workspace, workspace_bytes)) return -1;
@@ -1094,10 +1104,9 @@ extern "C" int sd_controlnet_forward_hw(sd_unet* u, void* stream, const float* l
     SD_REQUIRE(latent_batch > 0 && unet_batch % latent_batch == 0, "controlnet_forward: unet batch %d not a multiple of latent batch %d",
                unet_batch, latent_batch);
     Plan* pl;
-    const int rep = plan_rep(u, latent_batch, unet_batch);
-    u->last_rep = rep; u->last_ip = 0; u->last_cn = 0;
-    u->last_h = latent_h; u->last_w = latent_w;
-    int rc = get_plan(u, unet_batch, -1, &pl, rep, latent_h, latent_w);
+    u->last = plan_variant(u, unet_batch, -1, latent_h, latent_w);
+    u->last.rep = plan_rep(u, latent_batch, unet_batch);
+    int rc = get_plan(u, u->last, &pl);
     if (rc) return rc;
     return run_plan(u, *pl, "controlnet_forward", workspace, workspace_bytes, latents, latent_batch, (float*)residuals, timestep, stream);
 }
@@ -1108,7 +1117,7 @@ extern "C" int sd_unet_set_control_residuals_hw(sd_unet* u, const void* residual
         u->ctrl_res = nullptr;
         return 0;
     }
-    SD_REQUIRE(!u->fp8, "set_control_residuals: ControlNet residuals on an fp8 UNet handle are not built");
+    if (check_options("set_control_residuals", active_options(u) | opt_bit(OPT_CONTROL))) return -1;
     SD_REQUIRE(((uintptr_t)residuals & 255) == 0, "set_control_residuals: the residual buffer must be 256-byte aligned");
     SD_REQUIRE(scale == scale && fabsf(scale) <= 1e4f, "set_control_residuals: scale %g", scale);
     SD_REQUIRE(unet_batch > 0 && unet_batch <= 4096, "set_control_residuals: bad batch %d", unet_batch);
@@ -1120,21 +1129,17 @@ extern "C" int sd_unet_set_control_residuals_hw(sd_unet* u, const void* residual
 }
 
 // a forward of a handle with ControlNet residuals set must be the one they were laid out for
-static int check_control_set(const sd_unet* u, const char* who, int unet_batch, int latent_h, int latent_w, int cache_mode, int branch) {
+static int check_control_set(const sd_unet* u, const char* who, int unet_batch, int latent_h, int latent_w) {
     SD_REQUIRE(u->ctrl_ub == unet_batch && u->ctrl_h == latent_h && u->ctrl_w == latent_w,
                "%s: the ControlNet residuals were set for batch %d at %dx%d, the forward runs batch %d at %dx%d "
                "(sd_unet_set_control_residuals_hw; residuals = NULL clears them)", who, u->ctrl_ub, u->ctrl_h, u->ctrl_w, unet_batch,
                latent_h, latent_w);
-    SD_REQUIRE(cache_mode == SD_CACHE_OFF && branch < 0, "%s: ControlNet residuals with DeepCache are not built", who);
     return 0;
 }
 
 // a forward of a handle in a T-GATE mode must be the one its cache is laid out for; reuse needs a capture before it
 // (batch 2 b of a capture = the CFG pair [uncond | cond] of b latents, whether the caller passes b latents or all 2 b rows)
-static int check_tgate_forward(const sd_unet* u, const char* who, int latent_batch, int unet_batch, int latent_h, int latent_w,
-                               int cache_mode, int branch, int ip, int cn) {
-    SD_REQUIRE(cache_mode == SD_CACHE_OFF && branch < 0, "%s: T-GATE with DeepCache is not built (the cached features are stored at the CFG batch)", who);
-    SD_REQUIRE(!ip && !cn, "%s: T-GATE with an IP-Adapter image prompt or ControlNet residuals is not built", who);
+static int check_tgate_forward(const sd_unet* u, const char* who, int latent_batch, int unet_batch, int latent_h, int latent_w) {
     SD_REQUIRE(u->tg_h == latent_h && u->tg_w == latent_w,
                "%s: the T-GATE cache was set for %d latents at %dx%d, the forward runs at %dx%d (sd_unet_set_tgate_hw)", who,
                u->tg_b, u->tg_h, u->tg_w, latent_h, latent_w);
@@ -1152,26 +1157,31 @@ static int check_tgate_forward(const sd_unet* u, const char* who, int latent_bat
     return 0;
 }
 
-// a forward of a handle with a PAG mask runs [uncond | cond | perturbed] or [cond | perturbed] over ONE set of latents, alone
-static int check_pag_forward(const sd_unet* u, const char* who, int latent_batch, int unet_batch, int cache_mode, int branch, int ip, int cn) {
-    SD_REQUIRE(unet_batch == 3 * latent_batch || unet_batch == 2 * latent_batch, "%s: with PAG on the UNet batch is 3 or 2 times the latent "
-               "batch, [uncond | cond | perturbed] or [cond | perturbed] (UNet batch %d, %d latents; sd_unet_set_pag(u, 0) = off)", who,
-               unet_batch, latent_batch);
-    SD_REQUIRE(cache_mode == SD_CACHE_OFF && branch < 0, "%s: PAG with DeepCache is not built", who);
-    SD_REQUIRE(!ip && !cn, "%s: PAG with an IP-Adapter image prompt or ControlNet residuals is not built", who);
-    SD_REQUIRE(!u->tg_mode, "%s: PAG with T-GATE is not built", who);
-    SD_REQUIRE(!(u->tome_ratio > 0.0), "%s: PAG with Token Merging is not built", who);
-    return 0;
+// the last forward's variant (its size, replication, image prompt and residuals) at a batch and branch, under the handle's options now
+static PlanVariant last_variant(const sd_unet* u, int unet_batch, int branch) {
+    PlanVariant v = plan_variant(u, unet_batch, branch, u->last.lh > 0 ? u->last.lh : -1, u->last.lw > 0 ? u->last.lw : -1);
+    v.rep = u->last.rep; v.ip = u->last.ip; v.cn = u->last.cn;
+    return v;
 }
 
-// a forward with SAG capture on runs alone: no cache, no image prompt, no residuals, none of the other attention plug-ins
-static int check_sag_forward(const sd_unet* u, const char* who, int cache_mode, int branch, int ip, int cn) {
-    SD_REQUIRE(cache_mode == SD_CACHE_OFF && branch < 0, "%s: SAG with DeepCache is not built", who);
-    SD_REQUIRE(!ip && !cn, "%s: SAG with an IP-Adapter image prompt or ControlNet residuals is not built", who);
-    SD_REQUIRE(!u->tg_mode, "%s: SAG with T-GATE is not built", who);
-    SD_REQUIRE(!(u->tome_ratio > 0.0), "%s: SAG with Token Merging is not built", who);
-    SD_REQUIRE(!u->pag_mask, "%s: SAG with PAG is not built", who);
-    SD_REQUIRE(u->sag_mass, "%s: SAG capture is on and no mass buffer is set (sd_unet_set_sag_buffer)", who);
+// The variant a forward runs -- the handle's options with its image prompt and residuals, where set -- into u->last, refused
+// where two of its options are not built together or what is set on the handle was laid out for another forward
+static int forward_variant(sd_unet* u, const char* who, int latent_batch, int unet_batch, int cache_mode, int branch, int latent_h,
+                           int latent_w) {
+    PlanVariant v = plan_variant(u, unet_batch, branch, latent_h, latent_w);
+    v.rep = plan_rep(u, latent_batch, unet_batch);
+    v.ip = u->ip_keys.empty() ? 0 : 1;
+    v.cn = u->ctrl_res ? 1 : 0;
+    if (check_options(who, variant_options(u, v) | (cache_mode != SD_CACHE_OFF ? opt_bit(OPT_DEEPCACHE) : 0))) return -1;
+    if (v.ip && check_ip_set(u, who, unet_batch, branch, latent_h, latent_w)) return -1;
+    if (v.cn && check_control_set(u, who, unet_batch, latent_h, latent_w)) return -1;
+    if (v.tgate && check_tgate_forward(u, who, latent_batch, unet_batch, latent_h, latent_w)) return -1;
+    // with a PAG mask the forward runs [uncond | cond | perturbed] or [cond | perturbed] over ONE set of latents
+    SD_REQUIRE(!v.pag_mask || unet_batch == 3 * latent_batch || unet_batch == 2 * latent_batch, "%s: with PAG on the UNet batch is 3 or 2 "
+               "times the latent batch, [uncond | cond | perturbed] or [cond | perturbed] (UNet batch %d, %d latents; sd_unet_set_pag(u, 0) = "
+               "off)", who, unet_batch, latent_batch);
+    SD_REQUIRE(!v.sag || u->sag_mass, "%s: SAG capture is on and no mass buffer is set (sd_unet_set_sag_buffer)", who);
+    u->last = v;
     return 0;
 }
 
@@ -1208,17 +1218,8 @@ extern "C" int sd_unet_forward_hw(sd_unet* u, void* stream, const float* latents
     SD_REQUIRE(cache_mode >= 0 && cache_mode <= 2, "forward: cache_mode %d", cache_mode);
     SD_REQUIRE(cache_mode == SD_CACHE_OFF || cache_branch_id >= 0, "forward: DeepCache modes need cache_branch_id >= 0");
     Plan* pl;
-    const int rep = plan_rep(u, latent_batch, unet_batch);
-    const int ip = u->ip_keys.empty() ? 0 : 1;
-    if (ip && check_ip_set(u, "forward", unet_batch, cache_branch_id, latent_h, latent_w)) return -1;
-    const int cn = u->ctrl_res ? 1 : 0;
-    if (cn && check_control_set(u, "forward", unet_batch, latent_h, latent_w, cache_mode, cache_branch_id)) return -1;
-    if (u->tg_mode && check_tgate_forward(u, "forward", latent_batch, unet_batch, latent_h, latent_w, cache_mode, cache_branch_id, ip, cn)) return -1;
-    if (u->pag_mask && check_pag_forward(u, "forward", latent_batch, unet_batch, cache_mode, cache_branch_id, ip, cn)) return -1;
-    if (u->sag_on && check_sag_forward(u, "forward", cache_mode, cache_branch_id, ip, cn)) return -1;
-    u->last_rep = rep; u->last_ip = ip; u->last_cn = cn;
-    u->last_h = latent_h; u->last_w = latent_w;
-    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, latent_h, latent_w, ip, cn);
+    if (forward_variant(u, "forward", latent_batch, unet_batch, cache_mode, cache_branch_id, latent_h, latent_w)) return -1;
+    int rc = get_plan(u, u->last, &pl);
     if (rc) return rc;
     if ((rc = ensure_tome_choice(u, pl->tome_choice_bytes, stream))) return rc;
     rc = run_plan(u, *pl, "forward", workspace, workspace_bytes, latents, latent_batch, eps_out, timestep, stream, cache_mode);
@@ -1229,7 +1230,7 @@ extern "C" int sd_unet_forward_hw(sd_unet* u, void* stream, const float* latents
 // ---- FreeU (freeu.hip; the plan side is the up loop of Builder::build) ----------------------------------------------------
 extern "C" int sd_unet_set_freeu(sd_unet* u, float s1, float s2, float b1, float b2) {
     SD_REQUIRE(u && u->kind == 0, "set_freeu: not a UNet handle");
-    SD_REQUIRE(!u->fp8, "set_freeu: FreeU is refused on fp8 handles (the calibrated activation scales do not describe the scaled tensors)");
+    if (check_options("set_freeu", active_options(u) | opt_bit(OPT_FREEU))) return -1;
     const float f[4] = {s1, s2, b1, b2};
     for (int i = 0; i < 4; ++i)
         SD_REQUIRE(f[i] > 0.f && f[i] <= 3.0e38f, "set_freeu: s1=%g s2=%g b1=%g b2=%g (all four must be finite and > 0)", s1, s2, b1, b2);
@@ -1247,10 +1248,7 @@ extern "C" int sd_unet_disable_freeu(sd_unet* u) {
 // ---- T-GATE (tgate.hip; the plan side is Builder::transformer) ------------------------------------------------------------
 static int check_tgate_handle(const sd_unet* u, const char* who) {
     SD_REQUIRE(u && u->kind == 0, "%s: not a UNet handle", who);
-    SD_REQUIRE(!u->fp8, "%s: T-GATE is refused on fp8 handles (the calibrated activation scales do not describe the gated tensors)", who);
-    SD_REQUIRE(u->cfg.in_channels == 4, "%s: T-GATE is refused on a 9-channel inpainting UNet", who);
-    SD_REQUIRE(u->cfg.ip_adapter_tokens == 0, "%s: T-GATE is refused on a UNet with an IP-Adapter (its image branch is not cached)", who);
-    return 0;
+    return check_options(who, (active_options(u) & (opt_bit(OPT_FP8) | opt_bit(OPT_INPAINT9) | opt_bit(OPT_IP_MODEL))) | opt_bit(OPT_TGATE));
 }
 
 extern "C" long long sd_unet_tgate_bytes_hw(sd_unet* u, int latent_batch, int latent_h, int latent_w) {
@@ -1284,8 +1282,7 @@ extern "C" int sd_unet_set_tgate_hw(sd_unet* u, int mode, void* cache, long long
         return 0;
     }
     SD_REQUIRE(mode == TGATE_CAPTURE || mode == TGATE_REUSE, "set_tgate: mode %d (0 = off, 1 = capture, 2 = reuse)", mode);
-    if (check_tgate_handle(u, "set_tgate")) return -1;
-    SD_REQUIRE(!u->ctrl_res && u->ip_keys.empty(), "set_tgate: T-GATE with ControlNet residuals or an IP-Adapter image prompt set is not built");
+    if (check_options("set_tgate", active_options(u) | opt_bit(OPT_TGATE))) return -1;
     SD_REQUIRE(cache && ((uintptr_t)cache & 255) == 0, "set_tgate: the cache buffer must be a 256-byte aligned device pointer");
     const long long need = sd_unet_tgate_bytes_hw(u, latent_batch, latent_h, latent_w);
     if (need < 0) return -1;
@@ -1302,6 +1299,12 @@ extern "C" int sd_unet_set_tgate_hw(sd_unet* u, int mode, void* cache, long long
     u->tg_mode = mode; u->tg_cache = (char*)cache; u->tg_bytes = bytes;
     u->tg_b = latent_batch; u->tg_h = latent_h; u->tg_w = latent_w;
     return 0;
+}
+
+extern "C" const char* sd_unet_option_name(int i) { return option_name(i); }
+
+extern "C" const char* sd_unet_option_conflict(int a, int b) {
+    return a >= 0 && a < OPT_COUNT && b >= 0 && b < OPT_COUNT ? option_conflict(a, b) : nullptr;
 }
 
 extern "C" int sd_unet_plan_count(const sd_unet* u) {
@@ -1324,12 +1327,7 @@ extern "C" int sd_unet_set_pag(sd_unet* u, long long layer_mask) {
     const int nb = transformer_block_count(u->cfg);
     SD_REQUIRE(nb < 63 && layer_mask > 0 && (layer_mask >> nb) == 0, "set_pag: layer mask 0x%llx (bits 0 .. %d: the UNet has %d transformer "
                "blocks; 0 = off)", (unsigned long long)layer_mask, nb - 1, nb);
-    SD_REQUIRE(!u->fp8, "set_pag: PAG is not built for fp8 handles");
-    SD_REQUIRE(u->cfg.in_channels == 4, "set_pag: PAG is refused on a 9-channel inpainting UNet");
-    SD_REQUIRE(u->cfg.ip_adapter_tokens == 0, "set_pag: PAG is refused on a UNet with an IP-Adapter");
-    SD_REQUIRE(!(u->tome_ratio > 0.0), "set_pag: Token Merging is on (PAG and Token Merging together are not built)");
-    SD_REQUIRE(!u->tg_mode, "set_pag: T-GATE is on (PAG and T-GATE together are not built)");
-    SD_REQUIRE(!u->sag_on, "set_pag: SAG capture is on (PAG and SAG together are not built)");
+    if (check_options("set_pag", active_options(u) | opt_bit(OPT_PAG))) return -1;
     u->pag_mask = layer_mask;
     return 0;
 }
@@ -1341,12 +1339,7 @@ extern "C" int sd_unet_set_sag(sd_unet* u, int on) {
         u->sag_on = false;
         return 0;
     }
-    SD_REQUIRE(!u->fp8, "set_sag: SAG is not built for fp8 handles");
-    SD_REQUIRE(u->cfg.in_channels == 4, "set_sag: SAG is refused on a 9-channel inpainting UNet");
-    SD_REQUIRE(u->cfg.ip_adapter_tokens == 0, "set_sag: SAG is refused on a UNet with an IP-Adapter");
-    SD_REQUIRE(!u->pag_mask, "set_sag: PAG is on (SAG and PAG together are not built)");
-    SD_REQUIRE(!(u->tome_ratio > 0.0), "set_sag: Token Merging is on (SAG and Token Merging together are not built)");
-    SD_REQUIRE(!u->tg_mode, "set_sag: T-GATE is on (SAG and T-GATE together are not built)");
+    if (check_options("set_sag", active_options(u) | opt_bit(OPT_SAG))) return -1;
     u->sag_on = true;
     return 0;
 }
@@ -1368,8 +1361,7 @@ extern "C" int sd_unet_set_hypertile(sd_unet* u, int tile_tokens, int max_depth)
     }
     SD_REQUIRE(tile_tokens >= 8 && tile_tokens <= 256, "set_hypertile: tile side of %d tokens (8 .. 256, or 0 = off)", tile_tokens);
     SD_REQUIRE(max_depth >= 0 && max_depth <= 3, "set_hypertile: max_depth %d (0 .. 3)", max_depth);
-    SD_REQUIRE(!u->fp8, "set_hypertile: HyperTile is not built for fp8 handles");
-    SD_REQUIRE(!(u->tome_ratio > 0.0), "set_hypertile: Token Merging is on (HyperTile and Token Merging together are not built)");
+    if (check_options("set_hypertile", active_options(u) | opt_bit(OPT_HYPERTILE))) return -1;
     u->ht_tokens = tile_tokens; u->ht_max_depth = max_depth;
     return 0;
 }
@@ -1378,7 +1370,9 @@ extern "C" int sd_unet_set_hypertile(sd_unet* u, int tile_tokens, int max_depth)
 static int hypertile_layout(sd_unet* u, const char* who, int latent_h, int latent_w, Plan** pl) {
     SD_REQUIRE(u && u->kind == 0, "%s: not a UNet handle", who);
     if (check_latent_size(u, latent_h, latent_w, who)) return -1;
-    return get_plan(u, 1, -1, pl, 1, latent_h, latent_w, 0, 0, TGATE_OFF);
+    PlanVariant v = plan_variant(u, 1, -1, latent_h, latent_w);
+    v.tgate = TGATE_OFF; v.tg_pair = 1;
+    return get_plan(u, v, pl);
 }
 
 extern "C" int sd_unet_hypertile_block_count_hw(sd_unet* u, int latent_h, int latent_w) {
@@ -1409,8 +1403,7 @@ extern "C" int sd_unet_set_tome(sd_unet* u, double ratio, int max_downsample) {
     }
     SD_REQUIRE(ratio <= 0.75, "set_tome: ratio %g (0 .. 0.75: a 2x2 cell has three src tokens)", ratio);
     SD_REQUIRE(max_downsample == 1 || max_downsample == 2, "set_tome: max_downsample %d (1 or 2)", max_downsample);
-    SD_REQUIRE(!u->fp8, "set_tome: Token Merging is not built for fp8 handles");
-    SD_REQUIRE(u->ht_tokens == 0, "set_tome: HyperTile is on (HyperTile and Token Merging together are not built)");
+    if (check_options("set_tome", active_options(u) | opt_bit(OPT_TOME))) return -1;
     u->tome_ratio = ratio; u->tome_max_downsample = max_downsample;
     return 0;
 }
@@ -1420,7 +1413,7 @@ extern "C" int sd_unet_set_tome(sd_unet* u, double ratio, int max_downsample) {
 static int tome_layout(sd_unet* u, const char* who, int latent_h, int latent_w, Plan** pl) {
     SD_REQUIRE(u && u->kind == 0, "%s: not a UNet handle", who);
     if (check_latent_size(u, latent_h, latent_w, who)) return -1;
-    return get_plan(u, 1, -1, pl, 1, latent_h, latent_w);
+    return get_plan(u, plan_variant(u, 1, -1, latent_h, latent_w), pl);
 }
 
 extern "C" int sd_unet_tome_block_count_hw(sd_unet* u, int latent_h, int latent_w) {
@@ -1458,9 +1451,9 @@ extern "C" int sd_unet_set_tome_choice_hw(sd_unet* u, void* stream, const unsign
 extern "C" int sd_unet_tome_matching_hw(sd_unet* u, void* stream, int block, int unet_batch, int cache_branch_id, void* workspace,
                                         int* kept, int* merged, int* dst_idx, int* tok, int* r, int* batch) {
     SD_REQUIRE(u && u->kind == 0 && workspace, "tome_matching: not a UNet handle, or null workspace");
-    SD_REQUIRE(u->last_h > 0, "tome_matching: no forward has run");
+    SD_REQUIRE(u->last.lh > 0, "tome_matching: no forward has run");
     Plan* pl;
-    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, u->last_rep, u->last_h, u->last_w, u->last_ip, u->last_cn);
+    int rc = get_plan(u, last_variant(u, unet_batch, cache_branch_id), &pl);
     if (rc) return rc;
     SD_REQUIRE(block >= 0 && block < (int)pl->tome.size(), "tome_matching: block %d of %zu", block, pl->tome.size());
     const Plan::TomeBlock& tb = pl->tome[block];
@@ -1503,7 +1496,9 @@ extern "C" int sd_unet_calibrate_fp8(sd_unet* u, void* stream, const float* late
     SD_REQUIRE(margin >= 1.f && margin <= 64.f, "calibrate_fp8: margin %g (1 .. 64: headroom over the observed amax)", margin);
     Plan* plp;
     const int rep = plan_rep(u, latent_batch, unet_batch);
-    int rc = get_plan(u, unet_batch, -1, &plp, rep);
+    PlanVariant v = plan_variant(u, unet_batch);
+    v.rep = rep;
+    int rc = get_plan(u, v, &plp);
     if (rc) return rc;
     if (check_workspace(*plp, "calibrate_fp8", workspace, workspace_bytes)) return -1;
     // calibration runs the plan WITHOUT an image prompt, whose activations lie where the "IP on" plan keeps the folded
@@ -1661,18 +1656,8 @@ static int profiled_run(sd_unet* u, void* stream, const float* latents, int late
     SD_REQUIRE(latents && eps_out && workspace, "forward_profiled: null argument");
     SD_REQUIRE(latent_batch > 0 && unet_batch % latent_batch == 0, "forward_profiled: bad batch");
     Plan* pl;
-    const int rep = plan_rep(u, latent_batch, unet_batch);
-    const int ip = u->ip_keys.empty() ? 0 : 1;
-    if (ip && check_ip_set(u, "forward_profiled", unet_batch, cache_branch_id, u->cfg.sample_size, u->cfg.sample_size)) return -1;
-    const int cn = u->ctrl_res ? 1 : 0;
-    if (cn && check_control_set(u, "forward_profiled", unet_batch, u->cfg.sample_size, u->cfg.sample_size, cache_mode, cache_branch_id)) return -1;
-    if (u->tg_mode && check_tgate_forward(u, "forward_profiled", latent_batch, unet_batch, u->cfg.sample_size, u->cfg.sample_size, cache_mode,
-                                          cache_branch_id, ip, cn)) return -1;
-    if (u->pag_mask && check_pag_forward(u, "forward_profiled", latent_batch, unet_batch, cache_mode, cache_branch_id, ip, cn)) return -1;
-    if (u->sag_on && check_sag_forward(u, "forward_profiled", cache_mode, cache_branch_id, ip, cn)) return -1;
-    u->last_rep = rep; u->last_ip = ip; u->last_cn = cn;
-    u->last_h = u->last_w = u->cfg.sample_size;
-    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, rep, -1, -1, ip, cn);
+    if (forward_variant(u, "forward_profiled", latent_batch, unet_batch, cache_mode, cache_branch_id, u->cfg.sample_size, u->cfg.sample_size)) return -1;
+    int rc = get_plan(u, u->last, &pl);
     if (rc) return rc;
     *plan = pl;
     if ((rc = ensure_tome_choice(u, pl->tome_choice_bytes, stream))) return rc;
@@ -1787,7 +1772,7 @@ extern "C" int sd_unet_debug_tensor(sd_unet* u, void* stream, const char* name, 
         return 0;
     }
     Plan* pl;
-    int rc = get_plan(u, unet_batch, cache_branch_id, &pl, u->last_rep, u->last_h > 0 ? u->last_h : -1, u->last_w > 0 ? u->last_w : -1, u->last_ip, u->last_cn);
+    int rc = get_plan(u, last_variant(u, unet_batch, cache_branch_id), &pl);
     if (rc) return rc;
     auto it = pl->taps.find(name);
     SD_REQUIRE(it != pl->taps.end(), "debug_tensor: unknown tap '%s'", name);

@@ -33,6 +33,7 @@ from typing import Callable, List, Optional, Union
 import torch
 
 from . import dist as sdist
+from . import options
 from .registry import models_registry
 from .schedulers import PNDMConfigStub, pag_step_scale, sag_degrade
 from .unet import CACHE_FULL_AND_STORE, CACHE_OFF, CACHE_SKIP, LATENT_CHANNELS, HipUNet2DConditionModel
@@ -206,6 +207,30 @@ class StableDiffusionModel:
         self.sag_masses = []
         self._tgate_reserved = False    # the UNet's workspaces are sized for the capture plans as well
 
+    # -- options and the pairs of them that are not built (options.py) -------------------
+    IS_VARIANT = False              # the variant pipelines: options.VARIANT is on
+
+    @classmethod
+    def _model_options(cls, unet_config, weight_dtype) -> list:
+        """What a model has on by construction: its pipeline class and its UNet's dtype, input channels and adapter weights."""
+        return ([options.VARIANT] if cls.IS_VARIANT else []) + options.handle_options(unet_config, weight_dtype)
+
+    def _enabled(self, among=options.OPTIONS) -> list:
+        """The options ``enable_*`` / ``apply_tome`` / the DeepCache helper have switched on, of those in ``among``."""
+        state = ((options.DEEPCACHE, self._deepcache is not None), (options.TOME, self._tome is not None),
+                 (options.HYPERTILE, self._hypertile is not None), (options.FREEU, self._freeu is not None),
+                 (options.TGATE, self._tgate_step is not None))
+        return [name for name, on in state if on and name in among]
+
+    def _call_options(self, control=None, ip_adapter_image=None, ip_adapter_image_embeds=None, guidance_rescale=None) -> list:
+        """Everything one call runs with beside the option it checks: the model's own, what is enabled, a ControlNet or an
+        IP-Adapter loaded or passed, PAG when this call runs it, ``guidance_rescale``."""
+        state = ((options.CONTROL, control is not None or getattr(self, "_cn_cfg", None) is not None),
+                 (options.IP_PROMPT, ip_adapter_image is not None or ip_adapter_image_embeds is not None or self._ip_loaded),
+                 (options.PAG, self._pag_call is not None),
+                 (options.RESCALE, guidance_rescale is not None and guidance_rescale > 0.0))
+        return self._model_options(self.unet_config, self.weight_dtype) + self._enabled() + [name for name, on in state if on]
+
     # -- Token Merging (tomesd.apply_patch) ----------------------------------------------------------
     TOME_MAX_RATIO = 0.75
 
@@ -229,8 +254,8 @@ class StableDiffusionModel:
             raise NotImplementedError("merge_mlp=True: merging around the feed-forward is not built")
         if rand_every not in ("step", "call"):
             raise ValueError(f"rand_every={rand_every!r}: 'step' (a fresh dst choice before every UNet forward) or 'call'")
-        if float(ratio) > 0.0 and _lib_dtype_is_fp8(weight_dtype):
-            raise NotImplementedError("Token Merging on an fp8 UNet handle is not built (weight_dtype='fp8')")
+        if float(ratio) > 0.0:
+            options.check(options.TOME, options.handle_options(None, weight_dtype))
         if float(ratio) == 0.0:
             return None
         return dict(ratio=float(ratio), max_downsample=int(max_downsample), use_rand=bool(use_rand), seed=int(seed),
@@ -246,8 +271,8 @@ class StableDiffusionModel:
         (``"call"``); ``use_rand=False`` takes the top-left token of every cell.  ``ratio=0`` is ``remove_tome()``."""
         new = self.check_tome_args(ratio, max_downsample, sx, sy, use_rand, merge_attn, merge_crossattn, merge_mlp, seed,
                                    rand_every, self.weight_dtype)
-        if new is not None and self._hypertile is not None:
-            raise NotImplementedError("Token Merging and HyperTile on together are not built: disable_hypertile() first")
+        if new is not None:
+            options.check(options.TOME, self._enabled({options.HYPERTILE}))
         self._tome = new
         return self
 
@@ -315,8 +340,7 @@ class StableDiffusionModel:
         every pipeline and scheduler, DeepCache, T-GATE, FreeU, LCM-distilled UNets, SD 2.x, IP-Adapter, ControlNet, TAESD,
         every image size and batch sharding; refused by name with Token Merging and on fp8 UNets."""
         new = self.check_hypertile_args(tile_size, max_depth, swap_size, self.weight_dtype)
-        if self._tome is not None:
-            raise NotImplementedError("HyperTile and Token Merging on together are not built: remove_tome() first")
+        options.check(options.HYPERTILE, self._enabled({options.TOME}))
         self._hypertile = new
         return self
 
@@ -325,20 +349,15 @@ class StableDiffusionModel:
         self._hypertile = None
         return self
 
-    def _hypertile_begin(self, after_tome: bool):
-        """Start of a sampling loop: the setting onto the UNet handle -- off before Token Merging's setting goes on, on after it
-        went off (the handle refuses the two together).  A handle that never had the setting on is not touched while it is off."""
-        on = self._hypertile is not None
-        if on != after_tome:
-            return
-        if on:
+    def _hypertile_begin(self):
+        """Start of a sampling loop: the setting onto the UNet handle.  A handle that never had the setting on is not touched
+        while it is off."""
+        if self._hypertile is not None:
             self.unet.set_hypertile(*self._hypertile)
         elif getattr(self.unet, "_hypertile", None) is not None:
             self.unet.set_hypertile(0)
 
     # -- perturbed-attention guidance (diffusers PAGMixin; DESIGN.md 4s) -----------------------------------
-    PAG_VARIANT_RULE = None         # the variant pipelines set a sentence: they refuse PAG by name
-
     @staticmethod
     def check_pag_scales(pag_scale, pag_adaptive_scale):
         """``pag_scale`` / ``pag_adaptive_scale`` of ``enable_pag`` or of a call: finite numbers, the adaptive scale >= 0
@@ -358,13 +377,11 @@ class StableDiffusionModel:
         """Everything ``enable_pag`` can refuse from the model alone, by name, without touching the GPU.  Returns the setting:
         dict(scale, adaptive_scale, layers, mask) -- ``mask`` is None without a ``unet_config`` to resolve the names against."""
         scale, adaptive = cls.check_pag_scales(pag_scale, pag_adaptive_scale)
-        if cls.PAG_VARIANT_RULE is not None:
-            raise NotImplementedError(cls.PAG_VARIANT_RULE)
+        options.check(options.PAG, cls._model_options(unet_config, weight_dtype))
         layers = [pag_applied_layers] if isinstance(pag_applied_layers, str) else list(pag_applied_layers)
         mask = None
         if unet_config is not None:
             mask = HipUNet2DConditionModel.pag_layer_mask(unet_config, layers)
-            HipUNet2DConditionModel.check_pag_handle(unet_config, weight_dtype)
         return dict(scale=scale, adaptive_scale=adaptive, layers=layers, mask=mask)
 
     def enable_pag(self, pag_scale: float = 3.0, pag_adaptive_scale: float = 0.0, pag_applied_layers="mid"):
@@ -399,16 +416,7 @@ class StableDiffusionModel:
         if scale <= 0.0:
             return None
         self.check_pag_args(scale, adaptive, self._pag["layers"], self.unet_config, self.weight_dtype)
-        if self._tome is not None:
-            raise NotImplementedError("PAG with Token Merging is refused: merged tokens have no identity attention (remove_tome() first)")
-        if self._tgate_step is not None:
-            raise NotImplementedError("PAG with T-GATE is refused: behind the gate the UNet runs at the latent batch alone")
-        if self._deepcache is not None:
-            raise NotImplementedError("PAG with DeepCache is refused: the cached features are stored at the CFG batch")
-        if control is not None or getattr(self, "_cn_cfg", None) is not None:
-            raise NotImplementedError("PAG with ControlNet is refused: the residuals are computed for the CFG batch")
-        if ip_adapter_image is not None or ip_adapter_image_embeds is not None or self._ip_loaded:
-            raise NotImplementedError("PAG with an IP-Adapter is refused: the image prompt has no third branch")
+        options.check(options.PAG, self._call_options(control, ip_adapter_image, ip_adapter_image_embeds))
         return scale, adaptive
 
     def _pag_begin(self):
@@ -420,8 +428,6 @@ class StableDiffusionModel:
             self.unet.set_pag(0)
 
     # -- self-attention guidance (diffusers StableDiffusionSAGPipeline) -------------------------
-    SAG_VARIANT_RULE = None         # the variant pipelines set a sentence: they refuse SAG by name
-
     @staticmethod
     def check_sag_scale(sag_scale):
         """``sag_scale`` of ``enable_sag`` or of a call: a finite number (``ValueError`` otherwise).  Returns it as a float."""
@@ -433,12 +439,7 @@ class StableDiffusionModel:
     def check_sag_args(cls, sag_scale=0.75, unet_config=None, weight_dtype="bf16"):
         """Everything ``enable_sag`` can refuse from the model alone, by name, without touching the GPU.  Returns the scale."""
         scale = cls.check_sag_scale(sag_scale)
-        if cls.SAG_VARIANT_RULE is not None:
-            raise NotImplementedError(cls.SAG_VARIANT_RULE)
-        if unet_config is not None:
-            HipUNet2DConditionModel.check_sag_handle(unet_config, weight_dtype)
-        elif _lib_dtype_is_fp8(weight_dtype):
-            raise NotImplementedError("SAG on an fp8 UNet handle is not built (weight_dtype='fp8')")
+        options.check(options.SAG, cls._model_options(unet_config, weight_dtype))
         return scale
 
     def enable_sag(self, sag_scale: float = 0.75):
@@ -471,20 +472,7 @@ class StableDiffusionModel:
         if scale <= 0.0:
             return None
         self.check_sag_args(scale, self.unet_config, self.weight_dtype)
-        if self._pag_call is not None:
-            raise NotImplementedError("SAG with PAG is refused: one extra guidance branch per step is built (disable_pag() first)")
-        if guidance_rescale is not None and guidance_rescale > 0.0:
-            raise NotImplementedError("SAG with guidance_rescale > 0 is refused: upstream's SAG pipeline has no rescale")
-        if self._tome is not None:
-            raise NotImplementedError("SAG with Token Merging is refused: merged tokens have no attention mass (remove_tome() first)")
-        if self._tgate_step is not None:
-            raise NotImplementedError("SAG with T-GATE is refused: behind the gate the step has no pair to degrade from")
-        if self._deepcache is not None:
-            raise NotImplementedError("SAG with DeepCache is refused: a skip step does not run the mid block")
-        if control is not None or getattr(self, "_cn_cfg", None) is not None:
-            raise NotImplementedError("SAG with ControlNet is refused: the residuals are computed for the first forward alone")
-        if ip_adapter_image is not None or ip_adapter_image_embeds is not None or self._ip_loaded:
-            raise NotImplementedError("SAG with an IP-Adapter is refused: the image prompt has no branch on the degraded latents")
+        options.check(options.SAG, self._call_options(control, ip_adapter_image, ip_adapter_image_embeds, guidance_rescale))
         if self._hypertile is not None and self._hypertile[1] >= len(self.unet_config.block_out_channels) - 1:
             raise NotImplementedError(f"SAG with HyperTile max_depth={self._hypertile[1]} is refused: it tiles the mid block, whose "
                                       "whole-grid attention mass SAG reads")
@@ -536,8 +524,6 @@ class StableDiffusionModel:
             self.unet.set_freeu(*self._freeu)
 
     # -- T-GATE (Zhang et al. 2024) --------------------------------------------------------
-    TGATE_VARIANT_RULE = None       # the variant pipelines set a sentence: they refuse T-GATE by name
-
     @staticmethod
     def check_tgate_step(gate_step):
         """``gate_step`` of ``enable_tgate``: an integer >= 1 (``ValueError`` otherwise)."""
@@ -550,10 +536,7 @@ class StableDiffusionModel:
     def check_tgate_args(cls, gate_step, unet_config=None, weight_dtype="bf16"):
         """Everything ``enable_tgate`` can refuse from the model alone, by name, without touching the GPU."""
         gate_step = cls.check_tgate_step(gate_step)
-        if cls.TGATE_VARIANT_RULE is not None:
-            raise NotImplementedError(cls.TGATE_VARIANT_RULE)
-        if unet_config is not None:
-            HipUNet2DConditionModel.check_tgate_support(unet_config, weight_dtype)
+        options.check(options.TGATE, cls._model_options(unet_config, weight_dtype))
         return gate_step
 
     def enable_tgate(self, gate_step: int = 10):
@@ -577,13 +560,7 @@ class StableDiffusionModel:
         if self._tgate_step is None:
             return
         self.check_tgate_args(self._tgate_step, self.unet_config, self.weight_dtype)
-        if self._deepcache is not None:
-            raise NotImplementedError("T-GATE with DeepCache is refused: DeepCache's cached features are stored at the CFG batch "
-                                      "(gating at a multiple of cache_interval is not built)")
-        if control is not None or getattr(self, "_cn_cfg", None) is not None:
-            raise NotImplementedError("T-GATE with ControlNet is refused: the residuals are computed for the CFG batch")
-        if ip_adapter_image is not None or ip_adapter_image_embeds is not None or self._ip_loaded:
-            raise NotImplementedError("T-GATE with an IP-Adapter is refused: the image branch of the cross-attention is not cached")
+        options.check(options.TGATE, self._call_options(control, ip_adapter_image, ip_adapter_image_embeds))
 
     def _tgate_begin(self, latent_batch):
         """Start of a sampling loop: the UNet's workspace covers the capture plans while T-GATE is on.  A model that never
@@ -1099,10 +1076,7 @@ class StableDiffusionModel:
                              f"{self.CONTROL_WINDOW_RULE}")
         if mask_image is not None:
             raise NotImplementedError("control_image with mask_image (a ControlNet with inpainting) is not built")
-        if self._deepcache is not None:
-            raise NotImplementedError("control_image with DeepCache is not built (disable the DeepCache helper)")
-        if _lib_dtype_is_fp8(self.weight_dtype):
-            raise NotImplementedError("control_image with an fp8 UNet handle is not built (weight_dtype='bf16')")
+        options.check(options.CONTROL, self._model_options(self.unet_config, self.weight_dtype) + self._enabled({options.DEEPCACHE}))
         img, pil = control_image, False
         if hasattr(img, "convert"):
             img = [img]
@@ -1287,14 +1261,17 @@ class StableDiffusionModel:
     def _start_loop(self, batch_size, device, generator, latents, ctx, cache_branch_id, control=None):
         """Initial latents at the call's size, DeepCache branch and prompt context of the UNet."""
         latents = self.prepare_latents(batch_size, LATENT_CHANNELS, self._size[0], self._size[1], device, generator, latents)
-        self._hypertile_begin(False)
-        self._tome_begin()              # (before the context: the setting is part of the UNet's plans)
-        self._hypertile_begin(True)     # (likewise)
-        self._freeu_begin()             # (likewise)
-        self._tgate_begin(batch_size)   # (before the context: the workspace that holds it)
-        self.unet.set_deepcache(cache_branch_id)
-        self._pag_begin()               # (before the context: the layer mask is part of the UNet's plans)
-        self._sag_begin(batch_size, ctx)    # (likewise: capture is part of the UNet's plans)
+        # The settings of this call onto the UNet handle, before the context (they are part of the UNet's plans, T-GATE's of the
+        # workspace that holds it): first those the call does not use go off, then those it uses go on -- the handle refuses
+        # pairs (options.py), also between a setting the last call left on it and one this call brings
+        begins = ((self._hypertile, self._hypertile_begin), (self._tome, self._tome_begin), (self._freeu, self._freeu_begin),
+                  (self._tgate_step, lambda: self._tgate_begin(batch_size)),
+                  (None if cache_branch_id == -1 else cache_branch_id, lambda: self.unet.set_deepcache(cache_branch_id)),
+                  (self._pag_call, self._pag_begin), (self._sag_call, lambda: self._sag_begin(batch_size, ctx)))
+        for going_on in (False, True):
+            for setting, begin in begins:
+                if (setting is not None) == going_on:
+                    begin()
         self.unet.set_context(ctx, *self.latent_size)
         self._sag_context(batch_size, ctx)
         self._apply_ip_adapter(ctx.shape[0] == 2 * batch_size and self.do_classifier_free_guidance)
@@ -1383,7 +1360,7 @@ class StableDiffusionModel:
                 self.unet.set_tgate(self.unet.TGATE_OFF)
             if sag is not None:
                 self.unet.set_sag(False)
-        self._control_end()
+            self._control_end()         # (also when a step raised: no residuals stay on the handle for the next call)
         torch.cuda.synchronize(device)
         return latents, x0_preds, time.time() - start_time                                        # :284-285
 
@@ -1682,9 +1659,10 @@ class StableDiffusionModel:
                                       "without it upstream composites nothing in pixel space, and neither does this)")
         # (neither a prompt nor embeds: _begin refuses the call by name)
         n_prompt = None if prompt is None and prompt_embeds is None else _prompt_batch(prompt, prompt_embeds)
-        self._tgate_check_call(control_image, ip_adapter_image, ip_adapter_image_embeds)
+        # (PAG first: the other two checks see whether THIS call runs it, not the last one)
         self._pag_call = self._pag_check_call(pag_scale, pag_adaptive_scale, control_image, ip_adapter_image, ip_adapter_image_embeds)
         self._sag_call = self._sag_check_call(sag_scale, guidance_rescale, control_image, ip_adapter_image, ip_adapter_image_embeds)
+        self._tgate_check_call(control_image, ip_adapter_image, ip_adapter_image_embeds)
         control = self._control_args(control_image, controlnet_conditioning_scale, control_guidance_start,
                                      control_guidance_end, guess_mode, mask_image, n_prompt)
         a = SimpleNamespace(height=height, width=width, num_inference_steps=num_inference_steps, timesteps=timesteps,
@@ -1745,20 +1723,13 @@ def _combined(eps, do_cfg, guidance_scale, sched=None):
 
 class _VariantBase(StableDiffusionModel):
     """The variants run ``_sample`` over their own list of steps, without DeepCache, and refuse the image arguments."""
-    TGATE_VARIANT_RULE = ("T-GATE is refused on the variant pipelines (two schedulers, interleaving, skipped steps): their step "
-                          "lists are not one schedule to place a gate in; StableDiffusionModel runs it")
-
-    PAG_VARIANT_RULE = ("PAG is refused on the variant pipelines (two schedulers, interleaving, skipped steps): their history "
-                        "hand-off combines a CFG pair, not three branches; StableDiffusionModel runs it")
-
-    SAG_VARIANT_RULE = ("SAG is refused on the variant pipelines (two schedulers, interleaving, skipped steps): their history "
-                        "hand-off combines a CFG pair, not the SAG prediction; StableDiffusionModel runs it")
+    IS_VARIANT = True
 
     def _refuse_image(self, kwargs):
         if self._sag is not None or kwargs.get("sag_scale") is not None:
-            raise NotImplementedError(self.SAG_VARIANT_RULE)
+            options.check(options.SAG, [options.VARIANT])
         if self._pag is not None or kwargs.get("pag_scale") is not None or kwargs.get("pag_adaptive_scale") is not None:
-            raise NotImplementedError(self.PAG_VARIANT_RULE)
+            options.check(options.PAG, [options.VARIANT])
         if kwargs.get("control_image") is not None or kwargs.get("guess_mode"):
             raise NotImplementedError(f"control_image= (ControlNet) is not built for {type(self).__name__}; "
                                       "StableDiffusionModel runs it")

@@ -15,7 +15,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import _lib
+from . import _lib, options
 from .handle import ALIGN, HipHandle, Workspace, load_params as _load_params
 from .weights import UNetConfig, param_shapes
 
@@ -117,6 +117,17 @@ class HipUNet2DConditionModel(HipHandle):
             self._sag_ws.key = None
             self._sag_ctx_key = None
 
+    def options_on(self) -> list:
+        """The options on this handle now (``options.HANDLE_OPTIONS``): what every setter checks the one it is asked for against."""
+        state = ((options.DEEPCACHE, self.cache_branch_id != -1), (options.IP_PROMPT, self._ip_on),
+                 (options.CONTROL, self._control is not None), (options.TOME, self._tome is not None),
+                 (options.HYPERTILE, self._hypertile is not None), (options.FREEU, self._freeu is not None),
+                 (options.TGATE, self._tgate is not None), (options.PAG, bool(self._pag)), (options.SAG, self._sag))
+        return options.handle_options(self.config, self.weight_dtype) + [name for name, on in state if on]
+
+    def _check_option(self, asked: str) -> None:
+        options.check(asked, self.options_on(), options.HANDLE_OFF)
+
     def latent_size(self, height: Optional[int] = None, width: Optional[int] = None):
         """(h, w) of the latent: ``sample_size`` where not given."""
         s = self.config.sample_size
@@ -144,6 +155,8 @@ class HipUNet2DConditionModel(HipHandle):
 
     def set_deepcache(self, cache_branch_id: int) -> None:
         """-1 disables the DeepCache plan; >= 0 reserves that branch's cached tensors."""
+        if cache_branch_id != -1:
+            self._check_option(options.DEEPCACHE)
         if cache_branch_id != self.cache_branch_id:
             self.cache_branch_id = cache_branch_id
             self._ws_key = None
@@ -262,10 +275,7 @@ class HipUNet2DConditionModel(HipHandle):
         adds ``scale`` times the residuals to its twelve skip tensors and its mid block's output, in one launch after the mid
         block, until ``clear_control_residuals``.  The buffer is borrowed: the ControlNet may refill it before every step."""
         from .controlnet import residual_layout
-        if self.weight_dtype != "bf16":
-            raise NotImplementedError("ControlNet residuals on an fp8 UNet handle are not built")
-        if self.cache_branch_id != -1:
-            raise NotImplementedError("ControlNet residuals with DeepCache are not built")
+        self._check_option(options.CONTROL)
         h, w = self.latent_size(height, width)
         need = residual_layout(self.config, unet_batch, h, w)[1]
         if not torch.is_tensor(residuals) or residuals.dtype != torch.uint8 or residuals.device != self.device or \
@@ -302,14 +312,8 @@ class HipUNet2DConditionModel(HipHandle):
         whose level is at most ``max_downsample`` times coarser than the latent (``ratio`` 0: off, the handle of before).  A
         change needs a new workspace and a new ``set_context``; both follow from dropping the workspace key here."""
         ratio = float(ratio)
-        if ratio > 0.0 and self.weight_dtype != "bf16":
-            raise NotImplementedError("Token Merging on an fp8 UNet handle is not built")
-        if ratio > 0.0 and self._hypertile is not None:
-            raise NotImplementedError("Token Merging and HyperTile on together are not built: set_hypertile(0) first")
-        if ratio > 0.0 and self._pag:
-            raise NotImplementedError("Token Merging and PAG on together are not built: set_pag(0) first")
-        if ratio > 0.0 and self._sag:
-            raise NotImplementedError("Token Merging and SAG on together are not built: set_sag(False) first")
+        if ratio > 0.0:
+            self._check_option(options.TOME)
         _lib.check(self._lib.sd_unet_set_tome(self._handle, ratio, int(max_downsample) if ratio > 0.0 else 0), "sd_unet_set_tome")
         new = (ratio, int(max_downsample)) if ratio > 0.0 else None
         if new != self._tome:
@@ -379,8 +383,7 @@ class HipUNet2DConditionModel(HipHandle):
             return None
         if isinstance(max_depth, bool) or not isinstance(max_depth, int) or not 0 <= max_depth <= 3:
             raise ValueError(f"max_depth={max_depth!r}: HyperTile takes an integer max_depth of 0 .. 3")
-        if _lib.DTYPES.get(weight_dtype) == _lib.DTYPE_FP8_E4M3:
-            raise NotImplementedError("HyperTile on an fp8 UNet handle is not built (weight_dtype='fp8')")
+        options.check(options.HYPERTILE, options.handle_options(None, weight_dtype))
         return tile_tokens, max_depth
 
     def set_hypertile(self, tile_tokens: int, max_depth: int = 0) -> None:
@@ -389,8 +392,8 @@ class HipUNet2DConditionModel(HipHandle):
         runs in tile order, its self-attention inside each tile (``tile_tokens`` 0: off, the handle of before).  A change needs a new workspace and a new ``set_context``; both follow
         from dropping the workspace key here.  Refused together with Token Merging."""
         new = self.check_hypertile_args(tile_tokens, max_depth, self.weight_dtype)
-        if new is not None and self._tome is not None:
-            raise NotImplementedError("HyperTile and Token Merging on together are not built: set_tome(0.0) first")
+        if new is not None:
+            self._check_option(options.HYPERTILE)
         _lib.check(self._lib.sd_unet_set_hypertile(self._handle, *(new or (0, 0))), "sd_unet_set_hypertile")
         if new != self._hypertile:
             self._hypertile = new
@@ -451,12 +454,7 @@ class HipUNet2DConditionModel(HipHandle):
     @staticmethod
     def check_pag_handle(config, weight_dtype="bf16"):
         """What ``set_pag`` refuses about the handle, by name, without touching the GPU."""
-        if _lib.DTYPES.get(weight_dtype) == _lib.DTYPE_FP8_E4M3:
-            raise NotImplementedError("PAG on an fp8 UNet handle is not built (weight_dtype='fp8')")
-        if config.in_channels != LATENT_CHANNELS:
-            raise NotImplementedError(f"PAG on a {config.in_channels}-channel inpainting UNet is not built")
-        if getattr(config, "ip_adapter_embed_dim", None) is not None:
-            raise NotImplementedError("PAG on a UNet with an IP-Adapter is not built")
+        options.check(options.PAG, options.handle_options(config, weight_dtype))
 
     def set_pag(self, layer_mask: int) -> None:
         """Perturbed-attention guidance: bit ``k`` of ``layer_mask`` = transformer block ``k`` in plan order
@@ -469,17 +467,7 @@ class HipUNet2DConditionModel(HipHandle):
             raise ValueError(f"layer_mask={layer_mask!r}: a PAG layer mask has one bit per transformer block "
                              f"({len(self.pag_block_names(self.config))} here; 0 = off)")
         if layer_mask:
-            self.check_pag_handle(self.config, self.weight_dtype)
-            if self._tome is not None:
-                raise NotImplementedError("PAG and Token Merging on together are not built: set_tome(0.0) first")
-            if self._tgate is not None:
-                raise NotImplementedError("PAG and T-GATE on together are not built: set_tgate(TGATE_OFF) first")
-            if self.cache_branch_id != -1:
-                raise NotImplementedError("PAG with DeepCache is not built: set_deepcache(-1) first")
-            if self._control is not None or self._ip_on:
-                raise NotImplementedError("PAG with ControlNet residuals or an IP-Adapter image prompt is not built")
-            if self._sag:
-                raise NotImplementedError("PAG and SAG on together are not built: set_sag(False) first")
+            self._check_option(options.PAG)
         _lib.check(self._lib.sd_unet_set_pag(self._handle, layer_mask), "sd_unet_set_pag")
         if layer_mask != self._pag:
             self._pag = layer_mask
@@ -490,12 +478,7 @@ class HipUNet2DConditionModel(HipHandle):
     @staticmethod
     def check_sag_handle(config, weight_dtype="bf16"):
         """What ``set_sag`` refuses about the handle, by name, without touching the GPU."""
-        if _lib.DTYPES.get(weight_dtype) == _lib.DTYPE_FP8_E4M3:
-            raise NotImplementedError("SAG on an fp8 UNet handle is not built (weight_dtype='fp8')")
-        if config.in_channels != LATENT_CHANNELS:
-            raise NotImplementedError(f"SAG on a {config.in_channels}-channel inpainting UNet is not built")
-        if getattr(config, "ip_adapter_embed_dim", None) is not None:
-            raise NotImplementedError("SAG on a UNet with an IP-Adapter is not built")
+        options.check(options.SAG, options.handle_options(config, weight_dtype))
 
     @staticmethod
     def sag_mid_grid(config, h: int, w: int):
@@ -515,17 +498,7 @@ class HipUNet2DConditionModel(HipHandle):
         both kinds of plan, so toggling per forward keeps the workspace and its context.  Refused on fp8, 9-channel and IP-Adapter
         handles and together with PAG, Token Merging, T-GATE, DeepCache, ControlNet residuals and an image prompt."""
         if on:
-            self.check_sag_handle(self.config, self.weight_dtype)
-            if self._pag:
-                raise NotImplementedError("SAG and PAG on together are not built: set_pag(0) first")
-            if self._tome is not None:
-                raise NotImplementedError("SAG and Token Merging on together are not built: set_tome(0.0) first")
-            if self._tgate is not None:
-                raise NotImplementedError("SAG and T-GATE on together are not built: set_tgate(TGATE_OFF) first")
-            if self.cache_branch_id != -1:
-                raise NotImplementedError("SAG with DeepCache is not built: set_deepcache(-1) first")
-            if self._control is not None or self._ip_on:
-                raise NotImplementedError("SAG with ControlNet residuals or an IP-Adapter image prompt is not built")
+            self._check_option(options.SAG)
             if mass is not None:
                 if mass.dtype != torch.float32 or not mass.is_contiguous() or mass.device != self.device:
                     raise ValueError("set_sag: mass must be a contiguous fp32 tensor on the UNet's device")
@@ -578,9 +551,7 @@ class HipUNet2DConditionModel(HipHandle):
                 raise ValueError(f"{name}={v!r}: every FreeU factor must be a finite number > 0 (diffusers switches FreeU off "
                                  "silently when a factor is 0; here that is an error: use disable_freeu())")
             out.append(float(v))
-        if _lib.DTYPES.get(weight_dtype) == _lib.DTYPE_FP8_E4M3:
-            raise NotImplementedError("FreeU on an fp8 UNet handle is refused (weight_dtype='fp8'): the calibrated activation "
-                                      "scales do not describe the scaled tensors")
+        options.check(options.FREEU, options.handle_options(None, weight_dtype))
         return tuple(out)
 
     def set_freeu(self, s1: float, s2: float, b1: float, b2: float) -> None:
@@ -607,13 +578,7 @@ class HipUNet2DConditionModel(HipHandle):
     @staticmethod
     def check_tgate_support(config, weight_dtype="bf16"):
         """What T-GATE refuses on the UNet's side, by name, without touching the GPU."""
-        if _lib.DTYPES.get(weight_dtype) == _lib.DTYPE_FP8_E4M3 or weight_dtype == "fp8_e4m3":
-            raise NotImplementedError("T-GATE on an fp8 UNet handle is refused (weight_dtype='fp8'): the calibrated activation "
-                                      "scales do not describe the gated tensors")
-        if config.in_channels == 9:
-            raise NotImplementedError("T-GATE on a 9-channel inpainting UNet is refused (in_channels = 9)")
-        if getattr(config, "ip_adapter_embed_dim", None) is not None:
-            raise NotImplementedError("T-GATE with an IP-Adapter is refused: the image branch of the cross-attention is not cached")
+        options.check(options.TGATE, options.handle_options(config, weight_dtype))
 
     def tgate_blocks(self, latent_batch: int, height: Optional[int] = None, width: Optional[int] = None):
         """The cache slices of ``latent_batch`` latents, one per transformer block in plan order (down, mid, up): dicts of
@@ -677,11 +642,7 @@ class HipUNet2DConditionModel(HipHandle):
             self._tgate = None
             self._grow_workspace_for_control()      # (a workspace sized while capturing: the plain plans must fit it too)
             return
-        self.check_tgate_support(self.config, self.weight_dtype)
-        if self.cache_branch_id != -1:
-            raise NotImplementedError("T-GATE with DeepCache is refused: the cached features are stored at the CFG batch")
-        if self._control is not None or self._ip_on:
-            raise NotImplementedError("T-GATE with ControlNet residuals or an IP-Adapter image prompt set is refused")
+        self._check_option(options.TGATE)
         h, w = self.latent_size(height, width)
         buf = self._reserve_tgate_cache(latent_batch, h, w)
         _lib.check(self._lib.sd_unet_set_tgate_hw(self._handle, int(mode), buf.ptr, buf.nbytes, int(latent_batch), h, w),
